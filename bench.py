@@ -17,8 +17,16 @@ N > 1: one process per GPU (torch.distributed / RCCL), launched by torch.distrib
     (an all-reduce of a block every row of which exactly one rank wrote); value = Q / max-over-ranks wall time.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--max-len L] [--queue Q] [--dtype bf16|fp32]
+                    [--dump-outputs DIR] [--full]
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (the headline figure only).
+--full adds every other leg after the timed region: the T = 32 regime, isolated steps, per-kernel HIP-event durations and
+roofline, BASELINE configs[4], the fp32 parity leg, mixed lengths, the strong-scaling probe and the CPU baseline (the
+--no-* options and --only-mixed select among them).
+--dump-outputs DIR: what the timed region's last step computed - the token ids and lengths a caller of
+mocr_recognize_device receives (strong scaling: the whole exchanged queue) - as DIR/ids.npy and DIR/lengths.npy, float32;
+above 64 MB, a fixed seeded sample of rows and their indices in DIR/rows.npy.  The inputs are seeded: the same arguments
+give the same inputs in every run.
 """
 import argparse
 import dataclasses
@@ -112,6 +120,25 @@ def cpu_baseline(args, weights):
             "regimes": regimes}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, ids, lengths):
+    """ids [R, L], lengths [R] (integers) -> out_dir/ids.npy, out_dir/lengths.npy as float32 (exact: ids < 2^24).  Above
+    DUMP_LIMIT_BYTES, a fixed sample of rows (RandomState(0), sorted) is written, and its row indices as rows.npy."""
+    ids = np.asarray(ids)
+    lengths = np.asarray(lengths).reshape(-1)
+    rows = ids.shape[0]
+    per_row = ids[0].size * 4 + 4 + 8 if rows else 1
+    arrays = {"ids": ids, "lengths": lengths}
+    if rows * per_row > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.RandomState(0).choice(rows, DUMP_LIMIT_BYTES // per_row, replace=False))
+        arrays = {"ids": ids[keep], "lengths": lengths[keep], "rows": keep.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a if name == "rows" else a.astype(np.float32))
+
+
 class _FakeEngine:
     """CPU stand-in for the HIP engine, ONLY for the gloo rehearsal of the N > 1 path (MOCR_BENCH_FAKE_ENGINE=1,
     tests/test_bench_gloo.py): the same submit / synchronize surface, ids[b] = (start, byte-sum of crop b mod 6000, eos).
@@ -165,7 +192,14 @@ def main():
                          "report the strong-scaling bound it implies")
     ap.add_argument("--only-timed", action="store_true",
                     help="warm-up + timed region only (the rocprofv3 passes: every launch in the trace then belongs to the timed shape)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg (T = 32, isolated steps, kernels and roofline, configs[4], parity, mixed "
+                         "lengths, strong-scaling probe, CPU baseline); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the ids and lengths of the timed region's last step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.only_mixed:
+        args.full = True
 
     # ONE JSON line on stdout and nothing else: libraries write banners there (RCCL prints its version block on the
     # first communicator), so stdout is pointed at stderr until the line is ready
@@ -313,7 +347,20 @@ def main():
     value = crops_timed / dt
     steps_timed = max(steps_local, 1) if strong else args.steps
 
-    extras = rank == 0 and not args.only_timed
+    # ---- what the timed region's last step computed, before any later leg reuses the output blocks
+    if args.dump_outputs:
+        if strong:
+            out_ids, out_len = d_all[:, :L], d_all[:, L]
+        elif use_dist:
+            out_ids = d_all.view(world, K, B, L)[:, args.steps - 1].reshape(world * B, L)
+            out_len = torch.zeros((world * B,), dtype=torch.int32, device=dev)
+            dist.all_gather_into_tensor(out_len, d_len[args.steps - 1].contiguous())
+        else:
+            out_ids, out_len = d_ids[args.steps - 1], d_len[args.steps - 1]
+        if rank == 0:
+            dump_outputs(args.dump_outputs, out_ids.cpu().numpy(), out_len.cpu().numpy())
+
+    extras = rank == 0 and args.full and not args.only_timed
     if args.only_mixed:
         args.no_profile = args.no_config4 = args.no_parity_leg = args.no_cpu_baseline = True
         args.rows_per_rank_probe = 0

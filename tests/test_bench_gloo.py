@@ -68,6 +68,54 @@ def test_strong_scaling_queue_is_dealt_in_equal_chunks_at_world_2():
     assert d["gathered_shape"] == [Q, L + 1] and d["gathered_checksum"] == _strong_want(chunks, B)
 
 
+def _fake_rows(rank, b, L):
+    want = np.zeros((b, L), np.float32)
+    want[:, 0], want[:, 1], want[:, 2] = 2, _key(rank, b), 3
+    return want
+
+
+def test_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """--dump-outputs: the ids and lengths of the timed region's last step, float32, for one rank and gathered over two."""
+    B, K, L = 8, 3, 16
+    for world in (1, 2):
+        out = tmp_path / f"w{world}"
+        d = _run(world, ["--steps", str(K), "--warmup", "1", "--batch", str(B), "--max-len", str(L), "--dump-outputs", str(out)])
+        assert d["steps"] == K
+        ids, lens = np.load(out / "ids.npy"), np.load(out / "lengths.npy")
+        assert ids.dtype == np.float32 and lens.dtype == np.float32 and not (out / "rows.npy").exists()
+        np.testing.assert_array_equal(ids, np.concatenate([_fake_rows(r, B, L) for r in range(world)]))
+        np.testing.assert_array_equal(lens, np.full(world * B, 3, np.float32))
+
+
+def test_dump_outputs_of_a_dealt_queue_at_world_2(tmp_path):
+    B, L, Q = 8, 16, 37
+    _run(2, ["--queue", str(Q), "--batch", str(B), "--max-batch", "8", "--lanes", "2", "--max-len", str(L), "--steps", "2",
+             "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    ids, lens = np.load(tmp_path / "ids.npy"), np.load(tmp_path / "lengths.npy")
+    rows = _fake_rows(0, B, L)
+    # every chunk replays the same B crops from its first row on
+    sys.path.insert(0, os.path.join(ROOT, "manga-ocr_amd"))
+    from manga_ocr.multi import deal_sizes
+    want = np.concatenate([rows[np.arange(hi - lo) % B] for lo, hi in deal_sizes(Q, 2, 16)])
+    np.testing.assert_array_equal(ids, want)
+    np.testing.assert_array_equal(lens, np.full(Q, 3, np.float32))
+
+
+def test_dump_outputs_above_the_limit_is_a_fixed_sample_of_rows(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 * (16 * 4 + 4 + 8))
+    ids = np.arange(100 * 16, dtype=np.int32).reshape(100, 16)
+    lens = np.arange(100, dtype=np.int32)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), ids, lens)
+    rows = np.load(tmp_path / "a" / "rows.npy")
+    assert rows.shape == (10,) and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "ids.npy"), ids[rows.astype(int)].astype(np.float32))
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "lengths.npy"), rows.astype(np.float32))
+
+
 def test_strong_scaling_queue_guided_chunks_at_world_2():
     sys.path.insert(0, os.path.join(ROOT, "manga-ocr_amd"))
     from manga_ocr.multi import deal_sizes

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Print value / encoder_only / selected kernel averages of the gpurun_out/ab_*.log files written by tools/ab_bench.sh."""
+"""Print value / encoder_only / selected kernel averages of the $OUT/ab_*.log files written by tools/ab_bench.sh (OUT defaults
+to ab_out, under the repo root)."""
 import glob, json, os, sys
 keys = sys.argv[1:] or ["gemm_enc_qkv", "gemm_enc_oproj", "gemm_enc_fc1", "gemm_enc_fc2", "enc_attn_mfma", "layernorm", "lat_attn_cross", "lat_attn_self"]
-for f in sorted(glob.glob(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "ab_*.log"))):
+out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.environ.get("OUT", "ab_out"))
+for f in sorted(glob.glob(os.path.join(out, "ab_*.log"))):
     try:
         d = json.loads(open(f).read().strip().splitlines()[-1])
     except (ValueError, IndexError):
