@@ -225,6 +225,86 @@ int mocr_op_latent_attention_fp8(mocr_engine* e, const void* d_qt, const void* d
  * d_qt[m][h] = bf16(x[m] . Wq_h^T + bq_h) . wkT_h   for the 12 heads. */
 int mocr_op_qqt(mocr_engine* e, const void* d_x, const void* d_wq, const float* d_bq, const void* d_wkT, void* d_qt, int32_t n);
 
+/* Decode-step operators (kernel unit tests).  Each launches through the helper the decode step itself uses - the kernel
+ * variant it picks included - on the caller's device buffers; T = the engine's dtype, slab inputs are split-K partial sums
+ * [nslab][rows][N] fp32, and max_len / vocab / hidden are the engine's.
+ * Classic decode attention.  self != 0: d_slabs [nslab][n][2304] (q | k | v), d_bias [2304], d_k / d_v the K / V cache
+ * [rows][heads][max_len][64] T; slot s attends to row rowmap[s] (identity when d_rowmap is null): the cached positions
+ * 0 .. step[s] - 1 and its new key / value, which are appended at position step[s].  approx_len picks the kernel variant and
+ * must bound every step[s] + 1.  self == 0: d_slabs [nslab][n][768], d_bias [768], d_k = a cross K/V block [rows][197][NCKV]
+ * (NCKV = 2 x hidden x decoder layers; `layer` selects the K | V column pair), d_v and d_step unused.  d_ctx [n][768] T.
+ * nt: the K/V load policy (0 cached, 1 non-temporal), -1 = the decode step's choice for n rows. */
+int mocr_op_dec_attn(mocr_engine* e, int32_t self, const float* d_slabs, int32_t nslab, const float* d_bias, void* d_k, void* d_v,
+                     int32_t layer, const int32_t* d_step, const int32_t* d_rowmap, void* d_ctx, int32_t n, int32_t approx_len,
+                     int32_t nt);
+/* out = LayerNorm([gelu](sum of the slabs + bias) [+ d_resid]) on rows of 768: d_out_f32 [rows][768] (nullable), d_out_t
+ * [rows][768] T.  d_cache (nullable): the row is also written to row rowmap[s], position step[s] of d_cache [..][max_len][768]:
+ * as T, or (cache_fp8) as the e4m3 bytes of out * inv_sx. */
+int mocr_op_dec_add_ln(mocr_engine* e, const float* d_slabs, int32_t nslab, const float* d_bias, const float* d_resid,
+                       const float* d_gamma, const float* d_beta, int32_t gelu, float* d_out_f32, void* d_out_t, int32_t rows,
+                       void* d_cache, int32_t cache_fp8, float inv_sx, const int32_t* d_step, const int32_t* d_rowmap);
+/* d_out [rows][N] T = gelu(sum of the slabs + d_bias). */
+int mocr_op_dec_bias_gelu(mocr_engine* e, const float* d_slabs, int32_t nslab, const float* d_bias, void* d_out, int32_t rows,
+                          int32_t N);
+/* The token step (argmax, finish rules, next input embedding + LayerNorm from the engine's embedding weights).  Buffers indexed
+ * by decode slot: slabs, cand_*, forced, step, rowmap, x_f32, x_t; by row: ids, finished, len, cache. */
+typedef struct mocr_token_args {
+    int32_t struct_size;        /* sizeof(mocr_token_args) */
+    int32_t first;              /* 1: the start step (start token, rowmap = identity, rows >= n_real born finished) */
+    int32_t n;                  /* decode slots */
+    int32_t nslab;              /* slab path: slabs [nslab][n][vocab] */
+    const float* slabs;
+    const float* vbias;         /* slab path: LM-head bias [vocab]; null = the engine's */
+    const float* cand_val;      /* candidate path (ncand > 0): [n][ncand] per-tile maxima and their columns */
+    const int32_t* cand_idx;
+    int32_t ncand;
+    int32_t forced_T;
+    const int32_t* forced;      /* nullable: [n][forced_T] ids that override the argmax */
+    int32_t* ids;               /* [rows][ids_ld] */
+    int32_t* step;              /* [n] */
+    int32_t* finished;          /* [rows] */
+    int32_t* len;               /* [rows] */
+    int32_t* n_unfinished;      /* [1] */
+    int32_t* rowmap;            /* [n] */
+    int32_t ids_ld;
+    int32_t max_len;            /* generate(max_length) */
+    int32_t n_real;
+    int32_t cache_fp8;          /* cache holds e4m3 bytes of x * inv_sx */
+    float* x_f32;               /* [n][768] */
+    void* x_t;                  /* [n][768] T */
+    void* cache;                /* nullable: [rows][max_len][768], position step + 1 is written */
+    float inv_sx;
+} mocr_token_args;
+int mocr_op_dec_token(mocr_engine* e, const mocr_token_args* a);
+/* The LM head's fused argmax GEMM (tile 64 or 128, not split): d_cand_val / d_cand_idx [M][N / tile] = per row and N-tile
+ * the largest acc + bias and its column (the lowest column on a tie).  dA holds M rounded up to the tile. */
+int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                        int32_t* d_cand_idx, int32_t M, int32_t N, int32_t K, int32_t tile);
+/* bf16 engines: the small-batch projection (rows <= 32; kernels_smallm.h SmallMParams), one of the (pro, epi) pairs the
+ * small-batch decode step launches: (0,0) (1,0) (0,1) (1,2) (1,3). */
+typedef struct mocr_smallm_args {
+    int32_t struct_size;        /* sizeof(mocr_smallm_args) */
+    int32_t pro;                /* 0: A = a_bf16 [rows][K]; 1: A = bf16(LayerNorm(a_f32 [rows][768])) */
+    int32_t epi;                /* 0: fp32 raw; 1: fp32 + bias + residual; 2: bf16 gelu(+ bias); 3: fp32 gelu(+ bias) */
+    int32_t rows;
+    int32_t K;
+    int32_t N;
+    int32_t ldo;
+    const void* a_bf16;
+    const float* a_f32;
+    const float* ln_g;
+    const float* ln_b;
+    float* stats_out;           /* nullable: [rows][2] (mean, rstd) of a_f32 */
+    const void* w;              /* [N][K] bf16 */
+    const float* bias;
+    const float* resid;         /* [rows][N] */
+    const float* resid_stats;   /* nullable: resid are pre-LayerNorm sums with these (mean, rstd) and resid_g / resid_b */
+    const float* resid_g;
+    const float* resid_b;
+    void* out;                  /* [rows][ldo] */
+} mocr_smallm_args;
+int mocr_op_smallm_gemm(mocr_engine* e, const mocr_smallm_args* a);
+
 /* Decode-step HIP graphs this engine holds (test hook: the count must stay bounded whatever row counts callers submit). */
 int mocr_graph_count(mocr_engine* e);
 /* Row compactions this engine has performed (r04): between two chunks of decode steps the unfinished rows of a batch are

@@ -910,30 +910,57 @@ int dec_gemm(mocr_engine* e, const char* name, const void* A, int lda, const voi
     return split;
 }
 
+// The row-wise launches of the decode step are split in two: building the argument block from the engine's buffers, and
+// launching from an argument block.  The decode step does both; the operator test hooks (mocr_op_dec_*) fill the block
+// with their own device buffers and go through the same launch.
+struct DecAddLnArgs {
+    const float* slabs; int nslab; long long slab_stride;
+    const float* bias; const float* resid; const float* g; const float* b;
+    float* out_f32; void* out_t; int rows; bool gelu;
+    void* cache; uint8_t* cache8; float inv8; long long cstride;      // latent cache row (T or e4m3) at rowmap[slot], step[slot]
+    const int* step; const int* rowmap;
+};
+
+template <typename T>
+void launch_dec_add_ln(mocr_engine* e, const DecAddLnArgs& a) {
+    ProfScope ps(e, "dec_add_ln", 0, (double)a.rows * e->D * 4 * (a.nslab + 3));
+    if (a.gelu)
+        hipLaunchKernelGGL((dec_add_ln_kernel<T, 768, true>), dim3(a.rows), dim3(192), 0, e->stream, a.slabs, a.nslab,
+                           a.slab_stride, a.bias, a.resid, a.g, a.b, a.out_f32, reinterpret_cast<T*>(a.out_t), a.rows, e->cfg.ln_eps,
+                           reinterpret_cast<T*>(a.cache), a.cstride, a.step, a.cache8, a.inv8, a.rowmap);
+    else
+        hipLaunchKernelGGL((dec_add_ln_kernel<T, 768, false>), dim3(a.rows), dim3(192), 0, e->stream, a.slabs, a.nslab,
+                           a.slab_stride, a.bias, a.resid, a.g, a.b, a.out_f32, reinterpret_cast<T*>(a.out_t), a.rows, e->cfg.ln_eps,
+                           reinterpret_cast<T*>(a.cache), a.cstride, a.step, a.cache8, a.inv8, a.rowmap);
+    HIPCHECK(hipGetLastError());
+}
+
 template <typename T>
 void dec_add_ln(mocr_engine* e, int nslab, int N, const float* bias, const float* resid, const float* g, const float* b,
                 float* out_f32, void* out_t, int rows, bool gelu, int cache_layer = -1) {
-    ProfScope ps(e, "dec_add_ln", 0, (double)rows * N * 4 * (nslab + 3));
-    T* cache = nullptr;
-    uint8_t* cache8 = nullptr;
-    float inv8 = 0.f;
-    const long long cstride = (long long)e->cfg.max_len * e->D;
+    DecAddLnArgs a{};
+    a.slabs = e->slabs; a.nslab = nslab; a.slab_stride = (long long)e->Bp * N;
+    a.bias = bias; a.resid = resid; a.g = g; a.b = b; a.out_f32 = out_f32; a.out_t = out_t; a.rows = rows; a.gelu = gelu;
+    a.cstride = (long long)e->cfg.max_len * e->D;
+    a.step = e->step; a.rowmap = e->rowmap;
     if (cache_layer >= 0) {
         if (e->fp8attn) {
-            cache8 = e->x8cache + (size_t)cache_layer * e->Bp * cstride;
-            inv8 = 1.0f / e->w.sx_self[cache_layer];
+            a.cache8 = e->x8cache + (size_t)cache_layer * e->Bp * a.cstride;
+            a.inv8 = 1.0f / e->w.sx_self[cache_layer];
         } else {
-            cache = reinterpret_cast<T*>(e->xcache) + (size_t)cache_layer * e->Bp * cstride;
+            a.cache = reinterpret_cast<T*>(e->xcache) + (size_t)cache_layer * e->Bp * a.cstride;
         }
     }
-    if (gelu)
-        hipLaunchKernelGGL((dec_add_ln_kernel<T, 768, true>), dim3(rows), dim3(192), 0, e->stream, e->slabs, nslab,
-                           (long long)e->Bp * N, bias, resid, g, b, out_f32, reinterpret_cast<T*>(out_t), rows, e->cfg.ln_eps,
-                           cache, cstride, (const int*)e->step, cache8, inv8, (const int*)e->rowmap);
-    else
-        hipLaunchKernelGGL((dec_add_ln_kernel<T, 768, false>), dim3(rows), dim3(192), 0, e->stream, e->slabs, nslab,
-                           (long long)e->Bp * N, bias, resid, g, b, out_f32, reinterpret_cast<T*>(out_t), rows, e->cfg.ln_eps,
-                           cache, cstride, (const int*)e->step, cache8, inv8, (const int*)e->rowmap);
+    launch_dec_add_ln<T>(e, a);
+}
+
+// out T = gelu(sum of the FC1 slabs + bias): FC1 when it is split over K
+template <typename T>
+void launch_dec_bias_gelu(mocr_engine* e, const float* slabs, int nslab, long long slab_stride, const float* bias, void* out,
+                          int rows, int N) {
+    ProfScope ps(e, "dec_bias_gelu", 0, (double)rows * N * (4.0 * nslab + sizeof(T)));
+    hipLaunchKernelGGL((dec_bias_gelu_kernel<T>), dim3((unsigned)(((long long)rows * N / 4 + 255) / 256)), dim3(256), 0, e->stream,
+                       slabs, nslab, slab_stride, bias, reinterpret_cast<T*>(out), rows, N);
     HIPCHECK(hipGetLastError());
 }
 
@@ -948,50 +975,50 @@ static DecState make_state(mocr_engine* e, int max_len, const int* forced, int f
     return st;
 }
 
+// The token kernel's buffers; the embedding tables and their LayerNorm are always the engine's weights.
+struct DecTokenArgs {
+    const float* slabs; int nslab; long long slab_stride;
+    const float* vbias;                                   // LM-head bias (slab path)
+    const float* cand_val; const int* cand_idx; int ncand;   // per-tile candidates of the fused LM head (ncand > 0)
+    float* x_f32; void* x_t;
+    void* cache; uint8_t* cache8; float inv8; long long cstride;   // layer-0 latent cache row (T or e4m3), indexed by row
+};
+
 template <typename T, bool FIRST>
-void dec_token(mocr_engine* e, const DecState& st, int nslab, int n, int ncand = 0) {
+void launch_dec_token(mocr_engine* e, const DecState& st, const DecTokenArgs& a, int n) {
     auto& w = e->w;
-    ProfScope ps(e, FIRST ? "dec_token_first" : "dec_token", 0, FIRST ? 0.0 : (double)n * e->V * 4 * nslab);
-    const bool lat = e->use_latent(e->rrows(n));
-    hipLaunchKernelGGL((dec_token_kernel<T, 768, FIRST>), dim3(n), dim3(256), 0, e->stream, e->slabs, nslab,
-                       (long long)e->Bp * e->V, w.bv, e->V, st, w.word, w.type0, w.posd, w.embg, w.embb, e->x_f32,
-                       reinterpret_cast<T*>(e->x_t), e->cfg.ln_eps, (lat && !e->fp8attn) ? reinterpret_cast<T*>(e->xcache) : nullptr,
-                       (long long)e->cfg.max_len * e->D, ncand ? e->cand_val : nullptr, ncand ? e->cand_idx : nullptr, ncand,
-                       (lat && e->fp8attn) ? e->x8cache : nullptr, (lat && e->fp8attn) ? 1.0f / w.sx_self[0] : 0.f);
+    ProfScope ps(e, FIRST ? "dec_token_first" : "dec_token", 0, FIRST ? 0.0 : (double)n * e->V * 4 * a.nslab);
+    hipLaunchKernelGGL((dec_token_kernel<T, 768, FIRST>), dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab,
+                       a.slab_stride, a.vbias, e->V, st, w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32,
+                       reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps, reinterpret_cast<T*>(a.cache), a.cstride,
+                       a.ncand ? a.cand_val : nullptr, a.ncand ? a.cand_idx : nullptr, a.ncand, a.cache8, a.inv8);
     HIPCHECK(hipGetLastError());
 }
 
-template <typename T, bool SELF>
-void dec_attn(mocr_engine* e, int layer, int nslab, int n, const float* bias, int approx_len) {
-    const int D = e->D, H = e->H;
-    DecAttnParams p{};
-    p.slabs = e->slabs; p.nslab = nslab;
-    p.ldq = SELF ? 3 * D : D;
-    p.slab_stride = (long long)e->Bp * p.ldq;
-    p.bias = bias;
-    if (SELF) {
-        const size_t per_layer = (size_t)e->Bc * H * e->cfg.max_len * 64;
-        p.kbase = reinterpret_cast<char*>(e->kcache) + (size_t)layer * per_layer * sizeof(T);
-        p.vbase = reinterpret_cast<char*>(e->vcache) + (size_t)layer * per_layer * sizeof(T);
-        p.kv_batch_stride = (long long)H * e->cfg.max_len * 64;
-        p.kv_head_stride = (long long)e->cfg.max_len * 64;
-        p.kv_row_stride = 64;
-        p.step = e->step;
-    } else {
-        p.kbase = reinterpret_cast<char*>(e->CKV) + (size_t)(layer * 2 * D) * sizeof(T);
-        p.vbase = reinterpret_cast<char*>(e->CKV) + (size_t)(layer * 2 * D + D) * sizeof(T);
-        p.kv_batch_stride = (long long)e->S * e->NCKV;
-        p.kv_head_stride = 64;
-        p.kv_row_stride = e->NCKV;
-        p.cross_len = e->S;
-    }
-    p.ctx = e->ctx_t; p.H = H; p.scale = 0.125f;
-    p.rowmap = e->rowmap;
-    // K/V of a 64-row batch (2 layers x 197 keys x 3,072 B = 77 MB + the self cache) live in the Infinity Cache between
-    // steps; from about 128 rows they no longer do and the non-temporal policy wins (r02, isolated batch: 256 rows
-    // 100.2 -> 91.2 ms, 128 rows 69.1 -> 67.5 ms, 64 rows 49.8 -> 50.8 ms)
+template <typename T, bool FIRST>
+void dec_token(mocr_engine* e, const DecState& st, int nslab, int n, int ncand = 0) {
+    const bool lat = e->use_latent(e->rrows(n));
+    DecTokenArgs a{};
+    a.slabs = e->slabs; a.nslab = nslab; a.slab_stride = (long long)e->Bp * e->V; a.vbias = e->w.bv;
+    a.cand_val = e->cand_val; a.cand_idx = e->cand_idx; a.ncand = ncand;
+    a.x_f32 = e->x_f32; a.x_t = e->x_t;
+    a.cache = (lat && !e->fp8attn) ? e->xcache : nullptr;
+    a.cache8 = (lat && e->fp8attn) ? e->x8cache : nullptr;
+    a.inv8 = (lat && e->fp8attn) ? 1.0f / e->w.sx_self[0] : 0.f;
+    a.cstride = (long long)e->cfg.max_len * e->D;
+    launch_dec_token<T, FIRST>(e, st, a, n);
+}
+
+// non-temporal K/V loads from about 128 rows (see dec_attn_params)
+static bool dec_attn_nt(const mocr_engine* e, int n) {
     static const int nt_rows = env_int("MOCR_ATTN_NT_ROWS", 128);
-    p.nt = e->rrows(n) >= nt_rows;
+    return e->rrows(n) >= nt_rows;
+}
+
+// The launch of the classic decode attention: NG (8-key groups a wave may own) is chosen here, from approx_len.
+template <typename T, bool SELF>
+void launch_dec_attn(mocr_engine* e, const DecAttnParams& p, int n, int approx_len) {
+    const int H = e->H;
     ProfScope ps(e, SELF ? "dec_attn_self" : "dec_attn_cross", 4.0 * n * H * approx_len * 64,
                  2.0 * n * H * approx_len * 64 * sizeof(T));
     if (SELF) {
@@ -1007,6 +1034,54 @@ void dec_attn(mocr_engine* e, int layer, int nslab, int n, const float* bias, in
         hipLaunchKernelGGL((dec_attn_kernel<T, false, 7>), dim3(n * H), dim3(256), 0, e->stream, p);
     }
     HIPCHECK(hipGetLastError());
+}
+
+// The parameter block of one decode attention launch.  slabs: [nslab][slab_rows][ldq] fp32; SELF: kc / vc = the layer's
+// K / V cache [rows][H][max_len][64]; cross: kc = the cross K/V block [rows][S][NCKV] (layer = which column pair).
+template <typename T, bool SELF>
+DecAttnParams dec_attn_block(const mocr_engine* e, const float* slabs, long long slab_rows, int nslab, const float* bias,
+                             const void* kc, const void* vc, int layer, const int* step, const int* rowmap, void* ctx, int n) {
+    const int D = e->D, H = e->H;
+    DecAttnParams p{};
+    p.slabs = slabs; p.nslab = nslab;
+    p.ldq = SELF ? 3 * D : D;
+    p.slab_stride = slab_rows * p.ldq;
+    p.bias = bias;
+    if (SELF) {
+        p.kbase = kc;
+        p.vbase = vc;
+        p.kv_batch_stride = (long long)H * e->cfg.max_len * 64;
+        p.kv_head_stride = (long long)e->cfg.max_len * 64;
+        p.kv_row_stride = 64;
+        p.step = step;
+    } else {
+        p.kbase = reinterpret_cast<const char*>(kc) + (size_t)(layer * 2 * D) * sizeof(T);
+        p.vbase = reinterpret_cast<const char*>(kc) + (size_t)(layer * 2 * D + D) * sizeof(T);
+        p.kv_batch_stride = (long long)e->S * e->NCKV;
+        p.kv_head_stride = 64;
+        p.kv_row_stride = e->NCKV;
+        p.cross_len = e->S;
+    }
+    p.ctx = ctx; p.H = H; p.scale = 0.125f;
+    p.rowmap = rowmap;
+    // K/V of a 64-row batch (2 layers x 197 keys x 3,072 B = 77 MB + the self cache) live in the Infinity Cache between
+    // steps; from about 128 rows they no longer do and the non-temporal policy wins (r02, isolated batch: 256 rows
+    // 100.2 -> 91.2 ms, 128 rows 69.1 -> 67.5 ms, 64 rows 49.8 -> 50.8 ms)
+    p.nt = dec_attn_nt(e, n);
+    return p;
+}
+
+template <typename T, bool SELF>
+DecAttnParams dec_attn_params(mocr_engine* e, int layer, int nslab, int n, const float* bias) {
+    const size_t per_layer = (size_t)e->Bc * e->H * e->cfg.max_len * 64;
+    const void* kc = SELF ? reinterpret_cast<const char*>(e->kcache) + (size_t)layer * per_layer * sizeof(T) : e->CKV;
+    const void* vc = SELF ? reinterpret_cast<const char*>(e->vcache) + (size_t)layer * per_layer * sizeof(T) : nullptr;
+    return dec_attn_block<T, SELF>(e, e->slabs, e->Bp, nslab, bias, kc, vc, layer, e->step, e->rowmap, e->ctx_t, n);
+}
+
+template <typename T, bool SELF>
+void dec_attn(mocr_engine* e, int layer, int nslab, int n, const float* bias, int approx_len) {
+    launch_dec_attn<T, SELF>(e, dec_attn_params<T, SELF>(e, layer, nslab, n, bias), n, approx_len);
 }
 
 // The bf16 latent attention launch (r04).  Default: latent_attnT_kernel<.., 2> - 16-key tiles, the score tile transposed so that
@@ -1259,10 +1334,7 @@ void decode_step(mocr_engine* e, const DecState& st, int n, int t) {
             gemm<T>(e, "gemm_dec_fc1", e->c_t, D, L.w1, L.b1, e->h_t, F, nullptr, n, F, D, EPI_BIAS_GELU, dec_launch_tile(e, n), 1);
         } else {
             ns = dec_gemm<T>(e, "gemm_dec_fc1", e->c_t, D, L.w1, F, D, n);
-            ProfScope ps(e, "dec_bias_gelu", 0, (double)n * F * (4.0 * ns + sizeof(T)));
-            hipLaunchKernelGGL((dec_bias_gelu_kernel<T>), dim3((n * F / 4 + 255) / 256), dim3(256), 0, e->stream, e->slabs, ns,
-                               (long long)e->Bp * F, L.b1, reinterpret_cast<T*>(e->h_t), n, F);
-            HIPCHECK(hipGetLastError());
+            launch_dec_bias_gelu<T>(e, e->slabs, ns, (long long)e->Bp * F, L.b1, e->h_t, n, F);
         }
         ns = dec_gemm<T>(e, "gemm_dec_fc2", e->h_t, F, L.w2, D, F, n);
         dec_add_ln<T>(e, ns, D, L.b2, e->c_f32, L.ln3g, L.ln3b, e->x_f32, e->x_t, n, false,
@@ -2625,7 +2697,8 @@ int mocr_op_gemm(mocr_engine* e, const void* dA, const void* dW, const float* d_
         HIPCHECK(hipSetDevice(e->cfg.device));
         drive(e);
         e->bind(0);
-        if (epilogue == EPI_PATCH) throw ArgError{"EPI_PATCH is not exposed through mocr_op_gemm", MOCR_ERR_ARG};
+        if (epilogue == EPI_PATCH || epilogue == EPI_ARGMAX)
+            throw ArgError{"EPI_PATCH / EPI_ARGMAX are not exposed through mocr_op_gemm (EPI_ARGMAX: mocr_op_gemm_argmax)", MOCR_ERR_ARG};
         const long long slab = (long long)M * N;
         if (e->cfg.dtype == MOCR_BF16)
             gemm<bf16_t>(e, "op_gemm", dA, K, dW, d_bias, d_out, N, d_resid, M, N, K, epilogue, tile, split_k, slab);
@@ -2762,6 +2835,154 @@ int mocr_op_qqt(mocr_engine* e, const void* d_x, const void* d_wq, const float* 
         q.wkT = reinterpret_cast<const bf16_t*>(d_wkT); q.qt = reinterpret_cast<bf16_t*>(d_qt);
         ProfScope ps(e, "op_qqt", 4.0 * n * 768 * 768, 0);
         launch_qqt(e, q, n, n);
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_op_dec_attn(mocr_engine* e, int32_t self, const float* d_slabs, int32_t nslab, const float* d_bias, void* d_k, void* d_v,
+                     int32_t layer, const int32_t* d_step, const int32_t* d_rowmap, void* d_ctx, int32_t n, int32_t approx_len,
+                     int32_t nt) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!e->committed || !d_slabs || !d_bias || !d_k || !d_ctx || n < 1 || nslab < 1 || nt < -1 || nt > 1 || e->D != 768 ||
+            (self && (!d_v || !d_step || approx_len < 1 || approx_len > e->cfg.max_len)) ||
+            (!self && (layer < 0 || layer >= e->cfg.dec_layers)))
+            throw ArgError{"mocr_op_dec_attn: bad argument", MOCR_ERR_ARG};
+        dispatch(e, [&](auto tag) {
+            using T_ = decltype(tag);
+            if (self) {
+                DecAttnParams p = dec_attn_block<T_, true>(e, d_slabs, n, nslab, d_bias, d_k, d_v, 0, d_step, d_rowmap, d_ctx, n);
+                if (nt >= 0) p.nt = nt;
+                launch_dec_attn<T_, true>(e, p, n, approx_len);
+            } else {
+                DecAttnParams p = dec_attn_block<T_, false>(e, d_slabs, n, nslab, d_bias, d_k, nullptr, layer, nullptr, d_rowmap, d_ctx, n);
+                if (nt >= 0) p.nt = nt;
+                launch_dec_attn<T_, false>(e, p, n, e->S);
+            }
+        });
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_op_dec_add_ln(mocr_engine* e, const float* d_slabs, int32_t nslab, const float* d_bias, const float* d_resid,
+                       const float* d_gamma, const float* d_beta, int32_t gelu, float* d_out_f32, void* d_out_t, int32_t rows,
+                       void* d_cache, int32_t cache_fp8, float inv_sx, const int32_t* d_step, const int32_t* d_rowmap) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!e->committed || !d_slabs || !d_bias || !d_gamma || !d_beta || !d_out_t || rows < 1 || nslab < 1 || e->D != 768 ||
+            (d_cache && !d_step))
+            throw ArgError{"mocr_op_dec_add_ln: bad argument", MOCR_ERR_ARG};
+        DecAddLnArgs a{};
+        a.slabs = d_slabs; a.nslab = nslab; a.slab_stride = (long long)rows * e->D;
+        a.bias = d_bias; a.resid = d_resid; a.g = d_gamma; a.b = d_beta; a.out_f32 = d_out_f32; a.out_t = d_out_t; a.rows = rows;
+        a.gelu = gelu != 0;
+        a.cstride = (long long)e->cfg.max_len * e->D;
+        a.step = d_step; a.rowmap = d_rowmap;
+        if (d_cache && cache_fp8) { a.cache8 = reinterpret_cast<uint8_t*>(d_cache); a.inv8 = inv_sx; }
+        else a.cache = d_cache;
+        dispatch(e, [&](auto tag) { launch_dec_add_ln<decltype(tag)>(e, a); });
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_op_dec_bias_gelu(mocr_engine* e, const float* d_slabs, int32_t nslab, const float* d_bias, void* d_out, int32_t rows,
+                          int32_t N) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!d_slabs || !d_bias || !d_out || rows < 1 || nslab < 1 || N < 4 || N % 4)
+            throw ArgError{"mocr_op_dec_bias_gelu: bad argument", MOCR_ERR_ARG};
+        dispatch(e, [&](auto tag) { launch_dec_bias_gelu<decltype(tag)>(e, d_slabs, nslab, (long long)rows * N, d_bias, d_out, rows, N); });
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_op_dec_token(mocr_engine* e, const mocr_token_args* a) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!a || a->struct_size != (int32_t)sizeof(mocr_token_args)) throw ArgError{"mocr_op_dec_token: bad struct_size", MOCR_ERR_ARG};
+        const bool first = a->first != 0;
+        if (!e->committed || a->n < 1 || !a->ids || !a->step || !a->finished || !a->len || !a->n_unfinished || !a->rowmap ||
+            !a->x_f32 || !a->x_t || a->ids_ld < 1 || a->max_len < 2 || a->max_len > e->cfg.max_len || e->D != 768 || e->V != 6144 ||
+            (!first && a->ncand > 0 && (!a->cand_val || !a->cand_idx)) ||
+            (!first && a->ncand <= 0 && (!a->slabs || a->nslab < 1)) || (a->forced && a->forced_T < 1))
+            throw ArgError{"mocr_op_dec_token: bad argument", MOCR_ERR_ARG};
+        DecState st{};
+        st.n_real = a->n_real;
+        st.ids = a->ids; st.step = a->step; st.finished = a->finished; st.len = a->len; st.n_unfinished = a->n_unfinished;
+        st.forced = a->forced; st.forced_T = a->forced_T; st.logits_out = nullptr;
+        st.ids_ld = a->ids_ld; st.max_len = a->max_len;
+        st.start_id = e->cfg.start_id; st.eos_id = e->cfg.eos_id; st.pad_id = e->cfg.pad_id;
+        st.rowmap = a->rowmap;
+        DecTokenArgs t{};
+        t.slabs = a->slabs; t.nslab = first ? 0 : a->nslab; t.slab_stride = (long long)a->n * e->V;
+        t.vbias = a->vbias ? a->vbias : e->w.bv;
+        t.cand_val = a->cand_val; t.cand_idx = a->cand_idx; t.ncand = first ? 0 : std::max(a->ncand, 0);
+        t.x_f32 = a->x_f32; t.x_t = a->x_t;
+        if (a->cache && a->cache_fp8) { t.cache8 = reinterpret_cast<uint8_t*>(a->cache); t.inv8 = a->inv_sx; }
+        else t.cache = a->cache;
+        t.cstride = (long long)e->cfg.max_len * e->D;
+        dispatch(e, [&](auto tag) {
+            using T_ = decltype(tag);
+            if (first) launch_dec_token<T_, true>(e, st, t, a->n);
+            else launch_dec_token<T_, false>(e, st, t, a->n);
+        });
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                        int32_t* d_cand_idx, int32_t M, int32_t N, int32_t K, int32_t tile) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!e->committed || !dA || !dW || !d_bias || !d_cand_val || !d_cand_idx || M < 1 || K < 1 || (tile != 64 && tile != 128))
+            throw ArgError{"mocr_op_gemm_argmax: bad argument", MOCR_ERR_ARG};
+        dispatch(e, [&](auto tag) {
+            gemm<decltype(tag)>(e, "op_gemm_argmax", dA, K, dW, d_bias, d_cand_val, N, nullptr, M, N, K, EPI_ARGMAX, tile, 1, 0,
+                                nullptr, 0, nullptr, 0, d_cand_idx);
+        });
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_op_smallm_gemm(mocr_engine* e, const mocr_smallm_args* a) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!a || a->struct_size != (int32_t)sizeof(mocr_smallm_args)) throw ArgError{"mocr_op_smallm_gemm: bad struct_size", MOCR_ERR_ARG};
+        if (!e->committed || e->cfg.dtype != MOCR_BF16 || !a->w || !a->out || a->rows < 1 || a->N < 1 || a->ldo < a->N ||
+            (a->pro == SM_PRO_PLAIN && !a->a_bf16) || (a->pro == SM_PRO_LN && (!a->a_f32 || !a->ln_g || !a->ln_b)) ||
+            (a->epi != SM_EPI_RAW && !a->bias) || (a->epi == SM_EPI_SUM && !a->resid) ||
+            (a->resid_stats && (!a->resid_g || !a->resid_b)))
+            throw ArgError{"mocr_op_smallm_gemm: bad argument", MOCR_ERR_ARG};
+        SmallMParams p{};
+        p.a_bf16 = reinterpret_cast<const bf16_t*>(a->a_bf16); p.a_f32 = a->a_f32; p.ln_g = a->ln_g; p.ln_b = a->ln_b;
+        p.stats_out = a->stats_out; p.w = reinterpret_cast<const bf16_t*>(a->w); p.bias = a->bias; p.resid = a->resid;
+        p.resid_stats = a->resid_stats; p.resid_g = a->resid_g; p.resid_b = a->resid_b; p.out = a->out; p.ldo = a->ldo;
+        p.rows = a->rows; p.K = a->K; p.N = a->N;
+        const int pair = a->pro * 4 + a->epi;
+        if (pair == SM_PRO_PLAIN * 4 + SM_EPI_RAW) smallm_gemm<SM_PRO_PLAIN, SM_EPI_RAW>(e, "op_smallm", p);
+        else if (pair == SM_PRO_LN * 4 + SM_EPI_RAW) smallm_gemm<SM_PRO_LN, SM_EPI_RAW>(e, "op_smallm", p);
+        else if (pair == SM_PRO_PLAIN * 4 + SM_EPI_SUM) smallm_gemm<SM_PRO_PLAIN, SM_EPI_SUM>(e, "op_smallm", p);
+        else if (pair == SM_PRO_LN * 4 + SM_EPI_GELU_BF16) smallm_gemm<SM_PRO_LN, SM_EPI_GELU_BF16>(e, "op_smallm", p);
+        else if (pair == SM_PRO_LN * 4 + SM_EPI_GELU_F32) smallm_gemm<SM_PRO_LN, SM_EPI_GELU_F32>(e, "op_smallm", p);
+        else throw ArgError{"mocr_op_smallm_gemm: (pro, epi) is not a pair the small-batch decode step launches", MOCR_ERR_UNSUPPORTED};
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }

@@ -43,6 +43,24 @@ class MocrRegion(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("page", "x", "y", "width", "height")]
 
 
+class MocrTokenArgs(C.Structure):
+    """include/mocr.h: mocr_token_args"""
+    _fields_ = [("struct_size", C.c_int32), ("first", C.c_int32), ("n", C.c_int32), ("nslab", C.c_int32),
+                ("slabs", C.c_void_p), ("vbias", C.c_void_p), ("cand_val", C.c_void_p), ("cand_idx", C.c_void_p),
+                ("ncand", C.c_int32), ("forced_T", C.c_int32), ("forced", C.c_void_p), ("ids", C.c_void_p),
+                ("step", C.c_void_p), ("finished", C.c_void_p), ("len", C.c_void_p), ("n_unfinished", C.c_void_p),
+                ("rowmap", C.c_void_p), ("ids_ld", C.c_int32), ("max_len", C.c_int32), ("n_real", C.c_int32),
+                ("cache_fp8", C.c_int32), ("x_f32", C.c_void_p), ("x_t", C.c_void_p), ("cache", C.c_void_p),
+                ("inv_sx", C.c_float)]
+
+
+class MocrSmallmArgs(C.Structure):
+    """include/mocr.h: mocr_smallm_args"""
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "pro", "epi", "rows", "K", "N", "ldo")] + \
+        [(n, C.c_void_p) for n in ("a_bf16", "a_f32", "ln_g", "ln_b", "stats_out", "w", "bias", "resid", "resid_stats",
+                                   "resid_g", "resid_b", "out")]
+
+
 CHANNELS_BGR = -3
 ROTATE_NONE, ROTATE_90_CW, ROTATE_90_CCW = 0, 1, 2
 
@@ -78,6 +96,12 @@ SYMBOLS = {
     "mocr_op_quant_fp8": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float]),
     "mocr_op_latent_attention_fp8": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_float]),
     "mocr_op_qqt": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32]),
+    "mocr_op_dec_attn": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    "mocr_op_dec_add_ln": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_float, _P, _P]),
+    "mocr_op_dec_bias_gelu": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32]),
+    "mocr_op_dec_token": (C.c_int, [_P, C.POINTER(MocrTokenArgs)]),
+    "mocr_op_gemm_argmax": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "mocr_op_smallm_gemm": (C.c_int, [_P, C.POINTER(MocrSmallmArgs)]),
     "mocr_profile_enable": (C.c_int, [_P, C.c_int32]),
     "mocr_profile_reset": (C.c_int, [_P]),
     "mocr_profile_get": (C.c_int, [_P, C.POINTER(MocrKernelStat), C.c_int32, C.POINTER(C.c_int32)]),

@@ -245,6 +245,44 @@ class Engine:
     def op_latent_attention_fp8(self, d_qt, d_x8, d_out, n, length, x_batch_stride_bytes, sx) -> None:
         self._check(self.lib.mocr_op_latent_attention_fp8(self._h, _ptr(d_qt), _ptr(d_x8), _ptr(d_out), n, length, x_batch_stride_bytes, sx))
 
+    def op_dec_attn(self, self_attn: bool, d_slabs, nslab, d_bias, d_k, d_v, d_ctx, n, *, layer=0, d_step=None, d_rowmap=None,
+                    approx_len=0, nt=-1) -> None:
+        """Classic decode attention (include/mocr.h, mocr_op_dec_attn): self (appends the new K/V to the cache) or cross."""
+        self._check(self.lib.mocr_op_dec_attn(self._h, 1 if self_attn else 0, _ptr(d_slabs), nslab, _ptr(d_bias), _ptr(d_k), _ptr(d_v),
+                                              layer, _ptr(d_step), _ptr(d_rowmap), _ptr(d_ctx), n, approx_len, nt))
+
+    def op_dec_add_ln(self, d_slabs, nslab, d_bias, d_resid, d_gamma, d_beta, gelu, d_out_f32, d_out_t, rows, *, d_cache=None,
+                      cache_fp8=False, inv_sx=0.0, d_step=None, d_rowmap=None) -> None:
+        """Slab sum + bias [+ GELU] [+ residual] + LayerNorm, optionally writing the latent cache row."""
+        self._check(self.lib.mocr_op_dec_add_ln(self._h, _ptr(d_slabs), nslab, _ptr(d_bias), _ptr(d_resid), _ptr(d_gamma), _ptr(d_beta),
+                                                1 if gelu else 0, _ptr(d_out_f32), _ptr(d_out_t), rows, _ptr(d_cache),
+                                                1 if cache_fp8 else 0, inv_sx, _ptr(d_step), _ptr(d_rowmap)))
+
+    def op_dec_bias_gelu(self, d_slabs, nslab, d_bias, d_out, rows, N) -> None:
+        self._check(self.lib.mocr_op_dec_bias_gelu(self._h, _ptr(d_slabs), nslab, _ptr(d_bias), _ptr(d_out), rows, N))
+
+    def op_dec_token(self, **kw) -> None:
+        """The token step; keyword arguments are the fields of mocr_token_args (buffers as device tensors or addresses)."""
+        a = _capi.MocrTokenArgs()
+        a.struct_size = C.sizeof(_capi.MocrTokenArgs)
+        for name, value in kw.items():
+            ftype = dict(_capi.MocrTokenArgs._fields_)[name]
+            setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
+        self._check(self.lib.mocr_op_dec_token(self._h, C.byref(a)))
+
+    def op_gemm_argmax(self, dA, dW, d_bias, d_cand_val, d_cand_idx, M, N, K, tile) -> None:
+        self._check(self.lib.mocr_op_gemm_argmax(self._h, _ptr(dA), _ptr(dW), _ptr(d_bias), _ptr(d_cand_val), _ptr(d_cand_idx),
+                                                 M, N, K, tile))
+
+    def op_smallm_gemm(self, **kw) -> None:
+        """The small-batch projection; keyword arguments are the fields of mocr_smallm_args."""
+        a = _capi.MocrSmallmArgs()
+        a.struct_size = C.sizeof(_capi.MocrSmallmArgs)
+        for name, value in kw.items():
+            ftype = dict(_capi.MocrSmallmArgs._fields_)[name]
+            setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
+        self._check(self.lib.mocr_op_smallm_gemm(self._h, C.byref(a)))
+
     # ------------------------------------------------------------------ per-kernel timing
     def op_qqt(self, d_x, d_wq, d_bq, d_wkT, d_qt, n: int) -> None:
         self._check(self.lib.mocr_op_qqt(self._h, _ptr(d_x), _ptr(d_wq), _ptr(d_bq), _ptr(d_wkT), _ptr(d_qt), n))

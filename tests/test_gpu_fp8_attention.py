@@ -7,38 +7,13 @@ import os
 import numpy as np
 import pytest
 
-from gpu_util import bf16_round, crops, engine, oracle, report
+from gpu_util import bf16_round, crops, e4m3_quant, e4m3_table, engine, oracle, report
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 FP8 = 128          # MOCR_FLAG_FP8_ATTENTION
 LATENT_ALWAYS = 64
-
-
-def e4m3_table():
-    """byte -> float for OCP e4m3fn (bias 7, no infinities, 0x7F / 0xFF = NaN)."""
-    t = np.zeros(256, np.float64)
-    for b in range(256):
-        s, e, m = b >> 7, (b >> 3) & 15, b & 7
-        if e == 15 and m == 7:
-            v = np.nan
-        elif e == 0:
-            v = m * 2.0 ** -9
-        else:
-            v = (1 + m / 8.0) * 2.0 ** (e - 7)
-        t[b] = -v if s else v
-    return t
-
-
-def e4m3_quant(x):
-    """float -> nearest e4m3 value (round half to even), as float64; |x| <= 448 assumed."""
-    x = np.asarray(x, np.float64)
-    a = np.abs(x)
-    e = np.floor(np.log2(np.maximum(a, 2.0 ** -20)))
-    e = np.clip(e, -6, 8)
-    q = 2.0 ** (e - 3)
-    return np.sign(x) * np.round(a / q) * q          # numpy rounds half to even
 
 
 def _bf16_dev(a):

@@ -1,5 +1,8 @@
 """-m gpu: every HIP kernel class against a float64 numpy / torch-fp32 statement of the same op,
-called through the C ABI's operator hooks.  Device memory comes from torch (plumbing only)."""
+called through the C ABI's operator hooks.  Device memory comes from torch (plumbing only).
+This file covers the encoder's kernels and the latent attention path; the kernels of the classic and small-batch decode
+step (decode attention, slab sum + LayerNorm / GELU, the token step, the LM head's fused argmax, the small-batch
+projections) are in test_gpu_decode_kernels.py."""
 import os
 
 import numpy as np
