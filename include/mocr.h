@@ -305,6 +305,47 @@ typedef struct mocr_smallm_args {
 } mocr_smallm_args;
 int mocr_op_smallm_gemm(mocr_engine* e, const mocr_smallm_args* a);
 
+/* bf16 engines: the attention block of the latent decode path (flag-free default for batches above 256 rows), launched as
+ * the decode step launches it for one layer: q = x Wq^T + bq and Qt = bf16(q) . wkT per head (one fused launch, or two
+ * launches: gemm_dec_q, then a head-batched GEMM), Et = softmax(Qt X^T) X over the keys (bf16 or, on an fp8 engine, e4m3
+ * keys), ctx = Et_h Wv_h^T + bv_h per head.  Fused or not, the tile shapes and the GEMM ring depth are chosen by regime_rows
+ * as the decode step chooses them by its batch's regime; the attention kernel by the engine's flags.
+ * Rows read and written (N = n rounded up to 128):
+ *   x_in   rows < N are read (whole tiles); rows >= n do not reach outputs of rows < n.
+ *   q      rows < n written on the two-launch path, rows < N read back.
+ *   qt     heads 0..11 of rows < n written; the fused launch writes whole tiles, rows < N.  Heads 12..15 are neither
+ *          written nor read.
+ *   et     heads 0..11 of rows < n written, rows < n rounded up to 64 read.  Heads 12..15 are neither written nor read.
+ *   ctx    rows < n written.
+ *   keys   slot s reads keys + (rowmap ? rowmap[s] : s) * key_stride, rows 0 .. L-1 with L = step[0] + 1 (self) or
+ *          fixed_len (cross).  When L is not a whole key tile, the last tile is fetched in whole 1-KiB pieces that can carry
+ *          part of key row L, the row behind the context (the cache position a previous batch may have written); it is
+ *          multiplied by probability 0, so it must be readable and FINITE (0 x NaN = NaN): bf16 rows without NaN / Inf,
+ *          e4m3 bytes other than 0x7F / 0xFF. */
+typedef struct mocr_latent_args {
+    int32_t struct_size;        /* sizeof(mocr_latent_args) */
+    int32_t self;               /* 1: keys = cache positions 0 .. step[0] (context step[0] + 1); 0: fixed_len keys */
+    int32_t n;                  /* decode slots */
+    int32_t regime_rows;        /* the row count the kernel choices are made by (the batch's regime); 0 = n */
+    int32_t fixed_len;
+    const void* x_in;           /* [N][768] bf16 layer input */
+    const void* wq;             /* [768][768] bf16 */
+    const float* bq;            /* [768] */
+    const void* wkT;            /* [768 in][768 out] bf16: (Wk^T) / 8 */
+    const void* wv;             /* [768][768] bf16 */
+    const float* bv;            /* [768] */
+    const void* keys;           /* bf16 rows of 768, or e4m3 bytes (x = e4m3 * sx) on an fp8 engine */
+    int64_t key_stride;         /* elements (bytes for e4m3) between two slots' first key */
+    const int32_t* step;        /* self: [n], all equal (a batch decodes in lockstep) */
+    const int32_t* rowmap;      /* nullable: slot s reads key slot rowmap[s] */
+    float sx;                   /* fp8 engines: key scale */
+    void* q;                    /* [N][768] bf16 scratch */
+    void* qt;                   /* [N][16][768] bf16 */
+    void* et;                   /* [N][16][768] bf16 */
+    void* ctx;                  /* [n][768] bf16 */
+} mocr_latent_args;
+int mocr_op_latent_block(mocr_engine* e, const mocr_latent_args* a);
+
 /* Decode-step HIP graphs this engine holds (test hook: the count must stay bounded whatever row counts callers submit). */
 int mocr_graph_count(mocr_engine* e);
 /* Row compactions this engine has performed (r04): between two chunks of decode steps the unfinished rows of a batch are

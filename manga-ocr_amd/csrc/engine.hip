@@ -1129,50 +1129,55 @@ void launch_latent8(mocr_engine* e, bool self, const Latent8Params& p) {
     HIPCHECK(hipGetLastError());
 }
 
+// The latent attention block's buffers.  Like the decode helpers above it is built in one step - from the engine's state
+// for one layer (latent_block_args), or from a caller's buffers (mocr_op_latent_block) - and launched from in another
+// (launch_latent_block), so that the test hook runs the variants the decode step picks.
+struct LatentBlockArgs {
+    bool self; int n;
+    int approx_len;                                  // the profiler's context length
+    const void* xin; const void* wq; const float* bq; const void* wkT; const void* wv; const float* bv;
+    const void* keys;                                // bf16 rows, or e4m3 bytes on an fp8 engine
+    long long key_stride;                            // elements (bytes for e4m3) between two slots' first key
+    int fixed_len;                                   // cross: keys per slot; self: step[0] + 1
+    const int* step; const int* rowmap;
+    float sx;                                        // fp8: key = e4m3 * sx
+    void* q; void* qt; void* et; void* ctx;
+};
+
 // Latent attention of n rows: Qt [n,16,768] x keys (self: cached layer-input rows; cross: encoder
 // output) -> Et [n,16,768].  bytes: the X rows streamed once (1,536 B per key).
-void latent_attn(mocr_engine* e, bool self, int layer, int n, int approx_len) {
+void latent_attn(mocr_engine* e, const LatentBlockArgs& a) {
+    const int n = a.n, approx_len = a.approx_len;
     if (e->fp8attn) {
         Latent8Params p{};
-        p.qt = reinterpret_cast<const bf16_t*>(e->qt);
-        p.out = reinterpret_cast<bf16_t*>(e->et);
+        p.qt = reinterpret_cast<const bf16_t*>(a.qt);
+        p.out = reinterpret_cast<bf16_t*>(a.et);
         p.heads = e->H;
         p.rows = n;
-        p.rowmap = e->rowmap;
-        if (self) {
-            p.x8 = e->x8cache + (size_t)layer * e->Bp * e->cfg.max_len * e->D;
-            p.x_batch_stride = (long long)e->cfg.max_len * e->D;
-            p.step = e->step;
-            p.sx = e->w.sx_self[layer];
-        } else {
-            p.x8 = e->enc8;
-            p.x_batch_stride = (long long)e->S * e->D;
-            p.fixed_len = e->S;
-            p.sx = e->w.sx_enc;
-        }
-        ProfScope ps(e, self ? "lat8_attn_self" : "lat8_attn_cross", 4.0 * n * 16 * approx_len * e->D,
+        p.rowmap = a.rowmap;
+        p.x8 = reinterpret_cast<const uint8_t*>(a.keys);
+        p.x_batch_stride = a.key_stride;
+        p.step = a.step;
+        p.fixed_len = a.fixed_len;
+        p.sx = a.sx;
+        ProfScope ps(e, a.self ? "lat8_attn_self" : "lat8_attn_cross", 4.0 * n * 16 * approx_len * e->D,
                      (double)n * approx_len * e->D + 2.0 * n * e->H * e->D * 2);     // e4m3 keys + Qt in + Et out (12 heads, bf16)
-        launch_latent8(e, self, p);
+        launch_latent8(e, a.self, p);
         return;
     }
     LatentParams p{};
-    p.qt = reinterpret_cast<const bf16_t*>(e->qt);
-    p.out = reinterpret_cast<bf16_t*>(e->et);
+    p.qt = reinterpret_cast<const bf16_t*>(a.qt);
+    p.out = reinterpret_cast<bf16_t*>(a.et);
     p.heads = e->H;
     p.rows = n;
-    p.rowmap = e->rowmap;
-    if (self) {
-        p.x = reinterpret_cast<const bf16_t*>(e->xcache) + (size_t)layer * e->Bp * e->cfg.max_len * e->D;
-        p.x_batch_stride = (long long)e->cfg.max_len * e->D;
-        p.step = e->step;
-    } else {
-        p.x = reinterpret_cast<const bf16_t*>(e->ENC);
-        p.x_batch_stride = (long long)e->S * e->D;
-        p.fixed_len = e->S;
-    }
-    ProfScope ps(e, self ? "lat_attn_self" : "lat_attn_cross", 4.0 * n * 16 * approx_len * e->D,
+    p.rowmap = a.rowmap;
+    p.x = reinterpret_cast<const bf16_t*>(a.keys);
+    p.x_batch_stride = a.key_stride;
+    p.step = a.step;
+    p.fixed_len = a.fixed_len;
+    ProfScope ps(e, a.self ? "lat_attn_self" : "lat_attn_cross", 4.0 * n * 16 * approx_len * e->D,
                  (double)n * approx_len * e->D * 2 + 2.0 * n * e->H * e->D * 2);     // keys + Qt in + Et out (12 heads)
-    launch_latent(e, self, p);
+    launch_latent(e, a.self, p);
 }
 
 // The fused query launch (kernels_qqt.h): blocks of 64 rows for batches of up to MOCR_QQT_BM64_ROWS rows (a 16-KiB K-tile, seven
@@ -1186,11 +1191,11 @@ void launch_qqt(mocr_engine* e, const QqtParams& q, int n, int regime_rows) {
 }
 
 // q -> Qt -> latent attention -> ctx: the attention block of the latent path up to (not including)
-// the output projection.  wq/bq: query projection; wkT: (Wk^T)/8; wv/bv: value projection.
-void latent_block(mocr_engine* e, bool self, int layer, int n, int t, const void* xin, const void* wq, const float* bq,
-                  const void* wkT, const void* wv, const float* bv) {
+// the output projection.  wq/bq: query projection; wkT: (Wk^T)/8; wv/bv: value projection.  The choices are made by
+// e->rrows(n), the batch's regime.
+void launch_latent_block(mocr_engine* e, const LatentBlockArgs& a) {
     using T = bf16_t;
-    const int D = e->D;
+    const int D = e->D, n = a.n;
     // fat batches: q and Qt in one launch (kernels_qqt.h), 37 us instead of 16 + 31 at 4096 rows; bit-identical to the
     // two-launch path.  MOCR_DEC_QQT_ROWS = rows from which it is used (0 = never)
     // (r04, tools/r04_qqt_rows_ab.sh, isolated batch, two launches / fused: 512 rows 136.2 / 134.9 ms, 768 rows 165.4 / 163.5, below
@@ -1200,26 +1205,53 @@ void latent_block(mocr_engine* e, bool self, int layer, int n, int t, const void
     static const int qqt_rows = env_int("MOCR_DEC_QQT_ROWS", 257);
     if (qqt_rows > 0 && e->rrows(n) >= qqt_rows && D == 768 && e->H == 12 && !(e->cfg.flags & MOCR_FLAG_NO_FUSED_QQT)) {
         QqtParams q{};
-        q.x = reinterpret_cast<const bf16_t*>(xin); q.wq = reinterpret_cast<const bf16_t*>(wq); q.bq = bq;
-        q.wkT = reinterpret_cast<const bf16_t*>(wkT); q.qt = reinterpret_cast<bf16_t*>(e->qt);
+        q.x = reinterpret_cast<const bf16_t*>(a.xin); q.wq = reinterpret_cast<const bf16_t*>(a.wq); q.bq = a.bq;
+        q.wkT = reinterpret_cast<const bf16_t*>(a.wkT); q.qt = reinterpret_cast<bf16_t*>(a.qt);
         {
             ProfScope ps(e, "dec_qqt", 4.0 * n * D * D, (double)n * D * 2 + 2.0 * D * D * 2 + (double)n * e->H * D * 2);
             static const int neutral_by_rows = env_int("MOCR_NEUTRAL_BY_ROWS", 2);
             launch_qqt(e, q, n, neutral_by_rows ? n : e->rrows(n));
         }
-        latent_attn(e, self, layer, n, self ? t + 1 : e->S);
+        latent_attn(e, a);
         HeadBatch hc2; hc2.heads = e->H; hc2.a_yoff = D; hc2.w_yoff = (long long)64 * D; hc2.o_yoff = 64; hc2.b_yoff = 64; hc2.ldw = D;
-        gemm<T>(e, "gemm_dec_ctx", e->et, 16 * D, wv, bv, e->ctx_t, D, nullptr, n, 64, D, EPI_BIAS, 64, 1, 0, nullptr, 0, &hc2);
+        gemm<T>(e, "gemm_dec_ctx", a.et, 16 * D, a.wv, a.bv, a.ctx, D, nullptr, n, 64, D, EPI_BIAS, 64, 1, 0, nullptr, 0, &hc2);
         return;
     }
     static const int qtile = env_int("MOCR_DEC_QTILE", 64), qttile_env = env_int("MOCR_DEC_QTTILE", 0);
     const int qttile = qttile_env ? qttile_env : (e->rrows(n) >= 1024 ? 128 : 64);      // Qt is output-write bound: fewer, fatter blocks
-    gemm<T>(e, "gemm_dec_q", xin, D, wq, bq, e->q_t, D, nullptr, n, D, D, EPI_BIAS, qtile, 1);
+    gemm<T>(e, "gemm_dec_q", a.xin, D, a.wq, a.bq, a.q, D, nullptr, n, D, D, EPI_BIAS, qtile, 1);
     HeadBatch hq; hq.heads = e->H; hq.a_yoff = 64; hq.w_yoff = 64; hq.o_yoff = D; hq.b_yoff = 0; hq.ldw = D;
-    gemm<T>(e, "gemm_dec_qt", e->q_t, D, wkT, e->w.zero_bias, e->qt, 16 * D, nullptr, n, D, 64, EPI_BIAS, qttile, 1, 0, nullptr, 0, &hq);
-    latent_attn(e, self, layer, n, self ? t + 1 : e->S);
+    gemm<T>(e, "gemm_dec_qt", a.q, D, a.wkT, e->w.zero_bias, a.qt, 16 * D, nullptr, n, D, 64, EPI_BIAS, qttile, 1, 0, nullptr, 0, &hq);
+    latent_attn(e, a);
     HeadBatch hc; hc.heads = e->H; hc.a_yoff = D; hc.w_yoff = (long long)64 * D; hc.o_yoff = 64; hc.b_yoff = 64; hc.ldw = D;
-    gemm<T>(e, "gemm_dec_ctx", e->et, 16 * D, wv, bv, e->ctx_t, D, nullptr, n, 64, D, EPI_BIAS, 64, 1, 0, nullptr, 0, &hc);
+    gemm<T>(e, "gemm_dec_ctx", a.et, 16 * D, a.wv, a.bv, a.ctx, D, nullptr, n, 64, D, EPI_BIAS, 64, 1, 0, nullptr, 0, &hc);
+}
+
+// The decode step's latent block of one layer: keys = the layer's cached input rows (self, context t + 1) or the encoder
+// output (cross), intermediates in the engine's q / Qt / Et buffers, the result in ctx_t.
+LatentBlockArgs latent_block_args(const mocr_engine* e, bool self, int layer, int n, int t, const void* xin, const void* wq,
+                                  const float* bq, const void* wkT, const void* wv, const float* bv) {
+    LatentBlockArgs a{};
+    a.self = self; a.n = n; a.approx_len = self ? t + 1 : e->S;
+    a.xin = xin; a.wq = wq; a.bq = bq; a.wkT = wkT; a.wv = wv; a.bv = bv;
+    const size_t cache_layer = (size_t)layer * e->Bp * e->cfg.max_len * e->D;     // elements (bytes for e4m3)
+    if (e->fp8attn) {
+        a.keys = self ? e->x8cache + cache_layer : e->enc8;
+        a.sx = self ? e->w.sx_self[layer] : e->w.sx_enc;
+    } else {
+        a.keys = self ? reinterpret_cast<const bf16_t*>(e->xcache) + cache_layer : reinterpret_cast<const bf16_t*>(e->ENC);
+    }
+    a.key_stride = self ? (long long)e->cfg.max_len * e->D : (long long)e->S * e->D;
+    a.fixed_len = self ? 0 : e->S;
+    a.step = self ? e->step : nullptr;
+    a.rowmap = e->rowmap;
+    a.q = e->q_t; a.qt = e->qt; a.et = e->et; a.ctx = e->ctx_t;
+    return a;
+}
+
+void latent_block(mocr_engine* e, bool self, int layer, int n, int t, const void* xin, const void* wq, const float* bq,
+                  const void* wkT, const void* wv, const float* bv) {
+    launch_latent_block(e, latent_block_args(e, self, layer, n, t, xin, wq, bq, wkT, wv, bv));
 }
 
 template <int PRO, int EPI>
@@ -2983,6 +3015,34 @@ int mocr_op_smallm_gemm(mocr_engine* e, const mocr_smallm_args* a) {
         else if (pair == SM_PRO_LN * 4 + SM_EPI_GELU_BF16) smallm_gemm<SM_PRO_LN, SM_EPI_GELU_BF16>(e, "op_smallm", p);
         else if (pair == SM_PRO_LN * 4 + SM_EPI_GELU_F32) smallm_gemm<SM_PRO_LN, SM_EPI_GELU_F32>(e, "op_smallm", p);
         else throw ArgError{"mocr_op_smallm_gemm: (pro, epi) is not a pair the small-batch decode step launches", MOCR_ERR_UNSUPPORTED};
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_op_latent_block(mocr_engine* e, const mocr_latent_args* a) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!a || a->struct_size != (int32_t)sizeof(mocr_latent_args)) throw ArgError{"mocr_op_latent_block: bad struct_size", MOCR_ERR_ARG};
+        if (!e->committed || e->cfg.dtype != MOCR_BF16 || e->D != 768 || e->H != 12 || a->n < 1 || a->regime_rows < 0 ||
+            !a->x_in || !a->wq || !a->bq || !a->wkT || !a->wv || !a->bv || !a->keys || !a->q || !a->qt || !a->et || !a->ctx ||
+            a->key_stride < 1 || (a->self && !a->step) || (!a->self && a->fixed_len < 1) || (e->fp8attn && !(a->sx > 0.f)))
+            throw ArgError{"mocr_op_latent_block: bad argument", MOCR_ERR_ARG};
+        LatentBlockArgs b{};
+        b.self = a->self != 0; b.n = a->n; b.approx_len = b.self ? e->cfg.max_len : a->fixed_len;
+        b.xin = a->x_in; b.wq = a->wq; b.bq = a->bq; b.wkT = a->wkT; b.wv = a->wv; b.bv = a->bv;
+        b.keys = a->keys; b.key_stride = a->key_stride; b.fixed_len = b.self ? 0 : a->fixed_len;
+        b.step = b.self ? a->step : nullptr; b.rowmap = a->rowmap; b.sx = e->fp8attn ? a->sx : 0.f;
+        b.q = a->q; b.qt = a->qt; b.et = a->et; b.ctx = a->ctx;
+        // the choices are made by the batch's regime, as in the decode step (which sets it around a batch's steps)
+        struct RegimeScope {
+            mocr_engine* e; int old;
+            RegimeScope(mocr_engine* e_, int r) : e(e_), old(e_->regime) { e->regime = r; }
+            ~RegimeScope() { e->regime = old; }
+        } rs(e, a->regime_rows);
+        launch_latent_block(e, b);
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }

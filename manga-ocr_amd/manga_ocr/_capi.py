@@ -61,6 +61,14 @@ class MocrSmallmArgs(C.Structure):
                                    "resid_g", "resid_b", "out")]
 
 
+class MocrLatentArgs(C.Structure):
+    """include/mocr.h: mocr_latent_args"""
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "self", "n", "regime_rows", "fixed_len")] + \
+        [(n, C.c_void_p) for n in ("x_in", "wq", "bq", "wkT", "wv", "bv", "keys")] + \
+        [("key_stride", C.c_int64), ("step", C.c_void_p), ("rowmap", C.c_void_p), ("sx", C.c_float)] + \
+        [(n, C.c_void_p) for n in ("q", "qt", "et", "ctx")]
+
+
 CHANNELS_BGR = -3
 ROTATE_NONE, ROTATE_90_CW, ROTATE_90_CCW = 0, 1, 2
 
@@ -102,6 +110,7 @@ SYMBOLS = {
     "mocr_op_dec_token": (C.c_int, [_P, C.POINTER(MocrTokenArgs)]),
     "mocr_op_gemm_argmax": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mocr_op_smallm_gemm": (C.c_int, [_P, C.POINTER(MocrSmallmArgs)]),
+    "mocr_op_latent_block": (C.c_int, [_P, C.POINTER(MocrLatentArgs)]),
     "mocr_profile_enable": (C.c_int, [_P, C.c_int32]),
     "mocr_profile_reset": (C.c_int, [_P]),
     "mocr_profile_get": (C.c_int, [_P, C.POINTER(MocrKernelStat), C.c_int32, C.POINTER(C.c_int32)]),

@@ -283,6 +283,16 @@ class Engine:
             setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
         self._check(self.lib.mocr_op_smallm_gemm(self._h, C.byref(a)))
 
+    def op_latent_block(self, /, **kw) -> None:
+        """The latent attention block (q -> Qt -> latent attention -> ctx); keyword arguments are the fields of
+        mocr_latent_args (`self` among them: the engine is positional-only)."""
+        a = _capi.MocrLatentArgs()
+        a.struct_size = C.sizeof(_capi.MocrLatentArgs)
+        for name, value in kw.items():
+            ftype = dict(_capi.MocrLatentArgs._fields_)[name]
+            setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
+        self._check(self.lib.mocr_op_latent_block(self._h, C.byref(a)))
+
     # ------------------------------------------------------------------ per-kernel timing
     def op_qqt(self, d_x, d_wq, d_bq, d_wkT, d_qt, n: int) -> None:
         self._check(self.lib.mocr_op_qqt(self._h, _ptr(d_x), _ptr(d_wq), _ptr(d_bq), _ptr(d_wkT), _ptr(d_qt), n))

@@ -37,14 +37,15 @@ def test_config_struct_matches_header():
     assert fields == [f[0] for f in _capi.MocrConfig._fields_]
 
 
-@pytest.mark.parametrize("cname,pyname", [("mocr_token_args", "MocrTokenArgs"), ("mocr_smallm_args", "MocrSmallmArgs")])
+@pytest.mark.parametrize("cname,pyname", [("mocr_token_args", "MocrTokenArgs"), ("mocr_smallm_args", "MocrSmallmArgs"),
+                                          ("mocr_latent_args", "MocrLatentArgs")])
 def test_operator_arg_structs_match_header(cname, pyname):
     """the decode operator hooks' argument structs: same fields, same order, same C types as the ctypes mirrors"""
     import ctypes as C
     hdr = open(os.path.join(ROOT, "include", "mocr.h")).read()
     body = hdr[hdr.index(f"typedef struct {cname} {{"):hdr.index(f"}} {cname};")]
-    fields = re.findall(r"^\s*(?:const\s+)?(int32_t|float|void)\s*(\*?)\s*(\w+);", body, flags=re.M)
-    ctype = {("int32_t", ""): C.c_int32, ("float", ""): C.c_float}
+    fields = re.findall(r"^\s*(?:const\s+)?(int32_t|int64_t|float|void)\s*(\*?)\s*(\w+);", body, flags=re.M)
+    ctype = {("int32_t", ""): C.c_int32, ("int64_t", ""): C.c_int64, ("float", ""): C.c_float}
     mirror = getattr(_capi, pyname)._fields_
     assert [f[2] for f in fields] == [m[0] for m in mirror]
     for (base, star, name), (_, t) in zip(fields, mirror):
