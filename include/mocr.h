@@ -61,8 +61,8 @@ enum {
     MOCR_FLAG_NO_SMALL_BATCH_PATH = 1 << 8, /* bf16: batches of <= 32 rows through the generic split-K projections + add/LayerNorm
                                            * launches (28 per decode step) instead of the one-launch-per-projection path (19) */
     MOCR_FLAG_LATENT_TILE32 = 1 << 10,    /* bf16 latent attention on r03's kernel shape (32-key tiles, one persistent block per CU, three
-                                           * barriers per tile) instead of 16-key tiles on two blocks per CU with the score tile
-                                           * transposed (two barriers per tile): the A/B partner */
+                                           * barriers per tile) instead of the default, latent_attnT_kernel<., 2>: 16-key tiles on three
+                                           * blocks per CU with the score tile transposed (two barriers per tile): the A/B partner */
     MOCR_FLAG_NO_COMPACTION = 1 << 11,    /* keep every row of a batch in the decode steps until the whole batch has finished (r01-r03
                                            * behaviour) instead of compacting the unfinished rows between chunks of steps */
     MOCR_FLAG_FORCE_LN_FOLD = 1 << 13,    /* bf16: fold the encoder's LayerNorms even where this checkpoint's residual stream failed the
@@ -163,6 +163,24 @@ typedef struct mocr_region {
 int mocr_recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
                            int32_t n_regions, int32_t* out_ids, int32_t* out_len);
 
+/* ---- token scores ---------------------------------------------------------------------------
+ * The scored twin of every recognise entry point: one more output, out_logp float32 [n, max_len] with the row layout of
+ * out_ids - the log-probability of every emitted token, computed on the device inside the LM-head launch of the step that
+ * chose it (the logits still never reach memory):
+ *   out_logp[r][0] = 0                      the start token is given, not predicted
+ *   out_logp[r][t], 1 <= t < out_len[r]     = logits[ids[r][t]] - logsumexp(logits), logits = the step's fp32 LM-head outputs
+ *                                           (acc + bias); softmax in fp32 in both engine dtypes, natural log.  Greedy picks the
+ *                                           maximum, so this is -log(sum_j exp(logit_j - max)) <= 0.  The EOS token is scored,
+ *                                           and so is the last token of a row that ends by reaching max_len.
+ *   out_logp[r][t], t >= out_len[r]         = 0 (the pad tail; a whole row of 0 for a region reduced to a sliver, out_len 0)
+ * exp(mean of a row's scores over 1 .. out_len - 1) is the geometric-mean token probability (`Recognition.confidence` of
+ * the Python binding).  The ids and lengths are bit-identical to the unscored call's; out_logp = NULL IS the unscored call.
+ * Scored and unscored requests may share a batch. */
+int mocr_recognize_images_scored(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                                 float* out_logp);
+int mocr_recognize_regions_scored(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                  int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp);
+
 /* Preprocessing only (test hook): out_gray [n, image_size, image_size] uint8 (host) = the plane the encoder sees
  * in each of its three equal input channels before the 1/255 and (x - 0.5)/0.5 scaling. */
 int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t* out_gray);
@@ -174,6 +192,8 @@ int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t
  * lanes; mocr_synchronize() schedules every submitted batch to completion (greedy steps in
  * chunks, stopping a batch once all of its rows have emitted EOS) and waits for the GPU. */
 int mocr_recognize_device(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len);
+/* mocr_recognize_device plus d_out_logp, a device pointer to [n, max_len] float32 (token scores, see above; nullable). */
+int mocr_recognize_device_scored(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp);
 /* generate(max_length=...) of every batch submitted from now on, whatever the entry point (2 <= max_len <= the
  * engine's max_len; rows are still max_len wide; mocr_recognize_gray_host's own argument overrides it).  The reference always calls generate with 300; a speech bubble is
  * typically ~32 tokens (SURVEY.md §8d reports both regimes). */
@@ -192,6 +212,8 @@ int mocr_decode_logits(mocr_engine* e, const void* d_gray, int32_t n, const int3
 /* Greedy decode limited to max_len_override tokens (<= max_len); host outputs. */
 int mocr_recognize_gray_host(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override,
                              int32_t* out_ids, int32_t* out_len);
+int mocr_recognize_gray_host_scored(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override,
+                                    int32_t* out_ids, int32_t* out_len, float* out_logp);   /* + token scores (nullable) */
 
 /* Single operators on device buffers of the engine's dtype (kernel unit tests). */
 int mocr_op_gemm(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, void* d_out,
@@ -276,10 +298,19 @@ typedef struct mocr_token_args {
     float inv_sx;
 } mocr_token_args;
 int mocr_op_dec_token(mocr_engine* e, const mocr_token_args* a);
+/* The scored token step (token scores): the same launch with d_scores [rows][ids_ld] float32, indexed by row like ids:
+ * d_scores[rowmap[s]][step[s] + 1] = -log(sum_j exp(logit_j - max)) of slot s, 0 when the row is finished.  Candidate path:
+ * d_cand_sum [n][ncand] = the tiles' sums of exp(logit - cand_val) (mocr_op_gemm_argmax_lse); slab path: d_cand_sum unused.
+ * Not with first or forced ids.  d_scores = NULL is mocr_op_dec_token.  Rows without a finite logit score NaN. */
+int mocr_op_dec_token_scored(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores);
 /* The LM head's fused argmax GEMM (tile 64 or 128, not split): d_cand_val / d_cand_idx [M][N / tile] = per row and N-tile
  * the largest acc + bias and its column (the lowest column on a tie).  dA holds M rounded up to the tile. */
 int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
                         int32_t* d_cand_idx, int32_t M, int32_t N, int32_t K, int32_t tile);
+/* The scored LM head (token scores): mocr_op_gemm_argmax plus d_cand_sum [M][N / tile] = per row and N-tile the sum over the
+ * tile's columns of exp(acc + bias - d_cand_val); d_cand_val / d_cand_idx are bit-identical to mocr_op_gemm_argmax's. */
+int mocr_op_gemm_argmax_lse(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                            int32_t* d_cand_idx, float* d_cand_sum, int32_t M, int32_t N, int32_t K, int32_t tile);
 /* bf16 engines: the small-batch projection (rows <= 32; kernels_smallm.h SmallMParams), one of the (pro, epi) pairs the
  * small-batch decode step launches: (0,0) (1,0) (0,1) (1,2) (1,3). */
 typedef struct mocr_smallm_args {

@@ -122,6 +122,8 @@ struct LaneCtx {
     void *kcache = nullptr, *vcache = nullptr;     // [dec_layers][Bp][H][max_len][64]
     float* slabs = nullptr; long long slab_cap = 0; // floats
     float* cand_val = nullptr; int* cand_idx = nullptr;   // [Bp][vocab/64] per-tile argmax candidates of the LM head
+    float* cand_sum = nullptr;                      // [Bp][vocab/64] scored batches: per-tile sum of exp(logit - the tile's max)
+    float* scores = nullptr;                        // [Bp][max_len] scored batches: log-probability of every emitted token, by row like ids
     float *x_f32 = nullptr, *a_f32 = nullptr, *c_f32 = nullptr;
     float* ln_stats = nullptr;                      // small-batch path: (mean, rstd) per row of the three pre-LayerNorm sums, [3][Bp][2]
     void *x_t = nullptr, *a_t = nullptr, *c_t = nullptr, *ctx_t = nullptr, *h_t = nullptr, *z_t = nullptr;
@@ -146,6 +148,7 @@ struct Job {
     int n = 0, max_len = 0;
     int32_t* out_ids = nullptr;     // host (out_host) or device
     int32_t* out_len = nullptr;
+    float* out_logp = nullptr;      // nullable: [n][max_len] token log-probabilities (the *_scored entry points); host or device like out_ids
     bool out_host = false;
 };
 
@@ -156,6 +159,7 @@ struct Lane {
     int n = 0, max_len = 0;         // rows of the merged batch, its generate(max_length)
     int np = 0;                     // slots the decode steps run on: n rounded up (graph_rows), the extra ones are born finished; shrinks when the batch is compacted
     int np0 = 0;                    // np at the start of the batch = its kernel regime
+    bool scored = false;            // a job of this batch asked for token log-probabilities: its steps run the scored LM head / token kernel
     int t = 0, steps = 0, chunk = 0;
     bool finishing = false;         // a flag of this batch has reported a finished row: rows are leaving, chunks get shorter
     bool flag_pending[2] = {false, false};
@@ -204,7 +208,7 @@ struct mocr_engine : LaneCtx {
     size_t esz = 2;
     std::vector<Lane> lanes;
     std::vector<Job> pending;
-    // decode-step HIP graphs, keyed by (lane, rows, max_len, steps per graph)
+    // decode-step HIP graphs, keyed by (lane, rows, (max_len, context bucket, scored), steps per graph)
     std::map<std::tuple<int, int, int, int, int>, hipGraphExec_t> graphs;      // + the regime
     void bind(int i) { static_cast<LaneCtx&>(*this) = lanes[i].ctx; }
     void unbind(int i) { lanes[i].ctx = static_cast<LaneCtx&>(*this); }
@@ -360,6 +364,7 @@ void launch_gemm_epi(mocr_engine* e, const GemmParams& p, int epi, int split, in
         case EPI_PATCH: launch_gemm_t<T, BM, BN, EPI_PATCH>(e, p, split, ybatch); break;
         case EPI_BIAS_F32: launch_gemm_t<T, BM, BN, EPI_BIAS_F32>(e, p, split, ybatch); break;
         case EPI_ARGMAX: launch_gemm_t<T, BM, BN, EPI_ARGMAX>(e, p, split, ybatch); break;
+        case EPI_ARGMAX_LSE: launch_gemm_t<T, BM, BN, EPI_ARGMAX_LSE>(e, p, split, ybatch); break;
         default: throw ArgError{"unknown GEMM epilogue", MOCR_ERR_ARG};
     }
 }
@@ -548,13 +553,13 @@ template <typename T>
 void gemm(mocr_engine* e, const char* name, const void* A, int lda, const void* W, const float* bias, void* out, int ldo,
           const float* resid, int M, int N, int K, int epi, int tile, int split, long long slab_stride = 0,
           const float* pos = nullptr, int patches = 0, const HeadBatch* hb = nullptr, int group_n = 0, int* cand_idx = nullptr,
-          const LnFold* lnf = nullptr) {
+          const LnFold* lnf = nullptr, float* cand_sum = nullptr) {
     const int kt = 128 / (int)sizeof(T);
     if (N % (tile >= 1024 ? 256 : tile >= 256 ? 128 : std::max(tile, 1)) || K % (kt * split) || (split > 1 && epi != EPI_SLAB) ||
         (tile >= 256 && (sizeof(T) != 2 || split != 1)))
         throw ArgError{std::string("gemm shape not tileable: ") + name, MOCR_ERR_ARG};
     GemmParams p{};
-    p.A = A; p.W = W; p.bias = bias; p.out = out; p.resid = resid; p.pos = pos; p.cand_idx = cand_idx;
+    p.A = A; p.W = W; p.bias = bias; p.out = out; p.resid = resid; p.pos = pos; p.cand_idx = cand_idx; p.cand_sum = cand_sum;
     p.M = M; p.N = N; p.lda = lda; p.ldw = K; p.ldo = ldo;
     int ybatch = 1;
     if (hb) {
@@ -964,7 +969,8 @@ void launch_dec_bias_gelu(mocr_engine* e, const float* slabs, int nslab, long lo
     HIPCHECK(hipGetLastError());
 }
 
-static DecState make_state(mocr_engine* e, int max_len, const int* forced, int forced_T, float* logits_out, int n_real) {
+static DecState make_state(mocr_engine* e, int max_len, const int* forced, int forced_T, float* logits_out, int n_real,
+                           bool scored = false) {
     DecState st{};
     st.n_real = n_real;
     st.ids = e->ids; st.step = e->step; st.finished = e->finished; st.len = e->len; st.n_unfinished = e->n_unf;
@@ -972,6 +978,7 @@ static DecState make_state(mocr_engine* e, int max_len, const int* forced, int f
     st.ids_ld = e->cfg.max_len; st.max_len = max_len;
     st.start_id = e->cfg.start_id; st.eos_id = e->cfg.eos_id; st.pad_id = e->cfg.pad_id;
     st.rowmap = e->rowmap;
+    st.scores = scored ? e->scores : nullptr;
     return st;
 }
 
@@ -980,6 +987,7 @@ struct DecTokenArgs {
     const float* slabs; int nslab; long long slab_stride;
     const float* vbias;                                   // LM-head bias (slab path)
     const float* cand_val; const int* cand_idx; int ncand;   // per-tile candidates of the fused LM head (ncand > 0)
+    const float* cand_sum;                                // scored steps (st.scores set) on the candidate path: the tiles' exp sums
     float* x_f32; void* x_t;
     void* cache; uint8_t* cache8; float inv8; long long cstride;   // layer-0 latent cache row (T or e4m3), indexed by row
 };
@@ -987,6 +995,18 @@ struct DecTokenArgs {
 template <typename T, bool FIRST>
 void launch_dec_token(mocr_engine* e, const DecState& st, const DecTokenArgs& a, int n) {
     auto& w = e->w;
+    if constexpr (!FIRST) {
+        if (st.scores) {        // token scores: the start step has nothing to score (start_batch zeroes column 0)
+            ProfScope ps(e, "dec_token_lse", 0, (double)n * e->V * 4 * a.nslab);
+            hipLaunchKernelGGL((dec_token_kernel<T, 768, false, true>), dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab,
+                               a.slab_stride, a.vbias, e->V, st, w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32,
+                               reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps, reinterpret_cast<T*>(a.cache), a.cstride,
+                               a.ncand ? a.cand_val : nullptr, a.ncand ? a.cand_idx : nullptr, a.ncand, a.cache8, a.inv8,
+                               a.ncand ? a.cand_sum : nullptr);
+            HIPCHECK(hipGetLastError());
+            return;
+        }
+    }
     ProfScope ps(e, FIRST ? "dec_token_first" : "dec_token", 0, FIRST ? 0.0 : (double)n * e->V * 4 * a.nslab);
     hipLaunchKernelGGL((dec_token_kernel<T, 768, FIRST>), dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab,
                        a.slab_stride, a.vbias, e->V, st, w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32,
@@ -1000,7 +1020,7 @@ void dec_token(mocr_engine* e, const DecState& st, int nslab, int n, int ncand =
     const bool lat = e->use_latent(e->rrows(n));
     DecTokenArgs a{};
     a.slabs = e->slabs; a.nslab = nslab; a.slab_stride = (long long)e->Bp * e->V; a.vbias = e->w.bv;
-    a.cand_val = e->cand_val; a.cand_idx = e->cand_idx; a.ncand = ncand;
+    a.cand_val = e->cand_val; a.cand_idx = e->cand_idx; a.ncand = ncand; a.cand_sum = e->cand_sum;
     a.x_f32 = e->x_f32; a.x_t = e->x_t;
     a.cache = (lat && !e->fp8attn) ? e->xcache : nullptr;
     a.cache8 = (lat && e->fp8attn) ? e->x8cache : nullptr;
@@ -1381,6 +1401,11 @@ void decode_step(mocr_engine* e, const DecState& st, int n, int t) {
     const int vt = dec_launch_tile(e, n);
     if (!st.logits_out && !(e->cfg.flags & MOCR_FLAG_NO_FUSED_ARGMAX) && (vt == 64 || vt == 128) &&
         pick_split(e->V, D, 128 / (int)sizeof(T), rn, e->slab_cap / e->Bp) == 1) {
+        // (a scored batch - st.scores - also keeps every tile's sum of exp(logit - tile max): EPI_ARGMAX_LSE, same max / column)
+        if (st.scores)
+            gemm<T>(e, "gemm_dec_vocab_lse", e->z_t, D, w.wv, w.bv, e->cand_val, e->V, nullptr, n, e->V, D, EPI_ARGMAX_LSE, vt, 1, 0,
+                    nullptr, 0, nullptr, 0, e->cand_idx, nullptr, e->cand_sum);
+        else
         gemm<T>(e, "gemm_dec_vocab", e->z_t, D, w.wv, w.bv, e->cand_val, e->V, nullptr, n, e->V, D, EPI_ARGMAX, vt, 1, 0, nullptr, 0,
                 nullptr, 0, e->cand_idx);
         dec_token<T, false>(e, st, 1, n, e->V / vt);
@@ -1420,6 +1445,7 @@ template <typename T> void init_kernel_attrs() {
     set_max_lds(gemm_kernel<T, 128, 128, EPI_PATCH>, l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS_F32>, l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX>, l128);
+    set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_LSE>, l128);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_SLAB, 2>, l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS, 2>, l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_GELU, 2>, l64);
@@ -1427,6 +1453,7 @@ template <typename T> void init_kernel_attrs() {
     set_max_lds(gemm_kernel<T, 64, 64, EPI_PATCH, 2>, l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_F32, 2>, l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX, 2>, l64);
+    set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_LSE, 2>, l64);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_SLAB, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS_GELU, 4>, 2 * l128);
@@ -1434,6 +1461,7 @@ template <typename T> void init_kernel_attrs() {
     set_max_lds(gemm_kernel<T, 128, 128, EPI_PATCH, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS_F32, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX, 4>, 2 * l128);
+    set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_LSE, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_SLAB, 4>, 2 * l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS, 4>, 2 * l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_GELU, 4>, 2 * l64);
@@ -1441,6 +1469,7 @@ template <typename T> void init_kernel_attrs() {
     set_max_lds(gemm_kernel<T, 64, 64, EPI_PATCH, 4>, 2 * l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_F32, 4>, 2 * l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX, 4>, 2 * l64);
+    set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_LSE, 4>, 2 * l64);
     set_max_lds(enc_attn_simple_kernel<T>, (200 * 65 + 200 * 64 + 4 * 64 + 4 * 256) * 4);
     set_max_lds(enc_attn2_kernel, EA2_LDS);
     set_max_lds(enc_attn_f32_kernel, EAF_LDS);
@@ -1524,7 +1553,9 @@ hipGraphExec_t decode_graph(mocr_engine* e, const DecState& st, int n, int steps
     const int need = ((t0 + steps + 3) / 4 + 7) / 8;
     const int bucket = need <= 3 ? 3 : need <= 5 ? 5 : need <= 8 ? 8 : 10;
     const int t_hi = std::min(bucket * 32, st.max_len) - 1;      // largest context this bucket covers
-    const auto key = std::make_tuple(e->lane_id, n, st.max_len * 16 + bucket, steps, e->rrows(n));
+    // ... and by whether the steps are the scored ones (another LM-head epilogue and token kernel): a graph captured for an
+    // unscored batch is never replayed for a scored one, or the reverse
+    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * 2 + (st.scores ? 1 : 0), steps, e->rrows(n));
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) return it->second;
     hipGraph_t g = nullptr;
@@ -1623,6 +1654,10 @@ void start_batch(mocr_engine* e, Lane& L) {
     else if (e->fp8attn) quantize_enc(e, L.n);
     // rows read pad_id (= 0) beyond what the loop writes
     HIPCHECK(hipMemsetAsync(e->ids, 0, (size_t)L.np * e->cfg.max_len * sizeof(int), e->stream));
+    // token scores: the batch is scored when one of its jobs asked; the start token and the pad tail score 0
+    L.scored = false;
+    for (const Job& j : L.jobs) L.scored = L.scored || j.out_logp != nullptr;
+    if (L.scored) HIPCHECK(hipMemsetAsync(e->scores, 0, (size_t)L.np * e->cfg.max_len * sizeof(float), e->stream));
     // The decode steps run on np >= n rows (graph_rows): the padding rows are born finished, emit pad_id and read
     // whatever the workspace holds for them (finite values; no kernel mixes rows).
     DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n);
@@ -1638,6 +1673,8 @@ void finish_batch(mocr_engine* e, Lane& L) {
         const hipMemcpyKind kind = j.out_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
         HIPCHECK(hipMemcpyAsync(j.out_ids, e->ids + (size_t)row0 * e->cfg.max_len, (size_t)j.n * e->cfg.max_len * sizeof(int), kind, e->stream));
         HIPCHECK(hipMemcpyAsync(j.out_len, e->len + row0, (size_t)j.n * sizeof(int), kind, e->stream));
+        if (j.out_logp)
+            HIPCHECK(hipMemcpyAsync(j.out_logp, e->scores + (size_t)row0 * e->cfg.max_len, (size_t)j.n * e->cfg.max_len * sizeof(float), kind, e->stream));
         row0 += j.n;
     }
     L.jobs.clear();
@@ -1706,7 +1743,7 @@ void advance(mocr_engine* e, Lane& L) {
         }
     }
     if (L.t >= L.steps) { finish_batch(e, L); return; }
-    DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n);
+    DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n, L.scored);
     // (while rows are leaving, half-length chunks: the count a compaction acts on is at most 4 + 4 steps old instead of 8 + 8;
     // a batch none of whose rows has finished - the synthetic-weights headline - keeps the long chunks)
     const int chunk = L.finishing ? std::min(chunk_steps(L.np), CHUNK / 2) : chunk_steps(L.np);
@@ -2091,6 +2128,7 @@ void allocate_lane(mocr_engine* e, int lane_id) {
     e->slab_cap = (long long)Bp * 12288;
     e->slabs = e->dalloc<float>((size_t)e->slab_cap);
     e->cand_val = e->dalloc<float>((size_t)Bp * (e->V / 64)); e->cand_idx = e->dalloc<int>((size_t)Bp * (e->V / 64));
+    e->cand_sum = e->dalloc<float>((size_t)Bp * (e->V / 64)); e->scores = e->dalloc<float>(Bp * (size_t)c.max_len);
     e->x_f32 = e->dalloc<float>(Bp * D); e->a_f32 = e->dalloc<float>(Bp * D); e->c_f32 = e->dalloc<float>(Bp * D);
     e->ln_stats = e->dalloc<float>(3 * Bp * 2);
     e->x_t = e->dalloc<char>(Bp * D * esz); e->a_t = e->dalloc<char>(Bp * D * esz); e->c_t = e->dalloc<char>(Bp * D * esz);
@@ -2278,7 +2316,7 @@ int mocr_synchronize(mocr_engine* e) {
     });
 }
 
-int mocr_recognize_device(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len) {
+int mocr_recognize_device_scored(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_ready(e, n);
@@ -2288,12 +2326,18 @@ int mocr_recognize_device(mocr_engine* e, const void* d_gray, int32_t n, void* d
         j.src = reinterpret_cast<const uint8_t*>(d_gray); j.src_host = false;
         j.n = n; j.max_len = e->gen_max_len;
         j.out_ids = reinterpret_cast<int32_t*>(d_out_ids); j.out_len = reinterpret_cast<int32_t*>(d_out_len); j.out_host = false;
+        j.out_logp = reinterpret_cast<float*>(d_out_logp);
         submit(e, j);
     });
 }
 
+int mocr_recognize_device(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len) {
+    return mocr_recognize_device_scored(e, d_gray, n, d_out_ids, d_out_len, nullptr);
+}
+
 static void recognize_host_chunks(mocr_engine* e, const uint8_t* images, int n, int h, int w, int64_t row_stride,
-                                  int64_t image_stride, int channels, int max_len, int32_t* out_ids, int32_t* out_len) {
+                                  int64_t image_stride, int channels, int max_len, int32_t* out_ids, int32_t* out_len,
+                                  float* out_logp = nullptr) {
     const int IMG = e->cfg.image_size;
     if (h != IMG || w != IMG)
         throw ArgError{"crops must be image_size x image_size (resize with PIL BILINEAR on the caller side)", MOCR_ERR_UNSUPPORTED};
@@ -2306,6 +2350,7 @@ static void recognize_host_chunks(mocr_engine* e, const uint8_t* images, int n, 
         j.row_stride = row_stride; j.image_stride = image_stride;
         j.n = std::min(e->cfg.max_batch, n - base); j.max_len = max_len;
         j.out_ids = out_ids + (size_t)base * e->cfg.max_len; j.out_len = out_len + base; j.out_host = true;
+        j.out_logp = out_logp ? out_logp + (size_t)base * e->cfg.max_len : nullptr;
         e->pending.push_back(j);
     }
     drive(e);
@@ -2321,15 +2366,20 @@ int mocr_recognize(mocr_engine* e, const uint8_t* images, int32_t n, int32_t h, 
     });
 }
 
-int mocr_recognize_gray_host(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
-                             int32_t* out_len) {
+int mocr_recognize_gray_host_scored(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                    int32_t* out_len, float* out_logp) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_ready(e, n, false);
         HIPCHECK(hipSetDevice(e->cfg.device));
         const int IMG = e->cfg.image_size;
-        recognize_host_chunks(e, gray, n, IMG, IMG, IMG, (int64_t)IMG * IMG, 1, max_len_override, out_ids, out_len);
+        recognize_host_chunks(e, gray, n, IMG, IMG, IMG, (int64_t)IMG * IMG, 1, max_len_override, out_ids, out_len, out_logp);
     });
+}
+
+int mocr_recognize_gray_host(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                             int32_t* out_len) {
+    return mocr_recognize_gray_host_scored(e, gray, n, max_len_override, out_ids, out_len, nullptr);
 }
 
 // Host pixels uploaded once (an image, or a whole page several crops are cut from) ...
@@ -2493,7 +2543,7 @@ static void preprocess_images(mocr_engine* e, const mocr_image* imgs, int n, uin
 // the preparation stream) while the lanes decode chunk k; a job's lane stream waits ON THE DEVICE for its chunk's event,
 // so the host never blocks on a preparation.  r02 prepared ALL crops, synchronised, and only then started to decode.
 static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& srcs, const PrepView* views, int n, int32_t* out_ids,
-                               int32_t* out_len) {
+                               int32_t* out_len, float* out_logp = nullptr) {
     const size_t plane = (size_t)e->cfg.image_size * e->cfg.image_size;
     const int C = std::min(e->cfg.max_batch, 4096), nchunks = (n + C - 1) / C;
     uint8_t* const d_gray = (uint8_t*)e->grow(e->rs_gray, (size_t)n * plane);
@@ -2504,6 +2554,7 @@ static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& sr
         j.row_stride = e->cfg.image_size; j.image_stride = (int64_t)plane;
         j.n = std::min(C, n - k * C); j.max_len = e->gen_max_len;
         j.out_ids = out_ids + (size_t)k * C * e->cfg.max_len; j.out_len = out_len + (size_t)k * C; j.out_host = true;
+        j.out_logp = out_logp ? out_logp + (size_t)k * C * e->cfg.max_len : nullptr;
         e->pending.push_back(j);
     };
     std::vector<PrepHold> holds(nchunks);
@@ -2558,7 +2609,8 @@ int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t
     });
 }
 
-int mocr_recognize_images(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len) {
+int mocr_recognize_images_scored(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                                 float* out_logp) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_ready(e, n, false);
@@ -2571,8 +2623,12 @@ int mocr_recognize_images(mocr_engine* e, const mocr_image* images, int32_t n, i
             srcs[i] = source_of(images[i]);
             views[i] = PrepView{i, 0, 0, srcs[i].w, srcs[i].h, srcs[i].rot};
         }
-        prepare_and_decode(e, srcs, views.data(), n, out_ids, out_len);
+        prepare_and_decode(e, srcs, views.data(), n, out_ids, out_len, out_logp);
     });
+}
+
+int mocr_recognize_images(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len) {
+    return mocr_recognize_images_scored(e, images, n, out_ids, out_len, nullptr);
 }
 
 // The crop a detected text region gets (src/ui/main_window.py:9530-9540): its bounding box grown by
@@ -2588,8 +2644,8 @@ static bool padded_region(const mocr_region& r, int page_h, int page_w, PrepView
     return true;
 }
 
-int mocr_recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions, int32_t n_regions,
-                           int32_t* out_ids, int32_t* out_len) {
+int mocr_recognize_regions_scored(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                  int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         if (!e->committed) throw ArgError{"weights not committed (mocr_commit_weights)", MOCR_ERR_STATE};
@@ -2612,18 +2668,26 @@ int mocr_recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_pa
         }
         const int L = e->cfg.max_len, nv = (int)views.size();
         std::vector<int32_t> ids((size_t)nv * L), lens(nv);
-        if (nv > 0) prepare_and_decode(e, srcs, views.data(), nv, ids.data(), lens.data());
+        std::vector<float> logp(out_logp ? (size_t)nv * L : 0);
+        if (nv > 0) prepare_and_decode(e, srcs, views.data(), nv, ids.data(), lens.data(), out_logp ? logp.data() : nullptr);
         for (int i = 0; i < n_regions; ++i) {
             int32_t* row = out_ids + (size_t)i * L;
             if (where[i] < 0) {
                 for (int t = 0; t < L; ++t) row[t] = e->cfg.pad_id;
                 out_len[i] = 0;
+                if (out_logp) std::fill(out_logp + (size_t)i * L, out_logp + (size_t)(i + 1) * L, 0.f);
             } else {
                 memcpy(row, ids.data() + (size_t)where[i] * L, (size_t)L * sizeof(int32_t));
                 out_len[i] = lens[where[i]];
+                if (out_logp) memcpy(out_logp + (size_t)i * L, logp.data() + (size_t)where[i] * L, (size_t)L * sizeof(float));
             }
         }
     });
+}
+
+int mocr_recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions, int32_t n_regions,
+                           int32_t* out_ids, int32_t* out_len) {
+    return mocr_recognize_regions_scored(e, pages, n_pages, regions, n_regions, out_ids, out_len, nullptr);
 }
 
 int mocr_set_generate_max_length(mocr_engine* e, int32_t max_len) {
@@ -2729,7 +2793,7 @@ int mocr_op_gemm(mocr_engine* e, const void* dA, const void* dW, const float* d_
         HIPCHECK(hipSetDevice(e->cfg.device));
         drive(e);
         e->bind(0);
-        if (epilogue == EPI_PATCH || epilogue == EPI_ARGMAX)
+        if (epilogue == EPI_PATCH || epilogue == EPI_ARGMAX || epilogue == EPI_ARGMAX_LSE)
             throw ArgError{"EPI_PATCH / EPI_ARGMAX are not exposed through mocr_op_gemm (EPI_ARGMAX: mocr_op_gemm_argmax)", MOCR_ERR_ARG};
         const long long slab = (long long)M * N;
         if (e->cfg.dtype == MOCR_BF16)
@@ -2937,7 +3001,7 @@ int mocr_op_dec_bias_gelu(mocr_engine* e, const float* d_slabs, int32_t nslab, c
     });
 }
 
-int mocr_op_dec_token(mocr_engine* e, const mocr_token_args* a) {
+int mocr_op_dec_token_scored(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -2948,7 +3012,8 @@ int mocr_op_dec_token(mocr_engine* e, const mocr_token_args* a) {
         if (!e->committed || a->n < 1 || !a->ids || !a->step || !a->finished || !a->len || !a->n_unfinished || !a->rowmap ||
             !a->x_f32 || !a->x_t || a->ids_ld < 1 || a->max_len < 2 || a->max_len > e->cfg.max_len || e->D != 768 || e->V != 6144 ||
             (!first && a->ncand > 0 && (!a->cand_val || !a->cand_idx)) ||
-            (!first && a->ncand <= 0 && (!a->slabs || a->nslab < 1)) || (a->forced && a->forced_T < 1))
+            (!first && a->ncand <= 0 && (!a->slabs || a->nslab < 1)) || (a->forced && a->forced_T < 1) ||
+            (d_scores && (first || a->forced || (a->ncand > 0 && !d_cand_sum))))
             throw ArgError{"mocr_op_dec_token: bad argument", MOCR_ERR_ARG};
         DecState st{};
         st.n_real = a->n_real;
@@ -2957,10 +3022,12 @@ int mocr_op_dec_token(mocr_engine* e, const mocr_token_args* a) {
         st.ids_ld = a->ids_ld; st.max_len = a->max_len;
         st.start_id = e->cfg.start_id; st.eos_id = e->cfg.eos_id; st.pad_id = e->cfg.pad_id;
         st.rowmap = a->rowmap;
+        st.scores = d_scores;
         DecTokenArgs t{};
         t.slabs = a->slabs; t.nslab = first ? 0 : a->nslab; t.slab_stride = (long long)a->n * e->V;
         t.vbias = a->vbias ? a->vbias : e->w.bv;
         t.cand_val = a->cand_val; t.cand_idx = a->cand_idx; t.ncand = first ? 0 : std::max(a->ncand, 0);
+        t.cand_sum = d_cand_sum;
         t.x_f32 = a->x_f32; t.x_t = a->x_t;
         if (a->cache && a->cache_fp8) { t.cache8 = reinterpret_cast<uint8_t*>(a->cache); t.inv8 = a->inv_sx; }
         else t.cache = a->cache;
@@ -2974,8 +3041,10 @@ int mocr_op_dec_token(mocr_engine* e, const mocr_token_args* a) {
     });
 }
 
-int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
-                        int32_t* d_cand_idx, int32_t M, int32_t N, int32_t K, int32_t tile) {
+int mocr_op_dec_token(mocr_engine* e, const mocr_token_args* a) { return mocr_op_dec_token_scored(e, a, nullptr, nullptr); }
+
+int mocr_op_gemm_argmax_lse(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                            int32_t* d_cand_idx, float* d_cand_sum, int32_t M, int32_t N, int32_t K, int32_t tile) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -2984,11 +3053,20 @@ int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const fl
         if (!e->committed || !dA || !dW || !d_bias || !d_cand_val || !d_cand_idx || M < 1 || K < 1 || (tile != 64 && tile != 128))
             throw ArgError{"mocr_op_gemm_argmax: bad argument", MOCR_ERR_ARG};
         dispatch(e, [&](auto tag) {
+            if (d_cand_sum)
+                gemm<decltype(tag)>(e, "op_gemm_argmax_lse", dA, K, dW, d_bias, d_cand_val, N, nullptr, M, N, K, EPI_ARGMAX_LSE, tile, 1, 0,
+                                    nullptr, 0, nullptr, 0, d_cand_idx, nullptr, d_cand_sum);
+            else
             gemm<decltype(tag)>(e, "op_gemm_argmax", dA, K, dW, d_bias, d_cand_val, N, nullptr, M, N, K, EPI_ARGMAX, tile, 1, 0,
                                 nullptr, 0, nullptr, 0, d_cand_idx);
         });
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
+}
+
+int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                        int32_t* d_cand_idx, int32_t M, int32_t N, int32_t K, int32_t tile) {
+    return mocr_op_gemm_argmax_lse(e, dA, dW, d_bias, d_cand_val, d_cand_idx, nullptr, M, N, K, tile);
 }
 
 int mocr_op_smallm_gemm(mocr_engine* e, const mocr_smallm_args* a) {

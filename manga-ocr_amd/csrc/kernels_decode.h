@@ -121,6 +121,9 @@ struct DecState {
     // can run on fewer of them - a finished row stops costing, as in the reference, where every crop is its own
     // generate() call (TF/generation/utils.py:2929-2937, src/core/workers.py:213-225).
     int* rowmap;
+    // Token scores (nullable): [B][ids_ld] float32, by row like ids.  scores[row][t + 1] = log-probability of ids[row][t + 1]
+    // (fp32 log-softmax of the step's LM-head logits at the chosen token), 0 for a finished row's pad ids.
+    float* scores;
 };
 
 // End of a decode step, one block per sequence:
@@ -128,7 +131,11 @@ struct DecState {
 //   finished rows emit pad_id (utils.py:2929); EOS or reaching max_len finishes a row (:2936)
 //   then the NEXT step's input embedding: LN(word[tok] + type[0] + pos[t+1])  (modeling_bert.py:98-106)
 // FIRST = true: no logits yet; emits the start token's embedding at position 0.
-template <typename T, int D, bool FIRST>
+// SCORES = true (st.scores set): also the log-probability of the arg-max token, logit_max - logsumexp(logits) = -log S with
+//   S = sum_j exp(logit_j - max) >= 1, in fp32.  Candidate path: the LM head left cand_sum[c] = sum over tile c of
+//   exp(logit - cand_val[c]) (EPI_ARGMAX_LSE), so S = sum_c cand_sum[c] * exp(cand_val[c] - max).  Slab path: the summed
+//   logits are in this block's registers.  Either way a second short pass once the block knows the max.
+template <typename T, int D, bool FIRST, bool SCORES = false>
 __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict__ slabs, int nslab, long long slab_stride,
                                                         const float* __restrict__ vbias, int V,
                                                         DecState st,
@@ -139,7 +146,8 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                                                         long long cache_batch_stride = 0,
                                                         const float* __restrict__ cand_val = nullptr,
                                                         const int* __restrict__ cand_idx = nullptr, int ncand = 0,
-                                                        uint8_t* __restrict__ cache8 = nullptr, float inv_sx8 = 0.f) {
+                                                        uint8_t* __restrict__ cache8 = nullptr, float inv_sx8 = 0.f,
+                                                        const float* __restrict__ cand_sum = nullptr) {
     __shared__ float s_val[4];
     __shared__ int s_idx[4];
     __shared__ float s_red[4];
@@ -158,6 +166,8 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
         const int t = st.step[b];
         float best = -INFINITY;
         int bi = 0x7fffffff;
+        constexpr int NC = 6;                            // vocab = NC * 1024 columns (6144)
+        float4 a[NC];
         if (cand_val) {
             // the LM-head GEMM already reduced every 64/128-column tile (EPI_ARGMAX): ncand candidates per row
             for (int c = tid; c < ncand; c += 256) {
@@ -166,8 +176,6 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                 if (cv > best || (cv == best && ci < bi)) { best = cv; bi = ci; }
             }
         } else {
-        constexpr int NC = 6;                            // vocab = NC * 1024 columns (6144)
-        float4 a[NC];
 #pragma unroll
         for (int j = 0; j < NC; ++j) a[j] = *reinterpret_cast<const float4*>(vbias + tid * 4 + j * 1024);
         for (int s = 0; s < nslab; ++s) {
@@ -197,6 +205,21 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
         }
         if (lane == 0) { s_val[wave] = best; s_idx[wave] = bi; }
         __syncthreads();
+        if constexpr (SCORES) {
+            const float gmax = fmaxf(fmaxf(s_val[0], s_val[1]), fmaxf(s_val[2], s_val[3]));     // = the winner's logit
+            float es = 0.f;
+            if (cand_val) {
+                for (int c = tid; c < ncand; c += 256)
+                    es += cand_sum[(size_t)b * ncand + c] * __expf(cand_val[(size_t)b * ncand + c] - gmax);
+            } else {
+#pragma unroll
+                for (int j = 0; j < NC; ++j)
+                    es += (__expf(a[j].x - gmax) + __expf(a[j].y - gmax)) + (__expf(a[j].z - gmax) + __expf(a[j].w - gmax));
+            }
+            es = wave_sum(es);
+            if (lane == 0) s_red[wave] = es;             // (s_red is free until the embedding's LayerNorm below)
+            __syncthreads();
+        }
         if (tid == 0) {
             for (int w = 1; w < 4; ++w)
                 if (s_val[w] > best || (s_val[w] == best && s_idx[w] < bi)) { best = s_val[w]; bi = s_idx[w]; }
@@ -205,6 +228,10 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
             int tok = fin ? st.pad_id : bi;
             if (st.forced) tok = (t + 1 < st.forced_T) ? st.forced[(size_t)b * st.forced_T + t + 1] : st.pad_id;
             if (t + 1 < st.ids_ld) st.ids[(size_t)row * st.ids_ld + t + 1] = tok;
+            if constexpr (SCORES) {
+                const float S = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+                if (t + 1 < st.ids_ld) st.scores[(size_t)row * st.ids_ld + t + 1] = fin ? 0.f : -logf(S);
+            }
             if (!fin && !st.forced && (tok == st.eos_id || t + 2 >= st.max_len)) {
                 st.finished[row] = 1;
                 st.len[row] = t + 2;

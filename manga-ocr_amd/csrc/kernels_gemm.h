@@ -33,8 +33,10 @@ enum GemmEpilogue {
     EPI_BIAS_RESID = 3,  // out f32 = (acc + bias) + resid        (out may alias resid)
     EPI_PATCH = 4,       // patch-embed: out f32[b*197+1+p] = (acc + bias) + pos[1+p]
     EPI_BIAS_F32 = 5,    // out f32 = acc + bias
-    EPI_ARGMAX = 6       // LM head: per (row, N-tile) the fp32 max of acc + bias and its column (lowest column wins ties):
+    EPI_ARGMAX = 6,      // LM head: per (row, N-tile) the fp32 max of acc + bias and its column (lowest column wins ties):
                          //   out f32 [M][ntn] values, cand_idx int [M][ntn] columns - the logits never go to memory
+    EPI_ARGMAX_LSE = 7   // token scores: EPI_ARGMAX + cand_sum f32 [M][ntn] = the tile's sum of exp(acc + bias - the tile's max),
+                         //   from which the token kernel gets the chosen token's log-probability; the logits still stay in LDS
 };
 
 struct GemmParams {
@@ -63,6 +65,7 @@ struct GemmParams {
     const float* csum;     // [N] column sums of the folded weight W o gamma (as rounded to bf16)
     void* xb;              // fp32-residual GEMM: bf16 copy of the output rows, [M][ldo]
     float ln_eps;
+    float* cand_sum;       // EPI_ARGMAX_LSE: [M][ntn] sum of exp(logit - tile max) over the tile's columns
 };
 
 // Linear tile id -> (tm, tn).  Tiles are ordered column-group by column-group: inside a group of
@@ -140,7 +143,11 @@ __device__ __forceinline__ void gemm_epilogue(const float* sC, const GemmParams&
 // NT / BM threads share a row (adjacent lanes); a thread scans its BN / (NT/BM) physical columns of the LDS tile 4 at a
 // time, starting at a row-dependent rotation so that the 16 lanes of a ds_read_b128 group hit 16 different 16-byte
 // slots.  SWZ: the tile's 16-column groups are XORed with (row>>2)&3 (see gemm_epilogue): physical -> logical column.
-template <int BM, int BN, int NT, bool SWZ>
+// LSE (EPI_ARGMAX_LSE): once the row's threads agree on the tile's max, each walks its columns a second time - same
+// rotation, same swizzle, so as conflict-free as the first walk - and sums exp(v - max) in fp32; cand_sum[m][tile] gets the
+// row's sum (>= 1: the max itself contributes exp(0)).  v = acc + bias is recomputed with the same fp32 add as in the first
+// walk, so v - max is exactly 0 at the winning column and <= 0 everywhere else.
+template <int BM, int BN, int NT, bool SWZ, bool LSE = false>
 __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const GemmParams& p, int m0, int n0, int tid) {
     constexpr int TPRW = NT / BM, CPP = BN / TPRW;
     static_assert(TPRW == 2 || TPRW == 4, "two or four threads per row");
@@ -167,10 +174,24 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const Gemm
         const int oi = __shfl_xor(bi, o, 64);
         if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
     }
+    float esum = 0.f;
+    if constexpr (LSE) {
+#pragma unroll
+        for (int q = 0; q < CPP / 4; ++q) {
+            const int pc = part * CPP + ((rot + 4 * q) % CPP);
+            const float4 cv = *reinterpret_cast<const float4*>(&sC[row * BN + pc]);
+            const float4 bv = *reinterpret_cast<const float4*>(p.bias + n0 + (pc ^ sw));
+            esum += (__expf((cv.x + bv.x) - best) + __expf((cv.y + bv.y) - best)) +
+                    (__expf((cv.z + bv.z) - best) + __expf((cv.w + bv.w) - best));
+        }
+#pragma unroll
+        for (int o = TPRW / 2; o > 0; o >>= 1) esum += __shfl_xor(esum, o, 64);
+    }
     if (part == 0 && m < p.M) {
         const size_t c = (size_t)m * p.ntn + n0 / BN;
         reinterpret_cast<float*>(p.out)[c] = best;
         p.cand_idx[c] = bi;
+        if constexpr (LSE) p.cand_sum[c] = esum;
     }
 }
 
@@ -382,6 +403,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
 
     if constexpr (EPI == EPI_ARGMAX) {
         gemm_epilogue_argmax<BM, BN, 256, SWZ>(sC, p, m0, n0, tid);
+    } else if constexpr (EPI == EPI_ARGMAX_LSE) {
+        gemm_epilogue_argmax<BM, BN, 256, SWZ, true>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_BIAS) {
         GemmParams q = p;
         q.out = reinterpret_cast<T*>(p.out) + (size_t)blockIdx.y * p.o_yoff;

@@ -133,35 +133,46 @@ class Engine:
             d.rotate = int(rotate[i]) if rotate is not None else 0
         return descs, keep
 
-    def recognize_images(self, images, bgr: bool = False, rotate=None) -> Tuple[np.ndarray, np.ndarray]:
+    def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False):
         """Crops of any sizes (list of uint8 [h,w] / [h,w,3] arrays; `bgr`: 3-channel crops are in OpenCV order;
         `rotate`: per crop 0 / 1 (90 degrees clockwise) / 2 (counter-clockwise), applied on the device): luminance
         conversion and the Pillow-exact BILINEAR resize to 224x224 run on the device.
-        Returns (ids int32 [n,max_len], lengths int32 [n])."""
+        Returns (ids int32 [n,max_len], lengths int32 [n]); with ``scores=True`` (ids, lengths, logp float32 [n,max_len]):
+        the log-probability of every emitted token, computed on the device (include/mocr.h, "token scores"); same ids."""
         if len(images) == 0:
-            return np.zeros((0, self.spec.max_len), dtype=np.int32), np.zeros(0, dtype=np.int32)
+            empty = (np.zeros((0, self.spec.max_len), dtype=np.int32), np.zeros(0, dtype=np.int32))
+            return empty + (np.zeros((0, self.spec.max_len), dtype=np.float32),) if scores else empty
         descs, keep = self._image_descs(images, bgr, rotate)
         n = len(keep)
         ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
         lens = np.zeros(n, dtype=np.int32)
+        if scores:
+            logp = np.zeros((n, self.spec.max_len), dtype=np.float32)
+            self._check(self.lib.mocr_recognize_images_scored(self._h, descs, n, _ptr(ids), _ptr(lens), _ptr(logp)))
+            return ids, lens, logp
         self._check(self.lib.mocr_recognize_images(self._h, descs, n, _ptr(ids), _ptr(lens)))
         return ids, lens
 
-    def recognize_regions(self, pages, regions, bgr: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+    def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False):
         """pages: list of uint8 [H,W,3] (or [H,W]) arrays; regions: iterable of (page_index, x, y, w, h) bounding
         rectangles.  Each page is uploaded once; the 8 %-padded, page-clipped crop of every region
         (``src/ui/main_window.py:9530-9540``) is cut on the device.  Returns (ids [n,max_len], lengths [n]);
-        a region reduced to a sliver has length 0."""
+        a region reduced to a sliver has length 0.  ``scores=True``: (ids, lengths, logp float32 [n,max_len]), a sliver's
+        row all 0."""
         regs = list(regions)
         n = len(regs)
         ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
         lens = np.zeros(n, dtype=np.int32)
+        logp = np.zeros((n, self.spec.max_len), dtype=np.float32) if scores else None
         if n == 0:
-            return ids, lens
+            return (ids, lens, logp) if scores else (ids, lens)
         descs, keep = self._image_descs(pages, bgr)
         arr = (_capi.MocrRegion * n)()
         for i, (pg, x, y, w, h) in enumerate(regs):
             arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
+        if scores:
+            self._check(self.lib.mocr_recognize_regions_scored(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens), _ptr(logp)))
+            return ids, lens, logp
         self._check(self.lib.mocr_recognize_regions(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens)))
         return ids, lens
 
@@ -190,18 +201,27 @@ class Engine:
         self._check(self.lib.mocr_preprocess(self._h, descs, len(keep), _ptr(out)))
         return out
 
-    def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len) -> None:
-        """Asynchronous; all three are device buffers (torch CUDA tensors or raw addresses)."""
+    def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None) -> None:
+        """Asynchronous; all are device buffers (torch CUDA tensors or raw addresses).  ``d_out_logp`` (float32
+        [n,max_len]): also the token log-probabilities."""
+        if d_out_logp is not None:
+            self._check(self.lib.mocr_recognize_device_scored(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len), _ptr(d_out_logp)))
+            return
         self._check(self.lib.mocr_recognize_device(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len)))
 
     def set_generate_max_length(self, max_len: int) -> None:
         self._check(self.lib.mocr_set_generate_max_length(self._h, int(max_len)))
 
-    def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False):
         a = np.ascontiguousarray(gray, dtype=np.uint8)
         n = a.shape[0]
         ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
         lens = np.zeros(n, dtype=np.int32)
+        if scores:
+            logp = np.zeros((n, self.spec.max_len), dtype=np.float32)
+            self._check(self.lib.mocr_recognize_gray_host_scored(self._h, _ptr(a), n, max_len or self.spec.max_len, _ptr(ids), _ptr(lens),
+                                                                 _ptr(logp)))
+            return ids, lens, logp
         self._check(self.lib.mocr_recognize_gray_host(self._h, _ptr(a), n, max_len or self.spec.max_len, _ptr(ids), _ptr(lens)))
         return ids, lens
 
@@ -269,6 +289,19 @@ class Engine:
             ftype = dict(_capi.MocrTokenArgs._fields_)[name]
             setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
         self._check(self.lib.mocr_op_dec_token(self._h, C.byref(a)))
+
+    def op_dec_token_scored(self, d_cand_sum, d_scores, **kw) -> None:
+        """The scored token step: op_dec_token plus the tiles' exp sums (candidate path) and the score rows."""
+        a = _capi.MocrTokenArgs()
+        a.struct_size = C.sizeof(_capi.MocrTokenArgs)
+        for name, value in kw.items():
+            ftype = dict(_capi.MocrTokenArgs._fields_)[name]
+            setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
+        self._check(self.lib.mocr_op_dec_token_scored(self._h, C.byref(a), _ptr(d_cand_sum), _ptr(d_scores)))
+
+    def op_gemm_argmax_lse(self, dA, dW, d_bias, d_cand_val, d_cand_idx, d_cand_sum, M, N, K, tile) -> None:
+        self._check(self.lib.mocr_op_gemm_argmax_lse(self._h, _ptr(dA), _ptr(dW), _ptr(d_bias), _ptr(d_cand_val), _ptr(d_cand_idx),
+                                                     _ptr(d_cand_sum), M, N, K, tile))
 
     def op_gemm_argmax(self, dA, dW, d_bias, d_cand_val, d_cand_idx, M, N, K, tile) -> None:
         self._check(self.lib.mocr_op_gemm_argmax(self._h, _ptr(dA), _ptr(dW), _ptr(d_bias), _ptr(d_cand_val), _ptr(d_cand_idx),

@@ -17,6 +17,7 @@ import os
 import threading
 import time
 from concurrent.futures import Future
+from dataclasses import dataclass
 from pathlib import Path
 from typing import List, Optional, Sequence, Union
 
@@ -62,9 +63,37 @@ def to_pixels(img) -> np.ndarray:
     return np.asarray(img, dtype=np.uint8)
 
 
+@dataclass(frozen=True)
+class Recognition:
+    """One recognised crop with the recogniser's own confidence (the ``*_scored`` methods of :class:`MangaOcr`).
+
+    ``logprobs[k]`` is the natural-log probability the decoder gave ``ids[k + 1]`` - the generated tokens, EOS included;
+    the start token is given, not predicted, and carries no score.  ``confidence`` is the geometric-mean token
+    probability ``exp(mean(logprobs))``, ``min_prob`` the least certain token's ``exp(min(logprobs))``; both are 0.0 for a
+    region that was never decoded (reduced to a sliver: ``text == ''``, no ids)."""
+    text: str
+    ids: np.ndarray
+    logprobs: np.ndarray
+    confidence: float
+    min_prob: float
+
+    @classmethod
+    def from_row(cls, vocab, ids_row: np.ndarray, logp_row: np.ndarray, length: int) -> "Recognition":
+        """A row of the engine's (ids, logp) blocks and its length (0: a sliver region) -> Recognition."""
+        n = int(length)
+        ids = np.array(ids_row[:n], dtype=np.int32)
+        lp = np.array(logp_row[1:n], dtype=np.float32) if n > 1 else np.zeros(0, dtype=np.float32)
+        if lp.size == 0:
+            return cls("" if n == 0 else ids_to_text(vocab, ids), ids, lp, 0.0, 0.0)
+        lp64 = lp.astype(np.float64)
+        return cls(ids_to_text(vocab, ids), ids, lp, float(np.exp(lp64.mean())), float(np.exp(lp64.min())))
+
+
 class _Batcher:
     """Coalesces concurrent single-crop requests into engine batches (FIFO, per-request error
-    isolation like the reference's worker loop, ``src/core/workers.py:241-244``)."""
+    isolation like the reference's worker loop, ``src/core/workers.py:241-244``).  A request may ask for token scores;
+    a batch with such a request makes the engine's scored call (the ids do not depend on it), and every caller gets
+    what it asked for: ids, or (ids, logp)."""
 
     def __init__(self, engine: Engine, max_batch: int, timeout_ms: float):
         self.engine, self.max_batch, self.timeout = engine, max_batch, timeout_ms / 1000.0
@@ -74,12 +103,12 @@ class _Batcher:
         self._thread = threading.Thread(target=self._run, name="mocr-batcher", daemon=True)
         self._thread.start()
 
-    def submit(self, gray: np.ndarray) -> Future:
+    def submit(self, gray: np.ndarray, scored: bool = False) -> Future:
         f: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
-            self._q.append((gray, f))
+            self._q.append((gray, f, scored))
             self._cv.notify()
         return f
 
@@ -98,11 +127,14 @@ class _Batcher:
                     self._cv.wait(left)
                 batch, self._q = self._q[:self.max_batch], self._q[self.max_batch:]
             try:
-                ids, lens = self.engine.recognize_images([g for g, _ in batch])
-                for i, (_, f) in enumerate(batch):
-                    f.set_result(ids[i, :lens[i]].copy())
+                if any(sc for _, _, sc in batch):
+                    ids, lens, logp = self.engine.recognize_images([g for g, _, _ in batch], scores=True)
+                else:
+                    (ids, lens), logp = self.engine.recognize_images([g for g, _, _ in batch]), None
+                for i, (_, f, sc) in enumerate(batch):
+                    f.set_result((ids[i, :lens[i]].copy(), logp[i, :lens[i]].copy()) if sc else ids[i, :lens[i]].copy())
             except BaseException as exc:  # every waiting caller gets the error; the loop lives on
-                for _, f in batch:
+                for _, f, _ in batch:
                     if not f.done():
                         f.set_exception(exc)
 
@@ -240,6 +272,52 @@ class MangaOcr:
         ('' for a region reduced to a sliver, like the reference)."""
         ids, lens = self.engine.recognize_regions(list(pages_bgr), list(regions), True)
         return [ids_to_text(self.vocab, ids[i, :lens[i]]) if lens[i] > 0 else "" for i in range(len(lens))]
+
+    # ------------------------------------------------------------------ scored surface: the same recognitions + confidence
+    def _check_scored(self) -> None:
+        no = getattr(self.engine, "NO_SCORES", None)      # MultiGpuEngine: its exchange ships ids and lengths only
+        if no:
+            raise NotImplementedError(no)
+
+    def _recognitions(self, ids, lens, logp) -> List[Recognition]:
+        return [Recognition.from_row(self.vocab, ids[i], logp[i], lens[i]) for i in range(len(lens))]
+
+    def recognize_scored(self, img_or_path) -> Recognition:
+        """``__call__`` with the recogniser's confidence: same text, plus the token log-probabilities computed on the
+        device (include/mocr.h, "token scores").  Goes through the same batcher as ``__call__``; scored and unscored
+        callers may share a batch."""
+        from PIL import Image
+        self._check_scored()
+        if isinstance(img_or_path, (str, Path)):
+            img = Image.open(img_or_path)
+        elif isinstance(img_or_path, Image.Image):
+            img = img_or_path
+        else:
+            raise ValueError(f"img_or_path must be a path or PIL.Image, instead got: {img_or_path}")
+        ids, logp = self._batcher.submit(to_pixels(img), scored=True).result()
+        return Recognition.from_row(self.vocab, ids, logp, len(ids))
+
+    def recognize_batch_scored(self, images: Sequence) -> List[Recognition]:
+        """``recognize_batch`` with confidences."""
+        self._check_scored()
+        return self._recognitions(*self.engine.recognize_images([to_pixels(im) for im in images], scores=True))
+
+    def recognize_bgr_scored(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None) -> List[Recognition]:
+        """``recognize_bgr`` with confidences."""
+        from .queue_worker import rotation_code
+        self._check_scored()
+        crops = list(crops_bgr)
+        rot = None
+        if orientations is not None:
+            if len(orientations) != len(crops):
+                raise ValueError(f"recognize_bgr_scored: {len(crops)} crops but {len(orientations)} orientations")
+            rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
+        return self._recognitions(*self.engine.recognize_images(crops, True, rot, scores=True))
+
+    def recognize_regions_scored(self, pages_bgr: Sequence[np.ndarray], regions) -> List[Recognition]:
+        """``recognize_regions`` with confidences; a region reduced to a sliver gives text '' and confidence 0.0."""
+        self._check_scored()
+        return self._recognitions(*self.engine.recognize_regions(list(pages_bgr), list(regions), True, scores=True))
 
     def recognize_page(self, page_bgr: np.ndarray, regions):
         """``_collect_manga_detections`` for one page: ``regions`` = the detector's (text, polygon) pairs."""
