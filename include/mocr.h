@@ -181,6 +181,29 @@ int mocr_recognize_images_scored(mocr_engine* e, const mocr_image* images, int32
 int mocr_recognize_regions_scored(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
                                   int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp);
 
+/* ---- token alternatives -----------------------------------------------------------------------
+ * What else a position could have been: the four most probable tokens of every step, from the same LM-head launch that
+ * chose the token (the logits still never reach memory: the GEMM epilogue keeps four candidates per tile instead of one).
+ * Two more outputs with the row layout of out_ids and one more axis:
+ *   out_alt_ids  int32   [n, max_len, MOCR_ALTERNATIVES]
+ *   out_alt_logp float32 [n, max_len, MOCR_ALTERNATIVES]
+ * For 1 <= t < out_len[r], entry k holds the token with the k-th largest logit of the step that emitted ids[r][t] and its
+ * log-probability logit - logsumexp(logits) (fp32 softmax in both engine dtypes, as for the scores).  Entries are ordered by
+ * logit descending, equal logits the lower id first - the tie rule of the greedy pick - so
+ *   out_alt_ids[r][t][0] == out_ids[r][t], out_alt_logp[r][t][0] is bit-identical to out_logp[r][t],
+ *   the four ids of a position are distinct and its four log-probabilities do not increase.
+ * For t == 0 and t >= out_len[r] the ids are -1 and the log-probabilities 0 (a whole row of these for a region reduced to a
+ * sliver, out_len 0).  Rows without a finite logit are unspecified, as for the scores.
+ * Asking for alternatives moves no id and no length.  The two pointers are both null (= the scored call) or both set;
+ * out_logp stays nullable.  Unscored, scored and alternatives requests may share a batch; it runs in the richest mode asked.
+ * The buffers this needs on the device are allocated by the first request that asks. */
+#define MOCR_ALTERNATIVES 4
+int mocr_recognize_images_alts(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                               float* out_logp, int32_t* out_alt_ids, float* out_alt_logp);
+int mocr_recognize_regions_alts(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                float* out_alt_logp);
+
 /* Preprocessing only (test hook): out_gray [n, image_size, image_size] uint8 (host) = the plane the encoder sees
  * in each of its three equal input channels before the 1/255 and (x - 0.5)/0.5 scaling. */
 int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t* out_gray);
@@ -194,6 +217,10 @@ int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t
 int mocr_recognize_device(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len);
 /* mocr_recognize_device plus d_out_logp, a device pointer to [n, max_len] float32 (token scores, see above; nullable). */
 int mocr_recognize_device_scored(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp);
+/* ... plus d_out_alt_ids int32 / d_out_alt_logp float32, device pointers to [n, max_len, MOCR_ALTERNATIVES] (token
+ * alternatives, see above; both null or both set). */
+int mocr_recognize_device_alts(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp,
+                               void* d_out_alt_ids, void* d_out_alt_logp);
 /* generate(max_length=...) of every batch submitted from now on, whatever the entry point (2 <= max_len <= the
  * engine's max_len; rows are still max_len wide; mocr_recognize_gray_host's own argument overrides it).  The reference always calls generate with 300; a speech bubble is
  * typically ~32 tokens (SURVEY.md §8d reports both regimes). */
@@ -214,6 +241,8 @@ int mocr_recognize_gray_host(mocr_engine* e, const uint8_t* gray, int32_t n, int
                              int32_t* out_ids, int32_t* out_len);
 int mocr_recognize_gray_host_scored(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override,
                                     int32_t* out_ids, int32_t* out_len, float* out_logp);   /* + token scores (nullable) */
+int mocr_recognize_gray_host_alts(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                  int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp);   /* + token alternatives */
 
 /* Single operators on device buffers of the engine's dtype (kernel unit tests). */
 int mocr_op_gemm(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, void* d_out,
@@ -303,6 +332,13 @@ int mocr_op_dec_token(mocr_engine* e, const mocr_token_args* a);
  * d_cand_sum [n][ncand] = the tiles' sums of exp(logit - cand_val) (mocr_op_gemm_argmax_lse); slab path: d_cand_sum unused.
  * Not with first or forced ids.  d_scores = NULL is mocr_op_dec_token.  Rows without a finite logit score NaN. */
 int mocr_op_dec_token_scored(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores);
+/* The token step with alternatives (token alternatives): the scored launch plus d_alt_ids int32 / d_alt_logp float32
+ * [rows][ids_ld][4], indexed by row like ids: [rowmap[s]][step[s] + 1][k] = the token with the k-th largest logit of slot s
+ * and (logit_k - max) - log(sum_j exp(logit_j - max)); -1 / 0 when the row is finished.  Candidate path: d_top_val / d_top_idx
+ * [n][ncand][4] = the tiles' four best (mocr_op_gemm_topk); slab path: unused.  Needs d_scores; restrictions as for the scored
+ * step.  d_alt_ids = d_alt_logp = NULL is mocr_op_dec_token_scored. */
+int mocr_op_dec_token_topk(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                           const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp);
 /* The LM head's fused argmax GEMM (tile 64 or 128, not split): d_cand_val / d_cand_idx [M][N / tile] = per row and N-tile
  * the largest acc + bias and its column (the lowest column on a tie).  dA holds M rounded up to the tile. */
 int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
@@ -311,6 +347,12 @@ int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const fl
  * tile's columns of exp(acc + bias - d_cand_val); d_cand_val / d_cand_idx are bit-identical to mocr_op_gemm_argmax's. */
 int mocr_op_gemm_argmax_lse(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
                             int32_t* d_cand_idx, float* d_cand_sum, int32_t M, int32_t N, int32_t K, int32_t tile);
+/* The LM head with alternatives (token alternatives): mocr_op_gemm_argmax_lse plus d_top_val / d_top_idx [M][N / tile][4] =
+ * per row and N-tile the four largest acc + bias and their columns (value descending, the lower column first on a tie;
+ * entry 0 = d_cand_val / d_cand_idx); the three candidate arrays are bit-identical to mocr_op_gemm_argmax_lse's. */
+int mocr_op_gemm_topk(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                      int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N, int32_t K,
+                      int32_t tile);
 /* bf16 engines: the small-batch projection (rows <= 32; kernels_smallm.h SmallMParams), one of the (pro, epi) pairs the
  * small-batch decode step launches: (0,0) (1,0) (0,1) (1,2) (1,3). */
 typedef struct mocr_smallm_args {

@@ -140,3 +140,54 @@ __device__ __forceinline__ void glds16_nt(const void* gsrc_lane, void* lds_wave_
 #else
 #define LAT_GLDS glds16_nt
 #endif
+
+// A sorted list of the four best (value, column) pairs seen so far: value descending, the lower column first among equal
+// values - the order of the greedy pick.  Unfilled entries are (-inf, 0x7fffffff); a NaN wins no comparison and never enters.
+struct Top4 {
+    float v[4];
+    int i[4];
+};
+
+__device__ __forceinline__ void top4_clear(Top4& l) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { l.v[k] = -INFINITY; l.i[k] = 0x7fffffff; }
+}
+
+// Branch-free insertion: the candidate sinks down the list, taking the place of the first entry it precedes; the entry it
+// displaces precedes everything below it and pushes the rest down one place.
+__device__ __forceinline__ void top4_insert(Top4& l, float v, int i) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const bool c = (v > l.v[k]) | ((v == l.v[k]) & (i < l.i[k]));        // (bitwise: selects, no control flow)
+        const float tv = c ? l.v[k] : v;
+        const int ti = c ? l.i[k] : i;
+        l.v[k] = c ? v : l.v[k];
+        l.i[k] = c ? i : l.i[k];
+        v = tv; i = ti;
+    }
+}
+
+// l = the four best of l and of the list the lane `xor_mask` away holds (both lanes end with the same list).  Two sorted
+// lists: max(l[k], o[3 - k]), k = 0 .. 3, are the four best of the eight, as a bitonic sequence; two compare-exchange stages
+// ((0,2) (1,3), then (0,1) (2,3)) sort it.  8 comparisons where four insertions take 16.
+__device__ __forceinline__ bool top4_before(float av, int ai, float bv, int bi) {
+    return (av > bv) | ((av == bv) & (ai < bi));
+}
+__device__ __forceinline__ void top4_order(Top4& l, int a, int b) {      // afterwards entry a precedes entry b
+    const bool c = top4_before(l.v[b], l.i[b], l.v[a], l.i[a]);
+    const float va = l.v[a]; const int ia = l.i[a];
+    l.v[a] = c ? l.v[b] : va; l.i[a] = c ? l.i[b] : ia;
+    l.v[b] = c ? va : l.v[b]; l.i[b] = c ? ia : l.i[b];
+}
+__device__ __forceinline__ void top4_merge_xor(Top4& l, int xor_mask) {
+    Top4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { o.v[k] = __shfl_xor(l.v[3 - k], xor_mask, 64); o.i[k] = __shfl_xor(l.i[3 - k], xor_mask, 64); }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {           // o[k] = the other lane's entry 3 - k
+        const bool c = top4_before(o.v[k], o.i[k], l.v[k], l.i[k]);
+        l.v[k] = c ? o.v[k] : l.v[k]; l.i[k] = c ? o.i[k] : l.i[k];
+    }
+    top4_order(l, 0, 2); top4_order(l, 1, 3);
+    top4_order(l, 0, 1); top4_order(l, 2, 3);
+}

@@ -124,6 +124,9 @@ struct LaneCtx {
     float* cand_val = nullptr; int* cand_idx = nullptr;   // [Bp][vocab/64] per-tile argmax candidates of the LM head
     float* cand_sum = nullptr;                      // [Bp][vocab/64] scored batches: per-tile sum of exp(logit - the tile's max)
     float* scores = nullptr;                        // [Bp][max_len] scored batches: log-probability of every emitted token, by row like ids
+    // token alternatives: allocated by the first batch that asks (ensure_alt_buffers), so other engines keep their footprint
+    float* top_val = nullptr; int* top_idx = nullptr;   // [Bp][vocab/64][4] per-tile four best logits / columns of the LM head
+    int* alt_ids = nullptr; float* alt_logp = nullptr;  // [Bp][max_len][4] the four best tokens of every step / their log-probabilities, by row like ids
     float *x_f32 = nullptr, *a_f32 = nullptr, *c_f32 = nullptr;
     float* ln_stats = nullptr;                      // small-batch path: (mean, rstd) per row of the three pre-LayerNorm sums, [3][Bp][2]
     void *x_t = nullptr, *a_t = nullptr, *c_t = nullptr, *ctx_t = nullptr, *h_t = nullptr, *z_t = nullptr;
@@ -149,6 +152,8 @@ struct Job {
     int32_t* out_ids = nullptr;     // host (out_host) or device
     int32_t* out_len = nullptr;
     float* out_logp = nullptr;      // nullable: [n][max_len] token log-probabilities (the *_scored entry points); host or device like out_ids
+    int32_t* out_alt_ids = nullptr; // nullable, both or neither (the *_alts entry points): [n][max_len][MOCR_ALTERNATIVES] the four best tokens of
+    float* out_alt_logp = nullptr;  // every position and their log-probabilities; host or device like out_ids
     bool out_host = false;
 };
 
@@ -159,7 +164,8 @@ struct Lane {
     int n = 0, max_len = 0;         // rows of the merged batch, its generate(max_length)
     int np = 0;                     // slots the decode steps run on: n rounded up (graph_rows), the extra ones are born finished; shrinks when the batch is compacted
     int np0 = 0;                    // np at the start of the batch = its kernel regime
-    bool scored = false;            // a job of this batch asked for token log-probabilities: its steps run the scored LM head / token kernel
+    int mode = 0;                   // the richest kind of request among this batch's jobs: 0 ids only, 1 token log-probabilities (the scored
+                                    // LM head / token kernel), 2 also the token alternatives (EPI_TOPK / the TOPK token kernel)
     int t = 0, steps = 0, chunk = 0;
     bool finishing = false;         // a flag of this batch has reported a finished row: rows are leaving, chunks get shorter
     bool flag_pending[2] = {false, false};
@@ -208,7 +214,7 @@ struct mocr_engine : LaneCtx {
     size_t esz = 2;
     std::vector<Lane> lanes;
     std::vector<Job> pending;
-    // decode-step HIP graphs, keyed by (lane, rows, (max_len, context bucket, scored), steps per graph)
+    // decode-step HIP graphs, keyed by (lane, rows, (max_len, context bucket, mode 0 / 1 / 2), steps per graph)
     std::map<std::tuple<int, int, int, int, int>, hipGraphExec_t> graphs;      // + the regime
     void bind(int i) { static_cast<LaneCtx&>(*this) = lanes[i].ctx; }
     void unbind(int i) { lanes[i].ctx = static_cast<LaneCtx&>(*this); }
@@ -365,6 +371,7 @@ void launch_gemm_epi(mocr_engine* e, const GemmParams& p, int epi, int split, in
         case EPI_BIAS_F32: launch_gemm_t<T, BM, BN, EPI_BIAS_F32>(e, p, split, ybatch); break;
         case EPI_ARGMAX: launch_gemm_t<T, BM, BN, EPI_ARGMAX>(e, p, split, ybatch); break;
         case EPI_ARGMAX_LSE: launch_gemm_t<T, BM, BN, EPI_ARGMAX_LSE>(e, p, split, ybatch); break;
+        case EPI_TOPK: launch_gemm_t<T, BM, BN, EPI_TOPK>(e, p, split, ybatch); break;
         default: throw ArgError{"unknown GEMM epilogue", MOCR_ERR_ARG};
     }
 }
@@ -553,13 +560,14 @@ template <typename T>
 void gemm(mocr_engine* e, const char* name, const void* A, int lda, const void* W, const float* bias, void* out, int ldo,
           const float* resid, int M, int N, int K, int epi, int tile, int split, long long slab_stride = 0,
           const float* pos = nullptr, int patches = 0, const HeadBatch* hb = nullptr, int group_n = 0, int* cand_idx = nullptr,
-          const LnFold* lnf = nullptr, float* cand_sum = nullptr) {
+          const LnFold* lnf = nullptr, float* cand_sum = nullptr, float* top_val = nullptr, int* top_idx = nullptr) {
     const int kt = 128 / (int)sizeof(T);
     if (N % (tile >= 1024 ? 256 : tile >= 256 ? 128 : std::max(tile, 1)) || K % (kt * split) || (split > 1 && epi != EPI_SLAB) ||
         (tile >= 256 && (sizeof(T) != 2 || split != 1)))
         throw ArgError{std::string("gemm shape not tileable: ") + name, MOCR_ERR_ARG};
     GemmParams p{};
     p.A = A; p.W = W; p.bias = bias; p.out = out; p.resid = resid; p.pos = pos; p.cand_idx = cand_idx; p.cand_sum = cand_sum;
+    p.top_val = top_val; p.top_idx = top_idx;
     p.M = M; p.N = N; p.lda = lda; p.ldw = K; p.ldo = ldo;
     int ybatch = 1;
     if (hb) {
@@ -970,7 +978,7 @@ void launch_dec_bias_gelu(mocr_engine* e, const float* slabs, int nslab, long lo
 }
 
 static DecState make_state(mocr_engine* e, int max_len, const int* forced, int forced_T, float* logits_out, int n_real,
-                           bool scored = false) {
+                           int mode = 0) {
     DecState st{};
     st.n_real = n_real;
     st.ids = e->ids; st.step = e->step; st.finished = e->finished; st.len = e->len; st.n_unfinished = e->n_unf;
@@ -978,7 +986,8 @@ static DecState make_state(mocr_engine* e, int max_len, const int* forced, int f
     st.ids_ld = e->cfg.max_len; st.max_len = max_len;
     st.start_id = e->cfg.start_id; st.eos_id = e->cfg.eos_id; st.pad_id = e->cfg.pad_id;
     st.rowmap = e->rowmap;
-    st.scores = scored ? e->scores : nullptr;
+    st.scores = mode >= 1 ? e->scores : nullptr;
+    st.alt_ids = mode >= 2 ? e->alt_ids : nullptr; st.alt_logp = mode >= 2 ? e->alt_logp : nullptr;
     return st;
 }
 
@@ -988,6 +997,7 @@ struct DecTokenArgs {
     const float* vbias;                                   // LM-head bias (slab path)
     const float* cand_val; const int* cand_idx; int ncand;   // per-tile candidates of the fused LM head (ncand > 0)
     const float* cand_sum;                                // scored steps (st.scores set) on the candidate path: the tiles' exp sums
+    const float* top_val; const int* top_idx;             // alternatives steps (st.alt_ids set) on the candidate path: the tiles' four best
     float* x_f32; void* x_t;
     void* cache; uint8_t* cache8; float inv8; long long cstride;   // layer-0 latent cache row (T or e4m3), indexed by row
 };
@@ -996,6 +1006,16 @@ template <typename T, bool FIRST>
 void launch_dec_token(mocr_engine* e, const DecState& st, const DecTokenArgs& a, int n) {
     auto& w = e->w;
     if constexpr (!FIRST) {
+        if (st.alt_ids) {       // token alternatives (with the scores)
+            ProfScope ps(e, "dec_token_topk", 0, (double)n * e->V * 4 * a.nslab);
+            hipLaunchKernelGGL((dec_token_kernel<T, 768, false, true, true>), dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab,
+                               a.slab_stride, a.vbias, e->V, st, w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32,
+                               reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps, reinterpret_cast<T*>(a.cache), a.cstride,
+                               a.ncand ? a.cand_val : nullptr, a.ncand ? a.cand_idx : nullptr, a.ncand, a.cache8, a.inv8,
+                               a.ncand ? a.cand_sum : nullptr, a.ncand ? a.top_val : nullptr, a.ncand ? a.top_idx : nullptr);
+            HIPCHECK(hipGetLastError());
+            return;
+        }
         if (st.scores) {        // token scores: the start step has nothing to score (start_batch zeroes column 0)
             ProfScope ps(e, "dec_token_lse", 0, (double)n * e->V * 4 * a.nslab);
             hipLaunchKernelGGL((dec_token_kernel<T, 768, false, true>), dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab,
@@ -1021,6 +1041,7 @@ void dec_token(mocr_engine* e, const DecState& st, int nslab, int n, int ncand =
     DecTokenArgs a{};
     a.slabs = e->slabs; a.nslab = nslab; a.slab_stride = (long long)e->Bp * e->V; a.vbias = e->w.bv;
     a.cand_val = e->cand_val; a.cand_idx = e->cand_idx; a.ncand = ncand; a.cand_sum = e->cand_sum;
+    a.top_val = e->top_val; a.top_idx = e->top_idx;
     a.x_f32 = e->x_f32; a.x_t = e->x_t;
     a.cache = (lat && !e->fp8attn) ? e->xcache : nullptr;
     a.cache8 = (lat && e->fp8attn) ? e->x8cache : nullptr;
@@ -1402,7 +1423,11 @@ void decode_step(mocr_engine* e, const DecState& st, int n, int t) {
     if (!st.logits_out && !(e->cfg.flags & MOCR_FLAG_NO_FUSED_ARGMAX) && (vt == 64 || vt == 128) &&
         pick_split(e->V, D, 128 / (int)sizeof(T), rn, e->slab_cap / e->Bp) == 1) {
         // (a scored batch - st.scores - also keeps every tile's sum of exp(logit - tile max): EPI_ARGMAX_LSE, same max / column)
-        if (st.scores)
+        // (an alternatives batch - st.alt_ids - every tile's four best as well: EPI_TOPK)
+        if (st.alt_ids)
+            gemm<T>(e, "gemm_dec_vocab_topk", e->z_t, D, w.wv, w.bv, e->cand_val, e->V, nullptr, n, e->V, D, EPI_TOPK, vt, 1, 0,
+                    nullptr, 0, nullptr, 0, e->cand_idx, nullptr, e->cand_sum, e->top_val, e->top_idx);
+        else if (st.scores)
             gemm<T>(e, "gemm_dec_vocab_lse", e->z_t, D, w.wv, w.bv, e->cand_val, e->V, nullptr, n, e->V, D, EPI_ARGMAX_LSE, vt, 1, 0,
                     nullptr, 0, nullptr, 0, e->cand_idx, nullptr, e->cand_sum);
         else
@@ -1446,6 +1471,7 @@ template <typename T> void init_kernel_attrs() {
     set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS_F32>, l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX>, l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_LSE>, l128);
+    set_max_lds(gemm_kernel<T, 128, 128, EPI_TOPK>, l128);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_SLAB, 2>, l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS, 2>, l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_GELU, 2>, l64);
@@ -1454,6 +1480,7 @@ template <typename T> void init_kernel_attrs() {
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_F32, 2>, l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX, 2>, l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_LSE, 2>, l64);
+    set_max_lds(gemm_kernel<T, 64, 64, EPI_TOPK, 2>, l64);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_SLAB, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS_GELU, 4>, 2 * l128);
@@ -1462,6 +1489,7 @@ template <typename T> void init_kernel_attrs() {
     set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS_F32, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_LSE, 4>, 2 * l128);
+    set_max_lds(gemm_kernel<T, 128, 128, EPI_TOPK, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_SLAB, 4>, 2 * l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS, 4>, 2 * l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_GELU, 4>, 2 * l64);
@@ -1470,6 +1498,7 @@ template <typename T> void init_kernel_attrs() {
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_F32, 4>, 2 * l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX, 4>, 2 * l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_LSE, 4>, 2 * l64);
+    set_max_lds(gemm_kernel<T, 64, 64, EPI_TOPK, 4>, 2 * l64);
     set_max_lds(enc_attn_simple_kernel<T>, (200 * 65 + 200 * 64 + 4 * 64 + 4 * 256) * 4);
     set_max_lds(enc_attn2_kernel, EA2_LDS);
     set_max_lds(enc_attn_f32_kernel, EAF_LDS);
@@ -1553,9 +1582,10 @@ hipGraphExec_t decode_graph(mocr_engine* e, const DecState& st, int n, int steps
     const int need = ((t0 + steps + 3) / 4 + 7) / 8;
     const int bucket = need <= 3 ? 3 : need <= 5 ? 5 : need <= 8 ? 8 : 10;
     const int t_hi = std::min(bucket * 32, st.max_len) - 1;      // largest context this bucket covers
-    // ... and by whether the steps are the scored ones (another LM-head epilogue and token kernel): a graph captured for an
-    // unscored batch is never replayed for a scored one, or the reverse
-    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * 2 + (st.scores ? 1 : 0), steps, e->rrows(n));
+    // ... and by the mode of the steps (0 ids only, 1 scored, 2 scored with alternatives: another LM-head epilogue and token
+    // kernel each): a graph captured in one mode is never replayed in another
+    const int mode = st.alt_ids ? 2 : st.scores ? 1 : 0;
+    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * 4 + mode, steps, e->rrows(n));
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) return it->second;
     hipGraph_t g = nullptr;
@@ -1621,6 +1651,17 @@ static int graph_rows(int n, int max_batch) {
     return std::min(round_up(n, q), max_batch);
 }
 
+// The buffers of the token alternatives, for the bound lane: allocated by the first batch that needs them (under the engine
+// lock like every scheduling step, and never inside a graph capture: start_batch captures nothing), so an engine that is
+// never asked keeps the memory footprint it had - default_max_batch sizes batches from the free HBM.
+static void ensure_alt_buffers(mocr_engine* e) {
+    if (e->alt_ids) return;
+    const size_t Bp = (size_t)e->Bp;
+    e->top_val = e->dalloc<float>(Bp * (e->V / 64) * MOCR_ALTERNATIVES); e->top_idx = e->dalloc<int>(Bp * (e->V / 64) * MOCR_ALTERNATIVES);
+    e->alt_logp = e->dalloc<float>(Bp * e->cfg.max_len * MOCR_ALTERNATIVES);
+    e->alt_ids = e->dalloc<int>(Bp * e->cfg.max_len * MOCR_ALTERNATIVES);
+}
+
 template <typename T>
 void start_batch(mocr_engine* e, Lane& L) {
     const int IMG = e->cfg.image_size;
@@ -1655,9 +1696,15 @@ void start_batch(mocr_engine* e, Lane& L) {
     // rows read pad_id (= 0) beyond what the loop writes
     HIPCHECK(hipMemsetAsync(e->ids, 0, (size_t)L.np * e->cfg.max_len * sizeof(int), e->stream));
     // token scores: the batch is scored when one of its jobs asked; the start token and the pad tail score 0
-    L.scored = false;
-    for (const Job& j : L.jobs) L.scored = L.scored || j.out_logp != nullptr;
-    if (L.scored) HIPCHECK(hipMemsetAsync(e->scores, 0, (size_t)L.np * e->cfg.max_len * sizeof(float), e->stream));
+    // (token alternatives: the same, one mode richer; positions the steps do not write read -1 / 0)
+    L.mode = 0;
+    for (const Job& j : L.jobs) L.mode = std::max(L.mode, j.out_alt_ids ? 2 : j.out_logp ? 1 : 0);
+    if (L.mode >= 1) HIPCHECK(hipMemsetAsync(e->scores, 0, (size_t)L.np * e->cfg.max_len * sizeof(float), e->stream));
+    if (L.mode >= 2) {
+        ensure_alt_buffers(e);
+        HIPCHECK(hipMemsetAsync(e->alt_ids, 0xFF, (size_t)L.np * e->cfg.max_len * MOCR_ALTERNATIVES * sizeof(int), e->stream));
+        HIPCHECK(hipMemsetAsync(e->alt_logp, 0, (size_t)L.np * e->cfg.max_len * MOCR_ALTERNATIVES * sizeof(float), e->stream));
+    }
     // The decode steps run on np >= n rows (graph_rows): the padding rows are born finished, emit pad_id and read
     // whatever the workspace holds for them (finite values; no kernel mixes rows).
     DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n);
@@ -1675,6 +1722,11 @@ void finish_batch(mocr_engine* e, Lane& L) {
         HIPCHECK(hipMemcpyAsync(j.out_len, e->len + row0, (size_t)j.n * sizeof(int), kind, e->stream));
         if (j.out_logp)
             HIPCHECK(hipMemcpyAsync(j.out_logp, e->scores + (size_t)row0 * e->cfg.max_len, (size_t)j.n * e->cfg.max_len * sizeof(float), kind, e->stream));
+        if (j.out_alt_ids) {
+            const size_t ld = (size_t)e->cfg.max_len * MOCR_ALTERNATIVES;
+            HIPCHECK(hipMemcpyAsync(j.out_alt_ids, e->alt_ids + row0 * ld, j.n * ld * sizeof(int), kind, e->stream));
+            HIPCHECK(hipMemcpyAsync(j.out_alt_logp, e->alt_logp + row0 * ld, j.n * ld * sizeof(float), kind, e->stream));
+        }
         row0 += j.n;
     }
     L.jobs.clear();
@@ -1743,7 +1795,7 @@ void advance(mocr_engine* e, Lane& L) {
         }
     }
     if (L.t >= L.steps) { finish_batch(e, L); return; }
-    DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n, L.scored);
+    DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n, L.mode);
     // (while rows are leaving, half-length chunks: the count a compaction acts on is at most 4 + 4 steps old instead of 8 + 8;
     // a batch none of whose rows has finished - the synthetic-weights headline - keeps the long chunks)
     const int chunk = L.finishing ? std::min(chunk_steps(L.np), CHUNK / 2) : chunk_steps(L.np);
@@ -2316,9 +2368,17 @@ int mocr_synchronize(mocr_engine* e) {
     });
 }
 
-int mocr_recognize_device_scored(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp) {
+// (the token alternatives come as a pair of outputs)
+static void require_alt_pair(const void* alt_ids, const void* alt_logp) {
+    if ((alt_ids == nullptr) != (alt_logp == nullptr))
+        throw ArgError{"out_alt_ids and out_alt_logp must be both null or both set", MOCR_ERR_ARG};
+}
+
+int mocr_recognize_device_alts(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp,
+                               void* d_out_alt_ids, void* d_out_alt_logp) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
+        require_alt_pair(d_out_alt_ids, d_out_alt_logp);
         require_ready(e, n);
         if (!d_gray || !d_out_ids || !d_out_len) throw ArgError{"null device pointer", MOCR_ERR_ARG};
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -2327,8 +2387,13 @@ int mocr_recognize_device_scored(mocr_engine* e, const void* d_gray, int32_t n, 
         j.n = n; j.max_len = e->gen_max_len;
         j.out_ids = reinterpret_cast<int32_t*>(d_out_ids); j.out_len = reinterpret_cast<int32_t*>(d_out_len); j.out_host = false;
         j.out_logp = reinterpret_cast<float*>(d_out_logp);
+        j.out_alt_ids = reinterpret_cast<int32_t*>(d_out_alt_ids); j.out_alt_logp = reinterpret_cast<float*>(d_out_alt_logp);
         submit(e, j);
     });
+}
+
+int mocr_recognize_device_scored(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp) {
+    return mocr_recognize_device_alts(e, d_gray, n, d_out_ids, d_out_len, d_out_logp, nullptr, nullptr);
 }
 
 int mocr_recognize_device(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len) {
@@ -2337,7 +2402,7 @@ int mocr_recognize_device(mocr_engine* e, const void* d_gray, int32_t n, void* d
 
 static void recognize_host_chunks(mocr_engine* e, const uint8_t* images, int n, int h, int w, int64_t row_stride,
                                   int64_t image_stride, int channels, int max_len, int32_t* out_ids, int32_t* out_len,
-                                  float* out_logp = nullptr) {
+                                  float* out_logp = nullptr, int32_t* out_alt_ids = nullptr, float* out_alt_logp = nullptr) {
     const int IMG = e->cfg.image_size;
     if (h != IMG || w != IMG)
         throw ArgError{"crops must be image_size x image_size (resize with PIL BILINEAR on the caller side)", MOCR_ERR_UNSUPPORTED};
@@ -2351,6 +2416,8 @@ static void recognize_host_chunks(mocr_engine* e, const uint8_t* images, int n, 
         j.n = std::min(e->cfg.max_batch, n - base); j.max_len = max_len;
         j.out_ids = out_ids + (size_t)base * e->cfg.max_len; j.out_len = out_len + base; j.out_host = true;
         j.out_logp = out_logp ? out_logp + (size_t)base * e->cfg.max_len : nullptr;
+        j.out_alt_ids = out_alt_ids ? out_alt_ids + (size_t)base * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
+        j.out_alt_logp = out_alt_ids ? out_alt_logp + (size_t)base * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
         e->pending.push_back(j);
     }
     drive(e);
@@ -2366,15 +2433,22 @@ int mocr_recognize(mocr_engine* e, const uint8_t* images, int32_t n, int32_t h, 
     });
 }
 
-int mocr_recognize_gray_host_scored(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
-                                    int32_t* out_len, float* out_logp) {
+int mocr_recognize_gray_host_alts(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                  int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
+        require_alt_pair(out_alt_ids, out_alt_logp);
         require_ready(e, n, false);
         HIPCHECK(hipSetDevice(e->cfg.device));
         const int IMG = e->cfg.image_size;
-        recognize_host_chunks(e, gray, n, IMG, IMG, IMG, (int64_t)IMG * IMG, 1, max_len_override, out_ids, out_len, out_logp);
+        recognize_host_chunks(e, gray, n, IMG, IMG, IMG, (int64_t)IMG * IMG, 1, max_len_override, out_ids, out_len, out_logp,
+                              out_alt_ids, out_alt_logp);
     });
+}
+
+int mocr_recognize_gray_host_scored(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                    int32_t* out_len, float* out_logp) {
+    return mocr_recognize_gray_host_alts(e, gray, n, max_len_override, out_ids, out_len, out_logp, nullptr, nullptr);
 }
 
 int mocr_recognize_gray_host(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
@@ -2543,7 +2617,8 @@ static void preprocess_images(mocr_engine* e, const mocr_image* imgs, int n, uin
 // the preparation stream) while the lanes decode chunk k; a job's lane stream waits ON THE DEVICE for its chunk's event,
 // so the host never blocks on a preparation.  r02 prepared ALL crops, synchronised, and only then started to decode.
 static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& srcs, const PrepView* views, int n, int32_t* out_ids,
-                               int32_t* out_len, float* out_logp = nullptr) {
+                               int32_t* out_len, float* out_logp = nullptr, int32_t* out_alt_ids = nullptr,
+                               float* out_alt_logp = nullptr) {
     const size_t plane = (size_t)e->cfg.image_size * e->cfg.image_size;
     const int C = std::min(e->cfg.max_batch, 4096), nchunks = (n + C - 1) / C;
     uint8_t* const d_gray = (uint8_t*)e->grow(e->rs_gray, (size_t)n * plane);
@@ -2555,6 +2630,8 @@ static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& sr
         j.n = std::min(C, n - k * C); j.max_len = e->gen_max_len;
         j.out_ids = out_ids + (size_t)k * C * e->cfg.max_len; j.out_len = out_len + (size_t)k * C; j.out_host = true;
         j.out_logp = out_logp ? out_logp + (size_t)k * C * e->cfg.max_len : nullptr;
+        j.out_alt_ids = out_alt_ids ? out_alt_ids + (size_t)k * C * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
+        j.out_alt_logp = out_alt_ids ? out_alt_logp + (size_t)k * C * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
         e->pending.push_back(j);
     };
     std::vector<PrepHold> holds(nchunks);
@@ -2609,10 +2686,11 @@ int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t
     });
 }
 
-int mocr_recognize_images_scored(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
-                                 float* out_logp) {
+int mocr_recognize_images_alts(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                               float* out_logp, int32_t* out_alt_ids, float* out_alt_logp) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
+        require_alt_pair(out_alt_ids, out_alt_logp);
         require_ready(e, n, false);
         if (!images || !out_ids || !out_len) throw ArgError{"null pointer", MOCR_ERR_ARG};
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -2623,8 +2701,13 @@ int mocr_recognize_images_scored(mocr_engine* e, const mocr_image* images, int32
             srcs[i] = source_of(images[i]);
             views[i] = PrepView{i, 0, 0, srcs[i].w, srcs[i].h, srcs[i].rot};
         }
-        prepare_and_decode(e, srcs, views.data(), n, out_ids, out_len, out_logp);
+        prepare_and_decode(e, srcs, views.data(), n, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp);
     });
+}
+
+int mocr_recognize_images_scored(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                                 float* out_logp) {
+    return mocr_recognize_images_alts(e, images, n, out_ids, out_len, out_logp, nullptr, nullptr);
 }
 
 int mocr_recognize_images(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len) {
@@ -2644,10 +2727,12 @@ static bool padded_region(const mocr_region& r, int page_h, int page_w, PrepView
     return true;
 }
 
-int mocr_recognize_regions_scored(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
-                                  int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp) {
+int mocr_recognize_regions_alts(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                float* out_alt_logp) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
+        require_alt_pair(out_alt_ids, out_alt_logp);
         if (!e->committed) throw ArgError{"weights not committed (mocr_commit_weights)", MOCR_ERR_STATE};
         if (!pages || n_pages < 1 || n_regions < 0 || (n_regions > 0 && (!regions || !out_ids || !out_len)))
             throw ArgError{"bad argument", MOCR_ERR_ARG};
@@ -2669,20 +2754,38 @@ int mocr_recognize_regions_scored(mocr_engine* e, const mocr_image* pages, int32
         const int L = e->cfg.max_len, nv = (int)views.size();
         std::vector<int32_t> ids((size_t)nv * L), lens(nv);
         std::vector<float> logp(out_logp ? (size_t)nv * L : 0);
-        if (nv > 0) prepare_and_decode(e, srcs, views.data(), nv, ids.data(), lens.data(), out_logp ? logp.data() : nullptr);
+        const size_t LA = (size_t)L * MOCR_ALTERNATIVES;
+        std::vector<int32_t> alt_ids(out_alt_ids ? (size_t)nv * LA : 0);
+        std::vector<float> alt_logp(out_alt_ids ? (size_t)nv * LA : 0);
+        if (nv > 0)
+            prepare_and_decode(e, srcs, views.data(), nv, ids.data(), lens.data(), out_logp ? logp.data() : nullptr,
+                               out_alt_ids ? alt_ids.data() : nullptr, out_alt_ids ? alt_logp.data() : nullptr);
         for (int i = 0; i < n_regions; ++i) {
             int32_t* row = out_ids + (size_t)i * L;
             if (where[i] < 0) {
                 for (int t = 0; t < L; ++t) row[t] = e->cfg.pad_id;
                 out_len[i] = 0;
                 if (out_logp) std::fill(out_logp + (size_t)i * L, out_logp + (size_t)(i + 1) * L, 0.f);
+                if (out_alt_ids) {
+                    std::fill(out_alt_ids + i * LA, out_alt_ids + (i + 1) * LA, -1);
+                    std::fill(out_alt_logp + i * LA, out_alt_logp + (i + 1) * LA, 0.f);
+                }
             } else {
                 memcpy(row, ids.data() + (size_t)where[i] * L, (size_t)L * sizeof(int32_t));
                 out_len[i] = lens[where[i]];
                 if (out_logp) memcpy(out_logp + (size_t)i * L, logp.data() + (size_t)where[i] * L, (size_t)L * sizeof(float));
+                if (out_alt_ids) {
+                    memcpy(out_alt_ids + i * LA, alt_ids.data() + where[i] * LA, LA * sizeof(int32_t));
+                    memcpy(out_alt_logp + i * LA, alt_logp.data() + where[i] * LA, LA * sizeof(float));
+                }
             }
         }
     });
+}
+
+int mocr_recognize_regions_scored(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                  int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp) {
+    return mocr_recognize_regions_alts(e, pages, n_pages, regions, n_regions, out_ids, out_len, out_logp, nullptr, nullptr);
 }
 
 int mocr_recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions, int32_t n_regions,
@@ -2793,7 +2896,7 @@ int mocr_op_gemm(mocr_engine* e, const void* dA, const void* dW, const float* d_
         HIPCHECK(hipSetDevice(e->cfg.device));
         drive(e);
         e->bind(0);
-        if (epilogue == EPI_PATCH || epilogue == EPI_ARGMAX || epilogue == EPI_ARGMAX_LSE)
+        if (epilogue == EPI_PATCH || epilogue == EPI_ARGMAX || epilogue == EPI_ARGMAX_LSE || epilogue == EPI_TOPK)
             throw ArgError{"EPI_PATCH / EPI_ARGMAX are not exposed through mocr_op_gemm (EPI_ARGMAX: mocr_op_gemm_argmax)", MOCR_ERR_ARG};
         const long long slab = (long long)M * N;
         if (e->cfg.dtype == MOCR_BF16)
@@ -3001,7 +3104,8 @@ int mocr_op_dec_bias_gelu(mocr_engine* e, const float* d_slabs, int32_t nslab, c
     });
 }
 
-int mocr_op_dec_token_scored(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores) {
+int mocr_op_dec_token_topk(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                           const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -3013,7 +3117,8 @@ int mocr_op_dec_token_scored(mocr_engine* e, const mocr_token_args* a, const flo
             !a->x_f32 || !a->x_t || a->ids_ld < 1 || a->max_len < 2 || a->max_len > e->cfg.max_len || e->D != 768 || e->V != 6144 ||
             (!first && a->ncand > 0 && (!a->cand_val || !a->cand_idx)) ||
             (!first && a->ncand <= 0 && (!a->slabs || a->nslab < 1)) || (a->forced && a->forced_T < 1) ||
-            (d_scores && (first || a->forced || (a->ncand > 0 && !d_cand_sum))))
+            (d_scores && (first || a->forced || (a->ncand > 0 && !d_cand_sum))) ||
+            ((d_alt_ids == nullptr) != (d_alt_logp == nullptr)) || (d_alt_ids && (!d_scores || (a->ncand > 0 && (!d_top_val || !d_top_idx)))))
             throw ArgError{"mocr_op_dec_token: bad argument", MOCR_ERR_ARG};
         DecState st{};
         st.n_real = a->n_real;
@@ -3023,11 +3128,13 @@ int mocr_op_dec_token_scored(mocr_engine* e, const mocr_token_args* a, const flo
         st.start_id = e->cfg.start_id; st.eos_id = e->cfg.eos_id; st.pad_id = e->cfg.pad_id;
         st.rowmap = a->rowmap;
         st.scores = d_scores;
+        st.alt_ids = d_alt_ids; st.alt_logp = d_alt_logp;
         DecTokenArgs t{};
         t.slabs = a->slabs; t.nslab = first ? 0 : a->nslab; t.slab_stride = (long long)a->n * e->V;
         t.vbias = a->vbias ? a->vbias : e->w.bv;
         t.cand_val = a->cand_val; t.cand_idx = a->cand_idx; t.ncand = first ? 0 : std::max(a->ncand, 0);
         t.cand_sum = d_cand_sum;
+        t.top_val = d_top_val; t.top_idx = d_top_idx;
         t.x_f32 = a->x_f32; t.x_t = a->x_t;
         if (a->cache && a->cache_fp8) { t.cache8 = reinterpret_cast<uint8_t*>(a->cache); t.inv8 = a->inv_sx; }
         else t.cache = a->cache;
@@ -3041,10 +3148,15 @@ int mocr_op_dec_token_scored(mocr_engine* e, const mocr_token_args* a, const flo
     });
 }
 
+int mocr_op_dec_token_scored(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores) {
+    return mocr_op_dec_token_topk(e, a, d_cand_sum, d_scores, nullptr, nullptr, nullptr, nullptr);
+}
+
 int mocr_op_dec_token(mocr_engine* e, const mocr_token_args* a) { return mocr_op_dec_token_scored(e, a, nullptr, nullptr); }
 
-int mocr_op_gemm_argmax_lse(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
-                            int32_t* d_cand_idx, float* d_cand_sum, int32_t M, int32_t N, int32_t K, int32_t tile) {
+int mocr_op_gemm_topk(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                      int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N, int32_t K,
+                      int32_t tile) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -3052,8 +3164,13 @@ int mocr_op_gemm_argmax_lse(mocr_engine* e, const void* dA, const void* dW, cons
         e->bind(0);
         if (!e->committed || !dA || !dW || !d_bias || !d_cand_val || !d_cand_idx || M < 1 || K < 1 || (tile != 64 && tile != 128))
             throw ArgError{"mocr_op_gemm_argmax: bad argument", MOCR_ERR_ARG};
+        if ((d_top_val == nullptr) != (d_top_idx == nullptr) || (d_top_val && !d_cand_sum))
+            throw ArgError{"mocr_op_gemm_topk: d_top_val / d_top_idx come together and with d_cand_sum", MOCR_ERR_ARG};
         dispatch(e, [&](auto tag) {
-            if (d_cand_sum)
+            if (d_top_val)
+                gemm<decltype(tag)>(e, "op_gemm_topk", dA, K, dW, d_bias, d_cand_val, N, nullptr, M, N, K, EPI_TOPK, tile, 1, 0,
+                                    nullptr, 0, nullptr, 0, d_cand_idx, nullptr, d_cand_sum, d_top_val, d_top_idx);
+            else if (d_cand_sum)
                 gemm<decltype(tag)>(e, "op_gemm_argmax_lse", dA, K, dW, d_bias, d_cand_val, N, nullptr, M, N, K, EPI_ARGMAX_LSE, tile, 1, 0,
                                     nullptr, 0, nullptr, 0, d_cand_idx, nullptr, d_cand_sum);
             else
@@ -3062,6 +3179,11 @@ int mocr_op_gemm_argmax_lse(mocr_engine* e, const void* dA, const void* dW, cons
         });
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
+}
+
+int mocr_op_gemm_argmax_lse(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                            int32_t* d_cand_idx, float* d_cand_sum, int32_t M, int32_t N, int32_t K, int32_t tile) {
+    return mocr_op_gemm_topk(e, dA, dW, d_bias, d_cand_val, d_cand_idx, d_cand_sum, nullptr, nullptr, M, N, K, tile);
 }
 
 int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,

@@ -124,6 +124,11 @@ struct DecState {
     // Token scores (nullable): [B][ids_ld] float32, by row like ids.  scores[row][t + 1] = log-probability of ids[row][t + 1]
     // (fp32 log-softmax of the step's LM-head logits at the chosen token), 0 for a finished row's pad ids.
     float* scores;
+    // Token alternatives (nullable, both or neither; need scores): [B][ids_ld][4] int32 / float32, by row like ids.
+    // alt_ids[row][t + 1][k] = the token with the k-th largest logit of the step that chose ids[row][t + 1] (equal logits: the
+    // lower id first - the greedy pick's order, so entry 0 is that id), alt_logp its fp32 log-softmax; -1 / 0 for a finished row.
+    int* alt_ids;
+    float* alt_logp;
 };
 
 // End of a decode step, one block per sequence:
@@ -135,7 +140,12 @@ struct DecState {
 //   S = sum_j exp(logit_j - max) >= 1, in fp32.  Candidate path: the LM head left cand_sum[c] = sum over tile c of
 //   exp(logit - cand_val[c]) (EPI_ARGMAX_LSE), so S = sum_c cand_sum[c] * exp(cand_val[c] - max).  Slab path: the summed
 //   logits are in this block's registers.  Either way a second short pass once the block knows the max.
-template <typename T, int D, bool FIRST, bool SCORES = false>
+// TOPK = true (st.alt_ids / st.alt_logp set; implies SCORES): also the row's four best logits.  Candidate path: the LM head
+//   left every tile's four best (EPI_TOPK: top_val / top_idx [n][ncand][4]) and the top four of a row are the top four of
+//   the union of its tiles' top fours; slab path: from the 24 logits a thread holds.  A thread-local sorted list (Top4,
+//   kernels_gemm.h), merged across the wave by shuffles and across the four waves through LDS.  Entry k scores
+//   (val_k - max) - log S; entry 0 is written as the score itself, -log S (0 - log S would lose the sign of a -0 score).
+template <typename T, int D, bool FIRST, bool SCORES = false, bool TOPK = false>
 __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict__ slabs, int nslab, long long slab_stride,
                                                         const float* __restrict__ vbias, int V,
                                                         DecState st,
@@ -147,7 +157,10 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                                                         const float* __restrict__ cand_val = nullptr,
                                                         const int* __restrict__ cand_idx = nullptr, int ncand = 0,
                                                         uint8_t* __restrict__ cache8 = nullptr, float inv_sx8 = 0.f,
-                                                        const float* __restrict__ cand_sum = nullptr) {
+                                                        const float* __restrict__ cand_sum = nullptr,
+                                                        const float* __restrict__ top_val = nullptr,
+                                                        const int* __restrict__ top_idx = nullptr) {
+    static_assert(!TOPK || (SCORES && !FIRST), "alternatives come with scores, from the second token on");
     __shared__ float s_val[4];
     __shared__ int s_idx[4];
     __shared__ float s_red[4];
@@ -220,6 +233,39 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
             if (lane == 0) s_red[wave] = es;             // (s_red is free until the embedding's LayerNorm below)
             __syncthreads();
         }
+        Top4 top;
+        if constexpr (TOPK) {
+            __shared__ float s_tv[4][4];
+            __shared__ int s_ti[4][4];
+            top4_clear(top);
+            if (cand_val) {
+                for (int c = tid; c < ncand; c += 256) {
+                    const float4 tv = *reinterpret_cast<const float4*>(top_val + ((size_t)b * ncand + c) * 4);
+                    const int4 ti = *reinterpret_cast<const int4*>(top_idx + ((size_t)b * ncand + c) * 4);
+                    top4_insert(top, tv.x, ti.x); top4_insert(top, tv.y, ti.y);
+                    top4_insert(top, tv.z, ti.z); top4_insert(top, tv.w, ti.w);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NC; ++j) {
+                    const int c = tid * 4 + j * 1024;
+                    top4_insert(top, a[j].x, c); top4_insert(top, a[j].y, c + 1);
+                    top4_insert(top, a[j].z, c + 2); top4_insert(top, a[j].w, c + 3);
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) top4_merge_xor(top, o);
+            if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { s_tv[wave][k] = top.v[k]; s_ti[wave][k] = top.i[k]; }
+            }
+            __syncthreads();
+            if (tid == 0) {
+                for (int w = 1; w < 4; ++w)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) top4_insert(top, s_tv[w][k], s_ti[w][k]);
+            }
+        }
         if (tid == 0) {
             for (int w = 1; w < 4; ++w)
                 if (s_val[w] > best || (s_val[w] == best && s_idx[w] < bi)) { best = s_val[w]; bi = s_idx[w]; }
@@ -230,7 +276,23 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
             if (t + 1 < st.ids_ld) st.ids[(size_t)row * st.ids_ld + t + 1] = tok;
             if constexpr (SCORES) {
                 const float S = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-                if (t + 1 < st.ids_ld) st.scores[(size_t)row * st.ids_ld + t + 1] = fin ? 0.f : -logf(S);
+                const float score = -logf(S);
+                if (t + 1 < st.ids_ld) st.scores[(size_t)row * st.ids_ld + t + 1] = fin ? 0.f : score;
+                if constexpr (TOPK) {
+                    if (t + 1 < st.ids_ld) {
+                        const size_t o = ((size_t)row * st.ids_ld + t + 1) * 4;
+                        int4 ai = make_int4(-1, -1, -1, -1);
+                        float4 al = make_float4(0.f, 0.f, 0.f, 0.f);
+                        if (!fin) {
+                            const float gmax = top.v[0];
+                            ai = make_int4((unsigned)top.i[0] < (unsigned)V ? top.i[0] : -1, (unsigned)top.i[1] < (unsigned)V ? top.i[1] : -1,
+                                           (unsigned)top.i[2] < (unsigned)V ? top.i[2] : -1, (unsigned)top.i[3] < (unsigned)V ? top.i[3] : -1);
+                            al = make_float4(score, (top.v[1] - gmax) + score, (top.v[2] - gmax) + score, (top.v[3] - gmax) + score);
+                        }
+                        *reinterpret_cast<int4*>(st.alt_ids + o) = ai;
+                        *reinterpret_cast<float4*>(st.alt_logp + o) = al;
+                    }
+                }
             }
             if (!fin && !st.forced && (tok == st.eos_id || t + 2 >= st.max_len)) {
                 st.finished[row] = 1;

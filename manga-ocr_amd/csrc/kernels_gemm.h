@@ -35,8 +35,10 @@ enum GemmEpilogue {
     EPI_BIAS_F32 = 5,    // out f32 = acc + bias
     EPI_ARGMAX = 6,      // LM head: per (row, N-tile) the fp32 max of acc + bias and its column (lowest column wins ties):
                          //   out f32 [M][ntn] values, cand_idx int [M][ntn] columns - the logits never go to memory
-    EPI_ARGMAX_LSE = 7   // token scores: EPI_ARGMAX + cand_sum f32 [M][ntn] = the tile's sum of exp(acc + bias - the tile's max),
+    EPI_ARGMAX_LSE = 7,  // token scores: EPI_ARGMAX + cand_sum f32 [M][ntn] = the tile's sum of exp(acc + bias - the tile's max),
                          //   from which the token kernel gets the chosen token's log-probability; the logits still stay in LDS
+    EPI_TOPK = 8         // token alternatives: EPI_ARGMAX_LSE + top_val f32 / top_idx int [M][ntn][4] = the tile's four largest
+                         //   acc + bias and their columns (value descending, lower column first on a tie); entry 0 = the arg-max
 };
 
 struct GemmParams {
@@ -66,6 +68,8 @@ struct GemmParams {
     void* xb;              // fp32-residual GEMM: bf16 copy of the output rows, [M][ldo]
     float ln_eps;
     float* cand_sum;       // EPI_ARGMAX_LSE: [M][ntn] sum of exp(logit - tile max) over the tile's columns
+    float* top_val;        // EPI_TOPK: [M][ntn][4] the tile's four largest logits, descending ...
+    int* top_idx;          // ... and their columns
 };
 
 // Linear tile id -> (tm, tn).  Tiles are ordered column-group by column-group: inside a group of
@@ -147,7 +151,10 @@ __device__ __forceinline__ void gemm_epilogue(const float* sC, const GemmParams&
 // rotation, same swizzle, so as conflict-free as the first walk - and sums exp(v - max) in fp32; cand_sum[m][tile] gets the
 // row's sum (>= 1: the max itself contributes exp(0)).  v = acc + bias is recomputed with the same fp32 add as in the first
 // walk, so v - max is exactly 0 at the winning column and <= 0 everywhere else.
-template <int BM, int BN, int NT, bool SWZ, bool LSE = false>
+// TOPK (EPI_TOPK, implies LSE): the first walk keeps the thread's four best instead of its best (Top4: the same order, so
+// entry 0 is the arg-max the other variants find), the row's threads merge their lists by shuffles, and part 0 also writes
+// the row's list, top_val / top_idx [m][tile][0..3], as two 16-byte stores.
+template <int BM, int BN, int NT, bool SWZ, bool LSE = false, bool TOPK = false>
 __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const GemmParams& p, int m0, int n0, int tid) {
     constexpr int TPRW = NT / BM, CPP = BN / TPRW;
     static_assert(TPRW == 2 || TPRW == 4, "two or four threads per row");
@@ -157,6 +164,25 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const Gemm
     const int rot = 4 * (row % (CPP / 4));
     float best = -INFINITY;
     int bi = 0x7fffffff;
+    Top4 top;
+    if constexpr (TOPK) {
+        static_assert(LSE, "EPI_TOPK keeps the exp sums too");
+        top4_clear(top);
+#pragma unroll 2        // (a short body keeps the registers of the 128 x 128 variants below EPI_ARGMAX_LSE's: DESIGN.md 4.5)
+        for (int q = 0; q < CPP / 4; ++q) {
+            const int pc = part * CPP + ((rot + 4 * q) % CPP);
+            const float4 cv = *reinterpret_cast<const float4*>(&sC[row * BN + pc]);
+            const int n = n0 + (pc ^ sw);
+            const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
+            top4_insert(top, cv.x + bv.x, n);
+            top4_insert(top, cv.y + bv.y, n + 1);
+            top4_insert(top, cv.z + bv.z, n + 2);
+            top4_insert(top, cv.w + bv.w, n + 3);
+        }
+#pragma unroll
+        for (int o = TPRW / 2; o > 0; o >>= 1) top4_merge_xor(top, o);
+        best = top.v[0]; bi = top.i[0];
+    } else {
 #pragma unroll
     for (int q = 0; q < CPP / 4; ++q) {
         const int pc = part * CPP + ((rot + 4 * q) % CPP);          // physical column of this float4
@@ -173,6 +199,7 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const Gemm
         const float ov = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(bi, o, 64);
         if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
     }
     float esum = 0.f;
     if constexpr (LSE) {
@@ -192,6 +219,10 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const Gemm
         reinterpret_cast<float*>(p.out)[c] = best;
         p.cand_idx[c] = bi;
         if constexpr (LSE) p.cand_sum[c] = esum;
+        if constexpr (TOPK) {
+            *reinterpret_cast<float4*>(p.top_val + 4 * c) = make_float4(top.v[0], top.v[1], top.v[2], top.v[3]);
+            *reinterpret_cast<int4*>(p.top_idx + 4 * c) = make_int4(top.i[0], top.i[1], top.i[2], top.i[3]);
+        }
     }
 }
 
@@ -405,6 +436,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
         gemm_epilogue_argmax<BM, BN, 256, SWZ>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_ARGMAX_LSE) {
         gemm_epilogue_argmax<BM, BN, 256, SWZ, true>(sC, p, m0, n0, tid);
+    } else if constexpr (EPI == EPI_TOPK) {
+        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, true>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_BIAS) {
         GemmParams q = p;
         q.out = reinterpret_cast<T*>(p.out) + (size_t)blockIdx.y * p.o_yoff;

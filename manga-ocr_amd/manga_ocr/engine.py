@@ -133,19 +133,34 @@ class Engine:
             d.rotate = int(rotate[i]) if rotate is not None else 0
         return descs, keep
 
-    def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False):
+    def _alt_blocks(self, n: int):
+        """(alt_ids int32, alt_logp float32) [n, max_len, 4] as the engine leaves unwritten positions: -1 / 0"""
+        shape = (n, self.spec.max_len, _capi.ALTERNATIVES)
+        return np.full(shape, -1, dtype=np.int32), np.zeros(shape, dtype=np.float32)
+
+    def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False):
         """Crops of any sizes (list of uint8 [h,w] / [h,w,3] arrays; `bgr`: 3-channel crops are in OpenCV order;
         `rotate`: per crop 0 / 1 (90 degrees clockwise) / 2 (counter-clockwise), applied on the device): luminance
         conversion and the Pillow-exact BILINEAR resize to 224x224 run on the device.
         Returns (ids int32 [n,max_len], lengths int32 [n]); with ``scores=True`` (ids, lengths, logp float32 [n,max_len]):
-        the log-probability of every emitted token, computed on the device (include/mocr.h, "token scores"); same ids."""
+        the log-probability of every emitted token, computed on the device (include/mocr.h, "token scores"); same ids.
+        With ``alternatives=True`` (ids, lengths, logp, alt_ids int32 [n,max_len,4], alt_logp float32 [n,max_len,4]): the four
+        most probable tokens of every position and their log-probabilities (include/mocr.h, "token alternatives"); same ids."""
         if len(images) == 0:
             empty = (np.zeros((0, self.spec.max_len), dtype=np.int32), np.zeros(0, dtype=np.int32))
+            if alternatives:
+                return empty + (np.zeros((0, self.spec.max_len), dtype=np.float32),) + self._alt_blocks(0)
             return empty + (np.zeros((0, self.spec.max_len), dtype=np.float32),) if scores else empty
         descs, keep = self._image_descs(images, bgr, rotate)
         n = len(keep)
         ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
         lens = np.zeros(n, dtype=np.int32)
+        if alternatives:
+            logp = np.zeros((n, self.spec.max_len), dtype=np.float32)
+            alt_ids, alt_logp = self._alt_blocks(n)
+            self._check(self.lib.mocr_recognize_images_alts(self._h, descs, n, _ptr(ids), _ptr(lens), _ptr(logp), _ptr(alt_ids),
+                                                            _ptr(alt_logp)))
+            return ids, lens, logp, alt_ids, alt_logp
         if scores:
             logp = np.zeros((n, self.spec.max_len), dtype=np.float32)
             self._check(self.lib.mocr_recognize_images_scored(self._h, descs, n, _ptr(ids), _ptr(lens), _ptr(logp)))
@@ -153,23 +168,29 @@ class Engine:
         self._check(self.lib.mocr_recognize_images(self._h, descs, n, _ptr(ids), _ptr(lens)))
         return ids, lens
 
-    def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False):
+    def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False):
         """pages: list of uint8 [H,W,3] (or [H,W]) arrays; regions: iterable of (page_index, x, y, w, h) bounding
         rectangles.  Each page is uploaded once; the 8 %-padded, page-clipped crop of every region
         (``src/ui/main_window.py:9530-9540``) is cut on the device.  Returns (ids [n,max_len], lengths [n]);
         a region reduced to a sliver has length 0.  ``scores=True``: (ids, lengths, logp float32 [n,max_len]), a sliver's
-        row all 0."""
+        row all 0.  ``alternatives=True``: (ids, lengths, logp, alt_ids, alt_logp) as for recognize_images, a sliver's rows
+        all -1 / 0."""
         regs = list(regions)
         n = len(regs)
         ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
         lens = np.zeros(n, dtype=np.int32)
-        logp = np.zeros((n, self.spec.max_len), dtype=np.float32) if scores else None
+        logp = np.zeros((n, self.spec.max_len), dtype=np.float32) if (scores or alternatives) else None
+        alt_ids, alt_logp = self._alt_blocks(n) if alternatives else (None, None)
         if n == 0:
-            return (ids, lens, logp) if scores else (ids, lens)
+            return (ids, lens, logp, alt_ids, alt_logp) if alternatives else (ids, lens, logp) if scores else (ids, lens)
         descs, keep = self._image_descs(pages, bgr)
         arr = (_capi.MocrRegion * n)()
         for i, (pg, x, y, w, h) in enumerate(regs):
             arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
+        if alternatives:
+            self._check(self.lib.mocr_recognize_regions_alts(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens), _ptr(logp),
+                                                             _ptr(alt_ids), _ptr(alt_logp)))
+            return ids, lens, logp, alt_ids, alt_logp
         if scores:
             self._check(self.lib.mocr_recognize_regions_scored(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens), _ptr(logp)))
             return ids, lens, logp
@@ -201,9 +222,14 @@ class Engine:
         self._check(self.lib.mocr_preprocess(self._h, descs, len(keep), _ptr(out)))
         return out
 
-    def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None) -> None:
+    def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None, d_out_alt_ids=None, d_out_alt_logp=None) -> None:
         """Asynchronous; all are device buffers (torch CUDA tensors or raw addresses).  ``d_out_logp`` (float32
-        [n,max_len]): also the token log-probabilities."""
+        [n,max_len]): also the token log-probabilities.  ``d_out_alt_ids`` (int32) with ``d_out_alt_logp`` (float32), both
+        [n,max_len,4]: also the token alternatives."""
+        if d_out_alt_ids is not None or d_out_alt_logp is not None:
+            self._check(self.lib.mocr_recognize_device_alts(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len), _ptr(d_out_logp),
+                                                            _ptr(d_out_alt_ids), _ptr(d_out_alt_logp)))
+            return
         if d_out_logp is not None:
             self._check(self.lib.mocr_recognize_device_scored(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len), _ptr(d_out_logp)))
             return
@@ -212,11 +238,17 @@ class Engine:
     def set_generate_max_length(self, max_len: int) -> None:
         self._check(self.lib.mocr_set_generate_max_length(self._h, int(max_len)))
 
-    def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False):
+    def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False, alternatives: bool = False):
         a = np.ascontiguousarray(gray, dtype=np.uint8)
         n = a.shape[0]
         ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
         lens = np.zeros(n, dtype=np.int32)
+        if alternatives:
+            logp = np.zeros((n, self.spec.max_len), dtype=np.float32)
+            alt_ids, alt_logp = self._alt_blocks(n)
+            self._check(self.lib.mocr_recognize_gray_host_alts(self._h, _ptr(a), n, max_len or self.spec.max_len, _ptr(ids), _ptr(lens),
+                                                               _ptr(logp), _ptr(alt_ids), _ptr(alt_logp)))
+            return ids, lens, logp, alt_ids, alt_logp
         if scores:
             logp = np.zeros((n, self.spec.max_len), dtype=np.float32)
             self._check(self.lib.mocr_recognize_gray_host_scored(self._h, _ptr(a), n, max_len or self.spec.max_len, _ptr(ids), _ptr(lens),
@@ -298,6 +330,21 @@ class Engine:
             ftype = dict(_capi.MocrTokenArgs._fields_)[name]
             setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
         self._check(self.lib.mocr_op_dec_token_scored(self._h, C.byref(a), _ptr(d_cand_sum), _ptr(d_scores)))
+
+    def op_dec_token_topk(self, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, **kw) -> None:
+        """The token step with alternatives: op_dec_token_scored plus the tiles' four best (candidate path) and the
+        alternatives rows."""
+        a = _capi.MocrTokenArgs()
+        a.struct_size = C.sizeof(_capi.MocrTokenArgs)
+        for name, value in kw.items():
+            ftype = dict(_capi.MocrTokenArgs._fields_)[name]
+            setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
+        self._check(self.lib.mocr_op_dec_token_topk(self._h, C.byref(a), _ptr(d_cand_sum), _ptr(d_scores), _ptr(d_top_val),
+                                                    _ptr(d_top_idx), _ptr(d_alt_ids), _ptr(d_alt_logp)))
+
+    def op_gemm_topk(self, dA, dW, d_bias, d_cand_val, d_cand_idx, d_cand_sum, d_top_val, d_top_idx, M, N, K, tile) -> None:
+        self._check(self.lib.mocr_op_gemm_topk(self._h, _ptr(dA), _ptr(dW), _ptr(d_bias), _ptr(d_cand_val), _ptr(d_cand_idx),
+                                               _ptr(d_cand_sum), _ptr(d_top_val), _ptr(d_top_idx), M, N, K, tile))
 
     def op_gemm_argmax_lse(self, dA, dW, d_bias, d_cand_val, d_cand_idx, d_cand_sum, M, N, K, tile) -> None:
         self._check(self.lib.mocr_op_gemm_argmax_lse(self._h, _ptr(dA), _ptr(dW), _ptr(d_bias), _ptr(d_cand_val), _ptr(d_cand_idx),

@@ -254,10 +254,13 @@ def deal_sizes(n: int, world: int, max_chunk: int, min_chunk: int = _MIN_CHUNK, 
 
 class MultiGpuEngine:
     """The parent-side handle: same ``recognize_images`` / ``recognize_regions`` surface as ``Engine``; thread-safe.
-    Token scores (``scores=True``) are not implemented here: the exchange with the children ships ids and lengths only."""
+    Token scores (``scores=True``) and token alternatives (``alternatives=True``) are not implemented here: the exchange
+    with the children ships ids and lengths only."""
 
     NO_SCORES = ("token scores are not implemented for several devices (manga_ocr/multi.py ships ids and lengths only): "
                  "construct MangaOcr on one device to use the scored calls")
+    NO_ALTERNATIVES = ("token alternatives are not implemented for several devices (manga_ocr/multi.py ships ids and lengths only): "
+                       "construct MangaOcr on one device to use the *_alternatives calls")
 
     def __init__(self, devices: Sequence[int], factory: Callable = default_engine_factory, factory_args: Optional[dict] = None,
                  backend: str = "nccl", max_chunk: Optional[int] = None, min_chunk: int = _MIN_CHUNK):
@@ -515,7 +518,10 @@ class MultiGpuEngine:
         return descs, off, fill
 
     # ------------------------------------------------------------------ the hot path
-    def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False,
+                         alternatives: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        if alternatives:
+            raise NotImplementedError(self.NO_ALTERNATIVES)
         if scores:
             raise NotImplementedError(self.NO_SCORES)
         n = len(images)
@@ -530,7 +536,10 @@ class MultiGpuEngine:
         descs, size, fill = self._pack(images)
         return self._run(n, size, fill, dict(kind="images", descs=descs, bgr=bool(bgr), rotate=rotate))
 
-    def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False,
+                          alternatives: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        if alternatives:
+            raise NotImplementedError(self.NO_ALTERNATIVES)
         if scores:
             raise NotImplementedError(self.NO_SCORES)
         regs = [tuple(int(v) for v in r) for r in regions]

@@ -17,9 +17,9 @@ import os
 import threading
 import time
 from concurrent.futures import Future
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from pathlib import Path
-from typing import List, Optional, Sequence, Union
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -63,6 +63,9 @@ def to_pixels(img) -> np.ndarray:
     return np.asarray(img, dtype=np.uint8)
 
 
+_ALTERNATIVES = 4      # include/mocr.h MOCR_ALTERNATIVES
+
+
 @dataclass(frozen=True)
 class Recognition:
     """One recognised crop with the recogniser's own confidence (the ``*_scored`` methods of :class:`MangaOcr`).
@@ -70,30 +73,59 @@ class Recognition:
     ``logprobs[k]`` is the natural-log probability the decoder gave ``ids[k + 1]`` - the generated tokens, EOS included;
     the start token is given, not predicted, and carries no score.  ``confidence`` is the geometric-mean token
     probability ``exp(mean(logprobs))``, ``min_prob`` the least certain token's ``exp(min(logprobs))``; both are 0.0 for a
-    region that was never decoded (reduced to a sliver: ``text == ''``, no ids)."""
+    region that was never decoded (reduced to a sliver: ``text == ''``, no ids).
+
+    The ``*_alternatives`` methods also fill ``alt_ids`` int32 ``[len - 1, 4]`` and ``alt_logprobs`` float32 ``[len - 1, 4]``
+    (``None`` otherwise): row ``k`` belongs to ``ids[k + 1]`` like ``logprobs[k]`` and holds the four most probable tokens
+    of that position, most probable first, so ``alt_ids[k, 0] == ids[k + 1]`` and ``alt_logprobs[k, 0] == logprobs[k]``
+    (include/mocr.h, "token alternatives").  ``candidates(k)`` gives them as (token string, probability) pairs."""
     text: str
     ids: np.ndarray
     logprobs: np.ndarray
     confidence: float
     min_prob: float
+    alt_ids: Optional[np.ndarray] = None
+    alt_logprobs: Optional[np.ndarray] = None
+    _vocab: object = field(default=None, repr=False, compare=False)      # what candidates() names the tokens with
 
     @classmethod
-    def from_row(cls, vocab, ids_row: np.ndarray, logp_row: np.ndarray, length: int) -> "Recognition":
-        """A row of the engine's (ids, logp) blocks and its length (0: a sliver region) -> Recognition."""
+    def from_row(cls, vocab, ids_row: np.ndarray, logp_row: np.ndarray, length: int, alt_ids_row: Optional[np.ndarray] = None,
+                 alt_logp_row: Optional[np.ndarray] = None) -> "Recognition":
+        """A row of the engine's (ids, logp[, alt_ids, alt_logp]) blocks and its length (0: a sliver region) -> Recognition."""
         n = int(length)
         ids = np.array(ids_row[:n], dtype=np.int32)
         lp = np.array(logp_row[1:n], dtype=np.float32) if n > 1 else np.zeros(0, dtype=np.float32)
+        alts = {}
+        if alt_ids_row is not None:
+            k = _ALTERNATIVES
+            alts = dict(alt_ids=np.array(alt_ids_row[1:n], dtype=np.int32).reshape(-1, k) if n > 1 else np.zeros((0, k), np.int32),
+                        alt_logprobs=np.array(alt_logp_row[1:n], dtype=np.float32).reshape(-1, k) if n > 1 else np.zeros((0, k), np.float32),
+                        _vocab=vocab)
         if lp.size == 0:
-            return cls("" if n == 0 else ids_to_text(vocab, ids), ids, lp, 0.0, 0.0)
+            return cls("" if n == 0 else ids_to_text(vocab, ids), ids, lp, 0.0, 0.0, **alts)
         lp64 = lp.astype(np.float64)
-        return cls(ids_to_text(vocab, ids), ids, lp, float(np.exp(lp64.mean())), float(np.exp(lp64.min())))
+        return cls(ids_to_text(vocab, ids), ids, lp, float(np.exp(lp64.mean())), float(np.exp(lp64.min())), **alts)
+
+    def candidates(self, k: int) -> List[Tuple[str, float]]:
+        """The four most probable tokens of generated position ``k`` (the one that emitted ``ids[k + 1]``), most probable
+        first: (token as the vocabulary spells it, probability).  Entry 0 is the emitted token.  Needs a result of one of the
+        ``*_alternatives`` methods."""
+        if self.alt_ids is None or self.alt_logprobs is None:
+            raise ValueError("this Recognition carries no alternatives: use MangaOcr.recognize_alternatives and friends")
+        toks = self._vocab.tokens if self._vocab is not None else None
+        out = []
+        for i, lp in zip(self.alt_ids[k].tolist(), self.alt_logprobs[k].astype(np.float64).tolist()):
+            name = toks[i] if toks is not None and 0 <= i < len(toks) else f"[{i}]"
+            out.append((name, float(np.exp(lp))))
+        return out
 
 
 class _Batcher:
     """Coalesces concurrent single-crop requests into engine batches (FIFO, per-request error
     isolation like the reference's worker loop, ``src/core/workers.py:241-244``).  A request may ask for token scores;
     a batch with such a request makes the engine's scored call (the ids do not depend on it), and every caller gets
-    what it asked for: ids, or (ids, logp)."""
+    what it asked for: ids, or (ids, logp).  The same one kind further for token alternatives: the batch makes the richest
+    call any of its requests asked for, and such a caller gets (ids, logp, alt_ids, alt_logp)."""
 
     def __init__(self, engine: Engine, max_batch: int, timeout_ms: float):
         self.engine, self.max_batch, self.timeout = engine, max_batch, timeout_ms / 1000.0
@@ -103,12 +135,12 @@ class _Batcher:
         self._thread = threading.Thread(target=self._run, name="mocr-batcher", daemon=True)
         self._thread.start()
 
-    def submit(self, gray: np.ndarray, scored: bool = False) -> Future:
+    def submit(self, gray: np.ndarray, scored: bool = False, alternatives: bool = False) -> Future:
         f: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
-            self._q.append((gray, f, scored))
+            self._q.append((gray, f, 2 if alternatives else 1 if scored else 0))     # the kind of request
             self._cv.notify()
         return f
 
@@ -127,12 +159,20 @@ class _Batcher:
                     self._cv.wait(left)
                 batch, self._q = self._q[:self.max_batch], self._q[self.max_batch:]
             try:
-                if any(sc for _, _, sc in batch):
+                kind = max(k for _, _, k in batch)
+                logp = alt_ids = alt_logp = None
+                if kind == 2:
+                    ids, lens, logp, alt_ids, alt_logp = self.engine.recognize_images([g for g, _, _ in batch], alternatives=True)
+                elif kind == 1:
                     ids, lens, logp = self.engine.recognize_images([g for g, _, _ in batch], scores=True)
                 else:
-                    (ids, lens), logp = self.engine.recognize_images([g for g, _, _ in batch]), None
-                for i, (_, f, sc) in enumerate(batch):
-                    f.set_result((ids[i, :lens[i]].copy(), logp[i, :lens[i]].copy()) if sc else ids[i, :lens[i]].copy())
+                    ids, lens = self.engine.recognize_images([g for g, _, _ in batch])
+                for i, (_, f, k) in enumerate(batch):
+                    n = lens[i]
+                    if k == 2:
+                        f.set_result((ids[i, :n].copy(), logp[i, :n].copy(), alt_ids[i, :n].copy(), alt_logp[i, :n].copy()))
+                    else:
+                        f.set_result((ids[i, :n].copy(), logp[i, :n].copy()) if k else ids[i, :n].copy())
             except BaseException as exc:  # every waiting caller gets the error; the loop lives on
                 for _, f, _ in batch:
                     if not f.done():
@@ -318,6 +358,53 @@ class MangaOcr:
         """``recognize_regions`` with confidences; a region reduced to a sliver gives text '' and confidence 0.0."""
         self._check_scored()
         return self._recognitions(*self.engine.recognize_regions(list(pages_bgr), list(regions), True, scores=True))
+
+    # ------------------------------------------------------------------ alternatives surface: + the runners-up of every position
+    def _check_alternatives(self) -> None:
+        no = getattr(self.engine, "NO_ALTERNATIVES", None)      # MultiGpuEngine: its exchange ships ids and lengths only
+        if no:
+            raise NotImplementedError(no)
+
+    def _recognitions_alt(self, ids, lens, logp, alt_ids, alt_logp) -> List[Recognition]:
+        return [Recognition.from_row(self.vocab, ids[i], logp[i], lens[i], alt_ids[i], alt_logp[i]) for i in range(len(lens))]
+
+    def recognize_alternatives(self, img_or_path) -> Recognition:
+        """``recognize_scored`` plus, for every generated position, the four most probable tokens and their log-probabilities
+        (``Recognition.alt_ids`` / ``alt_logprobs`` / ``candidates``; include/mocr.h, "token alternatives").  Same text; goes
+        through the same batcher as ``__call__``, and callers of all three kinds may share a batch."""
+        from PIL import Image
+        self._check_alternatives()
+        if isinstance(img_or_path, (str, Path)):
+            img = Image.open(img_or_path)
+        elif isinstance(img_or_path, Image.Image):
+            img = img_or_path
+        else:
+            raise ValueError(f"img_or_path must be a path or PIL.Image, instead got: {img_or_path}")
+        ids, logp, alt_ids, alt_logp = self._batcher.submit(to_pixels(img), alternatives=True).result()
+        return Recognition.from_row(self.vocab, ids, logp, len(ids), alt_ids, alt_logp)
+
+    def recognize_batch_alternatives(self, images: Sequence) -> List[Recognition]:
+        """``recognize_batch`` with confidences and alternatives."""
+        self._check_alternatives()
+        return self._recognitions_alt(*self.engine.recognize_images([to_pixels(im) for im in images], alternatives=True))
+
+    def recognize_bgr_alternatives(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None) -> List[Recognition]:
+        """``recognize_bgr`` with confidences and alternatives."""
+        from .queue_worker import rotation_code
+        self._check_alternatives()
+        crops = list(crops_bgr)
+        rot = None
+        if orientations is not None:
+            if len(orientations) != len(crops):
+                raise ValueError(f"recognize_bgr_alternatives: {len(crops)} crops but {len(orientations)} orientations")
+            rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
+        return self._recognitions_alt(*self.engine.recognize_images(crops, True, rot, alternatives=True))
+
+    def recognize_regions_alternatives(self, pages_bgr: Sequence[np.ndarray], regions) -> List[Recognition]:
+        """``recognize_regions`` with confidences and alternatives; a region reduced to a sliver gives text '', confidence
+        0.0 and empty alternatives."""
+        self._check_alternatives()
+        return self._recognitions_alt(*self.engine.recognize_regions(list(pages_bgr), list(regions), True, alternatives=True))
 
     def recognize_page(self, page_bgr: np.ndarray, regions):
         """``_collect_manga_detections`` for one page: ``regions`` = the detector's (text, polygon) pairs."""
