@@ -204,6 +204,37 @@ int mocr_recognize_regions_alts(mocr_engine* e, const mocr_image* pages, int32_t
                                 int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
                                 float* out_alt_logp);
 
+/* ---- token constraints ------------------------------------------------------------------------
+ * What the caller knows about a crop: a page-number box holds digits, a sound-effect bubble kana, a pipeline never wants
+ * [UNK].  A TOKEN SET is a subset of the vocabulary; a crop decoded under a set behaves as if the logits of every other token
+ * were -inf before the argmax and before the softmax of EVERY step (the greedy loop feeds each token back, and the logits
+ * never reach memory, so the LM-head epilogue and the token kernel apply the set themselves):
+ *   ids           the argmax over the set's tokens, equal logits the lowest allowed id;
+ *   scores        the log-softmax over the set's tokens only (renormalised);
+ *   alternatives  the four best tokens of the set and their renormalised log-probabilities, in the order above, entry 0 the
+ *                 emitted id; a set of fewer than four tokens leaves id -1 / log-probability -inf in the missing entries
+ *                 (a finished row's positions stay -1 / 0).
+ * EOS belongs to every set (the engine adds it); the start token, the pad ids of finished rows and the max_len stop are not
+ * constrained, nor is the teacher-forced hook mocr_decode_logits.  Set MOCR_TOKEN_SET_ALL (0) is the whole vocabulary: a row
+ * under it, also inside a batch with constrained rows, gives ids, scores and alternatives bit-identical to an unconstrained
+ * batch of the same mode and size.  Sets are per crop and one batch may mix any of them (the scheduler merges requests).
+ *
+ * mocr_token_set_create: ids[n_ids] in [0, vocab), duplicates allowed; *out_set = the handle (>= 1), the existing one when a
+ * set of the same content exists.  Sets are immutable and live until mocr_destroy; at most MOCR_MAX_TOKEN_SETS including
+ * set 0.  MOCR_ERR_ARG: n_ids <= 0, an id out of range, the table full.  Thread-safe; needs committed weights.
+ * mocr_token_set_count: handles in use, set 0 included (valid handles are 0 .. count - 1).
+ * The *_constrained entry points: the *_alts twins plus `sets`, a HOST array of one handle per crop (per region), null = all
+ * MOCR_TOKEN_SET_ALL; out_logp / out_alt_ids / out_alt_logp nullable as there.  An unknown handle: MOCR_ERR_ARG. */
+#define MOCR_MAX_TOKEN_SETS 256
+#define MOCR_TOKEN_SET_ALL 0
+int mocr_token_set_create(mocr_engine* e, const int32_t* ids, int32_t n_ids, int32_t* out_set);
+int mocr_token_set_count(mocr_engine* e);
+int mocr_recognize_images_constrained(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                                      float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets);
+int mocr_recognize_regions_constrained(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                       int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                       float* out_alt_logp, const int32_t* sets);
+
 /* Preprocessing only (test hook): out_gray [n, image_size, image_size] uint8 (host) = the plane the encoder sees
  * in each of its three equal input channels before the 1/255 and (x - 0.5)/0.5 scaling. */
 int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t* out_gray);
@@ -221,6 +252,9 @@ int mocr_recognize_device_scored(mocr_engine* e, const void* d_gray, int32_t n, 
  * alternatives, see above; both null or both set). */
 int mocr_recognize_device_alts(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp,
                                void* d_out_alt_ids, void* d_out_alt_logp);
+/* ... plus `sets`, a HOST array of n token-set handles (token constraints, see above; nullable). */
+int mocr_recognize_device_constrained(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
+                                      void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets);
 /* generate(max_length=...) of every batch submitted from now on, whatever the entry point (2 <= max_len <= the
  * engine's max_len; rows are still max_len wide; mocr_recognize_gray_host's own argument overrides it).  The reference always calls generate with 300; a speech bubble is
  * typically ~32 tokens (SURVEY.md §8d reports both regimes). */
@@ -243,6 +277,9 @@ int mocr_recognize_gray_host_scored(mocr_engine* e, const uint8_t* gray, int32_t
                                     int32_t* out_ids, int32_t* out_len, float* out_logp);   /* + token scores (nullable) */
 int mocr_recognize_gray_host_alts(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
                                   int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp);   /* + token alternatives */
+int mocr_recognize_gray_host_constrained(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                         int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
+                                         const int32_t* sets);   /* + token constraints */
 
 /* Single operators on device buffers of the engine's dtype (kernel unit tests). */
 int mocr_op_gemm(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, void* d_out,
@@ -339,6 +376,14 @@ int mocr_op_dec_token_scored(mocr_engine* e, const mocr_token_args* a, const flo
  * step.  d_alt_ids = d_alt_logp = NULL is mocr_op_dec_token_scored. */
 int mocr_op_dec_token_topk(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
                            const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp);
+/* The token step under token sets (token constraints): d_tok_mask uint32 [sets][vocab / 32] (bit v of a set's row = token v is
+ * allowed; the caller keeps EOS in every set) and d_set_of_row int32 [rows], the set of every ROW (slot s decodes row
+ * rowmap[s] under set d_set_of_row[rowmap[s]]).  Runs the ids, scored or alternatives form by which outputs are non-null, as
+ * mocr_op_dec_token_topk does.  Candidate path: the candidates come from mocr_op_gemm_argmax_masked; slab path: the kernel
+ * masks the summed logits itself.  Not with first or forced ids.  d_tok_mask = d_set_of_row = NULL is mocr_op_dec_token_topk. */
+int mocr_op_dec_token_masked(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                             const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
+                             const uint32_t* d_tok_mask, const int32_t* d_set_of_row);
 /* The LM head's fused argmax GEMM (tile 64 or 128, not split): d_cand_val / d_cand_idx [M][N / tile] = per row and N-tile
  * the largest acc + bias and its column (the lowest column on a tie).  dA holds M rounded up to the tile. */
 int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
@@ -353,6 +398,15 @@ int mocr_op_gemm_argmax_lse(mocr_engine* e, const void* dA, const void* dW, cons
 int mocr_op_gemm_topk(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
                       int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N, int32_t K,
                       int32_t tile);
+/* The LM head under token sets (token constraints): GEMM row m is decode slot m = batch row d_rowmap[m] (NULL: m), decoded
+ * under set d_set_of_row[row] of d_tok_mask uint32 [sets][N / 32]; columns outside the set are left out of the max, the exp sum
+ * and the four best.  A tile without an allowed column: d_cand_val -inf, d_cand_idx 0x7fffffff, d_cand_sum exactly 0, list
+ * entries (-inf, 0x7fffffff).  Runs the ids (d_cand_sum NULL), scored or alternatives form by which outputs are non-null.
+ * N a multiple of 128.  d_tok_mask = d_set_of_row = NULL is mocr_op_gemm_topk. */
+int mocr_op_gemm_argmax_masked(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                               int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N,
+                               int32_t K, int32_t tile, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
+                               const int32_t* d_rowmap);
 /* bf16 engines: the small-batch projection (rows <= 32; kernels_smallm.h SmallMParams), one of the (pro, epi) pairs the
  * small-batch decode step launches: (0,0) (1,0) (0,1) (1,2) (1,3). */
 typedef struct mocr_smallm_args {

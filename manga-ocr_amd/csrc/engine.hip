@@ -127,6 +127,8 @@ struct LaneCtx {
     // token alternatives: allocated by the first batch that asks (ensure_alt_buffers), so other engines keep their footprint
     float* top_val = nullptr; int* top_idx = nullptr;   // [Bp][vocab/64][4] per-tile four best logits / columns of the LM head
     int* alt_ids = nullptr; float* alt_logp = nullptr;  // [Bp][max_len][4] the four best tokens of every step / their log-probabilities, by row like ids
+    // token constraints: allocated by the first constrained batch (ensure_set_buffer)
+    int* set_of_row = nullptr;                      // [Bp] constrained batches: the token set of every row, by row like ids
     float *x_f32 = nullptr, *a_f32 = nullptr, *c_f32 = nullptr;
     float* ln_stats = nullptr;                      // small-batch path: (mean, rstd) per row of the three pre-LayerNorm sums, [3][Bp][2]
     void *x_t = nullptr, *a_t = nullptr, *c_t = nullptr, *ctx_t = nullptr, *h_t = nullptr, *z_t = nullptr;
@@ -155,6 +157,7 @@ struct Job {
     int32_t* out_alt_ids = nullptr; // nullable, both or neither (the *_alts entry points): [n][max_len][MOCR_ALTERNATIVES] the four best tokens of
     float* out_alt_logp = nullptr;  // every position and their log-probabilities; host or device like out_ids
     bool out_host = false;
+    std::vector<int32_t> sets;      // token constraints (the *_constrained entry points): one set handle per crop; empty = all MOCR_TOKEN_SET_ALL
 };
 
 struct Lane {
@@ -166,6 +169,9 @@ struct Lane {
     int np0 = 0;                    // np at the start of the batch = its kernel regime
     int mode = 0;                   // the richest kind of request among this batch's jobs: 0 ids only, 1 token log-probabilities (the scored
                                     // LM head / token kernel), 2 also the token alternatives (EPI_TOPK / the TOPK token kernel)
+    bool constrained = false;       // a row of this batch decodes under a token set other than MOCR_TOKEN_SET_ALL: its steps run the
+                                    // masked (EPI_*_M / MASK) form of the mode's LM head and token kernel
+    std::vector<int> h_sets;        // the upload of set_of_row stages from here
     int t = 0, steps = 0, chunk = 0;
     bool finishing = false;         // a flag of this batch has reported a finished row: rows are leaving, chunks get shorter
     bool flag_pending[2] = {false, false};
@@ -214,7 +220,12 @@ struct mocr_engine : LaneCtx {
     size_t esz = 2;
     std::vector<Lane> lanes;
     std::vector<Job> pending;
-    // decode-step HIP graphs, keyed by (lane, rows, (max_len, context bucket, mode 0 / 1 / 2), steps per graph)
+    // token sets (mocr_token_set_create): immutable rows of a device bit table [MOCR_MAX_TOKEN_SETS][V / 32], row 0 all ones;
+    // the table is allocated by the first set, the host copies serve the lookup by content and the handle check
+    unsigned* tok_table = nullptr;
+    std::vector<std::vector<uint32_t>> tok_sets;
+    std::map<std::vector<uint32_t>, int> tok_index;
+    // decode-step HIP graphs, keyed by (lane, rows, (max_len, context bucket, constrained, mode 0 / 1 / 2), steps per graph)
     std::map<std::tuple<int, int, int, int, int>, hipGraphExec_t> graphs;      // + the regime
     void bind(int i) { static_cast<LaneCtx&>(*this) = lanes[i].ctx; }
     void unbind(int i) { lanes[i].ctx = static_cast<LaneCtx&>(*this); }
@@ -372,6 +383,9 @@ void launch_gemm_epi(mocr_engine* e, const GemmParams& p, int epi, int split, in
         case EPI_ARGMAX: launch_gemm_t<T, BM, BN, EPI_ARGMAX>(e, p, split, ybatch); break;
         case EPI_ARGMAX_LSE: launch_gemm_t<T, BM, BN, EPI_ARGMAX_LSE>(e, p, split, ybatch); break;
         case EPI_TOPK: launch_gemm_t<T, BM, BN, EPI_TOPK>(e, p, split, ybatch); break;
+        case EPI_ARGMAX_M: launch_gemm_t<T, BM, BN, EPI_ARGMAX_M>(e, p, split, ybatch); break;
+        case EPI_ARGMAX_LSE_M: launch_gemm_t<T, BM, BN, EPI_ARGMAX_LSE_M>(e, p, split, ybatch); break;
+        case EPI_TOPK_M: launch_gemm_t<T, BM, BN, EPI_TOPK_M>(e, p, split, ybatch); break;
         default: throw ArgError{"unknown GEMM epilogue", MOCR_ERR_ARG};
     }
 }
@@ -555,12 +569,15 @@ struct HeadBatch { int heads = 1; long long a_yoff = 0, w_yoff = 0, o_yoff = 0, 
 // LayerNorm folded into the persistent encoder GEMMs (tile code 4096; kernels_gemm_pers.h LNF).  EPI_BIAS_RESID: `part` and
 // `xb` are written; EPI_BIAS / EPI_BIAS_GELU: `part` and `csum` are read (W and bias are the folded ones).
 struct LnFold { float* part = nullptr; const float* csum = nullptr; void* xb = nullptr; };
+// Token constraints (EPI_*_M): the set table, the set of every batch row and the slot -> row map (kernels_gemm.h GemmParams)
+struct TokMask { const unsigned* table = nullptr; const int* set_of_row = nullptr; const int* rowmap = nullptr; };
 
 template <typename T>
 void gemm(mocr_engine* e, const char* name, const void* A, int lda, const void* W, const float* bias, void* out, int ldo,
           const float* resid, int M, int N, int K, int epi, int tile, int split, long long slab_stride = 0,
           const float* pos = nullptr, int patches = 0, const HeadBatch* hb = nullptr, int group_n = 0, int* cand_idx = nullptr,
-          const LnFold* lnf = nullptr, float* cand_sum = nullptr, float* top_val = nullptr, int* top_idx = nullptr) {
+          const LnFold* lnf = nullptr, float* cand_sum = nullptr, float* top_val = nullptr, int* top_idx = nullptr,
+          const TokMask* tm = nullptr) {
     const int kt = 128 / (int)sizeof(T);
     if (N % (tile >= 1024 ? 256 : tile >= 256 ? 128 : std::max(tile, 1)) || K % (kt * split) || (split > 1 && epi != EPI_SLAB) ||
         (tile >= 256 && (sizeof(T) != 2 || split != 1)))
@@ -568,6 +585,9 @@ void gemm(mocr_engine* e, const char* name, const void* A, int lda, const void* 
     GemmParams p{};
     p.A = A; p.W = W; p.bias = bias; p.out = out; p.resid = resid; p.pos = pos; p.cand_idx = cand_idx; p.cand_sum = cand_sum;
     p.top_val = top_val; p.top_idx = top_idx;
+    if ((epi == EPI_ARGMAX_M || epi == EPI_ARGMAX_LSE_M || epi == EPI_TOPK_M) != (tm != nullptr) || (tm && (!tm->table || !tm->set_of_row)))
+        throw ArgError{std::string("the masked LM-head epilogues come with a token-set table: ") + name, MOCR_ERR_ARG};
+    if (tm) { p.tok_mask = tm->table; p.set_of_row = tm->set_of_row; p.rowmap = tm->rowmap; }
     p.M = M; p.N = N; p.lda = lda; p.ldw = K; p.ldo = ldo;
     int ybatch = 1;
     if (hb) {
@@ -978,7 +998,7 @@ void launch_dec_bias_gelu(mocr_engine* e, const float* slabs, int nslab, long lo
 }
 
 static DecState make_state(mocr_engine* e, int max_len, const int* forced, int forced_T, float* logits_out, int n_real,
-                           int mode = 0) {
+                           int mode = 0, bool constrained = false) {
     DecState st{};
     st.n_real = n_real;
     st.ids = e->ids; st.step = e->step; st.finished = e->finished; st.len = e->len; st.n_unfinished = e->n_unf;
@@ -988,6 +1008,7 @@ static DecState make_state(mocr_engine* e, int max_len, const int* forced, int f
     st.rowmap = e->rowmap;
     st.scores = mode >= 1 ? e->scores : nullptr;
     st.alt_ids = mode >= 2 ? e->alt_ids : nullptr; st.alt_logp = mode >= 2 ? e->alt_logp : nullptr;
+    st.tok_mask = constrained ? e->tok_table : nullptr; st.set_of_row = constrained ? e->set_of_row : nullptr;
     return st;
 }
 
@@ -1006,6 +1027,21 @@ template <typename T, bool FIRST>
 void launch_dec_token(mocr_engine* e, const DecState& st, const DecTokenArgs& a, int n) {
     auto& w = e->w;
     if constexpr (!FIRST) {
+        if (st.tok_mask) {      // token constraints: the MASK form of the mode's kernel
+            ProfScope ps(e, st.alt_ids ? "dec_token_topk_m" : st.scores ? "dec_token_lse_m" : "dec_token_m", 0, (double)n * e->V * 4 * a.nslab);
+            auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab,
+                                   a.slab_stride, a.vbias, e->V, st, w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32,
+                                   reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps, reinterpret_cast<T*>(a.cache), a.cstride,
+                                   a.ncand ? a.cand_val : nullptr, a.ncand ? a.cand_idx : nullptr, a.ncand, a.cache8, a.inv8,
+                                   a.ncand ? a.cand_sum : nullptr, a.ncand ? a.top_val : nullptr, a.ncand ? a.top_idx : nullptr);
+            };
+            if (st.alt_ids) launch(dec_token_kernel<T, 768, false, true, true, true>);
+            else if (st.scores) launch(dec_token_kernel<T, 768, false, true, false, true>);
+            else launch(dec_token_kernel<T, 768, false, false, false, true>);
+            HIPCHECK(hipGetLastError());
+            return;
+        }
         if (st.alt_ids) {       // token alternatives (with the scores)
             ProfScope ps(e, "dec_token_topk", 0, (double)n * e->V * 4 * a.nslab);
             hipLaunchKernelGGL((dec_token_kernel<T, 768, false, true, true>), dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab,
@@ -1424,7 +1460,13 @@ void decode_step(mocr_engine* e, const DecState& st, int n, int t) {
         pick_split(e->V, D, 128 / (int)sizeof(T), rn, e->slab_cap / e->Bp) == 1) {
         // (a scored batch - st.scores - also keeps every tile's sum of exp(logit - tile max): EPI_ARGMAX_LSE, same max / column)
         // (an alternatives batch - st.alt_ids - every tile's four best as well: EPI_TOPK)
-        if (st.alt_ids)
+        // (a constrained batch - st.tok_mask - the masked form of its mode's epilogue: EPI_*_M)
+        if (st.tok_mask) {
+            const TokMask tm{st.tok_mask, st.set_of_row, st.rowmap};
+            gemm<T>(e, "gemm_dec_vocab_m", e->z_t, D, w.wv, w.bv, e->cand_val, e->V, nullptr, n, e->V, D,
+                    st.alt_ids ? EPI_TOPK_M : st.scores ? EPI_ARGMAX_LSE_M : EPI_ARGMAX_M, vt, 1, 0, nullptr, 0, nullptr, 0, e->cand_idx,
+                    nullptr, st.scores ? e->cand_sum : nullptr, st.alt_ids ? e->top_val : nullptr, st.alt_ids ? e->top_idx : nullptr, &tm);
+        } else if (st.alt_ids)
             gemm<T>(e, "gemm_dec_vocab_topk", e->z_t, D, w.wv, w.bv, e->cand_val, e->V, nullptr, n, e->V, D, EPI_TOPK, vt, 1, 0,
                     nullptr, 0, nullptr, 0, e->cand_idx, nullptr, e->cand_sum, e->top_val, e->top_idx);
         else if (st.scores)
@@ -1472,6 +1514,9 @@ template <typename T> void init_kernel_attrs() {
     set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX>, l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_LSE>, l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_TOPK>, l128);
+    set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_M>, l128);
+    set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_LSE_M>, l128);
+    set_max_lds(gemm_kernel<T, 128, 128, EPI_TOPK_M>, l128);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_SLAB, 2>, l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS, 2>, l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_GELU, 2>, l64);
@@ -1481,6 +1526,9 @@ template <typename T> void init_kernel_attrs() {
     set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX, 2>, l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_LSE, 2>, l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_TOPK, 2>, l64);
+    set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_M, 2>, l64);
+    set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_LSE_M, 2>, l64);
+    set_max_lds(gemm_kernel<T, 64, 64, EPI_TOPK_M, 2>, l64);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_SLAB, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS_GELU, 4>, 2 * l128);
@@ -1490,6 +1538,9 @@ template <typename T> void init_kernel_attrs() {
     set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_LSE, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 128, 128, EPI_TOPK, 4>, 2 * l128);
+    set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_M, 4>, 2 * l128);
+    set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_LSE_M, 4>, 2 * l128);
+    set_max_lds(gemm_kernel<T, 128, 128, EPI_TOPK_M, 4>, 2 * l128);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_SLAB, 4>, 2 * l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS, 4>, 2 * l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_GELU, 4>, 2 * l64);
@@ -1499,6 +1550,9 @@ template <typename T> void init_kernel_attrs() {
     set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX, 4>, 2 * l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_LSE, 4>, 2 * l64);
     set_max_lds(gemm_kernel<T, 64, 64, EPI_TOPK, 4>, 2 * l64);
+    set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_M, 4>, 2 * l64);
+    set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_LSE_M, 4>, 2 * l64);
+    set_max_lds(gemm_kernel<T, 64, 64, EPI_TOPK_M, 4>, 2 * l64);
     set_max_lds(enc_attn_simple_kernel<T>, (200 * 65 + 200 * 64 + 4 * 64 + 4 * 256) * 4);
     set_max_lds(enc_attn2_kernel, EA2_LDS);
     set_max_lds(enc_attn_f32_kernel, EAF_LDS);
@@ -1584,8 +1638,9 @@ hipGraphExec_t decode_graph(mocr_engine* e, const DecState& st, int n, int steps
     const int t_hi = std::min(bucket * 32, st.max_len) - 1;      // largest context this bucket covers
     // ... and by the mode of the steps (0 ids only, 1 scored, 2 scored with alternatives: another LM-head epilogue and token
     // kernel each): a graph captured in one mode is never replayed in another
-    const int mode = st.alt_ids ? 2 : st.scores ? 1 : 0;
-    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * 4 + mode, steps, e->rrows(n));
+    // ... and by whether they are the constrained ones (the masked forms of both)
+    const int mode = (st.alt_ids ? 2 : st.scores ? 1 : 0) + (st.tok_mask ? 4 : 0);
+    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * 8 + mode, steps, e->rrows(n));
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) return it->second;
     hipGraph_t g = nullptr;
@@ -1662,6 +1717,12 @@ static void ensure_alt_buffers(mocr_engine* e) {
     e->alt_ids = e->dalloc<int>(Bp * e->cfg.max_len * MOCR_ALTERNATIVES);
 }
 
+// The set of every row of a constrained batch, for the bound lane: allocated by the first constrained batch, like the
+// alternatives buffers.
+static void ensure_set_buffer(mocr_engine* e) {
+    if (!e->set_of_row) e->set_of_row = e->dalloc<int>((size_t)e->Bp);
+}
+
 template <typename T>
 void start_batch(mocr_engine* e, Lane& L) {
     const int IMG = e->cfg.image_size;
@@ -1704,6 +1765,21 @@ void start_batch(mocr_engine* e, Lane& L) {
         ensure_alt_buffers(e);
         HIPCHECK(hipMemsetAsync(e->alt_ids, 0xFF, (size_t)L.np * e->cfg.max_len * MOCR_ALTERNATIVES * sizeof(int), e->stream));
         HIPCHECK(hipMemsetAsync(e->alt_logp, 0, (size_t)L.np * e->cfg.max_len * MOCR_ALTERNATIVES * sizeof(float), e->stream));
+    }
+    // token constraints: the batch is constrained when a row of one of its jobs has a set other than MOCR_TOKEN_SET_ALL; the
+    // merged rows' sets go up before the first decode graph (the padding rows and the rows of unconstrained jobs: set 0)
+    L.constrained = false;
+    for (const Job& j : L.jobs)
+        for (int32_t h : j.sets) L.constrained = L.constrained || h != MOCR_TOKEN_SET_ALL;
+    if (L.constrained) {
+        ensure_set_buffer(e);
+        L.h_sets.assign((size_t)L.np, MOCR_TOKEN_SET_ALL);
+        int r0 = 0;
+        for (const Job& j : L.jobs) {
+            std::copy(j.sets.begin(), j.sets.end(), L.h_sets.begin() + r0);
+            r0 += j.n;
+        }
+        HIPCHECK(hipMemcpyAsync(e->set_of_row, L.h_sets.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
     }
     // The decode steps run on np >= n rows (graph_rows): the padding rows are born finished, emit pad_id and read
     // whatever the workspace holds for them (finite values; no kernel mixes rows).
@@ -1795,7 +1871,7 @@ void advance(mocr_engine* e, Lane& L) {
         }
     }
     if (L.t >= L.steps) { finish_batch(e, L); return; }
-    DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n, L.mode);
+    DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n, L.mode, L.constrained);
     // (while rows are leaving, half-length chunks: the count a compaction acts on is at most 4 + 4 steps old instead of 8 + 8;
     // a batch none of whose rows has finished - the synthetic-weights headline - keeps the long chunks)
     const int chunk = L.finishing ? std::min(chunk_steps(L.np), CHUNK / 2) : chunk_steps(L.np);
@@ -2368,18 +2444,77 @@ int mocr_synchronize(mocr_engine* e) {
     });
 }
 
+// ---- token constraints ------------------------------------------------------------------------
+static int token_set_count(const mocr_engine* e) { return std::max<int>(1, (int)e->tok_sets.size()); }
+
+// one handle per crop (null: every crop MOCR_TOKEN_SET_ALL), each a set this engine has created
+static void require_sets(const mocr_engine* e, const int32_t* sets, int n) {
+    if (!sets) return;
+    const int count = token_set_count(e);
+    for (int i = 0; i < n; ++i)
+        if (sets[i] < 0 || sets[i] >= count) throw ArgError{"unknown token set handle (mocr_token_set_create)", MOCR_ERR_ARG};
+}
+
+// rows [base, base + n) of a request's handles, for the job that decodes them (empty: all MOCR_TOKEN_SET_ALL)
+static std::vector<int32_t> job_sets(const int32_t* sets, size_t base, int n) {
+    if (!sets) return {};
+    std::vector<int32_t> v(sets + base, sets + base + n);
+    for (int32_t h : v)
+        if (h != MOCR_TOKEN_SET_ALL) return v;
+    return {};
+}
+
+int mocr_token_set_create(mocr_engine* e, const int32_t* ids, int32_t n_ids, int32_t* out_set) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (!e->committed) throw ArgError{"weights not committed (mocr_commit_weights)", MOCR_ERR_STATE};
+        if (!ids || n_ids <= 0 || !out_set || e->V % 32) throw ArgError{"mocr_token_set_create: bad argument", MOCR_ERR_ARG};
+        const size_t words = (size_t)e->V / 32;
+        std::vector<uint32_t> bits(words, 0u);
+        for (int i = 0; i < n_ids; ++i) {
+            if (ids[i] < 0 || ids[i] >= e->V) throw ArgError{"mocr_token_set_create: token id outside the vocabulary", MOCR_ERR_ARG};
+            bits[ids[i] >> 5] |= 1u << (ids[i] & 31);
+        }
+        const int eos = e->cfg.eos_id;       // a recogniser that cannot stop is useless: EOS is in every set
+        if (eos >= 0 && eos < e->V) bits[eos >> 5] |= 1u << (eos & 31);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        if (!e->tok_table) {
+            e->tok_table = e->dalloc<unsigned>((size_t)MOCR_MAX_TOKEN_SETS * words);
+            e->tok_sets.push_back(std::vector<uint32_t>(words, 0xffffffffu));        // set 0: the whole vocabulary
+            e->tok_index[e->tok_sets[0]] = MOCR_TOKEN_SET_ALL;
+            HIPCHECK(hipMemcpy(e->tok_table, e->tok_sets[0].data(), words * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
+        const auto it = e->tok_index.find(bits);
+        if (it != e->tok_index.end()) { *out_set = it->second; return; }
+        if ((int)e->tok_sets.size() >= MOCR_MAX_TOKEN_SETS) throw ArgError{"mocr_token_set_create: the set table is full", MOCR_ERR_ARG};
+        // a fresh table row: no queued or running batch can hold this handle yet, so the copy races with nothing
+        const int h = (int)e->tok_sets.size();
+        HIPCHECK(hipMemcpy(e->tok_table + (size_t)h * words, bits.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice));
+        e->tok_sets.push_back(bits);
+        e->tok_index[bits] = h;
+        *out_set = h;
+    });
+}
+
+int mocr_token_set_count(mocr_engine* e) {
+    if (!e) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return token_set_count(e);
+}
+
 // (the token alternatives come as a pair of outputs)
 static void require_alt_pair(const void* alt_ids, const void* alt_logp) {
     if ((alt_ids == nullptr) != (alt_logp == nullptr))
         throw ArgError{"out_alt_ids and out_alt_logp must be both null or both set", MOCR_ERR_ARG};
 }
 
-int mocr_recognize_device_alts(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp,
-                               void* d_out_alt_ids, void* d_out_alt_logp) {
+int mocr_recognize_device_constrained(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
+                                      void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_alt_pair(d_out_alt_ids, d_out_alt_logp);
         require_ready(e, n);
+        require_sets(e, sets, n);
         if (!d_gray || !d_out_ids || !d_out_len) throw ArgError{"null device pointer", MOCR_ERR_ARG};
         HIPCHECK(hipSetDevice(e->cfg.device));
         Job j;
@@ -2388,8 +2523,14 @@ int mocr_recognize_device_alts(mocr_engine* e, const void* d_gray, int32_t n, vo
         j.out_ids = reinterpret_cast<int32_t*>(d_out_ids); j.out_len = reinterpret_cast<int32_t*>(d_out_len); j.out_host = false;
         j.out_logp = reinterpret_cast<float*>(d_out_logp);
         j.out_alt_ids = reinterpret_cast<int32_t*>(d_out_alt_ids); j.out_alt_logp = reinterpret_cast<float*>(d_out_alt_logp);
+        j.sets = job_sets(sets, 0, n);
         submit(e, j);
     });
+}
+
+int mocr_recognize_device_alts(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp,
+                               void* d_out_alt_ids, void* d_out_alt_logp) {
+    return mocr_recognize_device_constrained(e, d_gray, n, d_out_ids, d_out_len, d_out_logp, d_out_alt_ids, d_out_alt_logp, nullptr);
 }
 
 int mocr_recognize_device_scored(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp) {
@@ -2402,7 +2543,8 @@ int mocr_recognize_device(mocr_engine* e, const void* d_gray, int32_t n, void* d
 
 static void recognize_host_chunks(mocr_engine* e, const uint8_t* images, int n, int h, int w, int64_t row_stride,
                                   int64_t image_stride, int channels, int max_len, int32_t* out_ids, int32_t* out_len,
-                                  float* out_logp = nullptr, int32_t* out_alt_ids = nullptr, float* out_alt_logp = nullptr) {
+                                  float* out_logp = nullptr, int32_t* out_alt_ids = nullptr, float* out_alt_logp = nullptr,
+                                  const int32_t* sets = nullptr) {
     const int IMG = e->cfg.image_size;
     if (h != IMG || w != IMG)
         throw ArgError{"crops must be image_size x image_size (resize with PIL BILINEAR on the caller side)", MOCR_ERR_UNSUPPORTED};
@@ -2418,6 +2560,7 @@ static void recognize_host_chunks(mocr_engine* e, const uint8_t* images, int n, 
         j.out_logp = out_logp ? out_logp + (size_t)base * e->cfg.max_len : nullptr;
         j.out_alt_ids = out_alt_ids ? out_alt_ids + (size_t)base * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
         j.out_alt_logp = out_alt_ids ? out_alt_logp + (size_t)base * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
+        j.sets = job_sets(sets, (size_t)base, j.n);
         e->pending.push_back(j);
     }
     drive(e);
@@ -2433,17 +2576,25 @@ int mocr_recognize(mocr_engine* e, const uint8_t* images, int32_t n, int32_t h, 
     });
 }
 
-int mocr_recognize_gray_host_alts(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
-                                  int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp) {
+int mocr_recognize_gray_host_constrained(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                         int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
+                                         const int32_t* sets) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_alt_pair(out_alt_ids, out_alt_logp);
         require_ready(e, n, false);
+        require_sets(e, sets, n);
         HIPCHECK(hipSetDevice(e->cfg.device));
         const int IMG = e->cfg.image_size;
         recognize_host_chunks(e, gray, n, IMG, IMG, IMG, (int64_t)IMG * IMG, 1, max_len_override, out_ids, out_len, out_logp,
-                              out_alt_ids, out_alt_logp);
+                              out_alt_ids, out_alt_logp, sets);
     });
+}
+
+int mocr_recognize_gray_host_alts(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                  int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp) {
+    return mocr_recognize_gray_host_constrained(e, gray, n, max_len_override, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp,
+                                                nullptr);
 }
 
 int mocr_recognize_gray_host_scored(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
@@ -2618,7 +2769,7 @@ static void preprocess_images(mocr_engine* e, const mocr_image* imgs, int n, uin
 // so the host never blocks on a preparation.  r02 prepared ALL crops, synchronised, and only then started to decode.
 static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& srcs, const PrepView* views, int n, int32_t* out_ids,
                                int32_t* out_len, float* out_logp = nullptr, int32_t* out_alt_ids = nullptr,
-                               float* out_alt_logp = nullptr) {
+                               float* out_alt_logp = nullptr, const int32_t* sets = nullptr) {
     const size_t plane = (size_t)e->cfg.image_size * e->cfg.image_size;
     const int C = std::min(e->cfg.max_batch, 4096), nchunks = (n + C - 1) / C;
     uint8_t* const d_gray = (uint8_t*)e->grow(e->rs_gray, (size_t)n * plane);
@@ -2632,6 +2783,7 @@ static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& sr
         j.out_logp = out_logp ? out_logp + (size_t)k * C * e->cfg.max_len : nullptr;
         j.out_alt_ids = out_alt_ids ? out_alt_ids + (size_t)k * C * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
         j.out_alt_logp = out_alt_ids ? out_alt_logp + (size_t)k * C * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
+        j.sets = job_sets(sets, (size_t)k * C, j.n);
         e->pending.push_back(j);
     };
     std::vector<PrepHold> holds(nchunks);
@@ -2686,12 +2838,13 @@ int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t
     });
 }
 
-int mocr_recognize_images_alts(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
-                               float* out_logp, int32_t* out_alt_ids, float* out_alt_logp) {
+int mocr_recognize_images_constrained(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                                      float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_alt_pair(out_alt_ids, out_alt_logp);
         require_ready(e, n, false);
+        require_sets(e, sets, n);
         if (!images || !out_ids || !out_len) throw ArgError{"null pointer", MOCR_ERR_ARG};
         HIPCHECK(hipSetDevice(e->cfg.device));
         drive(e);
@@ -2701,8 +2854,13 @@ int mocr_recognize_images_alts(mocr_engine* e, const mocr_image* images, int32_t
             srcs[i] = source_of(images[i]);
             views[i] = PrepView{i, 0, 0, srcs[i].w, srcs[i].h, srcs[i].rot};
         }
-        prepare_and_decode(e, srcs, views.data(), n, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp);
+        prepare_and_decode(e, srcs, views.data(), n, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, sets);
     });
+}
+
+int mocr_recognize_images_alts(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                               float* out_logp, int32_t* out_alt_ids, float* out_alt_logp) {
+    return mocr_recognize_images_constrained(e, images, n, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, nullptr);
 }
 
 int mocr_recognize_images_scored(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
@@ -2727,12 +2885,13 @@ static bool padded_region(const mocr_region& r, int page_h, int page_w, PrepView
     return true;
 }
 
-int mocr_recognize_regions_alts(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
-                                int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
-                                float* out_alt_logp) {
+int mocr_recognize_regions_constrained(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                       int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                       float* out_alt_logp, const int32_t* sets) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_alt_pair(out_alt_ids, out_alt_logp);
+        require_sets(e, sets, std::max(n_regions, 0));
         if (!e->committed) throw ArgError{"weights not committed (mocr_commit_weights)", MOCR_ERR_STATE};
         if (!pages || n_pages < 1 || n_regions < 0 || (n_regions > 0 && (!regions || !out_ids || !out_len)))
             throw ArgError{"bad argument", MOCR_ERR_ARG};
@@ -2743,6 +2902,7 @@ int mocr_recognize_regions_alts(mocr_engine* e, const mocr_image* pages, int32_t
         for (int i = 0; i < n_pages; ++i) srcs[i] = source_of(pages[i]);
         std::vector<PrepView> views;
         std::vector<int> where(n_regions, -1);          // region -> its row among the recognised crops (-1: sliver)
+        std::vector<int32_t> view_sets;                 // the recognised crops' token sets
         for (int i = 0; i < n_regions; ++i) {
             const mocr_region& r = regions[i];
             if (r.page < 0 || r.page >= n_pages) throw ArgError{"region of an unknown page", MOCR_ERR_ARG};
@@ -2750,6 +2910,7 @@ int mocr_recognize_regions_alts(mocr_engine* e, const mocr_image* pages, int32_t
             if (!padded_region(r, srcs[r.page].h, srcs[r.page].w, v)) continue;
             where[i] = (int)views.size();
             views.push_back(v);
+            if (sets) view_sets.push_back(sets[i]);
         }
         const int L = e->cfg.max_len, nv = (int)views.size();
         std::vector<int32_t> ids((size_t)nv * L), lens(nv);
@@ -2759,7 +2920,8 @@ int mocr_recognize_regions_alts(mocr_engine* e, const mocr_image* pages, int32_t
         std::vector<float> alt_logp(out_alt_ids ? (size_t)nv * LA : 0);
         if (nv > 0)
             prepare_and_decode(e, srcs, views.data(), nv, ids.data(), lens.data(), out_logp ? logp.data() : nullptr,
-                               out_alt_ids ? alt_ids.data() : nullptr, out_alt_ids ? alt_logp.data() : nullptr);
+                               out_alt_ids ? alt_ids.data() : nullptr, out_alt_ids ? alt_logp.data() : nullptr,
+                               sets ? view_sets.data() : nullptr);
         for (int i = 0; i < n_regions; ++i) {
             int32_t* row = out_ids + (size_t)i * L;
             if (where[i] < 0) {
@@ -2781,6 +2943,13 @@ int mocr_recognize_regions_alts(mocr_engine* e, const mocr_image* pages, int32_t
             }
         }
     });
+}
+
+int mocr_recognize_regions_alts(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                float* out_alt_logp) {
+    return mocr_recognize_regions_constrained(e, pages, n_pages, regions, n_regions, out_ids, out_len, out_logp, out_alt_ids,
+                                              out_alt_logp, nullptr);
 }
 
 int mocr_recognize_regions_scored(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
@@ -3104,8 +3273,9 @@ int mocr_op_dec_bias_gelu(mocr_engine* e, const float* d_slabs, int32_t nslab, c
     });
 }
 
-int mocr_op_dec_token_topk(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
-                           const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp) {
+int mocr_op_dec_token_masked(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                             const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
+                             const uint32_t* d_tok_mask, const int32_t* d_set_of_row) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -3118,7 +3288,8 @@ int mocr_op_dec_token_topk(mocr_engine* e, const mocr_token_args* a, const float
             (!first && a->ncand > 0 && (!a->cand_val || !a->cand_idx)) ||
             (!first && a->ncand <= 0 && (!a->slabs || a->nslab < 1)) || (a->forced && a->forced_T < 1) ||
             (d_scores && (first || a->forced || (a->ncand > 0 && !d_cand_sum))) ||
-            ((d_alt_ids == nullptr) != (d_alt_logp == nullptr)) || (d_alt_ids && (!d_scores || (a->ncand > 0 && (!d_top_val || !d_top_idx)))))
+            ((d_alt_ids == nullptr) != (d_alt_logp == nullptr)) || (d_alt_ids && (!d_scores || (a->ncand > 0 && (!d_top_val || !d_top_idx)))) ||
+            ((d_tok_mask == nullptr) != (d_set_of_row == nullptr)) || (d_tok_mask && (first || a->forced)))
             throw ArgError{"mocr_op_dec_token: bad argument", MOCR_ERR_ARG};
         DecState st{};
         st.n_real = a->n_real;
@@ -3129,6 +3300,7 @@ int mocr_op_dec_token_topk(mocr_engine* e, const mocr_token_args* a, const float
         st.rowmap = a->rowmap;
         st.scores = d_scores;
         st.alt_ids = d_alt_ids; st.alt_logp = d_alt_logp;
+        st.tok_mask = d_tok_mask; st.set_of_row = d_set_of_row;
         DecTokenArgs t{};
         t.slabs = a->slabs; t.nslab = first ? 0 : a->nslab; t.slab_stride = (long long)a->n * e->V;
         t.vbias = a->vbias ? a->vbias : e->w.bv;
@@ -3148,15 +3320,21 @@ int mocr_op_dec_token_topk(mocr_engine* e, const mocr_token_args* a, const float
     });
 }
 
+int mocr_op_dec_token_topk(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                           const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp) {
+    return mocr_op_dec_token_masked(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, nullptr, nullptr);
+}
+
 int mocr_op_dec_token_scored(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores) {
     return mocr_op_dec_token_topk(e, a, d_cand_sum, d_scores, nullptr, nullptr, nullptr, nullptr);
 }
 
 int mocr_op_dec_token(mocr_engine* e, const mocr_token_args* a) { return mocr_op_dec_token_scored(e, a, nullptr, nullptr); }
 
-int mocr_op_gemm_topk(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
-                      int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N, int32_t K,
-                      int32_t tile) {
+int mocr_op_gemm_argmax_masked(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                               int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N,
+                               int32_t K, int32_t tile, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
+                               const int32_t* d_rowmap) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -3166,8 +3344,15 @@ int mocr_op_gemm_topk(mocr_engine* e, const void* dA, const void* dW, const floa
             throw ArgError{"mocr_op_gemm_argmax: bad argument", MOCR_ERR_ARG};
         if ((d_top_val == nullptr) != (d_top_idx == nullptr) || (d_top_val && !d_cand_sum))
             throw ArgError{"mocr_op_gemm_topk: d_top_val / d_top_idx come together and with d_cand_sum", MOCR_ERR_ARG};
+        if ((d_tok_mask == nullptr) != (d_set_of_row == nullptr) || (d_tok_mask && N % 128))
+            throw ArgError{"mocr_op_gemm_argmax_masked: d_tok_mask and d_set_of_row come together, N a multiple of 128", MOCR_ERR_ARG};
         dispatch(e, [&](auto tag) {
-            if (d_top_val)
+            if (d_tok_mask) {
+                const TokMask tm{d_tok_mask, d_set_of_row, d_rowmap};
+                gemm<decltype(tag)>(e, "op_gemm_argmax_masked", dA, K, dW, d_bias, d_cand_val, N, nullptr, M, N, K,
+                                    d_top_val ? EPI_TOPK_M : d_cand_sum ? EPI_ARGMAX_LSE_M : EPI_ARGMAX_M, tile, 1, 0, nullptr, 0, nullptr, 0,
+                                    d_cand_idx, nullptr, d_cand_sum, d_top_val, d_top_idx, &tm);
+            } else if (d_top_val)
                 gemm<decltype(tag)>(e, "op_gemm_topk", dA, K, dW, d_bias, d_cand_val, N, nullptr, M, N, K, EPI_TOPK, tile, 1, 0,
                                     nullptr, 0, nullptr, 0, d_cand_idx, nullptr, d_cand_sum, d_top_val, d_top_idx);
             else if (d_cand_sum)
@@ -3179,6 +3364,13 @@ int mocr_op_gemm_topk(mocr_engine* e, const void* dA, const void* dW, const floa
         });
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
+}
+
+int mocr_op_gemm_topk(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                      int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N, int32_t K,
+                      int32_t tile) {
+    return mocr_op_gemm_argmax_masked(e, dA, dW, d_bias, d_cand_val, d_cand_idx, d_cand_sum, d_top_val, d_top_idx, M, N, K, tile,
+                                      nullptr, nullptr, nullptr);
 }
 
 int mocr_op_gemm_argmax_lse(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,

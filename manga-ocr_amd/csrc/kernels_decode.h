@@ -129,6 +129,11 @@ struct DecState {
     // lower id first - the greedy pick's order, so entry 0 is that id), alt_logp its fp32 log-softmax; -1 / 0 for a finished row.
     int* alt_ids;
     float* alt_logp;
+    // Token constraints (nullable, both or neither): tok_mask [sets][V / 32], bit v of a set's row = token v may be emitted
+    // (set 0: every token; EOS is in every set), and set_of_row [B], the set of every row - by ROW like ids, so a compaction
+    // moves nothing.  A token outside its row's set counts as a logit of -inf in the argmax, the softmax and the alternatives.
+    const unsigned* tok_mask;
+    const int* set_of_row;
 };
 
 // End of a decode step, one block per sequence:
@@ -145,7 +150,13 @@ struct DecState {
 //   the union of its tiles' top fours; slab path: from the 24 logits a thread holds.  A thread-local sorted list (Top4,
 //   kernels_gemm.h), merged across the wave by shuffles and across the four waves through LDS.  Entry k scores
 //   (val_k - max) - log S; entry 0 is written as the score itself, -log S (0 - log S would lose the sign of a -0 score).
-template <typename T, int D, bool FIRST, bool SCORES = false, bool TOPK = false>
+// MASK = true (st.tok_mask / st.set_of_row set): the row's allowed-token set applies.  Candidate path: the LM head (EPI_*_M)
+//   already left out the other columns; a tile with none comes as (-inf, index sentinel, sum 0), wins no comparison, adds
+//   0 * exp(-inf - max) = 0 to S and its unfilled list entries (-inf, sentinel) never enter a list.  Slab path: the thread's 24
+//   summed logits take -inf where the set's bit is clear (one nibble of one word per float4), before the argmax; in the
+//   alternatives they carry the index sentinel too.  EOS is in every set, so the row's max is finite; a set of fewer than
+//   four tokens leaves (-inf, sentinel) entries, written as id -1 / log-probability -inf.
+template <typename T, int D, bool FIRST, bool SCORES = false, bool TOPK = false, bool MASK = false>
 __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict__ slabs, int nslab, long long slab_stride,
                                                         const float* __restrict__ vbias, int V,
                                                         DecState st,
@@ -161,6 +172,7 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                                                         const float* __restrict__ top_val = nullptr,
                                                         const int* __restrict__ top_idx = nullptr) {
     static_assert(!TOPK || (SCORES && !FIRST), "alternatives come with scores, from the second token on");
+    static_assert(!MASK || !FIRST, "the start token is not constrained");
     __shared__ float s_val[4];
     __shared__ int s_idx[4];
     __shared__ float s_red[4];
@@ -181,6 +193,7 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
         int bi = 0x7fffffff;
         constexpr int NC = 6;                            // vocab = NC * 1024 columns (6144)
         float4 a[NC];
+        unsigned abits = 0xffffffu;                      // MASK, slab path: bit 4 j + e = the thread's logit a[j].e is allowed
         if (cand_val) {
             // the LM-head GEMM already reduced every 64/128-column tile (EPI_ARGMAX): ncand candidates per row
             for (int c = tid; c < ncand; c += 256) {
@@ -204,6 +217,13 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
             const int c = tid * 4 + j * 1024;
             if (st.logits_out)
                 *reinterpret_cast<float4*>(st.logits_out + ((size_t)b * st.forced_T + t) * V + c) = a[j];
+            if constexpr (MASK) {
+                const unsigned nib = (st.tok_mask[(size_t)st.set_of_row[row] * (V >> 5) + (c >> 5)] >> (c & 31)) & 15u;
+                if (j == 0) abits = 0;
+                abits |= nib << (4 * j);
+                a[j].x = (nib & 1) ? a[j].x : -INFINITY; a[j].y = (nib & 2) ? a[j].y : -INFINITY;
+                a[j].z = (nib & 4) ? a[j].z : -INFINITY; a[j].w = (nib & 8) ? a[j].w : -INFINITY;
+            }
             if (a[j].x > best) { best = a[j].x; bi = c; }
             if (a[j].y > best) { best = a[j].y; bi = c + 1; }
             if (a[j].z > best) { best = a[j].z; bi = c + 2; }
@@ -249,8 +269,14 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
 #pragma unroll
                 for (int j = 0; j < NC; ++j) {
                     const int c = tid * 4 + j * 1024;
+                    if constexpr (MASK) {
+                        const unsigned nib = abits >> (4 * j);
+                        top4_insert(top, a[j].x, (nib & 1) ? c : 0x7fffffff); top4_insert(top, a[j].y, (nib & 2) ? c + 1 : 0x7fffffff);
+                        top4_insert(top, a[j].z, (nib & 4) ? c + 2 : 0x7fffffff); top4_insert(top, a[j].w, (nib & 8) ? c + 3 : 0x7fffffff);
+                    } else {
                     top4_insert(top, a[j].x, c); top4_insert(top, a[j].y, c + 1);
                     top4_insert(top, a[j].z, c + 2); top4_insert(top, a[j].w, c + 3);
+                    }
                 }
             }
 #pragma unroll

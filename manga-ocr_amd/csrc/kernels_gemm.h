@@ -37,8 +37,11 @@ enum GemmEpilogue {
                          //   out f32 [M][ntn] values, cand_idx int [M][ntn] columns - the logits never go to memory
     EPI_ARGMAX_LSE = 7,  // token scores: EPI_ARGMAX + cand_sum f32 [M][ntn] = the tile's sum of exp(acc + bias - the tile's max),
                          //   from which the token kernel gets the chosen token's log-probability; the logits still stay in LDS
-    EPI_TOPK = 8         // token alternatives: EPI_ARGMAX_LSE + top_val f32 / top_idx int [M][ntn][4] = the tile's four largest
+    EPI_TOPK = 8,        // token alternatives: EPI_ARGMAX_LSE + top_val f32 / top_idx int [M][ntn][4] = the tile's four largest
                          //   acc + bias and their columns (value descending, lower column first on a tie); entry 0 = the arg-max
+    EPI_ARGMAX_M = 9,    // token constraints: the three LM-head epilogues above with the row's allowed-token set applied - a column
+    EPI_ARGMAX_LSE_M = 10, //   outside the set counts as -inf in the max, the exp sum and the four best (GemmParams::tok_mask /
+    EPI_TOPK_M = 11      //   set_of_row / rowmap); a tile without an allowed column leaves (-inf, 0x7fffffff), sum 0
 };
 
 struct GemmParams {
@@ -70,6 +73,10 @@ struct GemmParams {
     float* cand_sum;       // EPI_ARGMAX_LSE: [M][ntn] sum of exp(logit - tile max) over the tile's columns
     float* top_val;        // EPI_TOPK: [M][ntn][4] the tile's four largest logits, descending ...
     int* top_idx;          // ... and their columns
+    // EPI_*_M (token constraints): GEMM row m is decode slot m, which decodes batch row rowmap[m] under set set_of_row[row]
+    const unsigned* tok_mask;   // [sets][N / 32] bit n of a set's row = column n is allowed; set 0 is all ones
+    const int* set_of_row;      // [rows of the batch] set of every row, indexed by ROW like ids
+    const int* rowmap;          // [M] slot -> row (null: identity)
 };
 
 // Linear tile id -> (tm, tn).  Tiles are ordered column-group by column-group: inside a group of
@@ -154,7 +161,14 @@ __device__ __forceinline__ void gemm_epilogue(const float* sC, const GemmParams&
 // TOPK (EPI_TOPK, implies LSE): the first walk keeps the thread's four best instead of its best (Top4: the same order, so
 // entry 0 is the arg-max the other variants find), the row's threads merge their lists by shuffles, and part 0 also writes
 // the row's list, top_val / top_idx [m][tile][0..3], as two 16-byte stores.
-template <int BM, int BN, int NT, bool SWZ, bool LSE = false, bool TOPK = false>
+// MASK (EPI_*_M, token constraints): the row's set decides which columns exist.  A thread's CPP physical columns are one
+// CPP-aligned group of logical columns (the swizzle XORs multiples of 16 below CPP, or moves a 16-column group whole), so
+// its mask bits are 16 bits of one word or two whole words of the set's row, loaded once; a float4 starts at a multiple of 4,
+// so its four bits are one nibble.  A column outside the set takes (-inf, index sentinel) in the first walk - it wins no
+// comparison, not even the tie of two -inf against the initial entry - and contributes 0, by select, to the exp sum: a tile
+// with no allowed column stores best = -inf, the sentinel and cand_sum = 0 (never exp(-inf - -inf)), which the token
+// kernel's merge cand_sum * exp(cand_val - gmax) turns into 0 * 0.  Rows m >= M read set 0.
+template <int BM, int BN, int NT, bool SWZ, bool LSE = false, bool TOPK = false, bool MASK = false>
 __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const GemmParams& p, int m0, int n0, int tid) {
     constexpr int TPRW = NT / BM, CPP = BN / TPRW;
     static_assert(TPRW == 2 || TPRW == 4, "two or four threads per row");
@@ -164,6 +178,21 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const Gemm
     const int rot = 4 * (row % (CPP / 4));
     float best = -INFINITY;
     int bi = 0x7fffffff;
+    // MASK: bit (c - g0) of mbits = logical column c of the thread's group [g0, g0 + CPP) is allowed
+    unsigned long long mbits = ~0ull;
+    const int g0 = n0 + (CPP < 64 ? ((part * CPP) ^ sw) : part * CPP);
+    if constexpr (MASK) {
+        static_assert(CPP == 16 || CPP == 64, "the group is half a mask word or two words");
+        int set = 0;
+        if (m < p.M) set = p.set_of_row[p.rowmap ? p.rowmap[m] : m];
+        const unsigned* mrow = p.tok_mask + (size_t)set * (p.N >> 5);
+        if constexpr (CPP == 64) {
+            const uint2 w2 = *reinterpret_cast<const uint2*>(mrow + (g0 >> 5));
+            mbits = ((unsigned long long)w2.y << 32) | w2.x;
+        } else {
+            mbits = mrow[g0 >> 5] >> (g0 & 31);
+        }
+    }
     Top4 top;
     if constexpr (TOPK) {
         static_assert(LSE, "EPI_TOPK keeps the exp sums too");
@@ -174,10 +203,18 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const Gemm
             const float4 cv = *reinterpret_cast<const float4*>(&sC[row * BN + pc]);
             const int n = n0 + (pc ^ sw);
             const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
+            if constexpr (MASK) {
+                const unsigned nib = (unsigned)(mbits >> (n - g0)) & 15u;
+                top4_insert(top, (nib & 1) ? cv.x + bv.x : -INFINITY, (nib & 1) ? n : 0x7fffffff);
+                top4_insert(top, (nib & 2) ? cv.y + bv.y : -INFINITY, (nib & 2) ? n + 1 : 0x7fffffff);
+                top4_insert(top, (nib & 4) ? cv.z + bv.z : -INFINITY, (nib & 4) ? n + 2 : 0x7fffffff);
+                top4_insert(top, (nib & 8) ? cv.w + bv.w : -INFINITY, (nib & 8) ? n + 3 : 0x7fffffff);
+            } else {
             top4_insert(top, cv.x + bv.x, n);
             top4_insert(top, cv.y + bv.y, n + 1);
             top4_insert(top, cv.z + bv.z, n + 2);
             top4_insert(top, cv.w + bv.w, n + 3);
+            }
         }
 #pragma unroll
         for (int o = TPRW / 2; o > 0; o >>= 1) top4_merge_xor(top, o);
@@ -190,9 +227,16 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const Gemm
         const int n = n0 + (pc ^ sw);                                // logical (global) column of cv.x
         const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
         const float v[4] = {cv.x + bv.x, cv.y + bv.y, cv.z + bv.z, cv.w + bv.w};
+        if constexpr (MASK) {
+            const unsigned nib = (unsigned)(mbits >> (n - g0)) & 15u;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (((nib >> e) & 1) && (v[e] > best || (v[e] == best && n + e < bi))) { best = v[e]; bi = n + e; }
+        } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (v[e] > best || (v[e] == best && n + e < bi)) { best = v[e]; bi = n + e; }
+        }
     }
 #pragma unroll
     for (int o = TPRW / 2; o > 0; o >>= 1) {
@@ -208,8 +252,14 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const Gemm
             const int pc = part * CPP + ((rot + 4 * q) % CPP);
             const float4 cv = *reinterpret_cast<const float4*>(&sC[row * BN + pc]);
             const float4 bv = *reinterpret_cast<const float4*>(p.bias + n0 + (pc ^ sw));
+            if constexpr (MASK) {
+                const unsigned nib = (unsigned)(mbits >> (n0 + (pc ^ sw) - g0)) & 15u;
+                esum += (((nib & 1) ? __expf((cv.x + bv.x) - best) : 0.f) + ((nib & 2) ? __expf((cv.y + bv.y) - best) : 0.f)) +
+                        (((nib & 4) ? __expf((cv.z + bv.z) - best) : 0.f) + ((nib & 8) ? __expf((cv.w + bv.w) - best) : 0.f));
+            } else {
             esum += (__expf((cv.x + bv.x) - best) + __expf((cv.y + bv.y) - best)) +
                     (__expf((cv.z + bv.z) - best) + __expf((cv.w + bv.w) - best));
+            }
         }
 #pragma unroll
         for (int o = TPRW / 2; o > 0; o >>= 1) esum += __shfl_xor(esum, o, 64);
@@ -438,6 +488,12 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
         gemm_epilogue_argmax<BM, BN, 256, SWZ, true>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_TOPK) {
         gemm_epilogue_argmax<BM, BN, 256, SWZ, true, true>(sC, p, m0, n0, tid);
+    } else if constexpr (EPI == EPI_ARGMAX_M) {
+        gemm_epilogue_argmax<BM, BN, 256, SWZ, false, false, true>(sC, p, m0, n0, tid);
+    } else if constexpr (EPI == EPI_ARGMAX_LSE_M) {
+        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, false, true>(sC, p, m0, n0, tid);
+    } else if constexpr (EPI == EPI_TOPK_M) {
+        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, true, true>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_BIAS) {
         GemmParams q = p;
         q.out = reinterpret_cast<T*>(p.out) + (size_t)blockIdx.y * p.o_yoff;

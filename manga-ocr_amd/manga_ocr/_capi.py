@@ -70,6 +70,8 @@ class MocrLatentArgs(C.Structure):
 
 
 CHANNELS_BGR = -3
+MAX_TOKEN_SETS = 256      # MOCR_MAX_TOKEN_SETS: token sets per engine, set 0 included
+TOKEN_SET_ALL = 0         # MOCR_TOKEN_SET_ALL: the whole vocabulary
 ALTERNATIVES = 4          # MOCR_ALTERNATIVES: candidates per position of the *_alts entry points
 ROTATE_NONE, ROTATE_90_CW, ROTATE_90_CCW = 0, 1, 2
 
@@ -91,6 +93,12 @@ SYMBOLS = {
     "mocr_recognize_regions_alts": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.POINTER(MocrRegion), C.c_int32, _P, _P, _P, _P, _P]),
     "mocr_recognize_device_alts": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P]),
     "mocr_recognize_gray_host_alts": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "mocr_token_set_create": (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    "mocr_token_set_count": (C.c_int, [_P]),
+    "mocr_recognize_images_constrained": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "mocr_recognize_regions_constrained": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.POINTER(MocrRegion), C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "mocr_recognize_device_constrained": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "mocr_recognize_gray_host_constrained": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "mocr_graph_count": (C.c_int, [_P]),
     "mocr_compaction_count": (C.c_int64, [_P]),
     "mocr_decode_slot_steps": (C.c_int64, [_P]),
@@ -122,6 +130,8 @@ SYMBOLS = {
     "mocr_op_gemm_argmax_lse": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mocr_op_dec_token_topk": (C.c_int, [_P, C.POINTER(MocrTokenArgs), _P, _P, _P, _P, _P, _P]),
     "mocr_op_gemm_topk": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "mocr_op_dec_token_masked": (C.c_int, [_P, C.POINTER(MocrTokenArgs), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mocr_op_gemm_argmax_masked": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "mocr_op_smallm_gemm": (C.c_int, [_P, C.POINTER(MocrSmallmArgs)]),
     "mocr_op_latent_block": (C.c_int, [_P, C.POINTER(MocrLatentArgs)]),
     "mocr_profile_enable": (C.c_int, [_P, C.c_int32]),

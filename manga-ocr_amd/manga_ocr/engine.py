@@ -133,19 +133,63 @@ class Engine:
             d.rotate = int(rotate[i]) if rotate is not None else 0
         return descs, keep
 
+    # ------------------------------------------------------------------ token constraints
+    def token_set(self, ids) -> int:
+        """A token set of this engine (include/mocr.h, "token constraints"): the handle of the set holding ``ids`` (token ids
+        in [0, vocab), duplicates allowed) and EOS, which the engine adds.  Sets are immutable and live as long as the engine;
+        the same content gives the same handle.  Handle 0 is the whole vocabulary."""
+        a = np.ascontiguousarray(np.asarray(list(ids) if not isinstance(ids, np.ndarray) else ids).ravel(), dtype=np.int32)
+        out = C.c_int32(0)
+        self._check(self.lib.mocr_token_set_create(self._h, _ptr(a), int(a.size), C.byref(out)))
+        return int(out.value)
+
+    def token_set_count(self) -> int:
+        """Handles in use, set 0 included."""
+        return int(self.lib.mocr_token_set_count(self._h))
+
+    @staticmethod
+    def _sets(token_sets, n: int) -> np.ndarray:
+        """``token_sets=``: one handle for every crop, or one handle per crop -> int32 [n]"""
+        if isinstance(token_sets, (int, np.integer)):
+            return np.full(n, int(token_sets), dtype=np.int32)
+        a = np.ascontiguousarray(np.asarray(list(token_sets)).ravel(), dtype=np.int32)
+        if a.size != n:
+            raise ValueError(f"token_sets: {n} crops but {a.size} set handles")
+        return a
+
+    def _constrained_blocks(self, n: int, scores: bool, alternatives: bool):
+        """the output blocks of a *_constrained call (None where not asked) and what the caller gets back"""
+        ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
+        lens = np.zeros(n, dtype=np.int32)
+        logp = np.zeros((n, self.spec.max_len), dtype=np.float32) if (scores or alternatives) else None
+        alt_ids, alt_logp = self._alt_blocks(n) if alternatives else (None, None)
+        out = (ids, lens, logp, alt_ids, alt_logp) if alternatives else (ids, lens, logp) if scores else (ids, lens)
+        return ids, lens, logp, alt_ids, alt_logp, out
+
     def _alt_blocks(self, n: int):
         """(alt_ids int32, alt_logp float32) [n, max_len, 4] as the engine leaves unwritten positions: -1 / 0"""
         shape = (n, self.spec.max_len, _capi.ALTERNATIVES)
         return np.full(shape, -1, dtype=np.int32), np.zeros(shape, dtype=np.float32)
 
-    def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False):
+    def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False,
+                         token_sets=None):
         """Crops of any sizes (list of uint8 [h,w] / [h,w,3] arrays; `bgr`: 3-channel crops are in OpenCV order;
         `rotate`: per crop 0 / 1 (90 degrees clockwise) / 2 (counter-clockwise), applied on the device): luminance
         conversion and the Pillow-exact BILINEAR resize to 224x224 run on the device.
         Returns (ids int32 [n,max_len], lengths int32 [n]); with ``scores=True`` (ids, lengths, logp float32 [n,max_len]):
         the log-probability of every emitted token, computed on the device (include/mocr.h, "token scores"); same ids.
         With ``alternatives=True`` (ids, lengths, logp, alt_ids int32 [n,max_len,4], alt_logp float32 [n,max_len,4]): the four
-        most probable tokens of every position and their log-probabilities (include/mocr.h, "token alternatives"); same ids."""
+        most probable tokens of every position and their log-probabilities (include/mocr.h, "token alternatives"); same ids.
+        ``token_sets``: a handle of :meth:`token_set` for every crop, or one per crop - each crop is decoded under its set
+        (include/mocr.h, "token constraints"); the return value is shaped by ``scores`` / ``alternatives`` as above."""
+        if token_sets is not None and len(images) > 0:
+            descs, keep = self._image_descs(images, bgr, rotate)
+            n = len(keep)
+            sets = self._sets(token_sets, n)
+            ids, lens, logp, alt_ids, alt_logp, out = self._constrained_blocks(n, scores, alternatives)
+            self._check(self.lib.mocr_recognize_images_constrained(self._h, descs, n, _ptr(ids), _ptr(lens), _ptr(logp), _ptr(alt_ids),
+                                                                   _ptr(alt_logp), _ptr(sets)))
+            return out
         if len(images) == 0:
             empty = (np.zeros((0, self.spec.max_len), dtype=np.int32), np.zeros(0, dtype=np.int32))
             if alternatives:
@@ -168,13 +212,14 @@ class Engine:
         self._check(self.lib.mocr_recognize_images(self._h, descs, n, _ptr(ids), _ptr(lens)))
         return ids, lens
 
-    def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False):
+    def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False,
+                          token_sets=None):
         """pages: list of uint8 [H,W,3] (or [H,W]) arrays; regions: iterable of (page_index, x, y, w, h) bounding
         rectangles.  Each page is uploaded once; the 8 %-padded, page-clipped crop of every region
         (``src/ui/main_window.py:9530-9540``) is cut on the device.  Returns (ids [n,max_len], lengths [n]);
         a region reduced to a sliver has length 0.  ``scores=True``: (ids, lengths, logp float32 [n,max_len]), a sliver's
         row all 0.  ``alternatives=True``: (ids, lengths, logp, alt_ids, alt_logp) as for recognize_images, a sliver's rows
-        all -1 / 0."""
+        all -1 / 0.  ``token_sets``: a set handle for every region, or one per region (see recognize_images)."""
         regs = list(regions)
         n = len(regs)
         ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
@@ -187,6 +232,11 @@ class Engine:
         arr = (_capi.MocrRegion * n)()
         for i, (pg, x, y, w, h) in enumerate(regs):
             arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
+        if token_sets is not None:
+            sets = self._sets(token_sets, n)
+            self._check(self.lib.mocr_recognize_regions_constrained(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens), _ptr(logp),
+                                                                    _ptr(alt_ids), _ptr(alt_logp), _ptr(sets)))
+            return (ids, lens, logp, alt_ids, alt_logp) if alternatives else (ids, lens, logp) if scores else (ids, lens)
         if alternatives:
             self._check(self.lib.mocr_recognize_regions_alts(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens), _ptr(logp),
                                                              _ptr(alt_ids), _ptr(alt_logp)))
@@ -222,10 +272,16 @@ class Engine:
         self._check(self.lib.mocr_preprocess(self._h, descs, len(keep), _ptr(out)))
         return out
 
-    def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None, d_out_alt_ids=None, d_out_alt_logp=None) -> None:
+    def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None, d_out_alt_ids=None, d_out_alt_logp=None, *,
+                         token_sets=None) -> None:
         """Asynchronous; all are device buffers (torch CUDA tensors or raw addresses).  ``d_out_logp`` (float32
         [n,max_len]): also the token log-probabilities.  ``d_out_alt_ids`` (int32) with ``d_out_alt_logp`` (float32), both
-        [n,max_len,4]: also the token alternatives."""
+        [n,max_len,4]: also the token alternatives.  ``token_sets``: a set handle for every crop, or one per crop (host values)."""
+        if token_sets is not None:
+            sets = self._sets(token_sets, n)
+            self._check(self.lib.mocr_recognize_device_constrained(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len),
+                                                                   _ptr(d_out_logp), _ptr(d_out_alt_ids), _ptr(d_out_alt_logp), _ptr(sets)))
+            return
         if d_out_alt_ids is not None or d_out_alt_logp is not None:
             self._check(self.lib.mocr_recognize_device_alts(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len), _ptr(d_out_logp),
                                                             _ptr(d_out_alt_ids), _ptr(d_out_alt_logp)))
@@ -238,9 +294,16 @@ class Engine:
     def set_generate_max_length(self, max_len: int) -> None:
         self._check(self.lib.mocr_set_generate_max_length(self._h, int(max_len)))
 
-    def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False, alternatives: bool = False):
+    def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False, alternatives: bool = False,
+                       token_sets=None):
         a = np.ascontiguousarray(gray, dtype=np.uint8)
         n = a.shape[0]
+        if token_sets is not None:
+            sets = self._sets(token_sets, n)
+            ids, lens, logp, alt_ids, alt_logp, out = self._constrained_blocks(n, scores, alternatives)
+            self._check(self.lib.mocr_recognize_gray_host_constrained(self._h, _ptr(a), n, max_len or self.spec.max_len, _ptr(ids),
+                                                                      _ptr(lens), _ptr(logp), _ptr(alt_ids), _ptr(alt_logp), _ptr(sets)))
+            return out
         ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
         lens = np.zeros(n, dtype=np.int32)
         if alternatives:
@@ -341,6 +404,24 @@ class Engine:
             setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
         self._check(self.lib.mocr_op_dec_token_topk(self._h, C.byref(a), _ptr(d_cand_sum), _ptr(d_scores), _ptr(d_top_val),
                                                     _ptr(d_top_idx), _ptr(d_alt_ids), _ptr(d_alt_logp)))
+
+    def op_dec_token_masked(self, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, **kw) -> None:
+        """The token step under token sets: op_dec_token_topk (outputs nullable from the right) plus the set table and the
+        set of every row."""
+        a = _capi.MocrTokenArgs()
+        a.struct_size = C.sizeof(_capi.MocrTokenArgs)
+        for name, value in kw.items():
+            ftype = dict(_capi.MocrTokenArgs._fields_)[name]
+            setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
+        self._check(self.lib.mocr_op_dec_token_masked(self._h, C.byref(a), _ptr(d_cand_sum), _ptr(d_scores), _ptr(d_top_val),
+                                                      _ptr(d_top_idx), _ptr(d_alt_ids), _ptr(d_alt_logp), _ptr(d_tok_mask),
+                                                      _ptr(d_set_of_row)))
+
+    def op_gemm_argmax_masked(self, dA, dW, d_bias, d_cand_val, d_cand_idx, d_cand_sum, d_top_val, d_top_idx, M, N, K, tile,
+                              d_tok_mask, d_set_of_row, d_rowmap=None) -> None:
+        self._check(self.lib.mocr_op_gemm_argmax_masked(self._h, _ptr(dA), _ptr(dW), _ptr(d_bias), _ptr(d_cand_val), _ptr(d_cand_idx),
+                                                        _ptr(d_cand_sum), _ptr(d_top_val), _ptr(d_top_idx), M, N, K, tile,
+                                                        _ptr(d_tok_mask), _ptr(d_set_of_row), _ptr(d_rowmap)))
 
     def op_gemm_topk(self, dA, dW, d_bias, d_cand_val, d_cand_idx, d_cand_sum, d_top_val, d_top_idx, M, N, K, tile) -> None:
         self._check(self.lib.mocr_op_gemm_topk(self._h, _ptr(dA), _ptr(dW), _ptr(d_bias), _ptr(d_cand_val), _ptr(d_cand_idx),

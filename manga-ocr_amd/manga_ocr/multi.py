@@ -259,6 +259,8 @@ class MultiGpuEngine:
 
     NO_SCORES = ("token scores are not implemented for several devices (manga_ocr/multi.py ships ids and lengths only): "
                  "construct MangaOcr on one device to use the scored calls")
+    NO_CONSTRAINTS = ("token constraints are not implemented for several devices (manga_ocr/multi.py: a token set belongs to one "
+                      "engine): construct MangaOcr on one device to use token_set / allowed=")
     NO_ALTERNATIVES = ("token alternatives are not implemented for several devices (manga_ocr/multi.py ships ids and lengths only): "
                        "construct MangaOcr on one device to use the *_alternatives calls")
 
@@ -518,8 +520,13 @@ class MultiGpuEngine:
         return descs, off, fill
 
     # ------------------------------------------------------------------ the hot path
+    def token_set(self, ids) -> int:
+        raise NotImplementedError(self.NO_CONSTRAINTS)
+
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False,
-                         alternatives: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+                         alternatives: bool = False, token_sets=None) -> Tuple[np.ndarray, np.ndarray]:
+        if token_sets is not None:
+            raise NotImplementedError(self.NO_CONSTRAINTS)
         if alternatives:
             raise NotImplementedError(self.NO_ALTERNATIVES)
         if scores:
@@ -537,7 +544,9 @@ class MultiGpuEngine:
         return self._run(n, size, fill, dict(kind="images", descs=descs, bgr=bool(bgr), rotate=rotate))
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False,
-                          alternatives: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+                          alternatives: bool = False, token_sets=None) -> Tuple[np.ndarray, np.ndarray]:
+        if token_sets is not None:
+            raise NotImplementedError(self.NO_CONSTRAINTS)
         if alternatives:
             raise NotImplementedError(self.NO_ALTERNATIVES)
         if scores:

@@ -67,6 +67,27 @@ _ALTERNATIVES = 4      # include/mocr.h MOCR_ALTERNATIVES
 
 
 @dataclass(frozen=True)
+class TokenSet:
+    """What ``MangaOcr.token_set`` returns and ``allowed=`` takes: the engine's handle of an allowed-token set and the
+    number of tokens in it as the caller named it (the engine adds EOS).  Handle 0 is the whole vocabulary."""
+    handle: int
+    size: int
+
+
+def _set_handles(allowed, n: int) -> Optional[List[int]]:
+    """``allowed=``: None, one set (TokenSet or engine handle) for all ``n`` crops, or one per crop -> None / n handles"""
+    if allowed is None:
+        return None
+    one = lambda a: int(a.handle) if isinstance(a, TokenSet) else int(a)
+    if isinstance(allowed, (TokenSet, int, np.integer)):
+        return [one(allowed)] * n
+    hs = [one(a) for a in allowed]
+    if len(hs) != n:
+        raise ValueError(f"allowed: {n} crops but {len(hs)} token sets")
+    return hs
+
+
+@dataclass(frozen=True)
 class Recognition:
     """One recognised crop with the recogniser's own confidence (the ``*_scored`` methods of :class:`MangaOcr`).
 
@@ -108,13 +129,16 @@ class Recognition:
 
     def candidates(self, k: int) -> List[Tuple[str, float]]:
         """The four most probable tokens of generated position ``k`` (the one that emitted ``ids[k + 1]``), most probable
-        first: (token as the vocabulary spells it, probability).  Entry 0 is the emitted token.  Needs a result of one of the
-        ``*_alternatives`` methods."""
+        first: (token as the vocabulary spells it, probability).  Entry 0 is the emitted token.  Fewer than four when the crop
+        was decoded under a token set of fewer than four tokens (``allowed=``): the missing entries, id -1, are skipped.
+        Needs a result of one of the ``*_alternatives`` methods."""
         if self.alt_ids is None or self.alt_logprobs is None:
             raise ValueError("this Recognition carries no alternatives: use MangaOcr.recognize_alternatives and friends")
         toks = self._vocab.tokens if self._vocab is not None else None
         out = []
         for i, lp in zip(self.alt_ids[k].tolist(), self.alt_logprobs[k].astype(np.float64).tolist()):
+            if i < 0:
+                continue
             name = toks[i] if toks is not None and 0 <= i < len(toks) else f"[{i}]"
             out.append((name, float(np.exp(lp))))
         return out
@@ -125,7 +149,9 @@ class _Batcher:
     isolation like the reference's worker loop, ``src/core/workers.py:241-244``).  A request may ask for token scores;
     a batch with such a request makes the engine's scored call (the ids do not depend on it), and every caller gets
     what it asked for: ids, or (ids, logp).  The same one kind further for token alternatives: the batch makes the richest
-    call any of its requests asked for, and such a caller gets (ids, logp, alt_ids, alt_logp)."""
+    call any of its requests asked for, and such a caller gets (ids, logp, alt_ids, alt_logp).  A request may also carry a
+    token set (``allowed=``); only a batch with such a request passes ``token_sets=`` - one handle per crop, 0 for the others -
+    to the engine, so batches nobody constrains make exactly the calls they always made."""
 
     def __init__(self, engine: Engine, max_batch: int, timeout_ms: float):
         self.engine, self.max_batch, self.timeout = engine, max_batch, timeout_ms / 1000.0
@@ -135,12 +161,12 @@ class _Batcher:
         self._thread = threading.Thread(target=self._run, name="mocr-batcher", daemon=True)
         self._thread.start()
 
-    def submit(self, gray: np.ndarray, scored: bool = False, alternatives: bool = False) -> Future:
+    def submit(self, gray: np.ndarray, scored: bool = False, alternatives: bool = False, token_set: int = 0) -> Future:
         f: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
-            self._q.append((gray, f, 2 if alternatives else 1 if scored else 0))     # the kind of request
+            self._q.append((gray, f, 2 if alternatives else 1 if scored else 0, int(token_set)))     # the kind of request, its set
             self._cv.notify()
         return f
 
@@ -159,22 +185,24 @@ class _Batcher:
                     self._cv.wait(left)
                 batch, self._q = self._q[:self.max_batch], self._q[self.max_batch:]
             try:
-                kind = max(k for _, _, k in batch)
+                kind = max(k for _, _, k, _ in batch)
+                sets = [h for _, _, _, h in batch]
+                extra = dict(token_sets=sets) if any(sets) else {}
                 logp = alt_ids = alt_logp = None
                 if kind == 2:
-                    ids, lens, logp, alt_ids, alt_logp = self.engine.recognize_images([g for g, _, _ in batch], alternatives=True)
+                    ids, lens, logp, alt_ids, alt_logp = self.engine.recognize_images([g for g, _, _, _ in batch], alternatives=True, **extra)
                 elif kind == 1:
-                    ids, lens, logp = self.engine.recognize_images([g for g, _, _ in batch], scores=True)
+                    ids, lens, logp = self.engine.recognize_images([g for g, _, _, _ in batch], scores=True, **extra)
                 else:
-                    ids, lens = self.engine.recognize_images([g for g, _, _ in batch])
-                for i, (_, f, k) in enumerate(batch):
+                    ids, lens = self.engine.recognize_images([g for g, _, _, _ in batch], **extra)
+                for i, (_, f, k, _) in enumerate(batch):
                     n = lens[i]
                     if k == 2:
                         f.set_result((ids[i, :n].copy(), logp[i, :n].copy(), alt_ids[i, :n].copy(), alt_logp[i, :n].copy()))
                     else:
                         f.set_result((ids[i, :n].copy(), logp[i, :n].copy()) if k else ids[i, :n].copy())
             except BaseException as exc:  # every waiting caller gets the error; the loop lives on
-                for _, f, _ in batch:
+                for _, f, _, _ in batch:
                     if not f.done():
                         f.set_exception(exc)
 
@@ -260,39 +288,93 @@ class MangaOcr:
         if batch_timeout_ms is None:
             batch_timeout_ms = float(os.environ.get("MANGA_OCR_BATCH_WINDOW_MS", "0.3"))
         self._batcher = _Batcher(self.engine, max_batch, batch_timeout_ms)
+        self._token_sets = {}
+        self._token_sets_lock = threading.Lock()
         # same warm-up the reference's recogniser does in its constructor (one inference)
         self.recognize_ids([np.zeros((spec.image_size, spec.image_size), dtype=np.uint8)])
 
     # ------------------------------------------------------------------ reference call surface
     def __call__(self, img_or_path) -> str:
-        from PIL import Image
-        if isinstance(img_or_path, (str, Path)):
-            img = Image.open(img_or_path)
-        elif isinstance(img_or_path, Image.Image):
-            img = img_or_path
-        else:
-            raise ValueError(f"img_or_path must be a path or PIL.Image, instead got: {img_or_path}")
-        ids = self._batcher.submit(to_pixels(img)).result()
+        ids = self._batcher.submit(to_pixels(self._open(img_or_path))).result()
         return ids_to_text(self.vocab, ids)
 
+    # ------------------------------------------------------------------ token constraints
+    def token_set(self, chars=None, ids=None, exclude_chars=None) -> TokenSet:
+        """An allowed-token set for ``allowed=``: what the caller knows about a crop (a page-number box holds digits, a
+        sound-effect bubble kana) or never wants to see.  ``chars``: the tokens spelt with these characters only
+        (``Vocab.ids_for_chars``: matched on the raw token text of vocab.txt, before ``post_process`` - name half- and
+        full-width forms as the vocabulary spells them); ``ids``: these token ids; both: their union; neither: the whole
+        vocabulary.  ``exclude_chars`` then removes every token whose text contains one of these characters.  EOS is always
+        a member (the engine adds it).  The same content gives the same handle; sets live as long as this MangaOcr, at most
+        255 of them (include/mocr.h, "token constraints")."""
+        no = getattr(self.engine, "NO_CONSTRAINTS", None)      # MultiGpuEngine: a set belongs to one engine
+        if no:
+            raise NotImplementedError(no)
+        if chars is None and ids is None:
+            members = set(range(len(self.vocab)))
+        else:
+            members = set(self.vocab.ids_for_chars(chars)) if chars is not None else set()
+            if ids is not None:
+                members |= {int(i) for i in ids}
+        if exclude_chars:
+            banned = set("".join(exclude_chars))
+            members = {i for i in members if not (0 <= i < len(self.vocab)) or not (banned & set(self.vocab.tokens[i]))}
+        if not members:
+            raise ValueError("token_set: no token of the vocabulary is left in the set")
+        key = frozenset(members)
+        with self._token_sets_lock:
+            ts = self._token_sets.get(key)
+            if ts is None:
+                ts = self._token_sets[key] = TokenSet(self.engine.token_set(sorted(members)), len(members))
+            return ts
+
+    def _allowed(self, allowed, n: int) -> dict:
+        """the engine keyword of ``allowed=`` ({} for None: the call the method always made)"""
+        hs = _set_handles(allowed, n)
+        if hs is None:
+            return {}
+        no = getattr(self.engine, "NO_CONSTRAINTS", None)
+        if no:
+            raise NotImplementedError(no)
+        return dict(token_sets=hs)
+
     # ------------------------------------------------------------------ batch surface (callers that hold many crops)
-    def recognize_ids(self, crops: Sequence[np.ndarray], bgr: bool = False, rotate: Optional[Sequence[int]] = None) -> List[np.ndarray]:
+    def recognize_ids(self, crops: Sequence[np.ndarray], bgr: bool = False, rotate: Optional[Sequence[int]] = None, *,
+                      allowed=None) -> List[np.ndarray]:
         """uint8 crops of any sizes ([h,w] luminance or [h,w,3] RGB; BGR with ``bgr=True``; ``rotate``: per crop 0 / 1 (90
-        degrees clockwise) / 2 (counter-clockwise), done by the device) -> token ids (without padding)."""
-        ids, lens = self.engine.recognize_images(list(crops), bgr, rotate)
+        degrees clockwise) / 2 (counter-clockwise), done by the device) -> token ids (without padding).  ``allowed``: a
+        token set of :meth:`token_set` for all crops, or one per crop."""
+        crops = list(crops)
+        ids, lens = self.engine.recognize_images(crops, bgr, rotate, **self._allowed(allowed, len(crops)))
         return [ids[i, :lens[i]].copy() for i in range(len(lens))]
 
-    def recognize_batch(self, images: Sequence) -> List[str]:
+    def recognize(self, img_or_path, *, allowed=None) -> str:
+        """``__call__`` (which keeps the reference's signature) with ``allowed=``: one crop decoded under a token set."""
+        if allowed is None:
+            return self(img_or_path)
+        ids = self._batcher.submit(to_pixels(self._open(img_or_path)), token_set=self._allowed(allowed, 1)["token_sets"][0]).result()
+        return ids_to_text(self.vocab, ids)
+
+    @staticmethod
+    def _open(img_or_path):
+        from PIL import Image
+        if isinstance(img_or_path, (str, Path)):
+            return Image.open(img_or_path)
+        if isinstance(img_or_path, Image.Image):
+            return img_or_path
+        raise ValueError(f"img_or_path must be a path or PIL.Image, instead got: {img_or_path}")
+
+    def recognize_batch(self, images: Sequence, *, allowed=None) -> List[str]:
         """All crops of a page (or chapter) at once - what ``_collect_manga_detections``
         (``src/ui/main_window.py:9462-9476``) does one region at a time."""
-        return [ids_to_text(self.vocab, r) for r in self.recognize_ids([to_pixels(im) for im in images])]
+        return [ids_to_text(self.vocab, r) for r in self.recognize_ids([to_pixels(im) for im in images], allowed=allowed)]
 
-    def recognize_batch_arrays(self, crops: Sequence[np.ndarray]) -> List[str]:
+    def recognize_batch_arrays(self, crops: Sequence[np.ndarray], *, allowed=None) -> List[str]:
         """uint8 arrays ([h,w] luminance or [h,w,3] RGB, any sizes) -> strings: what a caller that already holds numpy
         crops (the crop-job queue) uses instead of wrapping each one in a PIL image."""
-        return [ids_to_text(self.vocab, r) for r in self.recognize_ids(list(crops))]
+        return [ids_to_text(self.vocab, r) for r in self.recognize_ids(list(crops), allowed=allowed)]
 
-    def recognize_bgr(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None) -> List[str]:
+    def recognize_bgr(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *, allowed=None) -> List[str]:
         """BGR crops exactly as the crop tools and the worker hold them (``cropped_cv_img``, ``src/core/workers.py:300``):
         the BGR -> RGB swap of ``src/ui/main_window.py:9800`` is folded into the device's luminance conversion, and with
         ``orientations`` (the jobs' "Auto-Detect" / "Vertical" / "Horizontal" settings) the orientation-only rotation of
@@ -304,13 +386,14 @@ class MangaOcr:
             if len(orientations) != len(crops):        # zip() would truncate silently: a short list must not cost a decode
                 raise ValueError(f"recognize_bgr: {len(crops)} crops but {len(orientations)} orientations")
             rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
-        return [ids_to_text(self.vocab, r) for r in self.recognize_ids(crops, bgr=True, rotate=rot)]
+        return [ids_to_text(self.vocab, r) for r in self.recognize_ids(crops, bgr=True, rotate=rot, allowed=allowed)]
 
-    def recognize_regions(self, pages_bgr: Sequence[np.ndarray], regions) -> List[str]:
+    def recognize_regions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None) -> List[str]:
         """``regions``: (page_index, x, y, w, h) bounding rectangles on BGR pages; every page is uploaded once and
         the padded crops (``src/ui/main_window.py:9530-9540``) are cut on the device.  One string per region
         ('' for a region reduced to a sliver, like the reference)."""
-        ids, lens = self.engine.recognize_regions(list(pages_bgr), list(regions), True)
+        regions = list(regions)
+        ids, lens = self.engine.recognize_regions(list(pages_bgr), regions, True, **self._allowed(allowed, len(regions)))
         return [ids_to_text(self.vocab, ids[i, :lens[i]]) if lens[i] > 0 else "" for i in range(len(lens))]
 
     # ------------------------------------------------------------------ scored surface: the same recognitions + confidence
@@ -322,27 +405,24 @@ class MangaOcr:
     def _recognitions(self, ids, lens, logp) -> List[Recognition]:
         return [Recognition.from_row(self.vocab, ids[i], logp[i], lens[i]) for i in range(len(lens))]
 
-    def recognize_scored(self, img_or_path) -> Recognition:
+    def recognize_scored(self, img_or_path, *, allowed=None) -> Recognition:
         """``__call__`` with the recogniser's confidence: same text, plus the token log-probabilities computed on the
         device (include/mocr.h, "token scores").  Goes through the same batcher as ``__call__``; scored and unscored
         callers may share a batch."""
-        from PIL import Image
         self._check_scored()
-        if isinstance(img_or_path, (str, Path)):
-            img = Image.open(img_or_path)
-        elif isinstance(img_or_path, Image.Image):
-            img = img_or_path
-        else:
-            raise ValueError(f"img_or_path must be a path or PIL.Image, instead got: {img_or_path}")
-        ids, logp = self._batcher.submit(to_pixels(img), scored=True).result()
+        img = self._open(img_or_path)
+        extra = dict(token_set=self._allowed(allowed, 1)["token_sets"][0]) if allowed is not None else {}
+        ids, logp = self._batcher.submit(to_pixels(img), scored=True, **extra).result()
         return Recognition.from_row(self.vocab, ids, logp, len(ids))
 
-    def recognize_batch_scored(self, images: Sequence) -> List[Recognition]:
+    def recognize_batch_scored(self, images: Sequence, *, allowed=None) -> List[Recognition]:
         """``recognize_batch`` with confidences."""
         self._check_scored()
-        return self._recognitions(*self.engine.recognize_images([to_pixels(im) for im in images], scores=True))
+        crops = [to_pixels(im) for im in images]
+        return self._recognitions(*self.engine.recognize_images(crops, scores=True, **self._allowed(allowed, len(crops))))
 
-    def recognize_bgr_scored(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None) -> List[Recognition]:
+    def recognize_bgr_scored(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
+                             allowed=None) -> List[Recognition]:
         """``recognize_bgr`` with confidences."""
         from .queue_worker import rotation_code
         self._check_scored()
@@ -352,12 +432,14 @@ class MangaOcr:
             if len(orientations) != len(crops):
                 raise ValueError(f"recognize_bgr_scored: {len(crops)} crops but {len(orientations)} orientations")
             rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
-        return self._recognitions(*self.engine.recognize_images(crops, True, rot, scores=True))
+        return self._recognitions(*self.engine.recognize_images(crops, True, rot, scores=True, **self._allowed(allowed, len(crops))))
 
-    def recognize_regions_scored(self, pages_bgr: Sequence[np.ndarray], regions) -> List[Recognition]:
+    def recognize_regions_scored(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None) -> List[Recognition]:
         """``recognize_regions`` with confidences; a region reduced to a sliver gives text '' and confidence 0.0."""
         self._check_scored()
-        return self._recognitions(*self.engine.recognize_regions(list(pages_bgr), list(regions), True, scores=True))
+        regions = list(regions)
+        return self._recognitions(*self.engine.recognize_regions(list(pages_bgr), regions, True, scores=True,
+                                                                 **self._allowed(allowed, len(regions))))
 
     # ------------------------------------------------------------------ alternatives surface: + the runners-up of every position
     def _check_alternatives(self) -> None:
@@ -368,27 +450,24 @@ class MangaOcr:
     def _recognitions_alt(self, ids, lens, logp, alt_ids, alt_logp) -> List[Recognition]:
         return [Recognition.from_row(self.vocab, ids[i], logp[i], lens[i], alt_ids[i], alt_logp[i]) for i in range(len(lens))]
 
-    def recognize_alternatives(self, img_or_path) -> Recognition:
+    def recognize_alternatives(self, img_or_path, *, allowed=None) -> Recognition:
         """``recognize_scored`` plus, for every generated position, the four most probable tokens and their log-probabilities
         (``Recognition.alt_ids`` / ``alt_logprobs`` / ``candidates``; include/mocr.h, "token alternatives").  Same text; goes
         through the same batcher as ``__call__``, and callers of all three kinds may share a batch."""
-        from PIL import Image
         self._check_alternatives()
-        if isinstance(img_or_path, (str, Path)):
-            img = Image.open(img_or_path)
-        elif isinstance(img_or_path, Image.Image):
-            img = img_or_path
-        else:
-            raise ValueError(f"img_or_path must be a path or PIL.Image, instead got: {img_or_path}")
-        ids, logp, alt_ids, alt_logp = self._batcher.submit(to_pixels(img), alternatives=True).result()
+        img = self._open(img_or_path)
+        extra = dict(token_set=self._allowed(allowed, 1)["token_sets"][0]) if allowed is not None else {}
+        ids, logp, alt_ids, alt_logp = self._batcher.submit(to_pixels(img), alternatives=True, **extra).result()
         return Recognition.from_row(self.vocab, ids, logp, len(ids), alt_ids, alt_logp)
 
-    def recognize_batch_alternatives(self, images: Sequence) -> List[Recognition]:
+    def recognize_batch_alternatives(self, images: Sequence, *, allowed=None) -> List[Recognition]:
         """``recognize_batch`` with confidences and alternatives."""
         self._check_alternatives()
-        return self._recognitions_alt(*self.engine.recognize_images([to_pixels(im) for im in images], alternatives=True))
+        crops = [to_pixels(im) for im in images]
+        return self._recognitions_alt(*self.engine.recognize_images(crops, alternatives=True, **self._allowed(allowed, len(crops))))
 
-    def recognize_bgr_alternatives(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None) -> List[Recognition]:
+    def recognize_bgr_alternatives(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
+                                   allowed=None) -> List[Recognition]:
         """``recognize_bgr`` with confidences and alternatives."""
         from .queue_worker import rotation_code
         self._check_alternatives()
@@ -398,13 +477,16 @@ class MangaOcr:
             if len(orientations) != len(crops):
                 raise ValueError(f"recognize_bgr_alternatives: {len(crops)} crops but {len(orientations)} orientations")
             rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
-        return self._recognitions_alt(*self.engine.recognize_images(crops, True, rot, alternatives=True))
+        return self._recognitions_alt(*self.engine.recognize_images(crops, True, rot, alternatives=True,
+                                                                    **self._allowed(allowed, len(crops))))
 
-    def recognize_regions_alternatives(self, pages_bgr: Sequence[np.ndarray], regions) -> List[Recognition]:
+    def recognize_regions_alternatives(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None) -> List[Recognition]:
         """``recognize_regions`` with confidences and alternatives; a region reduced to a sliver gives text '', confidence
         0.0 and empty alternatives."""
         self._check_alternatives()
-        return self._recognitions_alt(*self.engine.recognize_regions(list(pages_bgr), list(regions), True, alternatives=True))
+        regions = list(regions)
+        return self._recognitions_alt(*self.engine.recognize_regions(list(pages_bgr), regions, True, alternatives=True,
+                                                                     **self._allowed(allowed, len(regions))))
 
     def recognize_page(self, page_bgr: np.ndarray, regions):
         """``_collect_manga_detections`` for one page: ``regions`` = the detector's (text, polygon) pairs."""

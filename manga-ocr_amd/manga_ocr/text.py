@@ -125,6 +125,22 @@ class Vocab:
     def __len__(self) -> int:
         return len(self.tokens)
 
+    def ids_for_chars(self, chars: Iterable[str]) -> List[int]:
+        """The ids of the tokens spelt with ``chars`` only - what a token set for "digits" or "kana" is built from
+        (``MangaOcr.token_set``).  A token counts when its text, taken with a leading ``##`` and all whitespace stripped,
+        is non-empty and every character of it is in ``chars``; special tokens never count.  The match is on the RAW token
+        text of ``vocab.txt``, before ``post_process``: a set for full-width digits must name the half-width digits too if
+        the vocabulary spells them so, because the half -> full-width step runs on the decoded string, after the decoder."""
+        allowed = set("".join(chars))
+        out = []
+        for i, t in enumerate(self.tokens):
+            if i in self.special_ids:
+                continue
+            body = "".join((t[2:] if t.startswith("##") else t).split())
+            if body and all(ch in allowed for ch in body):
+                out.append(i)
+        return out
+
     def decode(self, ids: Iterable[int], skip_special_tokens: bool = True) -> str:
         import numpy as np
         a = np.asarray(list(ids) if not hasattr(ids, "__len__") else ids, dtype=np.int64).ravel()

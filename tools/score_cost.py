@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """What the token scores cost: HIP-event time per greedy step of the LM head + token kernel, and of the whole decode step,
-unscored, scored and scored with token alternatives, for isolated batches (the engine's own profiler: an instrumented eager pass per repetition).
+unscored, scored and scored with token alternatives, each also under token constraints (every row a random half of the vocabulary), for isolated batches (the engine's own profiler: an instrumented eager pass per repetition).
 
-    python tools/score_cost.py [--rows 64,2560] [--max-len 64] [--reps 5] [--unscored-only | --no-alternatives]
+    python tools/score_cost.py [--rows 64,2560] [--max-len 64] [--reps 5] [--unscored-only | --no-alternatives] [--no-constraints]
 
 With MOCR_LIB pointing at a library built from another commit (--unscored-only when it has no scored exports,
---no-alternatives when it has no alternatives exports) the numbers of the two builds can be compared: the unscored and
+--no-alternatives when it has no alternatives exports, --no-constraints when it has no token-set exports) the numbers of the two builds can be compared: the unscored and
 the scored kernels are meant to be the same code.
 Prints one JSON line per (rows, mode): medians over the repetitions and their min .. max spread, in microseconds."""
 import argparse
@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--unscored-only", action="store_true")
     ap.add_argument("--no-alternatives", action="store_true")
+    ap.add_argument("--no-constraints", action="store_true")
     args = ap.parse_args()
 
     import ctypes as C
@@ -39,6 +40,9 @@ def main():
         _capi.SYMBOLS = {k: v for k, v in _capi.SYMBOLS.items() if "_scored" not in k and not k.endswith("_lse")}
     if args.unscored_only or args.no_alternatives:      # ... or without the alternatives exports
         _capi.SYMBOLS = {k: v for k, v in _capi.SYMBOLS.items() if "_alts" not in k and not k.endswith("_topk")}
+    constraints = not (args.unscored_only or args.no_alternatives or args.no_constraints)
+    if not constraints:         # ... or without the token-set exports
+        _capi.SYMBOLS = {k: v for k, v in _capi.SYMBOLS.items() if "token_set" not in k and "_constrained" not in k and not k.endswith("_masked")}
     from manga_ocr.engine import Engine
     from manga_ocr.weights import DEFAULT_SPEC, synthetic_weights
 
@@ -47,10 +51,13 @@ def main():
     for rows in [int(r) for r in args.rows.split(",")]:
         eng = Engine(w, DEFAULT_SPEC, dtype="bf16", device=0, max_batch=rows, lanes=1)
         gray = np.random.RandomState(rows).randint(0, 256, size=(rows, 224, 224), dtype=np.uint8)
-        for mode in ([0] if args.unscored_only else [0, 1] if args.no_alternatives else [0, 1, 2]):
+        half = eng.token_set(np.nonzero(np.random.RandomState(7).rand(DEFAULT_SPEC.vocab) < 0.5)[0]) if constraints else 0
+        modes = [0] if args.unscored_only else [0, 1] if args.no_alternatives else [0, 1, 2]
+        for mode, constrained in [(m, c) for c in ([False, True] if constraints else [False]) for m in modes]:
             scored = mode >= 1
-            call = (lambda: eng.recognize_gray(gray, args.max_len, alternatives=True)) if mode == 2 else \
-                (lambda: eng.recognize_gray(gray, args.max_len, scores=True)) if mode == 1 else (lambda: eng.recognize_gray(gray, args.max_len))
+            kw = dict(token_sets=half) if constrained else {}
+            call = (lambda: eng.recognize_gray(gray, args.max_len, alternatives=True, **kw)) if mode == 2 else \
+                (lambda: eng.recognize_gray(gray, args.max_len, scores=True, **kw)) if mode == 1 else (lambda: eng.recognize_gray(gray, args.max_len, **kw))
             call()                                           # warm: graphs, caches, clocks
             call()
             head, step, per = [], [], {}
@@ -61,7 +68,7 @@ def main():
                 call()
                 st = {s["name"]: s for s in eng.profile_get()}
                 lm = [s for n, s in st.items() if n in ("gemm_dec_vocab", "gemm_dec_vocab_lse", "gemm_dec_vocab_topk", "sm_vocab", "dec_token", "dec_token_lse",
-                                                              "dec_token_topk")]
+                                                              "dec_token_topk", "gemm_dec_vocab_m", "dec_token_m", "dec_token_lse_m", "dec_token_topk_m")]
                 dec = [s for n, s in st.items() if n.startswith(DECODE_PREFIXES) and n != "dec_token_first"]
                 assert all(s["launches"] % steps == 0 for s in lm), {n: s["launches"] for n, s in st.items()}
                 head.append(1e3 * sum(s["total_ms"] for s in lm) / steps)
@@ -69,7 +76,7 @@ def main():
                     per.setdefault(s["name"], []).append(1e3 * s["total_ms"] / steps)
                 step.append(1e3 * sum(s["total_ms"] for s in dec) / steps)
             eng.profile_enable(False)
-            print(json.dumps(dict(rows=rows, max_len=args.max_len, scored=scored, alternatives=mode == 2, reps=args.reps,
+            print(json.dumps(dict(rows=rows, max_len=args.max_len, scored=scored, alternatives=mode == 2, constrained=constrained, reps=args.reps,
                                   lm_head_plus_token_us=round(statistics.median(head), 2), lm_head_spread_us=[round(min(head), 2), round(max(head), 2)],
                                   decode_step_us=round(statistics.median(step), 2), decode_step_spread_us=[round(min(step), 2), round(max(step), 2)],
                                   per_kernel_us={n: round(statistics.median(v), 2) for n, v in sorted(per.items())},
