@@ -235,6 +235,35 @@ int mocr_recognize_regions_constrained(mocr_engine* e, const mocr_image* pages, 
                                        int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
                                        float* out_alt_logp, const int32_t* sets);
 
+/* ---- no-repeat n-grams ------------------------------------------------------------------------
+ * The published checkpoint's generation config carries no_repeat_ngram_size = 3; under greedy decoding it is what stops a
+ * decoder that has fallen into a loop (repeated-character bubbles) from running to max_len.  The rule is that of
+ * transformers' NoRepeatNGramLogitsProcessor applied to greedy search.  Per row n = its size, 0 = off.  The row holds L
+ * tokens ids[0 .. L-1], the start token included; the step that chooses ids[L] bans a set of tokens:
+ *   L + 1 < n   nothing is banned;
+ *   otherwise   { ids[i+n-1] : 0 <= i <= L-n and ids[i .. i+n-2] == ids[L-n+1 .. L-1] };
+ *   n = 1       the key is empty: every token already in the row is banned, the start token too.
+ * A banned token counts as a logit of -inf before the argmax and before the softmax of that step, exactly as a token outside
+ * the row's token set does (token constraints, above); the effective set of a step is the row's set minus the bans:
+ *   ids           the argmax over what is left, equal logits the lowest id;
+ *   scores        and the four alternatives are renormalised over what is left; entry 0 of the alternatives stays the
+ *                 emitted id.
+ * EOS cannot be banned (an unfinished row's history never holds it), so every step keeps a finite maximum.  The start token,
+ * the pad ids of finished rows, the max_len stop and mocr_decode_logits are untouched.  n is per crop and one batch may mix
+ * any values (the scheduler merges requests); a row with n = 0 and set MOCR_TOKEN_SET_ALL, also inside a batch with rows
+ * that do have bans, gives ids, scores and alternatives bit-identical to an unconstrained batch of the same mode and size.
+ * The bans depend on the row's own history, so the engine keeps one effective mask per row on the device and the token
+ * kernel rebuilds it after every token, inside the captured decode steps.
+ *
+ * The *_norepeat entry points: the *_constrained twins plus `ngram`, a HOST array of one size per crop (per region), null =
+ * all 0; with `ngram` null they ARE the constrained calls.  A size outside 0 .. the engine's max_len: MOCR_ERR_ARG. */
+int mocr_recognize_images_norepeat(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                                   float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets,
+                                   const int32_t* ngram);
+int mocr_recognize_regions_norepeat(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                    int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                    float* out_alt_logp, const int32_t* sets, const int32_t* ngram);
+
 /* Preprocessing only (test hook): out_gray [n, image_size, image_size] uint8 (host) = the plane the encoder sees
  * in each of its three equal input channels before the 1/255 and (x - 0.5)/0.5 scaling. */
 int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t* out_gray);
@@ -255,6 +284,10 @@ int mocr_recognize_device_alts(mocr_engine* e, const void* d_gray, int32_t n, vo
 /* ... plus `sets`, a HOST array of n token-set handles (token constraints, see above; nullable). */
 int mocr_recognize_device_constrained(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
                                       void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets);
+/* ... plus `ngram`, a HOST array of n no-repeat n-gram sizes (no-repeat n-grams, see above; nullable). */
+int mocr_recognize_device_norepeat(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
+                                   void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets,
+                                   const int32_t* ngram);
 /* generate(max_length=...) of every batch submitted from now on, whatever the entry point (2 <= max_len <= the
  * engine's max_len; rows are still max_len wide; mocr_recognize_gray_host's own argument overrides it).  The reference always calls generate with 300; a speech bubble is
  * typically ~32 tokens (SURVEY.md §8d reports both regimes). */
@@ -280,6 +313,9 @@ int mocr_recognize_gray_host_alts(mocr_engine* e, const uint8_t* gray, int32_t n
 int mocr_recognize_gray_host_constrained(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
                                          int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
                                          const int32_t* sets);   /* + token constraints */
+int mocr_recognize_gray_host_norepeat(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                      int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
+                                      const int32_t* sets, const int32_t* ngram);   /* + no-repeat n-grams */
 
 /* Single operators on device buffers of the engine's dtype (kernel unit tests). */
 int mocr_op_gemm(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, void* d_out,
@@ -384,6 +420,21 @@ int mocr_op_dec_token_topk(mocr_engine* e, const mocr_token_args* a, const float
 int mocr_op_dec_token_masked(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
                              const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
                              const uint32_t* d_tok_mask, const int32_t* d_set_of_row);
+/* The token step with no-repeat n-grams: mocr_op_dec_token_masked plus d_row_mask uint32 [rows][vocab / 32] (in / out: the
+ * effective set of every ROW's next step), d_base_mask uint32 [sets][vocab / 32] with d_base_set_of_row int32 [rows] (the
+ * rows' token sets, which a rebuilt mask starts from) and d_ngram_of_row int32 [rows] (the rows' sizes, 0 = off).  The step
+ * itself is the masked one on d_tok_mask / d_set_of_row - the engine passes d_tok_mask = d_row_mask and d_set_of_row = 0, 1,
+ * 2, ... so that a row reads its own mask; then, for every unfinished row with n > 0, row_mask[row] = its base set minus the
+ * bans of the step that follows the token just stored (the rule above, on the row's ids).  Other rows' masks are left as
+ * they are.  The four new pointers all NULL is mocr_op_dec_token_masked. */
+int mocr_op_dec_token_ngram(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                            const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
+                            const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
+                            const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row);
+/* The start of a batch with no-repeat n-grams: d_row_mask[row] = d_base_mask[d_base_set_of_row[row]] for rows [0, rows), with
+ * the start token's bit cleared where d_ngram_of_row[row] == 1 (the first generated token already sees L = 1). */
+int mocr_op_ngram_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
+                       const int32_t* d_ngram_of_row, int32_t rows);
 /* The LM head's fused argmax GEMM (tile 64 or 128, not split): d_cand_val / d_cand_idx [M][N / tile] = per row and N-tile
  * the largest acc + bias and its column (the lowest column on a tie).  dA holds M rounded up to the tile. */
 int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,

@@ -129,6 +129,10 @@ struct LaneCtx {
     int* alt_ids = nullptr; float* alt_logp = nullptr;  // [Bp][max_len][4] the four best tokens of every step / their log-probabilities, by row like ids
     // token constraints: allocated by the first constrained batch (ensure_set_buffer)
     int* set_of_row = nullptr;                      // [Bp] constrained batches: the token set of every row, by row like ids
+    // no-repeat n-grams: allocated by the first batch with a row of n > 0 (ensure_ngram_buffers)
+    unsigned* row_mask = nullptr;                   // [Bp][V / 32] the effective set of every row's next step (base set minus the bans), by row
+    int* row_ident = nullptr;                       // [Bp] 0, 1, 2, ...: the "set of every row" that makes the masked kernels read row_mask[row]
+    int* ngram_of_row = nullptr;                    // [Bp] no_repeat_ngram_size of every row (0: off), by row
     float *x_f32 = nullptr, *a_f32 = nullptr, *c_f32 = nullptr;
     float* ln_stats = nullptr;                      // small-batch path: (mean, rstd) per row of the three pre-LayerNorm sums, [3][Bp][2]
     void *x_t = nullptr, *a_t = nullptr, *c_t = nullptr, *ctx_t = nullptr, *h_t = nullptr, *z_t = nullptr;
@@ -158,6 +162,7 @@ struct Job {
     float* out_alt_logp = nullptr;  // every position and their log-probabilities; host or device like out_ids
     bool out_host = false;
     std::vector<int32_t> sets;      // token constraints (the *_constrained entry points): one set handle per crop; empty = all MOCR_TOKEN_SET_ALL
+    std::vector<int32_t> ngram;     // no-repeat n-grams (the *_norepeat entry points): one size per crop; empty = all 0
 };
 
 struct Lane {
@@ -172,6 +177,9 @@ struct Lane {
     bool constrained = false;       // a row of this batch decodes under a token set other than MOCR_TOKEN_SET_ALL: its steps run the
                                     // masked (EPI_*_M / MASK) form of the mode's LM head and token kernel
     std::vector<int> h_sets;        // the upload of set_of_row stages from here
+    bool ngram = false;             // a row of this batch has no_repeat_ngram_size > 0: the batch is `constrained` on the per-row masks
+                                    // (row_mask through row_ident) and its token kernel is the NGRAM one, which rebuilds them
+    std::vector<int> h_ngram;       // the upload of ngram_of_row stages from here
     int t = 0, steps = 0, chunk = 0;
     bool finishing = false;         // a flag of this batch has reported a finished row: rows are leaving, chunks get shorter
     bool flag_pending[2] = {false, false};
@@ -225,7 +233,7 @@ struct mocr_engine : LaneCtx {
     unsigned* tok_table = nullptr;
     std::vector<std::vector<uint32_t>> tok_sets;
     std::map<std::vector<uint32_t>, int> tok_index;
-    // decode-step HIP graphs, keyed by (lane, rows, (max_len, context bucket, constrained, mode 0 / 1 / 2), steps per graph)
+    // decode-step HIP graphs, keyed by (lane, rows, (max_len, context bucket, n-gram, constrained, mode 0 / 1 / 2), steps per graph)
     std::map<std::tuple<int, int, int, int, int>, hipGraphExec_t> graphs;      // + the regime
     void bind(int i) { static_cast<LaneCtx&>(*this) = lanes[i].ctx; }
     void unbind(int i) { lanes[i].ctx = static_cast<LaneCtx&>(*this); }
@@ -998,7 +1006,7 @@ void launch_dec_bias_gelu(mocr_engine* e, const float* slabs, int nslab, long lo
 }
 
 static DecState make_state(mocr_engine* e, int max_len, const int* forced, int forced_T, float* logits_out, int n_real,
-                           int mode = 0, bool constrained = false) {
+                           int mode = 0, bool constrained = false, bool ngram = false) {
     DecState st{};
     st.n_real = n_real;
     st.ids = e->ids; st.step = e->step; st.finished = e->finished; st.len = e->len; st.n_unfinished = e->n_unf;
@@ -1009,6 +1017,10 @@ static DecState make_state(mocr_engine* e, int max_len, const int* forced, int f
     st.scores = mode >= 1 ? e->scores : nullptr;
     st.alt_ids = mode >= 2 ? e->alt_ids : nullptr; st.alt_logp = mode >= 2 ? e->alt_logp : nullptr;
     st.tok_mask = constrained ? e->tok_table : nullptr; st.set_of_row = constrained ? e->set_of_row : nullptr;
+    if (ngram) {        // the masked kernels read the row's own mask; the sets become the base the NGRAM token kernel rebuilds it from
+        st.tok_mask = e->row_mask; st.set_of_row = e->row_ident;
+        st.row_mask = e->row_mask; st.base_mask = e->tok_table; st.base_set_of_row = e->set_of_row; st.ngram_of_row = e->ngram_of_row;
+    }
     return st;
 }
 
@@ -1028,7 +1040,9 @@ void launch_dec_token(mocr_engine* e, const DecState& st, const DecTokenArgs& a,
     auto& w = e->w;
     if constexpr (!FIRST) {
         if (st.tok_mask) {      // token constraints: the MASK form of the mode's kernel
-            ProfScope ps(e, st.alt_ids ? "dec_token_topk_m" : st.scores ? "dec_token_lse_m" : "dec_token_m", 0, (double)n * e->V * 4 * a.nslab);
+            ProfScope ps(e, st.row_mask ? (st.alt_ids ? "dec_token_topk_ng" : st.scores ? "dec_token_lse_ng" : "dec_token_ng")
+                                        : (st.alt_ids ? "dec_token_topk_m" : st.scores ? "dec_token_lse_m" : "dec_token_m"),
+                         0, (double)n * e->V * 4 * a.nslab);
             auto launch = [&](auto kernel) {
                 hipLaunchKernelGGL(kernel, dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab,
                                    a.slab_stride, a.vbias, e->V, st, w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32,
@@ -1036,7 +1050,12 @@ void launch_dec_token(mocr_engine* e, const DecState& st, const DecTokenArgs& a,
                                    a.ncand ? a.cand_val : nullptr, a.ncand ? a.cand_idx : nullptr, a.ncand, a.cache8, a.inv8,
                                    a.ncand ? a.cand_sum : nullptr, a.ncand ? a.top_val : nullptr, a.ncand ? a.top_idx : nullptr);
             };
-            if (st.alt_ids) launch(dec_token_kernel<T, 768, false, true, true, true>);
+            if (st.row_mask) {      // no-repeat n-grams: the NGRAM form, which also rebuilds the row's mask for the next step
+                if (st.alt_ids) launch(dec_token_kernel<T, 768, false, true, true, true, true>);
+                else if (st.scores) launch(dec_token_kernel<T, 768, false, true, false, true, true>);
+                else launch(dec_token_kernel<T, 768, false, false, false, true, true>);
+            }
+            else if (st.alt_ids) launch(dec_token_kernel<T, 768, false, true, true, true>);
             else if (st.scores) launch(dec_token_kernel<T, 768, false, true, false, true>);
             else launch(dec_token_kernel<T, 768, false, false, false, true>);
             HIPCHECK(hipGetLastError());
@@ -1639,8 +1658,9 @@ hipGraphExec_t decode_graph(mocr_engine* e, const DecState& st, int n, int steps
     // ... and by the mode of the steps (0 ids only, 1 scored, 2 scored with alternatives: another LM-head epilogue and token
     // kernel each): a graph captured in one mode is never replayed in another
     // ... and by whether they are the constrained ones (the masked forms of both)
-    const int mode = (st.alt_ids ? 2 : st.scores ? 1 : 0) + (st.tok_mask ? 4 : 0);
-    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * 8 + mode, steps, e->rrows(n));
+    // ... and by whether the masks are the per-row ones of the no-repeat n-grams (other pointers, the NGRAM token kernel)
+    const int mode = (st.alt_ids ? 2 : st.scores ? 1 : 0) + (st.tok_mask ? 4 : 0) + (st.row_mask ? 8 : 0);
+    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * 16 + mode, steps, e->rrows(n));
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) return it->second;
     hipGraph_t g = nullptr;
@@ -1723,6 +1743,38 @@ static void ensure_set_buffer(mocr_engine* e) {
     if (!e->set_of_row) e->set_of_row = e->dalloc<int>((size_t)e->Bp);
 }
 
+// The device table of the token sets, row 0 (MOCR_TOKEN_SET_ALL) all ones: allocated by the first set or the first batch with
+// no-repeat n-grams, whose rows' base sets are rows of it.
+static void ensure_tok_table(mocr_engine* e) {
+    if (e->tok_table) return;
+    const size_t words = (size_t)e->V / 32;
+    e->tok_table = e->dalloc<unsigned>((size_t)MOCR_MAX_TOKEN_SETS * words);
+    e->tok_sets.push_back(std::vector<uint32_t>(words, 0xffffffffu));        // set 0: the whole vocabulary
+    e->tok_index[e->tok_sets[0]] = MOCR_TOKEN_SET_ALL;
+    HIPCHECK(hipMemcpy(e->tok_table, e->tok_sets[0].data(), words * sizeof(uint32_t), hipMemcpyHostToDevice));
+}
+
+// The per-row masks of the no-repeat n-grams, for the bound lane: allocated by the first batch that has a row with n > 0, like
+// the alternatives buffers (768 B a row).
+static void ensure_ngram_buffers(mocr_engine* e) {
+    if (e->row_mask) return;
+    const size_t Bp = (size_t)e->Bp;
+    e->row_mask = e->dalloc<unsigned>(Bp * (e->V / 32));
+    e->ngram_of_row = e->dalloc<int>(Bp);
+    e->row_ident = e->dalloc<int>(Bp);
+    std::vector<int> ident(Bp);
+    for (size_t i = 0; i < Bp; ++i) ident[i] = (int)i;
+    HIPCHECK(hipMemcpy(e->row_ident, ident.data(), Bp * sizeof(int), hipMemcpyHostToDevice));
+}
+
+static void launch_ngram_init(mocr_engine* e, unsigned* row_mask, const unsigned* base_mask, const int* base_set_of_row,
+                              const int* ngram_of_row, int rows) {
+    ProfScope ps(e, "ngram_init", 0, (double)rows * (e->V / 32) * 8);
+    hipLaunchKernelGGL(ngram_init_kernel, dim3(rows), dim3(192), 0, e->stream, row_mask, base_mask, base_set_of_row, ngram_of_row, rows,
+                       e->V / 32, e->cfg.start_id);
+    HIPCHECK(hipGetLastError());
+}
+
 template <typename T>
 void start_batch(mocr_engine* e, Lane& L) {
     const int IMG = e->cfg.image_size;
@@ -1771,6 +1823,11 @@ void start_batch(mocr_engine* e, Lane& L) {
     L.constrained = false;
     for (const Job& j : L.jobs)
         for (int32_t h : j.sets) L.constrained = L.constrained || h != MOCR_TOKEN_SET_ALL;
+    // no-repeat n-grams: a batch with a row of n > 0 is constrained too - on per-row masks, which start as the rows' sets
+    L.ngram = false;
+    for (const Job& j : L.jobs)
+        for (int32_t g : j.ngram) L.ngram = L.ngram || g > 0;
+    L.constrained = L.constrained || L.ngram;
     if (L.constrained) {
         ensure_set_buffer(e);
         L.h_sets.assign((size_t)L.np, MOCR_TOKEN_SET_ALL);
@@ -1780,6 +1837,18 @@ void start_batch(mocr_engine* e, Lane& L) {
             r0 += j.n;
         }
         HIPCHECK(hipMemcpyAsync(e->set_of_row, L.h_sets.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    }
+    if (L.ngram) {
+        ensure_tok_table(e);
+        ensure_ngram_buffers(e);
+        L.h_ngram.assign((size_t)L.np, 0);
+        int r0 = 0;
+        for (const Job& j : L.jobs) {
+            std::copy(j.ngram.begin(), j.ngram.end(), L.h_ngram.begin() + r0);
+            r0 += j.n;
+        }
+        HIPCHECK(hipMemcpyAsync(e->ngram_of_row, L.h_ngram.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        launch_ngram_init(e, e->row_mask, e->tok_table, e->set_of_row, e->ngram_of_row, L.np);
     }
     // The decode steps run on np >= n rows (graph_rows): the padding rows are born finished, emit pad_id and read
     // whatever the workspace holds for them (finite values; no kernel mixes rows).
@@ -1871,7 +1940,7 @@ void advance(mocr_engine* e, Lane& L) {
         }
     }
     if (L.t >= L.steps) { finish_batch(e, L); return; }
-    DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n, L.mode, L.constrained);
+    DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n, L.mode, L.constrained, L.ngram);
     // (while rows are leaving, half-length chunks: the count a compaction acts on is at most 4 + 4 steps old instead of 8 + 8;
     // a batch none of whose rows has finished - the synthetic-weights headline - keeps the long chunks)
     const int chunk = L.finishing ? std::min(chunk_steps(L.np), CHUNK / 2) : chunk_steps(L.np);
@@ -2464,6 +2533,23 @@ static std::vector<int32_t> job_sets(const int32_t* sets, size_t base, int n) {
     return {};
 }
 
+// ---- no-repeat n-grams --------------------------------------------------------------------------
+// one size per crop (null: every crop 0 = off), each in 0 .. the engine's max_len
+static void require_ngram(const mocr_engine* e, const int32_t* ngram, int n) {
+    if (!ngram) return;
+    for (int i = 0; i < n; ++i)
+        if (ngram[i] < 0 || ngram[i] > e->cfg.max_len) throw ArgError{"no_repeat_ngram_size outside 0 .. max_len", MOCR_ERR_ARG};
+}
+
+// rows [base, base + n) of a request's sizes, for the job that decodes them (empty: all 0)
+static std::vector<int32_t> job_ngram(const int32_t* ngram, size_t base, int n) {
+    if (!ngram) return {};
+    std::vector<int32_t> v(ngram + base, ngram + base + n);
+    for (int32_t g : v)
+        if (g > 0) return v;
+    return {};
+}
+
 int mocr_token_set_create(mocr_engine* e, const int32_t* ids, int32_t n_ids, int32_t* out_set) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
@@ -2478,12 +2564,7 @@ int mocr_token_set_create(mocr_engine* e, const int32_t* ids, int32_t n_ids, int
         const int eos = e->cfg.eos_id;       // a recogniser that cannot stop is useless: EOS is in every set
         if (eos >= 0 && eos < e->V) bits[eos >> 5] |= 1u << (eos & 31);
         HIPCHECK(hipSetDevice(e->cfg.device));
-        if (!e->tok_table) {
-            e->tok_table = e->dalloc<unsigned>((size_t)MOCR_MAX_TOKEN_SETS * words);
-            e->tok_sets.push_back(std::vector<uint32_t>(words, 0xffffffffu));        // set 0: the whole vocabulary
-            e->tok_index[e->tok_sets[0]] = MOCR_TOKEN_SET_ALL;
-            HIPCHECK(hipMemcpy(e->tok_table, e->tok_sets[0].data(), words * sizeof(uint32_t), hipMemcpyHostToDevice));
-        }
+        ensure_tok_table(e);
         const auto it = e->tok_index.find(bits);
         if (it != e->tok_index.end()) { *out_set = it->second; return; }
         if ((int)e->tok_sets.size() >= MOCR_MAX_TOKEN_SETS) throw ArgError{"mocr_token_set_create: the set table is full", MOCR_ERR_ARG};
@@ -2508,13 +2589,15 @@ static void require_alt_pair(const void* alt_ids, const void* alt_logp) {
         throw ArgError{"out_alt_ids and out_alt_logp must be both null or both set", MOCR_ERR_ARG};
 }
 
-int mocr_recognize_device_constrained(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
-                                      void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets) {
+int mocr_recognize_device_norepeat(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
+                                   void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets,
+                                   const int32_t* ngram) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_alt_pair(d_out_alt_ids, d_out_alt_logp);
         require_ready(e, n);
         require_sets(e, sets, n);
+        require_ngram(e, ngram, n);
         if (!d_gray || !d_out_ids || !d_out_len) throw ArgError{"null device pointer", MOCR_ERR_ARG};
         HIPCHECK(hipSetDevice(e->cfg.device));
         Job j;
@@ -2524,8 +2607,14 @@ int mocr_recognize_device_constrained(mocr_engine* e, const void* d_gray, int32_
         j.out_logp = reinterpret_cast<float*>(d_out_logp);
         j.out_alt_ids = reinterpret_cast<int32_t*>(d_out_alt_ids); j.out_alt_logp = reinterpret_cast<float*>(d_out_alt_logp);
         j.sets = job_sets(sets, 0, n);
+        j.ngram = job_ngram(ngram, 0, n);
         submit(e, j);
     });
+}
+
+int mocr_recognize_device_constrained(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
+                                      void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets) {
+    return mocr_recognize_device_norepeat(e, d_gray, n, d_out_ids, d_out_len, d_out_logp, d_out_alt_ids, d_out_alt_logp, sets, nullptr);
 }
 
 int mocr_recognize_device_alts(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp,
@@ -2544,7 +2633,7 @@ int mocr_recognize_device(mocr_engine* e, const void* d_gray, int32_t n, void* d
 static void recognize_host_chunks(mocr_engine* e, const uint8_t* images, int n, int h, int w, int64_t row_stride,
                                   int64_t image_stride, int channels, int max_len, int32_t* out_ids, int32_t* out_len,
                                   float* out_logp = nullptr, int32_t* out_alt_ids = nullptr, float* out_alt_logp = nullptr,
-                                  const int32_t* sets = nullptr) {
+                                  const int32_t* sets = nullptr, const int32_t* ngram = nullptr) {
     const int IMG = e->cfg.image_size;
     if (h != IMG || w != IMG)
         throw ArgError{"crops must be image_size x image_size (resize with PIL BILINEAR on the caller side)", MOCR_ERR_UNSUPPORTED};
@@ -2561,6 +2650,7 @@ static void recognize_host_chunks(mocr_engine* e, const uint8_t* images, int n, 
         j.out_alt_ids = out_alt_ids ? out_alt_ids + (size_t)base * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
         j.out_alt_logp = out_alt_ids ? out_alt_logp + (size_t)base * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
         j.sets = job_sets(sets, (size_t)base, j.n);
+        j.ngram = job_ngram(ngram, (size_t)base, j.n);
         e->pending.push_back(j);
     }
     drive(e);
@@ -2576,19 +2666,27 @@ int mocr_recognize(mocr_engine* e, const uint8_t* images, int32_t n, int32_t h, 
     });
 }
 
-int mocr_recognize_gray_host_constrained(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
-                                         int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
-                                         const int32_t* sets) {
+int mocr_recognize_gray_host_norepeat(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                      int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
+                                      const int32_t* sets, const int32_t* ngram) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_alt_pair(out_alt_ids, out_alt_logp);
         require_ready(e, n, false);
         require_sets(e, sets, n);
+        require_ngram(e, ngram, n);
         HIPCHECK(hipSetDevice(e->cfg.device));
         const int IMG = e->cfg.image_size;
         recognize_host_chunks(e, gray, n, IMG, IMG, IMG, (int64_t)IMG * IMG, 1, max_len_override, out_ids, out_len, out_logp,
-                              out_alt_ids, out_alt_logp, sets);
+                              out_alt_ids, out_alt_logp, sets, ngram);
     });
+}
+
+int mocr_recognize_gray_host_constrained(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                         int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
+                                         const int32_t* sets) {
+    return mocr_recognize_gray_host_norepeat(e, gray, n, max_len_override, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, sets,
+                                             nullptr);
 }
 
 int mocr_recognize_gray_host_alts(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
@@ -2769,7 +2867,7 @@ static void preprocess_images(mocr_engine* e, const mocr_image* imgs, int n, uin
 // so the host never blocks on a preparation.  r02 prepared ALL crops, synchronised, and only then started to decode.
 static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& srcs, const PrepView* views, int n, int32_t* out_ids,
                                int32_t* out_len, float* out_logp = nullptr, int32_t* out_alt_ids = nullptr,
-                               float* out_alt_logp = nullptr, const int32_t* sets = nullptr) {
+                               float* out_alt_logp = nullptr, const int32_t* sets = nullptr, const int32_t* ngram = nullptr) {
     const size_t plane = (size_t)e->cfg.image_size * e->cfg.image_size;
     const int C = std::min(e->cfg.max_batch, 4096), nchunks = (n + C - 1) / C;
     uint8_t* const d_gray = (uint8_t*)e->grow(e->rs_gray, (size_t)n * plane);
@@ -2784,6 +2882,7 @@ static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& sr
         j.out_alt_ids = out_alt_ids ? out_alt_ids + (size_t)k * C * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
         j.out_alt_logp = out_alt_ids ? out_alt_logp + (size_t)k * C * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
         j.sets = job_sets(sets, (size_t)k * C, j.n);
+        j.ngram = job_ngram(ngram, (size_t)k * C, j.n);
         e->pending.push_back(j);
     };
     std::vector<PrepHold> holds(nchunks);
@@ -2838,13 +2937,15 @@ int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t
     });
 }
 
-int mocr_recognize_images_constrained(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
-                                      float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets) {
+int mocr_recognize_images_norepeat(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                                   float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets,
+                                   const int32_t* ngram) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_alt_pair(out_alt_ids, out_alt_logp);
         require_ready(e, n, false);
         require_sets(e, sets, n);
+        require_ngram(e, ngram, n);
         if (!images || !out_ids || !out_len) throw ArgError{"null pointer", MOCR_ERR_ARG};
         HIPCHECK(hipSetDevice(e->cfg.device));
         drive(e);
@@ -2854,8 +2955,13 @@ int mocr_recognize_images_constrained(mocr_engine* e, const mocr_image* images, 
             srcs[i] = source_of(images[i]);
             views[i] = PrepView{i, 0, 0, srcs[i].w, srcs[i].h, srcs[i].rot};
         }
-        prepare_and_decode(e, srcs, views.data(), n, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, sets);
+        prepare_and_decode(e, srcs, views.data(), n, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, sets, ngram);
     });
+}
+
+int mocr_recognize_images_constrained(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                                      float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets) {
+    return mocr_recognize_images_norepeat(e, images, n, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, sets, nullptr);
 }
 
 int mocr_recognize_images_alts(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
@@ -2885,13 +2991,14 @@ static bool padded_region(const mocr_region& r, int page_h, int page_w, PrepView
     return true;
 }
 
-int mocr_recognize_regions_constrained(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
-                                       int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
-                                       float* out_alt_logp, const int32_t* sets) {
+int mocr_recognize_regions_norepeat(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                    int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                    float* out_alt_logp, const int32_t* sets, const int32_t* ngram) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_alt_pair(out_alt_ids, out_alt_logp);
         require_sets(e, sets, std::max(n_regions, 0));
+        require_ngram(e, ngram, std::max(n_regions, 0));
         if (!e->committed) throw ArgError{"weights not committed (mocr_commit_weights)", MOCR_ERR_STATE};
         if (!pages || n_pages < 1 || n_regions < 0 || (n_regions > 0 && (!regions || !out_ids || !out_len)))
             throw ArgError{"bad argument", MOCR_ERR_ARG};
@@ -2903,6 +3010,7 @@ int mocr_recognize_regions_constrained(mocr_engine* e, const mocr_image* pages, 
         std::vector<PrepView> views;
         std::vector<int> where(n_regions, -1);          // region -> its row among the recognised crops (-1: sliver)
         std::vector<int32_t> view_sets;                 // the recognised crops' token sets
+        std::vector<int32_t> view_ngram;                // ... and no-repeat n-gram sizes
         for (int i = 0; i < n_regions; ++i) {
             const mocr_region& r = regions[i];
             if (r.page < 0 || r.page >= n_pages) throw ArgError{"region of an unknown page", MOCR_ERR_ARG};
@@ -2911,6 +3019,7 @@ int mocr_recognize_regions_constrained(mocr_engine* e, const mocr_image* pages, 
             where[i] = (int)views.size();
             views.push_back(v);
             if (sets) view_sets.push_back(sets[i]);
+            if (ngram) view_ngram.push_back(ngram[i]);
         }
         const int L = e->cfg.max_len, nv = (int)views.size();
         std::vector<int32_t> ids((size_t)nv * L), lens(nv);
@@ -2921,7 +3030,7 @@ int mocr_recognize_regions_constrained(mocr_engine* e, const mocr_image* pages, 
         if (nv > 0)
             prepare_and_decode(e, srcs, views.data(), nv, ids.data(), lens.data(), out_logp ? logp.data() : nullptr,
                                out_alt_ids ? alt_ids.data() : nullptr, out_alt_ids ? alt_logp.data() : nullptr,
-                               sets ? view_sets.data() : nullptr);
+                               sets ? view_sets.data() : nullptr, ngram ? view_ngram.data() : nullptr);
         for (int i = 0; i < n_regions; ++i) {
             int32_t* row = out_ids + (size_t)i * L;
             if (where[i] < 0) {
@@ -2943,6 +3052,13 @@ int mocr_recognize_regions_constrained(mocr_engine* e, const mocr_image* pages, 
             }
         }
     });
+}
+
+int mocr_recognize_regions_constrained(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                       int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                       float* out_alt_logp, const int32_t* sets) {
+    return mocr_recognize_regions_norepeat(e, pages, n_pages, regions, n_regions, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp,
+                                           sets, nullptr);
 }
 
 int mocr_recognize_regions_alts(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
@@ -3273,9 +3389,24 @@ int mocr_op_dec_bias_gelu(mocr_engine* e, const float* d_slabs, int32_t nslab, c
     });
 }
 
-int mocr_op_dec_token_masked(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
-                             const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
-                             const uint32_t* d_tok_mask, const int32_t* d_set_of_row) {
+int mocr_op_ngram_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
+                       const int32_t* d_ngram_of_row, int32_t rows) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!e->committed || !d_row_mask || !d_base_mask || !d_base_set_of_row || !d_ngram_of_row || rows < 1 || e->V % 32)
+            throw ArgError{"mocr_op_ngram_init: bad argument", MOCR_ERR_ARG};
+        launch_ngram_init(e, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows);
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_op_dec_token_ngram(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                            const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
+                            const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
+                            const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -3289,7 +3420,9 @@ int mocr_op_dec_token_masked(mocr_engine* e, const mocr_token_args* a, const flo
             (!first && a->ncand <= 0 && (!a->slabs || a->nslab < 1)) || (a->forced && a->forced_T < 1) ||
             (d_scores && (first || a->forced || (a->ncand > 0 && !d_cand_sum))) ||
             ((d_alt_ids == nullptr) != (d_alt_logp == nullptr)) || (d_alt_ids && (!d_scores || (a->ncand > 0 && (!d_top_val || !d_top_idx)))) ||
-            ((d_tok_mask == nullptr) != (d_set_of_row == nullptr)) || (d_tok_mask && (first || a->forced)))
+            ((d_tok_mask == nullptr) != (d_set_of_row == nullptr)) || (d_tok_mask && (first || a->forced)) ||
+            ((d_row_mask == nullptr) != (d_base_mask == nullptr)) || ((d_row_mask == nullptr) != (d_base_set_of_row == nullptr)) ||
+            ((d_row_mask == nullptr) != (d_ngram_of_row == nullptr)) || (d_row_mask && !d_tok_mask))
             throw ArgError{"mocr_op_dec_token: bad argument", MOCR_ERR_ARG};
         DecState st{};
         st.n_real = a->n_real;
@@ -3301,6 +3434,7 @@ int mocr_op_dec_token_masked(mocr_engine* e, const mocr_token_args* a, const flo
         st.scores = d_scores;
         st.alt_ids = d_alt_ids; st.alt_logp = d_alt_logp;
         st.tok_mask = d_tok_mask; st.set_of_row = d_set_of_row;
+        st.row_mask = d_row_mask; st.base_mask = d_base_mask; st.base_set_of_row = d_base_set_of_row; st.ngram_of_row = d_ngram_of_row;
         DecTokenArgs t{};
         t.slabs = a->slabs; t.nslab = first ? 0 : a->nslab; t.slab_stride = (long long)a->n * e->V;
         t.vbias = a->vbias ? a->vbias : e->w.bv;
@@ -3318,6 +3452,13 @@ int mocr_op_dec_token_masked(mocr_engine* e, const mocr_token_args* a, const flo
         });
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
+}
+
+int mocr_op_dec_token_masked(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                             const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
+                             const uint32_t* d_tok_mask, const int32_t* d_set_of_row) {
+    return mocr_op_dec_token_ngram(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row,
+                                   nullptr, nullptr, nullptr, nullptr);
 }
 
 int mocr_op_dec_token_topk(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,

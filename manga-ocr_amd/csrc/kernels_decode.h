@@ -134,6 +134,15 @@ struct DecState {
     // moves nothing.  A token outside its row's set counts as a logit of -inf in the argmax, the softmax and the alternatives.
     const unsigned* tok_mask;
     const int* set_of_row;
+    // No-repeat n-grams (nullable, all four or none): row_mask [B][V / 32], the EFFECTIVE set of every row's next step = its
+    // base set base_mask[base_set_of_row[row]] minus the tokens that would complete an n-gram the row already holds
+    // (n = ngram_of_row[row], 0: off).  All by ROW like ids.  Such a state has tok_mask = row_mask and set_of_row = the
+    // identity, so the LM head and the MASK code of the token kernel read a row's own mask; ngram_init_kernel fills it at the
+    // start of a batch and the NGRAM token kernel rebuilds it after every token.
+    unsigned* row_mask;
+    const unsigned* base_mask;
+    const int* base_set_of_row;
+    const int* ngram_of_row;
 };
 
 // End of a decode step, one block per sequence:
@@ -156,7 +165,18 @@ struct DecState {
 //   summed logits take -inf where the set's bit is clear (one nibble of one word per float4), before the argmax; in the
 //   alternatives they carry the index sentinel too.  EOS is in every set, so the row's max is finite; a set of fewer than
 //   four tokens leaves (-inf, sentinel) entries, written as id -1 / log-probability -inf.
-template <typename T, int D, bool FIRST, bool SCORES = false, bool TOPK = false, bool MASK = false>
+// NGRAM = true (st.row_mask / base_mask / base_set_of_row / ngram_of_row set; implies MASK): no_repeat_ngram_size of
+//   transformers' NoRepeatNGramLogitsProcessor under greedy search.  The step's own masking is the MASK code above, on
+//   st.tok_mask = st.row_mask through the identity st.set_of_row.  Once thread 0 has stored the token, the row holds
+//   L = t + 2 tokens and the block rebuilds row_mask[row] for the step that will choose ids[L]: the 192 words of the base set
+//   go to LDS, the threads split the windows i = 0 .. L - n, a window whose n - 1 key tokens equal the row's last n - 1
+//   clears the bit of its follower ids[i + n - 1] (LDS atomic AND), and the words go back with plain vector stores.  n = 1
+//   has an empty key: every token of the row is banned.  L + 1 < n (and L + 1 = n) has no window: the base set is written.
+//   A finished row and a row with n = 0 (its mask is its base set since ngram_init_kernel) skip all of it.  An unfinished
+//   row's history never holds EOS, so EOS is never banned and the row's max stays finite.
+//   Slab path: every read of the row's mask for THIS step (the nibbles above) precedes the argmax reduction's
+//   __syncthreads, and the rewrite follows the barrier behind thread 0's token, so no thread reads a word already rewritten.
+template <typename T, int D, bool FIRST, bool SCORES = false, bool TOPK = false, bool MASK = false, bool NGRAM = false>
 __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict__ slabs, int nslab, long long slab_stride,
                                                         const float* __restrict__ vbias, int V,
                                                         DecState st,
@@ -173,6 +193,10 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                                                         const int* __restrict__ top_idx = nullptr) {
     static_assert(!TOPK || (SCORES && !FIRST), "alternatives come with scores, from the second token on");
     static_assert(!MASK || !FIRST, "the start token is not constrained");
+    static_assert(!NGRAM || MASK, "the n-gram bans are applied through the row's mask");
+    constexpr int MW = 192;                             // mask words of a row (vocab 6144)
+    __shared__ __attribute__((aligned(16))) unsigned s_mask[NGRAM ? MW : 4];
+    __shared__ int s_ng, s_L;                           // NGRAM: the row's n (0: leave the mask alone) and its token count
     __shared__ float s_val[4];
     __shared__ int s_idx[4];
     __shared__ float s_red[4];
@@ -327,9 +351,34 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
             }
             st.step[b] = t + 1;
             s_tok = tok; s_pos = t + 1;
+            if constexpr (NGRAM) {
+                // (a row that is or has just become finished keeps its mask: nothing reads it again; V != 32 MW or a token
+                // the row's stride did not take: no rebuild either)
+                const bool live = !fin && !st.finished[row] && t + 2 <= st.ids_ld && V == 32 * MW;
+                s_ng = live ? st.ngram_of_row[row] : 0;
+                s_L = t + 2;
+            }
         }
     }
     __syncthreads();
+    if constexpr (NGRAM) {
+        const int n = s_ng, L = s_L;                    // block-uniform
+        if (n > 0) {
+            const int* rid = st.ids + (size_t)row * st.ids_ld;      // ids[row][0 .. L - 1], the last one stored before the barrier
+            if (tid < MW) s_mask[tid] = st.base_mask[(size_t)st.base_set_of_row[row] * MW + tid];
+            __syncthreads();
+            const int* key = rid + (L - n + 1);         // the row's last n - 1 tokens
+            for (int i = tid; i <= L - n; i += 256) {
+                bool same = true;
+                for (int k = 0; k < n - 1 && same; ++k) same = rid[i + k] == key[k];
+                const int ban = rid[i + n - 1];
+                if (same && (unsigned)ban < (unsigned)V) atomicAnd(&s_mask[ban >> 5], ~(1u << (ban & 31)));
+            }
+            __syncthreads();
+            if (tid < MW / 4)
+                reinterpret_cast<uint4*>(st.row_mask + (size_t)row * MW)[tid] = reinterpret_cast<const uint4*>(s_mask)[tid];
+        }
+    }
     const int tok = s_tok, ps = s_pos;
     // embedding + LayerNorm of the next input, block-wide over D = 768 (3 per thread)
     constexpr int PER = D / 256;
@@ -362,6 +411,21 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
         elem<T>::st(x_t + (size_t)b * D + d, o);
         if (cache) elem<T>::st(cache + (size_t)row * cache_batch_stride + (size_t)ps * D + d, o);   // layer-0 key/value source
         if (cache8) cache8[(size_t)row * cache_batch_stride + (size_t)ps * D + d] = (uint8_t)(pack4_fp8(o * inv_sx8, 0.f, 0.f, 0.f) & 0xff);
+    }
+}
+
+// Start of a batch with no-repeat n-grams, one block of 192 threads per row: row_mask[row] = the row's base set.  The first
+// generated token is chosen with L = 1 token in the row (the start token): n = 1 bans it already, n >= 2 bans nothing yet.
+__global__ __launch_bounds__(192) void ngram_init_kernel(unsigned* __restrict__ row_mask, const unsigned* __restrict__ base_mask,
+                                                         const int* __restrict__ base_set_of_row, const int* __restrict__ ngram_of_row,
+                                                         int rows, int words, int start_id) {
+    const int row = blockIdx.x;
+    if (row >= rows) return;
+    const bool ban_start = ngram_of_row[row] == 1 && (unsigned)start_id < (unsigned)(words * 32);
+    for (int w = threadIdx.x; w < words; w += blockDim.x) {
+        unsigned m = base_mask[(size_t)base_set_of_row[row] * words + w];
+        if (ban_start && w == (start_id >> 5)) m &= ~(1u << (start_id & 31));
+        row_mask[(size_t)row * words + w] = m;
     }
 }
 

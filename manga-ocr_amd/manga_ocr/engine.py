@@ -157,6 +157,24 @@ class Engine:
             raise ValueError(f"token_sets: {n} crops but {a.size} set handles")
         return a
 
+    # ------------------------------------------------------------------ no-repeat n-grams
+    def _ngram(self, no_repeat_ngram, n: int) -> np.ndarray:
+        """``no_repeat_ngram=``: one size for every crop, or one size per crop -> int32 [n], each in 0 .. max_len"""
+        if isinstance(no_repeat_ngram, (bool, np.bool_)) or isinstance(no_repeat_ngram, str):
+            raise TypeError(f"no_repeat_ngram: an int or a sequence of ints, instead got {no_repeat_ngram!r}")
+        if isinstance(no_repeat_ngram, (int, np.integer)):
+            a = np.full(n, int(no_repeat_ngram), dtype=np.int64)
+        else:
+            a = np.asarray(list(no_repeat_ngram)).ravel()
+            if a.size != n:
+                raise ValueError(f"no_repeat_ngram: {n} crops but {a.size} sizes")
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise TypeError("no_repeat_ngram: the sizes must be ints")
+            a = a.astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() > self.spec.max_len):
+            raise ValueError(f"no_repeat_ngram: sizes must be in 0 .. max_len ({self.spec.max_len}), 0 = off")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
     def _constrained_blocks(self, n: int, scores: bool, alternatives: bool):
         """the output blocks of a *_constrained call (None where not asked) and what the caller gets back"""
         ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
@@ -172,7 +190,7 @@ class Engine:
         return np.full(shape, -1, dtype=np.int32), np.zeros(shape, dtype=np.float32)
 
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False,
-                         token_sets=None):
+                         token_sets=None, no_repeat_ngram=None):
         """Crops of any sizes (list of uint8 [h,w] / [h,w,3] arrays; `bgr`: 3-channel crops are in OpenCV order;
         `rotate`: per crop 0 / 1 (90 degrees clockwise) / 2 (counter-clockwise), applied on the device): luminance
         conversion and the Pillow-exact BILINEAR resize to 224x224 run on the device.
@@ -181,7 +199,18 @@ class Engine:
         With ``alternatives=True`` (ids, lengths, logp, alt_ids int32 [n,max_len,4], alt_logp float32 [n,max_len,4]): the four
         most probable tokens of every position and their log-probabilities (include/mocr.h, "token alternatives"); same ids.
         ``token_sets``: a handle of :meth:`token_set` for every crop, or one per crop - each crop is decoded under its set
-        (include/mocr.h, "token constraints"); the return value is shaped by ``scores`` / ``alternatives`` as above."""
+        (include/mocr.h, "token constraints"); the return value is shaped by ``scores`` / ``alternatives`` as above.
+        ``no_repeat_ngram``: transformers' ``no_repeat_ngram_size`` under greedy decoding, an int for every crop or one per
+        crop, 0 = off (include/mocr.h, "no-repeat n-grams"); combines with ``token_sets``."""
+        if no_repeat_ngram is not None and len(images) > 0:
+            descs, keep = self._image_descs(images, bgr, rotate)
+            n = len(keep)
+            ngram = self._ngram(no_repeat_ngram, n)
+            sets = self._sets(token_sets, n) if token_sets is not None else None
+            ids, lens, logp, alt_ids, alt_logp, out = self._constrained_blocks(n, scores, alternatives)
+            self._check(self.lib.mocr_recognize_images_norepeat(self._h, descs, n, _ptr(ids), _ptr(lens), _ptr(logp), _ptr(alt_ids),
+                                                                _ptr(alt_logp), _ptr(sets), _ptr(ngram)))
+            return out
         if token_sets is not None and len(images) > 0:
             descs, keep = self._image_descs(images, bgr, rotate)
             n = len(keep)
@@ -213,13 +242,14 @@ class Engine:
         return ids, lens
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False,
-                          token_sets=None):
+                          token_sets=None, no_repeat_ngram=None):
         """pages: list of uint8 [H,W,3] (or [H,W]) arrays; regions: iterable of (page_index, x, y, w, h) bounding
         rectangles.  Each page is uploaded once; the 8 %-padded, page-clipped crop of every region
         (``src/ui/main_window.py:9530-9540``) is cut on the device.  Returns (ids [n,max_len], lengths [n]);
         a region reduced to a sliver has length 0.  ``scores=True``: (ids, lengths, logp float32 [n,max_len]), a sliver's
         row all 0.  ``alternatives=True``: (ids, lengths, logp, alt_ids, alt_logp) as for recognize_images, a sliver's rows
-        all -1 / 0.  ``token_sets``: a set handle for every region, or one per region (see recognize_images)."""
+        all -1 / 0.  ``token_sets``: a set handle for every region, or one per region (see recognize_images);
+        ``no_repeat_ngram``: a no-repeat n-gram size for every region, or one per region (see recognize_images)."""
         regs = list(regions)
         n = len(regs)
         ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
@@ -232,6 +262,12 @@ class Engine:
         arr = (_capi.MocrRegion * n)()
         for i, (pg, x, y, w, h) in enumerate(regs):
             arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
+        if no_repeat_ngram is not None:
+            ngram = self._ngram(no_repeat_ngram, n)
+            sets = self._sets(token_sets, n) if token_sets is not None else None
+            self._check(self.lib.mocr_recognize_regions_norepeat(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens), _ptr(logp),
+                                                                 _ptr(alt_ids), _ptr(alt_logp), _ptr(sets), _ptr(ngram)))
+            return (ids, lens, logp, alt_ids, alt_logp) if alternatives else (ids, lens, logp) if scores else (ids, lens)
         if token_sets is not None:
             sets = self._sets(token_sets, n)
             self._check(self.lib.mocr_recognize_regions_constrained(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens), _ptr(logp),
@@ -273,10 +309,18 @@ class Engine:
         return out
 
     def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None, d_out_alt_ids=None, d_out_alt_logp=None, *,
-                         token_sets=None) -> None:
+                         token_sets=None, no_repeat_ngram=None) -> None:
         """Asynchronous; all are device buffers (torch CUDA tensors or raw addresses).  ``d_out_logp`` (float32
         [n,max_len]): also the token log-probabilities.  ``d_out_alt_ids`` (int32) with ``d_out_alt_logp`` (float32), both
-        [n,max_len,4]: also the token alternatives.  ``token_sets``: a set handle for every crop, or one per crop (host values)."""
+        [n,max_len,4]: also the token alternatives.  ``token_sets``: a set handle for every crop, or one per crop (host values).
+        ``no_repeat_ngram``: a no-repeat n-gram size for every crop, or one per crop (host values)."""
+        if no_repeat_ngram is not None:
+            ngram = self._ngram(no_repeat_ngram, n)
+            sets = self._sets(token_sets, n) if token_sets is not None else None
+            self._check(self.lib.mocr_recognize_device_norepeat(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len),
+                                                                _ptr(d_out_logp), _ptr(d_out_alt_ids), _ptr(d_out_alt_logp), _ptr(sets),
+                                                                _ptr(ngram)))
+            return
         if token_sets is not None:
             sets = self._sets(token_sets, n)
             self._check(self.lib.mocr_recognize_device_constrained(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len),
@@ -295,9 +339,17 @@ class Engine:
         self._check(self.lib.mocr_set_generate_max_length(self._h, int(max_len)))
 
     def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False, alternatives: bool = False,
-                       token_sets=None):
+                       token_sets=None, no_repeat_ngram=None):
         a = np.ascontiguousarray(gray, dtype=np.uint8)
         n = a.shape[0]
+        if no_repeat_ngram is not None:
+            ngram = self._ngram(no_repeat_ngram, n)
+            sets = self._sets(token_sets, n) if token_sets is not None else None
+            ids, lens, logp, alt_ids, alt_logp, out = self._constrained_blocks(n, scores, alternatives)
+            self._check(self.lib.mocr_recognize_gray_host_norepeat(self._h, _ptr(a), n, max_len or self.spec.max_len, _ptr(ids),
+                                                                   _ptr(lens), _ptr(logp), _ptr(alt_ids), _ptr(alt_logp), _ptr(sets),
+                                                                   _ptr(ngram)))
+            return out
         if token_sets is not None:
             sets = self._sets(token_sets, n)
             ids, lens, logp, alt_ids, alt_logp, out = self._constrained_blocks(n, scores, alternatives)
@@ -416,6 +468,25 @@ class Engine:
         self._check(self.lib.mocr_op_dec_token_masked(self._h, C.byref(a), _ptr(d_cand_sum), _ptr(d_scores), _ptr(d_top_val),
                                                       _ptr(d_top_idx), _ptr(d_alt_ids), _ptr(d_alt_logp), _ptr(d_tok_mask),
                                                       _ptr(d_set_of_row)))
+
+    def op_dec_token_ngram(self, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row,
+                           d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, **kw) -> None:
+        """The token step with no-repeat n-grams: op_dec_token_masked plus the per-row masks (in / out), the base sets and the
+        rows' sizes; the engine passes d_tok_mask = d_row_mask and d_set_of_row = 0, 1, 2, ..."""
+        a = _capi.MocrTokenArgs()
+        a.struct_size = C.sizeof(_capi.MocrTokenArgs)
+        for name, value in kw.items():
+            ftype = dict(_capi.MocrTokenArgs._fields_)[name]
+            setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
+        self._check(self.lib.mocr_op_dec_token_ngram(self._h, C.byref(a), _ptr(d_cand_sum), _ptr(d_scores), _ptr(d_top_val),
+                                                     _ptr(d_top_idx), _ptr(d_alt_ids), _ptr(d_alt_logp), _ptr(d_tok_mask),
+                                                     _ptr(d_set_of_row), _ptr(d_row_mask), _ptr(d_base_mask), _ptr(d_base_set_of_row),
+                                                     _ptr(d_ngram_of_row)))
+
+    def op_ngram_init(self, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows: int) -> None:
+        """Start of a batch with no-repeat n-grams: every row's mask = its base set (n = 1: minus the start token)."""
+        self._check(self.lib.mocr_op_ngram_init(self._h, _ptr(d_row_mask), _ptr(d_base_mask), _ptr(d_base_set_of_row),
+                                                _ptr(d_ngram_of_row), int(rows)))
 
     def op_gemm_argmax_masked(self, dA, dW, d_bias, d_cand_val, d_cand_idx, d_cand_sum, d_top_val, d_top_idx, M, N, K, tile,
                               d_tok_mask, d_set_of_row, d_rowmap=None) -> None:

@@ -87,6 +87,46 @@ def _set_handles(allowed, n: int) -> Optional[List[int]]:
     return hs
 
 
+def resolve_no_repeat_ngram(value, ignored: dict, max_len: int):
+    """``MangaOcr(no_repeat_ngram_size=...)`` -> (the size every call uses by default, or None for today's behaviour; what is
+    left of the checkpoint's ignored generation settings).  ``None``: nothing changes.  An int in 0 .. max_len: that size (0 =
+    off), whatever the checkpoint says - the checkpoint's own value then stays listed as ignored.  ``"checkpoint"``: the
+    checkpoint's ``no_repeat_ngram_size`` (0 when its config has none), which is then honoured and leaves the ignored
+    settings; the beam settings stay there."""
+    ignored = dict(ignored)
+    if value is None:
+        return None, ignored
+    if isinstance(value, str):
+        if value != "checkpoint":
+            raise ValueError(f"no_repeat_ngram_size: None, an int or 'checkpoint', instead got {value!r}")
+        value = ignored.pop("no_repeat_ngram_size", 0)
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        raise TypeError(f"no_repeat_ngram_size: None, an int or 'checkpoint', instead got {value!r}")
+    if not 0 <= int(value) <= max_len:
+        raise ValueError(f"no_repeat_ngram_size must be in 0 .. max_len ({max_len}), 0 = off; got {value}")
+    return int(value), ignored
+
+
+def _ngram_sizes(no_repeat_ngram, default, n: int) -> Optional[List[int]]:
+    """``no_repeat_ngram=`` of a call (None: the constructor's ``default``, itself None for "not used"), one size for all
+    ``n`` crops or one per crop -> None / n sizes"""
+    if no_repeat_ngram is None:
+        no_repeat_ngram = default
+    if no_repeat_ngram is None:
+        return None
+    if isinstance(no_repeat_ngram, (bool, np.bool_, str)):
+        raise TypeError(f"no_repeat_ngram: an int or a sequence of ints, instead got {no_repeat_ngram!r}")
+    if isinstance(no_repeat_ngram, (int, np.integer)):
+        gs = [int(no_repeat_ngram)] * n
+    else:
+        gs = [int(g) for g in no_repeat_ngram]
+        if len(gs) != n:
+            raise ValueError(f"no_repeat_ngram: {n} crops but {len(gs)} sizes")
+    if any(g < 0 for g in gs):
+        raise ValueError("no_repeat_ngram: sizes must be >= 0 (0 = off)")
+    return gs
+
+
 @dataclass(frozen=True)
 class Recognition:
     """One recognised crop with the recogniser's own confidence (the ``*_scored`` methods of :class:`MangaOcr`).
@@ -151,7 +191,8 @@ class _Batcher:
     what it asked for: ids, or (ids, logp).  The same one kind further for token alternatives: the batch makes the richest
     call any of its requests asked for, and such a caller gets (ids, logp, alt_ids, alt_logp).  A request may also carry a
     token set (``allowed=``); only a batch with such a request passes ``token_sets=`` - one handle per crop, 0 for the others -
-    to the engine, so batches nobody constrains make exactly the calls they always made."""
+    to the engine, so batches nobody constrains make exactly the calls they always made.  The same for a no-repeat n-gram size
+    (``no_repeat_ngram=``): only a batch with a request of size > 0 passes ``no_repeat_ngram=``, one size per crop."""
 
     def __init__(self, engine: Engine, max_batch: int, timeout_ms: float):
         self.engine, self.max_batch, self.timeout = engine, max_batch, timeout_ms / 1000.0
@@ -161,12 +202,14 @@ class _Batcher:
         self._thread = threading.Thread(target=self._run, name="mocr-batcher", daemon=True)
         self._thread.start()
 
-    def submit(self, gray: np.ndarray, scored: bool = False, alternatives: bool = False, token_set: int = 0) -> Future:
+    def submit(self, gray: np.ndarray, scored: bool = False, alternatives: bool = False, token_set: int = 0,
+               no_repeat_ngram: int = 0) -> Future:
         f: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
-            self._q.append((gray, f, 2 if alternatives else 1 if scored else 0, int(token_set)))     # the kind of request, its set
+            # the kind of request, its set, its no-repeat n-gram size
+            self._q.append((gray, f, 2 if alternatives else 1 if scored else 0, int(token_set), int(no_repeat_ngram)))
             self._cv.notify()
         return f
 
@@ -185,24 +228,27 @@ class _Batcher:
                     self._cv.wait(left)
                 batch, self._q = self._q[:self.max_batch], self._q[self.max_batch:]
             try:
-                kind = max(k for _, _, k, _ in batch)
-                sets = [h for _, _, _, h in batch]
+                kind = max(k for _, _, k, _, _ in batch)
+                sets = [h for _, _, _, h, _ in batch]
                 extra = dict(token_sets=sets) if any(sets) else {}
+                sizes = [g for _, _, _, _, g in batch]
+                if any(sizes):
+                    extra["no_repeat_ngram"] = sizes
                 logp = alt_ids = alt_logp = None
                 if kind == 2:
-                    ids, lens, logp, alt_ids, alt_logp = self.engine.recognize_images([g for g, _, _, _ in batch], alternatives=True, **extra)
+                    ids, lens, logp, alt_ids, alt_logp = self.engine.recognize_images([g for g, _, _, _, _ in batch], alternatives=True, **extra)
                 elif kind == 1:
-                    ids, lens, logp = self.engine.recognize_images([g for g, _, _, _ in batch], scores=True, **extra)
+                    ids, lens, logp = self.engine.recognize_images([g for g, _, _, _, _ in batch], scores=True, **extra)
                 else:
-                    ids, lens = self.engine.recognize_images([g for g, _, _, _ in batch], **extra)
-                for i, (_, f, k, _) in enumerate(batch):
+                    ids, lens = self.engine.recognize_images([g for g, _, _, _, _ in batch], **extra)
+                for i, (_, f, k, _, _) in enumerate(batch):
                     n = lens[i]
                     if k == 2:
                         f.set_result((ids[i, :n].copy(), logp[i, :n].copy(), alt_ids[i, :n].copy(), alt_logp[i, :n].copy()))
                     else:
                         f.set_result((ids[i, :n].copy(), logp[i, :n].copy()) if k else ids[i, :n].copy())
             except BaseException as exc:  # every waiting caller gets the error; the loop lives on
-                for _, f, _, _ in batch:
+                for _, f, _, _, _ in batch:
                     if not f.done():
                         f.set_exception(exc)
 
@@ -231,11 +277,15 @@ class MangaOcr:
     def __init__(self, pretrained_model_name_or_path: str = DEFAULT_MODEL, force_cpu: bool = False, *,
                  dtype: Optional[str] = None, device: Optional[int] = None, devices: Optional[Sequence[int]] = None,
                  max_batch: Optional[int] = None, lanes: Optional[int] = None, batch_timeout_ms: Optional[float] = None,
-                 synthetic_seed: Optional[int] = None):
+                 synthetic_seed: Optional[int] = None, no_repeat_ngram_size=None):
         """``MangaOcr()`` as the application calls it (``src/ui/main_window.py:3394``) builds the engine on this
         process's GPU with two lanes and an internal batch sized from the free HBM.  ``devices=[0, 1, ...]`` (or
         ``MANGA_OCR_DEVICES=0,1,...``) instead starts one child process per GPU and shards every batch call over
-        them (``manga_ocr/multi.py``); the parent then never touches a GPU."""
+        them (``manga_ocr/multi.py``); the parent then never touches a GPU.
+        ``no_repeat_ngram_size``: transformers' setting of that name under this engine's greedy decoding (include/mocr.h,
+        "no-repeat n-grams") for every call that does not say otherwise (``no_repeat_ngram=``): None = not used, as always; an
+        int; or ``"checkpoint"`` = the value in the checkpoint's generation config, which then leaves
+        ``ignored_generation_config`` (the beam settings stay ignored)."""
         if force_cpu:
             raise RuntimeError("this MangaOcr is the MI355X engine: there is no CPU path (force_cpu=True is not supported)")
         dtype = dtype or os.environ.get("MANGA_OCR_DTYPE", "bf16")
@@ -267,7 +317,11 @@ class MangaOcr:
         # what the checkpoint's config.json asked of generate() and this engine ignores (greedy decode only): the reference
         # application's recogniser would honour e.g. num_beams=4 / no_repeat_ngram_size=3, so on such a checkpoint the
         # strings can differ from the pip package's; {} when there is nothing to report
-        self.ignored_generation_config = dict(getattr(spec, "ignored_generation", ()))
+        self.no_repeat_ngram_size, self.ignored_generation_config = resolve_no_repeat_ngram(
+            no_repeat_ngram_size, dict(getattr(spec, "ignored_generation", ())), spec.max_len)
+        if self.no_repeat_ngram_size and devices is not None and len(devices) > 1:
+            from .multi import MultiGpuEngine
+            raise NotImplementedError(MultiGpuEngine.NO_NGRAM)
         if devices is not None and len(devices) > 1:
             from .multi import MultiGpuEngine
             max_batch = int(max_batch or 2048)
@@ -295,7 +349,7 @@ class MangaOcr:
 
     # ------------------------------------------------------------------ reference call surface
     def __call__(self, img_or_path) -> str:
-        ids = self._batcher.submit(to_pixels(self._open(img_or_path))).result()
+        ids = self._batcher.submit(to_pixels(self._open(img_or_path)), **self._single(None, None)).result()
         return ids_to_text(self.vocab, ids)
 
     # ------------------------------------------------------------------ token constraints
@@ -338,21 +392,45 @@ class MangaOcr:
             raise NotImplementedError(no)
         return dict(token_sets=hs)
 
+    # ------------------------------------------------------------------ no-repeat n-grams
+    def _decode_kw(self, allowed, no_repeat_ngram, n: int) -> dict:
+        """the engine keywords of ``allowed=`` and ``no_repeat_ngram=`` ({} when neither is in use: the call the method always
+        made); a call's ``no_repeat_ngram`` overrides the constructor's ``no_repeat_ngram_size`` (0 = off for this call)"""
+        kw = self._allowed(allowed, n)
+        gs = _ngram_sizes(no_repeat_ngram, getattr(self, "no_repeat_ngram_size", None), n)
+        if gs is not None and any(gs):
+            no = getattr(self.engine, "NO_NGRAM", None)      # MultiGpuEngine
+            if no:
+                raise NotImplementedError(no)
+            kw["no_repeat_ngram"] = gs
+        return kw
+
+    def _single(self, allowed, no_repeat_ngram) -> dict:
+        """the batcher keywords of one crop's ``allowed=`` / ``no_repeat_ngram=``"""
+        kw = self._decode_kw(allowed, no_repeat_ngram, 1)
+        out = {}
+        if "token_sets" in kw:
+            out["token_set"] = kw["token_sets"][0]
+        if "no_repeat_ngram" in kw:
+            out["no_repeat_ngram"] = kw["no_repeat_ngram"][0]
+        return out
+
     # ------------------------------------------------------------------ batch surface (callers that hold many crops)
     def recognize_ids(self, crops: Sequence[np.ndarray], bgr: bool = False, rotate: Optional[Sequence[int]] = None, *,
-                      allowed=None) -> List[np.ndarray]:
+                      allowed=None, no_repeat_ngram=None) -> List[np.ndarray]:
         """uint8 crops of any sizes ([h,w] luminance or [h,w,3] RGB; BGR with ``bgr=True``; ``rotate``: per crop 0 / 1 (90
         degrees clockwise) / 2 (counter-clockwise), done by the device) -> token ids (without padding).  ``allowed``: a
-        token set of :meth:`token_set` for all crops, or one per crop."""
+        token set of :meth:`token_set` for all crops, or one per crop.  ``no_repeat_ngram``: the no-repeat n-gram size of this
+        call, an int for all crops or one per crop, 0 = off (None: the constructor's ``no_repeat_ngram_size``); every
+        ``recognize*`` method takes both."""
         crops = list(crops)
-        ids, lens = self.engine.recognize_images(crops, bgr, rotate, **self._allowed(allowed, len(crops)))
+        ids, lens = self.engine.recognize_images(crops, bgr, rotate, **self._decode_kw(allowed, no_repeat_ngram, len(crops)))
         return [ids[i, :lens[i]].copy() for i in range(len(lens))]
 
-    def recognize(self, img_or_path, *, allowed=None) -> str:
-        """``__call__`` (which keeps the reference's signature) with ``allowed=``: one crop decoded under a token set."""
-        if allowed is None:
-            return self(img_or_path)
-        ids = self._batcher.submit(to_pixels(self._open(img_or_path)), token_set=self._allowed(allowed, 1)["token_sets"][0]).result()
+    def recognize(self, img_or_path, *, allowed=None, no_repeat_ngram=None) -> str:
+        """``__call__`` (which keeps the reference's signature) with ``allowed=``: one crop decoded under a token set, and
+        ``no_repeat_ngram=``: this call's no-repeat n-gram size (None: the constructor's ``no_repeat_ngram_size``)."""
+        ids = self._batcher.submit(to_pixels(self._open(img_or_path)), **self._single(allowed, no_repeat_ngram)).result()
         return ids_to_text(self.vocab, ids)
 
     @staticmethod
@@ -364,17 +442,17 @@ class MangaOcr:
             return img_or_path
         raise ValueError(f"img_or_path must be a path or PIL.Image, instead got: {img_or_path}")
 
-    def recognize_batch(self, images: Sequence, *, allowed=None) -> List[str]:
+    def recognize_batch(self, images: Sequence, *, allowed=None, no_repeat_ngram=None) -> List[str]:
         """All crops of a page (or chapter) at once - what ``_collect_manga_detections``
         (``src/ui/main_window.py:9462-9476``) does one region at a time."""
-        return [ids_to_text(self.vocab, r) for r in self.recognize_ids([to_pixels(im) for im in images], allowed=allowed)]
+        return [ids_to_text(self.vocab, r) for r in self.recognize_ids([to_pixels(im) for im in images], allowed=allowed, no_repeat_ngram=no_repeat_ngram)]
 
-    def recognize_batch_arrays(self, crops: Sequence[np.ndarray], *, allowed=None) -> List[str]:
+    def recognize_batch_arrays(self, crops: Sequence[np.ndarray], *, allowed=None, no_repeat_ngram=None) -> List[str]:
         """uint8 arrays ([h,w] luminance or [h,w,3] RGB, any sizes) -> strings: what a caller that already holds numpy
         crops (the crop-job queue) uses instead of wrapping each one in a PIL image."""
-        return [ids_to_text(self.vocab, r) for r in self.recognize_ids(list(crops), allowed=allowed)]
+        return [ids_to_text(self.vocab, r) for r in self.recognize_ids(list(crops), allowed=allowed, no_repeat_ngram=no_repeat_ngram)]
 
-    def recognize_bgr(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *, allowed=None) -> List[str]:
+    def recognize_bgr(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *, allowed=None, no_repeat_ngram=None) -> List[str]:
         """BGR crops exactly as the crop tools and the worker hold them (``cropped_cv_img``, ``src/core/workers.py:300``):
         the BGR -> RGB swap of ``src/ui/main_window.py:9800`` is folded into the device's luminance conversion, and with
         ``orientations`` (the jobs' "Auto-Detect" / "Vertical" / "Horizontal" settings) the orientation-only rotation of
@@ -386,14 +464,14 @@ class MangaOcr:
             if len(orientations) != len(crops):        # zip() would truncate silently: a short list must not cost a decode
                 raise ValueError(f"recognize_bgr: {len(crops)} crops but {len(orientations)} orientations")
             rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
-        return [ids_to_text(self.vocab, r) for r in self.recognize_ids(crops, bgr=True, rotate=rot, allowed=allowed)]
+        return [ids_to_text(self.vocab, r) for r in self.recognize_ids(crops, bgr=True, rotate=rot, allowed=allowed, no_repeat_ngram=no_repeat_ngram)]
 
-    def recognize_regions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None) -> List[str]:
+    def recognize_regions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None) -> List[str]:
         """``regions``: (page_index, x, y, w, h) bounding rectangles on BGR pages; every page is uploaded once and
         the padded crops (``src/ui/main_window.py:9530-9540``) are cut on the device.  One string per region
         ('' for a region reduced to a sliver, like the reference)."""
         regions = list(regions)
-        ids, lens = self.engine.recognize_regions(list(pages_bgr), regions, True, **self._allowed(allowed, len(regions)))
+        ids, lens = self.engine.recognize_regions(list(pages_bgr), regions, True, **self._decode_kw(allowed, no_repeat_ngram, len(regions)))
         return [ids_to_text(self.vocab, ids[i, :lens[i]]) if lens[i] > 0 else "" for i in range(len(lens))]
 
     # ------------------------------------------------------------------ scored surface: the same recognitions + confidence
@@ -405,24 +483,24 @@ class MangaOcr:
     def _recognitions(self, ids, lens, logp) -> List[Recognition]:
         return [Recognition.from_row(self.vocab, ids[i], logp[i], lens[i]) for i in range(len(lens))]
 
-    def recognize_scored(self, img_or_path, *, allowed=None) -> Recognition:
+    def recognize_scored(self, img_or_path, *, allowed=None, no_repeat_ngram=None) -> Recognition:
         """``__call__`` with the recogniser's confidence: same text, plus the token log-probabilities computed on the
         device (include/mocr.h, "token scores").  Goes through the same batcher as ``__call__``; scored and unscored
         callers may share a batch."""
         self._check_scored()
         img = self._open(img_or_path)
-        extra = dict(token_set=self._allowed(allowed, 1)["token_sets"][0]) if allowed is not None else {}
+        extra = self._single(allowed, no_repeat_ngram)
         ids, logp = self._batcher.submit(to_pixels(img), scored=True, **extra).result()
         return Recognition.from_row(self.vocab, ids, logp, len(ids))
 
-    def recognize_batch_scored(self, images: Sequence, *, allowed=None) -> List[Recognition]:
+    def recognize_batch_scored(self, images: Sequence, *, allowed=None, no_repeat_ngram=None) -> List[Recognition]:
         """``recognize_batch`` with confidences."""
         self._check_scored()
         crops = [to_pixels(im) for im in images]
-        return self._recognitions(*self.engine.recognize_images(crops, scores=True, **self._allowed(allowed, len(crops))))
+        return self._recognitions(*self.engine.recognize_images(crops, scores=True, **self._decode_kw(allowed, no_repeat_ngram, len(crops))))
 
     def recognize_bgr_scored(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
-                             allowed=None) -> List[Recognition]:
+                             allowed=None, no_repeat_ngram=None) -> List[Recognition]:
         """``recognize_bgr`` with confidences."""
         from .queue_worker import rotation_code
         self._check_scored()
@@ -432,14 +510,14 @@ class MangaOcr:
             if len(orientations) != len(crops):
                 raise ValueError(f"recognize_bgr_scored: {len(crops)} crops but {len(orientations)} orientations")
             rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
-        return self._recognitions(*self.engine.recognize_images(crops, True, rot, scores=True, **self._allowed(allowed, len(crops))))
+        return self._recognitions(*self.engine.recognize_images(crops, True, rot, scores=True, **self._decode_kw(allowed, no_repeat_ngram, len(crops))))
 
-    def recognize_regions_scored(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None) -> List[Recognition]:
+    def recognize_regions_scored(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None) -> List[Recognition]:
         """``recognize_regions`` with confidences; a region reduced to a sliver gives text '' and confidence 0.0."""
         self._check_scored()
         regions = list(regions)
         return self._recognitions(*self.engine.recognize_regions(list(pages_bgr), regions, True, scores=True,
-                                                                 **self._allowed(allowed, len(regions))))
+                                                                 **self._decode_kw(allowed, no_repeat_ngram, len(regions))))
 
     # ------------------------------------------------------------------ alternatives surface: + the runners-up of every position
     def _check_alternatives(self) -> None:
@@ -450,24 +528,24 @@ class MangaOcr:
     def _recognitions_alt(self, ids, lens, logp, alt_ids, alt_logp) -> List[Recognition]:
         return [Recognition.from_row(self.vocab, ids[i], logp[i], lens[i], alt_ids[i], alt_logp[i]) for i in range(len(lens))]
 
-    def recognize_alternatives(self, img_or_path, *, allowed=None) -> Recognition:
+    def recognize_alternatives(self, img_or_path, *, allowed=None, no_repeat_ngram=None) -> Recognition:
         """``recognize_scored`` plus, for every generated position, the four most probable tokens and their log-probabilities
         (``Recognition.alt_ids`` / ``alt_logprobs`` / ``candidates``; include/mocr.h, "token alternatives").  Same text; goes
         through the same batcher as ``__call__``, and callers of all three kinds may share a batch."""
         self._check_alternatives()
         img = self._open(img_or_path)
-        extra = dict(token_set=self._allowed(allowed, 1)["token_sets"][0]) if allowed is not None else {}
+        extra = self._single(allowed, no_repeat_ngram)
         ids, logp, alt_ids, alt_logp = self._batcher.submit(to_pixels(img), alternatives=True, **extra).result()
         return Recognition.from_row(self.vocab, ids, logp, len(ids), alt_ids, alt_logp)
 
-    def recognize_batch_alternatives(self, images: Sequence, *, allowed=None) -> List[Recognition]:
+    def recognize_batch_alternatives(self, images: Sequence, *, allowed=None, no_repeat_ngram=None) -> List[Recognition]:
         """``recognize_batch`` with confidences and alternatives."""
         self._check_alternatives()
         crops = [to_pixels(im) for im in images]
-        return self._recognitions_alt(*self.engine.recognize_images(crops, alternatives=True, **self._allowed(allowed, len(crops))))
+        return self._recognitions_alt(*self.engine.recognize_images(crops, alternatives=True, **self._decode_kw(allowed, no_repeat_ngram, len(crops))))
 
     def recognize_bgr_alternatives(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
-                                   allowed=None) -> List[Recognition]:
+                                   allowed=None, no_repeat_ngram=None) -> List[Recognition]:
         """``recognize_bgr`` with confidences and alternatives."""
         from .queue_worker import rotation_code
         self._check_alternatives()
@@ -478,15 +556,15 @@ class MangaOcr:
                 raise ValueError(f"recognize_bgr_alternatives: {len(crops)} crops but {len(orientations)} orientations")
             rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
         return self._recognitions_alt(*self.engine.recognize_images(crops, True, rot, alternatives=True,
-                                                                    **self._allowed(allowed, len(crops))))
+                                                                    **self._decode_kw(allowed, no_repeat_ngram, len(crops))))
 
-    def recognize_regions_alternatives(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None) -> List[Recognition]:
+    def recognize_regions_alternatives(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None) -> List[Recognition]:
         """``recognize_regions`` with confidences and alternatives; a region reduced to a sliver gives text '', confidence
         0.0 and empty alternatives."""
         self._check_alternatives()
         regions = list(regions)
         return self._recognitions_alt(*self.engine.recognize_regions(list(pages_bgr), regions, True, alternatives=True,
-                                                                     **self._allowed(allowed, len(regions))))
+                                                                     **self._decode_kw(allowed, no_repeat_ngram, len(regions))))
 
     def recognize_page(self, page_bgr: np.ndarray, regions):
         """``_collect_manga_detections`` for one page: ``regions`` = the detector's (text, polygon) pairs."""

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """What the token scores cost: HIP-event time per greedy step of the LM head + token kernel, and of the whole decode step,
-unscored, scored and scored with token alternatives, each also under token constraints (every row a random half of the vocabulary), for isolated batches (the engine's own profiler: an instrumented eager pass per repetition).
+unscored, scored and scored with token alternatives, each also under token constraints (every row a random half of the vocabulary) and with no-repeat n-grams (n = 3 on every row, whole vocabulary: per-row masks instead of the shared table, rebuilt by the token kernel), for isolated batches (the engine's own profiler: an instrumented eager pass per repetition).
 
-    python tools/score_cost.py [--rows 64,2560] [--max-len 64] [--reps 5] [--unscored-only | --no-alternatives] [--no-constraints]
+    python tools/score_cost.py [--rows 64,2560] [--max-len 64] [--reps 5] [--unscored-only | --no-alternatives] [--no-constraints] [--no-ngram]
 
 With MOCR_LIB pointing at a library built from another commit (--unscored-only when it has no scored exports,
---no-alternatives when it has no alternatives exports, --no-constraints when it has no token-set exports) the numbers of the two builds can be compared: the unscored and
+--no-alternatives when it has no alternatives exports, --no-constraints when it has no token-set exports, --no-ngram when it has no n-gram exports) the numbers of the two builds can be compared: the unscored and
 the scored kernels are meant to be the same code.
 Prints one JSON line per (rows, mode): medians over the repetitions and their min .. max spread, in microseconds."""
 import argparse
@@ -32,6 +32,7 @@ def main():
     ap.add_argument("--unscored-only", action="store_true")
     ap.add_argument("--no-alternatives", action="store_true")
     ap.add_argument("--no-constraints", action="store_true")
+    ap.add_argument("--no-ngram", action="store_true")
     args = ap.parse_args()
 
     import ctypes as C
@@ -43,6 +44,9 @@ def main():
     constraints = not (args.unscored_only or args.no_alternatives or args.no_constraints)
     if not constraints:         # ... or without the token-set exports
         _capi.SYMBOLS = {k: v for k, v in _capi.SYMBOLS.items() if "token_set" not in k and "_constrained" not in k and not k.endswith("_masked")}
+    ngram = constraints and not args.no_ngram
+    if not ngram:               # ... or without the n-gram exports
+        _capi.SYMBOLS = {k: v for k, v in _capi.SYMBOLS.items() if "_norepeat" not in k and "ngram" not in k}
     from manga_ocr.engine import Engine
     from manga_ocr.weights import DEFAULT_SPEC, synthetic_weights
 
@@ -53,9 +57,10 @@ def main():
         gray = np.random.RandomState(rows).randint(0, 256, size=(rows, 224, 224), dtype=np.uint8)
         half = eng.token_set(np.nonzero(np.random.RandomState(7).rand(DEFAULT_SPEC.vocab) < 0.5)[0]) if constraints else 0
         modes = [0] if args.unscored_only else [0, 1] if args.no_alternatives else [0, 1, 2]
-        for mode, constrained in [(m, c) for c in ([False, True] if constraints else [False]) for m in modes]:
+        legs = [(m, c, 0) for c in ([False, True] if constraints else [False]) for m in modes] + ([(m, False, 3) for m in modes] if ngram else [])
+        for mode, constrained, ng in legs:
             scored = mode >= 1
-            kw = dict(token_sets=half) if constrained else {}
+            kw = dict(token_sets=half) if constrained else dict(no_repeat_ngram=ng) if ng else {}
             call = (lambda: eng.recognize_gray(gray, args.max_len, alternatives=True, **kw)) if mode == 2 else \
                 (lambda: eng.recognize_gray(gray, args.max_len, scores=True, **kw)) if mode == 1 else (lambda: eng.recognize_gray(gray, args.max_len, **kw))
             call()                                           # warm: graphs, caches, clocks
@@ -68,7 +73,8 @@ def main():
                 call()
                 st = {s["name"]: s for s in eng.profile_get()}
                 lm = [s for n, s in st.items() if n in ("gemm_dec_vocab", "gemm_dec_vocab_lse", "gemm_dec_vocab_topk", "sm_vocab", "dec_token", "dec_token_lse",
-                                                              "dec_token_topk", "gemm_dec_vocab_m", "dec_token_m", "dec_token_lse_m", "dec_token_topk_m")]
+                                                              "dec_token_topk", "gemm_dec_vocab_m", "dec_token_m", "dec_token_lse_m", "dec_token_topk_m",
+                                                              "dec_token_ng", "dec_token_lse_ng", "dec_token_topk_ng")]
                 dec = [s for n, s in st.items() if n.startswith(DECODE_PREFIXES) and n != "dec_token_first"]
                 assert all(s["launches"] % steps == 0 for s in lm), {n: s["launches"] for n, s in st.items()}
                 head.append(1e3 * sum(s["total_ms"] for s in lm) / steps)
@@ -76,7 +82,7 @@ def main():
                     per.setdefault(s["name"], []).append(1e3 * s["total_ms"] / steps)
                 step.append(1e3 * sum(s["total_ms"] for s in dec) / steps)
             eng.profile_enable(False)
-            print(json.dumps(dict(rows=rows, max_len=args.max_len, scored=scored, alternatives=mode == 2, constrained=constrained, reps=args.reps,
+            print(json.dumps(dict(rows=rows, max_len=args.max_len, scored=scored, alternatives=mode == 2, constrained=constrained, ngram=ng, reps=args.reps,
                                   lm_head_plus_token_us=round(statistics.median(head), 2), lm_head_spread_us=[round(min(head), 2), round(max(head), 2)],
                                   decode_step_us=round(statistics.median(step), 2), decode_step_spread_us=[round(min(step), 2), round(max(step), 2)],
                                   per_kernel_us={n: round(statistics.median(v), 2) for n, v in sorted(per.items())},
