@@ -264,6 +264,42 @@ int mocr_recognize_regions_norepeat(mocr_engine* e, const mocr_image* pages, int
                                     int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
                                     float* out_alt_logp, const int32_t* sets, const int32_t* ngram);
 
+/* ---- token positions ---------------------------------------------------------------------------
+ * Where in the crop each token was read: the cross-attention of the LAST decoder layer over the encoder's 14 x 14 patch
+ * grid, reduced to a centre, a spread and a mass per token.  One more output with the row layout of out_ids and one more axis,
+ *   out_pos float32 [n, max_len, MOCR_POSITION_FIELDS].
+ * For 1 <= t < out_len[r], with a_vec = the last layer's LayerNorm-1 output of the step that consumed ids[r][t-1] and emitted
+ * ids[r][t] (in the engine's dtype: the row the cross-attention query projection reads), q = a_vec Wq^T + bq and
+ * K = ENC[r] Wk^T + bk over the row's 197 encoder outputs (both of that layer):
+ *   p_h = softmax_k(q_h . K_h[k] / 8) per head h of 12, in fp32, the maximum subtracted;  a[k] = (1/12) sum_h p_h[k].
+ * Key 0 is CLS; key k >= 1 is the patch in grid row i = (k-1) / 14, column j = (k-1) % 14, at u = (j + 0.5) / 14,
+ * v = (i + 0.5) / 14.  The fields:
+ *   [MOCR_POS_CX]   sum_{k>=1} a[k] u_k / mass          [MOCR_POS_CY]   the same in v
+ *   [MOCR_POS_SX]   sqrt(max(0, sum_{k>=1} a[k] u_k^2 / mass - cx^2))    [MOCR_POS_SY]   the same in v
+ *   [MOCR_POS_MASS] sum_{k>=1} a[k] - a small mass says that the step looked at CLS and the position means little;
+ *                   below 1e-20: cx = cy = 0.5, sx = sy = 0.
+ * (The device computes the spread in the equal, better conditioned centred form sqrt(sum_{k>=1} a[k] (u_k - cx)^2 / mass).)
+ * Coordinates are fractions of the 224 x 224 plane the encoder sees: AFTER mocr_image.rotate, and for a region inside its
+ * padded, clipped rectangle.  For t = 0, for t >= out_len[r] and for every position of a sliver region (out_len 0) the five
+ * fields are 0; the EOS position is computed like any other.
+ * Asking for positions moves no id, length, score or alternative, and a batch in which nobody asks launches exactly what it
+ * launched before: the decode steps of a batch that does ask only record a_vec (768 values per row and step, a store the
+ * LayerNorm launch already had), and ONE batched pass computes every position when the batch has finished - each row's keys
+ * are read once, not once per step.  Requests with and without positions may share a batch; rows of requests that did not ask
+ * get nothing written.  The buffers are allocated by the first request that asks: per lane max_batch (rounded up to 128) x
+ * max_len x (768 elements of the engine's dtype + 20 B), plus at most 64 MiB of scratch whatever max_batch is.
+ *
+ * The *_positions entry points: the *_norepeat twins plus out_pos (a device pointer for mocr_recognize_device_positions); with
+ * out_pos null they ARE the norepeat calls. */
+#define MOCR_POSITION_FIELDS 5
+enum { MOCR_POS_CX = 0, MOCR_POS_CY = 1, MOCR_POS_SX = 2, MOCR_POS_SY = 3, MOCR_POS_MASS = 4 };
+int mocr_recognize_images_positions(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                                    float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets,
+                                    const int32_t* ngram, float* out_pos);
+int mocr_recognize_regions_positions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                     int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                     float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos);
+
 /* Preprocessing only (test hook): out_gray [n, image_size, image_size] uint8 (host) = the plane the encoder sees
  * in each of its three equal input channels before the 1/255 and (x - 0.5)/0.5 scaling. */
 int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t* out_gray);
@@ -288,6 +324,10 @@ int mocr_recognize_device_constrained(mocr_engine* e, const void* d_gray, int32_
 int mocr_recognize_device_norepeat(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
                                    void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets,
                                    const int32_t* ngram);
+/* ... plus d_out_pos, a device pointer to [n, max_len, MOCR_POSITION_FIELDS] float32 (token positions, see above; nullable). */
+int mocr_recognize_device_positions(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
+                                    void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets,
+                                    const int32_t* ngram, void* d_out_pos);
 /* generate(max_length=...) of every batch submitted from now on, whatever the entry point (2 <= max_len <= the
  * engine's max_len; rows are still max_len wide; mocr_recognize_gray_host's own argument overrides it).  The reference always calls generate with 300; a speech bubble is
  * typically ~32 tokens (SURVEY.md §8d reports both regimes). */
@@ -316,6 +356,10 @@ int mocr_recognize_gray_host_constrained(mocr_engine* e, const uint8_t* gray, in
 int mocr_recognize_gray_host_norepeat(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
                                       int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
                                       const int32_t* sets, const int32_t* ngram);   /* + no-repeat n-grams */
+
+int mocr_recognize_gray_host_positions(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                       int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
+                                       const int32_t* sets, const int32_t* ngram, float* out_pos);   /* + token positions */
 
 /* Single operators on device buffers of the engine's dtype (kernel unit tests). */
 int mocr_op_gemm(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, void* d_out,
@@ -435,6 +479,12 @@ int mocr_op_dec_token_ngram(mocr_engine* e, const mocr_token_args* a, const floa
  * the start token's bit cleared where d_ngram_of_row[row] == 1 (the first generated token already sees L = 1). */
 int mocr_op_ngram_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
                        const int32_t* d_ngram_of_row, int32_t rows);
+/* The positions kernel (token positions), launched through the helper the deferred pass uses: d_q [rows][T][768] queries and
+ * d_k [rows][197][768] keys in the engine's dtype, d_len [rows] int32 - positions 0 .. d_len[r] - 1 of row r are computed
+ * (at most T), the rest written as 0.  d_out_pos [rows][T][MOCR_POSITION_FIELDS] float32; d_out_map (nullable) float32
+ * [rows][T][197] = the head-mean map a.  Nothing behind a row's 197 keys is read. */
+int mocr_op_attn_positions(mocr_engine* e, const void* d_q, const void* d_k, const int32_t* d_len, int32_t rows, int32_t T,
+                           float* d_out_pos, float* d_out_map);
 /* The LM head's fused argmax GEMM (tile 64 or 128, not split): d_cand_val / d_cand_idx [M][N / tile] = per row and N-tile
  * the largest acc + bias and its column (the lowest column on a tie).  dA holds M rounded up to the tile. */
 int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,

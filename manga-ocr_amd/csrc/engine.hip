@@ -46,6 +46,7 @@
 #include "prep_pipeline.h"
 #include "kernels_qqt.h"
 #include "kernels_misc.h"
+#include "kernels_positions.h"
 
 namespace {
 
@@ -133,6 +134,12 @@ struct LaneCtx {
     unsigned* row_mask = nullptr;                   // [Bp][V / 32] the effective set of every row's next step (base set minus the bans), by row
     int* row_ident = nullptr;                       // [Bp] 0, 1, 2, ...: the "set of every row" that makes the masked kernels read row_mask[row]
     int* ngram_of_row = nullptr;                    // [Bp] no_repeat_ngram_size of every row (0: off), by row
+    // token positions: allocated by the first batch that asks (ensure_pos_buffers)
+    void* pos_hist = nullptr;                       // [Bp][max_len][768] T (+ one GEMM tile of rows): the last layer's LayerNorm-1 output of every
+                                                    // (row, input position), by row like ids - what the cross-attention query projection read.
+                                                    // A batch packs it as [rows][its generate(max_length)][768]
+    float* pos_out = nullptr;                       // [Bp][max_len][MOCR_POSITION_FIELDS] by row like ids
+    void *pos_q = nullptr, *pos_k = nullptr;        // deferred pass: queries / keys of POS_CHUNK rows at a time
     float *x_f32 = nullptr, *a_f32 = nullptr, *c_f32 = nullptr;
     float* ln_stats = nullptr;                      // small-batch path: (mean, rstd) per row of the three pre-LayerNorm sums, [3][Bp][2]
     void *x_t = nullptr, *a_t = nullptr, *c_t = nullptr, *ctx_t = nullptr, *h_t = nullptr, *z_t = nullptr;
@@ -163,6 +170,7 @@ struct Job {
     bool out_host = false;
     std::vector<int32_t> sets;      // token constraints (the *_constrained entry points): one set handle per crop; empty = all MOCR_TOKEN_SET_ALL
     std::vector<int32_t> ngram;     // no-repeat n-grams (the *_norepeat entry points): one size per crop; empty = all 0
+    float* out_pos = nullptr;       // nullable (the *_positions entry points): [n][max_len][MOCR_POSITION_FIELDS]; host or device like out_ids
 };
 
 struct Lane {
@@ -180,6 +188,7 @@ struct Lane {
     bool ngram = false;             // a row of this batch has no_repeat_ngram_size > 0: the batch is `constrained` on the per-row masks
                                     // (row_mask through row_ident) and its token kernel is the NGRAM one, which rebuilds them
     std::vector<int> h_ngram;       // the upload of ngram_of_row stages from here
+    bool positions = false;         // a job of this batch asked for token positions: its steps record pos_hist, finish_batch runs the deferred pass
     int t = 0, steps = 0, chunk = 0;
     bool finishing = false;         // a flag of this batch has reported a finished row: rows are leaving, chunks get shorter
     bool flag_pending[2] = {false, false};
@@ -215,6 +224,7 @@ struct mocr_engine : LaneCtx {
     // keeps the summation order it started with and a row's ids do not depend on when its neighbours finished.
     int regime = 0;
     int rrows(int n) const { return regime > 0 ? regime : n; }
+    bool rec_pos = false;           // the batch being decoded records pos_hist (token positions); set around its steps like `regime`
     bool use_latent(int n) const { return latent && n > classic_rows; }
     int smallm_rows = 0;            // bf16: batches of up to this many rows take the one-launch-per-projection path (kernels_smallm.h)
     bool use_smallm(int n) const { return n <= smallm_rows && !use_latent(n); }
@@ -233,7 +243,7 @@ struct mocr_engine : LaneCtx {
     unsigned* tok_table = nullptr;
     std::vector<std::vector<uint32_t>> tok_sets;
     std::map<std::vector<uint32_t>, int> tok_index;
-    // decode-step HIP graphs, keyed by (lane, rows, (max_len, context bucket, n-gram, constrained, mode 0 / 1 / 2), steps per graph)
+    // decode-step HIP graphs, keyed by (lane, rows, (max_len, context bucket, positions, n-gram, constrained, mode 0 / 1 / 2), steps per graph)
     std::map<std::tuple<int, int, int, int, int>, hipGraphExec_t> graphs;      // + the regime
     void bind(int i) { static_cast<LaneCtx&>(*this) = lanes[i].ctx; }
     void unbind(int i) { lanes[i].ctx = static_cast<LaneCtx&>(*this); }
@@ -978,7 +988,7 @@ void launch_dec_add_ln(mocr_engine* e, const DecAddLnArgs& a) {
 
 template <typename T>
 void dec_add_ln(mocr_engine* e, int nslab, int N, const float* bias, const float* resid, const float* g, const float* b,
-                float* out_f32, void* out_t, int rows, bool gelu, int cache_layer = -1) {
+                float* out_f32, void* out_t, int rows, bool gelu, int cache_layer = -1, void* hist = nullptr, int hist_len = 0) {
     DecAddLnArgs a{};
     a.slabs = e->slabs; a.nslab = nslab; a.slab_stride = (long long)e->Bp * N;
     a.bias = bias; a.resid = resid; a.g = g; a.b = b; a.out_f32 = out_f32; a.out_t = out_t; a.rows = rows; a.gelu = gelu;
@@ -991,6 +1001,9 @@ void dec_add_ln(mocr_engine* e, int nslab, int N, const float* bias, const float
         } else {
             a.cache = reinterpret_cast<T*>(e->xcache) + (size_t)cache_layer * e->Bp * a.cstride;
         }
+    }
+    if (hist) {                     // token positions: the row as T at hist[rowmap[slot]][step[slot]], rows of hist_len positions
+        a.cache = hist; a.cstride = (long long)hist_len * e->D;      // (never together with a cache layer)
     }
     launch_dec_add_ln<T>(e, a);
 }
@@ -1399,6 +1412,13 @@ void decode_step_smallm(mocr_engine* e, const DecState& st, int n, int t) {
         c.rows = n; c.K = D; c.a_f32 = e->a_f32; c.ln_g = L.ln1g; c.ln_b = L.ln1b; c.stats_out = st1;
         c.w = W(L.wqc); c.N = D; c.out = e->slabs; c.ldo = D;
         smallm_gemm<SM_PRO_LN, SM_EPI_RAW>(e, "sm_qc", c);
+        if (e->rec_pos && l + 1 == e->cfg.dec_layers) {      // token positions: the rows sm_qc's prologue normalised, recorded
+            ProfScope ps(e, "pos_hist_ln", 0, (double)n * D * 6);
+            hipLaunchKernelGGL((hist_ln_rows_kernel<T>), dim3((n + 15) / 16), dim3(256), 0, e->stream, (const float*)e->a_f32, (const float*)L.ln1g,
+                               (const float*)L.ln1b, e->cfg.ln_eps, reinterpret_cast<T*>(e->pos_hist), (long long)st.max_len * D,
+                               (const int*)e->step, (const int*)e->rowmap, n);
+            HIPCHECK(hipGetLastError());
+        }
         dec_attn<T, false>(e, l, 1, n, L.bqc, e->S);
         SmallMParams oc{};
         oc.rows = n; oc.K = D; oc.a_bf16 = W(e->ctx_t); oc.w = W(L.woc); oc.N = D; oc.bias = L.boc; oc.out = e->c_f32; oc.ldo = D;
@@ -1448,7 +1468,9 @@ void decode_step(mocr_engine* e, const DecState& st, int n, int t) {
             dec_attn<T, true>(e, l, ns, n, L.bqkv, t + 1);   // t = step index = keys already cached
         }
         ns = dec_gemm<T>(e, "gemm_dec_proj", e->ctx_t, D, L.wo, D, D, n);
-        dec_add_ln<T>(e, ns, D, L.bo, xres, L.ln1g, L.ln1b, e->a_f32, e->a_t, n, false);
+        // (token positions: the last layer's LayerNorm-1 rows are also recorded, at the input token's position step[slot])
+        dec_add_ln<T>(e, ns, D, L.bo, xres, L.ln1g, L.ln1b, e->a_f32, e->a_t, n, false, -1,
+                      (e->rec_pos && l + 1 == e->cfg.dec_layers) ? e->pos_hist : nullptr, st.max_len);
         if (e->use_latent(rn)) {
             latent_block(e, false, l, n, t, e->a_t, L.wqc, L.bqc, L.wkT_c,
                          reinterpret_cast<const char*>(w.wckv) + (size_t)(2 * l + 1) * D * D * esz, w.bckv + (2 * l + 1) * D);
@@ -1659,8 +1681,9 @@ hipGraphExec_t decode_graph(mocr_engine* e, const DecState& st, int n, int steps
     // kernel each): a graph captured in one mode is never replayed in another
     // ... and by whether they are the constrained ones (the masked forms of both)
     // ... and by whether the masks are the per-row ones of the no-repeat n-grams (other pointers, the NGRAM token kernel)
-    const int mode = (st.alt_ids ? 2 : st.scores ? 1 : 0) + (st.tok_mask ? 4 : 0) + (st.row_mask ? 8 : 0);
-    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * 16 + mode, steps, e->rrows(n));
+    // ... and by whether they record the rows of the token positions (another pointer in one launch, or one more launch)
+    const int mode = (st.alt_ids ? 2 : st.scores ? 1 : 0) + (st.tok_mask ? 4 : 0) + (st.row_mask ? 8 : 0) + (e->rec_pos ? 16 : 0);
+    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * 32 + mode, steps, e->rrows(n));
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) return it->second;
     hipGraph_t g = nullptr;
@@ -1775,6 +1798,64 @@ static void launch_ngram_init(mocr_engine* e, unsigned* row_mask, const unsigned
     HIPCHECK(hipGetLastError());
 }
 
+// ---- token positions --------------------------------------------------------------
+// The deferred pass walks a batch's rows in chunks whose query and key scratch stays under this many bytes whatever
+// max_batch is (one row needs (197 + max_len) x 768 elements: 87 rows a chunk in bf16 at max_len 300, 43 in fp32).
+constexpr size_t POS_SCRATCH_BYTES = (size_t)64 << 20;
+static int pos_chunk_rows(const mocr_engine* e) {
+    const size_t per_row = (size_t)(e->S + e->cfg.max_len) * e->D * e->esz;
+    return (int)std::max<size_t>(1, POS_SCRATCH_BYTES / per_row);
+}
+
+// The buffers of the token positions, for the bound lane: allocated by the first batch that asks, like the alternatives
+// buffers.  The recorded rows end with one GEMM tile of slack: gemm_kernel reads whole 128-row tiles of its A operand.
+static void ensure_pos_buffers(mocr_engine* e) {
+    if (e->pos_hist) return;
+    const size_t Bp = (size_t)e->Bp, ML = (size_t)e->cfg.max_len, D = (size_t)e->D, R = (size_t)pos_chunk_rows(e);
+    e->pos_hist = e->dalloc<char>((Bp * ML + 128) * D * e->esz);
+    e->pos_out = e->dalloc<float>(Bp * ML * MOCR_POSITION_FIELDS);
+    e->pos_q = e->dalloc<char>(R * ML * D * e->esz);
+    e->pos_k = e->dalloc<char>(R * (size_t)e->S * D * e->esz);
+}
+
+// The positions kernel on the caller's buffers (kernels_positions.h PosParams): the deferred pass and the operator hook.
+template <typename T>
+void launch_attn_positions(mocr_engine* e, const PosParams& p, int rows) {
+    if (e->S != POS_KEYS || e->D != 768 || e->H != 12 || e->G != 14)
+        throw ArgError{"token positions: a 14 x 14 patch grid, 12 heads of 64 only", MOCR_ERR_UNSUPPORTED};
+    if (rows < 1 || p.T < 1) return;
+    ProfScope ps(e, "attn_positions", 2.0 * rows * p.T * POS_KEYS * 768, ((double)rows * POS_KEYS + (double)rows * p.T) * 768 * sizeof(T));
+    hipLaunchKernelGGL((attn_positions_kernel<T>), dim3((p.T + 15) / 16, rows), dim3(64), 0, e->stream, p);
+    HIPCHECK(hipGetLastError());
+}
+
+// The deferred pass of a finished batch, on its lane's stream: per chunk of rows the layer's keys K = ENC Wk^T + bk (the latent
+// path never builds CKV, so every path computes them here) and queries q = hist Wq^T + bq, both on gemm_kernel, then the
+// positions kernel.  Row r's recorded position p holds the step that emitted token p + 1: the outputs start one position in.
+template <typename T>
+void run_positions(mocr_engine* e, Lane& L) {
+    // (HL: the batch's generate(max_length) - its rows were recorded HL positions apart, so the query GEMM covers no more than
+    // the positions the batch could reach; which of them a row did reach is known on the device only)
+    const int D = e->D, ML = e->cfg.max_len, HL = L.max_len, S = e->S, l = e->cfg.dec_layers - 1;
+    const DecLayerW& W = e->w.dec[l];
+    const char* const wk = reinterpret_cast<const char*>(e->w.wckv) + (size_t)(2 * l) * D * D * sizeof(T);
+    const float* const bk = e->w.bckv + (size_t)(2 * l) * D;
+    const int R = pos_chunk_rows(e);
+    for (int r0 = 0; r0 < L.n; r0 += R) {
+        const int rows = std::min(R, L.n - r0);
+        gemm<T>(e, "gemm_pos_k", reinterpret_cast<const char*>(e->ENC) + (size_t)r0 * S * D * sizeof(T), D, wk, bk, e->pos_k, D, nullptr,
+                rows * S, D, D, EPI_BIAS, 128, 1);
+        gemm<T>(e, "gemm_pos_q", reinterpret_cast<const char*>(e->pos_hist) + (size_t)r0 * HL * D * sizeof(T), D, W.wqc, W.bqc, e->pos_q, D,
+                nullptr, rows * HL, D, D, EPI_BIAS, 128, 1);
+        PosParams p{};
+        p.q = e->pos_q; p.q_row_stride = (long long)HL * D;
+        p.k = e->pos_k; p.k_row_stride = (long long)S * D;
+        p.len = e->len + r0; p.len_bias = -1; p.T = L.max_len - 1;
+        p.out_pos = e->pos_out + ((size_t)r0 * ML + 1) * MOCR_POSITION_FIELDS; p.pos_row_stride = (long long)ML * MOCR_POSITION_FIELDS;
+        launch_attn_positions<T>(e, p, rows);
+    }
+}
+
 template <typename T>
 void start_batch(mocr_engine* e, Lane& L) {
     const int IMG = e->cfg.image_size;
@@ -1850,6 +1931,14 @@ void start_batch(mocr_engine* e, Lane& L) {
         HIPCHECK(hipMemcpyAsync(e->ngram_of_row, L.h_ngram.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
         launch_ngram_init(e, e->row_mask, e->tok_table, e->set_of_row, e->ngram_of_row, L.np);
     }
+    // token positions: the batch records its rows when one of its jobs asked; position 0, the pad tail and the rows of the
+    // other jobs read 0
+    L.positions = false;
+    for (const Job& j : L.jobs) L.positions = L.positions || j.out_pos;
+    if (L.positions) {
+        ensure_pos_buffers(e);
+        HIPCHECK(hipMemsetAsync(e->pos_out, 0, (size_t)L.n * e->cfg.max_len * MOCR_POSITION_FIELDS * sizeof(float), e->stream));
+    }
     // The decode steps run on np >= n rows (graph_rows): the padding rows are born finished, emit pad_id and read
     // whatever the workspace holds for them (finite values; no kernel mixes rows).
     DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n);
@@ -1860,6 +1949,9 @@ void start_batch(mocr_engine* e, Lane& L) {
 }
 
 void finish_batch(mocr_engine* e, Lane& L) {
+    if (L.positions) {      // token positions: the deferred pass over the rows the steps recorded, before the outputs leave
+        if (e->cfg.dtype == MOCR_BF16) run_positions<bf16_t>(e, L); else run_positions<float>(e, L);
+    }
     int row0 = 0;
     for (const Job& j : L.jobs) {
         const hipMemcpyKind kind = j.out_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
@@ -1871,6 +1963,10 @@ void finish_batch(mocr_engine* e, Lane& L) {
             const size_t ld = (size_t)e->cfg.max_len * MOCR_ALTERNATIVES;
             HIPCHECK(hipMemcpyAsync(j.out_alt_ids, e->alt_ids + row0 * ld, j.n * ld * sizeof(int), kind, e->stream));
             HIPCHECK(hipMemcpyAsync(j.out_alt_logp, e->alt_logp + row0 * ld, j.n * ld * sizeof(float), kind, e->stream));
+        }
+        if (j.out_pos) {
+            const size_t ld = (size_t)e->cfg.max_len * MOCR_POSITION_FIELDS;
+            HIPCHECK(hipMemcpyAsync(j.out_pos, e->pos_out + row0 * ld, j.n * ld * sizeof(float), kind, e->stream));
         }
         row0 += j.n;
     }
@@ -1946,14 +2042,21 @@ void advance(mocr_engine* e, Lane& L) {
     const int chunk = L.finishing ? std::min(chunk_steps(L.np), CHUNK / 2) : chunk_steps(L.np);
     const int k = std::min(chunk, L.steps - L.t);
     const bool use_graph = !e->prof_on && !(e->cfg.flags & MOCR_FLAG_NO_GRAPH);
-    if (use_graph && k == chunk) {
-        HIPCHECK(hipGraphLaunch(decode_graph<T>(e, st, L.np, chunk, L.t), e->stream));
-    } else {
-        for (int i = 0; i < k; ++i) {
-            if (use_graph) HIPCHECK(hipGraphLaunch(decode_graph<T>(e, st, L.np, 1, L.t + i), e->stream));
-            else decode_step<T>(e, st, L.np, L.t + i);
+    e->rec_pos = L.positions;
+    try {
+        if (use_graph && k == chunk) {
+            HIPCHECK(hipGraphLaunch(decode_graph<T>(e, st, L.np, chunk, L.t), e->stream));
+        } else {
+            for (int i = 0; i < k; ++i) {
+                if (use_graph) HIPCHECK(hipGraphLaunch(decode_graph<T>(e, st, L.np, 1, L.t + i), e->stream));
+                else decode_step<T>(e, st, L.np, L.t + i);
+            }
         }
+    } catch (...) {
+        e->rec_pos = false;
+        throw;
     }
+    e->rec_pos = false;
     L.t += k;
     e->n_slot_steps += (long long)L.np * k;
     if (early) {
@@ -2589,9 +2692,9 @@ static void require_alt_pair(const void* alt_ids, const void* alt_logp) {
         throw ArgError{"out_alt_ids and out_alt_logp must be both null or both set", MOCR_ERR_ARG};
 }
 
-int mocr_recognize_device_norepeat(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
-                                   void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets,
-                                   const int32_t* ngram) {
+int mocr_recognize_device_positions(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
+                                    void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets,
+                                    const int32_t* ngram, void* d_out_pos) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_alt_pair(d_out_alt_ids, d_out_alt_logp);
@@ -2608,8 +2711,16 @@ int mocr_recognize_device_norepeat(mocr_engine* e, const void* d_gray, int32_t n
         j.out_alt_ids = reinterpret_cast<int32_t*>(d_out_alt_ids); j.out_alt_logp = reinterpret_cast<float*>(d_out_alt_logp);
         j.sets = job_sets(sets, 0, n);
         j.ngram = job_ngram(ngram, 0, n);
+        j.out_pos = reinterpret_cast<float*>(d_out_pos);
         submit(e, j);
     });
+}
+
+int mocr_recognize_device_norepeat(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
+                                   void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets,
+                                   const int32_t* ngram) {
+    return mocr_recognize_device_positions(e, d_gray, n, d_out_ids, d_out_len, d_out_logp, d_out_alt_ids, d_out_alt_logp, sets, ngram,
+                                           nullptr);
 }
 
 int mocr_recognize_device_constrained(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
@@ -2633,7 +2744,7 @@ int mocr_recognize_device(mocr_engine* e, const void* d_gray, int32_t n, void* d
 static void recognize_host_chunks(mocr_engine* e, const uint8_t* images, int n, int h, int w, int64_t row_stride,
                                   int64_t image_stride, int channels, int max_len, int32_t* out_ids, int32_t* out_len,
                                   float* out_logp = nullptr, int32_t* out_alt_ids = nullptr, float* out_alt_logp = nullptr,
-                                  const int32_t* sets = nullptr, const int32_t* ngram = nullptr) {
+                                  const int32_t* sets = nullptr, const int32_t* ngram = nullptr, float* out_pos = nullptr) {
     const int IMG = e->cfg.image_size;
     if (h != IMG || w != IMG)
         throw ArgError{"crops must be image_size x image_size (resize with PIL BILINEAR on the caller side)", MOCR_ERR_UNSUPPORTED};
@@ -2651,6 +2762,7 @@ static void recognize_host_chunks(mocr_engine* e, const uint8_t* images, int n, 
         j.out_alt_logp = out_alt_ids ? out_alt_logp + (size_t)base * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
         j.sets = job_sets(sets, (size_t)base, j.n);
         j.ngram = job_ngram(ngram, (size_t)base, j.n);
+        j.out_pos = out_pos ? out_pos + (size_t)base * e->cfg.max_len * MOCR_POSITION_FIELDS : nullptr;
         e->pending.push_back(j);
     }
     drive(e);
@@ -2666,9 +2778,9 @@ int mocr_recognize(mocr_engine* e, const uint8_t* images, int32_t n, int32_t h, 
     });
 }
 
-int mocr_recognize_gray_host_norepeat(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
-                                      int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
-                                      const int32_t* sets, const int32_t* ngram) {
+int mocr_recognize_gray_host_positions(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                       int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
+                                       const int32_t* sets, const int32_t* ngram, float* out_pos) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_alt_pair(out_alt_ids, out_alt_logp);
@@ -2678,8 +2790,15 @@ int mocr_recognize_gray_host_norepeat(mocr_engine* e, const uint8_t* gray, int32
         HIPCHECK(hipSetDevice(e->cfg.device));
         const int IMG = e->cfg.image_size;
         recognize_host_chunks(e, gray, n, IMG, IMG, IMG, (int64_t)IMG * IMG, 1, max_len_override, out_ids, out_len, out_logp,
-                              out_alt_ids, out_alt_logp, sets, ngram);
+                              out_alt_ids, out_alt_logp, sets, ngram, out_pos);
     });
+}
+
+int mocr_recognize_gray_host_norepeat(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                      int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
+                                      const int32_t* sets, const int32_t* ngram) {
+    return mocr_recognize_gray_host_positions(e, gray, n, max_len_override, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, sets,
+                                              ngram, nullptr);
 }
 
 int mocr_recognize_gray_host_constrained(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
@@ -2867,7 +2986,8 @@ static void preprocess_images(mocr_engine* e, const mocr_image* imgs, int n, uin
 // so the host never blocks on a preparation.  r02 prepared ALL crops, synchronised, and only then started to decode.
 static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& srcs, const PrepView* views, int n, int32_t* out_ids,
                                int32_t* out_len, float* out_logp = nullptr, int32_t* out_alt_ids = nullptr,
-                               float* out_alt_logp = nullptr, const int32_t* sets = nullptr, const int32_t* ngram = nullptr) {
+                               float* out_alt_logp = nullptr, const int32_t* sets = nullptr, const int32_t* ngram = nullptr,
+                               float* out_pos = nullptr) {
     const size_t plane = (size_t)e->cfg.image_size * e->cfg.image_size;
     const int C = std::min(e->cfg.max_batch, 4096), nchunks = (n + C - 1) / C;
     uint8_t* const d_gray = (uint8_t*)e->grow(e->rs_gray, (size_t)n * plane);
@@ -2883,6 +3003,7 @@ static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& sr
         j.out_alt_logp = out_alt_ids ? out_alt_logp + (size_t)k * C * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
         j.sets = job_sets(sets, (size_t)k * C, j.n);
         j.ngram = job_ngram(ngram, (size_t)k * C, j.n);
+        j.out_pos = out_pos ? out_pos + (size_t)k * C * e->cfg.max_len * MOCR_POSITION_FIELDS : nullptr;
         e->pending.push_back(j);
     };
     std::vector<PrepHold> holds(nchunks);
@@ -2937,9 +3058,9 @@ int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t
     });
 }
 
-int mocr_recognize_images_norepeat(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
-                                   float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets,
-                                   const int32_t* ngram) {
+int mocr_recognize_images_positions(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                                    float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets,
+                                    const int32_t* ngram, float* out_pos) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_alt_pair(out_alt_ids, out_alt_logp);
@@ -2955,8 +3076,14 @@ int mocr_recognize_images_norepeat(mocr_engine* e, const mocr_image* images, int
             srcs[i] = source_of(images[i]);
             views[i] = PrepView{i, 0, 0, srcs[i].w, srcs[i].h, srcs[i].rot};
         }
-        prepare_and_decode(e, srcs, views.data(), n, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, sets, ngram);
+        prepare_and_decode(e, srcs, views.data(), n, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos);
     });
+}
+
+int mocr_recognize_images_norepeat(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                                   float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets,
+                                   const int32_t* ngram) {
+    return mocr_recognize_images_positions(e, images, n, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, sets, ngram, nullptr);
 }
 
 int mocr_recognize_images_constrained(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
@@ -2991,9 +3118,9 @@ static bool padded_region(const mocr_region& r, int page_h, int page_w, PrepView
     return true;
 }
 
-int mocr_recognize_regions_norepeat(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
-                                    int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
-                                    float* out_alt_logp, const int32_t* sets, const int32_t* ngram) {
+int mocr_recognize_regions_positions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                     int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                     float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         require_alt_pair(out_alt_ids, out_alt_logp);
@@ -3027,10 +3154,12 @@ int mocr_recognize_regions_norepeat(mocr_engine* e, const mocr_image* pages, int
         const size_t LA = (size_t)L * MOCR_ALTERNATIVES;
         std::vector<int32_t> alt_ids(out_alt_ids ? (size_t)nv * LA : 0);
         std::vector<float> alt_logp(out_alt_ids ? (size_t)nv * LA : 0);
+        const size_t LP = (size_t)L * MOCR_POSITION_FIELDS;
+        std::vector<float> posv(out_pos ? (size_t)nv * LP : 0);
         if (nv > 0)
             prepare_and_decode(e, srcs, views.data(), nv, ids.data(), lens.data(), out_logp ? logp.data() : nullptr,
                                out_alt_ids ? alt_ids.data() : nullptr, out_alt_ids ? alt_logp.data() : nullptr,
-                               sets ? view_sets.data() : nullptr, ngram ? view_ngram.data() : nullptr);
+                               sets ? view_sets.data() : nullptr, ngram ? view_ngram.data() : nullptr, out_pos ? posv.data() : nullptr);
         for (int i = 0; i < n_regions; ++i) {
             int32_t* row = out_ids + (size_t)i * L;
             if (where[i] < 0) {
@@ -3041,6 +3170,7 @@ int mocr_recognize_regions_norepeat(mocr_engine* e, const mocr_image* pages, int
                     std::fill(out_alt_ids + i * LA, out_alt_ids + (i + 1) * LA, -1);
                     std::fill(out_alt_logp + i * LA, out_alt_logp + (i + 1) * LA, 0.f);
                 }
+                if (out_pos) std::fill(out_pos + i * LP, out_pos + (i + 1) * LP, 0.f);
             } else {
                 memcpy(row, ids.data() + (size_t)where[i] * L, (size_t)L * sizeof(int32_t));
                 out_len[i] = lens[where[i]];
@@ -3049,9 +3179,17 @@ int mocr_recognize_regions_norepeat(mocr_engine* e, const mocr_image* pages, int
                     memcpy(out_alt_ids + i * LA, alt_ids.data() + where[i] * LA, LA * sizeof(int32_t));
                     memcpy(out_alt_logp + i * LA, alt_logp.data() + where[i] * LA, LA * sizeof(float));
                 }
+                if (out_pos) memcpy(out_pos + i * LP, posv.data() + where[i] * LP, LP * sizeof(float));
             }
         }
     });
+}
+
+int mocr_recognize_regions_norepeat(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                    int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                    float* out_alt_logp, const int32_t* sets, const int32_t* ngram) {
+    return mocr_recognize_regions_positions(e, pages, n_pages, regions, n_regions, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp,
+                                            sets, ngram, nullptr);
 }
 
 int mocr_recognize_regions_constrained(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
@@ -3385,6 +3523,29 @@ int mocr_op_dec_bias_gelu(mocr_engine* e, const float* d_slabs, int32_t nslab, c
         if (!d_slabs || !d_bias || !d_out || rows < 1 || nslab < 1 || N < 4 || N % 4)
             throw ArgError{"mocr_op_dec_bias_gelu: bad argument", MOCR_ERR_ARG};
         dispatch(e, [&](auto tag) { launch_dec_bias_gelu<decltype(tag)>(e, d_slabs, nslab, (long long)rows * N, d_bias, d_out, rows, N); });
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_op_attn_positions(mocr_engine* e, const void* d_q, const void* d_k, const int32_t* d_len, int32_t rows, int32_t T, float* d_out_pos,
+                           float* d_out_map) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!e->committed || !d_q || !d_k || !d_len || !d_out_pos || rows < 1 || T < 1)
+            throw ArgError{"mocr_op_attn_positions: bad argument", MOCR_ERR_ARG};
+        // positions at and behind d_len read 0: the kernel writes the computed ones only
+        HIPCHECK(hipMemsetAsync(d_out_pos, 0, (size_t)rows * T * MOCR_POSITION_FIELDS * sizeof(float), e->stream));
+        if (d_out_map) HIPCHECK(hipMemsetAsync(d_out_map, 0, (size_t)rows * T * POS_KEYS * sizeof(float), e->stream));
+        PosParams p{};
+        p.q = d_q; p.q_row_stride = (long long)T * e->D;
+        p.k = d_k; p.k_row_stride = (long long)e->S * e->D;
+        p.len = d_len; p.len_bias = 0; p.T = T;
+        p.out_pos = d_out_pos; p.pos_row_stride = (long long)T * MOCR_POSITION_FIELDS;
+        p.out_map = d_out_map;
+        if (e->cfg.dtype == MOCR_BF16) launch_attn_positions<bf16_t>(e, p, rows); else launch_attn_positions<float>(e, p, rows);
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }

@@ -73,6 +73,7 @@ CHANNELS_BGR = -3
 MAX_TOKEN_SETS = 256      # MOCR_MAX_TOKEN_SETS: token sets per engine, set 0 included
 TOKEN_SET_ALL = 0         # MOCR_TOKEN_SET_ALL: the whole vocabulary
 ALTERNATIVES = 4          # MOCR_ALTERNATIVES: candidates per position of the *_alts entry points
+POSITION_FIELDS = 5       # MOCR_POSITION_FIELDS: cx, cy, sx, sy, mass per position of the *_positions entry points
 ROTATE_NONE, ROTATE_90_CW, ROTATE_90_CCW = 0, 1, 2
 
 SYMBOLS = {
@@ -103,6 +104,10 @@ SYMBOLS = {
     "mocr_recognize_regions_norepeat": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.POINTER(MocrRegion), C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "mocr_recognize_device_norepeat": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "mocr_recognize_gray_host_norepeat": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "mocr_recognize_images_positions": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mocr_recognize_regions_positions": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.POINTER(MocrRegion), C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mocr_recognize_device_positions": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mocr_recognize_gray_host_positions": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mocr_graph_count": (C.c_int, [_P]),
     "mocr_compaction_count": (C.c_int64, [_P]),
     "mocr_decode_slot_steps": (C.c_int64, [_P]),
@@ -137,6 +142,7 @@ SYMBOLS = {
     "mocr_op_dec_token_masked": (C.c_int, [_P, C.POINTER(MocrTokenArgs), _P, _P, _P, _P, _P, _P, _P, _P]),
     "mocr_op_dec_token_ngram": (C.c_int, [_P, C.POINTER(MocrTokenArgs), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mocr_op_ngram_init": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32]),
+    "mocr_op_attn_positions": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     "mocr_op_gemm_argmax_masked": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "mocr_op_smallm_gemm": (C.c_int, [_P, C.POINTER(MocrSmallmArgs)]),
     "mocr_op_latent_block": (C.c_int, [_P, C.POINTER(MocrLatentArgs)]),

@@ -190,7 +190,7 @@ class Engine:
         return np.full(shape, -1, dtype=np.int32), np.zeros(shape, dtype=np.float32)
 
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False,
-                         token_sets=None, no_repeat_ngram=None):
+                         token_sets=None, no_repeat_ngram=None, positions: bool = False):
         """Crops of any sizes (list of uint8 [h,w] / [h,w,3] arrays; `bgr`: 3-channel crops are in OpenCV order;
         `rotate`: per crop 0 / 1 (90 degrees clockwise) / 2 (counter-clockwise), applied on the device): luminance
         conversion and the Pillow-exact BILINEAR resize to 224x224 run on the device.
@@ -201,7 +201,22 @@ class Engine:
         ``token_sets``: a handle of :meth:`token_set` for every crop, or one per crop - each crop is decoded under its set
         (include/mocr.h, "token constraints"); the return value is shaped by ``scores`` / ``alternatives`` as above.
         ``no_repeat_ngram``: transformers' ``no_repeat_ngram_size`` under greedy decoding, an int for every crop or one per
-        crop, 0 = off (include/mocr.h, "no-repeat n-grams"); combines with ``token_sets``."""
+        crop, 0 = off (include/mocr.h, "no-repeat n-grams"); combines with ``token_sets``.
+        ``positions=True``: the return value gets one more, LAST element, pos float32 [n,max_len,5] - per token the centre
+        (cx, cy), spread (sx, sy) and patch mass of the last decoder layer's cross-attention, in fractions of the 224 x 224
+        plane the encoder sees (include/mocr.h, "token positions"); same ids, scores and alternatives."""
+        if positions:
+            n = len(images)
+            pos = np.zeros((n, self.spec.max_len, _capi.POSITION_FIELDS), dtype=np.float32)
+            if n == 0:
+                return self.recognize_images(images, bgr, rotate, scores=scores, alternatives=alternatives) + (pos,)
+            descs, keep = self._image_descs(images, bgr, rotate)
+            ngram = self._ngram(no_repeat_ngram, n) if no_repeat_ngram is not None else None
+            sets = self._sets(token_sets, n) if token_sets is not None else None
+            ids, lens, logp, alt_ids, alt_logp, out = self._constrained_blocks(n, scores, alternatives)
+            self._check(self.lib.mocr_recognize_images_positions(self._h, descs, n, _ptr(ids), _ptr(lens), _ptr(logp), _ptr(alt_ids),
+                                                                 _ptr(alt_logp), _ptr(sets), _ptr(ngram), _ptr(pos)))
+            return out + (pos,)
         if no_repeat_ngram is not None and len(images) > 0:
             descs, keep = self._image_descs(images, bgr, rotate)
             n = len(keep)
@@ -242,26 +257,36 @@ class Engine:
         return ids, lens
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False,
-                          token_sets=None, no_repeat_ngram=None):
+                          token_sets=None, no_repeat_ngram=None, positions: bool = False):
         """pages: list of uint8 [H,W,3] (or [H,W]) arrays; regions: iterable of (page_index, x, y, w, h) bounding
         rectangles.  Each page is uploaded once; the 8 %-padded, page-clipped crop of every region
         (``src/ui/main_window.py:9530-9540``) is cut on the device.  Returns (ids [n,max_len], lengths [n]);
         a region reduced to a sliver has length 0.  ``scores=True``: (ids, lengths, logp float32 [n,max_len]), a sliver's
         row all 0.  ``alternatives=True``: (ids, lengths, logp, alt_ids, alt_logp) as for recognize_images, a sliver's rows
         all -1 / 0.  ``token_sets``: a set handle for every region, or one per region (see recognize_images);
-        ``no_repeat_ngram``: a no-repeat n-gram size for every region, or one per region (see recognize_images)."""
+        ``no_repeat_ngram``: a no-repeat n-gram size for every region, or one per region (see recognize_images).
+        ``positions=True``: one more, last element pos float32 [n,max_len,5] (see recognize_images), in fractions of the
+        region's padded, clipped rectangle (manga_ocr.regions.padded_rect); a sliver's rows all 0."""
         regs = list(regions)
         n = len(regs)
         ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
         lens = np.zeros(n, dtype=np.int32)
         logp = np.zeros((n, self.spec.max_len), dtype=np.float32) if (scores or alternatives) else None
         alt_ids, alt_logp = self._alt_blocks(n) if alternatives else (None, None)
+        pos = np.zeros((n, self.spec.max_len, _capi.POSITION_FIELDS), dtype=np.float32) if positions else None
         if n == 0:
-            return (ids, lens, logp, alt_ids, alt_logp) if alternatives else (ids, lens, logp) if scores else (ids, lens)
+            out = (ids, lens, logp, alt_ids, alt_logp) if alternatives else (ids, lens, logp) if scores else (ids, lens)
+            return out + (pos,) if positions else out
         descs, keep = self._image_descs(pages, bgr)
         arr = (_capi.MocrRegion * n)()
         for i, (pg, x, y, w, h) in enumerate(regs):
             arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
+        if positions:
+            ngram = self._ngram(no_repeat_ngram, n) if no_repeat_ngram is not None else None
+            sets = self._sets(token_sets, n) if token_sets is not None else None
+            self._check(self.lib.mocr_recognize_regions_positions(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens), _ptr(logp),
+                                                                  _ptr(alt_ids), _ptr(alt_logp), _ptr(sets), _ptr(ngram), _ptr(pos)))
+            return ((ids, lens, logp, alt_ids, alt_logp) if alternatives else (ids, lens, logp) if scores else (ids, lens)) + (pos,)
         if no_repeat_ngram is not None:
             ngram = self._ngram(no_repeat_ngram, n)
             sets = self._sets(token_sets, n) if token_sets is not None else None
@@ -309,11 +334,19 @@ class Engine:
         return out
 
     def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None, d_out_alt_ids=None, d_out_alt_logp=None, *,
-                         token_sets=None, no_repeat_ngram=None) -> None:
+                         token_sets=None, no_repeat_ngram=None, d_out_pos=None) -> None:
         """Asynchronous; all are device buffers (torch CUDA tensors or raw addresses).  ``d_out_logp`` (float32
         [n,max_len]): also the token log-probabilities.  ``d_out_alt_ids`` (int32) with ``d_out_alt_logp`` (float32), both
         [n,max_len,4]: also the token alternatives.  ``token_sets``: a set handle for every crop, or one per crop (host values).
-        ``no_repeat_ngram``: a no-repeat n-gram size for every crop, or one per crop (host values)."""
+        ``no_repeat_ngram``: a no-repeat n-gram size for every crop, or one per crop (host values).
+        ``d_out_pos`` (float32 [n,max_len,5]): also the token positions."""
+        if d_out_pos is not None:
+            ngram = self._ngram(no_repeat_ngram, n) if no_repeat_ngram is not None else None
+            sets = self._sets(token_sets, n) if token_sets is not None else None
+            self._check(self.lib.mocr_recognize_device_positions(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len),
+                                                                 _ptr(d_out_logp), _ptr(d_out_alt_ids), _ptr(d_out_alt_logp), _ptr(sets),
+                                                                 _ptr(ngram), _ptr(d_out_pos)))
+            return
         if no_repeat_ngram is not None:
             ngram = self._ngram(no_repeat_ngram, n)
             sets = self._sets(token_sets, n) if token_sets is not None else None
@@ -339,9 +372,18 @@ class Engine:
         self._check(self.lib.mocr_set_generate_max_length(self._h, int(max_len)))
 
     def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False, alternatives: bool = False,
-                       token_sets=None, no_repeat_ngram=None):
+                       token_sets=None, no_repeat_ngram=None, positions: bool = False):
         a = np.ascontiguousarray(gray, dtype=np.uint8)
         n = a.shape[0]
+        if positions:
+            ngram = self._ngram(no_repeat_ngram, n) if no_repeat_ngram is not None else None
+            sets = self._sets(token_sets, n) if token_sets is not None else None
+            pos = np.zeros((n, self.spec.max_len, _capi.POSITION_FIELDS), dtype=np.float32)
+            ids, lens, logp, alt_ids, alt_logp, out = self._constrained_blocks(n, scores, alternatives)
+            self._check(self.lib.mocr_recognize_gray_host_positions(self._h, _ptr(a), n, max_len or self.spec.max_len, _ptr(ids),
+                                                                    _ptr(lens), _ptr(logp), _ptr(alt_ids), _ptr(alt_logp), _ptr(sets),
+                                                                    _ptr(ngram), _ptr(pos)))
+            return out + (pos,)
         if no_repeat_ngram is not None:
             ngram = self._ngram(no_repeat_ngram, n)
             sets = self._sets(token_sets, n) if token_sets is not None else None
@@ -482,6 +524,11 @@ class Engine:
                                                      _ptr(d_top_idx), _ptr(d_alt_ids), _ptr(d_alt_logp), _ptr(d_tok_mask),
                                                      _ptr(d_set_of_row), _ptr(d_row_mask), _ptr(d_base_mask), _ptr(d_base_set_of_row),
                                                      _ptr(d_ngram_of_row)))
+
+    def op_attn_positions(self, d_q, d_k, d_len, rows: int, T: int, d_out_pos, d_out_map=None) -> None:
+        """The positions kernel on device buffers (include/mocr.h mocr_op_attn_positions)."""
+        self._check(self.lib.mocr_op_attn_positions(self._h, _ptr(d_q), _ptr(d_k), _ptr(d_len), int(rows), int(T), _ptr(d_out_pos),
+                                                    _ptr(d_out_map)))
 
     def op_ngram_init(self, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows: int) -> None:
         """Start of a batch with no-repeat n-grams: every row's mask = its base set (n = 1: minus the start token)."""

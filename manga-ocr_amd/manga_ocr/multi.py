@@ -263,6 +263,8 @@ class MultiGpuEngine:
                       "engine): construct MangaOcr on one device to use token_set / allowed=")
     NO_NGRAM = ("no-repeat n-grams are not implemented for several devices (manga_ocr/multi.py: the workers make the plain greedy "
                 "call): construct MangaOcr on one device to use no_repeat_ngram_size / no_repeat_ngram=")
+    NO_POSITIONS = ("token positions are not implemented for several devices (manga_ocr/multi.py ships ids and lengths only): "
+                    "construct MangaOcr on one device to use the *_positions calls")
     NO_ALTERNATIVES = ("token alternatives are not implemented for several devices (manga_ocr/multi.py ships ids and lengths only): "
                        "construct MangaOcr on one device to use the *_alternatives calls")
 
@@ -526,7 +528,9 @@ class MultiGpuEngine:
         raise NotImplementedError(self.NO_CONSTRAINTS)
 
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False,
-                         alternatives: bool = False, token_sets=None, no_repeat_ngram=None) -> Tuple[np.ndarray, np.ndarray]:
+                         alternatives: bool = False, token_sets=None, no_repeat_ngram=None, positions: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        if positions:
+            raise NotImplementedError(self.NO_POSITIONS)
         if no_repeat_ngram is not None:
             raise NotImplementedError(self.NO_NGRAM)
         if token_sets is not None:
@@ -548,7 +552,9 @@ class MultiGpuEngine:
         return self._run(n, size, fill, dict(kind="images", descs=descs, bgr=bool(bgr), rotate=rotate))
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False,
-                          alternatives: bool = False, token_sets=None, no_repeat_ngram=None) -> Tuple[np.ndarray, np.ndarray]:
+                          alternatives: bool = False, token_sets=None, no_repeat_ngram=None, positions: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        if positions:
+            raise NotImplementedError(self.NO_POSITIONS)
         if no_repeat_ngram is not None:
             raise NotImplementedError(self.NO_NGRAM)
         if token_sets is not None:

@@ -64,6 +64,7 @@ def to_pixels(img) -> np.ndarray:
 
 
 _ALTERNATIVES = 4      # include/mocr.h MOCR_ALTERNATIVES
+_POSITION_FIELDS = 5   # include/mocr.h MOCR_POSITION_FIELDS: cx, cy, sx, sy, mass
 
 
 @dataclass(frozen=True)
@@ -139,7 +140,13 @@ class Recognition:
     The ``*_alternatives`` methods also fill ``alt_ids`` int32 ``[len - 1, 4]`` and ``alt_logprobs`` float32 ``[len - 1, 4]``
     (``None`` otherwise): row ``k`` belongs to ``ids[k + 1]`` like ``logprobs[k]`` and holds the four most probable tokens
     of that position, most probable first, so ``alt_ids[k, 0] == ids[k + 1]`` and ``alt_logprobs[k, 0] == logprobs[k]``
-    (include/mocr.h, "token alternatives").  ``candidates(k)`` gives them as (token string, probability) pairs."""
+    (include/mocr.h, "token alternatives").  ``candidates(k)`` gives them as (token string, probability) pairs.
+
+    The ``*_positions`` methods also fill ``positions`` float32 ``[len, 5]`` (``None`` otherwise): row ``t`` belongs to
+    ``ids[t]`` and holds (cx, cy, sx, sy, mass) - centre, spread and patch mass of the last decoder layer's cross-attention
+    when it emitted that token, in fractions of the 224 x 224 plane the encoder saw (include/mocr.h, "token positions"); row 0
+    (the start token) is zeros.  ``boxes(width, height)`` turns them into pixel rectangles on the crop; for a region,
+    ``rect`` is its padded, clipped rectangle on the page and ``page_boxes()`` gives page pixels."""
     text: str
     ids: np.ndarray
     logprobs: np.ndarray
@@ -147,11 +154,13 @@ class Recognition:
     min_prob: float
     alt_ids: Optional[np.ndarray] = None
     alt_logprobs: Optional[np.ndarray] = None
+    positions: Optional[np.ndarray] = None
+    rect: Optional[Tuple[int, int, int, int]] = None     # regions: (x, y, w, h) of the padded, clipped crop in page pixels
     _vocab: object = field(default=None, repr=False, compare=False)      # what candidates() names the tokens with
 
     @classmethod
     def from_row(cls, vocab, ids_row: np.ndarray, logp_row: np.ndarray, length: int, alt_ids_row: Optional[np.ndarray] = None,
-                 alt_logp_row: Optional[np.ndarray] = None) -> "Recognition":
+                 alt_logp_row: Optional[np.ndarray] = None, pos_row: Optional[np.ndarray] = None, rect=None) -> "Recognition":
         """A row of the engine's (ids, logp[, alt_ids, alt_logp]) blocks and its length (0: a sliver region) -> Recognition."""
         n = int(length)
         ids = np.array(ids_row[:n], dtype=np.int32)
@@ -162,10 +171,44 @@ class Recognition:
             alts = dict(alt_ids=np.array(alt_ids_row[1:n], dtype=np.int32).reshape(-1, k) if n > 1 else np.zeros((0, k), np.int32),
                         alt_logprobs=np.array(alt_logp_row[1:n], dtype=np.float32).reshape(-1, k) if n > 1 else np.zeros((0, k), np.float32),
                         _vocab=vocab)
+        if pos_row is not None:
+            alts["positions"] = np.array(pos_row[:n], dtype=np.float32).reshape(-1, _POSITION_FIELDS)
+            alts["rect"] = tuple(int(v) for v in rect) if rect is not None else None
         if lp.size == 0:
             return cls("" if n == 0 else ids_to_text(vocab, ids), ids, lp, 0.0, 0.0, **alts)
         lp64 = lp.astype(np.float64)
         return cls(ids_to_text(vocab, ids), ids, lp, float(np.exp(lp64.mean())), float(np.exp(lp64.min())), **alts)
+
+    def boxes(self, width: float, height: float, rotate: int = 0, k: float = 2.0) -> np.ndarray:
+        """Per token (x0, y0, x1, y1) in pixels of a ``width`` x ``height`` crop AS IT LAY IN MEMORY: centre -+ ``k`` spreads,
+        clipped to the crop; float64 ``[len, 4]``, row 0 (the start token) and tokens without patch mass all 0.  ``rotate``: the
+        crop's device rotation (0; 1 = 90 degrees clockwise; 2 = counter-clockwise) - the encoder saw the rotated crop, so the
+        position is mapped back: clockwise x = cy', y = 1 - cx'; counter-clockwise x = 1 - cy', y = cx'; the spreads swap."""
+        if self.positions is None:
+            raise ValueError("this Recognition carries no positions: use MangaOcr.recognize_positions and friends")
+        if rotate not in (0, 1, 2):
+            raise ValueError(f"rotate must be 0, 1 or 2, instead got {rotate!r}")
+        p = self.positions.astype(np.float64)
+        cx, cy, sx, sy, mass = (p[:, i] for i in range(_POSITION_FIELDS))
+        if rotate == 1:
+            cx, cy, sx, sy = cy, 1.0 - cx, sy, sx
+        elif rotate == 2:
+            cx, cy, sx, sy = 1.0 - cy, cx, sy, sx
+        W, H = float(width), float(height)
+        out = np.stack([np.clip((cx - k * sx) * W, 0.0, W), np.clip((cy - k * sy) * H, 0.0, H),
+                        np.clip((cx + k * sx) * W, 0.0, W), np.clip((cy + k * sy) * H, 0.0, H)], axis=1)
+        out[mass <= 0.0] = 0.0
+        return out
+
+    def page_boxes(self, k: float = 2.0) -> np.ndarray:
+        """``boxes`` of a region's Recognition in PAGE pixels, through ``rect`` (regions are never rotated)."""
+        if self.rect is None:
+            raise ValueError("this Recognition is not a region's (no rect): use boxes(width, height)")
+        x, y, w, h = self.rect
+        b = self.boxes(w, h, 0, k)
+        live = (b != 0.0).any(axis=1)
+        b[live] += np.array([x, y, x, y], dtype=np.float64)
+        return b
 
     def candidates(self, k: int) -> List[Tuple[str, float]]:
         """The four most probable tokens of generated position ``k`` (the one that emitted ``ids[k + 1]``), most probable
@@ -192,7 +235,9 @@ class _Batcher:
     call any of its requests asked for, and such a caller gets (ids, logp, alt_ids, alt_logp).  A request may also carry a
     token set (``allowed=``); only a batch with such a request passes ``token_sets=`` - one handle per crop, 0 for the others -
     to the engine, so batches nobody constrains make exactly the calls they always made.  The same for a no-repeat n-gram size
-    (``no_repeat_ngram=``): only a batch with a request of size > 0 passes ``no_repeat_ngram=``, one size per crop."""
+    (``no_repeat_ngram=``): only a batch with a request of size > 0 passes ``no_repeat_ngram=``, one size per crop.  And for
+    token positions (``positions=True``): only a batch with such a request passes ``positions=True``, and such a caller gets
+    its positions as one more, last element of its result."""
 
     def __init__(self, engine: Engine, max_batch: int, timeout_ms: float):
         self.engine, self.max_batch, self.timeout = engine, max_batch, timeout_ms / 1000.0
@@ -203,13 +248,13 @@ class _Batcher:
         self._thread.start()
 
     def submit(self, gray: np.ndarray, scored: bool = False, alternatives: bool = False, token_set: int = 0,
-               no_repeat_ngram: int = 0) -> Future:
+               no_repeat_ngram: int = 0, positions: bool = False) -> Future:
         f: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
             # the kind of request, its set, its no-repeat n-gram size
-            self._q.append((gray, f, 2 if alternatives else 1 if scored else 0, int(token_set), int(no_repeat_ngram)))
+            self._q.append((gray, f, 2 if alternatives else 1 if scored else 0, int(token_set), int(no_repeat_ngram), bool(positions)))
             self._cv.notify()
         return f
 
@@ -228,27 +273,39 @@ class _Batcher:
                     self._cv.wait(left)
                 batch, self._q = self._q[:self.max_batch], self._q[self.max_batch:]
             try:
-                kind = max(k for _, _, k, _, _ in batch)
-                sets = [h for _, _, _, h, _ in batch]
+                kind = max(k for _, _, k, _, _, _ in batch)
+                sets = [h for _, _, _, h, _, _ in batch]
                 extra = dict(token_sets=sets) if any(sets) else {}
-                sizes = [g for _, _, _, _, g in batch]
+                sizes = [g for _, _, _, _, g, _ in batch]
                 if any(sizes):
                     extra["no_repeat_ngram"] = sizes
-                logp = alt_ids = alt_logp = None
+                want_pos = any(p for _, _, _, _, _, p in batch)
+                if want_pos:
+                    extra["positions"] = True
+                logp = alt_ids = alt_logp = pos = None
+                crops = [g for g, _, _, _, _, _ in batch]
                 if kind == 2:
-                    ids, lens, logp, alt_ids, alt_logp = self.engine.recognize_images([g for g, _, _, _, _ in batch], alternatives=True, **extra)
+                    res = self.engine.recognize_images(crops, alternatives=True, **extra)
+                    ids, lens, logp, alt_ids, alt_logp = res[:5]
                 elif kind == 1:
-                    ids, lens, logp = self.engine.recognize_images([g for g, _, _, _, _ in batch], scores=True, **extra)
+                    res = self.engine.recognize_images(crops, scores=True, **extra)
+                    ids, lens, logp = res[:3]
                 else:
-                    ids, lens = self.engine.recognize_images([g for g, _, _, _, _ in batch], **extra)
-                for i, (_, f, k, _, _) in enumerate(batch):
+                    res = self.engine.recognize_images(crops, **extra)
+                    ids, lens = res[:2]
+                if want_pos:
+                    pos = res[-1]
+                for i, (_, f, k, _, _, p) in enumerate(batch):
                     n = lens[i]
+                    tail = (pos[i, :n].copy(),) if p else ()
                     if k == 2:
-                        f.set_result((ids[i, :n].copy(), logp[i, :n].copy(), alt_ids[i, :n].copy(), alt_logp[i, :n].copy()))
+                        f.set_result((ids[i, :n].copy(), logp[i, :n].copy(), alt_ids[i, :n].copy(), alt_logp[i, :n].copy()) + tail)
+                    elif k or p:
+                        f.set_result(((ids[i, :n].copy(), logp[i, :n].copy()) if k else (ids[i, :n].copy(),)) + tail)
                     else:
-                        f.set_result((ids[i, :n].copy(), logp[i, :n].copy()) if k else ids[i, :n].copy())
+                        f.set_result(ids[i, :n].copy())
             except BaseException as exc:  # every waiting caller gets the error; the loop lives on
-                for _, f, _, _, _ in batch:
+                for _, f, _, _, _, _ in batch:
                     if not f.done():
                         f.set_exception(exc)
 
@@ -565,6 +622,59 @@ class MangaOcr:
         regions = list(regions)
         return self._recognitions_alt(*self.engine.recognize_regions(list(pages_bgr), regions, True, alternatives=True,
                                                                      **self._decode_kw(allowed, no_repeat_ngram, len(regions))))
+
+    # ------------------------------------------------------------------ positions surface: + where each token was read
+    def _check_positions(self) -> None:
+        no = getattr(self.engine, "NO_POSITIONS", None)      # MultiGpuEngine: its exchange ships ids and lengths only
+        if no:
+            raise NotImplementedError(no)
+
+    def _recognitions_pos(self, ids, lens, logp, pos, rects=None) -> List[Recognition]:
+        return [Recognition.from_row(self.vocab, ids[i], logp[i], lens[i], pos_row=pos[i], rect=rects[i] if rects is not None else None)
+                for i in range(len(lens))]
+
+    def recognize_positions(self, img_or_path, *, allowed=None, no_repeat_ngram=None) -> Recognition:
+        """``recognize_scored`` plus ``Recognition.positions``: per token where in the crop the decoder looked when it emitted
+        it (include/mocr.h, "token positions"); ``Recognition.boxes(width, height)`` gives pixel rectangles.  Same text and
+        scores; goes through the same batcher as ``__call__``, and callers of all kinds may share a batch."""
+        self._check_positions()
+        img = self._open(img_or_path)
+        ids, logp, pos = self._batcher.submit(to_pixels(img), scored=True, positions=True, **self._single(allowed, no_repeat_ngram)).result()
+        return Recognition.from_row(self.vocab, ids, logp, len(ids), pos_row=pos)
+
+    def recognize_batch_positions(self, images: Sequence, *, allowed=None, no_repeat_ngram=None) -> List[Recognition]:
+        """``recognize_batch_scored`` with positions."""
+        self._check_positions()
+        crops = [to_pixels(im) for im in images]
+        return self._recognitions_pos(*self.engine.recognize_images(crops, scores=True, positions=True,
+                                                                    **self._decode_kw(allowed, no_repeat_ngram, len(crops))))
+
+    def recognize_bgr_positions(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
+                                allowed=None, no_repeat_ngram=None) -> List[Recognition]:
+        """``recognize_bgr_scored`` with positions.  The positions are those of the crop the encoder saw, i.e. after the
+        orientation's rotation: pass the crop's rotation code (``queue_worker.rotation_code``) to ``Recognition.boxes`` to get
+        rectangles on the crop as it was handed in."""
+        from .queue_worker import rotation_code
+        self._check_positions()
+        crops = list(crops_bgr)
+        rot = None
+        if orientations is not None:
+            if len(orientations) != len(crops):
+                raise ValueError(f"recognize_bgr_positions: {len(crops)} crops but {len(orientations)} orientations")
+            rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
+        return self._recognitions_pos(*self.engine.recognize_images(crops, True, rot, scores=True, positions=True,
+                                                                    **self._decode_kw(allowed, no_repeat_ngram, len(crops))))
+
+    def recognize_regions_positions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None) -> List[Recognition]:
+        """``recognize_regions_scored`` with positions: every Recognition carries ``rect``, the region's padded, clipped
+        rectangle on its page (``regions.padded_rect``), so ``Recognition.page_boxes()`` gives the tokens' rectangles in page
+        pixels.  A region reduced to a sliver gives text '', no positions rows and ``rect`` None."""
+        from .regions import padded_rect
+        self._check_positions()
+        pages, regions = list(pages_bgr), list(regions)
+        rects = [padded_rect(r[1:5], pages[int(r[0])].shape[0], pages[int(r[0])].shape[1]) for r in regions]
+        return self._recognitions_pos(*self.engine.recognize_regions(pages, regions, True, scores=True, positions=True,
+                                                                     **self._decode_kw(allowed, no_repeat_ngram, len(regions))), rects=rects)
 
     def recognize_page(self, page_bgr: np.ndarray, regions):
         """``_collect_manga_detections`` for one page: ``regions`` = the detector's (text, polygon) pairs."""

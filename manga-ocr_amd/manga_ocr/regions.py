@@ -202,6 +202,20 @@ def polygon_crop_bgr(page_rgb: np.ndarray, polygon: Sequence[Point], bbox: Optio
 Detection = Dict[str, object]
 
 
+def padded_rect(rect: Tuple[int, int, int, int], page_h: int, page_w: int) -> Optional[Tuple[int, int, int, int]]:
+    """The crop a detected region gets (``src/ui/main_window.py:9530-9540``; the engine cuts it on the device): the bounding
+    rectangle (x, y, w, h) grown by ``int(max(w, h) * 0.08)`` on every side and clipped to the page, as (x, y, w, h) in page
+    pixels; ``None`` when no more than a 1-pixel sliver is left (the region is not decoded).  Token positions of a region
+    (``MangaOcr.recognize_regions_positions``) are fractions of this rectangle."""
+    x, y, w, h = (int(v) for v in rect)
+    pad = int(max(w, h) * 0.08)
+    x1, y1 = max(x - pad, 0), max(y - pad, 0)
+    x2, y2 = min(x + w + pad, int(page_w)), min(y + h + pad, int(page_h))
+    if x2 - x1 <= 1 or y2 - y1 <= 1:
+        return None
+    return x1, y1, x2 - x1, y2 - y1
+
+
 def region_rects(polygons: Iterable[Sequence[Point]]) -> List[Tuple[int, int, int, int]]:
     return [bounding_rect(p) for p in polygons]
 

@@ -2,11 +2,14 @@
 """What the token scores cost: HIP-event time per greedy step of the LM head + token kernel, and of the whole decode step,
 unscored, scored and scored with token alternatives, each also under token constraints (every row a random half of the vocabulary) and with no-repeat n-grams (n = 3 on every row, whole vocabulary: per-row masks instead of the shared table, rebuilt by the token kernel), for isolated batches (the engine's own profiler: an instrumented eager pass per repetition).
 
-    python tools/score_cost.py [--rows 64,2560] [--max-len 64] [--reps 5] [--unscored-only | --no-alternatives] [--no-constraints] [--no-ngram]
+    python tools/score_cost.py [--rows 64,2560] [--max-len 64] [--reps 5] [--unscored-only | --no-alternatives] [--no-constraints] [--no-ngram] [--positions | --no-positions]
 
 With MOCR_LIB pointing at a library built from another commit (--unscored-only when it has no scored exports,
 --no-alternatives when it has no alternatives exports, --no-constraints when it has no token-set exports, --no-ngram when it has no n-gram exports) the numbers of the two builds can be compared: the unscored and
 the scored kernels are meant to be the same code.
+--positions adds the token-positions leg (--no-positions: a library without the exports, e.g. the parent commit's - its
+position-less legs above are then the numbers to compare): the wall time of one batch (graph replays, not instrumented) with
+positions off and on, interleaved, and an instrumented pass's kernel times of the deferred pass.
 Prints one JSON line per (rows, mode): medians over the repetitions and their min .. max spread, in microseconds."""
 import argparse
 import json
@@ -33,6 +36,8 @@ def main():
     ap.add_argument("--no-alternatives", action="store_true")
     ap.add_argument("--no-constraints", action="store_true")
     ap.add_argument("--no-ngram", action="store_true")
+    ap.add_argument("--positions", action="store_true")
+    ap.add_argument("--no-positions", action="store_true")
     args = ap.parse_args()
 
     import ctypes as C
@@ -47,6 +52,8 @@ def main():
     ngram = constraints and not args.no_ngram
     if not ngram:               # ... or without the n-gram exports
         _capi.SYMBOLS = {k: v for k, v in _capi.SYMBOLS.items() if "_norepeat" not in k and "ngram" not in k}
+    if args.no_positions or not ngram:      # ... or without the positions exports
+        _capi.SYMBOLS = {k: v for k, v in _capi.SYMBOLS.items() if "_positions" not in k}
     from manga_ocr.engine import Engine
     from manga_ocr.weights import DEFAULT_SPEC, synthetic_weights
 
@@ -86,6 +93,30 @@ def main():
                                   lm_head_plus_token_us=round(statistics.median(head), 2), lm_head_spread_us=[round(min(head), 2), round(max(head), 2)],
                                   decode_step_us=round(statistics.median(step), 2), decode_step_spread_us=[round(min(step), 2), round(max(step), 2)],
                                   per_kernel_us={n: round(statistics.median(v), 2) for n, v in sorted(per.items())},
+                                  lib=os.environ.get("MOCR_LIB", "default"))), flush=True)
+        if args.positions and ngram and not args.no_positions:
+            import time
+            off = lambda: eng.recognize_gray(gray, args.max_len)                       # noqa: E731
+            on = lambda: eng.recognize_gray(gray, args.max_len, positions=True)        # noqa: E731
+            for f in (off, on, off, on):
+                f()                                           # warm: buffers, graphs of both kinds
+            t_off, t_on = [], []
+            for _ in range(args.reps):
+                for f, acc in ((off, t_off), (on, t_on)):
+                    t0 = time.perf_counter()
+                    f()
+                    acc.append(1e3 * (time.perf_counter() - t0))
+            eng.profile_enable(True)
+            on()
+            eng.profile_reset()
+            on()
+            st = {s["name"]: s for s in eng.profile_get()}
+            eng.profile_enable(False)
+            names = ("gemm_pos_k", "gemm_pos_q", "attn_positions", "pos_hist_ln")
+            print(json.dumps(dict(rows=rows, max_len=args.max_len, positions=True, reps=args.reps,
+                                  batch_ms_off=round(statistics.median(t_off), 3), batch_ms_off_spread=[round(min(t_off), 3), round(max(t_off), 3)],
+                                  batch_ms_on=round(statistics.median(t_on), 3), batch_ms_on_spread=[round(min(t_on), 3), round(max(t_on), 3)],
+                                  pass_kernels_ms={n: round(st[n]["total_ms"], 3) for n in names if n in st},
                                   lib=os.environ.get("MOCR_LIB", "default"))), flush=True)
         eng.close()
 
