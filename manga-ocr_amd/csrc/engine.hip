@@ -173,6 +173,44 @@ struct Job {
     float* out_pos = nullptr;       // nullable (the *_positions entry points): [n][max_len][MOCR_POSITION_FIELDS]; host or device like out_ids
 };
 
+// The kind of decode steps a batch runs: the richest of what its jobs asked for.  Every choice that follows from it - the
+// LM-head epilogue, the token kernel, the profile names, the decode-graph key - is made from this one value.
+struct DecMode {
+    int level = 0;                  // 0 ids only, 1 token log-probabilities (the scored LM head / token kernel), 2 also the token
+                                    // alternatives (EPI_TOPK / the TOPK token kernel)
+    bool mask = false;              // a row decodes under a token set other than MOCR_TOKEN_SET_ALL (or `ngram`): the steps run the
+                                    // masked (EPI_*_M / MASK) form of the level's LM head and token kernel
+    bool ngram = false;             // a row has no_repeat_ngram_size > 0: the masks are the per-row ones (row_mask through row_ident)
+                                    // and the token kernel is the NGRAM one, which rebuilds them
+    bool positions = false;         // a job asked for token positions: the steps record pos_hist, finish_batch runs the deferred pass
+    // a graph captured in one mode is never replayed in another: the mode's share of the decode-graph key (5 bits)
+    int key_bits() const { return level + (mask ? 4 : 0) + (ngram ? 8 : 0) + (positions ? 16 : 0); }
+    int epilogue() const { return mask ? (level == 2 ? EPI_TOPK_M : level == 1 ? EPI_ARGMAX_LSE_M : EPI_ARGMAX_M)
+                                       : (level == 2 ? EPI_TOPK : level == 1 ? EPI_ARGMAX_LSE : EPI_ARGMAX); }
+    // profile names of the fused LM head and of the token kernel
+    const char* head_name() const {
+        return mask ? "gemm_dec_vocab_m" : level == 2 ? "gemm_dec_vocab_topk" : level == 1 ? "gemm_dec_vocab_lse" : "gemm_dec_vocab";
+    }
+    const char* token_name() const {
+        static const char* const names[3][3] = {{"dec_token", "dec_token_m", "dec_token_ng"},
+                                                {"dec_token_lse", "dec_token_lse_m", "dec_token_lse_ng"},
+                                                {"dec_token_topk", "dec_token_topk_m", "dec_token_topk_ng"}};
+        return names[level][ngram ? 2 : mask ? 1 : 0];
+    }
+};
+
+static DecMode mode_of(const std::vector<Job>& jobs) {
+    DecMode m;
+    for (const Job& j : jobs) {
+        m.level = std::max(m.level, j.out_alt_ids ? 2 : j.out_logp ? 1 : 0);
+        for (int32_t h : j.sets) m.mask = m.mask || h != MOCR_TOKEN_SET_ALL;
+        for (int32_t g : j.ngram) m.ngram = m.ngram || g > 0;
+        m.positions = m.positions || j.out_pos;
+    }
+    m.mask = m.mask || m.ngram;     // the bans are applied through the rows' masks, which start as the rows' sets
+    return m;
+}
+
 struct Lane {
     LaneCtx ctx;
     bool active = false;
@@ -180,15 +218,8 @@ struct Lane {
     int n = 0, max_len = 0;         // rows of the merged batch, its generate(max_length)
     int np = 0;                     // slots the decode steps run on: n rounded up (graph_rows), the extra ones are born finished; shrinks when the batch is compacted
     int np0 = 0;                    // np at the start of the batch = its kernel regime
-    int mode = 0;                   // the richest kind of request among this batch's jobs: 0 ids only, 1 token log-probabilities (the scored
-                                    // LM head / token kernel), 2 also the token alternatives (EPI_TOPK / the TOPK token kernel)
-    bool constrained = false;       // a row of this batch decodes under a token set other than MOCR_TOKEN_SET_ALL: its steps run the
-                                    // masked (EPI_*_M / MASK) form of the mode's LM head and token kernel
-    std::vector<int> h_sets;        // the upload of set_of_row stages from here
-    bool ngram = false;             // a row of this batch has no_repeat_ngram_size > 0: the batch is `constrained` on the per-row masks
-                                    // (row_mask through row_ident) and its token kernel is the NGRAM one, which rebuilds them
-    std::vector<int> h_ngram;       // the upload of ngram_of_row stages from here
-    bool positions = false;         // a job of this batch asked for token positions: its steps record pos_hist, finish_batch runs the deferred pass
+    DecMode mode;                   // mode_of(jobs)
+    std::vector<int> h_sets, h_ngram;   // the uploads of set_of_row / ngram_of_row stage from here
     int t = 0, steps = 0, chunk = 0;
     bool finishing = false;         // a flag of this batch has reported a finished row: rows are leaving, chunks get shorter
     bool flag_pending[2] = {false, false};
@@ -224,7 +255,6 @@ struct mocr_engine : LaneCtx {
     // keeps the summation order it started with and a row's ids do not depend on when its neighbours finished.
     int regime = 0;
     int rrows(int n) const { return regime > 0 ? regime : n; }
-    bool rec_pos = false;           // the batch being decoded records pos_hist (token positions); set around its steps like `regime`
     bool use_latent(int n) const { return latent && n > classic_rows; }
     int smallm_rows = 0;            // bf16: batches of up to this many rows take the one-launch-per-projection path (kernels_smallm.h)
     bool use_smallm(int n) const { return n <= smallm_rows && !use_latent(n); }
@@ -243,7 +273,7 @@ struct mocr_engine : LaneCtx {
     unsigned* tok_table = nullptr;
     std::vector<std::vector<uint32_t>> tok_sets;
     std::map<std::vector<uint32_t>, int> tok_index;
-    // decode-step HIP graphs, keyed by (lane, rows, (max_len, context bucket, positions, n-gram, constrained, mode 0 / 1 / 2), steps per graph)
+    // decode-step HIP graphs, keyed by (lane, rows, (max_len, context bucket, DecMode::key_bits), steps per graph)
     std::map<std::tuple<int, int, int, int, int>, hipGraphExec_t> graphs;      // + the regime
     void bind(int i) { static_cast<LaneCtx&>(*this) = lanes[i].ctx; }
     void unbind(int i) { lanes[i].ctx = static_cast<LaneCtx&>(*this); }
@@ -589,23 +619,28 @@ struct HeadBatch { int heads = 1; long long a_yoff = 0, w_yoff = 0, o_yoff = 0, 
 struct LnFold { float* part = nullptr; const float* csum = nullptr; void* xb = nullptr; };
 // Token constraints (EPI_*_M): the set table, the set of every batch row and the slot -> row map (kernels_gemm.h GemmParams)
 struct TokMask { const unsigned* table = nullptr; const int* set_of_row = nullptr; const int* rowmap = nullptr; };
+// What the fused LM-head epilogues write per N-tile beside the candidate values in `out`: the columns (every EPI_ARGMAX* /
+// EPI_TOPK*), the exp sums (the _LSE and TOPK forms), the four best (TOPK) - and the mask the EPI_*_M forms apply
+struct LmHead { int* cand_idx = nullptr; float* cand_sum = nullptr; float* top_val = nullptr; int* top_idx = nullptr; TokMask mask; };
 
 template <typename T>
 void gemm(mocr_engine* e, const char* name, const void* A, int lda, const void* W, const float* bias, void* out, int ldo,
           const float* resid, int M, int N, int K, int epi, int tile, int split, long long slab_stride = 0,
-          const float* pos = nullptr, int patches = 0, const HeadBatch* hb = nullptr, int group_n = 0, int* cand_idx = nullptr,
-          const LnFold* lnf = nullptr, float* cand_sum = nullptr, float* top_val = nullptr, int* top_idx = nullptr,
-          const TokMask* tm = nullptr) {
+          const float* pos = nullptr, int patches = 0, const HeadBatch* hb = nullptr, int group_n = 0, const LmHead* lm = nullptr,
+          const LnFold* lnf = nullptr) {
     const int kt = 128 / (int)sizeof(T);
     if (N % (tile >= 1024 ? 256 : tile >= 256 ? 128 : std::max(tile, 1)) || K % (kt * split) || (split > 1 && epi != EPI_SLAB) ||
         (tile >= 256 && (sizeof(T) != 2 || split != 1)))
         throw ArgError{std::string("gemm shape not tileable: ") + name, MOCR_ERR_ARG};
     GemmParams p{};
-    p.A = A; p.W = W; p.bias = bias; p.out = out; p.resid = resid; p.pos = pos; p.cand_idx = cand_idx; p.cand_sum = cand_sum;
-    p.top_val = top_val; p.top_idx = top_idx;
-    if ((epi == EPI_ARGMAX_M || epi == EPI_ARGMAX_LSE_M || epi == EPI_TOPK_M) != (tm != nullptr) || (tm && (!tm->table || !tm->set_of_row)))
+    p.A = A; p.W = W; p.bias = bias; p.out = out; p.resid = resid; p.pos = pos;
+    const TokMask tm = lm ? lm->mask : TokMask{};
+    if ((epi == EPI_ARGMAX_M || epi == EPI_ARGMAX_LSE_M || epi == EPI_TOPK_M) != (tm.table || tm.set_of_row) || !tm.table != !tm.set_of_row)
         throw ArgError{std::string("the masked LM-head epilogues come with a token-set table: ") + name, MOCR_ERR_ARG};
-    if (tm) { p.tok_mask = tm->table; p.set_of_row = tm->set_of_row; p.rowmap = tm->rowmap; }
+    if (lm) {
+        p.cand_idx = lm->cand_idx; p.cand_sum = lm->cand_sum; p.top_val = lm->top_val; p.top_idx = lm->top_idx;
+        if (tm.table) { p.tok_mask = tm.table; p.set_of_row = tm.set_of_row; p.rowmap = tm.rowmap; }
+    }
     p.M = M; p.N = N; p.lda = lda; p.ldw = K; p.ldo = ldo;
     int ybatch = 1;
     if (hb) {
@@ -1019,7 +1054,7 @@ void launch_dec_bias_gelu(mocr_engine* e, const float* slabs, int nslab, long lo
 }
 
 static DecState make_state(mocr_engine* e, int max_len, const int* forced, int forced_T, float* logits_out, int n_real,
-                           int mode = 0, bool constrained = false, bool ngram = false) {
+                           const DecMode& m = DecMode{}) {
     DecState st{};
     st.n_real = n_real;
     st.ids = e->ids; st.step = e->step; st.finished = e->finished; st.len = e->len; st.n_unfinished = e->n_unf;
@@ -1027,10 +1062,10 @@ static DecState make_state(mocr_engine* e, int max_len, const int* forced, int f
     st.ids_ld = e->cfg.max_len; st.max_len = max_len;
     st.start_id = e->cfg.start_id; st.eos_id = e->cfg.eos_id; st.pad_id = e->cfg.pad_id;
     st.rowmap = e->rowmap;
-    st.scores = mode >= 1 ? e->scores : nullptr;
-    st.alt_ids = mode >= 2 ? e->alt_ids : nullptr; st.alt_logp = mode >= 2 ? e->alt_logp : nullptr;
-    st.tok_mask = constrained ? e->tok_table : nullptr; st.set_of_row = constrained ? e->set_of_row : nullptr;
-    if (ngram) {        // the masked kernels read the row's own mask; the sets become the base the NGRAM token kernel rebuilds it from
+    st.scores = m.level >= 1 ? e->scores : nullptr;
+    st.alt_ids = m.level >= 2 ? e->alt_ids : nullptr; st.alt_logp = m.level >= 2 ? e->alt_logp : nullptr;
+    st.tok_mask = m.mask ? e->tok_table : nullptr; st.set_of_row = m.mask ? e->set_of_row : nullptr;
+    if (m.ngram) {        // the masked kernels read the row's own mask; the sets become the base the NGRAM token kernel rebuilds it from
         st.tok_mask = e->row_mask; st.set_of_row = e->row_ident;
         st.row_mask = e->row_mask; st.base_mask = e->tok_table; st.base_set_of_row = e->set_of_row; st.ngram_of_row = e->ngram_of_row;
     }
@@ -1048,58 +1083,35 @@ struct DecTokenArgs {
     void* cache; uint8_t* cache8; float inv8; long long cstride;   // layer-0 latent cache row (T or e4m3), indexed by row
 };
 
+// The operator hooks come with a bare DecState, so the kernel's form is read off the state: scores / alternatives /
+// token sets / per-row masks set (make_state sets them from the batch's DecMode).
 template <typename T, bool FIRST>
 void launch_dec_token(mocr_engine* e, const DecState& st, const DecTokenArgs& a, int n) {
     auto& w = e->w;
-    if constexpr (!FIRST) {
-        if (st.tok_mask) {      // token constraints: the MASK form of the mode's kernel
-            ProfScope ps(e, st.row_mask ? (st.alt_ids ? "dec_token_topk_ng" : st.scores ? "dec_token_lse_ng" : "dec_token_ng")
-                                        : (st.alt_ids ? "dec_token_topk_m" : st.scores ? "dec_token_lse_m" : "dec_token_m"),
-                         0, (double)n * e->V * 4 * a.nslab);
-            auto launch = [&](auto kernel) {
-                hipLaunchKernelGGL(kernel, dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab,
-                                   a.slab_stride, a.vbias, e->V, st, w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32,
-                                   reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps, reinterpret_cast<T*>(a.cache), a.cstride,
-                                   a.ncand ? a.cand_val : nullptr, a.ncand ? a.cand_idx : nullptr, a.ncand, a.cache8, a.inv8,
-                                   a.ncand ? a.cand_sum : nullptr, a.ncand ? a.top_val : nullptr, a.ncand ? a.top_idx : nullptr);
-            };
-            if (st.row_mask) {      // no-repeat n-grams: the NGRAM form, which also rebuilds the row's mask for the next step
-                if (st.alt_ids) launch(dec_token_kernel<T, 768, false, true, true, true, true>);
-                else if (st.scores) launch(dec_token_kernel<T, 768, false, true, false, true, true>);
-                else launch(dec_token_kernel<T, 768, false, false, false, true, true>);
-            }
-            else if (st.alt_ids) launch(dec_token_kernel<T, 768, false, true, true, true>);
-            else if (st.scores) launch(dec_token_kernel<T, 768, false, true, false, true>);
-            else launch(dec_token_kernel<T, 768, false, false, false, true>);
-            HIPCHECK(hipGetLastError());
-            return;
-        }
-        if (st.alt_ids) {       // token alternatives (with the scores)
-            ProfScope ps(e, "dec_token_topk", 0, (double)n * e->V * 4 * a.nslab);
-            hipLaunchKernelGGL((dec_token_kernel<T, 768, false, true, true>), dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab,
-                               a.slab_stride, a.vbias, e->V, st, w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32,
-                               reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps, reinterpret_cast<T*>(a.cache), a.cstride,
-                               a.ncand ? a.cand_val : nullptr, a.ncand ? a.cand_idx : nullptr, a.ncand, a.cache8, a.inv8,
-                               a.ncand ? a.cand_sum : nullptr, a.ncand ? a.top_val : nullptr, a.ncand ? a.top_idx : nullptr);
-            HIPCHECK(hipGetLastError());
-            return;
-        }
-        if (st.scores) {        // token scores: the start step has nothing to score (start_batch zeroes column 0)
-            ProfScope ps(e, "dec_token_lse", 0, (double)n * e->V * 4 * a.nslab);
-            hipLaunchKernelGGL((dec_token_kernel<T, 768, false, true>), dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab,
-                               a.slab_stride, a.vbias, e->V, st, w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32,
-                               reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps, reinterpret_cast<T*>(a.cache), a.cstride,
-                               a.ncand ? a.cand_val : nullptr, a.ncand ? a.cand_idx : nullptr, a.ncand, a.cache8, a.inv8,
-                               a.ncand ? a.cand_sum : nullptr);
-            HIPCHECK(hipGetLastError());
-            return;
-        }
+    DecMode m;
+    m.level = st.alt_ids ? 2 : st.scores ? 1 : 0; m.mask = st.tok_mask != nullptr; m.ngram = st.row_mask != nullptr;
+    const bool cand = a.ncand > 0;
+    ProfScope ps(e, FIRST ? "dec_token_first" : m.token_name(), 0, FIRST ? 0.0 : (double)n * e->V * 4 * a.nslab);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab, a.slab_stride, a.vbias, e->V, st, w.word, w.type0,
+                           w.posd, w.embg, w.embb, a.x_f32, reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps, reinterpret_cast<T*>(a.cache),
+                           a.cstride, cand ? a.cand_val : nullptr, cand ? a.cand_idx : nullptr, a.ncand, a.cache8, a.inv8,
+                           cand && m.level >= 1 ? a.cand_sum : nullptr, cand && m.level >= 2 ? a.top_val : nullptr,
+                           cand && m.level >= 2 ? a.top_idx : nullptr);
+    };
+    // <T, 768, FIRST, SCORES, TOPK, MASK, NGRAM>: the start token's kernel, and level x (plain, MASK, NGRAM) for the steps
+    if constexpr (FIRST) launch(dec_token_kernel<T, 768, true>);      // (the start step has nothing to score or to mask)
+    else switch (m.level * 3 + (m.ngram ? 2 : m.mask ? 1 : 0)) {
+        case 0: launch(dec_token_kernel<T, 768, false>); break;
+        case 1: launch(dec_token_kernel<T, 768, false, false, false, true>); break;
+        case 2: launch(dec_token_kernel<T, 768, false, false, false, true, true>); break;
+        case 3: launch(dec_token_kernel<T, 768, false, true>); break;
+        case 4: launch(dec_token_kernel<T, 768, false, true, false, true>); break;
+        case 5: launch(dec_token_kernel<T, 768, false, true, false, true, true>); break;
+        case 6: launch(dec_token_kernel<T, 768, false, true, true>); break;
+        case 7: launch(dec_token_kernel<T, 768, false, true, true, true>); break;
+        default: launch(dec_token_kernel<T, 768, false, true, true, true, true>); break;
     }
-    ProfScope ps(e, FIRST ? "dec_token_first" : "dec_token", 0, FIRST ? 0.0 : (double)n * e->V * 4 * a.nslab);
-    hipLaunchKernelGGL((dec_token_kernel<T, 768, FIRST>), dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab,
-                       a.slab_stride, a.vbias, e->V, st, w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32,
-                       reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps, reinterpret_cast<T*>(a.cache), a.cstride,
-                       a.ncand ? a.cand_val : nullptr, a.ncand ? a.cand_idx : nullptr, a.ncand, a.cache8, a.inv8);
     HIPCHECK(hipGetLastError());
 }
 
@@ -1389,7 +1401,7 @@ void smallm_gemm(mocr_engine* e, const char* name, SmallMParams p) {
 // One greedy step of a SMALL bf16 batch (<= 32 rows, classic attention): 19 launches instead of 28 (kernels_smallm.h).
 // x_f32 / a_f32 / c_f32 hold PRE-LayerNorm sums here (s3 of the previous layer - or the embedding rows for layer 0 -,
 // s1, s2); ln_stats[k] the (mean, rstd) of s(k+1), published by the first projection that normalises it.
-void decode_step_smallm(mocr_engine* e, const DecState& st, int n, int t) {
+void decode_step_smallm(mocr_engine* e, const DecState& st, const DecMode& m, int n, int t) {
     using T = bf16_t;
     const int D = e->D, F = e->F;
     auto& w = e->w;
@@ -1412,7 +1424,7 @@ void decode_step_smallm(mocr_engine* e, const DecState& st, int n, int t) {
         c.rows = n; c.K = D; c.a_f32 = e->a_f32; c.ln_g = L.ln1g; c.ln_b = L.ln1b; c.stats_out = st1;
         c.w = W(L.wqc); c.N = D; c.out = e->slabs; c.ldo = D;
         smallm_gemm<SM_PRO_LN, SM_EPI_RAW>(e, "sm_qc", c);
-        if (e->rec_pos && l + 1 == e->cfg.dec_layers) {      // token positions: the rows sm_qc's prologue normalised, recorded
+        if (m.positions && l + 1 == e->cfg.dec_layers) {      // token positions: the rows sm_qc's prologue normalised, recorded
             ProfScope ps(e, "pos_hist_ln", 0, (double)n * D * 6);
             hipLaunchKernelGGL((hist_ln_rows_kernel<T>), dim3((n + 15) / 16), dim3(256), 0, e->stream, (const float*)e->a_f32, (const float*)L.ln1g,
                                (const float*)L.ln1b, e->cfg.ln_eps, reinterpret_cast<T*>(e->pos_hist), (long long)st.max_len * D,
@@ -1447,9 +1459,9 @@ void decode_step_smallm(mocr_engine* e, const DecState& st, int n, int t) {
 
 // One greedy step for n rows; `t` is only used for the profiler's byte estimate.
 template <typename T>
-void decode_step(mocr_engine* e, const DecState& st, int n, int t) {
+void decode_step(mocr_engine* e, const DecState& st, const DecMode& m, int n, int t) {
     if constexpr (sizeof(T) == 2) {
-        if (e->use_smallm(e->rrows(n))) { decode_step_smallm(e, st, n, t); return; }
+        if (e->use_smallm(e->rrows(n))) { decode_step_smallm(e, st, m, n, t); return; }
     }
     const int D = e->D, F = e->F;
     auto& w = e->w;
@@ -1470,7 +1482,7 @@ void decode_step(mocr_engine* e, const DecState& st, int n, int t) {
         ns = dec_gemm<T>(e, "gemm_dec_proj", e->ctx_t, D, L.wo, D, D, n);
         // (token positions: the last layer's LayerNorm-1 rows are also recorded, at the input token's position step[slot])
         dec_add_ln<T>(e, ns, D, L.bo, xres, L.ln1g, L.ln1b, e->a_f32, e->a_t, n, false, -1,
-                      (e->rec_pos && l + 1 == e->cfg.dec_layers) ? e->pos_hist : nullptr, st.max_len);
+                      (m.positions && l + 1 == e->cfg.dec_layers) ? e->pos_hist : nullptr, st.max_len);
         if (e->use_latent(rn)) {
             latent_block(e, false, l, n, t, e->a_t, L.wqc, L.bqc, L.wkT_c,
                          reinterpret_cast<const char*>(w.wckv) + (size_t)(2 * l + 1) * D * D * esz, w.bckv + (2 * l + 1) * D);
@@ -1499,23 +1511,15 @@ void decode_step(mocr_engine* e, const DecState& st, int n, int t) {
     const int vt = dec_launch_tile(e, n);
     if (!st.logits_out && !(e->cfg.flags & MOCR_FLAG_NO_FUSED_ARGMAX) && (vt == 64 || vt == 128) &&
         pick_split(e->V, D, 128 / (int)sizeof(T), rn, e->slab_cap / e->Bp) == 1) {
-        // (a scored batch - st.scores - also keeps every tile's sum of exp(logit - tile max): EPI_ARGMAX_LSE, same max / column)
-        // (an alternatives batch - st.alt_ids - every tile's four best as well: EPI_TOPK)
-        // (a constrained batch - st.tok_mask - the masked form of its mode's epilogue: EPI_*_M)
-        if (st.tok_mask) {
-            const TokMask tm{st.tok_mask, st.set_of_row, st.rowmap};
-            gemm<T>(e, "gemm_dec_vocab_m", e->z_t, D, w.wv, w.bv, e->cand_val, e->V, nullptr, n, e->V, D,
-                    st.alt_ids ? EPI_TOPK_M : st.scores ? EPI_ARGMAX_LSE_M : EPI_ARGMAX_M, vt, 1, 0, nullptr, 0, nullptr, 0, e->cand_idx,
-                    nullptr, st.scores ? e->cand_sum : nullptr, st.alt_ids ? e->top_val : nullptr, st.alt_ids ? e->top_idx : nullptr, &tm);
-        } else if (st.alt_ids)
-            gemm<T>(e, "gemm_dec_vocab_topk", e->z_t, D, w.wv, w.bv, e->cand_val, e->V, nullptr, n, e->V, D, EPI_TOPK, vt, 1, 0,
-                    nullptr, 0, nullptr, 0, e->cand_idx, nullptr, e->cand_sum, e->top_val, e->top_idx);
-        else if (st.scores)
-            gemm<T>(e, "gemm_dec_vocab_lse", e->z_t, D, w.wv, w.bv, e->cand_val, e->V, nullptr, n, e->V, D, EPI_ARGMAX_LSE, vt, 1, 0,
-                    nullptr, 0, nullptr, 0, e->cand_idx, nullptr, e->cand_sum);
-        else
-        gemm<T>(e, "gemm_dec_vocab", e->z_t, D, w.wv, w.bv, e->cand_val, e->V, nullptr, n, e->V, D, EPI_ARGMAX, vt, 1, 0, nullptr, 0,
-                nullptr, 0, e->cand_idx);
+        // (a scored batch also keeps every tile's sum of exp(logit - tile max): EPI_ARGMAX_LSE, same max / column; an
+        // alternatives batch every tile's four best as well: EPI_TOPK; a constrained batch the masked form of either: EPI_*_M)
+        LmHead lm;
+        lm.cand_idx = e->cand_idx;
+        if (m.level >= 1) lm.cand_sum = e->cand_sum;
+        if (m.level >= 2) { lm.top_val = e->top_val; lm.top_idx = e->top_idx; }
+        if (m.mask) lm.mask = TokMask{st.tok_mask, st.set_of_row, st.rowmap};
+        gemm<T>(e, m.head_name(), e->z_t, D, w.wv, w.bv, e->cand_val, e->V, nullptr, n, e->V, D, m.epilogue(), vt, 1, 0, nullptr, 0, nullptr,
+                0, &lm);
         dec_token<T, false>(e, st, 1, n, e->V / vt);
     } else {
         ns = dec_gemm<T>(e, "gemm_dec_vocab", e->z_t, D, w.wv, e->V, D, n);
@@ -1543,57 +1547,25 @@ void quantize_enc(mocr_engine* e, int n) {
     HIPCHECK(hipGetLastError());
 }
 
+// The epilogues gemm_kernel is built with (launch_gemm_epi), as integral constants.
+template <typename F> void for_each_gemm_epilogue(F&& f) {
+    auto each = [&](auto... epi) { (f(epi), ...); };
+    each(std::integral_constant<int, EPI_SLAB>{}, std::integral_constant<int, EPI_BIAS>{}, std::integral_constant<int, EPI_BIAS_GELU>{},
+         std::integral_constant<int, EPI_BIAS_RESID>{}, std::integral_constant<int, EPI_PATCH>{}, std::integral_constant<int, EPI_BIAS_F32>{},
+         std::integral_constant<int, EPI_ARGMAX>{}, std::integral_constant<int, EPI_ARGMAX_LSE>{}, std::integral_constant<int, EPI_TOPK>{},
+         std::integral_constant<int, EPI_ARGMAX_M>{}, std::integral_constant<int, EPI_ARGMAX_LSE_M>{}, std::integral_constant<int, EPI_TOPK_M>{});
+}
+
 // Raise the dynamic-LDS limit of every kernel that needs it (done once, outside any capture).
 template <typename T> void init_kernel_attrs() {
     constexpr int l128 = 2 * (128 + 128) * 128, l64 = 2 * (64 + 64) * 128;
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_SLAB>, l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS>, l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS_GELU>, l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS_RESID>, l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_PATCH>, l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS_F32>, l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX>, l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_LSE>, l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_TOPK>, l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_M>, l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_LSE_M>, l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_TOPK_M>, l128);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_SLAB, 2>, l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS, 2>, l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_GELU, 2>, l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_RESID, 2>, l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_PATCH, 2>, l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_F32, 2>, l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX, 2>, l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_LSE, 2>, l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_TOPK, 2>, l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_M, 2>, l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_LSE_M, 2>, l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_TOPK_M, 2>, l64);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_SLAB, 4>, 2 * l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS, 4>, 2 * l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS_GELU, 4>, 2 * l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS_RESID, 4>, 2 * l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_PATCH, 4>, 2 * l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_BIAS_F32, 4>, 2 * l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX, 4>, 2 * l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_LSE, 4>, 2 * l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_TOPK, 4>, 2 * l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_M, 4>, 2 * l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_ARGMAX_LSE_M, 4>, 2 * l128);
-    set_max_lds(gemm_kernel<T, 128, 128, EPI_TOPK_M, 4>, 2 * l128);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_SLAB, 4>, 2 * l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS, 4>, 2 * l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_GELU, 4>, 2 * l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_RESID, 4>, 2 * l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_PATCH, 4>, 2 * l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_BIAS_F32, 4>, 2 * l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX, 4>, 2 * l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_LSE, 4>, 2 * l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_TOPK, 4>, 2 * l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_M, 4>, 2 * l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_ARGMAX_LSE_M, 4>, 2 * l64);
-    set_max_lds(gemm_kernel<T, 64, 64, EPI_TOPK_M, 4>, 2 * l64);
+    for_each_gemm_epilogue([&](auto epi) {
+        constexpr int E = decltype(epi)::value;
+        set_max_lds(gemm_kernel<T, 128, 128, E>, l128);
+        set_max_lds(gemm_kernel<T, 64, 64, E, 2>, l64);
+        set_max_lds(gemm_kernel<T, 128, 128, E, 4>, 2 * l128);
+        set_max_lds(gemm_kernel<T, 64, 64, E, 4>, 2 * l64);
+    });
     set_max_lds(enc_attn_simple_kernel<T>, (200 * 65 + 200 * 64 + 4 * 64 + 4 * 256) * 4);
     set_max_lds(enc_attn2_kernel, EA2_LDS);
     set_max_lds(enc_attn_f32_kernel, EAF_LDS);
@@ -1672,24 +1644,19 @@ template <typename T> void init_kernel_attrs() {
 // `steps` consecutive greedy steps captured once and replayed: every per-step value (position,
 // token, finished flags) lives in device memory, so the launch sequence is identical each step.
 template <typename T>
-hipGraphExec_t decode_graph(mocr_engine* e, const DecState& st, int n, int steps, int t0) {
+hipGraphExec_t decode_graph(mocr_engine* e, const DecState& st, const DecMode& m, int n, int steps, int t0) {
     // the self-attention variant depends on the context length, so graphs are bucketed by it
     const int need = ((t0 + steps + 3) / 4 + 7) / 8;
     const int bucket = need <= 3 ? 3 : need <= 5 ? 5 : need <= 8 ? 8 : 10;
     const int t_hi = std::min(bucket * 32, st.max_len) - 1;      // largest context this bucket covers
-    // ... and by the mode of the steps (0 ids only, 1 scored, 2 scored with alternatives: another LM-head epilogue and token
-    // kernel each): a graph captured in one mode is never replayed in another
-    // ... and by whether they are the constrained ones (the masked forms of both)
-    // ... and by whether the masks are the per-row ones of the no-repeat n-grams (other pointers, the NGRAM token kernel)
-    // ... and by whether they record the rows of the token positions (another pointer in one launch, or one more launch)
-    const int mode = (st.alt_ids ? 2 : st.scores ? 1 : 0) + (st.tok_mask ? 4 : 0) + (st.row_mask ? 8 : 0) + (e->rec_pos ? 16 : 0);
-    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * 32 + mode, steps, e->rrows(n));
+    // ... and by the mode of the steps: another LM-head epilogue, token kernel, set of pointers or launch each
+    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * 32 + m.key_bits(), steps, e->rrows(n));
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) return it->second;
     hipGraph_t g = nullptr;
     HIPCHECK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     try {
-        for (int i = 0; i < steps; ++i) decode_step<T>(e, st, n, t_hi - 1);
+        for (int i = 0; i < steps; ++i) decode_step<T>(e, st, m, n, t_hi - 1);
     } catch (...) {
         (void)hipStreamEndCapture(e->stream, &g);
         if (g) (void)hipGraphDestroy(g);
@@ -1708,7 +1675,7 @@ template <typename T>
 void run_decode_forced(mocr_engine* e, int n, const int* forced, int forced_T, float* logits_out) {
     DecState st = make_state(e, e->cfg.max_len, forced, forced_T, logits_out, n);
     dec_token<T, true>(e, st, 0, n);
-    for (int t = 0; t < forced_T; ++t) decode_step<T>(e, st, n, t);
+    for (int t = 0; t < forced_T; ++t) decode_step<T>(e, st, DecMode{}, n, t);
 }
 
 // ---------------------------------------------------------------------------------------- scheduler
@@ -1856,6 +1823,17 @@ void run_positions(mocr_engine* e, Lane& L) {
     }
 }
 
+// A per-crop int array of the batch's jobs (an empty one: `fill`), merged in row order over the np slots and uploaded.
+static void upload_per_row(mocr_engine* e, const Lane& L, std::vector<int>& stage, std::vector<int32_t> Job::*field, int fill, int* d_dst) {
+    stage.assign((size_t)L.np, fill);
+    int r0 = 0;
+    for (const Job& j : L.jobs) {
+        std::copy((j.*field).begin(), (j.*field).end(), stage.begin() + r0);
+        r0 += j.n;
+    }
+    HIPCHECK(hipMemcpyAsync(d_dst, stage.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
+}
+
 template <typename T>
 void start_batch(mocr_engine* e, Lane& L) {
     const int IMG = e->cfg.image_size;
@@ -1889,53 +1867,30 @@ void start_batch(mocr_engine* e, Lane& L) {
     else if (e->fp8attn) quantize_enc(e, L.n);
     // rows read pad_id (= 0) beyond what the loop writes
     HIPCHECK(hipMemsetAsync(e->ids, 0, (size_t)L.np * e->cfg.max_len * sizeof(int), e->stream));
-    // token scores: the batch is scored when one of its jobs asked; the start token and the pad tail score 0
-    // (token alternatives: the same, one mode richer; positions the steps do not write read -1 / 0)
-    L.mode = 0;
-    for (const Job& j : L.jobs) L.mode = std::max(L.mode, j.out_alt_ids ? 2 : j.out_logp ? 1 : 0);
-    if (L.mode >= 1) HIPCHECK(hipMemsetAsync(e->scores, 0, (size_t)L.np * e->cfg.max_len * sizeof(float), e->stream));
-    if (L.mode >= 2) {
+    // The batch runs in the richest mode any of its jobs asked for.  Scores: the start token and the pad tail score 0;
+    // alternatives: positions the steps do not write read -1 / 0
+    const DecMode& m = L.mode = mode_of(L.jobs);
+    if (m.level >= 1) HIPCHECK(hipMemsetAsync(e->scores, 0, (size_t)L.np * e->cfg.max_len * sizeof(float), e->stream));
+    if (m.level >= 2) {
         ensure_alt_buffers(e);
         HIPCHECK(hipMemsetAsync(e->alt_ids, 0xFF, (size_t)L.np * e->cfg.max_len * MOCR_ALTERNATIVES * sizeof(int), e->stream));
         HIPCHECK(hipMemsetAsync(e->alt_logp, 0, (size_t)L.np * e->cfg.max_len * MOCR_ALTERNATIVES * sizeof(float), e->stream));
     }
-    // token constraints: the batch is constrained when a row of one of its jobs has a set other than MOCR_TOKEN_SET_ALL; the
-    // merged rows' sets go up before the first decode graph (the padding rows and the rows of unconstrained jobs: set 0)
-    L.constrained = false;
-    for (const Job& j : L.jobs)
-        for (int32_t h : j.sets) L.constrained = L.constrained || h != MOCR_TOKEN_SET_ALL;
-    // no-repeat n-grams: a batch with a row of n > 0 is constrained too - on per-row masks, which start as the rows' sets
-    L.ngram = false;
-    for (const Job& j : L.jobs)
-        for (int32_t g : j.ngram) L.ngram = L.ngram || g > 0;
-    L.constrained = L.constrained || L.ngram;
-    if (L.constrained) {
+    // token constraints: the merged rows' sets go up before the first decode graph (the padding rows and the rows of
+    // unconstrained jobs: set 0)
+    if (m.mask) {
         ensure_set_buffer(e);
-        L.h_sets.assign((size_t)L.np, MOCR_TOKEN_SET_ALL);
-        int r0 = 0;
-        for (const Job& j : L.jobs) {
-            std::copy(j.sets.begin(), j.sets.end(), L.h_sets.begin() + r0);
-            r0 += j.n;
-        }
-        HIPCHECK(hipMemcpyAsync(e->set_of_row, L.h_sets.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        upload_per_row(e, L, L.h_sets, &Job::sets, MOCR_TOKEN_SET_ALL, e->set_of_row);
     }
-    if (L.ngram) {
+    // no-repeat n-grams: the per-row masks start as the rows' sets
+    if (m.ngram) {
         ensure_tok_table(e);
         ensure_ngram_buffers(e);
-        L.h_ngram.assign((size_t)L.np, 0);
-        int r0 = 0;
-        for (const Job& j : L.jobs) {
-            std::copy(j.ngram.begin(), j.ngram.end(), L.h_ngram.begin() + r0);
-            r0 += j.n;
-        }
-        HIPCHECK(hipMemcpyAsync(e->ngram_of_row, L.h_ngram.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        upload_per_row(e, L, L.h_ngram, &Job::ngram, 0, e->ngram_of_row);
         launch_ngram_init(e, e->row_mask, e->tok_table, e->set_of_row, e->ngram_of_row, L.np);
     }
-    // token positions: the batch records its rows when one of its jobs asked; position 0, the pad tail and the rows of the
-    // other jobs read 0
-    L.positions = false;
-    for (const Job& j : L.jobs) L.positions = L.positions || j.out_pos;
-    if (L.positions) {
+    // token positions: position 0, the pad tail and the rows of the jobs that did not ask read 0
+    if (m.positions) {
         ensure_pos_buffers(e);
         HIPCHECK(hipMemsetAsync(e->pos_out, 0, (size_t)L.n * e->cfg.max_len * MOCR_POSITION_FIELDS * sizeof(float), e->stream));
     }
@@ -1949,7 +1904,7 @@ void start_batch(mocr_engine* e, Lane& L) {
 }
 
 void finish_batch(mocr_engine* e, Lane& L) {
-    if (L.positions) {      // token positions: the deferred pass over the rows the steps recorded, before the outputs leave
+    if (L.mode.positions) {      // token positions: the deferred pass over the rows the steps recorded, before the outputs leave
         if (e->cfg.dtype == MOCR_BF16) run_positions<bf16_t>(e, L); else run_positions<float>(e, L);
     }
     int row0 = 0;
@@ -2036,27 +1991,20 @@ void advance(mocr_engine* e, Lane& L) {
         }
     }
     if (L.t >= L.steps) { finish_batch(e, L); return; }
-    DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n, L.mode, L.constrained, L.ngram);
+    DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n, L.mode);
     // (while rows are leaving, half-length chunks: the count a compaction acts on is at most 4 + 4 steps old instead of 8 + 8;
     // a batch none of whose rows has finished - the synthetic-weights headline - keeps the long chunks)
     const int chunk = L.finishing ? std::min(chunk_steps(L.np), CHUNK / 2) : chunk_steps(L.np);
     const int k = std::min(chunk, L.steps - L.t);
     const bool use_graph = !e->prof_on && !(e->cfg.flags & MOCR_FLAG_NO_GRAPH);
-    e->rec_pos = L.positions;
-    try {
-        if (use_graph && k == chunk) {
-            HIPCHECK(hipGraphLaunch(decode_graph<T>(e, st, L.np, chunk, L.t), e->stream));
-        } else {
-            for (int i = 0; i < k; ++i) {
-                if (use_graph) HIPCHECK(hipGraphLaunch(decode_graph<T>(e, st, L.np, 1, L.t + i), e->stream));
-                else decode_step<T>(e, st, L.np, L.t + i);
-            }
+    if (use_graph && k == chunk) {
+        HIPCHECK(hipGraphLaunch(decode_graph<T>(e, st, L.mode, L.np, chunk, L.t), e->stream));
+    } else {
+        for (int i = 0; i < k; ++i) {
+            if (use_graph) HIPCHECK(hipGraphLaunch(decode_graph<T>(e, st, L.mode, L.np, 1, L.t + i), e->stream));
+            else decode_step<T>(e, st, L.mode, L.np, L.t + i);
         }
-    } catch (...) {
-        e->rec_pos = false;
-        throw;
     }
-    e->rec_pos = false;
     L.t += k;
     e->n_slot_steps += (long long)L.np * k;
     if (early) {
@@ -2627,30 +2575,12 @@ static void require_sets(const mocr_engine* e, const int32_t* sets, int n) {
         if (sets[i] < 0 || sets[i] >= count) throw ArgError{"unknown token set handle (mocr_token_set_create)", MOCR_ERR_ARG};
 }
 
-// rows [base, base + n) of a request's handles, for the job that decodes them (empty: all MOCR_TOKEN_SET_ALL)
-static std::vector<int32_t> job_sets(const int32_t* sets, size_t base, int n) {
-    if (!sets) return {};
-    std::vector<int32_t> v(sets + base, sets + base + n);
-    for (int32_t h : v)
-        if (h != MOCR_TOKEN_SET_ALL) return v;
-    return {};
-}
-
 // ---- no-repeat n-grams --------------------------------------------------------------------------
 // one size per crop (null: every crop 0 = off), each in 0 .. the engine's max_len
 static void require_ngram(const mocr_engine* e, const int32_t* ngram, int n) {
     if (!ngram) return;
     for (int i = 0; i < n; ++i)
         if (ngram[i] < 0 || ngram[i] > e->cfg.max_len) throw ArgError{"no_repeat_ngram_size outside 0 .. max_len", MOCR_ERR_ARG};
-}
-
-// rows [base, base + n) of a request's sizes, for the job that decodes them (empty: all 0)
-static std::vector<int32_t> job_ngram(const int32_t* ngram, size_t base, int n) {
-    if (!ngram) return {};
-    std::vector<int32_t> v(ngram + base, ngram + base + n);
-    for (int32_t g : v)
-        if (g > 0) return v;
-    return {};
 }
 
 int mocr_token_set_create(mocr_engine* e, const int32_t* ids, int32_t n_ids, int32_t* out_set) {
@@ -2686,65 +2616,105 @@ int mocr_token_set_count(mocr_engine* e) {
     return token_set_count(e);
 }
 
-// (the token alternatives come as a pair of outputs)
-static void require_alt_pair(const void* alt_ids, const void* alt_logp) {
-    if ((alt_ids == nullptr) != (alt_logp == nullptr))
+// ---- one recognise request -----------------------------------------------------------------------
+// What a caller may ask for beyond ids and lengths; every mocr_recognize_* symbol is its source kind's implementation with
+// some of these null.  The outputs are [n][max_len] rows (x MOCR_ALTERNATIVES / MOCR_POSITION_FIELDS), host or device like
+// out_ids; `sets` and `ngram` are host arrays of one int per crop.
+struct Request {
+    float* out_logp = nullptr;
+    int32_t* out_alt_ids = nullptr; float* out_alt_logp = nullptr;     // both or neither
+    const int32_t* sets = nullptr;
+    const int32_t* ngram = nullptr;
+    float* out_pos = nullptr;
+};
+
+// The checks of a request, in the order the entry points have always made them: the alternatives pair, then - for the
+// entry points that take crops - require_ready, then the per-crop arrays.
+enum class Ready { unchecked, any_n, max_batch };
+static void validate_request(mocr_engine* e, const Request& r, int n, Ready ready) {
+    if ((r.out_alt_ids == nullptr) != (r.out_alt_logp == nullptr))
         throw ArgError{"out_alt_ids and out_alt_logp must be both null or both set", MOCR_ERR_ARG};
+    if (ready != Ready::unchecked) require_ready(e, n, ready == Ready::max_batch);
+    require_sets(e, r.sets, n);
+    require_ngram(e, r.ngram, n);
 }
 
-int mocr_recognize_device_positions(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
-                                    void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets,
-                                    const int32_t* ngram, void* d_out_pos) {
+// rows [base, base + n) of a per-crop array whose default is `dflt`, for the job that decodes them (empty: all default)
+static std::vector<int32_t> slice_rows(const int32_t* v, size_t base, int n, int32_t dflt) {
+    if (v && std::any_of(v + base, v + base + n, [dflt](int32_t x) { return x != dflt; })) return {v + base, v + base + n};
+    return {};
+}
+
+// The one place a request and a row range become a job's optional outputs and per-crop vectors.
+static void slice_job(Job& j, const Request& r, size_t base, int n, int max_len) {
+    const size_t L = (size_t)max_len;
+    j.out_logp = r.out_logp ? r.out_logp + base * L : nullptr;
+    j.out_alt_ids = r.out_alt_ids ? r.out_alt_ids + base * L * MOCR_ALTERNATIVES : nullptr;
+    j.out_alt_logp = r.out_alt_logp ? r.out_alt_logp + base * L * MOCR_ALTERNATIVES : nullptr;
+    j.out_pos = r.out_pos ? r.out_pos + base * L * MOCR_POSITION_FIELDS : nullptr;
+    j.sets = slice_rows(r.sets, base, n, MOCR_TOKEN_SET_ALL);
+    j.ngram = slice_rows(r.ngram, base, n, 0);
+}
+
+// the exported twins' arguments as a request (the device entry points pass untyped pointers)
+static Request request_of(void* out_logp = nullptr, void* out_alt_ids = nullptr, void* out_alt_logp = nullptr,
+                          const int32_t* sets = nullptr, const int32_t* ngram = nullptr, void* out_pos = nullptr) {
+    Request r;
+    r.out_logp = static_cast<float*>(out_logp);
+    r.out_alt_ids = static_cast<int32_t*>(out_alt_ids); r.out_alt_logp = static_cast<float*>(out_alt_logp);
+    r.sets = sets; r.ngram = ngram;
+    r.out_pos = static_cast<float*>(out_pos);
+    return r;
+}
+
+static int recognize_device(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, const Request& req) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
-        require_alt_pair(d_out_alt_ids, d_out_alt_logp);
-        require_ready(e, n);
-        require_sets(e, sets, n);
-        require_ngram(e, ngram, n);
+        validate_request(e, req, n, Ready::max_batch);
         if (!d_gray || !d_out_ids || !d_out_len) throw ArgError{"null device pointer", MOCR_ERR_ARG};
         HIPCHECK(hipSetDevice(e->cfg.device));
         Job j;
         j.src = reinterpret_cast<const uint8_t*>(d_gray); j.src_host = false;
         j.n = n; j.max_len = e->gen_max_len;
         j.out_ids = reinterpret_cast<int32_t*>(d_out_ids); j.out_len = reinterpret_cast<int32_t*>(d_out_len); j.out_host = false;
-        j.out_logp = reinterpret_cast<float*>(d_out_logp);
-        j.out_alt_ids = reinterpret_cast<int32_t*>(d_out_alt_ids); j.out_alt_logp = reinterpret_cast<float*>(d_out_alt_logp);
-        j.sets = job_sets(sets, 0, n);
-        j.ngram = job_ngram(ngram, 0, n);
-        j.out_pos = reinterpret_cast<float*>(d_out_pos);
+        slice_job(j, req, 0, n, e->cfg.max_len);
         submit(e, j);
     });
+}
+
+int mocr_recognize_device_positions(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
+                                    void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets,
+                                    const int32_t* ngram, void* d_out_pos) {
+    return recognize_device(e, d_gray, n, d_out_ids, d_out_len, request_of(d_out_logp, d_out_alt_ids, d_out_alt_logp, sets, ngram, d_out_pos));
 }
 
 int mocr_recognize_device_norepeat(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
                                    void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets,
                                    const int32_t* ngram) {
-    return mocr_recognize_device_positions(e, d_gray, n, d_out_ids, d_out_len, d_out_logp, d_out_alt_ids, d_out_alt_logp, sets, ngram,
-                                           nullptr);
+    return recognize_device(e, d_gray, n, d_out_ids, d_out_len, request_of(d_out_logp, d_out_alt_ids, d_out_alt_logp, sets, ngram));
 }
 
 int mocr_recognize_device_constrained(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
                                       void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets) {
-    return mocr_recognize_device_norepeat(e, d_gray, n, d_out_ids, d_out_len, d_out_logp, d_out_alt_ids, d_out_alt_logp, sets, nullptr);
+    return recognize_device(e, d_gray, n, d_out_ids, d_out_len, request_of(d_out_logp, d_out_alt_ids, d_out_alt_logp, sets));
 }
 
 int mocr_recognize_device_alts(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp,
                                void* d_out_alt_ids, void* d_out_alt_logp) {
-    return mocr_recognize_device_constrained(e, d_gray, n, d_out_ids, d_out_len, d_out_logp, d_out_alt_ids, d_out_alt_logp, nullptr);
+    return recognize_device(e, d_gray, n, d_out_ids, d_out_len, request_of(d_out_logp, d_out_alt_ids, d_out_alt_logp));
 }
 
 int mocr_recognize_device_scored(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp) {
-    return mocr_recognize_device_alts(e, d_gray, n, d_out_ids, d_out_len, d_out_logp, nullptr, nullptr);
+    return recognize_device(e, d_gray, n, d_out_ids, d_out_len, request_of(d_out_logp));
 }
 
 int mocr_recognize_device(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len) {
-    return mocr_recognize_device_scored(e, d_gray, n, d_out_ids, d_out_len, nullptr);
+    return recognize_device(e, d_gray, n, d_out_ids, d_out_len, Request{});
 }
 
 static void recognize_host_chunks(mocr_engine* e, const uint8_t* images, int n, int h, int w, int64_t row_stride,
                                   int64_t image_stride, int channels, int max_len, int32_t* out_ids, int32_t* out_len,
-                                  float* out_logp = nullptr, int32_t* out_alt_ids = nullptr, float* out_alt_logp = nullptr,
-                                  const int32_t* sets = nullptr, const int32_t* ngram = nullptr, float* out_pos = nullptr) {
+                                  const Request& req) {
     const int IMG = e->cfg.image_size;
     if (h != IMG || w != IMG)
         throw ArgError{"crops must be image_size x image_size (resize with PIL BILINEAR on the caller side)", MOCR_ERR_UNSUPPORTED};
@@ -2757,12 +2727,7 @@ static void recognize_host_chunks(mocr_engine* e, const uint8_t* images, int n, 
         j.row_stride = row_stride; j.image_stride = image_stride;
         j.n = std::min(e->cfg.max_batch, n - base); j.max_len = max_len;
         j.out_ids = out_ids + (size_t)base * e->cfg.max_len; j.out_len = out_len + base; j.out_host = true;
-        j.out_logp = out_logp ? out_logp + (size_t)base * e->cfg.max_len : nullptr;
-        j.out_alt_ids = out_alt_ids ? out_alt_ids + (size_t)base * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
-        j.out_alt_logp = out_alt_ids ? out_alt_logp + (size_t)base * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
-        j.sets = job_sets(sets, (size_t)base, j.n);
-        j.ngram = job_ngram(ngram, (size_t)base, j.n);
-        j.out_pos = out_pos ? out_pos + (size_t)base * e->cfg.max_len * MOCR_POSITION_FIELDS : nullptr;
+        slice_job(j, req, (size_t)base, j.n, e->cfg.max_len);
         e->pending.push_back(j);
     }
     drive(e);
@@ -2774,54 +2739,52 @@ int mocr_recognize(mocr_engine* e, const uint8_t* images, int32_t n, int32_t h, 
         std::lock_guard<std::mutex> lk(e->mu);
         require_ready(e, n, false);
         HIPCHECK(hipSetDevice(e->cfg.device));
-        recognize_host_chunks(e, images, n, h, w, row_stride, image_stride, channels, e->gen_max_len, out_ids, out_len);
+        recognize_host_chunks(e, images, n, h, w, row_stride, image_stride, channels, e->gen_max_len, out_ids, out_len, Request{});
+    });
+}
+
+static int recognize_gray_host(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                               int32_t* out_len, const Request& req) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        validate_request(e, req, n, Ready::any_n);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        const int IMG = e->cfg.image_size;
+        recognize_host_chunks(e, gray, n, IMG, IMG, IMG, (int64_t)IMG * IMG, 1, max_len_override, out_ids, out_len, req);
     });
 }
 
 int mocr_recognize_gray_host_positions(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
                                        int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
                                        const int32_t* sets, const int32_t* ngram, float* out_pos) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        require_alt_pair(out_alt_ids, out_alt_logp);
-        require_ready(e, n, false);
-        require_sets(e, sets, n);
-        require_ngram(e, ngram, n);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        const int IMG = e->cfg.image_size;
-        recognize_host_chunks(e, gray, n, IMG, IMG, IMG, (int64_t)IMG * IMG, 1, max_len_override, out_ids, out_len, out_logp,
-                              out_alt_ids, out_alt_logp, sets, ngram, out_pos);
-    });
+    return recognize_gray_host(e, gray, n, max_len_override, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos));
 }
 
 int mocr_recognize_gray_host_norepeat(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
                                       int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
                                       const int32_t* sets, const int32_t* ngram) {
-    return mocr_recognize_gray_host_positions(e, gray, n, max_len_override, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, sets,
-                                              ngram, nullptr);
+    return recognize_gray_host(e, gray, n, max_len_override, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram));
 }
 
 int mocr_recognize_gray_host_constrained(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
                                          int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
                                          const int32_t* sets) {
-    return mocr_recognize_gray_host_norepeat(e, gray, n, max_len_override, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, sets,
-                                             nullptr);
+    return recognize_gray_host(e, gray, n, max_len_override, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp, sets));
 }
 
 int mocr_recognize_gray_host_alts(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
                                   int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp) {
-    return mocr_recognize_gray_host_constrained(e, gray, n, max_len_override, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp,
-                                                nullptr);
+    return recognize_gray_host(e, gray, n, max_len_override, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp));
 }
 
 int mocr_recognize_gray_host_scored(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
                                     int32_t* out_len, float* out_logp) {
-    return mocr_recognize_gray_host_alts(e, gray, n, max_len_override, out_ids, out_len, out_logp, nullptr, nullptr);
+    return recognize_gray_host(e, gray, n, max_len_override, out_ids, out_len, request_of(out_logp));
 }
 
 int mocr_recognize_gray_host(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
                              int32_t* out_len) {
-    return mocr_recognize_gray_host_scored(e, gray, n, max_len_override, out_ids, out_len, nullptr);
+    return recognize_gray_host(e, gray, n, max_len_override, out_ids, out_len, Request{});
 }
 
 // Host pixels uploaded once (an image, or a whole page several crops are cut from) ...
@@ -2985,9 +2948,7 @@ static void preprocess_images(mocr_engine* e, const mocr_image* imgs, int n, uin
 // the preparation stream) while the lanes decode chunk k; a job's lane stream waits ON THE DEVICE for its chunk's event,
 // so the host never blocks on a preparation.  r02 prepared ALL crops, synchronised, and only then started to decode.
 static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& srcs, const PrepView* views, int n, int32_t* out_ids,
-                               int32_t* out_len, float* out_logp = nullptr, int32_t* out_alt_ids = nullptr,
-                               float* out_alt_logp = nullptr, const int32_t* sets = nullptr, const int32_t* ngram = nullptr,
-                               float* out_pos = nullptr) {
+                               int32_t* out_len, const Request& req) {
     const size_t plane = (size_t)e->cfg.image_size * e->cfg.image_size;
     const int C = std::min(e->cfg.max_batch, 4096), nchunks = (n + C - 1) / C;
     uint8_t* const d_gray = (uint8_t*)e->grow(e->rs_gray, (size_t)n * plane);
@@ -2998,12 +2959,7 @@ static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& sr
         j.row_stride = e->cfg.image_size; j.image_stride = (int64_t)plane;
         j.n = std::min(C, n - k * C); j.max_len = e->gen_max_len;
         j.out_ids = out_ids + (size_t)k * C * e->cfg.max_len; j.out_len = out_len + (size_t)k * C; j.out_host = true;
-        j.out_logp = out_logp ? out_logp + (size_t)k * C * e->cfg.max_len : nullptr;
-        j.out_alt_ids = out_alt_ids ? out_alt_ids + (size_t)k * C * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
-        j.out_alt_logp = out_alt_ids ? out_alt_logp + (size_t)k * C * e->cfg.max_len * MOCR_ALTERNATIVES : nullptr;
-        j.sets = job_sets(sets, (size_t)k * C, j.n);
-        j.ngram = job_ngram(ngram, (size_t)k * C, j.n);
-        j.out_pos = out_pos ? out_pos + (size_t)k * C * e->cfg.max_len * MOCR_POSITION_FIELDS : nullptr;
+        slice_job(j, req, (size_t)k * C, j.n, e->cfg.max_len);
         e->pending.push_back(j);
     };
     std::vector<PrepHold> holds(nchunks);
@@ -3058,15 +3014,10 @@ int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t
     });
 }
 
-int mocr_recognize_images_positions(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
-                                    float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets,
-                                    const int32_t* ngram, float* out_pos) {
+static int recognize_images(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len, const Request& req) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
-        require_alt_pair(out_alt_ids, out_alt_logp);
-        require_ready(e, n, false);
-        require_sets(e, sets, n);
-        require_ngram(e, ngram, n);
+        validate_request(e, req, n, Ready::any_n);
         if (!images || !out_ids || !out_len) throw ArgError{"null pointer", MOCR_ERR_ARG};
         HIPCHECK(hipSetDevice(e->cfg.device));
         drive(e);
@@ -3076,33 +3027,39 @@ int mocr_recognize_images_positions(mocr_engine* e, const mocr_image* images, in
             srcs[i] = source_of(images[i]);
             views[i] = PrepView{i, 0, 0, srcs[i].w, srcs[i].h, srcs[i].rot};
         }
-        prepare_and_decode(e, srcs, views.data(), n, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos);
+        prepare_and_decode(e, srcs, views.data(), n, out_ids, out_len, req);
     });
+}
+
+int mocr_recognize_images_positions(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                                    float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets,
+                                    const int32_t* ngram, float* out_pos) {
+    return recognize_images(e, images, n, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos));
 }
 
 int mocr_recognize_images_norepeat(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
                                    float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets,
                                    const int32_t* ngram) {
-    return mocr_recognize_images_positions(e, images, n, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, sets, ngram, nullptr);
+    return recognize_images(e, images, n, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram));
 }
 
 int mocr_recognize_images_constrained(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
                                       float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets) {
-    return mocr_recognize_images_norepeat(e, images, n, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, sets, nullptr);
+    return recognize_images(e, images, n, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp, sets));
 }
 
 int mocr_recognize_images_alts(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
                                float* out_logp, int32_t* out_alt_ids, float* out_alt_logp) {
-    return mocr_recognize_images_constrained(e, images, n, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp, nullptr);
+    return recognize_images(e, images, n, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp));
 }
 
 int mocr_recognize_images_scored(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
                                  float* out_logp) {
-    return mocr_recognize_images_alts(e, images, n, out_ids, out_len, out_logp, nullptr, nullptr);
+    return recognize_images(e, images, n, out_ids, out_len, request_of(out_logp));
 }
 
 int mocr_recognize_images(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len) {
-    return mocr_recognize_images_scored(e, images, n, out_ids, out_len, nullptr);
+    return recognize_images(e, images, n, out_ids, out_len, Request{});
 }
 
 // The crop a detected text region gets (src/ui/main_window.py:9530-9540): its bounding box grown by
@@ -3118,14 +3075,11 @@ static bool padded_region(const mocr_region& r, int page_h, int page_w, PrepView
     return true;
 }
 
-int mocr_recognize_regions_positions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
-                                     int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
-                                     float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos) {
+static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions, int32_t n_regions,
+                             int32_t* out_ids, int32_t* out_len, const Request& req) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
-        require_alt_pair(out_alt_ids, out_alt_logp);
-        require_sets(e, sets, std::max(n_regions, 0));
-        require_ngram(e, ngram, std::max(n_regions, 0));
+        validate_request(e, req, std::max(n_regions, 0), Ready::unchecked);
         if (!e->committed) throw ArgError{"weights not committed (mocr_commit_weights)", MOCR_ERR_STATE};
         if (!pages || n_pages < 1 || n_regions < 0 || (n_regions > 0 && (!regions || !out_ids || !out_len)))
             throw ArgError{"bad argument", MOCR_ERR_ARG};
@@ -3145,75 +3099,70 @@ int mocr_recognize_regions_positions(mocr_engine* e, const mocr_image* pages, in
             if (!padded_region(r, srcs[r.page].h, srcs[r.page].w, v)) continue;
             where[i] = (int)views.size();
             views.push_back(v);
-            if (sets) view_sets.push_back(sets[i]);
-            if (ngram) view_ngram.push_back(ngram[i]);
+            if (req.sets) view_sets.push_back(req.sets[i]);
+            if (req.ngram) view_ngram.push_back(req.ngram[i]);
         }
-        const int L = e->cfg.max_len, nv = (int)views.size();
-        std::vector<int32_t> ids((size_t)nv * L), lens(nv);
-        std::vector<float> logp(out_logp ? (size_t)nv * L : 0);
-        const size_t LA = (size_t)L * MOCR_ALTERNATIVES;
-        std::vector<int32_t> alt_ids(out_alt_ids ? (size_t)nv * LA : 0);
-        std::vector<float> alt_logp(out_alt_ids ? (size_t)nv * LA : 0);
-        const size_t LP = (size_t)L * MOCR_POSITION_FIELDS;
-        std::vector<float> posv(out_pos ? (size_t)nv * LP : 0);
+        // Every output the caller asked for: the caller's rows (one per region), the elements of a row, what a sliver's row
+        // reads, and the recognised crops' rows (a buffer of ours).  All hold 4-byte elements, moved as bytes: a fill value is
+        // given as its bit pattern (0.f = 0, -1 = all ones).
+        const size_t L = (size_t)e->cfg.max_len, nv = views.size();
+        struct Out { void* dst; size_t per_row; uint32_t fill; std::vector<uint32_t> rows, sliver; };
+        Out outs[] = {{out_ids, L, (uint32_t)e->cfg.pad_id, {}, {}},
+                      {out_len, 1, 0u, {}, {}},
+                      {req.out_logp, L, 0u, {}, {}},
+                      {req.out_alt_ids, L * MOCR_ALTERNATIVES, 0xffffffffu, {}, {}},
+                      {req.out_alt_logp, L * MOCR_ALTERNATIVES, 0u, {}, {}},
+                      {req.out_pos, L * MOCR_POSITION_FIELDS, 0u, {}, {}}};
+        for (Out& o : outs)
+            if (o.dst) { o.rows.resize(nv * o.per_row); o.sliver.assign(o.per_row, o.fill); }
+        auto rows_of = [&](int k) { return outs[k].dst ? outs[k].rows.data() : nullptr; };
         if (nv > 0)
-            prepare_and_decode(e, srcs, views.data(), nv, ids.data(), lens.data(), out_logp ? logp.data() : nullptr,
-                               out_alt_ids ? alt_ids.data() : nullptr, out_alt_ids ? alt_logp.data() : nullptr,
-                               sets ? view_sets.data() : nullptr, ngram ? view_ngram.data() : nullptr, out_pos ? posv.data() : nullptr);
-        for (int i = 0; i < n_regions; ++i) {
-            int32_t* row = out_ids + (size_t)i * L;
-            if (where[i] < 0) {
-                for (int t = 0; t < L; ++t) row[t] = e->cfg.pad_id;
-                out_len[i] = 0;
-                if (out_logp) std::fill(out_logp + (size_t)i * L, out_logp + (size_t)(i + 1) * L, 0.f);
-                if (out_alt_ids) {
-                    std::fill(out_alt_ids + i * LA, out_alt_ids + (i + 1) * LA, -1);
-                    std::fill(out_alt_logp + i * LA, out_alt_logp + (i + 1) * LA, 0.f);
-                }
-                if (out_pos) std::fill(out_pos + i * LP, out_pos + (i + 1) * LP, 0.f);
-            } else {
-                memcpy(row, ids.data() + (size_t)where[i] * L, (size_t)L * sizeof(int32_t));
-                out_len[i] = lens[where[i]];
-                if (out_logp) memcpy(out_logp + (size_t)i * L, logp.data() + (size_t)where[i] * L, (size_t)L * sizeof(float));
-                if (out_alt_ids) {
-                    memcpy(out_alt_ids + i * LA, alt_ids.data() + where[i] * LA, LA * sizeof(int32_t));
-                    memcpy(out_alt_logp + i * LA, alt_logp.data() + where[i] * LA, LA * sizeof(float));
-                }
-                if (out_pos) memcpy(out_pos + i * LP, posv.data() + where[i] * LP, LP * sizeof(float));
+            prepare_and_decode(e, srcs, views.data(), (int)nv, reinterpret_cast<int32_t*>(rows_of(0)), reinterpret_cast<int32_t*>(rows_of(1)),
+                               request_of(rows_of(2), rows_of(3), rows_of(4), req.sets ? view_sets.data() : nullptr,
+                                          req.ngram ? view_ngram.data() : nullptr, rows_of(5)));
+        for (int i = 0; i < n_regions; ++i)
+            for (Out& o : outs) {
+                if (!o.dst) continue;
+                const size_t bytes = o.per_row * sizeof(uint32_t);
+                memcpy(static_cast<char*>(o.dst) + (size_t)i * bytes,
+                       where[i] < 0 ? o.sliver.data() : o.rows.data() + (size_t)where[i] * o.per_row, bytes);
             }
-        }
     });
+}
+
+int mocr_recognize_regions_positions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                     int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                     float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos) {
+    return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len,
+                             request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos));
 }
 
 int mocr_recognize_regions_norepeat(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
                                     int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
                                     float* out_alt_logp, const int32_t* sets, const int32_t* ngram) {
-    return mocr_recognize_regions_positions(e, pages, n_pages, regions, n_regions, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp,
-                                            sets, ngram, nullptr);
+    return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram));
 }
 
 int mocr_recognize_regions_constrained(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
                                        int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
                                        float* out_alt_logp, const int32_t* sets) {
-    return mocr_recognize_regions_norepeat(e, pages, n_pages, regions, n_regions, out_ids, out_len, out_logp, out_alt_ids, out_alt_logp,
-                                           sets, nullptr);
+    return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp, sets));
 }
 
 int mocr_recognize_regions_alts(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
                                 int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
                                 float* out_alt_logp) {
-    return mocr_recognize_regions_constrained(e, pages, n_pages, regions, n_regions, out_ids, out_len, out_logp, out_alt_ids,
-                                              out_alt_logp, nullptr);
+    return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp));
 }
 
 int mocr_recognize_regions_scored(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
                                   int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp) {
-    return mocr_recognize_regions_alts(e, pages, n_pages, regions, n_regions, out_ids, out_len, out_logp, nullptr, nullptr);
+    return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len, request_of(out_logp));
 }
 
 int mocr_recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions, int32_t n_regions,
                            int32_t* out_ids, int32_t* out_len) {
-    return mocr_recognize_regions_scored(e, pages, n_pages, regions, n_regions, out_ids, out_len, nullptr);
+    return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len, Request{});
 }
 
 int mocr_set_generate_max_length(mocr_engine* e, int32_t max_len) {
@@ -3564,10 +3513,12 @@ int mocr_op_ngram_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_b
     });
 }
 
-int mocr_op_dec_token_ngram(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
-                            const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
-                            const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
-                            const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row) {
+// The token kernel on the caller's buffers: the five mocr_op_dec_token* symbols are this with some of the pointers null.
+static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum = nullptr, float* d_scores = nullptr,
+                        const float* d_top_val = nullptr, const int32_t* d_top_idx = nullptr, int32_t* d_alt_ids = nullptr,
+                        float* d_alt_logp = nullptr, const uint32_t* d_tok_mask = nullptr, const int32_t* d_set_of_row = nullptr,
+                        uint32_t* d_row_mask = nullptr, const uint32_t* d_base_mask = nullptr,
+                        const int32_t* d_base_set_of_row = nullptr, const int32_t* d_ngram_of_row = nullptr) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -3615,28 +3566,39 @@ int mocr_op_dec_token_ngram(mocr_engine* e, const mocr_token_args* a, const floa
     });
 }
 
+int mocr_op_dec_token_ngram(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                            const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
+                            const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
+                            const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row) {
+    return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, d_row_mask,
+                        d_base_mask, d_base_set_of_row, d_ngram_of_row);
+}
+
 int mocr_op_dec_token_masked(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
                              const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
                              const uint32_t* d_tok_mask, const int32_t* d_set_of_row) {
-    return mocr_op_dec_token_ngram(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row,
-                                   nullptr, nullptr, nullptr, nullptr);
+    return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row);
 }
 
 int mocr_op_dec_token_topk(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
                            const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp) {
-    return mocr_op_dec_token_masked(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, nullptr, nullptr);
+    return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp);
 }
 
 int mocr_op_dec_token_scored(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores) {
-    return mocr_op_dec_token_topk(e, a, d_cand_sum, d_scores, nullptr, nullptr, nullptr, nullptr);
+    return op_dec_token(e, a, d_cand_sum, d_scores);
 }
 
-int mocr_op_dec_token(mocr_engine* e, const mocr_token_args* a) { return mocr_op_dec_token_scored(e, a, nullptr, nullptr); }
+int mocr_op_dec_token(mocr_engine* e, const mocr_token_args* a) { return op_dec_token(e, a); }
 
-int mocr_op_gemm_argmax_masked(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
-                               int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N,
-                               int32_t K, int32_t tile, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
-                               const int32_t* d_rowmap) {
+// The fused LM head on the caller's buffers: the four mocr_op_gemm_argmax* / _topk symbols are this with some of `lm` null.
+static int op_lm_head(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val, int32_t M, int32_t N,
+                      int32_t K, int32_t tile, const LmHead& lm) {
+    int32_t* const d_cand_idx = lm.cand_idx;
+    float* const d_cand_sum = lm.cand_sum, * const d_top_val = lm.top_val;
+    int32_t* const d_top_idx = lm.top_idx;
+    const uint32_t* const d_tok_mask = lm.mask.table;
+    const int32_t* const d_set_of_row = lm.mask.set_of_row;
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -3648,41 +3610,39 @@ int mocr_op_gemm_argmax_masked(mocr_engine* e, const void* dA, const void* dW, c
             throw ArgError{"mocr_op_gemm_topk: d_top_val / d_top_idx come together and with d_cand_sum", MOCR_ERR_ARG};
         if ((d_tok_mask == nullptr) != (d_set_of_row == nullptr) || (d_tok_mask && N % 128))
             throw ArgError{"mocr_op_gemm_argmax_masked: d_tok_mask and d_set_of_row come together, N a multiple of 128", MOCR_ERR_ARG};
+        // (the name and the epilogue by the richest output given, as the steps choose theirs by the batch's mode)
+        DecMode m;
+        m.level = d_top_val ? 2 : d_cand_sum ? 1 : 0; m.mask = d_tok_mask != nullptr;
+        const char* const name = m.mask ? "op_gemm_argmax_masked" : m.level == 2 ? "op_gemm_topk" : m.level == 1 ? "op_gemm_argmax_lse" : "op_gemm_argmax";
         dispatch(e, [&](auto tag) {
-            if (d_tok_mask) {
-                const TokMask tm{d_tok_mask, d_set_of_row, d_rowmap};
-                gemm<decltype(tag)>(e, "op_gemm_argmax_masked", dA, K, dW, d_bias, d_cand_val, N, nullptr, M, N, K,
-                                    d_top_val ? EPI_TOPK_M : d_cand_sum ? EPI_ARGMAX_LSE_M : EPI_ARGMAX_M, tile, 1, 0, nullptr, 0, nullptr, 0,
-                                    d_cand_idx, nullptr, d_cand_sum, d_top_val, d_top_idx, &tm);
-            } else if (d_top_val)
-                gemm<decltype(tag)>(e, "op_gemm_topk", dA, K, dW, d_bias, d_cand_val, N, nullptr, M, N, K, EPI_TOPK, tile, 1, 0,
-                                    nullptr, 0, nullptr, 0, d_cand_idx, nullptr, d_cand_sum, d_top_val, d_top_idx);
-            else if (d_cand_sum)
-                gemm<decltype(tag)>(e, "op_gemm_argmax_lse", dA, K, dW, d_bias, d_cand_val, N, nullptr, M, N, K, EPI_ARGMAX_LSE, tile, 1, 0,
-                                    nullptr, 0, nullptr, 0, d_cand_idx, nullptr, d_cand_sum);
-            else
-            gemm<decltype(tag)>(e, "op_gemm_argmax", dA, K, dW, d_bias, d_cand_val, N, nullptr, M, N, K, EPI_ARGMAX, tile, 1, 0,
-                                nullptr, 0, nullptr, 0, d_cand_idx);
+            gemm<decltype(tag)>(e, name, dA, K, dW, d_bias, d_cand_val, N, nullptr, M, N, K, m.epilogue(), tile, 1, 0, nullptr, 0, nullptr, 0, &lm);
         });
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
+int mocr_op_gemm_argmax_masked(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                               int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N,
+                               int32_t K, int32_t tile, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
+                               const int32_t* d_rowmap) {
+    return op_lm_head(e, dA, dW, d_bias, d_cand_val, M, N, K, tile,
+                      LmHead{d_cand_idx, d_cand_sum, d_top_val, d_top_idx, TokMask{d_tok_mask, d_set_of_row, d_rowmap}});
+}
+
 int mocr_op_gemm_topk(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
                       int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N, int32_t K,
                       int32_t tile) {
-    return mocr_op_gemm_argmax_masked(e, dA, dW, d_bias, d_cand_val, d_cand_idx, d_cand_sum, d_top_val, d_top_idx, M, N, K, tile,
-                                      nullptr, nullptr, nullptr);
+    return op_lm_head(e, dA, dW, d_bias, d_cand_val, M, N, K, tile, LmHead{d_cand_idx, d_cand_sum, d_top_val, d_top_idx, {}});
 }
 
 int mocr_op_gemm_argmax_lse(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
                             int32_t* d_cand_idx, float* d_cand_sum, int32_t M, int32_t N, int32_t K, int32_t tile) {
-    return mocr_op_gemm_topk(e, dA, dW, d_bias, d_cand_val, d_cand_idx, d_cand_sum, nullptr, nullptr, M, N, K, tile);
+    return op_lm_head(e, dA, dW, d_bias, d_cand_val, M, N, K, tile, LmHead{d_cand_idx, d_cand_sum, nullptr, nullptr, {}});
 }
 
 int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
                         int32_t* d_cand_idx, int32_t M, int32_t N, int32_t K, int32_t tile) {
-    return mocr_op_gemm_argmax_lse(e, dA, dW, d_bias, d_cand_val, d_cand_idx, nullptr, M, N, K, tile);
+    return op_lm_head(e, dA, dW, d_bias, d_cand_val, M, N, K, tile, LmHead{d_cand_idx, nullptr, nullptr, nullptr, {}});
 }
 
 int mocr_op_smallm_gemm(mocr_engine* e, const mocr_smallm_args* a) {

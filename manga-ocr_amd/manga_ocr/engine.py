@@ -175,19 +175,28 @@ class Engine:
             raise ValueError(f"no_repeat_ngram: sizes must be in 0 .. max_len ({self.spec.max_len}), 0 = off")
         return np.ascontiguousarray(a, dtype=np.int32)
 
-    def _constrained_blocks(self, n: int, scores: bool, alternatives: bool):
-        """the output blocks of a *_constrained call (None where not asked) and what the caller gets back"""
-        ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
-        lens = np.zeros(n, dtype=np.int32)
-        logp = np.zeros((n, self.spec.max_len), dtype=np.float32) if (scores or alternatives) else None
-        alt_ids, alt_logp = self._alt_blocks(n) if alternatives else (None, None)
-        out = (ids, lens, logp, alt_ids, alt_logp) if alternatives else (ids, lens, logp) if scores else (ids, lens)
-        return ids, lens, logp, alt_ids, alt_logp, out
+    def _blocks(self, n: int, scores: bool, alternatives: bool, positions: bool):
+        """The output blocks of a recognise call: (ids, lens, logp, alt_ids, alt_logp, pos), None where not asked - what
+        the engine is then passed as null.  The alternatives come as the engine leaves unwritten positions: -1 / 0."""
+        L = self.spec.max_len
+        logp = np.zeros((n, L), dtype=np.float32) if (scores or alternatives) else None
+        alt_ids = np.full((n, L, _capi.ALTERNATIVES), -1, dtype=np.int32) if alternatives else None
+        alt_logp = np.zeros((n, L, _capi.ALTERNATIVES), dtype=np.float32) if alternatives else None
+        pos = np.zeros((n, L, _capi.POSITION_FIELDS), dtype=np.float32) if positions else None
+        return np.zeros((n, L), dtype=np.int32), np.zeros(n, dtype=np.int32), logp, alt_ids, alt_logp, pos
 
-    def _alt_blocks(self, n: int):
-        """(alt_ids int32, alt_logp float32) [n, max_len, 4] as the engine leaves unwritten positions: -1 / 0"""
-        shape = (n, self.spec.max_len, _capi.ALTERNATIVES)
-        return np.full(shape, -1, dtype=np.int32), np.zeros(shape, dtype=np.float32)
+    @staticmethod
+    def _result(blocks, scores: bool, alternatives: bool, positions: bool):
+        """what the caller gets back: (ids, lens), then logp with ``scores``, logp and the pair with ``alternatives``, and pos
+        last with ``positions``"""
+        out = blocks[:5] if alternatives else blocks[:3] if scores else blocks[:2]
+        return out + (blocks[5],) if positions else out
+
+    def _per_crop(self, token_sets, no_repeat_ngram, n: int):
+        """(sets, ngram) int32 [n] each, None where not given (the sizes are checked first)"""
+        ngram = self._ngram(no_repeat_ngram, n) if no_repeat_ngram is not None else None
+        sets = self._sets(token_sets, n) if token_sets is not None else None
+        return sets, ngram
 
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False,
                          token_sets=None, no_repeat_ngram=None, positions: bool = False):
@@ -205,56 +214,14 @@ class Engine:
         ``positions=True``: the return value gets one more, LAST element, pos float32 [n,max_len,5] - per token the centre
         (cx, cy), spread (sx, sy) and patch mass of the last decoder layer's cross-attention, in fractions of the 224 x 224
         plane the encoder sees (include/mocr.h, "token positions"); same ids, scores and alternatives."""
-        if positions:
-            n = len(images)
-            pos = np.zeros((n, self.spec.max_len, _capi.POSITION_FIELDS), dtype=np.float32)
-            if n == 0:
-                return self.recognize_images(images, bgr, rotate, scores=scores, alternatives=alternatives) + (pos,)
+        n = len(images)
+        blocks = self._blocks(n, scores, alternatives, positions)
+        if n > 0:
             descs, keep = self._image_descs(images, bgr, rotate)
-            ngram = self._ngram(no_repeat_ngram, n) if no_repeat_ngram is not None else None
-            sets = self._sets(token_sets, n) if token_sets is not None else None
-            ids, lens, logp, alt_ids, alt_logp, out = self._constrained_blocks(n, scores, alternatives)
-            self._check(self.lib.mocr_recognize_images_positions(self._h, descs, n, _ptr(ids), _ptr(lens), _ptr(logp), _ptr(alt_ids),
-                                                                 _ptr(alt_logp), _ptr(sets), _ptr(ngram), _ptr(pos)))
-            return out + (pos,)
-        if no_repeat_ngram is not None and len(images) > 0:
-            descs, keep = self._image_descs(images, bgr, rotate)
-            n = len(keep)
-            ngram = self._ngram(no_repeat_ngram, n)
-            sets = self._sets(token_sets, n) if token_sets is not None else None
-            ids, lens, logp, alt_ids, alt_logp, out = self._constrained_blocks(n, scores, alternatives)
-            self._check(self.lib.mocr_recognize_images_norepeat(self._h, descs, n, _ptr(ids), _ptr(lens), _ptr(logp), _ptr(alt_ids),
-                                                                _ptr(alt_logp), _ptr(sets), _ptr(ngram)))
-            return out
-        if token_sets is not None and len(images) > 0:
-            descs, keep = self._image_descs(images, bgr, rotate)
-            n = len(keep)
-            sets = self._sets(token_sets, n)
-            ids, lens, logp, alt_ids, alt_logp, out = self._constrained_blocks(n, scores, alternatives)
-            self._check(self.lib.mocr_recognize_images_constrained(self._h, descs, n, _ptr(ids), _ptr(lens), _ptr(logp), _ptr(alt_ids),
-                                                                   _ptr(alt_logp), _ptr(sets)))
-            return out
-        if len(images) == 0:
-            empty = (np.zeros((0, self.spec.max_len), dtype=np.int32), np.zeros(0, dtype=np.int32))
-            if alternatives:
-                return empty + (np.zeros((0, self.spec.max_len), dtype=np.float32),) + self._alt_blocks(0)
-            return empty + (np.zeros((0, self.spec.max_len), dtype=np.float32),) if scores else empty
-        descs, keep = self._image_descs(images, bgr, rotate)
-        n = len(keep)
-        ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
-        lens = np.zeros(n, dtype=np.int32)
-        if alternatives:
-            logp = np.zeros((n, self.spec.max_len), dtype=np.float32)
-            alt_ids, alt_logp = self._alt_blocks(n)
-            self._check(self.lib.mocr_recognize_images_alts(self._h, descs, n, _ptr(ids), _ptr(lens), _ptr(logp), _ptr(alt_ids),
-                                                            _ptr(alt_logp)))
-            return ids, lens, logp, alt_ids, alt_logp
-        if scores:
-            logp = np.zeros((n, self.spec.max_len), dtype=np.float32)
-            self._check(self.lib.mocr_recognize_images_scored(self._h, descs, n, _ptr(ids), _ptr(lens), _ptr(logp)))
-            return ids, lens, logp
-        self._check(self.lib.mocr_recognize_images(self._h, descs, n, _ptr(ids), _ptr(lens)))
-        return ids, lens
+            sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
+            self._check(self.lib.mocr_recognize_images_positions(self._h, descs, n, *map(_ptr, blocks[:5]), _ptr(sets), _ptr(ngram),
+                                                                 _ptr(blocks[5])))
+        return self._result(blocks, scores, alternatives, positions)
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False,
                           token_sets=None, no_repeat_ngram=None, positions: bool = False):
@@ -269,44 +236,16 @@ class Engine:
         region's padded, clipped rectangle (manga_ocr.regions.padded_rect); a sliver's rows all 0."""
         regs = list(regions)
         n = len(regs)
-        ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
-        lens = np.zeros(n, dtype=np.int32)
-        logp = np.zeros((n, self.spec.max_len), dtype=np.float32) if (scores or alternatives) else None
-        alt_ids, alt_logp = self._alt_blocks(n) if alternatives else (None, None)
-        pos = np.zeros((n, self.spec.max_len, _capi.POSITION_FIELDS), dtype=np.float32) if positions else None
-        if n == 0:
-            out = (ids, lens, logp, alt_ids, alt_logp) if alternatives else (ids, lens, logp) if scores else (ids, lens)
-            return out + (pos,) if positions else out
-        descs, keep = self._image_descs(pages, bgr)
-        arr = (_capi.MocrRegion * n)()
-        for i, (pg, x, y, w, h) in enumerate(regs):
-            arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
-        if positions:
-            ngram = self._ngram(no_repeat_ngram, n) if no_repeat_ngram is not None else None
-            sets = self._sets(token_sets, n) if token_sets is not None else None
-            self._check(self.lib.mocr_recognize_regions_positions(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens), _ptr(logp),
-                                                                  _ptr(alt_ids), _ptr(alt_logp), _ptr(sets), _ptr(ngram), _ptr(pos)))
-            return ((ids, lens, logp, alt_ids, alt_logp) if alternatives else (ids, lens, logp) if scores else (ids, lens)) + (pos,)
-        if no_repeat_ngram is not None:
-            ngram = self._ngram(no_repeat_ngram, n)
-            sets = self._sets(token_sets, n) if token_sets is not None else None
-            self._check(self.lib.mocr_recognize_regions_norepeat(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens), _ptr(logp),
-                                                                 _ptr(alt_ids), _ptr(alt_logp), _ptr(sets), _ptr(ngram)))
-            return (ids, lens, logp, alt_ids, alt_logp) if alternatives else (ids, lens, logp) if scores else (ids, lens)
-        if token_sets is not None:
-            sets = self._sets(token_sets, n)
-            self._check(self.lib.mocr_recognize_regions_constrained(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens), _ptr(logp),
-                                                                    _ptr(alt_ids), _ptr(alt_logp), _ptr(sets)))
-            return (ids, lens, logp, alt_ids, alt_logp) if alternatives else (ids, lens, logp) if scores else (ids, lens)
-        if alternatives:
-            self._check(self.lib.mocr_recognize_regions_alts(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens), _ptr(logp),
-                                                             _ptr(alt_ids), _ptr(alt_logp)))
-            return ids, lens, logp, alt_ids, alt_logp
-        if scores:
-            self._check(self.lib.mocr_recognize_regions_scored(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens), _ptr(logp)))
-            return ids, lens, logp
-        self._check(self.lib.mocr_recognize_regions(self._h, descs, len(keep), arr, n, _ptr(ids), _ptr(lens)))
-        return ids, lens
+        blocks = self._blocks(n, scores, alternatives, positions)
+        if n > 0:
+            descs, keep = self._image_descs(pages, bgr)
+            arr = (_capi.MocrRegion * n)()
+            for i, (pg, x, y, w, h) in enumerate(regs):
+                arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
+            sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
+            self._check(self.lib.mocr_recognize_regions_positions(self._h, descs, len(keep), arr, n, *map(_ptr, blocks[:5]), _ptr(sets),
+                                                                  _ptr(ngram), _ptr(blocks[5])))
+        return self._result(blocks, scores, alternatives, positions)
 
     def graph_count(self) -> int:
         return int(self.lib.mocr_graph_count(self._h))
@@ -340,33 +279,10 @@ class Engine:
         [n,max_len,4]: also the token alternatives.  ``token_sets``: a set handle for every crop, or one per crop (host values).
         ``no_repeat_ngram``: a no-repeat n-gram size for every crop, or one per crop (host values).
         ``d_out_pos`` (float32 [n,max_len,5]): also the token positions."""
-        if d_out_pos is not None:
-            ngram = self._ngram(no_repeat_ngram, n) if no_repeat_ngram is not None else None
-            sets = self._sets(token_sets, n) if token_sets is not None else None
-            self._check(self.lib.mocr_recognize_device_positions(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len),
-                                                                 _ptr(d_out_logp), _ptr(d_out_alt_ids), _ptr(d_out_alt_logp), _ptr(sets),
-                                                                 _ptr(ngram), _ptr(d_out_pos)))
-            return
-        if no_repeat_ngram is not None:
-            ngram = self._ngram(no_repeat_ngram, n)
-            sets = self._sets(token_sets, n) if token_sets is not None else None
-            self._check(self.lib.mocr_recognize_device_norepeat(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len),
-                                                                _ptr(d_out_logp), _ptr(d_out_alt_ids), _ptr(d_out_alt_logp), _ptr(sets),
-                                                                _ptr(ngram)))
-            return
-        if token_sets is not None:
-            sets = self._sets(token_sets, n)
-            self._check(self.lib.mocr_recognize_device_constrained(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len),
-                                                                   _ptr(d_out_logp), _ptr(d_out_alt_ids), _ptr(d_out_alt_logp), _ptr(sets)))
-            return
-        if d_out_alt_ids is not None or d_out_alt_logp is not None:
-            self._check(self.lib.mocr_recognize_device_alts(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len), _ptr(d_out_logp),
-                                                            _ptr(d_out_alt_ids), _ptr(d_out_alt_logp)))
-            return
-        if d_out_logp is not None:
-            self._check(self.lib.mocr_recognize_device_scored(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len), _ptr(d_out_logp)))
-            return
-        self._check(self.lib.mocr_recognize_device(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len)))
+        sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
+        self._check(self.lib.mocr_recognize_device_positions(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len), _ptr(d_out_logp),
+                                                             _ptr(d_out_alt_ids), _ptr(d_out_alt_logp), _ptr(sets), _ptr(ngram),
+                                                             _ptr(d_out_pos)))
 
     def set_generate_max_length(self, max_len: int) -> None:
         self._check(self.lib.mocr_set_generate_max_length(self._h, int(max_len)))
@@ -375,44 +291,11 @@ class Engine:
                        token_sets=None, no_repeat_ngram=None, positions: bool = False):
         a = np.ascontiguousarray(gray, dtype=np.uint8)
         n = a.shape[0]
-        if positions:
-            ngram = self._ngram(no_repeat_ngram, n) if no_repeat_ngram is not None else None
-            sets = self._sets(token_sets, n) if token_sets is not None else None
-            pos = np.zeros((n, self.spec.max_len, _capi.POSITION_FIELDS), dtype=np.float32)
-            ids, lens, logp, alt_ids, alt_logp, out = self._constrained_blocks(n, scores, alternatives)
-            self._check(self.lib.mocr_recognize_gray_host_positions(self._h, _ptr(a), n, max_len or self.spec.max_len, _ptr(ids),
-                                                                    _ptr(lens), _ptr(logp), _ptr(alt_ids), _ptr(alt_logp), _ptr(sets),
-                                                                    _ptr(ngram), _ptr(pos)))
-            return out + (pos,)
-        if no_repeat_ngram is not None:
-            ngram = self._ngram(no_repeat_ngram, n)
-            sets = self._sets(token_sets, n) if token_sets is not None else None
-            ids, lens, logp, alt_ids, alt_logp, out = self._constrained_blocks(n, scores, alternatives)
-            self._check(self.lib.mocr_recognize_gray_host_norepeat(self._h, _ptr(a), n, max_len or self.spec.max_len, _ptr(ids),
-                                                                   _ptr(lens), _ptr(logp), _ptr(alt_ids), _ptr(alt_logp), _ptr(sets),
-                                                                   _ptr(ngram)))
-            return out
-        if token_sets is not None:
-            sets = self._sets(token_sets, n)
-            ids, lens, logp, alt_ids, alt_logp, out = self._constrained_blocks(n, scores, alternatives)
-            self._check(self.lib.mocr_recognize_gray_host_constrained(self._h, _ptr(a), n, max_len or self.spec.max_len, _ptr(ids),
-                                                                      _ptr(lens), _ptr(logp), _ptr(alt_ids), _ptr(alt_logp), _ptr(sets)))
-            return out
-        ids = np.zeros((n, self.spec.max_len), dtype=np.int32)
-        lens = np.zeros(n, dtype=np.int32)
-        if alternatives:
-            logp = np.zeros((n, self.spec.max_len), dtype=np.float32)
-            alt_ids, alt_logp = self._alt_blocks(n)
-            self._check(self.lib.mocr_recognize_gray_host_alts(self._h, _ptr(a), n, max_len or self.spec.max_len, _ptr(ids), _ptr(lens),
-                                                               _ptr(logp), _ptr(alt_ids), _ptr(alt_logp)))
-            return ids, lens, logp, alt_ids, alt_logp
-        if scores:
-            logp = np.zeros((n, self.spec.max_len), dtype=np.float32)
-            self._check(self.lib.mocr_recognize_gray_host_scored(self._h, _ptr(a), n, max_len or self.spec.max_len, _ptr(ids), _ptr(lens),
-                                                                 _ptr(logp)))
-            return ids, lens, logp
-        self._check(self.lib.mocr_recognize_gray_host(self._h, _ptr(a), n, max_len or self.spec.max_len, _ptr(ids), _ptr(lens)))
-        return ids, lens
+        sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
+        blocks = self._blocks(n, scores, alternatives, positions)
+        self._check(self.lib.mocr_recognize_gray_host_positions(self._h, _ptr(a), n, max_len or self.spec.max_len, *map(_ptr, blocks[:5]),
+                                                                _ptr(sets), _ptr(ngram), _ptr(blocks[5])))
+        return self._result(blocks, scores, alternatives, positions)
 
     # ------------------------------------------------------------------ test hooks
     def encode(self, d_gray, n: int) -> np.ndarray:
@@ -470,58 +353,43 @@ class Engine:
     def op_dec_bias_gelu(self, d_slabs, nslab, d_bias, d_out, rows, N) -> None:
         self._check(self.lib.mocr_op_dec_bias_gelu(self._h, _ptr(d_slabs), nslab, _ptr(d_bias), _ptr(d_out), rows, N))
 
+    @staticmethod
+    def _args(struct, kw):
+        """a ctypes argument struct of the C ABI (struct_size set) from keywords: buffers as device tensors or addresses"""
+        a = struct()
+        a.struct_size = C.sizeof(struct)
+        ftypes = dict(struct._fields_)
+        for name, value in kw.items():
+            setattr(a, name, _ptr(value).value if ftypes[name] is C.c_void_p else value)
+        return C.byref(a)
+
     def op_dec_token(self, **kw) -> None:
         """The token step; keyword arguments are the fields of mocr_token_args (buffers as device tensors or addresses)."""
-        a = _capi.MocrTokenArgs()
-        a.struct_size = C.sizeof(_capi.MocrTokenArgs)
-        for name, value in kw.items():
-            ftype = dict(_capi.MocrTokenArgs._fields_)[name]
-            setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
-        self._check(self.lib.mocr_op_dec_token(self._h, C.byref(a)))
+        self._check(self.lib.mocr_op_dec_token(self._h, self._args(_capi.MocrTokenArgs, kw)))
 
     def op_dec_token_scored(self, d_cand_sum, d_scores, **kw) -> None:
         """The scored token step: op_dec_token plus the tiles' exp sums (candidate path) and the score rows."""
-        a = _capi.MocrTokenArgs()
-        a.struct_size = C.sizeof(_capi.MocrTokenArgs)
-        for name, value in kw.items():
-            ftype = dict(_capi.MocrTokenArgs._fields_)[name]
-            setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
-        self._check(self.lib.mocr_op_dec_token_scored(self._h, C.byref(a), _ptr(d_cand_sum), _ptr(d_scores)))
+        self._check(self.lib.mocr_op_dec_token_scored(self._h, self._args(_capi.MocrTokenArgs, kw), _ptr(d_cand_sum), _ptr(d_scores)))
 
     def op_dec_token_topk(self, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, **kw) -> None:
         """The token step with alternatives: op_dec_token_scored plus the tiles' four best (candidate path) and the
         alternatives rows."""
-        a = _capi.MocrTokenArgs()
-        a.struct_size = C.sizeof(_capi.MocrTokenArgs)
-        for name, value in kw.items():
-            ftype = dict(_capi.MocrTokenArgs._fields_)[name]
-            setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
-        self._check(self.lib.mocr_op_dec_token_topk(self._h, C.byref(a), _ptr(d_cand_sum), _ptr(d_scores), _ptr(d_top_val),
-                                                    _ptr(d_top_idx), _ptr(d_alt_ids), _ptr(d_alt_logp)))
+        self._check(self.lib.mocr_op_dec_token_topk(self._h, self._args(_capi.MocrTokenArgs, kw), _ptr(d_cand_sum), _ptr(d_scores),
+                                                    _ptr(d_top_val), _ptr(d_top_idx), _ptr(d_alt_ids), _ptr(d_alt_logp)))
 
     def op_dec_token_masked(self, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, **kw) -> None:
         """The token step under token sets: op_dec_token_topk (outputs nullable from the right) plus the set table and the
         set of every row."""
-        a = _capi.MocrTokenArgs()
-        a.struct_size = C.sizeof(_capi.MocrTokenArgs)
-        for name, value in kw.items():
-            ftype = dict(_capi.MocrTokenArgs._fields_)[name]
-            setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
-        self._check(self.lib.mocr_op_dec_token_masked(self._h, C.byref(a), _ptr(d_cand_sum), _ptr(d_scores), _ptr(d_top_val),
-                                                      _ptr(d_top_idx), _ptr(d_alt_ids), _ptr(d_alt_logp), _ptr(d_tok_mask),
+        self._check(self.lib.mocr_op_dec_token_masked(self._h, self._args(_capi.MocrTokenArgs, kw), _ptr(d_cand_sum), _ptr(d_scores),
+                                                      _ptr(d_top_val), _ptr(d_top_idx), _ptr(d_alt_ids), _ptr(d_alt_logp), _ptr(d_tok_mask),
                                                       _ptr(d_set_of_row)))
 
     def op_dec_token_ngram(self, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row,
                            d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, **kw) -> None:
         """The token step with no-repeat n-grams: op_dec_token_masked plus the per-row masks (in / out), the base sets and the
         rows' sizes; the engine passes d_tok_mask = d_row_mask and d_set_of_row = 0, 1, 2, ..."""
-        a = _capi.MocrTokenArgs()
-        a.struct_size = C.sizeof(_capi.MocrTokenArgs)
-        for name, value in kw.items():
-            ftype = dict(_capi.MocrTokenArgs._fields_)[name]
-            setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
-        self._check(self.lib.mocr_op_dec_token_ngram(self._h, C.byref(a), _ptr(d_cand_sum), _ptr(d_scores), _ptr(d_top_val),
-                                                     _ptr(d_top_idx), _ptr(d_alt_ids), _ptr(d_alt_logp), _ptr(d_tok_mask),
+        self._check(self.lib.mocr_op_dec_token_ngram(self._h, self._args(_capi.MocrTokenArgs, kw), _ptr(d_cand_sum), _ptr(d_scores),
+                                                     _ptr(d_top_val), _ptr(d_top_idx), _ptr(d_alt_ids), _ptr(d_alt_logp), _ptr(d_tok_mask),
                                                      _ptr(d_set_of_row), _ptr(d_row_mask), _ptr(d_base_mask), _ptr(d_base_set_of_row),
                                                      _ptr(d_ngram_of_row)))
 
@@ -555,22 +423,12 @@ class Engine:
 
     def op_smallm_gemm(self, **kw) -> None:
         """The small-batch projection; keyword arguments are the fields of mocr_smallm_args."""
-        a = _capi.MocrSmallmArgs()
-        a.struct_size = C.sizeof(_capi.MocrSmallmArgs)
-        for name, value in kw.items():
-            ftype = dict(_capi.MocrSmallmArgs._fields_)[name]
-            setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
-        self._check(self.lib.mocr_op_smallm_gemm(self._h, C.byref(a)))
+        self._check(self.lib.mocr_op_smallm_gemm(self._h, self._args(_capi.MocrSmallmArgs, kw)))
 
     def op_latent_block(self, /, **kw) -> None:
         """The latent attention block (q -> Qt -> latent attention -> ctx); keyword arguments are the fields of
         mocr_latent_args (`self` among them: the engine is positional-only)."""
-        a = _capi.MocrLatentArgs()
-        a.struct_size = C.sizeof(_capi.MocrLatentArgs)
-        for name, value in kw.items():
-            ftype = dict(_capi.MocrLatentArgs._fields_)[name]
-            setattr(a, name, _ptr(value).value if ftype is C.c_void_p else value)
-        self._check(self.lib.mocr_op_latent_block(self._h, C.byref(a)))
+        self._check(self.lib.mocr_op_latent_block(self._h, self._args(_capi.MocrLatentArgs, kw)))
 
     # ------------------------------------------------------------------ per-kernel timing
     def op_qqt(self, d_x, d_wq, d_bq, d_wkT, d_qt, n: int) -> None:

@@ -527,18 +527,16 @@ class MultiGpuEngine:
     def token_set(self, ids) -> int:
         raise NotImplementedError(self.NO_CONSTRAINTS)
 
+    def _plain_only(self, scores, alternatives, token_sets, no_repeat_ngram, positions) -> None:
+        """the workers make the plain greedy call: the richest option asked for is the one refused"""
+        for asked, why in ((positions, self.NO_POSITIONS), (no_repeat_ngram is not None, self.NO_NGRAM),
+                           (token_sets is not None, self.NO_CONSTRAINTS), (alternatives, self.NO_ALTERNATIVES), (scores, self.NO_SCORES)):
+            if asked:
+                raise NotImplementedError(why)
+
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False,
                          alternatives: bool = False, token_sets=None, no_repeat_ngram=None, positions: bool = False) -> Tuple[np.ndarray, np.ndarray]:
-        if positions:
-            raise NotImplementedError(self.NO_POSITIONS)
-        if no_repeat_ngram is not None:
-            raise NotImplementedError(self.NO_NGRAM)
-        if token_sets is not None:
-            raise NotImplementedError(self.NO_CONSTRAINTS)
-        if alternatives:
-            raise NotImplementedError(self.NO_ALTERNATIVES)
-        if scores:
-            raise NotImplementedError(self.NO_SCORES)
+        self._plain_only(scores, alternatives, token_sets, no_repeat_ngram, positions)
         n = len(images)
         if n == 0:
             return np.zeros((0, self.max_len), np.int32), np.zeros(0, np.int32)
@@ -553,16 +551,7 @@ class MultiGpuEngine:
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False,
                           alternatives: bool = False, token_sets=None, no_repeat_ngram=None, positions: bool = False) -> Tuple[np.ndarray, np.ndarray]:
-        if positions:
-            raise NotImplementedError(self.NO_POSITIONS)
-        if no_repeat_ngram is not None:
-            raise NotImplementedError(self.NO_NGRAM)
-        if token_sets is not None:
-            raise NotImplementedError(self.NO_CONSTRAINTS)
-        if alternatives:
-            raise NotImplementedError(self.NO_ALTERNATIVES)
-        if scores:
-            raise NotImplementedError(self.NO_SCORES)
+        self._plain_only(scores, alternatives, token_sets, no_repeat_ngram, positions)
         regs = [tuple(int(v) for v in r) for r in regions]
         n = len(regs)
         if n == 0:

@@ -19,7 +19,7 @@ import time
 from concurrent.futures import Future
 from dataclasses import dataclass, field
 from pathlib import Path
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -227,6 +227,16 @@ class Recognition:
         return out
 
 
+class _Request(NamedTuple):
+    """one queued single-crop request of the batcher"""
+    gray: np.ndarray
+    future: Future
+    kind: int               # 0 ids, 1 scored, 2 with the alternatives
+    token_set: int          # 0: unconstrained
+    ngram: int              # no-repeat n-gram size, 0: off
+    positions: bool
+
+
 class _Batcher:
     """Coalesces concurrent single-crop requests into engine batches (FIFO, per-request error
     isolation like the reference's worker loop, ``src/core/workers.py:241-244``).  A request may ask for token scores;
@@ -253,8 +263,7 @@ class _Batcher:
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
-            # the kind of request, its set, its no-repeat n-gram size
-            self._q.append((gray, f, 2 if alternatives else 1 if scored else 0, int(token_set), int(no_repeat_ngram), bool(positions)))
+            self._q.append(_Request(gray, f, 2 if alternatives else 1 if scored else 0, int(token_set), int(no_repeat_ngram), bool(positions)))
             self._cv.notify()
         return f
 
@@ -273,41 +282,26 @@ class _Batcher:
                     self._cv.wait(left)
                 batch, self._q = self._q[:self.max_batch], self._q[self.max_batch:]
             try:
-                kind = max(k for _, _, k, _, _, _ in batch)
-                sets = [h for _, _, _, h, _, _ in batch]
-                extra = dict(token_sets=sets) if any(sets) else {}
-                sizes = [g for _, _, _, _, g, _ in batch]
-                if any(sizes):
-                    extra["no_repeat_ngram"] = sizes
-                want_pos = any(p for _, _, _, _, _, p in batch)
-                if want_pos:
-                    extra["positions"] = True
-                logp = alt_ids = alt_logp = pos = None
-                crops = [g for g, _, _, _, _, _ in batch]
-                if kind == 2:
-                    res = self.engine.recognize_images(crops, alternatives=True, **extra)
-                    ids, lens, logp, alt_ids, alt_logp = res[:5]
-                elif kind == 1:
-                    res = self.engine.recognize_images(crops, scores=True, **extra)
-                    ids, lens, logp = res[:3]
-                else:
-                    res = self.engine.recognize_images(crops, **extra)
-                    ids, lens = res[:2]
-                if want_pos:
-                    pos = res[-1]
-                for i, (_, f, k, _, _, p) in enumerate(batch):
-                    n = lens[i]
-                    tail = (pos[i, :n].copy(),) if p else ()
-                    if k == 2:
-                        f.set_result((ids[i, :n].copy(), logp[i, :n].copy(), alt_ids[i, :n].copy(), alt_logp[i, :n].copy()) + tail)
-                    elif k or p:
-                        f.set_result(((ids[i, :n].copy(), logp[i, :n].copy()) if k else (ids[i, :n].copy(),)) + tail)
-                    else:
-                        f.set_result(ids[i, :n].copy())
+                kind = max(r.kind for r in batch)
+                kw = {}         # only what somebody asked for: a batch of plain requests makes the plain call
+                if kind:
+                    kw["alternatives" if kind == 2 else "scores"] = True
+                if any(r.token_set for r in batch):
+                    kw["token_sets"] = [r.token_set for r in batch]
+                if any(r.ngram for r in batch):
+                    kw["no_repeat_ngram"] = [r.ngram for r in batch]
+                if any(r.positions for r in batch):
+                    kw["positions"] = True
+                res = self.engine.recognize_images([r.gray for r in batch], **kw)     # (ids, lens[, logp[, alt_ids, alt_logp]][, pos])
+                for i, r in enumerate(batch):
+                    # what this caller asked for, cut to its length: bare ids, or a tuple with its logp / alternatives / positions
+                    blocks = [0] + ([2] if r.kind else []) + ([3, 4] if r.kind == 2 else []) + ([-1] if r.positions else [])
+                    out = tuple(res[b][i, :res[1][i]].copy() for b in blocks)
+                    r.future.set_result(out if len(out) > 1 else out[0])
             except BaseException as exc:  # every waiting caller gets the error; the loop lives on
-                for _, f, _, _, _, _ in batch:
-                    if not f.done():
-                        f.set_exception(exc)
+                for r in batch:
+                    if not r.future.done():
+                        r.future.set_exception(exc)
 
     def close(self):
         with self._cv:
