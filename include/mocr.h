@@ -300,6 +300,43 @@ int mocr_recognize_regions_positions(mocr_engine* e, const mocr_image* pages, in
                                      int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
                                      float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos);
 
+/* ---- forced prefixes ---------------------------------------------------------------------------
+ * Score and continue caller-given tokens.  Per crop there is a prefix p[0 .. P-1] of token ids; the start token is NOT part of
+ * it and P = 0 means none.  Row r then holds ids[r][0] = start, ids[r][1 + i] = p[i] for i < P, and greedy tokens after that.
+ * The step that fills ids[r][t+1] with t < P is a FORCED step: it runs the decoder exactly as a free step does, only the token
+ * that is stored and fed back differs.
+ *   Stopping: the rules do not change.  A forced EOS finishes the row (out_len = t + 2, then pad); a row that reaches
+ *     generate(max_length) finishes there, forced or not.  EOS may appear only as the last prefix token.
+ *   Scores: out_logp[r][t+1] of a forced step = logit[p[t]] - logsumexp over the step's EFFECTIVE set (the row's token set minus
+ *     its n-gram bans, as in a free step); -inf when p[t] is outside that set - the token is still emitted and fed back.  On the
+ *     device (v - gmax) + (-log S), v the forced column's fp32 acc + bias (-inf when masked), gmax and S what the free step
+ *     forms; when the forced token IS the step's own pick the free step's expression is used (a -0 score keeps its sign).  A
+ *     prefix that is a whole text plus EOS therefore scores the text: sum_t out_logp[r][t] = log p(text | crop).
+ *   Alternatives: at a forced step the step's own four best, as if the step were free - entry 0 is what the model would have
+ *     chosen, not necessarily ids[r][t+1].
+ *   Sets, n-grams, positions: sets and bans apply to the normaliser and to the alternatives of forced steps; forced tokens enter
+ *     the row's history, so later bans see them; positions are computed for forced steps like any other.
+ *   Bit identity: a row with P = 0, also inside a batch that has prefixed rows, equals the same row of an un-prefixed batch of
+ *     the same mode and size in ids, lengths, scores, alternatives and positions; a row whose prefix equals the first P generated
+ *     tokens of its own free decode (same batch size and dtype) reproduces that decode bit for bit; a batch in which nobody
+ *     passes a prefix launches exactly what it launched before.
+ * A batch with a prefixed row runs the masked, scored decode steps (unconstrained rows under MOCR_TOKEN_SET_ALL); an ids-only
+ * caller sharing it gets the same ids.  The buffers (per lane max_batch x (max_len + 2) x 4 B) are allocated by the first
+ * request that asks.
+ *
+ * The *_prefix entry points: the *_positions twins plus `prefix`, a HOST int32 array [n][prefix_ld], `prefix_len`, a HOST
+ * int32 array [n], and prefix_ld (per region for the regions call; a sliver region ignores its prefix); with `prefix` and
+ * `prefix_len` null they ARE the positions calls.  MOCR_ERR_ARG: exactly one of the two null; prefix_len[i] outside
+ * 0 .. L - 1, L the call's generate(max_length) (the override of mocr_recognize_gray_host_prefix); prefix_len[i] > prefix_ld;
+ * an id outside [0, vocab); EOS before the last prefix position.  The arrays are copied before the call returns. */
+int mocr_recognize_images_prefix(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                                 float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets, const int32_t* ngram,
+                                 float* out_pos, const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld);
+int mocr_recognize_regions_prefix(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                  int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                  float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos, const int32_t* prefix,
+                                  const int32_t* prefix_len, int32_t prefix_ld);
+
 /* Preprocessing only (test hook): out_gray [n, image_size, image_size] uint8 (host) = the plane the encoder sees
  * in each of its three equal input channels before the 1/255 and (x - 0.5)/0.5 scaling. */
 int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t* out_gray);
@@ -328,6 +365,10 @@ int mocr_recognize_device_norepeat(mocr_engine* e, const void* d_gray, int32_t n
 int mocr_recognize_device_positions(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
                                     void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets,
                                     const int32_t* ngram, void* d_out_pos);
+/* ... plus prefix / prefix_len / prefix_ld, HOST arrays (forced prefixes, see above; both null or both set). */
+int mocr_recognize_device_prefix(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp,
+                                 void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets, const int32_t* ngram, void* d_out_pos,
+                                 const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld);
 /* generate(max_length=...) of every batch submitted from now on, whatever the entry point (2 <= max_len <= the
  * engine's max_len; rows are still max_len wide; mocr_recognize_gray_host's own argument overrides it).  The reference always calls generate with 300; a speech bubble is
  * typically ~32 tokens (SURVEY.md §8d reports both regimes). */
@@ -360,6 +401,11 @@ int mocr_recognize_gray_host_norepeat(mocr_engine* e, const uint8_t* gray, int32
 int mocr_recognize_gray_host_positions(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
                                        int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
                                        const int32_t* sets, const int32_t* ngram, float* out_pos);   /* + token positions */
+
+int mocr_recognize_gray_host_prefix(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                    int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets,
+                                    const int32_t* ngram, float* out_pos, const int32_t* prefix, const int32_t* prefix_len,
+                                    int32_t prefix_ld);   /* + forced prefixes */
 
 /* Single operators on device buffers of the engine's dtype (kernel unit tests). */
 int mocr_op_gemm(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, void* d_out,
@@ -475,6 +521,15 @@ int mocr_op_dec_token_ngram(mocr_engine* e, const mocr_token_args* a, const floa
                             const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
                             const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
                             const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row);
+/* The token step with forced prefixes: mocr_op_dec_token_ngram plus d_prefix int32 [rows][prefix_ld] and d_prefix_len int32
+ * [rows], by ROW, and d_tgt_val float32 [n], by SLOT (candidate path: mocr_op_gemm_argmax_target's; slab path: unused).  Slot s
+ * with step[s] < d_prefix_len[rowmap[s]] stores, finishes on and embeds d_prefix[row][step[s]] and scores it by the rule above.
+ * Needs d_scores and d_tok_mask.  d_prefix = d_prefix_len = NULL is mocr_op_dec_token_ngram. */
+int mocr_op_dec_token_prefix(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                             const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
+                             const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
+                             const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row,
+                             const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld, const float* d_tgt_val);
 /* The start of a batch with no-repeat n-grams: d_row_mask[row] = d_base_mask[d_base_set_of_row[row]] for rows [0, rows), with
  * the start token's bit cleared where d_ngram_of_row[row] == 1 (the first generated token already sees L = 1). */
 int mocr_op_ngram_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
@@ -508,6 +563,17 @@ int mocr_op_gemm_argmax_masked(mocr_engine* e, const void* dA, const void* dW, c
                                int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N,
                                int32_t K, int32_t tile, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
                                const int32_t* d_rowmap);
+/* The LM head with a target column (forced prefixes): mocr_op_gemm_argmax_masked (scored or alternatives form) plus d_prefix
+ * int32 [rows][prefix_ld] and d_prefix_len int32 [rows], by ROW, d_step int32 [M] and d_tgt_val float32 [M], by slot.  For
+ * GEMM row m with row = d_rowmap[m] and t = d_step[m] < d_prefix_len[row], the target column is d_prefix[row][t] and
+ * d_tgt_val[m] = its acc + bias (the fp32 value d_cand_val holds when that column wins its tile), -inf when the row's set
+ * leaves it out; other entries of d_tgt_val are not written.  Every other output is bit-identical to
+ * mocr_op_gemm_argmax_masked's.  The five new arguments all NULL / 0 is that call. */
+int mocr_op_gemm_argmax_target(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                               int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N,
+                               int32_t K, int32_t tile, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
+                               const int32_t* d_rowmap, const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld,
+                               const int32_t* d_step, float* d_tgt_val);
 /* bf16 engines: the small-batch projection (rows <= 32; kernels_smallm.h SmallMParams), one of the (pro, epi) pairs the
  * small-batch decode step launches: (0,0) (1,0) (0,1) (1,2) (1,3). */
 typedef struct mocr_smallm_args {

@@ -140,6 +140,10 @@ struct LaneCtx {
                                                     // A batch packs it as [rows][its generate(max_length)][768]
     float* pos_out = nullptr;                       // [Bp][max_len][MOCR_POSITION_FIELDS] by row like ids
     void *pos_q = nullptr, *pos_k = nullptr;        // deferred pass: queries / keys of POS_CHUNK rows at a time
+    // forced prefixes: allocated by the first batch that asks (ensure_prefix_buffers)
+    int* prefix = nullptr;                          // [Bp][max_len] the caller-given tokens of every row (without the start token), by row like ids
+    int* prefix_len = nullptr;                      // [Bp] by row (0: none)
+    float* tgt_val = nullptr;                       // [Bp] by slot: the LM head's value of the step's forced column
     float *x_f32 = nullptr, *a_f32 = nullptr, *c_f32 = nullptr;
     float* ln_stats = nullptr;                      // small-batch path: (mean, rstd) per row of the three pre-LayerNorm sums, [3][Bp][2]
     void *x_t = nullptr, *a_t = nullptr, *c_t = nullptr, *ctx_t = nullptr, *h_t = nullptr, *z_t = nullptr;
@@ -171,6 +175,9 @@ struct Job {
     std::vector<int32_t> sets;      // token constraints (the *_constrained entry points): one set handle per crop; empty = all MOCR_TOKEN_SET_ALL
     std::vector<int32_t> ngram;     // no-repeat n-grams (the *_norepeat entry points): one size per crop; empty = all 0
     float* out_pos = nullptr;       // nullable (the *_positions entry points): [n][max_len][MOCR_POSITION_FIELDS]; host or device like out_ids
+    std::vector<int32_t> prefix_len;    // forced prefixes (the *_prefix entry points): one length per crop; empty = all 0
+    std::vector<int32_t> prefix;        // ... and the tokens, [n][prefix_ld] (a copy: the caller's arrays need not outlive the call)
+    int prefix_ld = 0;
 };
 
 // The kind of decode steps a batch runs: the richest of what its jobs asked for.  Every choice that follows from it - the
@@ -183,8 +190,10 @@ struct DecMode {
     bool ngram = false;             // a row has no_repeat_ngram_size > 0: the masks are the per-row ones (row_mask through row_ident)
                                     // and the token kernel is the NGRAM one, which rebuilds them
     bool positions = false;         // a job asked for token positions: the steps record pos_hist, finish_batch runs the deferred pass
-    // a graph captured in one mode is never replayed in another: the mode's share of the decode-graph key (5 bits)
-    int key_bits() const { return level + (mask ? 4 : 0) + (ngram ? 8 : 0) + (positions ? 16 : 0); }
+    bool prefix = false;            // a row has a forced prefix: the steps run scored and masked (level >= 1, mask; unconstrained rows read
+                                    // set 0), the LM head also leaves the forced column's value and the token kernel stores the forced token
+    // a graph captured in one mode is never replayed in another: the mode's share of the decode-graph key (6 bits)
+    int key_bits() const { return level + (mask ? 4 : 0) + (ngram ? 8 : 0) + (positions ? 16 : 0) + (prefix ? 32 : 0); }
     int epilogue() const { return mask ? (level == 2 ? EPI_TOPK_M : level == 1 ? EPI_ARGMAX_LSE_M : EPI_ARGMAX_M)
                                        : (level == 2 ? EPI_TOPK : level == 1 ? EPI_ARGMAX_LSE : EPI_ARGMAX); }
     // profile names of the fused LM head and of the token kernel
@@ -206,8 +215,10 @@ static DecMode mode_of(const std::vector<Job>& jobs) {
         for (int32_t h : j.sets) m.mask = m.mask || h != MOCR_TOKEN_SET_ALL;
         for (int32_t g : j.ngram) m.ngram = m.ngram || g > 0;
         m.positions = m.positions || j.out_pos;
+        m.prefix = m.prefix || !j.prefix_len.empty();
     }
-    m.mask = m.mask || m.ngram;     // the bans are applied through the rows' masks, which start as the rows' sets
+    if (m.prefix) m.level = std::max(m.level, 1);      // a forced token is one more per-row fact of the masked, scored step
+    m.mask = m.mask || m.ngram || m.prefix;     // the bans are applied through the rows' masks, which start as the rows' sets
     return m;
 }
 
@@ -220,6 +231,7 @@ struct Lane {
     int np0 = 0;                    // np at the start of the batch = its kernel regime
     DecMode mode;                   // mode_of(jobs)
     std::vector<int> h_sets, h_ngram;   // the uploads of set_of_row / ngram_of_row stage from here
+    std::vector<int> h_plen, h_prefix;  // ... and those of prefix_len / prefix
     int t = 0, steps = 0, chunk = 0;
     bool finishing = false;         // a flag of this batch has reported a finished row: rows are leaving, chunks get shorter
     bool flag_pending[2] = {false, false};
@@ -387,7 +399,7 @@ template <typename K> void set_max_lds(K kernel, int bytes) {
 // ---------------------------------------------------------------------------------------- GEMM
 template <int BM> constexpr int gemm_ring() { return 2; }   // LDS ring depth per tile size
 
-template <typename T, int BM, int BN, int EPI>
+template <typename T, int BM, int BN, int EPI, bool TGT = false>
 void launch_gemm_t(mocr_engine* e, const GemmParams& p0, int split, int ybatch) {
     GemmParams p = p0;
     p.ntn = p.N / BN;
@@ -412,9 +424,9 @@ void launch_gemm_t(mocr_engine* e, const GemmParams& p0, int split, int ybatch) 
     // MOCR_NEUTRAL_BY_ROWS=0: by the batch's regime)
     static const int neutral_by_rows = env_int("MOCR_NEUTRAL_BY_ROWS", 2);
     if ((neutral_by_rows ? p.M : e->rrows(p.M)) < deep_rows && ktiles >= 4 && (long long)grid.x * grid.y * grid.z <= (long long)e->num_cus * (BM == 64 ? deep_mult64 : 1)) {
-        hipLaunchKernelGGL((gemm_kernel<T, BM, BN, EPI, 4>), grid, dim3(256), 4 * (BM + BN) * 128, e->stream, p);
+        hipLaunchKernelGGL((gemm_kernel<T, BM, BN, EPI, 4, TGT>), grid, dim3(256), 4 * (BM + BN) * 128, e->stream, p);
     } else {
-        hipLaunchKernelGGL((gemm_kernel<T, BM, BN, EPI, NST>), grid, dim3(256), lds, e->stream, p);
+        hipLaunchKernelGGL((gemm_kernel<T, BM, BN, EPI, NST, TGT>), grid, dim3(256), lds, e->stream, p);
     }
     HIPCHECK(hipGetLastError());
 }
@@ -432,8 +444,15 @@ void launch_gemm_epi(mocr_engine* e, const GemmParams& p, int epi, int split, in
         case EPI_ARGMAX_LSE: launch_gemm_t<T, BM, BN, EPI_ARGMAX_LSE>(e, p, split, ybatch); break;
         case EPI_TOPK: launch_gemm_t<T, BM, BN, EPI_TOPK>(e, p, split, ybatch); break;
         case EPI_ARGMAX_M: launch_gemm_t<T, BM, BN, EPI_ARGMAX_M>(e, p, split, ybatch); break;
-        case EPI_ARGMAX_LSE_M: launch_gemm_t<T, BM, BN, EPI_ARGMAX_LSE_M>(e, p, split, ybatch); break;
-        case EPI_TOPK_M: launch_gemm_t<T, BM, BN, EPI_TOPK_M>(e, p, split, ybatch); break;
+        // (a forced prefix's target column - GemmParams::tgt_val - is a template parameter of these two)
+        case EPI_ARGMAX_LSE_M:
+            if (p.tgt_val) launch_gemm_t<T, BM, BN, EPI_ARGMAX_LSE_M, true>(e, p, split, ybatch);
+            else launch_gemm_t<T, BM, BN, EPI_ARGMAX_LSE_M>(e, p, split, ybatch);
+            break;
+        case EPI_TOPK_M:
+            if (p.tgt_val) launch_gemm_t<T, BM, BN, EPI_TOPK_M, true>(e, p, split, ybatch);
+            else launch_gemm_t<T, BM, BN, EPI_TOPK_M>(e, p, split, ybatch);
+            break;
         default: throw ArgError{"unknown GEMM epilogue", MOCR_ERR_ARG};
     }
 }
@@ -621,7 +640,9 @@ struct LnFold { float* part = nullptr; const float* csum = nullptr; void* xb = n
 struct TokMask { const unsigned* table = nullptr; const int* set_of_row = nullptr; const int* rowmap = nullptr; };
 // What the fused LM-head epilogues write per N-tile beside the candidate values in `out`: the columns (every EPI_ARGMAX* /
 // EPI_TOPK*), the exp sums (the _LSE and TOPK forms), the four best (TOPK) - and the mask the EPI_*_M forms apply
-struct LmHead { int* cand_idx = nullptr; float* cand_sum = nullptr; float* top_val = nullptr; int* top_idx = nullptr; TokMask mask; };
+// Forced prefixes (EPI_ARGMAX_LSE_M / EPI_TOPK_M): the rows' prefixes, the slots' steps and where the target column's value goes
+struct TokTarget { const int* prefix = nullptr; const int* prefix_len = nullptr; int prefix_ld = 0; const int* step = nullptr; float* tgt_val = nullptr; };
+struct LmHead { int* cand_idx = nullptr; float* cand_sum = nullptr; float* top_val = nullptr; int* top_idx = nullptr; TokMask mask; TokTarget target; };
 
 template <typename T>
 void gemm(mocr_engine* e, const char* name, const void* A, int lda, const void* W, const float* bias, void* out, int ldo,
@@ -640,6 +661,12 @@ void gemm(mocr_engine* e, const char* name, const void* A, int lda, const void* 
     if (lm) {
         p.cand_idx = lm->cand_idx; p.cand_sum = lm->cand_sum; p.top_val = lm->top_val; p.top_idx = lm->top_idx;
         if (tm.table) { p.tok_mask = tm.table; p.set_of_row = tm.set_of_row; p.rowmap = tm.rowmap; }
+        const TokTarget& tt = lm->target;
+        if (tt.tgt_val) {
+            if ((epi != EPI_ARGMAX_LSE_M && epi != EPI_TOPK_M) || !tt.prefix || !tt.prefix_len || !tt.step || tt.prefix_ld < 1)
+                throw ArgError{std::string("a target column comes with the masked, scored LM-head epilogues and all five arrays: ") + name, MOCR_ERR_ARG};
+            p.prefix = tt.prefix; p.prefix_len = tt.prefix_len; p.prefix_ld = tt.prefix_ld; p.step = tt.step; p.tgt_val = tt.tgt_val;
+        }
     }
     p.M = M; p.N = N; p.lda = lda; p.ldw = K; p.ldo = ldo;
     int ybatch = 1;
@@ -1069,6 +1096,7 @@ static DecState make_state(mocr_engine* e, int max_len, const int* forced, int f
         st.tok_mask = e->row_mask; st.set_of_row = e->row_ident;
         st.row_mask = e->row_mask; st.base_mask = e->tok_table; st.base_set_of_row = e->set_of_row; st.ngram_of_row = e->ngram_of_row;
     }
+    if (m.prefix) { st.prefix = e->prefix; st.prefix_len = e->prefix_len; st.prefix_ld = e->cfg.max_len; st.tgt_val = e->tgt_val; }
     return st;
 }
 
@@ -1518,6 +1546,7 @@ void decode_step(mocr_engine* e, const DecState& st, const DecMode& m, int n, in
         if (m.level >= 1) lm.cand_sum = e->cand_sum;
         if (m.level >= 2) { lm.top_val = e->top_val; lm.top_idx = e->top_idx; }
         if (m.mask) lm.mask = TokMask{st.tok_mask, st.set_of_row, st.rowmap};
+        if (m.prefix) lm.target = TokTarget{st.prefix, st.prefix_len, st.prefix_ld, st.step, e->tgt_val};
         gemm<T>(e, m.head_name(), e->z_t, D, w.wv, w.bv, e->cand_val, e->V, nullptr, n, e->V, D, m.epilogue(), vt, 1, 0, nullptr, 0, nullptr,
                 0, &lm);
         dec_token<T, false>(e, st, 1, n, e->V / vt);
@@ -1565,6 +1594,12 @@ template <typename T> void init_kernel_attrs() {
         set_max_lds(gemm_kernel<T, 64, 64, E, 2>, l64);
         set_max_lds(gemm_kernel<T, 128, 128, E, 4>, 2 * l128);
         set_max_lds(gemm_kernel<T, 64, 64, E, 4>, 2 * l64);
+        if constexpr (E == EPI_ARGMAX_LSE_M || E == EPI_TOPK_M) {          // ... and with a forced prefix's target column
+            set_max_lds(gemm_kernel<T, 128, 128, E, 2, true>, l128);
+            set_max_lds(gemm_kernel<T, 64, 64, E, 2, true>, l64);
+            set_max_lds(gemm_kernel<T, 128, 128, E, 4, true>, 2 * l128);
+            set_max_lds(gemm_kernel<T, 64, 64, E, 4, true>, 2 * l64);
+        }
     });
     set_max_lds(enc_attn_simple_kernel<T>, (200 * 65 + 200 * 64 + 4 * 64 + 4 * 256) * 4);
     set_max_lds(enc_attn2_kernel, EA2_LDS);
@@ -1650,7 +1685,7 @@ hipGraphExec_t decode_graph(mocr_engine* e, const DecState& st, const DecMode& m
     const int bucket = need <= 3 ? 3 : need <= 5 ? 5 : need <= 8 ? 8 : 10;
     const int t_hi = std::min(bucket * 32, st.max_len) - 1;      // largest context this bucket covers
     // ... and by the mode of the steps: another LM-head epilogue, token kernel, set of pointers or launch each
-    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * 32 + m.key_bits(), steps, e->rrows(n));
+    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * 64 + m.key_bits(), steps, e->rrows(n));
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) return it->second;
     hipGraph_t g = nullptr;
@@ -1755,6 +1790,16 @@ static void ensure_ngram_buffers(mocr_engine* e) {
     std::vector<int> ident(Bp);
     for (size_t i = 0; i < Bp; ++i) ident[i] = (int)i;
     HIPCHECK(hipMemcpy(e->row_ident, ident.data(), Bp * sizeof(int), hipMemcpyHostToDevice));
+}
+
+// The rows' forced prefixes and the slots' target values, for the bound lane: allocated by the first batch that has a
+// prefix, like the alternatives buffers.
+static void ensure_prefix_buffers(mocr_engine* e) {
+    if (e->prefix) return;
+    const size_t Bp = (size_t)e->Bp;
+    e->prefix = e->dalloc<int>(Bp * e->cfg.max_len);
+    e->prefix_len = e->dalloc<int>(Bp);
+    e->tgt_val = e->dalloc<float>(Bp);
 }
 
 static void launch_ngram_init(mocr_engine* e, unsigned* row_mask, const unsigned* base_mask, const int* base_set_of_row,
@@ -1879,8 +1924,23 @@ void start_batch(mocr_engine* e, Lane& L) {
     // token constraints: the merged rows' sets go up before the first decode graph (the padding rows and the rows of
     // unconstrained jobs: set 0)
     if (m.mask) {
+        if (m.prefix) ensure_tok_table(e);      // (a prefixed batch runs masked even when nobody made a set: every row reads set 0)
         ensure_set_buffer(e);
         upload_per_row(e, L, L.h_sets, &Job::sets, MOCR_TOKEN_SET_ALL, e->set_of_row);
+    }
+    // forced prefixes: the merged rows' lengths and tokens (the padding rows and the rows of jobs without a prefix: length 0)
+    if (m.prefix) {
+        ensure_prefix_buffers(e);
+        upload_per_row(e, L, L.h_plen, &Job::prefix_len, 0, e->prefix_len);
+        const size_t ML = (size_t)e->cfg.max_len;
+        L.h_prefix.assign((size_t)L.np * ML, 0);
+        int r0 = 0;
+        for (const Job& j : L.jobs) {
+            for (size_t i = 0; i < j.prefix_len.size(); ++i)
+                std::copy_n(j.prefix.begin() + i * j.prefix_ld, j.prefix_len[i], L.h_prefix.begin() + (r0 + i) * ML);
+            r0 += j.n;
+        }
+        HIPCHECK(hipMemcpyAsync(e->prefix, L.h_prefix.data(), L.h_prefix.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
     }
     // no-repeat n-grams: the per-row masks start as the rows' sets
     if (m.ngram) {
@@ -2626,17 +2686,36 @@ struct Request {
     const int32_t* sets = nullptr;
     const int32_t* ngram = nullptr;
     float* out_pos = nullptr;
+    const int32_t* prefix = nullptr;        // host [n][prefix_ld], with prefix_len host [n]: both or neither
+    const int32_t* prefix_len = nullptr;
+    int32_t prefix_ld = 0;
 };
+
+// forced prefixes: per crop 0 .. gen_len - 1 tokens of the vocabulary, EOS as the last one only (gen_len: the call's generate(max_length))
+static void require_prefix(const mocr_engine* e, const Request& r, int n, int gen_len) {
+    if ((r.prefix == nullptr) != (r.prefix_len == nullptr)) throw ArgError{"prefix and prefix_len must be both null or both set", MOCR_ERR_ARG};
+    if (!r.prefix) return;
+    for (int i = 0; i < n; ++i) {
+        const int P = r.prefix_len[i];
+        if (P < 0 || P > gen_len - 1 || P > r.prefix_ld) throw ArgError{"prefix_len outside 0 .. generate(max_length) - 1, or above prefix_ld", MOCR_ERR_ARG};
+        const int32_t* p = r.prefix + (size_t)i * r.prefix_ld;
+        for (int k = 0; k < P; ++k) {
+            if (p[k] < 0 || p[k] >= e->V) throw ArgError{"prefix token outside the vocabulary", MOCR_ERR_ARG};
+            if (p[k] == e->cfg.eos_id && k + 1 < P) throw ArgError{"EOS may only be the last token of a prefix", MOCR_ERR_ARG};
+        }
+    }
+}
 
 // The checks of a request, in the order the entry points have always made them: the alternatives pair, then - for the
 // entry points that take crops - require_ready, then the per-crop arrays.
 enum class Ready { unchecked, any_n, max_batch };
-static void validate_request(mocr_engine* e, const Request& r, int n, Ready ready) {
+static void validate_request(mocr_engine* e, const Request& r, int n, Ready ready, int gen_len) {
     if ((r.out_alt_ids == nullptr) != (r.out_alt_logp == nullptr))
         throw ArgError{"out_alt_ids and out_alt_logp must be both null or both set", MOCR_ERR_ARG};
     if (ready != Ready::unchecked) require_ready(e, n, ready == Ready::max_batch);
     require_sets(e, r.sets, n);
     require_ngram(e, r.ngram, n);
+    require_prefix(e, r, n, gen_len);
 }
 
 // rows [base, base + n) of a per-crop array whose default is `dflt`, for the job that decodes them (empty: all default)
@@ -2654,23 +2733,31 @@ static void slice_job(Job& j, const Request& r, size_t base, int n, int max_len)
     j.out_pos = r.out_pos ? r.out_pos + base * L * MOCR_POSITION_FIELDS : nullptr;
     j.sets = slice_rows(r.sets, base, n, MOCR_TOKEN_SET_ALL);
     j.ngram = slice_rows(r.ngram, base, n, 0);
+    j.prefix_len = slice_rows(r.prefix_len, base, n, 0);
+    j.prefix.clear(); j.prefix_ld = 0;
+    if (!j.prefix_len.empty()) {
+        j.prefix_ld = r.prefix_ld;
+        j.prefix.assign(r.prefix + base * (size_t)r.prefix_ld, r.prefix + (base + n) * (size_t)r.prefix_ld);
+    }
 }
 
 // the exported twins' arguments as a request (the device entry points pass untyped pointers)
 static Request request_of(void* out_logp = nullptr, void* out_alt_ids = nullptr, void* out_alt_logp = nullptr,
-                          const int32_t* sets = nullptr, const int32_t* ngram = nullptr, void* out_pos = nullptr) {
+                          const int32_t* sets = nullptr, const int32_t* ngram = nullptr, void* out_pos = nullptr,
+                          const int32_t* prefix = nullptr, const int32_t* prefix_len = nullptr, int32_t prefix_ld = 0) {
     Request r;
     r.out_logp = static_cast<float*>(out_logp);
     r.out_alt_ids = static_cast<int32_t*>(out_alt_ids); r.out_alt_logp = static_cast<float*>(out_alt_logp);
     r.sets = sets; r.ngram = ngram;
     r.out_pos = static_cast<float*>(out_pos);
+    r.prefix = prefix; r.prefix_len = prefix_len; r.prefix_ld = prefix_ld;
     return r;
 }
 
 static int recognize_device(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, const Request& req) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
-        validate_request(e, req, n, Ready::max_batch);
+        validate_request(e, req, n, Ready::max_batch, e->gen_max_len);
         if (!d_gray || !d_out_ids || !d_out_len) throw ArgError{"null device pointer", MOCR_ERR_ARG};
         HIPCHECK(hipSetDevice(e->cfg.device));
         Job j;
@@ -2686,6 +2773,13 @@ int mocr_recognize_device_positions(mocr_engine* e, const void* d_gray, int32_t 
                                     void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets,
                                     const int32_t* ngram, void* d_out_pos) {
     return recognize_device(e, d_gray, n, d_out_ids, d_out_len, request_of(d_out_logp, d_out_alt_ids, d_out_alt_logp, sets, ngram, d_out_pos));
+}
+
+int mocr_recognize_device_prefix(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len, void* d_out_logp,
+                                 void* d_out_alt_ids, void* d_out_alt_logp, const int32_t* sets, const int32_t* ngram, void* d_out_pos,
+                                 const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld) {
+    return recognize_device(e, d_gray, n, d_out_ids, d_out_len,
+                            request_of(d_out_logp, d_out_alt_ids, d_out_alt_logp, sets, ngram, d_out_pos, prefix, prefix_len, prefix_ld));
 }
 
 int mocr_recognize_device_norepeat(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
@@ -2747,7 +2841,7 @@ static int recognize_gray_host(mocr_engine* e, const uint8_t* gray, int32_t n, i
                                int32_t* out_len, const Request& req) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
-        validate_request(e, req, n, Ready::any_n);
+        validate_request(e, req, n, Ready::any_n, max_len_override);
         HIPCHECK(hipSetDevice(e->cfg.device));
         const int IMG = e->cfg.image_size;
         recognize_host_chunks(e, gray, n, IMG, IMG, IMG, (int64_t)IMG * IMG, 1, max_len_override, out_ids, out_len, req);
@@ -2758,6 +2852,14 @@ int mocr_recognize_gray_host_positions(mocr_engine* e, const uint8_t* gray, int3
                                        int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
                                        const int32_t* sets, const int32_t* ngram, float* out_pos) {
     return recognize_gray_host(e, gray, n, max_len_override, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos));
+}
+
+int mocr_recognize_gray_host_prefix(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
+                                    int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets,
+                                    const int32_t* ngram, float* out_pos, const int32_t* prefix, const int32_t* prefix_len,
+                                    int32_t prefix_ld) {
+    return recognize_gray_host(e, gray, n, max_len_override, out_ids, out_len,
+                               request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len, prefix_ld));
 }
 
 int mocr_recognize_gray_host_norepeat(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
@@ -3017,7 +3119,7 @@ int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t
 static int recognize_images(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len, const Request& req) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
-        validate_request(e, req, n, Ready::any_n);
+        validate_request(e, req, n, Ready::any_n, e->gen_max_len);
         if (!images || !out_ids || !out_len) throw ArgError{"null pointer", MOCR_ERR_ARG};
         HIPCHECK(hipSetDevice(e->cfg.device));
         drive(e);
@@ -3035,6 +3137,13 @@ int mocr_recognize_images_positions(mocr_engine* e, const mocr_image* images, in
                                     float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets,
                                     const int32_t* ngram, float* out_pos) {
     return recognize_images(e, images, n, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos));
+}
+
+int mocr_recognize_images_prefix(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
+                                 float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets, const int32_t* ngram,
+                                 float* out_pos, const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld) {
+    return recognize_images(e, images, n, out_ids, out_len,
+                            request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len, prefix_ld));
 }
 
 int mocr_recognize_images_norepeat(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
@@ -3079,7 +3188,7 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
                              int32_t* out_ids, int32_t* out_len, const Request& req) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
-        validate_request(e, req, std::max(n_regions, 0), Ready::unchecked);
+        validate_request(e, req, std::max(n_regions, 0), Ready::unchecked, e->gen_max_len);
         if (!e->committed) throw ArgError{"weights not committed (mocr_commit_weights)", MOCR_ERR_STATE};
         if (!pages || n_pages < 1 || n_regions < 0 || (n_regions > 0 && (!regions || !out_ids || !out_len)))
             throw ArgError{"bad argument", MOCR_ERR_ARG};
@@ -3092,6 +3201,7 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
         std::vector<int> where(n_regions, -1);          // region -> its row among the recognised crops (-1: sliver)
         std::vector<int32_t> view_sets;                 // the recognised crops' token sets
         std::vector<int32_t> view_ngram;                // ... and no-repeat n-gram sizes
+        std::vector<int32_t> view_plen, view_prefix;    // ... and forced prefixes (a sliver's prefix is ignored)
         for (int i = 0; i < n_regions; ++i) {
             const mocr_region& r = regions[i];
             if (r.page < 0 || r.page >= n_pages) throw ArgError{"region of an unknown page", MOCR_ERR_ARG};
@@ -3101,6 +3211,10 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
             views.push_back(v);
             if (req.sets) view_sets.push_back(req.sets[i]);
             if (req.ngram) view_ngram.push_back(req.ngram[i]);
+            if (req.prefix) {
+                view_plen.push_back(req.prefix_len[i]);
+                view_prefix.insert(view_prefix.end(), req.prefix + (size_t)i * req.prefix_ld, req.prefix + (size_t)(i + 1) * req.prefix_ld);
+            }
         }
         // Every output the caller asked for: the caller's rows (one per region), the elements of a row, what a sliver's row
         // reads, and the recognised crops' rows (a buffer of ours).  All hold 4-byte elements, moved as bytes: a fill value is
@@ -3116,10 +3230,14 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
         for (Out& o : outs)
             if (o.dst) { o.rows.resize(nv * o.per_row); o.sliver.assign(o.per_row, o.fill); }
         auto rows_of = [&](int k) { return outs[k].dst ? outs[k].rows.data() : nullptr; };
+        // prefix_ld 0 (validated: every length is 0 then) leaves no tokens to point at: the inner request carries no prefix,
+        // so its two pointers stay both null or both set
+        const bool pre = req.prefix && !view_prefix.empty();
         if (nv > 0)
             prepare_and_decode(e, srcs, views.data(), (int)nv, reinterpret_cast<int32_t*>(rows_of(0)), reinterpret_cast<int32_t*>(rows_of(1)),
                                request_of(rows_of(2), rows_of(3), rows_of(4), req.sets ? view_sets.data() : nullptr,
-                                          req.ngram ? view_ngram.data() : nullptr, rows_of(5)));
+                                          req.ngram ? view_ngram.data() : nullptr, rows_of(5), pre ? view_prefix.data() : nullptr,
+                                          pre ? view_plen.data() : nullptr, pre ? req.prefix_ld : 0));
         for (int i = 0; i < n_regions; ++i)
             for (Out& o : outs) {
                 if (!o.dst) continue;
@@ -3135,6 +3253,14 @@ int mocr_recognize_regions_positions(mocr_engine* e, const mocr_image* pages, in
                                      float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos) {
     return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len,
                              request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos));
+}
+
+int mocr_recognize_regions_prefix(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                  int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                  float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos, const int32_t* prefix,
+                                  const int32_t* prefix_len, int32_t prefix_ld) {
+    return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len,
+                             request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len, prefix_ld));
 }
 
 int mocr_recognize_regions_norepeat(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
@@ -3518,7 +3644,9 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d
                         const float* d_top_val = nullptr, const int32_t* d_top_idx = nullptr, int32_t* d_alt_ids = nullptr,
                         float* d_alt_logp = nullptr, const uint32_t* d_tok_mask = nullptr, const int32_t* d_set_of_row = nullptr,
                         uint32_t* d_row_mask = nullptr, const uint32_t* d_base_mask = nullptr,
-                        const int32_t* d_base_set_of_row = nullptr, const int32_t* d_ngram_of_row = nullptr) {
+                        const int32_t* d_base_set_of_row = nullptr, const int32_t* d_ngram_of_row = nullptr,
+                        const int32_t* d_prefix = nullptr, const int32_t* d_prefix_len = nullptr, int32_t prefix_ld = 0,
+                        const float* d_tgt_val = nullptr) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -3534,7 +3662,9 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d
             ((d_alt_ids == nullptr) != (d_alt_logp == nullptr)) || (d_alt_ids && (!d_scores || (a->ncand > 0 && (!d_top_val || !d_top_idx)))) ||
             ((d_tok_mask == nullptr) != (d_set_of_row == nullptr)) || (d_tok_mask && (first || a->forced)) ||
             ((d_row_mask == nullptr) != (d_base_mask == nullptr)) || ((d_row_mask == nullptr) != (d_base_set_of_row == nullptr)) ||
-            ((d_row_mask == nullptr) != (d_ngram_of_row == nullptr)) || (d_row_mask && !d_tok_mask))
+            ((d_row_mask == nullptr) != (d_ngram_of_row == nullptr)) || (d_row_mask && !d_tok_mask) ||
+            ((d_prefix == nullptr) != (d_prefix_len == nullptr)) ||
+            (d_prefix && (!d_scores || !d_tok_mask || prefix_ld < 1 || (a->ncand > 0 && !d_tgt_val))))
             throw ArgError{"mocr_op_dec_token: bad argument", MOCR_ERR_ARG};
         DecState st{};
         st.n_real = a->n_real;
@@ -3547,6 +3677,7 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d
         st.alt_ids = d_alt_ids; st.alt_logp = d_alt_logp;
         st.tok_mask = d_tok_mask; st.set_of_row = d_set_of_row;
         st.row_mask = d_row_mask; st.base_mask = d_base_mask; st.base_set_of_row = d_base_set_of_row; st.ngram_of_row = d_ngram_of_row;
+        st.prefix = d_prefix; st.prefix_len = d_prefix_len; st.prefix_ld = prefix_ld; st.tgt_val = d_tgt_val;
         DecTokenArgs t{};
         t.slabs = a->slabs; t.nslab = first ? 0 : a->nslab; t.slab_stride = (long long)a->n * e->V;
         t.vbias = a->vbias ? a->vbias : e->w.bv;
@@ -3572,6 +3703,15 @@ int mocr_op_dec_token_ngram(mocr_engine* e, const mocr_token_args* a, const floa
                             const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row) {
     return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, d_row_mask,
                         d_base_mask, d_base_set_of_row, d_ngram_of_row);
+}
+
+int mocr_op_dec_token_prefix(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                             const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
+                             const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
+                             const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row,
+                             const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld, const float* d_tgt_val) {
+    return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, d_row_mask,
+                        d_base_mask, d_base_set_of_row, d_ngram_of_row, d_prefix, d_prefix_len, prefix_ld, d_tgt_val);
 }
 
 int mocr_op_dec_token_masked(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
@@ -3610,6 +3750,10 @@ static int op_lm_head(mocr_engine* e, const void* dA, const void* dW, const floa
             throw ArgError{"mocr_op_gemm_topk: d_top_val / d_top_idx come together and with d_cand_sum", MOCR_ERR_ARG};
         if ((d_tok_mask == nullptr) != (d_set_of_row == nullptr) || (d_tok_mask && N % 128))
             throw ArgError{"mocr_op_gemm_argmax_masked: d_tok_mask and d_set_of_row come together, N a multiple of 128", MOCR_ERR_ARG};
+        const TokTarget& tt = lm.target;
+        if ((tt.prefix || tt.prefix_len || tt.step || tt.tgt_val) &&
+            (!tt.prefix || !tt.prefix_len || !tt.step || !tt.tgt_val || tt.prefix_ld < 1 || !d_tok_mask || !d_cand_sum))
+            throw ArgError{"mocr_op_gemm_argmax_target: the five target arrays come together, with d_tok_mask and d_cand_sum", MOCR_ERR_ARG};
         // (the name and the epilogue by the richest output given, as the steps choose theirs by the batch's mode)
         DecMode m;
         m.level = d_top_val ? 2 : d_cand_sum ? 1 : 0; m.mask = d_tok_mask != nullptr;
@@ -3627,6 +3771,16 @@ int mocr_op_gemm_argmax_masked(mocr_engine* e, const void* dA, const void* dW, c
                                const int32_t* d_rowmap) {
     return op_lm_head(e, dA, dW, d_bias, d_cand_val, M, N, K, tile,
                       LmHead{d_cand_idx, d_cand_sum, d_top_val, d_top_idx, TokMask{d_tok_mask, d_set_of_row, d_rowmap}});
+}
+
+int mocr_op_gemm_argmax_target(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                               int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N,
+                               int32_t K, int32_t tile, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
+                               const int32_t* d_rowmap, const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld,
+                               const int32_t* d_step, float* d_tgt_val) {
+    return op_lm_head(e, dA, dW, d_bias, d_cand_val, M, N, K, tile,
+                      LmHead{d_cand_idx, d_cand_sum, d_top_val, d_top_idx, TokMask{d_tok_mask, d_set_of_row, d_rowmap},
+                             TokTarget{d_prefix, d_prefix_len, prefix_ld, d_step, d_tgt_val}});
 }
 
 int mocr_op_gemm_topk(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,

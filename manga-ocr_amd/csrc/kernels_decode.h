@@ -143,6 +143,14 @@ struct DecState {
     const unsigned* base_mask;
     const int* base_set_of_row;
     const int* ngram_of_row;
+    // Forced prefixes (nullable, all or none; honoured by the SCORES && MASK kernels - the engine runs such a batch in that
+    // mode): prefix [B][prefix_ld] / prefix_len [B] by ROW like ids, the caller-given tokens behind the start token.  The
+    // step that fills ids[row][t + 1] with t < prefix_len[row] stores prefix[row][t] instead of its arg-max.  tgt_val [B] by
+    // SLOT: the LM head's value of that column (candidate path; GemmParams::tgt_val).
+    const int* prefix;
+    const int* prefix_len;
+    int prefix_ld;
+    const float* tgt_val;
 };
 
 // End of a decode step, one block per sequence:
@@ -176,6 +184,11 @@ struct DecState {
 //   row's history never holds EOS, so EOS is never banned and the row's max stays finite.
 //   Slab path: every read of the row's mask for THIS step (the nibbles above) precedes the argmax reduction's
 //   __syncthreads, and the rewrite follows the barrier behind thread 0's token, so no thread reads a word already rewritten.
+// Forced prefixes (SCORES && MASK, st.prefix set): a step t < prefix_len[row] runs like any other - the same max, S and
+//   alternatives - but thread 0 stores, finishes on and feeds back prefix[row][t].  Its score is (v - gmax) + (-log S), v the
+//   forced column's masked logit: tgt_val[slot] on the candidate path, published through LDS by the thread that holds the
+//   column on the slab path (before the argmax reduction's barrier).  A token outside the effective set has v = -inf and
+//   scores -inf; a forced token that IS the arg-max takes the free step's expression (a -0 score keeps its sign).
 template <typename T, int D, bool FIRST, bool SCORES = false, bool TOPK = false, bool MASK = false, bool NGRAM = false>
 __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict__ slabs, int nslab, long long slab_stride,
                                                         const float* __restrict__ vbias, int V,
@@ -201,6 +214,7 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
     __shared__ int s_idx[4];
     __shared__ float s_red[4];
     __shared__ int s_tok, s_pos;
+    __shared__ float s_fv;                              // forced prefixes, slab path: the forced column's masked logit
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int row = FIRST ? b : st.rowmap[b];       // slot b decodes row `row` of the batch
     if (FIRST) {
@@ -213,6 +227,10 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
         }
     } else {
         const int t = st.step[b];
+        int ftok = -1;                                   // the step's forced token (block-uniform), -1: a free step
+        if constexpr (SCORES && MASK) {
+            if (st.prefix && (unsigned)t < (unsigned)st.prefix_len[row]) ftok = st.prefix[(size_t)row * st.prefix_ld + t];
+        }
         float best = -INFINITY;
         int bi = 0x7fffffff;
         constexpr int NC = 6;                            // vocab = NC * 1024 columns (6144)
@@ -247,6 +265,9 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                 abits |= nib << (4 * j);
                 a[j].x = (nib & 1) ? a[j].x : -INFINITY; a[j].y = (nib & 2) ? a[j].y : -INFINITY;
                 a[j].z = (nib & 4) ? a[j].z : -INFINITY; a[j].w = (nib & 8) ? a[j].w : -INFINITY;
+                if constexpr (SCORES) {
+                    if ((ftok & ~3) == c) s_fv = (ftok & 2) ? ((ftok & 1) ? a[j].w : a[j].z) : ((ftok & 1) ? a[j].y : a[j].x);
+                }
             }
             if (a[j].x > best) { best = a[j].x; bi = c; }
             if (a[j].y > best) { best = a[j].y; bi = c + 1; }
@@ -323,11 +344,17 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
             int fin = st.finished[row];
             int tok = fin ? st.pad_id : bi;
             if (st.forced) tok = (t + 1 < st.forced_T) ? st.forced[(size_t)b * st.forced_T + t + 1] : st.pad_id;
+            const bool force = ftok >= 0 && !fin;
+            if (force) tok = ftok;
             if (t + 1 < st.ids_ld) st.ids[(size_t)row * st.ids_ld + t + 1] = tok;
             if constexpr (SCORES) {
                 const float S = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
                 const float score = -logf(S);
-                if (t + 1 < st.ids_ld) st.scores[(size_t)row * st.ids_ld + t + 1] = fin ? 0.f : score;
+                float tscore = score;                    // the stored token's: a forced one that is not the step's pick scores its own logit
+                if constexpr (MASK) {
+                    if (force && ftok != bi) tscore = ((cand_val ? st.tgt_val[b] : s_fv) - best) + score;
+                }
+                if (t + 1 < st.ids_ld) st.scores[(size_t)row * st.ids_ld + t + 1] = fin ? 0.f : tscore;
                 if constexpr (TOPK) {
                     if (t + 1 < st.ids_ld) {
                         const size_t o = ((size_t)row * st.ids_ld + t + 1) * 4;

@@ -77,6 +77,13 @@ struct GemmParams {
     const unsigned* tok_mask;   // [sets][N / 32] bit n of a set's row = column n is allowed; set 0 is all ones
     const int* set_of_row;      // [rows of the batch] set of every row, indexed by ROW like ids
     const int* rowmap;          // [M] slot -> row (null: identity)
+    // Forced prefixes (EPI_ARGMAX_LSE_M / EPI_TOPK_M; tgt_val null = none: the launcher picks gemm_kernel's TGT by it).  Slot m decodes row
+    // rowmap[m] at step step[m]; a step below the row's prefix_len has the target column prefix[row * prefix_ld + step]
+    const int* prefix;          // [rows of the batch][prefix_ld] the caller-given tokens (without the start token), by ROW
+    const int* prefix_len;      // [rows of the batch] by ROW
+    int prefix_ld;
+    const int* step;            // [M] by slot
+    float* tgt_val;             // [M] by slot: acc + bias of the target column, -inf when the row's set leaves it out
 };
 
 // Linear tile id -> (tm, tn).  Tiles are ordered column-group by column-group: inside a group of
@@ -168,7 +175,12 @@ __device__ __forceinline__ void gemm_epilogue(const float* sC, const GemmParams&
 // comparison, not even the tie of two -inf against the initial entry - and contributes 0, by select, to the exp sum: a tile
 // with no allowed column stores best = -inf, the sentinel and cand_sum = 0 (never exp(-inf - -inf)), which the token
 // kernel's merge cand_sum * exp(cand_val - gmax) turns into 0 * 0.  Rows m >= M read set 0.
-template <int BM, int BN, int NT, bool SWZ, bool LSE = false, bool TOPK = false, bool MASK = false>
+// Forced prefixes (MASK with LSE and TGT - a template parameter, so that batches without a prefix run the code they always
+// ran, see profiles/prefix_cost.jsonl; GemmParams::tgt_val is set): a row whose step is below its prefix length has a target
+// column.  The one thread of the one tile whose column group holds it stores tgt_val[m] = allowed ? sC + bias : -inf - the
+// same fp32 add as in the first walk, so the value equals the tile's `best` bit for bit when the target wins.  One writer
+// per row, a plain vector store; rows without a target leave tgt_val[m] alone.
+template <int BM, int BN, int NT, bool SWZ, bool LSE = false, bool TOPK = false, bool MASK = false, bool TGT = false>
 __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const GemmParams& p, int m0, int n0, int tid) {
     constexpr int TPRW = NT / BM, CPP = BN / TPRW;
     static_assert(TPRW == 2 || TPRW == 4, "two or four threads per row");
@@ -264,6 +276,19 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const Gemm
 #pragma unroll
         for (int o = TPRW / 2; o > 0; o >>= 1) esum += __shfl_xor(esum, o, 64);
     }
+    if constexpr (MASK && LSE && TGT) {
+        if (m < p.M) {
+            const int brow = p.rowmap ? p.rowmap[m] : m;
+            const int t = p.step[m];
+            if ((unsigned)t < (unsigned)p.prefix_len[brow]) {
+                const int tgt = p.prefix[(size_t)brow * p.prefix_ld + t];
+                if (tgt >= g0 && tgt < g0 + CPP) {          // (logical column tgt - n0 sits at physical column (tgt - n0) ^ sw)
+                    const float v = sC[row * BN + ((tgt - n0) ^ sw)] + p.bias[tgt];
+                    p.tgt_val[m] = ((mbits >> (tgt - g0)) & 1ull) ? v : -INFINITY;
+                }
+            }
+        }
+    }
     if (part == 0 && m < p.M) {
         const size_t c = (size_t)m * p.ntn + n0 / BN;
         reinterpret_cast<float*>(p.out)[c] = best;
@@ -298,7 +323,8 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
 // NST = depth of the LDS ring: K-tile t+NST-1 is issued while K-tile t is multiplied.  NST = 2 is
 // the plain double buffer; the latency-bound skinny GEMMs of the decode step use NST = 4 (64x64
 // tile: 4 x 16 KiB) so a DMA has three K-tiles of time to land.
-template <typename T, int BM, int BN, int EPI, int NST = 2>
+// TGT (EPI_ARGMAX_LSE_M / EPI_TOPK_M only): the epilogue also stores the forced prefixes' target column (GemmParams::tgt_val).
+template <typename T, int BM, int BN, int EPI, int NST = 2, bool TGT = false>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
     constexpr int TM = BM / 64, TN = BN / 64;          // 32x32 MFMA tiles per wave
     constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE = A_BYTES + B_BYTES;
@@ -491,9 +517,9 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
     } else if constexpr (EPI == EPI_ARGMAX_M) {
         gemm_epilogue_argmax<BM, BN, 256, SWZ, false, false, true>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_ARGMAX_LSE_M) {
-        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, false, true>(sC, p, m0, n0, tid);
+        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, false, true, TGT>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_TOPK_M) {
-        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, true, true>(sC, p, m0, n0, tid);
+        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, true, true, TGT>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_BIAS) {
         GemmParams q = p;
         q.out = reinterpret_cast<T*>(p.out) + (size_t)blockIdx.y * p.o_yoff;

@@ -108,6 +108,11 @@ SYMBOLS = {
     "mocr_recognize_regions_positions": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.POINTER(MocrRegion), C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mocr_recognize_device_positions": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mocr_recognize_gray_host_positions": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mocr_recognize_images_prefix": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32]),
+    "mocr_recognize_regions_prefix": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.POINTER(MocrRegion), C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                _P, _P, C.c_int32]),
+    "mocr_recognize_device_prefix": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32]),
+    "mocr_recognize_gray_host_prefix": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32]),
     "mocr_graph_count": (C.c_int, [_P]),
     "mocr_compaction_count": (C.c_int64, [_P]),
     "mocr_decode_slot_steps": (C.c_int64, [_P]),
@@ -141,9 +146,12 @@ SYMBOLS = {
     "mocr_op_gemm_topk": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mocr_op_dec_token_masked": (C.c_int, [_P, C.POINTER(MocrTokenArgs), _P, _P, _P, _P, _P, _P, _P, _P]),
     "mocr_op_dec_token_ngram": (C.c_int, [_P, C.POINTER(MocrTokenArgs), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mocr_op_dec_token_prefix": (C.c_int, [_P, C.POINTER(MocrTokenArgs), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P]),
     "mocr_op_ngram_init": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32]),
     "mocr_op_attn_positions": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     "mocr_op_gemm_argmax_masked": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "mocr_op_gemm_argmax_target": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                             _P, _P, C.c_int32, _P, _P]),
     "mocr_op_smallm_gemm": (C.c_int, [_P, C.POINTER(MocrSmallmArgs)]),
     "mocr_op_latent_block": (C.c_int, [_P, C.POINTER(MocrLatentArgs)]),
     "mocr_profile_enable": (C.c_int, [_P, C.c_int32]),

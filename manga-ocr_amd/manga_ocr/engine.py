@@ -175,6 +175,23 @@ class Engine:
             raise ValueError(f"no_repeat_ngram: sizes must be in 0 .. max_len ({self.spec.max_len}), 0 = off")
         return np.ascontiguousarray(a, dtype=np.int32)
 
+    # ------------------------------------------------------------------ forced prefixes
+    @staticmethod
+    def _prefixes(prefixes, n: int):
+        """``prefixes=``: one int sequence (or None) per crop -> (tokens int32 [n, ld], lengths int32 [n], ld), one block"""
+        rows = list(prefixes)
+        if len(rows) != n:
+            raise ValueError(f"prefixes: {n} crops but {len(rows)} prefixes")
+        rows = [np.zeros(0, dtype=np.int64) if r is None else np.asarray(list(r)) for r in rows]
+        for r in rows:
+            if r.ndim != 1 or (r.size and not np.issubdtype(r.dtype, np.integer)):
+                raise TypeError("prefixes: every prefix is a flat sequence of token ids")
+        ld = max([int(r.size) for r in rows] + [1])
+        block = np.zeros((n, ld), dtype=np.int32)
+        for i, r in enumerate(rows):
+            block[i, :r.size] = r
+        return block, np.array([r.size for r in rows], dtype=np.int32), ld
+
     def _blocks(self, n: int, scores: bool, alternatives: bool, positions: bool):
         """The output blocks of a recognise call: (ids, lens, logp, alt_ids, alt_logp, pos), None where not asked - what
         the engine is then passed as null.  The alternatives come as the engine leaves unwritten positions: -1 / 0."""
@@ -199,7 +216,7 @@ class Engine:
         return sets, ngram
 
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False,
-                         token_sets=None, no_repeat_ngram=None, positions: bool = False):
+                         token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None):
         """Crops of any sizes (list of uint8 [h,w] / [h,w,3] arrays; `bgr`: 3-channel crops are in OpenCV order;
         `rotate`: per crop 0 / 1 (90 degrees clockwise) / 2 (counter-clockwise), applied on the device): luminance
         conversion and the Pillow-exact BILINEAR resize to 224x224 run on the device.
@@ -213,18 +230,25 @@ class Engine:
         crop, 0 = off (include/mocr.h, "no-repeat n-grams"); combines with ``token_sets``.
         ``positions=True``: the return value gets one more, LAST element, pos float32 [n,max_len,5] - per token the centre
         (cx, cy), spread (sx, sy) and patch mass of the last decoder layer's cross-attention, in fractions of the 224 x 224
-        plane the encoder sees (include/mocr.h, "token positions"); same ids, scores and alternatives."""
+        plane the encoder sees (include/mocr.h, "token positions"); same ids, scores and alternatives.
+        ``prefixes``: per crop a sequence of token ids (or None) the row starts with, behind the start token; the engine
+        scores them and continues greedily (include/mocr.h, "forced prefixes")."""
         n = len(images)
         blocks = self._blocks(n, scores, alternatives, positions)
         if n > 0:
             descs, keep = self._image_descs(images, bgr, rotate)
             sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
-            self._check(self.lib.mocr_recognize_images_positions(self._h, descs, n, *map(_ptr, blocks[:5]), _ptr(sets), _ptr(ngram),
-                                                                 _ptr(blocks[5])))
+            if prefixes is not None:
+                pre, plen, ld = self._prefixes(prefixes, n)
+                self._check(self.lib.mocr_recognize_images_prefix(self._h, descs, n, *map(_ptr, blocks[:5]), _ptr(sets), _ptr(ngram),
+                                                                  _ptr(blocks[5]), _ptr(pre), _ptr(plen), ld))
+            else:
+                self._check(self.lib.mocr_recognize_images_positions(self._h, descs, n, *map(_ptr, blocks[:5]), _ptr(sets), _ptr(ngram),
+                                                                     _ptr(blocks[5])))
         return self._result(blocks, scores, alternatives, positions)
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False,
-                          token_sets=None, no_repeat_ngram=None, positions: bool = False):
+                          token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None):
         """pages: list of uint8 [H,W,3] (or [H,W]) arrays; regions: iterable of (page_index, x, y, w, h) bounding
         rectangles.  Each page is uploaded once; the 8 %-padded, page-clipped crop of every region
         (``src/ui/main_window.py:9530-9540``) is cut on the device.  Returns (ids [n,max_len], lengths [n]);
@@ -233,7 +257,8 @@ class Engine:
         all -1 / 0.  ``token_sets``: a set handle for every region, or one per region (see recognize_images);
         ``no_repeat_ngram``: a no-repeat n-gram size for every region, or one per region (see recognize_images).
         ``positions=True``: one more, last element pos float32 [n,max_len,5] (see recognize_images), in fractions of the
-        region's padded, clipped rectangle (manga_ocr.regions.padded_rect); a sliver's rows all 0."""
+        region's padded, clipped rectangle (manga_ocr.regions.padded_rect); a sliver's rows all 0.
+        ``prefixes``: per region a forced prefix or None (see recognize_images); a sliver ignores its prefix."""
         regs = list(regions)
         n = len(regs)
         blocks = self._blocks(n, scores, alternatives, positions)
@@ -243,8 +268,13 @@ class Engine:
             for i, (pg, x, y, w, h) in enumerate(regs):
                 arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
             sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
-            self._check(self.lib.mocr_recognize_regions_positions(self._h, descs, len(keep), arr, n, *map(_ptr, blocks[:5]), _ptr(sets),
-                                                                  _ptr(ngram), _ptr(blocks[5])))
+            if prefixes is not None:
+                pre, plen, ld = self._prefixes(prefixes, n)
+                self._check(self.lib.mocr_recognize_regions_prefix(self._h, descs, len(keep), arr, n, *map(_ptr, blocks[:5]), _ptr(sets),
+                                                                   _ptr(ngram), _ptr(blocks[5]), _ptr(pre), _ptr(plen), ld))
+            else:
+                self._check(self.lib.mocr_recognize_regions_positions(self._h, descs, len(keep), arr, n, *map(_ptr, blocks[:5]), _ptr(sets),
+                                                                      _ptr(ngram), _ptr(blocks[5])))
         return self._result(blocks, scores, alternatives, positions)
 
     def graph_count(self) -> int:
@@ -273,13 +303,20 @@ class Engine:
         return out
 
     def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None, d_out_alt_ids=None, d_out_alt_logp=None, *,
-                         token_sets=None, no_repeat_ngram=None, d_out_pos=None) -> None:
+                         token_sets=None, no_repeat_ngram=None, d_out_pos=None, prefixes=None) -> None:
         """Asynchronous; all are device buffers (torch CUDA tensors or raw addresses).  ``d_out_logp`` (float32
         [n,max_len]): also the token log-probabilities.  ``d_out_alt_ids`` (int32) with ``d_out_alt_logp`` (float32), both
         [n,max_len,4]: also the token alternatives.  ``token_sets``: a set handle for every crop, or one per crop (host values).
         ``no_repeat_ngram``: a no-repeat n-gram size for every crop, or one per crop (host values).
-        ``d_out_pos`` (float32 [n,max_len,5]): also the token positions."""
+        ``d_out_pos`` (float32 [n,max_len,5]): also the token positions.  ``prefixes``: per crop a forced prefix or None (host
+        values, copied by the call)."""
         sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
+        if prefixes is not None:
+            pre, plen, ld = self._prefixes(prefixes, n)
+            self._check(self.lib.mocr_recognize_device_prefix(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len), _ptr(d_out_logp),
+                                                              _ptr(d_out_alt_ids), _ptr(d_out_alt_logp), _ptr(sets), _ptr(ngram),
+                                                              _ptr(d_out_pos), _ptr(pre), _ptr(plen), ld))
+            return
         self._check(self.lib.mocr_recognize_device_positions(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len), _ptr(d_out_logp),
                                                              _ptr(d_out_alt_ids), _ptr(d_out_alt_logp), _ptr(sets), _ptr(ngram),
                                                              _ptr(d_out_pos)))
@@ -288,11 +325,16 @@ class Engine:
         self._check(self.lib.mocr_set_generate_max_length(self._h, int(max_len)))
 
     def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False, alternatives: bool = False,
-                       token_sets=None, no_repeat_ngram=None, positions: bool = False):
+                       token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None):
         a = np.ascontiguousarray(gray, dtype=np.uint8)
         n = a.shape[0]
         sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
         blocks = self._blocks(n, scores, alternatives, positions)
+        if prefixes is not None:
+            pre, plen, ld = self._prefixes(prefixes, n)
+            self._check(self.lib.mocr_recognize_gray_host_prefix(self._h, _ptr(a), n, max_len or self.spec.max_len, *map(_ptr, blocks[:5]),
+                                                                 _ptr(sets), _ptr(ngram), _ptr(blocks[5]), _ptr(pre), _ptr(plen), ld))
+            return self._result(blocks, scores, alternatives, positions)
         self._check(self.lib.mocr_recognize_gray_host_positions(self._h, _ptr(a), n, max_len or self.spec.max_len, *map(_ptr, blocks[:5]),
                                                                 _ptr(sets), _ptr(ngram), _ptr(blocks[5])))
         return self._result(blocks, scores, alternatives, positions)
@@ -393,6 +435,17 @@ class Engine:
                                                      _ptr(d_set_of_row), _ptr(d_row_mask), _ptr(d_base_mask), _ptr(d_base_set_of_row),
                                                      _ptr(d_ngram_of_row)))
 
+    def op_dec_token_prefix(self, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row,
+                            d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, d_prefix, d_prefix_len, prefix_ld, d_tgt_val,
+                            **kw) -> None:
+        """The token step with forced prefixes: op_dec_token_ngram plus the rows' prefixes and lengths and, on the candidate
+        path, the LM head's target values (op_gemm_argmax_target)."""
+        self._check(self.lib.mocr_op_dec_token_prefix(self._h, self._args(_capi.MocrTokenArgs, kw), _ptr(d_cand_sum), _ptr(d_scores),
+                                                      _ptr(d_top_val), _ptr(d_top_idx), _ptr(d_alt_ids), _ptr(d_alt_logp), _ptr(d_tok_mask),
+                                                      _ptr(d_set_of_row), _ptr(d_row_mask), _ptr(d_base_mask), _ptr(d_base_set_of_row),
+                                                      _ptr(d_ngram_of_row), _ptr(d_prefix), _ptr(d_prefix_len), int(prefix_ld),
+                                                      _ptr(d_tgt_val)))
+
     def op_attn_positions(self, d_q, d_k, d_len, rows: int, T: int, d_out_pos, d_out_map=None) -> None:
         """The positions kernel on device buffers (include/mocr.h mocr_op_attn_positions)."""
         self._check(self.lib.mocr_op_attn_positions(self._h, _ptr(d_q), _ptr(d_k), _ptr(d_len), int(rows), int(T), _ptr(d_out_pos),
@@ -408,6 +461,14 @@ class Engine:
         self._check(self.lib.mocr_op_gemm_argmax_masked(self._h, _ptr(dA), _ptr(dW), _ptr(d_bias), _ptr(d_cand_val), _ptr(d_cand_idx),
                                                         _ptr(d_cand_sum), _ptr(d_top_val), _ptr(d_top_idx), M, N, K, tile,
                                                         _ptr(d_tok_mask), _ptr(d_set_of_row), _ptr(d_rowmap)))
+
+    def op_gemm_argmax_target(self, dA, dW, d_bias, d_cand_val, d_cand_idx, d_cand_sum, d_top_val, d_top_idx, M, N, K, tile,
+                              d_tok_mask, d_set_of_row, d_rowmap, d_prefix, d_prefix_len, prefix_ld, d_step, d_tgt_val) -> None:
+        """The masked, scored LM head plus the target column of every row with a forced step (include/mocr.h)."""
+        self._check(self.lib.mocr_op_gemm_argmax_target(self._h, _ptr(dA), _ptr(dW), _ptr(d_bias), _ptr(d_cand_val), _ptr(d_cand_idx),
+                                                        _ptr(d_cand_sum), _ptr(d_top_val), _ptr(d_top_idx), M, N, K, tile,
+                                                        _ptr(d_tok_mask), _ptr(d_set_of_row), _ptr(d_rowmap), _ptr(d_prefix),
+                                                        _ptr(d_prefix_len), int(prefix_ld), _ptr(d_step), _ptr(d_tgt_val)))
 
     def op_gemm_topk(self, dA, dW, d_bias, d_cand_val, d_cand_idx, d_cand_sum, d_top_val, d_top_idx, M, N, K, tile) -> None:
         self._check(self.lib.mocr_op_gemm_topk(self._h, _ptr(dA), _ptr(dW), _ptr(d_bias), _ptr(d_cand_val), _ptr(d_cand_idx),

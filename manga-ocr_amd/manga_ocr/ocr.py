@@ -17,7 +17,7 @@ import os
 import threading
 import time
 from concurrent.futures import Future
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from pathlib import Path
 from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
@@ -128,6 +128,43 @@ def _ngram_sizes(no_repeat_ngram, default, n: int) -> Optional[List[int]]:
     return gs
 
 
+def _prefix_rows(prefix, n: int, vocab) -> Optional[List[Optional[List[int]]]]:
+    """``prefix=`` of a call -> None (no crop has one) or, per crop, its token ids / None.  A ``str`` (encoded with
+    ``Vocab.encode_chars``) or a flat int sequence applies to all ``n`` crops; a sequence of ``str``, int sequences or ``None``
+    holds one entry per crop."""
+    scalars = (bytes, bool, np.bool_, int, np.integer, float)
+
+    def one(p):
+        if p is None:
+            return None
+        if isinstance(p, str):
+            return vocab.encode_chars(p) or None
+        if isinstance(p, scalars) or not hasattr(p, "__iter__"):
+            raise TypeError(f"prefix: a str, a sequence of token ids or None per crop, instead got {p!r}")
+        ids = list(p)
+        if any(isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)) for t in ids):
+            raise TypeError(f"prefix: token ids must be ints, instead got {p!r}")
+        return [int(t) for t in ids] or None
+
+    if prefix is None:
+        return None
+    if isinstance(prefix, str):
+        rows = [one(prefix)] * n
+    elif isinstance(prefix, scalars) or not hasattr(prefix, "__iter__"):
+        raise TypeError(f"prefix: a str, a sequence of token ids, or one of those (or None) per crop, instead got {prefix!r}")
+    else:
+        items = list(prefix)
+        if not items:                       # an empty flat sequence: no prefix
+            return None
+        if all(isinstance(t, (int, np.integer)) and not isinstance(t, (bool, np.bool_)) for t in items):
+            rows = [one(items)] * n         # a flat int sequence: every crop
+        else:
+            if len(items) != n:
+                raise ValueError(f"prefix: {n} crops but {len(items)} prefixes")
+            rows = [one(p) for p in items]
+    return rows if any(r is not None for r in rows) else None
+
+
 @dataclass(frozen=True)
 class Recognition:
     """One recognised crop with the recogniser's own confidence (the ``*_scored`` methods of :class:`MangaOcr`).
@@ -156,6 +193,7 @@ class Recognition:
     alt_logprobs: Optional[np.ndarray] = None
     positions: Optional[np.ndarray] = None
     rect: Optional[Tuple[int, int, int, int]] = None     # regions: (x, y, w, h) of the padded, clipped crop in page pixels
+    n_forced: int = 0       # ``prefix=``: how many of ids[1:] the caller gave (their logprobs score the caller's tokens)
     _vocab: object = field(default=None, repr=False, compare=False)      # what candidates() names the tokens with
 
     @classmethod
@@ -210,9 +248,30 @@ class Recognition:
         b[live] += np.array([x, y, x, y], dtype=np.float64)
         return b
 
+    @property
+    def logprob(self) -> float:
+        """The natural-log probability of the whole row, ``sum(logprobs)`` in float64: for a ``score_text`` result
+        ``log p(text | crop)``."""
+        return float(self.logprobs.astype(np.float64).sum())
+
+    def branch(self, k: int, j: int) -> List[int]:
+        """The prefix that acts on an alternative: the row as decoded up to generated position ``k``, then candidate ``j`` of
+        that position - ``ids[1:k+1] + [alt_ids[k, j]]``, ready to pass as ``prefix=`` to decode the rest under the
+        correction.  Needs a result of one of the ``*_alternatives`` methods."""
+        if self.alt_ids is None:
+            raise ValueError("this Recognition carries no alternatives: use MangaOcr.recognize_alternatives and friends")
+        if not 0 <= k < len(self.alt_ids) or not 0 <= j < self.alt_ids.shape[1]:
+            raise IndexError(f"branch: position {k} / candidate {j} outside the {len(self.alt_ids)} x {self.alt_ids.shape[1]} alternatives")
+        tok = int(self.alt_ids[k, j])
+        if tok < 0:
+            raise ValueError(f"branch: position {k} has no candidate {j} (the crop's token set left fewer)")
+        return [int(t) for t in self.ids[1:k + 1]] + [tok]
+
     def candidates(self, k: int) -> List[Tuple[str, float]]:
         """The four most probable tokens of generated position ``k`` (the one that emitted ``ids[k + 1]``), most probable
-        first: (token as the vocabulary spells it, probability).  Entry 0 is the emitted token.  Fewer than four when the crop
+        first: (token as the vocabulary spells it, probability).  Entry 0 is the emitted token - except at a forced position (``k < n_forced``), where the entries
+        are the step's own four best: entry 0 is what the model would have chosen, not necessarily the forced ``ids[k + 1]``.
+        Fewer than four when the crop
         was decoded under a token set of fewer than four tokens (``allowed=``): the missing entries, id -1, are skipped.
         Needs a result of one of the ``*_alternatives`` methods."""
         if self.alt_ids is None or self.alt_logprobs is None:
@@ -235,6 +294,7 @@ class _Request(NamedTuple):
     token_set: int          # 0: unconstrained
     ngram: int              # no-repeat n-gram size, 0: off
     positions: bool
+    prefix: Optional[tuple] = None      # forced prefix (token ids), None: none
 
 
 class _Batcher:
@@ -247,7 +307,8 @@ class _Batcher:
     to the engine, so batches nobody constrains make exactly the calls they always made.  The same for a no-repeat n-gram size
     (``no_repeat_ngram=``): only a batch with a request of size > 0 passes ``no_repeat_ngram=``, one size per crop.  And for
     token positions (``positions=True``): only a batch with such a request passes ``positions=True``, and such a caller gets
-    its positions as one more, last element of its result."""
+    its positions as one more, last element of its result.  And for forced prefixes (``prefix=``): only a batch with such a
+    request passes ``prefixes=``, one per crop, None for the others."""
 
     def __init__(self, engine: Engine, max_batch: int, timeout_ms: float):
         self.engine, self.max_batch, self.timeout = engine, max_batch, timeout_ms / 1000.0
@@ -258,12 +319,13 @@ class _Batcher:
         self._thread.start()
 
     def submit(self, gray: np.ndarray, scored: bool = False, alternatives: bool = False, token_set: int = 0,
-               no_repeat_ngram: int = 0, positions: bool = False) -> Future:
+               no_repeat_ngram: int = 0, positions: bool = False, prefix=None) -> Future:
         f: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
-            self._q.append(_Request(gray, f, 2 if alternatives else 1 if scored else 0, int(token_set), int(no_repeat_ngram), bool(positions)))
+            self._q.append(_Request(gray, f, 2 if alternatives else 1 if scored else 0, int(token_set), int(no_repeat_ngram), bool(positions),
+                                    tuple(prefix) if prefix else None))
             self._cv.notify()
         return f
 
@@ -292,6 +354,8 @@ class _Batcher:
                     kw["no_repeat_ngram"] = [r.ngram for r in batch]
                 if any(r.positions for r in batch):
                     kw["positions"] = True
+                if any(r.prefix for r in batch):
+                    kw["prefixes"] = [list(r.prefix) if r.prefix else None for r in batch]
                 res = self.engine.recognize_images([r.gray for r in batch], **kw)     # (ids, lens[, logp[, alt_ids, alt_logp]][, pos])
                 for i, r in enumerate(batch):
                     # what this caller asked for, cut to its length: bare ids, or a tuple with its logp / alternatives / positions
@@ -444,7 +508,7 @@ class MangaOcr:
         return dict(token_sets=hs)
 
     # ------------------------------------------------------------------ no-repeat n-grams
-    def _decode_kw(self, allowed, no_repeat_ngram, n: int) -> dict:
+    def _decode_kw(self, allowed, no_repeat_ngram, n: int, prefix=None) -> dict:
         """the engine keywords of ``allowed=`` and ``no_repeat_ngram=`` ({} when neither is in use: the call the method always
         made); a call's ``no_repeat_ngram`` overrides the constructor's ``no_repeat_ngram_size`` (0 = off for this call)"""
         kw = self._allowed(allowed, n)
@@ -454,34 +518,44 @@ class MangaOcr:
             if no:
                 raise NotImplementedError(no)
             kw["no_repeat_ngram"] = gs
+        rows = _prefix_rows(prefix, n, self.vocab) if prefix is not None else None
+        if rows is not None:
+            no = getattr(self.engine, "NO_PREFIX", None)      # MultiGpuEngine
+            if no:
+                raise NotImplementedError(no)
+            kw["prefixes"] = rows
         return kw
 
-    def _single(self, allowed, no_repeat_ngram) -> dict:
-        """the batcher keywords of one crop's ``allowed=`` / ``no_repeat_ngram=``"""
-        kw = self._decode_kw(allowed, no_repeat_ngram, 1)
+    def _single(self, allowed, no_repeat_ngram, prefix=None) -> dict:
+        """the batcher keywords of one crop's ``allowed=`` / ``no_repeat_ngram=`` / ``prefix=``"""
+        kw = self._decode_kw(allowed, no_repeat_ngram, 1, prefix)
         out = {}
         if "token_sets" in kw:
             out["token_set"] = kw["token_sets"][0]
         if "no_repeat_ngram" in kw:
             out["no_repeat_ngram"] = kw["no_repeat_ngram"][0]
+        if "prefixes" in kw:
+            out["prefix"] = kw["prefixes"][0]
         return out
 
     # ------------------------------------------------------------------ batch surface (callers that hold many crops)
     def recognize_ids(self, crops: Sequence[np.ndarray], bgr: bool = False, rotate: Optional[Sequence[int]] = None, *,
-                      allowed=None, no_repeat_ngram=None) -> List[np.ndarray]:
+                      allowed=None, no_repeat_ngram=None, prefix=None) -> List[np.ndarray]:
         """uint8 crops of any sizes ([h,w] luminance or [h,w,3] RGB; BGR with ``bgr=True``; ``rotate``: per crop 0 / 1 (90
         degrees clockwise) / 2 (counter-clockwise), done by the device) -> token ids (without padding).  ``allowed``: a
         token set of :meth:`token_set` for all crops, or one per crop.  ``no_repeat_ngram``: the no-repeat n-gram size of this
-        call, an int for all crops or one per crop, 0 = off (None: the constructor's ``no_repeat_ngram_size``); every
-        ``recognize*`` method takes both."""
+        call, an int for all crops or one per crop, 0 = off (None: the constructor's ``no_repeat_ngram_size``).  ``prefix``:
+        tokens the rows start with, behind the start token - a ``str`` (one token per character, ``Vocab.encode_chars``) or a
+        flat sequence of token ids for all crops, or a sequence of those (or None) per crop; the engine scores them and decodes
+        on from there (include/mocr.h, "forced prefixes").  Every ``recognize*`` method takes all three."""
         crops = list(crops)
-        ids, lens = self.engine.recognize_images(crops, bgr, rotate, **self._decode_kw(allowed, no_repeat_ngram, len(crops)))
+        ids, lens = self.engine.recognize_images(crops, bgr, rotate, **self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix))
         return [ids[i, :lens[i]].copy() for i in range(len(lens))]
 
-    def recognize(self, img_or_path, *, allowed=None, no_repeat_ngram=None) -> str:
+    def recognize(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> str:
         """``__call__`` (which keeps the reference's signature) with ``allowed=``: one crop decoded under a token set, and
         ``no_repeat_ngram=``: this call's no-repeat n-gram size (None: the constructor's ``no_repeat_ngram_size``)."""
-        ids = self._batcher.submit(to_pixels(self._open(img_or_path)), **self._single(allowed, no_repeat_ngram)).result()
+        ids = self._batcher.submit(to_pixels(self._open(img_or_path)), **self._single(allowed, no_repeat_ngram, prefix)).result()
         return ids_to_text(self.vocab, ids)
 
     @staticmethod
@@ -493,17 +567,17 @@ class MangaOcr:
             return img_or_path
         raise ValueError(f"img_or_path must be a path or PIL.Image, instead got: {img_or_path}")
 
-    def recognize_batch(self, images: Sequence, *, allowed=None, no_repeat_ngram=None) -> List[str]:
+    def recognize_batch(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
         """All crops of a page (or chapter) at once - what ``_collect_manga_detections``
         (``src/ui/main_window.py:9462-9476``) does one region at a time."""
-        return [ids_to_text(self.vocab, r) for r in self.recognize_ids([to_pixels(im) for im in images], allowed=allowed, no_repeat_ngram=no_repeat_ngram)]
+        return [ids_to_text(self.vocab, r) for r in self.recognize_ids([to_pixels(im) for im in images], allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix)]
 
-    def recognize_batch_arrays(self, crops: Sequence[np.ndarray], *, allowed=None, no_repeat_ngram=None) -> List[str]:
+    def recognize_batch_arrays(self, crops: Sequence[np.ndarray], *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
         """uint8 arrays ([h,w] luminance or [h,w,3] RGB, any sizes) -> strings: what a caller that already holds numpy
         crops (the crop-job queue) uses instead of wrapping each one in a PIL image."""
-        return [ids_to_text(self.vocab, r) for r in self.recognize_ids(list(crops), allowed=allowed, no_repeat_ngram=no_repeat_ngram)]
+        return [ids_to_text(self.vocab, r) for r in self.recognize_ids(list(crops), allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix)]
 
-    def recognize_bgr(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *, allowed=None, no_repeat_ngram=None) -> List[str]:
+    def recognize_bgr(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
         """BGR crops exactly as the crop tools and the worker hold them (``cropped_cv_img``, ``src/core/workers.py:300``):
         the BGR -> RGB swap of ``src/ui/main_window.py:9800`` is folded into the device's luminance conversion, and with
         ``orientations`` (the jobs' "Auto-Detect" / "Vertical" / "Horizontal" settings) the orientation-only rotation of
@@ -515,14 +589,14 @@ class MangaOcr:
             if len(orientations) != len(crops):        # zip() would truncate silently: a short list must not cost a decode
                 raise ValueError(f"recognize_bgr: {len(crops)} crops but {len(orientations)} orientations")
             rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
-        return [ids_to_text(self.vocab, r) for r in self.recognize_ids(crops, bgr=True, rotate=rot, allowed=allowed, no_repeat_ngram=no_repeat_ngram)]
+        return [ids_to_text(self.vocab, r) for r in self.recognize_ids(crops, bgr=True, rotate=rot, allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix)]
 
-    def recognize_regions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None) -> List[str]:
+    def recognize_regions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
         """``regions``: (page_index, x, y, w, h) bounding rectangles on BGR pages; every page is uploaded once and
         the padded crops (``src/ui/main_window.py:9530-9540``) are cut on the device.  One string per region
         ('' for a region reduced to a sliver, like the reference)."""
         regions = list(regions)
-        ids, lens = self.engine.recognize_regions(list(pages_bgr), regions, True, **self._decode_kw(allowed, no_repeat_ngram, len(regions)))
+        ids, lens = self.engine.recognize_regions(list(pages_bgr), regions, True, **self._decode_kw(allowed, no_repeat_ngram, len(regions), prefix))
         return [ids_to_text(self.vocab, ids[i, :lens[i]]) if lens[i] > 0 else "" for i in range(len(lens))]
 
     # ------------------------------------------------------------------ scored surface: the same recognitions + confidence
@@ -531,27 +605,35 @@ class MangaOcr:
         if no:
             raise NotImplementedError(no)
 
+    @staticmethod
+    def _mark_forced(recs: List[Recognition], prefixes) -> List[Recognition]:
+        """``Recognition.n_forced`` of the rows that were given a prefix (a row that finished inside it counts what it took)"""
+        if prefixes is None:
+            return recs
+        return [replace(r, n_forced=min(len(p), max(len(r.ids) - 1, 0))) if p else r for r, p in zip(recs, prefixes)]
+
     def _recognitions(self, ids, lens, logp) -> List[Recognition]:
         return [Recognition.from_row(self.vocab, ids[i], logp[i], lens[i]) for i in range(len(lens))]
 
-    def recognize_scored(self, img_or_path, *, allowed=None, no_repeat_ngram=None) -> Recognition:
+    def recognize_scored(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> Recognition:
         """``__call__`` with the recogniser's confidence: same text, plus the token log-probabilities computed on the
         device (include/mocr.h, "token scores").  Goes through the same batcher as ``__call__``; scored and unscored
         callers may share a batch."""
         self._check_scored()
         img = self._open(img_or_path)
-        extra = self._single(allowed, no_repeat_ngram)
+        extra = self._single(allowed, no_repeat_ngram, prefix)
         ids, logp = self._batcher.submit(to_pixels(img), scored=True, **extra).result()
-        return Recognition.from_row(self.vocab, ids, logp, len(ids))
+        return self._mark_forced([Recognition.from_row(self.vocab, ids, logp, len(ids))], [extra.get("prefix")])[0]
 
-    def recognize_batch_scored(self, images: Sequence, *, allowed=None, no_repeat_ngram=None) -> List[Recognition]:
+    def recognize_batch_scored(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
         """``recognize_batch`` with confidences."""
         self._check_scored()
         crops = [to_pixels(im) for im in images]
-        return self._recognitions(*self.engine.recognize_images(crops, scores=True, **self._decode_kw(allowed, no_repeat_ngram, len(crops))))
+        kw = self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix)
+        return self._mark_forced(self._recognitions(*self.engine.recognize_images(crops, scores=True, **kw)), kw.get("prefixes"))
 
     def recognize_bgr_scored(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
-                             allowed=None, no_repeat_ngram=None) -> List[Recognition]:
+                             allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
         """``recognize_bgr`` with confidences."""
         from .queue_worker import rotation_code
         self._check_scored()
@@ -561,14 +643,15 @@ class MangaOcr:
             if len(orientations) != len(crops):
                 raise ValueError(f"recognize_bgr_scored: {len(crops)} crops but {len(orientations)} orientations")
             rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
-        return self._recognitions(*self.engine.recognize_images(crops, True, rot, scores=True, **self._decode_kw(allowed, no_repeat_ngram, len(crops))))
+        kw = self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix)
+        return self._mark_forced(self._recognitions(*self.engine.recognize_images(crops, True, rot, scores=True, **kw)), kw.get("prefixes"))
 
-    def recognize_regions_scored(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None) -> List[Recognition]:
+    def recognize_regions_scored(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
         """``recognize_regions`` with confidences; a region reduced to a sliver gives text '' and confidence 0.0."""
         self._check_scored()
         regions = list(regions)
-        return self._recognitions(*self.engine.recognize_regions(list(pages_bgr), regions, True, scores=True,
-                                                                 **self._decode_kw(allowed, no_repeat_ngram, len(regions))))
+        kw = self._decode_kw(allowed, no_repeat_ngram, len(regions), prefix)
+        return self._mark_forced(self._recognitions(*self.engine.recognize_regions(list(pages_bgr), regions, True, scores=True, **kw)), kw.get("prefixes"))
 
     # ------------------------------------------------------------------ alternatives surface: + the runners-up of every position
     def _check_alternatives(self) -> None:
@@ -579,24 +662,25 @@ class MangaOcr:
     def _recognitions_alt(self, ids, lens, logp, alt_ids, alt_logp) -> List[Recognition]:
         return [Recognition.from_row(self.vocab, ids[i], logp[i], lens[i], alt_ids[i], alt_logp[i]) for i in range(len(lens))]
 
-    def recognize_alternatives(self, img_or_path, *, allowed=None, no_repeat_ngram=None) -> Recognition:
+    def recognize_alternatives(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> Recognition:
         """``recognize_scored`` plus, for every generated position, the four most probable tokens and their log-probabilities
         (``Recognition.alt_ids`` / ``alt_logprobs`` / ``candidates``; include/mocr.h, "token alternatives").  Same text; goes
         through the same batcher as ``__call__``, and callers of all three kinds may share a batch."""
         self._check_alternatives()
         img = self._open(img_or_path)
-        extra = self._single(allowed, no_repeat_ngram)
+        extra = self._single(allowed, no_repeat_ngram, prefix)
         ids, logp, alt_ids, alt_logp = self._batcher.submit(to_pixels(img), alternatives=True, **extra).result()
-        return Recognition.from_row(self.vocab, ids, logp, len(ids), alt_ids, alt_logp)
+        return self._mark_forced([Recognition.from_row(self.vocab, ids, logp, len(ids), alt_ids, alt_logp)], [extra.get("prefix")])[0]
 
-    def recognize_batch_alternatives(self, images: Sequence, *, allowed=None, no_repeat_ngram=None) -> List[Recognition]:
+    def recognize_batch_alternatives(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
         """``recognize_batch`` with confidences and alternatives."""
         self._check_alternatives()
         crops = [to_pixels(im) for im in images]
-        return self._recognitions_alt(*self.engine.recognize_images(crops, alternatives=True, **self._decode_kw(allowed, no_repeat_ngram, len(crops))))
+        kw = self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix)
+        return self._mark_forced(self._recognitions_alt(*self.engine.recognize_images(crops, alternatives=True, **kw)), kw.get("prefixes"))
 
     def recognize_bgr_alternatives(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
-                                   allowed=None, no_repeat_ngram=None) -> List[Recognition]:
+                                   allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
         """``recognize_bgr`` with confidences and alternatives."""
         from .queue_worker import rotation_code
         self._check_alternatives()
@@ -606,16 +690,16 @@ class MangaOcr:
             if len(orientations) != len(crops):
                 raise ValueError(f"recognize_bgr_alternatives: {len(crops)} crops but {len(orientations)} orientations")
             rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
-        return self._recognitions_alt(*self.engine.recognize_images(crops, True, rot, alternatives=True,
-                                                                    **self._decode_kw(allowed, no_repeat_ngram, len(crops))))
+        kw = self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix)
+        return self._mark_forced(self._recognitions_alt(*self.engine.recognize_images(crops, True, rot, alternatives=True, **kw)), kw.get("prefixes"))
 
-    def recognize_regions_alternatives(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None) -> List[Recognition]:
+    def recognize_regions_alternatives(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
         """``recognize_regions`` with confidences and alternatives; a region reduced to a sliver gives text '', confidence
         0.0 and empty alternatives."""
         self._check_alternatives()
         regions = list(regions)
-        return self._recognitions_alt(*self.engine.recognize_regions(list(pages_bgr), regions, True, alternatives=True,
-                                                                     **self._decode_kw(allowed, no_repeat_ngram, len(regions))))
+        kw = self._decode_kw(allowed, no_repeat_ngram, len(regions), prefix)
+        return self._mark_forced(self._recognitions_alt(*self.engine.recognize_regions(list(pages_bgr), regions, True, alternatives=True, **kw)), kw.get("prefixes"))
 
     # ------------------------------------------------------------------ positions surface: + where each token was read
     def _check_positions(self) -> None:
@@ -627,24 +711,25 @@ class MangaOcr:
         return [Recognition.from_row(self.vocab, ids[i], logp[i], lens[i], pos_row=pos[i], rect=rects[i] if rects is not None else None)
                 for i in range(len(lens))]
 
-    def recognize_positions(self, img_or_path, *, allowed=None, no_repeat_ngram=None) -> Recognition:
+    def recognize_positions(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> Recognition:
         """``recognize_scored`` plus ``Recognition.positions``: per token where in the crop the decoder looked when it emitted
         it (include/mocr.h, "token positions"); ``Recognition.boxes(width, height)`` gives pixel rectangles.  Same text and
         scores; goes through the same batcher as ``__call__``, and callers of all kinds may share a batch."""
         self._check_positions()
         img = self._open(img_or_path)
-        ids, logp, pos = self._batcher.submit(to_pixels(img), scored=True, positions=True, **self._single(allowed, no_repeat_ngram)).result()
-        return Recognition.from_row(self.vocab, ids, logp, len(ids), pos_row=pos)
+        extra = self._single(allowed, no_repeat_ngram, prefix)
+        ids, logp, pos = self._batcher.submit(to_pixels(img), scored=True, positions=True, **extra).result()
+        return self._mark_forced([Recognition.from_row(self.vocab, ids, logp, len(ids), pos_row=pos)], [extra.get("prefix")])[0]
 
-    def recognize_batch_positions(self, images: Sequence, *, allowed=None, no_repeat_ngram=None) -> List[Recognition]:
+    def recognize_batch_positions(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
         """``recognize_batch_scored`` with positions."""
         self._check_positions()
         crops = [to_pixels(im) for im in images]
-        return self._recognitions_pos(*self.engine.recognize_images(crops, scores=True, positions=True,
-                                                                    **self._decode_kw(allowed, no_repeat_ngram, len(crops))))
+        kw = self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix)
+        return self._mark_forced(self._recognitions_pos(*self.engine.recognize_images(crops, scores=True, positions=True, **kw)), kw.get("prefixes"))
 
     def recognize_bgr_positions(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
-                                allowed=None, no_repeat_ngram=None) -> List[Recognition]:
+                                allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
         """``recognize_bgr_scored`` with positions.  The positions are those of the crop the encoder saw, i.e. after the
         orientation's rotation: pass the crop's rotation code (``queue_worker.rotation_code``) to ``Recognition.boxes`` to get
         rectangles on the crop as it was handed in."""
@@ -656,10 +741,10 @@ class MangaOcr:
             if len(orientations) != len(crops):
                 raise ValueError(f"recognize_bgr_positions: {len(crops)} crops but {len(orientations)} orientations")
             rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
-        return self._recognitions_pos(*self.engine.recognize_images(crops, True, rot, scores=True, positions=True,
-                                                                    **self._decode_kw(allowed, no_repeat_ngram, len(crops))))
+        kw = self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix)
+        return self._mark_forced(self._recognitions_pos(*self.engine.recognize_images(crops, True, rot, scores=True, positions=True, **kw)), kw.get("prefixes"))
 
-    def recognize_regions_positions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None) -> List[Recognition]:
+    def recognize_regions_positions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
         """``recognize_regions_scored`` with positions: every Recognition carries ``rect``, the region's padded, clipped
         rectangle on its page (``regions.padded_rect``), so ``Recognition.page_boxes()`` gives the tokens' rectangles in page
         pixels.  A region reduced to a sliver gives text '', no positions rows and ``rect`` None."""
@@ -667,8 +752,27 @@ class MangaOcr:
         self._check_positions()
         pages, regions = list(pages_bgr), list(regions)
         rects = [padded_rect(r[1:5], pages[int(r[0])].shape[0], pages[int(r[0])].shape[1]) for r in regions]
-        return self._recognitions_pos(*self.engine.recognize_regions(pages, regions, True, scores=True, positions=True,
-                                                                     **self._decode_kw(allowed, no_repeat_ngram, len(regions))), rects=rects)
+        kw = self._decode_kw(allowed, no_repeat_ngram, len(regions), prefix)
+        return self._mark_forced(self._recognitions_pos(*self.engine.recognize_regions(pages, regions, True, scores=True, positions=True, **kw), rects=rects), kw.get("prefixes"))
+
+    # ------------------------------------------------------------------ forced prefixes: score a given text
+    def _text_prefix(self, text) -> List[int]:
+        ids = self.vocab.encode_chars(text) if isinstance(text, str) else [int(t) for t in text]
+        if len(ids) + 2 > self.spec.max_len:
+            raise ValueError(f"score_text: {len(ids)} tokens do not fit max_len {self.spec.max_len} with the start token and EOS")
+        return ids + [int(self.spec.eos_id)]
+
+    def score_text(self, img_or_path, text) -> Recognition:
+        """How likely is ``text`` (a ``str``, one token per character, or token ids) for this crop: the row is forced to the
+        text plus EOS and scored, so ``Recognition.logprob`` is ``log p(text | crop)`` and ``logprobs`` its per-token terms."""
+        return self.recognize_scored(img_or_path, prefix=self._text_prefix(text))
+
+    def score_texts(self, images: Sequence, texts: Sequence) -> List[Recognition]:
+        """``score_text`` for many crops at once: one text per crop."""
+        images, texts = list(images), list(texts)
+        if len(images) != len(texts):
+            raise ValueError(f"score_texts: {len(images)} crops but {len(texts)} texts")
+        return self.recognize_batch_scored(images, prefix=[self._text_prefix(t) for t in texts])
 
     def recognize_page(self, page_bgr: np.ndarray, regions):
         """``_collect_manga_detections`` for one page: ``regions`` = the detector's (text, polygon) pairs."""

@@ -141,6 +141,30 @@ class Vocab:
                 out.append(i)
         return out
 
+    def encode_chars(self, text: str) -> List[int]:
+        """``text`` as one token per character - what a forced prefix (``MangaOcr.recognize(prefix=...)``, ``score_text``) is
+        built from.  Matched on the RAW token text of ``vocab.txt`` as ``ids_for_chars`` does (a leading ``##`` and whitespace
+        stripped, special tokens never count, the lowest id wins); whitespace in ``text`` is skipped.  A character without a
+        single-token spelling raises ``ValueError`` naming it."""
+        table = getattr(self, "_char_ids", None)
+        if table is None:
+            table = {}
+            for i, t in enumerate(self.tokens):
+                if i in self.special_ids:
+                    continue
+                body = "".join((t[2:] if t.startswith("##") else t).split())
+                if len(body) == 1:
+                    table.setdefault(body, i)
+            self._char_ids = table
+        out = []
+        for ch in str(text):
+            if ch.isspace():
+                continue
+            if ch not in table:
+                raise ValueError(f"encode_chars: the vocabulary has no single token for the character {ch!r} (U+{ord(ch):04X})")
+            out.append(table[ch])
+        return out
+
     def decode(self, ids: Iterable[int], skip_special_tokens: bool = True) -> str:
         import numpy as np
         a = np.asarray(list(ids) if not hasattr(ids, "__len__") else ids, dtype=np.int64).ravel()
