@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -388,26 +389,70 @@ static int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
     return (v && *v) ? atoi(v) : dflt;
 }
+#define LAB_ONLY(...) __VA_ARGS__      // rows of a table that exist in the experiments build only
 #else
 static constexpr int env_int(const char*, int dflt) { return dflt; }
+#define LAB_ONLY(...)
 #endif
 
 template <typename K> void set_max_lds(K kernel, int bytes) {
     HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
 }
 
-// ---------------------------------------------------------------------------------------- GEMM
-template <int BM> constexpr int gemm_ring() { return 2; }   // LDS ring depth per tile size
+// ---------------------------------------------------------------------------------------- kernel families
+// A kernel template that is built in several forms has ONE table, `forms`: each row is a set of template arguments (a literal
+// struct, `Args`) and nothing else.  Row I gives the instantiation (kernel<I>()) and the dynamic LDS it may use (lds(row)), and
+// the row itself is the run-time key a launch asks for.  A launch walks its family's table (find_form) and init_kernel_attrs
+// walks the same tables (raise_lds): what is launched is listed, what is listed is built, and no other line names a form.
+template <typename Kernel> struct Form {
+    Kernel kernel = nullptr;      // null: the family has no such form
+    int lds = 0;
+};
 
-template <typename T, int BM, int BN, int EPI, bool TGT = false>
-void launch_gemm_t(mocr_engine* e, const GemmParams& p0, int split, int ybatch) {
+template <typename Fam, size_t... I> Form<typename Fam::Kernel> find_form(const typename Fam::Args& key, std::index_sequence<I...>) {
+    Form<typename Fam::Kernel> r;
+    (void)((Fam::forms[I] == key && (r = {Fam::template kernel<I>(), Fam::lds(Fam::forms[I])}, true)) || ...);
+    return r;
+}
+template <typename Fam> Form<typename Fam::Kernel> find_form(const typename Fam::Args& key) {
+    return find_form<Fam>(key, std::make_index_sequence<std::size(Fam::forms)>{});
+}
+
+template <typename Fam, size_t... I> void raise_lds(std::index_sequence<I...>) {
+    (set_max_lds(Fam::template kernel<I>(), Fam::lds(Fam::forms[I])), ...);
+}
+template <typename... Fam> void raise_lds() { (raise_lds<Fam>(std::make_index_sequence<std::size(Fam::forms)>{}), ...); }
+
+// ---------------------------------------------------------------------------------------- GEMM
+// gemm_kernel (kernels_gemm.h): epilogue x 64 / 128 tiles x two / four ring slots; the two scored masked epilogues also with a
+// forced prefix's target column (GemmParams::tgt_val is a template parameter of theirs).
+struct TileArgs { int epi, bm, ring; bool tgt; };
+constexpr bool operator==(const TileArgs& a, const TileArgs& b) { return a.epi == b.epi && a.bm == b.bm && a.ring == b.ring && a.tgt == b.tgt; }
+constexpr std::array<TileArgs, 56> tile_forms() {
+    std::array<TileArgs, 56> a{};
+    int n = 0;
+    for (int epi : {EPI_SLAB, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_PATCH, EPI_BIAS_F32, EPI_ARGMAX, EPI_ARGMAX_LSE, EPI_TOPK,
+                    EPI_ARGMAX_M, EPI_ARGMAX_LSE_M, EPI_TOPK_M})
+        for (int bm : {64, 128})
+            for (int ring : {2, 4})
+                for (bool tgt : {false, true})
+                    if (!tgt || epi == EPI_ARGMAX_LSE_M || epi == EPI_TOPK_M) a[n++] = TileArgs{epi, bm, ring, tgt};
+    return a;
+}
+template <typename T> struct TileFamily {
+    using Args = TileArgs;
+    using Kernel = void (*)(GemmParams);
+    static constexpr std::array<Args, 56> forms = tile_forms();
+    static_assert(forms[55].bm == 128 && forms[55].tgt, "tile_forms fills its table");
+    template <size_t I> static constexpr Kernel kernel() { constexpr Args a = forms[I]; return gemm_kernel<T, a.bm, a.bm, a.epi, a.ring, a.tgt>; }
+    static constexpr int lds(const Args& a) { return a.ring * (a.bm + a.bm) * 128; }
+};
+
+template <typename T>
+void launch_gemm_tile(mocr_engine* e, const GemmParams& p0, int epi, int bm, int split, int ybatch) {
     GemmParams p = p0;
-    p.ntn = p.N / BN;
-    const int ntm = (p.M + BM - 1) / BM;
-    p.ntm = ntm;
-    constexpr int NST = gemm_ring<BM>();
-    constexpr int lds = NST * (BM + BN) * 128;
-    dim3 grid(ntm * p.ntn, ybatch, split);
+    p.ntn = p.N / bm; p.ntm = (p.M + bm - 1) / bm;
+    dim3 grid(p.ntm * p.ntn, ybatch, split);
     // Grids of at most one block per CU walk their K-tiles alone on a CU, one memory round trip per K-tile on the two-slot
     // ring.  A four-slot ring (three K-tiles in flight, 128 KiB of LDS for the 128 x 128 tile) changed nothing for the encoder
     // of a few crops (r02: QKV of one crop 16.1 vs 15.9 us - its cost is the DMA issue), but the decode step's split-K
@@ -423,93 +468,73 @@ void launch_gemm_t(mocr_engine* e, const GemmParams& p0, int split, int ybatch) 
     // launch_qqt its rows per block: r04, tools/r04_neutral_ab.sh, mixed-lengths leg 11.93 -> 12.11 k crops/s, ids bit-identical;
     // MOCR_NEUTRAL_BY_ROWS=0: by the batch's regime)
     static const int neutral_by_rows = env_int("MOCR_NEUTRAL_BY_ROWS", 2);
-    if ((neutral_by_rows ? p.M : e->rrows(p.M)) < deep_rows && ktiles >= 4 && (long long)grid.x * grid.y * grid.z <= (long long)e->num_cus * (BM == 64 ? deep_mult64 : 1)) {
-        hipLaunchKernelGGL((gemm_kernel<T, BM, BN, EPI, 4, TGT>), grid, dim3(256), 4 * (BM + BN) * 128, e->stream, p);
-    } else {
-        hipLaunchKernelGGL((gemm_kernel<T, BM, BN, EPI, NST, TGT>), grid, dim3(256), lds, e->stream, p);
-    }
+    const bool deep = (neutral_by_rows ? p.M : e->rrows(p.M)) < deep_rows && ktiles >= 4 &&
+                      (long long)grid.x * grid.y * grid.z <= (long long)e->num_cus * (bm == 64 ? deep_mult64 : 1);
+    const auto f = find_form<TileFamily<T>>({epi, bm, deep ? 4 : 2, p.tgt_val != nullptr});
+    if (!f.kernel) throw ArgError{"unknown GEMM epilogue", MOCR_ERR_ARG};
+    hipLaunchKernelGGL(f.kernel, grid, dim3(256), f.lds, e->stream, p);
     HIPCHECK(hipGetLastError());
-}
-
-template <typename T, int BM, int BN>
-void launch_gemm_epi(mocr_engine* e, const GemmParams& p, int epi, int split, int ybatch = 1) {
-    switch (epi) {
-        case EPI_SLAB: launch_gemm_t<T, BM, BN, EPI_SLAB>(e, p, split, ybatch); break;
-        case EPI_BIAS: launch_gemm_t<T, BM, BN, EPI_BIAS>(e, p, split, ybatch); break;
-        case EPI_BIAS_GELU: launch_gemm_t<T, BM, BN, EPI_BIAS_GELU>(e, p, split, ybatch); break;
-        case EPI_BIAS_RESID: launch_gemm_t<T, BM, BN, EPI_BIAS_RESID>(e, p, split, ybatch); break;
-        case EPI_PATCH: launch_gemm_t<T, BM, BN, EPI_PATCH>(e, p, split, ybatch); break;
-        case EPI_BIAS_F32: launch_gemm_t<T, BM, BN, EPI_BIAS_F32>(e, p, split, ybatch); break;
-        case EPI_ARGMAX: launch_gemm_t<T, BM, BN, EPI_ARGMAX>(e, p, split, ybatch); break;
-        case EPI_ARGMAX_LSE: launch_gemm_t<T, BM, BN, EPI_ARGMAX_LSE>(e, p, split, ybatch); break;
-        case EPI_TOPK: launch_gemm_t<T, BM, BN, EPI_TOPK>(e, p, split, ybatch); break;
-        case EPI_ARGMAX_M: launch_gemm_t<T, BM, BN, EPI_ARGMAX_M>(e, p, split, ybatch); break;
-        // (a forced prefix's target column - GemmParams::tgt_val - is a template parameter of these two)
-        case EPI_ARGMAX_LSE_M:
-            if (p.tgt_val) launch_gemm_t<T, BM, BN, EPI_ARGMAX_LSE_M, true>(e, p, split, ybatch);
-            else launch_gemm_t<T, BM, BN, EPI_ARGMAX_LSE_M>(e, p, split, ybatch);
-            break;
-        case EPI_TOPK_M:
-            if (p.tgt_val) launch_gemm_t<T, BM, BN, EPI_TOPK_M, true>(e, p, split, ybatch);
-            else launch_gemm_t<T, BM, BN, EPI_TOPK_M>(e, p, split, ybatch);
-            break;
-        default: throw ArgError{"unknown GEMM epilogue", MOCR_ERR_ARG};
-    }
 }
 
 #ifdef MOCR_EXPERIMENTS
-template <int EPI>
-void launch_gemm256_t(mocr_engine* e, const GemmParams& p0) {
+// The A/B kernels of kernels_gemm_lab.h: gemm256_kernel, gemm_wide_kernel (256 x 128 / 256 x 256 tiles: WN = 2 / 4), gemm_wide2_kernel.
+struct EpiArgs { int epi, wn; };      // (wn: gemm_wide_kernel only)
+constexpr bool operator==(const EpiArgs& a, const EpiArgs& b) { return a.epi == b.epi && a.wn == b.wn; }
+struct Gemm256Family {
+    using Args = EpiArgs;
+    using Kernel = void (*)(GemmParams);
+    static constexpr Args forms[] = {{EPI_BIAS, 0}, {EPI_BIAS_GELU, 0}, {EPI_BIAS_RESID, 0}, {EPI_PATCH, 0}, {EPI_BIAS_F32, 0}};
+    template <size_t I> static constexpr Kernel kernel() { return gemm256_kernel<forms[I].epi>; }
+    static constexpr int lds(const Args&) { return 3 * (256 + 128) * 128; }
+};
+struct WideFamily {
+    using Args = EpiArgs;
+    using Kernel = void (*)(GemmParams);
+    static constexpr Args forms[] = {{EPI_BIAS, 2}, {EPI_BIAS_GELU, 2}, {EPI_BIAS_RESID, 2}, {EPI_BIAS, 4}, {EPI_BIAS_GELU, 4}, {EPI_BIAS_RESID, 4}};
+    template <size_t I> static constexpr Kernel kernel() { return gemm_wide_kernel<forms[I].epi, forms[I].wn>; }
+    static constexpr int lds(const Args& a) { return 3 * (256 + 64 * a.wn) * 64; }
+};
+struct Wide2Family {
+    using Args = EpiArgs;
+    using Kernel = void (*)(GemmParams);
+    static constexpr Args forms[] = {{EPI_BIAS, 0}, {EPI_BIAS_GELU, 0}, {EPI_BIAS_RESID, 0}};
+    template <size_t I> static constexpr Kernel kernel() { return gemm_wide2_kernel<forms[I].epi>; }
+    static constexpr int lds(const Args&) { return 4 * (256 + 256) * 64; }
+};
+
+void launch_gemm256(mocr_engine* e, const GemmParams& p0, int epi) {
+    const auto f = find_form<Gemm256Family>({epi, 0});
+    if (!f.kernel) throw ArgError{"gemm256: unsupported epilogue", MOCR_ERR_ARG};
     GemmParams p = p0;
-    p.ntn = p.N / 128;
-    const int ntm = (p.M + 255) / 256;
-    p.ntm = ntm;
-    hipLaunchKernelGGL((gemm256_kernel<EPI>), dim3(ntm * p.ntn), dim3(256), 3 * (256 + 128) * 128, e->stream, p);
+    p.ntn = p.N / 128; p.ntm = (p.M + 255) / 256;
+    hipLaunchKernelGGL(f.kernel, dim3(p.ntm * p.ntn), dim3(256), f.lds, e->stream, p);
     HIPCHECK(hipGetLastError());
 }
 
-void launch_gemm256(mocr_engine* e, const GemmParams& p, int epi) {
-    switch (epi) {
-        case EPI_BIAS: launch_gemm256_t<EPI_BIAS>(e, p); break;
-        case EPI_BIAS_GELU: launch_gemm256_t<EPI_BIAS_GELU>(e, p); break;
-        case EPI_BIAS_RESID: launch_gemm256_t<EPI_BIAS_RESID>(e, p); break;
-        case EPI_PATCH: launch_gemm256_t<EPI_PATCH>(e, p); break;
-        case EPI_BIAS_F32: launch_gemm256_t<EPI_BIAS_F32>(e, p); break;
-        default: throw ArgError{"gemm256: unsupported epilogue", MOCR_ERR_ARG};
-    }
-}
-
-template <int EPI, int WN>
-void launch_gemm_wide_t(mocr_engine* e, const GemmParams& p0) {
+// one tile per block; the grid is rounded up to 8 so that every XCD gets the same count (an empty block returns at once)
+void launch_gemm_wide(mocr_engine* e, const GemmParams& p0, int epi, int wn) {
+    const auto f = find_form<WideFamily>({epi, wn});
+    if (!f.kernel) throw ArgError{"wide gemm: unsupported epilogue", MOCR_ERR_ARG};
     GemmParams p = p0;
-    p.ntn = p.N / (64 * WN);
-    const int ntm = (p.M + 255) / 256;
-    p.ntm = ntm;
-    // persistent: one (256x256) or two (256x128) blocks per CU, a multiple of 8 so that every XCD gets the same count
-    const int ntiles = ntm * p.ntn;
-    // one tile per block; the grid is rounded up to 8 so that every XCD gets the same count (an empty block returns at once)
-    const int grid = (ntiles + 7) / 8 * 8;
-    hipLaunchKernelGGL((gemm_wide_kernel<EPI, WN>), dim3(grid), dim3(128 * WN), 3 * (256 + 64 * WN) * 64, e->stream, p);
+    p.ntn = p.N / (64 * wn); p.ntm = (p.M + 255) / 256;
+    hipLaunchKernelGGL(f.kernel, dim3((p.ntm * p.ntn + 7) / 8 * 8), dim3(128 * wn), f.lds, e->stream, p);
     HIPCHECK(hipGetLastError());
 }
 
-template <int EPI>
-void launch_gemm_wide2_t(mocr_engine* e, const GemmParams& p0) {
+void launch_gemm_wide2(mocr_engine* e, const GemmParams& p0, int epi) {
+    if (p0.k_per_split % 64 || p0.k_per_split < 128) throw ArgError{"wide2 gemm: K must be a multiple of 64, >= 128", MOCR_ERR_ARG};
+    const auto f = find_form<Wide2Family>({epi, 0});
+    if (!f.kernel) throw ArgError{"wide2 gemm: unsupported epilogue", MOCR_ERR_ARG};
     GemmParams p = p0;
-    p.ntn = p.N / 256;
-    p.ntm = (p.M + 255) / 256;
-    const int grid = (p.ntm * p.ntn + 7) / 8 * 8;
+    p.ntn = p.N / 256; p.ntm = (p.M + 255) / 256;
     static const int stagger_env = env_int("MOCR_GEMM_STAGGER", -1);
     p.stagger = stagger_env > 0 ? stagger_env : 0;      // measured r02: no gain (the store drain is not what a phase shift hides), default off
     p.first_round = e->num_cus;
-    hipLaunchKernelGGL((gemm_wide2_kernel<EPI>), dim3(grid), dim3(512), 4 * (256 + 256) * 64, e->stream, p);
+    hipLaunchKernelGGL(f.kernel, dim3((p.ntm * p.ntn + 7) / 8 * 8), dim3(512), f.lds, e->stream, p);
     HIPCHECK(hipGetLastError());
 }
-
 #endif  // MOCR_EXPERIMENTS
 
-// The persistent kernel (kernels_gemm_pers.h): one block per CU walks its share of the 256 x 256 tiles.  `blocks` = 0:
-// one block per CU (a multiple of 8, at most one per tile); a test may ask for fewer blocks (longer tile sequences).
 // The strip schedule of the persistent kernel (kernels_gemm_pers.h, STRIP): rows per strip for a grid of `grid` blocks,
 // 0 when the grid cannot hold a strip.  Host mirror of the kernel's arithmetic.
 static int pers_strip_rows(int M, int ntn, int grid) {
@@ -535,103 +560,95 @@ static bool pers_strip_wins(int M, int ntn, int grid) {
     return strip_cost <= 0.965 * per_block;
 }
 
-template <int EPI, bool SPLIT_DMA, bool PAIR = false, bool STRIP = false, bool LNF = false>
-void launch_gemm_pers_t(mocr_engine* e, const GemmParams& p0, int blocks) {
+// gemm_pers_kernel (kernels_gemm_pers.h): <epilogue, split DMA, pair loop, strips, LayerNorm fold>.  The product runs split DMA
+// on the one-barrier-per-two-K-tiles loop (K64: 64-deep LDS image, whole-line DMA requests), every epilogue with and without
+// strips and fold.
+struct PersArgs { int epi; bool split_dma, pair, strip, lnf; };
+constexpr bool operator==(const PersArgs& a, const PersArgs& b) {
+    return a.epi == b.epi && a.split_dma == b.split_dma && a.pair == b.pair && a.strip == b.strip && a.lnf == b.lnf;
+}
+struct PersFamily {
+    using Args = PersArgs;
+    using Kernel = void (*)(GemmParams);
+    static constexpr Args forms[] = {
+        {EPI_BIAS, true, true, false, false}, {EPI_BIAS, true, true, true, false}, {EPI_BIAS, true, true, false, true}, {EPI_BIAS, true, true, true, true},
+        {EPI_BIAS_GELU, true, true, false, false}, {EPI_BIAS_GELU, true, true, true, false}, {EPI_BIAS_GELU, true, true, false, true}, {EPI_BIAS_GELU, true, true, true, true},
+        {EPI_BIAS_RESID, true, true, false, false}, {EPI_BIAS_RESID, true, true, true, false}, {EPI_BIAS_RESID, true, true, false, true}, {EPI_BIAS_RESID, true, true, true, true},
+#ifdef MOCR_EXPERIMENTS
+        // the one-barrier-per-K-tile loop on the 32-deep image, A/B partner of the pair loop (its fp32-residual form never folds)
+        {EPI_BIAS, true, false, false, false}, {EPI_BIAS, true, false, true, false}, {EPI_BIAS, true, false, false, true}, {EPI_BIAS, true, false, true, true},
+        {EPI_BIAS_GELU, true, false, false, false}, {EPI_BIAS_GELU, true, false, true, false}, {EPI_BIAS_GELU, true, false, false, true}, {EPI_BIAS_GELU, true, false, true, true},
+        {EPI_BIAS_RESID, true, false, false, false}, {EPI_BIAS_RESID, true, false, true, false},
+        // every wave requests LDS-DMA: both loops, tile list only
+        {EPI_BIAS, false, false, false, false}, {EPI_BIAS_GELU, false, false, false, false}, {EPI_BIAS_RESID, false, false, false, false},
+        {EPI_BIAS, false, true, false, false}, {EPI_BIAS_GELU, false, true, false, false}, {EPI_BIAS_RESID, false, true, false, false},
+#endif
+    };
+    template <size_t I> static constexpr Kernel kernel() { constexpr Args a = forms[I]; return gemm_pers_kernel<a.epi, a.split_dma, a.pair, a.strip, a.lnf>; }
+    static constexpr int lds(const Args&) { return PERS_LDS; }
+};
+
+// One launch of the persistent kernel.  blocks = 0: one block per CU (a multiple of 8, at most one per tile); a test may ask for
+// fewer blocks (longer tile sequences).  strip: 0 tile list, 1 strips wherever the grid can hold one, -1 whichever walks fewer
+// rounds; strips exist for the split-DMA forms only.  p.ln_part set: the LayerNorm-folding forms (kernels_gemm_pers.h, LNF).
+void launch_gemm_pers(mocr_engine* e, const GemmParams& p0, int epi, bool split_dma, bool pair, int blocks, int strip) {
     GemmParams p = p0;
-    p.ntn = p.N / 256;
-    p.ntm = (p.M + 255) / 256;
-    const int ntiles = p.ntm * p.ntn;
-    int grid = std::min(blocks > 0 ? blocks : e->num_cus, (ntiles + 7) / 8 * 8);
-    grid = std::max(8, grid / 8 * 8);
+    if (p.k_per_split % 64 || p.k_per_split < 128) throw ArgError{"persistent gemm: K must be a multiple of 64, >= 128", MOCR_ERR_ARG};
+    const bool lnf = p.ln_part != nullptr;
+    if (lnf && !(split_dma && (epi == EPI_BIAS_RESID ? (pair && p.N <= 1024 && p.xb) : p.csum != nullptr)))
+        throw ArgError{"persistent gemm: LayerNorm folding needs the product kernel forms and their operands", MOCR_ERR_ARG};
+    p.ntn = p.N / 256; p.ntm = (p.M + 255) / 256;
+    const int grid = std::max(8, std::min(blocks > 0 ? blocks : e->num_cus, (p.ntm * p.ntn + 7) / 8 * 8) / 8 * 8);
+    const bool strips = split_dma && strip && (strip > 0 ? pers_strip_rows(p.M, p.ntn, grid) > 0 : pers_strip_wins(p.M, p.ntn, grid));
+    const auto f = find_form<PersFamily>({epi, split_dma, pair, strips, lnf});
+    if (!f.kernel && lnf) throw ArgError{"persistent gemm: no LayerNorm-folding form of this kernel variant", MOCR_ERR_ARG};
+    if (!f.kernel) throw ArgError{"persistent gemm: unsupported epilogue", MOCR_ERR_ARG};
     static const int stagger_env = env_int("MOCR_GEMM_STAGGER", 0);
     p.stagger = stagger_env;
     static const int hpos_env = env_int("MOCR_GEMM_HPOS", 0);
     p.first_round = hpos_env;
-    hipLaunchKernelGGL((gemm_pers_kernel<EPI, SPLIT_DMA, PAIR, STRIP, LNF>), dim3(grid), dim3(512), PERS_LDS, e->stream, p);
+    hipLaunchKernelGGL(f.kernel, dim3(grid), dim3(512), f.lds, e->stream, p);
     HIPCHECK(hipGetLastError());
 }
 
-// strip: 0 tile list, 1 strips, -1 whichever walks fewer rounds (EPI_BIAS_RESID only; the other epilogues keep the list).
-// p.ln_part set: the LayerNorm-folding forms of the kernel (kernels_gemm_pers.h, LNF).
-template <bool SPLIT_DMA, bool PAIR = false>
-void launch_gemm_pers(mocr_engine* e, const GemmParams& p, int epi, int blocks, int strip = 0) {
-    if (p.k_per_split % 64 || p.k_per_split < 128) throw ArgError{"persistent gemm: K must be a multiple of 64, >= 128", MOCR_ERR_ARG};
-    const bool lnf = p.ln_part != nullptr;
-    if (lnf && !(SPLIT_DMA && (epi == EPI_BIAS_RESID ? (PAIR && p.N <= 1024 && p.xb) : p.csum != nullptr)))
-        throw ArgError{"persistent gemm: LayerNorm folding needs the product kernel forms and their operands", MOCR_ERR_ARG};
-    if constexpr (SPLIT_DMA) {
-        bool strips = false;
-        if (strip) {
-            const int ntn = p.N / 256, ntiles = ((p.M + 255) / 256) * ntn;
-            const int grid = std::max(8, std::min(blocks > 0 ? blocks : e->num_cus, (ntiles + 7) / 8 * 8) / 8 * 8);
-            strips = strip > 0 ? pers_strip_rows(p.M, ntn, grid) > 0 : pers_strip_wins(p.M, ntn, grid);
-        }
-        if constexpr (PAIR) {
-            if (epi == EPI_BIAS_RESID) {
-                if (strips && lnf) { launch_gemm_pers_t<EPI_BIAS_RESID, true, true, true, true>(e, p, blocks); return; }
-                if (strips) { launch_gemm_pers_t<EPI_BIAS_RESID, true, true, true>(e, p, blocks); return; }
-                if (lnf) { launch_gemm_pers_t<EPI_BIAS_RESID, true, true, false, true>(e, p, blocks); return; }
-            }
-            // the bf16 epilogues on the one-barrier-per-two-K-tiles loop (K64: 64-deep LDS image, whole-line DMA requests)
-            if (epi == EPI_BIAS_GELU) {
-                if (strips && lnf) { launch_gemm_pers_t<EPI_BIAS_GELU, true, true, true, true>(e, p, blocks); return; }
-                if (strips) { launch_gemm_pers_t<EPI_BIAS_GELU, true, true, true>(e, p, blocks); return; }
-                if (lnf) { launch_gemm_pers_t<EPI_BIAS_GELU, true, true, false, true>(e, p, blocks); return; }
-            }
-            if (epi == EPI_BIAS) {
-                if (strips && lnf) { launch_gemm_pers_t<EPI_BIAS, true, true, true, true>(e, p, blocks); return; }
-                if (strips) { launch_gemm_pers_t<EPI_BIAS, true, true, true>(e, p, blocks); return; }
-                if (lnf) { launch_gemm_pers_t<EPI_BIAS, true, true, false, true>(e, p, blocks); return; }
-            }
-        } else {
-            if (epi == EPI_BIAS_RESID && strips) { launch_gemm_pers_t<EPI_BIAS_RESID, true, false, true>(e, p, blocks); return; }
-            if (epi == EPI_BIAS_GELU) {
-                if (strips && lnf) { launch_gemm_pers_t<EPI_BIAS_GELU, true, false, true, true>(e, p, blocks); return; }
-                if (strips) { launch_gemm_pers_t<EPI_BIAS_GELU, true, false, true>(e, p, blocks); return; }
-                if (lnf) { launch_gemm_pers_t<EPI_BIAS_GELU, true, false, false, true>(e, p, blocks); return; }
-            }
-            if (epi == EPI_BIAS) {
-                if (strips && lnf) { launch_gemm_pers_t<EPI_BIAS, true, false, true, true>(e, p, blocks); return; }
-                if (strips) { launch_gemm_pers_t<EPI_BIAS, true, false, true>(e, p, blocks); return; }
-                if (lnf) { launch_gemm_pers_t<EPI_BIAS, true, false, false, true>(e, p, blocks); return; }
-            }
-        }
-        if (lnf) throw ArgError{"persistent gemm: no LayerNorm-folding form of this kernel variant", MOCR_ERR_ARG};
-    }
-    switch (epi) {
-        case EPI_BIAS: launch_gemm_pers_t<EPI_BIAS, SPLIT_DMA, PAIR>(e, p, blocks); break;
-        case EPI_BIAS_GELU: launch_gemm_pers_t<EPI_BIAS_GELU, SPLIT_DMA, PAIR>(e, p, blocks); break;
-        case EPI_BIAS_RESID: launch_gemm_pers_t<EPI_BIAS_RESID, SPLIT_DMA, PAIR>(e, p, blocks); break;
-        default: throw ArgError{"persistent gemm: unsupported epilogue", MOCR_ERR_ARG};
-    }
-}
-
+// Tile codes.  The numbers belong to the boundaries that own them (mocr_op_gemm / mocr_op_gemm_ln, the MOCR_*_TILE knobs, DESIGN's
+// appendix, the tests); inside, this one table says what a code means and everybody else asks the row.
+enum class GemmKind { Tile, Persistent, Lab256, Wide, Wide2, LabOnly };
+struct TileCode {
+    int code;
+    GemmKind kind;
+    int arg;                  // Tile: the tile's rows = columns; Wide: WN
+    int blocks;               // Persistent: 0 = one block per CU, 8 = a test hook, 8 blocks walk all the tiles
+    int strip;                // Persistent: 0 tile list, 1 the strip schedule forced (test hooks), -1 by the shape (MOCR_GEMM_STRIP)
+    bool split_dma, pair;     // Persistent: the kernel form (PersArgs)
+    bool knobs;               // Persistent: the codes of the product, which MOCR_GEMM_PAIR_BF16 moves to the other loop
+    bool persistent() const { return kind == GemmKind::Persistent; }
+    bool product_persistent() const { return persistent() && knobs && !blocks && strip < 0; }      // the form run_encoder picks (and folds)
+};
+constexpr int TILE_PERSISTENT = 4096;
+constexpr TileCode TILE_CODES[] = {
+    {64, GemmKind::Tile, 64}, {128, GemmKind::Tile, 128},
+    // one barrier per two K-tiles for the fp32-residual GEMMs (r03, M = 50,432: O-proj 137 -> 129 us, FC2 305 -> 302; the
+    // bf16-output GEMMs lose with it: QKV 175 -> 208 us)
+    // 4097: a test hook, 8 blocks walk all the tiles; 4099 / 4100: the strip schedule forced (whole grid / 8 blocks) - test hooks too
+    {TILE_PERSISTENT, GemmKind::Persistent, 0, 0, -1, true, true, true}, {4097, GemmKind::Persistent, 0, 8, 0, true, true, true},
+    {4099, GemmKind::Persistent, 0, 0, 1, true, true, true}, {4100, GemmKind::Persistent, 0, 8, 1, true, true, true},
 #ifdef MOCR_EXPERIMENTS
-void launch_gemm_wide2(mocr_engine* e, const GemmParams& p, int epi) {
-    if (p.k_per_split % 64 || p.k_per_split < 128) throw ArgError{"wide2 gemm: K must be a multiple of 64, >= 128", MOCR_ERR_ARG};
-    switch (epi) {
-        case EPI_BIAS: launch_gemm_wide2_t<EPI_BIAS>(e, p); break;
-        case EPI_BIAS_GELU: launch_gemm_wide2_t<EPI_BIAS_GELU>(e, p); break;
-        case EPI_BIAS_RESID: launch_gemm_wide2_t<EPI_BIAS_RESID>(e, p); break;
-        default: throw ArgError{"wide2 gemm: unsupported epilogue", MOCR_ERR_ARG};
-    }
+    {256, GemmKind::Lab256}, {512, GemmKind::Wide, 2}, {1024, GemmKind::Wide, 4}, {2048, GemmKind::Wide2},
+    {4098, GemmKind::Persistent, 0, 0, 0, false, false},                                                        // every wave requests LDS-DMA
+    {4101, GemmKind::Persistent, 0, 0, 0, true, true}, {4102, GemmKind::Persistent, 0, 8, 0, true, true},      // one barrier per two K-tiles
+    {4103, GemmKind::Persistent, 0, 0, 1, true, false}, {4104, GemmKind::Persistent, 0, 8, 1, true, false},    // strips on the one-barrier-per-K-tile loop
+    {4105, GemmKind::Persistent, 0, 0, 0, false, true}, {4106, GemmKind::Persistent, 0, 8, 0, false, true},    // the pair loop with every wave requesting LDS-DMA
+#else
+    {256, GemmKind::LabOnly}, {512, GemmKind::LabOnly}, {1024, GemmKind::LabOnly}, {2048, GemmKind::LabOnly}, {4098, GemmKind::LabOnly},
+#endif
+};
+static const TileCode* tile_code(int code) {
+    for (const TileCode& t : TILE_CODES) if (t.code == code) return &t;
+    return nullptr;      // not a tile code
 }
+static bool tile_is(int code, GemmKind kind) { const TileCode* t = tile_code(code); return t && t->kind == kind; }
 
-template <int WN>
-void launch_gemm_wide(mocr_engine* e, const GemmParams& p, int epi) {
-    switch (epi) {
-        case EPI_BIAS: launch_gemm_wide_t<EPI_BIAS, WN>(e, p); break;
-        case EPI_BIAS_GELU: launch_gemm_wide_t<EPI_BIAS_GELU, WN>(e, p); break;
-        case EPI_BIAS_RESID: launch_gemm_wide_t<EPI_BIAS_RESID, WN>(e, p); break;
-        default: throw ArgError{"wide gemm: unsupported epilogue", MOCR_ERR_ARG};
-    }
-}
-
-#endif  // MOCR_EXPERIMENTS
-
-// A [M,K] (lda), W [N,K] (ldw=K), out (ldo).  tile: 64 / 128 (gemm_kernel), 4096 (the persistent 256 x 256 encoder kernel;
-// 4097: the same on 8 blocks, a test hook); experiments build only: 256, 512, 1024, 2048, 4098 (kernels_gemm_lab.h).
-// split > 1 only with EPI_SLAB.
 struct HeadBatch { int heads = 1; long long a_yoff = 0, w_yoff = 0, o_yoff = 0, b_yoff = 0; int ldw = 0; };
 // LayerNorm folded into the persistent encoder GEMMs (tile code 4096; kernels_gemm_pers.h LNF).  EPI_BIAS_RESID: `part` and
 // `xb` are written; EPI_BIAS / EPI_BIAS_GELU: `part` and `csum` are read (W and bias are the folded ones).
@@ -644,112 +661,128 @@ struct TokMask { const unsigned* table = nullptr; const int* set_of_row = nullpt
 struct TokTarget { const int* prefix = nullptr; const int* prefix_len = nullptr; int prefix_ld = 0; const int* step = nullptr; float* tgt_val = nullptr; };
 struct LmHead { int* cand_idx = nullptr; float* cand_sum = nullptr; float* top_val = nullptr; int* top_idx = nullptr; TokMask mask; TokTarget target; };
 
+// One GEMM: A [M,K] (lda), W [N,K] (ldw = K), out (ldo).  tile: a tile code (TILE_CODES).  gemm_call states the operands and the
+// shape; a call site then names every extra it sets.  split > 1 only with EPI_SLAB.
+struct GemmCall {
+    const char* name;
+    const void* A; int lda;
+    const void* W; const float* bias;
+    void* out; int ldo;
+    int M, N, K, epi, tile;
+    const float* resid = nullptr;                       // EPI_BIAS_RESID
+    int split = 1; long long slab_stride = 0;           // EPI_SLAB: K slices, and the elements between two slices' slabs
+    const float* pos = nullptr; int patches = 0;        // EPI_PATCH: the position table and the patches per crop
+    const HeadBatch* hb = nullptr;                      // one GEMM per head (grid.y)
+    int group_n = 0;                                    // N-tiles per column group of the tile order (0: none)
+    const LmHead* lm = nullptr;                         // the fused LM-head epilogues
+    const LnFold* lnf = nullptr;                        // LayerNorm folded in
+};
+static GemmCall gemm_call(const char* name, const void* A, int lda, const void* W, const float* bias, void* out, int ldo, int M, int N,
+                          int K, int epi, int tile) {
+    GemmCall c{};
+    c.name = name; c.A = A; c.lda = lda; c.W = W; c.bias = bias; c.out = out; c.ldo = ldo; c.M = M; c.N = N; c.K = K; c.epi = epi; c.tile = tile;
+    return c;
+}
+
+#ifdef MOCR_EXPERIMENTS
+// Diagnostics of the persistent kernel, MOCR_GEMM_ABLATE & 8192 (kernels_gemm_pers.h, MOCR_STAMP): the kernel's cycle stamps go
+// to a buffer passed in GemmParams::pos (stamps_arm) and are summed up per role behind the launch (stamps_report).
+static unsigned long long* g_stamp_buf = nullptr;
+static void stamps_arm(mocr_engine* e, GemmParams& p) {
+    if (!g_stamp_buf) HIPCHECK(hipMalloc(&g_stamp_buf, 1024 * 8 * 4 * 8));
+    HIPCHECK(hipMemsetAsync(g_stamp_buf, 0, 1024 * 8 * 4 * 8, e->stream));
+    p.pos = reinterpret_cast<const float*>(g_stamp_buf);
+}
+static void stamps_report(mocr_engine* e, const char* name) {
+    if (!g_stamp_buf) return;
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    std::vector<unsigned long long> h(256 * 8 * 4);
+    HIPCHECK(hipMemcpy(h.data(), g_stamp_buf, h.size() * 8, hipMemcpyDeviceToHost));
+    double s0[2] = {0, 0}, s1[2] = {0, 0}, s2[2] = {0, 0}, pairs = 0;
+    int nb = 0;
+    for (int b = 0; b < 256; ++b) {
+        if (!h[(b * 8) * 4 + 3]) continue;
+        ++nb;
+        pairs += (double)h[(b * 8) * 4 + 3] / 2;
+        for (int w = 0; w < 8; ++w) { s0[w >> 2] += h[(b * 8 + w) * 4]; s1[w >> 2] += h[(b * 8 + w) * 4 + 1]; s2[w >> 2] += h[(b * 8 + w) * 4 + 2]; }
+    }
+    if (nb) {
+        const double n = pairs * 4;      // wave-pairs per role
+        fprintf(stderr, "[stamps] %s: %d blocks, %.0f K-tile pairs each; cycles per pair  DMA waves: work %.0f, DMA wait %.0f, barrier %.0f | store waves: work %.0f, -, barrier %.0f\n",
+                name, nb, pairs / nb, s0[0] / n, s1[0] / n, s2[0] / n, s0[1] / n, (s1[1] + s2[1]) / n);
+    }
+}
+#endif
+
 template <typename T>
-void gemm(mocr_engine* e, const char* name, const void* A, int lda, const void* W, const float* bias, void* out, int ldo,
-          const float* resid, int M, int N, int K, int epi, int tile, int split, long long slab_stride = 0,
-          const float* pos = nullptr, int patches = 0, const HeadBatch* hb = nullptr, int group_n = 0, const LmHead* lm = nullptr,
-          const LnFold* lnf = nullptr) {
+void gemm(mocr_engine* e, const GemmCall& c) {
+    const int M = c.M, N = c.N, K = c.K, epi = c.epi, tile = c.tile, split = c.split;
+    const LmHead* const lm = c.lm;
     const int kt = 128 / (int)sizeof(T);
     if (N % (tile >= 1024 ? 256 : tile >= 256 ? 128 : std::max(tile, 1)) || K % (kt * split) || (split > 1 && epi != EPI_SLAB) ||
         (tile >= 256 && (sizeof(T) != 2 || split != 1)))
-        throw ArgError{std::string("gemm shape not tileable: ") + name, MOCR_ERR_ARG};
+        throw ArgError{std::string("gemm shape not tileable: ") + c.name, MOCR_ERR_ARG};
     GemmParams p{};
-    p.A = A; p.W = W; p.bias = bias; p.out = out; p.resid = resid; p.pos = pos;
+    p.A = c.A; p.W = c.W; p.bias = c.bias; p.out = c.out; p.resid = c.resid; p.pos = c.pos;
     const TokMask tm = lm ? lm->mask : TokMask{};
     if ((epi == EPI_ARGMAX_M || epi == EPI_ARGMAX_LSE_M || epi == EPI_TOPK_M) != (tm.table || tm.set_of_row) || !tm.table != !tm.set_of_row)
-        throw ArgError{std::string("the masked LM-head epilogues come with a token-set table: ") + name, MOCR_ERR_ARG};
+        throw ArgError{std::string("the masked LM-head epilogues come with a token-set table: ") + c.name, MOCR_ERR_ARG};
     if (lm) {
         p.cand_idx = lm->cand_idx; p.cand_sum = lm->cand_sum; p.top_val = lm->top_val; p.top_idx = lm->top_idx;
         if (tm.table) { p.tok_mask = tm.table; p.set_of_row = tm.set_of_row; p.rowmap = tm.rowmap; }
         const TokTarget& tt = lm->target;
         if (tt.tgt_val) {
             if ((epi != EPI_ARGMAX_LSE_M && epi != EPI_TOPK_M) || !tt.prefix || !tt.prefix_len || !tt.step || tt.prefix_ld < 1)
-                throw ArgError{std::string("a target column comes with the masked, scored LM-head epilogues and all five arrays: ") + name, MOCR_ERR_ARG};
+                throw ArgError{std::string("a target column comes with the masked, scored LM-head epilogues and all five arrays: ") + c.name, MOCR_ERR_ARG};
             p.prefix = tt.prefix; p.prefix_len = tt.prefix_len; p.prefix_ld = tt.prefix_ld; p.step = tt.step; p.tgt_val = tt.tgt_val;
         }
     }
-    p.M = M; p.N = N; p.lda = lda; p.ldw = K; p.ldo = ldo;
+    p.M = M; p.N = N; p.lda = c.lda; p.ldw = K; p.ldo = c.ldo;
     int ybatch = 1;
-    if (hb) {
+    if (const HeadBatch* hb = c.hb) {
         if (epi != EPI_BIAS || tile >= 256) throw ArgError{"per-head batched GEMM needs EPI_BIAS on the 64/128 kernel", MOCR_ERR_ARG};
         ybatch = hb->heads; p.a_yoff = hb->a_yoff; p.w_yoff = hb->w_yoff; p.o_yoff = hb->o_yoff; p.b_yoff = hb->b_yoff;
         if (hb->ldw) p.ldw = hb->ldw;
     }
-    p.k_per_split = K / split; p.slab_stride = slab_stride; p.patches = patches;
-    if (lnf) {
+    p.k_per_split = K / split; p.slab_stride = c.slab_stride; p.patches = c.patches;
+    if (c.lnf) {
         if (tile < 4096 || tile > 4100 || sizeof(T) != 2) throw ArgError{"LayerNorm folding: persistent bf16 GEMMs only", MOCR_ERR_ARG};
-        p.ln_part = lnf->part; p.csum = lnf->csum; p.xb = lnf->xb; p.ln_eps = e->cfg.ln_eps;
+        p.ln_part = c.lnf->part; p.csum = c.lnf->csum; p.xb = c.lnf->xb; p.ln_eps = e->cfg.ln_eps;
     }
+    const TileCode* const tc = tile_code(tile);
     static const int ablate = env_int("MOCR_GEMM_ABLATE", 0);
     p.ablate = ablate;
 #ifdef MOCR_EXPERIMENTS
-    static unsigned long long* stamp_buf = nullptr;      // diagnostics: MOCR_GEMM_ABLATE & 8192 (kernels_gemm_pers.h, MOCR_STAMP)
-    if ((ablate & 8192) && tile >= 4096 && epi != EPI_PATCH) {
-        if (!stamp_buf) HIPCHECK(hipMalloc(&stamp_buf, 1024 * 8 * 4 * 8));
-        HIPCHECK(hipMemsetAsync(stamp_buf, 0, 1024 * 8 * 4 * 8, e->stream));
-        p.pos = reinterpret_cast<const float*>(stamp_buf);
-    }
+    const bool stamps = (ablate & 8192) && tc && tc->persistent();
+    if (stamps && epi != EPI_PATCH) stamps_arm(e, p);
 #endif
     static const int group_env = env_int("MOCR_GEMM_GROUPN", -1);
-    p.group_n = group_env >= 0 ? group_env : group_n;
+    p.group_n = group_env >= 0 ? group_env : c.group_n;
     const double out_b = (epi == EPI_BIAS || epi == EPI_BIAS_GELU) ? sizeof(T) : 4.0;
     const double bytes = ((double)M * K + (double)N * K) * sizeof(T) + (double)M * N * out_b * (epi == EPI_SLAB ? split : 1) +
-                         (epi == EPI_BIAS_RESID ? (double)M * N * 4 : 0) + (lnf && epi == EPI_BIAS_RESID ? (double)M * N * 2 : 0);
-    ProfScope ps(e, name, 2.0 * M * N * K * ybatch, bytes * ybatch);
-    // one barrier per two K-tiles for the fp32-residual GEMMs (r03, M = 50,432: O-proj 137 -> 129 us, FC2 305 -> 302; the
-    // bf16-output GEMMs lose with it: QKV 175 -> 208 us)
-    // 4099 / 4100: the strip schedule forced (whole grid / 8 blocks) - test hooks like 4097
-    if (tile == 4096 || tile == 4097 || tile == 4099 || tile == 4100) {
-        const int blocks = (tile == 4097 || tile == 4100) ? 8 : 0;     // 4097: test hook, 8 blocks walk all the tiles
-        static const int strip_env = env_int("MOCR_GEMM_STRIP", -1);     // -1: strips where they walk fewer rounds (r03, M = 50,432: O-proj 133 -> 113 us, FC2 303 -> 275)
-        const int strip = tile >= 4099 ? 1 : tile == 4097 ? 0 : strip_env;
-        // the bf16-epilogue GEMMs: 1 = the one-barrier-per-two-K-tiles loop with the 64-deep LDS image (K64), 0 = one barrier per
-        // 32-deep K-tile, three K-tiles in flight (r03 first session's choice, when both loops fed on half-line requests)
+                         (epi == EPI_BIAS_RESID ? (double)M * N * 4 : 0) + (c.lnf && epi == EPI_BIAS_RESID ? (double)M * N * 2 : 0);
+    ProfScope ps(e, c.name, 2.0 * M * N * K * ybatch, bytes * ybatch);
+    if (!tc) throw ArgError{"gemm tile must be 64, 128 or 4096", MOCR_ERR_ARG};
+    switch (tc->kind) {
+        case GemmKind::Tile: launch_gemm_tile<T>(e, p, epi, tc->arg, split, ybatch); break;
+        case GemmKind::Persistent: {
+            static const int strip_env = env_int("MOCR_GEMM_STRIP", -1);     // -1: strips where they walk fewer rounds (r03, M = 50,432: O-proj 133 -> 113 us, FC2 303 -> 275)
+            // the bf16-epilogue GEMMs: 1 = the one-barrier-per-two-K-tiles loop with the 64-deep LDS image (K64), 0 = one barrier per
+            // 32-deep K-tile, three K-tiles in flight (r03 first session's choice, when both loops fed on half-line requests)
+            static const int pair_bf16 = env_int("MOCR_GEMM_PAIR_BF16", 1);
+            const bool pair = tc->pair && !(tc->knobs && epi != EPI_BIAS_RESID && !pair_bf16);
+            launch_gemm_pers(e, p, epi, tc->split_dma, pair, tc->blocks, tc->strip < 0 ? strip_env : tc->strip);
+            break;
+        }
 #ifdef MOCR_EXPERIMENTS
-        static const int pair_bf16 = env_int("MOCR_GEMM_PAIR_BF16", 1);
-        if (epi != EPI_BIAS_RESID && !pair_bf16) launch_gemm_pers<true, false>(e, p, epi, blocks, strip);
-        else
+        case GemmKind::Lab256: launch_gemm256(e, p, epi); break;
+        case GemmKind::Wide: launch_gemm_wide(e, p, epi, tc->arg); break;
+        case GemmKind::Wide2: launch_gemm_wide2(e, p, epi); break;
 #endif
-        launch_gemm_pers<true, true>(e, p, epi, blocks, strip);
+        default: throw ArgError{"this GEMM tile code is an A/B kernel of the experiments build (build.py --experiments)", MOCR_ERR_UNSUPPORTED};
     }
 #ifdef MOCR_EXPERIMENTS
-    else if (tile == 4098) launch_gemm_pers<false>(e, p, epi, 0);   // experiment: every wave requests LDS-DMA
-    else if (tile == 4101) launch_gemm_pers<true, true>(e, p, epi, 0);    // experiment: one barrier per two K-tiles
-    else if (tile == 4102) launch_gemm_pers<true, true>(e, p, epi, 8);
-    else if (tile == 4105) launch_gemm_pers<false, true>(e, p, epi, 0);        // experiment: the pair loop with every wave requesting LDS-DMA
-    else if (tile == 4106) launch_gemm_pers<false, true>(e, p, epi, 8);
-    else if (tile == 4103) launch_gemm_pers<true, false>(e, p, epi, 0, 1);      // experiment: strips on the one-barrier-per-K-tile loop
-    else if (tile == 4104) launch_gemm_pers<true, false>(e, p, epi, 8, 1);
-    else if (tile == 2048) launch_gemm_wide2(e, p, epi);
-    else if (tile == 1024) launch_gemm_wide<4>(e, p, epi);
-    else if (tile == 512) launch_gemm_wide<2>(e, p, epi);
-    else if (tile == 256) launch_gemm256(e, p, epi);
-#else
-    else if (tile == 256 || tile == 512 || tile == 1024 || tile == 2048 || tile == 4098)
-        throw ArgError{"this GEMM tile code is an A/B kernel of the experiments build (build.py --experiments)", MOCR_ERR_UNSUPPORTED};
-#endif
-    else if (tile == 128) launch_gemm_epi<T, 128, 128>(e, p, epi, split, ybatch);
-    else if (tile == 64) launch_gemm_epi<T, 64, 64>(e, p, epi, split, ybatch);
-    else throw ArgError{"gemm tile must be 64, 128 or 4096", MOCR_ERR_ARG};
-#ifdef MOCR_EXPERIMENTS
-    if ((ablate & 8192) && tile >= 4096 && stamp_buf) {
-        HIPCHECK(hipStreamSynchronize(e->stream));
-        std::vector<unsigned long long> h(256 * 8 * 4);
-        HIPCHECK(hipMemcpy(h.data(), stamp_buf, h.size() * 8, hipMemcpyDeviceToHost));
-        double s0[2] = {0, 0}, s1[2] = {0, 0}, s2[2] = {0, 0}, pairs = 0;
-        int nb = 0;
-        for (int b = 0; b < 256; ++b) {
-            if (!h[(b * 8) * 4 + 3]) continue;
-            ++nb;
-            pairs += (double)h[(b * 8) * 4 + 3] / 2;
-            for (int w = 0; w < 8; ++w) { s0[w >> 2] += h[(b * 8 + w) * 4]; s1[w >> 2] += h[(b * 8 + w) * 4 + 1]; s2[w >> 2] += h[(b * 8 + w) * 4 + 2]; }
-        }
-        if (nb) {
-            const double n = pairs * 4;      // wave-pairs per role
-            fprintf(stderr, "[stamps] %s: %d blocks, %.0f K-tile pairs each; cycles per pair  DMA waves: work %.0f, DMA wait %.0f, barrier %.0f | store waves: work %.0f, -, barrier %.0f\n",
-                    name, nb, pairs / nb, s0[0] / n, s1[0] / n, s2[0] / n, s0[1] / n, (s1[1] + s2[1]) / n);
-        }
-    }
+    if (stamps) stamps_report(e, c.name);
 #endif
 }
 
@@ -760,6 +793,21 @@ void layernorm(mocr_engine* e, const float* x, const float* g, const float* b, v
     hipLaunchKernelGGL((layernorm_kernel<T, 768>), dim3((M + 3) / 4), dim3(256), 0, e->stream, x, g, b,
                        reinterpret_cast<T*>(out), M, e->cfg.ln_eps);
     HIPCHECK(hipGetLastError());
+}
+
+// The encoder attentions: four kernels with argument lists of their own, so their family is the list of (kernel, LDS) that
+// init_kernel_attrs walks; enc_attention launches each with the same constant.
+constexpr int ENC_SIMPLE_LDS = (200 * 65 + 200 * 64 + 4 * 64 + 4 * 256) * 4;
+#ifdef MOCR_EXPERIMENTS
+constexpr int ENC_MFMA_R02_LDS = ENC_SP * 128 + 64 * ENC_VT_LD * 2;
+#endif
+template <typename T, typename F> void for_each_enc_attn(F&& f) {
+    f(enc_attn_simple_kernel<T>, ENC_SIMPLE_LDS);
+    f(enc_attn2_kernel, EA2_LDS);
+    f(enc_attn_f32_kernel, EAF_LDS);
+#ifdef MOCR_EXPERIMENTS
+    f(enc_attn_mfma_kernel, ENC_MFMA_R02_LDS);
+#endif
 }
 
 template <typename T>
@@ -779,11 +827,10 @@ void enc_attention(mocr_engine* e, const void* qkv, void* ctx, int n, int impl) 
 #ifdef MOCR_EXPERIMENTS
     } else if (impl == 2 && sizeof(T) == 2) {          // r01-r02 kernel (K / V staged through registers), A/B only
         ProfScope ps(e, "enc_attn_mfma_r02", flops, bytes);
-        constexpr int lds = ENC_SP * 128 + 64 * ENC_VT_LD * 2;
         static const int qsplit_env = env_int("MOCR_ENC_ATTN_QSPLIT", 1);
         const int ysplit = (qsplit_env && n * H * 2 <= e->num_cus) ? 2 : 1;
         static const int ablate_env = env_int("MOCR_ENC_ATTN_ABLATE", 0);
-        hipLaunchKernelGGL(enc_attn_mfma_kernel, dim3(n * H, ysplit), dim3(256), lds, e->stream,
+        hipLaunchKernelGGL(enc_attn_mfma_kernel, dim3(n * H, ysplit), dim3(256), ENC_MFMA_R02_LDS, e->stream,
                            reinterpret_cast<const bf16_t*>(qkv), reinterpret_cast<bf16_t*>(ctx), H, 3 * e->D, e->D, ablate_env);
 #endif
     } else if (impl == 1 && sizeof(T) == 4) {          // r04: the parity mode on the f32-input matrix cores
@@ -792,8 +839,7 @@ void enc_attention(mocr_engine* e, const void* qkv, void* ctx, int n, int impl) 
                            reinterpret_cast<float*>(ctx), H, 3 * e->D, e->D);
     } else {
         ProfScope ps(e, "enc_attn_simple", flops, bytes);
-        constexpr int lds = (200 * 65 + 200 * 64 + 4 * 64 + 4 * 256) * 4;
-        hipLaunchKernelGGL((enc_attn_simple_kernel<T>), dim3(n * H), dim3(256), lds, e->stream,
+        hipLaunchKernelGGL((enc_attn_simple_kernel<T>), dim3(n * H), dim3(256), ENC_SIMPLE_LDS, e->stream,
                            reinterpret_cast<const T*>(qkv), reinterpret_cast<T*>(ctx), S, H, 3 * e->D, e->D, 0.125f);
     }
     HIPCHECK(hipGetLastError());
@@ -887,9 +933,11 @@ void run_encoder(mocr_engine* e, const uint8_t* d_gray, int n) {
     // once per group.  128 x 128 tiles: groups of 9 / 12 N-tiles (r01).  Persistent 256 x 256 tiles: groups of 6 (r04: QKV 6 + 3,
     // FC1 6 + 6: the whole 3.4 / 4.5 MiB weight does not fit beside the A panels, and without groups every XCD re-fetches it
     // per round of row-panels - at batch 256 QKV 210 -> 200 us, FC1 337 -> 331 us, one box; tools/r04_groupn_ab.sh)
-    const int gq = ETQ >= 4096 ? 6 : 9, g1 = ET1 >= 4096 ? 6 : 12;
-    gemm<T>(e, "gemm_patch_embed", e->Hb, P * P, w.wpe, w.bpe, e->X, D, nullptr, MPATCH, D, P * P, EPI_PATCH, ET, 1, 0,
-            w.pos_enc, NP);
+    const bool pers_q = tile_is(ETQ, GemmKind::Persistent), pers_1 = tile_is(ET1, GemmKind::Persistent);
+    const int gq = pers_q ? 6 : 9, g1 = pers_1 ? 6 : 12;
+    GemmCall embed = gemm_call("gemm_patch_embed", e->Hb, P * P, w.wpe, w.bpe, e->X, D, MPATCH, D, P * P, EPI_PATCH, ET);
+    embed.pos = w.pos_enc; embed.patches = NP;
+    gemm<T>(e, embed);
     const int impl = (e->cfg.flags & MOCR_FLAG_SIMPLE_ATTENTION) ? 0 : 1;
     // A few crops (the 64 x 64 grid of the two N = 768 GEMMs is at most one block per CU: up to 5 crops): O-proj and FC2
     // are split over K into fp32 slabs - for one crop 12 / 48 K-tiles walked alone by 48 blocks become 4 / 6 K-tiles on
@@ -912,7 +960,8 @@ void run_encoder(mocr_engine* e, const uint8_t* d_gray, int n) {
     bool fold = false;
     if constexpr (sizeof(T) == 2) {
         static const int fold_env = env_int("MOCR_ENC_LN_FOLD", 1);
-        fold = fold_env && !(e->cfg.flags & MOCR_FLAG_NO_LN_FOLD) && ETQ == 4096 && ETO == 4096 && ET1 == 4096 && ET2 == 4096 &&
+        auto folds = [](int code) { const TileCode* t = tile_code(code); return t && t->product_persistent(); };
+        fold = fold_env && !(e->cfg.flags & MOCR_FLAG_NO_LN_FOLD) && folds(ETQ) && folds(ETO) && folds(ET1) && folds(ET2) &&
                D == 768 && w.enc[0].wqkv_f && !e->calib && (e->fold_ok || (e->cfg.flags & MOCR_FLAG_FORCE_LN_FOLD));
     }
     const float* pend_bias = nullptr;      // bias of a split GEMM whose slabs the next LayerNorm has to add to X
@@ -927,47 +976,38 @@ void run_encoder(mocr_engine* e, const uint8_t* d_gray, int n) {
         pend_slabs = 0;
     };
     if (fold) {
-        {
-            ProfScope ps(e, "ln_prep", 0, (double)M * D * 6);
-            hipLaunchKernelGGL((ln_prep_kernel<768>), dim3((M + 3) / 4), dim3(256), 0, e->stream, e->X, reinterpret_cast<bf16_t*>(e->Xn),
-                               e->ln_part, M);
-            HIPCHECK(hipGetLastError());
-        }
-        for (int l = 0; l < e->cfg.enc_layers; ++l) {
-            const EncLayerW& L = w.enc[l];
-            LnFold use_q{e->ln_part, L.sqkv, nullptr}, use_1{e->ln_part, L.s1, nullptr}, emit{e->ln_part, nullptr, e->Xn};
-            gemm<T>(e, "gemm_enc_qkv", e->Xn, D, L.wqkv_f, L.bqkv_f, e->QKV, 3 * D, nullptr, M, 3 * D, D, EPI_BIAS, ETQ, 1, 0, nullptr, 0, nullptr,
-                    gq, nullptr, &use_q);
-            enc_attention<T>(e, e->QKV, e->CTX, n, impl);
-            gemm<T>(e, "gemm_enc_oproj", e->CTX, D, L.wo, L.bo, e->X, D, e->X, M, D, D, EPI_BIAS_RESID, ETO, 1, 0, nullptr, 0, nullptr, 0,
-                    nullptr, &emit);
-            gemm<T>(e, "gemm_enc_fc1", e->Xn, D, L.w1_f, L.b1_f, e->Hb, F, nullptr, M, F, D, EPI_BIAS_GELU, ET1, 1, 0, nullptr, 0, nullptr, g1,
-                    nullptr, &use_1);
-            gemm<T>(e, "gemm_enc_fc2", e->Hb, F, L.w2, L.b2, e->X, D, e->X, M, D, F, EPI_BIAS_RESID, ET2, 1, 0, nullptr, 0, nullptr, 0,
-                    nullptr, &emit);
-        }
-        norm(w.lnfg, w.lnfb, e->ENC);
-        return;
+        ProfScope ps(e, "ln_prep", 0, (double)M * D * 6);
+        hipLaunchKernelGGL((ln_prep_kernel<768>), dim3((M + 3) / 4), dim3(256), 0, e->stream, e->X, reinterpret_cast<bf16_t*>(e->Xn),
+                           e->ln_part, M);
+        HIPCHECK(hipGetLastError());
     }
+    // a layer GEMM split over K: fp32 slabs on the 64 x 64 kernel, the bias left to the LayerNorm launch behind it
+    auto into_slabs = [&](GemmCall c, int split) {
+        pend_bias = c.bias; pend_slabs = split;
+        c.bias = nullptr; c.resid = nullptr; c.out = e->slabs; c.epi = EPI_SLAB; c.tile = 64; c.split = split; c.slab_stride = (long long)M * D;
+        return c;
+    };
     for (int l = 0; l < e->cfg.enc_layers; ++l) {
         const EncLayerW& L = w.enc[l];
-        norm(L.ln1g, L.ln1b, e->Xn);
-        gemm<T>(e, "gemm_enc_qkv", e->Xn, D, L.wqkv, L.bqkv, e->QKV, 3 * D, nullptr, M, 3 * D, D, EPI_BIAS, ETQ, 1, 0, nullptr, 0, nullptr, gq);
+        GemmCall qkv = gemm_call("gemm_enc_qkv", e->Xn, D, L.wqkv, L.bqkv, e->QKV, 3 * D, M, 3 * D, D, EPI_BIAS, ETQ);
+        GemmCall oproj = gemm_call("gemm_enc_oproj", e->CTX, D, L.wo, L.bo, e->X, D, M, D, D, EPI_BIAS_RESID, ETO);
+        GemmCall fc1 = gemm_call("gemm_enc_fc1", e->Xn, D, L.w1, L.b1, e->Hb, F, M, F, D, EPI_BIAS_GELU, ET1);
+        GemmCall fc2 = gemm_call("gemm_enc_fc2", e->Hb, F, L.w2, L.b2, e->X, D, M, D, F, EPI_BIAS_RESID, ET2);
+        qkv.group_n = gq; fc1.group_n = g1; oproj.resid = e->X; fc2.resid = e->X;
+        // folded: QKV / FC1 read the rows' statistics and take the folded weights, O-proj / FC2 emit x as bf16 and its statistics
+        const LnFold use_q{e->ln_part, L.sqkv, nullptr}, use_1{e->ln_part, L.s1, nullptr}, emit{e->ln_part, nullptr, e->Xn};
+        if (fold) {
+            qkv.W = L.wqkv_f; qkv.bias = L.bqkv_f; qkv.lnf = &use_q;
+            fc1.W = L.w1_f; fc1.bias = L.b1_f; fc1.lnf = &use_1;
+            oproj.lnf = &emit; fc2.lnf = &emit;
+        }
+        if (!fold) norm(L.ln1g, L.ln1b, e->Xn);
+        gemm<T>(e, qkv);
         enc_attention<T>(e, e->QKV, e->CTX, n, impl);
-        if (split_o > 1) {
-            gemm<T>(e, "gemm_enc_oproj", e->CTX, D, L.wo, nullptr, e->slabs, D, nullptr, M, D, D, EPI_SLAB, 64, split_o, (long long)M * D);
-            pend_bias = L.bo; pend_slabs = split_o;
-        } else {
-            gemm<T>(e, "gemm_enc_oproj", e->CTX, D, L.wo, L.bo, e->X, D, e->X, M, D, D, EPI_BIAS_RESID, ETO, 1);
-        }
-        norm(L.ln2g, L.ln2b, e->Xn);
-        gemm<T>(e, "gemm_enc_fc1", e->Xn, D, L.w1, L.b1, e->Hb, F, nullptr, M, F, D, EPI_BIAS_GELU, ET1, 1, 0, nullptr, 0, nullptr, g1);
-        if (split_2 > 1) {
-            gemm<T>(e, "gemm_enc_fc2", e->Hb, F, L.w2, nullptr, e->slabs, D, nullptr, M, D, F, EPI_SLAB, 64, split_2, (long long)M * D);
-            pend_bias = L.b2; pend_slabs = split_2;
-        } else {
-            gemm<T>(e, "gemm_enc_fc2", e->Hb, F, L.w2, L.b2, e->X, D, e->X, M, D, F, EPI_BIAS_RESID, ET2, 1);
-        }
+        gemm<T>(e, split_o > 1 ? into_slabs(oproj, split_o) : oproj);
+        if (!fold) norm(L.ln2g, L.ln2b, e->Xn);
+        gemm<T>(e, fc1);
+        gemm<T>(e, split_2 > 1 ? into_slabs(fc2, split_2) : fc2);
     }
     norm(w.lnfg, w.lnfb, e->ENC);
 }
@@ -1019,7 +1059,9 @@ template <typename T>
 int dec_gemm(mocr_engine* e, const char* name, const void* A, int lda, const void* W, int N, int K, int rows) {
     const int kt = 128 / (int)sizeof(T);
     const int split = pick_split(N, K, kt, e->rrows(rows), e->slab_cap / e->Bp);
-    gemm<T>(e, name, A, lda, W, nullptr, e->slabs, N, nullptr, rows, N, K, EPI_SLAB, dec_launch_tile(e, rows), split, (long long)e->Bp * N);
+    GemmCall c = gemm_call(name, A, lda, W, nullptr, e->slabs, N, rows, N, K, EPI_SLAB, dec_launch_tile(e, rows));
+    c.split = split; c.slab_stride = (long long)e->Bp * N;
+    gemm<T>(e, c);
     return split;
 }
 
@@ -1239,25 +1281,47 @@ void dec_attn(mocr_engine* e, int layer, int nslab, int n, const float* bias, in
 // latent_attn_kernel on 32-key tiles, one block per CU, three barriers per tile (kernels_latent.h).  Experiments build,
 // MOCR_LAT_TK = 17: the default kernel on three-slot rings, two blocks per CU (-2 % in the bench); 16: latent_attn_kernel on
 // 16-key tiles, two blocks per CU (the first half of r04; equal to 17 within noise).
+struct LatentArgs { bool self; int v; };      // v: TK of latent_attn_kernel, NST of latent_attnT_kernel, unused (0) by the fp8 kernels
+constexpr bool operator==(const LatentArgs& a, const LatentArgs& b) { return a.self == b.self && a.v == b.v; }
+struct LatentFamily {          // latent_attn_kernel<SELF, TK>
+    using Args = LatentArgs;
+    using Kernel = void (*)(LatentParams);
+    static constexpr Args forms[] = {{true, 32}, {false, 32}, LAB_ONLY({true, 16}, {false, 16})};
+    template <size_t I> static constexpr Kernel kernel() { return latent_attn_kernel<forms[I].self, forms[I].v>; }
+    static constexpr int lds(const Args& a) { return a.v == 32 ? LatCfg<32>::LDS : LatCfg<16>::LDS; }
+};
+struct LatentTFamily {         // latent_attnT_kernel<SELF, NST>
+    using Args = LatentArgs;
+    using Kernel = void (*)(LatentParams);
+    static constexpr Args forms[] = {{true, 2}, {false, 2}, LAB_ONLY({true, 3}, {false, 3})};
+    template <size_t I> static constexpr Kernel kernel() { return latent_attnT_kernel<forms[I].self, forms[I].v>; }
+    static constexpr int lds(const Args& a) { return LATT_LDS_OF(a.v); }
+};
+struct Latent8Family {         // latent_attn_fp8_kernel<SELF>
+    using Args = LatentArgs;
+    using Kernel = void (*)(Latent8Params);
+    static constexpr Args forms[] = {{true, 0}, {false, 0}};
+    template <size_t I> static constexpr Kernel kernel() { return latent_attn_fp8_kernel<forms[I].self>; }
+    static constexpr int lds(const Args&) { return LAT8_LDS; }
+};
+struct LatentT8Family {        // latent_attnT8_kernel<SELF>
+    using Args = LatentArgs;
+    using Kernel = void (*)(Latent8Params);
+    static constexpr Args forms[] = {{true, 0}, {false, 0}};
+    template <size_t I> static constexpr Kernel kernel() { return latent_attnT8_kernel<forms[I].self>; }
+    static constexpr int lds(const Args&) { return LATT8_LDS; }
+};
+
 void launch_latent(mocr_engine* e, bool self, const LatentParams& p) {
     static const int lat_blocks = env_int("MOCR_LAT_BLOCKS", 0);      // persistent blocks (experiments; 0: one or two per CU by tile)
     const int per_cu = e->lat_tk == 32 ? 1 : e->lat_tk == 18 ? 3 : 2;
     const int grid = std::min(p.rows, lat_blocks > 0 ? lat_blocks : per_cu * e->num_cus);
-    if (e->lat_tk == 18) {          // the default: three blocks per CU on two-slot rings
-        if (self) hipLaunchKernelGGL((latent_attnT_kernel<true, 2>), dim3(grid), dim3(256), LATT_LDS_OF(2), e->stream, p);
-        else hipLaunchKernelGGL((latent_attnT_kernel<false, 2>), dim3(grid), dim3(256), LATT_LDS_OF(2), e->stream, p);
-#ifdef MOCR_EXPERIMENTS
-    } else if (e->lat_tk == 17) {
-        if (self) hipLaunchKernelGGL(latent_attnT_kernel<true>, dim3(grid), dim3(256), LATT_LDS, e->stream, p);
-        else hipLaunchKernelGGL(latent_attnT_kernel<false>, dim3(grid), dim3(256), LATT_LDS, e->stream, p);
-    } else if (e->lat_tk == 16) {
-        if (self) hipLaunchKernelGGL((latent_attn_kernel<true, 16>), dim3(grid), dim3(256), LatCfg<16>::LDS, e->stream, p);
-        else hipLaunchKernelGGL((latent_attn_kernel<false, 16>), dim3(grid), dim3(256), LatCfg<16>::LDS, e->stream, p);
-#endif
-    } else {
-        if (self) hipLaunchKernelGGL((latent_attn_kernel<true, 32>), dim3(grid), dim3(256), LatCfg<32>::LDS, e->stream, p);
-        else hipLaunchKernelGGL((latent_attn_kernel<false, 32>), dim3(grid), dim3(256), LatCfg<32>::LDS, e->stream, p);
-    }
+    // lat_tk 18 (the default) / 17: latent_attnT_kernel on two / three ring slots; 16: latent_attn_kernel on 16-key tiles; anything
+    // else, and whatever this build does not have: latent_attn_kernel on 32-key tiles
+    auto f = find_form<LatentTFamily>({self, 20 - e->lat_tk});
+    if (!f.kernel) f = find_form<LatentFamily>({self, e->lat_tk});
+    if (!f.kernel) f = find_form<LatentFamily>({self, 32});
+    hipLaunchKernelGGL(f.kernel, dim3(grid), dim3(256), f.lds, e->stream, p);
     HIPCHECK(hipGetLastError());
 }
 
@@ -1266,15 +1330,10 @@ void launch_latent(mocr_engine* e, bool self, const LatentParams& p) {
 // on a five-slot ring, one block per CU).
 void launch_latent8(mocr_engine* e, bool self, const Latent8Params& p) {
     static const int lat_blocks = env_int("MOCR_LAT_BLOCKS", 0);
-    if (e->lat_tk == 32) {
-        const int grid = std::min(p.rows, lat_blocks > 0 ? lat_blocks : e->num_cus);
-        if (self) hipLaunchKernelGGL(latent_attn_fp8_kernel<true>, dim3(grid), dim3(256), LAT8_LDS, e->stream, p);
-        else hipLaunchKernelGGL(latent_attn_fp8_kernel<false>, dim3(grid), dim3(256), LAT8_LDS, e->stream, p);
-    } else {
-        const int grid = std::min(p.rows, lat_blocks > 0 ? lat_blocks : 2 * e->num_cus);
-        if (self) hipLaunchKernelGGL(latent_attnT8_kernel<true>, dim3(grid), dim3(256), LATT8_LDS, e->stream, p);
-        else hipLaunchKernelGGL(latent_attnT8_kernel<false>, dim3(grid), dim3(256), LATT8_LDS, e->stream, p);
-    }
+    const bool tile32 = e->lat_tk == 32;
+    const int grid = std::min(p.rows, lat_blocks > 0 ? lat_blocks : (tile32 ? 1 : 2) * e->num_cus);
+    const auto f = tile32 ? find_form<Latent8Family>({self, 0}) : find_form<LatentT8Family>({self, 0});
+    hipLaunchKernelGGL(f.kernel, dim3(grid), dim3(256), f.lds, e->stream, p);
     HIPCHECK(hipGetLastError());
 }
 
@@ -1332,10 +1391,21 @@ void latent_attn(mocr_engine* e, const LatentBlockArgs& a) {
 // The fused query launch (kernels_qqt.h): blocks of 64 rows for batches of up to MOCR_QQT_BM64_ROWS rows (a 16-KiB K-tile, seven
 // in flight, twice the blocks: r04, tools/r04_qqt_bm_ab.sh), of 128 rows above - there every CU has a block either way and the
 // 128-row block reads each weight tile for twice the rows.  `regime_rows` = the row count the choice is made by.
+struct QqtArgs { int bm; };
+constexpr bool operator==(const QqtArgs& a, const QqtArgs& b) { return a.bm == b.bm; }
+struct QqtFamily {             // dec_qqt_kernel<BM>
+    using Args = QqtArgs;
+    using Kernel = void (*)(QqtParams);
+    static constexpr Args forms[] = {{64}, {128}};
+    template <size_t I> static constexpr Kernel kernel() { return dec_qqt_kernel<forms[I].bm>; }
+    static constexpr int lds(const Args&) { return 160 * 1024; }      // the limit: a launch asks for QqtCfg<BM>::LDS (MOCR_QQT_LDS: more)
+};
+
 void launch_qqt(mocr_engine* e, const QqtParams& q, int n, int regime_rows) {
     static const int bm64_rows = env_int("MOCR_QQT_BM64_ROWS", 1280);
-    if (regime_rows <= bm64_rows) hipLaunchKernelGGL(dec_qqt_kernel<64>, dim3((n + 63) / 64, 12), dim3(256), QqtCfg<64>::LDS, e->stream, q);
-    else hipLaunchKernelGGL(dec_qqt_kernel<128>, dim3((n + 127) / 128, 12), dim3(256), env_int("MOCR_QQT_LDS", QQT_LDS), e->stream, q);
+    const int bm = regime_rows <= bm64_rows ? 64 : 128;
+    const int lds = bm == 64 ? QqtCfg<64>::LDS : env_int("MOCR_QQT_LDS", QQT_LDS);
+    hipLaunchKernelGGL(find_form<QqtFamily>({bm}).kernel, dim3((n + bm - 1) / bm, 12), dim3(256), lds, e->stream, q);
     HIPCHECK(hipGetLastError());
 }
 
@@ -1345,6 +1415,12 @@ void launch_qqt(mocr_engine* e, const QqtParams& q, int n, int regime_rows) {
 void launch_latent_block(mocr_engine* e, const LatentBlockArgs& a) {
     using T = bf16_t;
     const int D = e->D, n = a.n;
+    auto latent_ctx = [&] {          // ctx = Et Wv^T + bv, one GEMM per head
+        HeadBatch hc; hc.heads = e->H; hc.a_yoff = D; hc.w_yoff = (long long)64 * D; hc.o_yoff = 64; hc.b_yoff = 64; hc.ldw = D;
+        GemmCall c = gemm_call("gemm_dec_ctx", a.et, 16 * D, a.wv, a.bv, a.ctx, D, n, 64, D, EPI_BIAS, 64);
+        c.hb = &hc;
+        gemm<T>(e, c);
+    };
     // fat batches: q and Qt in one launch (kernels_qqt.h), 37 us instead of 16 + 31 at 4096 rows; bit-identical to the
     // two-launch path.  MOCR_DEC_QQT_ROWS = rows from which it is used (0 = never)
     // (r04, tools/r04_qqt_rows_ab.sh, isolated batch, two launches / fused: 512 rows 136.2 / 134.9 ms, 768 rows 165.4 / 163.5, below
@@ -1362,18 +1438,18 @@ void launch_latent_block(mocr_engine* e, const LatentBlockArgs& a) {
             launch_qqt(e, q, n, neutral_by_rows ? n : e->rrows(n));
         }
         latent_attn(e, a);
-        HeadBatch hc2; hc2.heads = e->H; hc2.a_yoff = D; hc2.w_yoff = (long long)64 * D; hc2.o_yoff = 64; hc2.b_yoff = 64; hc2.ldw = D;
-        gemm<T>(e, "gemm_dec_ctx", a.et, 16 * D, a.wv, a.bv, a.ctx, D, nullptr, n, 64, D, EPI_BIAS, 64, 1, 0, nullptr, 0, &hc2);
+        latent_ctx();
         return;
     }
     static const int qtile = env_int("MOCR_DEC_QTILE", 64), qttile_env = env_int("MOCR_DEC_QTTILE", 0);
     const int qttile = qttile_env ? qttile_env : (e->rrows(n) >= 1024 ? 128 : 64);      // Qt is output-write bound: fewer, fatter blocks
-    gemm<T>(e, "gemm_dec_q", a.xin, D, a.wq, a.bq, a.q, D, nullptr, n, D, D, EPI_BIAS, qtile, 1);
+    gemm<T>(e, gemm_call("gemm_dec_q", a.xin, D, a.wq, a.bq, a.q, D, n, D, D, EPI_BIAS, qtile));
     HeadBatch hq; hq.heads = e->H; hq.a_yoff = 64; hq.w_yoff = 64; hq.o_yoff = D; hq.b_yoff = 0; hq.ldw = D;
-    gemm<T>(e, "gemm_dec_qt", a.q, D, a.wkT, e->w.zero_bias, a.qt, 16 * D, nullptr, n, D, 64, EPI_BIAS, qttile, 1, 0, nullptr, 0, &hq);
+    GemmCall qt = gemm_call("gemm_dec_qt", a.q, D, a.wkT, e->w.zero_bias, a.qt, 16 * D, n, D, 64, EPI_BIAS, qttile);
+    qt.hb = &hq;
+    gemm<T>(e, qt);
     latent_attn(e, a);
-    HeadBatch hc; hc.heads = e->H; hc.a_yoff = D; hc.w_yoff = (long long)64 * D; hc.o_yoff = 64; hc.b_yoff = 64; hc.ldw = D;
-    gemm<T>(e, "gemm_dec_ctx", a.et, 16 * D, a.wv, a.bv, a.ctx, D, nullptr, n, 64, D, EPI_BIAS, 64, 1, 0, nullptr, 0, &hc);
+    latent_ctx();
 }
 
 // The decode step's latent block of one layer: keys = the layer's cached input rows (self, context t + 1) or the encoder
@@ -1403,26 +1479,42 @@ void latent_block(mocr_engine* e, bool self, int layer, int n, int t, const void
     launch_latent_block(e, latent_block_args(e, self, layer, n, t, xin, wq, bq, wkT, wv, bv));
 }
 
-template <int PRO, int EPI>
-void smallm_gemm(mocr_engine* e, const char* name, SmallMParams p) {
+// smallm_gemm_kernel<PRO, EPI, MT, KS> (kernels_smallm.h): the (prologue, epilogue) pairs of the small-batch step x one / two
+// 16-row tiles x K = 768 / 3072 (KS = 3 / 12; the LayerNorm prologue has K = 768 only).
+struct SmallMArgs { int pro, epi, mt, ks; };
+constexpr bool operator==(const SmallMArgs& a, const SmallMArgs& b) { return a.pro == b.pro && a.epi == b.epi && a.mt == b.mt && a.ks == b.ks; }
+constexpr std::array<SmallMArgs, 14> smallm_forms() {
+    constexpr int pairs[][2] = {{SM_PRO_PLAIN, SM_EPI_RAW}, {SM_PRO_LN, SM_EPI_RAW}, {SM_PRO_PLAIN, SM_EPI_SUM}, {SM_PRO_LN, SM_EPI_GELU_BF16},
+                                {SM_PRO_LN, SM_EPI_GELU_F32}};
+    std::array<SmallMArgs, 14> a{};
+    int n = 0;
+    for (const auto& pe : pairs)
+        for (int mt : {1, 2})
+            for (int ks : {3, 12})
+                if (ks == 3 || pe[0] == SM_PRO_PLAIN) a[n++] = SmallMArgs{pe[0], pe[1], mt, ks};
+    return a;
+}
+struct SmallMFamily {
+    using Args = SmallMArgs;
+    using Kernel = void (*)(SmallMParams);
+    static constexpr std::array<Args, 14> forms = smallm_forms();
+    static_assert(forms[13].mt == 2, "smallm_forms fills its table");
+    template <size_t I> static constexpr Kernel kernel() { constexpr Args a = forms[I]; return smallm_gemm_kernel<a.pro, a.epi, a.mt, a.ks>; }
+    static constexpr int lds(const Args& a) { return SM_LDS(a.pro, a.mt); }
+};
+static bool smallm_pair_exists(int pro, int epi) {
+    return std::any_of(SmallMFamily::forms.begin(), SmallMFamily::forms.end(), [&](const SmallMArgs& f) { return f.pro == pro && f.epi == epi; });
+}
+
+void smallm_gemm(mocr_engine* e, const char* name, int pro, int epi, SmallMParams p) {
     p.eps = e->cfg.ln_eps;
     const int mt = (p.rows + 15) / 16;
-    if (mt < 1 || mt > 2 || p.N % SM_NT || (p.K != 768 && p.K != 3072) || (PRO == SM_PRO_LN && p.K != 768))
+    if (mt < 1 || mt > 2 || p.N % SM_NT || (p.K != 768 && p.K != 3072) || (pro == SM_PRO_LN && p.K != 768))
         throw ArgError{"small-batch GEMM: unsupported shape", MOCR_ERR_UNSUPPORTED};
+    const auto f = find_form<SmallMFamily>({pro, epi, mt, p.K / 256});
+    if (!f.kernel) throw ArgError{"small-batch GEMM: (pro, epi) is not a pair the small-batch decode step launches", MOCR_ERR_UNSUPPORTED};
     ProfScope ps(e, name, 2.0 * p.rows * p.N * p.K, (double)p.N * p.K * 2);
-    const dim3 grid(p.N / SM_NT), block(64 * SM_NW);
-    if constexpr (PRO == SM_PRO_LN) {
-        if (mt == 1) hipLaunchKernelGGL((smallm_gemm_kernel<PRO, EPI, 1, 3>), grid, block, SM_LDS(PRO, 1), e->stream, p);
-        else hipLaunchKernelGGL((smallm_gemm_kernel<PRO, EPI, 2, 3>), grid, block, SM_LDS(PRO, 2), e->stream, p);
-    } else {
-        if (p.K == 768) {
-            if (mt == 1) hipLaunchKernelGGL((smallm_gemm_kernel<PRO, EPI, 1, 3>), grid, block, SM_LDS(PRO, 1), e->stream, p);
-            else hipLaunchKernelGGL((smallm_gemm_kernel<PRO, EPI, 2, 3>), grid, block, SM_LDS(PRO, 2), e->stream, p);
-        } else {
-            if (mt == 1) hipLaunchKernelGGL((smallm_gemm_kernel<PRO, EPI, 1, 12>), grid, block, SM_LDS(PRO, 1), e->stream, p);
-            else hipLaunchKernelGGL((smallm_gemm_kernel<PRO, EPI, 2, 12>), grid, block, SM_LDS(PRO, 2), e->stream, p);
-        }
-    }
+    hipLaunchKernelGGL(f.kernel, dim3(p.N / SM_NT), dim3(64 * SM_NW), f.lds, e->stream, p);
     HIPCHECK(hipGetLastError());
 }
 
@@ -1440,18 +1532,18 @@ void decode_step_smallm(mocr_engine* e, const DecState& st, const DecMode& m, in
         const DecLayerW* P = l ? &w.dec[l - 1] : nullptr;        // the layer whose LayerNorm 3 produces this layer's input
         SmallMParams q{};
         q.rows = n; q.K = D; q.w = W(L.wqkv); q.N = 3 * D; q.out = e->slabs; q.ldo = 3 * D;
-        if (!P) { q.a_bf16 = W(e->x_t); smallm_gemm<SM_PRO_PLAIN, SM_EPI_RAW>(e, "sm_qkv", q); }
-        else { q.a_f32 = e->x_f32; q.ln_g = P->ln3g; q.ln_b = P->ln3b; q.stats_out = st3; smallm_gemm<SM_PRO_LN, SM_EPI_RAW>(e, "sm_qkv", q); }
+        if (!P) { q.a_bf16 = W(e->x_t); smallm_gemm(e, "sm_qkv", SM_PRO_PLAIN, SM_EPI_RAW, q); }
+        else { q.a_f32 = e->x_f32; q.ln_g = P->ln3g; q.ln_b = P->ln3b; q.stats_out = st3; smallm_gemm(e, "sm_qkv", SM_PRO_LN, SM_EPI_RAW, q); }
         dec_attn<T, true>(e, l, 1, n, L.bqkv, t + 1);
         SmallMParams o{};
         o.rows = n; o.K = D; o.a_bf16 = W(e->ctx_t); o.w = W(L.wo); o.N = D; o.bias = L.bo; o.out = e->a_f32; o.ldo = D;
         o.resid = e->x_f32;
         if (P) { o.resid_stats = st3; o.resid_g = P->ln3g; o.resid_b = P->ln3b; }
-        smallm_gemm<SM_PRO_PLAIN, SM_EPI_SUM>(e, "sm_proj", o);                       // s1 = ctx Wo^T + bo + layer input
+        smallm_gemm(e, "sm_proj", SM_PRO_PLAIN, SM_EPI_SUM, o);                       // s1 = ctx Wo^T + bo + layer input
         SmallMParams c{};
         c.rows = n; c.K = D; c.a_f32 = e->a_f32; c.ln_g = L.ln1g; c.ln_b = L.ln1b; c.stats_out = st1;
         c.w = W(L.wqc); c.N = D; c.out = e->slabs; c.ldo = D;
-        smallm_gemm<SM_PRO_LN, SM_EPI_RAW>(e, "sm_qc", c);
+        smallm_gemm(e, "sm_qc", SM_PRO_LN, SM_EPI_RAW, c);
         if (m.positions && l + 1 == e->cfg.dec_layers) {      // token positions: the rows sm_qc's prologue normalised, recorded
             ProfScope ps(e, "pos_hist_ln", 0, (double)n * D * 6);
             hipLaunchKernelGGL((hist_ln_rows_kernel<T>), dim3((n + 15) / 16), dim3(256), 0, e->stream, (const float*)e->a_f32, (const float*)L.ln1g,
@@ -1463,25 +1555,25 @@ void decode_step_smallm(mocr_engine* e, const DecState& st, const DecMode& m, in
         SmallMParams oc{};
         oc.rows = n; oc.K = D; oc.a_bf16 = W(e->ctx_t); oc.w = W(L.woc); oc.N = D; oc.bias = L.boc; oc.out = e->c_f32; oc.ldo = D;
         oc.resid = e->a_f32; oc.resid_stats = st1; oc.resid_g = L.ln1g; oc.resid_b = L.ln1b;
-        smallm_gemm<SM_PRO_PLAIN, SM_EPI_SUM>(e, "sm_proj", oc);                      // s2 = ctx Woc^T + boc + LN1(s1)
+        smallm_gemm(e, "sm_proj", SM_PRO_PLAIN, SM_EPI_SUM, oc);                      // s2 = ctx Woc^T + boc + LN1(s1)
         SmallMParams f1{};
         f1.rows = n; f1.K = D; f1.a_f32 = e->c_f32; f1.ln_g = L.ln2g; f1.ln_b = L.ln2b; f1.stats_out = st2;
         f1.w = W(L.w1); f1.N = F; f1.bias = L.b1; f1.out = e->h_t; f1.ldo = F;
-        smallm_gemm<SM_PRO_LN, SM_EPI_GELU_BF16>(e, "sm_fc1", f1);
+        smallm_gemm(e, "sm_fc1", SM_PRO_LN, SM_EPI_GELU_BF16, f1);
         SmallMParams f2{};
         f2.rows = n; f2.K = F; f2.a_bf16 = W(e->h_t); f2.w = W(L.w2); f2.N = D; f2.bias = L.b2; f2.out = e->x_f32; f2.ldo = D;
         f2.resid = e->c_f32; f2.resid_stats = st2; f2.resid_g = L.ln2g; f2.resid_b = L.ln2b;
-        smallm_gemm<SM_PRO_PLAIN, SM_EPI_SUM>(e, "sm_fc2", f2);                       // s3 = h W2^T + b2 + LN2(s2)
+        smallm_gemm(e, "sm_fc2", SM_PRO_PLAIN, SM_EPI_SUM, f2);                       // s3 = h W2^T + b2 + LN2(s2)
     }
     const DecLayerW& Z = w.dec[e->cfg.dec_layers - 1];
     SmallMParams tr{};
     tr.rows = n; tr.K = D; tr.a_f32 = e->x_f32; tr.ln_g = Z.ln3g; tr.ln_b = Z.ln3b;
     tr.w = W(w.wt); tr.N = D; tr.bias = w.bt; tr.out = e->a_f32; tr.ldo = D;
-    smallm_gemm<SM_PRO_LN, SM_EPI_GELU_F32>(e, "sm_transform", tr);                   // gelu(LN3(s3) Wt^T + bt), pre-LayerNorm
+    smallm_gemm(e, "sm_transform", SM_PRO_LN, SM_EPI_GELU_F32, tr);                   // gelu(LN3(s3) Wt^T + bt), pre-LayerNorm
     SmallMParams v{};
     v.rows = n; v.K = D; v.a_f32 = e->a_f32; v.ln_g = w.lntg; v.ln_b = w.lntb;
     v.w = W(w.wv); v.N = e->V; v.out = e->slabs; v.ldo = e->V;
-    smallm_gemm<SM_PRO_LN, SM_EPI_RAW>(e, "sm_vocab", v);
+    smallm_gemm(e, "sm_vocab", SM_PRO_LN, SM_EPI_RAW, v);
     dec_token<T, false>(e, st, 1, n);
 }
 
@@ -1521,7 +1613,7 @@ void decode_step(mocr_engine* e, const DecState& st, const DecMode& m, int n, in
         ns = dec_gemm<T>(e, "gemm_dec_proj", e->ctx_t, D, L.woc, D, D, n);
         dec_add_ln<T>(e, ns, D, L.boc, e->a_f32, L.ln2g, L.ln2b, e->c_f32, e->c_t, n, false);
         if (pick_split(F, D, 128 / (int)sizeof(T), rn, e->slab_cap / e->Bp) == 1) {
-            gemm<T>(e, "gemm_dec_fc1", e->c_t, D, L.w1, L.b1, e->h_t, F, nullptr, n, F, D, EPI_BIAS_GELU, dec_launch_tile(e, n), 1);
+            gemm<T>(e, gemm_call("gemm_dec_fc1", e->c_t, D, L.w1, L.b1, e->h_t, F, n, F, D, EPI_BIAS_GELU, dec_launch_tile(e, n)));
         } else {
             ns = dec_gemm<T>(e, "gemm_dec_fc1", e->c_t, D, L.w1, F, D, n);
             launch_dec_bias_gelu<T>(e, e->slabs, ns, (long long)e->Bp * F, L.b1, e->h_t, n, F);
@@ -1537,7 +1629,7 @@ void decode_step(mocr_engine* e, const DecState& st, const DecMode& m, int n, in
     // to (max, column) and the token kernel picks among V/tile candidates: the [n, V] fp32 logits (100 MB at 4096
     // rows) are neither written nor read.  acc + bias is the same fp32 value either way, so the argmax is identical.
     const int vt = dec_launch_tile(e, n);
-    if (!st.logits_out && !(e->cfg.flags & MOCR_FLAG_NO_FUSED_ARGMAX) && (vt == 64 || vt == 128) &&
+    if (!st.logits_out && !(e->cfg.flags & MOCR_FLAG_NO_FUSED_ARGMAX) && tile_is(vt, GemmKind::Tile) &&
         pick_split(e->V, D, 128 / (int)sizeof(T), rn, e->slab_cap / e->Bp) == 1) {
         // (a scored batch also keeps every tile's sum of exp(logit - tile max): EPI_ARGMAX_LSE, same max / column; an
         // alternatives batch every tile's four best as well: EPI_TOPK; a constrained batch the masked form of either: EPI_*_M)
@@ -1547,8 +1639,9 @@ void decode_step(mocr_engine* e, const DecState& st, const DecMode& m, int n, in
         if (m.level >= 2) { lm.top_val = e->top_val; lm.top_idx = e->top_idx; }
         if (m.mask) lm.mask = TokMask{st.tok_mask, st.set_of_row, st.rowmap};
         if (m.prefix) lm.target = TokTarget{st.prefix, st.prefix_len, st.prefix_ld, st.step, e->tgt_val};
-        gemm<T>(e, m.head_name(), e->z_t, D, w.wv, w.bv, e->cand_val, e->V, nullptr, n, e->V, D, m.epilogue(), vt, 1, 0, nullptr, 0, nullptr,
-                0, &lm);
+        GemmCall head = gemm_call(m.head_name(), e->z_t, D, w.wv, w.bv, e->cand_val, e->V, n, e->V, D, m.epilogue(), vt);
+        head.lm = &lm;
+        gemm<T>(e, head);
         dec_token<T, false>(e, st, 1, n, e->V / vt);
     } else {
         ns = dec_gemm<T>(e, "gemm_dec_vocab", e->z_t, D, w.wv, e->V, D, n);
@@ -1562,9 +1655,8 @@ void run_cross_kv(mocr_engine* e, int n) {
     static const int enc_tile_env = env_int("MOCR_ENC_TILE", 0);
     const bool few_blocks = (long long)((M + 127) / 128) * (e->NCKV / 128) * 5 <= 4LL * e->num_cus;      // see run_encoder
     const bool big = sizeof(T) == 2 && (long long)((M + 255) / 256) * (e->NCKV / 256) >= e->num_cus && e->NCKV % 256 == 0;
-    const int ET = enc_tile_env ? enc_tile_env : big ? 4096 : few_blocks ? 64 : 128;
-    gemm<T>(e, "gemm_cross_kv", e->ENC, e->D, e->w.wckv, e->w.bckv, e->CKV, e->NCKV, nullptr, M, e->NCKV, e->D,
-            EPI_BIAS, ET, 1);
+    const int ET = enc_tile_env ? enc_tile_env : big ? TILE_PERSISTENT : few_blocks ? 64 : 128;
+    gemm<T>(e, gemm_call("gemm_cross_kv", e->ENC, e->D, e->w.wckv, e->w.bckv, e->CKV, e->NCKV, M, e->NCKV, e->D, EPI_BIAS, ET));
 }
 
 // fp8 attention: the batch's encoder output as e4m3 rows (static scale), once per batch
@@ -1576,104 +1668,14 @@ void quantize_enc(mocr_engine* e, int n) {
     HIPCHECK(hipGetLastError());
 }
 
-// The epilogues gemm_kernel is built with (launch_gemm_epi), as integral constants.
-template <typename F> void for_each_gemm_epilogue(F&& f) {
-    auto each = [&](auto... epi) { (f(epi), ...); };
-    each(std::integral_constant<int, EPI_SLAB>{}, std::integral_constant<int, EPI_BIAS>{}, std::integral_constant<int, EPI_BIAS_GELU>{},
-         std::integral_constant<int, EPI_BIAS_RESID>{}, std::integral_constant<int, EPI_PATCH>{}, std::integral_constant<int, EPI_BIAS_F32>{},
-         std::integral_constant<int, EPI_ARGMAX>{}, std::integral_constant<int, EPI_ARGMAX_LSE>{}, std::integral_constant<int, EPI_TOPK>{},
-         std::integral_constant<int, EPI_ARGMAX_M>{}, std::integral_constant<int, EPI_ARGMAX_LSE_M>{}, std::integral_constant<int, EPI_TOPK_M>{});
-}
-
-// Raise the dynamic-LDS limit of every kernel that needs it (done once, outside any capture).
+// Raise the dynamic-LDS limit of every form of every kernel family (done once, at creation: outside any capture, from the
+// calling thread - decode steps are launched inside stream capture and from several lane threads).
 template <typename T> void init_kernel_attrs() {
-    constexpr int l128 = 2 * (128 + 128) * 128, l64 = 2 * (64 + 64) * 128;
-    for_each_gemm_epilogue([&](auto epi) {
-        constexpr int E = decltype(epi)::value;
-        set_max_lds(gemm_kernel<T, 128, 128, E>, l128);
-        set_max_lds(gemm_kernel<T, 64, 64, E, 2>, l64);
-        set_max_lds(gemm_kernel<T, 128, 128, E, 4>, 2 * l128);
-        set_max_lds(gemm_kernel<T, 64, 64, E, 4>, 2 * l64);
-        if constexpr (E == EPI_ARGMAX_LSE_M || E == EPI_TOPK_M) {          // ... and with a forced prefix's target column
-            set_max_lds(gemm_kernel<T, 128, 128, E, 2, true>, l128);
-            set_max_lds(gemm_kernel<T, 64, 64, E, 2, true>, l64);
-            set_max_lds(gemm_kernel<T, 128, 128, E, 4, true>, 2 * l128);
-            set_max_lds(gemm_kernel<T, 64, 64, E, 4, true>, 2 * l64);
-        }
-    });
-    set_max_lds(enc_attn_simple_kernel<T>, (200 * 65 + 200 * 64 + 4 * 64 + 4 * 256) * 4);
-    set_max_lds(enc_attn2_kernel, EA2_LDS);
-    set_max_lds(enc_attn_f32_kernel, EAF_LDS);
+    raise_lds<TileFamily<T>, PersFamily, QqtFamily, SmallMFamily, LatentFamily, LatentTFamily, Latent8Family, LatentT8Family>();
+    for_each_enc_attn<T>([](auto kernel, int lds) { set_max_lds(kernel, lds); });
 #ifdef MOCR_EXPERIMENTS
-    set_max_lds(enc_attn_mfma_kernel, ENC_SP * 128 + 64 * ENC_VT_LD * 2);
+    raise_lds<Gemm256Family, WideFamily, Wide2Family>();
 #endif
-    set_max_lds(dec_qqt_kernel<128>, 160 * 1024);
-    set_max_lds(dec_qqt_kernel<64>, 160 * 1024);
-#ifdef MOCR_EXPERIMENTS
-    constexpr int l256 = 3 * (256 + 128) * 128;
-    set_max_lds(gemm_wide_kernel<EPI_BIAS, 2>, 3 * (256 + 128) * 64);
-    set_max_lds(gemm_wide_kernel<EPI_BIAS_GELU, 2>, 3 * (256 + 128) * 64);
-    set_max_lds(gemm_wide_kernel<EPI_BIAS_RESID, 2>, 3 * (256 + 128) * 64);
-    set_max_lds(gemm_wide_kernel<EPI_BIAS, 4>, 3 * (256 + 256) * 64);
-    set_max_lds(gemm_wide_kernel<EPI_BIAS_GELU, 4>, 3 * (256 + 256) * 64);
-    set_max_lds(gemm_wide_kernel<EPI_BIAS_RESID, 4>, 3 * (256 + 256) * 64);
-    set_max_lds(gemm_wide2_kernel<EPI_BIAS>, 4 * (256 + 256) * 64);
-    set_max_lds(gemm_wide2_kernel<EPI_BIAS_GELU>, 4 * (256 + 256) * 64);
-    set_max_lds(gemm_wide2_kernel<EPI_BIAS_RESID>, 4 * (256 + 256) * 64);
-#endif
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_RESID, true, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_RESID, true, true, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_RESID, true, true, true, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_RESID, true, true, false, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS, true, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_GELU, true, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS, true, true, false, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_GELU, true, true, false, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS, true, true, true, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_GELU, true, true, true, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS, true, true, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_GELU, true, true, true>, PERS_LDS);
-#ifdef MOCR_EXPERIMENTS
-    // (the one-barrier-per-K-tile loop on the 32-deep image: A/B partner of the pair loop)
-    set_max_lds(gemm_pers_kernel<EPI_BIAS, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_GELU, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_RESID, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS, true, false, false, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_GELU, true, false, false, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS, true, false, true, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_GELU, true, false, true, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS, true, false, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_GELU, true, false, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_RESID, true, false, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS, false, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_GELU, false, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_RESID, false, true>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS, false>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_GELU, false>, PERS_LDS);
-    set_max_lds(gemm_pers_kernel<EPI_BIAS_RESID, false>, PERS_LDS);
-    set_max_lds(gemm256_kernel<EPI_BIAS>, l256);
-    set_max_lds(gemm256_kernel<EPI_BIAS_GELU>, l256);
-    set_max_lds(gemm256_kernel<EPI_BIAS_RESID>, l256);
-    set_max_lds(gemm256_kernel<EPI_PATCH>, l256);
-    set_max_lds(gemm256_kernel<EPI_BIAS_F32>, l256);
-#endif
-    set_max_lds(smallm_gemm_kernel<SM_PRO_LN, SM_EPI_RAW, 2, 3>, SM_LDS(SM_PRO_LN, 2));
-    set_max_lds(smallm_gemm_kernel<SM_PRO_LN, SM_EPI_GELU_BF16, 2, 3>, SM_LDS(SM_PRO_LN, 2));
-    set_max_lds(smallm_gemm_kernel<SM_PRO_LN, SM_EPI_GELU_F32, 2, 3>, SM_LDS(SM_PRO_LN, 2));
-    set_max_lds(latent_attn_kernel<true, 32>, LatCfg<32>::LDS);
-    set_max_lds(latent_attn_kernel<false, 32>, LatCfg<32>::LDS);
-#ifdef MOCR_EXPERIMENTS
-    set_max_lds(latent_attn_kernel<true, 16>, LatCfg<16>::LDS);
-    set_max_lds(latent_attn_kernel<false, 16>, LatCfg<16>::LDS);
-    set_max_lds(latent_attnT_kernel<true>, LATT_LDS);
-    set_max_lds(latent_attnT_kernel<false>, LATT_LDS);
-#endif
-    set_max_lds((latent_attnT_kernel<true, 2>), LATT_LDS_OF(2));
-    set_max_lds((latent_attnT_kernel<false, 2>), LATT_LDS_OF(2));
-    set_max_lds(latent_attn_fp8_kernel<true>, LAT8_LDS);
-    set_max_lds(latent_attn_fp8_kernel<false>, LAT8_LDS);
-    set_max_lds(latent_attnT8_kernel<true>, LATT8_LDS);
-    set_max_lds(latent_attnT8_kernel<false>, LATT8_LDS);
 }
 
 // `steps` consecutive greedy steps captured once and replayed: every per-step value (position,
@@ -1855,10 +1857,10 @@ void run_positions(mocr_engine* e, Lane& L) {
     const int R = pos_chunk_rows(e);
     for (int r0 = 0; r0 < L.n; r0 += R) {
         const int rows = std::min(R, L.n - r0);
-        gemm<T>(e, "gemm_pos_k", reinterpret_cast<const char*>(e->ENC) + (size_t)r0 * S * D * sizeof(T), D, wk, bk, e->pos_k, D, nullptr,
-                rows * S, D, D, EPI_BIAS, 128, 1);
-        gemm<T>(e, "gemm_pos_q", reinterpret_cast<const char*>(e->pos_hist) + (size_t)r0 * HL * D * sizeof(T), D, W.wqc, W.bqc, e->pos_q, D,
-                nullptr, rows * HL, D, D, EPI_BIAS, 128, 1);
+        gemm<T>(e, gemm_call("gemm_pos_k", reinterpret_cast<const char*>(e->ENC) + (size_t)r0 * S * D * sizeof(T), D, wk, bk, e->pos_k, D,
+                             rows * S, D, D, EPI_BIAS, 128));
+        gemm<T>(e, gemm_call("gemm_pos_q", reinterpret_cast<const char*>(e->pos_hist) + (size_t)r0 * HL * D * sizeof(T), D, W.wqc, W.bqc,
+                             e->pos_q, D, rows * HL, D, D, EPI_BIAS, 128));
         PosParams p{};
         p.q = e->pos_q; p.q_row_stride = (long long)HL * D;
         p.k = e->pos_k; p.k_row_stride = (long long)S * D;
@@ -3396,11 +3398,9 @@ int mocr_op_gemm(mocr_engine* e, const void* dA, const void* dW, const float* d_
         e->bind(0);
         if (epilogue == EPI_PATCH || epilogue == EPI_ARGMAX || epilogue == EPI_ARGMAX_LSE || epilogue == EPI_TOPK)
             throw ArgError{"EPI_PATCH / EPI_ARGMAX are not exposed through mocr_op_gemm (EPI_ARGMAX: mocr_op_gemm_argmax)", MOCR_ERR_ARG};
-        const long long slab = (long long)M * N;
-        if (e->cfg.dtype == MOCR_BF16)
-            gemm<bf16_t>(e, "op_gemm", dA, K, dW, d_bias, d_out, N, d_resid, M, N, K, epilogue, tile, split_k, slab);
-        else
-            gemm<float>(e, "op_gemm", dA, K, dW, d_bias, d_out, N, d_resid, M, N, K, epilogue, tile, split_k, slab);
+        GemmCall c = gemm_call("op_gemm", dA, K, dW, d_bias, d_out, N, M, N, K, epilogue, tile);
+        c.resid = d_resid; c.split = split_k; c.slab_stride = (long long)M * N;
+        if (e->cfg.dtype == MOCR_BF16) gemm<bf16_t>(e, c); else gemm<float>(e, c);
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
@@ -3414,7 +3414,9 @@ int mocr_op_gemm_ln(mocr_engine* e, const void* dA, const void* dW, const float*
         e->bind(0);
         if (e->cfg.dtype != MOCR_BF16) throw ArgError{"mocr_op_gemm_ln: bf16 engines only", MOCR_ERR_UNSUPPORTED};
         LnFold f{d_part, d_csum, d_xb};
-        gemm<bf16_t>(e, "op_gemm_ln", dA, K, dW, d_bias, d_out, N, d_resid, M, N, K, epilogue, tile, 1, 0, nullptr, 0, nullptr, 0, nullptr, &f);
+        GemmCall c = gemm_call("op_gemm_ln", dA, K, dW, d_bias, d_out, N, M, N, K, epilogue, tile);
+        c.resid = d_resid; c.lnf = &f;
+        gemm<bf16_t>(e, c);
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
@@ -3758,9 +3760,9 @@ static int op_lm_head(mocr_engine* e, const void* dA, const void* dW, const floa
         DecMode m;
         m.level = d_top_val ? 2 : d_cand_sum ? 1 : 0; m.mask = d_tok_mask != nullptr;
         const char* const name = m.mask ? "op_gemm_argmax_masked" : m.level == 2 ? "op_gemm_topk" : m.level == 1 ? "op_gemm_argmax_lse" : "op_gemm_argmax";
-        dispatch(e, [&](auto tag) {
-            gemm<decltype(tag)>(e, name, dA, K, dW, d_bias, d_cand_val, N, nullptr, M, N, K, m.epilogue(), tile, 1, 0, nullptr, 0, nullptr, 0, &lm);
-        });
+        GemmCall c = gemm_call(name, dA, K, dW, d_bias, d_cand_val, N, M, N, K, m.epilogue(), tile);
+        c.lm = &lm;
+        dispatch(e, [&](auto tag) { gemm<decltype(tag)>(e, c); });
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
@@ -3816,13 +3818,9 @@ int mocr_op_smallm_gemm(mocr_engine* e, const mocr_smallm_args* a) {
         p.stats_out = a->stats_out; p.w = reinterpret_cast<const bf16_t*>(a->w); p.bias = a->bias; p.resid = a->resid;
         p.resid_stats = a->resid_stats; p.resid_g = a->resid_g; p.resid_b = a->resid_b; p.out = a->out; p.ldo = a->ldo;
         p.rows = a->rows; p.K = a->K; p.N = a->N;
-        const int pair = a->pro * 4 + a->epi;
-        if (pair == SM_PRO_PLAIN * 4 + SM_EPI_RAW) smallm_gemm<SM_PRO_PLAIN, SM_EPI_RAW>(e, "op_smallm", p);
-        else if (pair == SM_PRO_LN * 4 + SM_EPI_RAW) smallm_gemm<SM_PRO_LN, SM_EPI_RAW>(e, "op_smallm", p);
-        else if (pair == SM_PRO_PLAIN * 4 + SM_EPI_SUM) smallm_gemm<SM_PRO_PLAIN, SM_EPI_SUM>(e, "op_smallm", p);
-        else if (pair == SM_PRO_LN * 4 + SM_EPI_GELU_BF16) smallm_gemm<SM_PRO_LN, SM_EPI_GELU_BF16>(e, "op_smallm", p);
-        else if (pair == SM_PRO_LN * 4 + SM_EPI_GELU_F32) smallm_gemm<SM_PRO_LN, SM_EPI_GELU_F32>(e, "op_smallm", p);
-        else throw ArgError{"mocr_op_smallm_gemm: (pro, epi) is not a pair the small-batch decode step launches", MOCR_ERR_UNSUPPORTED};
+        if (!smallm_pair_exists(a->pro, a->epi))
+            throw ArgError{"mocr_op_smallm_gemm: (pro, epi) is not a pair the small-batch decode step launches", MOCR_ERR_UNSUPPORTED};
+        smallm_gemm(e, "op_smallm", a->pro, a->epi, p);
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }

@@ -303,6 +303,39 @@ def test_gemm_persistent_with_folded_layernorm(epi, tile, M, N):
     assert np.isfinite(got[:M]).all() and e_ident <= 6e-3 and e_real <= 2e-2
 
 
+def test_gemm_refusals_by_code():
+    """What the host refuses before any launch, by tile code, epilogue and fold operands - each with the message of the check
+    that owns it.  One small bf16 operand set; nothing is written (the output stays NaN)."""
+    from manga_ocr._capi import MocrError
+    eng = engine("bf16")
+    M, N, K = 64, 256, 128
+    dA = torch.zeros((256, K), device="cuda", dtype=torch.bfloat16)      # (whole tiles of A, as for a GEMM that runs)
+    dW = torch.zeros((N, K), device="cuda", dtype=torch.bfloat16)
+    dB = torch.zeros(N, device="cuda", dtype=torch.float32)
+    dO = torch.full((M, N), float("nan"), device="cuda", dtype=torch.float32)
+    dP = torch.zeros((M, 4, 2), device="cuda", dtype=torch.float32)
+    dC = torch.zeros(N, device="cuda", dtype=torch.float32)
+    dXb = torch.zeros((M, N), device="cuda", dtype=torch.bfloat16)
+    torch.cuda.synchronize()
+    if not LAB:         # the A/B kernels of the experiments build
+        for tile in (256, 512, 1024, 2048, 4098):
+            with pytest.raises(MocrError, match="A/B kernel of the experiments build"):
+                eng.op_gemm(dA, dW, dB, dO, None, M, N, K, EPI_BIAS, tile=tile)
+    # (the tileability check comes first and divides N by the code: 200 of the 256 columns, so that code 100 gets past it)
+    with pytest.raises(MocrError, match="gemm tile must be"):
+        eng.op_gemm(dA, dW, dB, dO, None, M, 200, K, EPI_BIAS, tile=100)
+    with pytest.raises(MocrError, match="not tileable"):
+        eng.op_gemm(dA, dW, dB, dO, None, M, N, K, EPI_BIAS, tile=128, split_k=2)
+    with pytest.raises(MocrError, match="persistent bf16 GEMMs only"):
+        eng.op_gemm_ln(dA, dW, dB, dO, dO, M, N, K, EPI_BIAS_RESID, 128, dP, None, dXb)
+    with pytest.raises(MocrError, match="LayerNorm folding needs"):
+        eng.op_gemm_ln(dA, dW, dB, dO, dO, M, N, K, EPI_BIAS_RESID, 4096, dP, None, None)
+    with pytest.raises(MocrError, match="LayerNorm folding needs"):
+        eng.op_gemm_ln(dA, dW, dB, dO, None, M, N, K, EPI_BIAS, 4096, dP, None, None)
+    torch.cuda.synchronize()
+    assert torch.isnan(dO).all(), "a refused GEMM wrote its output"
+
+
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("M,N,K,split", [(64, 768, 768, 12), (37, 2304, 768, 4), (128, 768, 3072, 16), (64, 6144, 768, 2)])
 def test_gemm_split_k_slabs(dtype, M, N, K, split):
