@@ -337,6 +337,50 @@ int mocr_recognize_regions_prefix(mocr_engine* e, const mocr_image* pages, int32
                                   float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos, const int32_t* prefix,
                                   const int32_t* prefix_len, int32_t prefix_ld);
 
+/* ---- shared encodings ---------------------------------------------------------------------------
+ * Several decode rows per crop from one encoder pass.  Scoring eight candidate readings of one bubble, or continuing the
+ * alternatives of one reading, are eight rows over the same pixels; the *_shared entry points let the caller say so, and the
+ * crop is preprocessed and encoded once per internal batch instead of once per row.
+ *   `source` is a HOST int32 array [n_rows]: row r decodes image / region / plane number source[r] of the call.  Any order,
+ *     repeats are the point.  It is copied before the call returns.
+ *   Every output and every per-crop array of the older sections is per ROW here, [n_rows]...: out_ids, out_len, out_logp, the
+ *     alternatives, out_pos, and `sets`, `ngram`, `prefix`, `prefix_len`.
+ *   Semantics: sharing changes what the encoder is run on, and nothing else.  A call with source = 0, 1, ..., n - 1 is
+ *     bit-identical to the prefix call in every output.  A shared row is NOT promised bit-identical to the same crop sent twice:
+ *     the encoder's kernel choice - and in bf16 the LayerNorm fold - go by how many crops it runs on; the decode regime goes by
+ *     rows as always.  Rows of different calls may still be merged into one batch, and a request that shares and one that does
+ *     not may share a batch.  A call of more than max_batch rows is cut in row order; a crop whose rows fall into two internal
+ *     batches is encoded once in each, and results do not depend on where the cut falls.
+ *   How: the batch's encoder runs on the distinct crops, then one launch (profile name enc_expand) copies every row's encoding
+ *     into place - 197 x hidden elements a row - and the decode kernels run on rows as before.  The per-lane row -> crop map
+ *     (max_batch x 4 B) is allocated by the first batch that shares; a batch in which nobody shares launches exactly what it
+ *     launched before.
+ * The *_shared entry points: the *_prefix twins plus n_rows and `source`; with `source` null they require n_rows == the
+ * number of images / regions / planes and ARE the prefix calls.  MOCR_ERR_ARG: n_rows < 1; an index outside [0, number of
+ * images); an image, region or plane that no row names; for the device call n_rows > max_batch.  A sliver region gives every
+ * one of its rows length 0 (ids all pad_id, the other outputs 0, alternative ids -1; prefixes ignored there). */
+int mocr_recognize_images_shared(mocr_engine* e, const mocr_image* images, int32_t n_images, int32_t n_rows, const int32_t* source,
+                                 int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
+                                 const int32_t* sets, const int32_t* ngram, float* out_pos, const int32_t* prefix,
+                                 const int32_t* prefix_len, int32_t prefix_ld);
+int mocr_recognize_regions_shared(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                  int32_t n_regions, int32_t n_rows, const int32_t* source, int32_t* out_ids, int32_t* out_len,
+                                  float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets, const int32_t* ngram,
+                                  float* out_pos, const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld);
+/* The device call (see mocr_recognize_device_prefix below): d_gray holds n_planes planes, the outputs n_rows rows. */
+int mocr_recognize_device_shared(mocr_engine* e, const void* d_gray, int32_t n_planes, int32_t n_rows, const int32_t* source,
+                                 void* d_out_ids, void* d_out_len, void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp,
+                                 const int32_t* sets, const int32_t* ngram, void* d_out_pos, const int32_t* prefix,
+                                 const int32_t* prefix_len, int32_t prefix_ld);
+/* The host-plane call (see mocr_recognize_gray_host_prefix below). */
+int mocr_recognize_gray_host_shared(mocr_engine* e, const uint8_t* gray, int32_t n_planes, int32_t n_rows, const int32_t* source,
+                                    int32_t max_len_override, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                    float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos,
+                                    const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld);
+/* Crops the recognise calls' batches have put through the encoder since mocr_create (statistic, cumulative like
+ * mocr_decode_slot_steps): how a caller sees that sharing happened - 64 for 512 rows over 64 crops in one batch. */
+int64_t mocr_encoded_crops(mocr_engine* e);
+
 /* Preprocessing only (test hook): out_gray [n, image_size, image_size] uint8 (host) = the plane the encoder sees
  * in each of its three equal input channels before the 1/255 and (x - 0.5)/0.5 scaling. */
 int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t* out_gray);
@@ -534,6 +578,11 @@ int mocr_op_dec_token_prefix(mocr_engine* e, const mocr_token_args* a, const flo
  * the start token's bit cleared where d_ngram_of_row[row] == 1 (the first generated token already sees L = 1). */
 int mocr_op_ngram_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
                        const int32_t* d_ngram_of_row, int32_t rows);
+/* The expansion of shared encodings, as a batch runs it: d_enc holds max(n_src, n_rows) rows of 197 x hidden elements of the
+ * engine's dtype, its first n_src rows the encodings; d_src_of_row is a device int32 [n_rows] of indices into them.  On return
+ * row r < n_rows holds what row d_src_of_row[r] held before the call (in place from the caller's view: the engine stages the
+ * sources in its own workspace first); rows >= n_rows are not written.  n_src, n_rows <= max_batch; lane 0's stream. */
+int mocr_op_enc_expand(mocr_engine* e, void* d_enc, const int32_t* d_src_of_row, int32_t n_src, int32_t n_rows);
 /* The positions kernel (token positions), launched through the helper the deferred pass uses: d_q [rows][T][768] queries and
  * d_k [rows][197][768] keys in the engine's dtype, d_len [rows] int32 - positions 0 .. d_len[r] - 1 of row r are computed
  * (at most T), the rest written as 0.  d_out_pos [rows][T][MOCR_POSITION_FIELDS] float32; d_out_map (nullable) float32

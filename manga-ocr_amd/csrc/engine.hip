@@ -48,6 +48,7 @@
 #include "kernels_qqt.h"
 #include "kernels_misc.h"
 #include "kernels_positions.h"
+#include "kernels_share.h"
 
 namespace {
 
@@ -145,6 +146,9 @@ struct LaneCtx {
     int* prefix = nullptr;                          // [Bp][max_len] the caller-given tokens of every row (without the start token), by row like ids
     int* prefix_len = nullptr;                      // [Bp] by row (0: none)
     float* tgt_val = nullptr;                       // [Bp] by slot: the LM head's value of the step's forced column
+    // shared encodings: allocated by the first batch with a job that shares (ensure_share_buffer)
+    int* src_of_row = nullptr;                      // [Bp] the encoder row (crop of the batch) every decode row reads, by row like ids
+    size_t ctx_cap = 0;                             // bytes CTX was allocated with: a sharing batch stages its encodings there (expand_encodings)
     float *x_f32 = nullptr, *a_f32 = nullptr, *c_f32 = nullptr;
     float* ln_stats = nullptr;                      // small-batch path: (mean, rstd) per row of the three pre-LayerNorm sums, [3][Bp][2]
     void *x_t = nullptr, *a_t = nullptr, *c_t = nullptr, *ctx_t = nullptr, *h_t = nullptr, *z_t = nullptr;
@@ -166,7 +170,11 @@ struct Job {
     bool src_host = false;
     int channels = 1;
     int64_t row_stride = 0, image_stride = 0;
-    int n = 0, max_len = 0;
+    int n = 0, max_len = 0;         // decode rows
+    // shared encodings (the *_shared entry points): the job brings n_src planes, row r reads plane src_of_row[r] of them
+    // (empty: every row its own plane, n_src == n); `planes`: where they lie behind `src`, in planes (empty: 0, 1, 2, ...)
+    int n_src = 0;
+    std::vector<int32_t> src_of_row, planes;
     int32_t* out_ids = nullptr;     // host (out_host) or device
     int32_t* out_len = nullptr;
     float* out_logp = nullptr;      // nullable: [n][max_len] token log-probabilities (the *_scored entry points); host or device like out_ids
@@ -228,6 +236,8 @@ struct Lane {
     bool active = false;
     std::vector<Job> jobs;          // requests merged into this lane's current batch, in row order
     int n = 0, max_len = 0;         // rows of the merged batch, its generate(max_length)
+    int n_enc = 0;                  // crops the encoder runs on: the jobs' planes (n unless a job shares encodings)
+    std::vector<int> h_src;         // the upload of src_of_row stages from here
     int np = 0;                     // slots the decode steps run on: n rounded up (graph_rows), the extra ones are born finished; shrinks when the batch is compacted
     int np0 = 0;                    // np at the start of the batch = its kernel regime
     DecMode mode;                   // mode_of(jobs)
@@ -260,6 +270,7 @@ struct mocr_engine : LaneCtx {
     float fold_ratio = 0.f;         // the worst ratio measured (0: not measured)
     long long n_slot_steps = 0;     // decode slots x steps enqueued so far (mocr_decode_slot_steps): what the steps cost, in rows
     long long n_compactions = 0;    // batches whose rows were compacted, counted per compaction (mocr_compaction_count)
+    long long n_encoded = 0;        // crops the recognise calls' batches have put through the encoder (mocr_encoded_crops)
     int lat_tk = 18;                // bf16 latent attention kernel: 18 = latent_attnT_kernel, three blocks per CU (default); 32 = latent_attn_kernel on 32-key tiles; experiments: 17, 16
     int Bc = 0;                     // rows the classic K/V buffers are sized for
     // Kernel regime of the batch being decoded: the row count the batch STARTED with (0: the launch's own row count).
@@ -873,8 +884,9 @@ static void calib_observe(mocr_engine* e, int M) {
     c.idx += 1;
 }
 
+// (enc_out: where the final LayerNorm writes the n encodings; null = ENC)
 template <typename T>
-void run_encoder(mocr_engine* e, const uint8_t* d_gray, int n) {
+void run_encoder(mocr_engine* e, const uint8_t* d_gray, int n, void* enc_out = nullptr) {
     const int D = e->D, F = e->F, S = e->S, M = n * S, P = e->cfg.patch_size, IMG = e->cfg.image_size;
     const int NP = e->G * e->G, MPATCH = n * NP;
     auto& w = e->w;
@@ -1009,7 +1021,7 @@ void run_encoder(mocr_engine* e, const uint8_t* d_gray, int n) {
         gemm<T>(e, fc1);
         gemm<T>(e, split_2 > 1 ? into_slabs(fc2, split_2) : fc2);
     }
-    norm(w.lnfg, w.lnfb, e->ENC);
+    norm(w.lnfg, w.lnfb, enc_out ? enc_out : e->ENC);
 }
 
 // ---------------------------------------------------------------------------------------- decoder
@@ -1881,35 +1893,81 @@ static void upload_per_row(mocr_engine* e, const Lane& L, std::vector<int>& stag
     HIPCHECK(hipMemcpyAsync(d_dst, stage.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
 }
 
+// The decode rows' source of a batch with shared encodings, for the bound lane: allocated by the first batch in which a job
+// shares, like the alternatives buffers.
+static void ensure_share_buffer(mocr_engine* e) {
+    if (!e->src_of_row) e->src_of_row = e->dalloc<int>((size_t)e->Bp);
+}
+
+// out[r] = in[d_src_of_row[r]] for r < rows, rows of S x D elements of the engine's dtype; `in` holds n_src of them and is
+// not `out` (kernels_share.h).
+static void launch_enc_expand(mocr_engine* e, const void* in, void* out, const int* d_src_of_row, int n_src, int rows) {
+    const size_t row_bytes = (size_t)e->S * e->D * e->esz;
+    if (row_bytes % 16 || in == out) throw ArgError{"enc_expand: rows of whole 16-byte pieces, out of place", MOCR_ERR_UNSUPPORTED};
+    const int chunks = (int)(row_bytes / 16), per_row = (chunks + EXPAND_THREADS - 1) / EXPAND_THREADS;
+    ProfScope ps(e, "enc_expand", 0, 2.0 * rows * (double)row_bytes);
+    hipLaunchKernelGGL(enc_expand_kernel, dim3((unsigned)rows * (unsigned)per_row), dim3(EXPAND_THREADS), 0, e->stream,
+                       reinterpret_cast<const uint4*>(in), reinterpret_cast<uint4*>(out), d_src_of_row, n_src, rows, chunks, per_row);
+    HIPCHECK(hipGetLastError());
+}
+
 template <typename T>
 void start_batch(mocr_engine* e, Lane& L) {
     const int IMG = e->cfg.image_size;
     const size_t plane = (size_t)IMG * IMG;
-    int row0 = 0;
+    // one plane per distinct source of every job: the encoder runs on n_enc <= n crops
+    int plane0 = 0;
+    bool shares = false;
     for (const Job& j : L.jobs) {
-        uint8_t* gdst = e->d_in + (size_t)row0 * plane;
+        uint8_t* gdst = e->d_in + (size_t)plane0 * plane;
+        const size_t rowb = (size_t)IMG * j.channels;
+        uint8_t* dst = (!j.src_host || j.channels == 1) ? gdst : e->d_rgb + (size_t)plane0 * plane * 3;
         if (j.wait_ev) HIPCHECK(hipStreamWaitEvent(e->stream, j.wait_ev, 0));
-        if (!j.src_host) {
-            HIPCHECK(hipMemcpyAsync(gdst, j.src, plane * j.n, hipMemcpyDeviceToDevice, e->stream));
-        } else {
-            const size_t rowb = (size_t)IMG * j.channels;
-            uint8_t* dst = j.channels == 1 ? gdst : e->d_rgb + (size_t)row0 * plane * 3;
-            if (j.row_stride == (int64_t)rowb && j.image_stride == (int64_t)(rowb * IMG)) {
-                HIPCHECK(hipMemcpyAsync(dst, j.src, rowb * IMG * j.n, hipMemcpyHostToDevice, e->stream));
+        // `count` consecutive planes of the job's source, from plane `first` of it, to the job's plane `at`
+        auto copy_planes = [&](int at, int first, int count) {
+            if (!j.src_host) {
+                HIPCHECK(hipMemcpyAsync(gdst + (size_t)at * plane, j.src + (size_t)first * plane, plane * count, hipMemcpyDeviceToDevice, e->stream));
+            } else if (j.row_stride == (int64_t)rowb && j.image_stride == (int64_t)(rowb * IMG)) {
+                HIPCHECK(hipMemcpyAsync(dst + (size_t)at * rowb * IMG, j.src + (size_t)first * j.image_stride, rowb * IMG * count,
+                                        hipMemcpyHostToDevice, e->stream));
             } else {
-                for (int i = 0; i < j.n; ++i)
-                    HIPCHECK(hipMemcpy2DAsync(dst + (size_t)i * IMG * rowb, rowb, j.src + (size_t)i * j.image_stride, j.row_stride,
-                                              rowb, IMG, hipMemcpyHostToDevice, e->stream));
+                for (int i = 0; i < count; ++i)
+                    HIPCHECK(hipMemcpy2DAsync(dst + (size_t)(at + i) * IMG * rowb, rowb, j.src + (size_t)(first + i) * j.image_stride,
+                                              j.row_stride, rowb, IMG, hipMemcpyHostToDevice, e->stream));
             }
-            if (j.channels == 3) {
-                const long long npix = (long long)j.n * IMG * IMG;
-                hipLaunchKernelGGL(rgb_to_l_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, e->stream, dst, gdst, npix);
-                HIPCHECK(hipGetLastError());
+        };
+        if (j.planes.empty()) copy_planes(0, 0, j.n_src);
+        else
+            for (int i0 = 0, i1; i0 < j.n_src; i0 = i1) {      // runs of neighbouring planes move as one copy
+                for (i1 = i0 + 1; i1 < j.n_src && j.planes[i1] == j.planes[i1 - 1] + 1; ++i1) {}
+                copy_planes(i0, j.planes[i0], i1 - i0);
             }
+        if (j.src_host && j.channels == 3) {
+            const long long npix = (long long)j.n_src * IMG * IMG;
+            hipLaunchKernelGGL(rgb_to_l_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, e->stream, dst, gdst, npix);
+            HIPCHECK(hipGetLastError());
         }
-        row0 += j.n;
+        plane0 += j.n_src;
+        shares = shares || !j.src_of_row.empty();
     }
-    run_encoder<T>(e, e->d_in, L.n);
+    e->n_encoded += L.n_enc;
+    if (!shares) run_encoder<T>(e, e->d_in, L.n);
+    else {
+        // Shared encodings: the final LayerNorm leaves the n_enc encodings in CTX - dead since the last layer's O-projection -
+        // and one gather gives every decode row its own copy in ENC; everything behind it goes by row as always.
+        if (L.n_enc > L.n || (size_t)L.n_enc * e->S * e->D * sizeof(T) > e->ctx_cap)
+            throw ArgError{"shared encodings: the staging buffer is too small for this batch", MOCR_ERR_STATE};
+        ensure_share_buffer(e);
+        L.h_src.assign((size_t)L.np, 0);
+        int r0 = 0, p0 = 0;
+        for (const Job& j : L.jobs) {
+            for (int i = 0; i < j.n; ++i) L.h_src[r0 + i] = p0 + (j.src_of_row.empty() ? i : j.src_of_row[i]);
+            r0 += j.n; p0 += j.n_src;
+        }
+        HIPCHECK(hipMemcpyAsync(e->src_of_row, L.h_src.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        run_encoder<T>(e, e->d_in, L.n_enc, e->CTX);
+        launch_enc_expand(e, e->CTX, e->ENC, e->src_of_row, L.n_enc, L.n);
+    }
     if (!e->use_latent(L.np0)) run_cross_kv<T>(e, L.n);
     else if (e->fp8attn) quantize_enc(e, L.n);
     // rows read pad_id (= 0) beyond what the loop writes
@@ -2086,7 +2144,7 @@ bool pump_once(mocr_engine* e) {
         Lane& L = e->lanes[i];
         if (!L.active && !e->pending.empty()) {
             L.jobs.clear();
-            L.n = 0;
+            L.n = L.n_enc = 0;
             L.max_len = e->pending.front().max_len;
             // An idle lane takes as many queued requests as fit in max_batch rows.  When SEVERAL lanes are idle and the
             // queue would fit into fewer of them, it is split evenly over the idle lanes as long as every part keeps
@@ -2110,6 +2168,7 @@ bool pump_once(mocr_engine* e) {
             while (take < e->pending.size() && e->pending[take].max_len == L.max_len &&
                    (take == 0 || L.n + e->pending[take].n <= cap) && L.n + e->pending[take].n <= e->cfg.max_batch) {
                 L.n += e->pending[take].n;
+                L.n_enc += e->pending[take].n_src;
                 L.jobs.push_back(e->pending[take]);
                 ++take;
             }
@@ -2415,7 +2474,8 @@ void allocate_lane(mocr_engine* e, int lane_id) {
         HIPCHECK(hipMemset(e->ln_part, 0, Mp * 8 * sizeof(float)));      // (partial 3 stays zero: N = 768 has three column slices)
     }
     e->QKV = e->dalloc<char>(Mp * 3 * D * esz);
-    e->CTX = e->dalloc<char>(Mp * D * esz);
+    e->ctx_cap = Mp * D * esz;      // (also the staging buffer of shared encodings: start_batch checks a batch against it)
+    e->CTX = e->dalloc<char>(e->ctx_cap);
     e->Hb = e->dalloc<char>(Mp * (size_t)e->F * esz);
     e->ENC = e->dalloc<char>(Mp * D * esz);
     if (e->latent && e->classic_rows < c.max_batch) {      // else every batch takes the classic kernels
@@ -2691,7 +2751,27 @@ struct Request {
     const int32_t* prefix = nullptr;        // host [n][prefix_ld], with prefix_len host [n]: both or neither
     const int32_t* prefix_len = nullptr;
     int32_t prefix_ld = 0;
+    // shared encodings (the *_shared entry points): host [rows], the image / region / plane every row decodes (null: row r
+    // reads number r), and how many of those the call brings (-1: not said - as many as rows)
+    const int32_t* source = nullptr;
+    int32_t n_images = -1;
 };
+
+// shared encodings: every index names an image of the call, and every image is named by a row
+static void require_source(const Request& r, int n) {
+    if (!r.source) {
+        if (r.n_images >= 0 && r.n_images != n) throw ArgError{"source is null: n_rows must equal the number of images", MOCR_ERR_ARG};
+        return;
+    }
+    if (n < 1) throw ArgError{"n_rows must be positive", MOCR_ERR_ARG};
+    if (r.n_images < 1) throw ArgError{"the number of images must be positive", MOCR_ERR_ARG};
+    std::vector<char> named((size_t)r.n_images, 0);
+    for (int i = 0; i < n; ++i) {
+        if (r.source[i] < 0 || r.source[i] >= r.n_images) throw ArgError{"source index outside [0, number of images)", MOCR_ERR_ARG};
+        named[r.source[i]] = 1;
+    }
+    if (std::find(named.begin(), named.end(), 0) != named.end()) throw ArgError{"an image that no row names", MOCR_ERR_ARG};
+}
 
 // forced prefixes: per crop 0 .. gen_len - 1 tokens of the vocabulary, EOS as the last one only (gen_len: the call's generate(max_length))
 static void require_prefix(const mocr_engine* e, const Request& r, int n, int gen_len) {
@@ -2715,6 +2795,7 @@ static void validate_request(mocr_engine* e, const Request& r, int n, Ready read
     if ((r.out_alt_ids == nullptr) != (r.out_alt_logp == nullptr))
         throw ArgError{"out_alt_ids and out_alt_logp must be both null or both set", MOCR_ERR_ARG};
     if (ready != Ready::unchecked) require_ready(e, n, ready == Ready::max_batch);
+    require_source(r, n);
     require_sets(e, r.sets, n);
     require_ngram(e, r.ngram, n);
     require_prefix(e, r, n, gen_len);
@@ -2741,13 +2822,27 @@ static void slice_job(Job& j, const Request& r, size_t base, int n, int max_len)
         j.prefix_ld = r.prefix_ld;
         j.prefix.assign(r.prefix + base * (size_t)r.prefix_ld, r.prefix + (base + n) * (size_t)r.prefix_ld);
     }
+    // shared encodings: the job brings the distinct sources of its own rows, in ascending order (`planes`: their numbers in
+    // the call - the caller of slice_job makes them the job's planes), and its rows name them by their place in that list
+    j.n_src = n; j.src_of_row.clear(); j.planes.clear();
+    if (r.source) {
+        j.planes.assign(r.source + base, r.source + base + n);
+        std::sort(j.planes.begin(), j.planes.end());
+        j.planes.erase(std::unique(j.planes.begin(), j.planes.end()), j.planes.end());
+        j.n_src = (int)j.planes.size();
+        j.src_of_row.resize((size_t)n);
+        for (int i = 0; i < n; ++i)
+            j.src_of_row[i] = (int32_t)(std::lower_bound(j.planes.begin(), j.planes.end(), r.source[base + i]) - j.planes.begin());
+    }
 }
 
 // the exported twins' arguments as a request (the device entry points pass untyped pointers)
 static Request request_of(void* out_logp = nullptr, void* out_alt_ids = nullptr, void* out_alt_logp = nullptr,
                           const int32_t* sets = nullptr, const int32_t* ngram = nullptr, void* out_pos = nullptr,
-                          const int32_t* prefix = nullptr, const int32_t* prefix_len = nullptr, int32_t prefix_ld = 0) {
+                          const int32_t* prefix = nullptr, const int32_t* prefix_len = nullptr, int32_t prefix_ld = 0,
+                          const int32_t* source = nullptr, int32_t n_images = -1) {
     Request r;
+    r.source = source; r.n_images = n_images;
     r.out_logp = static_cast<float*>(out_logp);
     r.out_alt_ids = static_cast<int32_t*>(out_alt_ids); r.out_alt_logp = static_cast<float*>(out_alt_logp);
     r.sets = sets; r.ngram = ngram;
@@ -2782,6 +2877,15 @@ int mocr_recognize_device_prefix(mocr_engine* e, const void* d_gray, int32_t n, 
                                  const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld) {
     return recognize_device(e, d_gray, n, d_out_ids, d_out_len,
                             request_of(d_out_logp, d_out_alt_ids, d_out_alt_logp, sets, ngram, d_out_pos, prefix, prefix_len, prefix_ld));
+}
+
+int mocr_recognize_device_shared(mocr_engine* e, const void* d_gray, int32_t n_planes, int32_t n_rows, const int32_t* source,
+                                 void* d_out_ids, void* d_out_len, void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp,
+                                 const int32_t* sets, const int32_t* ngram, void* d_out_pos, const int32_t* prefix,
+                                 const int32_t* prefix_len, int32_t prefix_ld) {
+    return recognize_device(e, d_gray, n_rows, d_out_ids, d_out_len,
+                            request_of(d_out_logp, d_out_alt_ids, d_out_alt_logp, sets, ngram, d_out_pos, prefix, prefix_len, prefix_ld,
+                                       source, n_planes));
 }
 
 int mocr_recognize_device_norepeat(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
@@ -2819,7 +2923,8 @@ static void recognize_host_chunks(mocr_engine* e, const uint8_t* images, int n, 
     if (max_len < 2 || max_len > e->cfg.max_len) throw ArgError{"bad max_len override", MOCR_ERR_ARG};
     for (int base = 0; base < n; base += e->cfg.max_batch) {
         Job j;
-        j.src = images + (size_t)base * image_stride; j.src_host = true; j.channels = channels;
+        // (a job that shares finds its planes by their numbers in the call: slice_job's `planes`)
+        j.src = images + (req.source ? 0 : (size_t)base * image_stride); j.src_host = true; j.channels = channels;
         j.row_stride = row_stride; j.image_stride = image_stride;
         j.n = std::min(e->cfg.max_batch, n - base); j.max_len = max_len;
         j.out_ids = out_ids + (size_t)base * e->cfg.max_len; j.out_len = out_len + base; j.out_host = true;
@@ -2862,6 +2967,15 @@ int mocr_recognize_gray_host_prefix(mocr_engine* e, const uint8_t* gray, int32_t
                                     int32_t prefix_ld) {
     return recognize_gray_host(e, gray, n, max_len_override, out_ids, out_len,
                                request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len, prefix_ld));
+}
+
+int mocr_recognize_gray_host_shared(mocr_engine* e, const uint8_t* gray, int32_t n_planes, int32_t n_rows, const int32_t* source,
+                                    int32_t max_len_override, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                    float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos,
+                                    const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld) {
+    return recognize_gray_host(e, gray, n_rows, max_len_override, out_ids, out_len,
+                               request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len, prefix_ld,
+                                          source, n_planes));
 }
 
 int mocr_recognize_gray_host_norepeat(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
@@ -3055,21 +3169,40 @@ static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& sr
                                int32_t* out_len, const Request& req) {
     const size_t plane = (size_t)e->cfg.image_size * e->cfg.image_size;
     const int C = std::min(e->cfg.max_batch, 4096), nchunks = (n + C - 1) / C;
-    uint8_t* const d_gray = (uint8_t*)e->grow(e->rs_gray, (size_t)n * plane);
-    auto push_job = [&](int k, hipEvent_t ev) {
-        Job j;
-        j.wait_ev = ev;
-        j.src = d_gray + (size_t)k * C * plane; j.src_host = false; j.channels = 1;
+    // `n` decode rows over the views (req.source; without it row r reads view r).  A chunk prepares the views its own rows
+    // name, once each: the planes of its job.
+    struct Chunk { int plane0 = 0; std::vector<PrepView> own; const PrepView* views = nullptr; Job job; };
+    std::vector<Chunk> chunks(nchunks);
+    int total_planes = 0;
+    for (int k = 0; k < nchunks; ++k) {
+        Chunk& c = chunks[k];
+        Job& j = c.job;
+        j.src_host = false; j.channels = 1;
         j.row_stride = e->cfg.image_size; j.image_stride = (int64_t)plane;
         j.n = std::min(C, n - k * C); j.max_len = e->gen_max_len;
         j.out_ids = out_ids + (size_t)k * C * e->cfg.max_len; j.out_len = out_len + (size_t)k * C; j.out_host = true;
         slice_job(j, req, (size_t)k * C, j.n, e->cfg.max_len);
+        c.views = views + (size_t)k * C;
+        if (req.source) {
+            for (int32_t v : j.planes) c.own.push_back(views[v]);
+            c.views = c.own.data();
+            j.planes.clear();       // prepared side by side, in that order
+        }
+        c.plane0 = total_planes;
+        total_planes += j.n_src;
+    }
+    uint8_t* const d_gray = (uint8_t*)e->grow(e->rs_gray, (size_t)total_planes * plane);
+    auto chunk_out = [&](int k) { return d_gray + (size_t)chunks[k].plane0 * plane; };
+    auto push_job = [&](int k, hipEvent_t ev) {
+        Job& j = chunks[k].job;
+        j.wait_ev = ev;
+        j.src = chunk_out(k);
         e->pending.push_back(j);
     };
     std::vector<PrepHold> holds(nchunks);
     if (nchunks == 1 || e->prof_on) {              // nothing to overlap (or an instrumented pass: one thread records the events)
         for (int k = 0; k < nchunks; ++k) {
-            prep_enqueue(e, srcs, views + (size_t)k * C, std::min(C, n - k * C), d_gray + (size_t)k * C * plane, 0, e->prof_on, holds[k]);
+            prep_enqueue(e, srcs, chunks[k].views, chunks[k].job.n_src, chunk_out(k), 0, e->prof_on, holds[k]);
             HIPCHECK(hipStreamSynchronize(e->prep_stream));
             push_job(k, nullptr);
         }
@@ -3089,7 +3222,7 @@ static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& sr
             if (k >= 2) HIPCHECK(hipEventSynchronize(ev[k - 2]));
         },
         [&](int k) {                                   // producer thread
-            prep_enqueue(e, srcs, views + (size_t)k * C, std::min(C, n - k * C), d_gray + (size_t)k * C * plane, k & 1, false, holds[k]);
+            prep_enqueue(e, srcs, chunks[k].views, chunks[k].job.n_src, chunk_out(k), k & 1, false, holds[k]);
             HIPCHECK(hipEventRecord(ev[k], e->prep_stream));
         },
         [&](int k) { push_job(k, ev[k]); },            // calling thread
@@ -3125,9 +3258,10 @@ static int recognize_images(mocr_engine* e, const mocr_image* images, int32_t n,
         if (!images || !out_ids || !out_len) throw ArgError{"null pointer", MOCR_ERR_ARG};
         HIPCHECK(hipSetDevice(e->cfg.device));
         drive(e);
-        std::vector<PrepSource> srcs(n);
-        std::vector<PrepView> views(n);
-        for (int i = 0; i < n; ++i) {
+        const int n_images = req.source ? req.n_images : n;      // n: decode rows
+        std::vector<PrepSource> srcs(n_images);
+        std::vector<PrepView> views(n_images);
+        for (int i = 0; i < n_images; ++i) {
             srcs[i] = source_of(images[i]);
             views[i] = PrepView{i, 0, 0, srcs[i].w, srcs[i].h, srcs[i].rot};
         }
@@ -3146,6 +3280,15 @@ int mocr_recognize_images_prefix(mocr_engine* e, const mocr_image* images, int32
                                  float* out_pos, const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld) {
     return recognize_images(e, images, n, out_ids, out_len,
                             request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len, prefix_ld));
+}
+
+int mocr_recognize_images_shared(mocr_engine* e, const mocr_image* images, int32_t n_images, int32_t n_rows, const int32_t* source,
+                                 int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
+                                 const int32_t* sets, const int32_t* ngram, float* out_pos, const int32_t* prefix,
+                                 const int32_t* prefix_len, int32_t prefix_ld) {
+    return recognize_images(e, images, n_rows, out_ids, out_len,
+                            request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len, prefix_ld, source,
+                                       n_images));
 }
 
 int mocr_recognize_images_norepeat(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
@@ -3186,31 +3329,41 @@ static bool padded_region(const mocr_region& r, int page_h, int page_w, PrepView
     return true;
 }
 
+// n_rows decode rows over n_regions regions (req.source; without it n_rows == n_regions and row r reads region r): the per-row
+// arrays of the request and every output go by row.
 static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions, int32_t n_regions,
-                             int32_t* out_ids, int32_t* out_len, const Request& req) {
+                             int32_t n_rows, int32_t* out_ids, int32_t* out_len, const Request& req) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
-        validate_request(e, req, std::max(n_regions, 0), Ready::unchecked, e->gen_max_len);
+        validate_request(e, req, std::max(n_rows, 0), Ready::unchecked, e->gen_max_len);
         if (!e->committed) throw ArgError{"weights not committed (mocr_commit_weights)", MOCR_ERR_STATE};
-        if (!pages || n_pages < 1 || n_regions < 0 || (n_regions > 0 && (!regions || !out_ids || !out_len)))
+        if (!pages || n_pages < 1 || n_regions < 0 || n_rows < 0 || (n_rows > 0 && (!regions || !out_ids || !out_len)))
             throw ArgError{"bad argument", MOCR_ERR_ARG};
-        if (n_regions == 0) return;
+        if (n_rows == 0) return;
         HIPCHECK(hipSetDevice(e->cfg.device));
         drive(e);
         std::vector<PrepSource> srcs(n_pages);
         for (int i = 0; i < n_pages; ++i) srcs[i] = source_of(pages[i]);
         std::vector<PrepView> views;
-        std::vector<int> where(n_regions, -1);          // region -> its row among the recognised crops (-1: sliver)
-        std::vector<int32_t> view_sets;                 // the recognised crops' token sets
-        std::vector<int32_t> view_ngram;                // ... and no-repeat n-gram sizes
-        std::vector<int32_t> view_plen, view_prefix;    // ... and forced prefixes (a sliver's prefix is ignored)
+        std::vector<int> view_of(n_regions, -1);        // region -> its place among the recognised crops (-1: sliver)
         for (int i = 0; i < n_regions; ++i) {
             const mocr_region& r = regions[i];
             if (r.page < 0 || r.page >= n_pages) throw ArgError{"region of an unknown page", MOCR_ERR_ARG};
             PrepView v{r.page, 0, 0, 0, 0, MOCR_ROTATE_NONE};
             if (!padded_region(r, srcs[r.page].h, srcs[r.page].w, v)) continue;
-            where[i] = (int)views.size();
+            view_of[i] = (int)views.size();
             views.push_back(v);
+        }
+        std::vector<int> where(n_rows, -1);             // row -> its row among the recognised rows (-1: a sliver's)
+        std::vector<int32_t> view_src;                  // the recognised rows' crops
+        std::vector<int32_t> view_sets;                 // ... token sets
+        std::vector<int32_t> view_ngram;                // ... and no-repeat n-gram sizes
+        std::vector<int32_t> view_plen, view_prefix;    // ... and forced prefixes (a sliver's prefix is ignored)
+        for (int i = 0; i < n_rows; ++i) {
+            const int v = view_of[req.source ? req.source[i] : i];
+            if (v < 0) continue;
+            where[i] = (int)view_src.size();
+            view_src.push_back(v);
             if (req.sets) view_sets.push_back(req.sets[i]);
             if (req.ngram) view_ngram.push_back(req.ngram[i]);
             if (req.prefix) {
@@ -3218,10 +3371,10 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
                 view_prefix.insert(view_prefix.end(), req.prefix + (size_t)i * req.prefix_ld, req.prefix + (size_t)(i + 1) * req.prefix_ld);
             }
         }
-        // Every output the caller asked for: the caller's rows (one per region), the elements of a row, what a sliver's row
-        // reads, and the recognised crops' rows (a buffer of ours).  All hold 4-byte elements, moved as bytes: a fill value is
+        // Every output the caller asked for: the caller's rows, the elements of a row, what a sliver's row
+        // reads, and the recognised rows (a buffer of ours).  All hold 4-byte elements, moved as bytes: a fill value is
         // given as its bit pattern (0.f = 0, -1 = all ones).
-        const size_t L = (size_t)e->cfg.max_len, nv = views.size();
+        const size_t L = (size_t)e->cfg.max_len, nv = view_src.size();
         struct Out { void* dst; size_t per_row; uint32_t fill; std::vector<uint32_t> rows, sliver; };
         Out outs[] = {{out_ids, L, (uint32_t)e->cfg.pad_id, {}, {}},
                       {out_len, 1, 0u, {}, {}},
@@ -3239,8 +3392,9 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
             prepare_and_decode(e, srcs, views.data(), (int)nv, reinterpret_cast<int32_t*>(rows_of(0)), reinterpret_cast<int32_t*>(rows_of(1)),
                                request_of(rows_of(2), rows_of(3), rows_of(4), req.sets ? view_sets.data() : nullptr,
                                           req.ngram ? view_ngram.data() : nullptr, rows_of(5), pre ? view_prefix.data() : nullptr,
-                                          pre ? view_plen.data() : nullptr, pre ? req.prefix_ld : 0));
-        for (int i = 0; i < n_regions; ++i)
+                                          pre ? view_plen.data() : nullptr, pre ? req.prefix_ld : 0,
+                                          req.source ? view_src.data() : nullptr, req.source ? (int32_t)views.size() : -1));
+        for (int i = 0; i < n_rows; ++i)
             for (Out& o : outs) {
                 if (!o.dst) continue;
                 const size_t bytes = o.per_row * sizeof(uint32_t);
@@ -3253,7 +3407,7 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
 int mocr_recognize_regions_positions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
                                      int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
                                      float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos) {
-    return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len,
+    return recognize_regions(e, pages, n_pages, regions, n_regions, n_regions, out_ids, out_len,
                              request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos));
 }
 
@@ -3261,36 +3415,45 @@ int mocr_recognize_regions_prefix(mocr_engine* e, const mocr_image* pages, int32
                                   int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
                                   float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos, const int32_t* prefix,
                                   const int32_t* prefix_len, int32_t prefix_ld) {
-    return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len,
+    return recognize_regions(e, pages, n_pages, regions, n_regions, n_regions, out_ids, out_len,
                              request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len, prefix_ld));
+}
+
+int mocr_recognize_regions_shared(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                  int32_t n_regions, int32_t n_rows, const int32_t* source, int32_t* out_ids, int32_t* out_len,
+                                  float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets, const int32_t* ngram,
+                                  float* out_pos, const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld) {
+    return recognize_regions(e, pages, n_pages, regions, n_regions, n_rows, out_ids, out_len,
+                             request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len, prefix_ld, source,
+                                        n_regions));
 }
 
 int mocr_recognize_regions_norepeat(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
                                     int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
                                     float* out_alt_logp, const int32_t* sets, const int32_t* ngram) {
-    return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram));
+    return recognize_regions(e, pages, n_pages, regions, n_regions, n_regions, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram));
 }
 
 int mocr_recognize_regions_constrained(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
                                        int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
                                        float* out_alt_logp, const int32_t* sets) {
-    return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp, sets));
+    return recognize_regions(e, pages, n_pages, regions, n_regions, n_regions, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp, sets));
 }
 
 int mocr_recognize_regions_alts(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
                                 int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
                                 float* out_alt_logp) {
-    return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp));
+    return recognize_regions(e, pages, n_pages, regions, n_regions, n_regions, out_ids, out_len, request_of(out_logp, out_alt_ids, out_alt_logp));
 }
 
 int mocr_recognize_regions_scored(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
                                   int32_t n_regions, int32_t* out_ids, int32_t* out_len, float* out_logp) {
-    return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len, request_of(out_logp));
+    return recognize_regions(e, pages, n_pages, regions, n_regions, n_regions, out_ids, out_len, request_of(out_logp));
 }
 
 int mocr_recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions, int32_t n_regions,
                            int32_t* out_ids, int32_t* out_len) {
-    return recognize_regions(e, pages, n_pages, regions, n_regions, out_ids, out_len, Request{});
+    return recognize_regions(e, pages, n_pages, regions, n_regions, n_regions, out_ids, out_len, Request{});
 }
 
 int mocr_set_generate_max_length(mocr_engine* e, int32_t max_len) {
@@ -3313,6 +3476,12 @@ int64_t mocr_decode_slot_steps(mocr_engine* e) {
     if (!e) return 0;
     std::lock_guard<std::mutex> lk(e->mu);
     return e->n_slot_steps;
+}
+
+int64_t mocr_encoded_crops(mocr_engine* e) {
+    if (!e) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return e->n_encoded;
 }
 
 int64_t mocr_compaction_count(mocr_engine* e) {
@@ -3623,6 +3792,28 @@ int mocr_op_attn_positions(mocr_engine* e, const void* d_q, const void* d_k, con
         p.out_pos = d_out_pos; p.pos_row_stride = (long long)T * MOCR_POSITION_FIELDS;
         p.out_map = d_out_map;
         if (e->cfg.dtype == MOCR_BF16) launch_attn_positions<bf16_t>(e, p, rows); else launch_attn_positions<float>(e, p, rows);
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+// The expansion of shared encodings as start_batch runs it, on the caller's buffer: its first n_src rows are staged in the
+// lane's CTX, then row r of it becomes staged row d_src_of_row[r].
+int mocr_op_enc_expand(mocr_engine* e, void* d_enc, const int32_t* d_src_of_row, int32_t n_src, int32_t n_rows) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        const size_t row_bytes = (size_t)e->S * e->D * e->esz;
+        if (!d_enc || !d_src_of_row || n_src < 1 || n_rows < 1 || n_src > e->cfg.max_batch || n_rows > e->cfg.max_batch ||
+            (size_t)n_src * row_bytes > e->ctx_cap)
+            throw ArgError{"mocr_op_enc_expand: bad argument", MOCR_ERR_ARG};
+        std::vector<int32_t> h((size_t)n_rows);
+        HIPCHECK(hipMemcpy(h.data(), d_src_of_row, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int32_t v : h)
+            if (v < 0 || v >= n_src) throw ArgError{"mocr_op_enc_expand: source index outside [0, n_src)", MOCR_ERR_ARG};
+        HIPCHECK(hipMemcpyAsync(e->CTX, d_enc, (size_t)n_src * row_bytes, hipMemcpyDeviceToDevice, e->stream));
+        launch_enc_expand(e, e->CTX, d_enc, d_src_of_row, n_src, n_rows);
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }

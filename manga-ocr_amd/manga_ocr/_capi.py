@@ -113,6 +113,15 @@ SYMBOLS = {
                                                 _P, _P, C.c_int32]),
     "mocr_recognize_device_prefix": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32]),
     "mocr_recognize_gray_host_prefix": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32]),
+    "mocr_recognize_images_shared": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                               C.c_int32]),
+    "mocr_recognize_regions_shared": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.POINTER(MocrRegion), C.c_int32, C.c_int32, _P, _P, _P,
+                                                _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32]),
+    "mocr_recognize_device_shared": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32]),
+    "mocr_recognize_gray_host_shared": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                  C.c_int32]),
+    "mocr_encoded_crops": (C.c_int64, [_P]),
+    "mocr_op_enc_expand": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),
     "mocr_graph_count": (C.c_int, [_P]),
     "mocr_compaction_count": (C.c_int64, [_P]),
     "mocr_decode_slot_steps": (C.c_int64, [_P]),

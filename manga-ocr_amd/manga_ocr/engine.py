@@ -192,6 +192,32 @@ class Engine:
             block[i, :r.size] = r
         return block, np.array([r.size for r in rows], dtype=np.int32), ld
 
+    # ------------------------------------------------------------------ shared encodings
+    @staticmethod
+    def _sources(sources, n_images: int) -> np.ndarray:
+        """``sources=``: a flat sequence of ints, one per output row - the image, region or plane the row decodes -> int32
+        [rows].  Every index is in [0, n_images) and every image is named (the engine checks the same)."""
+        if isinstance(sources, (str, bytes, int, np.integer, bool, np.bool_)):
+            raise TypeError(f"sources: a flat sequence of ints, one per output row, instead got {sources!r}")
+        a = np.asarray(list(sources))
+        if a.ndim != 1 or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("sources: a flat, non-empty sequence of ints, one per output row")
+        if a.min() < 0 or a.max() >= n_images:
+            raise ValueError(f"sources: indices must be in [0, {n_images})")
+        if np.unique(a).size != n_images:
+            raise ValueError("sources: every image, region or plane must be named by a row")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def _prefix_args(self, prefixes, n: int):
+        """the (prefix, prefix_len, prefix_ld) tail of a *_prefix / *_shared call; the arrays must outlive the call"""
+        if prefixes is None:
+            return None, None, 0
+        return self._prefixes(prefixes, n)
+
+    def encoded_crops(self) -> int:
+        """Crops the recognise calls have put through the encoder so far (include/mocr.h, "shared encodings")."""
+        return int(self.lib.mocr_encoded_crops(self._h))
+
     def _blocks(self, n: int, scores: bool, alternatives: bool, positions: bool):
         """The output blocks of a recognise call: (ids, lens, logp, alt_ids, alt_logp, pos), None where not asked - what
         the engine is then passed as null.  The alternatives come as the engine leaves unwritten positions: -1 / 0."""
@@ -216,7 +242,7 @@ class Engine:
         return sets, ngram
 
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False,
-                         token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None):
+                         token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None):
         """Crops of any sizes (list of uint8 [h,w] / [h,w,3] arrays; `bgr`: 3-channel crops are in OpenCV order;
         `rotate`: per crop 0 / 1 (90 degrees clockwise) / 2 (counter-clockwise), applied on the device): luminance
         conversion and the Pillow-exact BILINEAR resize to 224x224 run on the device.
@@ -232,13 +258,23 @@ class Engine:
         (cx, cy), spread (sx, sy) and patch mass of the last decoder layer's cross-attention, in fractions of the 224 x 224
         plane the encoder sees (include/mocr.h, "token positions"); same ids, scores and alternatives.
         ``prefixes``: per crop a sequence of token ids (or None) the row starts with, behind the start token; the engine
-        scores them and continues greedily (include/mocr.h, "forced prefixes")."""
+        scores them and continues greedily (include/mocr.h, "forced prefixes").
+        ``sources``: a flat sequence of ints, one per output ROW - row r decodes ``images[sources[r]]``, which is encoded
+        once however many rows name it (include/mocr.h, "shared encodings").  The outputs then have ``len(sources)`` rows,
+        and ``token_sets`` / ``no_repeat_ngram`` / ``prefixes`` are per row."""
         n = len(images)
+        if sources is not None:
+            src = self._sources(sources, n)
+            n = int(src.size)
         blocks = self._blocks(n, scores, alternatives, positions)
         if n > 0:
             descs, keep = self._image_descs(images, bgr, rotate)
             sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
-            if prefixes is not None:
+            if sources is not None:
+                pre, plen, ld = self._prefix_args(prefixes, n)
+                self._check(self.lib.mocr_recognize_images_shared(self._h, descs, len(keep), n, _ptr(src), *map(_ptr, blocks[:5]),
+                                                                  _ptr(sets), _ptr(ngram), _ptr(blocks[5]), _ptr(pre), _ptr(plen), ld))
+            elif prefixes is not None:
                 pre, plen, ld = self._prefixes(prefixes, n)
                 self._check(self.lib.mocr_recognize_images_prefix(self._h, descs, n, *map(_ptr, blocks[:5]), _ptr(sets), _ptr(ngram),
                                                                   _ptr(blocks[5]), _ptr(pre), _ptr(plen), ld))
@@ -248,7 +284,7 @@ class Engine:
         return self._result(blocks, scores, alternatives, positions)
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False,
-                          token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None):
+                          token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None):
         """pages: list of uint8 [H,W,3] (or [H,W]) arrays; regions: iterable of (page_index, x, y, w, h) bounding
         rectangles.  Each page is uploaded once; the 8 %-padded, page-clipped crop of every region
         (``src/ui/main_window.py:9530-9540``) is cut on the device.  Returns (ids [n,max_len], lengths [n]);
@@ -258,17 +294,27 @@ class Engine:
         ``no_repeat_ngram``: a no-repeat n-gram size for every region, or one per region (see recognize_images).
         ``positions=True``: one more, last element pos float32 [n,max_len,5] (see recognize_images), in fractions of the
         region's padded, clipped rectangle (manga_ocr.regions.padded_rect); a sliver's rows all 0.
-        ``prefixes``: per region a forced prefix or None (see recognize_images); a sliver ignores its prefix."""
+        ``prefixes``: per region a forced prefix or None (see recognize_images); a sliver ignores its prefix.
+        ``sources``: one region index per output ROW (see recognize_images): the outputs have ``len(sources)`` rows, the
+        per-region arguments are per row, and every row of a sliver region has length 0."""
         regs = list(regions)
-        n = len(regs)
+        n = n_regions = len(regs)
+        if sources is not None:
+            src = self._sources(sources, n_regions)
+            n = int(src.size)
         blocks = self._blocks(n, scores, alternatives, positions)
         if n > 0:
             descs, keep = self._image_descs(pages, bgr)
-            arr = (_capi.MocrRegion * n)()
+            arr = (_capi.MocrRegion * n_regions)()
             for i, (pg, x, y, w, h) in enumerate(regs):
                 arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
             sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
-            if prefixes is not None:
+            if sources is not None:
+                pre, plen, ld = self._prefix_args(prefixes, n)
+                self._check(self.lib.mocr_recognize_regions_shared(self._h, descs, len(keep), arr, n_regions, n, _ptr(src),
+                                                                   *map(_ptr, blocks[:5]), _ptr(sets), _ptr(ngram), _ptr(blocks[5]),
+                                                                   _ptr(pre), _ptr(plen), ld))
+            elif prefixes is not None:
                 pre, plen, ld = self._prefixes(prefixes, n)
                 self._check(self.lib.mocr_recognize_regions_prefix(self._h, descs, len(keep), arr, n, *map(_ptr, blocks[:5]), _ptr(sets),
                                                                    _ptr(ngram), _ptr(blocks[5]), _ptr(pre), _ptr(plen), ld))
@@ -303,13 +349,24 @@ class Engine:
         return out
 
     def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None, d_out_alt_ids=None, d_out_alt_logp=None, *,
-                         token_sets=None, no_repeat_ngram=None, d_out_pos=None, prefixes=None) -> None:
+                         token_sets=None, no_repeat_ngram=None, d_out_pos=None, prefixes=None, sources=None) -> None:
         """Asynchronous; all are device buffers (torch CUDA tensors or raw addresses).  ``d_out_logp`` (float32
         [n,max_len]): also the token log-probabilities.  ``d_out_alt_ids`` (int32) with ``d_out_alt_logp`` (float32), both
         [n,max_len,4]: also the token alternatives.  ``token_sets``: a set handle for every crop, or one per crop (host values).
         ``no_repeat_ngram``: a no-repeat n-gram size for every crop, or one per crop (host values).
         ``d_out_pos`` (float32 [n,max_len,5]): also the token positions.  ``prefixes``: per crop a forced prefix or None (host
-        values, copied by the call)."""
+        values, copied by the call).  ``sources``: one plane index per output ROW (host values, see recognize_images) -
+        ``n`` then counts the planes of ``d_gray``, the output buffers have ``len(sources)`` rows and the per-crop arguments
+        are per row."""
+        if sources is not None:
+            src = self._sources(sources, n)
+            rows = int(src.size)
+            sets, ngram = self._per_crop(token_sets, no_repeat_ngram, rows)
+            pre, plen, ld = self._prefix_args(prefixes, rows)
+            self._check(self.lib.mocr_recognize_device_shared(self._h, _ptr(d_gray), n, rows, _ptr(src), _ptr(d_out_ids), _ptr(d_out_len),
+                                                              _ptr(d_out_logp), _ptr(d_out_alt_ids), _ptr(d_out_alt_logp), _ptr(sets),
+                                                              _ptr(ngram), _ptr(d_out_pos), _ptr(pre), _ptr(plen), ld))
+            return
         sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
         if prefixes is not None:
             pre, plen, ld = self._prefixes(prefixes, n)
@@ -325,11 +382,22 @@ class Engine:
         self._check(self.lib.mocr_set_generate_max_length(self._h, int(max_len)))
 
     def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False, alternatives: bool = False,
-                       token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None):
+                       token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None):
+        """Luminance planes uint8 [n,224,224] (host), generate(max_length) ``max_len``; the keywords as for recognize_images
+        (``sources``: one plane index per output row)."""
         a = np.ascontiguousarray(gray, dtype=np.uint8)
-        n = a.shape[0]
+        n = n_planes = a.shape[0]
+        if sources is not None:
+            src = self._sources(sources, n_planes)
+            n = int(src.size)
         sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
         blocks = self._blocks(n, scores, alternatives, positions)
+        if sources is not None:
+            pre, plen, ld = self._prefix_args(prefixes, n)
+            self._check(self.lib.mocr_recognize_gray_host_shared(self._h, _ptr(a), n_planes, n, _ptr(src), max_len or self.spec.max_len,
+                                                                 *map(_ptr, blocks[:5]), _ptr(sets), _ptr(ngram), _ptr(blocks[5]),
+                                                                 _ptr(pre), _ptr(plen), ld))
+            return self._result(blocks, scores, alternatives, positions)
         if prefixes is not None:
             pre, plen, ld = self._prefixes(prefixes, n)
             self._check(self.lib.mocr_recognize_gray_host_prefix(self._h, _ptr(a), n, max_len or self.spec.max_len, *map(_ptr, blocks[:5]),
@@ -450,6 +518,10 @@ class Engine:
         """The positions kernel on device buffers (include/mocr.h mocr_op_attn_positions)."""
         self._check(self.lib.mocr_op_attn_positions(self._h, _ptr(d_q), _ptr(d_k), _ptr(d_len), int(rows), int(T), _ptr(d_out_pos),
                                                     _ptr(d_out_map)))
+
+    def op_enc_expand(self, d_enc, d_src_of_row, n_src: int, n_rows: int) -> None:
+        """The expansion of shared encodings on a device buffer (include/mocr.h mocr_op_enc_expand)."""
+        self._check(self.lib.mocr_op_enc_expand(self._h, _ptr(d_enc), _ptr(d_src_of_row), int(n_src), int(n_rows)))
 
     def op_ngram_init(self, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows: int) -> None:
         """Start of a batch with no-repeat n-grams: every row's mask = its base set (n = 1: minus the start token)."""

@@ -774,6 +774,92 @@ class MangaOcr:
             raise ValueError(f"score_texts: {len(images)} crops but {len(texts)} texts")
         return self.recognize_batch_scored(images, prefix=[self._text_prefix(t) for t in texts])
 
+    # ------------------------------------------------------------------ shared encodings: many rows of one crop
+    def _check_shared(self) -> None:
+        no = getattr(self.engine, "NO_PREFIX", None)      # MultiGpuEngine: the workers make the plain greedy call
+        if no:
+            raise NotImplementedError(no)
+
+    def score_candidates(self, img_or_path, texts) -> List[Recognition]:
+        """``score_text`` for many texts of ONE crop, in the order given: every text (a ``str`` or token ids) is forced through
+        EOS and scored, so ``Recognition.logprob`` is ``log p(text | crop)``.  One engine call; the crop is encoded once for
+        all of its rows (include/mocr.h, "shared encodings")."""
+        self._check_scored()
+        self._check_shared()
+        prefixes = [self._text_prefix(t) for t in texts]
+        if not prefixes:
+            return []
+        crop = to_pixels(self._open(img_or_path))
+        kw = self._decode_kw(None, None, len(prefixes), prefixes)
+        out = self.engine.recognize_images([crop], scores=True, sources=[0] * len(prefixes), **kw)
+        return self._mark_forced(self._recognitions(*out), kw.get("prefixes"))
+
+    @staticmethod
+    def _nbest_branches(rec: Recognition, count: int) -> List[Tuple[int, int]]:
+        """The ``count`` cheapest single-token deviations (t, j) of an alternatives row: generated position ``t`` before the
+        row's last one, candidate ``j >= 1`` with a token and a finite log-probability; cost ``alt_logprobs[t, 0] -
+        alt_logprobs[t, j]``, ties to the lower ``t``, then the lower ``j``."""
+        found = []
+        for t in range(len(rec.alt_ids) - 1):
+            top = float(rec.alt_logprobs[t, 0])
+            for j in range(1, rec.alt_ids.shape[1]):
+                lp = float(rec.alt_logprobs[t, j])
+                if rec.alt_ids[t, j] >= 0 and np.isfinite(lp):
+                    found.append((top - lp, t, j))
+        found.sort()
+        return [(t, j) for _, t, j in found[:max(count, 0)]]
+
+    def recognize_batch_nbest(self, images: Sequence, k: int = 4, *, allowed=None, no_repeat_ngram=None) -> List[List[Recognition]]:
+        """Up to ``k`` readings per crop, most probable first, in two engine calls for the whole batch.  Call 1 decodes every
+        crop greedily with alternatives.  Call 2 takes, per crop, the ``k - 1`` cheapest single-token deviations from that
+        reading - position ``t`` before the row's last, candidate ``j >= 1``, cost ``alt_logprobs[t, 0] - alt_logprobs[t, j]`` -
+        and continues each greedily from ``Recognition.branch(t, j)``, scored, all crops' branches in one call that encodes
+        every crop once (include/mocr.h, "shared encodings").  A crop's result is its greedy row plus the continuations,
+        rows with equal ids dropped (the first kept), sorted by ``logprob`` descending (ties in that order of construction):
+        at most ``k`` entries, fewer when fewer deviations exist; ``k = 1`` is the greedy row and makes no second call.
+        ``allowed`` / ``no_repeat_ngram`` apply to both calls, per crop.
+
+        This is NOT beam search and is not guaranteed to hold the ``k`` most probable sequences: it holds the greedy reading
+        and the ``k - 1`` cheapest one-token departures from it, each continued greedily."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"recognize_nbest: k must be an int >= 1, instead got {k!r}")
+        self._check_alternatives()
+        if k > 1:
+            self._check_shared()
+        crops = [to_pixels(im) for im in images]
+        if not crops:
+            return []
+        kw = self._decode_kw(allowed, no_repeat_ngram, len(crops))
+        first = self._recognitions_alt(*self.engine.recognize_images(crops, alternatives=True, **kw))
+        results = [[r] for r in first]
+        prefixes, owner = [], []
+        if k > 1:
+            for c, rec in enumerate(first):
+                for t, j in self._nbest_branches(rec, k - 1):
+                    prefixes.append(rec.branch(t, j))
+                    owner.append(c)
+        if prefixes:
+            used = sorted(set(owner))       # a crop without a deviation (a one-token row) is not sent again
+            place = {c: i for i, c in enumerate(used)}
+            kw2 = {name: [vals[c] for c in owner] for name, vals in kw.items()}
+            out = self.engine.recognize_images([crops[c] for c in used], scores=True, prefixes=prefixes,
+                                               sources=[place[c] for c in owner], **kw2)
+            for c, rec in zip(owner, self._mark_forced(self._recognitions(*out), prefixes)):
+                results[c].append(rec)
+        ranked = []
+        for rows in results:
+            kept = []
+            for r in rows:
+                if not any(np.array_equal(r.ids, q.ids) for q in kept):
+                    kept.append(r)
+            kept.sort(key=lambda r: -r.logprob)     # (stable: ties keep the order of construction)
+            ranked.append(kept[:k])
+        return ranked
+
+    def recognize_nbest(self, img_or_path, k: int = 4, *, allowed=None, no_repeat_ngram=None) -> List[Recognition]:
+        """``recognize_batch_nbest`` for one crop."""
+        return self.recognize_batch_nbest([self._open(img_or_path)], k, allowed=allowed, no_repeat_ngram=no_repeat_ngram)[0]
+
     def recognize_page(self, page_bgr: np.ndarray, regions):
         """``_collect_manga_detections`` for one page: ``regions`` = the detector's (text, polygon) pairs."""
         from .regions import recognize_page
