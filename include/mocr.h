@@ -723,6 +723,62 @@ int mocr_profile_enable(mocr_engine* e, int32_t on); /* on: record an event pair
 int mocr_profile_reset(mocr_engine* e);
 int mocr_profile_get(mocr_engine* e, mocr_kernel_stat* out, int32_t cap, int32_t* n_out);
 
+/* ---- beam search -------------------------------------------------------------------------- */
+/* generate(num_beams = K, length_penalty, early_stopping, no_repeat_ngram_size) of transformers 5.x
+ * (GenerationMixin._beam_search, do_sample = False), per crop: every step takes log_softmax over the full row, sets the
+ * tokens the beam's own history bans to -inf (no renormalising), adds the beam's running score (they start as
+ * [0, -1e9, ...]) and keeps the 2 K best of the K x vocab accumulated scores.  A candidate stops when its token is EOS or
+ * completes generate(max_length) tokens; the next running beams are the best K that did not stop; the stopped ones among
+ * the first K enter the finished set with score / (tokens generated) ^ length_penalty; the early-stop heuristic and the
+ * end condition are the reference's for early_stopping false / true / "never".
+ * TIES: equal accumulated scores go to the lower flat index beam * vocab + token; a new finished sequence whose score
+ * equals one already in the set goes behind it.  (torch.topk promises no order, so nothing should rely on an exact tie.)
+ * Beam k of crop c is decode row c K + k: a request of n crops is n K rows over n encodings (one encoder pass per crop),
+ * so n * K <= max_batch.  A beam request carries no token sets, prefixes, positions, alternatives or source array. */
+#define MOCR_MAX_BEAMS 4
+typedef struct mocr_beam_config {
+    int32_t num_beams;              /* K: 2 .. MOCR_MAX_BEAMS */
+    float length_penalty;
+    int32_t early_stopping;         /* 0 false, 1 true, 2 "never" */
+    int32_t no_repeat_ngram_size;   /* 0 = off */
+} mocr_beam_config;
+/* Outputs (host, except the device twin's): out_ids [n][K][max_len] int32, out_len [n][K] int32, out_score [n][K] float32 =
+ * the crop's K finished hypotheses, hypothesis 0 the best, with the reference's sequences_scores.  A slot that never
+ * received a finished sequence has len 0 and score -1e9; ids behind a hypothesis' length are pad_id.  Bad arguments
+ * (K outside 2 .. MOCR_MAX_BEAMS, n * K > max_batch, early_stopping outside 0 .. 2, a negative n-gram size, a null
+ * pointer) return MOCR_ERR_ARG before any work. */
+int mocr_recognize_images_beam(mocr_engine* e, const mocr_image* images, int32_t n, const mocr_beam_config* beam,
+                               int32_t* out_ids, int32_t* out_len, float* out_score);
+/* (a sliver region's K slots read pad_id / 0 / -1e9) */
+int mocr_recognize_regions_beam(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                int32_t n_regions, const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len, float* out_score);
+int mocr_recognize_gray_host_beam(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override,
+                                  const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len, float* out_score);
+/* device pointers, asynchronous like mocr_recognize_device */
+int mocr_recognize_device_beam(mocr_engine* e, const void* d_gray, int32_t n, const mocr_beam_config* beam, void* d_out_ids,
+                               void* d_out_len, void* d_out_score);
+
+/* Bytes of beam state this engine holds, over its lanes (test hook): 0 until a lane runs its first beam batch - creating an
+ * engine and greedy calls of any kind allocate none of it. */
+int64_t mocr_beam_state_bytes(mocr_engine* e);
+/* The first n entries of a lane's decode slot -> row map as its last batch left it (test hook; all lanes idle first): behind
+ * a compacted beam batch the K rows of a crop still sit in K neighbouring slots, in beam order, from a slot that is a
+ * multiple of K. */
+int mocr_lane_rowmap(mocr_engine* e, int32_t lane, int32_t* out_rowmap, int32_t n);
+
+/* The selection that ends a beam step (kernel unit tests): the token-step arguments on the slab path (no first, forced or
+ * candidate form; a->n slots = groups of K, a trailing partial group is padding), plus the beam state by ROW like ids:
+ * d_beam_score / d_parent / d_hyp_len / d_hyp_score [rows], d_hyp_ids [rows][ids_ld], d_heuristic_open [rows / K]. */
+int mocr_op_beam_select(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score,
+                        int32_t* d_parent, int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open);
+/* The cache reorder behind it: d_cache viewed as [layers][rows][segs][positions][pos_bytes] through byte strides; for
+ * every group of K slots whose crop is live (d_finished[rowmap[g K]] == 0), row rowmap[g K + k] <- row
+ * rowmap[g K + d_parent[rowmap[g K + k]]], bytes 0 .. d_step[g K] * pos_bytes - 1 of every (layer, segment).  max_pos bounds
+ * every step (the grid). */
+int mocr_op_beam_permute(mocr_engine* e, void* d_cache, int32_t layers, int64_t layer_stride, int64_t row_stride, int32_t segs,
+                         int64_t seg_stride, int32_t pos_bytes, int32_t K, const int32_t* d_parent, const int32_t* d_rowmap,
+                         const int32_t* d_finished, const int32_t* d_step, int32_t n_slots, int32_t max_pos);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,3 +191,38 @@ __device__ __forceinline__ void top4_merge_xor(Top4& l, int xor_mask) {
     top4_order(l, 0, 2); top4_order(l, 1, 3);
     top4_order(l, 0, 1); top4_order(l, 2, 3);
 }
+
+// Top4's order for lists of any length (beam search keeps the 2 K best of K x V accumulated scores, kernels_beam.h): value
+// descending, the lower index first among equal values; unfilled entries are (-inf, 0x7fffffff), a NaN never enters.
+template <int N> struct TopN {
+    float v[N];
+    int i[N];
+};
+
+template <int N> __device__ __forceinline__ void topn_clear(TopN<N>& l) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) { l.v[k] = -INFINITY; l.i[k] = 0x7fffffff; }
+}
+
+// the same branch-free insertion as top4_insert
+template <int N> __device__ __forceinline__ void topn_insert(TopN<N>& l, float v, int i) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const bool c = (v > l.v[k]) | ((v == l.v[k]) & (i < l.i[k]));
+        const float tv = c ? l.v[k] : v;
+        const int ti = c ? l.i[k] : i;
+        l.v[k] = c ? v : l.v[k];
+        l.i[k] = c ? i : l.i[k];
+        v = tv; i = ti;
+    }
+}
+
+// l = the N best of l and of the list the lane `xor_mask` away holds (both lanes end with the same list): the other lane's
+// entries are inserted one by one.  The two lists never share an index, so no entry is taken twice.
+template <int N> __device__ __forceinline__ void topn_merge_xor(TopN<N>& l, int xor_mask) {
+    TopN<N> o;
+#pragma unroll
+    for (int k = 0; k < N; ++k) { o.v[k] = __shfl_xor(l.v[k], xor_mask, 64); o.i[k] = __shfl_xor(l.i[k], xor_mask, 64); }
+#pragma unroll
+    for (int k = 0; k < N; ++k) topn_insert(l, o.v[k], o.i[k]);
+}

@@ -49,6 +49,7 @@
 #include "kernels_misc.h"
 #include "kernels_positions.h"
 #include "kernels_share.h"
+#include "kernels_beam.h"
 
 namespace {
 
@@ -149,6 +150,10 @@ struct LaneCtx {
     // shared encodings: allocated by the first batch with a job that shares (ensure_share_buffer)
     int* src_of_row = nullptr;                      // [Bp] the encoder row (crop of the batch) every decode row reads, by row like ids
     size_t ctx_cap = 0;                             // bytes CTX was allocated with: a sharing batch stages its encodings there (expand_encodings)
+    // beam search: allocated by the first beam batch (ensure_beam_buffers); all by row like ids (kernels_beam.h: BeamState)
+    float *beam_score = nullptr, *hyp_score = nullptr;    // [Bp]
+    int *beam_parent = nullptr, *hyp_len = nullptr, *heuristic_open = nullptr;      // [Bp] ([Bp / 2] used of the last)
+    int* hyp_ids = nullptr;                         // [Bp][max_len]
     float *x_f32 = nullptr, *a_f32 = nullptr, *c_f32 = nullptr;
     float* ln_stats = nullptr;                      // small-batch path: (mean, rstd) per row of the three pre-LayerNorm sums, [3][Bp][2]
     void *x_t = nullptr, *a_t = nullptr, *c_t = nullptr, *ctx_t = nullptr, *h_t = nullptr, *z_t = nullptr;
@@ -187,7 +192,16 @@ struct Job {
     std::vector<int32_t> prefix_len;    // forced prefixes (the *_prefix entry points): one length per crop; empty = all 0
     std::vector<int32_t> prefix;        // ... and the tokens, [n][prefix_ld] (a copy: the caller's arrays need not outlive the call)
     int prefix_ld = 0;
+    // beam search (the *_beam entry points; beam.num_beams = 0: a greedy job): n = crops x K rows that share the crops'
+    // encodings, out_ids / out_len receive the finished hypotheses [crops][K] and out_score their scores
+    mocr_beam_config beam{};
+    float* out_score = nullptr;
 };
+
+static bool same_beam(const mocr_beam_config& a, const mocr_beam_config& b) {
+    return a.num_beams == b.num_beams && a.length_penalty == b.length_penalty && a.early_stopping == b.early_stopping &&
+           a.no_repeat_ngram_size == b.no_repeat_ngram_size;
+}
 
 // The kind of decode steps a batch runs: the richest of what its jobs asked for.  Every choice that follows from it - the
 // LM-head epilogue, the token kernel, the profile names, the decode-graph key - is made from this one value.
@@ -201,8 +215,13 @@ struct DecMode {
     bool positions = false;         // a job asked for token positions: the steps record pos_hist, finish_batch runs the deferred pass
     bool prefix = false;            // a row has a forced prefix: the steps run scored and masked (level >= 1, mask; unconstrained rows read
                                     // set 0), the LM head also leaves the forced column's value and the token kernel stores the forced token
-    // a graph captured in one mode is never replayed in another: the mode's share of the decode-graph key (6 bits)
-    int key_bits() const { return level + (mask ? 4 : 0) + (ngram ? 8 : 0) + (positions ? 16 : 0) + (prefix ? 32 : 0); }
+    bool beam = false;              // a beam-search batch (all of its jobs, with one configuration): the steps end in the selection and
+                                    // the cache reorder instead of the token kernel, the LM head always in its slab form
+    mocr_beam_config beam_cfg{};
+    // a graph captured in one mode is never replayed in another: the mode's share of the decode-graph key (6 bits; a beam
+    // batch: bit 6, and its configuration - kernel arguments of the captured launches - in the bits above, beam_key)
+    int key_bits() const { return level + (mask ? 4 : 0) + (ngram ? 8 : 0) + (positions ? 16 : 0) + (prefix ? 32 : 0) + (beam ? 64 : 0); }
+    static constexpr int KEY_SPAN = 128;
     int epilogue() const { return mask ? (level == 2 ? EPI_TOPK_M : level == 1 ? EPI_ARGMAX_LSE_M : EPI_ARGMAX_M)
                                        : (level == 2 ? EPI_TOPK : level == 1 ? EPI_ARGMAX_LSE : EPI_ARGMAX); }
     // profile names of the fused LM head and of the token kernel
@@ -228,6 +247,8 @@ static DecMode mode_of(const std::vector<Job>& jobs) {
     }
     if (m.prefix) m.level = std::max(m.level, 1);      // a forced token is one more per-row fact of the masked, scored step
     m.mask = m.mask || m.ngram || m.prefix;     // the bans are applied through the rows' masks, which start as the rows' sets
+    // beam search: pump_once never mixes - a batch is all beam jobs of one configuration, or has none
+    if (!jobs.empty() && jobs.front().beam.num_beams > 0) { m.beam = true; m.beam_cfg = jobs.front().beam; }
     return m;
 }
 
@@ -281,7 +302,9 @@ struct mocr_engine : LaneCtx {
     int rrows(int n) const { return regime > 0 ? regime : n; }
     bool use_latent(int n) const { return latent && n > classic_rows; }
     int smallm_rows = 0;            // bf16: batches of up to this many rows take the one-launch-per-projection path (kernels_smallm.h)
-    bool use_smallm(int n) const { return n <= smallm_rows && !use_latent(n); }
+    bool beam_batch = false;        // the batch being scheduled is a beam batch (set with `regime`): no one-launch-per-projection path
+    bool use_smallm(int n) const { return n <= smallm_rows && !use_latent(n) && !beam_batch; }
+    std::vector<mocr_beam_config> beam_cfgs;    // the beam configurations seen: a decode graph bakes one in, its key names it by index
     std::map<std::string, std::vector<float>> host_w;
     std::map<std::string, std::vector<int64_t>> host_shape;
     std::vector<void*> allocs;
@@ -1212,6 +1235,88 @@ void dec_token(mocr_engine* e, const DecState& st, int nslab, int n, int ncand =
     launch_dec_token<T, FIRST>(e, st, a, n);
 }
 
+// ---- beam search: the selection and the cache reorder that end a beam step (kernels_beam.h) ----
+static BeamState make_beam_state(mocr_engine* e, const mocr_beam_config& c) {
+    BeamState bs{};
+    bs.beam_score = e->beam_score; bs.parent = e->beam_parent;
+    bs.hyp_ids = e->hyp_ids; bs.hyp_len = e->hyp_len; bs.hyp_score = e->hyp_score; bs.heuristic_open = e->heuristic_open;
+    bs.length_penalty = c.length_penalty; bs.early_stopping = c.early_stopping; bs.ngram = c.no_repeat_ngram_size;
+    return bs;
+}
+
+// n decode slots = groups of K (a trailing partial group is padding); the LM head's slabs, by slot, are in `a`
+template <typename T>
+void launch_beam_select(mocr_engine* e, const DecState& st, const BeamState& bs, const DecTokenArgs& a, int n, int K) {
+    auto& w = e->w;
+    if (e->D != 768 || e->V != 6144 || st.ids_ld > BEAM_HIST || st.max_len > st.ids_ld || a.nslab < 1)
+        throw ArgError{"beam search needs hidden 768, vocab 6144 and max_len <= 320", MOCR_ERR_UNSUPPORTED};
+    ProfScope ps(e, "beam_select", 0, (double)n * e->V * 4 * a.nslab);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((n + K - 1) / K), dim3(256), 0, e->stream, a.slabs, a.nslab, a.slab_stride, a.vbias, e->V, st, bs, n,
+                           w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32, reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps,
+                           reinterpret_cast<T*>(a.cache), a.cstride, a.cache8, a.inv8);
+    };
+    switch (K) {
+        case 2: launch(beam_select_kernel<T, 2>); break;
+        case 3: launch(beam_select_kernel<T, 3>); break;
+        case 4: launch(beam_select_kernel<T, 4>); break;
+        default: throw ArgError{"num_beams must be 2 .. 4", MOCR_ERR_ARG};
+    }
+    HIPCHECK(hipGetLastError());
+}
+
+// max_pos bounds every slot's step (positions 0 .. step - 1 move): it sizes the grid
+static void launch_beam_permute(mocr_engine* e, const BeamPermuteView& v, int layers, int K, const int* parent, const int* rowmap,
+                                const int* finished, const int* step, int n, int max_pos) {
+    if (v.pos_bytes < 16 || v.pos_bytes % 16 || layers < 1 || v.segs < 1 || max_pos < 1)
+        throw ArgError{"beam_permute: positions of whole 16-byte pieces", MOCR_ERR_ARG};
+    const int groups = n / K;
+    if (groups < 1) return;
+    const long long pieces = (long long)max_pos * v.pos_bytes / 16;
+    const dim3 grid((unsigned)groups, (unsigned)(layers * v.segs), (unsigned)((pieces + 255) / 256));
+    ProfScope ps(e, "beam_permute", 0, 2.0 * n * layers * v.segs * (double)max_pos * v.pos_bytes);
+    switch (K) {
+        case 2: hipLaunchKernelGGL(beam_permute_kernel<2>, grid, dim3(256), 0, e->stream, v, parent, rowmap, finished, step, n, max_pos); break;
+        case 3: hipLaunchKernelGGL(beam_permute_kernel<3>, grid, dim3(256), 0, e->stream, v, parent, rowmap, finished, step, n, max_pos); break;
+        case 4: hipLaunchKernelGGL(beam_permute_kernel<4>, grid, dim3(256), 0, e->stream, v, parent, rowmap, finished, step, n, max_pos); break;
+        default: throw ArgError{"num_beams must be 2 .. 4", MOCR_ERR_ARG};
+    }
+    HIPCHECK(hipGetLastError());
+}
+
+// The end of a beam step on the engine's buffers: the selection over the LM head's slabs, then the reorder of whichever
+// self-attention cache the batch's regime keeps (latent rows, their e4m3 form, or the classic K and V).
+template <typename T>
+void beam_finish_step(mocr_engine* e, const DecState& st, const DecMode& m, int nslab, int n, int t) {
+    const int K = m.beam_cfg.num_beams;
+    const bool lat = e->use_latent(e->rrows(n));
+    DecTokenArgs a{};
+    a.slabs = e->slabs; a.nslab = nslab; a.slab_stride = (long long)e->Bp * e->V; a.vbias = e->w.bv;
+    a.x_f32 = e->x_f32; a.x_t = e->x_t;
+    a.cache = (lat && !e->fp8attn) ? e->xcache : nullptr;
+    a.cache8 = (lat && e->fp8attn) ? e->x8cache : nullptr;
+    a.inv8 = (lat && e->fp8attn) ? 1.0f / e->w.sx_self[0] : 0.f;
+    a.cstride = (long long)e->cfg.max_len * e->D;
+    launch_beam_select<T>(e, st, make_beam_state(e, m.beam_cfg), a, n, K);
+    // `t` bounds the step index of this launch from above only when it is exact (eager steps).  A captured graph passes
+    // t = t_hi - 1 for every step of its bucket (decode_graph), and the bucket's last device step is t_hi itself
+    // (t0 + steps <= 32 * bucket): behind it `step` is t_hi + 1 = t + 2 positions.  The grid is sized for that; the kernel
+    // moves `step` positions, never more than the grid covers, and a live crop's step is below max_len.
+    const int layers = e->cfg.dec_layers, max_pos = std::min(t + 2, st.max_len - 1);
+    const long long ML = e->cfg.max_len;
+    if (lat) {
+        const long long pb = e->fp8attn ? e->D : (long long)e->D * sizeof(T);
+        BeamPermuteView v{reinterpret_cast<char*>(e->fp8attn ? (void*)e->x8cache : e->xcache), (long long)e->Bp * ML * pb, ML * pb, 0, 1, (int)pb};
+        launch_beam_permute(e, v, layers, K, e->beam_parent, e->rowmap, e->finished, e->step, n, max_pos);
+    } else {
+        const long long pb = 64 * (long long)sizeof(T);
+        for (void* base : {e->kcache, e->vcache}) {
+            BeamPermuteView v{reinterpret_cast<char*>(base), (long long)e->Bc * e->H * ML * pb, (long long)e->H * ML * pb, ML * pb, e->H, (int)pb};
+            launch_beam_permute(e, v, layers, K, e->beam_parent, e->rowmap, e->finished, e->step, n, max_pos);
+        }
+    }
+}
+
 // non-temporal K/V loads from about 128 rows (see dec_attn_params)
 static bool dec_attn_nt(const mocr_engine* e, int n) {
     static const int nt_rows = env_int("MOCR_ATTN_NT_ROWS", 128);
@@ -1593,7 +1698,7 @@ void decode_step_smallm(mocr_engine* e, const DecState& st, const DecMode& m, in
 template <typename T>
 void decode_step(mocr_engine* e, const DecState& st, const DecMode& m, int n, int t) {
     if constexpr (sizeof(T) == 2) {
-        if (e->use_smallm(e->rrows(n))) { decode_step_smallm(e, st, m, n, t); return; }
+        if (!m.beam && e->use_smallm(e->rrows(n))) { decode_step_smallm(e, st, m, n, t); return; }
     }
     const int D = e->D, F = e->F;
     auto& w = e->w;
@@ -1640,6 +1745,11 @@ void decode_step(mocr_engine* e, const DecState& st, const DecMode& m, int n, in
     // LM head.  When the GEMM is not split over K and nobody asked for the logits, its epilogue reduces every N-tile
     // to (max, column) and the token kernel picks among V/tile candidates: the [n, V] fp32 logits (100 MB at 4096
     // rows) are neither written nor read.  acc + bias is the same fp32 value either way, so the argmax is identical.
+    if (m.beam) {       // beam search: the selection needs whole rows - always the slab form of the LM head
+        ns = dec_gemm<T>(e, "gemm_dec_vocab", e->z_t, D, w.wv, e->V, D, n);
+        beam_finish_step<T>(e, st, m, ns, n, t);
+        return;
+    }
     const int vt = dec_launch_tile(e, n);
     if (!st.logits_out && !(e->cfg.flags & MOCR_FLAG_NO_FUSED_ARGMAX) && tile_is(vt, GemmKind::Tile) &&
         pick_split(e->V, D, 128 / (int)sizeof(T), rn, e->slab_cap / e->Bp) == 1) {
@@ -1699,7 +1809,18 @@ hipGraphExec_t decode_graph(mocr_engine* e, const DecState& st, const DecMode& m
     const int bucket = need <= 3 ? 3 : need <= 5 ? 5 : need <= 8 ? 8 : 10;
     const int t_hi = std::min(bucket * 32, st.max_len) - 1;      // largest context this bucket covers
     // ... and by the mode of the steps: another LM-head epilogue, token kernel, set of pointers or launch each
-    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * 64 + m.key_bits(), steps, e->rrows(n));
+    int beam_key = 0;                // a beam batch: which configuration the captured launches carry (1-based, above the mode bits)
+    if (m.beam) {
+        auto& cfgs = e->beam_cfgs;
+        size_t i = 0;
+        while (i < cfgs.size() && !same_beam(cfgs[i], m.beam_cfg)) ++i;
+        if (i == cfgs.size()) {
+            if (i >= 100) throw ArgError{"more than 100 distinct beam configurations on one engine", MOCR_ERR_UNSUPPORTED};
+            cfgs.push_back(m.beam_cfg);
+        }
+        beam_key = ((int)i + 1) << 24;
+    }
+    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * DecMode::KEY_SPAN + m.key_bits() + beam_key, steps, e->rrows(n));
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) return it->second;
     hipGraph_t g = nullptr;
@@ -1901,6 +2022,15 @@ static void ensure_share_buffer(mocr_engine* e) {
 
 // out[r] = in[d_src_of_row[r]] for r < rows, rows of S x D elements of the engine's dtype; `in` holds n_src of them and is
 // not `out` (kernels_share.h).
+// The beam state of the bound lane: allocated by the first beam batch, like the alternatives buffers.
+static void ensure_beam_buffers(mocr_engine* e) {
+    if (e->hyp_ids) return;
+    const size_t Bp = (size_t)e->Bp;
+    e->beam_score = e->dalloc<float>(Bp); e->hyp_score = e->dalloc<float>(Bp);
+    e->beam_parent = e->dalloc<int>(Bp); e->hyp_len = e->dalloc<int>(Bp); e->heuristic_open = e->dalloc<int>(Bp);
+    e->hyp_ids = e->dalloc<int>(Bp * e->cfg.max_len);
+}
+
 static void launch_enc_expand(mocr_engine* e, const void* in, void* out, const int* d_src_of_row, int n_src, int rows) {
     const size_t row_bytes = (size_t)e->S * e->D * e->esz;
     if (row_bytes % 16 || in == out) throw ArgError{"enc_expand: rows of whole 16-byte pieces, out of place", MOCR_ERR_UNSUPPORTED};
@@ -2018,6 +2148,14 @@ void start_batch(mocr_engine* e, Lane& L) {
     // whatever the workspace holds for them (finite values; no kernel mixes rows).
     DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n);
     dec_token<T, true>(e, st, 0, L.np);
+    // beam search: the start token's kernel is the greedy one; the beam state starts as [0, -1e9, ...] and an empty finished set
+    if (m.beam) {
+        ensure_beam_buffers(e);
+        ProfScope ps(e, "beam_init", 0, (double)L.np * e->cfg.max_len * 4);
+        hipLaunchKernelGGL(beam_init_kernel, dim3(L.np), dim3(64), 0, e->stream, make_beam_state(e, m.beam_cfg), m.beam_cfg.num_beams, L.np,
+                           e->cfg.max_len, e->cfg.pad_id);
+        HIPCHECK(hipGetLastError());
+    }
     L.t = 0; L.steps = L.max_len - 1; L.chunk = 0;
     L.finishing = false;
     L.flag_pending[0] = L.flag_pending[1] = false;
@@ -2030,6 +2168,13 @@ void finish_batch(mocr_engine* e, Lane& L) {
     int row0 = 0;
     for (const Job& j : L.jobs) {
         const hipMemcpyKind kind = j.out_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        if (j.beam.num_beams > 0) {      // beam search: the crops' finished sets, [crops][K] = the job's rows
+            HIPCHECK(hipMemcpyAsync(j.out_ids, e->hyp_ids + (size_t)row0 * e->cfg.max_len, (size_t)j.n * e->cfg.max_len * sizeof(int), kind, e->stream));
+            HIPCHECK(hipMemcpyAsync(j.out_len, e->hyp_len + row0, (size_t)j.n * sizeof(int), kind, e->stream));
+            HIPCHECK(hipMemcpyAsync(j.out_score, e->hyp_score + row0, (size_t)j.n * sizeof(float), kind, e->stream));
+            row0 += j.n;
+            continue;
+        }
         HIPCHECK(hipMemcpyAsync(j.out_ids, e->ids + (size_t)row0 * e->cfg.max_len, (size_t)j.n * e->cfg.max_len * sizeof(int), kind, e->stream));
         HIPCHECK(hipMemcpyAsync(j.out_len, e->len + row0, (size_t)j.n * sizeof(int), kind, e->stream));
         if (j.out_logp)
@@ -2165,7 +2310,9 @@ bool pump_once(mocr_engine* e) {
                 cap = std::min<long long>(cap, (rows_pending + parts - 1) / parts);
             }
             size_t take = 0;
-            while (take < e->pending.size() && e->pending[take].max_len == L.max_len &&
+            // (beam search: a batch is all beam jobs of one configuration, or has none)
+            const mocr_beam_config front_beam = e->pending.front().beam;
+            while (take < e->pending.size() && e->pending[take].max_len == L.max_len && same_beam(e->pending[take].beam, front_beam) &&
                    (take == 0 || L.n + e->pending[take].n <= cap) && L.n + e->pending[take].n <= e->cfg.max_batch) {
                 L.n += e->pending[take].n;
                 L.n_enc += e->pending[take].n_src;
@@ -2177,15 +2324,17 @@ bool pump_once(mocr_engine* e) {
             L.active = true;
             e->bind((int)i);
             e->regime = L.np0;
+            e->beam_batch = L.jobs.front().beam.num_beams > 0;
             start_batch<T>(e, L);
-            e->regime = 0;
+            e->regime = 0; e->beam_batch = false;
             e->unbind((int)i);
         }
         if (L.active) {
             e->bind((int)i);
             e->regime = L.np0;
+            e->beam_batch = L.mode.beam;
             advance<T>(e, L);
-            e->regime = 0;
+            e->regime = 0; e->beam_batch = false;
             e->unbind((int)i);
             any = true;
         }
@@ -2199,7 +2348,7 @@ void drive(mocr_engine* e) {
         if (e->cfg.dtype == MOCR_BF16) { while (pump_once<bf16_t>(e)) {} }
         else { while (pump_once<float>(e)) {} }
     } catch (...) {
-        e->regime = 0;
+        e->regime = 0; e->beam_batch = false;
         e->pending.clear();
         for (auto& L : e->lanes) { L.active = false; L.jobs.clear(); (void)hipStreamSynchronize(L.ctx.stream); }
         throw;
@@ -2755,6 +2904,10 @@ struct Request {
     // reads number r), and how many of those the call brings (-1: not said - as many as rows)
     const int32_t* source = nullptr;
     int32_t n_images = -1;
+    // beam search (the *_beam entry points; null: greedy): the rows are the crops' beams, K per crop through `source`, and
+    // out_score [rows] receives the hypotheses' scores
+    const mocr_beam_config* beam = nullptr;
+    float* out_score = nullptr;
 };
 
 // shared encodings: every index names an image of the call, and every image is named by a row
@@ -2814,6 +2967,11 @@ static void slice_job(Job& j, const Request& r, size_t base, int n, int max_len)
     j.out_alt_ids = r.out_alt_ids ? r.out_alt_ids + base * L * MOCR_ALTERNATIVES : nullptr;
     j.out_alt_logp = r.out_alt_logp ? r.out_alt_logp + base * L * MOCR_ALTERNATIVES : nullptr;
     j.out_pos = r.out_pos ? r.out_pos + base * L * MOCR_POSITION_FIELDS : nullptr;
+    j.beam = mocr_beam_config{}; j.out_score = nullptr;
+    if (r.beam) {       // a crop's K rows stay in one job: the callers cut a beam request at multiples of K only
+        if (base % r.beam->num_beams || n % r.beam->num_beams) throw ArgError{"a beam job is cut at multiples of num_beams", MOCR_ERR_STATE};
+        j.beam = *r.beam; j.out_score = r.out_score + base;
+    }
     j.sets = slice_rows(r.sets, base, n, MOCR_TOKEN_SET_ALL);
     j.ngram = slice_rows(r.ngram, base, n, 0);
     j.prefix_len = slice_rows(r.prefix_len, base, n, 0);
@@ -3168,7 +3326,8 @@ static void preprocess_images(mocr_engine* e, const mocr_image* imgs, int n, uin
 static void prepare_and_decode(mocr_engine* e, const std::vector<PrepSource>& srcs, const PrepView* views, int n, int32_t* out_ids,
                                int32_t* out_len, const Request& req) {
     const size_t plane = (size_t)e->cfg.image_size * e->cfg.image_size;
-    const int C = std::min(e->cfg.max_batch, 4096), nchunks = (n + C - 1) / C;
+    const int Kb = req.beam ? req.beam->num_beams : 1;       // (a beam request is cut at multiples of K: a crop's beams stay together)
+    const int C = std::min(e->cfg.max_batch, 4096) / Kb * Kb, nchunks = (n + C - 1) / C;
     // `n` decode rows over the views (req.source; without it row r reads view r).  A chunk prepares the views its own rows
     // name, once each: the planes of its job.
     struct Chunk { int plane0 = 0; std::vector<PrepView> own; const PrepView* views = nullptr; Job job; };
@@ -3381,19 +3540,22 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
                       {req.out_logp, L, 0u, {}, {}},
                       {req.out_alt_ids, L * MOCR_ALTERNATIVES, 0xffffffffu, {}, {}},
                       {req.out_alt_logp, L * MOCR_ALTERNATIVES, 0u, {}, {}},
-                      {req.out_pos, L * MOCR_POSITION_FIELDS, 0u, {}, {}}};
+                      {req.out_pos, L * MOCR_POSITION_FIELDS, 0u, {}, {}},
+                      {req.out_score, 1, 0xce6e6b28u /* -1e9f: beam search, a sliver's slots are empty */, {}, {}}};
         for (Out& o : outs)
             if (o.dst) { o.rows.resize(nv * o.per_row); o.sliver.assign(o.per_row, o.fill); }
         auto rows_of = [&](int k) { return outs[k].dst ? outs[k].rows.data() : nullptr; };
         // prefix_ld 0 (validated: every length is 0 then) leaves no tokens to point at: the inner request carries no prefix,
         // so its two pointers stay both null or both set
         const bool pre = req.prefix && !view_prefix.empty();
-        if (nv > 0)
-            prepare_and_decode(e, srcs, views.data(), (int)nv, reinterpret_cast<int32_t*>(rows_of(0)), reinterpret_cast<int32_t*>(rows_of(1)),
-                               request_of(rows_of(2), rows_of(3), rows_of(4), req.sets ? view_sets.data() : nullptr,
-                                          req.ngram ? view_ngram.data() : nullptr, rows_of(5), pre ? view_prefix.data() : nullptr,
-                                          pre ? view_plen.data() : nullptr, pre ? req.prefix_ld : 0,
-                                          req.source ? view_src.data() : nullptr, req.source ? (int32_t)views.size() : -1));
+        if (nv > 0) {
+            Request inner = request_of(rows_of(2), rows_of(3), rows_of(4), req.sets ? view_sets.data() : nullptr,
+                                       req.ngram ? view_ngram.data() : nullptr, rows_of(5), pre ? view_prefix.data() : nullptr,
+                                       pre ? view_plen.data() : nullptr, pre ? req.prefix_ld : 0,
+                                       req.source ? view_src.data() : nullptr, req.source ? (int32_t)views.size() : -1);
+            inner.beam = req.beam; inner.out_score = reinterpret_cast<float*>(rows_of(6));      // (a sliver drops all K rows of its crop)
+            prepare_and_decode(e, srcs, views.data(), (int)nv, reinterpret_cast<int32_t*>(rows_of(0)), reinterpret_cast<int32_t*>(rows_of(1)), inner);
+        }
         for (int i = 0; i < n_rows; ++i)
             for (Out& o : outs) {
                 if (!o.dst) continue;
@@ -3454,6 +3616,55 @@ int mocr_recognize_regions_scored(mocr_engine* e, const mocr_image* pages, int32
 int mocr_recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions, int32_t n_regions,
                            int32_t* out_ids, int32_t* out_len) {
     return recognize_regions(e, pages, n_pages, regions, n_regions, n_regions, out_ids, out_len, Request{});
+}
+
+// ---- beam search: the four source kinds.  A request of n crops is n K decode rows over n encodings - the shared-encodings
+// request with source[c K + k] = c - plus the configuration and the score output; the checks come before any work.
+struct BeamCall { std::vector<int32_t> source; Request req; int rows = 0; };
+static int beam_call(mocr_engine* e, const mocr_beam_config* beam, int32_t n, void* out_score, BeamCall& bc) {
+    return guarded(e, [&] {
+        if (!beam || beam->num_beams < 2 || beam->num_beams > MOCR_MAX_BEAMS) throw ArgError{"num_beams must be 2 .. MOCR_MAX_BEAMS (4)", MOCR_ERR_ARG};
+        if (beam->early_stopping < 0 || beam->early_stopping > 2) throw ArgError{"early_stopping must be 0 (false), 1 (true) or 2 (never)", MOCR_ERR_ARG};
+        if (beam->no_repeat_ngram_size < 0 || !std::isfinite(beam->length_penalty))
+            throw ArgError{"no_repeat_ngram_size must be >= 0 and length_penalty finite", MOCR_ERR_ARG};
+        if (n < 1) throw ArgError{"n must be positive", MOCR_ERR_ARG};
+        if ((long long)n * beam->num_beams > e->cfg.max_batch) throw ArgError{"n * num_beams exceeds max_batch", MOCR_ERR_ARG};
+        if (!out_score) throw ArgError{"null pointer", MOCR_ERR_ARG};
+        const int K = beam->num_beams;
+        bc.rows = n * K;
+        bc.source.resize((size_t)bc.rows);
+        for (int i = 0; i < bc.rows; ++i) bc.source[i] = i / K;
+        bc.req.source = bc.source.data(); bc.req.n_images = n;
+        bc.req.beam = beam; bc.req.out_score = static_cast<float*>(out_score);
+    });
+}
+
+int mocr_recognize_images_beam(mocr_engine* e, const mocr_image* images, int32_t n, const mocr_beam_config* beam, int32_t* out_ids,
+                               int32_t* out_len, float* out_score) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, out_score, bc)) return rc;
+    return recognize_images(e, images, bc.rows, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_regions_beam(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions, int32_t n_regions,
+                                const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len, float* out_score) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n_regions, out_score, bc)) return rc;
+    return recognize_regions(e, pages, n_pages, regions, n_regions, bc.rows, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_gray_host_beam(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, const mocr_beam_config* beam,
+                                  int32_t* out_ids, int32_t* out_len, float* out_score) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, out_score, bc)) return rc;
+    return recognize_gray_host(e, gray, bc.rows, max_len_override, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_device_beam(mocr_engine* e, const void* d_gray, int32_t n, const mocr_beam_config* beam, void* d_out_ids, void* d_out_len,
+                               void* d_out_score) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, d_out_score, bc)) return rc;
+    return recognize_device(e, d_gray, bc.rows, d_out_ids, d_out_len, bc.req);
 }
 
 int mocr_set_generate_max_length(mocr_engine* e, int32_t max_len) {
@@ -4075,6 +4286,79 @@ int mocr_profile_get(mocr_engine* e, mocr_kernel_stat* out, int32_t cap, int32_t
         for (auto& s : e->stats)
             if (s.launches > 0 && k < cap) out[k++] = s;
         *n_out = k;
+    });
+}
+
+int mocr_op_beam_select(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score, int32_t* d_parent,
+                        int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!a || a->struct_size != (int32_t)sizeof(mocr_token_args)) throw ArgError{"mocr_op_beam_select: bad struct_size", MOCR_ERR_ARG};
+        if (!e->committed || !beam || beam->num_beams < 2 || beam->num_beams > MOCR_MAX_BEAMS || beam->early_stopping < 0 ||
+            beam->early_stopping > 2 || beam->no_repeat_ngram_size < 0 || a->first || a->forced || a->ncand > 0 || a->n < 1 || !a->slabs ||
+            a->nslab < 1 || !a->ids || !a->step || !a->finished || !a->len || !a->n_unfinished || !a->rowmap || !a->x_f32 || !a->x_t ||
+            a->ids_ld < 2 || a->ids_ld > BEAM_HIST || a->max_len < 2 || a->max_len > a->ids_ld || a->max_len > e->cfg.max_len ||
+            !d_beam_score || !d_parent || !d_hyp_ids || !d_hyp_len || !d_hyp_score || !d_heuristic_open)
+            throw ArgError{"mocr_op_beam_select: bad argument", MOCR_ERR_ARG};
+        DecState st{};
+        st.n_real = a->n_real;
+        st.ids = a->ids; st.step = a->step; st.finished = a->finished; st.len = a->len; st.n_unfinished = a->n_unfinished;
+        st.ids_ld = a->ids_ld; st.max_len = a->max_len;
+        st.start_id = e->cfg.start_id; st.eos_id = e->cfg.eos_id; st.pad_id = e->cfg.pad_id;
+        st.rowmap = a->rowmap;
+        BeamState bs{};
+        bs.beam_score = d_beam_score; bs.parent = d_parent; bs.hyp_ids = d_hyp_ids; bs.hyp_len = d_hyp_len; bs.hyp_score = d_hyp_score;
+        bs.heuristic_open = d_heuristic_open;
+        bs.length_penalty = beam->length_penalty; bs.early_stopping = beam->early_stopping; bs.ngram = beam->no_repeat_ngram_size;
+        DecTokenArgs t{};
+        t.slabs = a->slabs; t.nslab = a->nslab; t.slab_stride = (long long)a->n * e->V;
+        t.vbias = a->vbias ? a->vbias : e->w.bv;
+        t.x_f32 = a->x_f32; t.x_t = a->x_t;
+        if (a->cache && a->cache_fp8) { t.cache8 = reinterpret_cast<uint8_t*>(a->cache); t.inv8 = a->inv_sx; }
+        else t.cache = a->cache;
+        t.cstride = (long long)e->cfg.max_len * e->D;
+        dispatch(e, [&](auto tag) { launch_beam_select<decltype(tag)>(e, st, bs, t, a->n, beam->num_beams); });
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_op_beam_permute(mocr_engine* e, void* d_cache, int32_t layers, int64_t layer_stride, int64_t row_stride, int32_t segs,
+                         int64_t seg_stride, int32_t pos_bytes, int32_t K, const int32_t* d_parent, const int32_t* d_rowmap,
+                         const int32_t* d_finished, const int32_t* d_step, int32_t n_slots, int32_t max_pos) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!d_cache || !d_parent || !d_rowmap || !d_finished || !d_step || n_slots < 1 || K < 2 || K > MOCR_MAX_BEAMS || layer_stride < 0 ||
+            row_stride < 16 || seg_stride < 0 || layer_stride % 16 || row_stride % 16 || seg_stride % 16 ||
+            (reinterpret_cast<uintptr_t>(d_cache) & 15))
+            throw ArgError{"mocr_op_beam_permute: bad argument", MOCR_ERR_ARG};
+        BeamPermuteView v{reinterpret_cast<char*>(d_cache), layer_stride, row_stride, seg_stride, segs, pos_bytes};
+        launch_beam_permute(e, v, layers, K, d_parent, d_rowmap, d_finished, d_step, n_slots, max_pos);
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int64_t mocr_beam_state_bytes(mocr_engine* e) {
+    if (!e) return -1;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int64_t bytes = 0;
+    for (const Lane& L : e->lanes)
+        if (L.ctx.hyp_ids) bytes += (int64_t)e->Bp * (5 + e->cfg.max_len) * 4;      // five [Bp] arrays and hyp_ids [Bp][max_len]
+    return bytes;
+}
+
+int mocr_lane_rowmap(mocr_engine* e, int32_t lane, int32_t* out_rowmap, int32_t n) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (!out_rowmap || lane < 0 || lane >= (int)e->lanes.size() || n < 1 || n > e->Bp) throw ArgError{"mocr_lane_rowmap: bad argument", MOCR_ERR_ARG};
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        HIPCHECK(hipMemcpy(out_rowmap, e->lanes[lane].ctx.rowmap, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
     });
 }
 

@@ -1,0 +1,347 @@
+// Beam search on the device (GenerationMixin._beam_search of transformers 5.x, do_sample = False, one EOS id, a prompt of
+// one token): the selection that ends a decode step in place of the greedy token kernel, and the reorder of the
+// self-attention caches that follows it.  Beam k of crop c is row c K + k of the batch; the K rows of a crop sit in K
+// neighbouring decode slots (a crop's rows finish together and the compaction is a stable partition, so a group of slots
+// g K .. g K + K - 1 always holds one crop's rows in beam order).
+#pragma once
+#include "common.h"
+#include "kernels_decode.h"
+
+constexpr int BEAM_MAX = 4;             // = MOCR_MAX_BEAMS
+constexpr int BEAM_HIST = 320;          // tokens of a history the selection keeps in LDS: ids_ld <= this (the attention kernels' limit)
+#define BEAM_NEG 1.0e9f                 // transformers' "minus infinity" of beam scores
+
+// Per-lane beam state, by ROW like ids (a compaction moves nothing).
+struct BeamState {
+    float* beam_score;      // [rows] accumulated log-probability of the running beam
+    int* parent;            // [rows] the beam (0 .. K - 1, of the same crop) whose history and caches the row continues
+    int* hyp_ids;           // [rows][ids_ld] the crop's K finished hypotheses, best first, pad_id behind their length
+    int* hyp_len;           // [rows] 0: the slot never received a finished sequence
+    float* hyp_score;       // [rows] -1e9 then
+    int* heuristic_open;    // [crops] is_early_stop_heuristic_unsatisfied
+    float length_penalty;
+    int early_stopping;     // 0 false, 1 true, 2 "never"
+    int ngram;              // no_repeat_ngram_size, 0: off
+};
+
+// Start of a beam batch, one block of 64 threads per row: running scores [0, -1e9, ...], an empty finished set.
+__global__ __launch_bounds__(64) void beam_init_kernel(BeamState bs, int K, int rows, int ids_ld, int pad_id) {
+    const int r = blockIdx.x;
+    if (r >= rows) return;
+    for (int i = threadIdx.x; i < ids_ld; i += 64) bs.hyp_ids[(size_t)r * ids_ld + i] = pad_id;
+    if (threadIdx.x == 0) {
+        bs.beam_score[r] = (r % K == 0) ? 0.f : -BEAM_NEG;
+        bs.parent[r] = r % K;
+        bs.hyp_len[r] = 0;
+        bs.hyp_score[r] = -BEAM_NEG;
+        if (r % K == 0) bs.heuristic_open[r / K] = 1;
+    }
+}
+
+// End of a beam step, one block of 256 threads per crop (slots g K .. g K + K - 1):
+//   per beam: logits = sum_s slab_s + bias (the slab path of dec_token_kernel, the same fp32 sums), the row's max and log S,
+//     the beam's n-gram bans from ITS history (the window scan of the NGRAM token kernel, from scratch, in LDS), and
+//     score = ((logit - max) - log S) + beam_score - log_softmax over the full row first, bans as -inf without renormalising;
+//   the 2 K best of the K V scores (TopN: equal scores go to the lower flat index beam V + token);
+//   thread 0: the stopping rule (EOS, or the token completes max_len), the K running beams of the next step (the best
+//     candidates that did not stop), the finished set (its K entries merged with the stopped candidates among the first K,
+//     score / (tokens generated) ^ length_penalty), the early-stop heuristic and the end of the crop;
+//   the block: ids[row_k] = the parent's history plus the token (the K old histories are in LDS before anything is
+//     written), new hypotheses into hyp_ids, and every new beam's next input LN(word[tok] + type0 + pos[t + 1]) into x_f32 /
+//     x_t of its slot and into the layer-0 cache row of position t + 1.
+// The two -1e9 guards of _update_finished_beams ("beams full and early_stopping", "heuristic satisfied") hold exactly when
+// the crop's own end condition holds, and a crop that ended is frozen: its block only advances `step`, like the block of
+// a trailing partial group of padding slots.  (The guards are applied all the same, for states given through the hook.)
+template <typename T, int K>
+__global__ __launch_bounds__(256) void beam_select_kernel(const float* __restrict__ slabs, int nslab, long long slab_stride,
+                                                          const float* __restrict__ vbias, int V, DecState st, BeamState bs, int np,
+                                                          const float* __restrict__ word, const float* __restrict__ type0,
+                                                          const float* __restrict__ pos, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, float* __restrict__ x_f32,
+                                                          T* __restrict__ x_t, float eps, T* __restrict__ cache,
+                                                          long long cache_batch_stride, uint8_t* __restrict__ cache8, float inv_sx8) {
+    static_assert(K >= 2 && K <= BEAM_MAX, "2 .. 4 beams");
+    constexpr int D = 768, MW = 192, NC = 6, C2 = 2 * K;
+    __shared__ int s_hist[K][BEAM_HIST];
+    __shared__ int s_hyp[K][BEAM_HIST];
+    __shared__ unsigned s_mask[MW];
+    __shared__ float s_red[4];
+    __shared__ float s_cv[4][C2];
+    __shared__ int s_ci[4][C2];
+    __shared__ int s_row[K], s_ntok[K], s_npar[K];
+    __shared__ int s_hsrc[K], s_hlen[K];              // finished slot j <- (>= 0: old slot, < 0: candidate -1 - i), its length
+    __shared__ int s_ctok[C2], s_cpar[C2];
+    __shared__ int s_new, s_done;
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int slot0 = g * K;
+    if (slot0 + K > np) {                             // a trailing partial group: padding slots, born finished
+        if (slot0 + tid < np) st.step[slot0 + tid] += 1;
+        return;
+    }
+    const int t = st.step[slot0];
+    const int row0 = st.rowmap[slot0];
+    // the crop has ended (or is padding); a live crop's step is below max_len - 1 <= ids_ld - 1 (it would have ended on length)
+    if (st.finished[row0] || (unsigned)t >= (unsigned)(st.max_len - 1)) {
+        if (tid < K) st.step[slot0 + tid] = t + 1;
+        return;
+    }
+    const int L = t + 1;                              // tokens every running beam holds
+    const int crop = row0 / K;
+    if (tid < K) s_row[tid] = st.rowmap[slot0 + tid];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        for (int i = tid; i < L; i += 256) s_hist[k][i] = st.ids[(size_t)s_row[k] * st.ids_ld + i];
+    __syncthreads();
+
+    TopN<C2> top;
+    topn_clear(top);
+    const int n = bs.ngram;
+    for (int k = 0; k < K; ++k) {
+        const int b = slot0 + k;
+        float4 a[NC];
+#pragma unroll
+        for (int j = 0; j < NC; ++j) a[j] = *reinterpret_cast<const float4*>(vbias + tid * 4 + j * 1024);
+        for (int s = 0; s < nslab; ++s) {
+            const float* sp = slabs + (size_t)s * slab_stride + (size_t)b * V + tid * 4;
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                const float4 x = *reinterpret_cast<const float4*>(sp + j * 1024);
+                a[j].x += x.x; a[j].y += x.y; a[j].z += x.z; a[j].w += x.w;
+            }
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < NC; ++j) mx = fmaxf(fmaxf(mx, fmaxf(a[j].x, a[j].y)), fmaxf(a[j].z, a[j].w));
+        mx = wave_max(mx);
+        if (lane == 0) s_red[wave] = mx;
+        if (n > 0 && tid < MW) s_mask[tid] = 0xffffffffu;
+        __syncthreads();
+        const float gmax = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+        __syncthreads();
+        float es = 0.f;
+#pragma unroll
+        for (int j = 0; j < NC; ++j)
+            es += (__expf(a[j].x - gmax) + __expf(a[j].y - gmax)) + (__expf(a[j].z - gmax) + __expf(a[j].w - gmax));
+        es = wave_sum(es);
+        if (lane == 0) s_red[wave] = es;
+        if (n > 0) {                                  // the bans of this beam's own history: windows i = 0 .. L - n
+            const int* rid = s_hist[k];
+            const int* key = rid + (L - n + 1);       // its last n - 1 tokens
+            for (int i = tid; i <= L - n; i += 256) {
+                bool same = true;
+                for (int q = 0; q < n - 1 && same; ++q) same = rid[i + q] == key[q];
+                const int ban = rid[i + n - 1];
+                if (same && (unsigned)ban < (unsigned)V) atomicAnd(&s_mask[ban >> 5], ~(1u << (ban & 31)));
+            }
+        }
+        __syncthreads();
+        const float logS = logf((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
+        const float bsc = bs.beam_score[s_row[k]];
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            const int c = tid * 4 + j * 1024;
+            const unsigned nib = n > 0 ? (s_mask[c >> 5] >> (c & 31)) & 15u : 15u;
+            const float v[4] = {a[j].x, a[j].y, a[j].z, a[j].w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float sc = ((nib >> q) & 1) ? ((v[q] - gmax) - logS) + bsc : -INFINITY;
+                topn_insert(top, sc, k * V + c + q);
+            }
+        }
+        __syncthreads();                              // s_red / s_mask are the next beam's
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) topn_merge_xor(top, o);
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < C2; ++i) { s_cv[wave][i] = top.v[i]; s_ci[wave][i] = top.i[i]; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w)
+#pragma unroll
+            for (int i = 0; i < C2; ++i) topn_insert(top, s_cv[w][i], s_ci[w][i]);
+        float cv[C2];
+        int ctok[C2], cpar[C2];
+        bool stop[C2];
+        const bool stop_len = t + 2 >= st.max_len;
+        bool all_stop = true;
+#pragma unroll
+        for (int i = 0; i < C2; ++i) {
+            const bool ok = (unsigned)top.i[i] < (unsigned)(K * V);      // (all-NaN logits win no comparison: stay inside the tables)
+            cv[i] = top.v[i];
+            cpar[i] = ok ? top.i[i] / V : 0;
+            ctok[i] = ok ? top.i[i] - cpar[i] * V : 0;
+            stop[i] = ctok[i] == st.eos_id || stop_len;
+            all_stop = all_stop && stop[i];
+            s_ctok[i] = ctok[i]; s_cpar[i] = cpar[i];
+        }
+        // the running beams of the next step: the best K candidates after -1e9 on those that stopped = the ones that did
+        // not stop, in order, then (only when fewer than K are left: the crop ends) the stopped ones
+        float rsc[K];
+        int nr = 0;
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass)
+#pragma unroll
+            for (int i = 0; i < C2; ++i)
+                if (nr < K && stop[i] == (pass == 1)) {
+                    rsc[nr] = pass ? cv[i] - BEAM_NEG : cv[i];
+                    s_ntok[nr] = ctok[i]; s_npar[nr] = cpar[i];
+                    ++nr;
+                }
+        // the finished set: its K entries (sorted) merged with the stopped candidates among the first K
+        const float div = powf((float)L, bs.length_penalty);            // (cur_len + 1 - prompt) ^ length_penalty, L tokens generated
+        float hs[K], ns[K];
+        int hl[K], src[K], nl[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) { hs[j] = bs.hyp_score[crop * K + j]; hl[j] = min(max(bs.hyp_len[crop * K + j], 0), st.ids_ld); }
+        // (the reference's two guards: a full set under early_stopping = true, or a satisfied heuristic, takes nothing more -
+        // states the engine never steps, since such a crop has ended; the operator hook can present them)
+        bool guard = bs.early_stopping == 1 || !bs.heuristic_open[crop];
+        if (bs.heuristic_open[crop])
+            for (int j = 0; j < K; ++j) guard = guard && hl[j] > 0;
+        int io = 0, ic = 0, any_new = 0;                                // the next old entry (io <= j < K), the next candidate
+        for (int j = 0; j < K; ++j) {
+            while (ic < K && !stop[ic]) ++ic;
+            const float cs = ic < K ? (guard ? cv[ic] / div - BEAM_NEG : cv[ic] / div) : -INFINITY;
+            if (ic < K && cs > hs[io]) { ns[j] = cs; nl[j] = t + 2; src[j] = -1 - ic; ++ic; any_new = 1; }      // (equal: the old entry first)
+            else { ns[j] = hs[io]; nl[j] = hl[io]; src[j] = io; ++io; }
+        }
+        bool all_fin = true;
+        for (int j = 0; j < K; ++j) {
+            bs.hyp_score[crop * K + j] = ns[j]; bs.hyp_len[crop * K + j] = nl[j];
+            s_hsrc[j] = src[j]; s_hlen[j] = src[j] >= 0 ? nl[j] : 0;
+            all_fin = all_fin && nl[j] > 0;
+        }
+        // the heuristic of the next iteration (cur_len = t + 2) and the three-way end condition
+        const float hyp_len_best = (bs.early_stopping == 2 && bs.length_penalty > 0.f) ? (float)(st.max_len - 1) : (float)(t + 1);
+        const float best_possible = rsc[0] / powf(hyp_len_best, bs.length_penalty);
+        const int open = bs.heuristic_open[crop] && best_possible > ns[K - 1];
+        bs.heuristic_open[crop] = open;
+        const bool done = !open || (all_fin && bs.early_stopping == 1) || all_stop;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int r = s_row[k];
+            bs.beam_score[r] = rsc[k];
+            bs.parent[r] = done ? k : s_npar[k];
+            st.step[slot0 + k] = t + 1;
+            if (done) { st.finished[r] = 1; st.len[r] = t + 2; }
+        }
+        if (done) atomicSub(st.n_unfinished, K);
+        s_new = any_new; s_done = done ? 1 : 0;
+    }
+    __syncthreads();
+    if (s_new) {                                      // block-uniform: the old hypotheses to LDS, then every slot from its source
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            for (int i = tid; i < s_hlen[j]; i += 256) s_hyp[s_hsrc[j] >= 0 ? s_hsrc[j] : 0][i] = bs.hyp_ids[(size_t)(crop * K + s_hsrc[j]) * st.ids_ld + i];
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            int* dst = bs.hyp_ids + (size_t)(crop * K + j) * st.ids_ld;
+            const int src = s_hsrc[j];
+            if (src == j) continue;
+            if (src >= 0) {
+                for (int i = tid; i < st.ids_ld; i += 256) dst[i] = i < s_hlen[j] ? s_hyp[src][i] : st.pad_id;
+            } else {
+                const int ci = -1 - src;
+                for (int i = tid; i < st.ids_ld; i += 256) dst[i] = i < L ? s_hist[s_cpar[ci]][i] : i == L ? s_ctok[ci] : st.pad_id;
+            }
+        }
+    }
+    if (s_done) return;                               // block-uniform
+    // the new beams' rows: the parent's history plus the token
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        int* dst = st.ids + (size_t)s_row[k] * st.ids_ld;
+        const int p = s_npar[k];
+        if (p != k)
+            for (int i = tid; i < L; i += 256) dst[i] = s_hist[p][i];
+        if (tid == 0 && L < st.ids_ld) dst[L] = s_ntok[k];
+    }
+    // embedding + LayerNorm of every new beam's next input (the tail of dec_token_kernel)
+    constexpr int PER = D / 256;
+    const int ps = t + 1;
+    for (int k = 0; k < K; ++k) {
+        const int tok = s_ntok[k], b = slot0 + k, row = s_row[k];
+        float v[PER];
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int d = tid + i * 256;
+            float e = word[(size_t)tok * D + d] + type0[d];
+            e = e + pos[(size_t)ps * D + d];
+            v[i] = e; s += e;
+        }
+        s = wave_sum(s);
+        if (lane == 0) s_red[wave] = s;
+        __syncthreads();
+        const float mean = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) * (1.0f / D);
+        __syncthreads();
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) { const float d = v[i] - mean; q += d * d; }
+        q = wave_sum(q);
+        if (lane == 0) s_red[wave] = q;
+        __syncthreads();
+        const float rstd = 1.0f / sqrtf((s_red[0] + s_red[1] + s_red[2] + s_red[3]) * (1.0f / D) + eps);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int d = tid + i * 256;
+            const float o = (v[i] - mean) * rstd * gamma[d] + beta[d];
+            x_f32[(size_t)b * D + d] = o;
+            elem<T>::st(x_t + (size_t)b * D + d, o);
+            if (cache) elem<T>::st(cache + (size_t)row * cache_batch_stride + (size_t)ps * D + d, o);
+            if (cache8) cache8[(size_t)row * cache_batch_stride + (size_t)ps * D + d] = (uint8_t)(pack4_fp8(o * inv_sx8, 0.f, 0.f, 0.f) & 0xff);
+        }
+    }
+}
+
+// In-place reorder of a self-attention cache behind the selection: dst beam k <- src beam parent[k], positions 0 .. t of
+// every (layer, segment); position t + 1 was written by the selection for the NEW order and is not touched.  One generic
+// kernel over a strided view in bytes: [layers][rows][segments][positions][pos_bytes] - the latent xcache / x8cache have one
+// segment per (layer, row), the classic kcache / vcache one per head.  A thread owns one 16-byte piece offset within a crop's
+// group of K rows: it loads the K beams' pieces into registers and stores them permuted, so no two threads share a byte and
+// the permutation needs no barrier, no scratch and no second cache - cycles and "all from beam 0" alike.
+struct BeamPermuteView {
+    char* base;
+    long long layer_stride, row_stride, seg_stride;     // bytes
+    int segs, pos_bytes;                                 // pos_bytes: a multiple of 16
+};
+
+template <int K>
+__global__ __launch_bounds__(256) void beam_permute_kernel(BeamPermuteView v, const int* __restrict__ parent, const int* __restrict__ rowmap,
+                                                           const int* __restrict__ finished, const int* __restrict__ step, int np, int max_pos) {
+    const int slot0 = blockIdx.x * K;
+    if (slot0 + K > np) return;
+    int row[K], par[K];
+    bool ident = true;
+#pragma unroll
+    for (int k = 0; k < K; ++k) row[k] = rowmap[slot0 + k];
+    if (finished[row[0]]) return;                      // a crop that has ended keeps its caches (nothing reads them again)
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        par[k] = min(max(parent[row[k]], 0), K - 1);
+        ident = ident && par[k] == k;
+    }
+    if (ident) return;
+    // the selection has advanced step to t + 1: positions 0 .. t (max_pos, which sized the grid, bounds it)
+    const long long nbytes = (long long)min(max(step[slot0], 0), max_pos) * v.pos_bytes;
+    const long long off = ((long long)blockIdx.z * 256 + threadIdx.x) * 16;
+    if (off >= nbytes) return;
+    const int layer = blockIdx.y / v.segs, seg = blockIdx.y - layer * v.segs;
+    char* const p0 = v.base + (long long)layer * v.layer_stride + (long long)seg * v.seg_stride + off;
+    uint4 r[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) r[k] = *reinterpret_cast<const uint4*>(p0 + (long long)row[k] * v.row_stride);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        if (par[k] == k) continue;
+        uint4 x = r[0];
+#pragma unroll
+        for (int j = 1; j < K; ++j) x = par[k] == j ? r[j] : x;
+        *reinterpret_cast<uint4*>(p0 + (long long)row[k] * v.row_stride) = x;
+    }
+}

@@ -69,6 +69,13 @@ class MocrLatentArgs(C.Structure):
         [(n, C.c_void_p) for n in ("q", "qt", "et", "ctx")]
 
 
+class MocrBeamConfig(C.Structure):
+    """include/mocr.h: mocr_beam_config"""
+    _fields_ = [("num_beams", C.c_int32), ("length_penalty", C.c_float), ("early_stopping", C.c_int32),
+                ("no_repeat_ngram_size", C.c_int32)]
+
+
+MAX_BEAMS = 4             # MOCR_MAX_BEAMS
 CHANNELS_BGR = -3
 MAX_TOKEN_SETS = 256      # MOCR_MAX_TOKEN_SETS: token sets per engine, set 0 included
 TOKEN_SET_ALL = 0         # MOCR_TOKEN_SET_ALL: the whole vocabulary
@@ -163,6 +170,16 @@ SYMBOLS = {
                                              _P, _P, C.c_int32, _P, _P]),
     "mocr_op_smallm_gemm": (C.c_int, [_P, C.POINTER(MocrSmallmArgs)]),
     "mocr_op_latent_block": (C.c_int, [_P, C.POINTER(MocrLatentArgs)]),
+    "mocr_recognize_images_beam": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.POINTER(MocrBeamConfig), _P, _P, _P]),
+    "mocr_recognize_regions_beam": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.POINTER(MocrRegion), C.c_int32,
+                                              C.POINTER(MocrBeamConfig), _P, _P, _P]),
+    "mocr_recognize_gray_host_beam": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(MocrBeamConfig), _P, _P, _P]),
+    "mocr_recognize_device_beam": (C.c_int, [_P, _P, C.c_int32, C.POINTER(MocrBeamConfig), _P, _P, _P]),
+    "mocr_beam_state_bytes": (C.c_int64, [_P]),
+    "mocr_lane_rowmap": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
+    "mocr_op_beam_select": (C.c_int, [_P, C.POINTER(MocrTokenArgs), C.POINTER(MocrBeamConfig), _P, _P, _P, _P, _P, _P]),
+    "mocr_op_beam_permute": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P,
+                                       C.c_int32, C.c_int32]),
     "mocr_profile_enable": (C.c_int, [_P, C.c_int32]),
     "mocr_profile_reset": (C.c_int, [_P]),
     "mocr_profile_get": (C.c_int, [_P, C.POINTER(MocrKernelStat), C.c_int32, C.POINTER(C.c_int32)]),

@@ -13,6 +13,44 @@ DTYPES = {"fp32": _capi.MOCR_F32, "f32": _capi.MOCR_F32, "float32": _capi.MOCR_F
           "bf16": _capi.MOCR_BF16, "bfloat16": _capi.MOCR_BF16}
 
 
+EARLY_STOPPING = {False: 0, True: 1, "never": 2}
+
+
+class BeamConfig:
+    """generate(num_beams, length_penalty, early_stopping, no_repeat_ngram_size) of a beam request (include/mocr.h, "beam
+    search"): ``num_beams`` 2 .. 4, ``early_stopping`` False / True / "never", ``no_repeat_ngram`` 0 = off."""
+    __slots__ = ("num_beams", "length_penalty", "early_stopping", "no_repeat_ngram")
+
+    def __init__(self, num_beams: int = 4, length_penalty: float = 1.0, early_stopping=False, no_repeat_ngram: int = 0):
+        if isinstance(num_beams, (bool, np.bool_)) or not isinstance(num_beams, (int, np.integer)):
+            raise TypeError(f"num_beams: an int, instead got {num_beams!r}")
+        if not 2 <= int(num_beams) <= _capi.MAX_BEAMS:
+            raise ValueError(f"num_beams must be in 2 .. {_capi.MAX_BEAMS} (the engine's limit), instead got {num_beams}")
+        if isinstance(early_stopping, (bool, np.bool_)):
+            early_stopping = bool(early_stopping)
+        elif early_stopping != "never":
+            raise ValueError(f"early_stopping must be False, True or 'never', instead got {early_stopping!r}")
+        if isinstance(no_repeat_ngram, (bool, np.bool_)) or not isinstance(no_repeat_ngram, (int, np.integer)) or no_repeat_ngram < 0:
+            raise ValueError(f"no_repeat_ngram: an int >= 0, instead got {no_repeat_ngram!r}")
+        self.num_beams, self.length_penalty = int(num_beams), float(length_penalty)
+        self.early_stopping, self.no_repeat_ngram = early_stopping, int(no_repeat_ngram)
+
+    def key(self):
+        return (self.num_beams, self.length_penalty, self.early_stopping, self.no_repeat_ngram)
+
+    def __eq__(self, other):
+        return isinstance(other, BeamConfig) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return "BeamConfig(num_beams=%d, length_penalty=%r, early_stopping=%r, no_repeat_ngram=%d)" % self.key()
+
+    def as_struct(self) -> "_capi.MocrBeamConfig":
+        return _capi.MocrBeamConfig(self.num_beams, self.length_penalty, EARLY_STOPPING[self.early_stopping], self.no_repeat_ngram)
+
+
 def _ptr(a) -> C.c_void_p:
     """numpy array (host) / torch tensor (host or device) / int address -> void*"""
     if a is None:
@@ -235,6 +273,21 @@ class Engine:
         out = blocks[:5] if alternatives else blocks[:3] if scores else blocks[:2]
         return out + (blocks[5],) if positions else out
 
+    # ------------------------------------------------------------------ beam search
+    def _beam_blocks(self, beam, n: int, **others):
+        """``beam=``: the config struct and the output blocks (ids [n,K,max_len], lens [n,K], scores [n,K]) of a beam call, which
+        takes none of the per-row keywords"""
+        if not isinstance(beam, BeamConfig):
+            raise TypeError(f"beam: a BeamConfig, instead got {beam!r}")
+        used = [k for k, v in others.items() if v is not None and v is not False]
+        if used:
+            raise ValueError(f"beam search does not combine with {', '.join(used)}")
+        K, L = beam.num_beams, self.spec.max_len
+        if n * K > self.max_batch:
+            raise ValueError(f"beam search: {n} crops x {K} beams exceed max_batch ({self.max_batch})")
+        return (beam.as_struct(), np.full((n, K, L), self.spec.pad_id, dtype=np.int32), np.zeros((n, K), dtype=np.int32),
+                np.full((n, K), -1e9, dtype=np.float32))
+
     def _per_crop(self, token_sets, no_repeat_ngram, n: int):
         """(sets, ngram) int32 [n] each, None where not given (the sizes are checked first)"""
         ngram = self._ngram(no_repeat_ngram, n) if no_repeat_ngram is not None else None
@@ -242,7 +295,7 @@ class Engine:
         return sets, ngram
 
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False,
-                         token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None):
+                         token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None):
         """Crops of any sizes (list of uint8 [h,w] / [h,w,3] arrays; `bgr`: 3-channel crops are in OpenCV order;
         `rotate`: per crop 0 / 1 (90 degrees clockwise) / 2 (counter-clockwise), applied on the device): luminance
         conversion and the Pillow-exact BILINEAR resize to 224x224 run on the device.
@@ -261,8 +314,18 @@ class Engine:
         scores them and continues greedily (include/mocr.h, "forced prefixes").
         ``sources``: a flat sequence of ints, one per output ROW - row r decodes ``images[sources[r]]``, which is encoded
         once however many rows name it (include/mocr.h, "shared encodings").  The outputs then have ``len(sources)`` rows,
-        and ``token_sets`` / ``no_repeat_ngram`` / ``prefixes`` are per row."""
+        and ``token_sets`` / ``no_repeat_ngram`` / ``prefixes`` are per row.
+        ``beam``: a :class:`BeamConfig` - beam search instead of greedy decoding (include/mocr.h, "beam search"), with none of
+        the other keywords.  Returns (ids int32 [n,K,max_len], lengths int32 [n,K], scores float32 [n,K]): every crop's K
+        finished hypotheses, the best first, with their sequence scores; an empty slot has length 0 and score -1e9."""
         n = len(images)
+        if beam is not None:
+            cfg, ids, lens, sc = self._beam_blocks(beam, n, scores=scores, alternatives=alternatives, token_sets=token_sets,
+                                                   no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources)
+            if n > 0:
+                descs, keep = self._image_descs(images, bgr, rotate)
+                self._check(self.lib.mocr_recognize_images_beam(self._h, descs, n, C.byref(cfg), _ptr(ids), _ptr(lens), _ptr(sc)))
+            return ids, lens, sc
         if sources is not None:
             src = self._sources(sources, n)
             n = int(src.size)
@@ -284,7 +347,7 @@ class Engine:
         return self._result(blocks, scores, alternatives, positions)
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False,
-                          token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None):
+                          token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None):
         """pages: list of uint8 [H,W,3] (or [H,W]) arrays; regions: iterable of (page_index, x, y, w, h) bounding
         rectangles.  Each page is uploaded once; the 8 %-padded, page-clipped crop of every region
         (``src/ui/main_window.py:9530-9540``) is cut on the device.  Returns (ids [n,max_len], lengths [n]);
@@ -296,9 +359,22 @@ class Engine:
         region's padded, clipped rectangle (manga_ocr.regions.padded_rect); a sliver's rows all 0.
         ``prefixes``: per region a forced prefix or None (see recognize_images); a sliver ignores its prefix.
         ``sources``: one region index per output ROW (see recognize_images): the outputs have ``len(sources)`` rows, the
-        per-region arguments are per row, and every row of a sliver region has length 0."""
+        per-region arguments are per row, and every row of a sliver region has length 0.
+        ``beam``: a :class:`BeamConfig` (see recognize_images): (ids [n,K,max_len], lengths [n,K], scores [n,K]); a sliver's K
+        slots are empty."""
         regs = list(regions)
         n = n_regions = len(regs)
+        if beam is not None:
+            cfg, ids, lens, sc = self._beam_blocks(beam, n, scores=scores, alternatives=alternatives, token_sets=token_sets,
+                                                   no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources)
+            if n > 0:
+                descs, keep = self._image_descs(pages, bgr)
+                arr = (_capi.MocrRegion * n_regions)()
+                for i, (pg, x, y, w, h) in enumerate(regs):
+                    arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
+                self._check(self.lib.mocr_recognize_regions_beam(self._h, descs, len(keep), arr, n_regions, C.byref(cfg), _ptr(ids),
+                                                                 _ptr(lens), _ptr(sc)))
+            return ids, lens, sc
         if sources is not None:
             src = self._sources(sources, n_regions)
             n = int(src.size)
@@ -337,6 +413,16 @@ class Engine:
         """Decode slots x steps enqueued so far (what the decode launches were sized for, in row-steps)."""
         return int(self.lib.mocr_decode_slot_steps(self._h))
 
+    def beam_state_bytes(self) -> int:
+        """Bytes of beam state the engine holds: 0 until its first beam batch (include/mocr.h, test hook)."""
+        return int(self.lib.mocr_beam_state_bytes(self._h))
+
+    def lane_rowmap(self, n: int, lane: int = 0) -> np.ndarray:
+        """The first ``n`` entries of a lane's decode slot -> row map as its last batch left it (include/mocr.h, test hook)."""
+        out = np.zeros(n, dtype=np.int32)
+        self._check(self.lib.mocr_lane_rowmap(self._h, int(lane), _ptr(out), int(n)))
+        return out
+
     def compaction_count(self) -> int:
         """Row compactions performed so far: unfinished rows moved to the first decode slots between chunks of steps."""
         return int(self.lib.mocr_compaction_count(self._h))
@@ -349,7 +435,8 @@ class Engine:
         return out
 
     def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None, d_out_alt_ids=None, d_out_alt_logp=None, *,
-                         token_sets=None, no_repeat_ngram=None, d_out_pos=None, prefixes=None, sources=None) -> None:
+                         token_sets=None, no_repeat_ngram=None, d_out_pos=None, prefixes=None, sources=None, beam=None,
+                         d_out_score=None) -> None:
         """Asynchronous; all are device buffers (torch CUDA tensors or raw addresses).  ``d_out_logp`` (float32
         [n,max_len]): also the token log-probabilities.  ``d_out_alt_ids`` (int32) with ``d_out_alt_logp`` (float32), both
         [n,max_len,4]: also the token alternatives.  ``token_sets``: a set handle for every crop, or one per crop (host values).
@@ -357,7 +444,15 @@ class Engine:
         ``d_out_pos`` (float32 [n,max_len,5]): also the token positions.  ``prefixes``: per crop a forced prefix or None (host
         values, copied by the call).  ``sources``: one plane index per output ROW (host values, see recognize_images) -
         ``n`` then counts the planes of ``d_gray``, the output buffers have ``len(sources)`` rows and the per-crop arguments
-        are per row."""
+        are per row.  ``beam`` (a :class:`BeamConfig`) with ``d_out_score``: beam search - ``d_out_ids`` int32 [n,K,max_len],
+        ``d_out_len`` int32 [n,K] and ``d_out_score`` float32 [n,K] receive the hypotheses; none of the other keywords."""
+        if beam is not None:
+            cfg = self._beam_blocks(beam, 0, d_out_logp=d_out_logp, d_out_alt_ids=d_out_alt_ids, d_out_alt_logp=d_out_alt_logp,
+                                    token_sets=token_sets, no_repeat_ngram=no_repeat_ngram, d_out_pos=d_out_pos, prefixes=prefixes,
+                                    sources=sources)[0]
+            self._check(self.lib.mocr_recognize_device_beam(self._h, _ptr(d_gray), n, C.byref(cfg), _ptr(d_out_ids), _ptr(d_out_len),
+                                                            _ptr(d_out_score)))
+            return
         if sources is not None:
             src = self._sources(sources, n)
             rows = int(src.size)
@@ -382,11 +477,17 @@ class Engine:
         self._check(self.lib.mocr_set_generate_max_length(self._h, int(max_len)))
 
     def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False, alternatives: bool = False,
-                       token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None):
+                       token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None):
         """Luminance planes uint8 [n,224,224] (host), generate(max_length) ``max_len``; the keywords as for recognize_images
-        (``sources``: one plane index per output row)."""
+        (``sources``: one plane index per output row; ``beam``: (ids [n,K,max_len], lengths [n,K], scores [n,K]))."""
         a = np.ascontiguousarray(gray, dtype=np.uint8)
         n = n_planes = a.shape[0]
+        if beam is not None:
+            cfg, ids, lens, sc = self._beam_blocks(beam, n, scores=scores, alternatives=alternatives, token_sets=token_sets,
+                                                   no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources)
+            self._check(self.lib.mocr_recognize_gray_host_beam(self._h, _ptr(a), n, max_len or self.spec.max_len, C.byref(cfg), _ptr(ids),
+                                                               _ptr(lens), _ptr(sc)))
+            return ids, lens, sc
         if sources is not None:
             src = self._sources(sources, n_planes)
             n = int(src.size)
@@ -513,6 +614,19 @@ class Engine:
                                                       _ptr(d_set_of_row), _ptr(d_row_mask), _ptr(d_base_mask), _ptr(d_base_set_of_row),
                                                       _ptr(d_ngram_of_row), _ptr(d_prefix), _ptr(d_prefix_len), int(prefix_ld),
                                                       _ptr(d_tgt_val)))
+
+    def op_beam_select(self, beam: BeamConfig, d_beam_score, d_parent, d_hyp_ids, d_hyp_len, d_hyp_score, d_heuristic_open, **kw) -> None:
+        """The selection that ends a beam step (include/mocr.h mocr_op_beam_select); keywords: the fields of mocr_token_args."""
+        cfg = beam.as_struct()
+        self._check(self.lib.mocr_op_beam_select(self._h, self._args(_capi.MocrTokenArgs, kw), C.byref(cfg), _ptr(d_beam_score),
+                                                 _ptr(d_parent), _ptr(d_hyp_ids), _ptr(d_hyp_len), _ptr(d_hyp_score), _ptr(d_heuristic_open)))
+
+    def op_beam_permute(self, d_cache, layers: int, layer_stride: int, row_stride: int, segs: int, seg_stride: int, pos_bytes: int,
+                        K: int, d_parent, d_rowmap, d_finished, d_step, n_slots: int, max_pos: int) -> None:
+        """The cache reorder behind the selection on a device buffer (include/mocr.h mocr_op_beam_permute); strides in bytes."""
+        self._check(self.lib.mocr_op_beam_permute(self._h, _ptr(d_cache), int(layers), int(layer_stride), int(row_stride), int(segs),
+                                                  int(seg_stride), int(pos_bytes), int(K), _ptr(d_parent), _ptr(d_rowmap),
+                                                  _ptr(d_finished), _ptr(d_step), int(n_slots), int(max_pos)))
 
     def op_attn_positions(self, d_q, d_k, d_len, rows: int, T: int, d_out_pos, d_out_map=None) -> None:
         """The positions kernel on device buffers (include/mocr.h mocr_op_attn_positions)."""

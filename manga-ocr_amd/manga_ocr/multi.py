@@ -267,6 +267,8 @@ class MultiGpuEngine:
                     "construct MangaOcr on one device to use the *_positions calls")
     NO_PREFIX = ("forced prefixes are not implemented for several devices (manga_ocr/multi.py: the workers make the plain greedy "
                  "call): construct MangaOcr on one device to use prefix= / score_text")
+    NO_BEAM = ("beam search is not implemented for several devices (manga_ocr/multi.py: the workers make the plain greedy call): "
+               "construct MangaOcr on one device to use num_beams / recognize_beam")
     NO_ALTERNATIVES = ("token alternatives are not implemented for several devices (manga_ocr/multi.py ships ids and lengths only): "
                        "construct MangaOcr on one device to use the *_alternatives calls")
 
@@ -529,17 +531,17 @@ class MultiGpuEngine:
     def token_set(self, ids) -> int:
         raise NotImplementedError(self.NO_CONSTRAINTS)
 
-    def _plain_only(self, scores, alternatives, token_sets, no_repeat_ngram, positions, prefixes=None) -> None:
+    def _plain_only(self, scores, alternatives, token_sets, no_repeat_ngram, positions, prefixes=None, beam=None) -> None:
         """the workers make the plain greedy call: the richest option asked for is the one refused"""
-        for asked, why in ((prefixes is not None, self.NO_PREFIX), (positions, self.NO_POSITIONS), (no_repeat_ngram is not None, self.NO_NGRAM),
+        for asked, why in ((beam is not None, self.NO_BEAM), (prefixes is not None, self.NO_PREFIX), (positions, self.NO_POSITIONS), (no_repeat_ngram is not None, self.NO_NGRAM),
                            (token_sets is not None, self.NO_CONSTRAINTS), (alternatives, self.NO_ALTERNATIVES), (scores, self.NO_SCORES)):
             if asked:
                 raise NotImplementedError(why)
 
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False,
                          alternatives: bool = False, token_sets=None, no_repeat_ngram=None, positions: bool = False,
-                         prefixes=None) -> Tuple[np.ndarray, np.ndarray]:
-        self._plain_only(scores, alternatives, token_sets, no_repeat_ngram, positions, prefixes)
+                         prefixes=None, beam=None) -> Tuple[np.ndarray, np.ndarray]:
+        self._plain_only(scores, alternatives, token_sets, no_repeat_ngram, positions, prefixes, beam)
         n = len(images)
         if n == 0:
             return np.zeros((0, self.max_len), np.int32), np.zeros(0, np.int32)
@@ -554,8 +556,8 @@ class MultiGpuEngine:
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False,
                           alternatives: bool = False, token_sets=None, no_repeat_ngram=None, positions: bool = False,
-                         prefixes=None) -> Tuple[np.ndarray, np.ndarray]:
-        self._plain_only(scores, alternatives, token_sets, no_repeat_ngram, positions, prefixes)
+                         prefixes=None, beam=None) -> Tuple[np.ndarray, np.ndarray]:
+        self._plain_only(scores, alternatives, token_sets, no_repeat_ngram, positions, prefixes, beam)
         regs = [tuple(int(v) for v in r) for r in regions]
         n = len(regs)
         if n == 0:

@@ -23,7 +23,8 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from .engine import Engine
+from ._capi import MAX_BEAMS
+from .engine import BeamConfig, Engine
 from .text import Vocab, find_vocab, ids_to_text
 from .weights import DEFAULT_SPEC, load_checkpoint, synthetic_weights
 
@@ -106,6 +107,32 @@ def resolve_no_repeat_ngram(value, ignored: dict, max_len: int):
     if not 0 <= int(value) <= max_len:
         raise ValueError(f"no_repeat_ngram_size must be in 0 .. max_len ({max_len}), 0 = off; got {value}")
     return int(value), ignored
+
+
+def resolve_num_beams(value, ignored: dict, ngram_default=None):
+    """``MangaOcr(num_beams=...)`` -> (the :class:`BeamConfig` every plain call decodes with, or None for today's greedy
+    behaviour; what is left of the checkpoint's ignored generation settings).  ``None``: nothing changes.  ``"checkpoint"``:
+    ``num_beams``, ``length_penalty``, ``early_stopping`` and ``no_repeat_ngram_size`` of the checkpoint's config, which are
+    then honoured and leave the ignored settings (a checkpoint that asks for no beams: None, nothing leaves).  An int in
+    2 .. 4: the same with the caller's number of beams.  ``ngram_default``: the size ``no_repeat_ngram_size=`` already
+    resolved to (it may have taken the checkpoint's value out of ``ignored`` before)."""
+    ignored = dict(ignored)
+    if value is None:
+        return None, ignored
+    if isinstance(value, str):
+        if value != "checkpoint":
+            raise ValueError(f"num_beams: None, an int or 'checkpoint', instead got {value!r}")
+        if int(ignored.get("num_beams", 1)) < 2:
+            return None, ignored
+        value = int(ignored["num_beams"])
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        raise TypeError(f"num_beams: None, an int or 'checkpoint', instead got {value!r}")
+    if not 2 <= int(value) <= MAX_BEAMS:
+        raise ValueError(f"num_beams must be in 2 .. {MAX_BEAMS} (the engine's limit; None = greedy), instead got {value}")
+    ignored.pop("num_beams", None)
+    ngram = ignored.pop("no_repeat_ngram_size", ngram_default or 0)
+    cfg = BeamConfig(int(value), float(ignored.pop("length_penalty", 1.0)), ignored.pop("early_stopping", False), int(ngram))
+    return cfg, ignored
 
 
 def _ngram_sizes(no_repeat_ngram, default, n: int) -> Optional[List[int]]:
@@ -194,6 +221,9 @@ class Recognition:
     positions: Optional[np.ndarray] = None
     rect: Optional[Tuple[int, int, int, int]] = None     # regions: (x, y, w, h) of the padded, clipped crop in page pixels
     n_forced: int = 0       # ``prefix=``: how many of ids[1:] the caller gave (their logprobs score the caller's tokens)
+    # the ``*_beam`` methods: the hypothesis' beam-search score, sum of its token log-probabilities / (tokens generated) **
+    # length_penalty (transformers' ``sequences_scores``); such a Recognition carries no per-token logprobs (confidence 0.0)
+    sequence_score: Optional[float] = None
     _vocab: object = field(default=None, repr=False, compare=False)      # what candidates() names the tokens with
 
     @classmethod
@@ -295,6 +325,7 @@ class _Request(NamedTuple):
     ngram: int              # no-repeat n-gram size, 0: off
     positions: bool
     prefix: Optional[tuple] = None      # forced prefix (token ids), None: none
+    beam: Optional[BeamConfig] = None   # beam search with this configuration, None: greedy
 
 
 class _Batcher:
@@ -308,7 +339,10 @@ class _Batcher:
     (``no_repeat_ngram=``): only a batch with a request of size > 0 passes ``no_repeat_ngram=``, one size per crop.  And for
     token positions (``positions=True``): only a batch with such a request passes ``positions=True``, and such a caller gets
     its positions as one more, last element of its result.  And for forced prefixes (``prefix=``): only a batch with such a
-    request passes ``prefixes=``, one per crop, None for the others."""
+    request passes ``prefixes=``, one per crop, None for the others.  Beam search (``beam=``) is a call of its own: a batch
+    is the run of queued requests that share the head's beam configuration (None for the greedy ones), so beam and greedy
+    submissions are never merged, and a beam batch holds at most ``max_batch // num_beams`` crops; such a caller gets
+    (ids [K, max_len], lengths [K], scores [K])."""
 
     def __init__(self, engine: Engine, max_batch: int, timeout_ms: float):
         self.engine, self.max_batch, self.timeout = engine, max_batch, timeout_ms / 1000.0
@@ -319,13 +353,13 @@ class _Batcher:
         self._thread.start()
 
     def submit(self, gray: np.ndarray, scored: bool = False, alternatives: bool = False, token_set: int = 0,
-               no_repeat_ngram: int = 0, positions: bool = False, prefix=None) -> Future:
+               no_repeat_ngram: int = 0, positions: bool = False, prefix=None, beam: Optional[BeamConfig] = None) -> Future:
         f: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
             self._q.append(_Request(gray, f, 2 if alternatives else 1 if scored else 0, int(token_set), int(no_repeat_ngram), bool(positions),
-                                    tuple(prefix) if prefix else None))
+                                    tuple(prefix) if prefix else None, beam))
             self._cv.notify()
         return f
 
@@ -342,8 +376,18 @@ class _Batcher:
                     if left <= 0:
                         break
                     self._cv.wait(left)
-                batch, self._q = self._q[:self.max_batch], self._q[self.max_batch:]
+                head = self._q[0].beam
+                cap = self.max_batch if head is None else max(1, self.max_batch // head.num_beams)
+                take = 1
+                while take < min(cap, len(self._q)) and self._q[take].beam == head:
+                    take += 1
+                batch, self._q = self._q[:take], self._q[take:]
             try:
+                if head is not None:
+                    ids, lens, sc = self.engine.recognize_images([r.gray for r in batch], beam=head)
+                    for i, r in enumerate(batch):
+                        r.future.set_result((ids[i].copy(), lens[i].copy(), sc[i].copy()))
+                    continue
                 kind = max(r.kind for r in batch)
                 kw = {}         # only what somebody asked for: a batch of plain requests makes the plain call
                 if kind:
@@ -392,7 +436,7 @@ class MangaOcr:
     def __init__(self, pretrained_model_name_or_path: str = DEFAULT_MODEL, force_cpu: bool = False, *,
                  dtype: Optional[str] = None, device: Optional[int] = None, devices: Optional[Sequence[int]] = None,
                  max_batch: Optional[int] = None, lanes: Optional[int] = None, batch_timeout_ms: Optional[float] = None,
-                 synthetic_seed: Optional[int] = None, no_repeat_ngram_size=None):
+                 synthetic_seed: Optional[int] = None, no_repeat_ngram_size=None, num_beams=None):
         """``MangaOcr()`` as the application calls it (``src/ui/main_window.py:3394``) builds the engine on this
         process's GPU with two lanes and an internal batch sized from the free HBM.  ``devices=[0, 1, ...]`` (or
         ``MANGA_OCR_DEVICES=0,1,...``) instead starts one child process per GPU and shards every batch call over
@@ -400,7 +444,15 @@ class MangaOcr:
         ``no_repeat_ngram_size``: transformers' setting of that name under this engine's greedy decoding (include/mocr.h,
         "no-repeat n-grams") for every call that does not say otherwise (``no_repeat_ngram=``): None = not used, as always; an
         int; or ``"checkpoint"`` = the value in the checkpoint's generation config, which then leaves
-        ``ignored_generation_config`` (the beam settings stay ignored)."""
+        ``ignored_generation_config`` (the beam settings stay ignored).
+        ``num_beams``: beam search (include/mocr.h, "beam search") for ``__call__`` and every plain ``recognize*`` method,
+        which then return the best hypothesis: None = greedy, as always; ``"checkpoint"`` = ``num_beams``,
+        ``length_penalty``, ``early_stopping`` and ``no_repeat_ngram_size`` of the checkpoint's generation config, which then
+        leave ``ignored_generation_config``; an int in 2 .. 4 = the same with that many beams.  The loader's warning about
+        ignored generation settings is then given only for what is still ignored.  The scored, alternatives, positions and
+        n-best methods (``recognize_scored``, ``recognize_alternatives``, ``recognize_positions``, ``recognize_nbest`` and
+        their batch forms, ``score_text``) keep decoding greedily: a beam hypothesis carries no per-token outputs; use
+        ``recognize_beam`` for all hypotheses with their scores."""
         if force_cpu:
             raise RuntimeError("this MangaOcr is the MI355X engine: there is no CPU path (force_cpu=True is not supported)")
         dtype = dtype or os.environ.get("MANGA_OCR_DTYPE", "bf16")
@@ -421,7 +473,15 @@ class MangaOcr:
                 raise FileNotFoundError(
                     f"no local copy of '{pretrained_model_name_or_path}' (looked at the path, $MANGA_OCR_MODEL_DIR and the "
                     "HF cache; this build never downloads). Set MANGA_OCR_SYNTHETIC=<seed> for synthetic weights.")
-            spec, weights = load_checkpoint(model_dir)
+            import warnings
+            with warnings.catch_warnings(record=num_beams is not None) as caught:
+                # (with num_beams= the loader's "ignores it" may not be true: what is still ignored is said below)
+                if num_beams is not None:
+                    warnings.simplefilter("always")         # recorded whatever the caller's filters; the others are given again
+                spec, weights = load_checkpoint(model_dir)
+            for w_ in caught or ():
+                if not (issubclass(w_.category, RuntimeWarning) and "non-greedy generation" in str(w_.message)):
+                    warnings.warn_explicit(w_.message, w_.category, w_.filename, w_.lineno)
             vp = find_vocab(model_dir)
             if vp is None:
                 raise FileNotFoundError(f"vocab.txt not found in {model_dir}")
@@ -434,9 +494,18 @@ class MangaOcr:
         # strings can differ from the pip package's; {} when there is nothing to report
         self.no_repeat_ngram_size, self.ignored_generation_config = resolve_no_repeat_ngram(
             no_repeat_ngram_size, dict(getattr(spec, "ignored_generation", ())), spec.max_len)
+        self.beam, self.ignored_generation_config = resolve_num_beams(num_beams, self.ignored_generation_config, self.no_repeat_ngram_size)
+        if num_beams is not None and self.ignored_generation_config:
+            import warnings
+            warnings.warn("checkpoint config asks for generation settings this engine still ignores: " + repr(self.ignored_generation_config) +
+                          (" (num_beams=: the checkpoint asks for no beams; greedy decode)" if self.beam is None else ""),
+                          RuntimeWarning, stacklevel=2)
         if self.no_repeat_ngram_size and devices is not None and len(devices) > 1:
             from .multi import MultiGpuEngine
             raise NotImplementedError(MultiGpuEngine.NO_NGRAM)
+        if self.beam is not None and devices is not None and len(devices) > 1:
+            from .multi import MultiGpuEngine
+            raise NotImplementedError(MultiGpuEngine.NO_BEAM)
         if devices is not None and len(devices) > 1:
             from .multi import MultiGpuEngine
             max_batch = int(max_batch or 2048)
@@ -464,6 +533,8 @@ class MangaOcr:
 
     # ------------------------------------------------------------------ reference call surface
     def __call__(self, img_or_path) -> str:
+        if getattr(self, "beam", None) is not None:
+            return self._best_text(self._batcher.submit(to_pixels(self._open(img_or_path)), beam=self.beam).result())
         ids = self._batcher.submit(to_pixels(self._open(img_or_path)), **self._single(None, None)).result()
         return ids_to_text(self.vocab, ids)
 
@@ -549,12 +620,17 @@ class MangaOcr:
         flat sequence of token ids for all crops, or a sequence of those (or None) per crop; the engine scores them and decodes
         on from there (include/mocr.h, "forced prefixes").  Every ``recognize*`` method takes all three."""
         crops = list(crops)
+        if self._beam_default(allowed, no_repeat_ngram, prefix):
+            ids, lens, _ = self._beam_images(crops, bgr, rotate, self.beam)
+            return [ids[i, 0, :lens[i, 0]].copy() for i in range(len(lens))]
         ids, lens = self.engine.recognize_images(crops, bgr, rotate, **self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix))
         return [ids[i, :lens[i]].copy() for i in range(len(lens))]
 
     def recognize(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> str:
         """``__call__`` (which keeps the reference's signature) with ``allowed=``: one crop decoded under a token set, and
         ``no_repeat_ngram=``: this call's no-repeat n-gram size (None: the constructor's ``no_repeat_ngram_size``)."""
+        if self._beam_default(allowed, no_repeat_ngram, prefix):
+            return self._best_text(self._batcher.submit(to_pixels(self._open(img_or_path)), beam=self.beam).result())
         ids = self._batcher.submit(to_pixels(self._open(img_or_path)), **self._single(allowed, no_repeat_ngram, prefix)).result()
         return ids_to_text(self.vocab, ids)
 
@@ -596,6 +672,9 @@ class MangaOcr:
         the padded crops (``src/ui/main_window.py:9530-9540``) are cut on the device.  One string per region
         ('' for a region reduced to a sliver, like the reference)."""
         regions = list(regions)
+        if self._beam_default(allowed, no_repeat_ngram, prefix):
+            ids, lens, _ = self._beam_regions(list(pages_bgr), regions, self.beam)
+            return [ids_to_text(self.vocab, ids[i, 0, :lens[i, 0]]) if lens[i, 0] > 0 else "" for i in range(len(lens))]
         ids, lens = self.engine.recognize_regions(list(pages_bgr), regions, True, **self._decode_kw(allowed, no_repeat_ngram, len(regions), prefix))
         return [ids_to_text(self.vocab, ids[i, :lens[i]]) if lens[i] > 0 else "" for i in range(len(lens))]
 
@@ -820,7 +899,8 @@ class MangaOcr:
         ``allowed`` / ``no_repeat_ngram`` apply to both calls, per crop.
 
         This is NOT beam search and is not guaranteed to hold the ``k`` most probable sequences: it holds the greedy reading
-        and the ``k - 1`` cheapest one-token departures from it, each continued greedily."""
+        and the ``k - 1`` cheapest one-token departures from it, each continued greedily.  Beam search proper is
+        :meth:`recognize_beam` / :meth:`recognize_batch_beam`."""
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
             raise ValueError(f"recognize_nbest: k must be an int >= 1, instead got {k!r}")
         self._check_alternatives()
@@ -859,6 +939,88 @@ class MangaOcr:
     def recognize_nbest(self, img_or_path, k: int = 4, *, allowed=None, no_repeat_ngram=None) -> List[Recognition]:
         """``recognize_batch_nbest`` for one crop."""
         return self.recognize_batch_nbest([self._open(img_or_path)], k, allowed=allowed, no_repeat_ngram=no_repeat_ngram)[0]
+
+    # ------------------------------------------------------------------ beam search
+    def _beam_default(self, allowed, no_repeat_ngram, prefix) -> bool:
+        """does a plain call decode with the constructor's beams?  (They do not combine with the per-call keywords.)"""
+        if getattr(self, "beam", None) is None:
+            return False
+        if allowed is not None or no_repeat_ngram is not None or prefix is not None:
+            raise ValueError("this MangaOcr decodes with beam search (num_beams=): allowed= / no_repeat_ngram= / prefix= do not combine with it")
+        return True
+
+    def _check_beam(self) -> None:
+        no = getattr(self.engine, "NO_BEAM", None)      # MultiGpuEngine: the workers make the plain greedy call
+        if no:
+            raise NotImplementedError(no)
+
+    def _best_text(self, triple) -> str:
+        ids, lens, _ = triple
+        return ids_to_text(self.vocab, ids[0, :lens[0]]) if lens[0] > 0 else ""
+
+    def _beam_chunks(self, n: int, beam: BeamConfig):
+        step = max(1, int(self.max_batch) // beam.num_beams)         # a beam request fits one batch: n * K <= max_batch
+        return [(i, min(n, i + step)) for i in range(0, n, step)]
+
+    def _beam_images(self, crops, bgr, rotate, beam: BeamConfig):
+        """(ids [n, K, max_len], lengths [n, K], scores [n, K]) of any number of crops, max_batch // K of them per engine call"""
+        self._check_beam()
+        parts = [self.engine.recognize_images(crops[a:b], bgr, None if rotate is None else list(rotate)[a:b], beam=beam)
+                 for a, b in self._beam_chunks(len(crops), beam)]
+        if not parts:
+            parts = [self.engine.recognize_images([], beam=beam)]
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
+
+    def _beam_regions(self, pages, regions, beam: BeamConfig):
+        self._check_beam()
+        parts = [self.engine.recognize_regions(pages, regions[a:b], True, beam=beam) for a, b in self._beam_chunks(len(regions), beam)]
+        if not parts:
+            parts = [self.engine.recognize_regions(pages, [], True, beam=beam)]
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
+
+    def _hypotheses(self, ids, lens, scores) -> List[Recognition]:
+        """one crop's [K, max_len] / [K] / [K] -> its finished hypotheses, best first (empty slots dropped)"""
+        none = np.zeros(0, dtype=np.float32)
+        return [Recognition(ids_to_text(self.vocab, ids[j, :lens[j]]), np.array(ids[j, :lens[j]], dtype=np.int32), none, 0.0, 0.0,
+                            sequence_score=float(scores[j])) for j in range(len(lens)) if lens[j] > 0]
+
+    def recognize_beam(self, img_or_path, num_beams: int = 4, length_penalty: float = 1.0, early_stopping=False,
+                       no_repeat_ngram: int = 0) -> List[Recognition]:
+        """Beam search for one crop (include/mocr.h, "beam search"): what transformers' ``generate(num_beams=...,
+        length_penalty=..., early_stopping=..., no_repeat_ngram_size=...)`` returns with ``num_return_sequences=num_beams`` -
+        the finished hypotheses, best first, each with its ``sequence_score``.  ``num_beams`` 2 .. 4; ``early_stopping``
+        False, True or "never".  Goes through the batcher; beam and greedy callers never share a batch."""
+        self._check_beam()
+        beam = BeamConfig(num_beams, length_penalty, early_stopping, no_repeat_ngram)
+        return self._hypotheses(*self._batcher.submit(to_pixels(self._open(img_or_path)), beam=beam).result())
+
+    def recognize_batch_beam(self, images: Sequence, num_beams: int = 4, length_penalty: float = 1.0, early_stopping=False,
+                             no_repeat_ngram: int = 0) -> List[List[Recognition]]:
+        """``recognize_beam`` for many crops: one list of hypotheses per crop."""
+        beam = BeamConfig(num_beams, length_penalty, early_stopping, no_repeat_ngram)
+        ids, lens, sc = self._beam_images([to_pixels(im) for im in images], False, None, beam)
+        return [self._hypotheses(ids[i], lens[i], sc[i]) for i in range(len(lens))]
+
+    def recognize_bgr_beam(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, num_beams: int = 4,
+                           length_penalty: float = 1.0, early_stopping=False, no_repeat_ngram: int = 0) -> List[List[Recognition]]:
+        """``recognize_bgr`` with beam search: one list of hypotheses per crop."""
+        from .queue_worker import rotation_code
+        beam = BeamConfig(num_beams, length_penalty, early_stopping, no_repeat_ngram)
+        crops = list(crops_bgr)
+        rot = None
+        if orientations is not None:
+            if len(orientations) != len(crops):
+                raise ValueError(f"recognize_bgr_beam: {len(crops)} crops but {len(orientations)} orientations")
+            rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
+        ids, lens, sc = self._beam_images(crops, True, rot, beam)
+        return [self._hypotheses(ids[i], lens[i], sc[i]) for i in range(len(lens))]
+
+    def recognize_regions_beam(self, pages_bgr: Sequence[np.ndarray], regions, num_beams: int = 4, length_penalty: float = 1.0,
+                               early_stopping=False, no_repeat_ngram: int = 0) -> List[List[Recognition]]:
+        """``recognize_regions`` with beam search: one list of hypotheses per region ([] for a sliver)."""
+        beam = BeamConfig(num_beams, length_penalty, early_stopping, no_repeat_ngram)
+        ids, lens, sc = self._beam_regions(list(pages_bgr), list(regions), beam)
+        return [self._hypotheses(ids[i], lens[i], sc[i]) for i in range(len(lens))]
 
     def recognize_page(self, page_bgr: np.ndarray, regions):
         """``_collect_manga_detections`` for one page: ``regions`` = the detector's (text, polygon) pairs."""

@@ -278,7 +278,7 @@ def spec_from_hf_config(cfg: dict) -> ModelSpec:
     # north_star fixes GREEDY decode, so the engine decodes greedily and says so once (warn, not fail).
     non_greedy = {}
     for k, dflt in (("num_beams", 1), ("no_repeat_ngram_size", 0), ("length_penalty", 1.0), ("do_sample", False),
-                    ("repetition_penalty", 1.0), ("num_beam_groups", 1)):
+                    ("repetition_penalty", 1.0), ("num_beam_groups", 1), ("early_stopping", False)):
         v = cfg.get(k, dec.get(k, dflt))
         if v is not None and v != dflt:
             non_greedy[k] = v

@@ -1,0 +1,79 @@
+#!/usr/bin/env python3
+"""What beam search costs: wall time per call of a bf16 engine, 64 crops, generate length 32, for
+  (i)   beam search, K = 4 (include/mocr.h "beam search": 256 decode rows over 64 encodings),
+  (ii)  the same 64 crops as 256 greedy scored rows through ``sources=`` - the same encoder pass, the same number of decode
+        rows, no selection and no cache reorder: (i) / (ii) is the price of those two,
+  (iii) plain greedy, 64 rows,
+and, with --profile, the two new kernels' times from the engine's per-kernel profile at 400 rows.
+
+    python tools/beam_cost.py [--tree DIR] [--label NAME] [--crops 64] [--beams 4] [--max-len 32] [--reps 7] [--profile]
+
+--tree: the checkout whose package and library are measured (default: this one); a built checkout of the parent commit runs
+(ii) and (iii) alone - they are the yardsticks and must agree between the two builds within their own run-to-run spread.
+Prints one JSON line per form: the median over the repetitions after two warm-ups and their min .. max, in milliseconds."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap.add_argument("--label", default="this")
+    ap.add_argument("--crops", type=int, default=64)
+    ap.add_argument("--beams", type=int, default=4)
+    ap.add_argument("--max-len", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--profile", action="store_true")
+    args = ap.parse_args()
+    tree = os.path.abspath(args.tree)
+    for p in (tree, os.path.join(tree, "manga-ocr_amd")):
+        sys.path.insert(0, p)
+    import numpy as np
+    import manga_ocr.engine as me
+    from manga_ocr.weights import DEFAULT_SPEC, synthetic_weights
+
+    K = args.beams
+    rows = args.crops * K
+    w = synthetic_weights(0)
+    eng = me.Engine(w, DEFAULT_SPEC, dtype="bf16", device=0, max_batch=rows, lanes=1)
+    gray = np.random.RandomState(rows).randint(0, 256, size=(args.crops, 224, 224), dtype=np.uint8)
+    source = np.repeat(np.arange(args.crops), K)
+    forms = [("greedy_shared_rows", lambda: eng.recognize_gray(gray, args.max_len, scores=True, sources=source)),
+             ("greedy", lambda: eng.recognize_gray(gray, args.max_len))]
+    beam = getattr(me, "BeamConfig", None)      # (the parent commit has no beam search)
+    if beam is not None:
+        cfg = beam(K, 2.0, True, 3)
+        forms.insert(0, ("beam", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg)))
+    for form, call in forms:
+        for _ in range(2):
+            call()
+        ms = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            call()
+            ms.append(1e3 * (time.perf_counter() - t0))
+        print(json.dumps(dict(what="beam_cost", build=args.label, form=form, crops=args.crops, beams=K, max_len=args.max_len, reps=args.reps,
+                              ms_per_call=round(statistics.median(ms), 3), spread_ms=[round(min(ms), 3), round(max(ms), 3)])), flush=True)
+    eng.close()
+    if args.profile and beam is not None:
+        n = 400 // K
+        eng = me.Engine(w, DEFAULT_SPEC, dtype="bf16", device=0, max_batch=n * K, lanes=1)
+        g = np.random.RandomState(7).randint(0, 256, size=(n, 224, 224), dtype=np.uint8)
+        eng.recognize_gray(g, args.max_len, beam=cfg)
+        eng.profile_enable(True)
+        eng.profile_reset()
+        eng.recognize_gray(g, args.max_len, beam=cfg)
+        for s in eng.profile_get():
+            if s["name"] in ("beam_select", "beam_permute", "beam_init", "dec_attn_self", "latent_self", "gemm_dec_vocab"):
+                print(json.dumps(dict(what="beam_kernels", build=args.label, rows=n * K, max_len=args.max_len, kernel=s["name"],
+                                      launches=s["launches"], total_ms=round(s["total_ms"], 3),
+                                      us_per_launch=round(1e3 * s["total_ms"] / max(s["launches"], 1), 2))), flush=True)
+        eng.close()
+
+
+if __name__ == "__main__":
+    main()
