@@ -51,6 +51,17 @@ class BeamConfig:
         return _capi.MocrBeamConfig(self.num_beams, self.length_penalty, EARLY_STOPPING[self.early_stopping], self.no_repeat_ngram)
 
 
+BLOCKS = ("ids", "lens", "logp", "alt_ids", "alt_logp", "pos")       # the output blocks of a greedy recognise call, in C order
+
+
+def result_layout(scores: bool = False, alternatives: bool = False, positions: bool = False) -> Tuple[str, ...]:
+    """The names of what a greedy recognise call returns, in order: (ids, lens[, logp[, alt_ids, alt_logp]][, pos]) - logp with
+    ``scores``, logp and the pair with ``alternatives``, pos last with ``positions``.  The one place that writes the layout
+    down: ``Engine._result`` packs by it, the batcher of ``manga_ocr/ocr.py`` unpacks by it."""
+    names = BLOCKS[:5] if alternatives else BLOCKS[:3] if scores else BLOCKS[:2]
+    return names + BLOCKS[5:] if positions else names
+
+
 def _ptr(a) -> C.c_void_p:
     """numpy array (host) / torch tensor (host or device) / int address -> void*"""
     if a is None:
@@ -268,10 +279,9 @@ class Engine:
 
     @staticmethod
     def _result(blocks, scores: bool, alternatives: bool, positions: bool):
-        """what the caller gets back: (ids, lens), then logp with ``scores``, logp and the pair with ``alternatives``, and pos
-        last with ``positions``"""
-        out = blocks[:5] if alternatives else blocks[:3] if scores else blocks[:2]
-        return out + (blocks[5],) if positions else out
+        """what the caller gets back of the six blocks: the ones :func:`result_layout` names"""
+        named = dict(zip(BLOCKS, blocks))
+        return tuple(named[name] for name in result_layout(scores, alternatives, positions))
 
     # ------------------------------------------------------------------ beam search
     def _beam_blocks(self, beam, n: int, **others):
@@ -293,6 +303,41 @@ class Engine:
         ngram = self._ngram(no_repeat_ngram, n) if no_repeat_ngram is not None else None
         sets = self._sets(token_sets, n) if token_sets is not None else None
         return sets, ngram
+
+    def _recognize(self, kind: str, n: int, lead, tail=(), *, beam, d_out=None, skip_empty: bool = False, **req):
+        """The one request path under recognize_images / _regions / _gray / _device.  ``kind``: the source kind as the C symbols
+        spell it; ``n``: its number of sources; ``lead()``: (the call's leading C arguments, sources counted last; whatever they
+        point into, kept until the call returns) - built only once the call is going to be made; ``tail``: what follows the
+        sources (recognize_gray's max_len).  ``req``: the method's other keywords IN ITS ORDER (the beam refusal names them so);
+        a host kind's ``scores`` / ``alternatives`` / ``positions`` flags make the output blocks here, with one row per entry
+        of ``sources`` when given; recognize_device brings buffers: ``d_out`` = (ids, lengths, beam scores) and the rest in
+        ``req``.  ``skip_empty``: no sources, no call.
+        The arguments are checked in this order: beam with anything else, ``sources``, the n-gram sizes, the sets, the
+        prefixes.  The symbol is mocr_recognize_{kind}_beam, else _shared with ``sources``, else _prefix with ``prefixes``, else
+        _positions - each the richest of its line, every output nobody asked for passed as null."""
+        host = d_out is None
+        if beam is not None:
+            cfg, *out = self._beam_blocks(beam, n if host else 0, **req)
+            if n > 0 or not skip_empty:
+                args, keep = lead()
+                self._check(getattr(self.lib, f"mocr_recognize_{kind}_beam")(self._h, *args, *tail, C.byref(cfg), *map(_ptr, out if host else d_out)))
+            return tuple(out) if host else None
+        rows, shared = n, ()
+        if req["sources"] is not None:
+            src = self._sources(req["sources"], n)
+            rows = int(src.size)
+            shared = (rows, _ptr(src))
+        flags = (req["scores"], req["alternatives"], req["positions"]) if host else None
+        blocks = self._blocks(rows, *flags) if host else d_out[:2] + (req["d_out_logp"], req["d_out_alt_ids"], req["d_out_alt_logp"], req["d_out_pos"])
+        if rows > 0 or not skip_empty:
+            args, keep = lead()
+            sets, ngram = self._per_crop(req["token_sets"], req["no_repeat_ngram"], rows)
+            pre, plen, ld = self._prefix_args(req["prefixes"], rows)
+            variant = "shared" if shared else "prefix" if req["prefixes"] is not None else "positions"
+            forced = (_ptr(pre), _ptr(plen), ld) if variant != "positions" else ()
+            self._check(getattr(self.lib, f"mocr_recognize_{kind}_{variant}")(self._h, *args, *shared, *tail, *map(_ptr, blocks[:5]), _ptr(sets), _ptr(ngram),
+                                                                            _ptr(blocks[5]), *forced))
+        return self._result(blocks, *flags) if host else None
 
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False,
                          token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None):
@@ -318,33 +363,11 @@ class Engine:
         ``beam``: a :class:`BeamConfig` - beam search instead of greedy decoding (include/mocr.h, "beam search"), with none of
         the other keywords.  Returns (ids int32 [n,K,max_len], lengths int32 [n,K], scores float32 [n,K]): every crop's K
         finished hypotheses, the best first, with their sequence scores; an empty slot has length 0 and score -1e9."""
-        n = len(images)
-        if beam is not None:
-            cfg, ids, lens, sc = self._beam_blocks(beam, n, scores=scores, alternatives=alternatives, token_sets=token_sets,
-                                                   no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources)
-            if n > 0:
-                descs, keep = self._image_descs(images, bgr, rotate)
-                self._check(self.lib.mocr_recognize_images_beam(self._h, descs, n, C.byref(cfg), _ptr(ids), _ptr(lens), _ptr(sc)))
-            return ids, lens, sc
-        if sources is not None:
-            src = self._sources(sources, n)
-            n = int(src.size)
-        blocks = self._blocks(n, scores, alternatives, positions)
-        if n > 0:
+        def lead():
             descs, keep = self._image_descs(images, bgr, rotate)
-            sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
-            if sources is not None:
-                pre, plen, ld = self._prefix_args(prefixes, n)
-                self._check(self.lib.mocr_recognize_images_shared(self._h, descs, len(keep), n, _ptr(src), *map(_ptr, blocks[:5]),
-                                                                  _ptr(sets), _ptr(ngram), _ptr(blocks[5]), _ptr(pre), _ptr(plen), ld))
-            elif prefixes is not None:
-                pre, plen, ld = self._prefixes(prefixes, n)
-                self._check(self.lib.mocr_recognize_images_prefix(self._h, descs, n, *map(_ptr, blocks[:5]), _ptr(sets), _ptr(ngram),
-                                                                  _ptr(blocks[5]), _ptr(pre), _ptr(plen), ld))
-            else:
-                self._check(self.lib.mocr_recognize_images_positions(self._h, descs, n, *map(_ptr, blocks[:5]), _ptr(sets), _ptr(ngram),
-                                                                     _ptr(blocks[5])))
-        return self._result(blocks, scores, alternatives, positions)
+            return (descs, len(keep)), keep
+        return self._recognize("images", len(images), lead, beam=beam, skip_empty=True, scores=scores, alternatives=alternatives, token_sets=token_sets,
+                               no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources)
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False,
                           token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None):
@@ -363,41 +386,15 @@ class Engine:
         ``beam``: a :class:`BeamConfig` (see recognize_images): (ids [n,K,max_len], lengths [n,K], scores [n,K]); a sliver's K
         slots are empty."""
         regs = list(regions)
-        n = n_regions = len(regs)
-        if beam is not None:
-            cfg, ids, lens, sc = self._beam_blocks(beam, n, scores=scores, alternatives=alternatives, token_sets=token_sets,
-                                                   no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources)
-            if n > 0:
-                descs, keep = self._image_descs(pages, bgr)
-                arr = (_capi.MocrRegion * n_regions)()
-                for i, (pg, x, y, w, h) in enumerate(regs):
-                    arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
-                self._check(self.lib.mocr_recognize_regions_beam(self._h, descs, len(keep), arr, n_regions, C.byref(cfg), _ptr(ids),
-                                                                 _ptr(lens), _ptr(sc)))
-            return ids, lens, sc
-        if sources is not None:
-            src = self._sources(sources, n_regions)
-            n = int(src.size)
-        blocks = self._blocks(n, scores, alternatives, positions)
-        if n > 0:
+
+        def lead():
             descs, keep = self._image_descs(pages, bgr)
-            arr = (_capi.MocrRegion * n_regions)()
+            arr = (_capi.MocrRegion * len(regs))()
             for i, (pg, x, y, w, h) in enumerate(regs):
                 arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
-            sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
-            if sources is not None:
-                pre, plen, ld = self._prefix_args(prefixes, n)
-                self._check(self.lib.mocr_recognize_regions_shared(self._h, descs, len(keep), arr, n_regions, n, _ptr(src),
-                                                                   *map(_ptr, blocks[:5]), _ptr(sets), _ptr(ngram), _ptr(blocks[5]),
-                                                                   _ptr(pre), _ptr(plen), ld))
-            elif prefixes is not None:
-                pre, plen, ld = self._prefixes(prefixes, n)
-                self._check(self.lib.mocr_recognize_regions_prefix(self._h, descs, len(keep), arr, n, *map(_ptr, blocks[:5]), _ptr(sets),
-                                                                   _ptr(ngram), _ptr(blocks[5]), _ptr(pre), _ptr(plen), ld))
-            else:
-                self._check(self.lib.mocr_recognize_regions_positions(self._h, descs, len(keep), arr, n, *map(_ptr, blocks[:5]), _ptr(sets),
-                                                                      _ptr(ngram), _ptr(blocks[5])))
-        return self._result(blocks, scores, alternatives, positions)
+            return (descs, len(keep), arr, len(regs)), keep
+        return self._recognize("regions", len(regs), lead, beam=beam, skip_empty=True, scores=scores, alternatives=alternatives, token_sets=token_sets,
+                               no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources)
 
     def graph_count(self) -> int:
         return int(self.lib.mocr_graph_count(self._h))
@@ -446,32 +443,9 @@ class Engine:
         ``n`` then counts the planes of ``d_gray``, the output buffers have ``len(sources)`` rows and the per-crop arguments
         are per row.  ``beam`` (a :class:`BeamConfig`) with ``d_out_score``: beam search - ``d_out_ids`` int32 [n,K,max_len],
         ``d_out_len`` int32 [n,K] and ``d_out_score`` float32 [n,K] receive the hypotheses; none of the other keywords."""
-        if beam is not None:
-            cfg = self._beam_blocks(beam, 0, d_out_logp=d_out_logp, d_out_alt_ids=d_out_alt_ids, d_out_alt_logp=d_out_alt_logp,
-                                    token_sets=token_sets, no_repeat_ngram=no_repeat_ngram, d_out_pos=d_out_pos, prefixes=prefixes,
-                                    sources=sources)[0]
-            self._check(self.lib.mocr_recognize_device_beam(self._h, _ptr(d_gray), n, C.byref(cfg), _ptr(d_out_ids), _ptr(d_out_len),
-                                                            _ptr(d_out_score)))
-            return
-        if sources is not None:
-            src = self._sources(sources, n)
-            rows = int(src.size)
-            sets, ngram = self._per_crop(token_sets, no_repeat_ngram, rows)
-            pre, plen, ld = self._prefix_args(prefixes, rows)
-            self._check(self.lib.mocr_recognize_device_shared(self._h, _ptr(d_gray), n, rows, _ptr(src), _ptr(d_out_ids), _ptr(d_out_len),
-                                                              _ptr(d_out_logp), _ptr(d_out_alt_ids), _ptr(d_out_alt_logp), _ptr(sets),
-                                                              _ptr(ngram), _ptr(d_out_pos), _ptr(pre), _ptr(plen), ld))
-            return
-        sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
-        if prefixes is not None:
-            pre, plen, ld = self._prefixes(prefixes, n)
-            self._check(self.lib.mocr_recognize_device_prefix(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len), _ptr(d_out_logp),
-                                                              _ptr(d_out_alt_ids), _ptr(d_out_alt_logp), _ptr(sets), _ptr(ngram),
-                                                              _ptr(d_out_pos), _ptr(pre), _ptr(plen), ld))
-            return
-        self._check(self.lib.mocr_recognize_device_positions(self._h, _ptr(d_gray), n, _ptr(d_out_ids), _ptr(d_out_len), _ptr(d_out_logp),
-                                                             _ptr(d_out_alt_ids), _ptr(d_out_alt_logp), _ptr(sets), _ptr(ngram),
-                                                             _ptr(d_out_pos)))
+        self._recognize("device", n, lambda: ((_ptr(d_gray), n), None), beam=beam, d_out=(d_out_ids, d_out_len, d_out_score), d_out_logp=d_out_logp,
+                        d_out_alt_ids=d_out_alt_ids, d_out_alt_logp=d_out_alt_logp, token_sets=token_sets, no_repeat_ngram=no_repeat_ngram,
+                        d_out_pos=d_out_pos, prefixes=prefixes, sources=sources)
 
     def set_generate_max_length(self, max_len: int) -> None:
         self._check(self.lib.mocr_set_generate_max_length(self._h, int(max_len)))
@@ -481,32 +455,9 @@ class Engine:
         """Luminance planes uint8 [n,224,224] (host), generate(max_length) ``max_len``; the keywords as for recognize_images
         (``sources``: one plane index per output row; ``beam``: (ids [n,K,max_len], lengths [n,K], scores [n,K]))."""
         a = np.ascontiguousarray(gray, dtype=np.uint8)
-        n = n_planes = a.shape[0]
-        if beam is not None:
-            cfg, ids, lens, sc = self._beam_blocks(beam, n, scores=scores, alternatives=alternatives, token_sets=token_sets,
-                                                   no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources)
-            self._check(self.lib.mocr_recognize_gray_host_beam(self._h, _ptr(a), n, max_len or self.spec.max_len, C.byref(cfg), _ptr(ids),
-                                                               _ptr(lens), _ptr(sc)))
-            return ids, lens, sc
-        if sources is not None:
-            src = self._sources(sources, n_planes)
-            n = int(src.size)
-        sets, ngram = self._per_crop(token_sets, no_repeat_ngram, n)
-        blocks = self._blocks(n, scores, alternatives, positions)
-        if sources is not None:
-            pre, plen, ld = self._prefix_args(prefixes, n)
-            self._check(self.lib.mocr_recognize_gray_host_shared(self._h, _ptr(a), n_planes, n, _ptr(src), max_len or self.spec.max_len,
-                                                                 *map(_ptr, blocks[:5]), _ptr(sets), _ptr(ngram), _ptr(blocks[5]),
-                                                                 _ptr(pre), _ptr(plen), ld))
-            return self._result(blocks, scores, alternatives, positions)
-        if prefixes is not None:
-            pre, plen, ld = self._prefixes(prefixes, n)
-            self._check(self.lib.mocr_recognize_gray_host_prefix(self._h, _ptr(a), n, max_len or self.spec.max_len, *map(_ptr, blocks[:5]),
-                                                                 _ptr(sets), _ptr(ngram), _ptr(blocks[5]), _ptr(pre), _ptr(plen), ld))
-            return self._result(blocks, scores, alternatives, positions)
-        self._check(self.lib.mocr_recognize_gray_host_positions(self._h, _ptr(a), n, max_len or self.spec.max_len, *map(_ptr, blocks[:5]),
-                                                                _ptr(sets), _ptr(ngram), _ptr(blocks[5])))
-        return self._result(blocks, scores, alternatives, positions)
+        return self._recognize("gray_host", a.shape[0], lambda: ((_ptr(a), a.shape[0]), a), (max_len or self.spec.max_len,), beam=beam, scores=scores,
+                               alternatives=alternatives, token_sets=token_sets, no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes,
+                               sources=sources)
 
     # ------------------------------------------------------------------ test hooks
     def encode(self, d_gray, n: int) -> np.ndarray:

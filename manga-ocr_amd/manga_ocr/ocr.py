@@ -24,7 +24,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from ._capi import MAX_BEAMS
-from .engine import BeamConfig, Engine
+from .engine import BeamConfig, Engine, result_layout
 from .text import Vocab, find_vocab, ids_to_text
 from .weights import DEFAULT_SPEC, load_checkpoint, synthetic_weights
 
@@ -320,10 +320,11 @@ class _Request(NamedTuple):
     """one queued single-crop request of the batcher"""
     gray: np.ndarray
     future: Future
-    kind: int               # 0 ids, 1 scored, 2 with the alternatives
+    scored: bool            # wants its logp (alternatives imply it)
+    alternatives: bool
+    positions: bool
     token_set: int          # 0: unconstrained
     ngram: int              # no-repeat n-gram size, 0: off
-    positions: bool
     prefix: Optional[tuple] = None      # forced prefix (token ids), None: none
     beam: Optional[BeamConfig] = None   # beam search with this configuration, None: greedy
 
@@ -358,7 +359,7 @@ class _Batcher:
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
-            self._q.append(_Request(gray, f, 2 if alternatives else 1 if scored else 0, int(token_set), int(no_repeat_ngram), bool(positions),
+            self._q.append(_Request(gray, f, bool(scored or alternatives), bool(alternatives), bool(positions), int(token_set), int(no_repeat_ngram),
                                     tuple(prefix) if prefix else None, beam))
             self._cv.notify()
         return f
@@ -388,10 +389,9 @@ class _Batcher:
                     for i, r in enumerate(batch):
                         r.future.set_result((ids[i].copy(), lens[i].copy(), sc[i].copy()))
                     continue
-                kind = max(r.kind for r in batch)
                 kw = {}         # only what somebody asked for: a batch of plain requests makes the plain call
-                if kind:
-                    kw["alternatives" if kind == 2 else "scores"] = True
+                if any(r.scored for r in batch):        # the richest call any request asked for
+                    kw["alternatives" if any(r.alternatives for r in batch) else "scores"] = True
                 if any(r.token_set for r in batch):
                     kw["token_sets"] = [r.token_set for r in batch]
                 if any(r.ngram for r in batch):
@@ -400,11 +400,12 @@ class _Batcher:
                     kw["positions"] = True
                 if any(r.prefix for r in batch):
                     kw["prefixes"] = [list(r.prefix) if r.prefix else None for r in batch]
-                res = self.engine.recognize_images([r.gray for r in batch], **kw)     # (ids, lens[, logp[, alt_ids, alt_logp]][, pos])
+                res = self.engine.recognize_images([r.gray for r in batch], **kw)
+                got = dict(zip(result_layout(kw.get("scores", False), kw.get("alternatives", False), kw.get("positions", False)), res))
                 for i, r in enumerate(batch):
                     # what this caller asked for, cut to its length: bare ids, or a tuple with its logp / alternatives / positions
-                    blocks = [0] + ([2] if r.kind else []) + ([3, 4] if r.kind == 2 else []) + ([-1] if r.positions else [])
-                    out = tuple(res[b][i, :res[1][i]].copy() for b in blocks)
+                    names = ["ids"] + ["logp"] * r.scored + ["alt_ids", "alt_logp"] * r.alternatives + ["pos"] * r.positions
+                    out = tuple(got[name][i, :got["lens"][i]].copy() for name in names)
                     r.future.set_result(out if len(out) > 1 else out[0])
             except BaseException as exc:  # every waiting caller gets the error; the loop lives on
                 for r in batch:
@@ -430,6 +431,73 @@ def default_max_batch(device: int, lanes: int) -> int:
     free, _total = device_memory(device)
     rows = int(free * 0.2 / (max(1, lanes) * _BYTES_PER_ROW_PER_LANE))
     return max(64, min(2048, rows // 64 * 64))
+
+
+class _Kind(NamedTuple):
+    """A result kind of the recognise surface: the engine flags that ask for it, what :meth:`MangaOcr._require` refuses it by on
+    several devices, and ``rows(ocr, source, *the engine's blocks)``: one result per row."""
+    flags: dict
+    refusal: Optional[str]
+    rows: object
+
+
+_TEXT = _Kind({}, None, lambda ocr, src, ids, lens: [ids[i, :lens[i]].copy() for i in range(len(lens))])      # token ids: the methods make the strings
+_SCORED = _Kind(dict(scores=True), "SCORES", lambda ocr, src, *blocks: ocr._recognitions(*blocks))
+_ALTS = _Kind(dict(alternatives=True), "ALTERNATIVES", lambda ocr, src, *blocks: ocr._recognitions_alt(*blocks))
+_POS = _Kind(dict(scores=True, positions=True), "POSITIONS", lambda ocr, src, *blocks: ocr._recognitions_pos(*blocks, rects=src.rects))
+
+
+class _Images(NamedTuple):
+    """A source of the recognise surface: crops for ``recognize_images``, 3-channel ones in OpenCV order with ``bgr``, each
+    with its rotation code in ``rotate``.  ``call(ocr, a, b, **kw)``: the engine call for crops a .. b (all of them by default)."""
+    crops: list
+    bgr: bool = False
+    rotate: Optional[Sequence[int]] = None
+    rects = None
+
+    @property
+    def n(self) -> int:
+        return len(self.crops)
+
+    def call(self, ocr, a: int = 0, b: Optional[int] = None, **kw):
+        return ocr.engine.recognize_images(self.crops[a:b], self.bgr, None if self.rotate is None else list(self.rotate)[a:b], **kw)
+
+
+class _Regions(NamedTuple):
+    """A source: (page_index, x, y, w, h) regions on BGR pages for ``recognize_regions``; ``rects`` (the positions kind): every
+    region's padded, clipped rectangle on its page."""
+    pages: list
+    regions: list
+    rects: Optional[list] = None
+
+    @property
+    def n(self) -> int:
+        return len(self.regions)
+
+    def with_rects(self) -> "_Regions":
+        from .regions import padded_rect
+        return self._replace(rects=[padded_rect(r[1:5], self.pages[int(r[0])].shape[0], self.pages[int(r[0])].shape[1]) for r in self.regions])
+
+    def call(self, ocr, a: int = 0, b: Optional[int] = None, **kw):
+        return ocr.engine.recognize_regions(self.pages, self.regions[a:b], True, **kw)
+
+
+class _Single(NamedTuple):
+    """A source: one crop that goes through the batcher and comes back as the one-row blocks the engine would have returned."""
+    pixels: np.ndarray
+    n = 1
+    rects = None
+
+    @staticmethod
+    def batcher_kw(kw: dict) -> dict:
+        """one row's engine keywords (``MangaOcr._decode_kw``) as ``_Batcher.submit`` names them"""
+        names = (("token_sets", "token_set"), ("no_repeat_ngram", "no_repeat_ngram"), ("prefixes", "prefix"))
+        return {single: kw[many][0] for many, single in names if many in kw}
+
+    def call(self, ocr, scores: bool = False, alternatives: bool = False, positions: bool = False, **kw):
+        out = ocr._batcher.submit(self.pixels, scored=scores, alternatives=alternatives, positions=positions, **self.batcher_kw(kw)).result()
+        ids, *rest = out if isinstance(out, tuple) else (out,)
+        return (ids[None], np.array([len(ids)]), *(a[None] for a in rest))
 
 
 class MangaOcr:
@@ -533,10 +601,14 @@ class MangaOcr:
 
     # ------------------------------------------------------------------ reference call surface
     def __call__(self, img_or_path) -> str:
-        if getattr(self, "beam", None) is not None:
-            return self._best_text(self._batcher.submit(to_pixels(self._open(img_or_path)), beam=self.beam).result())
-        ids = self._batcher.submit(to_pixels(self._open(img_or_path)), **self._single(None, None)).result()
-        return ids_to_text(self.vocab, ids)
+        return self.recognize(img_or_path)
+
+    def _require(self, what: str) -> None:
+        """refuse ``what`` (SCORES, CONSTRAINTS, NGRAM, PREFIX, POSITIONS, ALTERNATIVES, BEAM) on an engine that says it cannot:
+        MultiGpuEngine, whose workers make the plain greedy call and ship ids and lengths only, has a NO_* message for each"""
+        no = getattr(self.engine, "NO_" + what, None)
+        if no:
+            raise NotImplementedError(no)
 
     # ------------------------------------------------------------------ token constraints
     def token_set(self, chars=None, ids=None, exclude_chars=None) -> TokenSet:
@@ -547,9 +619,7 @@ class MangaOcr:
         vocabulary.  ``exclude_chars`` then removes every token whose text contains one of these characters.  EOS is always
         a member (the engine adds it).  The same content gives the same handle; sets live as long as this MangaOcr, at most
         255 of them (include/mocr.h, "token constraints")."""
-        no = getattr(self.engine, "NO_CONSTRAINTS", None)      # MultiGpuEngine: a set belongs to one engine
-        if no:
-            raise NotImplementedError(no)
+        self._require("CONSTRAINTS")
         if chars is None and ids is None:
             members = set(range(len(self.vocab)))
         else:
@@ -573,66 +643,46 @@ class MangaOcr:
         hs = _set_handles(allowed, n)
         if hs is None:
             return {}
-        no = getattr(self.engine, "NO_CONSTRAINTS", None)
-        if no:
-            raise NotImplementedError(no)
+        self._require("CONSTRAINTS")
         return dict(token_sets=hs)
 
-    # ------------------------------------------------------------------ no-repeat n-grams
+    # ------------------------------------------------------------------ the request path: a source x a result kind
     def _decode_kw(self, allowed, no_repeat_ngram, n: int, prefix=None) -> dict:
-        """the engine keywords of ``allowed=`` and ``no_repeat_ngram=`` ({} when neither is in use: the call the method always
-        made); a call's ``no_repeat_ngram`` overrides the constructor's ``no_repeat_ngram_size`` (0 = off for this call)"""
+        """the engine keywords of ``allowed=``, ``no_repeat_ngram=`` and ``prefix=`` ({} when none is in use: the call the method
+        always made); a call's ``no_repeat_ngram`` overrides the constructor's ``no_repeat_ngram_size`` (0 = off for this call)"""
         kw = self._allowed(allowed, n)
         gs = _ngram_sizes(no_repeat_ngram, getattr(self, "no_repeat_ngram_size", None), n)
         if gs is not None and any(gs):
-            no = getattr(self.engine, "NO_NGRAM", None)      # MultiGpuEngine
-            if no:
-                raise NotImplementedError(no)
+            self._require("NGRAM")
             kw["no_repeat_ngram"] = gs
         rows = _prefix_rows(prefix, n, self.vocab) if prefix is not None else None
         if rows is not None:
-            no = getattr(self.engine, "NO_PREFIX", None)      # MultiGpuEngine
-            if no:
-                raise NotImplementedError(no)
+            self._require("PREFIX")
             kw["prefixes"] = rows
         return kw
 
     def _single(self, allowed, no_repeat_ngram, prefix=None) -> dict:
         """the batcher keywords of one crop's ``allowed=`` / ``no_repeat_ngram=`` / ``prefix=``"""
-        kw = self._decode_kw(allowed, no_repeat_ngram, 1, prefix)
-        out = {}
-        if "token_sets" in kw:
-            out["token_set"] = kw["token_sets"][0]
-        if "no_repeat_ngram" in kw:
-            out["no_repeat_ngram"] = kw["no_repeat_ngram"][0]
-        if "prefixes" in kw:
-            out["prefix"] = kw["prefixes"][0]
-        return out
+        return _Single.batcher_kw(self._decode_kw(allowed, no_repeat_ngram, 1, prefix))
 
-    # ------------------------------------------------------------------ batch surface (callers that hold many crops)
-    def recognize_ids(self, crops: Sequence[np.ndarray], bgr: bool = False, rotate: Optional[Sequence[int]] = None, *,
-                      allowed=None, no_repeat_ngram=None, prefix=None) -> List[np.ndarray]:
-        """uint8 crops of any sizes ([h,w] luminance or [h,w,3] RGB; BGR with ``bgr=True``; ``rotate``: per crop 0 / 1 (90
-        degrees clockwise) / 2 (counter-clockwise), done by the device) -> token ids (without padding).  ``allowed``: a
-        token set of :meth:`token_set` for all crops, or one per crop.  ``no_repeat_ngram``: the no-repeat n-gram size of this
-        call, an int for all crops or one per crop, 0 = off (None: the constructor's ``no_repeat_ngram_size``).  ``prefix``:
-        tokens the rows start with, behind the start token - a ``str`` (one token per character, ``Vocab.encode_chars``) or a
-        flat sequence of token ids for all crops, or a sequence of those (or None) per crop; the engine scores them and decodes
-        on from there (include/mocr.h, "forced prefixes").  Every ``recognize*`` method takes all three."""
-        crops = list(crops)
-        if self._beam_default(allowed, no_repeat_ngram, prefix):
-            ids, lens, _ = self._beam_images(crops, bgr, rotate, self.beam)
+    def _run(self, source, kind: _Kind, allowed=None, no_repeat_ngram=None, prefix=None, sources=None) -> list:
+        """Every greedy recognise method: one row of ``kind`` per crop or region of the source - or per entry of ``sources``
+        (shared encodings).  In this order: the kind's refusal (several devices), before the image is opened or any argument
+        is looked at; for plain text, whether the constructor's beams decode it instead (``_beam_default``); ``source()``, which
+        opens, converts and checks the inputs; ``_decode_kw``; the ONE engine call, with the kind's flags and only the keywords
+        somebody asked for; the kind's rows; ``n_forced`` of the rows that were given a prefix."""
+        if kind.refusal:
+            self._require(kind.refusal)
+        beams = kind is _TEXT and self._beam_default(allowed, no_repeat_ngram, prefix)
+        src = source()
+        if beams:
+            ids, lens, _ = self._beam(src, self.beam)
             return [ids[i, 0, :lens[i, 0]].copy() for i in range(len(lens))]
-        ids, lens = self.engine.recognize_images(crops, bgr, rotate, **self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix))
-        return [ids[i, :lens[i]].copy() for i in range(len(lens))]
-
-    def recognize(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> str:
-        """``__call__`` (which keeps the reference's signature) with ``allowed=``: one crop decoded under a token set, and
-        ``no_repeat_ngram=``: this call's no-repeat n-gram size (None: the constructor's ``no_repeat_ngram_size``)."""
-        if self._beam_default(allowed, no_repeat_ngram, prefix):
-            return self._best_text(self._batcher.submit(to_pixels(self._open(img_or_path)), beam=self.beam).result())
-        ids = self._batcher.submit(to_pixels(self._open(img_or_path)), **self._single(allowed, no_repeat_ngram, prefix)).result()
-        return ids_to_text(self.vocab, ids)
+        kw = self._decode_kw(allowed, no_repeat_ngram, src.n if sources is None else len(sources), prefix)
+        if sources is not None:
+            kw["sources"] = sources
+        rows = kind.rows(self, src, *src.call(self, **kind.flags, **kw))
+        return rows if kind is _TEXT else self._mark_forced(rows, kw.get("prefixes"))
 
     @staticmethod
     def _open(img_or_path):
@@ -643,46 +693,29 @@ class MangaOcr:
             return img_or_path
         raise ValueError(f"img_or_path must be a path or PIL.Image, instead got: {img_or_path}")
 
-    def recognize_batch(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
-        """All crops of a page (or chapter) at once - what ``_collect_manga_detections``
-        (``src/ui/main_window.py:9462-9476``) does one region at a time."""
-        return [ids_to_text(self.vocab, r) for r in self.recognize_ids([to_pixels(im) for im in images], allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix)]
+    def _one(self, img_or_path):
+        """source of the single-crop methods: the image, opened, through the batcher"""
+        return lambda: _Single(to_pixels(self._open(img_or_path)))
 
-    def recognize_batch_arrays(self, crops: Sequence[np.ndarray], *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
-        """uint8 arrays ([h,w] luminance or [h,w,3] RGB, any sizes) -> strings: what a caller that already holds numpy
-        crops (the crop-job queue) uses instead of wrapping each one in a PIL image."""
-        return [ids_to_text(self.vocab, r) for r in self.recognize_ids(list(crops), allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix)]
+    @staticmethod
+    def _pil(images):
+        """source of the ``recognize_batch*`` methods: PIL images"""
+        return lambda: _Images([to_pixels(im) for im in images])
 
-    def recognize_bgr(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
-        """BGR crops exactly as the crop tools and the worker hold them (``cropped_cv_img``, ``src/core/workers.py:300``):
-        the BGR -> RGB swap of ``src/ui/main_window.py:9800`` is folded into the device's luminance conversion, and with
-        ``orientations`` (the jobs' "Auto-Detect" / "Vertical" / "Horizontal" settings) the orientation-only rotation of
-        ``src/core/workers.py:320-326`` / ``src/ui/main_window.py:9787-9795`` into the device's resize addressing."""
+    @staticmethod
+    def _bgr(method: str, crops_bgr, orientations) -> _Images:
+        """source of the ``recognize_bgr*`` methods: BGR crops, each with the rotation code of its orientation setting"""
         from .queue_worker import rotation_code
         crops = list(crops_bgr)
         rot = None
         if orientations is not None:
             if len(orientations) != len(crops):        # zip() would truncate silently: a short list must not cost a decode
-                raise ValueError(f"recognize_bgr: {len(crops)} crops but {len(orientations)} orientations")
+                raise ValueError(f"{method}: {len(crops)} crops but {len(orientations)} orientations")
             rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
-        return [ids_to_text(self.vocab, r) for r in self.recognize_ids(crops, bgr=True, rotate=rot, allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix)]
+        return _Images(crops, True, rot)
 
-    def recognize_regions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
-        """``regions``: (page_index, x, y, w, h) bounding rectangles on BGR pages; every page is uploaded once and
-        the padded crops (``src/ui/main_window.py:9530-9540``) are cut on the device.  One string per region
-        ('' for a region reduced to a sliver, like the reference)."""
-        regions = list(regions)
-        if self._beam_default(allowed, no_repeat_ngram, prefix):
-            ids, lens, _ = self._beam_regions(list(pages_bgr), regions, self.beam)
-            return [ids_to_text(self.vocab, ids[i, 0, :lens[i, 0]]) if lens[i, 0] > 0 else "" for i in range(len(lens))]
-        ids, lens = self.engine.recognize_regions(list(pages_bgr), regions, True, **self._decode_kw(allowed, no_repeat_ngram, len(regions), prefix))
-        return [ids_to_text(self.vocab, ids[i, :lens[i]]) if lens[i] > 0 else "" for i in range(len(lens))]
-
-    # ------------------------------------------------------------------ scored surface: the same recognitions + confidence
-    def _check_scored(self) -> None:
-        no = getattr(self.engine, "NO_SCORES", None)      # MultiGpuEngine: its exchange ships ids and lengths only
-        if no:
-            raise NotImplementedError(no)
+    def _texts(self, rows) -> List[str]:
+        return [ids_to_text(self.vocab, r) for r in rows]
 
     @staticmethod
     def _mark_forced(recs: List[Recognition], prefixes) -> List[Recognition]:
@@ -694,145 +727,118 @@ class MangaOcr:
     def _recognitions(self, ids, lens, logp) -> List[Recognition]:
         return [Recognition.from_row(self.vocab, ids[i], logp[i], lens[i]) for i in range(len(lens))]
 
-    def recognize_scored(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> Recognition:
-        """``__call__`` with the recogniser's confidence: same text, plus the token log-probabilities computed on the
-        device (include/mocr.h, "token scores").  Goes through the same batcher as ``__call__``; scored and unscored
-        callers may share a batch."""
-        self._check_scored()
-        img = self._open(img_or_path)
-        extra = self._single(allowed, no_repeat_ngram, prefix)
-        ids, logp = self._batcher.submit(to_pixels(img), scored=True, **extra).result()
-        return self._mark_forced([Recognition.from_row(self.vocab, ids, logp, len(ids))], [extra.get("prefix")])[0]
-
-    def recognize_batch_scored(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
-        """``recognize_batch`` with confidences."""
-        self._check_scored()
-        crops = [to_pixels(im) for im in images]
-        kw = self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix)
-        return self._mark_forced(self._recognitions(*self.engine.recognize_images(crops, scores=True, **kw)), kw.get("prefixes"))
-
-    def recognize_bgr_scored(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
-                             allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
-        """``recognize_bgr`` with confidences."""
-        from .queue_worker import rotation_code
-        self._check_scored()
-        crops = list(crops_bgr)
-        rot = None
-        if orientations is not None:
-            if len(orientations) != len(crops):
-                raise ValueError(f"recognize_bgr_scored: {len(crops)} crops but {len(orientations)} orientations")
-            rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
-        kw = self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix)
-        return self._mark_forced(self._recognitions(*self.engine.recognize_images(crops, True, rot, scores=True, **kw)), kw.get("prefixes"))
-
-    def recognize_regions_scored(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
-        """``recognize_regions`` with confidences; a region reduced to a sliver gives text '' and confidence 0.0."""
-        self._check_scored()
-        regions = list(regions)
-        kw = self._decode_kw(allowed, no_repeat_ngram, len(regions), prefix)
-        return self._mark_forced(self._recognitions(*self.engine.recognize_regions(list(pages_bgr), regions, True, scores=True, **kw)), kw.get("prefixes"))
-
-    # ------------------------------------------------------------------ alternatives surface: + the runners-up of every position
-    def _check_alternatives(self) -> None:
-        no = getattr(self.engine, "NO_ALTERNATIVES", None)      # MultiGpuEngine: its exchange ships ids and lengths only
-        if no:
-            raise NotImplementedError(no)
-
     def _recognitions_alt(self, ids, lens, logp, alt_ids, alt_logp) -> List[Recognition]:
         return [Recognition.from_row(self.vocab, ids[i], logp[i], lens[i], alt_ids[i], alt_logp[i]) for i in range(len(lens))]
-
-    def recognize_alternatives(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> Recognition:
-        """``recognize_scored`` plus, for every generated position, the four most probable tokens and their log-probabilities
-        (``Recognition.alt_ids`` / ``alt_logprobs`` / ``candidates``; include/mocr.h, "token alternatives").  Same text; goes
-        through the same batcher as ``__call__``, and callers of all three kinds may share a batch."""
-        self._check_alternatives()
-        img = self._open(img_or_path)
-        extra = self._single(allowed, no_repeat_ngram, prefix)
-        ids, logp, alt_ids, alt_logp = self._batcher.submit(to_pixels(img), alternatives=True, **extra).result()
-        return self._mark_forced([Recognition.from_row(self.vocab, ids, logp, len(ids), alt_ids, alt_logp)], [extra.get("prefix")])[0]
-
-    def recognize_batch_alternatives(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
-        """``recognize_batch`` with confidences and alternatives."""
-        self._check_alternatives()
-        crops = [to_pixels(im) for im in images]
-        kw = self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix)
-        return self._mark_forced(self._recognitions_alt(*self.engine.recognize_images(crops, alternatives=True, **kw)), kw.get("prefixes"))
-
-    def recognize_bgr_alternatives(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
-                                   allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
-        """``recognize_bgr`` with confidences and alternatives."""
-        from .queue_worker import rotation_code
-        self._check_alternatives()
-        crops = list(crops_bgr)
-        rot = None
-        if orientations is not None:
-            if len(orientations) != len(crops):
-                raise ValueError(f"recognize_bgr_alternatives: {len(crops)} crops but {len(orientations)} orientations")
-            rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
-        kw = self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix)
-        return self._mark_forced(self._recognitions_alt(*self.engine.recognize_images(crops, True, rot, alternatives=True, **kw)), kw.get("prefixes"))
-
-    def recognize_regions_alternatives(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
-        """``recognize_regions`` with confidences and alternatives; a region reduced to a sliver gives text '', confidence
-        0.0 and empty alternatives."""
-        self._check_alternatives()
-        regions = list(regions)
-        kw = self._decode_kw(allowed, no_repeat_ngram, len(regions), prefix)
-        return self._mark_forced(self._recognitions_alt(*self.engine.recognize_regions(list(pages_bgr), regions, True, alternatives=True, **kw)), kw.get("prefixes"))
-
-    # ------------------------------------------------------------------ positions surface: + where each token was read
-    def _check_positions(self) -> None:
-        no = getattr(self.engine, "NO_POSITIONS", None)      # MultiGpuEngine: its exchange ships ids and lengths only
-        if no:
-            raise NotImplementedError(no)
 
     def _recognitions_pos(self, ids, lens, logp, pos, rects=None) -> List[Recognition]:
         return [Recognition.from_row(self.vocab, ids[i], logp[i], lens[i], pos_row=pos[i], rect=rects[i] if rects is not None else None)
                 for i in range(len(lens))]
 
+    # ------------------------------------------------------------------ batch surface (callers that hold many crops)
+    def recognize_ids(self, crops: Sequence[np.ndarray], bgr: bool = False, rotate: Optional[Sequence[int]] = None, *,
+                      allowed=None, no_repeat_ngram=None, prefix=None) -> List[np.ndarray]:
+        """uint8 crops of any sizes ([h,w] luminance or [h,w,3] RGB; BGR with ``bgr=True``; ``rotate``: per crop 0 / 1 (90
+        degrees clockwise) / 2 (counter-clockwise), done by the device) -> token ids (without padding).  ``allowed``: a
+        token set of :meth:`token_set` for all crops, or one per crop.  ``no_repeat_ngram``: the no-repeat n-gram size of this
+        call, an int for all crops or one per crop, 0 = off (None: the constructor's ``no_repeat_ngram_size``).  ``prefix``:
+        tokens the rows start with, behind the start token - a ``str`` (one token per character, ``Vocab.encode_chars``) or a
+        flat sequence of token ids for all crops, or a sequence of those (or None) per crop; the engine scores them and decodes
+        on from there (include/mocr.h, "forced prefixes").  Every ``recognize*`` method takes all three."""
+        return self._run(lambda: _Images(list(crops), bgr, rotate), _TEXT, allowed, no_repeat_ngram, prefix)
+
+    def recognize(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> str:
+        """``__call__`` (which keeps the reference's signature) with ``allowed=``: one crop decoded under a token set, and
+        ``no_repeat_ngram=``: this call's no-repeat n-gram size (None: the constructor's ``no_repeat_ngram_size``)."""
+        return self._texts(self._run(self._one(img_or_path), _TEXT, allowed, no_repeat_ngram, prefix))[0]
+
+    def recognize_batch(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
+        """All crops of a page (or chapter) at once - what ``_collect_manga_detections``
+        (``src/ui/main_window.py:9462-9476``) does one region at a time."""
+        return self._texts(self.recognize_ids([to_pixels(im) for im in images], allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix))
+
+    def recognize_batch_arrays(self, crops: Sequence[np.ndarray], *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
+        """uint8 arrays ([h,w] luminance or [h,w,3] RGB, any sizes) -> strings: what a caller that already holds numpy
+        crops (the crop-job queue) uses instead of wrapping each one in a PIL image."""
+        return self._texts(self.recognize_ids(crops, allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix))
+
+    def recognize_bgr(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
+        """BGR crops exactly as the crop tools and the worker hold them (``cropped_cv_img``, ``src/core/workers.py:300``):
+        the BGR -> RGB swap of ``src/ui/main_window.py:9800`` is folded into the device's luminance conversion, and with
+        ``orientations`` (the jobs' "Auto-Detect" / "Vertical" / "Horizontal" settings) the orientation-only rotation of
+        ``src/core/workers.py:320-326`` / ``src/ui/main_window.py:9787-9795`` into the device's resize addressing."""
+        src = self._bgr("recognize_bgr", crops_bgr, orientations)
+        return self._texts(self._run(lambda: src, _TEXT, allowed, no_repeat_ngram, prefix))
+
+    def recognize_regions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
+        """``regions``: (page_index, x, y, w, h) bounding rectangles on BGR pages; every page is uploaded once and
+        the padded crops (``src/ui/main_window.py:9530-9540``) are cut on the device.  One string per region
+        ('' for a region reduced to a sliver, like the reference)."""
+        return self._texts(self._run(lambda: _Regions(list(pages_bgr), list(regions)), _TEXT, allowed, no_repeat_ngram, prefix))
+
+    # ------------------------------------------------------------------ scored surface: the same recognitions + confidence
+    def recognize_scored(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> Recognition:
+        """``__call__`` with the recogniser's confidence: same text, plus the token log-probabilities computed on the
+        device (include/mocr.h, "token scores").  Goes through the same batcher as ``__call__``; scored and unscored
+        callers may share a batch."""
+        return self._run(self._one(img_or_path), _SCORED, allowed, no_repeat_ngram, prefix)[0]
+
+    def recognize_batch_scored(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+        """``recognize_batch`` with confidences."""
+        return self._run(self._pil(images), _SCORED, allowed, no_repeat_ngram, prefix)
+
+    def recognize_bgr_scored(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
+                             allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+        """``recognize_bgr`` with confidences."""
+        return self._run(lambda: self._bgr("recognize_bgr_scored", crops_bgr, orientations), _SCORED, allowed, no_repeat_ngram, prefix)
+
+    def recognize_regions_scored(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+        """``recognize_regions`` with confidences; a region reduced to a sliver gives text '' and confidence 0.0."""
+        return self._run(lambda: _Regions(list(pages_bgr), list(regions)), _SCORED, allowed, no_repeat_ngram, prefix)
+
+    # ------------------------------------------------------------------ alternatives surface: + the runners-up of every position
+    def recognize_alternatives(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> Recognition:
+        """``recognize_scored`` plus, for every generated position, the four most probable tokens and their log-probabilities
+        (``Recognition.alt_ids`` / ``alt_logprobs`` / ``candidates``; include/mocr.h, "token alternatives").  Same text; goes
+        through the same batcher as ``__call__``, and callers of all three kinds may share a batch."""
+        return self._run(self._one(img_or_path), _ALTS, allowed, no_repeat_ngram, prefix)[0]
+
+    def recognize_batch_alternatives(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+        """``recognize_batch`` with confidences and alternatives."""
+        return self._run(self._pil(images), _ALTS, allowed, no_repeat_ngram, prefix)
+
+    def recognize_bgr_alternatives(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
+                                   allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+        """``recognize_bgr`` with confidences and alternatives."""
+        return self._run(lambda: self._bgr("recognize_bgr_alternatives", crops_bgr, orientations), _ALTS, allowed, no_repeat_ngram, prefix)
+
+    def recognize_regions_alternatives(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+        """``recognize_regions`` with confidences and alternatives; a region reduced to a sliver gives text '', confidence
+        0.0 and empty alternatives."""
+        return self._run(lambda: _Regions(list(pages_bgr), list(regions)), _ALTS, allowed, no_repeat_ngram, prefix)
+
+    # ------------------------------------------------------------------ positions surface: + where each token was read
     def recognize_positions(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> Recognition:
         """``recognize_scored`` plus ``Recognition.positions``: per token where in the crop the decoder looked when it emitted
         it (include/mocr.h, "token positions"); ``Recognition.boxes(width, height)`` gives pixel rectangles.  Same text and
         scores; goes through the same batcher as ``__call__``, and callers of all kinds may share a batch."""
-        self._check_positions()
-        img = self._open(img_or_path)
-        extra = self._single(allowed, no_repeat_ngram, prefix)
-        ids, logp, pos = self._batcher.submit(to_pixels(img), scored=True, positions=True, **extra).result()
-        return self._mark_forced([Recognition.from_row(self.vocab, ids, logp, len(ids), pos_row=pos)], [extra.get("prefix")])[0]
+        return self._run(self._one(img_or_path), _POS, allowed, no_repeat_ngram, prefix)[0]
 
     def recognize_batch_positions(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
         """``recognize_batch_scored`` with positions."""
-        self._check_positions()
-        crops = [to_pixels(im) for im in images]
-        kw = self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix)
-        return self._mark_forced(self._recognitions_pos(*self.engine.recognize_images(crops, scores=True, positions=True, **kw)), kw.get("prefixes"))
+        return self._run(self._pil(images), _POS, allowed, no_repeat_ngram, prefix)
 
     def recognize_bgr_positions(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
                                 allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
         """``recognize_bgr_scored`` with positions.  The positions are those of the crop the encoder saw, i.e. after the
         orientation's rotation: pass the crop's rotation code (``queue_worker.rotation_code``) to ``Recognition.boxes`` to get
         rectangles on the crop as it was handed in."""
-        from .queue_worker import rotation_code
-        self._check_positions()
-        crops = list(crops_bgr)
-        rot = None
-        if orientations is not None:
-            if len(orientations) != len(crops):
-                raise ValueError(f"recognize_bgr_positions: {len(crops)} crops but {len(orientations)} orientations")
-            rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
-        kw = self._decode_kw(allowed, no_repeat_ngram, len(crops), prefix)
-        return self._mark_forced(self._recognitions_pos(*self.engine.recognize_images(crops, True, rot, scores=True, positions=True, **kw)), kw.get("prefixes"))
+        return self._run(lambda: self._bgr("recognize_bgr_positions", crops_bgr, orientations), _POS, allowed, no_repeat_ngram, prefix)
 
     def recognize_regions_positions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
         """``recognize_regions_scored`` with positions: every Recognition carries ``rect``, the region's padded, clipped
         rectangle on its page (``regions.padded_rect``), so ``Recognition.page_boxes()`` gives the tokens' rectangles in page
         pixels.  A region reduced to a sliver gives text '', no positions rows and ``rect`` None."""
-        from .regions import padded_rect
-        self._check_positions()
-        pages, regions = list(pages_bgr), list(regions)
-        rects = [padded_rect(r[1:5], pages[int(r[0])].shape[0], pages[int(r[0])].shape[1]) for r in regions]
-        kw = self._decode_kw(allowed, no_repeat_ngram, len(regions), prefix)
-        return self._mark_forced(self._recognitions_pos(*self.engine.recognize_regions(pages, regions, True, scores=True, positions=True, **kw), rects=rects), kw.get("prefixes"))
+        return self._run(lambda: _Regions(list(pages_bgr), list(regions)).with_rects(), _POS, allowed, no_repeat_ngram, prefix)
 
     # ------------------------------------------------------------------ forced prefixes: score a given text
     def _text_prefix(self, text) -> List[int]:
@@ -854,24 +860,16 @@ class MangaOcr:
         return self.recognize_batch_scored(images, prefix=[self._text_prefix(t) for t in texts])
 
     # ------------------------------------------------------------------ shared encodings: many rows of one crop
-    def _check_shared(self) -> None:
-        no = getattr(self.engine, "NO_PREFIX", None)      # MultiGpuEngine: the workers make the plain greedy call
-        if no:
-            raise NotImplementedError(no)
-
     def score_candidates(self, img_or_path, texts) -> List[Recognition]:
         """``score_text`` for many texts of ONE crop, in the order given: every text (a ``str`` or token ids) is forced through
         EOS and scored, so ``Recognition.logprob`` is ``log p(text | crop)``.  One engine call; the crop is encoded once for
         all of its rows (include/mocr.h, "shared encodings")."""
-        self._check_scored()
-        self._check_shared()
+        self._require("SCORES")
+        self._require("PREFIX")      # MultiGpuEngine: the workers make the plain greedy call
         prefixes = [self._text_prefix(t) for t in texts]
         if not prefixes:
             return []
-        crop = to_pixels(self._open(img_or_path))
-        kw = self._decode_kw(None, None, len(prefixes), prefixes)
-        out = self.engine.recognize_images([crop], scores=True, sources=[0] * len(prefixes), **kw)
-        return self._mark_forced(self._recognitions(*out), kw.get("prefixes"))
+        return self._run(lambda: _Images([to_pixels(self._open(img_or_path))]), _SCORED, prefix=prefixes, sources=[0] * len(prefixes))
 
     @staticmethod
     def _nbest_branches(rec: Recognition, count: int) -> List[Tuple[int, int]]:
@@ -903,14 +901,14 @@ class MangaOcr:
         :meth:`recognize_beam` / :meth:`recognize_batch_beam`."""
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
             raise ValueError(f"recognize_nbest: k must be an int >= 1, instead got {k!r}")
-        self._check_alternatives()
+        self._require("ALTERNATIVES")
         if k > 1:
-            self._check_shared()
-        crops = [to_pixels(im) for im in images]
-        if not crops:
+            self._require("PREFIX")
+        src = self._pil(images)()
+        if not src.n:
             return []
-        kw = self._decode_kw(allowed, no_repeat_ngram, len(crops))
-        first = self._recognitions_alt(*self.engine.recognize_images(crops, alternatives=True, **kw))
+        kw = self._decode_kw(allowed, no_repeat_ngram, src.n)
+        first = self._recognitions_alt(*src.call(self, alternatives=True, **kw))
         results = [[r] for r in first]
         prefixes, owner = [], []
         if k > 1:
@@ -922,8 +920,7 @@ class MangaOcr:
             used = sorted(set(owner))       # a crop without a deviation (a one-token row) is not sent again
             place = {c: i for i, c in enumerate(used)}
             kw2 = {name: [vals[c] for c in owner] for name, vals in kw.items()}
-            out = self.engine.recognize_images([crops[c] for c in used], scores=True, prefixes=prefixes,
-                                               sources=[place[c] for c in owner], **kw2)
+            out = _Images([src.crops[c] for c in used]).call(self, scores=True, prefixes=prefixes, sources=[place[c] for c in owner], **kw2)
             for c, rec in zip(owner, self._mark_forced(self._recognitions(*out), prefixes)):
                 results[c].append(rec)
         ranked = []
@@ -949,33 +946,16 @@ class MangaOcr:
             raise ValueError("this MangaOcr decodes with beam search (num_beams=): allowed= / no_repeat_ngram= / prefix= do not combine with it")
         return True
 
-    def _check_beam(self) -> None:
-        no = getattr(self.engine, "NO_BEAM", None)      # MultiGpuEngine: the workers make the plain greedy call
-        if no:
-            raise NotImplementedError(no)
-
-    def _best_text(self, triple) -> str:
-        ids, lens, _ = triple
-        return ids_to_text(self.vocab, ids[0, :lens[0]]) if lens[0] > 0 else ""
-
-    def _beam_chunks(self, n: int, beam: BeamConfig):
-        step = max(1, int(self.max_batch) // beam.num_beams)         # a beam request fits one batch: n * K <= max_batch
-        return [(i, min(n, i + step)) for i in range(0, n, step)]
-
-    def _beam_images(self, crops, bgr, rotate, beam: BeamConfig):
-        """(ids [n, K, max_len], lengths [n, K], scores [n, K]) of any number of crops, max_batch // K of them per engine call"""
-        self._check_beam()
-        parts = [self.engine.recognize_images(crops[a:b], bgr, None if rotate is None else list(rotate)[a:b], beam=beam)
-                 for a, b in self._beam_chunks(len(crops), beam)]
-        if not parts:
-            parts = [self.engine.recognize_images([], beam=beam)]
-        return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
-
-    def _beam_regions(self, pages, regions, beam: BeamConfig):
-        self._check_beam()
-        parts = [self.engine.recognize_regions(pages, regions[a:b], True, beam=beam) for a, b in self._beam_chunks(len(regions), beam)]
-        if not parts:
-            parts = [self.engine.recognize_regions(pages, [], True, beam=beam)]
+    def _beam(self, src, beam: BeamConfig):
+        """(ids [n, K, max_len], lengths [n, K], scores [n, K]) of a source: one crop through the batcher, any number of crops
+        or regions max_batch // K of them per engine call (a beam request fits one batch: n * K <= max_batch)"""
+        self._require("BEAM")
+        if isinstance(src, _Single):
+            return tuple(a[None] for a in self._batcher.submit(src.pixels, beam=beam).result())
+        if not src.n and isinstance(src, _Images):
+            src = _Images([])       # no crops: the bare call, which only shapes the empty result
+        step = max(1, int(self.max_batch) // beam.num_beams)
+        parts = [src.call(self, a, a + step, beam=beam) for a in range(0, src.n, step)] or [src.call(self, beam=beam)]
         return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
 
     def _hypotheses(self, ids, lens, scores) -> List[Recognition]:
@@ -984,43 +964,35 @@ class MangaOcr:
         return [Recognition(ids_to_text(self.vocab, ids[j, :lens[j]]), np.array(ids[j, :lens[j]], dtype=np.int32), none, 0.0, 0.0,
                             sequence_score=float(scores[j])) for j in range(len(lens)) if lens[j] > 0]
 
+    def _run_beam(self, source, *config) -> List[List[Recognition]]:
+        """the ``*_beam`` methods: the configuration is checked, then the inputs; one list of hypotheses per crop or region"""
+        beam = BeamConfig(*config)
+        ids, lens, sc = self._beam(source(), beam)
+        return [self._hypotheses(ids[i], lens[i], sc[i]) for i in range(len(lens))]
+
     def recognize_beam(self, img_or_path, num_beams: int = 4, length_penalty: float = 1.0, early_stopping=False,
                        no_repeat_ngram: int = 0) -> List[Recognition]:
         """Beam search for one crop (include/mocr.h, "beam search"): what transformers' ``generate(num_beams=...,
         length_penalty=..., early_stopping=..., no_repeat_ngram_size=...)`` returns with ``num_return_sequences=num_beams`` -
         the finished hypotheses, best first, each with its ``sequence_score``.  ``num_beams`` 2 .. 4; ``early_stopping``
         False, True or "never".  Goes through the batcher; beam and greedy callers never share a batch."""
-        self._check_beam()
-        beam = BeamConfig(num_beams, length_penalty, early_stopping, no_repeat_ngram)
-        return self._hypotheses(*self._batcher.submit(to_pixels(self._open(img_or_path)), beam=beam).result())
+        self._require("BEAM")
+        return self._run_beam(self._one(img_or_path), num_beams, length_penalty, early_stopping, no_repeat_ngram)[0]
 
     def recognize_batch_beam(self, images: Sequence, num_beams: int = 4, length_penalty: float = 1.0, early_stopping=False,
                              no_repeat_ngram: int = 0) -> List[List[Recognition]]:
         """``recognize_beam`` for many crops: one list of hypotheses per crop."""
-        beam = BeamConfig(num_beams, length_penalty, early_stopping, no_repeat_ngram)
-        ids, lens, sc = self._beam_images([to_pixels(im) for im in images], False, None, beam)
-        return [self._hypotheses(ids[i], lens[i], sc[i]) for i in range(len(lens))]
+        return self._run_beam(self._pil(images), num_beams, length_penalty, early_stopping, no_repeat_ngram)
 
     def recognize_bgr_beam(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, num_beams: int = 4,
                            length_penalty: float = 1.0, early_stopping=False, no_repeat_ngram: int = 0) -> List[List[Recognition]]:
         """``recognize_bgr`` with beam search: one list of hypotheses per crop."""
-        from .queue_worker import rotation_code
-        beam = BeamConfig(num_beams, length_penalty, early_stopping, no_repeat_ngram)
-        crops = list(crops_bgr)
-        rot = None
-        if orientations is not None:
-            if len(orientations) != len(crops):
-                raise ValueError(f"recognize_bgr_beam: {len(crops)} crops but {len(orientations)} orientations")
-            rot = [rotation_code(c.shape[0], c.shape[1], o) for c, o in zip(crops, orientations)]
-        ids, lens, sc = self._beam_images(crops, True, rot, beam)
-        return [self._hypotheses(ids[i], lens[i], sc[i]) for i in range(len(lens))]
+        return self._run_beam(lambda: self._bgr("recognize_bgr_beam", crops_bgr, orientations), num_beams, length_penalty, early_stopping, no_repeat_ngram)
 
     def recognize_regions_beam(self, pages_bgr: Sequence[np.ndarray], regions, num_beams: int = 4, length_penalty: float = 1.0,
                                early_stopping=False, no_repeat_ngram: int = 0) -> List[List[Recognition]]:
         """``recognize_regions`` with beam search: one list of hypotheses per region ([] for a sliver)."""
-        beam = BeamConfig(num_beams, length_penalty, early_stopping, no_repeat_ngram)
-        ids, lens, sc = self._beam_regions(list(pages_bgr), list(regions), beam)
-        return [self._hypotheses(ids[i], lens[i], sc[i]) for i in range(len(lens))]
+        return self._run_beam(lambda: _Regions(list(pages_bgr), list(regions)), num_beams, length_penalty, early_stopping, no_repeat_ngram)
 
     def recognize_page(self, page_bgr: np.ndarray, regions):
         """``_collect_manga_detections`` for one page: ``regions`` = the detector's (text, polygon) pairs."""
