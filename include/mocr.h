@@ -734,7 +734,8 @@ int mocr_profile_get(mocr_engine* e, mocr_kernel_stat* out, int32_t cap, int32_t
  * TIES: equal accumulated scores go to the lower flat index beam * vocab + token; a new finished sequence whose score
  * equals one already in the set goes behind it.  (torch.topk promises no order, so nothing should rely on an exact tie.)
  * Beam k of crop c is decode row c K + k: a request of n crops is n K rows over n encodings (one encoder pass per crop),
- * so n * K <= max_batch.  A beam request carries no token sets, prefixes, positions, alternatives or source array. */
+ * so n * K <= max_batch.  A beam request may carry one token set per crop and ask for the hypotheses' token scores (the
+ * *_beam_tokens calls below); it carries no prefixes, positions, alternatives or source array. */
 #define MOCR_MAX_BEAMS 4
 typedef struct mocr_beam_config {
     int32_t num_beams;              /* K: 2 .. MOCR_MAX_BEAMS */
@@ -758,9 +759,44 @@ int mocr_recognize_gray_host_beam(mocr_engine* e, const uint8_t* gray, int32_t n
 int mocr_recognize_device_beam(mocr_engine* e, const void* d_gray, int32_t n, const mocr_beam_config* beam, void* d_out_ids,
                                void* d_out_len, void* d_out_score);
 
+/* Beam search with token sets and token scores: the *_beam calls plus
+ *   out_logp  [n][K][max_len] float32, laid out like out_ids (a device pointer for the device twin), nullable;
+ *   sets      HOST int32 [n], one handle of mocr_token_set_create per crop or region, nullable = all MOCR_TOKEN_SET_ALL.
+ * With both null they ARE the *_beam calls.  An unknown handle returns MOCR_ERR_ARG, like everything the *_beam calls refuse.
+ * TOKEN SETS: all K beams of a crop decode under its set.  A token outside the set scores -inf at every step, before the
+ * beam's running score is added, and combines with the n-gram bans of the beam's own history (both are -inf) - this is
+ * generate(prefix_allowed_tokens_fn = lambda b, ids: allowed), the PrefixConstrainedLogitsProcessor, with EOS a member of
+ * every set.  The log_softmax is taken over the FULL row and nothing renormalises, unlike the greedy *_constrained calls,
+ * whose softmax is taken over the set.  MOCR_TOKEN_SET_ALL for every crop is the unconstrained search, bit for bit.
+ * DEAD CANDIDATES: with a small set (or one the bans emptied) fewer than 2 K accumulated scores can be finite.  A -inf
+ * candidate never outranks a finite one and never enters the finished set (-inf < the empty slots' -1e9); among -inf
+ * candidates the lower flat index goes first; a running beam that is dead keeps score -inf, its tokens are unspecified
+ * but lie in [0, vocab).  The next running beams are the best K of (score, -1e9 on the stopped ones) by value.
+ * TOKEN SCORES of hypothesis (c, j) of length len: out_logp[c][j][0] = 0 (the start token is given); for 1 <= t < len the
+ * processed log-probability of ids[t] at the step that appended it, from the beam the hypothesis descends from at that
+ * step (compute_transition_scores(sequences, scores, beam_indices, normalize_logits = False)): the fp32 value
+ * (logit - row max) - log S the selection ranked.  EOS is scored, and so is the last token of a hypothesis that ends by
+ * length.  Positions t >= len, and every position of an empty slot (len 0) or of a sliver region, read 0.  The running score
+ * is lp + running, one fp32 add per step from 0, so the fp32 sum of out_logp[1 .. len - 1] taken in order IS the accumulated
+ * score, and out_score = that sum / (len - 1) ^ length_penalty.  Asking for token scores, or passing sets that are all
+ * MOCR_TOKEN_SET_ALL, moves no id, length or sequence score. */
+int mocr_recognize_images_beam_tokens(mocr_engine* e, const mocr_image* images, int32_t n, const mocr_beam_config* beam,
+                                      int32_t* out_ids, int32_t* out_len, float* out_score, float* out_logp, const int32_t* sets);
+int mocr_recognize_regions_beam_tokens(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                       int32_t n_regions, const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len,
+                                       float* out_score, float* out_logp, const int32_t* sets);
+int mocr_recognize_gray_host_beam_tokens(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override,
+                                         const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len, float* out_score,
+                                         float* out_logp, const int32_t* sets);
+int mocr_recognize_device_beam_tokens(mocr_engine* e, const void* d_gray, int32_t n, const mocr_beam_config* beam, void* d_out_ids,
+                                      void* d_out_len, void* d_out_score, void* d_out_logp, const int32_t* sets);
+
 /* Bytes of beam state this engine holds, over its lanes (test hook): 0 until a lane runs its first beam batch - creating an
  * engine and greedy calls of any kind allocate none of it. */
 int64_t mocr_beam_state_bytes(mocr_engine* e);
+/* ... and of the token form's two histories, which mocr_beam_state_bytes does not count: 0 until a lane runs its first beam
+ * batch that asks for token scores or brings a set other than MOCR_TOKEN_SET_ALL. */
+int64_t mocr_beam_token_state_bytes(mocr_engine* e);
 /* The first n entries of a lane's decode slot -> row map as its last batch left it (test hook; all lanes idle first): behind
  * a compacted beam batch the K rows of a crop still sit in K neighbouring slots, in beam order, from a slot that is a
  * multiple of K. */
@@ -771,6 +807,12 @@ int mocr_lane_rowmap(mocr_engine* e, int32_t lane, int32_t* out_rowmap, int32_t 
  * d_beam_score / d_parent / d_hyp_len / d_hyp_score [rows], d_hyp_ids [rows][ids_ld], d_heuristic_open [rows / K]. */
 int mocr_op_beam_select(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score,
                         int32_t* d_parent, int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open);
+/* ... in its token form: plus d_beam_logp / d_hyp_logp [rows][ids_ld] float32 (both or neither) and d_tok_mask
+ * [sets][vocab / 32] with d_set_of_row [rows] (both or neither; every entry a row of d_tok_mask, the K rows of a crop naming one set).  With all four null it is
+ * mocr_op_beam_select. */
+int mocr_op_beam_select_tokens(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score,
+                               int32_t* d_parent, int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open,
+                               float* d_beam_logp, float* d_hyp_logp, const uint32_t* d_tok_mask, const int32_t* d_set_of_row);
 /* The cache reorder behind it: d_cache viewed as [layers][rows][segs][positions][pos_bytes] through byte strides; for
  * every group of K slots whose crop is live (d_finished[rowmap[g K]] == 0), row rowmap[g K + k] <- row
  * rowmap[g K + d_parent[rowmap[g K + k]]], bytes 0 .. d_step[g K] * pos_bytes - 1 of every (layer, segment).  max_pos bounds

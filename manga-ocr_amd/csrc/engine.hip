@@ -154,6 +154,9 @@ struct LaneCtx {
     float *beam_score = nullptr, *hyp_score = nullptr;    // [Bp]
     int *beam_parent = nullptr, *hyp_len = nullptr, *heuristic_open = nullptr;      // [Bp] ([Bp / 2] used of the last)
     int* hyp_ids = nullptr;                         // [Bp][max_len]
+    // ... and its token form: allocated by the first beam batch that asks for token scores or brings a token set
+    // (ensure_beam_token_buffers); the rows' sets are set_of_row
+    float *beam_logp = nullptr, *hyp_logp = nullptr;    // [Bp][max_len]
     float *x_f32 = nullptr, *a_f32 = nullptr, *c_f32 = nullptr;
     float* ln_stats = nullptr;                      // small-batch path: (mean, rstd) per row of the three pre-LayerNorm sums, [3][Bp][2]
     void *x_t = nullptr, *a_t = nullptr, *c_t = nullptr, *ctx_t = nullptr, *h_t = nullptr, *z_t = nullptr;
@@ -218,10 +221,15 @@ struct DecMode {
     bool beam = false;              // a beam-search batch (all of its jobs, with one configuration): the steps end in the selection and
                                     // the cache reorder instead of the token kernel, the LM head always in its slab form
     mocr_beam_config beam_cfg{};
+    bool beam_tokens = false;       // ... in which a job asks for token scores or brings a token set other than MOCR_TOKEN_SET_ALL: the
+                                    // selection runs in its token form (level and mask stay 0: the LM head and the caches do not change)
     // a graph captured in one mode is never replayed in another: the mode's share of the decode-graph key (6 bits; a beam
-    // batch: bit 6, and its configuration - kernel arguments of the captured launches - in the bits above, beam_key)
-    int key_bits() const { return level + (mask ? 4 : 0) + (ngram ? 8 : 0) + (positions ? 16 : 0) + (prefix ? 32 : 0) + (beam ? 64 : 0); }
-    static constexpr int KEY_SPAN = 128;
+    // batch: bit 6, its token form: bit 7, and its configuration - kernel arguments of the captured launches - in the bits
+    // above, beam_key)
+    int key_bits() const {
+        return level + (mask ? 4 : 0) + (ngram ? 8 : 0) + (positions ? 16 : 0) + (prefix ? 32 : 0) + (beam ? 64 : 0) + (beam_tokens ? 128 : 0);
+    }
+    static constexpr int KEY_SPAN = 256;
     int epilogue() const { return mask ? (level == 2 ? EPI_TOPK_M : level == 1 ? EPI_ARGMAX_LSE_M : EPI_ARGMAX_M)
                                        : (level == 2 ? EPI_TOPK : level == 1 ? EPI_ARGMAX_LSE : EPI_ARGMAX); }
     // profile names of the fused LM head and of the token kernel
@@ -238,6 +246,13 @@ struct DecMode {
 
 static DecMode mode_of(const std::vector<Job>& jobs) {
     DecMode m;
+    // beam search: pump_once never mixes - a batch is all beam jobs of one configuration, or has none.  Its jobs' token
+    // scores and sets are the selection's business alone (the token form), not the LM head's.
+    if (!jobs.empty() && jobs.front().beam.num_beams > 0) {
+        m.beam = true; m.beam_cfg = jobs.front().beam;
+        for (const Job& j : jobs) m.beam_tokens = m.beam_tokens || j.out_logp || !j.sets.empty();
+        return m;
+    }
     for (const Job& j : jobs) {
         m.level = std::max(m.level, j.out_alt_ids ? 2 : j.out_logp ? 1 : 0);
         for (int32_t h : j.sets) m.mask = m.mask || h != MOCR_TOKEN_SET_ALL;
@@ -247,8 +262,6 @@ static DecMode mode_of(const std::vector<Job>& jobs) {
     }
     if (m.prefix) m.level = std::max(m.level, 1);      // a forced token is one more per-row fact of the masked, scored step
     m.mask = m.mask || m.ngram || m.prefix;     // the bans are applied through the rows' masks, which start as the rows' sets
-    // beam search: pump_once never mixes - a batch is all beam jobs of one configuration, or has none
-    if (!jobs.empty() && jobs.front().beam.num_beams > 0) { m.beam = true; m.beam_cfg = jobs.front().beam; }
     return m;
 }
 
@@ -1236,8 +1249,9 @@ void dec_token(mocr_engine* e, const DecState& st, int nslab, int n, int ncand =
 }
 
 // ---- beam search: the selection and the cache reorder that end a beam step (kernels_beam.h) ----
-static BeamState make_beam_state(mocr_engine* e, const mocr_beam_config& c) {
+static BeamState make_beam_state(mocr_engine* e, const mocr_beam_config& c, bool tokens) {
     BeamState bs{};
+    if (tokens) { bs.beam_logp = e->beam_logp; bs.hyp_logp = e->hyp_logp; bs.tok_mask = e->tok_table; bs.set_of_row = e->set_of_row; }
     bs.beam_score = e->beam_score; bs.parent = e->beam_parent;
     bs.hyp_ids = e->hyp_ids; bs.hyp_len = e->hyp_len; bs.hyp_score = e->hyp_score; bs.heuristic_open = e->heuristic_open;
     bs.length_penalty = c.length_penalty; bs.early_stopping = c.early_stopping; bs.ngram = c.no_repeat_ngram_size;
@@ -1250,16 +1264,23 @@ void launch_beam_select(mocr_engine* e, const DecState& st, const BeamState& bs,
     auto& w = e->w;
     if (e->D != 768 || e->V != 6144 || st.ids_ld > BEAM_HIST || st.max_len > st.ids_ld || a.nslab < 1)
         throw ArgError{"beam search needs hidden 768, vocab 6144 and max_len <= 320", MOCR_ERR_UNSUPPORTED};
-    ProfScope ps(e, "beam_select", 0, (double)n * e->V * 4 * a.nslab);
+    ProfScope ps(e, (bs.beam_logp || bs.tok_mask) ? "beam_select_tok" : "beam_select", 0, (double)n * e->V * 4 * a.nslab);
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3((n + K - 1) / K), dim3(256), 0, e->stream, a.slabs, a.nslab, a.slab_stride, a.vbias, e->V, st, bs, n,
                            w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32, reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps,
                            reinterpret_cast<T*>(a.cache), a.cstride, a.cache8, a.inv8);
     };
-    switch (K) {
-        case 2: launch(beam_select_kernel<T, 2>); break;
-        case 3: launch(beam_select_kernel<T, 3>); break;
-        case 4: launch(beam_select_kernel<T, 4>); break;
+    // the token form when the state carries any of its four arrays (make_beam_state sets them from the batch's DecMode)
+    const bool tok = bs.beam_logp || bs.hyp_logp || bs.tok_mask || bs.set_of_row;
+    if ((bs.beam_logp == nullptr) != (bs.hyp_logp == nullptr) || (bs.tok_mask == nullptr) != (bs.set_of_row == nullptr))
+        throw ArgError{"beam_select: the two token histories, and the set table with the rows' sets, come in pairs", MOCR_ERR_ARG};
+    switch (K * 2 + (tok ? 1 : 0)) {
+        case 4: launch(beam_select_kernel<T, 2>); break;
+        case 6: launch(beam_select_kernel<T, 3>); break;
+        case 8: launch(beam_select_kernel<T, 4>); break;
+        case 5: launch(beam_select_kernel<T, 2, true>); break;
+        case 7: launch(beam_select_kernel<T, 3, true>); break;
+        case 9: launch(beam_select_kernel<T, 4, true>); break;
         default: throw ArgError{"num_beams must be 2 .. 4", MOCR_ERR_ARG};
     }
     HIPCHECK(hipGetLastError());
@@ -1297,7 +1318,7 @@ void beam_finish_step(mocr_engine* e, const DecState& st, const DecMode& m, int 
     a.cache8 = (lat && e->fp8attn) ? e->x8cache : nullptr;
     a.inv8 = (lat && e->fp8attn) ? 1.0f / e->w.sx_self[0] : 0.f;
     a.cstride = (long long)e->cfg.max_len * e->D;
-    launch_beam_select<T>(e, st, make_beam_state(e, m.beam_cfg), a, n, K);
+    launch_beam_select<T>(e, st, make_beam_state(e, m.beam_cfg, m.beam_tokens), a, n, K);
     // `t` bounds the step index of this launch from above only when it is exact (eager steps).  A captured graph passes
     // t = t_hi - 1 for every step of its bucket (decode_graph), and the bucket's last device step is t_hi itself
     // (t0 + steps <= 32 * bucket): behind it `step` is t_hi + 1 = t + 2 positions.  The grid is sized for that; the kernel
@@ -2031,6 +2052,15 @@ static void ensure_beam_buffers(mocr_engine* e) {
     e->hyp_ids = e->dalloc<int>(Bp * e->cfg.max_len);
 }
 
+// The token form's two histories, for the bound lane: allocated by the first beam batch that asks for token scores or
+// brings a token set, so engines that run plain beam batches keep the footprint mocr_beam_state_bytes reports.
+static void ensure_beam_token_buffers(mocr_engine* e) {
+    if (e->hyp_logp) return;
+    const size_t Bp = (size_t)e->Bp;
+    e->beam_logp = e->dalloc<float>(Bp * e->cfg.max_len);
+    e->hyp_logp = e->dalloc<float>(Bp * e->cfg.max_len);
+}
+
 static void launch_enc_expand(mocr_engine* e, const void* in, void* out, const int* d_src_of_row, int n_src, int rows) {
     const size_t row_bytes = (size_t)e->S * e->D * e->esz;
     if (row_bytes % 16 || in == out) throw ArgError{"enc_expand: rows of whole 16-byte pieces, out of place", MOCR_ERR_UNSUPPORTED};
@@ -2151,8 +2181,14 @@ void start_batch(mocr_engine* e, Lane& L) {
     // beam search: the start token's kernel is the greedy one; the beam state starts as [0, -1e9, ...] and an empty finished set
     if (m.beam) {
         ensure_beam_buffers(e);
+        if (m.beam_tokens) {        // the crops' handles by row (c K + k: a beam job carries them expanded), padding rows under set 0
+            ensure_tok_table(e);
+            ensure_set_buffer(e);
+            ensure_beam_token_buffers(e);
+            upload_per_row(e, L, L.h_sets, &Job::sets, MOCR_TOKEN_SET_ALL, e->set_of_row);
+        }
         ProfScope ps(e, "beam_init", 0, (double)L.np * e->cfg.max_len * 4);
-        hipLaunchKernelGGL(beam_init_kernel, dim3(L.np), dim3(64), 0, e->stream, make_beam_state(e, m.beam_cfg), m.beam_cfg.num_beams, L.np,
+        hipLaunchKernelGGL(beam_init_kernel, dim3(L.np), dim3(64), 0, e->stream, make_beam_state(e, m.beam_cfg, m.beam_tokens), m.beam_cfg.num_beams, L.np,
                            e->cfg.max_len, e->cfg.pad_id);
         HIPCHECK(hipGetLastError());
     }
@@ -2172,6 +2208,8 @@ void finish_batch(mocr_engine* e, Lane& L) {
             HIPCHECK(hipMemcpyAsync(j.out_ids, e->hyp_ids + (size_t)row0 * e->cfg.max_len, (size_t)j.n * e->cfg.max_len * sizeof(int), kind, e->stream));
             HIPCHECK(hipMemcpyAsync(j.out_len, e->hyp_len + row0, (size_t)j.n * sizeof(int), kind, e->stream));
             HIPCHECK(hipMemcpyAsync(j.out_score, e->hyp_score + row0, (size_t)j.n * sizeof(float), kind, e->stream));
+            if (j.out_logp)         // (a batch with such a job ran the token form)
+                HIPCHECK(hipMemcpyAsync(j.out_logp, e->hyp_logp + (size_t)row0 * e->cfg.max_len, (size_t)j.n * e->cfg.max_len * sizeof(float), kind, e->stream));
             row0 += j.n;
             continue;
         }
@@ -3620,8 +3658,10 @@ int mocr_recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_pa
 
 // ---- beam search: the four source kinds.  A request of n crops is n K decode rows over n encodings - the shared-encodings
 // request with source[c K + k] = c - plus the configuration and the score output; the checks come before any work.
-struct BeamCall { std::vector<int32_t> source; Request req; int rows = 0; };
-static int beam_call(mocr_engine* e, const mocr_beam_config* beam, int32_t n, void* out_score, BeamCall& bc) {
+// The *_beam_tokens twins add out_logp [n][K][max_len] = [rows][max_len] and one set handle per crop, expanded to its K rows.
+struct BeamCall { std::vector<int32_t> source, sets; Request req; int rows = 0; };
+static int beam_call(mocr_engine* e, const mocr_beam_config* beam, int32_t n, void* out_score, BeamCall& bc, void* out_logp = nullptr,
+                     const int32_t* sets = nullptr) {
     return guarded(e, [&] {
         if (!beam || beam->num_beams < 2 || beam->num_beams > MOCR_MAX_BEAMS) throw ArgError{"num_beams must be 2 .. MOCR_MAX_BEAMS (4)", MOCR_ERR_ARG};
         if (beam->early_stopping < 0 || beam->early_stopping > 2) throw ArgError{"early_stopping must be 0 (false), 1 (true) or 2 (never)", MOCR_ERR_ARG};
@@ -3636,7 +3676,43 @@ static int beam_call(mocr_engine* e, const mocr_beam_config* beam, int32_t n, vo
         for (int i = 0; i < bc.rows; ++i) bc.source[i] = i / K;
         bc.req.source = bc.source.data(); bc.req.n_images = n;
         bc.req.beam = beam; bc.req.out_score = static_cast<float*>(out_score);
+        bc.req.out_logp = static_cast<float*>(out_logp);
+        if (sets) {
+            bc.sets.resize((size_t)bc.rows);
+            for (int i = 0; i < bc.rows; ++i) bc.sets[i] = sets[i / K];
+            bc.req.sets = bc.sets.data();        // (validate_request refuses an unknown handle)
+        }
     });
+}
+
+int mocr_recognize_images_beam_tokens(mocr_engine* e, const mocr_image* images, int32_t n, const mocr_beam_config* beam, int32_t* out_ids,
+                                      int32_t* out_len, float* out_score, float* out_logp, const int32_t* sets) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, out_score, bc, out_logp, sets)) return rc;
+    return recognize_images(e, images, bc.rows, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_regions_beam_tokens(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                       int32_t n_regions, const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len,
+                                       float* out_score, float* out_logp, const int32_t* sets) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n_regions, out_score, bc, out_logp, sets)) return rc;
+    return recognize_regions(e, pages, n_pages, regions, n_regions, bc.rows, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_gray_host_beam_tokens(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override,
+                                         const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len, float* out_score,
+                                         float* out_logp, const int32_t* sets) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, out_score, bc, out_logp, sets)) return rc;
+    return recognize_gray_host(e, gray, bc.rows, max_len_override, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_device_beam_tokens(mocr_engine* e, const void* d_gray, int32_t n, const mocr_beam_config* beam, void* d_out_ids,
+                                      void* d_out_len, void* d_out_score, void* d_out_logp, const int32_t* sets) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, d_out_score, bc, d_out_logp, sets)) return rc;
+    return recognize_device(e, d_gray, bc.rows, d_out_ids, d_out_len, bc.req);
 }
 
 int mocr_recognize_images_beam(mocr_engine* e, const mocr_image* images, int32_t n, const mocr_beam_config* beam, int32_t* out_ids,
@@ -4291,6 +4367,13 @@ int mocr_profile_get(mocr_engine* e, mocr_kernel_stat* out, int32_t cap, int32_t
 
 int mocr_op_beam_select(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score, int32_t* d_parent,
                         int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open) {
+    return mocr_op_beam_select_tokens(e, a, beam, d_beam_score, d_parent, d_hyp_ids, d_hyp_len, d_hyp_score, d_heuristic_open, nullptr,
+                                      nullptr, nullptr, nullptr);
+}
+
+int mocr_op_beam_select_tokens(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score,
+                               int32_t* d_parent, int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open,
+                               float* d_beam_logp, float* d_hyp_logp, const uint32_t* d_tok_mask, const int32_t* d_set_of_row) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -4312,6 +4395,7 @@ int mocr_op_beam_select(mocr_engine* e, const mocr_token_args* a, const mocr_bea
         BeamState bs{};
         bs.beam_score = d_beam_score; bs.parent = d_parent; bs.hyp_ids = d_hyp_ids; bs.hyp_len = d_hyp_len; bs.hyp_score = d_hyp_score;
         bs.heuristic_open = d_heuristic_open;
+        bs.beam_logp = d_beam_logp; bs.hyp_logp = d_hyp_logp; bs.tok_mask = d_tok_mask; bs.set_of_row = d_set_of_row;
         bs.length_penalty = beam->length_penalty; bs.early_stopping = beam->early_stopping; bs.ngram = beam->no_repeat_ngram_size;
         DecTokenArgs t{};
         t.slabs = a->slabs; t.nslab = a->nslab; t.slab_stride = (long long)a->n * e->V;
@@ -4349,6 +4433,15 @@ int64_t mocr_beam_state_bytes(mocr_engine* e) {
     int64_t bytes = 0;
     for (const Lane& L : e->lanes)
         if (L.ctx.hyp_ids) bytes += (int64_t)e->Bp * (5 + e->cfg.max_len) * 4;      // five [Bp] arrays and hyp_ids [Bp][max_len]
+    return bytes;
+}
+
+int64_t mocr_beam_token_state_bytes(mocr_engine* e) {
+    if (!e) return -1;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int64_t bytes = 0;
+    for (const Lane& L : e->lanes)
+        if (L.ctx.hyp_logp) bytes += (int64_t)e->Bp * e->cfg.max_len * 2 * 4;      // beam_logp and hyp_logp [Bp][max_len]
     return bytes;
 }
 

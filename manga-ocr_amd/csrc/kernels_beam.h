@@ -22,6 +22,11 @@ struct BeamState {
     float length_penalty;
     int early_stopping;     // 0 false, 1 true, 2 "never"
     int ngram;              // no_repeat_ngram_size, 0: off
+    // the token form of the selection (all nullable; the plain form reads none of them)
+    float* beam_logp;       // [rows][ids_ld] the running beam's token log-probabilities, by row like ids: [0] = 0 (the start token)
+    float* hyp_logp;        // [rows][ids_ld] those of the finished hypotheses, 0 behind their length: moves as hyp_ids does
+    const unsigned* tok_mask;   // [sets][V / 32] the engine's token-set bit table ...
+    const int* set_of_row;      // [rows] ... and the set of every row (the K rows of a crop name the same one)
 };
 
 // Start of a beam batch, one block of 64 threads per row: running scores [0, -1e9, ...], an empty finished set.
@@ -29,6 +34,10 @@ __global__ __launch_bounds__(64) void beam_init_kernel(BeamState bs, int K, int 
     const int r = blockIdx.x;
     if (r >= rows) return;
     for (int i = threadIdx.x; i < ids_ld; i += 64) bs.hyp_ids[(size_t)r * ids_ld + i] = pad_id;
+    if (bs.beam_logp)
+        for (int i = threadIdx.x; i < ids_ld; i += 64) bs.beam_logp[(size_t)r * ids_ld + i] = 0.f;
+    if (bs.hyp_logp)
+        for (int i = threadIdx.x; i < ids_ld; i += 64) bs.hyp_logp[(size_t)r * ids_ld + i] = 0.f;
     if (threadIdx.x == 0) {
         bs.beam_score[r] = (r % K == 0) ? 0.f : -BEAM_NEG;
         bs.parent[r] = r % K;
@@ -52,7 +61,22 @@ __global__ __launch_bounds__(64) void beam_init_kernel(BeamState bs, int K, int 
 // The two -1e9 guards of _update_finished_beams ("beams full and early_stopping", "heuristic satisfied") hold exactly when
 // the crop's own end condition holds, and a crop that ended is frozen: its block only advances `step`, like the block of
 // a trailing partial group of padding slots.  (The guards are applied all the same, for states given through the hook.)
-template <typename T, int K>
+//
+// TOK, the token form (token sets and token scores; the plain form is the code above and compiles to what it was):
+//   s_mask starts from the crop's row of the token-set table instead of all-ones and then takes the bans; it is applied at
+//     every step.  A token outside the set is -inf exactly like a banned one - log_softmax over the full row first, no
+//     renormalising (transformers' PrefixConstrainedLogitsProcessor), NOT the greedy sets' renormalised softmax;
+//   max and log S of every beam stay in LDS, and behind thread 0's section 2 K lanes recompute lp = (v - max) - log S of the
+//     2 K winners from (parent, token), one winner each: v = bias + slab 0 + ... + slab nslab - 1 in the order of the row pass,
+//     so it is the very fp32 value the selection ranked, and running' = lp + running holds exactly (score - running would
+//     round differently);
+//   beam_logp travels with ids (through s_lhist), hyp_logp with hyp_ids (through s_lhyp);
+//   with fewer than 2 K finite scores a winner can be dead (-inf): it never enters the finished set (-inf < -1e9), and the
+//     next running beams are the best K of (score, -1e9 on the stopped ones) by value, the earlier candidate first among
+//     equals - the plain form's "those that did not stop, then the stopped ones" whenever no candidate is dead.
+// LDS, static, at K = 4: ids and hypotheses 2 x 5 KiB, their log-probabilities 2 x 5 KiB (token form only), the mask 768 B,
+// under 1 KiB of lists - 21.5 KiB of the 64 KiB a block may declare.
+template <typename T, int K, bool TOK = false>
 __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restrict__ slabs, int nslab, long long slab_stride,
                                                           const float* __restrict__ vbias, int V, DecState st, BeamState bs, int np,
                                                           const float* __restrict__ word, const float* __restrict__ type0,
@@ -72,6 +96,13 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
     __shared__ int s_hsrc[K], s_hlen[K];              // finished slot j <- (>= 0: old slot, < 0: candidate -1 - i), its length
     __shared__ int s_ctok[C2], s_cpar[C2];
     __shared__ int s_new, s_done;
+    constexpr int KT = TOK ? K : 1, HT = TOK ? BEAM_HIST : 1;
+    __shared__ float s_lhist[KT][HT];
+    __shared__ float s_lhyp[KT][HT];
+    __shared__ float s_gmax[K], s_logS[K], s_clp[C2];
+    __shared__ int s_clive[C2], s_nsrc[K];            // the candidate is not dead; the candidate new beam k was made from
+    static_assert(sizeof(s_hist) + sizeof(s_hyp) + sizeof(s_lhist) + sizeof(s_lhyp) + sizeof(s_mask) + 1024 <= 65536,
+                  "static LDS of the selection: the histories, the mask and under 1 KiB of lists");
     const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int slot0 = g * K;
     if (slot0 + K > np) {                             // a trailing partial group: padding slots, born finished
@@ -92,8 +123,19 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
 #pragma unroll
     for (int k = 0; k < K; ++k)
         for (int i = tid; i < L; i += 256) s_hist[k][i] = st.ids[(size_t)s_row[k] * st.ids_ld + i];
+    if constexpr (TOK) {
+        if (bs.beam_logp) {
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+                for (int i = tid; i < L; i += 256) s_lhist[k][i] = bs.beam_logp[(size_t)s_row[k] * st.ids_ld + i];
+        }
+    }
     __syncthreads();
 
+    unsigned setw = 0xffffffffu;                      // this thread's word of the crop's set (its K rows name one set): read once
+    if constexpr (TOK) {
+        if (bs.tok_mask && tid < MW) setw = bs.tok_mask[(size_t)bs.set_of_row[row0] * MW + tid];
+    }
     TopN<C2> top;
     topn_clear(top);
     const int n = bs.ngram;
@@ -115,7 +157,11 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
         for (int j = 0; j < NC; ++j) mx = fmaxf(fmaxf(mx, fmaxf(a[j].x, a[j].y)), fmaxf(a[j].z, a[j].w));
         mx = wave_max(mx);
         if (lane == 0) s_red[wave] = mx;
-        if (n > 0 && tid < MW) s_mask[tid] = 0xffffffffu;
+        if constexpr (TOK) {
+            if (tid < MW) s_mask[tid] = setw;
+        } else {
+            if (n > 0 && tid < MW) s_mask[tid] = 0xffffffffu;
+        }
         __syncthreads();
         const float gmax = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
         __syncthreads();
@@ -138,10 +184,13 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
         __syncthreads();
         const float logS = logf((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
         const float bsc = bs.beam_score[s_row[k]];
+        if constexpr (TOK) {
+            if (tid == 0) { s_gmax[k] = gmax; s_logS[k] = logS; }
+        }
 #pragma unroll
         for (int j = 0; j < NC; ++j) {
             const int c = tid * 4 + j * 1024;
-            const unsigned nib = n > 0 ? (s_mask[c >> 5] >> (c & 31)) & 15u : 15u;
+            const unsigned nib = (TOK || n > 0) ? (s_mask[c >> 5] >> (c & 31)) & 15u : 15u;
             const float v[4] = {a[j].x, a[j].y, a[j].z, a[j].w};
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -176,20 +225,43 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
             stop[i] = ctok[i] == st.eos_id || stop_len;
             all_stop = all_stop && stop[i];
             s_ctok[i] = ctok[i]; s_cpar[i] = cpar[i];
+            if constexpr (TOK) s_clive[i] = ok && cv[i] > -INFINITY;      // (a dead candidate: masked, or the child of a dead beam)
         }
         // the running beams of the next step: the best K candidates after -1e9 on those that stopped = the ones that did
         // not stop, in order, then (only when fewer than K are left: the crop ends) the stopped ones
         float rsc[K];
-        int nr = 0;
+        if constexpr (TOK) {
+            // (by value: a dead candidate that did not stop ranks behind a stopped one's score - 1e9)
+            float adj[C2];
+            bool used[C2];
 #pragma unroll
-        for (int pass = 0; pass < 2; ++pass)
+            for (int i = 0; i < C2; ++i) { adj[i] = stop[i] ? cv[i] - BEAM_NEG : cv[i]; used[i] = false; }
 #pragma unroll
-            for (int i = 0; i < C2; ++i)
-                if (nr < K && stop[i] == (pass == 1)) {
-                    rsc[nr] = pass ? cv[i] - BEAM_NEG : cv[i];
-                    s_ntok[nr] = ctok[i]; s_npar[nr] = cpar[i];
-                    ++nr;
+            for (int k = 0; k < K; ++k) {             // (constant indices only: the lists stay in registers)
+                int b = -1, bt = 0, bp = 0;
+                float bv = 0.f;
+#pragma unroll
+                for (int i = 0; i < C2; ++i) {
+                    const bool take = !used[i] && (b < 0 || adj[i] > bv);
+                    b = take ? i : b; bv = take ? adj[i] : bv; bt = take ? ctok[i] : bt; bp = take ? cpar[i] : bp;
                 }
+#pragma unroll
+                for (int i = 0; i < C2; ++i) used[i] = used[i] || i == b;
+                rsc[k] = bv;
+                s_ntok[k] = bt; s_npar[k] = bp; s_nsrc[k] = b;
+            }
+        } else {
+            int nr = 0;
+#pragma unroll
+            for (int pass = 0; pass < 2; ++pass)
+#pragma unroll
+                for (int i = 0; i < C2; ++i)
+                    if (nr < K && stop[i] == (pass == 1)) {
+                        rsc[nr] = pass ? cv[i] - BEAM_NEG : cv[i];
+                        s_ntok[nr] = ctok[i]; s_npar[nr] = cpar[i];
+                        ++nr;
+                    }
+        }
         // the finished set: its K entries (sorted) merged with the stopped candidates among the first K
         const float div = powf((float)L, bs.length_penalty);            // (cur_len + 1 - prompt) ^ length_penalty, L tokens generated
         float hs[K], ns[K];
@@ -232,10 +304,32 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
         s_new = any_new; s_done = done ? 1 : 0;
     }
     __syncthreads();
+    if constexpr (TOK) {
+        // the winners' log-probabilities, one lane each (no decision above needed them): the row pass's own sums, in its order
+        if (tid < C2) {
+            float lp = -INFINITY;
+            if (s_clive[tid]) {
+                const int p = s_cpar[tid], c = s_ctok[tid];
+                float v = vbias[c];
+                for (int s = 0; s < nslab; ++s) v += slabs[(size_t)s * slab_stride + (size_t)(slot0 + p) * V + c];
+                lp = (v - s_gmax[p]) - s_logS[p];
+            }
+            s_clp[tid] = lp;
+        }
+        __syncthreads();
+    }
     if (s_new) {                                      // block-uniform: the old hypotheses to LDS, then every slot from its source
 #pragma unroll
         for (int j = 0; j < K; ++j)
             for (int i = tid; i < s_hlen[j]; i += 256) s_hyp[s_hsrc[j] >= 0 ? s_hsrc[j] : 0][i] = bs.hyp_ids[(size_t)(crop * K + s_hsrc[j]) * st.ids_ld + i];
+        if constexpr (TOK) {
+            if (bs.hyp_logp) {
+#pragma unroll
+                for (int j = 0; j < K; ++j)
+                    for (int i = tid; i < s_hlen[j]; i += 256)
+                        s_lhyp[s_hsrc[j] >= 0 ? s_hsrc[j] : 0][i] = bs.hyp_logp[(size_t)(crop * K + s_hsrc[j]) * st.ids_ld + i];
+            }
+        }
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < K; ++j) {
@@ -249,6 +343,22 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
                 for (int i = tid; i < st.ids_ld; i += 256) dst[i] = i < L ? s_hist[s_cpar[ci]][i] : i == L ? s_ctok[ci] : st.pad_id;
             }
         }
+        if constexpr (TOK) {
+            if (bs.hyp_logp) {
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    float* dst = bs.hyp_logp + (size_t)(crop * K + j) * st.ids_ld;
+                    const int src = s_hsrc[j];
+                    if (src == j) continue;
+                    if (src >= 0) {
+                        for (int i = tid; i < st.ids_ld; i += 256) dst[i] = i < s_hlen[j] ? s_lhyp[src][i] : 0.f;
+                    } else {
+                        const int ci = -1 - src;
+                        for (int i = tid; i < st.ids_ld; i += 256) dst[i] = i < L ? s_lhist[s_cpar[ci]][i] : i == L ? s_clp[ci] : 0.f;
+                    }
+                }
+            }
+        }
     }
     if (s_done) return;                               // block-uniform
     // the new beams' rows: the parent's history plus the token
@@ -259,6 +369,18 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
         if (p != k)
             for (int i = tid; i < L; i += 256) dst[i] = s_hist[p][i];
         if (tid == 0 && L < st.ids_ld) dst[L] = s_ntok[k];
+    }
+    if constexpr (TOK) {
+        if (bs.beam_logp) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                float* dst = bs.beam_logp + (size_t)s_row[k] * st.ids_ld;
+                const int p = s_npar[k];
+                if (p != k)
+                    for (int i = tid; i < L; i += 256) dst[i] = s_lhist[p][i];
+                if (tid == 0 && L < st.ids_ld) dst[L] = s_clp[s_nsrc[k]];
+            }
+        }
     }
     // embedding + LayerNorm of every new beam's next input (the tail of dec_token_kernel)
     constexpr int PER = D / 256;

@@ -223,6 +223,7 @@ class Recognition:
     n_forced: int = 0       # ``prefix=``: how many of ids[1:] the caller gave (their logprobs score the caller's tokens)
     # the ``*_beam`` methods: the hypothesis' beam-search score, sum of its token log-probabilities / (tokens generated) **
     # length_penalty (transformers' ``sequences_scores``); such a Recognition carries no per-token logprobs (confidence 0.0)
+    # unless the call asked with ``token_scores=True``
     sequence_score: Optional[float] = None
     _vocab: object = field(default=None, repr=False, compare=False)      # what candidates() names the tokens with
 
@@ -279,6 +280,11 @@ class Recognition:
         return b
 
     @property
+    def token_logp(self) -> np.ndarray:
+        """``logprobs`` in the engine's row form: float32 ``[len]``, one value per id, 0 for the start token."""
+        return np.concatenate([np.zeros(min(1, len(self.ids)), dtype=np.float32), np.asarray(self.logprobs, dtype=np.float32)])
+
+    @property
     def logprob(self) -> float:
         """The natural-log probability of the whole row, ``sum(logprobs)`` in float64: for a ``score_text`` result
         ``log p(text | crop)``."""
@@ -327,6 +333,8 @@ class _Request(NamedTuple):
     ngram: int              # no-repeat n-gram size, 0: off
     prefix: Optional[tuple] = None      # forced prefix (token ids), None: none
     beam: Optional[BeamConfig] = None   # beam search with this configuration, None: greedy
+    beam_scores: bool = False           # a beam request: wants its hypotheses' token log-probabilities
+    beam_set: int = 0                   # a beam request: the token set its beams search under, 0: unconstrained
 
 
 class _Batcher:
@@ -343,7 +351,9 @@ class _Batcher:
     request passes ``prefixes=``, one per crop, None for the others.  Beam search (``beam=``) is a call of its own: a batch
     is the run of queued requests that share the head's beam configuration (None for the greedy ones), so beam and greedy
     submissions are never merged, and a beam batch holds at most ``max_batch // num_beams`` crops; such a caller gets
-    (ids [K, max_len], lengths [K], scores [K])."""
+    (ids [K, max_len], lengths [K], scores [K]).  A beam request may ask for its token scores (``beam_scores``) and carry a
+    token set (``beam_set``): only a beam batch with such a request passes ``beam_scores=True`` / ``beam_sets=`` (one handle per
+    crop, 0 for the others), and only a caller that asked gets logp [K, max_len] as a fourth element."""
 
     def __init__(self, engine: Engine, max_batch: int, timeout_ms: float):
         self.engine, self.max_batch, self.timeout = engine, max_batch, timeout_ms / 1000.0
@@ -354,13 +364,14 @@ class _Batcher:
         self._thread.start()
 
     def submit(self, gray: np.ndarray, scored: bool = False, alternatives: bool = False, token_set: int = 0,
-               no_repeat_ngram: int = 0, positions: bool = False, prefix=None, beam: Optional[BeamConfig] = None) -> Future:
+               no_repeat_ngram: int = 0, positions: bool = False, prefix=None, beam: Optional[BeamConfig] = None,
+               beam_scores: bool = False, beam_set: int = 0) -> Future:
         f: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
             self._q.append(_Request(gray, f, bool(scored or alternatives), bool(alternatives), bool(positions), int(token_set), int(no_repeat_ngram),
-                                    tuple(prefix) if prefix else None, beam))
+                                    tuple(prefix) if prefix else None, beam, bool(beam_scores), int(beam_set)))
             self._cv.notify()
         return f
 
@@ -385,9 +396,14 @@ class _Batcher:
                 batch, self._q = self._q[:take], self._q[take:]
             try:
                 if head is not None:
-                    ids, lens, sc = self.engine.recognize_images([r.gray for r in batch], beam=head)
+                    bkw = {}        # only what somebody asked for: a batch of plain beam requests makes the plain beam call
+                    if any(r.beam_scores for r in batch):
+                        bkw["beam_scores"] = True
+                    if any(r.beam_set for r in batch):
+                        bkw["beam_sets"] = [r.beam_set for r in batch]
+                    ids, lens, sc, *logp = self.engine.recognize_images([r.gray for r in batch], beam=head, **bkw)
                     for i, r in enumerate(batch):
-                        r.future.set_result((ids[i].copy(), lens[i].copy(), sc[i].copy()))
+                        r.future.set_result((ids[i].copy(), lens[i].copy(), sc[i].copy()) + ((logp[0][i].copy(),) if r.beam_scores else ()))
                     continue
                 kw = {}         # only what somebody asked for: a batch of plain requests makes the plain call
                 if any(r.scored for r in batch):        # the richest call any request asked for
@@ -519,8 +535,9 @@ class MangaOcr:
         leave ``ignored_generation_config``; an int in 2 .. 4 = the same with that many beams.  The loader's warning about
         ignored generation settings is then given only for what is still ignored.  The scored, alternatives, positions and
         n-best methods (``recognize_scored``, ``recognize_alternatives``, ``recognize_positions``, ``recognize_nbest`` and
-        their batch forms, ``score_text``) keep decoding greedily: a beam hypothesis carries no per-token outputs; use
-        ``recognize_beam`` for all hypotheses with their scores."""
+        their batch forms, ``score_text``) keep decoding greedily: they return one greedy row per crop, with its alternatives,
+        positions or prefix; use ``recognize_beam`` for all hypotheses with their sequence scores - and, with
+        ``token_scores=True`` / ``allowed=``, their token log-probabilities and a search under a token set."""
         if force_cpu:
             raise RuntimeError("this MangaOcr is the MI355X engine: there is no CPU path (force_cpu=True is not supported)")
         dtype = dtype or os.environ.get("MANGA_OCR_DTYPE", "bf16")
@@ -946,53 +963,75 @@ class MangaOcr:
             raise ValueError("this MangaOcr decodes with beam search (num_beams=): allowed= / no_repeat_ngram= / prefix= do not combine with it")
         return True
 
-    def _beam(self, src, beam: BeamConfig):
+    def _beam(self, src, beam: BeamConfig, token_scores: bool = False, allowed=None):
         """(ids [n, K, max_len], lengths [n, K], scores [n, K]) of a source: one crop through the batcher, any number of crops
-        or regions max_batch // K of them per engine call (a beam request fits one batch: n * K <= max_batch)"""
+        or regions max_batch // K of them per engine call (a beam request fits one batch: n * K <= max_batch).  With
+        ``token_scores`` also logp [n, K, max_len]; ``allowed``: the crops' token sets.  The engine is passed only what was asked."""
         self._require("BEAM")
+        hs = _set_handles(allowed, src.n)
+        if hs is not None:
+            self._require("CONSTRAINTS")
         if isinstance(src, _Single):
-            return tuple(a[None] for a in self._batcher.submit(src.pixels, beam=beam).result())
+            kw = dict(beam_scores=True) if token_scores else {}
+            if hs is not None:
+                kw["beam_set"] = hs[0]
+            return tuple(a[None] for a in self._batcher.submit(src.pixels, beam=beam, **kw).result())
         if not src.n and isinstance(src, _Images):
             src = _Images([])       # no crops: the bare call, which only shapes the empty result
         step = max(1, int(self.max_batch) // beam.num_beams)
-        parts = [src.call(self, a, a + step, beam=beam) for a in range(0, src.n, step)] or [src.call(self, beam=beam)]
-        return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
+        kw = lambda a: dict(**(dict(beam_scores=True) if token_scores else {}), **(dict(beam_sets=hs[a:a + step]) if hs is not None else {}))
+        parts = [src.call(self, a, a + step, beam=beam, **kw(a)) for a in range(0, src.n, step)] or [src.call(self, beam=beam, **kw(0))]
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(4 if token_scores else 3))
 
-    def _hypotheses(self, ids, lens, scores) -> List[Recognition]:
-        """one crop's [K, max_len] / [K] / [K] -> its finished hypotheses, best first (empty slots dropped)"""
+    def _hypotheses(self, ids, lens, scores, logp=None) -> List[Recognition]:
+        """one crop's [K, max_len] / [K] / [K] (/ [K, max_len]) -> its finished hypotheses, best first (empty slots dropped);
+        with ``logp`` they carry their token log-probabilities and the confidence of a greedy row (Recognition.from_row)"""
         none = np.zeros(0, dtype=np.float32)
+        if logp is not None:
+            return [replace(Recognition.from_row(self.vocab, ids[j], logp[j], lens[j]), sequence_score=float(scores[j]))
+                    for j in range(len(lens)) if lens[j] > 0]
         return [Recognition(ids_to_text(self.vocab, ids[j, :lens[j]]), np.array(ids[j, :lens[j]], dtype=np.int32), none, 0.0, 0.0,
                             sequence_score=float(scores[j])) for j in range(len(lens)) if lens[j] > 0]
 
-    def _run_beam(self, source, *config) -> List[List[Recognition]]:
+    def _run_beam(self, source, *config, token_scores: bool = False, allowed=None) -> List[List[Recognition]]:
         """the ``*_beam`` methods: the configuration is checked, then the inputs; one list of hypotheses per crop or region"""
         beam = BeamConfig(*config)
-        ids, lens, sc = self._beam(source(), beam)
-        return [self._hypotheses(ids[i], lens[i], sc[i]) for i in range(len(lens))]
+        ids, lens, sc, *logp = self._beam(source(), beam, bool(token_scores), allowed)
+        return [self._hypotheses(ids[i], lens[i], sc[i], logp[0][i] if logp else None) for i in range(len(lens))]
 
     def recognize_beam(self, img_or_path, num_beams: int = 4, length_penalty: float = 1.0, early_stopping=False,
-                       no_repeat_ngram: int = 0) -> List[Recognition]:
+                       no_repeat_ngram: int = 0, *, token_scores: bool = False, allowed=None) -> List[Recognition]:
         """Beam search for one crop (include/mocr.h, "beam search"): what transformers' ``generate(num_beams=...,
         length_penalty=..., early_stopping=..., no_repeat_ngram_size=...)`` returns with ``num_return_sequences=num_beams`` -
         the finished hypotheses, best first, each with its ``sequence_score``.  ``num_beams`` 2 .. 4; ``early_stopping``
-        False, True or "never".  Goes through the batcher; beam and greedy callers never share a batch."""
+        False, True or "never".  Goes through the batcher; beam and greedy callers never share a batch.
+        ``token_scores=True``: every hypothesis also carries ``logprobs`` (one per token behind the start token: the
+        log-probability the search gave it, EOS included), ``confidence`` and ``min_prob`` as a greedy scored row does.
+        ``allowed``: a :class:`TokenSet` - the search runs under it: a token outside scores -inf at every step, WITHOUT the
+        renormalising of the greedy ``allowed=`` (transformers' ``prefix_allowed_tokens_fn``; include/mocr.h)."""
         self._require("BEAM")
-        return self._run_beam(self._one(img_or_path), num_beams, length_penalty, early_stopping, no_repeat_ngram)[0]
+        return self._run_beam(self._one(img_or_path), num_beams, length_penalty, early_stopping, no_repeat_ngram, token_scores=token_scores,
+                              allowed=allowed)[0]
 
     def recognize_batch_beam(self, images: Sequence, num_beams: int = 4, length_penalty: float = 1.0, early_stopping=False,
-                             no_repeat_ngram: int = 0) -> List[List[Recognition]]:
-        """``recognize_beam`` for many crops: one list of hypotheses per crop."""
-        return self._run_beam(self._pil(images), num_beams, length_penalty, early_stopping, no_repeat_ngram)
+                             no_repeat_ngram: int = 0, *, token_scores: bool = False, allowed=None) -> List[List[Recognition]]:
+        """``recognize_beam`` for many crops: one list of hypotheses per crop (``allowed``: one set for all, or one per crop)."""
+        return self._run_beam(self._pil(images), num_beams, length_penalty, early_stopping, no_repeat_ngram, token_scores=token_scores, allowed=allowed)
 
     def recognize_bgr_beam(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, num_beams: int = 4,
-                           length_penalty: float = 1.0, early_stopping=False, no_repeat_ngram: int = 0) -> List[List[Recognition]]:
-        """``recognize_bgr`` with beam search: one list of hypotheses per crop."""
-        return self._run_beam(lambda: self._bgr("recognize_bgr_beam", crops_bgr, orientations), num_beams, length_penalty, early_stopping, no_repeat_ngram)
+                           length_penalty: float = 1.0, early_stopping=False, no_repeat_ngram: int = 0, *, token_scores: bool = False,
+                           allowed=None) -> List[List[Recognition]]:
+        """``recognize_bgr`` with beam search: one list of hypotheses per crop (``token_scores`` / ``allowed``: see recognize_beam)."""
+        return self._run_beam(lambda: self._bgr("recognize_bgr_beam", crops_bgr, orientations), num_beams, length_penalty, early_stopping, no_repeat_ngram,
+                              token_scores=token_scores, allowed=allowed)
 
     def recognize_regions_beam(self, pages_bgr: Sequence[np.ndarray], regions, num_beams: int = 4, length_penalty: float = 1.0,
-                               early_stopping=False, no_repeat_ngram: int = 0) -> List[List[Recognition]]:
-        """``recognize_regions`` with beam search: one list of hypotheses per region ([] for a sliver)."""
-        return self._run_beam(lambda: _Regions(list(pages_bgr), list(regions)), num_beams, length_penalty, early_stopping, no_repeat_ngram)
+                               early_stopping=False, no_repeat_ngram: int = 0, *, token_scores: bool = False,
+                               allowed=None) -> List[List[Recognition]]:
+        """``recognize_regions`` with beam search: one list of hypotheses per region ([] for a sliver; ``token_scores`` /
+        ``allowed``: see recognize_beam, one set per region)."""
+        return self._run_beam(lambda: _Regions(list(pages_bgr), list(regions)), num_beams, length_penalty, early_stopping, no_repeat_ngram,
+                              token_scores=token_scores, allowed=allowed)
 
     def recognize_page(self, page_bgr: np.ndarray, regions):
         """``_collect_manga_detections`` for one page: ``regions`` = the detector's (text, polygon) pairs."""

@@ -4,6 +4,10 @@
   (ii)  the same 64 crops as 256 greedy scored rows through ``sources=`` - the same encoder pass, the same number of decode
         rows, no selection and no cache reorder: (i) / (ii) is the price of those two,
   (iii) plain greedy, 64 rows,
+  (iv)  the beam batch of (i) with token scores (``beam_scores=True``) and (v) with token scores under a set of 40 tokens
+        (``beam_sets=``): the token form of the selection (include/mocr.h "beam search with token sets and token scores");
+        (iv) / (i) is its price - a build without it (the parent commit) runs (i) - (iii) alone, and (i) must agree between
+        the two builds within its run-to-run spread (best-of-N, the ``spread_ms`` minimum, is the figure to compare),
 and, with --profile, the two new kernels' times from the engine's per-kernel profile at 400 rows.
 
     python tools/beam_cost.py [--tree DIR] [--label NAME] [--crops 64] [--beams 4] [--max-len 32] [--reps 7] [--profile]
@@ -48,6 +52,10 @@ def main():
     if beam is not None:
         cfg = beam(K, 2.0, True, 3)
         forms.insert(0, ("beam", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg)))
+        if hasattr(eng, "beam_token_state_bytes"):      # (the parent commit has no token form)
+            some = eng.token_set(np.random.RandomState(40).choice(np.arange(5, DEFAULT_SPEC.vocab), 40, replace=False).tolist())
+            forms.append(("beam_token_scores", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg, beam_scores=True)))
+            forms.append(("beam_token_scores_set40", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg, beam_scores=True, beam_sets=some)))
     for form, call in forms:
         for _ in range(2):
             call()
@@ -63,15 +71,18 @@ def main():
         n = 400 // K
         eng = me.Engine(w, DEFAULT_SPEC, dtype="bf16", device=0, max_batch=n * K, lanes=1)
         g = np.random.RandomState(7).randint(0, 256, size=(n, 224, 224), dtype=np.uint8)
-        eng.recognize_gray(g, args.max_len, beam=cfg)
-        eng.profile_enable(True)
-        eng.profile_reset()
-        eng.recognize_gray(g, args.max_len, beam=cfg)
-        for s in eng.profile_get():
-            if s["name"] in ("beam_select", "beam_permute", "beam_init", "dec_attn_self", "latent_self", "gemm_dec_vocab"):
-                print(json.dumps(dict(what="beam_kernels", build=args.label, rows=n * K, max_len=args.max_len, kernel=s["name"],
-                                      launches=s["launches"], total_ms=round(s["total_ms"], 3),
-                                      us_per_launch=round(1e3 * s["total_ms"] / max(s["launches"], 1), 2))), flush=True)
+        kws = [{}] + ([dict(beam_scores=True)] if hasattr(eng, "beam_token_state_bytes") else [])
+        for kw in kws:
+            eng.recognize_gray(g, args.max_len, beam=cfg, **kw)
+            eng.profile_enable(True)
+            eng.profile_reset()
+            eng.recognize_gray(g, args.max_len, beam=cfg, **kw)
+            for s in eng.profile_get():
+                if s["name"] in ("beam_select", "beam_select_tok", "beam_permute", "beam_init", "dec_attn_self", "latent_self", "gemm_dec_vocab"):
+                    print(json.dumps(dict(what="beam_kernels", build=args.label, rows=n * K, max_len=args.max_len, kernel=s["name"],
+                                          launches=s["launches"], total_ms=round(s["total_ms"], 3),
+                                          us_per_launch=round(1e3 * s["total_ms"] / max(s["launches"], 1), 2))), flush=True)
+            eng.profile_enable(False)
         eng.close()
 
 
