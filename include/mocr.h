@@ -467,6 +467,20 @@ int mocr_op_gemm_ln(mocr_engine* e, const void* dA, const void* dW, const float*
                     float* d_part, const float* d_csum, void* d_xb);
 int mocr_op_ln_prep(mocr_engine* e, const float* d_x, void* d_xb, float* d_part, int32_t M);
 int mocr_op_enc_attention(mocr_engine* e, const void* d_qkv, void* d_ctx, int32_t n, int32_t impl);
+/* The encoder's front end, launched as the encoder launches it: d_gray uint8 [n,224,224] -> d_patches [round_up(n*196, 128), 256]
+ * of the engine's dtype (rows n*196 .. are left alone) -> d_x float32 [n*197, 768]: row b*197 = cls + pos[0], row b*197 + 1 + p =
+ * patch p of crop b times the channel-summed patch weight + bias + pos[1 + p].  tile: the patch embedding's GEMM tile, 64 or 128;
+ * 0 = the encoder's own choice for n crops (mocr_encoder_plan).  n <= max_batch. */
+int mocr_op_embed(mocr_engine* e, const void* d_gray, int32_t n, int32_t tile, void* d_patches, float* d_x);
+/* What finishes an encoder GEMM split over K: d_x [M,768] float32 += d_bias + the nslab slabs d_slabs + k * slab_stride (floats,
+ * a multiple of 4, >= M * 768), summed in the order k = 0, 1, ..., in place; d_out [M,768] of the engine's dtype = LayerNorm(d_x). */
+int mocr_op_layernorm_slab(mocr_engine* e, float* d_x, const float* d_slabs, int32_t nslab, int64_t slab_stride,
+                           const float* d_bias, const float* d_gamma, const float* d_beta, void* d_out, int32_t M);
+/* What the encoder decides from the number of crops n <= max_batch (test hook; the decisions also depend on the engine's dtype,
+ * flags, compute units and max_batch): out = { patch-embedding tile, tile codes of QKV / O-proj / FC1 / FC2 (64, 128, 4096),
+ * K slices of O-proj, K slices of FC2 (1 = not split; the LayerNorm behind a split GEMM adds that many slabs), 1 if the
+ * LayerNorms are folded into the GEMMs, blocks per (crop, head) of the attention, attention kernel (0 VALU, 1 matrix cores) }. */
+int mocr_encoder_plan(mocr_engine* e, int32_t n, int32_t out[10]);
 /* Latent decode attention (bf16 engines): d_qt [n,16,768], keys d_x with x_batch_stride elements between
  * sequences, context length len for every row; d_out [n,16,768] = softmax(qt . x^T) x per head. */
 int mocr_op_latent_attention(mocr_engine* e, const void* d_qt, const void* d_x, void* d_out, int32_t n, int32_t len,

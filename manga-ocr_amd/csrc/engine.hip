@@ -857,17 +857,24 @@ template <typename T, typename F> void for_each_enc_attn(F&& f) {
 #endif
 }
 
+// Blocks per (image, head) of the encoder attention of n crops: only enc_attn2_kernel (bf16, impl 1) shares a head among blocks.
+// A few crops: two / four blocks per (image, head) share its thirteen 16-query units while n * H blocks would leave most of
+// the chip idle (three blocks fit a CU).  On 256 CUs: up to 10 crops four blocks, 11 .. 21 two, from 22 one.
 template <typename T>
-void enc_attention(mocr_engine* e, const void* qkv, void* ctx, int n, int impl) {
+int enc_attn_ysplit(const mocr_engine* e, int n, int impl) {
+    if (impl != 1 || sizeof(T) != 2) return 1;
+    const long long blocks = (long long)n * e->H;
+    return blocks * 4 <= 2LL * e->num_cus ? 4 : blocks * 2 <= 2LL * e->num_cus ? 2 : 1;
+}
+
+// (ysplit: enc_attn_ysplit's answer - the encoder passes its plan's)
+template <typename T>
+void enc_attention(mocr_engine* e, const void* qkv, void* ctx, int n, int impl, int ysplit) {
     const int S = e->S, H = e->H;
     const double flops = 4.0 * n * H * (double)S * S * 64;
     const double bytes = (double)n * S * e->D * 4 * sizeof(T);
     if (impl == 1 && sizeof(T) == 2) {
         ProfScope ps(e, "enc_attn_mfma", flops, bytes);
-        // a few crops: two / four blocks per (image, head) share its thirteen 16-query units while n * H blocks would leave
-        // most of the chip idle (three blocks fit a CU)
-        const long long blocks = (long long)n * H;
-        const int ysplit = blocks * 4 <= 2LL * e->num_cus ? 4 : blocks * 2 <= 2LL * e->num_cus ? 2 : 1;
         static const int ablate2_env = env_int("MOCR_ENC_ATTN_ABLATE", 0);
         hipLaunchKernelGGL(enc_attn2_kernel, dim3(n * H, ysplit), dim3(256), EA2_LDS, e->stream,
                            reinterpret_cast<const bf16_t*>(qkv), reinterpret_cast<bf16_t*>(ctx), H, 3 * e->D, e->D, ablate2_env);
@@ -875,9 +882,9 @@ void enc_attention(mocr_engine* e, const void* qkv, void* ctx, int n, int impl) 
     } else if (impl == 2 && sizeof(T) == 2) {          // r01-r02 kernel (K / V staged through registers), A/B only
         ProfScope ps(e, "enc_attn_mfma_r02", flops, bytes);
         static const int qsplit_env = env_int("MOCR_ENC_ATTN_QSPLIT", 1);
-        const int ysplit = (qsplit_env && n * H * 2 <= e->num_cus) ? 2 : 1;
+        const int qsplit = (qsplit_env && n * H * 2 <= e->num_cus) ? 2 : 1;
         static const int ablate_env = env_int("MOCR_ENC_ATTN_ABLATE", 0);
-        hipLaunchKernelGGL(enc_attn_mfma_kernel, dim3(n * H, ysplit), dim3(256), ENC_MFMA_R02_LDS, e->stream,
+        hipLaunchKernelGGL(enc_attn_mfma_kernel, dim3(n * H, qsplit), dim3(256), ENC_MFMA_R02_LDS, e->stream,
                            reinterpret_cast<const bf16_t*>(qkv), reinterpret_cast<bf16_t*>(ctx), H, 3 * e->D, e->D, ablate_env);
 #endif
     } else if (impl == 1 && sizeof(T) == 4) {          // r04: the parity mode on the f32-input matrix cores
@@ -920,29 +927,24 @@ static void calib_observe(mocr_engine* e, int M) {
     c.idx += 1;
 }
 
-// (enc_out: where the final LayerNorm writes the n encodings; null = ENC)
+// What run_encoder decides from the number of crops (and the engine: its type, its CUs, its slab buffer, its flags) - made
+// once, here; run_encoder and the front end consume it and mocr_encoder_plan reports it.
+struct EncPlan {
+    int embed_tile;                   // patch embedding: 64 / 128
+    int tq, to, t1, t2;               // tile codes of QKV / O-proj / FC1 / FC2 (TILE_CODES)
+    int split_o, split_2;             // K slices of O-proj / FC2 (1: not split)
+    bool fold;                        // the LayerNorms between the layer GEMMs folded into them
+    int impl, ysplit;                 // the attention kernel (0 VALU, 1 matrix cores) and its blocks per (image, head)
+};
 template <typename T>
-void run_encoder(mocr_engine* e, const uint8_t* d_gray, int n, void* enc_out = nullptr) {
-    const int D = e->D, F = e->F, S = e->S, M = n * S, P = e->cfg.patch_size, IMG = e->cfg.image_size;
-    const int NP = e->G * e->G, MPATCH = n * NP;
-    auto& w = e->w;
-    {
-        const long long total = (long long)n * IMG * e->G;
-        ProfScope ps(e, "patchify", 0, (double)n * IMG * IMG * (1 + sizeof(T)));
-        hipLaunchKernelGGL((patchify_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, d_gray,
-                           w.lut, reinterpret_cast<T*>(e->Hb), n, IMG, P);
-        HIPCHECK(hipGetLastError());
-    }
-    {
-        ProfScope ps(e, "cls_rows", 0, (double)n * D * 4);
-        hipLaunchKernelGGL(cls_rows_kernel, dim3((n * D + 255) / 256), dim3(256), 0, e->stream, w.cls, w.pos_enc, e->X, n, S, D);
-        HIPCHECK(hipGetLastError());
-    }
+EncPlan encoder_plan(const mocr_engine* e, int n) {
+    const int D = e->D, F = e->F, M = n * e->S, MPATCH = n * e->G * e->G;
+    EncPlan pl{};
     // MOCR_ENC_TILE forces one tile code for the layer GEMMs (experiments); the patch embedding has its own epilogue
     // and stays on the 128x128 kernel unless a tile code that supports it (64/128/256) is forced
     static const int enc_tile_env = env_int("MOCR_ENC_TILE", 0);
-    const int ET = (enc_tile_env && enc_tile_env <= 256) ? enc_tile_env
-                   : ((long long)((MPATCH + 127) / 128) * (e->D / 128) * 5 <= 4LL * e->num_cus ? 64 : 128);
+    pl.embed_tile = (enc_tile_env && enc_tile_env <= 256) ? enc_tile_env
+                    : ((long long)((MPATCH + 127) / 128) * (e->D / 128) * 5 <= 4LL * e->num_cus ? 64 : 128);
     // The 128x128 kernel walks QKV / FC1 in column groups of 9 / 12 N-tiles (a 1.7 / 2.3 MB weight slice stays in
     // the XCD's L2): +4 % / +2 % at M = 806,912 (r01).
     // Layer GEMMs: the 256x256 "wide" kernel (tile code 1024) once it fills the chip about three times over
@@ -975,52 +977,98 @@ void run_encoder(mocr_engine* e, const uint8_t* d_gray, int n, void* enc_out = n
     // per-GEMM overrides for experiments: MOCR_ENC_TILE_QKV / _O / _FC1 / _FC2 (tile codes as in gemm())
     static const int tq_env = env_int("MOCR_ENC_TILE_QKV", 0), to_env = env_int("MOCR_ENC_TILE_O", 0),
                      t1_env = env_int("MOCR_ENC_TILE_FC1", 0), t2_env = env_int("MOCR_ENC_TILE_FC2", 0);
-    const int ETQ = tq_env ? tq_env : layer_tile(3 * D), ETO = to_env ? to_env : layer_tile(D), ET1 = t1_env ? t1_env : layer_tile(F);
-    const int ET2 = t2_env ? t2_env : ETO;
+    pl.tq = tq_env ? tq_env : layer_tile(3 * D); pl.to = to_env ? to_env : layer_tile(D); pl.t1 = t1_env ? t1_env : layer_tile(F);
+    pl.t2 = t2_env ? t2_env : pl.to;
+    pl.impl = (e->cfg.flags & MOCR_FLAG_SIMPLE_ATTENTION) ? 0 : 1;
+    pl.ysplit = enc_attn_ysplit<T>(e, n, pl.impl);
+    // A few crops (the 64 x 64 grid of the two N = 768 GEMMs is at most one block per CU: up to 6 crops on 256 CUs): O-proj
+    // and FC2 are split over K into fp32 slabs - for one crop 12 / 48 K-tiles walked alone by 48 blocks become 4 / 6 K-tiles
+    // on 144 / 384 blocks - and the LayerNorm launch that follows anyway finishes them (bias + slabs + residual, in place,
+    // fixed order; layernorm_slab_kernel).  r02, encoder of 1 / 2 / 4 crops: 1.07 / 1.07 / 1.12 -> 0.88 / 0.90 / 1.01 ms
+    // (one crop: FC2 28.3 -> 9.3 us, O-proj 11.8 -> 7.7, the LayerNorm behind them 6.6 -> 10.3)
+    // The split then shrinks until its slabs fit the slab buffer (round_up(max_batch, 128) * 12288 floats), so the (O-proj,
+    // FC2) splits depend on max_batch too.  max_batch <= 128: one crop (3, 8), two (3, 4), three (3, 2), four and five
+    // (1, 2), six unsplit; max_batch 129 .. 256: one and two crops (3, 8), three to five (3, 4), six (3, 2).
+    static const int enc_split_env = env_int("MOCR_ENC_SPLITK", 1);
+    const long long blocks64 = (long long)((M + 63) / 64) * (D / 64);
+    pl.split_o = 1; pl.split_2 = 1;
+    static const int enc_split_blocks = env_int("MOCR_ENC_SPLITK_BLOCKS", 0);      // largest unsplit 64 x 64 grid that is split (0: one block per CU)
+    if (enc_split_env && !enc_tile_env && !e->calib && pl.to == 64 && blocks64 <= (enc_split_blocks ? enc_split_blocks : e->num_cus)) {
+        pl.split_o = 3; pl.split_2 = 8;
+        while (pl.split_2 > 1 && (long long)M * D * pl.split_2 > e->slab_cap) pl.split_2 >>= 1;
+        if ((long long)M * D * pl.split_o > e->slab_cap) pl.split_o = 1;
+        if (pl.split_2 < 2) pl.split_2 = 1;
+    }
+    // bf16, all four layer GEMMs on the persistent kernel: the 24 LayerNorms between them are FOLDED into those GEMMs
+    // (kernels_gemm_pers.h LNF; r03: 25 launches of 38-40 us were 7.5 % of the encoder at batch 256).  Xn then holds x itself
+    // as bf16; only the final LayerNorm (the encoder's output) is a launch.
+    pl.fold = false;
+    if constexpr (sizeof(T) == 2) {
+        static const int fold_env = env_int("MOCR_ENC_LN_FOLD", 1);
+        auto folds = [](int code) { const TileCode* t = tile_code(code); return t && t->product_persistent(); };
+        pl.fold = fold_env && !(e->cfg.flags & MOCR_FLAG_NO_LN_FOLD) && folds(pl.tq) && folds(pl.to) && folds(pl.t1) && folds(pl.t2) &&
+                  D == 768 && e->w.enc[0].wqkv_f && !e->calib && (e->fold_ok || (e->cfg.flags & MOCR_FLAG_FORCE_LN_FOLD));
+    }
+    return pl;
+}
+
+// The encoder's front end: gray [n, IMG, IMG] -> patches T [n * 196, 256] (patchify) -> x f32 [n * 197, 768] (CLS rows + patch
+// embedding).  tile: the patch embedding's tile code, 0 = the plan's.  `patches` holds round_up(n * 196, 128) rows (the GEMM
+// stages whole tiles of A).  run_encoder and mocr_op_embed both come through here.
+template <typename T>
+void encoder_front(mocr_engine* e, const uint8_t* d_gray, int n, void* patches, float* x, int tile) {
+    const int D = e->D, S = e->S, P = e->cfg.patch_size, IMG = e->cfg.image_size, NP = e->G * e->G;
+    auto& w = e->w;
+    {
+        const long long total = (long long)n * IMG * e->G;
+        ProfScope ps(e, "patchify", 0, (double)n * IMG * IMG * (1 + sizeof(T)));
+        hipLaunchKernelGGL((patchify_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, d_gray,
+                           w.lut, reinterpret_cast<T*>(patches), n, IMG, P);
+        HIPCHECK(hipGetLastError());
+    }
+    {
+        ProfScope ps(e, "cls_rows", 0, (double)n * D * 4);
+        hipLaunchKernelGGL(cls_rows_kernel, dim3((n * D + 255) / 256), dim3(256), 0, e->stream, w.cls, w.pos_enc, x, n, S, D);
+        HIPCHECK(hipGetLastError());
+    }
+    GemmCall embed = gemm_call("gemm_patch_embed", patches, P * P, w.wpe, w.bpe, x, D, n * NP, D, P * P, EPI_PATCH,
+                               tile ? tile : encoder_plan<T>(e, n).embed_tile);
+    embed.pos = w.pos_enc; embed.patches = NP;
+    gemm<T>(e, embed);
+}
+
+// x += bias + the nslab fp32 slabs (slab_stride floats apart), in place, then out = LayerNorm(x): what finishes a layer GEMM
+// split over K (layernorm_slab_kernel)
+template <typename T>
+void layernorm_slab(mocr_engine* e, float* x, const float* slabs, int nslab, long long slab_stride, const float* bias, const float* g,
+                    const float* b, void* out, int M) {
+    ProfScope ps(e, "layernorm_slab", 0, (double)M * e->D * (4.0 * (nslab + 2) + sizeof(T)));
+    hipLaunchKernelGGL((layernorm_slab_kernel<T, 768>), dim3((M + 3) / 4), dim3(256), 0, e->stream, x, slabs, nslab, slab_stride, bias,
+                       g, b, reinterpret_cast<T*>(out), M, e->cfg.ln_eps);
+    HIPCHECK(hipGetLastError());
+}
+
+// (enc_out: where the final LayerNorm writes the n encodings; null = ENC)
+template <typename T>
+void run_encoder(mocr_engine* e, const uint8_t* d_gray, int n, void* enc_out = nullptr) {
+    const int D = e->D, F = e->F, S = e->S, M = n * S;
+    auto& w = e->w;
+    const EncPlan pl = encoder_plan<T>(e, n);
+    const int ETQ = pl.tq, ETO = pl.to, ET1 = pl.t1, ET2 = pl.t2, split_o = pl.split_o, split_2 = pl.split_2;
+    const bool fold = pl.fold;
     // tile order of QKV / FC1: column groups whose weight slices stay in an XCD's 4 MiB L2 while the A row-panels stream through
     // once per group.  128 x 128 tiles: groups of 9 / 12 N-tiles (r01).  Persistent 256 x 256 tiles: groups of 6 (r04: QKV 6 + 3,
     // FC1 6 + 6: the whole 3.4 / 4.5 MiB weight does not fit beside the A panels, and without groups every XCD re-fetches it
     // per round of row-panels - at batch 256 QKV 210 -> 200 us, FC1 337 -> 331 us, one box; tools/r04_groupn_ab.sh)
     const bool pers_q = tile_is(ETQ, GemmKind::Persistent), pers_1 = tile_is(ET1, GemmKind::Persistent);
     const int gq = pers_q ? 6 : 9, g1 = pers_1 ? 6 : 12;
-    GemmCall embed = gemm_call("gemm_patch_embed", e->Hb, P * P, w.wpe, w.bpe, e->X, D, MPATCH, D, P * P, EPI_PATCH, ET);
-    embed.pos = w.pos_enc; embed.patches = NP;
-    gemm<T>(e, embed);
-    const int impl = (e->cfg.flags & MOCR_FLAG_SIMPLE_ATTENTION) ? 0 : 1;
-    // A few crops (the 64 x 64 grid of the two N = 768 GEMMs is at most one block per CU: up to 5 crops): O-proj and FC2
-    // are split over K into fp32 slabs - for one crop 12 / 48 K-tiles walked alone by 48 blocks become 4 / 6 K-tiles on
-    // 144 / 384 blocks - and the LayerNorm launch that follows anyway finishes them (bias + slabs + residual, in place,
-    // fixed order; layernorm_slab_kernel).  r02, encoder of 1 / 2 / 4 crops: 1.07 / 1.07 / 1.12 -> 0.88 / 0.90 / 1.01 ms
-    // (one crop: FC2 28.3 -> 9.3 us, O-proj 11.8 -> 7.7, the LayerNorm behind them 6.6 -> 10.3)
-    static const int enc_split_env = env_int("MOCR_ENC_SPLITK", 1);
-    const long long blocks64 = (long long)((M + 63) / 64) * (D / 64);
-    int split_o = 1, split_2 = 1;
-    static const int enc_split_blocks = env_int("MOCR_ENC_SPLITK_BLOCKS", 0);      // largest unsplit 64 x 64 grid that is split (0: one block per CU)
-    if (enc_split_env && !enc_tile_env && !e->calib && ETO == 64 && blocks64 <= (enc_split_blocks ? enc_split_blocks : e->num_cus)) {
-        split_o = 3; split_2 = 8;
-        while (split_2 > 1 && (long long)M * D * split_2 > e->slab_cap) split_2 >>= 1;
-        if ((long long)M * D * split_o > e->slab_cap) split_o = 1;
-        if (split_2 < 2) split_2 = 1;
-    }
-    // bf16, all four layer GEMMs on the persistent kernel: the 24 LayerNorms between them are FOLDED into those GEMMs
-    // (kernels_gemm_pers.h LNF; r03: 25 launches of 38-40 us were 7.5 % of the encoder at batch 256).  Xn then holds x itself
-    // as bf16; only the final LayerNorm (the encoder's output) is a launch.
-    bool fold = false;
-    if constexpr (sizeof(T) == 2) {
-        static const int fold_env = env_int("MOCR_ENC_LN_FOLD", 1);
-        auto folds = [](int code) { const TileCode* t = tile_code(code); return t && t->product_persistent(); };
-        fold = fold_env && !(e->cfg.flags & MOCR_FLAG_NO_LN_FOLD) && folds(ETQ) && folds(ETO) && folds(ET1) && folds(ET2) &&
-               D == 768 && w.enc[0].wqkv_f && !e->calib && (e->fold_ok || (e->cfg.flags & MOCR_FLAG_FORCE_LN_FOLD));
-    }
+    encoder_front<T>(e, d_gray, n, e->Hb, e->X, pl.embed_tile);
     const float* pend_bias = nullptr;      // bias of a split GEMM whose slabs the next LayerNorm has to add to X
     int pend_slabs = 0;
     auto norm = [&](const float* g, const float* b, void* out) {
         if (e->calib && !pend_slabs) calib_observe(e, M);
         if (!pend_slabs) { layernorm<T>(e, e->X, g, b, out, M); return; }
-        ProfScope ps(e, "layernorm_slab", 0, (double)M * D * (4.0 * (pend_slabs + 2) + sizeof(T)));
-        hipLaunchKernelGGL((layernorm_slab_kernel<T, 768>), dim3((M + 3) / 4), dim3(256), 0, e->stream, e->X, e->slabs, pend_slabs,
-                           (long long)M * D, pend_bias, g, b, reinterpret_cast<T*>(out), M, e->cfg.ln_eps);
-        HIPCHECK(hipGetLastError());
+        layernorm_slab<T>(e, e->X, e->slabs, pend_slabs, (long long)M * D, pend_bias, g, b, out, M);
         pend_slabs = 0;
     };
     if (fold) {
@@ -1051,7 +1099,7 @@ void run_encoder(mocr_engine* e, const uint8_t* d_gray, int n, void* enc_out = n
         }
         if (!fold) norm(L.ln1g, L.ln1b, e->Xn);
         gemm<T>(e, qkv);
-        enc_attention<T>(e, e->QKV, e->CTX, n, impl);
+        enc_attention<T>(e, e->QKV, e->CTX, n, pl.impl, pl.ysplit);
         gemm<T>(e, split_o > 1 ? into_slabs(oproj, split_o) : oproj);
         if (!fold) norm(L.ln2g, L.ln2b, e->Xn);
         gemm<T>(e, fc1);
@@ -3907,8 +3955,56 @@ int mocr_op_enc_attention(mocr_engine* e, const void* d_qkv, void* d_ctx, int32_
         HIPCHECK(hipSetDevice(e->cfg.device));
         drive(e);
         e->bind(0);
-        dispatch(e, [&](auto tag) { enc_attention<decltype(tag)>(e, d_qkv, d_ctx, n, impl); });
+        dispatch(e, [&](auto tag) {
+            using T_ = decltype(tag);
+            enc_attention<T_>(e, d_qkv, d_ctx, n, impl, enc_attn_ysplit<T_>(e, n, impl));
+        });
         HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_op_embed(mocr_engine* e, const void* d_gray, int32_t n, int32_t tile, void* d_patches, float* d_x) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        require_ready(e, n);
+        if (!d_gray || !d_patches || !d_x) throw ArgError{"mocr_op_embed: null pointer", MOCR_ERR_ARG};
+        if (tile != 0 && tile != 64 && tile != 128) throw ArgError{"mocr_op_embed: tile must be 0 (the encoder's choice), 64 or 128", MOCR_ERR_ARG};
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        const uint8_t* g = reinterpret_cast<const uint8_t*>(d_gray);
+        dispatch(e, [&](auto tag) { encoder_front<decltype(tag)>(e, g, n, d_patches, d_x, tile); });
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_op_layernorm_slab(mocr_engine* e, float* d_x, const float* d_slabs, int32_t nslab, int64_t slab_stride, const float* d_bias,
+                           const float* d_gamma, const float* d_beta, void* d_out, int32_t M) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (e->D != 768) throw ArgError{"mocr_op_layernorm_slab: hidden size 768 only", MOCR_ERR_UNSUPPORTED};
+        if (!d_x || !d_slabs || !d_bias || !d_gamma || !d_beta || !d_out || nslab < 1 || M < 1 || slab_stride < (int64_t)M * e->D ||
+            (slab_stride & 3))
+            throw ArgError{"mocr_op_layernorm_slab: bad argument", MOCR_ERR_ARG};
+        dispatch(e, [&](auto tag) {
+            layernorm_slab<decltype(tag)>(e, d_x, d_slabs, nslab, (long long)slab_stride, d_bias, d_gamma, d_beta, d_out, M);
+        });
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_encoder_plan(mocr_engine* e, int32_t n, int32_t out[10]) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        require_ready(e, n);
+        if (!out) throw ArgError{"mocr_encoder_plan: null pointer", MOCR_ERR_ARG};
+        EncPlan pl{};
+        dispatch(e, [&](auto tag) { pl = encoder_plan<decltype(tag)>(e, n); });
+        const int32_t v[10] = {pl.embed_tile, pl.tq, pl.to, pl.t1, pl.t2, pl.split_o, pl.split_2, pl.fold ? 1 : 0, pl.ysplit, pl.impl};
+        memcpy(out, v, sizeof(v));
     });
 }
 

@@ -147,6 +147,9 @@ SYMBOLS = {
     "mocr_op_gemm_ln": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "mocr_op_ln_prep": (C.c_int, [_P, _P, _P, _P, C.c_int32]),
     "mocr_op_enc_attention": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),
+    "mocr_op_embed": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "mocr_op_layernorm_slab": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, C.c_int32]),
+    "mocr_encoder_plan": (C.c_int, [_P, C.c_int32, _P]),
     "mocr_op_latent_attention": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64]),
     "mocr_op_quant_fp8": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float]),
     "mocr_op_latent_attention_fp8": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_float]),

@@ -524,6 +524,23 @@ class Engine:
     def op_enc_attention(self, d_qkv, d_ctx, n, impl) -> None:
         self._check(self.lib.mocr_op_enc_attention(self._h, _ptr(d_qkv), _ptr(d_ctx), n, impl))
 
+    def op_embed(self, d_gray, n, tile, d_patches, d_x) -> None:
+        """The encoder's front end on the caller's buffers (include/mocr.h, mocr_op_embed); tile 0 = the encoder's choice."""
+        self._check(self.lib.mocr_op_embed(self._h, _ptr(d_gray), int(n), int(tile), _ptr(d_patches), _ptr(d_x)))
+
+    def op_layernorm_slab(self, d_x, d_slabs, nslab, slab_stride, d_bias, d_gamma, d_beta, d_out, M) -> None:
+        """x += bias + slabs in place, out = LayerNorm(x) (include/mocr.h, mocr_op_layernorm_slab)."""
+        self._check(self.lib.mocr_op_layernorm_slab(self._h, _ptr(d_x), _ptr(d_slabs), int(nslab), int(slab_stride), _ptr(d_bias),
+                                                    _ptr(d_gamma), _ptr(d_beta), _ptr(d_out), int(M)))
+
+    ENCODER_PLAN_FIELDS = ("embed_tile", "tile_qkv", "tile_o", "tile_fc1", "tile_fc2", "split_o", "split_2", "fold", "ysplit", "attn_impl")
+
+    def encoder_plan(self, n: int) -> dict:
+        """What the encoder decides from the number of crops (include/mocr.h, mocr_encoder_plan), by name."""
+        out = np.zeros(10, dtype=np.int32)
+        self._check(self.lib.mocr_encoder_plan(self._h, int(n), _ptr(out)))
+        return dict(zip(self.ENCODER_PLAN_FIELDS, (int(v) for v in out)))
+
     def op_latent_attention(self, d_qt, d_x, d_out, n, length, x_batch_stride) -> None:
         self._check(self.lib.mocr_op_latent_attention(self._h, _ptr(d_qt), _ptr(d_x), _ptr(d_out), n, length, x_batch_stride))
 

@@ -58,6 +58,42 @@ def bf16_round(a: np.ndarray) -> np.ndarray:
     return r.astype(np.uint32).view(np.float32)
 
 
+BF16_ULP = 2.0 ** -8
+
+
+def _nan(shape, dtype):
+    """NaN-filled output of the engine's storage type ("f32" / "fp32": float32)"""
+    import torch
+    return torch.full(shape, float("nan"), device="cuda", dtype=torch.bfloat16 if dtype == "bf16" else torch.float32)
+
+
+def _store(x, dtype):
+    """a float64 array as the engine's storage type holds it"""
+    return bf16_round(np.asarray(x, np.float32)).astype(np.float64) if dtype == "bf16" else np.asarray(x, np.float32).astype(np.float64)
+
+
+def _grid_vals(rs, shape, scale=1.0):
+    """values on a 2^-10 grid (|v| < 8 scale): fp32 sums of a few dozen of them are exact in any order"""
+    return (np.round(rs.standard_normal(shape) * scale * 256) / 1024).clip(-8 * scale, 8 * scale).astype(np.float32)
+
+
+def _check_bf16_or_f32(got, ref, scale, dtype, what, extra=0.0):
+    """|got - ref| <= (2^-8 |ref| for bf16) + 1e-5 scale + extra; returns the worst ratio err / tol"""
+    tol = (BF16_ULP * np.abs(ref) if dtype == "bf16" else 0.0) + 1e-5 * scale + extra
+    err = np.abs(got - ref)
+    assert np.isfinite(got).all(), f"{what}: non-finite output"
+    ratio = float((err / tol).max())
+    bad = np.argwhere(err > tol)
+    assert bad.size == 0, f"{what}: {len(bad)} elements out of tolerance, first at {tuple(bad[0])}: got {got[tuple(bad[0])]} want {ref[tuple(bad[0])]}"
+    return ratio, float((err / np.broadcast_to(scale, err.shape)).max())
+
+
+def _ln64(v, g, b, eps=1e-12):
+    m = v.mean(-1, keepdims=True)
+    var = ((v - m) ** 2).mean(-1, keepdims=True)
+    return (v - m) / np.sqrt(var + eps) * g + b, m[..., 0], np.sqrt(var[..., 0])
+
+
 def e4m3_table():
     """byte -> float for OCP e4m3fn (bias 7, no infinities, 0x7F / 0xFF = NaN)."""
     t = np.zeros(256, np.float64)

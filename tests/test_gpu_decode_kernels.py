@@ -10,7 +10,7 @@ with each other exactly.  Every output sits between NaN guard rows / positions t
 import numpy as np
 import pytest
 
-from gpu_util import bf16_round, e4m3_quant, e4m3_table, engine, report, weights
+from gpu_util import BF16_ULP, _check_bf16_or_f32, _grid_vals, _ln64, _nan, _store, bf16_round, e4m3_quant, e4m3_table, engine, report, weights
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -19,7 +19,6 @@ D, H, DH, V, S = 768, 12, 64, 6144, 197
 MAX_LEN = 300                       # the engines' max_len: the K/V and latent caches' position stride
 NCKV = 2 * D * 2                    # cross K/V block columns (2 decoder layers)
 START, EOS, PAD = 2, 3, 0
-BF16_ULP = 2.0 ** -8
 SENT = -777                         # guard value of int buffers
 GUARD = 2                           # guard rows behind every output
 
@@ -38,39 +37,13 @@ def _t(a, dtype):
     return t.to(torch.bfloat16) if dtype == "bf16" else t
 
 
-def _nan(shape, dtype):
-    """NaN-filled output of the engine's storage type ("f32" / "fp32": float32)"""
-    return torch.full(shape, float("nan"), device="cuda", dtype=torch.bfloat16 if dtype == "bf16" else torch.float32)
-
-
 def _np(t):
     return t.float().cpu().numpy().astype(np.float64) if t.dtype != torch.int32 and t.dtype != torch.uint8 else t.cpu().numpy()
-
-
-def _store(x, dtype):
-    """a float64 array as the engine's storage type holds it"""
-    return bf16_round(np.asarray(x, np.float32)).astype(np.float64) if dtype == "bf16" else np.asarray(x, np.float32).astype(np.float64)
 
 
 def _gelu(x):
     from scipy.special import erf
     return 0.5 * x * (1.0 + erf(x / np.sqrt(2.0)))
-
-
-def _grid_vals(rs, shape, scale=1.0):
-    """values on a 2^-10 grid (|v| < 8 scale): fp32 sums of a few dozen of them are exact in any order"""
-    return (np.round(rs.standard_normal(shape) * scale * 256) / 1024).clip(-8 * scale, 8 * scale).astype(np.float32)
-
-
-def _check_bf16_or_f32(got, ref, scale, dtype, what, extra=0.0):
-    """|got - ref| <= (2^-8 |ref| for bf16) + 1e-5 scale + extra; returns the worst ratio err / tol"""
-    tol = (BF16_ULP * np.abs(ref) if dtype == "bf16" else 0.0) + 1e-5 * scale + extra
-    err = np.abs(got - ref)
-    assert np.isfinite(got).all(), f"{what}: non-finite output"
-    ratio = float((err / tol).max())
-    bad = np.argwhere(err > tol)
-    assert bad.size == 0, f"{what}: {len(bad)} elements out of tolerance, first at {tuple(bad[0])}: got {got[tuple(bad[0])]} want {ref[tuple(bad[0])]}"
-    return ratio, float((err / np.broadcast_to(scale, err.shape)).max())
 
 
 # ------------------------------------------------------------------------------------------------ decode attention
@@ -216,12 +189,6 @@ def test_cross_attention_against_float64(dtype, nslab, layer):
 
 
 # ------------------------------------------------------------------------------------------------ slab sum + LayerNorm
-def _ln64(v, g, b, eps=1e-12):
-    m = v.mean(-1, keepdims=True)
-    var = ((v - m) ** 2).mean(-1, keepdims=True)
-    return (v - m) / np.sqrt(var + eps) * g + b, m[..., 0], np.sqrt(var[..., 0])
-
-
 def _run_add_ln(eng, dtype, slabs, bias, resid, g, b, gelu, with_f32, cache=None, step=None, rowmap=None, inv_sx=0.0):
     rows = slabs.shape[1]
     out_f32 = torch.full((rows + GUARD, D), float("nan"), device="cuda") if with_f32 else None

@@ -1,6 +1,7 @@
 """-m gpu: every HIP kernel class against a float64 numpy / torch-fp32 statement of the same op,
 called through the C ABI's operator hooks.  Device memory comes from torch (plumbing only).
-This file covers the encoder's kernels and the latent attention path; the kernels of the classic and small-batch decode
+This file covers the encoder's kernels and the latent attention path (the encoder's front end, LayerNorms and attention
+elementwise against float64, and the encoder per kernel regime, are in test_gpu_encoder_kernels.py); the kernels of the classic and small-batch decode
 step (decode attention, slab sum + LayerNorm / GELU, the token step, the LM head's fused argmax, the small-batch
 projections) are in test_gpu_decode_kernels.py."""
 import os
@@ -386,8 +387,9 @@ def test_layernorm(dtype):
 def test_encoder_attention(dtype, impl, n):
     """impl 0: the VALU kernel; 1: fp32 - the parity mode's kernel on the f32-input matrix cores (enc_attn_f32_kernel: exact fp32
     products), bf16 - the MFMA kernel of the bf16 engine (K / V by LDS-DMA, V read
-    column-wise with ds_read_b64_tr_b16) - 1 crop (four blocks share a head's 13 query units), 3 / 30 (two), 70 (one block
-    per head, three blocks per CU); 2: the r02 kernel (experiments build)."""
+    column-wise with ds_read_b64_tr_b16) - 1 and 3 crops (four blocks share a head's 13 query units: up to 10 crops on 256
+    CUs), 30 and 70 (one block per head, three blocks per CU: from 22 crops; the two blocks per head of 11 .. 21 crops are
+    run by test_gpu_encoder_kernels.py, which reads the split from mocr_encoder_plan); 2: the r02 kernel (experiments build)."""
     eng = engine(dtype)
     rs = np.random.RandomState(11 + impl + n)
     S, H, dh = 197, 12, 64

@@ -172,7 +172,7 @@ def test_graph_cache_is_bounded_and_padding_rows_do_not_leak():
     gray = crops(55, 40)
     full, _ = eng.recognize_gray(gray, max_len=20)
     small, _ = eng.recognize_gray(gray[:32], max_len=20)      # <= 32 rows: the one-launch-per-projection path (kernels_smallm.h)
-    tiny, _ = eng.recognize_gray(gray[:5], max_len=20)        # <= 5 crops: the encoder's O-proj / FC2 split over K
+    tiny, _ = eng.recognize_gray(gray[:5], max_len=20)        # <= 5 crops (max_batch <= 128): the encoder's O-proj / FC2 split over K
     base = eng.graph_count()
     for n in range(1, 41):
         ids, lens = eng.recognize_gray(gray[:n], max_len=20)

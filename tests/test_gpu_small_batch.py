@@ -44,8 +44,11 @@ def test_small_batch_path_logits_agree_with_the_generic_path_and_the_oracle(rows
 
 
 def test_small_batch_rows_do_not_depend_on_the_batch():
-    """A crop decodes to the same ids whatever else is in its batch, as long as the batch stays in one kernel regime: up to 5
-    crops the encoder splits its O-proj / FC2 GEMMs over K (another summation order), from 6 to 32 rows it does not."""
+    """A crop decodes to the same ids whatever else is in its batch, as long as the batch stays in one kernel regime.  On this
+    engine (max_batch 32: a slab buffer of 128 rows' worth) the encoder splits its O-proj / FC2 GEMMs over K up to 5 crops -
+    (3, 8) ways for one crop, (3, 4) for two, (3, 2) for three, (1, 2) for four and five (mocr_encoder_plan; other summation
+    orders, which these ids survive) - and from 6 to 32 rows it does not: six crops are still eligible for the split (228
+    blocks of 64 x 64 on 256 CUs), but their slabs do not fit this engine's buffer; from max_batch 129 they do, (3, 2)."""
     eng = engine("bf16", max_batch=32, flags=CLASSIC)
     gray = crops(4343, 32)
     full, _ = eng.recognize_gray(gray, max_len=40)
