@@ -481,6 +481,55 @@ int mocr_op_layernorm_slab(mocr_engine* e, float* d_x, const float* d_slabs, int
  * K slices of O-proj, K slices of FC2 (1 = not split; the LayerNorm behind a split GEMM adds that many slabs), 1 if the
  * LayerNorms are folded into the GEMMs, blocks per (crop, head) of the attention, attention kernel (0 VALU, 1 matrix cores) }. */
 int mocr_encoder_plan(mocr_engine* e, int32_t n, int32_t out[10]);
+/* What a greedy decode step of `rows` rows decides on this engine (test hook; computed by the helpers the step launches
+ * through, nothing is launched).  regime_rows = the rows the batch started with (0 = rows): after a compaction the split over
+ * K follows the regime, the tile and the ring depth follow the rows that are left.  rows need not fit max_batch.  out =
+ *   [0]  path: 0 small-batch (bf16, <= 32 regime rows, not latent), 1 classic attention, 2 latent attention (bf16, regime rows
+ *        above the engine's own switch: min(256, max_batch), 0 with MOCR_FLAG_LATENT_ALWAYS, never with
+ *        MOCR_FLAG_CLASSIC_ATTENTION) - the path fields [0], [18] .. [22] use THIS engine's switch
+ *   [1]  regime tile: 128 from 1024 regime rows, else 64 (the split is chosen for it)     [2] launch tile: the same rule on rows
+ *   [3 + 3 g], [4 + 3 g], [5 + 3 g] for g = 0 QKV [2304 x 768], 1 the 768 x 768 projections, 2 FC1 [3072 x 768], 3 FC2
+ *        [768 x 3072], 4 vocabulary [vocab x 768]: K slices (1 = not split), ring slots of the launch (2 or 4: 4 iff rows <
+ *        1280, >= 4 K-tiles of 128 bytes per K slice and M-tiles x N-tiles x slices <= compute units) and the epilogue launched:
+ *        0 fp32 slabs; FC1 2 = bias + GELU fused (its split is 1); vocabulary 6 = the fused LM head (split 1, no
+ *        MOCR_FLAG_NO_FUSED_ARGMAX; a scored / constrained batch launches that head's own form of it, a logits or beam request
+ *        the slabs).  These fifteen say how gemm_kernel is launched for the shape at these rows whether or not the path
+ *        launches it; they depend on the dtype, the compute units and the flags, not on max_batch
+ *   [18] 1 if the step launches QKV as a tile GEMM (classic path; the latent path projects the queries in its own block and the
+ *        small-batch path launches none of the five as a tile GEMM)
+ *   [19] latent path: 1 if q and Qt come from the fused query kernel (from 257 regime rows)   [20] its rows per block (64 up to
+ *        1280 rows, else 128; 0 when not fused)   [21] the Qt GEMM's tile on the two-launch path (128 from 1024 regime rows, else
+ *        64; 0 when fused or not latent)
+ *   [22] classic and small-batch attention: 1 = non-temporal K/V loads (from 128 regime rows)
+ *   [23] steps per graph replay: 2 up to 16 rows, 4 up to 128, else 8
+ *   [24] the rows a batch of `rows` decodes on: rows rounded up to 1 (<= 8), 8 (<= 64), 32 (<= 256), 64 (<= 1024) or 256,
+ *        at most max_batch. */
+#define MOCR_DECODE_PLAN_FIELDS 25
+int mocr_decode_plan(mocr_engine* e, int32_t rows, int32_t regime_rows, int32_t out[MOCR_DECODE_PLAN_FIELDS]);
+/* mocr_op_gemm on the 64 / 128 tile kernel with the operands a caller of the engine sets itself: the decode step's slabs lie
+ * round_up(max_batch, 128) * N floats apart, the encoder walks QKV / FC1 in column groups.  Through the same launch, so the
+ * ring depth is the one the step gets at M rows.  Refuses what mocr_op_gemm refuses, a tile code other than 64 / 128, rows
+ * that are not 16-byte aligned and a slab stride that cannot hold a slab.  A holds M rounded up to the tile rows. */
+typedef struct mocr_gemm_args {
+    int32_t struct_size;        /* sizeof(mocr_gemm_args) */
+    int32_t M, N, K;
+    int32_t epilogue;           /* 0 slabs, 1 bias, 2 bias + GELU, 3 bias + residual (fp32 out), 5 bias (fp32 out) */
+    int32_t tile;               /* 64 or 128 */
+    int32_t split_k;            /* K slices (> 1 with epilogue 0 only) */
+    int32_t lda;                /* elements between two rows of A (0 = K) */
+    int32_t ldo;                /* elements between two rows of out and of resid (0 = N) */
+    int32_t group_n;            /* N-tiles per column group of the tile order (0 = one group) */
+    int64_t slab_stride;        /* epilogue 0: floats between two K slices' slabs (0 = M * ldo) */
+    const void* A;
+    const void* W;              /* [N][K] */
+    const float* bias;          /* [N]; unused by epilogue 0 */
+    void* out;
+    const float* resid;         /* epilogue 3 */
+} mocr_gemm_args;
+int mocr_op_gemm_args(mocr_engine* e, const mocr_gemm_args* a);
+/* The calling thread's last gemm_kernel launch (any hook that runs a 64 / 128 tile GEMM, the fused LM heads included):
+ * out = { tile, ring slots, blocks in the grid, K slices }. */
+int mocr_last_tile_launch(mocr_engine* e, int32_t out[4]);
 /* Latent decode attention (bf16 engines): d_qt [n,16,768], keys d_x with x_batch_stride elements between
  * sequences, context length len for every row; d_out [n,16,768] = softmax(qt . x^T) x per head. */
 int mocr_op_latent_attention(mocr_engine* e, const void* d_qt, const void* d_x, void* d_out, int32_t n, int32_t len,

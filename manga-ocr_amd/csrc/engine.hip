@@ -495,11 +495,16 @@ template <typename T> struct TileFamily {
     static constexpr int lds(const Args& a) { return a.ring * (a.bm + a.bm) * 128; }
 };
 
-template <typename T>
-void launch_gemm_tile(mocr_engine* e, const GemmParams& p0, int epi, int bm, int split, int ybatch) {
-    GemmParams p = p0;
-    p.ntn = p.N / bm; p.ntm = (p.M + bm - 1) / bm;
-    dim3 grid(p.ntm * p.ntn, ybatch, split);
+// The grid and the ring depth of one gemm_kernel launch: M x N outputs on bm x bm tiles, `split` K slices of `ktiles` K-tiles
+// each, `ybatch` GEMMs (heads).  launch_gemm_tile launches what this says and decode_plan reports it (mocr_decode_plan: "ring
+// slots"), so the rule below is stated once.
+struct TileLaunch { int ntm, ntn; long long blocks; int ring; };
+struct LastTile { int bm, ring, blocks, split; };
+static thread_local LastTile g_last_tile{};      // what this thread's last launch_gemm_tile launched (mocr_op_gemm_args reports it)
+static TileLaunch tile_launch(const mocr_engine* e, int M, int N, int bm, int split, int ybatch, int ktiles) {
+    TileLaunch t{};
+    t.ntn = N / bm; t.ntm = (M + bm - 1) / bm;
+    t.blocks = (long long)t.ntm * t.ntn * ybatch * split;
     // Grids of at most one block per CU walk their K-tiles alone on a CU, one memory round trip per K-tile on the two-slot
     // ring.  A four-slot ring (three K-tiles in flight, 128 KiB of LDS for the 128 x 128 tile) changed nothing for the encoder
     // of a few crops (r02: QKV of one crop 16.1 vs 15.9 us - its cost is the DMA issue), but the decode step's split-K
@@ -508,19 +513,31 @@ void launch_gemm_tile(mocr_engine* e, const GemmParams& p0, int epi, int bm, int
     // 104.7, 512 rows 128.5 / 122.4, 1024 rows 196.0 / 193.7 - and the headline's two lanes x 2560 rows 7.02-7.11 / 6.90-6.92 k
     // crops/s: two 64-KiB blocks of two lanes share a CU, a 128-KiB block does not.  So: four slots for batches below the
     // rows from which a queue is split over two lanes (1280).  Same K order, same sums: bit-identical either way.
+    // The rule, as the plan reports it: four slots iff M < 1280 rows, at least 4 K-tiles per K slice and at most one block per
+    // CU in the whole grid (N-tiles x M-tiles x heads x K slices); two slots otherwise.
     static const int deep_rows = env_int("MOCR_GEMM_DEEP_ROWS", 1280);
-    const int ktiles = p.k_per_split / (128 / (int)sizeof(T));
     static const int deep_mult64 = env_int("MOCR_GEMM_DEEP_MULT64", 1);      // (experiments: 64 x 64 tiles, two 64-KiB rings fit a CU)
     // (the ring depth does not touch the arithmetic, so a compacted batch's tail chooses it by the rows it has LEFT, as
     // launch_qqt its rows per block: r04, tools/r04_neutral_ab.sh, mixed-lengths leg 11.93 -> 12.11 k crops/s, ids bit-identical;
     // MOCR_NEUTRAL_BY_ROWS=0: by the batch's regime)
     static const int neutral_by_rows = env_int("MOCR_NEUTRAL_BY_ROWS", 2);
-    const bool deep = (neutral_by_rows ? p.M : e->rrows(p.M)) < deep_rows && ktiles >= 4 &&
-                      (long long)grid.x * grid.y * grid.z <= (long long)e->num_cus * (bm == 64 ? deep_mult64 : 1);
-    const auto f = find_form<TileFamily<T>>({epi, bm, deep ? 4 : 2, p.tgt_val != nullptr});
+    const bool deep = (neutral_by_rows ? M : e->rrows(M)) < deep_rows && ktiles >= 4 &&
+                      t.blocks <= (long long)e->num_cus * (bm == 64 ? deep_mult64 : 1);
+    t.ring = deep ? 4 : 2;
+    return t;
+}
+
+template <typename T>
+void launch_gemm_tile(mocr_engine* e, const GemmParams& p0, int epi, int bm, int split, int ybatch) {
+    GemmParams p = p0;
+    const TileLaunch t = tile_launch(e, p.M, p.N, bm, split, ybatch, p.k_per_split / (128 / (int)sizeof(T)));
+    p.ntn = t.ntn; p.ntm = t.ntm;
+    dim3 grid(p.ntm * p.ntn, ybatch, split);
+    const auto f = find_form<TileFamily<T>>({epi, bm, t.ring, p.tgt_val != nullptr});
     if (!f.kernel) throw ArgError{"unknown GEMM epilogue", MOCR_ERR_ARG};
     hipLaunchKernelGGL(f.kernel, grid, dim3(256), f.lds, e->stream, p);
     HIPCHECK(hipGetLastError());
+    g_last_tile = {bm, t.ring, (int)std::min<long long>(t.blocks, INT32_MAX), split};
 }
 
 #ifdef MOCR_EXPERIMENTS
@@ -1114,6 +1131,7 @@ static int dec_tile(int rows) {
     // 128 x 128 tiles from 1024 rows (r02: from 512 - at 256 rows the 64 x 64 tiles need a third of the split-K slabs, 113 -> 101
     // ms for an isolated 256-crop batch.  r04, tools/r04_dectile_ab.sh, isolated batches, 64 / 128 tiles: 512 rows 128.0 / 134.3
     // ms, 640 rows 143.4 / 147.4, 768 rows 157.5 / 162.7, 1024 rows 199.8 / 195.4, 1280 rows 229 / 224)
+    // (mocr_decode_plan: "regime tile" = this rule on the batch's regime, "launch tile" = on the rows of the launch)
     static const int fat = env_int("MOCR_DEC_FAT_ROWS", 1024);
     if (forced) return forced;
     return rows >= fat ? 128 : 64;
@@ -1140,6 +1158,8 @@ static int pick_split(int N, int K, int kt, int rows, long long slab_cap_per_row
     static const int target_env = env_int("MOCR_DEC_BLOCKS", 0);
     // (r04, with the four-slot rings of lone batches, tools/r04_decblocks_small_ab.sh, targets 150 / 100: 96 rows 58.4 / 56.4 ms,
     // 128 rows 66.3 / 63.0, 40 / 64 / 192 / 256 rows equal; 320 and 768 rows lose with 100)
+    // (mocr_decode_plan: the five "K slices".  Over the graph grid the N = 768 GEMMs reach two slabs at 1792 rows - 84 tiles x 2
+    // >= 150 -, return to four at 2048 - 96 x 2 < 200 - and stay at two from 2304)
     const int target = target_env ? target_env : (rows >= 2048 ? 200 : rows <= 128 ? 100 : 150);
     const int tile = dec_tile(rows);
     const int tiles = (N / tile) * ((rows + tile - 1) / tile);
@@ -1151,10 +1171,25 @@ static int pick_split(int N, int K, int kt, int rows, long long slab_cap_per_row
     return split;
 }
 
+// K slices of a decode-step GEMM [rows, N] = A [rows, K] W^T: by the batch's regime, so that a compacted batch keeps its sums
+// (the slab buffer holds 12288 floats per row whatever max_batch is, so the split does not depend on the engine's size)
+template <typename T>
+static int dec_split(const mocr_engine* e, int N, int K, int rows) {
+    return pick_split(N, K, 128 / (int)sizeof(T), e->rrows(rows), e->slab_cap / e->Bp);
+}
+// FC1 unsplit: bias + GELU in the GEMM's epilogue (EPI_BIAS_GELU) instead of one slab and a bias_gelu launch
+template <typename T>
+static bool dec_fc1_fused(const mocr_engine* e, int rows) { return dec_split<T>(e, e->F, e->D, rows) == 1; }
+// The LM head unsplit on a 64 / 128 tile: its epilogue reduces every N-tile to candidates (EPI_ARGMAX and its scored / masked
+// forms) - unless the caller wants the logits or the batch is a beam batch, which decode_step checks itself
+template <typename T>
+static bool dec_head_fused(const mocr_engine* e, int rows) {
+    return !(e->cfg.flags & MOCR_FLAG_NO_FUSED_ARGMAX) && tile_is(dec_launch_tile(e, rows), GemmKind::Tile) && dec_split<T>(e, e->V, e->D, rows) == 1;
+}
+
 template <typename T>
 int dec_gemm(mocr_engine* e, const char* name, const void* A, int lda, const void* W, int N, int K, int rows) {
-    const int kt = 128 / (int)sizeof(T);
-    const int split = pick_split(N, K, kt, e->rrows(rows), e->slab_cap / e->Bp);
+    const int split = dec_split<T>(e, N, K, rows);
     GemmCall c = gemm_call(name, A, lda, W, nullptr, e->slabs, N, rows, N, K, EPI_SLAB, dec_launch_tile(e, rows));
     c.split = split; c.slab_stride = (long long)e->Bp * N;
     gemm<T>(e, c);
@@ -1386,7 +1421,7 @@ void beam_finish_step(mocr_engine* e, const DecState& st, const DecMode& m, int 
     }
 }
 
-// non-temporal K/V loads from about 128 rows (see dec_attn_params)
+// non-temporal K/V loads from about 128 rows of the batch's regime (see dec_attn_params; mocr_decode_plan: field 22)
 static bool dec_attn_nt(const mocr_engine* e, int n) {
     static const int nt_rows = env_int("MOCR_ATTN_NT_ROWS", 128);
     return e->rrows(n) >= nt_rows;
@@ -1587,12 +1622,40 @@ struct QqtFamily {             // dec_qqt_kernel<BM>
     static constexpr int lds(const Args&) { return 160 * 1024; }      // the limit: a launch asks for QqtCfg<BM>::LDS (MOCR_QQT_LDS: more)
 };
 
-void launch_qqt(mocr_engine* e, const QqtParams& q, int n, int regime_rows) {
+static int qqt_block_rows(int regime_rows) {
     static const int bm64_rows = env_int("MOCR_QQT_BM64_ROWS", 1280);
-    const int bm = regime_rows <= bm64_rows ? 64 : 128;
+    return regime_rows <= bm64_rows ? 64 : 128;
+}
+// ... and the row count the decode step makes that choice by: the rows the launch has (the block shape does not touch a sum;
+// MOCR_NEUTRAL_BY_ROWS=0: the batch's regime)
+static int qqt_choice_rows(const mocr_engine* e, int n) {
+    static const int neutral_by_rows = env_int("MOCR_NEUTRAL_BY_ROWS", 2);
+    return neutral_by_rows ? n : e->rrows(n);
+}
+
+void launch_qqt(mocr_engine* e, const QqtParams& q, int n, int regime_rows) {
+    const int bm = qqt_block_rows(regime_rows);
     const int lds = bm == 64 ? QqtCfg<64>::LDS : env_int("MOCR_QQT_LDS", QQT_LDS);
     hipLaunchKernelGGL(find_form<QqtFamily>({bm}).kernel, dim3((n + bm - 1) / bm, 12), dim3(256), lds, e->stream, q);
     HIPCHECK(hipGetLastError());
+}
+
+// The latent block's query path, by the batch's regime.  dec_use_qqt: q and Qt in one launch (kernels_qqt.h) from 257 rows,
+// i.e. for every batch the product decodes on the latent path; dec_qt_tile: the tile of the head-batched Qt GEMM of the
+// two-launch path (128 from 1024 rows).  launch_latent_block launches by them and decode_plan reports them.
+static bool dec_use_qqt(const mocr_engine* e, int n) {
+    // fat batches: q and Qt in one launch (kernels_qqt.h), 37 us instead of 16 + 31 at 4096 rows; bit-identical to the
+    // two-launch path.  MOCR_DEC_QQT_ROWS = rows from which it is used (0 = never)
+    // (r04, tools/r04_qqt_rows_ab.sh, isolated batch, two launches / fused: 512 rows 136.2 / 134.9 ms, 768 rows 165.4 / 163.5, below
+    // 512 rows the two launches stay ahead: the switch moved from 1024 to 512 rows)
+    // (r04, 64-row blocks, tools/r04_qqt_rows_ab2.sh, two launches / fused: 288 rows 103.6 / 100.4 ms, 320 rows 105.0 / 101.5, 384 rows
+    // 107.7 / 104.6, 448 and 512 rows equal: every latent batch - 257 rows and up - takes the fused launch)
+    static const int qqt_rows = env_int("MOCR_DEC_QQT_ROWS", 257);
+    return qqt_rows > 0 && e->rrows(n) >= qqt_rows && e->D == 768 && e->H == 12 && !(e->cfg.flags & MOCR_FLAG_NO_FUSED_QQT);
+}
+static int dec_qt_tile(const mocr_engine* e, int n) {
+    static const int qttile_env = env_int("MOCR_DEC_QTTILE", 0);
+    return qttile_env ? qttile_env : (e->rrows(n) >= 1024 ? 128 : 64);      // Qt is output-write bound: fewer, fatter blocks
 }
 
 // q -> Qt -> latent attention -> ctx: the attention block of the latent path up to (not including)
@@ -1607,28 +1670,20 @@ void launch_latent_block(mocr_engine* e, const LatentBlockArgs& a) {
         c.hb = &hc;
         gemm<T>(e, c);
     };
-    // fat batches: q and Qt in one launch (kernels_qqt.h), 37 us instead of 16 + 31 at 4096 rows; bit-identical to the
-    // two-launch path.  MOCR_DEC_QQT_ROWS = rows from which it is used (0 = never)
-    // (r04, tools/r04_qqt_rows_ab.sh, isolated batch, two launches / fused: 512 rows 136.2 / 134.9 ms, 768 rows 165.4 / 163.5, below
-    // 512 rows the two launches stay ahead: the switch moved from 1024 to 512 rows)
-    // (r04, 64-row blocks, tools/r04_qqt_rows_ab2.sh, two launches / fused: 288 rows 103.6 / 100.4 ms, 320 rows 105.0 / 101.5, 384 rows
-    // 107.7 / 104.6, 448 and 512 rows equal: every latent batch - 257 rows and up - takes the fused launch)
-    static const int qqt_rows = env_int("MOCR_DEC_QQT_ROWS", 257);
-    if (qqt_rows > 0 && e->rrows(n) >= qqt_rows && D == 768 && e->H == 12 && !(e->cfg.flags & MOCR_FLAG_NO_FUSED_QQT)) {
+    if (dec_use_qqt(e, n)) {
         QqtParams q{};
         q.x = reinterpret_cast<const bf16_t*>(a.xin); q.wq = reinterpret_cast<const bf16_t*>(a.wq); q.bq = a.bq;
         q.wkT = reinterpret_cast<const bf16_t*>(a.wkT); q.qt = reinterpret_cast<bf16_t*>(a.qt);
         {
             ProfScope ps(e, "dec_qqt", 4.0 * n * D * D, (double)n * D * 2 + 2.0 * D * D * 2 + (double)n * e->H * D * 2);
-            static const int neutral_by_rows = env_int("MOCR_NEUTRAL_BY_ROWS", 2);
-            launch_qqt(e, q, n, neutral_by_rows ? n : e->rrows(n));
+            launch_qqt(e, q, n, qqt_choice_rows(e, n));
         }
         latent_attn(e, a);
         latent_ctx();
         return;
     }
-    static const int qtile = env_int("MOCR_DEC_QTILE", 64), qttile_env = env_int("MOCR_DEC_QTTILE", 0);
-    const int qttile = qttile_env ? qttile_env : (e->rrows(n) >= 1024 ? 128 : 64);      // Qt is output-write bound: fewer, fatter blocks
+    static const int qtile = env_int("MOCR_DEC_QTILE", 64);
+    const int qttile = dec_qt_tile(e, n);
     gemm<T>(e, gemm_call("gemm_dec_q", a.xin, D, a.wq, a.bq, a.q, D, n, D, D, EPI_BIAS, qtile));
     HeadBatch hq; hq.heads = e->H; hq.a_yoff = 64; hq.w_yoff = 64; hq.o_yoff = D; hq.b_yoff = 0; hq.ldw = D;
     GemmCall qt = gemm_call("gemm_dec_qt", a.q, D, a.wkT, e->w.zero_bias, a.qt, 16 * D, n, D, 64, EPI_BIAS, qttile);
@@ -1798,7 +1853,7 @@ void decode_step(mocr_engine* e, const DecState& st, const DecMode& m, int n, in
         }
         ns = dec_gemm<T>(e, "gemm_dec_proj", e->ctx_t, D, L.woc, D, D, n);
         dec_add_ln<T>(e, ns, D, L.boc, e->a_f32, L.ln2g, L.ln2b, e->c_f32, e->c_t, n, false);
-        if (pick_split(F, D, 128 / (int)sizeof(T), rn, e->slab_cap / e->Bp) == 1) {
+        if (dec_fc1_fused<T>(e, n)) {
             gemm<T>(e, gemm_call("gemm_dec_fc1", e->c_t, D, L.w1, L.b1, e->h_t, F, n, F, D, EPI_BIAS_GELU, dec_launch_tile(e, n)));
         } else {
             ns = dec_gemm<T>(e, "gemm_dec_fc1", e->c_t, D, L.w1, F, D, n);
@@ -1820,8 +1875,7 @@ void decode_step(mocr_engine* e, const DecState& st, const DecMode& m, int n, in
         return;
     }
     const int vt = dec_launch_tile(e, n);
-    if (!st.logits_out && !(e->cfg.flags & MOCR_FLAG_NO_FUSED_ARGMAX) && tile_is(vt, GemmKind::Tile) &&
-        pick_split(e->V, D, 128 / (int)sizeof(T), rn, e->slab_cap / e->Bp) == 1) {
+    if (!st.logits_out && dec_head_fused<T>(e, n)) {
         // (a scored batch also keeps every tile's sum of exp(logit - tile max): EPI_ARGMAX_LSE, same max / column; an
         // alternatives batch every tile's four best as well: EPI_TOPK; a constrained batch the masked form of either: EPI_*_M)
         LmHead lm;
@@ -1953,6 +2007,55 @@ static int graph_rows(int n, int max_batch) {
     }
     else q = 256;       // (r04: 512 until rows were compacted - a batch now passes through these row counts on its way down)
     return std::min(round_up(n, q), max_batch);
+}
+
+// What a greedy decode step of `rows` rows decides (the batch's regime is e->regime, 0 = rows) - from the helpers the step
+// itself launches through: use_smallm / use_latent, dec_tile / dec_launch_tile, dec_split (pick_split), dec_fc1_fused,
+// dec_head_fused, tile_launch (the ring), dec_use_qqt, qqt_block_rows, dec_qt_tile, dec_attn_nt, chunk_steps, graph_rows.
+// Nothing is launched and rows need not fit max_batch; mocr_decode_plan reports it.  The five GEMM entries say how the tile
+// kernel is launched for that shape at these rows whether or not this engine's path launches it (the small-batch path
+// launches none of them, the latent path no QKV GEMM): they depend on the dtype, the CUs and the flags, not on max_batch.
+struct DecGemmPlan { int split, ring, epi; };     // K slices, ring slots (2 / 4), epilogue (EPI_SLAB, EPI_BIAS_GELU, EPI_ARGMAX)
+struct DecPlan {
+    int path;                         // 0 small-batch (kernels_smallm.h), 1 classic attention, 2 latent attention
+    int regime_tile, launch_tile;     // the tile the split is chosen for (the regime's) / the tile the GEMMs are launched on
+    DecGemmPlan g[5];                 // QKV 2304 x 768, projections 768 x 768, FC1 3072 x 768, FC2 768 x 3072, vocabulary V x 768
+    bool qkv_tile_gemm;               // the step launches QKV as a tile GEMM (classic path only)
+    bool qqt; int qqt_bm;             // latent path: q and Qt in one launch, and its rows per block (0: two launches)
+    int qt_tile;                      // latent path, two launches: the Qt GEMM's tile (0: not launched)
+    bool attn_nt;                     // classic attention: non-temporal K/V loads
+    int chunk, graph_rows;            // steps per graph replay; the rows this count is rounded up to (<= max_batch)
+};
+// a test hook's regime: set for the hook's launches (or its plan), as the scheduler sets it around a batch's steps
+struct RegimeScope {
+    mocr_engine* e; int old;
+    RegimeScope(mocr_engine* e_, int r) : e(e_), old(e_->regime) { e->regime = r; }
+    ~RegimeScope() { e->regime = old; }
+};
+template <typename T>
+DecPlan decode_plan(const mocr_engine* e, int rows) {
+    const int D = e->D, F = e->F, V = e->V, kt = 128 / (int)sizeof(T), rn = e->rrows(rows);
+    DecPlan pl{};
+    pl.path = (sizeof(T) == 2 && e->use_smallm(rn)) ? 0 : e->use_latent(rn) ? 2 : 1;
+    pl.regime_tile = dec_tile(rn);
+    pl.launch_tile = dec_launch_tile(e, rows);
+    auto launched = [&](int N, int K, int split, int epi) {
+        return DecGemmPlan{split, tile_launch(e, rows, N, pl.launch_tile, split, 1, K / split / kt).ring, epi};
+    };
+    auto slabs = [&](int N, int K) { return launched(N, K, dec_split<T>(e, N, K, rows), EPI_SLAB); };
+    pl.g[0] = slabs(3 * D, D);
+    pl.g[1] = slabs(D, D);
+    pl.g[2] = dec_fc1_fused<T>(e, rows) ? launched(F, D, 1, EPI_BIAS_GELU) : slabs(F, D);
+    pl.g[3] = slabs(D, F);
+    pl.g[4] = dec_head_fused<T>(e, rows) ? launched(V, D, 1, EPI_ARGMAX) : slabs(V, D);
+    pl.qkv_tile_gemm = pl.path == 1;
+    pl.qqt = pl.path == 2 && dec_use_qqt(e, rows);
+    pl.qqt_bm = pl.qqt ? qqt_block_rows(qqt_choice_rows(e, rows)) : 0;
+    pl.qt_tile = (pl.path == 2 && !pl.qqt) ? dec_qt_tile(e, rows) : 0;
+    pl.attn_nt = pl.path != 2 && dec_attn_nt(e, rows);
+    pl.chunk = chunk_steps(rows);
+    pl.graph_rows = graph_rows(rows, e->cfg.max_batch);
+    return pl;
 }
 
 // The buffers of the token alternatives, for the bound lane: allocated by the first batch that needs them (under the engine
@@ -4008,6 +4111,63 @@ int mocr_encoder_plan(mocr_engine* e, int32_t n, int32_t out[10]) {
     });
 }
 
+int mocr_decode_plan(mocr_engine* e, int32_t rows, int32_t regime_rows, int32_t out[MOCR_DECODE_PLAN_FIELDS]) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (!e->committed) throw ArgError{"mocr_decode_plan: weights not committed", MOCR_ERR_ARG};
+        if (!out || rows < 1 || regime_rows < 0) throw ArgError{"mocr_decode_plan: bad argument", MOCR_ERR_ARG};
+        DecPlan pl{};
+        {
+            RegimeScope rs(e, regime_rows);
+            dispatch(e, [&](auto tag) { pl = decode_plan<decltype(tag)>(e, rows); });
+        }
+        int32_t v[MOCR_DECODE_PLAN_FIELDS] = {pl.path, pl.regime_tile, pl.launch_tile};
+        for (int i = 0; i < 5; ++i) { v[3 + 3 * i] = pl.g[i].split; v[4 + 3 * i] = pl.g[i].ring; v[5 + 3 * i] = pl.g[i].epi; }
+        const int32_t tail[7] = {pl.qkv_tile_gemm, pl.qqt, pl.qqt_bm, pl.qt_tile, pl.attn_nt, pl.chunk, pl.graph_rows};
+        memcpy(v + 18, tail, sizeof(tail));
+        static_assert(MOCR_DECODE_PLAN_FIELDS == 25, "mocr_decode_plan's layout");
+        memcpy(out, v, sizeof(v));
+    });
+}
+
+int mocr_op_gemm_args(mocr_engine* e, const mocr_gemm_args* a) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!a || a->struct_size != (int32_t)sizeof(mocr_gemm_args)) throw ArgError{"mocr_op_gemm_args: bad struct_size", MOCR_ERR_ARG};
+        const int epi = a->epilogue;
+        if (epi == EPI_PATCH || epi == EPI_ARGMAX || epi == EPI_ARGMAX_LSE || epi == EPI_TOPK)
+            throw ArgError{"EPI_PATCH / EPI_ARGMAX are not exposed through mocr_op_gemm_args (EPI_ARGMAX: mocr_op_gemm_argmax)", MOCR_ERR_ARG};
+        const int esz = e->cfg.dtype == MOCR_BF16 ? 2 : 4;
+        const int lda = a->lda ? a->lda : a->K, ldo = a->ldo ? a->ldo : a->N;
+        if (!a->A || !a->W || !a->out || a->M < 1 || a->N < 1 || a->K < 1 || a->split_k < 1 || a->group_n < 0 ||
+            (epi != EPI_SLAB && !a->bias) || (epi == EPI_BIAS_RESID && !a->resid))
+            throw ArgError{"mocr_op_gemm_args: bad argument", MOCR_ERR_ARG};
+        if (!tile_is(a->tile, GemmKind::Tile)) throw ArgError{"mocr_op_gemm_args: the tile GEMM only (tile 64 or 128)", MOCR_ERR_ARG};
+        // rows are fetched and stored in 16-byte pieces
+        if (lda < a->K || (lda * esz) % 16 || ldo < a->N || ldo % 4)
+            throw ArgError{"mocr_op_gemm_args: lda >= K and ldo >= N, rows 16-byte aligned", MOCR_ERR_ARG};
+        const long long dense = (long long)(a->M - 1) * ldo + a->N;       // elements one slab spans
+        const long long slab_stride = a->slab_stride ? a->slab_stride : (long long)a->M * ldo;
+        if (epi == EPI_SLAB && (slab_stride < dense || (slab_stride & 3)))
+            throw ArgError{"mocr_op_gemm_args: slab_stride must hold a slab and be a multiple of 4", MOCR_ERR_ARG};
+        GemmCall c = gemm_call("op_gemm", a->A, lda, a->W, a->bias, a->out, ldo, a->M, a->N, a->K, epi, a->tile);
+        c.resid = a->resid; c.split = a->split_k; c.slab_stride = slab_stride; c.group_n = a->group_n;
+        if (e->cfg.dtype == MOCR_BF16) gemm<bf16_t>(e, c); else gemm<float>(e, c);
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_last_tile_launch(mocr_engine* e, int32_t out[4]) {
+    return guarded(e, [&] {
+        if (!out) throw ArgError{"mocr_last_tile_launch: null pointer", MOCR_ERR_ARG};
+        const int32_t v[4] = {g_last_tile.bm, g_last_tile.ring, g_last_tile.blocks, g_last_tile.split};
+        memcpy(out, v, sizeof(v));
+    });
+}
+
 int mocr_op_latent_attention(mocr_engine* e, const void* d_qt, const void* d_x, void* d_out, int32_t n, int32_t len,
                              int64_t x_batch_stride) {
     return guarded(e, [&] {
@@ -4417,11 +4577,7 @@ int mocr_op_latent_block(mocr_engine* e, const mocr_latent_args* a) {
         b.step = b.self ? a->step : nullptr; b.rowmap = a->rowmap; b.sx = e->fp8attn ? a->sx : 0.f;
         b.q = a->q; b.qt = a->qt; b.et = a->et; b.ctx = a->ctx;
         // the choices are made by the batch's regime, as in the decode step (which sets it around a batch's steps)
-        struct RegimeScope {
-            mocr_engine* e; int old;
-            RegimeScope(mocr_engine* e_, int r) : e(e_), old(e_->regime) { e->regime = r; }
-            ~RegimeScope() { e->regime = old; }
-        } rs(e, a->regime_rows);
+        RegimeScope rs(e, a->regime_rows);
         launch_latent_block(e, b);
         HIPCHECK(hipStreamSynchronize(e->stream));
     });

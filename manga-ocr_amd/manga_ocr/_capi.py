@@ -61,6 +61,15 @@ class MocrSmallmArgs(C.Structure):
                                    "resid_g", "resid_b", "out")]
 
 
+class MocrGemmArgs(C.Structure):
+    """include/mocr.h: mocr_gemm_args"""
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "M", "N", "K", "epilogue", "tile", "split_k", "lda", "ldo", "group_n")] + \
+        [("slab_stride", C.c_int64)] + [(n, C.c_void_p) for n in ("A", "W", "bias", "out", "resid")]
+
+
+DECODE_PLAN_FIELDS = 25   # MOCR_DECODE_PLAN_FIELDS
+
+
 class MocrLatentArgs(C.Structure):
     """include/mocr.h: mocr_latent_args"""
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "self", "n", "regime_rows", "fixed_len")] + \
@@ -150,6 +159,9 @@ SYMBOLS = {
     "mocr_op_embed": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     "mocr_op_layernorm_slab": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, C.c_int32]),
     "mocr_encoder_plan": (C.c_int, [_P, C.c_int32, _P]),
+    "mocr_decode_plan": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    "mocr_op_gemm_args": (C.c_int, [_P, C.POINTER(MocrGemmArgs)]),
+    "mocr_last_tile_launch": (C.c_int, [_P, _P]),
     "mocr_op_latent_attention": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64]),
     "mocr_op_quant_fp8": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float]),
     "mocr_op_latent_attention_fp8": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_float]),

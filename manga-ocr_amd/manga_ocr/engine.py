@@ -541,6 +541,31 @@ class Engine:
         self._check(self.lib.mocr_encoder_plan(self._h, int(n), _ptr(out)))
         return dict(zip(self.ENCODER_PLAN_FIELDS, (int(v) for v in out)))
 
+    DECODE_PLAN_GEMMS = ("qkv", "proj", "fc1", "fc2", "vocab")
+    DECODE_PLAN_FIELDS = ("path", "regime_tile", "launch_tile") + \
+        tuple(f"{g}_{f}" for g in DECODE_PLAN_GEMMS for f in ("split", "ring", "epi")) + \
+        ("qkv_tile_gemm", "fused_query", "query_block_rows", "qt_tile", "attn_nt", "chunk_steps", "graph_rows")
+    DECODE_PATHS = ("small-batch", "classic", "latent")
+
+    def decode_plan(self, rows: int, regime_rows: int = 0) -> dict:
+        """What a greedy decode step of ``rows`` rows decides, ``regime_rows`` being the rows its batch started with (0: the
+        same), by name (include/mocr.h, mocr_decode_plan); ``path`` as one of DECODE_PATHS.  Nothing is launched."""
+        out = np.zeros(_capi.DECODE_PLAN_FIELDS, dtype=np.int32)
+        self._check(self.lib.mocr_decode_plan(self._h, int(rows), int(regime_rows), _ptr(out)))
+        pl = dict(zip(self.DECODE_PLAN_FIELDS, (int(v) for v in out)))
+        pl["path"] = self.DECODE_PATHS[pl["path"]]
+        return pl
+
+    def op_gemm_args(self, **kw) -> None:
+        """The 64 / 128 tile GEMM; keyword arguments are the fields of mocr_gemm_args (buffers as device tensors or addresses)."""
+        self._check(self.lib.mocr_op_gemm_args(self._h, self._args(_capi.MocrGemmArgs, kw)))
+
+    def last_tile_launch(self) -> dict:
+        """The calling thread's last tile-GEMM launch (include/mocr.h, mocr_last_tile_launch)."""
+        out = np.zeros(4, dtype=np.int32)
+        self._check(self.lib.mocr_last_tile_launch(self._h, _ptr(out)))
+        return dict(zip(("tile", "ring", "blocks", "split"), (int(v) for v in out)))
+
     def op_latent_attention(self, d_qt, d_x, d_out, n, length, x_batch_stride) -> None:
         self._check(self.lib.mocr_op_latent_attention(self._h, _ptr(d_qt), _ptr(d_x), _ptr(d_out), n, length, x_batch_stride))
 
