@@ -652,6 +652,12 @@ int mocr_op_enc_expand(mocr_engine* e, void* d_enc, const int32_t* d_src_of_row,
  * [rows][T][197] = the head-mean map a.  Nothing behind a row's 197 keys is read. */
 int mocr_op_attn_positions(mocr_engine* e, const void* d_q, const void* d_k, const int32_t* d_len, int32_t rows, int32_t T,
                            float* d_out_pos, float* d_out_map);
+/* ... in its gathered-query form (token positions of beam hypotheses): plus d_trail, uint8 [rows][trail_ld] with
+ * trail_ld >= T + 1, and K (1 .. MOCR_MAX_BEAMS; rows a multiple of it).  The query of position p of row r is read from row
+ * (r / K) * K + min(d_trail[r][p + 1], K - 1), position p, of d_q; keys, lengths and outputs stay by row r.  With d_trail null
+ * it is mocr_op_attn_positions. */
+int mocr_op_attn_positions_gathered(mocr_engine* e, const void* d_q, const void* d_k, const int32_t* d_len, int32_t rows, int32_t T,
+                                    float* d_out_pos, float* d_out_map, const uint8_t* d_trail, int32_t trail_ld, int32_t K);
 /* The LM head's fused argmax GEMM (tile 64 or 128, not split): d_cand_val / d_cand_idx [M][N / tile] = per row and N-tile
  * the largest acc + bias and its column (the lowest column on a tie).  dA holds M rounded up to the tile. */
 int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
@@ -798,7 +804,8 @@ int mocr_profile_get(mocr_engine* e, mocr_kernel_stat* out, int32_t cap, int32_t
  * equals one already in the set goes behind it.  (torch.topk promises no order, so nothing should rely on an exact tie.)
  * Beam k of crop c is decode row c K + k: a request of n crops is n K rows over n encodings (one encoder pass per crop),
  * so n * K <= max_batch.  A beam request may carry one token set per crop and ask for the hypotheses' token scores (the
- * *_beam_tokens calls below); it carries no prefixes, positions, alternatives or source array. */
+ * *_beam_tokens calls below) and token positions (the *_beam_positions calls); it carries no prefixes, alternatives or
+ * source array. */
 #define MOCR_MAX_BEAMS 4
 typedef struct mocr_beam_config {
     int32_t num_beams;              /* K: 2 .. MOCR_MAX_BEAMS */
@@ -854,12 +861,40 @@ int mocr_recognize_gray_host_beam_tokens(mocr_engine* e, const uint8_t* gray, in
 int mocr_recognize_device_beam_tokens(mocr_engine* e, const void* d_gray, int32_t n, const mocr_beam_config* beam, void* d_out_ids,
                                       void* d_out_len, void* d_out_score, void* d_out_logp, const int32_t* sets);
 
+/* Beam search with token positions: the *_beam_tokens calls plus
+ *   out_pos   [n][K][max_len][MOCR_POSITION_FIELDS] float32, laid out like out_ids (a device pointer for the device twin),
+ *             nullable.
+ * With out_pos null they ARE the *_beam_tokens calls.
+ * TOKEN POSITIONS of hypothesis (c, j) of length len: for 1 <= t < len the five fields of "token positions" above, computed
+ * from a_vec - the last decoder layer's LayerNorm-1 output - of the step that appended ids[t], taken on the beam the
+ * hypothesis descends from at that step (transformers' beam_indices), over the keys of crop c's encoder rows.  That is
+ * exactly what a teacher-forced greedy row over the hypothesis' own ids gives.  EOS has a position like any other token.
+ * Zeros are written for t = 0 and t >= len, for every position of an empty slot (len 0) and of a sliver region.
+ * Asking for positions moves no id, length, sequence score or token score, bit for bit, and a beam batch in which nobody
+ * asks launches exactly what it launched before.  How: the decode steps record a_vec by row, as the greedy positions do;
+ * the selection keeps, beside ids and the finished set, the group-relative index of the beam that ran every step (one
+ * byte per token); the deferred pass behind the batch gathers each hypothesis' queries through that trail. */
+int mocr_recognize_images_beam_positions(mocr_engine* e, const mocr_image* images, int32_t n, const mocr_beam_config* beam,
+                                         int32_t* out_ids, int32_t* out_len, float* out_score, float* out_logp, const int32_t* sets,
+                                         float* out_pos);
+int mocr_recognize_regions_beam_positions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                          int32_t n_regions, const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len,
+                                          float* out_score, float* out_logp, const int32_t* sets, float* out_pos);
+int mocr_recognize_gray_host_beam_positions(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override,
+                                            const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len, float* out_score,
+                                            float* out_logp, const int32_t* sets, float* out_pos);
+int mocr_recognize_device_beam_positions(mocr_engine* e, const void* d_gray, int32_t n, const mocr_beam_config* beam, void* d_out_ids,
+                                         void* d_out_len, void* d_out_score, void* d_out_logp, const int32_t* sets, void* d_out_pos);
+
 /* Bytes of beam state this engine holds, over its lanes (test hook): 0 until a lane runs its first beam batch - creating an
  * engine and greedy calls of any kind allocate none of it. */
 int64_t mocr_beam_state_bytes(mocr_engine* e);
 /* ... and of the token form's two histories, which mocr_beam_state_bytes does not count: 0 until a lane runs its first beam
  * batch that asks for token scores or brings a set other than MOCR_TOKEN_SET_ALL. */
 int64_t mocr_beam_token_state_bytes(mocr_engine* e);
+/* ... and of the two beam-index trails, which neither of the two counts: 0 until a lane runs its first beam batch that asks
+ * for token positions.  (The buffers of the token positions themselves are those of the greedy *_positions calls.) */
+int64_t mocr_beam_position_state_bytes(mocr_engine* e);
 /* The first n entries of a lane's decode slot -> row map as its last batch left it (test hook; all lanes idle first): behind
  * a compacted beam batch the K rows of a crop still sit in K neighbouring slots, in beam order, from a slot that is a
  * multiple of K. */
@@ -876,6 +911,14 @@ int mocr_op_beam_select(mocr_engine* e, const mocr_token_args* a, const mocr_bea
 int mocr_op_beam_select_tokens(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score,
                                int32_t* d_parent, int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open,
                                float* d_beam_logp, float* d_hyp_logp, const uint32_t* d_tok_mask, const int32_t* d_set_of_row);
+/* ... in its trail form: plus d_beam_trail / d_hyp_trail, uint8 [rows][ids_ld] (both or neither).  d_beam_trail[row][t],
+ * t >= 1, is the beam 0 .. K - 1 of the crop's group whose row ran the step that appended ids[row][t]; it moves with ids,
+ * and the entry of the token a step appends is the candidate's parent.  d_hyp_trail moves with d_hyp_ids, 0 behind a
+ * hypothesis' length.  With both null it is mocr_op_beam_select_tokens. */
+int mocr_op_beam_select_positions(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score,
+                                  int32_t* d_parent, int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open,
+                                  float* d_beam_logp, float* d_hyp_logp, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
+                                  uint8_t* d_beam_trail, uint8_t* d_hyp_trail);
 /* The cache reorder behind it: d_cache viewed as [layers][rows][segs][positions][pos_bytes] through byte strides; for
  * every group of K slots whose crop is live (d_finished[rowmap[g K]] == 0), row rowmap[g K + k] <- row
  * rowmap[g K + d_parent[rowmap[g K + k]]], bytes 0 .. d_step[g K] * pos_bytes - 1 of every (layer, segment).  max_pos bounds

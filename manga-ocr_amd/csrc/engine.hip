@@ -157,6 +157,8 @@ struct LaneCtx {
     // ... and its token form: allocated by the first beam batch that asks for token scores or brings a token set
     // (ensure_beam_token_buffers); the rows' sets are set_of_row
     float *beam_logp = nullptr, *hyp_logp = nullptr;    // [Bp][max_len]
+    // ... and its trail form: allocated by the first beam batch that asks for token positions (ensure_beam_position_buffers)
+    uint8_t *beam_trail = nullptr, *hyp_trail = nullptr;    // [Bp][max_len]
     float *x_f32 = nullptr, *a_f32 = nullptr, *c_f32 = nullptr;
     float* ln_stats = nullptr;                      // small-batch path: (mean, rstd) per row of the three pre-LayerNorm sums, [3][Bp][2]
     void *x_t = nullptr, *a_t = nullptr, *c_t = nullptr, *ctx_t = nullptr, *h_t = nullptr, *z_t = nullptr;
@@ -216,6 +218,7 @@ struct DecMode {
     bool ngram = false;             // a row has no_repeat_ngram_size > 0: the masks are the per-row ones (row_mask through row_ident)
                                     // and the token kernel is the NGRAM one, which rebuilds them
     bool positions = false;         // a job asked for token positions: the steps record pos_hist, finish_batch runs the deferred pass
+                                    // (a beam batch too: its selection then also keeps the beam-index trails the pass gathers by)
     bool prefix = false;            // a row has a forced prefix: the steps run scored and masked (level >= 1, mask; unconstrained rows read
                                     // set 0), the LM head also leaves the forced column's value and the token kernel stores the forced token
     bool beam = false;              // a beam-search batch (all of its jobs, with one configuration): the steps end in the selection and
@@ -250,7 +253,10 @@ static DecMode mode_of(const std::vector<Job>& jobs) {
     // scores and sets are the selection's business alone (the token form), not the LM head's.
     if (!jobs.empty() && jobs.front().beam.num_beams > 0) {
         m.beam = true; m.beam_cfg = jobs.front().beam;
-        for (const Job& j : jobs) m.beam_tokens = m.beam_tokens || j.out_logp || !j.sets.empty();
+        for (const Job& j : jobs) {
+            m.beam_tokens = m.beam_tokens || j.out_logp || !j.sets.empty();
+            m.positions = m.positions || j.out_pos;
+        }
         return m;
     }
     for (const Job& j : jobs) {
@@ -1332,9 +1338,10 @@ void dec_token(mocr_engine* e, const DecState& st, int nslab, int n, int ncand =
 }
 
 // ---- beam search: the selection and the cache reorder that end a beam step (kernels_beam.h) ----
-static BeamState make_beam_state(mocr_engine* e, const mocr_beam_config& c, bool tokens) {
+static BeamState make_beam_state(mocr_engine* e, const mocr_beam_config& c, bool tokens, bool trails) {
     BeamState bs{};
     if (tokens) { bs.beam_logp = e->beam_logp; bs.hyp_logp = e->hyp_logp; bs.tok_mask = e->tok_table; bs.set_of_row = e->set_of_row; }
+    if (trails) { bs.beam_trail = e->beam_trail; bs.hyp_trail = e->hyp_trail; }
     bs.beam_score = e->beam_score; bs.parent = e->beam_parent;
     bs.hyp_ids = e->hyp_ids; bs.hyp_len = e->hyp_len; bs.hyp_score = e->hyp_score; bs.heuristic_open = e->heuristic_open;
     bs.length_penalty = c.length_penalty; bs.early_stopping = c.early_stopping; bs.ngram = c.no_repeat_ngram_size;
@@ -1357,13 +1364,23 @@ void launch_beam_select(mocr_engine* e, const DecState& st, const BeamState& bs,
     const bool tok = bs.beam_logp || bs.hyp_logp || bs.tok_mask || bs.set_of_row;
     if ((bs.beam_logp == nullptr) != (bs.hyp_logp == nullptr) || (bs.tok_mask == nullptr) != (bs.set_of_row == nullptr))
         throw ArgError{"beam_select: the two token histories, and the set table with the rows' sets, come in pairs", MOCR_ERR_ARG};
-    switch (K * 2 + (tok ? 1 : 0)) {
-        case 4: launch(beam_select_kernel<T, 2>); break;
-        case 6: launch(beam_select_kernel<T, 3>); break;
-        case 8: launch(beam_select_kernel<T, 4>); break;
-        case 5: launch(beam_select_kernel<T, 2, true>); break;
-        case 7: launch(beam_select_kernel<T, 3, true>); break;
-        case 9: launch(beam_select_kernel<T, 4, true>); break;
+    // ... and the trail form when it carries the two trails (a batch that records token positions)
+    const bool trail = bs.beam_trail || bs.hyp_trail;
+    if ((bs.beam_trail == nullptr) != (bs.hyp_trail == nullptr))
+        throw ArgError{"beam_select: the two trails come as a pair", MOCR_ERR_ARG};
+    switch (K * 4 + (trail ? 2 : 0) + (tok ? 1 : 0)) {
+        case 8: launch(beam_select_kernel<T, 2>); break;
+        case 12: launch(beam_select_kernel<T, 3>); break;
+        case 16: launch(beam_select_kernel<T, 4>); break;
+        case 9: launch(beam_select_kernel<T, 2, true>); break;
+        case 13: launch(beam_select_kernel<T, 3, true>); break;
+        case 17: launch(beam_select_kernel<T, 4, true>); break;
+        case 10: launch(beam_select_kernel<T, 2, false, true>); break;
+        case 14: launch(beam_select_kernel<T, 3, false, true>); break;
+        case 18: launch(beam_select_kernel<T, 4, false, true>); break;
+        case 11: launch(beam_select_kernel<T, 2, true, true>); break;
+        case 15: launch(beam_select_kernel<T, 3, true, true>); break;
+        case 19: launch(beam_select_kernel<T, 4, true, true>); break;
         default: throw ArgError{"num_beams must be 2 .. 4", MOCR_ERR_ARG};
     }
     HIPCHECK(hipGetLastError());
@@ -1401,7 +1418,7 @@ void beam_finish_step(mocr_engine* e, const DecState& st, const DecMode& m, int 
     a.cache8 = (lat && e->fp8attn) ? e->x8cache : nullptr;
     a.inv8 = (lat && e->fp8attn) ? 1.0f / e->w.sx_self[0] : 0.f;
     a.cstride = (long long)e->cfg.max_len * e->D;
-    launch_beam_select<T>(e, st, make_beam_state(e, m.beam_cfg, m.beam_tokens), a, n, K);
+    launch_beam_select<T>(e, st, make_beam_state(e, m.beam_cfg, m.beam_tokens, m.positions), a, n, K);
     // `t` bounds the step index of this launch from above only when it is exact (eager steps).  A captured graph passes
     // t = t_hi - 1 for every step of its bucket (decode_graph), and the bucket's last device step is t_hi itself
     // (t0 + steps <= 32 * bucket): behind it `step` is t_hi + 1 = t + 2 positions.  The grid is sized for that; the kernel
@@ -2142,6 +2159,9 @@ template <typename T>
 void launch_attn_positions(mocr_engine* e, const PosParams& p, int rows) {
     if (e->S != POS_KEYS || e->D != 768 || e->H != 12 || e->G != 14)
         throw ArgError{"token positions: a 14 x 14 patch grid, 12 heads of 64 only", MOCR_ERR_UNSUPPORTED};
+    // the gathered-query form reads the queries of a row's whole group of K, and entry p + 1 <= T of its trail
+    if (p.trail && (p.K < 1 || p.K > MOCR_MAX_BEAMS || rows % p.K || p.trail_ld < (long long)p.T + 1))
+        throw ArgError{"token positions: the gathered form takes whole groups of K <= 4 rows and a trail of T + 1 entries", MOCR_ERR_ARG};
     if (rows < 1 || p.T < 1) return;
     ProfScope ps(e, "attn_positions", 2.0 * rows * p.T * POS_KEYS * 768, ((double)rows * POS_KEYS + (double)rows * p.T) * 768 * sizeof(T));
     hipLaunchKernelGGL((attn_positions_kernel<T>), dim3((p.T + 15) / 16, rows), dim3(64), 0, e->stream, p);
@@ -2151,6 +2171,8 @@ void launch_attn_positions(mocr_engine* e, const PosParams& p, int rows) {
 // The deferred pass of a finished batch, on its lane's stream: per chunk of rows the layer's keys K = ENC Wk^T + bk (the latent
 // path never builds CKV, so every path computes them here) and queries q = hist Wq^T + bq, both on gemm_kernel, then the
 // positions kernel.  Row r's recorded position p holds the step that emitted token p + 1: the outputs start one position in.
+// A beam batch: the rows of the outputs are the finished hypotheses - their lengths, and their queries
+// gathered through hyp_trail from the rows that ran their steps, which lie in the same chunk: chunks are whole groups of K.
 template <typename T>
 void run_positions(mocr_engine* e, Lane& L) {
     // (HL: the batch's generate(max_length) - its rows were recorded HL positions apart, so the query GEMM covers no more than
@@ -2159,7 +2181,10 @@ void run_positions(mocr_engine* e, Lane& L) {
     const DecLayerW& W = e->w.dec[l];
     const char* const wk = reinterpret_cast<const char*>(e->w.wckv) + (size_t)(2 * l) * D * D * sizeof(T);
     const float* const bk = e->w.bckv + (size_t)(2 * l) * D;
-    const int R = pos_chunk_rows(e);
+    const bool beam = L.mode.beam;
+    const int K = beam ? L.mode.beam_cfg.num_beams : 1;
+    const int R = pos_chunk_rows(e) / K * K;
+    if (R < K) throw ArgError{"token positions: the scratch of the deferred pass holds no whole beam group", MOCR_ERR_UNSUPPORTED};
     for (int r0 = 0; r0 < L.n; r0 += R) {
         const int rows = std::min(R, L.n - r0);
         gemm<T>(e, gemm_call("gemm_pos_k", reinterpret_cast<const char*>(e->ENC) + (size_t)r0 * S * D * sizeof(T), D, wk, bk, e->pos_k, D,
@@ -2169,7 +2194,8 @@ void run_positions(mocr_engine* e, Lane& L) {
         PosParams p{};
         p.q = e->pos_q; p.q_row_stride = (long long)HL * D;
         p.k = e->pos_k; p.k_row_stride = (long long)S * D;
-        p.len = e->len + r0; p.len_bias = -1; p.T = L.max_len - 1;
+        p.len = (beam ? e->hyp_len : e->len) + r0; p.len_bias = -1; p.T = L.max_len - 1;
+        if (beam) { p.trail = e->hyp_trail + (size_t)r0 * ML; p.trail_ld = ML; p.K = K; }
         p.out_pos = e->pos_out + ((size_t)r0 * ML + 1) * MOCR_POSITION_FIELDS; p.pos_row_stride = (long long)ML * MOCR_POSITION_FIELDS;
         launch_attn_positions<T>(e, p, rows);
     }
@@ -2210,6 +2236,14 @@ static void ensure_beam_token_buffers(mocr_engine* e) {
     const size_t Bp = (size_t)e->Bp;
     e->beam_logp = e->dalloc<float>(Bp * e->cfg.max_len);
     e->hyp_logp = e->dalloc<float>(Bp * e->cfg.max_len);
+}
+
+// The trail form's two histories, for the bound lane: allocated by the first beam batch that asks for token positions.
+static void ensure_beam_position_buffers(mocr_engine* e) {
+    if (e->hyp_trail) return;
+    const size_t Bp = (size_t)e->Bp;
+    e->beam_trail = e->dalloc<uint8_t>(Bp * e->cfg.max_len);
+    e->hyp_trail = e->dalloc<uint8_t>(Bp * e->cfg.max_len);
 }
 
 static void launch_enc_expand(mocr_engine* e, const void* in, void* out, const int* d_src_of_row, int n_src, int rows) {
@@ -2338,9 +2372,10 @@ void start_batch(mocr_engine* e, Lane& L) {
             ensure_beam_token_buffers(e);
             upload_per_row(e, L, L.h_sets, &Job::sets, MOCR_TOKEN_SET_ALL, e->set_of_row);
         }
+        if (m.positions) ensure_beam_position_buffers(e);
         ProfScope ps(e, "beam_init", 0, (double)L.np * e->cfg.max_len * 4);
-        hipLaunchKernelGGL(beam_init_kernel, dim3(L.np), dim3(64), 0, e->stream, make_beam_state(e, m.beam_cfg, m.beam_tokens), m.beam_cfg.num_beams, L.np,
-                           e->cfg.max_len, e->cfg.pad_id);
+        hipLaunchKernelGGL(beam_init_kernel, dim3(L.np), dim3(64), 0, e->stream, make_beam_state(e, m.beam_cfg, m.beam_tokens, m.positions),
+                           m.beam_cfg.num_beams, L.np, e->cfg.max_len, e->cfg.pad_id);
         HIPCHECK(hipGetLastError());
     }
     L.t = 0; L.steps = L.max_len - 1; L.chunk = 0;
@@ -2361,6 +2396,10 @@ void finish_batch(mocr_engine* e, Lane& L) {
             HIPCHECK(hipMemcpyAsync(j.out_score, e->hyp_score + row0, (size_t)j.n * sizeof(float), kind, e->stream));
             if (j.out_logp)         // (a batch with such a job ran the token form)
                 HIPCHECK(hipMemcpyAsync(j.out_logp, e->hyp_logp + (size_t)row0 * e->cfg.max_len, (size_t)j.n * e->cfg.max_len * sizeof(float), kind, e->stream));
+            if (j.out_pos) {        // (a batch with such a job kept the trails and ran the deferred pass over its hypotheses)
+                const size_t ld = (size_t)e->cfg.max_len * MOCR_POSITION_FIELDS;
+                HIPCHECK(hipMemcpyAsync(j.out_pos, e->pos_out + row0 * ld, j.n * ld * sizeof(float), kind, e->stream));
+            }
             row0 += j.n;
             continue;
         }
@@ -3809,10 +3848,11 @@ int mocr_recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_pa
 
 // ---- beam search: the four source kinds.  A request of n crops is n K decode rows over n encodings - the shared-encodings
 // request with source[c K + k] = c - plus the configuration and the score output; the checks come before any work.
-// The *_beam_tokens twins add out_logp [n][K][max_len] = [rows][max_len] and one set handle per crop, expanded to its K rows.
+// The *_beam_tokens twins add out_logp [n][K][max_len] = [rows][max_len] and one set handle per crop, expanded to its K rows;
+// the *_beam_positions twins add out_pos [n][K][max_len][MOCR_POSITION_FIELDS] to those.
 struct BeamCall { std::vector<int32_t> source, sets; Request req; int rows = 0; };
 static int beam_call(mocr_engine* e, const mocr_beam_config* beam, int32_t n, void* out_score, BeamCall& bc, void* out_logp = nullptr,
-                     const int32_t* sets = nullptr) {
+                     const int32_t* sets = nullptr, void* out_pos = nullptr) {
     return guarded(e, [&] {
         if (!beam || beam->num_beams < 2 || beam->num_beams > MOCR_MAX_BEAMS) throw ArgError{"num_beams must be 2 .. MOCR_MAX_BEAMS (4)", MOCR_ERR_ARG};
         if (beam->early_stopping < 0 || beam->early_stopping > 2) throw ArgError{"early_stopping must be 0 (false), 1 (true) or 2 (never)", MOCR_ERR_ARG};
@@ -3828,6 +3868,7 @@ static int beam_call(mocr_engine* e, const mocr_beam_config* beam, int32_t n, vo
         bc.req.source = bc.source.data(); bc.req.n_images = n;
         bc.req.beam = beam; bc.req.out_score = static_cast<float*>(out_score);
         bc.req.out_logp = static_cast<float*>(out_logp);
+        bc.req.out_pos = static_cast<float*>(out_pos);
         if (sets) {
             bc.sets.resize((size_t)bc.rows);
             for (int i = 0; i < bc.rows; ++i) bc.sets[i] = sets[i / K];
@@ -3863,6 +3904,36 @@ int mocr_recognize_device_beam_tokens(mocr_engine* e, const void* d_gray, int32_
                                       void* d_out_len, void* d_out_score, void* d_out_logp, const int32_t* sets) {
     BeamCall bc;
     if (const int rc = beam_call(e, beam, n, d_out_score, bc, d_out_logp, sets)) return rc;
+    return recognize_device(e, d_gray, bc.rows, d_out_ids, d_out_len, bc.req);
+}
+
+int mocr_recognize_images_beam_positions(mocr_engine* e, const mocr_image* images, int32_t n, const mocr_beam_config* beam, int32_t* out_ids,
+                                         int32_t* out_len, float* out_score, float* out_logp, const int32_t* sets, float* out_pos) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, out_score, bc, out_logp, sets, out_pos)) return rc;
+    return recognize_images(e, images, bc.rows, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_regions_beam_positions(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                          int32_t n_regions, const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len,
+                                          float* out_score, float* out_logp, const int32_t* sets, float* out_pos) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n_regions, out_score, bc, out_logp, sets, out_pos)) return rc;
+    return recognize_regions(e, pages, n_pages, regions, n_regions, bc.rows, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_gray_host_beam_positions(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override,
+                                            const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len, float* out_score,
+                                            float* out_logp, const int32_t* sets, float* out_pos) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, out_score, bc, out_logp, sets, out_pos)) return rc;
+    return recognize_gray_host(e, gray, bc.rows, max_len_override, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_device_beam_positions(mocr_engine* e, const void* d_gray, int32_t n, const mocr_beam_config* beam, void* d_out_ids,
+                                         void* d_out_len, void* d_out_score, void* d_out_logp, const int32_t* sets, void* d_out_pos) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, d_out_score, bc, d_out_logp, sets, d_out_pos)) return rc;
     return recognize_device(e, d_gray, bc.rows, d_out_ids, d_out_len, bc.req);
 }
 
@@ -4318,6 +4389,11 @@ int mocr_op_dec_bias_gelu(mocr_engine* e, const float* d_slabs, int32_t nslab, c
 
 int mocr_op_attn_positions(mocr_engine* e, const void* d_q, const void* d_k, const int32_t* d_len, int32_t rows, int32_t T, float* d_out_pos,
                            float* d_out_map) {
+    return mocr_op_attn_positions_gathered(e, d_q, d_k, d_len, rows, T, d_out_pos, d_out_map, nullptr, 0, 0);
+}
+
+int mocr_op_attn_positions_gathered(mocr_engine* e, const void* d_q, const void* d_k, const int32_t* d_len, int32_t rows, int32_t T,
+                                    float* d_out_pos, float* d_out_map, const uint8_t* d_trail, int32_t trail_ld, int32_t K) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -4334,6 +4410,7 @@ int mocr_op_attn_positions(mocr_engine* e, const void* d_q, const void* d_k, con
         p.len = d_len; p.len_bias = 0; p.T = T;
         p.out_pos = d_out_pos; p.pos_row_stride = (long long)T * MOCR_POSITION_FIELDS;
         p.out_map = d_out_map;
+        if (d_trail) { p.trail = d_trail; p.trail_ld = trail_ld; p.K = K; }      // (launch_attn_positions checks the three)
         if (e->cfg.dtype == MOCR_BF16) launch_attn_positions<bf16_t>(e, p, rows); else launch_attn_positions<float>(e, p, rows);
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
@@ -4619,13 +4696,21 @@ int mocr_profile_get(mocr_engine* e, mocr_kernel_stat* out, int32_t cap, int32_t
 
 int mocr_op_beam_select(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score, int32_t* d_parent,
                         int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open) {
-    return mocr_op_beam_select_tokens(e, a, beam, d_beam_score, d_parent, d_hyp_ids, d_hyp_len, d_hyp_score, d_heuristic_open, nullptr,
-                                      nullptr, nullptr, nullptr);
+    return mocr_op_beam_select_positions(e, a, beam, d_beam_score, d_parent, d_hyp_ids, d_hyp_len, d_hyp_score, d_heuristic_open, nullptr,
+                                         nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 int mocr_op_beam_select_tokens(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score,
                                int32_t* d_parent, int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open,
                                float* d_beam_logp, float* d_hyp_logp, const uint32_t* d_tok_mask, const int32_t* d_set_of_row) {
+    return mocr_op_beam_select_positions(e, a, beam, d_beam_score, d_parent, d_hyp_ids, d_hyp_len, d_hyp_score, d_heuristic_open, d_beam_logp,
+                                         d_hyp_logp, d_tok_mask, d_set_of_row, nullptr, nullptr);
+}
+
+int mocr_op_beam_select_positions(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score,
+                                  int32_t* d_parent, int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open,
+                                  float* d_beam_logp, float* d_hyp_logp, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
+                                  uint8_t* d_beam_trail, uint8_t* d_hyp_trail) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -4648,6 +4733,7 @@ int mocr_op_beam_select_tokens(mocr_engine* e, const mocr_token_args* a, const m
         bs.beam_score = d_beam_score; bs.parent = d_parent; bs.hyp_ids = d_hyp_ids; bs.hyp_len = d_hyp_len; bs.hyp_score = d_hyp_score;
         bs.heuristic_open = d_heuristic_open;
         bs.beam_logp = d_beam_logp; bs.hyp_logp = d_hyp_logp; bs.tok_mask = d_tok_mask; bs.set_of_row = d_set_of_row;
+        bs.beam_trail = d_beam_trail; bs.hyp_trail = d_hyp_trail;      // (launch_beam_select refuses one without the other)
         bs.length_penalty = beam->length_penalty; bs.early_stopping = beam->early_stopping; bs.ngram = beam->no_repeat_ngram_size;
         DecTokenArgs t{};
         t.slabs = a->slabs; t.nslab = a->nslab; t.slab_stride = (long long)a->n * e->V;
@@ -4694,6 +4780,15 @@ int64_t mocr_beam_token_state_bytes(mocr_engine* e) {
     int64_t bytes = 0;
     for (const Lane& L : e->lanes)
         if (L.ctx.hyp_logp) bytes += (int64_t)e->Bp * e->cfg.max_len * 2 * 4;      // beam_logp and hyp_logp [Bp][max_len]
+    return bytes;
+}
+
+int64_t mocr_beam_position_state_bytes(mocr_engine* e) {
+    if (!e) return -1;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int64_t bytes = 0;
+    for (const Lane& L : e->lanes)
+        if (L.ctx.hyp_trail) bytes += (int64_t)e->Bp * e->cfg.max_len * 2;      // beam_trail and hyp_trail [Bp][max_len], a byte each
     return bytes;
 }
 

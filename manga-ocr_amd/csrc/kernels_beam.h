@@ -27,6 +27,9 @@ struct BeamState {
     float* hyp_logp;        // [rows][ids_ld] those of the finished hypotheses, 0 behind their length: moves as hyp_ids does
     const unsigned* tok_mask;   // [sets][V / 32] the engine's token-set bit table ...
     const int* set_of_row;      // [rows] ... and the set of every row (the K rows of a crop name the same one)
+    // the trail form (both or neither; every other form reads neither): transformers' beam_indices, relative to the crop's group
+    uint8_t* beam_trail;    // [rows][ids_ld] [t], t >= 1: the beam 0 .. K - 1 whose row ran the step that appended token t; by row like ids
+    uint8_t* hyp_trail;     // [rows][ids_ld] those of the finished hypotheses, 0 behind their length: moves as hyp_ids does
 };
 
 // Start of a beam batch, one block of 64 threads per row: running scores [0, -1e9, ...], an empty finished set.
@@ -38,6 +41,10 @@ __global__ __launch_bounds__(64) void beam_init_kernel(BeamState bs, int K, int 
         for (int i = threadIdx.x; i < ids_ld; i += 64) bs.beam_logp[(size_t)r * ids_ld + i] = 0.f;
     if (bs.hyp_logp)
         for (int i = threadIdx.x; i < ids_ld; i += 64) bs.hyp_logp[(size_t)r * ids_ld + i] = 0.f;
+    if (bs.beam_trail)
+        for (int i = threadIdx.x; i < ids_ld; i += 64) bs.beam_trail[(size_t)r * ids_ld + i] = 0;
+    if (bs.hyp_trail)
+        for (int i = threadIdx.x; i < ids_ld; i += 64) bs.hyp_trail[(size_t)r * ids_ld + i] = 0;
     if (threadIdx.x == 0) {
         bs.beam_score[r] = (r % K == 0) ? 0.f : -BEAM_NEG;
         bs.parent[r] = r % K;
@@ -74,9 +81,15 @@ __global__ __launch_bounds__(64) void beam_init_kernel(BeamState bs, int K, int 
 //   with fewer than 2 K finite scores a winner can be dead (-inf): it never enters the finished set (-inf < -1e9), and the
 //     next running beams are the best K of (score, -1e9 on the stopped ones) by value, the earlier candidate first among
 //     equals - the plain form's "those that did not stop, then the stopped ones" whenever no candidate is dead.
-// LDS, static, at K = 4: ids and hypotheses 2 x 5 KiB, their log-probabilities 2 x 5 KiB (token form only), the mask 768 B,
-// under 1 KiB of lists - 21.5 KiB of the 64 KiB a block may declare.
-template <typename T, int K, bool TOK = false>
+//
+// TRAIL, the trail form (token positions of the hypotheses; orthogonal to TOK, and without it the code is what it was):
+//   beam_trail[row][t] is the beam, 0 .. K - 1 of the crop's group, whose row ran the step that appended token t - the row
+//     that step's recordings (the engine's pos_hist) lie in, since those are written by row and never reordered.  It travels
+//     with ids (through s_thist), and the entry of the token this step appends is the candidate's parent; hyp_trail travels
+//     with hyp_ids (through s_thyp), the shift under an inserted hypothesis included.  One byte per entry: K <= 4.
+// LDS, static, at K = 4: ids and hypotheses 2 x 5 KiB, their log-probabilities 2 x 5 KiB (token form only), their trails
+// 2 x 1.25 KiB (trail form only), the mask 768 B, under 1 KiB of lists - 24 KiB of the 64 KiB a block may declare.
+template <typename T, int K, bool TOK = false, bool TRAIL = false>
 __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restrict__ slabs, int nslab, long long slab_stride,
                                                           const float* __restrict__ vbias, int V, DecState st, BeamState bs, int np,
                                                           const float* __restrict__ word, const float* __restrict__ type0,
@@ -99,9 +112,12 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
     constexpr int KT = TOK ? K : 1, HT = TOK ? BEAM_HIST : 1;
     __shared__ float s_lhist[KT][HT];
     __shared__ float s_lhyp[KT][HT];
+    constexpr int KR = TRAIL ? K : 1, HR = TRAIL ? BEAM_HIST : 4;
+    __shared__ uint8_t s_thist[KR][HR];
+    __shared__ uint8_t s_thyp[KR][HR];
     __shared__ float s_gmax[K], s_logS[K], s_clp[C2];
     __shared__ int s_clive[C2], s_nsrc[K];            // the candidate is not dead; the candidate new beam k was made from
-    static_assert(sizeof(s_hist) + sizeof(s_hyp) + sizeof(s_lhist) + sizeof(s_lhyp) + sizeof(s_mask) + 1024 <= 65536,
+    static_assert(sizeof(s_hist) + sizeof(s_hyp) + sizeof(s_lhist) + sizeof(s_lhyp) + sizeof(s_thist) + sizeof(s_thyp) + sizeof(s_mask) + 1024 <= 65536,
                   "static LDS of the selection: the histories, the mask and under 1 KiB of lists");
     const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int slot0 = g * K;
@@ -129,6 +145,11 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
             for (int k = 0; k < K; ++k)
                 for (int i = tid; i < L; i += 256) s_lhist[k][i] = bs.beam_logp[(size_t)s_row[k] * st.ids_ld + i];
         }
+    }
+    if constexpr (TRAIL) {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            for (int i = tid; i < L; i += 256) s_thist[k][i] = bs.beam_trail[(size_t)s_row[k] * st.ids_ld + i];
     }
     __syncthreads();
 
@@ -330,6 +351,12 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
                         s_lhyp[s_hsrc[j] >= 0 ? s_hsrc[j] : 0][i] = bs.hyp_logp[(size_t)(crop * K + s_hsrc[j]) * st.ids_ld + i];
             }
         }
+        if constexpr (TRAIL) {
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+                for (int i = tid; i < s_hlen[j]; i += 256)
+                    s_thyp[s_hsrc[j] >= 0 ? s_hsrc[j] : 0][i] = bs.hyp_trail[(size_t)(crop * K + s_hsrc[j]) * st.ids_ld + i];
+        }
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < K; ++j) {
@@ -359,6 +386,21 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
                 }
             }
         }
+        if constexpr (TRAIL) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                uint8_t* dst = bs.hyp_trail + (size_t)(crop * K + j) * st.ids_ld;
+                const int src = s_hsrc[j];
+                if (src == j) continue;
+                if (src >= 0) {
+                    for (int i = tid; i < st.ids_ld; i += 256) dst[i] = i < s_hlen[j] ? s_thyp[src][i] : (uint8_t)0;
+                } else {
+                    const int ci = -1 - src;
+                    for (int i = tid; i < st.ids_ld; i += 256)
+                        dst[i] = i < L ? s_thist[s_cpar[ci]][i] : i == L ? (uint8_t)s_cpar[ci] : (uint8_t)0;
+                }
+            }
+        }
     }
     if (s_done) return;                               // block-uniform
     // the new beams' rows: the parent's history plus the token
@@ -380,6 +422,16 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
                     for (int i = tid; i < L; i += 256) dst[i] = s_lhist[p][i];
                 if (tid == 0 && L < st.ids_ld) dst[L] = s_clp[s_nsrc[k]];
             }
+        }
+    }
+    if constexpr (TRAIL) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            uint8_t* dst = bs.beam_trail + (size_t)s_row[k] * st.ids_ld;
+            const int p = s_npar[k];
+            if (p != k)
+                for (int i = tid; i < L; i += 256) dst[i] = s_thist[p][i];
+            if (tid == 0 && L < st.ids_ld) dst[L] = (uint8_t)p;
         }
     }
     // embedding + LayerNorm of every new beam's next input (the tail of dec_token_kernel)

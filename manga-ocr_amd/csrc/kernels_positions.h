@@ -19,6 +19,10 @@
 //     cancellation.
 //   * a tile behind the row's length exits at once; positions behind it inside a tile are computed on the last valid
 //     query and not written.
+//   * the gathered-query form (PosParams::trail set; beam search): row r of the launch is a finished
+//     hypothesis, and the query of its position p lies in the row that RAN that step - row (r / K) K + trail[r][p + 1] of
+//     the query block, position p.  Keys, lengths and outputs stay by row r.  One byte load per lane before the head loop:
+//     it moves the lane's query base and nothing else, the key loop is the same instructions.
 #pragma once
 #include "common.h"
 #include "kernels_latent.h"      // row16_sum
@@ -37,6 +41,10 @@ struct PosParams {
     float* out_pos;             // position t of row r at out_pos + r * pos_row_stride + t * 5 (cx, cy, sx, sy, mass)
     long long pos_row_stride;   // floats
     float* out_map;             // nullable: [rows][T][197] the head-mean map
+    // the gathered-query form (null: every row reads its own queries)
+    const uint8_t* trail;       // [rows][trail_ld]: [p + 1] = the row, 0 .. K - 1 of r's group of K, that holds the query of position p
+    long long trail_ld;
+    int K;                      // rows is a multiple of it
 };
 
 template <typename T>
@@ -46,7 +54,9 @@ __global__ __launch_bounds__(64) void attn_positions_kernel(PosParams p) {
     if (t0 >= n) return;
     const int lane = threadIdx.x, l15 = lane & 15, g = lane >> 4;
     const int pos = min(t0 + l15, n - 1);
-    const T* const qrow = reinterpret_cast<const T*>(p.q) + (size_t)r * p.q_row_stride + (size_t)pos * 768;
+    int qr = r;
+    if (p.trail) qr = r - r % p.K + min((int)p.trail[(size_t)r * p.trail_ld + pos + 1], p.K - 1);
+    const T* const qrow = reinterpret_cast<const T*>(p.q) + (size_t)qr * p.q_row_stride + (size_t)pos * 768;
     const T* const kbase = reinterpret_cast<const T*>(p.k) + (size_t)r * p.k_row_stride;
     float amap[POS_KT][4];
 #pragma unroll

@@ -305,7 +305,7 @@ class Engine:
         return sets, ngram
 
     def _recognize(self, kind: str, n: int, lead, tail=(), *, beam, d_out=None, skip_empty: bool = False, beam_scores=False, beam_sets=None,
-                   **req):
+                   beam_positions=False, **req):
         """The one request path under recognize_images / _regions / _gray / _device.  ``kind``: the source kind as the C symbols
         spell it; ``n``: its number of sources; ``lead()``: (the call's leading C arguments, sources counted last; whatever they
         point into, kept until the call returns) - built only once the call is going to be made; ``tail``: what follows the
@@ -318,13 +318,29 @@ class Engine:
         _positions - each the richest of its line, every output nobody asked for passed as null.
         ``beam_scores`` (a host kind's flag; recognize_device: its ``d_out_beam_logp`` buffer) and ``beam_sets`` belong to a beam
         call: with either in use the symbol is mocr_recognize_{kind}_beam_tokens - the beam call plus (out_logp, sets), null
-        where not asked - and a host kind returns logp [n,K,max_len] behind the scores when asked."""
+        where not asked - and a host kind returns logp [n,K,max_len] behind the scores when asked.
+        ``beam_positions`` (a host kind's flag; recognize_device: its ``d_out_beam_pos`` buffer) belongs to a beam call too: the
+        symbol is then mocr_recognize_{kind}_beam_positions - the _beam_tokens call plus out_pos - and a host kind returns pos
+        [n,K,max_len,5] as the LAST element."""
         host = d_out is None
+        wants_pos = beam_positions is not None and beam_positions is not False
         tokens = (beam_scores is not None and beam_scores is not False) or beam_sets is not None
-        if tokens and beam is None:
-            raise ValueError("beam_scores / beam_sets belong to a beam call: pass beam=")
+        if (tokens or wants_pos) and beam is None:
+            raise ValueError("beam_scores / beam_sets / beam_positions belong to a beam call: pass beam=")
         if beam is not None:
             cfg, *out = self._beam_blocks(beam, n if host else 0, **req)
+            if wants_pos:
+                sets = self._sets(beam_sets, n) if beam_sets is not None else None
+                if host:
+                    logp = np.zeros(out[0].shape, dtype=np.float32) if beam_scores else None
+                    pos = np.zeros(out[0].shape + (_capi.POSITION_FIELDS,), dtype=np.float32)
+                else:
+                    logp, pos = beam_scores, beam_positions
+                if n > 0 or not skip_empty:
+                    args, keep = lead()
+                    self._check(getattr(self.lib, f"mocr_recognize_{kind}_beam_positions")(
+                        self._h, *args, *tail, C.byref(cfg), *map(_ptr, out if host else d_out), _ptr(logp), _ptr(sets), _ptr(pos)))
+                return (tuple(out) + ((logp,) if logp is not None else ()) + (pos,)) if host else None
             if not tokens:
                 if n > 0 or not skip_empty:
                     args, keep = lead()
@@ -359,7 +375,7 @@ class Engine:
 
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False,
                          token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
-                         beam_scores: bool = False, beam_sets=None):
+                         beam_scores: bool = False, beam_sets=None, beam_positions: bool = False):
         """Crops of any sizes (list of uint8 [h,w] / [h,w,3] arrays; `bgr`: 3-channel crops are in OpenCV order;
         `rotate`: per crop 0 / 1 (90 degrees clockwise) / 2 (counter-clockwise), applied on the device): luminance
         conversion and the Pillow-exact BILINEAR resize to 224x224 run on the device.
@@ -386,16 +402,20 @@ class Engine:
         ``beam_sets`` is a handle of :meth:`token_set` for every crop, or one per crop - all K beams of a crop search under it,
         a token outside scoring -inf without renormalising; ``beam_scores`` adds a LAST element logp float32 [n,K,max_len], the
         log-probability of every token of every hypothesis at the step that appended it (0 at the start token and behind the
-        length).  Neither moves an id, a length or a sequence score of an unconstrained search."""
+        length).  Neither moves an id, a length or a sequence score of an unconstrained search.
+        ``beam_positions=True`` (only with ``beam``; include/mocr.h, "beam search with token positions"): one more, LAST element
+        pos float32 [n,K,max_len,5] - the token positions of every hypothesis, as ``positions=True`` gives them for a greedy row
+        teacher-forced on the hypothesis' ids; zeros at the start token, behind the length and in empty slots.  Same ids,
+        lengths, scores and token scores."""
         def lead():
             descs, keep = self._image_descs(images, bgr, rotate)
             return (descs, len(keep)), keep
-        return self._recognize("images", len(images), lead, beam=beam, beam_scores=beam_scores, beam_sets=beam_sets, skip_empty=True, scores=scores, alternatives=alternatives, token_sets=token_sets,
+        return self._recognize("images", len(images), lead, beam=beam, beam_scores=beam_scores, beam_sets=beam_sets, beam_positions=beam_positions, skip_empty=True, scores=scores, alternatives=alternatives, token_sets=token_sets,
                                no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources)
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False,
                           token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
-                          beam_scores: bool = False, beam_sets=None):
+                          beam_scores: bool = False, beam_sets=None, beam_positions: bool = False):
         """pages: list of uint8 [H,W,3] (or [H,W]) arrays; regions: iterable of (page_index, x, y, w, h) bounding
         rectangles.  Each page is uploaded once; the 8 %-padded, page-clipped crop of every region
         (``src/ui/main_window.py:9530-9540``) is cut on the device.  Returns (ids [n,max_len], lengths [n]);
@@ -409,7 +429,8 @@ class Engine:
         ``sources``: one region index per output ROW (see recognize_images): the outputs have ``len(sources)`` rows, the
         per-region arguments are per row, and every row of a sliver region has length 0.
         ``beam``: a :class:`BeamConfig` (see recognize_images): (ids [n,K,max_len], lengths [n,K], scores [n,K]); a sliver's K
-        slots are empty.  ``beam_scores`` / ``beam_sets``: as for recognize_images, one set per region; a sliver's logp rows all 0."""
+        slots are empty.  ``beam_scores`` / ``beam_sets``: as for recognize_images, one set per region; a sliver's logp rows all 0.
+        ``beam_positions``: as for recognize_images, in fractions of the region's padded, clipped rectangle; a sliver's rows all 0."""
         regs = list(regions)
 
         def lead():
@@ -418,7 +439,7 @@ class Engine:
             for i, (pg, x, y, w, h) in enumerate(regs):
                 arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
             return (descs, len(keep), arr, len(regs)), keep
-        return self._recognize("regions", len(regs), lead, beam=beam, beam_scores=beam_scores, beam_sets=beam_sets, skip_empty=True, scores=scores, alternatives=alternatives, token_sets=token_sets,
+        return self._recognize("regions", len(regs), lead, beam=beam, beam_scores=beam_scores, beam_sets=beam_sets, beam_positions=beam_positions, skip_empty=True, scores=scores, alternatives=alternatives, token_sets=token_sets,
                                no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources)
 
     def graph_count(self) -> int:
@@ -444,6 +465,11 @@ class Engine:
         scores or a token set (include/mocr.h, test hook)."""
         return int(self.lib.mocr_beam_token_state_bytes(self._h))
 
+    def beam_position_state_bytes(self) -> int:
+        """Bytes of the two beam-index trails, which neither of the two above counts: 0 until the first beam batch that asks for
+        token positions (include/mocr.h, test hook)."""
+        return int(self.lib.mocr_beam_position_state_bytes(self._h))
+
     def lane_rowmap(self, n: int, lane: int = 0) -> np.ndarray:
         """The first ``n`` entries of a lane's decode slot -> row map as its last batch left it (include/mocr.h, test hook)."""
         out = np.zeros(n, dtype=np.int32)
@@ -463,7 +489,7 @@ class Engine:
 
     def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None, d_out_alt_ids=None, d_out_alt_logp=None, *,
                          token_sets=None, no_repeat_ngram=None, d_out_pos=None, prefixes=None, sources=None, beam=None,
-                         d_out_score=None, d_out_beam_logp=None, beam_sets=None) -> None:
+                         d_out_score=None, d_out_beam_logp=None, beam_sets=None, d_out_beam_pos=None) -> None:
         """Asynchronous; all are device buffers (torch CUDA tensors or raw addresses).  ``d_out_logp`` (float32
         [n,max_len]): also the token log-probabilities.  ``d_out_alt_ids`` (int32) with ``d_out_alt_logp`` (float32), both
         [n,max_len,4]: also the token alternatives.  ``token_sets``: a set handle for every crop, or one per crop (host values).
@@ -473,8 +499,9 @@ class Engine:
         ``n`` then counts the planes of ``d_gray``, the output buffers have ``len(sources)`` rows and the per-crop arguments
         are per row.  ``beam`` (a :class:`BeamConfig`) with ``d_out_score``: beam search - ``d_out_ids`` int32 [n,K,max_len],
         ``d_out_len`` int32 [n,K] and ``d_out_score`` float32 [n,K] receive the hypotheses; none of the other keywords but ``d_out_beam_logp`` (float32
-        [n,K,max_len]: also the hypotheses' token scores) and ``beam_sets`` (host values), as for recognize_images."""
-        self._recognize("device", n, lambda: ((_ptr(d_gray), n), None), beam=beam, beam_scores=d_out_beam_logp, beam_sets=beam_sets, d_out=(d_out_ids, d_out_len, d_out_score), d_out_logp=d_out_logp,
+        [n,K,max_len]: also the hypotheses' token scores), ``beam_sets`` (host values) and ``d_out_beam_pos`` (float32 [n,K,max_len,5]: also
+        the hypotheses' token positions), as for recognize_images."""
+        self._recognize("device", n, lambda: ((_ptr(d_gray), n), None), beam=beam, beam_scores=d_out_beam_logp, beam_sets=beam_sets, beam_positions=d_out_beam_pos, d_out=(d_out_ids, d_out_len, d_out_score), d_out_logp=d_out_logp,
                         d_out_alt_ids=d_out_alt_ids, d_out_alt_logp=d_out_alt_logp, token_sets=token_sets, no_repeat_ngram=no_repeat_ngram,
                         d_out_pos=d_out_pos, prefixes=prefixes, sources=sources)
 
@@ -483,13 +510,13 @@ class Engine:
 
     def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False, alternatives: bool = False,
                        token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
-                       beam_scores: bool = False, beam_sets=None):
+                       beam_scores: bool = False, beam_sets=None, beam_positions: bool = False):
         """Luminance planes uint8 [n,224,224] (host), generate(max_length) ``max_len``; the keywords as for recognize_images
         (``sources``: one plane index per output row; ``beam``: (ids [n,K,max_len], lengths [n,K], scores [n,K]), with ``beam_scores`` also
-        logp [n,K,max_len]; ``beam_sets``: one set per plane)."""
+        logp [n,K,max_len]; ``beam_sets``: one set per plane; ``beam_positions``: also pos [n,K,max_len,5], last)."""
         a = np.ascontiguousarray(gray, dtype=np.uint8)
         return self._recognize("gray_host", a.shape[0], lambda: ((_ptr(a), a.shape[0]), a), (max_len or self.spec.max_len,), beam=beam, beam_scores=beam_scores,
-                               beam_sets=beam_sets, scores=scores,
+                               beam_sets=beam_sets, beam_positions=beam_positions, scores=scores,
                                alternatives=alternatives, token_sets=token_sets, no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes,
                                sources=sources)
 
@@ -657,6 +684,16 @@ class Engine:
                                                         _ptr(d_heuristic_open), _ptr(d_beam_logp), _ptr(d_hyp_logp), _ptr(d_tok_mask),
                                                         _ptr(d_set_of_row)))
 
+    def op_beam_select_positions(self, beam: BeamConfig, d_beam_score, d_parent, d_hyp_ids, d_hyp_len, d_hyp_score, d_heuristic_open,
+                                 d_beam_logp=None, d_hyp_logp=None, d_tok_mask=None, d_set_of_row=None, d_beam_trail=None,
+                                 d_hyp_trail=None, **kw) -> None:
+        """The selection in its trail form (include/mocr.h mocr_op_beam_select_positions); keywords: the fields of mocr_token_args."""
+        cfg = beam.as_struct()
+        self._check(self.lib.mocr_op_beam_select_positions(self._h, self._args(_capi.MocrTokenArgs, kw), C.byref(cfg), _ptr(d_beam_score),
+                                                           _ptr(d_parent), _ptr(d_hyp_ids), _ptr(d_hyp_len), _ptr(d_hyp_score),
+                                                           _ptr(d_heuristic_open), _ptr(d_beam_logp), _ptr(d_hyp_logp), _ptr(d_tok_mask),
+                                                           _ptr(d_set_of_row), _ptr(d_beam_trail), _ptr(d_hyp_trail)))
+
     def op_beam_permute(self, d_cache, layers: int, layer_stride: int, row_stride: int, segs: int, seg_stride: int, pos_bytes: int,
                         K: int, d_parent, d_rowmap, d_finished, d_step, n_slots: int, max_pos: int) -> None:
         """The cache reorder behind the selection on a device buffer (include/mocr.h mocr_op_beam_permute); strides in bytes."""
@@ -668,6 +705,12 @@ class Engine:
         """The positions kernel on device buffers (include/mocr.h mocr_op_attn_positions)."""
         self._check(self.lib.mocr_op_attn_positions(self._h, _ptr(d_q), _ptr(d_k), _ptr(d_len), int(rows), int(T), _ptr(d_out_pos),
                                                     _ptr(d_out_map)))
+
+    def op_attn_positions_gathered(self, d_q, d_k, d_len, rows: int, T: int, d_out_pos, d_out_map=None, d_trail=None, trail_ld: int = 0,
+                                   K: int = 0) -> None:
+        """The positions kernel in its gathered-query form (include/mocr.h mocr_op_attn_positions_gathered)."""
+        self._check(self.lib.mocr_op_attn_positions_gathered(self._h, _ptr(d_q), _ptr(d_k), _ptr(d_len), int(rows), int(T), _ptr(d_out_pos),
+                                                             _ptr(d_out_map), _ptr(d_trail), int(trail_ld), int(K)))
 
     def op_enc_expand(self, d_enc, d_src_of_row, n_src: int, n_rows: int) -> None:
         """The expansion of shared encodings on a device buffer (include/mocr.h mocr_op_enc_expand)."""

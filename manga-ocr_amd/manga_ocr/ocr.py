@@ -335,6 +335,7 @@ class _Request(NamedTuple):
     beam: Optional[BeamConfig] = None   # beam search with this configuration, None: greedy
     beam_scores: bool = False           # a beam request: wants its hypotheses' token log-probabilities
     beam_set: int = 0                   # a beam request: the token set its beams search under, 0: unconstrained
+    beam_positions: bool = False        # a beam request: wants its hypotheses' token positions
 
 
 class _Batcher:
@@ -353,7 +354,9 @@ class _Batcher:
     submissions are never merged, and a beam batch holds at most ``max_batch // num_beams`` crops; such a caller gets
     (ids [K, max_len], lengths [K], scores [K]).  A beam request may ask for its token scores (``beam_scores``) and carry a
     token set (``beam_set``): only a beam batch with such a request passes ``beam_scores=True`` / ``beam_sets=`` (one handle per
-    crop, 0 for the others), and only a caller that asked gets logp [K, max_len] as a fourth element."""
+    crop, 0 for the others), and only a caller that asked gets logp [K, max_len] as a fourth element.  The same for the
+    hypotheses' token positions (``beam_positions``): only a beam batch with such a request passes ``beam_positions=True``, and
+    only a caller that asked gets pos [K, max_len, 5] as its last element."""
 
     def __init__(self, engine: Engine, max_batch: int, timeout_ms: float):
         self.engine, self.max_batch, self.timeout = engine, max_batch, timeout_ms / 1000.0
@@ -365,13 +368,13 @@ class _Batcher:
 
     def submit(self, gray: np.ndarray, scored: bool = False, alternatives: bool = False, token_set: int = 0,
                no_repeat_ngram: int = 0, positions: bool = False, prefix=None, beam: Optional[BeamConfig] = None,
-               beam_scores: bool = False, beam_set: int = 0) -> Future:
+               beam_scores: bool = False, beam_set: int = 0, beam_positions: bool = False) -> Future:
         f: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
             self._q.append(_Request(gray, f, bool(scored or alternatives), bool(alternatives), bool(positions), int(token_set), int(no_repeat_ngram),
-                                    tuple(prefix) if prefix else None, beam, bool(beam_scores), int(beam_set)))
+                                    tuple(prefix) if prefix else None, beam, bool(beam_scores), int(beam_set), bool(beam_positions)))
             self._cv.notify()
         return f
 
@@ -401,9 +404,14 @@ class _Batcher:
                         bkw["beam_scores"] = True
                     if any(r.beam_set for r in batch):
                         bkw["beam_sets"] = [r.beam_set for r in batch]
-                    ids, lens, sc, *logp = self.engine.recognize_images([r.gray for r in batch], beam=head, **bkw)
+                    if any(r.beam_positions for r in batch):
+                        bkw["beam_positions"] = True
+                    ids, lens, sc, *rest = self.engine.recognize_images([r.gray for r in batch], beam=head, **bkw)
+                    logp = rest.pop(0) if bkw.get("beam_scores") else None
+                    pos = rest.pop(0) if bkw.get("beam_positions") else None
                     for i, r in enumerate(batch):
-                        r.future.set_result((ids[i].copy(), lens[i].copy(), sc[i].copy()) + ((logp[0][i].copy(),) if r.beam_scores else ()))
+                        r.future.set_result((ids[i].copy(), lens[i].copy(), sc[i].copy()) + ((logp[i].copy(),) if r.beam_scores else ()) +
+                                            ((pos[i].copy(),) if r.beam_positions else ()))
                     continue
                 kw = {}         # only what somebody asked for: a batch of plain requests makes the plain call
                 if any(r.scored for r in batch):        # the richest call any request asked for
@@ -533,11 +541,16 @@ class MangaOcr:
         which then return the best hypothesis: None = greedy, as always; ``"checkpoint"`` = ``num_beams``,
         ``length_penalty``, ``early_stopping`` and ``no_repeat_ngram_size`` of the checkpoint's generation config, which then
         leave ``ignored_generation_config``; an int in 2 .. 4 = the same with that many beams.  The loader's warning about
-        ignored generation settings is then given only for what is still ignored.  The scored, alternatives, positions and
-        n-best methods (``recognize_scored``, ``recognize_alternatives``, ``recognize_positions``, ``recognize_nbest`` and
-        their batch forms, ``score_text``) keep decoding greedily: they return one greedy row per crop, with its alternatives,
-        positions or prefix; use ``recognize_beam`` for all hypotheses with their sequence scores - and, with
-        ``token_scores=True`` / ``allowed=``, their token log-probabilities and a search under a token set."""
+        ignored generation settings is then given only for what is still ignored.  The ``*_positions`` methods
+        (``recognize_positions`` and its batch, BGR and regions forms) then decode with the beams too: they return the best
+        hypothesis - the text ``__call__`` returns - with its token scores, ``sequence_score`` and ``positions`` (include/mocr.h,
+        "beam search with token positions"), so ``boxes`` / ``page_boxes`` belong to the text returned; like the plain methods
+        they then refuse ``allowed=`` / ``no_repeat_ngram=`` / ``prefix=`` (the instance's ``beam_positions``, set here whenever
+        ``beam`` is, says so).  The scored, alternatives and n-best methods
+        (``recognize_scored``, ``recognize_alternatives``, ``recognize_nbest`` and their batch forms, ``score_text``) keep decoding
+        greedily: they return one greedy row per crop, with its alternatives or prefix; use ``recognize_beam`` for all
+        hypotheses with their sequence scores - and, with ``token_scores=True`` / ``allowed=`` / ``positions=True``, their token
+        log-probabilities, a search under a token set and their token positions."""
         if force_cpu:
             raise RuntimeError("this MangaOcr is the MI355X engine: there is no CPU path (force_cpu=True is not supported)")
         dtype = dtype or os.environ.get("MANGA_OCR_DTYPE", "bf16")
@@ -580,6 +593,9 @@ class MangaOcr:
         self.no_repeat_ngram_size, self.ignored_generation_config = resolve_no_repeat_ngram(
             no_repeat_ngram_size, dict(getattr(spec, "ignored_generation", ())), spec.max_len)
         self.beam, self.ignored_generation_config = resolve_num_beams(num_beams, self.ignored_generation_config, self.no_repeat_ngram_size)
+        # do the *_positions methods decode with those beams too (the best hypothesis with its positions)?  Every MangaOcr this
+        # constructor builds with beams says yes; an instance that holds ``beam`` alone keeps the greedy positions rows it had
+        self.beam_positions = self.beam is not None
         if num_beams is not None and self.ignored_generation_config:
             import warnings
             warnings.warn("checkpoint config asks for generation settings this engine still ignores: " + repr(self.ignored_generation_config) +
@@ -621,7 +637,7 @@ class MangaOcr:
         return self.recognize(img_or_path)
 
     def _require(self, what: str) -> None:
-        """refuse ``what`` (SCORES, CONSTRAINTS, NGRAM, PREFIX, POSITIONS, ALTERNATIVES, BEAM) on an engine that says it cannot:
+        """refuse ``what`` (SCORES, CONSTRAINTS, NGRAM, PREFIX, POSITIONS, ALTERNATIVES, BEAM, BEAM_POSITIONS) on an engine that says it cannot:
         MultiGpuEngine, whose workers make the plain greedy call and ship ids and lengths only, has a NO_* message for each"""
         no = getattr(self.engine, "NO_" + what, None)
         if no:
@@ -685,13 +701,20 @@ class MangaOcr:
     def _run(self, source, kind: _Kind, allowed=None, no_repeat_ngram=None, prefix=None, sources=None) -> list:
         """Every greedy recognise method: one row of ``kind`` per crop or region of the source - or per entry of ``sources``
         (shared encodings).  In this order: the kind's refusal (several devices), before the image is opened or any argument
-        is looked at; for plain text, whether the constructor's beams decode it instead (``_beam_default``); ``source()``, which
+        is looked at; for plain text and positions, whether the constructor's beams decode it instead (``_beam_default``: text
+        gets the best hypothesis' ids, positions the best hypothesis with its token scores and positions); ``source()``, which
         opens, converts and checks the inputs; ``_decode_kw``; the ONE engine call, with the kind's flags and only the keywords
         somebody asked for; the kind's rows; ``n_forced`` of the rows that were given a prefix."""
         if kind.refusal:
             self._require(kind.refusal)
-        beams = kind is _TEXT and self._beam_default(allowed, no_repeat_ngram, prefix)
+        beams = (kind is _TEXT or (kind is _POS and getattr(self, "beam_positions", False))) and self._beam_default(allowed, no_repeat_ngram, prefix)
+        if beams and kind is _POS:
+            self._require("BEAM_POSITIONS")
         src = source()
+        if beams and kind is _POS:
+            ids, lens, sc, logp, pos = self._beam(src, self.beam, True, positions=True)
+            return [self._best_hypothesis(ids[i], lens[i], sc[i], logp[i], pos[i], src.rects[i] if src.rects is not None else None)
+                    for i in range(len(lens))]
         if beams:
             ids, lens, _ = self._beam(src, self.beam)
             return [ids[i, 0, :lens[i, 0]].copy() for i in range(len(lens))]
@@ -963,44 +986,64 @@ class MangaOcr:
             raise ValueError("this MangaOcr decodes with beam search (num_beams=): allowed= / no_repeat_ngram= / prefix= do not combine with it")
         return True
 
-    def _beam(self, src, beam: BeamConfig, token_scores: bool = False, allowed=None):
+    def _beam(self, src, beam: BeamConfig, token_scores: bool = False, allowed=None, positions: bool = False):
         """(ids [n, K, max_len], lengths [n, K], scores [n, K]) of a source: one crop through the batcher, any number of crops
         or regions max_batch // K of them per engine call (a beam request fits one batch: n * K <= max_batch).  With
-        ``token_scores`` also logp [n, K, max_len]; ``allowed``: the crops' token sets.  The engine is passed only what was asked."""
+        ``token_scores`` also logp [n, K, max_len]; ``allowed``: the crops' token sets; with ``positions`` also, last, pos
+        [n, K, max_len, 5].  The engine is passed only what was asked."""
         self._require("BEAM")
+        if positions:
+            self._require("BEAM_POSITIONS")
         hs = _set_handles(allowed, src.n)
         if hs is not None:
             self._require("CONSTRAINTS")
+        flags = dict(**(dict(beam_scores=True) if token_scores else {}), **(dict(beam_positions=True) if positions else {}))
         if isinstance(src, _Single):
-            kw = dict(beam_scores=True) if token_scores else {}
+            kw = dict(flags)
             if hs is not None:
                 kw["beam_set"] = hs[0]
             return tuple(a[None] for a in self._batcher.submit(src.pixels, beam=beam, **kw).result())
         if not src.n and isinstance(src, _Images):
             src = _Images([])       # no crops: the bare call, which only shapes the empty result
         step = max(1, int(self.max_batch) // beam.num_beams)
-        kw = lambda a: dict(**(dict(beam_scores=True) if token_scores else {}), **(dict(beam_sets=hs[a:a + step]) if hs is not None else {}))
+        kw = lambda a: dict(**flags, **(dict(beam_sets=hs[a:a + step]) if hs is not None else {}))
         parts = [src.call(self, a, a + step, beam=beam, **kw(a)) for a in range(0, src.n, step)] or [src.call(self, beam=beam, **kw(0))]
-        return tuple(np.concatenate([p[i] for p in parts]) for i in range(4 if token_scores else 3))
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(3 + bool(token_scores) + bool(positions)))
 
-    def _hypotheses(self, ids, lens, scores, logp=None) -> List[Recognition]:
-        """one crop's [K, max_len] / [K] / [K] (/ [K, max_len]) -> its finished hypotheses, best first (empty slots dropped);
-        with ``logp`` they carry their token log-probabilities and the confidence of a greedy row (Recognition.from_row)"""
+    def _hypotheses(self, ids, lens, scores, logp=None, pos=None, rect=None) -> List[Recognition]:
+        """one crop's [K, max_len] / [K] / [K] (/ [K, max_len] / [K, max_len, 5]) -> its finished hypotheses, best first (empty
+        slots dropped); with ``logp`` they carry their token log-probabilities and the confidence of a greedy row
+        (Recognition.from_row), with ``pos`` their ``positions`` [len, 5] - and ``rect``, a region's rectangle on its page"""
         none = np.zeros(0, dtype=np.float32)
         if logp is not None:
-            return [replace(Recognition.from_row(self.vocab, ids[j], logp[j], lens[j]), sequence_score=float(scores[j]))
-                    for j in range(len(lens)) if lens[j] > 0]
-        return [Recognition(ids_to_text(self.vocab, ids[j, :lens[j]]), np.array(ids[j, :lens[j]], dtype=np.int32), none, 0.0, 0.0,
+            return [replace(Recognition.from_row(self.vocab, ids[j], logp[j], lens[j], pos_row=None if pos is None else pos[j], rect=rect),
                             sequence_score=float(scores[j])) for j in range(len(lens)) if lens[j] > 0]
+        where = lambda j: {} if pos is None else dict(positions=np.array(pos[j, :lens[j]], dtype=np.float32).reshape(-1, pos.shape[-1]),
+                                                      rect=tuple(int(v) for v in rect) if rect is not None else None)
+        return [Recognition(ids_to_text(self.vocab, ids[j, :lens[j]]), np.array(ids[j, :lens[j]], dtype=np.int32), none, 0.0, 0.0,
+                            sequence_score=float(scores[j]), **where(j)) for j in range(len(lens)) if lens[j] > 0]
 
-    def _run_beam(self, source, *config, token_scores: bool = False, allowed=None) -> List[List[Recognition]]:
+    def _best_hypothesis(self, ids, lens, scores, logp, pos, rect=None) -> Recognition:
+        """the ``*_positions`` methods of a MangaOcr that decodes with beams: one crop's best hypothesis with its token scores and
+        positions; a region reduced to a sliver (no hypothesis) gives what the greedy methods give - text '', no rows, no rect"""
+        hyps = self._hypotheses(ids[:1], lens[:1], scores[:1], logp[:1], pos[:1], rect)
+        return hyps[0] if hyps else Recognition.from_row(self.vocab, ids[0], logp[0], 0, pos_row=pos[0])
+
+    def _run_beam(self, source, *config, token_scores: bool = False, allowed=None, positions: bool = False) -> List[List[Recognition]]:
         """the ``*_beam`` methods: the configuration is checked, then the inputs; one list of hypotheses per crop or region"""
         beam = BeamConfig(*config)
-        ids, lens, sc, *logp = self._beam(source(), beam, bool(token_scores), allowed)
-        return [self._hypotheses(ids[i], lens[i], sc[i], logp[0][i] if logp else None) for i in range(len(lens))]
+        src = source()
+        if positions and isinstance(src, _Regions):
+            src = src.with_rects()
+        ids, lens, sc, *rest = self._beam(src, beam, bool(token_scores), allowed, bool(positions))
+        logp = rest.pop(0) if token_scores else None
+        pos = rest.pop(0) if positions else None
+        rects = src.rects if positions else None
+        return [self._hypotheses(ids[i], lens[i], sc[i], None if logp is None else logp[i], None if pos is None else pos[i],
+                                 rects[i] if rects is not None else None) for i in range(len(lens))]
 
     def recognize_beam(self, img_or_path, num_beams: int = 4, length_penalty: float = 1.0, early_stopping=False,
-                       no_repeat_ngram: int = 0, *, token_scores: bool = False, allowed=None) -> List[Recognition]:
+                       no_repeat_ngram: int = 0, *, token_scores: bool = False, allowed=None, positions: bool = False) -> List[Recognition]:
         """Beam search for one crop (include/mocr.h, "beam search"): what transformers' ``generate(num_beams=...,
         length_penalty=..., early_stopping=..., no_repeat_ngram_size=...)`` returns with ``num_return_sequences=num_beams`` -
         the finished hypotheses, best first, each with its ``sequence_score``.  ``num_beams`` 2 .. 4; ``early_stopping``
@@ -1008,30 +1051,37 @@ class MangaOcr:
         ``token_scores=True``: every hypothesis also carries ``logprobs`` (one per token behind the start token: the
         log-probability the search gave it, EOS included), ``confidence`` and ``min_prob`` as a greedy scored row does.
         ``allowed``: a :class:`TokenSet` - the search runs under it: a token outside scores -inf at every step, WITHOUT the
-        renormalising of the greedy ``allowed=`` (transformers' ``prefix_allowed_tokens_fn``; include/mocr.h)."""
+        renormalising of the greedy ``allowed=`` (transformers' ``prefix_allowed_tokens_fn``; include/mocr.h).
+        ``positions=True``: every hypothesis also carries ``positions`` float32 ``[len, 5]`` - where the decoder looked when the
+        search appended each of ITS tokens, what a greedy row teacher-forced on the hypothesis would give (include/mocr.h, "beam
+        search with token positions") - so ``Recognition.boxes`` works on it.  Nothing else of the result moves."""
         self._require("BEAM")
         return self._run_beam(self._one(img_or_path), num_beams, length_penalty, early_stopping, no_repeat_ngram, token_scores=token_scores,
-                              allowed=allowed)[0]
+                              allowed=allowed, positions=positions)[0]
 
     def recognize_batch_beam(self, images: Sequence, num_beams: int = 4, length_penalty: float = 1.0, early_stopping=False,
-                             no_repeat_ngram: int = 0, *, token_scores: bool = False, allowed=None) -> List[List[Recognition]]:
+                             no_repeat_ngram: int = 0, *, token_scores: bool = False, allowed=None,
+                             positions: bool = False) -> List[List[Recognition]]:
         """``recognize_beam`` for many crops: one list of hypotheses per crop (``allowed``: one set for all, or one per crop)."""
-        return self._run_beam(self._pil(images), num_beams, length_penalty, early_stopping, no_repeat_ngram, token_scores=token_scores, allowed=allowed)
+        return self._run_beam(self._pil(images), num_beams, length_penalty, early_stopping, no_repeat_ngram, token_scores=token_scores, allowed=allowed,
+                              positions=positions)
 
     def recognize_bgr_beam(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, num_beams: int = 4,
                            length_penalty: float = 1.0, early_stopping=False, no_repeat_ngram: int = 0, *, token_scores: bool = False,
-                           allowed=None) -> List[List[Recognition]]:
-        """``recognize_bgr`` with beam search: one list of hypotheses per crop (``token_scores`` / ``allowed``: see recognize_beam)."""
+                           allowed=None, positions: bool = False) -> List[List[Recognition]]:
+        """``recognize_bgr`` with beam search: one list of hypotheses per crop (``token_scores`` / ``allowed`` / ``positions``: see
+        recognize_beam; the positions are those of the rotated crop, as for ``recognize_bgr_positions``)."""
         return self._run_beam(lambda: self._bgr("recognize_bgr_beam", crops_bgr, orientations), num_beams, length_penalty, early_stopping, no_repeat_ngram,
-                              token_scores=token_scores, allowed=allowed)
+                              token_scores=token_scores, allowed=allowed, positions=positions)
 
     def recognize_regions_beam(self, pages_bgr: Sequence[np.ndarray], regions, num_beams: int = 4, length_penalty: float = 1.0,
                                early_stopping=False, no_repeat_ngram: int = 0, *, token_scores: bool = False,
-                               allowed=None) -> List[List[Recognition]]:
+                               allowed=None, positions: bool = False) -> List[List[Recognition]]:
         """``recognize_regions`` with beam search: one list of hypotheses per region ([] for a sliver; ``token_scores`` /
-        ``allowed``: see recognize_beam, one set per region)."""
+        ``allowed``: see recognize_beam, one set per region; ``positions``: every hypothesis also carries ``rect``, so
+        ``page_boxes()`` works)."""
         return self._run_beam(lambda: _Regions(list(pages_bgr), list(regions)), num_beams, length_penalty, early_stopping, no_repeat_ngram,
-                              token_scores=token_scores, allowed=allowed)
+                              token_scores=token_scores, allowed=allowed, positions=positions)
 
     def recognize_page(self, page_bgr: np.ndarray, regions):
         """``_collect_manga_detections`` for one page: ``regions`` = the detector's (text, polygon) pairs."""

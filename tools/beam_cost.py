@@ -8,9 +8,15 @@
         (``beam_sets=``): the token form of the selection (include/mocr.h "beam search with token sets and token scores");
         (iv) / (i) is its price - a build without it (the parent commit) runs (i) - (iii) alone, and (i) must agree between
         the two builds within its run-to-run spread (best-of-N, the ``spread_ms`` minimum, is the figure to compare),
+  (vi)  the beam batch of (i) with token positions (``beam_positions=True``; include/mocr.h "beam search with token
+        positions") and (vii) with token scores and positions: (vi) / (i) is the price of the recorded rows, the trails in the
+        selection and the deferred pass.  The lines of (i), (vi) and (vii) are also appended to --positions-out (by default
+        profiles/beam_positions_cost.jsonl of this checkout): run it on this build and, with --tree, on a built checkout of
+        the parent commit, whose plain beam batch (i) is the yardstick - that build has no (vi) / (vii),
 and, with --profile, the two new kernels' times from the engine's per-kernel profile at 400 rows.
 
     python tools/beam_cost.py [--tree DIR] [--label NAME] [--crops 64] [--beams 4] [--max-len 32] [--reps 7] [--profile]
+                              [--positions-out profiles/beam_positions_cost.jsonl]
 
 --tree: the checkout whose package and library are measured (default: this one); a built checkout of the parent commit runs
 (ii) and (iii) alone - they are the yardsticks and must agree between the two builds within their own run-to-run spread.
@@ -32,6 +38,8 @@ def main():
     ap.add_argument("--max-len", type=int, default=32)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--positions-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "beam_positions_cost.jsonl"),
+                    help="append the plain beam line and the positions lines to this file ('' = nowhere)")
     args = ap.parse_args()
     tree = os.path.abspath(args.tree)
     for p in (tree, os.path.join(tree, "manga-ocr_amd")):
@@ -56,6 +64,9 @@ def main():
             some = eng.token_set(np.random.RandomState(40).choice(np.arange(5, DEFAULT_SPEC.vocab), 40, replace=False).tolist())
             forms.append(("beam_token_scores", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg, beam_scores=True)))
             forms.append(("beam_token_scores_set40", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg, beam_scores=True, beam_sets=some)))
+        if hasattr(eng, "beam_position_state_bytes"):   # (the parent commit has no positions for hypotheses)
+            forms.append(("beam_positions", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg, beam_positions=True)))
+            forms.append(("beam_token_scores_positions", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg, beam_scores=True, beam_positions=True)))
     for form, call in forms:
         for _ in range(2):
             call()
@@ -64,21 +75,28 @@ def main():
             t0 = time.perf_counter()
             call()
             ms.append(1e3 * (time.perf_counter() - t0))
-        print(json.dumps(dict(what="beam_cost", build=args.label, form=form, crops=args.crops, beams=K, max_len=args.max_len, reps=args.reps,
-                              ms_per_call=round(statistics.median(ms), 3), spread_ms=[round(min(ms), 3), round(max(ms), 3)])), flush=True)
+        line = json.dumps(dict(what="beam_cost", build=args.label, form=form, crops=args.crops, beams=K, max_len=args.max_len, reps=args.reps,
+                               ms_per_call=round(statistics.median(ms), 3), spread_ms=[round(min(ms), 3), round(max(ms), 3)]))
+        print(line, flush=True)
+        if args.positions_out and form in ("beam", "beam_positions", "beam_token_scores_positions"):
+            os.makedirs(os.path.dirname(os.path.abspath(args.positions_out)), exist_ok=True)
+            with open(args.positions_out, "a", encoding="utf-8") as f:
+                f.write(line + "\n")
     eng.close()
     if args.profile and beam is not None:
         n = 400 // K
         eng = me.Engine(w, DEFAULT_SPEC, dtype="bf16", device=0, max_batch=n * K, lanes=1)
         g = np.random.RandomState(7).randint(0, 256, size=(n, 224, 224), dtype=np.uint8)
         kws = [{}] + ([dict(beam_scores=True)] if hasattr(eng, "beam_token_state_bytes") else [])
+        kws += [dict(beam_positions=True)] if hasattr(eng, "beam_position_state_bytes") else []
         for kw in kws:
             eng.recognize_gray(g, args.max_len, beam=cfg, **kw)
             eng.profile_enable(True)
             eng.profile_reset()
             eng.recognize_gray(g, args.max_len, beam=cfg, **kw)
             for s in eng.profile_get():
-                if s["name"] in ("beam_select", "beam_select_tok", "beam_permute", "beam_init", "dec_attn_self", "latent_self", "gemm_dec_vocab"):
+                if s["name"] in ("beam_select", "beam_select_tok", "beam_permute", "beam_init", "dec_attn_self", "latent_self", "gemm_dec_vocab",
+                                 "gemm_pos_k", "gemm_pos_q", "attn_positions"):
                     print(json.dumps(dict(what="beam_kernels", build=args.label, rows=n * K, max_len=args.max_len, kernel=s["name"],
                                           launches=s["launches"], total_ms=round(s["total_ms"], 3),
                                           us_per_launch=round(1e3 * s["total_ms"] / max(s["launches"], 1), 2))), flush=True)
