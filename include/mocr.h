@@ -481,6 +481,9 @@ int mocr_op_layernorm_slab(mocr_engine* e, float* d_x, const float* d_slabs, int
  * K slices of O-proj, K slices of FC2 (1 = not split; the LayerNorm behind a split GEMM adds that many slabs), 1 if the
  * LayerNorms are folded into the GEMMs, blocks per (crop, head) of the attention, attention kernel (0 VALU, 1 matrix cores) }. */
 int mocr_encoder_plan(mocr_engine* e, int32_t n, int32_t out[10]);
+/* The rest of that plan: out = { N-tiles per column group of the tile order of QKV, of FC1 } for n crops - 9 / 12 on the 128 x 128
+ * kernel, 6 / 6 on the persistent one (column groups 6 + 3 and 6 + 6 of 256-column tiles). */
+int mocr_encoder_groups(mocr_engine* e, int32_t n, int32_t out[2]);
 /* What a greedy decode step of `rows` rows decides on this engine (test hook; computed by the helpers the step launches
  * through, nothing is launched).  regime_rows = the rows the batch started with (0 = rows): after a compaction the split over
  * K follows the regime, the tile and the ring depth follow the rows that are left.  rows need not fit max_batch.  out =
@@ -530,6 +533,32 @@ int mocr_op_gemm_args(mocr_engine* e, const mocr_gemm_args* a);
 /* The calling thread's last gemm_kernel launch (any hook that runs a 64 / 128 tile GEMM, the fused LM heads included):
  * out = { tile, ring slots, blocks in the grid, K slices }. */
 int mocr_last_tile_launch(mocr_engine* e, int32_t out[4]);
+/* bf16 engines: the persistent encoder GEMM launched as the encoder launches a layer GEMM - dense rows, out = A W^T + bias
+ * through the epilogue, the tile order in column groups of group_n N-tiles, the LayerNorm fold operands of mocr_op_gemm_ln when
+ * ln_part is set (csum and xb come with it only).  Refuses what the engine's own GEMM call and the kernel's launch refuse, with
+ * their messages.  Tile-list codes stage whole 256-row tiles of A (A holds M rounded up to 256 rows); the strip codes read no row
+ * behind M and need M >= 256. */
+typedef struct mocr_gemm_pers_args {
+    int32_t struct_size;        /* sizeof(mocr_gemm_pers_args) */
+    int32_t M;
+    int32_t N;                  /* a multiple of 256 */
+    int32_t K;                  /* a multiple of 64, >= 128 */
+    int32_t epilogue;           /* 1 bias, 2 bias + GELU (bf16 out), 3 bias + residual (fp32 out) */
+    int32_t tile;               /* 4096 the product's choice of schedule, 4097 the tile list on 8 blocks, 4099 strips, 4100 strips on 8 blocks */
+    int32_t group_n;            /* N-tiles per column group of the tile order (0 = one group); the strip schedule has no tile order */
+    const void* A;              /* [M][K] bf16 */
+    const void* W;              /* [N][K] bf16 */
+    const float* bias;          /* [N] */
+    void* out;                  /* [M][N] */
+    const float* resid;         /* epilogue 3: [M][N], may be out */
+    float* ln_part;             /* [M][4][2] or null: written by epilogue 3, read by 1 and 2 */
+    const float* csum;          /* [N], epilogues 1 and 2 with ln_part */
+    void* xb;                   /* [M][N] bf16, epilogue 3 with ln_part */
+} mocr_gemm_pers_args;
+int mocr_op_gemm_pers(mocr_engine* e, const mocr_gemm_pers_args* a);
+/* The calling thread's last launch of the persistent kernel (any hook that runs it): out = { blocks in the grid, 1 if the strip
+ * schedule ran (0: the tile list), tiles (M-tiles x N-tiles of 256 x 256), group_n as the kernel was given it }. */
+int mocr_last_pers_launch(mocr_engine* e, int32_t out[4]);
 /* Latent decode attention (bf16 engines): d_qt [n,16,768], keys d_x with x_batch_stride elements between
  * sequences, context length len for every row; d_out [n,16,768] = softmax(qt . x^T) x per head. */
 int mocr_op_latent_attention(mocr_engine* e, const void* d_qt, const void* d_x, void* d_out, int32_t n, int32_t len,

@@ -658,6 +658,10 @@ struct PersFamily {
     static constexpr int lds(const Args&) { return PERS_LDS; }
 };
 
+// What this thread's last launch_gemm_pers launched (mocr_last_pers_launch reports it)
+struct LastPers { int blocks, strips, tiles, group_n; };
+static thread_local LastPers g_last_pers{};
+
 // One launch of the persistent kernel.  blocks = 0: one block per CU (a multiple of 8, at most one per tile); a test may ask for
 // fewer blocks (longer tile sequences).  strip: 0 tile list, 1 strips wherever the grid can hold one, -1 whichever walks fewer
 // rounds; strips exist for the split-DMA forms only.  p.ln_part set: the LayerNorm-folding forms (kernels_gemm_pers.h, LNF).
@@ -670,6 +674,8 @@ void launch_gemm_pers(mocr_engine* e, const GemmParams& p0, int epi, bool split_
     p.ntn = p.N / 256; p.ntm = (p.M + 255) / 256;
     const int grid = std::max(8, std::min(blocks > 0 ? blocks : e->num_cus, (p.ntm * p.ntn + 7) / 8 * 8) / 8 * 8);
     const bool strips = split_dma && strip && (strip > 0 ? pers_strip_rows(p.M, p.ntn, grid) > 0 : pers_strip_wins(p.M, p.ntn, grid));
+    // (a strip's tile reads a whole 256-row window of A that ends with the tile's last row: below 256 rows it would start above A)
+    if (strips && p.M < 256) throw ArgError{"persistent gemm: the strip schedule needs at least 256 rows", MOCR_ERR_ARG};
     const auto f = find_form<PersFamily>({epi, split_dma, pair, strips, lnf});
     if (!f.kernel && lnf) throw ArgError{"persistent gemm: no LayerNorm-folding form of this kernel variant", MOCR_ERR_ARG};
     if (!f.kernel) throw ArgError{"persistent gemm: unsupported epilogue", MOCR_ERR_ARG};
@@ -679,6 +685,7 @@ void launch_gemm_pers(mocr_engine* e, const GemmParams& p0, int epi, bool split_
     p.first_round = hpos_env;
     hipLaunchKernelGGL(f.kernel, dim3(grid), dim3(512), f.lds, e->stream, p);
     HIPCHECK(hipGetLastError());
+    g_last_pers = {grid, strips ? 1 : 0, p.ntm * p.ntn, p.group_n};
 }
 
 // Tile codes.  The numbers belong to the boundaries that own them (mocr_op_gemm / mocr_op_gemm_ln, the MOCR_*_TILE knobs, DESIGN's
@@ -958,6 +965,7 @@ struct EncPlan {
     int split_o, split_2;             // K slices of O-proj / FC2 (1: not split)
     bool fold;                        // the LayerNorms between the layer GEMMs folded into them
     int impl, ysplit;                 // the attention kernel (0 VALU, 1 matrix cores) and its blocks per (image, head)
+    int gq, g1;                       // N-tiles per column group of QKV's / FC1's tile order (gemm_tile_of)
 };
 template <typename T>
 EncPlan encoder_plan(const mocr_engine* e, int n) {
@@ -1002,6 +1010,12 @@ EncPlan encoder_plan(const mocr_engine* e, int n) {
                      t1_env = env_int("MOCR_ENC_TILE_FC1", 0), t2_env = env_int("MOCR_ENC_TILE_FC2", 0);
     pl.tq = tq_env ? tq_env : layer_tile(3 * D); pl.to = to_env ? to_env : layer_tile(D); pl.t1 = t1_env ? t1_env : layer_tile(F);
     pl.t2 = t2_env ? t2_env : pl.to;
+    // tile order of QKV / FC1: column groups whose weight slices stay in an XCD's 4 MiB L2 while the A row-panels stream through
+    // once per group.  128 x 128 tiles: groups of 9 / 12 N-tiles (r01).  Persistent 256 x 256 tiles: groups of 6 (r04: QKV 6 + 3,
+    // FC1 6 + 6: the whole 3.4 / 4.5 MiB weight does not fit beside the A panels, and without groups every XCD re-fetches it
+    // per round of row-panels - at batch 256 QKV 210 -> 200 us, FC1 337 -> 331 us, one box; tools/r04_groupn_ab.sh)
+    pl.gq = tile_is(pl.tq, GemmKind::Persistent) ? 6 : 9;
+    pl.g1 = tile_is(pl.t1, GemmKind::Persistent) ? 6 : 12;
     pl.impl = (e->cfg.flags & MOCR_FLAG_SIMPLE_ATTENTION) ? 0 : 1;
     pl.ysplit = enc_attn_ysplit<T>(e, n, pl.impl);
     // A few crops (the 64 x 64 grid of the two N = 768 GEMMs is at most one block per CU: up to 6 crops on 256 CUs): O-proj
@@ -1079,12 +1093,7 @@ void run_encoder(mocr_engine* e, const uint8_t* d_gray, int n, void* enc_out = n
     const EncPlan pl = encoder_plan<T>(e, n);
     const int ETQ = pl.tq, ETO = pl.to, ET1 = pl.t1, ET2 = pl.t2, split_o = pl.split_o, split_2 = pl.split_2;
     const bool fold = pl.fold;
-    // tile order of QKV / FC1: column groups whose weight slices stay in an XCD's 4 MiB L2 while the A row-panels stream through
-    // once per group.  128 x 128 tiles: groups of 9 / 12 N-tiles (r01).  Persistent 256 x 256 tiles: groups of 6 (r04: QKV 6 + 3,
-    // FC1 6 + 6: the whole 3.4 / 4.5 MiB weight does not fit beside the A panels, and without groups every XCD re-fetches it
-    // per round of row-panels - at batch 256 QKV 210 -> 200 us, FC1 337 -> 331 us, one box; tools/r04_groupn_ab.sh)
-    const bool pers_q = tile_is(ETQ, GemmKind::Persistent), pers_1 = tile_is(ET1, GemmKind::Persistent);
-    const int gq = pers_q ? 6 : 9, g1 = pers_1 ? 6 : 12;
+    const int gq = pl.gq, g1 = pl.g1;      // column groups of QKV's / FC1's tile order
     encoder_front<T>(e, d_gray, n, e->Hb, e->X, pl.embed_tile);
     const float* pend_bias = nullptr;      // bias of a split GEMM whose slabs the next LayerNorm has to add to X
     int pend_slabs = 0;
@@ -4182,6 +4191,17 @@ int mocr_encoder_plan(mocr_engine* e, int32_t n, int32_t out[10]) {
     });
 }
 
+int mocr_encoder_groups(mocr_engine* e, int32_t n, int32_t out[2]) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        require_ready(e, n);
+        if (!out) throw ArgError{"mocr_encoder_groups: null pointer", MOCR_ERR_ARG};
+        EncPlan pl{};
+        dispatch(e, [&](auto tag) { pl = encoder_plan<decltype(tag)>(e, n); });
+        out[0] = pl.gq; out[1] = pl.g1;
+    });
+}
+
 int mocr_decode_plan(mocr_engine* e, int32_t rows, int32_t regime_rows, int32_t out[MOCR_DECODE_PLAN_FIELDS]) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
@@ -4235,6 +4255,39 @@ int mocr_last_tile_launch(mocr_engine* e, int32_t out[4]) {
     return guarded(e, [&] {
         if (!out) throw ArgError{"mocr_last_tile_launch: null pointer", MOCR_ERR_ARG};
         const int32_t v[4] = {g_last_tile.bm, g_last_tile.ring, g_last_tile.blocks, g_last_tile.split};
+        memcpy(out, v, sizeof(v));
+    });
+}
+
+int mocr_op_gemm_pers(mocr_engine* e, const mocr_gemm_pers_args* a) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!a || a->struct_size != (int32_t)sizeof(mocr_gemm_pers_args)) throw ArgError{"mocr_op_gemm_pers: bad struct_size", MOCR_ERR_ARG};
+        if (e->cfg.dtype != MOCR_BF16) throw ArgError{"mocr_op_gemm_pers: bf16 engines only", MOCR_ERR_UNSUPPORTED};
+        const int epi = a->epilogue;
+        if (epi != EPI_BIAS && epi != EPI_BIAS_GELU && epi != EPI_BIAS_RESID)
+            throw ArgError{"mocr_op_gemm_pers: epilogue 1 (bias), 2 (bias + GELU) or 3 (bias + residual)", MOCR_ERR_ARG};
+        if (!a->A || !a->W || !a->bias || !a->out || a->M < 1 || a->N < 1 || a->K < 1 || a->group_n < 0 || (epi == EPI_BIAS_RESID && !a->resid) ||
+            ((a->csum || a->xb) && !a->ln_part))
+            throw ArgError{"mocr_op_gemm_pers: bad argument", MOCR_ERR_ARG};
+        if (a->tile < TILE_PERSISTENT) throw ArgError{"mocr_op_gemm_pers: the persistent kernel only (tile codes from 4096)", MOCR_ERR_ARG};
+        // the GemmCall run_encoder builds for a layer GEMM: dense rows, the residual, the column groups, the fold operands
+        const LnFold f{a->ln_part, a->csum, a->xb};
+        GemmCall c = gemm_call("op_gemm_pers", a->A, a->K, a->W, a->bias, a->out, a->N, a->M, a->N, a->K, epi, a->tile);
+        c.resid = a->resid; c.group_n = a->group_n;
+        if (a->ln_part) c.lnf = &f;
+        gemm<bf16_t>(e, c);
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int mocr_last_pers_launch(mocr_engine* e, int32_t out[4]) {
+    return guarded(e, [&] {
+        if (!out) throw ArgError{"mocr_last_pers_launch: null pointer", MOCR_ERR_ARG};
+        const int32_t v[4] = {g_last_pers.blocks, g_last_pers.strips, g_last_pers.tiles, g_last_pers.group_n};
         memcpy(out, v, sizeof(v));
     });
 }

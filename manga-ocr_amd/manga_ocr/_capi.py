@@ -67,6 +67,12 @@ class MocrGemmArgs(C.Structure):
         [("slab_stride", C.c_int64)] + [(n, C.c_void_p) for n in ("A", "W", "bias", "out", "resid")]
 
 
+class MocrGemmPersArgs(C.Structure):
+    """include/mocr.h: mocr_gemm_pers_args"""
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "M", "N", "K", "epilogue", "tile", "group_n")] + \
+        [(n, C.c_void_p) for n in ("A", "W", "bias", "out", "resid", "ln_part", "csum", "xb")]
+
+
 DECODE_PLAN_FIELDS = 25   # MOCR_DECODE_PLAN_FIELDS
 
 
@@ -162,6 +168,9 @@ SYMBOLS = {
     "mocr_decode_plan": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "mocr_op_gemm_args": (C.c_int, [_P, C.POINTER(MocrGemmArgs)]),
     "mocr_last_tile_launch": (C.c_int, [_P, _P]),
+    "mocr_encoder_groups": (C.c_int, [_P, C.c_int32, _P]),
+    "mocr_op_gemm_pers": (C.c_int, [_P, C.POINTER(MocrGemmPersArgs)]),
+    "mocr_last_pers_launch": (C.c_int, [_P, _P]),
     "mocr_op_latent_attention": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64]),
     "mocr_op_quant_fp8": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float]),
     "mocr_op_latent_attention_fp8": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_float]),

@@ -593,6 +593,23 @@ class Engine:
         self._check(self.lib.mocr_last_tile_launch(self._h, _ptr(out)))
         return dict(zip(("tile", "ring", "blocks", "split"), (int(v) for v in out)))
 
+    def encoder_groups(self, n: int) -> dict:
+        """N-tiles per column group of the tile order of the encoder's QKV and FC1 for n crops (include/mocr.h, mocr_encoder_groups)."""
+        out = np.zeros(2, dtype=np.int32)
+        self._check(self.lib.mocr_encoder_groups(self._h, int(n), _ptr(out)))
+        return {"qkv": int(out[0]), "fc1": int(out[1])}
+
+    def op_gemm_pers(self, **kw) -> None:
+        """The persistent encoder GEMM as the encoder launches it; keyword arguments are the fields of mocr_gemm_pers_args
+        (buffers as device tensors or addresses)."""
+        self._check(self.lib.mocr_op_gemm_pers(self._h, self._args(_capi.MocrGemmPersArgs, kw)))
+
+    def last_pers_launch(self) -> dict:
+        """The calling thread's last launch of the persistent GEMM (include/mocr.h, mocr_last_pers_launch)."""
+        out = np.zeros(4, dtype=np.int32)
+        self._check(self.lib.mocr_last_pers_launch(self._h, _ptr(out)))
+        return dict(zip(("blocks", "strips", "tiles", "group_n"), (int(v) for v in out)))
+
     def op_latent_attention(self, d_qt, d_x, d_out, n, length, x_batch_stride) -> None:
         self._check(self.lib.mocr_op_latent_attention(self._h, _ptr(d_qt), _ptr(d_x), _ptr(d_out), n, length, x_batch_stride))
 

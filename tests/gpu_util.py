@@ -72,6 +72,43 @@ def _store(x, dtype):
     return bf16_round(np.asarray(x, np.float32)).astype(np.float64) if dtype == "bf16" else np.asarray(x, np.float32).astype(np.float64)
 
 
+ACC = 2.0 ** -16                    # fp32 accumulation, relative to the sum of the absolute terms
+GELU_SLOPE = 1.13                   # GELU's largest slope
+_EPI_SLAB, _EPI_BIAS_GELU = 0, 2
+
+
+def gelu64(x):
+    from scipy.special import erf
+    return 0.5 * x * (1.0 + erf(x / np.sqrt(2.0)))
+
+
+def gemm_bound(dtype, epi, ref_pre, s1, bias, resid=None, out_f32=False):
+    """(reference of a GEMM's output, elementwise tolerance) from the float64 product ref_pre = A W^T and S1 = |A| |W|^T:
+    |err| <= u |ref| + ACC S1' with S1' = S1 + |bias| (+ |resid|) the sum of the absolute terms, u = 2^-8 for a bf16 output
+    and 0 for an fp32 one (slabs, out_f32).  Fused GELU: GELU_SLOPE x the pre-activation bound, + 1e-5 of the row's largest
+    |ref| (+ 3e-5 for bf16 outputs) for the device's erf."""
+    if epi == _EPI_SLAB:
+        return ref_pre, ACC * s1
+    u = BF16_ULP if (dtype == "bf16" and not out_f32) else 0.0
+    pre, s1b = ref_pre + bias, s1 + np.abs(bias)
+    if resid is not None:
+        pre, s1b = pre + resid, s1b + np.abs(resid)
+    if epi == _EPI_BIAS_GELU:
+        ref = gelu64(pre)
+        erf_allowance = 1e-5 * np.abs(ref).max(-1, keepdims=True) + (3e-5 if dtype == "bf16" else 0.0)
+        return ref, u * np.abs(ref) + GELU_SLOPE * ACC * s1b + erf_allowance
+    return pre, u * np.abs(pre) + ACC * s1b
+
+
+def check_elementwise(got, ref, tol, what):
+    """every element within its own tolerance; returns the worst err / tol"""
+    assert np.isfinite(got).all(), f"{what}: non-finite output (a tile no block took, or a NaN row of A reached an output)"
+    err = np.abs(got - ref)
+    bad = np.argwhere(err > tol)
+    assert bad.size == 0, f"{what}: {len(bad)} elements out of tolerance, first at {tuple(bad[0])}: got {got[tuple(bad[0])]} want {ref[tuple(bad[0])]}"
+    return float((err / tol).max())
+
+
 def _grid_vals(rs, shape, scale=1.0):
     """values on a 2^-10 grid (|v| < 8 scale): fp32 sums of a few dozen of them are exact in any order"""
     return (np.round(rs.standard_normal(shape) * scale * 256) / 1024).clip(-8 * scale, 8 * scale).astype(np.float32)

@@ -21,7 +21,8 @@ import functools
 import numpy as np
 import pytest
 
-from gpu_util import BF16_ULP, _nan, _store, engine, report
+from gpu_util import ACC, _nan, _store, engine, report
+from gpu_util import check_elementwise as _check, gemm_bound as _bound      # the bound stated above
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -30,8 +31,6 @@ EPI_SLAB, EPI_BIAS, EPI_BIAS_GELU, EPI_ARGMAX = 0, 1, 2, 6
 D, F, V = 768, 3072, 6144
 GEMMS = {"qkv": (3 * D, D), "proj": (D, D), "fc1": (F, D), "fc2": (D, F), "vocab": (V, D)}
 GUARD = 3
-ACC = 2.0 ** -16                    # fp32 accumulation, relative to the sum of the absolute terms
-GELU_SLOPE = 1.13
 DTYPES = ["fp32", "bf16"]
 
 ROWS = (8, 72, 136, 256, 288, 512, 960, 1024, 1216, 1280, 2304, 2560)
@@ -190,11 +189,6 @@ def _np(t):
     return t.float().cpu().numpy().astype(np.float64)
 
 
-def _gelu(x):
-    from scipy.special import erf
-    return 0.5 * x * (1.0 + erf(x / np.sqrt(2.0)))
-
-
 @functools.lru_cache(maxsize=4)
 def _operands(dtype, M, N, K):
     """A [M, K], W [N, K] as the engine stores them (float64 values), bias [N]"""
@@ -248,27 +242,6 @@ def _launch(eng, dtype, M, N, K, tile, split, epi, *, lda=0, ldo=0, group_n=0):
     assert np.isnan(got[:, M:]).all(), "guard rows written"
     assert np.isnan(got[:, :M, N:]).all(), "columns behind N written"
     return got[:, :M, :N], rec
-
-
-def _check(got, ref, tol, what):
-    assert np.isfinite(got).all(), f"{what}: non-finite output (a tile no block took, or a NaN row of A reached an output)"
-    err = np.abs(got - ref)
-    bad = np.argwhere(err > tol)
-    assert bad.size == 0, f"{what}: {len(bad)} elements out of tolerance, first at {tuple(bad[0])}: got {got[tuple(bad[0])]} want {ref[tuple(bad[0])]}"
-    return float((err / tol).max())
-
-
-def _bound(dtype, epi, ref_pre, s1, bias):
-    """(reference of the output, elementwise tolerance) from the float64 pre-epilogue product"""
-    u = BF16_ULP if (dtype == "bf16" and epi != EPI_SLAB) else 0.0
-    if epi == EPI_SLAB:
-        return ref_pre, ACC * s1
-    pre, s1b = ref_pre + bias, s1 + np.abs(bias)
-    if epi == EPI_BIAS_GELU:
-        ref = _gelu(pre)
-        erf_allowance = 1e-5 * np.abs(ref).max(-1, keepdims=True) + (3e-5 if dtype == "bf16" else 0.0)
-        return ref, u * np.abs(ref) + GELU_SLOPE * ACC * s1b + erf_allowance
-    return pre, u * np.abs(pre) + ACC * s1b
 
 
 def _forms(eng, dtype):

@@ -38,7 +38,7 @@ def test_config_struct_matches_header():
 
 
 @pytest.mark.parametrize("cname,pyname", [("mocr_token_args", "MocrTokenArgs"), ("mocr_smallm_args", "MocrSmallmArgs"),
-                                          ("mocr_latent_args", "MocrLatentArgs")])
+                                          ("mocr_latent_args", "MocrLatentArgs"), ("mocr_gemm_pers_args", "MocrGemmPersArgs")])
 def test_operator_arg_structs_match_header(cname, pyname):
     """the decode operator hooks' argument structs: same fields, same order, same C types as the ctypes mirrors"""
     import ctypes as C

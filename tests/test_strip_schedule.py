@@ -1,52 +1,13 @@
 """CPU: the strip schedule of the persistent encoder GEMM (csrc/kernels_gemm_pers.h, STRIP; host mirror pers_strip_rows /
-pers_strip_wins in csrc/engine.hip) restated in Python and checked as a PROPERTY over many shapes: whatever M, the number
-of 256-column slices and the grid, every (row, slice) of the output is owned by exactly one tile of exactly one block, no
-tile's window reads a row behind M, a half tile owns at most 128 rows and a block has at most one.  The GPU tests
-(tests/test_gpu_kernels.py::test_gemm_persistent_strip_schedule*) check the kernel itself at a handful of shapes; this
-pins the arithmetic they share."""
+pers_strip_wins in csrc/engine.hip) restated in Python (tests/pers_schedule.py) and checked as a PROPERTY over many shapes:
+whatever M, the number of 256-column slices and the grid, every (row, slice) of the output is owned by exactly one tile of
+exactly one block, no tile's window reads a row behind M, a half tile owns at most 128 rows and a block has at most one.
+The GPU tests (tests/test_gpu_kernels.py::test_gemm_persistent_strip_schedule*, tests/test_gpu_encoder_gemm.py) check the
+kernel itself at a handful of shapes; this pins the arithmetic they share."""
 import numpy as np
 import pytest
 
-
-def strip_blocks(M, ntn, grid):
-    """-> list of (block, col, [(m0, lo, hi, half), ...]) exactly as the kernel derives them from blockIdx.x."""
-    out = []
-    slots = grid >> 3
-    spx = slots // ntn
-    used = spx * ntn
-    nstrips = 8 * spx + (8 * (slots - used)) // ntn
-    for b in range(grid):
-        xcd, k = b & 7, b >> 3
-        if k < used:
-            strip, col = xcd * spx + k // ntn, k % ntn
-        else:
-            j = (k - used) * 8 + xcd
-            strip, col = 8 * spx + j // ntn, j % ntn
-        if strip >= nstrips:
-            continue
-        U = (M + 15) >> 4
-        base, extra = U // nstrips, U % nstrips
-        u0 = strip * base + min(strip, extra)
-        nu = base + (1 if strip < extra else 0)
-        rs, re = u0 * 16, min(M, (u0 + nu) * 16)
-        if re <= rs:
-            continue
-        R = re - rs
-        rem = R & 255
-        ntl = (R >> 8) + (1 if rem else 0)
-        hpos = -1
-        if rem and rem <= 128:
-            v = strip % 3
-            hpos = ntl - 1 if v == 0 else 0 if v == 1 else ntl >> 1
-        tiles = []
-        for t in range(ntl):
-            half = t == hpos
-            lo = rs + 256 * t - ((256 - rem) if (hpos >= 0 and t > hpos) else 0)
-            hi = min(re, lo + (rem if half else 256))
-            m0 = max(0, min(lo, hi - (128 if half else 256)))
-            tiles.append((m0, lo, hi, half))
-        out.append((b, col, tiles))
-    return out
+from pers_schedule import strip_blocks
 
 
 @pytest.mark.parametrize("ntn", [1, 2, 3, 4, 9, 12])
