@@ -381,6 +381,85 @@ int mocr_recognize_gray_host_shared(mocr_engine* e, const uint8_t* gray, int32_t
  * mocr_decode_slot_steps): how a caller sees that sharing happened - 64 for 512 rows over 64 crops in one batch. */
 int64_t mocr_encoded_crops(mocr_engine* e);
 
+/* ---- token automata -----------------------------------------------------------------------------
+ * Greedy decoding under a constraint that depends on what the row has emitted so far: a lexicon (a trie over token ids) or a
+ * pattern.  This is transformers' prefix_allowed_tokens_fn in its history-dependent form, at one decode row per crop whatever
+ * the size of the list.
+ *   A TOKEN AUTOMATON is a deterministic finite automaton over token ids: states 0 .. n_states - 1, state 0 the start, given
+ *     in CSR form - edge_begin [n_states + 1], edge_token / edge_next [n_edges] hold the edges of every state sorted by token,
+ *     strictly ascending, and accepting [n_states] one byte per state.  EOS is never an edge token.
+ *   A row decoded under an automaton is in a state s: the start state before the first generated token.  At the step that
+ *     chooses ids[L]:
+ *       the automaton's set A(s) = the edge tokens of s, plus EOS iff s is accepting; A(MOCR_STATE_DEAD) is empty;
+ *       the step's effective set = A(s) AND the row's token set, minus the row's n-gram bans - sets and bans exactly as in
+ *         the sections above.  The automaton is the only thing that can take EOS away: the engine still adds EOS to every
+ *         token set, so EOS survives the intersection exactly when s accepts;
+ *       DEAD-END RULE: an empty effective set becomes {EOS} - the row ends there and every step keeps a finite maximum.  The
+ *         rule applies to rows under an automaton only;
+ *       ids are the arg-max over the effective set (equal logits: the lowest id), scores and the four alternatives are
+ *         renormalised over it - word for word the rule of the constrained calls.
+ *     After the step, every token stored by a row that was unfinished before the step, and that is not EOS, moves the state:
+ *     s' = next(s, tok), or MOCR_STATE_DEAD where s has no such edge.  The last token of a row that ends by
+ *     generate(max_length) is included; EOS moves nothing.  Forced prefix tokens walk the automaton like emitted ones: one
+ *     outside the effective set scores -inf as before, and one without an edge leaves the row DEAD.  The start token, the pad
+ *     tail, the max_len stop and mocr_decode_logits are untouched.
+ *   Automata are per ROW: a batch may mix rows under different automata and rows under none, and the scheduler still merges
+ *     requests.  A row with MOCR_AUTOMATON_NONE gives ids, lengths, scores, alternatives and positions bit-identical to the
+ *     same row of a batch of the same mode and size in which nobody brings an automaton - also inside a batch with automaton
+ *     rows.  A batch in which nobody brings an automaton launches exactly what it launched before.  A row under the universal
+ *     automaton - one accepting state with a self-loop on every token except EOS - is bit-identical to a
+ *     MOCR_AUTOMATON_NONE row.
+ *   How: the rows' effective sets are the per-row masks of the no-repeat n-grams; the token kernel (profile names
+ *     dec_token*_am) looks the stored token up among the old state's edges, block-wide, and rebuilds the row's mask from the
+ *     new state's edges.  The tables live in one device arena allocated at full capacity by the first mocr_automaton_create
+ *     (about 37 MiB; capacity is bounded by edges, not by states x 768 B, so a dictionary-sized trie fits); the rows' states
+ *     (12 B a row and lane) are allocated by the first batch that brings an automaton.
+ *   Beam search is out of scope: the *_beam entry points take no automaton. */
+#define MOCR_MAX_AUTOMATA          256
+#define MOCR_MAX_AUTOMATON_STATES  (1 << 20)    /* over all automata of an engine */
+#define MOCR_MAX_AUTOMATON_EDGES   (1 << 22)
+#define MOCR_AUTOMATON_NONE        0
+enum { MOCR_STATE_NONE = -1, MOCR_STATE_DEAD = -2 };
+typedef struct mocr_automaton_desc {
+    int32_t struct_size;            /* sizeof(mocr_automaton_desc) */
+    int32_t n_states;
+    const int32_t* edge_begin;      /* [n_states + 1], edge_begin[0] = 0, monotone */
+    const int32_t* edge_token;      /* [edge_begin[n_states]] */
+    const int32_t* edge_next;       /* [edge_begin[n_states]], each in [0, n_states) */
+    const uint8_t* accepting;       /* [n_states] */
+} mocr_automaton_desc;
+/* A new automaton; *out_handle >= 1.  Automata are immutable and live until mocr_destroy; the arrays are copied before the
+ * call returns.  Thread-safe.  MOCR_ERR_ARG: a null or short struct, n_states < 1; edge_begin[0] != 0 or edge_begin not
+ * monotone; a token outside [0, vocab) or equal to EOS; tokens of a state not strictly ascending; edge_next outside
+ * [0, n_states); a table or the handle list full.  MOCR_ERR_STATE before mocr_commit_weights. */
+int mocr_automaton_create(mocr_engine* e, const mocr_automaton_desc* desc, int32_t* out_handle);
+int mocr_automaton_count(mocr_engine* e);
+/* Device bytes the automata hold: the arena plus the lanes' row states; 0 until the first create / first automaton batch. */
+int64_t mocr_automaton_state_bytes(mocr_engine* e);
+/* The *_automaton entry points: the *_shared twins plus `automata`, a HOST int32 array [n_rows] of handles (null: every row
+ * MOCR_AUTOMATON_NONE; copied before the call returns), and out_state int32 [n_rows] (nullable; host, or device for the device
+ * twin): the state the row was in after its last non-EOS token, in its automaton's own numbering; MOCR_STATE_NONE for a row
+ * without an automaton or of a sliver region, MOCR_STATE_DEAD for a dead row.  With both null they ARE the shared calls.  An
+ * unknown handle is MOCR_ERR_ARG before any work. */
+int mocr_recognize_images_automaton(mocr_engine* e, const mocr_image* images, int32_t n_images, int32_t n_rows, const int32_t* source,
+                                    int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
+                                    const int32_t* sets, const int32_t* ngram, float* out_pos, const int32_t* prefix,
+                                    const int32_t* prefix_len, int32_t prefix_ld, const int32_t* automata, int32_t* out_state);
+int mocr_recognize_regions_automaton(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                     int32_t n_regions, int32_t n_rows, const int32_t* source, int32_t* out_ids, int32_t* out_len,
+                                     float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets, const int32_t* ngram,
+                                     float* out_pos, const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld,
+                                     const int32_t* automata, int32_t* out_state);
+int mocr_recognize_device_automaton(mocr_engine* e, const void* d_gray, int32_t n_planes, int32_t n_rows, const int32_t* source,
+                                    void* d_out_ids, void* d_out_len, void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp,
+                                    const int32_t* sets, const int32_t* ngram, void* d_out_pos, const int32_t* prefix,
+                                    const int32_t* prefix_len, int32_t prefix_ld, const int32_t* automata, void* d_out_state);
+int mocr_recognize_gray_host_automaton(mocr_engine* e, const uint8_t* gray, int32_t n_planes, int32_t n_rows, const int32_t* source,
+                                       int32_t max_len_override, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                       float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos,
+                                       const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld, const int32_t* automata,
+                                       int32_t* out_state);
+
 /* Preprocessing only (test hook): out_gray [n, image_size, image_size] uint8 (host) = the plane the encoder sees
  * in each of its three equal input channels before the 1/255 and (x - 0.5)/0.5 scaling. */
 int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t* out_gray);
@@ -670,6 +749,25 @@ int mocr_op_dec_token_prefix(mocr_engine* e, const mocr_token_args* a, const flo
  * the start token's bit cleared where d_ngram_of_row[row] == 1 (the first generated token already sees L = 1). */
 int mocr_op_ngram_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
                        const int32_t* d_ngram_of_row, int32_t rows);
+/* The token step with token automata: mocr_op_dec_token_prefix plus the tables in CSR form over GLOBAL state numbers -
+ * d_edge_begin int32 [states + 1], d_edge_token / d_edge_next int32 [edges], d_accepting uint8 [states] - and by ROW
+ * d_aut_base_of_row int32 [rows] (the row's start state, -1: no automaton) and d_aut_state int32 [rows] (in / out: the state
+ * the row is in, MOCR_STATE_DEAD allowed).  A row that was unfinished before the step and brings an automaton walks its state
+ * with the stored token and, if still unfinished, gets row_mask[row] rebuilt by the rule of the token automata section; a row
+ * without one takes mocr_op_dec_token_prefix's path.  Needs d_row_mask.  The six new pointers all NULL is that call. */
+int mocr_op_dec_token_automaton(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                                const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
+                                const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
+                                const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row,
+                                const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld, const float* d_tgt_val,
+                                const int32_t* d_edge_begin, const int32_t* d_edge_token, const int32_t* d_edge_next,
+                                const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state);
+/* The start of a batch with token automata: for rows [0, rows), a row with d_aut_base_of_row[row] >= 0 gets
+ * d_row_mask[row] = A(start) AND its base set, minus the start token where d_ngram_of_row[row] == 1, {EOS} if that is empty,
+ * and d_aut_state[row] = its start state; any other row gets what mocr_op_ngram_init gives it and MOCR_STATE_NONE. */
+int mocr_op_automaton_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
+                           const int32_t* d_ngram_of_row, int32_t rows, const int32_t* d_edge_begin, const int32_t* d_edge_token,
+                           const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state);
 /* The expansion of shared encodings, as a batch runs it: d_enc holds max(n_src, n_rows) rows of 197 x hidden elements of the
  * engine's dtype, its first n_src rows the encodings; d_src_of_row is a device int32 [n_rows] of indices into them.  On return
  * row r < n_rows holds what row d_src_of_row[r] held before the call (in place from the caller's view: the engine stages the

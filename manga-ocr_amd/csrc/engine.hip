@@ -137,8 +137,12 @@ struct LaneCtx {
     unsigned* row_mask = nullptr;                   // [Bp][V / 32] the effective set of every row's next step (base set minus the bans), by row
     int* row_ident = nullptr;                       // [Bp] 0, 1, 2, ...: the "set of every row" that makes the masked kernels read row_mask[row]
     int* ngram_of_row = nullptr;                    // [Bp] no_repeat_ngram_size of every row (0: off), by row
+    // token automata: allocated by the first batch with a row that brings one (ensure_automaton_buffers)
+    int* aut_base_of_row = nullptr;                 // [Bp] the global number of every row's start state (-1: no automaton), by row
+    int* aut_state = nullptr;                       // [Bp] the global state every row is in (AUT_STATE_NONE / AUT_STATE_DEAD), by row
+    int* aut_state_out = nullptr;                   // [Bp] ... in the automaton's own numbering: what the jobs' out_state receives
     // token positions: allocated by the first batch that asks (ensure_pos_buffers)
-    void* pos_hist = nullptr;                       // [Bp][max_len][768] T (+ one GEMM tile of rows): the last layer's LayerNorm-1 output of every
+    void* pos_hist = nullptr;                      // [Bp][max_len][768] T (+ one GEMM tile of rows): the last layer's LayerNorm-1 output of every
                                                     // (row, input position), by row like ids - what the cross-attention query projection read.
                                                     // A batch packs it as [rows][its generate(max_length)][768]
     float* pos_out = nullptr;                       // [Bp][max_len][MOCR_POSITION_FIELDS] by row like ids
@@ -193,7 +197,9 @@ struct Job {
     bool out_host = false;
     std::vector<int32_t> sets;      // token constraints (the *_constrained entry points): one set handle per crop; empty = all MOCR_TOKEN_SET_ALL
     std::vector<int32_t> ngram;     // no-repeat n-grams (the *_norepeat entry points): one size per crop; empty = all 0
-    float* out_pos = nullptr;       // nullable (the *_positions entry points): [n][max_len][MOCR_POSITION_FIELDS]; host or device like out_ids
+    std::vector<int32_t> automata;  // token automata (the *_automaton entry points): one handle per row; empty = all MOCR_AUTOMATON_NONE
+    int32_t* out_state = nullptr;   // nullable: [n] the rows' final automaton states; host or device like out_ids
+    float* out_pos = nullptr;      // nullable (the *_positions entry points): [n][max_len][MOCR_POSITION_FIELDS]; host or device like out_ids
     std::vector<int32_t> prefix_len;    // forced prefixes (the *_prefix entry points): one length per crop; empty = all 0
     std::vector<int32_t> prefix;        // ... and the tokens, [n][prefix_ld] (a copy: the caller's arrays need not outlive the call)
     int prefix_ld = 0;
@@ -217,7 +223,9 @@ struct DecMode {
                                     // masked (EPI_*_M / MASK) form of the level's LM head and token kernel
     bool ngram = false;             // a row has no_repeat_ngram_size > 0: the masks are the per-row ones (row_mask through row_ident)
                                     // and the token kernel is the NGRAM one, which rebuilds them
-    bool positions = false;         // a job asked for token positions: the steps record pos_hist, finish_batch runs the deferred pass
+    bool automaton = false;         // a row brings a token automaton (implies `ngram`: the same per-row masks): the token kernel is the
+                                    // AUTOMATON one, which also walks the rows' states, and the batch starts with automaton_init_kernel
+    bool positions = false;        // a job asked for token positions: the steps record pos_hist, finish_batch runs the deferred pass
                                     // (a beam batch too: its selection then also keeps the beam-index trails the pass gathers by)
     bool prefix = false;            // a row has a forced prefix: the steps run scored and masked (level >= 1, mask; unconstrained rows read
                                     // set 0), the LM head also leaves the forced column's value and the token kernel stores the forced token
@@ -227,12 +235,13 @@ struct DecMode {
     bool beam_tokens = false;       // ... in which a job asks for token scores or brings a token set other than MOCR_TOKEN_SET_ALL: the
                                     // selection runs in its token form (level and mask stay 0: the LM head and the caches do not change)
     // a graph captured in one mode is never replayed in another: the mode's share of the decode-graph key (6 bits; a beam
-    // batch: bit 6, its token form: bit 7, and its configuration - kernel arguments of the captured launches - in the bits
-    // above, beam_key)
+    // batch: bit 6, its token form: bit 7, an automaton batch: bit 8, and a beam batch's configuration - kernel arguments of
+    // the captured launches - in the bits above, beam_key)
     int key_bits() const {
-        return level + (mask ? 4 : 0) + (ngram ? 8 : 0) + (positions ? 16 : 0) + (prefix ? 32 : 0) + (beam ? 64 : 0) + (beam_tokens ? 128 : 0);
+        return level + (mask ? 4 : 0) + (ngram ? 8 : 0) + (positions ? 16 : 0) + (prefix ? 32 : 0) + (beam ? 64 : 0) + (beam_tokens ? 128 : 0) +
+               (automaton ? 256 : 0);
     }
-    static constexpr int KEY_SPAN = 256;
+    static constexpr int KEY_SPAN = 512;
     int epilogue() const { return mask ? (level == 2 ? EPI_TOPK_M : level == 1 ? EPI_ARGMAX_LSE_M : EPI_ARGMAX_M)
                                        : (level == 2 ? EPI_TOPK : level == 1 ? EPI_ARGMAX_LSE : EPI_ARGMAX); }
     // profile names of the fused LM head and of the token kernel
@@ -243,7 +252,8 @@ struct DecMode {
         static const char* const names[3][3] = {{"dec_token", "dec_token_m", "dec_token_ng"},
                                                 {"dec_token_lse", "dec_token_lse_m", "dec_token_lse_ng"},
                                                 {"dec_token_topk", "dec_token_topk_m", "dec_token_topk_ng"}};
-        return names[level][ngram ? 2 : mask ? 1 : 0];
+        static const char* const automaton_names[3] = {"dec_token_am", "dec_token_lse_am", "dec_token_topk_am"};
+        return automaton ? automaton_names[level] : names[level][ngram ? 2 : mask ? 1 : 0];
     }
 };
 
@@ -263,9 +273,11 @@ static DecMode mode_of(const std::vector<Job>& jobs) {
         m.level = std::max(m.level, j.out_alt_ids ? 2 : j.out_logp ? 1 : 0);
         for (int32_t h : j.sets) m.mask = m.mask || h != MOCR_TOKEN_SET_ALL;
         for (int32_t g : j.ngram) m.ngram = m.ngram || g > 0;
+        m.automaton = m.automaton || !j.automata.empty();      // (slice_rows: an array of MOCR_AUTOMATON_NONE alone comes as empty)
         m.positions = m.positions || j.out_pos;
         m.prefix = m.prefix || !j.prefix_len.empty();
     }
+    m.ngram = m.ngram || m.automaton;           // an automaton's sets reach the step through the same per-row masks
     if (m.prefix) m.level = std::max(m.level, 1);      // a forced token is one more per-row fact of the masked, scored step
     m.mask = m.mask || m.ngram || m.prefix;     // the bans are applied through the rows' masks, which start as the rows' sets
     return m;
@@ -283,6 +295,7 @@ struct Lane {
     DecMode mode;                   // mode_of(jobs)
     std::vector<int> h_sets, h_ngram;   // the uploads of set_of_row / ngram_of_row stage from here
     std::vector<int> h_plen, h_prefix;  // ... and those of prefix_len / prefix
+    std::vector<int> h_aut;             // ... and that of aut_base_of_row
     int t = 0, steps = 0, chunk = 0;
     bool finishing = false;         // a flag of this batch has reported a finished row: rows are leaving, chunks get shorter
     bool flag_pending[2] = {false, false};
@@ -322,6 +335,7 @@ struct mocr_engine : LaneCtx {
     bool use_latent(int n) const { return latent && n > classic_rows; }
     int smallm_rows = 0;            // bf16: batches of up to this many rows take the one-launch-per-projection path (kernels_smallm.h)
     bool beam_batch = false;        // the batch being scheduled is a beam batch (set with `regime`): no one-launch-per-projection path
+    bool automaton_batch = false;   // the batch being advanced brings token automata (set with `regime`): the token kernel gets the tables
     bool use_smallm(int n) const { return n <= smallm_rows && !use_latent(n) && !beam_batch; }
     std::vector<mocr_beam_config> beam_cfgs;    // the beam configurations seen: a decode graph bakes one in, its key names it by index
     std::map<std::string, std::vector<float>> host_w;
@@ -339,6 +353,14 @@ struct mocr_engine : LaneCtx {
     unsigned* tok_table = nullptr;
     std::vector<std::vector<uint32_t>> tok_sets;
     std::map<std::vector<uint32_t>, int> tok_index;
+    // token automata (mocr_automaton_create): one device arena in CSR form over global state numbers, allocated at full
+    // capacity by the first create so that its addresses - kernel arguments of captured decode graphs - never move; a new
+    // automaton is appended behind the last.  aut_first[h] / aut_states[h]: handle h's first global state and state count
+    // (handle 0 = MOCR_AUTOMATON_NONE holds nothing)
+    int *aut_edge_begin = nullptr, *aut_edge_token = nullptr, *aut_edge_next = nullptr;
+    uint8_t* aut_accepting = nullptr;
+    std::vector<int> aut_first{0}, aut_states{0};
+    int aut_n_states = 0, aut_n_edges = 0;
     // decode-step HIP graphs, keyed by (lane, rows, (max_len, context bucket, DecMode::key_bits), steps per graph)
     std::map<std::tuple<int, int, int, int, int>, hipGraphExec_t> graphs;      // + the regime
     void bind(int i) { static_cast<LaneCtx&>(*this) = lanes[i].ctx; }
@@ -1297,6 +1319,7 @@ struct DecTokenArgs {
     const float* top_val; const int* top_idx;             // alternatives steps (st.alt_ids set) on the candidate path: the tiles' four best
     float* x_f32; void* x_t;
     void* cache; uint8_t* cache8; float inv8; long long cstride;   // layer-0 latent cache row (T or e4m3), indexed by row
+    DecAutomata aut;                                      // token automata (all set: the AUTOMATON form; the state then has the per-row masks)
 };
 
 // The operator hooks come with a bare DecState, so the kernel's form is read off the state: scores / alternatives /
@@ -1306,6 +1329,7 @@ void launch_dec_token(mocr_engine* e, const DecState& st, const DecTokenArgs& a,
     auto& w = e->w;
     DecMode m;
     m.level = st.alt_ids ? 2 : st.scores ? 1 : 0; m.mask = st.tok_mask != nullptr; m.ngram = st.row_mask != nullptr;
+    m.automaton = a.aut.state != nullptr;
     const bool cand = a.ncand > 0;
     ProfScope ps(e, FIRST ? "dec_token_first" : m.token_name(), 0, FIRST ? 0.0 : (double)n * e->V * 4 * a.nslab);
     auto launch = [&](auto kernel) {
@@ -1313,10 +1337,15 @@ void launch_dec_token(mocr_engine* e, const DecState& st, const DecTokenArgs& a,
                            w.posd, w.embg, w.embb, a.x_f32, reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps, reinterpret_cast<T*>(a.cache),
                            a.cstride, cand ? a.cand_val : nullptr, cand ? a.cand_idx : nullptr, a.ncand, a.cache8, a.inv8,
                            cand && m.level >= 1 ? a.cand_sum : nullptr, cand && m.level >= 2 ? a.top_val : nullptr,
-                           cand && m.level >= 2 ? a.top_idx : nullptr);
+                           cand && m.level >= 2 ? a.top_idx : nullptr, a.aut);
     };
     // <T, 768, FIRST, SCORES, TOPK, MASK, NGRAM>: the start token's kernel, and level x (plain, MASK, NGRAM) for the steps
     if constexpr (FIRST) launch(dec_token_kernel<T, 768, true>);      // (the start step has nothing to score or to mask)
+    else if (m.automaton) switch (m.level) {      // ... and the AUTOMATON form of every level
+        case 0: launch(dec_token_kernel<T, 768, false, false, false, true, true, true>); break;
+        case 1: launch(dec_token_kernel<T, 768, false, true, false, true, true, true>); break;
+        default: launch(dec_token_kernel<T, 768, false, true, true, true, true, true>); break;
+    }
     else switch (m.level * 3 + (m.ngram ? 2 : m.mask ? 1 : 0)) {
         case 0: launch(dec_token_kernel<T, 768, false>); break;
         case 1: launch(dec_token_kernel<T, 768, false, false, false, true>); break;
@@ -1343,6 +1372,8 @@ void dec_token(mocr_engine* e, const DecState& st, int nslab, int n, int ncand =
     a.cache8 = (lat && e->fp8attn) ? e->x8cache : nullptr;
     a.inv8 = (lat && e->fp8attn) ? 1.0f / e->w.sx_self[0] : 0.f;
     a.cstride = (long long)e->cfg.max_len * e->D;
+    if (!FIRST && e->automaton_batch)
+        a.aut = DecAutomata{e->aut_edge_begin, e->aut_edge_token, e->aut_edge_next, e->aut_accepting, e->aut_base_of_row, e->aut_state};
     launch_dec_token<T, FIRST>(e, st, a, n);
 }
 
@@ -2143,6 +2174,39 @@ static void launch_ngram_init(mocr_engine* e, unsigned* row_mask, const unsigned
     HIPCHECK(hipGetLastError());
 }
 
+// ---- token automata --------------------------------------------------------------
+constexpr size_t AUT_ARENA_BYTES = ((size_t)MOCR_MAX_AUTOMATON_STATES + 1) * sizeof(int) + 2 * (size_t)MOCR_MAX_AUTOMATON_EDGES * sizeof(int) +
+                                   (size_t)MOCR_MAX_AUTOMATON_STATES;
+
+// The device arena of the automata, allocated once at full capacity by the first mocr_automaton_create (about 37 MiB): the
+// captured decode graphs hold its addresses, so it never grows or moves.
+static void ensure_automaton_arena(mocr_engine* e) {
+    if (e->aut_edge_begin) return;
+    e->aut_edge_begin = e->dalloc<int>((size_t)MOCR_MAX_AUTOMATON_STATES + 1);
+    e->aut_edge_token = e->dalloc<int>((size_t)MOCR_MAX_AUTOMATON_EDGES);
+    e->aut_edge_next = e->dalloc<int>((size_t)MOCR_MAX_AUTOMATON_EDGES);
+    e->aut_accepting = e->dalloc<uint8_t>((size_t)MOCR_MAX_AUTOMATON_STATES);
+}
+
+// The rows' start states and current states, for the bound lane: allocated by the first batch in which a row brings an
+// automaton, like the alternatives buffers (12 B a row).
+static void ensure_automaton_buffers(mocr_engine* e) {
+    if (e->aut_state) return;
+    const size_t Bp = (size_t)e->Bp;
+    e->aut_base_of_row = e->dalloc<int>(Bp);
+    e->aut_state = e->dalloc<int>(Bp);
+    e->aut_state_out = e->dalloc<int>(Bp);
+}
+
+static void launch_automaton_init(mocr_engine* e, unsigned* row_mask, const unsigned* base_mask, const int* base_set_of_row,
+                                  const int* ngram_of_row, int rows, const int* edge_begin, const int* edge_token,
+                                  const uint8_t* accepting, const int* aut_base_of_row, int* aut_state) {
+    ProfScope ps(e, "automaton_init", 0, (double)rows * (e->V / 32) * 8);
+    hipLaunchKernelGGL(automaton_init_kernel, dim3(rows), dim3(192), 0, e->stream, row_mask, base_mask, base_set_of_row, ngram_of_row, rows,
+                       e->V / 32, e->cfg.start_id, e->cfg.eos_id, edge_begin, edge_token, accepting, aut_base_of_row, aut_state);
+    HIPCHECK(hipGetLastError());
+}
+
 // ---- token positions --------------------------------------------------------------
 // The deferred pass walks a batch's rows in chunks whose query and key scratch stays under this many bytes whatever
 // max_batch is (one row needs (197 + max_len) x 768 elements: 87 rows a chunk in bf16 at max_len 300, 43 in fp32).
@@ -2361,7 +2425,22 @@ void start_batch(mocr_engine* e, Lane& L) {
         ensure_tok_table(e);
         ensure_ngram_buffers(e);
         upload_per_row(e, L, L.h_ngram, &Job::ngram, 0, e->ngram_of_row);
-        launch_ngram_init(e, e->row_mask, e->tok_table, e->set_of_row, e->ngram_of_row, L.np);
+        if (!m.automaton) launch_ngram_init(e, e->row_mask, e->tok_table, e->set_of_row, e->ngram_of_row, L.np);
+    }
+    // token automata: the rows' start states (the padding rows and the rows without an automaton: -1), their first masks
+    if (m.automaton) {
+        if (e->V != 6144) throw ArgError{"token automata need the 6144-token vocabulary", MOCR_ERR_UNSUPPORTED};
+        ensure_automaton_buffers(e);
+        L.h_aut.assign((size_t)L.np, -1);
+        int r0 = 0;
+        for (const Job& j : L.jobs) {
+            for (size_t i = 0; i < j.automata.size(); ++i)
+                if (j.automata[i] != MOCR_AUTOMATON_NONE) L.h_aut[r0 + i] = e->aut_first[j.automata[i]];
+            r0 += j.n;
+        }
+        HIPCHECK(hipMemcpyAsync(e->aut_base_of_row, L.h_aut.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        launch_automaton_init(e, e->row_mask, e->tok_table, e->set_of_row, e->ngram_of_row, L.np, e->aut_edge_begin, e->aut_edge_token,
+                              e->aut_accepting, e->aut_base_of_row, e->aut_state);
     }
     // token positions: position 0, the pad tail and the rows of the jobs that did not ask read 0
     if (m.positions) {
@@ -2396,6 +2475,11 @@ void finish_batch(mocr_engine* e, Lane& L) {
     if (L.mode.positions) {      // token positions: the deferred pass over the rows the steps recorded, before the outputs leave
         if (e->cfg.dtype == MOCR_BF16) run_positions<bf16_t>(e, L); else run_positions<float>(e, L);
     }
+    if (L.mode.automaton) {      // token automata: the rows' states in their automata's own numbering
+        hipLaunchKernelGGL(automaton_state_out_kernel, dim3((L.n + 255) / 256), dim3(256), 0, e->stream, (const int*)e->aut_state,
+                           (const int*)e->aut_base_of_row, e->aut_state_out, L.n);
+        HIPCHECK(hipGetLastError());
+    }
     int row0 = 0;
     for (const Job& j : L.jobs) {
         const hipMemcpyKind kind = j.out_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
@@ -2424,6 +2508,11 @@ void finish_batch(mocr_engine* e, Lane& L) {
         if (j.out_pos) {
             const size_t ld = (size_t)e->cfg.max_len * MOCR_POSITION_FIELDS;
             HIPCHECK(hipMemcpyAsync(j.out_pos, e->pos_out + row0 * ld, j.n * ld * sizeof(float), kind, e->stream));
+        }
+        if (j.out_state) {      // (a batch in which nobody brings an automaton keeps no states: every row MOCR_STATE_NONE = -1)
+            if (L.mode.automaton) HIPCHECK(hipMemcpyAsync(j.out_state, e->aut_state_out + row0, (size_t)j.n * sizeof(int), kind, e->stream));
+            else if (j.out_host) std::fill(j.out_state, j.out_state + j.n, (int32_t)MOCR_STATE_NONE);
+            else HIPCHECK(hipMemsetAsync(j.out_state, 0xFF, (size_t)j.n * sizeof(int), e->stream));
         }
         row0 += j.n;
     }
@@ -2569,9 +2658,9 @@ bool pump_once(mocr_engine* e) {
         if (L.active) {
             e->bind((int)i);
             e->regime = L.np0;
-            e->beam_batch = L.mode.beam;
+            e->beam_batch = L.mode.beam; e->automaton_batch = L.mode.automaton;
             advance<T>(e, L);
-            e->regime = 0; e->beam_batch = false;
+            e->regime = 0; e->beam_batch = false; e->automaton_batch = false;
             e->unbind((int)i);
             any = true;
         }
@@ -2585,7 +2674,7 @@ void drive(mocr_engine* e) {
         if (e->cfg.dtype == MOCR_BF16) { while (pump_once<bf16_t>(e)) {} }
         else { while (pump_once<float>(e)) {} }
     } catch (...) {
-        e->regime = 0; e->beam_batch = false;
+        e->regime = 0; e->beam_batch = false; e->automaton_batch = false;
         e->pending.clear();
         for (auto& L : e->lanes) { L.active = false; L.jobs.clear(); (void)hipStreamSynchronize(L.ctx.stream); }
         throw;
@@ -3124,6 +3213,66 @@ int mocr_token_set_count(mocr_engine* e) {
     return token_set_count(e);
 }
 
+// ---- token automata ----------------------------------------------------------------------------
+int mocr_automaton_create(mocr_engine* e, const mocr_automaton_desc* d, int32_t* out_handle) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (!e->committed) throw ArgError{"weights not committed (mocr_commit_weights)", MOCR_ERR_STATE};
+        if (!d || d->struct_size < (int32_t)sizeof(mocr_automaton_desc) || !out_handle || d->n_states < 1 || !d->edge_begin || !d->accepting)
+            throw ArgError{"mocr_automaton_create: bad argument", MOCR_ERR_ARG};
+        const int ns = d->n_states;
+        if (d->edge_begin[0] != 0) throw ArgError{"mocr_automaton_create: edge_begin[0] must be 0", MOCR_ERR_ARG};
+        for (int s = 0; s < ns; ++s)
+            if (d->edge_begin[s + 1] < d->edge_begin[s]) throw ArgError{"mocr_automaton_create: edge_begin is not monotone", MOCR_ERR_ARG};
+        const int ne = d->edge_begin[ns];
+        if (ne > 0 && (!d->edge_token || !d->edge_next)) throw ArgError{"mocr_automaton_create: edges without their arrays", MOCR_ERR_ARG};
+        if ((int)e->aut_first.size() > MOCR_MAX_AUTOMATA || ns > MOCR_MAX_AUTOMATON_STATES - e->aut_n_states ||
+            ne > MOCR_MAX_AUTOMATON_EDGES - e->aut_n_edges)
+            throw ArgError{"mocr_automaton_create: the automaton tables are full", MOCR_ERR_ARG};
+        const int S0 = e->aut_n_states, E0 = e->aut_n_edges;
+        std::vector<int> begin((size_t)ns + 1), next((size_t)ne);
+        for (int s = 0; s <= ns; ++s) begin[s] = E0 + d->edge_begin[s];
+        for (int s = 0; s < ns; ++s)
+            for (int i = d->edge_begin[s]; i < d->edge_begin[s + 1]; ++i) {
+                const int tok = d->edge_token[i];
+                if (tok < 0 || tok >= e->V || tok == e->cfg.eos_id)
+                    throw ArgError{"mocr_automaton_create: edge token outside the vocabulary, or EOS", MOCR_ERR_ARG};
+                if (i > d->edge_begin[s] && tok <= d->edge_token[i - 1])
+                    throw ArgError{"mocr_automaton_create: a state's tokens must be strictly ascending", MOCR_ERR_ARG};
+                if (d->edge_next[i] < 0 || d->edge_next[i] >= ns) throw ArgError{"mocr_automaton_create: edge_next outside [0, n_states)", MOCR_ERR_ARG};
+                next[i] = S0 + d->edge_next[i];
+            }
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        ensure_automaton_arena(e);
+        // fresh states behind the last automaton's: no queued or running batch can hold this handle yet, so the copies race
+        // with nothing (edge_begin[S0] is rewritten with the value it has)
+        HIPCHECK(hipMemcpy(e->aut_edge_begin + S0, begin.data(), begin.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (ne > 0) {
+            HIPCHECK(hipMemcpy(e->aut_edge_token + E0, d->edge_token, (size_t)ne * sizeof(int), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(e->aut_edge_next + E0, next.data(), (size_t)ne * sizeof(int), hipMemcpyHostToDevice));
+        }
+        HIPCHECK(hipMemcpy(e->aut_accepting + S0, d->accepting, (size_t)ns, hipMemcpyHostToDevice));
+        *out_handle = (int32_t)e->aut_first.size();
+        e->aut_first.push_back(S0); e->aut_states.push_back(ns);
+        e->aut_n_states += ns; e->aut_n_edges += ne;
+    });
+}
+
+int mocr_automaton_count(mocr_engine* e) {
+    if (!e) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return (int)e->aut_first.size() - 1;
+}
+
+int64_t mocr_automaton_state_bytes(mocr_engine* e) {
+    if (!e) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int64_t bytes = e->aut_edge_begin ? (int64_t)AUT_ARENA_BYTES : 0;
+    for (const Lane& L : e->lanes)
+        if (L.ctx.aut_state) bytes += 3 * (int64_t)e->Bp * (int64_t)sizeof(int);
+    return bytes;
+}
+
 // ---- one recognise request -----------------------------------------------------------------------
 // What a caller may ask for beyond ids and lengths; every mocr_recognize_* symbol is its source kind's implementation with
 // some of these null.  The outputs are [n][max_len] rows (x MOCR_ALTERNATIVES / MOCR_POSITION_FIELDS), host or device like
@@ -3145,7 +3294,20 @@ struct Request {
     // out_score [rows] receives the hypotheses' scores
     const mocr_beam_config* beam = nullptr;
     float* out_score = nullptr;
+    // token automata (the *_automaton entry points): host [rows] handles (null: every row MOCR_AUTOMATON_NONE), and [rows]
+    // final states, host or device like out_ids
+    const int32_t* automata = nullptr;
+    int32_t* out_state = nullptr;
 };
+
+// token automata: one handle per row, MOCR_AUTOMATON_NONE or an automaton this engine has created; never on a beam request
+static void require_automata(const mocr_engine* e, const Request& r, int n) {
+    if ((r.automata || r.out_state) && r.beam) throw ArgError{"beam search takes no token automaton", MOCR_ERR_ARG};
+    if (!r.automata) return;
+    const int count = (int)e->aut_first.size();
+    for (int i = 0; i < n; ++i)
+        if (r.automata[i] < 0 || r.automata[i] >= count) throw ArgError{"unknown automaton handle (mocr_automaton_create)", MOCR_ERR_ARG};
+}
 
 // shared encodings: every index names an image of the call, and every image is named by a row
 static void require_source(const Request& r, int n) {
@@ -3189,6 +3351,7 @@ static void validate_request(mocr_engine* e, const Request& r, int n, Ready read
     require_sets(e, r.sets, n);
     require_ngram(e, r.ngram, n);
     require_prefix(e, r, n, gen_len);
+    require_automata(e, r, n);
 }
 
 // rows [base, base + n) of a per-crop array whose default is `dflt`, for the job that decodes them (empty: all default)
@@ -3211,6 +3374,8 @@ static void slice_job(Job& j, const Request& r, size_t base, int n, int max_len)
     }
     j.sets = slice_rows(r.sets, base, n, MOCR_TOKEN_SET_ALL);
     j.ngram = slice_rows(r.ngram, base, n, 0);
+    j.automata = slice_rows(r.automata, base, n, MOCR_AUTOMATON_NONE);
+    j.out_state = r.out_state ? r.out_state + base : nullptr;
     j.prefix_len = slice_rows(r.prefix_len, base, n, 0);
     j.prefix.clear(); j.prefix_ld = 0;
     if (!j.prefix_len.empty()) {
@@ -3243,6 +3408,12 @@ static Request request_of(void* out_logp = nullptr, void* out_alt_ids = nullptr,
     r.sets = sets; r.ngram = ngram;
     r.out_pos = static_cast<float*>(out_pos);
     r.prefix = prefix; r.prefix_len = prefix_len; r.prefix_ld = prefix_ld;
+    return r;
+}
+
+// ... and a request with the two arguments the *_automaton twins add
+static Request with_automata(Request r, const int32_t* automata, void* out_state) {
+    r.automata = automata; r.out_state = static_cast<int32_t*>(out_state);
     return r;
 }
 
@@ -3281,6 +3452,15 @@ int mocr_recognize_device_shared(mocr_engine* e, const void* d_gray, int32_t n_p
     return recognize_device(e, d_gray, n_rows, d_out_ids, d_out_len,
                             request_of(d_out_logp, d_out_alt_ids, d_out_alt_logp, sets, ngram, d_out_pos, prefix, prefix_len, prefix_ld,
                                        source, n_planes));
+}
+
+int mocr_recognize_device_automaton(mocr_engine* e, const void* d_gray, int32_t n_planes, int32_t n_rows, const int32_t* source,
+                                    void* d_out_ids, void* d_out_len, void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp,
+                                    const int32_t* sets, const int32_t* ngram, void* d_out_pos, const int32_t* prefix,
+                                    const int32_t* prefix_len, int32_t prefix_ld, const int32_t* automata, void* d_out_state) {
+    return recognize_device(e, d_gray, n_rows, d_out_ids, d_out_len,
+                            with_automata(request_of(d_out_logp, d_out_alt_ids, d_out_alt_logp, sets, ngram, d_out_pos, prefix, prefix_len,
+                                                     prefix_ld, source, n_planes), automata, d_out_state));
 }
 
 int mocr_recognize_device_norepeat(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
@@ -3371,6 +3551,16 @@ int mocr_recognize_gray_host_shared(mocr_engine* e, const uint8_t* gray, int32_t
     return recognize_gray_host(e, gray, n_rows, max_len_override, out_ids, out_len,
                                request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len, prefix_ld,
                                           source, n_planes));
+}
+
+int mocr_recognize_gray_host_automaton(mocr_engine* e, const uint8_t* gray, int32_t n_planes, int32_t n_rows, const int32_t* source,
+                                       int32_t max_len_override, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                       float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos,
+                                       const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld, const int32_t* automata,
+                                       int32_t* out_state) {
+    return recognize_gray_host(e, gray, n_rows, max_len_override, out_ids, out_len,
+                               with_automata(request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len,
+                                                        prefix_ld, source, n_planes), automata, out_state));
 }
 
 int mocr_recognize_gray_host_norepeat(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
@@ -3687,6 +3877,15 @@ int mocr_recognize_images_shared(mocr_engine* e, const mocr_image* images, int32
                                        n_images));
 }
 
+int mocr_recognize_images_automaton(mocr_engine* e, const mocr_image* images, int32_t n_images, int32_t n_rows, const int32_t* source,
+                                    int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
+                                    const int32_t* sets, const int32_t* ngram, float* out_pos, const int32_t* prefix,
+                                    const int32_t* prefix_len, int32_t prefix_ld, const int32_t* automata, int32_t* out_state) {
+    return recognize_images(e, images, n_rows, out_ids, out_len,
+                            with_automata(request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len, prefix_ld,
+                                                     source, n_images), automata, out_state));
+}
+
 int mocr_recognize_images_norepeat(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
                                    float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets,
                                    const int32_t* ngram) {
@@ -3755,6 +3954,7 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
         std::vector<int32_t> view_sets;                 // ... token sets
         std::vector<int32_t> view_ngram;                // ... and no-repeat n-gram sizes
         std::vector<int32_t> view_plen, view_prefix;    // ... and forced prefixes (a sliver's prefix is ignored)
+        std::vector<int32_t> view_automata;             // ... and automata
         for (int i = 0; i < n_rows; ++i) {
             const int v = view_of[req.source ? req.source[i] : i];
             if (v < 0) continue;
@@ -3762,6 +3962,7 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
             view_src.push_back(v);
             if (req.sets) view_sets.push_back(req.sets[i]);
             if (req.ngram) view_ngram.push_back(req.ngram[i]);
+            if (req.automata) view_automata.push_back(req.automata[i]);
             if (req.prefix) {
                 view_plen.push_back(req.prefix_len[i]);
                 view_prefix.insert(view_prefix.end(), req.prefix + (size_t)i * req.prefix_ld, req.prefix + (size_t)(i + 1) * req.prefix_ld);
@@ -3778,7 +3979,8 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
                       {req.out_alt_ids, L * MOCR_ALTERNATIVES, 0xffffffffu, {}, {}},
                       {req.out_alt_logp, L * MOCR_ALTERNATIVES, 0u, {}, {}},
                       {req.out_pos, L * MOCR_POSITION_FIELDS, 0u, {}, {}},
-                      {req.out_score, 1, 0xce6e6b28u /* -1e9f: beam search, a sliver's slots are empty */, {}, {}}};
+                      {req.out_score, 1, 0xce6e6b28u /* -1e9f: beam search, a sliver's slots are empty */, {}, {}},
+                      {req.out_state, 1, 0xffffffffu /* MOCR_STATE_NONE */, {}, {}}};
         for (Out& o : outs)
             if (o.dst) { o.rows.resize(nv * o.per_row); o.sliver.assign(o.per_row, o.fill); }
         auto rows_of = [&](int k) { return outs[k].dst ? outs[k].rows.data() : nullptr; };
@@ -3791,6 +3993,7 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
                                        pre ? view_plen.data() : nullptr, pre ? req.prefix_ld : 0,
                                        req.source ? view_src.data() : nullptr, req.source ? (int32_t)views.size() : -1);
             inner.beam = req.beam; inner.out_score = reinterpret_cast<float*>(rows_of(6));      // (a sliver drops all K rows of its crop)
+            inner.automata = req.automata ? view_automata.data() : nullptr; inner.out_state = reinterpret_cast<int32_t*>(rows_of(7));
             prepare_and_decode(e, srcs, views.data(), (int)nv, reinterpret_cast<int32_t*>(rows_of(0)), reinterpret_cast<int32_t*>(rows_of(1)), inner);
         }
         for (int i = 0; i < n_rows; ++i)
@@ -3825,6 +4028,16 @@ int mocr_recognize_regions_shared(mocr_engine* e, const mocr_image* pages, int32
     return recognize_regions(e, pages, n_pages, regions, n_regions, n_rows, out_ids, out_len,
                              request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len, prefix_ld, source,
                                         n_regions));
+}
+
+int mocr_recognize_regions_automaton(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                     int32_t n_regions, int32_t n_rows, const int32_t* source, int32_t* out_ids, int32_t* out_len,
+                                     float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets, const int32_t* ngram,
+                                     float* out_pos, const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld,
+                                     const int32_t* automata, int32_t* out_state) {
+    return recognize_regions(e, pages, n_pages, regions, n_regions, n_rows, out_ids, out_len,
+                             with_automata(request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len, prefix_ld,
+                                                      source, n_regions), automata, out_state));
 }
 
 int mocr_recognize_regions_norepeat(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
@@ -4512,7 +4725,9 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d
                         uint32_t* d_row_mask = nullptr, const uint32_t* d_base_mask = nullptr,
                         const int32_t* d_base_set_of_row = nullptr, const int32_t* d_ngram_of_row = nullptr,
                         const int32_t* d_prefix = nullptr, const int32_t* d_prefix_len = nullptr, int32_t prefix_ld = 0,
-                        const float* d_tgt_val = nullptr) {
+                        const float* d_tgt_val = nullptr, const int32_t* d_edge_begin = nullptr, const int32_t* d_edge_token = nullptr,
+                        const int32_t* d_edge_next = nullptr, const uint8_t* d_accepting = nullptr,
+                        const int32_t* d_aut_base_of_row = nullptr, int32_t* d_aut_state = nullptr) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -4530,7 +4745,10 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d
             ((d_row_mask == nullptr) != (d_base_mask == nullptr)) || ((d_row_mask == nullptr) != (d_base_set_of_row == nullptr)) ||
             ((d_row_mask == nullptr) != (d_ngram_of_row == nullptr)) || (d_row_mask && !d_tok_mask) ||
             ((d_prefix == nullptr) != (d_prefix_len == nullptr)) ||
-            (d_prefix && (!d_scores || !d_tok_mask || prefix_ld < 1 || (a->ncand > 0 && !d_tgt_val))))
+            (d_prefix && (!d_scores || !d_tok_mask || prefix_ld < 1 || (a->ncand > 0 && !d_tgt_val))) ||
+            ((d_aut_state == nullptr) != (d_edge_begin == nullptr)) || ((d_aut_state == nullptr) != (d_edge_token == nullptr)) ||
+            ((d_aut_state == nullptr) != (d_edge_next == nullptr)) || ((d_aut_state == nullptr) != (d_accepting == nullptr)) ||
+            ((d_aut_state == nullptr) != (d_aut_base_of_row == nullptr)) || (d_aut_state && !d_row_mask))
             throw ArgError{"mocr_op_dec_token: bad argument", MOCR_ERR_ARG};
         DecState st{};
         st.n_real = a->n_real;
@@ -4545,6 +4763,7 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d
         st.row_mask = d_row_mask; st.base_mask = d_base_mask; st.base_set_of_row = d_base_set_of_row; st.ngram_of_row = d_ngram_of_row;
         st.prefix = d_prefix; st.prefix_len = d_prefix_len; st.prefix_ld = prefix_ld; st.tgt_val = d_tgt_val;
         DecTokenArgs t{};
+        t.aut = DecAutomata{d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state};
         t.slabs = a->slabs; t.nslab = first ? 0 : a->nslab; t.slab_stride = (long long)a->n * e->V;
         t.vbias = a->vbias ? a->vbias : e->w.bv;
         t.cand_val = a->cand_val; t.cand_idx = a->cand_idx; t.ncand = first ? 0 : std::max(a->ncand, 0);
@@ -4578,6 +4797,35 @@ int mocr_op_dec_token_prefix(mocr_engine* e, const mocr_token_args* a, const flo
                              const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld, const float* d_tgt_val) {
     return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, d_row_mask,
                         d_base_mask, d_base_set_of_row, d_ngram_of_row, d_prefix, d_prefix_len, prefix_ld, d_tgt_val);
+}
+
+int mocr_op_dec_token_automaton(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                                const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
+                                const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
+                                const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row,
+                                const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld, const float* d_tgt_val,
+                                const int32_t* d_edge_begin, const int32_t* d_edge_token, const int32_t* d_edge_next,
+                                const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state) {
+    return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, d_row_mask,
+                        d_base_mask, d_base_set_of_row, d_ngram_of_row, d_prefix, d_prefix_len, prefix_ld, d_tgt_val, d_edge_begin,
+                        d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state);
+}
+
+int mocr_op_automaton_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
+                           const int32_t* d_ngram_of_row, int32_t rows, const int32_t* d_edge_begin, const int32_t* d_edge_token,
+                           const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!e->committed || !d_row_mask || !d_base_mask || !d_base_set_of_row || !d_ngram_of_row || rows < 1 || e->V != 6144 ||
+            !d_edge_begin || !d_edge_token || !d_accepting || !d_aut_base_of_row || !d_aut_state)
+            throw ArgError{"mocr_op_automaton_init: bad argument", MOCR_ERR_ARG};
+        launch_automaton_init(e, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows, d_edge_begin, d_edge_token, d_accepting,
+                              d_aut_base_of_row, d_aut_state);
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
 }
 
 int mocr_op_dec_token_masked(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,

@@ -153,6 +153,36 @@ struct DecState {
     const float* tgt_val;
 };
 
+// Token automata: the last argument of dec_token_kernel, read by its AUTOMATON form only (all six pointers set, and the
+// state has the four n-gram pointers) - a trailing argument, so that every other form keeps the argument block it had.  The
+// engine's tables in CSR form over GLOBAL state numbers - edge_begin [states + 1], edge_token / edge_next [edges] (a state's
+// tokens strictly ascending, never EOS), accepting [states] - and by ROW like ids base_of_row [B], the global number of the
+// row's start state (-1: the row brings no automaton), and state [B], the state the row is in (global; AUT_STATE_DEAD once
+// a stored token had no edge).  automaton_init_kernel sets a row's state and first mask, the AUTOMATON token kernel walks the
+// state and rebuilds the mask after every token.
+struct DecAutomata {
+    const int* edge_begin;
+    const int* edge_token;
+    const int* edge_next;
+    const uint8_t* accepting;
+    const int* base_of_row;
+    int* state;
+};
+
+constexpr int AUT_STATE_NONE = -1, AUT_STATE_DEAD = -2;     // = MOCR_STATE_NONE / MOCR_STATE_DEAD (mocr.h)
+
+// The n-gram bans of a row that holds L tokens rid[0 .. L - 1], on its mask in LDS: the threads split the windows
+// i = 0 .. L - n, a window whose n - 1 key tokens equal the row's last n - 1 clears the bit of its follower.
+__device__ __forceinline__ void ngram_ban_windows(unsigned* s_mask, const int* rid, int L, int n, int V, int tid) {
+    const int* key = rid + (L - n + 1);         // the row's last n - 1 tokens
+    for (int i = tid; i <= L - n; i += 256) {
+        bool same = true;
+        for (int k = 0; k < n - 1 && same; ++k) same = rid[i + k] == key[k];
+        const int ban = rid[i + n - 1];
+        if (same && (unsigned)ban < (unsigned)V) atomicAnd(&s_mask[ban >> 5], ~(1u << (ban & 31)));
+    }
+}
+
 // End of a decode step, one block per sequence:
 //   logits = sum_s slab_s + bias  -> fp32 argmax (lowest index wins ties, like torch.argmax)
 //   finished rows emit pad_id (utils.py:2929); EOS or reaching max_len finishes a row (:2936)
@@ -189,7 +219,18 @@ struct DecState {
 //   forced column's masked logit: tgt_val[slot] on the candidate path, published through LDS by the thread that holds the
 //   column on the slab path (before the argmax reduction's barrier).  A token outside the effective set has v = -inf and
 //   scores -inf; a forced token that IS the arg-max takes the free step's expression (a -0 score keeps its sign).
-template <typename T, int D, bool FIRST, bool SCORES = false, bool TOPK = false, bool MASK = false, bool NGRAM = false>
+// AUTOMATON = true (the six pointers of `aut` set; implies NGRAM): rows decode under token automata (mocr.h, "token
+//   automata").  The step's own masking is again the MASK code on st.row_mask.  Behind the barrier that follows thread 0's
+//   token, a row that brings an automaton and was unfinished before the step
+//   1. walks: unless the token is EOS, the threads stride over the old state's edges and the one that holds the token (a
+//      state's tokens are distinct: at most one thread) publishes its target through LDS; no match, or a dead state: DEAD;
+//   2. if the row is still unfinished, rebuilds row_mask[row]: zero the LDS words, OR in the bits of the new state's edge
+//      tokens (LDS atomics) and EOS if it accepts, AND the base set's words, apply the n-gram windows as above, and if a
+//      block-wide OR finds no bit left, the dead-end rule: the mask becomes {EOS}.  The words go back with vector stores;
+//   3. thread 0 stores the new state.  Every thread read the old state before the barrier of step 1 or 2 that precedes it.
+//   A row without an automaton takes the NGRAM path; a row that was finished before the step touches neither mask nor state.
+template <typename T, int D, bool FIRST, bool SCORES = false, bool TOPK = false, bool MASK = false, bool NGRAM = false,
+          bool AUTOMATON = false>
 __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict__ slabs, int nslab, long long slab_stride,
                                                         const float* __restrict__ vbias, int V,
                                                         DecState st,
@@ -203,13 +244,17 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                                                         uint8_t* __restrict__ cache8 = nullptr, float inv_sx8 = 0.f,
                                                         const float* __restrict__ cand_sum = nullptr,
                                                         const float* __restrict__ top_val = nullptr,
-                                                        const int* __restrict__ top_idx = nullptr) {
+                                                        const int* __restrict__ top_idx = nullptr,
+                                                        DecAutomata aut = DecAutomata{}) {
     static_assert(!TOPK || (SCORES && !FIRST), "alternatives come with scores, from the second token on");
     static_assert(!MASK || !FIRST, "the start token is not constrained");
     static_assert(!NGRAM || MASK, "the n-gram bans are applied through the row's mask");
+    static_assert(!AUTOMATON || NGRAM, "an automaton's sets are applied through the row's mask");
     constexpr int MW = 192;                             // mask words of a row (vocab 6144)
     __shared__ __attribute__((aligned(16))) unsigned s_mask[NGRAM ? MW : 4];
     __shared__ int s_ng, s_L;                           // NGRAM: the row's n (0: leave the mask alone) and its token count
+    __shared__ int s_abase, s_awalk, s_alive, s_anext;  // AUTOMATON: the row's start state (-1: none or finished before), whether the
+                                                        // stored token moves the state, whether the mask is rebuilt, the edge's target
     __shared__ float s_val[4];
     __shared__ int s_idx[4];
     __shared__ float s_red[4];
@@ -384,23 +429,67 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                 const bool live = !fin && !st.finished[row] && t + 2 <= st.ids_ld && V == 32 * MW;
                 s_ng = live ? st.ngram_of_row[row] : 0;
                 s_L = t + 2;
+                if constexpr (AUTOMATON) {
+                    s_abase = fin ? -1 : aut.base_of_row[row];
+                    s_awalk = tok != st.eos_id;
+                    s_alive = live;
+                    s_anext = AUT_STATE_DEAD;
+                }
             }
         }
     }
     __syncthreads();
+    bool plain = true;                                  // the row rebuilds its mask the NGRAM way (or not at all)
+    if constexpr (AUTOMATON) {
+        const int abase = s_abase;                      // block-uniform, like everything read from LDS here
+        if (abase >= 0) {
+            plain = false;
+            const int n = s_ng, L = s_L, tok = s_tok;
+            const bool walk = s_awalk != 0, live = s_alive != 0;
+            int state = aut.state[row];              // (thread 0 stores the new one behind at least one more barrier)
+            if (walk) {
+                if (state >= 0) {
+                    const int e1 = aut.edge_begin[state + 1];
+                    for (int i = aut.edge_begin[state] + tid; i < e1; i += 256)
+                        if (aut.edge_token[i] == tok) s_anext = aut.edge_next[i];
+                }
+                __syncthreads();
+                state = s_anext;
+            }
+            if (live) {
+                if (tid < MW) s_mask[tid] = 0u;
+                __syncthreads();
+                if (state >= 0) {
+                    const int e1 = aut.edge_begin[state + 1];
+                    for (int i = aut.edge_begin[state] + tid; i < e1; i += 256) {
+                        const int a = aut.edge_token[i];
+                        if ((unsigned)a < (unsigned)V) atomicOr(&s_mask[a >> 5], 1u << (a & 31));
+                    }
+                    if (tid == 0 && aut.accepting[state] && (unsigned)st.eos_id < (unsigned)V)
+                        atomicOr(&s_mask[st.eos_id >> 5], 1u << (st.eos_id & 31));
+                }
+                __syncthreads();
+                if (tid < MW) s_mask[tid] &= st.base_mask[(size_t)st.base_set_of_row[row] * MW + tid];
+                __syncthreads();
+                if (n > 0) ngram_ban_windows(s_mask, st.ids + (size_t)row * st.ids_ld, L, n, V, tid);
+                __syncthreads();
+                // the dead-end rule
+                const int any = __syncthreads_or(tid < MW && s_mask[tid] != 0u);
+                if (!any && tid == 0 && (unsigned)st.eos_id < (unsigned)V) s_mask[st.eos_id >> 5] = 1u << (st.eos_id & 31);
+                __syncthreads();
+                if (tid < MW / 4)
+                    reinterpret_cast<uint4*>(st.row_mask + (size_t)row * MW)[tid] = reinterpret_cast<const uint4*>(s_mask)[tid];
+            }
+            if (tid == 0 && walk) aut.state[row] = state;
+        }
+    }
     if constexpr (NGRAM) {
         const int n = s_ng, L = s_L;                    // block-uniform
-        if (n > 0) {
+        if (plain && n > 0) {
             const int* rid = st.ids + (size_t)row * st.ids_ld;      // ids[row][0 .. L - 1], the last one stored before the barrier
             if (tid < MW) s_mask[tid] = st.base_mask[(size_t)st.base_set_of_row[row] * MW + tid];
             __syncthreads();
-            const int* key = rid + (L - n + 1);         // the row's last n - 1 tokens
-            for (int i = tid; i <= L - n; i += 256) {
-                bool same = true;
-                for (int k = 0; k < n - 1 && same; ++k) same = rid[i + k] == key[k];
-                const int ban = rid[i + n - 1];
-                if (same && (unsigned)ban < (unsigned)V) atomicAnd(&s_mask[ban >> 5], ~(1u << (ban & 31)));
-            }
+            ngram_ban_windows(s_mask, rid, L, n, V, tid);
             __syncthreads();
             if (tid < MW / 4)
                 reinterpret_cast<uint4*>(st.row_mask + (size_t)row * MW)[tid] = reinterpret_cast<const uint4*>(s_mask)[tid];
@@ -454,6 +543,60 @@ __global__ __launch_bounds__(192) void ngram_init_kernel(unsigned* __restrict__ 
         if (ban_start && w == (start_id >> 5)) m &= ~(1u << (start_id & 31));
         row_mask[(size_t)row * words + w] = m;
     }
+}
+
+// Start of a batch with token automata, one block of 192 threads per row (words <= 192): the sibling of ngram_init_kernel.
+// A row that brings an automaton (aut_base_of_row[row] >= 0) starts in its start state with the mask A(start) AND its base
+// set, minus the start token when n = 1, and {EOS} if nothing is left (the dead-end rule); a row without one gets what
+// ngram_init_kernel gives it and the state AUT_STATE_NONE.
+__global__ __launch_bounds__(192) void automaton_init_kernel(unsigned* __restrict__ row_mask, const unsigned* __restrict__ base_mask,
+                                                             const int* __restrict__ base_set_of_row, const int* __restrict__ ngram_of_row,
+                                                             int rows, int words, int start_id, int eos_id,
+                                                             const int* __restrict__ edge_begin, const int* __restrict__ edge_token,
+                                                             const uint8_t* __restrict__ accepting,
+                                                             const int* __restrict__ aut_base_of_row, int* __restrict__ aut_state) {
+    __shared__ unsigned s_mask[192];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    if (row >= rows) return;
+    const int V = words * 32;
+    const int base = aut_base_of_row[row];              // block-uniform
+    const bool ban_start = ngram_of_row[row] == 1 && (unsigned)start_id < (unsigned)V;
+    if (tid == 0) aut_state[row] = base >= 0 ? base : AUT_STATE_NONE;
+    if (base < 0) {
+        for (int w = tid; w < words; w += blockDim.x) {
+            unsigned m = base_mask[(size_t)base_set_of_row[row] * words + w];
+            if (ban_start && w == (start_id >> 5)) m &= ~(1u << (start_id & 31));
+            row_mask[(size_t)row * words + w] = m;
+        }
+        return;
+    }
+    if (tid < words) s_mask[tid] = 0u;
+    __syncthreads();
+    const int e1 = edge_begin[base + 1];
+    for (int i = edge_begin[base] + tid; i < e1; i += blockDim.x) {
+        const int a = edge_token[i];
+        if ((unsigned)a < (unsigned)V) atomicOr(&s_mask[a >> 5], 1u << (a & 31));
+    }
+    if (tid == 0 && accepting[base] && (unsigned)eos_id < (unsigned)V) atomicOr(&s_mask[eos_id >> 5], 1u << (eos_id & 31));
+    __syncthreads();
+    unsigned m = 0u;
+    if (tid < words) {
+        m = s_mask[tid] & base_mask[(size_t)base_set_of_row[row] * words + tid];
+        if (ban_start && tid == (start_id >> 5)) m &= ~(1u << (start_id & 31));
+    }
+    const int any = __syncthreads_or(m != 0u);
+    if (!any && (unsigned)eos_id < (unsigned)V && tid == (eos_id >> 5)) m = 1u << (eos_id & 31);
+    if (tid < words) row_mask[(size_t)row * words + tid] = m;
+}
+
+// End of a batch with token automata: the rows' states in their automata's own numbering (a state of automaton h is
+// global state aut_first[h] + s), AUT_STATE_DEAD as it is, AUT_STATE_NONE for a row without an automaton.
+__global__ __launch_bounds__(256) void automaton_state_out_kernel(const int* __restrict__ aut_state, const int* __restrict__ aut_base_of_row,
+                                                                  int* __restrict__ out, int rows) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= rows) return;
+    const int base = aut_base_of_row[row], s = aut_state[row];
+    out[row] = base < 0 ? AUT_STATE_NONE : s >= 0 ? s - base : s;
 }
 
 // ------------------------------------------------------------------------------------------------

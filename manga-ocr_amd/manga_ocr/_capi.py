@@ -90,6 +90,17 @@ class MocrBeamConfig(C.Structure):
                 ("no_repeat_ngram_size", C.c_int32)]
 
 
+class MocrAutomatonDesc(C.Structure):
+    """include/mocr.h: mocr_automaton_desc"""
+    _fields_ = [("struct_size", C.c_int32), ("n_states", C.c_int32), ("edge_begin", C.c_void_p), ("edge_token", C.c_void_p),
+                ("edge_next", C.c_void_p), ("accepting", C.c_void_p)]
+
+
+MAX_AUTOMATA = 256                    # MOCR_MAX_AUTOMATA
+MAX_AUTOMATON_STATES = 1 << 20        # MOCR_MAX_AUTOMATON_STATES: over all automata of an engine
+MAX_AUTOMATON_EDGES = 1 << 22         # MOCR_MAX_AUTOMATON_EDGES
+AUTOMATON_NONE = 0                    # MOCR_AUTOMATON_NONE
+STATE_NONE, STATE_DEAD = -1, -2       # MOCR_STATE_NONE, MOCR_STATE_DEAD
 MAX_BEAMS = 4             # MOCR_MAX_BEAMS
 CHANNELS_BGR = -3
 MAX_TOKEN_SETS = 256      # MOCR_MAX_TOKEN_SETS: token sets per engine, set 0 included
@@ -143,6 +154,19 @@ SYMBOLS = {
     "mocr_recognize_gray_host_shared": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                                   C.c_int32]),
     "mocr_encoded_crops": (C.c_int64, [_P]),
+    "mocr_automaton_create": (C.c_int, [_P, C.POINTER(MocrAutomatonDesc), C.POINTER(C.c_int32)]),
+    "mocr_automaton_count": (C.c_int, [_P]),
+    "mocr_automaton_state_bytes": (C.c_int64, [_P]),
+    "mocr_recognize_images_automaton": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                  C.c_int32, _P, _P]),
+    "mocr_recognize_regions_automaton": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.POINTER(MocrRegion), C.c_int32, C.c_int32, _P, _P, _P,
+                                                   _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P]),
+    "mocr_recognize_device_automaton": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P]),
+    "mocr_recognize_gray_host_automaton": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                     C.c_int32, _P, _P]),
+    "mocr_op_dec_token_automaton": (C.c_int, [_P, C.POINTER(MocrTokenArgs), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P,
+                                              _P, _P, _P, _P, _P, _P]),
+    "mocr_op_automaton_init": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
     "mocr_op_enc_expand": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),
     "mocr_graph_count": (C.c_int, [_P]),
     "mocr_compaction_count": (C.c_int64, [_P]),

@@ -206,6 +206,45 @@ class Engine:
             raise ValueError(f"token_sets: {n} crops but {a.size} set handles")
         return a
 
+    # ------------------------------------------------------------------ token automata
+    def automaton(self, edge_begin, edge_token, edge_next, accepting) -> int:
+        """A token automaton of this engine (include/mocr.h, "token automata") in CSR form: state s has the edges
+        ``edge_begin[s] .. edge_begin[s + 1]`` of ``edge_token`` / ``edge_next``, tokens strictly ascending, state 0 the start;
+        ``accepting``: one flag per state.  Returns its handle (>= 1) for ``automata=``; automata are immutable and live as
+        long as the engine."""
+        eb = np.ascontiguousarray(np.asarray(edge_begin).ravel(), dtype=np.int32)
+        et = np.ascontiguousarray(np.asarray(edge_token).ravel(), dtype=np.int32)
+        en = np.ascontiguousarray(np.asarray(edge_next).ravel(), dtype=np.int32)
+        acc = np.ascontiguousarray(np.asarray(accepting).ravel() != 0, dtype=np.uint8)
+        if eb.size < 2 or acc.size != eb.size - 1 or et.size != en.size or (eb.size and int(eb[-1]) != et.size):
+            raise ValueError("automaton: edge_begin [states + 1], accepting [states] and edge_token / edge_next [edge_begin[-1]]")
+        desc = _capi.MocrAutomatonDesc(C.sizeof(_capi.MocrAutomatonDesc), int(acc.size), _ptr(eb), _ptr(et), _ptr(en), _ptr(acc))
+        out = C.c_int32(0)
+        self._check(self.lib.mocr_automaton_create(self._h, C.byref(desc), C.byref(out)))
+        return int(out.value)
+
+    def automaton_count(self) -> int:
+        """Automata created so far."""
+        return int(self.lib.mocr_automaton_count(self._h))
+
+    def automaton_state_bytes(self) -> int:
+        """Device bytes the automata hold: 0 until the first :meth:`automaton` / the first batch that brings one."""
+        return int(self.lib.mocr_automaton_state_bytes(self._h))
+
+    @staticmethod
+    def _automata(automata, n: int) -> np.ndarray:
+        """``automata=``: one handle for every row, or one per row (None = no automaton) -> int32 [n]"""
+        if isinstance(automata, (bool, np.bool_, str)):
+            raise TypeError(f"automata: a handle or a sequence of handles, instead got {automata!r}")
+        if isinstance(automata, (int, np.integer)):
+            return np.full(n, int(automata), dtype=np.int32)
+        hs = [_capi.AUTOMATON_NONE if h is None else h for h in automata]
+        if len(hs) != n:
+            raise ValueError(f"automata: {n} rows but {len(hs)} handles")
+        if any(isinstance(h, (bool, np.bool_)) or not isinstance(h, (int, np.integer)) for h in hs):
+            raise TypeError("automata: the handles must be ints (or None)")
+        return np.ascontiguousarray(np.asarray(hs, dtype=np.int64).ravel(), dtype=np.int32)
+
     # ------------------------------------------------------------------ no-repeat n-grams
     def _ngram(self, no_repeat_ngram, n: int) -> np.ndarray:
         """``no_repeat_ngram=``: one size for every crop, or one size per crop -> int32 [n], each in 0 .. max_len"""
@@ -314,8 +353,10 @@ class Engine:
         of ``sources`` when given; recognize_device brings buffers: ``d_out`` = (ids, lengths, beam scores) and the rest in
         ``req``.  ``skip_empty``: no sources, no call.
         The arguments are checked in this order: beam with anything else, ``sources``, the n-gram sizes, the sets, the
-        prefixes.  The symbol is mocr_recognize_{kind}_beam, else _shared with ``sources``, else _prefix with ``prefixes``, else
-        _positions - each the richest of its line, every output nobody asked for passed as null.
+        prefixes, the automata.  The symbol is mocr_recognize_{kind}_beam, else _automaton with ``automata`` or ``states``
+        (recognize_device: ``d_out_state``), else _shared with ``sources``, else _prefix with ``prefixes``, else _positions - each
+        the richest of its line, every output nobody asked for passed as null.  ``states``: a host kind returns the rows' final
+        automaton states int32 [rows] as the LAST element.
         ``beam_scores`` (a host kind's flag; recognize_device: its ``d_out_beam_logp`` buffer) and ``beam_sets`` belong to a beam
         call: with either in use the symbol is mocr_recognize_{kind}_beam_tokens - the beam call plus (out_logp, sets), null
         where not asked - and a host kind returns logp [n,K,max_len] behind the scores when asked.
@@ -323,6 +364,9 @@ class Engine:
         symbol is then mocr_recognize_{kind}_beam_positions - the _beam_tokens call plus out_pos - and a host kind returns pos
         [n,K,max_len,5] as the LAST element."""
         host = d_out is None
+        automata, states = req.pop("automata", None), req.pop("states" if host else "d_out_state", None)
+        if beam is not None and (automata is not None or (states is not None and states is not False)):
+            raise ValueError("beam search does not combine with automata / states")
         wants_pos = beam_positions is not None and beam_positions is not False
         tokens = (beam_scores is not None and beam_scores is not False) or beam_sets is not None
         if (tokens or wants_pos) and beam is None:
@@ -363,19 +407,26 @@ class Engine:
             shared = (rows, _ptr(src))
         flags = (req["scores"], req["alternatives"], req["positions"]) if host else None
         blocks = self._blocks(rows, *flags) if host else d_out[:2] + (req["d_out_logp"], req["d_out_alt_ids"], req["d_out_alt_logp"], req["d_out_pos"])
+        state = (np.full(rows, _capi.STATE_NONE, dtype=np.int32) if states else None) if host else states
         if rows > 0 or not skip_empty:
             args, keep = lead()
             sets, ngram = self._per_crop(req["token_sets"], req["no_repeat_ngram"], rows)
             pre, plen, ld = self._prefix_args(req["prefixes"], rows)
             variant = "shared" if shared else "prefix" if req["prefixes"] is not None else "positions"
             forced = (_ptr(pre), _ptr(plen), ld) if variant != "positions" else ()
+            if automata is not None or state is not None:      # the shared call (source null: row r reads number r) plus two
+                variant, shared, forced = "automaton", shared or (rows, _ptr(None)), (_ptr(pre), _ptr(plen), ld)
+                handles = self._automata(automata, rows) if automata is not None else None      # (kept until the call returns)
+                forced += (_ptr(handles), _ptr(state))
             self._check(getattr(self.lib, f"mocr_recognize_{kind}_{variant}")(self._h, *args, *shared, *tail, *map(_ptr, blocks[:5]), _ptr(sets), _ptr(ngram),
                                                                             _ptr(blocks[5]), *forced))
-        return self._result(blocks, *flags) if host else None
+        if not host:
+            return None
+        return self._result(blocks, *flags) + ((state,) if state is not None else ())
 
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False,
                          token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
-                         beam_scores: bool = False, beam_sets=None, beam_positions: bool = False):
+                         beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False):
         """Crops of any sizes (list of uint8 [h,w] / [h,w,3] arrays; `bgr`: 3-channel crops are in OpenCV order;
         `rotate`: per crop 0 / 1 (90 degrees clockwise) / 2 (counter-clockwise), applied on the device): luminance
         conversion and the Pillow-exact BILINEAR resize to 224x224 run on the device.
@@ -406,16 +457,20 @@ class Engine:
         ``beam_positions=True`` (only with ``beam``; include/mocr.h, "beam search with token positions"): one more, LAST element
         pos float32 [n,K,max_len,5] - the token positions of every hypothesis, as ``positions=True`` gives them for a greedy row
         teacher-forced on the hypothesis' ids; zeros at the start token, behind the length and in empty slots.  Same ids,
-        lengths, scores and token scores."""
+        lengths, scores and token scores.
+        ``automata``: a handle of :meth:`automaton` for every ROW, or one per row, None / 0 = none - the row is decoded under
+        that token automaton (include/mocr.h, "token automata"); combines with everything but ``beam``.  ``states=True``: one
+        more, LAST element state int32 [rows] - the state every row ended in, in its automaton's numbering; -1 without an
+        automaton, -2 for a dead row."""
         def lead():
             descs, keep = self._image_descs(images, bgr, rotate)
             return (descs, len(keep)), keep
         return self._recognize("images", len(images), lead, beam=beam, beam_scores=beam_scores, beam_sets=beam_sets, beam_positions=beam_positions, skip_empty=True, scores=scores, alternatives=alternatives, token_sets=token_sets,
-                               no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources)
+                               no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources, automata=automata, states=states)
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False,
                           token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
-                          beam_scores: bool = False, beam_sets=None, beam_positions: bool = False):
+                          beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False):
         """pages: list of uint8 [H,W,3] (or [H,W]) arrays; regions: iterable of (page_index, x, y, w, h) bounding
         rectangles.  Each page is uploaded once; the 8 %-padded, page-clipped crop of every region
         (``src/ui/main_window.py:9530-9540``) is cut on the device.  Returns (ids [n,max_len], lengths [n]);
@@ -430,7 +485,8 @@ class Engine:
         per-region arguments are per row, and every row of a sliver region has length 0.
         ``beam``: a :class:`BeamConfig` (see recognize_images): (ids [n,K,max_len], lengths [n,K], scores [n,K]); a sliver's K
         slots are empty.  ``beam_scores`` / ``beam_sets``: as for recognize_images, one set per region; a sliver's logp rows all 0.
-        ``beam_positions``: as for recognize_images, in fractions of the region's padded, clipped rectangle; a sliver's rows all 0."""
+        ``beam_positions``: as for recognize_images, in fractions of the region's padded, clipped rectangle; a sliver's rows all 0.
+        ``automata`` / ``states``: as for recognize_images, per row; a sliver's state is -1."""
         regs = list(regions)
 
         def lead():
@@ -440,7 +496,7 @@ class Engine:
                 arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
             return (descs, len(keep), arr, len(regs)), keep
         return self._recognize("regions", len(regs), lead, beam=beam, beam_scores=beam_scores, beam_sets=beam_sets, beam_positions=beam_positions, skip_empty=True, scores=scores, alternatives=alternatives, token_sets=token_sets,
-                               no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources)
+                               no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources, automata=automata, states=states)
 
     def graph_count(self) -> int:
         return int(self.lib.mocr_graph_count(self._h))
@@ -489,7 +545,8 @@ class Engine:
 
     def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None, d_out_alt_ids=None, d_out_alt_logp=None, *,
                          token_sets=None, no_repeat_ngram=None, d_out_pos=None, prefixes=None, sources=None, beam=None,
-                         d_out_score=None, d_out_beam_logp=None, beam_sets=None, d_out_beam_pos=None) -> None:
+                         d_out_score=None, d_out_beam_logp=None, beam_sets=None, d_out_beam_pos=None, automata=None,
+                         d_out_state=None) -> None:
         """Asynchronous; all are device buffers (torch CUDA tensors or raw addresses).  ``d_out_logp`` (float32
         [n,max_len]): also the token log-probabilities.  ``d_out_alt_ids`` (int32) with ``d_out_alt_logp`` (float32), both
         [n,max_len,4]: also the token alternatives.  ``token_sets``: a set handle for every crop, or one per crop (host values).
@@ -500,17 +557,18 @@ class Engine:
         are per row.  ``beam`` (a :class:`BeamConfig`) with ``d_out_score``: beam search - ``d_out_ids`` int32 [n,K,max_len],
         ``d_out_len`` int32 [n,K] and ``d_out_score`` float32 [n,K] receive the hypotheses; none of the other keywords but ``d_out_beam_logp`` (float32
         [n,K,max_len]: also the hypotheses' token scores), ``beam_sets`` (host values) and ``d_out_beam_pos`` (float32 [n,K,max_len,5]: also
-        the hypotheses' token positions), as for recognize_images."""
+        the hypotheses' token positions), as for recognize_images.  ``automata`` (host values): a token automaton for every row, or
+        one per row; ``d_out_state`` (int32 [rows]): also the rows' final states."""
         self._recognize("device", n, lambda: ((_ptr(d_gray), n), None), beam=beam, beam_scores=d_out_beam_logp, beam_sets=beam_sets, beam_positions=d_out_beam_pos, d_out=(d_out_ids, d_out_len, d_out_score), d_out_logp=d_out_logp,
                         d_out_alt_ids=d_out_alt_ids, d_out_alt_logp=d_out_alt_logp, token_sets=token_sets, no_repeat_ngram=no_repeat_ngram,
-                        d_out_pos=d_out_pos, prefixes=prefixes, sources=sources)
+                        d_out_pos=d_out_pos, prefixes=prefixes, sources=sources, automata=automata, d_out_state=d_out_state)
 
     def set_generate_max_length(self, max_len: int) -> None:
         self._check(self.lib.mocr_set_generate_max_length(self._h, int(max_len)))
 
     def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False, alternatives: bool = False,
                        token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
-                       beam_scores: bool = False, beam_sets=None, beam_positions: bool = False):
+                       beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False):
         """Luminance planes uint8 [n,224,224] (host), generate(max_length) ``max_len``; the keywords as for recognize_images
         (``sources``: one plane index per output row; ``beam``: (ids [n,K,max_len], lengths [n,K], scores [n,K]), with ``beam_scores`` also
         logp [n,K,max_len]; ``beam_sets``: one set per plane; ``beam_positions``: also pos [n,K,max_len,5], last)."""
@@ -518,7 +576,7 @@ class Engine:
         return self._recognize("gray_host", a.shape[0], lambda: ((_ptr(a), a.shape[0]), a), (max_len or self.spec.max_len,), beam=beam, beam_scores=beam_scores,
                                beam_sets=beam_sets, beam_positions=beam_positions, scores=scores,
                                alternatives=alternatives, token_sets=token_sets, no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes,
-                               sources=sources)
+                               sources=sources, automata=automata, states=states)
 
     # ------------------------------------------------------------------ test hooks
     def encode(self, d_gray, n: int) -> np.ndarray:
@@ -732,6 +790,24 @@ class Engine:
     def op_enc_expand(self, d_enc, d_src_of_row, n_src: int, n_rows: int) -> None:
         """The expansion of shared encodings on a device buffer (include/mocr.h mocr_op_enc_expand)."""
         self._check(self.lib.mocr_op_enc_expand(self._h, _ptr(d_enc), _ptr(d_src_of_row), int(n_src), int(n_rows)))
+
+    def op_dec_token_automaton(self, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row,
+                               d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, d_prefix, d_prefix_len, prefix_ld, d_tgt_val,
+                               d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state, **kw) -> None:
+        """The token step with token automata: op_dec_token_prefix plus the tables (global state numbers), the rows' start
+        states (-1: none) and the rows' current states, which the step walks (include/mocr.h)."""
+        self._check(self.lib.mocr_op_dec_token_automaton(
+            self._h, self._args(_capi.MocrTokenArgs, kw), _ptr(d_cand_sum), _ptr(d_scores), _ptr(d_top_val), _ptr(d_top_idx),
+            _ptr(d_alt_ids), _ptr(d_alt_logp), _ptr(d_tok_mask), _ptr(d_set_of_row), _ptr(d_row_mask), _ptr(d_base_mask),
+            _ptr(d_base_set_of_row), _ptr(d_ngram_of_row), _ptr(d_prefix), _ptr(d_prefix_len), int(prefix_ld), _ptr(d_tgt_val),
+            _ptr(d_edge_begin), _ptr(d_edge_token), _ptr(d_edge_next), _ptr(d_accepting), _ptr(d_aut_base_of_row), _ptr(d_aut_state)))
+
+    def op_automaton_init(self, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows: int, d_edge_begin, d_edge_token,
+                          d_accepting, d_aut_base_of_row, d_aut_state) -> None:
+        """The start of a batch with token automata on the caller's buffers (include/mocr.h: mocr_op_automaton_init)."""
+        self._check(self.lib.mocr_op_automaton_init(self._h, _ptr(d_row_mask), _ptr(d_base_mask), _ptr(d_base_set_of_row),
+                                                    _ptr(d_ngram_of_row), int(rows), _ptr(d_edge_begin), _ptr(d_edge_token),
+                                                    _ptr(d_accepting), _ptr(d_aut_base_of_row), _ptr(d_aut_state)))
 
     def op_ngram_init(self, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows: int) -> None:
         """Start of a batch with no-repeat n-grams: every row's mask = its base set (n = 1: minus the start token)."""

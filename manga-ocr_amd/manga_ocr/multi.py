@@ -271,6 +271,8 @@ class MultiGpuEngine:
                "construct MangaOcr on one device to use num_beams / recognize_beam")
     NO_BEAM_POSITIONS = ("token positions of beam hypotheses are not implemented for several devices (manga_ocr/multi.py: the workers "
                          "make the plain greedy call): construct MangaOcr on one device to use recognize_beam(positions=True)")
+    NO_LEXICON = ("token automata (lexicon=) are not implemented for several devices (manga_ocr/multi.py: an automaton belongs to one "
+                  "engine): use a single device")
     NO_ALTERNATIVES = ("token alternatives are not implemented for several devices (manga_ocr/multi.py ships ids and lengths only): "
                        "construct MangaOcr on one device to use the *_alternatives calls")
 

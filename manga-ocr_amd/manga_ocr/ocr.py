@@ -89,6 +89,31 @@ def _set_handles(allowed, n: int) -> Optional[List[int]]:
     return hs
 
 
+class Lexicon(NamedTuple):
+    """A token automaton of a MangaOcr (:meth:`MangaOcr.lexicon`, :meth:`MangaOcr.automaton`) for ``lexicon=``: its engine
+    handle, its accepting states, and for a lexicon the entry index of every accepting state and the entries themselves."""
+    handle: int
+    accepting: frozenset
+    entries: dict
+    texts: tuple
+
+
+def _lexicons(lexicon, n: int) -> Optional[List[Optional[Lexicon]]]:
+    """``lexicon=`` (None: not used; one Lexicon for all crops; or one Lexicon / None per crop) -> a list of n, or None"""
+    if lexicon is None:
+        return None
+    if isinstance(lexicon, Lexicon):
+        return [lexicon] * n
+    if isinstance(lexicon, (str, bytes, int, np.integer)):
+        raise TypeError(f"lexicon: a Lexicon of MangaOcr.lexicon() / automaton() or a sequence of them, instead got {lexicon!r}")
+    ls = list(lexicon)
+    if len(ls) != n:
+        raise ValueError(f"lexicon: {n} crops but {len(ls)} lexicons")
+    if any(x is not None and not isinstance(x, Lexicon) for x in ls):
+        raise TypeError("lexicon: every entry is a Lexicon of MangaOcr.lexicon() / automaton(), or None")
+    return ls if any(x is not None for x in ls) else None
+
+
 def resolve_no_repeat_ngram(value, ignored: dict, max_len: int):
     """``MangaOcr(no_repeat_ngram_size=...)`` -> (the size every call uses by default, or None for today's behaviour; what is
     left of the checkpoint's ignored generation settings).  ``None``: nothing changes.  An int in 0 .. max_len: that size (0 =
@@ -225,6 +250,11 @@ class Recognition:
     # length_penalty (transformers' ``sequences_scores``); such a Recognition carries no per-token logprobs (confidence 0.0)
     # unless the call asked with ``token_scores=True``
     sequence_score: Optional[float] = None
+    # ``lexicon=``: the automaton state the row ended in (-1: the crop had no lexicon, -2: it left its automaton), whether it
+    # ended by EOS in an accepting state, and for a lexicon the index of the entry it read (None otherwise)
+    state: Optional[int] = None
+    accepted: bool = False
+    entry: Optional[int] = None
     _vocab: object = field(default=None, repr=False, compare=False)      # what candidates() names the tokens with
 
     @classmethod
@@ -336,6 +366,7 @@ class _Request(NamedTuple):
     beam_scores: bool = False           # a beam request: wants its hypotheses' token log-probabilities
     beam_set: int = 0                   # a beam request: the token set its beams search under, 0: unconstrained
     beam_positions: bool = False        # a beam request: wants its hypotheses' token positions
+    automaton: int = 0                  # token automaton handle (``lexicon=``), 0: none; such a caller gets its final state, last
 
 
 class _Batcher:
@@ -368,13 +399,13 @@ class _Batcher:
 
     def submit(self, gray: np.ndarray, scored: bool = False, alternatives: bool = False, token_set: int = 0,
                no_repeat_ngram: int = 0, positions: bool = False, prefix=None, beam: Optional[BeamConfig] = None,
-               beam_scores: bool = False, beam_set: int = 0, beam_positions: bool = False) -> Future:
+               beam_scores: bool = False, beam_set: int = 0, beam_positions: bool = False, automaton: int = 0) -> Future:
         f: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
             self._q.append(_Request(gray, f, bool(scored or alternatives), bool(alternatives), bool(positions), int(token_set), int(no_repeat_ngram),
-                                    tuple(prefix) if prefix else None, beam, bool(beam_scores), int(beam_set), bool(beam_positions)))
+                                    tuple(prefix) if prefix else None, beam, bool(beam_scores), int(beam_set), bool(beam_positions), int(automaton)))
             self._cv.notify()
         return f
 
@@ -424,12 +455,16 @@ class _Batcher:
                     kw["positions"] = True
                 if any(r.prefix for r in batch):
                     kw["prefixes"] = [list(r.prefix) if r.prefix else None for r in batch]
+                if any(r.automaton for r in batch):         # (the same again for a token automaton, ``lexicon=``)
+                    kw["automata"] = [r.automaton for r in batch]
+                    kw["states"] = True
                 res = self.engine.recognize_images([r.gray for r in batch], **kw)
+                state = res[-1] if kw.get("states") else None
                 got = dict(zip(result_layout(kw.get("scores", False), kw.get("alternatives", False), kw.get("positions", False)), res))
                 for i, r in enumerate(batch):
                     # what this caller asked for, cut to its length: bare ids, or a tuple with its logp / alternatives / positions
                     names = ["ids"] + ["logp"] * r.scored + ["alt_ids", "alt_logp"] * r.alternatives + ["pos"] * r.positions
-                    out = tuple(got[name][i, :got["lens"][i]].copy() for name in names)
+                    out = tuple(got[name][i, :got["lens"][i]].copy() for name in names) + ((state[i:i + 1].copy(),) if r.automaton else ())
                     r.future.set_result(out if len(out) > 1 else out[0])
             except BaseException as exc:  # every waiting caller gets the error; the loop lives on
                 for r in batch:
@@ -515,13 +550,14 @@ class _Single(NamedTuple):
     @staticmethod
     def batcher_kw(kw: dict) -> dict:
         """one row's engine keywords (``MangaOcr._decode_kw``) as ``_Batcher.submit`` names them"""
-        names = (("token_sets", "token_set"), ("no_repeat_ngram", "no_repeat_ngram"), ("prefixes", "prefix"))
+        names = (("token_sets", "token_set"), ("no_repeat_ngram", "no_repeat_ngram"), ("prefixes", "prefix"), ("automata", "automaton"))
         return {single: kw[many][0] for many, single in names if many in kw}
 
-    def call(self, ocr, scores: bool = False, alternatives: bool = False, positions: bool = False, **kw):
+    def call(self, ocr, scores: bool = False, alternatives: bool = False, positions: bool = False, states: bool = False, **kw):
         out = ocr._batcher.submit(self.pixels, scored=scores, alternatives=alternatives, positions=positions, **self.batcher_kw(kw)).result()
         ids, *rest = out if isinstance(out, tuple) else (out,)
-        return (ids[None], np.array([len(ids)]), *(a[None] for a in rest))
+        state = (rest.pop(),) if states else ()           # (the row's final state comes as an array of one already)
+        return (ids[None], np.array([len(ids)]), *(a[None] for a in rest), *state)
 
 
 class MangaOcr:
@@ -671,6 +707,26 @@ class MangaOcr:
                 ts = self._token_sets[key] = TokenSet(self.engine.token_set(sorted(members)), len(members))
             return ts
 
+    # ------------------------------------------------------------------ token automata
+    def lexicon(self, texts) -> Lexicon:
+        """A closed list of texts for ``lexicon=``: the crop is read as one of them (include/mocr.h, "token automata") at one
+        decode row, whatever the size of the list.  The entries are spelt one token per character (``Vocab.encode_chars``, on
+        the raw token text of vocab.txt); an empty list or a character without a single-token spelling raises ``ValueError``.
+        ``Recognition.entry`` then indexes ``texts``.  Lexicons live as long as this MangaOcr, at most 256 of them."""
+        from .text import lexicon_trie, pack_automaton
+        self._require("LEXICON")
+        texts = tuple(str(t) for t in texts)
+        trans, entry = lexicon_trie(self.vocab, texts)
+        return Lexicon(self.engine.automaton(*pack_automaton(trans, entry)), frozenset(entry), dict(entry), texts)
+
+    def automaton(self, transitions, accepting) -> Lexicon:
+        """The raw form, for patterns such as "one or two digits": ``transitions`` = {state: {token id: next state}} with state 0
+        the start, ``accepting`` = the states a row may end in.  For ``lexicon=``; ``Recognition.entry`` stays None."""
+        from .text import pack_automaton
+        self._require("LEXICON")
+        acc = frozenset(int(s) for s in accepting)
+        return Lexicon(self.engine.automaton(*pack_automaton(transitions, acc)), acc, {}, ())
+
     def _allowed(self, allowed, n: int) -> dict:
         """the engine keyword of ``allowed=`` ({} for None: the call the method always made)"""
         hs = _set_handles(allowed, n)
@@ -698,16 +754,18 @@ class MangaOcr:
         """the batcher keywords of one crop's ``allowed=`` / ``no_repeat_ngram=`` / ``prefix=``"""
         return _Single.batcher_kw(self._decode_kw(allowed, no_repeat_ngram, 1, prefix))
 
-    def _run(self, source, kind: _Kind, allowed=None, no_repeat_ngram=None, prefix=None, sources=None) -> list:
+    def _run(self, source, kind: _Kind, allowed=None, no_repeat_ngram=None, prefix=None, sources=None, lexicon=None) -> list:
         """Every greedy recognise method: one row of ``kind`` per crop or region of the source - or per entry of ``sources``
         (shared encodings).  In this order: the kind's refusal (several devices), before the image is opened or any argument
         is looked at; for plain text and positions, whether the constructor's beams decode it instead (``_beam_default``: text
         gets the best hypothesis' ids, positions the best hypothesis with its token scores and positions); ``source()``, which
         opens, converts and checks the inputs; ``_decode_kw``; the ONE engine call, with the kind's flags and only the keywords
-        somebody asked for; the kind's rows; ``n_forced`` of the rows that were given a prefix."""
+        somebody asked for; the kind's rows; ``n_forced`` of the rows that were given a prefix.  ``lexicon=`` (a token automaton per
+        crop) makes the call greedy and adds ``automata=`` / ``states=True``; the rows then carry ``state``, ``accepted``, ``entry``."""
         if kind.refusal:
             self._require(kind.refusal)
-        beams = (kind is _TEXT or (kind is _POS and getattr(self, "beam_positions", False))) and self._beam_default(allowed, no_repeat_ngram, prefix)
+        beams = (kind is _TEXT or (kind is _POS and getattr(self, "beam_positions", False))) and lexicon is None and \
+            self._beam_default(allowed, no_repeat_ngram, prefix)
         if beams and kind is _POS:
             self._require("BEAM_POSITIONS")
         src = source()
@@ -721,8 +779,14 @@ class MangaOcr:
         kw = self._decode_kw(allowed, no_repeat_ngram, src.n if sources is None else len(sources), prefix)
         if sources is not None:
             kw["sources"] = sources
-        rows = kind.rows(self, src, *src.call(self, **kind.flags, **kw))
-        return rows if kind is _TEXT else self._mark_forced(rows, kw.get("prefixes"))
+        lex = _lexicons(lexicon, src.n if sources is None else len(sources))
+        if lex is None:
+            rows = kind.rows(self, src, *src.call(self, **kind.flags, **kw))
+            return rows if kind is _TEXT else self._mark_forced(rows, kw.get("prefixes"))
+        self._require("LEXICON")
+        *blocks, state = src.call(self, **kind.flags, **kw, automata=[0 if x is None else x.handle for x in lex], states=True)
+        rows = kind.rows(self, src, *blocks)
+        return rows if kind is _TEXT else self._mark_lexicon(self._mark_forced(rows, kw.get("prefixes")), lex, state)
 
     @staticmethod
     def _open(img_or_path):
@@ -764,6 +828,16 @@ class MangaOcr:
             return recs
         return [replace(r, n_forced=min(len(p), max(len(r.ids) - 1, 0))) if p else r for r, p in zip(recs, prefixes)]
 
+    def _mark_lexicon(self, recs: List[Recognition], lex, state) -> List[Recognition]:
+        """``Recognition.state`` / ``accepted`` / ``entry`` of a call with ``lexicon=``: accepted = the row ended by EOS in an
+        accepting state of its automaton; entry = the lexicon entry that state stands for"""
+        out = []
+        for r, x, s in zip(recs, lex, state):
+            s = int(s)
+            ok = x is not None and len(r.ids) > 1 and int(r.ids[-1]) == self.spec.eos_id and s in x.accepting
+            out.append(replace(r, state=s, accepted=bool(ok), entry=x.entries.get(s) if ok else None))
+        return out
+
     def _recognitions(self, ids, lens, logp) -> List[Recognition]:
         return [Recognition.from_row(self.vocab, ids[i], logp[i], lens[i]) for i in range(len(lens))]
 
@@ -776,109 +850,112 @@ class MangaOcr:
 
     # ------------------------------------------------------------------ batch surface (callers that hold many crops)
     def recognize_ids(self, crops: Sequence[np.ndarray], bgr: bool = False, rotate: Optional[Sequence[int]] = None, *,
-                      allowed=None, no_repeat_ngram=None, prefix=None) -> List[np.ndarray]:
+                      allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[np.ndarray]:
         """uint8 crops of any sizes ([h,w] luminance or [h,w,3] RGB; BGR with ``bgr=True``; ``rotate``: per crop 0 / 1 (90
         degrees clockwise) / 2 (counter-clockwise), done by the device) -> token ids (without padding).  ``allowed``: a
         token set of :meth:`token_set` for all crops, or one per crop.  ``no_repeat_ngram``: the no-repeat n-gram size of this
         call, an int for all crops or one per crop, 0 = off (None: the constructor's ``no_repeat_ngram_size``).  ``prefix``:
         tokens the rows start with, behind the start token - a ``str`` (one token per character, ``Vocab.encode_chars``) or a
         flat sequence of token ids for all crops, or a sequence of those (or None) per crop; the engine scores them and decodes
-        on from there (include/mocr.h, "forced prefixes").  Every ``recognize*`` method takes all three."""
-        return self._run(lambda: _Images(list(crops), bgr, rotate), _TEXT, allowed, no_repeat_ngram, prefix)
+        on from there (include/mocr.h, "forced prefixes").  ``lexicon``: a :class:`Lexicon` of :meth:`lexicon` / :meth:`automaton`
+        for all crops, or one (or None) per crop - the row is decoded under that token automaton (include/mocr.h, "token
+        automata"); the scored kinds then fill ``Recognition.state`` / ``accepted`` / ``entry``.  Every greedy ``recognize*``
+        method takes all four."""
+        return self._run(lambda: _Images(list(crops), bgr, rotate), _TEXT, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
 
-    def recognize(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> str:
+    def recognize(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> str:
         """``__call__`` (which keeps the reference's signature) with ``allowed=``: one crop decoded under a token set, and
         ``no_repeat_ngram=``: this call's no-repeat n-gram size (None: the constructor's ``no_repeat_ngram_size``)."""
-        return self._texts(self._run(self._one(img_or_path), _TEXT, allowed, no_repeat_ngram, prefix))[0]
+        return self._texts(self._run(self._one(img_or_path), _TEXT, allowed, no_repeat_ngram, prefix, lexicon=lexicon))[0]
 
-    def recognize_batch(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
+    def recognize_batch(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[str]:
         """All crops of a page (or chapter) at once - what ``_collect_manga_detections``
         (``src/ui/main_window.py:9462-9476``) does one region at a time."""
-        return self._texts(self.recognize_ids([to_pixels(im) for im in images], allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix))
+        return self._texts(self.recognize_ids([to_pixels(im) for im in images], allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix, lexicon=lexicon))
 
-    def recognize_batch_arrays(self, crops: Sequence[np.ndarray], *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
+    def recognize_batch_arrays(self, crops: Sequence[np.ndarray], *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[str]:
         """uint8 arrays ([h,w] luminance or [h,w,3] RGB, any sizes) -> strings: what a caller that already holds numpy
         crops (the crop-job queue) uses instead of wrapping each one in a PIL image."""
-        return self._texts(self.recognize_ids(crops, allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix))
+        return self._texts(self.recognize_ids(crops, allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix, lexicon=lexicon))
 
-    def recognize_bgr(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
+    def recognize_bgr(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[str]:
         """BGR crops exactly as the crop tools and the worker hold them (``cropped_cv_img``, ``src/core/workers.py:300``):
         the BGR -> RGB swap of ``src/ui/main_window.py:9800`` is folded into the device's luminance conversion, and with
         ``orientations`` (the jobs' "Auto-Detect" / "Vertical" / "Horizontal" settings) the orientation-only rotation of
         ``src/core/workers.py:320-326`` / ``src/ui/main_window.py:9787-9795`` into the device's resize addressing."""
         src = self._bgr("recognize_bgr", crops_bgr, orientations)
-        return self._texts(self._run(lambda: src, _TEXT, allowed, no_repeat_ngram, prefix))
+        return self._texts(self._run(lambda: src, _TEXT, allowed, no_repeat_ngram, prefix, lexicon=lexicon))
 
-    def recognize_regions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[str]:
+    def recognize_regions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[str]:
         """``regions``: (page_index, x, y, w, h) bounding rectangles on BGR pages; every page is uploaded once and
         the padded crops (``src/ui/main_window.py:9530-9540``) are cut on the device.  One string per region
         ('' for a region reduced to a sliver, like the reference)."""
-        return self._texts(self._run(lambda: _Regions(list(pages_bgr), list(regions)), _TEXT, allowed, no_repeat_ngram, prefix))
+        return self._texts(self._run(lambda: _Regions(list(pages_bgr), list(regions)), _TEXT, allowed, no_repeat_ngram, prefix, lexicon=lexicon))
 
     # ------------------------------------------------------------------ scored surface: the same recognitions + confidence
-    def recognize_scored(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> Recognition:
+    def recognize_scored(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> Recognition:
         """``__call__`` with the recogniser's confidence: same text, plus the token log-probabilities computed on the
         device (include/mocr.h, "token scores").  Goes through the same batcher as ``__call__``; scored and unscored
         callers may share a batch."""
-        return self._run(self._one(img_or_path), _SCORED, allowed, no_repeat_ngram, prefix)[0]
+        return self._run(self._one(img_or_path), _SCORED, allowed, no_repeat_ngram, prefix, lexicon=lexicon)[0]
 
-    def recognize_batch_scored(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+    def recognize_batch_scored(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
         """``recognize_batch`` with confidences."""
-        return self._run(self._pil(images), _SCORED, allowed, no_repeat_ngram, prefix)
+        return self._run(self._pil(images), _SCORED, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
 
     def recognize_bgr_scored(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
-                             allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+                             allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
         """``recognize_bgr`` with confidences."""
-        return self._run(lambda: self._bgr("recognize_bgr_scored", crops_bgr, orientations), _SCORED, allowed, no_repeat_ngram, prefix)
+        return self._run(lambda: self._bgr("recognize_bgr_scored", crops_bgr, orientations), _SCORED, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
 
-    def recognize_regions_scored(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+    def recognize_regions_scored(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
         """``recognize_regions`` with confidences; a region reduced to a sliver gives text '' and confidence 0.0."""
-        return self._run(lambda: _Regions(list(pages_bgr), list(regions)), _SCORED, allowed, no_repeat_ngram, prefix)
+        return self._run(lambda: _Regions(list(pages_bgr), list(regions)), _SCORED, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
 
     # ------------------------------------------------------------------ alternatives surface: + the runners-up of every position
-    def recognize_alternatives(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> Recognition:
+    def recognize_alternatives(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> Recognition:
         """``recognize_scored`` plus, for every generated position, the four most probable tokens and their log-probabilities
         (``Recognition.alt_ids`` / ``alt_logprobs`` / ``candidates``; include/mocr.h, "token alternatives").  Same text; goes
         through the same batcher as ``__call__``, and callers of all three kinds may share a batch."""
-        return self._run(self._one(img_or_path), _ALTS, allowed, no_repeat_ngram, prefix)[0]
+        return self._run(self._one(img_or_path), _ALTS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)[0]
 
-    def recognize_batch_alternatives(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+    def recognize_batch_alternatives(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
         """``recognize_batch`` with confidences and alternatives."""
-        return self._run(self._pil(images), _ALTS, allowed, no_repeat_ngram, prefix)
+        return self._run(self._pil(images), _ALTS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
 
     def recognize_bgr_alternatives(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
-                                   allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+                                   allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
         """``recognize_bgr`` with confidences and alternatives."""
-        return self._run(lambda: self._bgr("recognize_bgr_alternatives", crops_bgr, orientations), _ALTS, allowed, no_repeat_ngram, prefix)
+        return self._run(lambda: self._bgr("recognize_bgr_alternatives", crops_bgr, orientations), _ALTS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
 
-    def recognize_regions_alternatives(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+    def recognize_regions_alternatives(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
         """``recognize_regions`` with confidences and alternatives; a region reduced to a sliver gives text '', confidence
         0.0 and empty alternatives."""
-        return self._run(lambda: _Regions(list(pages_bgr), list(regions)), _ALTS, allowed, no_repeat_ngram, prefix)
+        return self._run(lambda: _Regions(list(pages_bgr), list(regions)), _ALTS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
 
     # ------------------------------------------------------------------ positions surface: + where each token was read
-    def recognize_positions(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None) -> Recognition:
+    def recognize_positions(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> Recognition:
         """``recognize_scored`` plus ``Recognition.positions``: per token where in the crop the decoder looked when it emitted
         it (include/mocr.h, "token positions"); ``Recognition.boxes(width, height)`` gives pixel rectangles.  Same text and
         scores; goes through the same batcher as ``__call__``, and callers of all kinds may share a batch."""
-        return self._run(self._one(img_or_path), _POS, allowed, no_repeat_ngram, prefix)[0]
+        return self._run(self._one(img_or_path), _POS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)[0]
 
-    def recognize_batch_positions(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+    def recognize_batch_positions(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
         """``recognize_batch_scored`` with positions."""
-        return self._run(self._pil(images), _POS, allowed, no_repeat_ngram, prefix)
+        return self._run(self._pil(images), _POS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
 
     def recognize_bgr_positions(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
-                                allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+                                allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
         """``recognize_bgr_scored`` with positions.  The positions are those of the crop the encoder saw, i.e. after the
         orientation's rotation: pass the crop's rotation code (``queue_worker.rotation_code``) to ``Recognition.boxes`` to get
         rectangles on the crop as it was handed in."""
-        return self._run(lambda: self._bgr("recognize_bgr_positions", crops_bgr, orientations), _POS, allowed, no_repeat_ngram, prefix)
+        return self._run(lambda: self._bgr("recognize_bgr_positions", crops_bgr, orientations), _POS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
 
-    def recognize_regions_positions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None) -> List[Recognition]:
+    def recognize_regions_positions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
         """``recognize_regions_scored`` with positions: every Recognition carries ``rect``, the region's padded, clipped
         rectangle on its page (``regions.padded_rect``), so ``Recognition.page_boxes()`` gives the tokens' rectangles in page
         pixels.  A region reduced to a sliver gives text '', no positions rows and ``rect`` None."""
-        return self._run(lambda: _Regions(list(pages_bgr), list(regions)).with_rects(), _POS, allowed, no_repeat_ngram, prefix)
+        return self._run(lambda: _Regions(list(pages_bgr), list(regions)).with_rects(), _POS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
 
     # ------------------------------------------------------------------ forced prefixes: score a given text
     def _text_prefix(self, text) -> List[int]:
@@ -1029,8 +1106,11 @@ class MangaOcr:
         hyps = self._hypotheses(ids[:1], lens[:1], scores[:1], logp[:1], pos[:1], rect)
         return hyps[0] if hyps else Recognition.from_row(self.vocab, ids[0], logp[0], 0, pos_row=pos[0])
 
-    def _run_beam(self, source, *config, token_scores: bool = False, allowed=None, positions: bool = False) -> List[List[Recognition]]:
-        """the ``*_beam`` methods: the configuration is checked, then the inputs; one list of hypotheses per crop or region"""
+    def _run_beam(self, source, *config, token_scores: bool = False, allowed=None, positions: bool = False, lexicon=None) -> List[List[Recognition]]:
+        """the ``*_beam`` methods: the configuration is checked, then the inputs; one list of hypotheses per crop or region.
+        ``lexicon=`` is refused: beam search takes no token automaton (include/mocr.h, "token automata")"""
+        if lexicon is not None:
+            raise ValueError("beam search does not combine with lexicon= (token automata are for greedy decoding)")
         beam = BeamConfig(*config)
         src = source()
         if positions and isinstance(src, _Regions):
@@ -1043,7 +1123,7 @@ class MangaOcr:
                                  rects[i] if rects is not None else None) for i in range(len(lens))]
 
     def recognize_beam(self, img_or_path, num_beams: int = 4, length_penalty: float = 1.0, early_stopping=False,
-                       no_repeat_ngram: int = 0, *, token_scores: bool = False, allowed=None, positions: bool = False) -> List[Recognition]:
+                       no_repeat_ngram: int = 0, *, token_scores: bool = False, allowed=None, positions: bool = False, lexicon=None) -> List[Recognition]:
         """Beam search for one crop (include/mocr.h, "beam search"): what transformers' ``generate(num_beams=...,
         length_penalty=..., early_stopping=..., no_repeat_ngram_size=...)`` returns with ``num_return_sequences=num_beams`` -
         the finished hypotheses, best first, each with its ``sequence_score``.  ``num_beams`` 2 .. 4; ``early_stopping``
@@ -1057,31 +1137,31 @@ class MangaOcr:
         search with token positions") - so ``Recognition.boxes`` works on it.  Nothing else of the result moves."""
         self._require("BEAM")
         return self._run_beam(self._one(img_or_path), num_beams, length_penalty, early_stopping, no_repeat_ngram, token_scores=token_scores,
-                              allowed=allowed, positions=positions)[0]
+                              allowed=allowed, positions=positions, lexicon=lexicon)[0]
 
     def recognize_batch_beam(self, images: Sequence, num_beams: int = 4, length_penalty: float = 1.0, early_stopping=False,
                              no_repeat_ngram: int = 0, *, token_scores: bool = False, allowed=None,
-                             positions: bool = False) -> List[List[Recognition]]:
+                             positions: bool = False, lexicon=None) -> List[List[Recognition]]:
         """``recognize_beam`` for many crops: one list of hypotheses per crop (``allowed``: one set for all, or one per crop)."""
         return self._run_beam(self._pil(images), num_beams, length_penalty, early_stopping, no_repeat_ngram, token_scores=token_scores, allowed=allowed,
-                              positions=positions)
+                              positions=positions, lexicon=lexicon)
 
     def recognize_bgr_beam(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, num_beams: int = 4,
                            length_penalty: float = 1.0, early_stopping=False, no_repeat_ngram: int = 0, *, token_scores: bool = False,
-                           allowed=None, positions: bool = False) -> List[List[Recognition]]:
+                           allowed=None, positions: bool = False, lexicon=None) -> List[List[Recognition]]:
         """``recognize_bgr`` with beam search: one list of hypotheses per crop (``token_scores`` / ``allowed`` / ``positions``: see
         recognize_beam; the positions are those of the rotated crop, as for ``recognize_bgr_positions``)."""
         return self._run_beam(lambda: self._bgr("recognize_bgr_beam", crops_bgr, orientations), num_beams, length_penalty, early_stopping, no_repeat_ngram,
-                              token_scores=token_scores, allowed=allowed, positions=positions)
+                              token_scores=token_scores, allowed=allowed, positions=positions, lexicon=lexicon)
 
     def recognize_regions_beam(self, pages_bgr: Sequence[np.ndarray], regions, num_beams: int = 4, length_penalty: float = 1.0,
                                early_stopping=False, no_repeat_ngram: int = 0, *, token_scores: bool = False,
-                               allowed=None, positions: bool = False) -> List[List[Recognition]]:
+                               allowed=None, positions: bool = False, lexicon=None) -> List[List[Recognition]]:
         """``recognize_regions`` with beam search: one list of hypotheses per region ([] for a sliver; ``token_scores`` /
         ``allowed``: see recognize_beam, one set per region; ``positions``: every hypothesis also carries ``rect``, so
         ``page_boxes()`` works)."""
         return self._run_beam(lambda: _Regions(list(pages_bgr), list(regions)), num_beams, length_penalty, early_stopping, no_repeat_ngram,
-                              token_scores=token_scores, allowed=allowed, positions=positions)
+                              token_scores=token_scores, allowed=allowed, positions=positions, lexicon=lexicon)
 
     def recognize_page(self, page_bgr: np.ndarray, regions):
         """``_collect_manga_detections`` for one page: ``regions`` = the detector's (text, polygon) pairs."""

@@ -200,6 +200,50 @@ def ids_to_text(vocab: Vocab, ids: Iterable[int]) -> str:
     return text
 
 
+def pack_automaton(transitions, accepting, n_states: Optional[int] = None):
+    """A token automaton ``{state: {token id: next state}}`` with its accepting states -> the CSR form the engine takes
+    (include/mocr.h, "token automata"): (edge_begin [states + 1], edge_token, edge_next [edges], accepting [states]), every
+    state's edges sorted by token.  State 0 is the start; states are 0 .. the largest one named (or ``n_states`` - 1)."""
+    trans = {int(s): {int(t): int(n) for t, n in e.items()} for s, e in dict(transitions).items()}
+    acc = {int(s) for s in accepting}
+    named = set(trans) | acc | {n for e in trans.values() for n in e.values()} | {0}
+    if min(named) < 0:
+        raise ValueError("automaton: states are numbered from 0")
+    n = max(named) + 1 if n_states is None else int(n_states)
+    if max(named) >= n:
+        raise ValueError(f"automaton: a state beyond n_states ({n})")
+    begin, tok, nxt = [0], [], []
+    for s in range(n):
+        for t, to in sorted(trans.get(s, {}).items()):
+            tok.append(t)
+            nxt.append(to)
+        begin.append(len(tok))
+    return begin, tok, nxt, [1 if s in acc else 0 for s in range(n)]
+
+
+def lexicon_trie(vocab: Vocab, texts: Sequence[str]):
+    """The trie of ``texts`` over token ids, one token per character (``Vocab.encode_chars``): (transitions, {accepting state:
+    index of its entry}) for :func:`pack_automaton` - a word's last node accepts, and an entry given twice keeps its first
+    index.  An empty list, an entry without a character, or a character without a single-token spelling raises ``ValueError``."""
+    texts = list(texts)
+    if not texts:
+        raise ValueError("lexicon: no entries")
+    trans, entry, n = {0: {}}, {}, 1
+    for k, text in enumerate(texts):
+        ids = vocab.encode_chars(text)
+        if not ids:
+            raise ValueError(f"lexicon: entry {k} ({text!r}) has no characters")
+        s = 0
+        for t in ids:
+            nxt = trans.setdefault(s, {})
+            if t not in nxt:
+                nxt[t] = n
+                n += 1
+            s = nxt[t]
+        entry.setdefault(s, k)
+    return trans, entry
+
+
 def find_vocab(model_dir: Optional[str]) -> Optional[str]:
     if model_dir:
         p = os.path.join(model_dir, "vocab.txt")
