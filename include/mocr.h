@@ -414,7 +414,8 @@ int64_t mocr_encoded_crops(mocr_engine* e);
  *     new state's edges.  The tables live in one device arena allocated at full capacity by the first mocr_automaton_create
  *     (about 37 MiB; capacity is bounded by edges, not by states x 768 B, so a dictionary-sized trie fits); the rows' states
  *     (12 B a row and lane) are allocated by the first batch that brings an automaton.
- *   Beam search is out of scope: the *_beam entry points take no automaton. */
+ *   Beam search: the *_beam, *_beam_tokens and *_beam_positions entry points take no automaton; the *_beam_automaton twins do,
+ *     under the rule of the section "beam search under a token automaton" below. */
 #define MOCR_MAX_AUTOMATA          256
 #define MOCR_MAX_AUTOMATON_STATES  (1 << 20)    /* over all automata of an engine */
 #define MOCR_MAX_AUTOMATON_EDGES   (1 << 22)
@@ -434,7 +435,8 @@ typedef struct mocr_automaton_desc {
  * [0, n_states); a table or the handle list full.  MOCR_ERR_STATE before mocr_commit_weights. */
 int mocr_automaton_create(mocr_engine* e, const mocr_automaton_desc* desc, int32_t* out_handle);
 int mocr_automaton_count(mocr_engine* e);
-/* Device bytes the automata hold: the arena plus the lanes' row states; 0 until the first create / first automaton batch. */
+/* Device bytes the automata hold: the arena plus the lanes' row states (and, 4 B a row more, the hypothesis states of a lane
+ * that has run a beam batch under an automaton); 0 until the first create / first automaton batch. */
 int64_t mocr_automaton_state_bytes(mocr_engine* e);
 /* The *_automaton entry points: the *_shared twins plus `automata`, a HOST int32 array [n_rows] of handles (null: every row
  * MOCR_AUTOMATON_NONE; copied before the call returns), and out_state int32 [n_rows] (nullable; host, or device for the device
@@ -1013,6 +1015,61 @@ int mocr_recognize_gray_host_beam_positions(mocr_engine* e, const uint8_t* gray,
 int mocr_recognize_device_beam_positions(mocr_engine* e, const void* d_gray, int32_t n, const mocr_beam_config* beam, void* d_out_ids,
                                          void* d_out_len, void* d_out_score, void* d_out_logp, const int32_t* sets, void* d_out_pos);
 
+/* ---- beam search under a token automaton ------------------------------------------------------------------------------
+ * The K best entries of a lexicon: a beam search whose every beam walks a token automaton - transformers'
+ * generate(num_beams = K, prefix_allowed_tokens_fn = f) with f depending on the beam's history; the *_beam_tokens section is
+ * its history-free case.
+ *   Every crop may bring an automaton: a handle of mocr_automaton_create, or MOCR_AUTOMATON_NONE.  All K beams of the crop
+ *     walk that automaton, each with a state of its own; every beam starts in the start state.
+ *   THE MASK at the step that chooses token L of beam k, in state s_k: log_softmax over the full row first; a token is -inf
+ *     unless it is in A(s_k) AND the crop's token set - A(s) the edge tokens of s plus EOS iff s accepts, A(MOCR_STATE_DEAD)
+ *     empty, EOS a member of every token set as in the *_beam_tokens section; the beam's own n-gram bans are -inf as well.
+ *     Nothing renormalises: PrefixConstrainedLogitsProcessor word for word, the rule of the *_beam_tokens section with the set
+ *     depending on the state.  There is NO dead-end rule here, unlike greedy: a beam whose effective set is empty is a dead
+ *     beam, all its candidates are -inf, and the DEAD CANDIDATES rule of the token form handles it - a dead candidate never
+ *     enters the finished set, -inf ties go to the lower flat index, the next beams are the best K of (score, -1e9 on the
+ *     stopped ones) by value.
+ *   THE STATE after the selection: a new running beam made from candidate (parent p, token x) is in next(s_p, x), or in
+ *     MOCR_STATE_DEAD where s_p has no such edge (a -inf candidate, or a stopped one carried on at -1e9: EOS is never an
+ *     edge).  A hypothesis that enters the finished set keeps s_p if it stopped on EOS (EOS moves nothing) and next(s_p, x)
+ *     if it stopped by completing generate(max_length) tokens (the last token walks, as in greedy).  The state moves with the
+ *     hypothesis wherever its ids move, the shift under an inserted hypothesis included.  The K old states are read before
+ *     any state is written.
+ *   Everything else - stopping, the finished set, length_penalty, early_stopping, the heuristic, the ties, the token scores
+ *     (the very fp32 value that was ranked), the trail and the positions - is the token form's definition.
+ *   Bit-identities, in ids, lengths, sequence scores, token scores and positions: a crop with MOCR_AUTOMATON_NONE inside a batch
+ *     that has automaton crops gives the result of the same crop in a token-form batch of the same size; a crop under the
+ *     universal automaton gives the same as a crop with MOCR_AUTOMATON_NONE; a one-state automaton whose self-loops are the
+ *     members of a token set gives the same as that set passed through `sets`.  A batch in which nobody brings an automaton
+ *     launches exactly what it launched before.
+ *   out_state int32 [n][K]: for hypothesis (c, j) the state after the hypothesis' last non-EOS token, in the automaton's own
+ *     numbering; MOCR_STATE_NONE for a crop without an automaton, for an empty slot (length 0) and for a sliver region.  A
+ *     finished hypothesis is never MOCR_STATE_DEAD: its score is finite, so every one of its tokens had an edge.
+ *   With fewer reachable entries than K, the slots beyond them hold what the search leaves there: continuations of the
+ *     padding beams that start at -1e9 (duplicates that score about -1e9), or nothing.  The calls deliver that as it is.
+ *   How: the selection kernel's automaton form (profile names beam_select_am / beam_select_am_tr) builds every beam's mask in
+ *     LDS from the edges of its state; one lane per winner finds the next state by binary search.  The tables reach it as one
+ *     trailing argument.  The beams' states are the greedy calls' row states; the hypotheses' states (4 B a row and lane) are
+ *     allocated by the first beam batch that brings an automaton, and mocr_automaton_state_bytes counts them.
+ * The *_beam_automaton entry points: the *_beam_positions twins plus `automata`, a HOST int32 array [n] of handles, one per
+ * crop (null: every crop MOCR_AUTOMATON_NONE; copied before the call returns), and out_state int32 [n][K] (nullable; host, or
+ * device for the device twin).  With both null they ARE the *_beam_positions calls.  An unknown handle is MOCR_ERR_ARG before
+ * any work. */
+int mocr_recognize_images_beam_automaton(mocr_engine* e, const mocr_image* images, int32_t n, const mocr_beam_config* beam, int32_t* out_ids,
+                                         int32_t* out_len, float* out_score, float* out_logp, const int32_t* sets, float* out_pos,
+                                         const int32_t* automata, int32_t* out_state);
+int mocr_recognize_regions_beam_automaton(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                          int32_t n_regions, const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len,
+                                          float* out_score, float* out_logp, const int32_t* sets, float* out_pos,
+                                          const int32_t* automata, int32_t* out_state);
+int mocr_recognize_gray_host_beam_automaton(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override,
+                                            const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len, float* out_score,
+                                            float* out_logp, const int32_t* sets, float* out_pos, const int32_t* automata,
+                                            int32_t* out_state);
+int mocr_recognize_device_beam_automaton(mocr_engine* e, const void* d_gray, int32_t n, const mocr_beam_config* beam, void* d_out_ids,
+                                         void* d_out_len, void* d_out_score, void* d_out_logp, const int32_t* sets, void* d_out_pos,
+                                         const int32_t* automata, void* d_out_state);
+
 /* Bytes of beam state this engine holds, over its lanes (test hook): 0 until a lane runs its first beam batch - creating an
  * engine and greedy calls of any kind allocate none of it. */
 int64_t mocr_beam_state_bytes(mocr_engine* e);
@@ -1046,6 +1103,16 @@ int mocr_op_beam_select_positions(mocr_engine* e, const mocr_token_args* a, cons
                                   int32_t* d_parent, int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open,
                                   float* d_beam_logp, float* d_hyp_logp, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
                                   uint8_t* d_beam_trail, uint8_t* d_hyp_trail);
+/* ... under token automata: mocr_op_beam_select_positions plus the CSR tables over global state numbers (as
+ * mocr_op_dec_token_automaton takes them), d_aut_base_of_row [rows] (the crop's start state, -1: none), d_aut_state [rows] (in /
+ * out: the running beams' states) and d_hyp_state [rows] (in / out: the finished hypotheses' states, by crop K + slot).  All
+ * seven null: it IS mocr_op_beam_select_positions; otherwise all seven set. */
+int mocr_op_beam_select_automaton(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score,
+                                  int32_t* d_parent, int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open,
+                                  float* d_beam_logp, float* d_hyp_logp, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
+                                  uint8_t* d_beam_trail, uint8_t* d_hyp_trail, const int32_t* d_edge_begin, const int32_t* d_edge_token,
+                                  const int32_t* d_edge_next, const uint8_t* d_accepting, const int32_t* d_aut_base_of_row,
+                                  int32_t* d_aut_state, int32_t* d_hyp_state);
 /* The cache reorder behind it: d_cache viewed as [layers][rows][segs][positions][pos_bytes] through byte strides; for
  * every group of K slots whose crop is live (d_finished[rowmap[g K]] == 0), row rowmap[g K + k] <- row
  * rowmap[g K + d_parent[rowmap[g K + k]]], bytes 0 .. d_step[g K] * pos_bytes - 1 of every (layer, segment).  max_pos bounds

@@ -163,6 +163,9 @@ struct LaneCtx {
     float *beam_logp = nullptr, *hyp_logp = nullptr;    // [Bp][max_len]
     // ... and its trail form: allocated by the first beam batch that asks for token positions (ensure_beam_position_buffers)
     uint8_t *beam_trail = nullptr, *hyp_trail = nullptr;    // [Bp][max_len]
+    // ... and its automaton form: allocated by the first beam batch that brings a token automaton (ensure_beam_automaton_buffers);
+    // the running beams' states are aut_state, the crops' start states aut_base_of_row
+    int* hyp_state = nullptr;                       // [Bp] the global state of every finished hypothesis (AUT_STATE_NONE: none), by row
     float *x_f32 = nullptr, *a_f32 = nullptr, *c_f32 = nullptr;
     float* ln_stats = nullptr;                      // small-batch path: (mean, rstd) per row of the three pre-LayerNorm sums, [3][Bp][2]
     void *x_t = nullptr, *a_t = nullptr, *c_t = nullptr, *ctx_t = nullptr, *h_t = nullptr, *z_t = nullptr;
@@ -234,14 +237,16 @@ struct DecMode {
     mocr_beam_config beam_cfg{};
     bool beam_tokens = false;       // ... in which a job asks for token scores or brings a token set other than MOCR_TOKEN_SET_ALL: the
                                     // selection runs in its token form (level and mask stay 0: the LM head and the caches do not change)
+    bool beam_automaton = false;    // ... in which a job brings a token automaton other than MOCR_AUTOMATON_NONE (implies beam_tokens): the
+                                    // selection runs in its automaton form and the batch starts with beam_automaton_init_kernel
     // a graph captured in one mode is never replayed in another: the mode's share of the decode-graph key (6 bits; a beam
-    // batch: bit 6, its token form: bit 7, an automaton batch: bit 8, and a beam batch's configuration - kernel arguments of
-    // the captured launches - in the bits above, beam_key)
+    // batch: bit 6, its token form: bit 7, an automaton batch: bit 8, a beam batch's automaton form: bit 9, and a beam
+    // batch's configuration - kernel arguments of the captured launches - in the bits above, beam_key)
     int key_bits() const {
         return level + (mask ? 4 : 0) + (ngram ? 8 : 0) + (positions ? 16 : 0) + (prefix ? 32 : 0) + (beam ? 64 : 0) + (beam_tokens ? 128 : 0) +
-               (automaton ? 256 : 0);
+               (automaton ? 256 : 0) + (beam_automaton ? 512 : 0);
     }
-    static constexpr int KEY_SPAN = 512;
+    static constexpr int KEY_SPAN = 1024;
     int epilogue() const { return mask ? (level == 2 ? EPI_TOPK_M : level == 1 ? EPI_ARGMAX_LSE_M : EPI_ARGMAX_M)
                                        : (level == 2 ? EPI_TOPK : level == 1 ? EPI_ARGMAX_LSE : EPI_ARGMAX); }
     // profile names of the fused LM head and of the token kernel
@@ -266,7 +271,9 @@ static DecMode mode_of(const std::vector<Job>& jobs) {
         for (const Job& j : jobs) {
             m.beam_tokens = m.beam_tokens || j.out_logp || !j.sets.empty();
             m.positions = m.positions || j.out_pos;
+            m.beam_automaton = m.beam_automaton || !j.automata.empty();     // (slice_rows: MOCR_AUTOMATON_NONE alone comes as empty)
         }
+        m.beam_tokens = m.beam_tokens || m.beam_automaton;
         return m;
     }
     for (const Job& j : jobs) {
@@ -1388,17 +1395,24 @@ static BeamState make_beam_state(mocr_engine* e, const mocr_beam_config& c, bool
     return bs;
 }
 
+// the trailing argument of the automaton form, on the engine's tables and the bound lane's states
+static BeamAutomata make_beam_automata(mocr_engine* e) {
+    return BeamAutomata{e->aut_edge_begin, e->aut_edge_token, e->aut_edge_next, e->aut_accepting, e->aut_base_of_row, e->aut_state, e->hyp_state};
+}
+
 // n decode slots = groups of K (a trailing partial group is padding); the LM head's slabs, by slot, are in `a`
 template <typename T>
-void launch_beam_select(mocr_engine* e, const DecState& st, const BeamState& bs, const DecTokenArgs& a, int n, int K) {
+void launch_beam_select(mocr_engine* e, const DecState& st, const BeamState& bs, const DecTokenArgs& a, int n, int K,
+                        const BeamAutomata& aut = BeamAutomata{}) {
     auto& w = e->w;
     if (e->D != 768 || e->V != 6144 || st.ids_ld > BEAM_HIST || st.max_len > st.ids_ld || a.nslab < 1)
         throw ArgError{"beam search needs hidden 768, vocab 6144 and max_len <= 320", MOCR_ERR_UNSUPPORTED};
-    ProfScope ps(e, (bs.beam_logp || bs.tok_mask) ? "beam_select_tok" : "beam_select", 0, (double)n * e->V * 4 * a.nslab);
+    ProfScope ps(e, aut.state ? (bs.beam_trail ? "beam_select_am_tr" : "beam_select_am") : (bs.beam_logp || bs.tok_mask) ? "beam_select_tok" : "beam_select",
+                 0, (double)n * e->V * 4 * a.nslab);
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3((n + K - 1) / K), dim3(256), 0, e->stream, a.slabs, a.nslab, a.slab_stride, a.vbias, e->V, st, bs, n,
                            w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32, reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps,
-                           reinterpret_cast<T*>(a.cache), a.cstride, a.cache8, a.inv8);
+                           reinterpret_cast<T*>(a.cache), a.cstride, a.cache8, a.inv8, aut);
     };
     // the token form when the state carries any of its four arrays (make_beam_state sets them from the batch's DecMode)
     const bool tok = bs.beam_logp || bs.hyp_logp || bs.tok_mask || bs.set_of_row;
@@ -1408,6 +1422,22 @@ void launch_beam_select(mocr_engine* e, const DecState& st, const BeamState& bs,
     const bool trail = bs.beam_trail || bs.hyp_trail;
     if ((bs.beam_trail == nullptr) != (bs.hyp_trail == nullptr))
         throw ArgError{"beam_select: the two trails come as a pair", MOCR_ERR_ARG};
+    // ... and the automaton form, a token form, when the trailing argument is set (all seven pointers or none)
+    if (aut.state) {
+        if (!aut.edge_begin || !aut.edge_token || !aut.edge_next || !aut.accepting || !aut.base_of_row || !aut.hyp_state)
+            throw ArgError{"beam_select: the automaton tables, the rows' bases and the two state arrays come together", MOCR_ERR_ARG};
+        switch (K * 2 + (trail ? 1 : 0)) {
+            case 4: launch(beam_select_kernel<T, 2, true, false, true>); break;
+            case 6: launch(beam_select_kernel<T, 3, true, false, true>); break;
+            case 8: launch(beam_select_kernel<T, 4, true, false, true>); break;
+            case 5: launch(beam_select_kernel<T, 2, true, true, true>); break;
+            case 7: launch(beam_select_kernel<T, 3, true, true, true>); break;
+            case 9: launch(beam_select_kernel<T, 4, true, true, true>); break;
+            default: throw ArgError{"num_beams must be 2 .. 4", MOCR_ERR_ARG};
+        }
+        HIPCHECK(hipGetLastError());
+        return;
+    }
     switch (K * 4 + (trail ? 2 : 0) + (tok ? 1 : 0)) {
         case 8: launch(beam_select_kernel<T, 2>); break;
         case 12: launch(beam_select_kernel<T, 3>); break;
@@ -1458,7 +1488,8 @@ void beam_finish_step(mocr_engine* e, const DecState& st, const DecMode& m, int 
     a.cache8 = (lat && e->fp8attn) ? e->x8cache : nullptr;
     a.inv8 = (lat && e->fp8attn) ? 1.0f / e->w.sx_self[0] : 0.f;
     a.cstride = (long long)e->cfg.max_len * e->D;
-    launch_beam_select<T>(e, st, make_beam_state(e, m.beam_cfg, m.beam_tokens, m.positions), a, n, K);
+    launch_beam_select<T>(e, st, make_beam_state(e, m.beam_cfg, m.beam_tokens, m.positions), a, n, K,
+                          m.beam_automaton ? make_beam_automata(e) : BeamAutomata{});
     // `t` bounds the step index of this launch from above only when it is exact (eager steps).  A captured graph passes
     // t = t_hi - 1 for every step of its bucket (decode_graph), and the bucket's last device step is t_hi itself
     // (t0 + steps <= 32 * bucket): behind it `step` is t_hi + 1 = t + 2 positions.  The grid is sized for that; the kernel
@@ -2311,6 +2342,14 @@ static void ensure_beam_token_buffers(mocr_engine* e) {
     e->hyp_logp = e->dalloc<float>(Bp * e->cfg.max_len);
 }
 
+// The automaton form's hypothesis states, for the bound lane (the beams' states and the crops' start states are the greedy
+// automaton buffers): allocated by the first beam batch that brings a token automaton.
+static void ensure_beam_automaton_buffers(mocr_engine* e) {
+    ensure_automaton_buffers(e);
+    if (e->hyp_state) return;
+    e->hyp_state = e->dalloc<int>((size_t)e->Bp);
+}
+
 // The trail form's two histories, for the bound lane: allocated by the first beam batch that asks for token positions.
 static void ensure_beam_position_buffers(mocr_engine* e) {
     if (e->hyp_trail) return;
@@ -2461,6 +2500,21 @@ void start_batch(mocr_engine* e, Lane& L) {
             upload_per_row(e, L, L.h_sets, &Job::sets, MOCR_TOKEN_SET_ALL, e->set_of_row);
         }
         if (m.positions) ensure_beam_position_buffers(e);
+        if (m.beam_automaton) {     // the crops' start states by row (c K + k, like the sets), padding rows without one
+            ensure_beam_automaton_buffers(e);
+            L.h_aut.assign((size_t)L.np, -1);
+            int r0 = 0;
+            for (const Job& j : L.jobs) {
+                for (size_t i = 0; i < j.automata.size(); ++i)
+                    if (j.automata[i] != MOCR_AUTOMATON_NONE) L.h_aut[r0 + i] = e->aut_first[j.automata[i]];
+                r0 += j.n;
+            }
+            HIPCHECK(hipMemcpyAsync(e->aut_base_of_row, L.h_aut.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
+            ProfScope pa(e, "beam_automaton_init", 0, (double)L.np * 12);
+            hipLaunchKernelGGL(beam_automaton_init_kernel, dim3((L.np + 255) / 256), dim3(256), 0, e->stream, (const int*)e->aut_base_of_row,
+                               e->aut_state, e->hyp_state, L.np);
+            HIPCHECK(hipGetLastError());
+        }
         ProfScope ps(e, "beam_init", 0, (double)L.np * e->cfg.max_len * 4);
         hipLaunchKernelGGL(beam_init_kernel, dim3(L.np), dim3(64), 0, e->stream, make_beam_state(e, m.beam_cfg, m.beam_tokens, m.positions),
                            m.beam_cfg.num_beams, L.np, e->cfg.max_len, e->cfg.pad_id);
@@ -2480,6 +2534,11 @@ void finish_batch(mocr_engine* e, Lane& L) {
                            (const int*)e->aut_base_of_row, e->aut_state_out, L.n);
         HIPCHECK(hipGetLastError());
     }
+    if (L.mode.beam_automaton) { // ... and the hypotheses' states (an empty slot and a crop without an automaton: MOCR_STATE_NONE)
+        hipLaunchKernelGGL(automaton_state_out_kernel, dim3((L.n + 255) / 256), dim3(256), 0, e->stream, (const int*)e->hyp_state,
+                           (const int*)e->aut_base_of_row, e->aut_state_out, L.n);
+        HIPCHECK(hipGetLastError());
+    }
     int row0 = 0;
     for (const Job& j : L.jobs) {
         const hipMemcpyKind kind = j.out_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
@@ -2492,6 +2551,11 @@ void finish_batch(mocr_engine* e, Lane& L) {
             if (j.out_pos) {        // (a batch with such a job kept the trails and ran the deferred pass over its hypotheses)
                 const size_t ld = (size_t)e->cfg.max_len * MOCR_POSITION_FIELDS;
                 HIPCHECK(hipMemcpyAsync(j.out_pos, e->pos_out + row0 * ld, j.n * ld * sizeof(float), kind, e->stream));
+            }
+            if (j.out_state) {      // (a batch in which nobody brings an automaton keeps no states)
+                if (L.mode.beam_automaton) HIPCHECK(hipMemcpyAsync(j.out_state, e->aut_state_out + row0, (size_t)j.n * sizeof(int), kind, e->stream));
+                else if (j.out_host) std::fill(j.out_state, j.out_state + j.n, (int32_t)MOCR_STATE_NONE);
+                else HIPCHECK(hipMemsetAsync(j.out_state, 0xFF, (size_t)j.n * sizeof(int), e->stream));
             }
             row0 += j.n;
             continue;
@@ -3269,7 +3333,10 @@ int64_t mocr_automaton_state_bytes(mocr_engine* e) {
     std::lock_guard<std::mutex> lk(e->mu);
     int64_t bytes = e->aut_edge_begin ? (int64_t)AUT_ARENA_BYTES : 0;
     for (const Lane& L : e->lanes)
+    {
         if (L.ctx.aut_state) bytes += 3 * (int64_t)e->Bp * (int64_t)sizeof(int);
+        if (L.ctx.hyp_state) bytes += (int64_t)e->Bp * (int64_t)sizeof(int);      // the automaton form of beam search
+    }
     return bytes;
 }
 
@@ -3300,9 +3367,9 @@ struct Request {
     int32_t* out_state = nullptr;
 };
 
-// token automata: one handle per row, MOCR_AUTOMATON_NONE or an automaton this engine has created; never on a beam request
+// token automata: one handle per row, MOCR_AUTOMATON_NONE or an automaton this engine has created (a beam request comes
+// from the *_beam_automaton entry points alone, with its crops' handles expanded to their K rows)
 static void require_automata(const mocr_engine* e, const Request& r, int n) {
-    if ((r.automata || r.out_state) && r.beam) throw ArgError{"beam search takes no token automaton", MOCR_ERR_ARG};
     if (!r.automata) return;
     const int count = (int)e->aut_first.size();
     for (int i = 0; i < n; ++i)
@@ -4072,9 +4139,10 @@ int mocr_recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_pa
 // request with source[c K + k] = c - plus the configuration and the score output; the checks come before any work.
 // The *_beam_tokens twins add out_logp [n][K][max_len] = [rows][max_len] and one set handle per crop, expanded to its K rows;
 // the *_beam_positions twins add out_pos [n][K][max_len][MOCR_POSITION_FIELDS] to those.
-struct BeamCall { std::vector<int32_t> source, sets; Request req; int rows = 0; };
+// The *_beam_automaton twins add one automaton handle per crop, expanded like the sets, and out_state [n][K] = [rows].
+struct BeamCall { std::vector<int32_t> source, sets, automata; Request req; int rows = 0; };
 static int beam_call(mocr_engine* e, const mocr_beam_config* beam, int32_t n, void* out_score, BeamCall& bc, void* out_logp = nullptr,
-                     const int32_t* sets = nullptr, void* out_pos = nullptr) {
+                     const int32_t* sets = nullptr, void* out_pos = nullptr, const int32_t* automata = nullptr, void* out_state = nullptr) {
     return guarded(e, [&] {
         if (!beam || beam->num_beams < 2 || beam->num_beams > MOCR_MAX_BEAMS) throw ArgError{"num_beams must be 2 .. MOCR_MAX_BEAMS (4)", MOCR_ERR_ARG};
         if (beam->early_stopping < 0 || beam->early_stopping > 2) throw ArgError{"early_stopping must be 0 (false), 1 (true) or 2 (never)", MOCR_ERR_ARG};
@@ -4096,6 +4164,12 @@ static int beam_call(mocr_engine* e, const mocr_beam_config* beam, int32_t n, vo
             for (int i = 0; i < bc.rows; ++i) bc.sets[i] = sets[i / K];
             bc.req.sets = bc.sets.data();        // (validate_request refuses an unknown handle)
         }
+        if (automata) {
+            bc.automata.resize((size_t)bc.rows);
+            for (int i = 0; i < bc.rows; ++i) bc.automata[i] = automata[i / K];
+            bc.req.automata = bc.automata.data();       // (likewise)
+        }
+        bc.req.out_state = static_cast<int32_t*>(out_state);
     });
 }
 
@@ -4156,6 +4230,40 @@ int mocr_recognize_device_beam_positions(mocr_engine* e, const void* d_gray, int
                                          void* d_out_len, void* d_out_score, void* d_out_logp, const int32_t* sets, void* d_out_pos) {
     BeamCall bc;
     if (const int rc = beam_call(e, beam, n, d_out_score, bc, d_out_logp, sets, d_out_pos)) return rc;
+    return recognize_device(e, d_gray, bc.rows, d_out_ids, d_out_len, bc.req);
+}
+
+int mocr_recognize_images_beam_automaton(mocr_engine* e, const mocr_image* images, int32_t n, const mocr_beam_config* beam, int32_t* out_ids,
+                                         int32_t* out_len, float* out_score, float* out_logp, const int32_t* sets, float* out_pos,
+                                         const int32_t* automata, int32_t* out_state) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, out_score, bc, out_logp, sets, out_pos, automata, out_state)) return rc;
+    return recognize_images(e, images, bc.rows, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_regions_beam_automaton(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                          int32_t n_regions, const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len,
+                                          float* out_score, float* out_logp, const int32_t* sets, float* out_pos,
+                                          const int32_t* automata, int32_t* out_state) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n_regions, out_score, bc, out_logp, sets, out_pos, automata, out_state)) return rc;
+    return recognize_regions(e, pages, n_pages, regions, n_regions, bc.rows, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_gray_host_beam_automaton(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override,
+                                            const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len, float* out_score,
+                                            float* out_logp, const int32_t* sets, float* out_pos, const int32_t* automata,
+                                            int32_t* out_state) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, out_score, bc, out_logp, sets, out_pos, automata, out_state)) return rc;
+    return recognize_gray_host(e, gray, bc.rows, max_len_override, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_device_beam_automaton(mocr_engine* e, const void* d_gray, int32_t n, const mocr_beam_config* beam, void* d_out_ids,
+                                         void* d_out_len, void* d_out_score, void* d_out_logp, const int32_t* sets, void* d_out_pos,
+                                         const int32_t* automata, void* d_out_state) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, d_out_score, bc, d_out_logp, sets, d_out_pos, automata, d_out_state)) return rc;
     return recognize_device(e, d_gray, bc.rows, d_out_ids, d_out_len, bc.req);
 }
 
@@ -5012,6 +5120,17 @@ int mocr_op_beam_select_positions(mocr_engine* e, const mocr_token_args* a, cons
                                   int32_t* d_parent, int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open,
                                   float* d_beam_logp, float* d_hyp_logp, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
                                   uint8_t* d_beam_trail, uint8_t* d_hyp_trail) {
+    return mocr_op_beam_select_automaton(e, a, beam, d_beam_score, d_parent, d_hyp_ids, d_hyp_len, d_hyp_score, d_heuristic_open, d_beam_logp,
+                                         d_hyp_logp, d_tok_mask, d_set_of_row, d_beam_trail, d_hyp_trail, nullptr, nullptr, nullptr, nullptr,
+                                         nullptr, nullptr, nullptr);
+}
+
+int mocr_op_beam_select_automaton(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score,
+                                  int32_t* d_parent, int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open,
+                                  float* d_beam_logp, float* d_hyp_logp, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
+                                  uint8_t* d_beam_trail, uint8_t* d_hyp_trail, const int32_t* d_edge_begin, const int32_t* d_edge_token,
+                                  const int32_t* d_edge_next, const uint8_t* d_accepting, const int32_t* d_aut_base_of_row,
+                                  int32_t* d_aut_state, int32_t* d_hyp_state) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -5024,6 +5143,10 @@ int mocr_op_beam_select_positions(mocr_engine* e, const mocr_token_args* a, cons
             a->ids_ld < 2 || a->ids_ld > BEAM_HIST || a->max_len < 2 || a->max_len > a->ids_ld || a->max_len > e->cfg.max_len ||
             !d_beam_score || !d_parent || !d_hyp_ids || !d_hyp_len || !d_hyp_score || !d_heuristic_open)
             throw ArgError{"mocr_op_beam_select: bad argument", MOCR_ERR_ARG};
+        const void* const aut_ptrs[7] = {d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state, d_hyp_state};
+        for (const void* p : aut_ptrs)
+            if ((p == nullptr) != (d_aut_state == nullptr))
+                throw ArgError{"mocr_op_beam_select_automaton: the seven automaton pointers must be all null or all set", MOCR_ERR_ARG};
         DecState st{};
         st.n_real = a->n_real;
         st.ids = a->ids; st.step = a->step; st.finished = a->finished; st.len = a->len; st.n_unfinished = a->n_unfinished;
@@ -5043,7 +5166,8 @@ int mocr_op_beam_select_positions(mocr_engine* e, const mocr_token_args* a, cons
         if (a->cache && a->cache_fp8) { t.cache8 = reinterpret_cast<uint8_t*>(a->cache); t.inv8 = a->inv_sx; }
         else t.cache = a->cache;
         t.cstride = (long long)e->cfg.max_len * e->D;
-        dispatch(e, [&](auto tag) { launch_beam_select<decltype(tag)>(e, st, bs, t, a->n, beam->num_beams); });
+        const BeamAutomata aut{d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state, d_hyp_state};
+        dispatch(e, [&](auto tag) { launch_beam_select<decltype(tag)>(e, st, bs, t, a->n, beam->num_beams, aut); });
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }

@@ -32,6 +32,33 @@ struct BeamState {
     uint8_t* hyp_trail;     // [rows][ids_ld] those of the finished hypotheses, 0 behind their length: moves as hyp_ids does
 };
 
+// Token automata under beam search (mocr.h, "beam search under a token automaton"): the LAST argument of beam_select_kernel,
+// read by its AUT form only - a trailing argument, so that BeamState and every other argument stay where they were.  The
+// engine's tables in CSR form over GLOBAL state numbers (DecAutomata's), and by ROW like ids: base_of_row, the global number of
+// the crop's start state (-1: the crop brings no automaton; its K rows name the same one), state, the state every running
+// beam is in (AUT_STATE_DEAD once a chosen token had no edge), and hyp_state, the state of every finished hypothesis behind
+// its last token other than EOS - it moves as hyp_ids does.
+struct BeamAutomata {
+    const int* edge_begin;
+    const int* edge_token;
+    const int* edge_next;
+    const uint8_t* accepting;
+    const int* base_of_row;
+    int* state;
+    int* hyp_state;
+};
+
+// Start of a beam batch under token automata, beside beam_init_kernel (as automaton_init_kernel is to ngram_init_kernel):
+// every running beam in its crop's start state, every finished slot without one.
+__global__ __launch_bounds__(256) void beam_automaton_init_kernel(const int* __restrict__ base_of_row, int* __restrict__ state,
+                                                                  int* __restrict__ hyp_state, int rows) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const int base = base_of_row[r];
+    state[r] = base >= 0 ? base : AUT_STATE_NONE;
+    hyp_state[r] = AUT_STATE_NONE;
+}
+
 // Start of a beam batch, one block of 64 threads per row: running scores [0, -1e9, ...], an empty finished set.
 __global__ __launch_bounds__(64) void beam_init_kernel(BeamState bs, int K, int rows, int ids_ld, int pad_id) {
     const int r = blockIdx.x;
@@ -87,17 +114,32 @@ __global__ __launch_bounds__(64) void beam_init_kernel(BeamState bs, int K, int 
 //     that step's recordings (the engine's pos_hist) lie in, since those are written by row and never reordered.  It travels
 //     with ids (through s_thist), and the entry of the token this step appends is the candidate's parent; hyp_trail travels
 //     with hyp_ids (through s_thyp), the shift under an inserted hypothesis included.  One byte per entry: K <= 4.
+// AUT, the automaton form (implies TOK; a crop whose base_of_row is -1 takes the token form's path, bit for bit):
+//   every beam walks the crop's automaton with a state of its own.  Beam k's mask is built in LDS from the edge range of its
+//     state - zero, barrier, the 256 threads stride over the edges (the universal state: 6,143 of them, 24 a thread) with LDS
+//     atomicOr plus the EOS bit iff the state accepts, barrier, AND the crop's set word - and then takes the n-gram bans as in
+//     the token form.  A DEAD beam, or a set that meets no edge, leaves an empty mask: a dead beam, the token form's DEAD
+//     CANDIDATES rule.  There is no dead-end rule.  Every branch is block-uniform (the base and the states come from LDS);
+//   behind thread 0's section, beside the lanes that recompute lp, one lane per winner finds next(state of the parent, token)
+//     by binary search over the parent's edges (a state's tokens are strictly ascending): AUT_STATE_DEAD when absent.  Thread
+//     0's decisions need no state;
+//   a new running beam takes its candidate's state; a hypothesis that enters the finished set keeps the parent's state if it
+//     stopped on EOS (EOS moves nothing) and the candidate's if it stopped by length (the last token walks, as in greedy).
+//     The K old beam states and the K old hypothesis states are in LDS before any state is written - the argument of s_hist.
 // LDS, static, at K = 4: ids and hypotheses 2 x 5 KiB, their log-probabilities 2 x 5 KiB (token form only), their trails
-// 2 x 1.25 KiB (trail form only), the mask 768 B, under 1 KiB of lists - 24 KiB of the 64 KiB a block may declare.
-template <typename T, int K, bool TOK = false, bool TRAIL = false>
+// 2 x 1.25 KiB (trail form only), the mask 768 B, under 1 KiB of lists - 24 KiB of the 64 KiB a block may declare (the
+// automaton form's K + K + 2 K states and the base: 68 B more).
+template <typename T, int K, bool TOK = false, bool TRAIL = false, bool AUT = false>
 __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restrict__ slabs, int nslab, long long slab_stride,
                                                           const float* __restrict__ vbias, int V, DecState st, BeamState bs, int np,
                                                           const float* __restrict__ word, const float* __restrict__ type0,
                                                           const float* __restrict__ pos, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, float* __restrict__ x_f32,
                                                           T* __restrict__ x_t, float eps, T* __restrict__ cache,
-                                                          long long cache_batch_stride, uint8_t* __restrict__ cache8, float inv_sx8) {
+                                                          long long cache_batch_stride, uint8_t* __restrict__ cache8, float inv_sx8,
+                                                          BeamAutomata aut = BeamAutomata{}) {
     static_assert(K >= 2 && K <= BEAM_MAX, "2 .. 4 beams");
+    static_assert(!AUT || TOK, "the automaton form is a token form: its masks and the dead-candidate rule");
     constexpr int D = 768, MW = 192, NC = 6, C2 = 2 * K;
     __shared__ int s_hist[K][BEAM_HIST];
     __shared__ int s_hyp[K][BEAM_HIST];
@@ -117,8 +159,12 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
     __shared__ uint8_t s_thyp[KR][HR];
     __shared__ float s_gmax[K], s_logS[K], s_clp[C2];
     __shared__ int s_clive[C2], s_nsrc[K];            // the candidate is not dead; the candidate new beam k was made from
-    static_assert(sizeof(s_hist) + sizeof(s_hyp) + sizeof(s_lhist) + sizeof(s_lhyp) + sizeof(s_thist) + sizeof(s_thyp) + sizeof(s_mask) + 1024 <= 65536,
-                  "static LDS of the selection: the histories, the mask and under 1 KiB of lists");
+    constexpr int KA = AUT ? K : 1;
+    __shared__ int s_ast[KA], s_hst[KA], s_cst[2 * KA];   // the K beams' states, the K hypotheses' states, the 2 K candidates' next states
+    __shared__ int s_abase;                               // the crop's start state (-1: it brings no automaton)
+    static_assert(sizeof(s_hist) + sizeof(s_hyp) + sizeof(s_lhist) + sizeof(s_lhyp) + sizeof(s_thist) + sizeof(s_thyp) + sizeof(s_mask) +
+                          sizeof(s_ast) + sizeof(s_hst) + sizeof(s_cst) + sizeof(s_abase) + 1024 <= 65536,
+                  "static LDS of the selection: the histories, the mask, the states and under 1 KiB of lists");
     const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int slot0 = g * K;
     if (slot0 + K > np) {                             // a trailing partial group: padding slots, born finished
@@ -135,6 +181,10 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
     const int L = t + 1;                              // tokens every running beam holds
     const int crop = row0 / K;
     if (tid < K) s_row[tid] = st.rowmap[slot0 + tid];
+    if constexpr (AUT) {                              // the K old states of both kinds, before any is written
+        if (tid < K) { s_ast[tid] = aut.state[st.rowmap[slot0 + tid]]; s_hst[tid] = aut.hyp_state[crop * K + tid]; }
+        if (tid == 0) s_abase = aut.base_of_row[row0];
+    }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < K; ++k)
@@ -178,7 +228,26 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
         for (int j = 0; j < NC; ++j) mx = fmaxf(fmaxf(mx, fmaxf(a[j].x, a[j].y)), fmaxf(a[j].z, a[j].w));
         mx = wave_max(mx);
         if (lane == 0) s_red[wave] = mx;
-        if constexpr (TOK) {
+        if constexpr (AUT) {
+            if (s_abase >= 0) {                       // block-uniform: A(state of beam k), then the crop's set
+                if (tid < MW) s_mask[tid] = 0u;
+                __syncthreads();
+                const int sk = s_ast[k];
+                if (sk >= 0) {
+                    const int e1 = aut.edge_begin[sk + 1];
+                    for (int i = aut.edge_begin[sk] + tid; i < e1; i += 256) {
+                        const int x = aut.edge_token[i];
+                        if ((unsigned)x < (unsigned)V) atomicOr(&s_mask[x >> 5], 1u << (x & 31));
+                    }
+                    if (tid == 0 && aut.accepting[sk] && (unsigned)st.eos_id < (unsigned)V)
+                        atomicOr(&s_mask[st.eos_id >> 5], 1u << (st.eos_id & 31));
+                }
+                __syncthreads();
+                if (tid < MW) s_mask[tid] &= setw;
+            } else {
+                if (tid < MW) s_mask[tid] = setw;
+            }
+        } else if constexpr (TOK) {
             if (tid < MW) s_mask[tid] = setw;
         } else {
             if (n > 0 && tid < MW) s_mask[tid] = 0xffffffffu;
@@ -336,6 +405,23 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
                 lp = (v - s_gmax[p]) - s_logS[p];
             }
             s_clp[tid] = lp;
+            if constexpr (AUT) {
+                // ... and their states: next(state of the parent, token), a binary search over the parent's ascending tokens
+                int ns = AUT_STATE_NONE;
+                if (s_abase >= 0) {
+                    ns = AUT_STATE_DEAD;
+                    const int sp = s_ast[s_cpar[tid]], c = s_ctok[tid];
+                    if (sp >= 0) {
+                        int lo = aut.edge_begin[sp], hi = aut.edge_begin[sp + 1];
+                        while (lo < hi) {
+                            const int mid = (lo + hi) >> 1;
+                            if (aut.edge_token[mid] < c) lo = mid + 1; else hi = mid;
+                        }
+                        if (lo < aut.edge_begin[sp + 1] && aut.edge_token[lo] == c) ns = aut.edge_next[lo];
+                    }
+                }
+                s_cst[tid] = ns;
+            }
         }
         __syncthreads();
     }
@@ -386,6 +472,22 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
                 }
             }
         }
+        if constexpr (AUT) {
+            // the hypotheses' states move with them: an old slot's from LDS, a new one's from its candidate - the parent's
+            // state behind EOS, the candidate's own behind a token that completed max_len
+            if (tid < K) {
+                const int src = s_hsrc[tid];
+                if (src != tid) {
+                    int v;
+                    if (src >= 0) v = s_hst[src];
+                    else {
+                        const int ci = -1 - src;
+                        v = s_abase < 0 ? AUT_STATE_NONE : s_ctok[ci] == st.eos_id ? s_ast[s_cpar[ci]] : s_cst[ci];
+                    }
+                    aut.hyp_state[crop * K + tid] = v;
+                }
+            }
+        }
         if constexpr (TRAIL) {
 #pragma unroll
             for (int j = 0; j < K; ++j) {
@@ -423,6 +525,9 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
                 if (tid == 0 && L < st.ids_ld) dst[L] = s_clp[s_nsrc[k]];
             }
         }
+    }
+    if constexpr (AUT) {
+        if (tid < K) aut.state[s_row[tid]] = s_cst[s_nsrc[tid]];
     }
     if constexpr (TRAIL) {
 #pragma unroll

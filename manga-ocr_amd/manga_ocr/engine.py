@@ -344,7 +344,7 @@ class Engine:
         return sets, ngram
 
     def _recognize(self, kind: str, n: int, lead, tail=(), *, beam, d_out=None, skip_empty: bool = False, beam_scores=False, beam_sets=None,
-                   beam_positions=False, **req):
+                   beam_positions=False, beam_automata=None, beam_states=False, **req):
         """The one request path under recognize_images / _regions / _gray / _device.  ``kind``: the source kind as the C symbols
         spell it; ``n``: its number of sources; ``lead()``: (the call's leading C arguments, sources counted last; whatever they
         point into, kept until the call returns) - built only once the call is going to be made; ``tail``: what follows the
@@ -362,7 +362,11 @@ class Engine:
         where not asked - and a host kind returns logp [n,K,max_len] behind the scores when asked.
         ``beam_positions`` (a host kind's flag; recognize_device: its ``d_out_beam_pos`` buffer) belongs to a beam call too: the
         symbol is then mocr_recognize_{kind}_beam_positions - the _beam_tokens call plus out_pos - and a host kind returns pos
-        [n,K,max_len,5] as the LAST element."""
+        [n,K,max_len,5] as the LAST element.
+        ``beam_automata`` (one automaton handle for every crop, or one per crop, None / 0 = none) and ``beam_states`` (a host kind's
+        flag; recognize_device: its ``d_out_beam_state`` buffer) belong to a beam call as well: with either in use the symbol is
+        mocr_recognize_{kind}_beam_automaton - the _beam_positions call plus (automata, out_state), null where not asked - and
+        a host kind returns state int32 [n,K] as the LAST element, behind pos."""
         host = d_out is None
         automata, states = req.pop("automata", None), req.pop("states" if host else "d_out_state", None)
         if beam is not None and (automata is not None or (states is not None and states is not False)):
@@ -371,8 +375,26 @@ class Engine:
         tokens = (beam_scores is not None and beam_scores is not False) or beam_sets is not None
         if (tokens or wants_pos) and beam is None:
             raise ValueError("beam_scores / beam_sets / beam_positions belong to a beam call: pass beam=")
+        wants_aut = beam_automata is not None or (beam_states is not None and beam_states is not False)
+        if wants_aut and beam is None:
+            raise ValueError("beam_automata / beam_states belong to a beam call: pass beam=")
         if beam is not None:
             cfg, *out = self._beam_blocks(beam, n if host else 0, **req)
+            if wants_aut:
+                sets = self._sets(beam_sets, n) if beam_sets is not None else None
+                handles = self._automata(beam_automata, n) if beam_automata is not None else None
+                if host:
+                    logp = np.zeros(out[0].shape, dtype=np.float32) if beam_scores else None
+                    pos = np.zeros(out[0].shape + (_capi.POSITION_FIELDS,), dtype=np.float32) if wants_pos else None
+                    state = np.full(out[1].shape, _capi.STATE_NONE, dtype=np.int32) if beam_states else None
+                else:
+                    logp, pos, state = beam_scores, (beam_positions if wants_pos else None), (beam_states if beam_states is not False else None)
+                if n > 0 or not skip_empty:
+                    args, keep = lead()
+                    self._check(getattr(self.lib, f"mocr_recognize_{kind}_beam_automaton")(
+                        self._h, *args, *tail, C.byref(cfg), *map(_ptr, out if host else d_out), _ptr(logp), _ptr(sets), _ptr(pos),
+                        _ptr(handles), _ptr(state)))
+                return (tuple(out) + tuple(x for x in (logp, pos, state) if x is not None)) if host else None
             if wants_pos:
                 sets = self._sets(beam_sets, n) if beam_sets is not None else None
                 if host:
@@ -426,7 +448,8 @@ class Engine:
 
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False,
                          token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
-                         beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False):
+                         beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False,
+                         beam_automata=None, beam_states: bool = False):
         """Crops of any sizes (list of uint8 [h,w] / [h,w,3] arrays; `bgr`: 3-channel crops are in OpenCV order;
         `rotate`: per crop 0 / 1 (90 degrees clockwise) / 2 (counter-clockwise), applied on the device): luminance
         conversion and the Pillow-exact BILINEAR resize to 224x224 run on the device.
@@ -461,16 +484,24 @@ class Engine:
         ``automata``: a handle of :meth:`automaton` for every ROW, or one per row, None / 0 = none - the row is decoded under
         that token automaton (include/mocr.h, "token automata"); combines with everything but ``beam``.  ``states=True``: one
         more, LAST element state int32 [rows] - the state every row ended in, in its automaton's numbering; -1 without an
-        automaton, -2 for a dead row."""
+        automaton, -2 for a dead row.
+        ``beam_automata`` / ``beam_states=True`` (only with ``beam``; include/mocr.h, "beam search under a token automaton"):
+        ``beam_automata`` is a handle of :meth:`automaton` for every crop, or one per crop, None / 0 = none - all K beams of the
+        crop walk it, each with its own state, so the hypotheses are the K best paths the automaton allows; ``beam_states`` adds
+        a LAST element state int32 [n,K], the state behind every hypothesis' last token other than EOS (-1: no automaton, or an
+        empty slot).  They combine with ``beam_scores`` / ``beam_sets`` / ``beam_positions``; ``automata`` / ``states`` stay
+        refused with ``beam``."""
         def lead():
             descs, keep = self._image_descs(images, bgr, rotate)
             return (descs, len(keep)), keep
         return self._recognize("images", len(images), lead, beam=beam, beam_scores=beam_scores, beam_sets=beam_sets, beam_positions=beam_positions, skip_empty=True, scores=scores, alternatives=alternatives, token_sets=token_sets,
-                               no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources, automata=automata, states=states)
+                               no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources, automata=automata, states=states,
+                               beam_automata=beam_automata, beam_states=beam_states)
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False,
                           token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
-                          beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False):
+                          beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False,
+                         beam_automata=None, beam_states: bool = False):
         """pages: list of uint8 [H,W,3] (or [H,W]) arrays; regions: iterable of (page_index, x, y, w, h) bounding
         rectangles.  Each page is uploaded once; the 8 %-padded, page-clipped crop of every region
         (``src/ui/main_window.py:9530-9540``) is cut on the device.  Returns (ids [n,max_len], lengths [n]);
@@ -496,7 +527,8 @@ class Engine:
                 arr[i].page, arr[i].x, arr[i].y, arr[i].width, arr[i].height = int(pg), int(x), int(y), int(w), int(h)
             return (descs, len(keep), arr, len(regs)), keep
         return self._recognize("regions", len(regs), lead, beam=beam, beam_scores=beam_scores, beam_sets=beam_sets, beam_positions=beam_positions, skip_empty=True, scores=scores, alternatives=alternatives, token_sets=token_sets,
-                               no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources, automata=automata, states=states)
+                               no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources, automata=automata, states=states,
+                               beam_automata=beam_automata, beam_states=beam_states)
 
     def graph_count(self) -> int:
         return int(self.lib.mocr_graph_count(self._h))
@@ -546,7 +578,7 @@ class Engine:
     def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None, d_out_alt_ids=None, d_out_alt_logp=None, *,
                          token_sets=None, no_repeat_ngram=None, d_out_pos=None, prefixes=None, sources=None, beam=None,
                          d_out_score=None, d_out_beam_logp=None, beam_sets=None, d_out_beam_pos=None, automata=None,
-                         d_out_state=None) -> None:
+                         d_out_state=None, beam_automata=None, d_out_beam_state=None) -> None:
         """Asynchronous; all are device buffers (torch CUDA tensors or raw addresses).  ``d_out_logp`` (float32
         [n,max_len]): also the token log-probabilities.  ``d_out_alt_ids`` (int32) with ``d_out_alt_logp`` (float32), both
         [n,max_len,4]: also the token alternatives.  ``token_sets``: a set handle for every crop, or one per crop (host values).
@@ -558,17 +590,20 @@ class Engine:
         ``d_out_len`` int32 [n,K] and ``d_out_score`` float32 [n,K] receive the hypotheses; none of the other keywords but ``d_out_beam_logp`` (float32
         [n,K,max_len]: also the hypotheses' token scores), ``beam_sets`` (host values) and ``d_out_beam_pos`` (float32 [n,K,max_len,5]: also
         the hypotheses' token positions), as for recognize_images.  ``automata`` (host values): a token automaton for every row, or
-        one per row; ``d_out_state`` (int32 [rows]): also the rows' final states."""
+        one per row; ``d_out_state`` (int32 [rows]): also the rows' final states.  ``beam_automata`` (host values, only with ``beam``): a
+        token automaton for every crop, or one per crop; ``d_out_beam_state`` (int32 [n,K]): also the hypotheses' states."""
         self._recognize("device", n, lambda: ((_ptr(d_gray), n), None), beam=beam, beam_scores=d_out_beam_logp, beam_sets=beam_sets, beam_positions=d_out_beam_pos, d_out=(d_out_ids, d_out_len, d_out_score), d_out_logp=d_out_logp,
                         d_out_alt_ids=d_out_alt_ids, d_out_alt_logp=d_out_alt_logp, token_sets=token_sets, no_repeat_ngram=no_repeat_ngram,
-                        d_out_pos=d_out_pos, prefixes=prefixes, sources=sources, automata=automata, d_out_state=d_out_state)
+                        d_out_pos=d_out_pos, prefixes=prefixes, sources=sources, automata=automata, d_out_state=d_out_state,
+                        beam_automata=beam_automata, beam_states=d_out_beam_state if d_out_beam_state is not None else False)
 
     def set_generate_max_length(self, max_len: int) -> None:
         self._check(self.lib.mocr_set_generate_max_length(self._h, int(max_len)))
 
     def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False, alternatives: bool = False,
                        token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
-                       beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False):
+                       beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False,
+                         beam_automata=None, beam_states: bool = False):
         """Luminance planes uint8 [n,224,224] (host), generate(max_length) ``max_len``; the keywords as for recognize_images
         (``sources``: one plane index per output row; ``beam``: (ids [n,K,max_len], lengths [n,K], scores [n,K]), with ``beam_scores`` also
         logp [n,K,max_len]; ``beam_sets``: one set per plane; ``beam_positions``: also pos [n,K,max_len,5], last)."""
@@ -576,7 +611,8 @@ class Engine:
         return self._recognize("gray_host", a.shape[0], lambda: ((_ptr(a), a.shape[0]), a), (max_len or self.spec.max_len,), beam=beam, beam_scores=beam_scores,
                                beam_sets=beam_sets, beam_positions=beam_positions, scores=scores,
                                alternatives=alternatives, token_sets=token_sets, no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes,
-                               sources=sources, automata=automata, states=states)
+                               sources=sources, automata=automata, states=states,
+                               beam_automata=beam_automata, beam_states=beam_states)
 
     # ------------------------------------------------------------------ test hooks
     def encode(self, d_gray, n: int) -> np.ndarray:
@@ -768,6 +804,20 @@ class Engine:
                                                            _ptr(d_parent), _ptr(d_hyp_ids), _ptr(d_hyp_len), _ptr(d_hyp_score),
                                                            _ptr(d_heuristic_open), _ptr(d_beam_logp), _ptr(d_hyp_logp), _ptr(d_tok_mask),
                                                            _ptr(d_set_of_row), _ptr(d_beam_trail), _ptr(d_hyp_trail)))
+
+    def op_beam_select_automaton(self, beam: BeamConfig, d_beam_score, d_parent, d_hyp_ids, d_hyp_len, d_hyp_score, d_heuristic_open,
+                                 d_beam_logp=None, d_hyp_logp=None, d_tok_mask=None, d_set_of_row=None, d_beam_trail=None,
+                                 d_hyp_trail=None, d_edge_begin=None, d_edge_token=None, d_edge_next=None, d_accepting=None,
+                                 d_aut_base_of_row=None, d_aut_state=None, d_hyp_state=None, **kw) -> None:
+        """The selection in its automaton form (include/mocr.h mocr_op_beam_select_automaton): op_beam_select_positions plus the
+        tables (global state numbers), the rows' start states (-1: none), the beams' states and the hypotheses' states, both
+        in / out; keywords: the fields of mocr_token_args."""
+        cfg = beam.as_struct()
+        self._check(self.lib.mocr_op_beam_select_automaton(
+            self._h, self._args(_capi.MocrTokenArgs, kw), C.byref(cfg), _ptr(d_beam_score), _ptr(d_parent), _ptr(d_hyp_ids),
+            _ptr(d_hyp_len), _ptr(d_hyp_score), _ptr(d_heuristic_open), _ptr(d_beam_logp), _ptr(d_hyp_logp), _ptr(d_tok_mask),
+            _ptr(d_set_of_row), _ptr(d_beam_trail), _ptr(d_hyp_trail), _ptr(d_edge_begin), _ptr(d_edge_token), _ptr(d_edge_next),
+            _ptr(d_accepting), _ptr(d_aut_base_of_row), _ptr(d_aut_state), _ptr(d_hyp_state)))
 
     def op_beam_permute(self, d_cache, layers: int, layer_stride: int, row_stride: int, segs: int, seg_stride: int, pos_bytes: int,
                         K: int, d_parent, d_rowmap, d_finished, d_step, n_slots: int, max_pos: int) -> None:

@@ -367,6 +367,8 @@ class _Request(NamedTuple):
     beam_set: int = 0                   # a beam request: the token set its beams search under, 0: unconstrained
     beam_positions: bool = False        # a beam request: wants its hypotheses' token positions
     automaton: int = 0                  # token automaton handle (``lexicon=``), 0: none; such a caller gets its final state, last
+    beam_automaton: int = 0             # a beam request (``match``): the automaton its beams walk, 0: none; such a caller gets its
+                                        # hypotheses' states [K], last
 
 
 class _Batcher:
@@ -387,7 +389,9 @@ class _Batcher:
     token set (``beam_set``): only a beam batch with such a request passes ``beam_scores=True`` / ``beam_sets=`` (one handle per
     crop, 0 for the others), and only a caller that asked gets logp [K, max_len] as a fourth element.  The same for the
     hypotheses' token positions (``beam_positions``): only a beam batch with such a request passes ``beam_positions=True``, and
-    only a caller that asked gets pos [K, max_len, 5] as its last element."""
+    only a caller that asked gets pos [K, max_len, 5] as its last element.  And for a beam request's token automaton
+    (``beam_automaton``, the ``match`` methods): only a beam batch with such a request passes ``beam_automata=`` (one handle per
+    crop, 0 for the others) and ``beam_states=True``, and only such a caller gets state [K], behind everything else."""
 
     def __init__(self, engine: Engine, max_batch: int, timeout_ms: float):
         self.engine, self.max_batch, self.timeout = engine, max_batch, timeout_ms / 1000.0
@@ -399,13 +403,15 @@ class _Batcher:
 
     def submit(self, gray: np.ndarray, scored: bool = False, alternatives: bool = False, token_set: int = 0,
                no_repeat_ngram: int = 0, positions: bool = False, prefix=None, beam: Optional[BeamConfig] = None,
-               beam_scores: bool = False, beam_set: int = 0, beam_positions: bool = False, automaton: int = 0) -> Future:
+               beam_scores: bool = False, beam_set: int = 0, beam_positions: bool = False, automaton: int = 0,
+               beam_automaton: int = 0) -> Future:
         f: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
             self._q.append(_Request(gray, f, bool(scored or alternatives), bool(alternatives), bool(positions), int(token_set), int(no_repeat_ngram),
-                                    tuple(prefix) if prefix else None, beam, bool(beam_scores), int(beam_set), bool(beam_positions), int(automaton)))
+                                    tuple(prefix) if prefix else None, beam, bool(beam_scores), int(beam_set), bool(beam_positions), int(automaton),
+                                    int(beam_automaton)))
             self._cv.notify()
         return f
 
@@ -437,12 +443,16 @@ class _Batcher:
                         bkw["beam_sets"] = [r.beam_set for r in batch]
                     if any(r.beam_positions for r in batch):
                         bkw["beam_positions"] = True
+                    if any(r.beam_automaton for r in batch):
+                        bkw["beam_automata"] = [r.beam_automaton for r in batch]
+                        bkw["beam_states"] = True
                     ids, lens, sc, *rest = self.engine.recognize_images([r.gray for r in batch], beam=head, **bkw)
                     logp = rest.pop(0) if bkw.get("beam_scores") else None
                     pos = rest.pop(0) if bkw.get("beam_positions") else None
+                    state = rest.pop(0) if bkw.get("beam_states") else None
                     for i, r in enumerate(batch):
                         r.future.set_result((ids[i].copy(), lens[i].copy(), sc[i].copy()) + ((logp[i].copy(),) if r.beam_scores else ()) +
-                                            ((pos[i].copy(),) if r.beam_positions else ()))
+                                            ((pos[i].copy(),) if r.beam_positions else ()) + ((state[i].copy(),) if r.beam_automaton else ()))
                     continue
                 kw = {}         # only what somebody asked for: a batch of plain requests makes the plain call
                 if any(r.scored for r in batch):        # the richest call any request asked for
@@ -1063,11 +1073,12 @@ class MangaOcr:
             raise ValueError("this MangaOcr decodes with beam search (num_beams=): allowed= / no_repeat_ngram= / prefix= do not combine with it")
         return True
 
-    def _beam(self, src, beam: BeamConfig, token_scores: bool = False, allowed=None, positions: bool = False):
+    def _beam(self, src, beam: BeamConfig, token_scores: bool = False, allowed=None, positions: bool = False, lexicons=None):
         """(ids [n, K, max_len], lengths [n, K], scores [n, K]) of a source: one crop through the batcher, any number of crops
         or regions max_batch // K of them per engine call (a beam request fits one batch: n * K <= max_batch).  With
         ``token_scores`` also logp [n, K, max_len]; ``allowed``: the crops' token sets; with ``positions`` also, last, pos
-        [n, K, max_len, 5].  The engine is passed only what was asked."""
+        [n, K, max_len, 5].  ``lexicons`` (the ``match`` methods): one Lexicon or None per crop - the beams walk the crops'
+        automata, and the hypotheses' states [n, K] come behind everything else.  The engine is passed only what was asked."""
         self._require("BEAM")
         if positions:
             self._require("BEAM_POSITIONS")
@@ -1079,13 +1090,20 @@ class MangaOcr:
             kw = dict(flags)
             if hs is not None:
                 kw["beam_set"] = hs[0]
-            return tuple(a[None] for a in self._batcher.submit(src.pixels, beam=beam, **kw).result())
+            if lexicons is not None and lexicons[0] is not None:
+                kw["beam_automaton"] = lexicons[0].handle
+            out = tuple(a[None] for a in self._batcher.submit(src.pixels, beam=beam, **kw).result())
+            if lexicons is not None and lexicons[0] is None:        # (no automaton: the batcher made the call it always made)
+                out += (np.full(out[1].shape, -1, dtype=np.int32),)
+            return out
         if not src.n and isinstance(src, _Images):
             src = _Images([])       # no crops: the bare call, which only shapes the empty result
         step = max(1, int(self.max_batch) // beam.num_beams)
-        kw = lambda a: dict(**flags, **(dict(beam_sets=hs[a:a + step]) if hs is not None else {}))
+        aut = None if lexicons is None else [0 if x is None else x.handle for x in lexicons]
+        kw = lambda a: dict(**flags, **(dict(beam_sets=hs[a:a + step]) if hs is not None else {}),
+                            **(dict(beam_automata=aut[a:a + step], beam_states=True) if aut is not None else {}))
         parts = [src.call(self, a, a + step, beam=beam, **kw(a)) for a in range(0, src.n, step)] or [src.call(self, beam=beam, **kw(0))]
-        return tuple(np.concatenate([p[i] for p in parts]) for i in range(3 + bool(token_scores) + bool(positions)))
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(3 + bool(token_scores) + bool(positions) + (aut is not None)))
 
     def _hypotheses(self, ids, lens, scores, logp=None, pos=None, rect=None) -> List[Recognition]:
         """one crop's [K, max_len] / [K] / [K] (/ [K, max_len] / [K, max_len, 5]) -> its finished hypotheses, best first (empty
@@ -1110,7 +1128,8 @@ class MangaOcr:
         """the ``*_beam`` methods: the configuration is checked, then the inputs; one list of hypotheses per crop or region.
         ``lexicon=`` is refused: beam search takes no token automaton (include/mocr.h, "token automata")"""
         if lexicon is not None:
-            raise ValueError("beam search does not combine with lexicon= (token automata are for greedy decoding)")
+            raise ValueError("the *_beam methods do not combine with lexicon= (token automata are for greedy decoding here): "
+                             "match() / match_batch() / match_bgr() / match_regions() search a lexicon with beams")
         beam = BeamConfig(*config)
         src = source()
         if positions and isinstance(src, _Regions):
@@ -1162,6 +1181,87 @@ class MangaOcr:
         ``page_boxes()`` works)."""
         return self._run_beam(lambda: _Regions(list(pages_bgr), list(regions)), num_beams, length_penalty, early_stopping, no_repeat_ngram,
                               token_scores=token_scores, allowed=allowed, positions=positions, lexicon=lexicon)
+
+    # ------------------------------------------------------------------ beam search under a lexicon
+    def _run_match(self, source, lexicon, k, length_penalty, early_stopping, no_repeat_ngram, token_scores, allowed, positions,
+                   raw) -> List[List[Recognition]]:
+        """the ``match*`` methods: the refusals (several devices), the configuration, the inputs, the lexicons; ONE beam search per
+        crop whose K beams walk the crop's automaton; per crop the hypotheses marked with ``state`` / ``accepted`` / ``entry``,
+        and unless ``raw`` only the distinct accepted ones that are no padding beam's duplicate"""
+        self._require("BEAM")
+        self._require("LEXICON")
+        if lexicon is None:
+            raise ValueError("match: lexicon= is required (a Lexicon of MangaOcr.lexicon() / automaton(), or one or None per crop)")
+        beam = BeamConfig(k, length_penalty, early_stopping, no_repeat_ngram)
+        src = source()
+        if positions and isinstance(src, _Regions):
+            src = src.with_rects()
+        lex = _lexicons(lexicon, src.n) or [None] * src.n
+        ids, lens, sc, *rest = self._beam(src, beam, bool(token_scores), allowed, bool(positions), lex)
+        logp = rest.pop(0) if token_scores else None
+        pos = rest.pop(0) if positions else None
+        state = rest.pop(0)
+        rects = src.rects if positions else None
+        eos = self.spec.eos_id
+        # a padding beam's descendant scores -1e9 / (tokens generated) ** length_penalty: at or below this, whatever its length
+        junk = -1.0e9 / float(self.spec.max_len) ** max(float(beam.length_penalty), 0.0)
+        out = []
+        for i, x in enumerate(lex):
+            live = [j for j in range(lens.shape[1]) if lens[i, j] > 0]
+            hyps = self._hypotheses(ids[i], lens[i], sc[i], None if logp is None else logp[i], None if pos is None else pos[i],
+                                    rects[i] if rects is not None else None)
+            marked = []
+            for j, h in zip(live, hyps):
+                st = int(state[i, j])
+                ok = x is not None and len(h.ids) > 1 and int(h.ids[-1]) == eos and st in x.accepting
+                marked.append(replace(h, state=st, accepted=bool(ok), entry=x.entries.get(st) if ok else None))
+            if not raw:
+                seen, kept = set(), []
+                for h in marked:
+                    key = h.entry if h.entry is not None else ("state", h.state, tuple(int(t) for t in h.ids))
+                    if h.accepted and h.sequence_score > junk and key not in seen:
+                        seen.add(key)
+                        kept.append(h)
+                marked = kept
+            out.append(marked)
+        return out
+
+    def match(self, img_or_path, lexicon, k: int = 4, *, length_penalty: float = 1.0, early_stopping=False, no_repeat_ngram: int = 0,
+              token_scores: bool = False, allowed=None, positions: bool = False, raw: bool = False) -> List[Recognition]:
+        """The entries of ``lexicon`` (:meth:`lexicon` / :meth:`automaton`) that fit one crop best: a beam search of ``k`` beams
+        (2 .. 4) whose every beam walks the automaton (include/mocr.h, "beam search under a token automaton") - transformers'
+        ``generate(num_beams=k, prefix_allowed_tokens_fn=...)``.  Where the greedy ``lexicon=`` commits to one branch of the trie at
+        the first character, this ranks whole entries.  Returns the distinct accepted entries in score order, at most ``k``: each
+        a :class:`Recognition` with ``text``, ``sequence_score``, ``state``, ``accepted=True`` and ``entry``.  A hypothesis is
+        dropped if it did not end by EOS in an accepting state, if it is a padding beam's duplicate (the lexicon has fewer
+        reachable entries than beams; such a hypothesis scores -1e9 / tokens ** length_penalty, so the line is drawn at
+        -1e9 / max_len ** length_penalty), or if it repeats an earlier one.  ``raw=True``: all hypotheses as
+        the engine delivered them, with ``state`` / ``accepted`` / ``entry`` filled.  ``length_penalty`` / ``early_stopping`` /
+        ``no_repeat_ngram`` / ``token_scores`` / ``allowed`` / ``positions``: as for :meth:`recognize_beam`.  Goes through the
+        batcher; only requests of one beam configuration share a batch."""
+        return self._run_match(self._one(img_or_path), lexicon, k, length_penalty, early_stopping, no_repeat_ngram, token_scores, allowed,
+                               positions, raw)[0]
+
+    def match_batch(self, images: Sequence, lexicon, k: int = 4, *, length_penalty: float = 1.0, early_stopping=False,
+                    no_repeat_ngram: int = 0, token_scores: bool = False, allowed=None, positions: bool = False,
+                    raw: bool = False) -> List[List[Recognition]]:
+        """:meth:`match` for many crops: one list per crop (``lexicon``: one for all, or one Lexicon or None per crop - a crop
+        without one is searched freely and, accepting nothing, keeps its hypotheses only with ``raw=True``)."""
+        return self._run_match(self._pil(images), lexicon, k, length_penalty, early_stopping, no_repeat_ngram, token_scores, allowed, positions, raw)
+
+    def match_bgr(self, crops_bgr: Sequence[np.ndarray], lexicon, orientations: Optional[Sequence[str]] = None, k: int = 4, *,
+                  length_penalty: float = 1.0, early_stopping=False, no_repeat_ngram: int = 0, token_scores: bool = False, allowed=None,
+                  positions: bool = False, raw: bool = False) -> List[List[Recognition]]:
+        """:meth:`match_batch` on BGR crops with their orientation settings, as ``recognize_bgr`` takes them."""
+        return self._run_match(lambda: self._bgr("match_bgr", crops_bgr, orientations), lexicon, k, length_penalty, early_stopping,
+                               no_repeat_ngram, token_scores, allowed, positions, raw)
+
+    def match_regions(self, pages_bgr: Sequence[np.ndarray], regions, lexicon, k: int = 4, *, length_penalty: float = 1.0,
+                      early_stopping=False, no_repeat_ngram: int = 0, token_scores: bool = False, allowed=None,
+                      positions: bool = False, raw: bool = False) -> List[List[Recognition]]:
+        """:meth:`match_batch` on regions of BGR pages, as ``recognize_regions`` takes them: [] for a sliver."""
+        return self._run_match(lambda: _Regions(list(pages_bgr), list(regions)), lexicon, k, length_penalty, early_stopping,
+                               no_repeat_ngram, token_scores, allowed, positions, raw)
 
     def recognize_page(self, page_bgr: np.ndarray, regions):
         """``_collect_manga_detections`` for one page: ``regions`` = the detector's (text, polygon) pairs."""

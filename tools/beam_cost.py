@@ -13,10 +13,15 @@
         selection and the deferred pass.  The lines of (i), (vi) and (vii) are also appended to --positions-out (by default
         profiles/beam_positions_cost.jsonl of this checkout): run it on this build and, with --tree, on a built checkout of
         the parent commit, whose plain beam batch (i) is the yardstick - that build has no (vi) / (vii),
+  (viii) the beam batch of (i) with every crop under a trie of 8,000 random words of 2 to 12 tokens and (ix) under the universal
+        automaton, the worst case - 6,143 edges to scan per beam and step (include/mocr.h "beam search under a token
+        automaton").  The lines of (i), (v), (viii) and (ix) are also appended to --automaton-out (by default
+        profiles/beam_automaton_cost.jsonl): on the parent commit's build, which has no (viii) / (ix), (i) and (v) are the
+        yardsticks - they launch what they launched and must lie within that build's own min .. max,
 and, with --profile, the two new kernels' times from the engine's per-kernel profile at 400 rows.
 
     python tools/beam_cost.py [--tree DIR] [--label NAME] [--crops 64] [--beams 4] [--max-len 32] [--reps 7] [--profile]
-                              [--positions-out profiles/beam_positions_cost.jsonl]
+                              [--positions-out profiles/beam_positions_cost.jsonl] [--automaton-out profiles/beam_automaton_cost.jsonl]
 
 --tree: the checkout whose package and library are measured (default: this one); a built checkout of the parent commit runs
 (ii) and (iii) alone - they are the yardsticks and must agree between the two builds within their own run-to-run spread.
@@ -40,6 +45,8 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--positions-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "beam_positions_cost.jsonl"),
                     help="append the plain beam line and the positions lines to this file ('' = nowhere)")
+    ap.add_argument("--automaton-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "beam_automaton_cost.jsonl"),
+                    help="append the plain beam line, the 40-token-set line and the automaton lines to this file ('' = nowhere)")
     args = ap.parse_args()
     tree = os.path.abspath(args.tree)
     for p in (tree, os.path.join(tree, "manga-ocr_amd")):
@@ -67,6 +74,23 @@ def main():
         if hasattr(eng, "beam_position_state_bytes"):   # (the parent commit has no positions for hypotheses)
             forms.append(("beam_positions", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg, beam_positions=True)))
             forms.append(("beam_token_scores_positions", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg, beam_scores=True, beam_positions=True)))
+        if hasattr(eng, "op_beam_select_automaton"):    # (the parent commit has no beam search under automata)
+            rs = np.random.RandomState(8000)
+            trans, accepting, n_states = {0: {}}, set(), 1
+            for _ in range(8000):       # a trie of 8,000 random words over 400 tokens: wide at the root, deep below
+                s = 0
+                for t in rs.randint(5, 405, size=rs.randint(2, 13)):
+                    t = int(t) + (1 if int(t) >= DEFAULT_SPEC.eos_id else 0)
+                    if t not in trans.setdefault(s, {}):
+                        trans[s][t] = n_states
+                        n_states += 1
+                    s = trans[s][t]
+                accepting.add(s)
+            from manga_ocr.text import pack_automaton
+            trie = eng.automaton(*pack_automaton(trans, accepting))
+            uni = eng.automaton(*pack_automaton({0: {t: 0 for t in range(DEFAULT_SPEC.vocab) if t != DEFAULT_SPEC.eos_id}}, [0]))
+            forms.append(("beam_automaton_trie8000", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg, beam_automata=trie, beam_states=True)))
+            forms.append(("beam_automaton_universal", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg, beam_automata=uni, beam_states=True)))
     for form, call in forms:
         for _ in range(2):
             call()
@@ -81,6 +105,10 @@ def main():
         if args.positions_out and form in ("beam", "beam_positions", "beam_token_scores_positions"):
             os.makedirs(os.path.dirname(os.path.abspath(args.positions_out)), exist_ok=True)
             with open(args.positions_out, "a", encoding="utf-8") as f:
+                f.write(line + "\n")
+        if args.automaton_out and form in ("beam", "beam_token_scores_set40", "beam_automaton_trie8000", "beam_automaton_universal"):
+            os.makedirs(os.path.dirname(os.path.abspath(args.automaton_out)), exist_ok=True)
+            with open(args.automaton_out, "a", encoding="utf-8") as f:
                 f.write(line + "\n")
     eng.close()
     if args.profile and beam is not None:
