@@ -415,10 +415,42 @@ int64_t mocr_encoded_crops(mocr_engine* e);
  *     (about 37 MiB; capacity is bounded by edges, not by states x 768 B, so a dictionary-sized trie fits); the rows' states
  *     (12 B a row and lane) are allocated by the first batch that brings an automaton.
  *   Beam search: the *_beam, *_beam_tokens and *_beam_positions entry points take no automaton; the *_beam_automaton twins do,
- *     under the rule of the section "beam search under a token automaton" below. */
+ *     under the rule of the section "beam search under a token automaton" below.
+ *
+ * ---- soft token automata (glossary boosts; transformers' generate(sequence_bias=...)) ----
+ *   mocr_automaton_desc has two nullable trailing fields, guarded by struct_size: a caller that passes the struct without them,
+ *   or nulls, gets the automaton described above.  An automaton that brings either array is SOFT.
+ *     edge_weight float32 [n_edges]: finite (NaN or +-inf: MOCR_ERR_ARG); null = all 0.
+ *     default_next int32 [n_states]: each in [0, n_states) or -1; null = all -1.
+ *   A state s with default_next[s] >= 0 is OPEN: A(s) = every non-EOS token, plus EOS iff s accepts, and a stored non-EOS token
+ *     without an edge moves the row to default_next[s].  A state with -1 is closed, as above: A(s) = its edge tokens, no edge
+ *     = MOCR_STATE_DEAD.  One automaton may mix open and closed states.  EOS is still never an edge token.
+ *   A default_next value may carry the bit MOCR_DEFAULT_FALLBACK (d | MOCR_DEFAULT_FALLBACK, d in [0, n_states)): then a
+ *     token without an edge in s is walked from d - the row moves to the target of d's edge on that token if d has one, and to
+ *     d otherwise (one level: d's own default is not followed).  Nothing else changes: s is open, and only s's own edges weigh.
+ *     It is what keeps an Aho-Corasick automaton smaller: a state need not repeat the root's zero-weight edges.  It still keeps
+ *     every WEIGHTED edge it inherits along its fail chain, because the LM head reads a state's own edges only: 8,000 random
+ *     names over 200 tokens take 23,329 states and 866,750 edges (about 37 a state, 21 % of MOCR_MAX_AUTOMATON_EDGES) instead
+ *     of 4,665,800.
+ *   At the step that chooses ids[L] in state s, the logit of token t is logit(t) + edge_weight(s, t) where s has an edge on t,
+ *     and the plain logit otherwise; the add is in fp32.  Everything the step derives is computed from these logits, exactly as
+ *     masked columns count as -inf: the arg-max over the effective set (equal values: the lowest id), the token scores and the
+ *     four alternatives, renormalised over that set, and the value a forced prefix token scores.  The effective set is A(s) AND
+ *     the token set, minus the n-gram bans; the dead-end rule stays; forced prefix tokens walk default edges like emitted ones.
+ *   Bit identity, as far as the caller can observe: a soft row under one accepting open state with default_next = 0 and no
+ *     edges equals a MOCR_AUTOMATON_NONE row; a hard automaton created with an all-zero edge_weight equals the same automaton
+ *     created without one; rows of a soft batch under a hard automaton or under none keep their results; a batch in which no
+ *     row brings a soft automaton launches exactly what it launched before.
+ *   How: the fused LM head's SOFT form (profile name gemm_dec_vocab_sw) adds a row's state's edge weights to the fp32 tile in
+ *     LDS before it reduces it; on the slab paths the token kernel's SOFT form (dec_token*_sw) adds them to the summed logits.
+ *     The arena grows by edge_weight (2^22 floats) and default_next (2^20 ints), 20 MiB, allocated at full capacity by the first
+ *     create of a soft automaton and pre-filled with 0 / -1 for every automaton that exists or comes later.
+ *   Out of scope: beam search - the *_beam_automaton entry points refuse a soft handle with MOCR_ERR_ARG before any work -,
+ *     weights on EOS, non-finite weights (a ban is a token set). */
 #define MOCR_MAX_AUTOMATA          256
 #define MOCR_MAX_AUTOMATON_STATES  (1 << 20)    /* over all automata of an engine */
 #define MOCR_MAX_AUTOMATON_EDGES   (1 << 22)
+#define MOCR_DEFAULT_FALLBACK      (1 << 30)    /* a bit of a default_next value: walk the token from the default state */
 #define MOCR_AUTOMATON_NONE        0
 enum { MOCR_STATE_NONE = -1, MOCR_STATE_DEAD = -2 };
 typedef struct mocr_automaton_desc {
@@ -428,14 +460,17 @@ typedef struct mocr_automaton_desc {
     const int32_t* edge_token;      /* [edge_begin[n_states]] */
     const int32_t* edge_next;       /* [edge_begin[n_states]], each in [0, n_states) */
     const uint8_t* accepting;       /* [n_states] */
+    const float* edge_weight;       /* nullable: [edge_begin[n_states]], finite (soft token automata) */
+    const int32_t* default_next;    /* nullable: [n_states], each in [0, n_states) (| MOCR_DEFAULT_FALLBACK) or -1 */
 } mocr_automaton_desc;
 /* A new automaton; *out_handle >= 1.  Automata are immutable and live until mocr_destroy; the arrays are copied before the
  * call returns.  Thread-safe.  MOCR_ERR_ARG: a null or short struct, n_states < 1; edge_begin[0] != 0 or edge_begin not
  * monotone; a token outside [0, vocab) or equal to EOS; tokens of a state not strictly ascending; edge_next outside
- * [0, n_states); a table or the handle list full.  MOCR_ERR_STATE before mocr_commit_weights. */
+ * [0, n_states); a non-finite edge_weight; default_next outside [0, n_states) and not -1; a table or the handle list full.
+ * MOCR_ERR_STATE before mocr_commit_weights. */
 int mocr_automaton_create(mocr_engine* e, const mocr_automaton_desc* desc, int32_t* out_handle);
 int mocr_automaton_count(mocr_engine* e);
-/* Device bytes the automata hold: the arena plus the lanes' row states (and, 4 B a row more, the hypothesis states of a lane
+/* Device bytes the automata hold: the arena (its soft part from the first soft create on) plus the lanes' row states (and, 4 B a row more, the hypothesis states of a lane
  * that has run a beam batch under an automaton); 0 until the first create / first automaton batch. */
 int64_t mocr_automaton_state_bytes(mocr_engine* e);
 /* The *_automaton entry points: the *_shared twins plus `automata`, a HOST int32 array [n_rows] of handles (null: every row
@@ -764,6 +799,24 @@ int mocr_op_dec_token_automaton(mocr_engine* e, const mocr_token_args* a, const 
                                 const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld, const float* d_tgt_val,
                                 const int32_t* d_edge_begin, const int32_t* d_edge_token, const int32_t* d_edge_next,
                                 const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state);
+/* The token step with soft token automata: mocr_op_dec_token_automaton plus d_edge_weight float32 [edges] and d_default_next
+ * int32 [states] (global numbers, with MOCR_DEFAULT_FALLBACK where set; -1: closed), both or neither.  Slab path: the weights of the row's state's edges are added to
+ * the summed logits before masking; walk: no edge -> d_default_next[state], DEAD only where that is -1; rebuild: an open state
+ * starts from every token, EOS by d_accepting.  Both NULL is mocr_op_dec_token_automaton. */
+int mocr_op_dec_token_soft(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                           const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
+                           const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
+                           const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row,
+                           const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld, const float* d_tgt_val,
+                           const int32_t* d_edge_begin, const int32_t* d_edge_token, const int32_t* d_edge_next,
+                           const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state,
+                           const float* d_edge_weight, const int32_t* d_default_next);
+/* The start of a batch with soft token automata: mocr_op_automaton_init, where a start state with d_default_next >= 0 is open.
+ * d_default_next NULL is mocr_op_automaton_init. */
+int mocr_op_automaton_init_soft(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
+                                const int32_t* d_ngram_of_row, int32_t rows, const int32_t* d_edge_begin, const int32_t* d_edge_token,
+                                const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state,
+                                const int32_t* d_default_next);
 /* The start of a batch with token automata: for rows [0, rows), a row with d_aut_base_of_row[row] >= 0 gets
  * d_row_mask[row] = A(start) AND its base set, minus the start token where d_ngram_of_row[row] == 1, {EOS} if that is empty,
  * and d_aut_state[row] = its start state; any other row gets what mocr_op_ngram_init gives it and MOCR_STATE_NONE. */
@@ -821,6 +874,22 @@ int mocr_op_gemm_argmax_target(mocr_engine* e, const void* dA, const void* dW, c
                                int32_t K, int32_t tile, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
                                const int32_t* d_rowmap, const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld,
                                const int32_t* d_step, float* d_tgt_val);
+/* The LM head with edge weights (soft token automata): mocr_op_gemm_argmax_target plus `soft` - d_aut_state int32 [rows] by ROW
+ * (the global state every row is in; < 0: none / dead) and the tables d_edge_begin [states + 1], d_edge_token [edges] (a state's
+ * tokens strictly ascending), d_edge_weight float32 [edges].  GEMM row m in state s = d_aut_state[d_rowmap[m]] >= 0 has the
+ * weight of every edge of s added to its column before the tile is reduced; needs d_tok_mask.  soft = NULL is that call. */
+typedef struct mocr_soft_tables {
+    int32_t struct_size;        /* sizeof(mocr_soft_tables) */
+    const int32_t* d_aut_state;
+    const int32_t* d_edge_begin;
+    const int32_t* d_edge_token;
+    const float* d_edge_weight;
+} mocr_soft_tables;
+int mocr_op_gemm_argmax_soft(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                             int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N,
+                             int32_t K, int32_t tile, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
+                             const int32_t* d_rowmap, const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld,
+                             const int32_t* d_step, float* d_tgt_val, const mocr_soft_tables* soft);
 /* bf16 engines: the small-batch projection (rows <= 32; kernels_smallm.h SmallMParams), one of the (pro, epi) pairs the
  * small-batch decode step launches: (0,0) (1,0) (0,1) (1,2) (1,3). */
 typedef struct mocr_smallm_args {

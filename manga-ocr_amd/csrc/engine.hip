@@ -228,6 +228,9 @@ struct DecMode {
                                     // and the token kernel is the NGRAM one, which rebuilds them
     bool automaton = false;         // a row brings a token automaton (implies `ngram`: the same per-row masks): the token kernel is the
                                     // AUTOMATON one, which also walks the rows' states, and the batch starts with automaton_init_kernel
+    bool soft = false;              // ... and one of those automata is SOFT (edge weights / open states; implies `automaton`): the LM head is the
+                                    // SOFT form of the masked epilogue, the token kernel the SOFT one, the batch starts with
+                                    // automaton_init_soft_kernel
     bool positions = false;        // a job asked for token positions: the steps record pos_hist, finish_batch runs the deferred pass
                                     // (a beam batch too: its selection then also keeps the beam-index trails the pass gathers by)
     bool prefix = false;            // a row has a forced prefix: the steps run scored and masked (level >= 1, mask; unconstrained rows read
@@ -240,25 +243,26 @@ struct DecMode {
     bool beam_automaton = false;    // ... in which a job brings a token automaton other than MOCR_AUTOMATON_NONE (implies beam_tokens): the
                                     // selection runs in its automaton form and the batch starts with beam_automaton_init_kernel
     // a graph captured in one mode is never replayed in another: the mode's share of the decode-graph key (6 bits; a beam
-    // batch: bit 6, its token form: bit 7, an automaton batch: bit 8, a beam batch's automaton form: bit 9, and a beam
-    // batch's configuration - kernel arguments of the captured launches - in the bits above, beam_key)
+    // batch: bit 6, its token form: bit 7, an automaton batch: bit 8, a beam batch's automaton form: bit 9, a soft automaton
+    // batch: bit 10, and a beam batch's configuration - kernel arguments of the captured launches - in the bits above, beam_key)
     int key_bits() const {
         return level + (mask ? 4 : 0) + (ngram ? 8 : 0) + (positions ? 16 : 0) + (prefix ? 32 : 0) + (beam ? 64 : 0) + (beam_tokens ? 128 : 0) +
-               (automaton ? 256 : 0) + (beam_automaton ? 512 : 0);
+               (automaton ? 256 : 0) + (beam_automaton ? 512 : 0) + (soft ? 1024 : 0);
     }
-    static constexpr int KEY_SPAN = 1024;
+    static constexpr int KEY_SPAN = 2048;
     int epilogue() const { return mask ? (level == 2 ? EPI_TOPK_M : level == 1 ? EPI_ARGMAX_LSE_M : EPI_ARGMAX_M)
                                        : (level == 2 ? EPI_TOPK : level == 1 ? EPI_ARGMAX_LSE : EPI_ARGMAX); }
     // profile names of the fused LM head and of the token kernel
     const char* head_name() const {
-        return mask ? "gemm_dec_vocab_m" : level == 2 ? "gemm_dec_vocab_topk" : level == 1 ? "gemm_dec_vocab_lse" : "gemm_dec_vocab";
+        return soft ? "gemm_dec_vocab_sw" : mask ? "gemm_dec_vocab_m" : level == 2 ? "gemm_dec_vocab_topk" : level == 1 ? "gemm_dec_vocab_lse" : "gemm_dec_vocab";
     }
     const char* token_name() const {
         static const char* const names[3][3] = {{"dec_token", "dec_token_m", "dec_token_ng"},
                                                 {"dec_token_lse", "dec_token_lse_m", "dec_token_lse_ng"},
                                                 {"dec_token_topk", "dec_token_topk_m", "dec_token_topk_ng"}};
         static const char* const automaton_names[3] = {"dec_token_am", "dec_token_lse_am", "dec_token_topk_am"};
-        return automaton ? automaton_names[level] : names[level][ngram ? 2 : mask ? 1 : 0];
+        static const char* const soft_names[3] = {"dec_token_sw", "dec_token_lse_sw", "dec_token_topk_sw"};
+        return soft ? soft_names[level] : automaton ? automaton_names[level] : names[level][ngram ? 2 : mask ? 1 : 0];
     }
 };
 
@@ -343,6 +347,7 @@ struct mocr_engine : LaneCtx {
     int smallm_rows = 0;            // bf16: batches of up to this many rows take the one-launch-per-projection path (kernels_smallm.h)
     bool beam_batch = false;        // the batch being scheduled is a beam batch (set with `regime`): no one-launch-per-projection path
     bool automaton_batch = false;   // the batch being advanced brings token automata (set with `regime`): the token kernel gets the tables
+    bool soft_batch = false;        // ... and one of them is soft: the token kernel and the LM head get the weights and the default edges too
     bool use_smallm(int n) const { return n <= smallm_rows && !use_latent(n) && !beam_batch; }
     std::vector<mocr_beam_config> beam_cfgs;    // the beam configurations seen: a decode graph bakes one in, its key names it by index
     std::map<std::string, std::vector<float>> host_w;
@@ -366,6 +371,11 @@ struct mocr_engine : LaneCtx {
     // (handle 0 = MOCR_AUTOMATON_NONE holds nothing)
     int *aut_edge_begin = nullptr, *aut_edge_token = nullptr, *aut_edge_next = nullptr;
     uint8_t* aut_accepting = nullptr;
+    // ... and its soft part, allocated at full capacity by the first create of a SOFT automaton and
+    // pre-filled with weight 0 / default -1, which is what every automaton created without the two arrays reads there
+    float* aut_edge_weight = nullptr;
+    int* aut_default_next = nullptr;
+    std::vector<char> aut_soft{0};      // by handle: the automaton brought edge_weight or default_next
     std::vector<int> aut_first{0}, aut_states{0};
     int aut_n_states = 0, aut_n_edges = 0;
     // decode-step HIP graphs, keyed by (lane, rows, (max_len, context bucket, DecMode::key_bits), steps per graph)
@@ -530,6 +540,29 @@ template <typename T> struct TileFamily {
     static constexpr int lds(const Args& a) { return a.ring * (a.bm + a.bm) * 128; }
 };
 
+// ... and the SOFT forms of the three masked epilogues (soft token automata: the rows' edge weights go into the tile), on
+// GemmParamsSoft; a family of its own, so that TileFamily's table and its kernels' argument type stay what they were
+constexpr std::array<TileArgs, 20> soft_tile_forms() {
+    std::array<TileArgs, 20> a{};
+    int n = 0;
+    for (int epi : {EPI_ARGMAX_M, EPI_ARGMAX_LSE_M, EPI_TOPK_M})
+        for (int bm : {64, 128})
+            for (int ring : {2, 4})
+                for (bool tgt : {false, true})
+                    if (!tgt || epi != EPI_ARGMAX_M) a[n++] = TileArgs{epi, bm, ring, tgt};
+    return a;
+}
+template <typename T> struct SoftTileFamily {
+    using Args = TileArgs;
+    using Kernel = void (*)(GemmParamsSoft);
+    static constexpr std::array<Args, 20> forms = soft_tile_forms();
+    static_assert(forms[19].bm == 128 && forms[19].tgt, "soft_tile_forms fills its table");
+    template <size_t I> static constexpr Kernel kernel() { constexpr Args a = forms[I]; return gemm_kernel<T, a.bm, a.bm, a.epi, a.ring, a.tgt, true>; }
+    static constexpr int lds(const Args& a) { return a.ring * (a.bm + a.bm) * 128; }
+};
+// Soft token automata (the SOFT forms): the rows' states and the arena's edge tables (kernels_gemm.h GemmParamsSoft)
+struct TokSoft { const int* state = nullptr; const int* edge_begin = nullptr; const int* edge_token = nullptr; const float* edge_weight = nullptr; };
+
 // The grid and the ring depth of one gemm_kernel launch: M x N outputs on bm x bm tiles, `split` K slices of `ktiles` K-tiles
 // each, `ybatch` GEMMs (heads).  launch_gemm_tile launches what this says and decode_plan reports it (mocr_decode_plan: "ring
 // slots"), so the rule below is stated once.
@@ -563,14 +596,23 @@ static TileLaunch tile_launch(const mocr_engine* e, int M, int N, int bm, int sp
 }
 
 template <typename T>
-void launch_gemm_tile(mocr_engine* e, const GemmParams& p0, int epi, int bm, int split, int ybatch) {
+void launch_gemm_tile(mocr_engine* e, const GemmParams& p0, int epi, int bm, int split, int ybatch, const TokSoft* soft = nullptr) {
     GemmParams p = p0;
     const TileLaunch t = tile_launch(e, p.M, p.N, bm, split, ybatch, p.k_per_split / (128 / (int)sizeof(T)));
     p.ntn = t.ntn; p.ntm = t.ntm;
     dim3 grid(p.ntm * p.ntn, ybatch, split);
+    if (soft) {
+        const auto f = find_form<SoftTileFamily<T>>({epi, bm, t.ring, p.tgt_val != nullptr});
+        if (!f.kernel) throw ArgError{"edge weights go into the masked LM-head epilogues", MOCR_ERR_ARG};
+        GemmParamsSoft ps{};
+        static_cast<GemmParams&>(ps) = p;
+        ps.aut_state = soft->state; ps.edge_begin = soft->edge_begin; ps.edge_token = soft->edge_token; ps.edge_weight = soft->edge_weight;
+        hipLaunchKernelGGL(f.kernel, grid, dim3(256), f.lds, e->stream, ps);
+    } else {
     const auto f = find_form<TileFamily<T>>({epi, bm, t.ring, p.tgt_val != nullptr});
     if (!f.kernel) throw ArgError{"unknown GEMM epilogue", MOCR_ERR_ARG};
     hipLaunchKernelGGL(f.kernel, grid, dim3(256), f.lds, e->stream, p);
+    }
     HIPCHECK(hipGetLastError());
     g_last_tile = {bm, t.ring, (int)std::min<long long>(t.blocks, INT32_MAX), split};
 }
@@ -765,7 +807,7 @@ struct TokMask { const unsigned* table = nullptr; const int* set_of_row = nullpt
 // EPI_TOPK*), the exp sums (the _LSE and TOPK forms), the four best (TOPK) - and the mask the EPI_*_M forms apply
 // Forced prefixes (EPI_ARGMAX_LSE_M / EPI_TOPK_M): the rows' prefixes, the slots' steps and where the target column's value goes
 struct TokTarget { const int* prefix = nullptr; const int* prefix_len = nullptr; int prefix_ld = 0; const int* step = nullptr; float* tgt_val = nullptr; };
-struct LmHead { int* cand_idx = nullptr; float* cand_sum = nullptr; float* top_val = nullptr; int* top_idx = nullptr; TokMask mask; TokTarget target; };
+struct LmHead { int* cand_idx = nullptr; float* cand_sum = nullptr; float* top_val = nullptr; int* top_idx = nullptr; TokMask mask; TokTarget target; TokSoft soft; };
 
 // One GEMM: A [M,K] (lda), W [N,K] (ldw = K), out (ldo).  tile: a tile code (TILE_CODES).  gemm_call states the operands and the
 // shape; a call site then names every extra it sets.  split > 1 only with EPI_SLAB.
@@ -843,6 +885,9 @@ void gemm(mocr_engine* e, const GemmCall& c) {
             p.prefix = tt.prefix; p.prefix_len = tt.prefix_len; p.prefix_ld = tt.prefix_ld; p.step = tt.step; p.tgt_val = tt.tgt_val;
         }
     }
+    const TokSoft* const soft = lm && lm->soft.state ? &lm->soft : nullptr;
+    if (soft && (!tm.table || !soft->edge_begin || !soft->edge_token || !soft->edge_weight || !tile_is(tile, GemmKind::Tile)))
+        throw ArgError{std::string("edge weights come with a masked LM-head epilogue on a 64 / 128 tile and all four arrays: ") + c.name, MOCR_ERR_ARG};
     p.M = M; p.N = N; p.lda = c.lda; p.ldw = K; p.ldo = c.ldo;
     int ybatch = 1;
     if (const HeadBatch* hb = c.hb) {
@@ -870,7 +915,7 @@ void gemm(mocr_engine* e, const GemmCall& c) {
     ProfScope ps(e, c.name, 2.0 * M * N * K * ybatch, bytes * ybatch);
     if (!tc) throw ArgError{"gemm tile must be 64, 128 or 4096", MOCR_ERR_ARG};
     switch (tc->kind) {
-        case GemmKind::Tile: launch_gemm_tile<T>(e, p, epi, tc->arg, split, ybatch); break;
+        case GemmKind::Tile: launch_gemm_tile<T>(e, p, epi, tc->arg, split, ybatch, soft); break;
         case GemmKind::Persistent: {
             static const int strip_env = env_int("MOCR_GEMM_STRIP", -1);     // -1: strips where they walk fewer rounds (r03, M = 50,432: O-proj 133 -> 113 us, FC2 303 -> 275)
             // the bf16-epilogue GEMMs: 1 = the one-barrier-per-two-K-tiles loop with the 64-deep LDS image (K64), 0 = one barrier per
@@ -1326,7 +1371,8 @@ struct DecTokenArgs {
     const float* top_val; const int* top_idx;             // alternatives steps (st.alt_ids set) on the candidate path: the tiles' four best
     float* x_f32; void* x_t;
     void* cache; uint8_t* cache8; float inv8; long long cstride;   // layer-0 latent cache row (T or e4m3), indexed by row
-    DecAutomata aut;                                      // token automata (all set: the AUTOMATON form; the state then has the per-row masks)
+    DecSoftAutomata aut;                                  // token automata (the six set: the AUTOMATON form; the state then has the per-row masks;
+                                                          // edge_weight and default_next set too: the SOFT form)
 };
 
 // The operator hooks come with a bare DecState, so the kernel's form is read off the state: scores / alternatives /
@@ -1336,7 +1382,7 @@ void launch_dec_token(mocr_engine* e, const DecState& st, const DecTokenArgs& a,
     auto& w = e->w;
     DecMode m;
     m.level = st.alt_ids ? 2 : st.scores ? 1 : 0; m.mask = st.tok_mask != nullptr; m.ngram = st.row_mask != nullptr;
-    m.automaton = a.aut.state != nullptr;
+    m.automaton = a.aut.state != nullptr; m.soft = a.aut.edge_weight != nullptr;
     const bool cand = a.ncand > 0;
     ProfScope ps(e, FIRST ? "dec_token_first" : m.token_name(), 0, FIRST ? 0.0 : (double)n * e->V * 4 * a.nslab);
     auto launch = [&](auto kernel) {
@@ -1348,6 +1394,11 @@ void launch_dec_token(mocr_engine* e, const DecState& st, const DecTokenArgs& a,
     };
     // <T, 768, FIRST, SCORES, TOPK, MASK, NGRAM>: the start token's kernel, and level x (plain, MASK, NGRAM) for the steps
     if constexpr (FIRST) launch(dec_token_kernel<T, 768, true>);      // (the start step has nothing to score or to mask)
+    else if (m.soft) switch (m.level) {           // the SOFT form of every level
+        case 0: launch(dec_token_kernel<T, 768, false, false, false, true, true, true, true>); break;
+        case 1: launch(dec_token_kernel<T, 768, false, true, false, true, true, true, true>); break;
+        default: launch(dec_token_kernel<T, 768, false, true, true, true, true, true, true>); break;
+    }
     else if (m.automaton) switch (m.level) {      // ... and the AUTOMATON form of every level
         case 0: launch(dec_token_kernel<T, 768, false, false, false, true, true, true>); break;
         case 1: launch(dec_token_kernel<T, 768, false, true, false, true, true, true>); break;
@@ -1379,8 +1430,10 @@ void dec_token(mocr_engine* e, const DecState& st, int nslab, int n, int ncand =
     a.cache8 = (lat && e->fp8attn) ? e->x8cache : nullptr;
     a.inv8 = (lat && e->fp8attn) ? 1.0f / e->w.sx_self[0] : 0.f;
     a.cstride = (long long)e->cfg.max_len * e->D;
-    if (!FIRST && e->automaton_batch)
-        a.aut = DecAutomata{e->aut_edge_begin, e->aut_edge_token, e->aut_edge_next, e->aut_accepting, e->aut_base_of_row, e->aut_state};
+    if (!FIRST && e->automaton_batch) {
+        static_cast<DecAutomata&>(a.aut) = DecAutomata{e->aut_edge_begin, e->aut_edge_token, e->aut_edge_next, e->aut_accepting, e->aut_base_of_row, e->aut_state};
+        if (e->soft_batch) { a.aut.edge_weight = e->aut_edge_weight; a.aut.default_next = e->aut_default_next; }
+    }
     launch_dec_token<T, FIRST>(e, st, a, n);
 }
 
@@ -1972,6 +2025,7 @@ void decode_step(mocr_engine* e, const DecState& st, const DecMode& m, int n, in
         if (m.level >= 2) { lm.top_val = e->top_val; lm.top_idx = e->top_idx; }
         if (m.mask) lm.mask = TokMask{st.tok_mask, st.set_of_row, st.rowmap};
         if (m.prefix) lm.target = TokTarget{st.prefix, st.prefix_len, st.prefix_ld, st.step, e->tgt_val};
+        if (m.soft) lm.soft = TokSoft{e->aut_state, e->aut_edge_begin, e->aut_edge_token, e->aut_edge_weight};
         GemmCall head = gemm_call(m.head_name(), e->z_t, D, w.wv, w.bv, e->cand_val, e->V, n, e->V, D, m.epilogue(), vt);
         head.lm = &lm;
         gemm<T>(e, head);
@@ -2004,7 +2058,7 @@ void quantize_enc(mocr_engine* e, int n) {
 // Raise the dynamic-LDS limit of every form of every kernel family (done once, at creation: outside any capture, from the
 // calling thread - decode steps are launched inside stream capture and from several lane threads).
 template <typename T> void init_kernel_attrs() {
-    raise_lds<TileFamily<T>, PersFamily, QqtFamily, SmallMFamily, LatentFamily, LatentTFamily, Latent8Family, LatentT8Family>();
+    raise_lds<TileFamily<T>, SoftTileFamily<T>, PersFamily, QqtFamily, SmallMFamily, LatentFamily, LatentTFamily, Latent8Family, LatentT8Family>();
     for_each_enc_attn<T>([](auto kernel, int lds) { set_max_lds(kernel, lds); });
 #ifdef MOCR_EXPERIMENTS
     raise_lds<Gemm256Family, WideFamily, Wide2Family>();
@@ -2219,6 +2273,19 @@ static void ensure_automaton_arena(mocr_engine* e) {
     e->aut_accepting = e->dalloc<uint8_t>((size_t)MOCR_MAX_AUTOMATON_STATES);
 }
 
+// The arena's soft part: edge_weight [2^22] and default_next [2^20], 20 MiB, allocated at full capacity by the
+// first create of a soft automaton and filled with 0 / -1 - what every automaton that exists or comes later without the two
+// arrays reads there.  Nothing has been launched on them yet, so the fill races with nothing.
+constexpr size_t AUT_SOFT_ARENA_BYTES = (size_t)MOCR_MAX_AUTOMATON_EDGES * sizeof(float) + (size_t)MOCR_MAX_AUTOMATON_STATES * sizeof(int);
+static void ensure_soft_arena(mocr_engine* e) {
+    if (e->aut_edge_weight) return;
+    float* w = e->dalloc<float>((size_t)MOCR_MAX_AUTOMATON_EDGES);
+    int* d = e->dalloc<int>((size_t)MOCR_MAX_AUTOMATON_STATES);
+    HIPCHECK(hipMemset(w, 0, (size_t)MOCR_MAX_AUTOMATON_EDGES * sizeof(float)));
+    HIPCHECK(hipMemset(d, 0xFF, (size_t)MOCR_MAX_AUTOMATON_STATES * sizeof(int)));
+    e->aut_edge_weight = w; e->aut_default_next = d;
+}
+
 // The rows' start states and current states, for the bound lane: allocated by the first batch in which a row brings an
 // automaton, like the alternatives buffers (12 B a row).
 static void ensure_automaton_buffers(mocr_engine* e) {
@@ -2231,8 +2298,14 @@ static void ensure_automaton_buffers(mocr_engine* e) {
 
 static void launch_automaton_init(mocr_engine* e, unsigned* row_mask, const unsigned* base_mask, const int* base_set_of_row,
                                   const int* ngram_of_row, int rows, const int* edge_begin, const int* edge_token,
-                                  const uint8_t* accepting, const int* aut_base_of_row, int* aut_state) {
-    ProfScope ps(e, "automaton_init", 0, (double)rows * (e->V / 32) * 8);
+                                  const uint8_t* accepting, const int* aut_base_of_row, int* aut_state,
+                                  const int* default_next = nullptr) {
+    ProfScope ps(e, default_next ? "automaton_init_sw" : "automaton_init", 0, (double)rows * (e->V / 32) * 8);
+    if (default_next)       // soft token automata: the start state may be open
+        hipLaunchKernelGGL(automaton_init_soft_kernel, dim3(rows), dim3(192), 0, e->stream, row_mask, base_mask, base_set_of_row, ngram_of_row,
+                           rows, e->V / 32, e->cfg.start_id, e->cfg.eos_id, edge_begin, edge_token, accepting, aut_base_of_row, aut_state,
+                           default_next);
+    else
     hipLaunchKernelGGL(automaton_init_kernel, dim3(rows), dim3(192), 0, e->stream, row_mask, base_mask, base_set_of_row, ngram_of_row, rows,
                        e->V / 32, e->cfg.start_id, e->cfg.eos_id, edge_begin, edge_token, accepting, aut_base_of_row, aut_state);
     HIPCHECK(hipGetLastError());
@@ -2431,7 +2504,11 @@ void start_batch(mocr_engine* e, Lane& L) {
     HIPCHECK(hipMemsetAsync(e->ids, 0, (size_t)L.np * e->cfg.max_len * sizeof(int), e->stream));
     // The batch runs in the richest mode any of its jobs asked for.  Scores: the start token and the pad tail score 0;
     // alternatives: positions the steps do not write read -1 / 0
-    const DecMode& m = L.mode = mode_of(L.jobs);
+    L.mode = mode_of(L.jobs);
+    if (L.mode.automaton)       // soft token automata: the batch takes the mode if any row's automaton is soft
+        for (const Job& j : L.jobs)
+            for (int32_t h : j.automata) L.mode.soft = L.mode.soft || e->aut_soft[h] != 0;
+    const DecMode& m = L.mode;
     if (m.level >= 1) HIPCHECK(hipMemsetAsync(e->scores, 0, (size_t)L.np * e->cfg.max_len * sizeof(float), e->stream));
     if (m.level >= 2) {
         ensure_alt_buffers(e);
@@ -2479,7 +2556,7 @@ void start_batch(mocr_engine* e, Lane& L) {
         }
         HIPCHECK(hipMemcpyAsync(e->aut_base_of_row, L.h_aut.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
         launch_automaton_init(e, e->row_mask, e->tok_table, e->set_of_row, e->ngram_of_row, L.np, e->aut_edge_begin, e->aut_edge_token,
-                              e->aut_accepting, e->aut_base_of_row, e->aut_state);
+                              e->aut_accepting, e->aut_base_of_row, e->aut_state, m.soft ? e->aut_default_next : nullptr);
     }
     // token positions: position 0, the pad tail and the rows of the jobs that did not ask read 0
     if (m.positions) {
@@ -2722,9 +2799,9 @@ bool pump_once(mocr_engine* e) {
         if (L.active) {
             e->bind((int)i);
             e->regime = L.np0;
-            e->beam_batch = L.mode.beam; e->automaton_batch = L.mode.automaton;
+            e->beam_batch = L.mode.beam; e->automaton_batch = L.mode.automaton; e->soft_batch = L.mode.soft;
             advance<T>(e, L);
-            e->regime = 0; e->beam_batch = false; e->automaton_batch = false;
+            e->regime = 0; e->beam_batch = false; e->automaton_batch = false; e->soft_batch = false;
             e->unbind((int)i);
             any = true;
         }
@@ -2738,7 +2815,7 @@ void drive(mocr_engine* e) {
         if (e->cfg.dtype == MOCR_BF16) { while (pump_once<bf16_t>(e)) {} }
         else { while (pump_once<float>(e)) {} }
     } catch (...) {
-        e->regime = 0; e->beam_batch = false; e->automaton_batch = false;
+        e->regime = 0; e->beam_batch = false; e->automaton_batch = false; e->soft_batch = false;
         e->pending.clear();
         for (auto& L : e->lanes) { L.active = false; L.jobs.clear(); (void)hipStreamSynchronize(L.ctx.stream); }
         throw;
@@ -3282,8 +3359,14 @@ int mocr_automaton_create(mocr_engine* e, const mocr_automaton_desc* d, int32_t*
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         if (!e->committed) throw ArgError{"weights not committed (mocr_commit_weights)", MOCR_ERR_STATE};
-        if (!d || d->struct_size < (int32_t)sizeof(mocr_automaton_desc) || !out_handle || d->n_states < 1 || !d->edge_begin || !d->accepting)
+        // (the struct grew by edge_weight and default_next: a caller that passes the short struct gets a hard automaton)
+        if (!d || d->struct_size < (int32_t)offsetof(mocr_automaton_desc, edge_weight) || !out_handle || d->n_states < 1 || !d->edge_begin ||
+            !d->accepting)
             throw ArgError{"mocr_automaton_create: bad argument", MOCR_ERR_ARG};
+        const bool grown = d->struct_size >= (int32_t)sizeof(mocr_automaton_desc);
+        const float* const edge_weight = grown ? d->edge_weight : nullptr;
+        const int32_t* const default_next = grown ? d->default_next : nullptr;
+        const bool soft = edge_weight || default_next;
         const int ns = d->n_states;
         if (d->edge_begin[0] != 0) throw ArgError{"mocr_automaton_create: edge_begin[0] must be 0", MOCR_ERR_ARG};
         for (int s = 0; s < ns; ++s)
@@ -3306,8 +3389,23 @@ int mocr_automaton_create(mocr_engine* e, const mocr_automaton_desc* d, int32_t*
                 if (d->edge_next[i] < 0 || d->edge_next[i] >= ns) throw ArgError{"mocr_automaton_create: edge_next outside [0, n_states)", MOCR_ERR_ARG};
                 next[i] = S0 + d->edge_next[i];
             }
+        std::vector<int> dnext;
+        if (edge_weight)
+            for (int i = 0; i < ne; ++i)
+                if (!std::isfinite(edge_weight[i])) throw ArgError{"mocr_automaton_create: edge_weight must be finite", MOCR_ERR_ARG};
+        if (default_next) {
+            dnext.resize((size_t)ns);
+            for (int s = 0; s < ns; ++s) {
+                // (a state number, with or without MOCR_DEFAULT_FALLBACK, or -1; the arena keeps the bit on the global number)
+                const int to = default_next[s] < 0 ? default_next[s] : default_next[s] & ~MOCR_DEFAULT_FALLBACK;
+                if (to < -1 || to >= ns)
+                    throw ArgError{"mocr_automaton_create: default_next outside [0, n_states) and not -1", MOCR_ERR_ARG};
+                dnext[s] = to < 0 ? -1 : (S0 + to) | (default_next[s] & MOCR_DEFAULT_FALLBACK);
+            }
+        }
         HIPCHECK(hipSetDevice(e->cfg.device));
         ensure_automaton_arena(e);
+        if (soft) ensure_soft_arena(e);
         // fresh states behind the last automaton's: no queued or running batch can hold this handle yet, so the copies race
         // with nothing (edge_begin[S0] is rewritten with the value it has)
         HIPCHECK(hipMemcpy(e->aut_edge_begin + S0, begin.data(), begin.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -3316,8 +3414,11 @@ int mocr_automaton_create(mocr_engine* e, const mocr_automaton_desc* d, int32_t*
             HIPCHECK(hipMemcpy(e->aut_edge_next + E0, next.data(), (size_t)ne * sizeof(int), hipMemcpyHostToDevice));
         }
         HIPCHECK(hipMemcpy(e->aut_accepting + S0, d->accepting, (size_t)ns, hipMemcpyHostToDevice));
+        // (the soft arrays hold 0 / -1 wherever no create has written: nothing to do for an array that did not come)
+        if (edge_weight && ne > 0) HIPCHECK(hipMemcpy(e->aut_edge_weight + E0, edge_weight, (size_t)ne * sizeof(float), hipMemcpyHostToDevice));
+        if (default_next) HIPCHECK(hipMemcpy(e->aut_default_next + S0, dnext.data(), (size_t)ns * sizeof(int), hipMemcpyHostToDevice));
         *out_handle = (int32_t)e->aut_first.size();
-        e->aut_first.push_back(S0); e->aut_states.push_back(ns);
+        e->aut_first.push_back(S0); e->aut_states.push_back(ns); e->aut_soft.push_back(soft ? 1 : 0);
         e->aut_n_states += ns; e->aut_n_edges += ne;
     });
 }
@@ -3332,6 +3433,7 @@ int64_t mocr_automaton_state_bytes(mocr_engine* e) {
     if (!e) return 0;
     std::lock_guard<std::mutex> lk(e->mu);
     int64_t bytes = e->aut_edge_begin ? (int64_t)AUT_ARENA_BYTES : 0;
+    if (e->aut_edge_weight) bytes += (int64_t)AUT_SOFT_ARENA_BYTES;
     for (const Lane& L : e->lanes)
     {
         if (L.ctx.aut_state) bytes += 3 * (int64_t)e->Bp * (int64_t)sizeof(int);
@@ -3374,6 +3476,9 @@ static void require_automata(const mocr_engine* e, const Request& r, int n) {
     const int count = (int)e->aut_first.size();
     for (int i = 0; i < n; ++i)
         if (r.automata[i] < 0 || r.automata[i] >= count) throw ArgError{"unknown automaton handle (mocr_automaton_create)", MOCR_ERR_ARG};
+    if (r.beam)         // beam search ranks what an automaton allows; biases inside a beam's score are out of scope
+        for (int i = 0; i < n; ++i)
+            if (e->aut_soft[r.automata[i]]) throw ArgError{"beam search takes no soft automaton (edge_weight / default_next)", MOCR_ERR_ARG};
 }
 
 // shared encodings: every index names an image of the call, and every image is named by a row
@@ -4835,7 +4940,8 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d
                         const int32_t* d_prefix = nullptr, const int32_t* d_prefix_len = nullptr, int32_t prefix_ld = 0,
                         const float* d_tgt_val = nullptr, const int32_t* d_edge_begin = nullptr, const int32_t* d_edge_token = nullptr,
                         const int32_t* d_edge_next = nullptr, const uint8_t* d_accepting = nullptr,
-                        const int32_t* d_aut_base_of_row = nullptr, int32_t* d_aut_state = nullptr) {
+                        const int32_t* d_aut_base_of_row = nullptr, int32_t* d_aut_state = nullptr,
+                        const float* d_edge_weight = nullptr, const int32_t* d_default_next = nullptr) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -4856,7 +4962,8 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d
             (d_prefix && (!d_scores || !d_tok_mask || prefix_ld < 1 || (a->ncand > 0 && !d_tgt_val))) ||
             ((d_aut_state == nullptr) != (d_edge_begin == nullptr)) || ((d_aut_state == nullptr) != (d_edge_token == nullptr)) ||
             ((d_aut_state == nullptr) != (d_edge_next == nullptr)) || ((d_aut_state == nullptr) != (d_accepting == nullptr)) ||
-            ((d_aut_state == nullptr) != (d_aut_base_of_row == nullptr)) || (d_aut_state && !d_row_mask))
+            ((d_aut_state == nullptr) != (d_aut_base_of_row == nullptr)) || (d_aut_state && !d_row_mask) ||
+            ((d_edge_weight == nullptr) != (d_default_next == nullptr)) || (d_edge_weight && !d_aut_state))
             throw ArgError{"mocr_op_dec_token: bad argument", MOCR_ERR_ARG};
         DecState st{};
         st.n_real = a->n_real;
@@ -4871,7 +4978,8 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d
         st.row_mask = d_row_mask; st.base_mask = d_base_mask; st.base_set_of_row = d_base_set_of_row; st.ngram_of_row = d_ngram_of_row;
         st.prefix = d_prefix; st.prefix_len = d_prefix_len; st.prefix_ld = prefix_ld; st.tgt_val = d_tgt_val;
         DecTokenArgs t{};
-        t.aut = DecAutomata{d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state};
+        static_cast<DecAutomata&>(t.aut) = DecAutomata{d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state};
+        t.aut.edge_weight = d_edge_weight; t.aut.default_next = d_default_next;
         t.slabs = a->slabs; t.nslab = first ? 0 : a->nslab; t.slab_stride = (long long)a->n * e->V;
         t.vbias = a->vbias ? a->vbias : e->w.bv;
         t.cand_val = a->cand_val; t.cand_idx = a->cand_idx; t.ncand = first ? 0 : std::max(a->ncand, 0);
@@ -4919,9 +5027,43 @@ int mocr_op_dec_token_automaton(mocr_engine* e, const mocr_token_args* a, const 
                         d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state);
 }
 
+int mocr_op_dec_token_soft(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                           const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
+                           const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
+                           const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row,
+                           const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld, const float* d_tgt_val,
+                           const int32_t* d_edge_begin, const int32_t* d_edge_token, const int32_t* d_edge_next,
+                           const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state,
+                           const float* d_edge_weight, const int32_t* d_default_next) {
+    return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, d_row_mask,
+                        d_base_mask, d_base_set_of_row, d_ngram_of_row, d_prefix, d_prefix_len, prefix_ld, d_tgt_val, d_edge_begin,
+                        d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state, d_edge_weight, d_default_next);
+}
+
+static int op_automaton_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
+                             const int32_t* d_ngram_of_row, int32_t rows, const int32_t* d_edge_begin, const int32_t* d_edge_token,
+                             const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state,
+                             const int32_t* d_default_next);
+
+int mocr_op_automaton_init_soft(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
+                                const int32_t* d_ngram_of_row, int32_t rows, const int32_t* d_edge_begin, const int32_t* d_edge_token,
+                                const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state,
+                                const int32_t* d_default_next) {
+    return op_automaton_init(e, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows, d_edge_begin, d_edge_token, d_accepting,
+                             d_aut_base_of_row, d_aut_state, d_default_next);
+}
+
 int mocr_op_automaton_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
                            const int32_t* d_ngram_of_row, int32_t rows, const int32_t* d_edge_begin, const int32_t* d_edge_token,
                            const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state) {
+    return op_automaton_init(e, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows, d_edge_begin, d_edge_token, d_accepting,
+                             d_aut_base_of_row, d_aut_state, nullptr);
+}
+
+static int op_automaton_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
+                             const int32_t* d_ngram_of_row, int32_t rows, const int32_t* d_edge_begin, const int32_t* d_edge_token,
+                             const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state,
+                             const int32_t* d_default_next) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -4931,7 +5073,7 @@ int mocr_op_automaton_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t*
             !d_edge_begin || !d_edge_token || !d_accepting || !d_aut_base_of_row || !d_aut_state)
             throw ArgError{"mocr_op_automaton_init: bad argument", MOCR_ERR_ARG};
         launch_automaton_init(e, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows, d_edge_begin, d_edge_token, d_accepting,
-                              d_aut_base_of_row, d_aut_state);
+                              d_aut_base_of_row, d_aut_state, d_default_next);
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
@@ -4976,6 +5118,10 @@ static int op_lm_head(mocr_engine* e, const void* dA, const void* dW, const floa
         if ((tt.prefix || tt.prefix_len || tt.step || tt.tgt_val) &&
             (!tt.prefix || !tt.prefix_len || !tt.step || !tt.tgt_val || tt.prefix_ld < 1 || !d_tok_mask || !d_cand_sum))
             throw ArgError{"mocr_op_gemm_argmax_target: the five target arrays come together, with d_tok_mask and d_cand_sum", MOCR_ERR_ARG};
+        const TokSoft& ts = lm.soft;
+        if ((ts.state || ts.edge_begin || ts.edge_token || ts.edge_weight) &&
+            (!ts.state || !ts.edge_begin || !ts.edge_token || !ts.edge_weight || !d_tok_mask))
+            throw ArgError{"mocr_op_gemm_argmax_soft: the states and the three tables come together, with d_tok_mask", MOCR_ERR_ARG};
         // (the name and the epilogue by the richest output given, as the steps choose theirs by the batch's mode)
         DecMode m;
         m.level = d_top_val ? 2 : d_cand_sum ? 1 : 0; m.mask = d_tok_mask != nullptr;
@@ -5003,6 +5149,21 @@ int mocr_op_gemm_argmax_target(mocr_engine* e, const void* dA, const void* dW, c
     return op_lm_head(e, dA, dW, d_bias, d_cand_val, M, N, K, tile,
                       LmHead{d_cand_idx, d_cand_sum, d_top_val, d_top_idx, TokMask{d_tok_mask, d_set_of_row, d_rowmap},
                              TokTarget{d_prefix, d_prefix_len, prefix_ld, d_step, d_tgt_val}});
+}
+
+int mocr_op_gemm_argmax_soft(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                             int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N,
+                             int32_t K, int32_t tile, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
+                             const int32_t* d_rowmap, const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld,
+                             const int32_t* d_step, float* d_tgt_val, const mocr_soft_tables* soft) {
+    TokSoft ts{};
+    if (soft) {
+        if (soft->struct_size != (int32_t)sizeof(mocr_soft_tables)) return MOCR_ERR_ARG;
+        ts = TokSoft{soft->d_aut_state, soft->d_edge_begin, soft->d_edge_token, soft->d_edge_weight};
+    }
+    return op_lm_head(e, dA, dW, d_bias, d_cand_val, M, N, K, tile,
+                      LmHead{d_cand_idx, d_cand_sum, d_top_val, d_top_idx, TokMask{d_tok_mask, d_set_of_row, d_rowmap},
+                             TokTarget{d_prefix, d_prefix_len, prefix_ld, d_step, d_tgt_val}, ts});
 }
 
 int mocr_op_gemm_topk(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,

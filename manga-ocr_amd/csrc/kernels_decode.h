@@ -5,6 +5,7 @@
 // atomics), adds the bias and fuses the element-wise work that follows.
 #pragma once
 #include "common.h"
+#include <type_traits>
 
 // out = LayerNorm( [gelu]( sum_s slab_s + bias ) [+ resid] ) ; writes fp32 (next residual) and T
 // (next GEMM operand).  One block of D/4 threads per row, one float4 per thread; the slab loads
@@ -170,6 +171,18 @@ struct DecAutomata {
 };
 
 constexpr int AUT_STATE_NONE = -1, AUT_STATE_DEAD = -2;     // = MOCR_STATE_NONE / MOCR_STATE_DEAD (mocr.h)
+constexpr int AUT_DEFAULT_FALLBACK = 1 << 30;               // = MOCR_DEFAULT_FALLBACK: a bit of a default_next value
+constexpr int AUT_DEFAULT_STATE = AUT_DEFAULT_FALLBACK - 1; // ... and the bits of its state
+
+// Soft token automata (mocr.h, "soft token automata"): the argument of dec_token_kernel's SOFT form in the place of DecAutomata -
+// the same six pointers plus the two arena arrays a soft batch reads: edge_weight [edges], the fp32 bias an edge adds to its
+// token's logit (0 for every automaton created without weights), and default_next [states], where an OPEN state sends a
+// token without an edge (global; -1: the state is closed).  Only the SOFT instantiations take this type, so every other form
+// keeps the argument block it had.
+struct DecSoftAutomata : DecAutomata {
+    const float* edge_weight;
+    const int* default_next;
+};
 
 // The n-gram bans of a row that holds L tokens rid[0 .. L - 1], on its mask in LDS: the threads split the windows
 // i = 0 .. L - n, a window whose n - 1 key tokens equal the row's last n - 1 clears the bit of its follower.
@@ -229,8 +242,17 @@ __device__ __forceinline__ void ngram_ban_windows(unsigned* s_mask, const int* r
 //      block-wide OR finds no bit left, the dead-end rule: the mask becomes {EOS}.  The words go back with vector stores;
 //   3. thread 0 stores the new state.  Every thread read the old state before the barrier of step 1 or 2 that precedes it.
 //   A row without an automaton takes the NGRAM path; a row that was finished before the step touches neither mask nor state.
+// SOFT = true (the eight pointers of `aut`, a DecSoftAutomata; implies AUTOMATON): soft token automata.  Three things differ.
+//   Slab path: before the masking, a thread adds the weights of the row's state's edges that fall into its 24 columns - per
+//   float4 one binary search in the state's ascending tokens - so the argmax, the exp sum, the alternatives and the forced
+//   column's value see logit + weight; the read of the row's state precedes the argmax reduction's barrier like the mask
+//   reads.  (Candidate path: the LM head's SOFT form has already added them.)  Walk: a token without an edge moves the row to
+//   default_next[state], DEAD only where that is -1; where the value carries AUT_DEFAULT_FALLBACK, the token is walked from
+//   the default state - to the target of that state's edge on it, if it has one (one more scan and barrier).  Mask rebuild: an open state starts from all ones, EOS by `accepting`,
+//   instead of zero plus the OR of the edge bits.  Rows under a hard automaton read weight 0 / default -1 and do what the
+//   AUTOMATON form does.
 template <typename T, int D, bool FIRST, bool SCORES = false, bool TOPK = false, bool MASK = false, bool NGRAM = false,
-          bool AUTOMATON = false>
+          bool AUTOMATON = false, bool SOFT = false>
 __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict__ slabs, int nslab, long long slab_stride,
                                                         const float* __restrict__ vbias, int V,
                                                         DecState st,
@@ -245,16 +267,18 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                                                         const float* __restrict__ cand_sum = nullptr,
                                                         const float* __restrict__ top_val = nullptr,
                                                         const int* __restrict__ top_idx = nullptr,
-                                                        DecAutomata aut = DecAutomata{}) {
+                                                        std::conditional_t<SOFT, DecSoftAutomata, DecAutomata> aut = {}) {
     static_assert(!TOPK || (SCORES && !FIRST), "alternatives come with scores, from the second token on");
     static_assert(!MASK || !FIRST, "the start token is not constrained");
     static_assert(!NGRAM || MASK, "the n-gram bans are applied through the row's mask");
     static_assert(!AUTOMATON || NGRAM, "an automaton's sets are applied through the row's mask");
+    static_assert(!SOFT || AUTOMATON, "weights and default edges belong to an automaton");
     constexpr int MW = 192;                             // mask words of a row (vocab 6144)
     __shared__ __attribute__((aligned(16))) unsigned s_mask[NGRAM ? MW : 4];
     __shared__ int s_ng, s_L;                           // NGRAM: the row's n (0: leave the mask alone) and its token count
     __shared__ int s_abase, s_awalk, s_alive, s_anext;  // AUTOMATON: the row's start state (-1: none or finished before), whether the
                                                         // stored token moves the state, whether the mask is rebuilt, the edge's target
+    __shared__ int s_afall;                             // SOFT: the target of the default state's edge (MOCR_DEFAULT_FALLBACK)
     __shared__ float s_val[4];
     __shared__ int s_idx[4];
     __shared__ float s_red[4];
@@ -299,11 +323,31 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                 a[j].x += x.x; a[j].y += x.y; a[j].z += x.z; a[j].w += x.w;
             }
         }
+        int se0 = 0, se1 = 0;                            // SOFT: the edge range of the row's state (empty: NONE or DEAD)
+        if constexpr (SOFT) {
+            const int sst = aut.state[row];
+            if (sst >= 0) { se0 = aut.edge_begin[sst]; se1 = aut.edge_begin[sst + 1]; }
+        }
 #pragma unroll
         for (int j = 0; j < NC; ++j) {
             const int c = tid * 4 + j * 1024;
             if (st.logits_out)
                 *reinterpret_cast<float4*>(st.logits_out + ((size_t)b * st.forced_T + t) * V + c) = a[j];
+            if constexpr (SOFT) {
+                int lo = se0, hi = se1;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (aut.edge_token[mid] < c) lo = mid + 1; else hi = mid;
+                }
+                for (; lo < se1; ++lo) {
+                    const int d = aut.edge_token[lo] - c;
+                    if (d >= 4) break;
+                    const float wgt = aut.edge_weight[lo];
+                    if (wgt != 0.f) {
+                        if (d == 0) a[j].x += wgt; else if (d == 1) a[j].y += wgt; else if (d == 2) a[j].z += wgt; else a[j].w += wgt;
+                    }
+                }
+            }
             if constexpr (MASK) {
                 const unsigned nib = (st.tok_mask[(size_t)st.set_of_row[row] * (V >> 5) + (c >> 5)] >> (c & 31)) & 15u;
                 if (j == 0) abits = 0;
@@ -434,6 +478,7 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                     s_awalk = tok != st.eos_id;
                     s_alive = live;
                     s_anext = AUT_STATE_DEAD;
+                    if constexpr (SOFT) s_afall = AUT_STATE_DEAD;
                 }
             }
         }
@@ -454,12 +499,32 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                         if (aut.edge_token[i] == tok) s_anext = aut.edge_next[i];
                 }
                 __syncthreads();
+                const int old = state;
                 state = s_anext;
+                if constexpr (SOFT) {                   // (an edge's target is >= 0: DEAD here means no edge)
+                    const int dn = state == AUT_STATE_DEAD && old >= 0 ? aut.default_next[old] : -1;    // block-uniform
+                    if (dn >= 0) {
+                        state = dn & AUT_DEFAULT_STATE;
+                        if (dn & AUT_DEFAULT_FALLBACK) {    // the token is walked from the default state: its edge, if it has one
+                            // (a word of its own: a thread may still be reading s_anext above)
+                            const int f1 = aut.edge_begin[state + 1];
+                            for (int i = aut.edge_begin[state] + tid; i < f1; i += 256)
+                                if (aut.edge_token[i] == tok) s_afall = aut.edge_next[i];
+                            __syncthreads();
+                            if (s_afall >= 0) state = s_afall;
+                        }
+                    }
+                }
             }
             if (live) {
-                if (tid < MW) s_mask[tid] = 0u;
+                bool open = false;                      // SOFT: the new state allows every token, EOS iff it accepts
+                if constexpr (SOFT) open = state >= 0 && aut.default_next[state] >= 0;
+                if (tid < MW) s_mask[tid] = open ? ~0u : 0u;
                 __syncthreads();
-                if (state >= 0) {
+                if (open) {
+                    if (tid == 0 && !aut.accepting[state] && (unsigned)st.eos_id < (unsigned)V)
+                        s_mask[st.eos_id >> 5] &= ~(1u << (st.eos_id & 31));
+                } else if (state >= 0) {
                     const int e1 = aut.edge_begin[state + 1];
                     for (int i = aut.edge_begin[state] + tid; i < e1; i += 256) {
                         const int a = aut.edge_token[i];
@@ -578,6 +643,54 @@ __global__ __launch_bounds__(192) void automaton_init_kernel(unsigned* __restric
         if ((unsigned)a < (unsigned)V) atomicOr(&s_mask[a >> 5], 1u << (a & 31));
     }
     if (tid == 0 && accepting[base] && (unsigned)eos_id < (unsigned)V) atomicOr(&s_mask[eos_id >> 5], 1u << (eos_id & 31));
+    __syncthreads();
+    unsigned m = 0u;
+    if (tid < words) {
+        m = s_mask[tid] & base_mask[(size_t)base_set_of_row[row] * words + tid];
+        if (ban_start && tid == (start_id >> 5)) m &= ~(1u << (start_id & 31));
+    }
+    const int any = __syncthreads_or(m != 0u);
+    if (!any && (unsigned)eos_id < (unsigned)V && tid == (eos_id >> 5)) m = 1u << (eos_id & 31);
+    if (tid < words) row_mask[(size_t)row * words + tid] = m;
+}
+
+// ... and its soft sibling: the start state may be OPEN (default_next[base] >= 0) - then A(start) is every token, EOS iff
+// the state accepts; a closed start state, and a row without an automaton, get what automaton_init_kernel gives them.
+__global__ __launch_bounds__(192) void automaton_init_soft_kernel(unsigned* __restrict__ row_mask, const unsigned* __restrict__ base_mask,
+                                                                  const int* __restrict__ base_set_of_row,
+                                                                  const int* __restrict__ ngram_of_row, int rows, int words, int start_id,
+                                                                  int eos_id, const int* __restrict__ edge_begin,
+                                                                  const int* __restrict__ edge_token, const uint8_t* __restrict__ accepting,
+                                                                  const int* __restrict__ aut_base_of_row, int* __restrict__ aut_state,
+                                                                  const int* __restrict__ default_next) {
+    __shared__ unsigned s_mask[192];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    if (row >= rows) return;
+    const int V = words * 32;
+    const int base = aut_base_of_row[row];              // block-uniform
+    const bool ban_start = ngram_of_row[row] == 1 && (unsigned)start_id < (unsigned)V;
+    if (tid == 0) aut_state[row] = base >= 0 ? base : AUT_STATE_NONE;
+    if (base < 0) {
+        for (int w = tid; w < words; w += blockDim.x) {
+            unsigned m = base_mask[(size_t)base_set_of_row[row] * words + w];
+            if (ban_start && w == (start_id >> 5)) m &= ~(1u << (start_id & 31));
+            row_mask[(size_t)row * words + w] = m;
+        }
+        return;
+    }
+    const bool open = default_next[base] >= 0;          // block-uniform
+    if (tid < words) s_mask[tid] = open ? ~0u : 0u;
+    __syncthreads();
+    if (open) {
+        if (tid == 0 && !accepting[base] && (unsigned)eos_id < (unsigned)V) s_mask[eos_id >> 5] &= ~(1u << (eos_id & 31));
+    } else {
+        const int e1 = edge_begin[base + 1];
+        for (int i = edge_begin[base] + tid; i < e1; i += blockDim.x) {
+            const int a = edge_token[i];
+            if ((unsigned)a < (unsigned)V) atomicOr(&s_mask[a >> 5], 1u << (a & 31));
+        }
+        if (tid == 0 && accepting[base] && (unsigned)eos_id < (unsigned)V) atomicOr(&s_mask[eos_id >> 5], 1u << (eos_id & 31));
+    }
     __syncthreads();
     unsigned m = 0u;
     if (tid < words) {

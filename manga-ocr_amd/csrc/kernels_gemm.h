@@ -21,6 +21,7 @@
 //     contiguous run of tiles, so tiles sharing an A row-panel share an L2.
 #pragma once
 #include "common.h"
+#include <type_traits>
 
 #ifndef MOCR_GEMM_MFMA16
 #define MOCR_GEMM_MFMA16 1      // 1: v_mfma_f32_16x16x32_bf16 in gemm_kernel's bf16 path (+2..6 % at M = 806,912, r01); 0: 32x32x16
@@ -84,6 +85,15 @@ struct GemmParams {
     int prefix_ld;
     const int* step;            // [M] by slot
     float* tgt_val;             // [M] by slot: acc + bias of the target column, -inf when the row's set leaves it out
+};
+
+// Soft token automata (EPI_*_M with gemm_kernel's SOFT): GemmParams plus the rows' states and the arena's tables, the argument of
+// the SOFT instantiations alone - every other form takes GemmParams as it was, so its argument block does not change.
+struct GemmParamsSoft : GemmParams {
+    const int* aut_state;       // [rows of the batch] by ROW: the global state the row is in (< 0: no automaton / dead)
+    const int* edge_begin;      // [states + 1]
+    const int* edge_token;      // [edges] a state's tokens strictly ascending
+    const float* edge_weight;   // [edges] what the edge adds to its token's logit
 };
 
 // Linear tile id -> (tm, tn).  Tiles are ordered column-group by column-group: inside a group of
@@ -180,8 +190,16 @@ __device__ __forceinline__ void gemm_epilogue(const float* sC, const GemmParams&
 // column.  The one thread of the one tile whose column group holds it stores tgt_val[m] = allowed ? sC + bias : -inf - the
 // same fp32 add as in the first walk, so the value equals the tile's `best` bit for bit when the target wins.  One writer
 // per row, a plain vector store; rows without a target leave tgt_val[m] alone.
-template <int BM, int BN, int NT, bool SWZ, bool LSE = false, bool TOPK = false, bool MASK = false, bool TGT = false>
-__device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const GemmParams& p, int m0, int n0, int tid) {
+// SOFT (implies MASK; p is a GemmParamsSoft): soft token automata.  Before the first walk the thread that owns the column group
+// [g0, g0 + CPP) of row m reads the row's state - written by the previous step's token kernel, an earlier launch -, binary-
+// searches g0 in the state's ascending edge tokens and adds the weight of every edge inside its group to the tile value in
+// LDS, at the swizzled column.  A thread reads and writes its own group only, so there is no barrier; the max walk, the exp-sum
+// walk, the four best and the target column then see logit + weight with no further change.  Rows without an automaton, dead
+// rows and rows >= M add nothing.
+template <int BM, int BN, int NT, bool SWZ, bool LSE = false, bool TOPK = false, bool MASK = false, bool TGT = false, bool SOFT = false,
+          typename P = GemmParams>
+__device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const P& p, int m0, int n0, int tid) {
+    static_assert(!SOFT || MASK, "the weighted LM head is a masked one");
     constexpr int TPRW = NT / BM, CPP = BN / TPRW;
     static_assert(TPRW == 2 || TPRW == 4, "two or four threads per row");
     const int row = tid / TPRW, part = tid % TPRW;
@@ -203,6 +221,26 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const Gemm
             mbits = ((unsigned long long)w2.y << 32) | w2.x;
         } else {
             mbits = mrow[g0 >> 5] >> (g0 & 31);
+        }
+    }
+    if constexpr (SOFT) {
+        if (m < p.M) {
+            const int s = p.aut_state[p.rowmap ? p.rowmap[m] : m];
+            if (s >= 0) {
+                float* const srow = const_cast<float*>(sC) + row * BN;
+                const int e1 = p.edge_begin[s + 1];
+                int lo = p.edge_begin[s], hi = e1;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (p.edge_token[mid] < g0) lo = mid + 1; else hi = mid;
+                }
+                for (; lo < e1; ++lo) {
+                    const int tok = p.edge_token[lo];
+                    if (tok >= g0 + CPP) break;
+                    const float wgt = p.edge_weight[lo];
+                    if (wgt != 0.f) srow[(tok - n0) ^ sw] += wgt;      // (as the target column: logical tok - n0 sits at physical (tok - n0) ^ sw)
+                }
+            }
         }
     }
     Top4 top;
@@ -324,8 +362,11 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
 // the plain double buffer; the latency-bound skinny GEMMs of the decode step use NST = 4 (64x64
 // tile: 4 x 16 KiB) so a DMA has three K-tiles of time to land.
 // TGT (EPI_ARGMAX_LSE_M / EPI_TOPK_M only): the epilogue also stores the forced prefixes' target column (GemmParams::tgt_val).
-template <typename T, int BM, int BN, int EPI, int NST = 2, bool TGT = false>
-__global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
+// SOFT (the three EPI_*_M forms only): the epilogue first adds the rows' automaton edge weights; the argument is a GemmParamsSoft.
+template <typename T, int BM, int BN, int EPI, int NST = 2, bool TGT = false, bool SOFT = false>
+__global__ __launch_bounds__(256) void gemm_kernel(std::conditional_t<SOFT, GemmParamsSoft, GemmParams> p) {
+    static_assert(!SOFT || EPI == EPI_ARGMAX_M || EPI == EPI_ARGMAX_LSE_M || EPI == EPI_TOPK_M, "edge weights go into the masked LM head");
+    using P = std::conditional_t<SOFT, GemmParamsSoft, GemmParams>;
     constexpr int TM = BM / 64, TN = BN / 64;          // 32x32 MFMA tiles per wave
     constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE = A_BYTES + B_BYTES;
     constexpr int LPT = (BM / 8 + BN / 8) / 4;         // DMA instructions per wave per K-tile
@@ -515,11 +556,11 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
     } else if constexpr (EPI == EPI_TOPK) {
         gemm_epilogue_argmax<BM, BN, 256, SWZ, true, true>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_ARGMAX_M) {
-        gemm_epilogue_argmax<BM, BN, 256, SWZ, false, false, true>(sC, p, m0, n0, tid);
+        gemm_epilogue_argmax<BM, BN, 256, SWZ, false, false, true, false, SOFT, P>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_ARGMAX_LSE_M) {
-        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, false, true, TGT>(sC, p, m0, n0, tid);
+        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, false, true, TGT, SOFT, P>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_TOPK_M) {
-        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, true, true, TGT>(sC, p, m0, n0, tid);
+        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, true, true, TGT, SOFT, P>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_BIAS) {
         GemmParams q = p;
         q.out = reinterpret_cast<T*>(p.out) + (size_t)blockIdx.y * p.o_yoff;

@@ -96,6 +96,18 @@ class MocrAutomatonDesc(C.Structure):
                 ("edge_next", C.c_void_p), ("accepting", C.c_void_p)]
 
 
+class MocrSoftAutomatonDesc(C.Structure):
+    """include/mocr.h: mocr_automaton_desc with its two trailing fields (soft token automata); MocrAutomatonDesc is the
+    struct as it was before it grew, which the library still takes"""
+    _fields_ = MocrAutomatonDesc._fields_ + [("edge_weight", C.c_void_p), ("default_next", C.c_void_p)]
+
+
+class MocrSoftTables(C.Structure):
+    """include/mocr.h: mocr_soft_tables"""
+    _fields_ = [("struct_size", C.c_int32), ("d_aut_state", C.c_void_p), ("d_edge_begin", C.c_void_p), ("d_edge_token", C.c_void_p),
+                ("d_edge_weight", C.c_void_p)]
+
+
 MAX_AUTOMATA = 256                    # MOCR_MAX_AUTOMATA
 MAX_AUTOMATON_STATES = 1 << 20        # MOCR_MAX_AUTOMATON_STATES: over all automata of an engine
 MAX_AUTOMATON_EDGES = 1 << 22         # MOCR_MAX_AUTOMATON_EDGES
@@ -167,6 +179,11 @@ SYMBOLS = {
     "mocr_op_dec_token_automaton": (C.c_int, [_P, C.POINTER(MocrTokenArgs), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P,
                                               _P, _P, _P, _P, _P, _P]),
     "mocr_op_automaton_init": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    "mocr_op_dec_token_soft": (C.c_int, [_P, C.POINTER(MocrTokenArgs), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P,
+                                         _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mocr_op_automaton_init_soft": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "mocr_op_gemm_argmax_soft": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
+                                           C.c_int32, _P, _P, C.POINTER(MocrSoftTables)]),
     "mocr_op_enc_expand": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),
     "mocr_graph_count": (C.c_int, [_P]),
     "mocr_compaction_count": (C.c_int64, [_P]),

@@ -207,21 +207,40 @@ class Engine:
         return a
 
     # ------------------------------------------------------------------ token automata
-    def automaton(self, edge_begin, edge_token, edge_next, accepting) -> int:
+    def automaton(self, edge_begin, edge_token, edge_next, accepting, edge_weight=None, default_next=None) -> int:
         """A token automaton of this engine (include/mocr.h, "token automata") in CSR form: state s has the edges
         ``edge_begin[s] .. edge_begin[s + 1]`` of ``edge_token`` / ``edge_next``, tokens strictly ascending, state 0 the start;
         ``accepting``: one flag per state.  Returns its handle (>= 1) for ``automata=``; automata are immutable and live as
-        long as the engine."""
+        long as the engine.  ``edge_weight`` (float32 per edge, finite) and ``default_next`` (per state: where a token without
+        an edge goes, -1 = nowhere) make it a SOFT automaton ("soft token automata"); with both None the call is the one it
+        always was."""
         eb = np.ascontiguousarray(np.asarray(edge_begin).ravel(), dtype=np.int32)
         et = np.ascontiguousarray(np.asarray(edge_token).ravel(), dtype=np.int32)
         en = np.ascontiguousarray(np.asarray(edge_next).ravel(), dtype=np.int32)
         acc = np.ascontiguousarray(np.asarray(accepting).ravel() != 0, dtype=np.uint8)
         if eb.size < 2 or acc.size != eb.size - 1 or et.size != en.size or (eb.size and int(eb[-1]) != et.size):
             raise ValueError("automaton: edge_begin [states + 1], accepting [states] and edge_token / edge_next [edge_begin[-1]]")
+        # (without the two arrays: the struct as it was before it grew, which the library reads as a hard automaton)
         desc = _capi.MocrAutomatonDesc(C.sizeof(_capi.MocrAutomatonDesc), int(acc.size), _ptr(eb), _ptr(et), _ptr(en), _ptr(acc))
+        ref = C.byref(desc)
+        if edge_weight is not None or default_next is not None:
+            ew = None if edge_weight is None else np.ascontiguousarray(np.asarray(edge_weight).ravel(), dtype=np.float32)
+            dn = None if default_next is None else np.ascontiguousarray(np.asarray(default_next).ravel(), dtype=np.int32)
+            if (ew is not None and ew.size != et.size) or (dn is not None and dn.size != acc.size):
+                raise ValueError("automaton: edge_weight [edges] and default_next [states]")
+            desc = _capi.MocrSoftAutomatonDesc(C.sizeof(_capi.MocrSoftAutomatonDesc), int(acc.size), _ptr(eb), _ptr(et), _ptr(en),
+                                               _ptr(acc), _ptr(ew), _ptr(dn))
+            ref = C.cast(C.pointer(desc), C.POINTER(_capi.MocrAutomatonDesc))
         out = C.c_int32(0)
-        self._check(self.lib.mocr_automaton_create(self._h, C.byref(desc), C.byref(out)))
+        self._check(self.lib.mocr_automaton_create(self._h, ref, C.byref(out)))
+        used = self.automaton_used()
+        self._automaton_used = (used[0] + int(acc.size), used[1] + int(et.size))
         return int(out.value)
+
+    def automaton_used(self) -> tuple:
+        """(states, edges) of the automata this object has created: what is taken of the engine's tables, which all its
+        automata share (``_capi.MAX_AUTOMATON_STATES`` / ``MAX_AUTOMATON_EDGES``)."""
+        return getattr(self, "_automaton_used", (0, 0))
 
     def automaton_count(self) -> int:
         """Automata created so far."""
@@ -858,6 +877,42 @@ class Engine:
         self._check(self.lib.mocr_op_automaton_init(self._h, _ptr(d_row_mask), _ptr(d_base_mask), _ptr(d_base_set_of_row),
                                                     _ptr(d_ngram_of_row), int(rows), _ptr(d_edge_begin), _ptr(d_edge_token),
                                                     _ptr(d_accepting), _ptr(d_aut_base_of_row), _ptr(d_aut_state)))
+
+    def op_dec_token_soft(self, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row,
+                          d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, d_prefix, d_prefix_len, prefix_ld, d_tgt_val,
+                          d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state, d_edge_weight,
+                          d_default_next, **kw) -> None:
+        """The token step with soft token automata: op_dec_token_automaton plus the edges' weights and the states' default
+        edges (include/mocr.h mocr_op_dec_token_soft); both None is that call."""
+        self._check(self.lib.mocr_op_dec_token_soft(
+            self._h, self._args(_capi.MocrTokenArgs, kw), _ptr(d_cand_sum), _ptr(d_scores), _ptr(d_top_val), _ptr(d_top_idx),
+            _ptr(d_alt_ids), _ptr(d_alt_logp), _ptr(d_tok_mask), _ptr(d_set_of_row), _ptr(d_row_mask), _ptr(d_base_mask),
+            _ptr(d_base_set_of_row), _ptr(d_ngram_of_row), _ptr(d_prefix), _ptr(d_prefix_len), int(prefix_ld), _ptr(d_tgt_val),
+            _ptr(d_edge_begin), _ptr(d_edge_token), _ptr(d_edge_next), _ptr(d_accepting), _ptr(d_aut_base_of_row), _ptr(d_aut_state),
+            _ptr(d_edge_weight), _ptr(d_default_next)))
+
+    def op_automaton_init_soft(self, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows: int, d_edge_begin, d_edge_token,
+                               d_accepting, d_aut_base_of_row, d_aut_state, d_default_next) -> None:
+        """The start of a batch with soft token automata (include/mocr.h: mocr_op_automaton_init_soft); d_default_next None is
+        op_automaton_init."""
+        self._check(self.lib.mocr_op_automaton_init_soft(self._h, _ptr(d_row_mask), _ptr(d_base_mask), _ptr(d_base_set_of_row),
+                                                         _ptr(d_ngram_of_row), int(rows), _ptr(d_edge_begin), _ptr(d_edge_token),
+                                                         _ptr(d_accepting), _ptr(d_aut_base_of_row), _ptr(d_aut_state),
+                                                         _ptr(d_default_next)))
+
+    def op_gemm_argmax_soft(self, dA, dW, d_bias, d_cand_val, d_cand_idx, d_cand_sum, d_top_val, d_top_idx, M, N, K, tile,
+                            d_tok_mask, d_set_of_row, d_rowmap, d_prefix, d_prefix_len, prefix_ld, d_step, d_tgt_val,
+                            d_aut_state=None, d_edge_begin=None, d_edge_token=None, d_edge_weight=None) -> None:
+        """The masked LM head with the rows' automaton edge weights added (include/mocr.h mocr_op_gemm_argmax_soft); the four
+        last arguments all None is op_gemm_argmax_target."""
+        soft = None
+        if not (d_aut_state is None and d_edge_begin is None and d_edge_token is None and d_edge_weight is None):
+            soft = self._args(_capi.MocrSoftTables, dict(d_aut_state=d_aut_state, d_edge_begin=d_edge_begin, d_edge_token=d_edge_token,
+                                                          d_edge_weight=d_edge_weight))
+        self._check(self.lib.mocr_op_gemm_argmax_soft(self._h, _ptr(dA), _ptr(dW), _ptr(d_bias), _ptr(d_cand_val), _ptr(d_cand_idx),
+                                                      _ptr(d_cand_sum), _ptr(d_top_val), _ptr(d_top_idx), M, N, K, tile,
+                                                      _ptr(d_tok_mask), _ptr(d_set_of_row), _ptr(d_rowmap), _ptr(d_prefix),
+                                                      _ptr(d_prefix_len), int(prefix_ld), _ptr(d_step), _ptr(d_tgt_val), soft))
 
     def op_ngram_init(self, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows: int) -> None:
         """Start of a batch with no-repeat n-grams: every row's mask = its base set (n = 1: minus the start token)."""

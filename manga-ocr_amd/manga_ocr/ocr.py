@@ -23,7 +23,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from ._capi import MAX_BEAMS
+from ._capi import MAX_AUTOMATON_EDGES, MAX_AUTOMATON_STATES, MAX_BEAMS
 from .engine import BeamConfig, Engine, result_layout
 from .text import Vocab, find_vocab, ids_to_text
 from .weights import DEFAULT_SPEC, load_checkpoint, synthetic_weights
@@ -96,6 +96,21 @@ class Lexicon(NamedTuple):
     accepting: frozenset
     entries: dict
     texts: tuple
+    # a soft automaton (:meth:`MangaOcr.sequence_bias`, :meth:`MangaOcr.glossary`, :meth:`MangaOcr.automaton` with weights or
+    # default edges): it biases, it does not confine - ``accepted`` / ``entry`` stay None and ``match`` refuses it
+    soft: bool = False
+    spellings: tuple = ()       # glossary: the token ids of every entry, for :meth:`find`
+
+    def find(self, ids) -> list:
+        """Host code: (start position, entry index) of every glossary entry contained in the row ``ids`` (token ids, with or
+        without the start token, EOS and padding), in order of position, then of entry."""
+        row = [int(t) for t in ids]
+        out = []
+        for at in range(len(row)):
+            for k, sp in enumerate(self.spellings):
+                if sp and tuple(row[at:at + len(sp)]) == sp:
+                    out.append((at, k))
+        return out
 
 
 def _lexicons(lexicon, n: int) -> Optional[List[Optional[Lexicon]]]:
@@ -729,13 +744,74 @@ class MangaOcr:
         trans, entry = lexicon_trie(self.vocab, texts)
         return Lexicon(self.engine.automaton(*pack_automaton(trans, entry)), frozenset(entry), dict(entry), texts)
 
-    def automaton(self, transitions, accepting) -> Lexicon:
+    def automaton(self, transitions, accepting, weights=None, default=None) -> Lexicon:
         """The raw form, for patterns such as "one or two digits": ``transitions`` = {state: {token id: next state}} with state 0
-        the start, ``accepting`` = the states a row may end in.  For ``lexicon=``; ``Recognition.entry`` stays None."""
+        the start, ``accepting`` = the states a row may end in.  For ``lexicon=``; ``Recognition.entry`` stays None.
+        ``weights`` (the nesting of ``transitions``: {state: {token id: bias}}) and ``default`` ({state: next state}, or one int
+        for every state) make it a soft automaton (include/mocr.h, "soft token automata"): an edge's bias is added to its
+        token's logit, and a state with a default edge allows every token."""
         from .text import pack_automaton
         self._require("LEXICON")
         acc = frozenset(int(s) for s in accepting)
-        return Lexicon(self.engine.automaton(*pack_automaton(transitions, acc)), acc, {}, ())
+        if weights is None and default is None:
+            return Lexicon(self.engine.automaton(*pack_automaton(transitions, acc)), acc, {}, ())
+        return Lexicon(self.engine.automaton(*pack_automaton(transitions, acc, weights=weights, default=default)), acc, {}, (), True)
+
+    def sequence_bias(self, sequence_bias) -> Lexicon:
+        """transformers' ``generate(sequence_bias=...)`` for ``lexicon=``: ``{text or tuple of token ids: bias}``.  A text is
+        spelt one token per character (``Vocab.encode_chars``).  The bias goes to the last token of a sequence whose earlier
+        tokens are the row's most recent ones; a one-token sequence applies at every step; overlapping sequences add (in
+        float64, rounded once).  Nothing is forbidden: the row may say anything and ends wherever EOS wins.  ``ValueError``:
+        an empty dict, EOS or a special token in a sequence, a bias that is not finite."""
+        import math
+        from .text import bias_automaton, pack_automaton
+        self._require("LEXICON")
+        if not isinstance(sequence_bias, dict) or not sequence_bias:
+            raise ValueError("sequence_bias: a non-empty dict {text or tuple of token ids: bias}")
+        seqs = {}
+        for key, b in sequence_bias.items():
+            ids = tuple(self.vocab.encode_chars(key)) if isinstance(key, str) else tuple(int(t) for t in key)
+            if not ids:
+                raise ValueError(f"sequence_bias: {key!r} has no tokens")
+            if any(t < 0 or t >= self.spec.vocab or t == self.spec.eos_id or t in self.vocab.special_ids for t in ids):
+                raise ValueError(f"sequence_bias: {key!r} holds EOS, a special token or an id outside the vocabulary")
+            if isinstance(b, bool) or not math.isfinite(float(b)):
+                raise ValueError(f"sequence_bias: the bias of {key!r} is not a finite number")
+            seqs[ids] = seqs.get(ids, 0.0) + float(b)
+        # (the compact form: a state does not repeat the root's edges, the fallback walk finds them there)
+        trans, weights = bias_automaton(seqs, compact=True)
+        edges = sum(len(e) for e in trans.values())
+        # (the tables are shared by every automaton of the engine: what counts is what the earlier ones have left)
+        used = self.engine.automaton_used() if hasattr(self.engine, "automaton_used") else (0, 0)
+        if len(trans) > MAX_AUTOMATON_STATES - used[0] or edges > MAX_AUTOMATON_EDGES - used[1]:
+            raise ValueError(f"sequence_bias: the automaton of these sequences has {len(trans)} states and {edges} edges; an engine holds "
+                             f"{MAX_AUTOMATON_STATES} states and {MAX_AUTOMATON_EDGES} edges over ALL its automata, and the earlier ones "
+                             f"have taken {used[0]} states and {used[1]} edges")
+        return Lexicon(self.engine.automaton(*pack_automaton(trans, set(trans), weights=weights, default=0, fallback=True)), frozenset(trans),
+                       {}, (), True)
+
+    def glossary(self, texts, bonus: float = 2.0, start_bonus: float = 0.0) -> Lexicon:
+        """A cast list or series glossary for ``lexicon=``, as a preference instead of a confinement: once the model has started
+        an entry, its continuation is preferred by ``bonus`` (natural-log units on the logit) per token; ``start_bonus``
+        (default 0: a name is not suggested out of nothing) goes to every entry's first token at every step.  Every prefix of
+        two or more tokens of an entry is a :meth:`sequence_bias` sequence with ``bonus`` - a prefix shared by several entries
+        counts once.  The returned Lexicon carries the entries: ``Lexicon.find(recognition.ids)`` lists which were read where."""
+        texts = tuple(str(t) for t in texts)
+        if not texts:
+            raise ValueError("glossary: no entries")
+        spellings = tuple(tuple(self.vocab.encode_chars(t)) for t in texts)
+        seqs = {}
+        for k, sp in enumerate(spellings):
+            if not sp:
+                raise ValueError(f"glossary: entry {k} ({texts[k]!r}) has no characters")
+            for n in range(2, len(sp) + 1):
+                seqs[sp[:n]] = float(bonus)
+            if start_bonus:
+                seqs[sp[:1]] = float(start_bonus)
+        if not seqs:
+            raise ValueError("glossary: every entry is a single token and start_bonus is 0: nothing to prefer")
+        lex = self.sequence_bias(seqs)
+        return lex._replace(texts=texts, spellings=spellings)
 
     def _allowed(self, allowed, n: int) -> dict:
         """the engine keyword of ``allowed=`` ({} for None: the call the method always made)"""
@@ -844,6 +920,9 @@ class MangaOcr:
         out = []
         for r, x, s in zip(recs, lex, state):
             s = int(s)
+            if x is not None and x.soft:        # a soft automaton confines nothing: there is nothing to accept
+                out.append(replace(r, state=s, accepted=None, entry=None))
+                continue
             ok = x is not None and len(r.ids) > 1 and int(r.ids[-1]) == self.spec.eos_id and s in x.accepting
             out.append(replace(r, state=s, accepted=bool(ok), entry=x.entries.get(s) if ok else None))
         return out
@@ -1197,6 +1276,8 @@ class MangaOcr:
         if positions and isinstance(src, _Regions):
             src = src.with_rects()
         lex = _lexicons(lexicon, src.n) or [None] * src.n
+        if any(x is not None and x.soft for x in lex):
+            raise ValueError("match: beam search takes no soft automaton (sequence_bias / glossary / weights): use recognize*(lexicon=)")
         ids, lens, sc, *rest = self._beam(src, beam, bool(token_scores), allowed, bool(positions), lex)
         logp = rest.pop(0) if token_scores else None
         pos = rest.pop(0) if positions else None

@@ -200,13 +200,34 @@ def ids_to_text(vocab: Vocab, ids: Iterable[int]) -> str:
     return text
 
 
-def pack_automaton(transitions, accepting, n_states: Optional[int] = None):
+DEFAULT_FALLBACK = 1 << 30      # MOCR_DEFAULT_FALLBACK (include/mocr.h): a bit of a default_next value
+
+
+def pack_automaton(transitions, accepting, n_states: Optional[int] = None, weights=None, default=None, fallback: bool = False):
     """A token automaton ``{state: {token id: next state}}`` with its accepting states -> the CSR form the engine takes
     (include/mocr.h, "token automata"): (edge_begin [states + 1], edge_token, edge_next [edges], accepting [states]), every
-    state's edges sorted by token.  State 0 is the start; states are 0 .. the largest one named (or ``n_states`` - 1)."""
+    state's edges sorted by token.  State 0 is the start; states are 0 .. the largest one named (or ``n_states`` - 1).
+    Soft automata: ``weights`` = ``{state: {token id: bias}}`` (an edge without one: 0; a weight without an edge: ValueError) and
+    ``default`` = ``{state: next state}``, or one int for every state (a state without one: -1, closed); ``fallback`` = True
+    marks every default edge with ``DEFAULT_FALLBACK``: a token without an edge is walked from the default state, to the target
+    of that state's edge on it if it has one.  With either of ``weights`` / ``default`` given the result has two more elements,
+    edge_weight [edges] and default_next [states]; with both None it is what it always was."""
     trans = {int(s): {int(t): int(n) for t, n in e.items()} for s, e in dict(transitions).items()}
     acc = {int(s) for s in accepting}
     named = set(trans) | acc | {n for e in trans.values() for n in e.values()} | {0}
+    soft = weights is not None or default is not None
+    dflt = {}
+    if default is not None and not isinstance(default, dict):
+        if isinstance(default, bool) or int(default) != default:
+            raise ValueError("automaton: default is {state: next state} or one state number")
+        named |= {int(default)}
+    elif default is not None:
+        dflt = {int(s): int(d) for s, d in default.items()}
+        named |= set(dflt) | {d for d in dflt.values() if d >= 0}
+    wts = {int(s): {int(t): float(w) for t, w in e.items()} for s, e in dict(weights or {}).items()}
+    for s, e in wts.items():
+        if set(e) - set(trans.get(s, {})):
+            raise ValueError(f"automaton: state {s} has a weight on a token without an edge")
     if min(named) < 0:
         raise ValueError("automaton: states are numbered from 0")
     n = max(named) + 1 if n_states is None else int(n_states)
@@ -218,7 +239,76 @@ def pack_automaton(transitions, accepting, n_states: Optional[int] = None):
             tok.append(t)
             nxt.append(to)
         begin.append(len(tok))
+    if soft:
+        if any(d < -1 or d >= n for d in dflt.values()):
+            raise ValueError(f"automaton: a default edge beyond n_states ({n})")
+        wt = [wts.get(s, {}).get(t, 0.0) for s in range(n) for t in sorted(trans.get(s, {}))]
+        dn = [int(default)] * n if default is not None and not isinstance(default, dict) else [dflt.get(s, -1) for s in range(n)]
+        if fallback:
+            dn = [d | DEFAULT_FALLBACK if d >= 0 else d for d in dn]
+        return begin, tok, nxt, [1 if s in acc else 0 for s in range(n)], wt, dn
     return begin, tok, nxt, [1 if s in acc else 0 for s in range(n)]
+
+
+def bias_automaton(sequence_bias, compact: bool = False):
+    """transformers' ``generate(sequence_bias=...)`` (SequenceBiasLogitsProcessor) as a soft token automaton:
+    ``{tuple of token ids: bias}`` -> (transitions, weights) for :func:`pack_automaton` with ``default=0`` and every state
+    accepting.  The bias of a sequence goes to its last token when its earlier tokens are the row's most recent ones; a
+    one-token sequence applies at every step; overlapping sequences add.
+    The Aho-Corasick automaton of the sequences WITHOUT their last tokens: a state is the longest suffix of the history that
+    is a proper prefix of a sequence; its edges are the union of the trie children along its fail chain (the child of the
+    deepest node wins the target - that is the goto function), and an edge's weight is the sum, formed in float64 and rounded
+    once by the engine, of the biases of every sequence that completes there - the ones ending at any node of the chain.  A
+    token without an edge falls to the root.
+    ``compact`` = True, for :func:`pack_automaton` with ``default=0, fallback=True``: a state other than the root leaves out
+    every edge that weighs nothing and leads where the root's edge on that token leads (or to the root, where it has none) -
+    the fallback walk finds those in the root.  The flat form repeats the root's edges in every state, states x first tokens
+    edges in all; the compact one keeps a state's own children and completions, those of its fail chain below the root, and
+    the root's weighted edges.  Both walk through the same states and weigh the same tokens."""
+    seqs = {}
+    for ids, b in dict(sequence_bias).items():
+        ids = tuple(int(t) for t in ids)
+        if not ids:
+            raise ValueError("sequence_bias: an empty sequence")
+        seqs[ids] = seqs.get(ids, 0.0) + float(b)
+    # the trie over every proper prefix of a sequence (node 0: the empty history)
+    child = [{}]
+    ends = [{}]                                 # node -> {last token: summed bias of the sequences prefix(node) + token}
+    for ids, b in sorted(seqs.items()):            # (sorted: the state numbers do not depend on the dict's order)
+        s = 0
+        for t in ids[:-1]:
+            if t not in child[s]:
+                child[s][t] = len(child)
+                child.append({})
+                ends.append({})
+            s = child[s][t]
+        ends[s][ids[-1]] = ends[s].get(ids[-1], 0.0) + b
+    # breadth-first, so that a node's fail target (shallower) is done first: the full goto row and the weights of a node are
+    # those of its fail target, overridden / increased by its own children and completions
+    fail = [0] * len(child)
+    trans, weights = {}, {}
+    queue, at = [0], 0
+    while at < len(queue):
+        s = queue[at]
+        at += 1
+        if compact and s and not fail[s]:       # below the root: only what the fallback walk does not find there
+            go = {t: trans[0][t] for t, w in weights[0].items() if w != 0.0}
+            wt = {t: w for t, w in weights[0].items() if w != 0.0}
+        else:
+            go = dict(trans[fail[s]]) if s else {}
+            wt = dict(weights[fail[s]]) if s else {}
+        for t, c in child[s].items():
+            # goto(fail[s], t), before this node's own child replaces it
+            fail[c] = (go[t] if t in go else trans[0].get(t, 0) if compact else 0) if s else 0
+            queue.append(c)
+        for t, c in child[s].items():
+            go[t] = c
+        for t, b in ends[s].items():
+            wt[t] = wt.get(t, 0.0) + b
+            # a completing token that continues nothing: an edge for its weight, to where the token leads anyway
+            go.setdefault(t, trans[0].get(t, 0) if compact and s else 0)
+        trans[s], weights[s] = go, wt
+    return trans, weights
 
 
 def lexicon_trie(vocab: Vocab, texts: Sequence[str]):

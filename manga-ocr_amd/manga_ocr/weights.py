@@ -282,6 +282,12 @@ def spec_from_hf_config(cfg: dict) -> ModelSpec:
         v = cfg.get(k, dec.get(k, dflt))
         if v is not None and v != dflt:
             non_greedy[k] = v
+    # transformers' generate(sequence_bias=...) lives on as MangaOcr.sequence_bias(...) for lexicon=: a checkpoint's own one
+    # is named here, never applied silently (JSON: {"ids": bias} is not possible, so [[ids, bias], ...]; a dict passes too)
+    sb = cfg.get("sequence_bias", dec.get("sequence_bias"))
+    if sb:
+        pairs = sb.items() if isinstance(sb, dict) else sb
+        non_greedy["sequence_bias"] = tuple((tuple(int(t) for t in ((ids,) if isinstance(ids, int) else ids)), float(b)) for ids, b in pairs)
     if non_greedy:
         import warnings
         warnings.warn("checkpoint config asks for non-greedy generation " + repr(non_greedy) +
