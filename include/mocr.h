@@ -445,8 +445,10 @@ int64_t mocr_encoded_crops(mocr_engine* e);
  *     LDS before it reduces it; on the slab paths the token kernel's SOFT form (dec_token*_sw) adds them to the summed logits.
  *     The arena grows by edge_weight (2^22 floats) and default_next (2^20 ints), 20 MiB, allocated at full capacity by the first
  *     create of a soft automaton and pre-filled with 0 / -1 for every automaton that exists or comes later.
- *   Out of scope: beam search - the *_beam_automaton entry points refuse a soft handle with MOCR_ERR_ARG before any work -,
- *     weights on EOS, non-finite weights (a ban is a token set). */
+ *   Beam search: a bias inside a beam's score is a different rule, not this one - the section "beam search under soft token
+ *     automata" below, through the *_beam_soft entry points.  The *_beam_automaton entry points refuse a soft handle with
+ *     MOCR_ERR_ARG before any work.
+ *   Out of scope: weights on EOS, non-finite weights (a ban is a token set). */
 #define MOCR_MAX_AUTOMATA          256
 #define MOCR_MAX_AUTOMATON_STATES  (1 << 20)    /* over all automata of an engine */
 #define MOCR_MAX_AUTOMATON_EDGES   (1 << 22)
@@ -1139,6 +1141,54 @@ int mocr_recognize_device_beam_automaton(mocr_engine* e, const void* d_gray, int
                                          void* d_out_len, void* d_out_score, void* d_out_logp, const int32_t* sets, void* d_out_pos,
                                          const int32_t* automata, void* d_out_state);
 
+/* ---- beam search under soft token automata ---------------------------------------------------------------------------
+ * transformers' generate(num_beams = K, sequence_bias = ...): the bias is a logits processor applied BEHIND the log_softmax,
+ * so it enters the beam's accumulated score and sequences_scores - a glossary re-ranks whole hypotheses instead of one token
+ * at a time.  It is the rule of the section above with the automaton allowed to be SOFT (edge_weight / default_next of
+ * mocr_automaton_desc), and NOT the greedy soft rule, which adds the weight before its softmax.
+ *   THE MASK at the step that chooses token L of beam k, in state s_k:
+ *     1. lp = log_softmax over the FULL row of the raw logits: the row's max and log-sum never see a weight;
+ *     2. s = lp + edge_weight(s_k, t) in fp32 where s_k has an edge on t, s = lp elsewhere (a zero weight adds nothing);
+ *     3. -inf outside A(s_k) AND the crop's token set, and on the beam's n-gram bans;
+ *     4. acc = s + the beam's running score.
+ *     A(s) of an OPEN state (default_next[s] >= 0) is every non-EOS token, plus EOS iff s accepts; A(s) of a closed state is
+ *     the section above's.  Nothing renormalises, a weight never revives a masked token, and there is no dead-end rule.
+ *   THE STATE: a candidate (parent p, token x) goes to next(s_p, x) where s_p has an edge on x; else along default_next[s_p] -
+ *     with MOCR_DEFAULT_FALLBACK the token is looked up in the default state's edges, one level, exactly as the greedy soft
+ *     walk does -; else, only where default_next[s_p] is -1, to MOCR_STATE_DEAD.  A candidate that stopped on EOS and is
+ *     carried on at score - 1e9 follows the default edge of an open state like any token without an edge (EOS is never an
+ *     edge, so under the fallback form it lands on the default state - transformers' suffix match restarts), and is
+ *     MOCR_STATE_DEAD in a closed state.  The hypotheses' states move as in the section above.
+ *   TOKEN SCORES are the very fp32 value that was ranked, s = lp + w (compute_transition_scores(normalize_logits = False)):
+ *     running' = s + running holds exactly, and the sequential fp32 sum of a hypothesis' token scores over
+ *     (len - 1) ^ length_penalty IS its score.
+ *   Bit-identities, in ids, lengths, sequence scores, token scores, positions and states: a hard automaton created with
+ *     all-zero weights equals the same automaton created without, inside a soft beam batch; the universal-open automaton (one
+ *     accepting open state, default_next = 0, no edges) equals MOCR_AUTOMATON_NONE; hard and plain crops of a soft beam batch
+ *     equal the same crops in a *_beam_automaton batch of the same size; a beam batch in which no crop brings a soft automaton
+ *     launches exactly what it launched before.
+ *   How: the selection kernel's SOFT form (profile names beam_select_sw / beam_select_sw_tr), chosen iff a crop of the batch
+ *     brings a soft handle.  A thread binary-searches the state's ascending edge tokens once per float4 of the row it holds
+ *     and adds the weights inside it; the winners' lanes take the weight of the edge they find.  The arena's two soft arrays
+ *     reach it in the trailing argument; no buffer is new, and mocr_automaton_state_bytes does not move.
+ *   Out of scope: weights on EOS, non-finite weights, two automata per crop, more than MOCR_MAX_BEAMS beams.
+ * The *_beam_soft entry points: the argument lists of the *_beam_automaton twins; `automata` may hold soft handles.  With no
+ * soft handle among them a *_beam_soft call IS the *_beam_automaton call: the same launches, the same bits. */
+int mocr_recognize_images_beam_soft(mocr_engine* e, const mocr_image* images, int32_t n, const mocr_beam_config* beam, int32_t* out_ids,
+                                    int32_t* out_len, float* out_score, float* out_logp, const int32_t* sets, float* out_pos,
+                                    const int32_t* automata, int32_t* out_state);
+int mocr_recognize_regions_beam_soft(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                     int32_t n_regions, const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len,
+                                     float* out_score, float* out_logp, const int32_t* sets, float* out_pos,
+                                     const int32_t* automata, int32_t* out_state);
+int mocr_recognize_gray_host_beam_soft(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override,
+                                       const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len, float* out_score,
+                                       float* out_logp, const int32_t* sets, float* out_pos, const int32_t* automata,
+                                       int32_t* out_state);
+int mocr_recognize_device_beam_soft(mocr_engine* e, const void* d_gray, int32_t n, const mocr_beam_config* beam, void* d_out_ids,
+                                    void* d_out_len, void* d_out_score, void* d_out_logp, const int32_t* sets, void* d_out_pos,
+                                    const int32_t* automata, void* d_out_state);
+
 /* Bytes of beam state this engine holds, over its lanes (test hook): 0 until a lane runs its first beam batch - creating an
  * engine and greedy calls of any kind allocate none of it. */
 int64_t mocr_beam_state_bytes(mocr_engine* e);
@@ -1182,6 +1232,15 @@ int mocr_op_beam_select_automaton(mocr_engine* e, const mocr_token_args* a, cons
                                   uint8_t* d_beam_trail, uint8_t* d_hyp_trail, const int32_t* d_edge_begin, const int32_t* d_edge_token,
                                   const int32_t* d_edge_next, const uint8_t* d_accepting, const int32_t* d_aut_base_of_row,
                                   int32_t* d_aut_state, int32_t* d_hyp_state);
+/* ... under soft token automata: mocr_op_beam_select_automaton plus d_edge_weight float32 [edges] and d_default_next int32
+ * [states] over global state numbers (MOCR_DEFAULT_FALLBACK as in the arena; -1: closed), both or neither, and only with the
+ * seven automaton pointers.  Both null: it IS mocr_op_beam_select_automaton. */
+int mocr_op_beam_select_soft(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score, int32_t* d_parent,
+                             int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open, float* d_beam_logp,
+                             float* d_hyp_logp, const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint8_t* d_beam_trail,
+                             uint8_t* d_hyp_trail, const int32_t* d_edge_begin, const int32_t* d_edge_token, const int32_t* d_edge_next,
+                             const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state, int32_t* d_hyp_state,
+                             const float* d_edge_weight, const int32_t* d_default_next);
 /* The cache reorder behind it: d_cache viewed as [layers][rows][segs][positions][pos_bytes] through byte strides; for
  * every group of K slots whose crop is live (d_finished[rowmap[g K]] == 0), row rowmap[g K + k] <- row
  * rowmap[g K + d_parent[rowmap[g K + k]]], bytes 0 .. d_step[g K] * pos_bytes - 1 of every (layer, segment).  max_pos bounds

@@ -241,7 +241,8 @@ struct DecMode {
     bool beam_tokens = false;       // ... in which a job asks for token scores or brings a token set other than MOCR_TOKEN_SET_ALL: the
                                     // selection runs in its token form (level and mask stay 0: the LM head and the caches do not change)
     bool beam_automaton = false;    // ... in which a job brings a token automaton other than MOCR_AUTOMATON_NONE (implies beam_tokens): the
-                                    // selection runs in its automaton form and the batch starts with beam_automaton_init_kernel
+                                    // selection runs in its automaton form and the batch starts with beam_automaton_init_kernel; with
+                                    // `soft` (one of those automata is soft) in its SOFT form, on the arena's weights and default edges
     // a graph captured in one mode is never replayed in another: the mode's share of the decode-graph key (6 bits; a beam
     // batch: bit 6, its token form: bit 7, an automaton batch: bit 8, a beam batch's automaton form: bit 9, a soft automaton
     // batch: bit 10, and a beam batch's configuration - kernel arguments of the captured launches - in the bits above, beam_key)
@@ -1449,24 +1450,33 @@ static BeamState make_beam_state(mocr_engine* e, const mocr_beam_config& c, bool
 }
 
 // the trailing argument of the automaton form, on the engine's tables and the bound lane's states
-static BeamAutomata make_beam_automata(mocr_engine* e) {
-    return BeamAutomata{e->aut_edge_begin, e->aut_edge_token, e->aut_edge_next, e->aut_accepting, e->aut_base_of_row, e->aut_state, e->hyp_state};
+// (`soft`: a crop of the batch brings a soft handle - the arena's soft part too, and with it the selection's SOFT form)
+static BeamSoftAutomata make_beam_automata(mocr_engine* e, bool soft) {
+    BeamSoftAutomata a{};
+    static_cast<BeamAutomata&>(a) =
+        BeamAutomata{e->aut_edge_begin, e->aut_edge_token, e->aut_edge_next, e->aut_accepting, e->aut_base_of_row, e->aut_state, e->hyp_state};
+    if (soft) { a.edge_weight = e->aut_edge_weight; a.default_next = e->aut_default_next; }
+    return a;
 }
 
 // n decode slots = groups of K (a trailing partial group is padding); the LM head's slabs, by slot, are in `a`
 template <typename T>
 void launch_beam_select(mocr_engine* e, const DecState& st, const BeamState& bs, const DecTokenArgs& a, int n, int K,
-                        const BeamAutomata& aut = BeamAutomata{}) {
+                        const BeamSoftAutomata& aut = BeamSoftAutomata{}) {
     auto& w = e->w;
     if (e->D != 768 || e->V != 6144 || st.ids_ld > BEAM_HIST || st.max_len > st.ids_ld || a.nslab < 1)
         throw ArgError{"beam search needs hidden 768, vocab 6144 and max_len <= 320", MOCR_ERR_UNSUPPORTED};
-    ProfScope ps(e, aut.state ? (bs.beam_trail ? "beam_select_am_tr" : "beam_select_am") : (bs.beam_logp || bs.tok_mask) ? "beam_select_tok" : "beam_select",
+    ProfScope ps(e, aut.edge_weight ? (bs.beam_trail ? "beam_select_sw_tr" : "beam_select_sw")
+                    : aut.state     ? (bs.beam_trail ? "beam_select_am_tr" : "beam_select_am")
+                    : (bs.beam_logp || bs.tok_mask) ? "beam_select_tok" : "beam_select",
                  0, (double)n * e->V * 4 * a.nslab);
-    auto launch = [&](auto kernel) {
+    // (`tail`: the trailing argument in the type the form takes - every form but the SOFT one gets the seven pointers alone)
+    auto launch_with = [&](auto kernel, const auto& tail) {
         hipLaunchKernelGGL(kernel, dim3((n + K - 1) / K), dim3(256), 0, e->stream, a.slabs, a.nslab, a.slab_stride, a.vbias, e->V, st, bs, n,
                            w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32, reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps,
-                           reinterpret_cast<T*>(a.cache), a.cstride, a.cache8, a.inv8, aut);
+                           reinterpret_cast<T*>(a.cache), a.cstride, a.cache8, a.inv8, tail);
     };
+    auto launch = [&](auto kernel) { launch_with(kernel, static_cast<const BeamAutomata&>(aut)); };
     // the token form when the state carries any of its four arrays (make_beam_state sets them from the batch's DecMode)
     const bool tok = bs.beam_logp || bs.hyp_logp || bs.tok_mask || bs.set_of_row;
     if ((bs.beam_logp == nullptr) != (bs.hyp_logp == nullptr) || (bs.tok_mask == nullptr) != (bs.set_of_row == nullptr))
@@ -1479,6 +1489,21 @@ void launch_beam_select(mocr_engine* e, const DecState& st, const BeamState& bs,
     if (aut.state) {
         if (!aut.edge_begin || !aut.edge_token || !aut.edge_next || !aut.accepting || !aut.base_of_row || !aut.hyp_state)
             throw ArgError{"beam_select: the automaton tables, the rows' bases and the two state arrays come together", MOCR_ERR_ARG};
+        if ((aut.edge_weight == nullptr) != (aut.default_next == nullptr))
+            throw ArgError{"beam_select: edge_weight and default_next come as a pair", MOCR_ERR_ARG};
+        if (aut.edge_weight) {      // the SOFT form: weights inside the beams' scores, open states
+            switch (K * 2 + (trail ? 1 : 0)) {
+                case 4: launch_with(beam_select_kernel<T, 2, true, false, true, true>, aut); break;
+                case 6: launch_with(beam_select_kernel<T, 3, true, false, true, true>, aut); break;
+                case 8: launch_with(beam_select_kernel<T, 4, true, false, true, true>, aut); break;
+                case 5: launch_with(beam_select_kernel<T, 2, true, true, true, true>, aut); break;
+                case 7: launch_with(beam_select_kernel<T, 3, true, true, true, true>, aut); break;
+                case 9: launch_with(beam_select_kernel<T, 4, true, true, true, true>, aut); break;
+                default: throw ArgError{"num_beams must be 2 .. 4", MOCR_ERR_ARG};
+            }
+            HIPCHECK(hipGetLastError());
+            return;
+        }
         switch (K * 2 + (trail ? 1 : 0)) {
             case 4: launch(beam_select_kernel<T, 2, true, false, true>); break;
             case 6: launch(beam_select_kernel<T, 3, true, false, true>); break;
@@ -1542,7 +1567,7 @@ void beam_finish_step(mocr_engine* e, const DecState& st, const DecMode& m, int 
     a.inv8 = (lat && e->fp8attn) ? 1.0f / e->w.sx_self[0] : 0.f;
     a.cstride = (long long)e->cfg.max_len * e->D;
     launch_beam_select<T>(e, st, make_beam_state(e, m.beam_cfg, m.beam_tokens, m.positions), a, n, K,
-                          m.beam_automaton ? make_beam_automata(e) : BeamAutomata{});
+                          m.beam_automaton ? make_beam_automata(e, m.soft) : BeamSoftAutomata{});
     // `t` bounds the step index of this launch from above only when it is exact (eager steps).  A captured graph passes
     // t = t_hi - 1 for every step of its bucket (decode_graph), and the bucket's last device step is t_hi itself
     // (t0 + steps <= 32 * bucket): behind it `step` is t_hi + 1 = t + 2 positions.  The grid is sized for that; the kernel
@@ -2505,7 +2530,7 @@ void start_batch(mocr_engine* e, Lane& L) {
     // The batch runs in the richest mode any of its jobs asked for.  Scores: the start token and the pad tail score 0;
     // alternatives: positions the steps do not write read -1 / 0
     L.mode = mode_of(L.jobs);
-    if (L.mode.automaton)       // soft token automata: the batch takes the mode if any row's automaton is soft
+    if (L.mode.automaton || L.mode.beam_automaton)      // soft token automata: the batch takes the mode if any row's automaton is soft
         for (const Job& j : L.jobs)
             for (int32_t h : j.automata) L.mode.soft = L.mode.soft || e->aut_soft[h] != 0;
     const DecMode& m = L.mode;
@@ -3467,6 +3492,7 @@ struct Request {
     // final states, host or device like out_ids
     const int32_t* automata = nullptr;
     int32_t* out_state = nullptr;
+    bool beam_soft = false;     // a beam request from the *_beam_soft entry points: its automata may be soft
 };
 
 // token automata: one handle per row, MOCR_AUTOMATON_NONE or an automaton this engine has created (a beam request comes
@@ -3476,7 +3502,7 @@ static void require_automata(const mocr_engine* e, const Request& r, int n) {
     const int count = (int)e->aut_first.size();
     for (int i = 0; i < n; ++i)
         if (r.automata[i] < 0 || r.automata[i] >= count) throw ArgError{"unknown automaton handle (mocr_automaton_create)", MOCR_ERR_ARG};
-    if (r.beam)         // beam search ranks what an automaton allows; biases inside a beam's score are out of scope
+    if (r.beam && !r.beam_soft)     // the *_beam_automaton contract: biases inside a beam's score are the *_beam_soft rule
         for (int i = 0; i < n; ++i)
             if (e->aut_soft[r.automata[i]]) throw ArgError{"beam search takes no soft automaton (edge_weight / default_next)", MOCR_ERR_ARG};
 }
@@ -4247,7 +4273,8 @@ int mocr_recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_pa
 // The *_beam_automaton twins add one automaton handle per crop, expanded like the sets, and out_state [n][K] = [rows].
 struct BeamCall { std::vector<int32_t> source, sets, automata; Request req; int rows = 0; };
 static int beam_call(mocr_engine* e, const mocr_beam_config* beam, int32_t n, void* out_score, BeamCall& bc, void* out_logp = nullptr,
-                     const int32_t* sets = nullptr, void* out_pos = nullptr, const int32_t* automata = nullptr, void* out_state = nullptr) {
+                     const int32_t* sets = nullptr, void* out_pos = nullptr, const int32_t* automata = nullptr, void* out_state = nullptr,
+                     bool soft = false) {
     return guarded(e, [&] {
         if (!beam || beam->num_beams < 2 || beam->num_beams > MOCR_MAX_BEAMS) throw ArgError{"num_beams must be 2 .. MOCR_MAX_BEAMS (4)", MOCR_ERR_ARG};
         if (beam->early_stopping < 0 || beam->early_stopping > 2) throw ArgError{"early_stopping must be 0 (false), 1 (true) or 2 (never)", MOCR_ERR_ARG};
@@ -4275,6 +4302,7 @@ static int beam_call(mocr_engine* e, const mocr_beam_config* beam, int32_t n, vo
             bc.req.automata = bc.automata.data();       // (likewise)
         }
         bc.req.out_state = static_cast<int32_t*>(out_state);
+        bc.req.beam_soft = soft;
     });
 }
 
@@ -4369,6 +4397,41 @@ int mocr_recognize_device_beam_automaton(mocr_engine* e, const void* d_gray, int
                                          const int32_t* automata, void* d_out_state) {
     BeamCall bc;
     if (const int rc = beam_call(e, beam, n, d_out_score, bc, d_out_logp, sets, d_out_pos, automata, d_out_state)) return rc;
+    return recognize_device(e, d_gray, bc.rows, d_out_ids, d_out_len, bc.req);
+}
+
+// The *_beam_soft twins: the *_beam_automaton calls with soft handles allowed (without one they ARE those calls).
+int mocr_recognize_images_beam_soft(mocr_engine* e, const mocr_image* images, int32_t n, const mocr_beam_config* beam, int32_t* out_ids,
+                                    int32_t* out_len, float* out_score, float* out_logp, const int32_t* sets, float* out_pos,
+                                    const int32_t* automata, int32_t* out_state) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, out_score, bc, out_logp, sets, out_pos, automata, out_state, true)) return rc;
+    return recognize_images(e, images, bc.rows, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_regions_beam_soft(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                     int32_t n_regions, const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len,
+                                     float* out_score, float* out_logp, const int32_t* sets, float* out_pos,
+                                     const int32_t* automata, int32_t* out_state) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n_regions, out_score, bc, out_logp, sets, out_pos, automata, out_state, true)) return rc;
+    return recognize_regions(e, pages, n_pages, regions, n_regions, bc.rows, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_gray_host_beam_soft(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override,
+                                       const mocr_beam_config* beam, int32_t* out_ids, int32_t* out_len, float* out_score,
+                                       float* out_logp, const int32_t* sets, float* out_pos, const int32_t* automata,
+                                       int32_t* out_state) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, out_score, bc, out_logp, sets, out_pos, automata, out_state, true)) return rc;
+    return recognize_gray_host(e, gray, bc.rows, max_len_override, out_ids, out_len, bc.req);
+}
+
+int mocr_recognize_device_beam_soft(mocr_engine* e, const void* d_gray, int32_t n, const mocr_beam_config* beam, void* d_out_ids,
+                                    void* d_out_len, void* d_out_score, void* d_out_logp, const int32_t* sets, void* d_out_pos,
+                                    const int32_t* automata, void* d_out_state) {
+    BeamCall bc;
+    if (const int rc = beam_call(e, beam, n, d_out_score, bc, d_out_logp, sets, d_out_pos, automata, d_out_state, true)) return rc;
     return recognize_device(e, d_gray, bc.rows, d_out_ids, d_out_len, bc.req);
 }
 
@@ -5292,6 +5355,17 @@ int mocr_op_beam_select_automaton(mocr_engine* e, const mocr_token_args* a, cons
                                   uint8_t* d_beam_trail, uint8_t* d_hyp_trail, const int32_t* d_edge_begin, const int32_t* d_edge_token,
                                   const int32_t* d_edge_next, const uint8_t* d_accepting, const int32_t* d_aut_base_of_row,
                                   int32_t* d_aut_state, int32_t* d_hyp_state) {
+    return mocr_op_beam_select_soft(e, a, beam, d_beam_score, d_parent, d_hyp_ids, d_hyp_len, d_hyp_score, d_heuristic_open, d_beam_logp,
+                                    d_hyp_logp, d_tok_mask, d_set_of_row, d_beam_trail, d_hyp_trail, d_edge_begin, d_edge_token, d_edge_next,
+                                    d_accepting, d_aut_base_of_row, d_aut_state, d_hyp_state, nullptr, nullptr);
+}
+
+int mocr_op_beam_select_soft(mocr_engine* e, const mocr_token_args* a, const mocr_beam_config* beam, float* d_beam_score, int32_t* d_parent,
+                             int32_t* d_hyp_ids, int32_t* d_hyp_len, float* d_hyp_score, int32_t* d_heuristic_open, float* d_beam_logp,
+                             float* d_hyp_logp, const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint8_t* d_beam_trail,
+                             uint8_t* d_hyp_trail, const int32_t* d_edge_begin, const int32_t* d_edge_token, const int32_t* d_edge_next,
+                             const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state, int32_t* d_hyp_state,
+                             const float* d_edge_weight, const int32_t* d_default_next) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -5308,6 +5382,8 @@ int mocr_op_beam_select_automaton(mocr_engine* e, const mocr_token_args* a, cons
         for (const void* p : aut_ptrs)
             if ((p == nullptr) != (d_aut_state == nullptr))
                 throw ArgError{"mocr_op_beam_select_automaton: the seven automaton pointers must be all null or all set", MOCR_ERR_ARG};
+        if ((d_edge_weight == nullptr) != (d_default_next == nullptr) || (d_edge_weight && !d_aut_state))
+            throw ArgError{"mocr_op_beam_select_soft: d_edge_weight and d_default_next come as a pair, with the seven automaton pointers", MOCR_ERR_ARG};
         DecState st{};
         st.n_real = a->n_real;
         st.ids = a->ids; st.step = a->step; st.finished = a->finished; st.len = a->len; st.n_unfinished = a->n_unfinished;
@@ -5327,7 +5403,9 @@ int mocr_op_beam_select_automaton(mocr_engine* e, const mocr_token_args* a, cons
         if (a->cache && a->cache_fp8) { t.cache8 = reinterpret_cast<uint8_t*>(a->cache); t.inv8 = a->inv_sx; }
         else t.cache = a->cache;
         t.cstride = (long long)e->cfg.max_len * e->D;
-        const BeamAutomata aut{d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state, d_hyp_state};
+        BeamSoftAutomata aut{};
+        static_cast<BeamAutomata&>(aut) = BeamAutomata{d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state, d_hyp_state};
+        aut.edge_weight = d_edge_weight; aut.default_next = d_default_next;
         dispatch(e, [&](auto tag) { launch_beam_select<decltype(tag)>(e, st, bs, t, a->n, beam->num_beams, aut); });
         HIPCHECK(hipStreamSynchronize(e->stream));
     });

@@ -48,6 +48,16 @@ struct BeamAutomata {
     int* hyp_state;
 };
 
+// Soft token automata under beam search (mocr.h, "beam search under soft token automata"): the trailing argument of the SOFT
+// form in the place of BeamAutomata - the same seven pointers plus the arena's two soft arrays (DecSoftAutomata's): edge_weight
+// [edges], the fp32 bias an edge adds to its token's log-probability, and default_next [states], where an OPEN state sends a
+// token without an edge (global, AUT_DEFAULT_FALLBACK as in the greedy form; -1: the state is closed).  Only the SOFT
+// instantiations take this type, so every other form keeps the argument block it had.
+struct BeamSoftAutomata : BeamAutomata {
+    const float* edge_weight;
+    const int* default_next;
+};
+
 // Start of a beam batch under token automata, beside beam_init_kernel (as automaton_init_kernel is to ngram_init_kernel):
 // every running beam in its crop's start state, every finished slot without one.
 __global__ __launch_bounds__(256) void beam_automaton_init_kernel(const int* __restrict__ base_of_row, int* __restrict__ state,
@@ -126,10 +136,26 @@ __global__ __launch_bounds__(64) void beam_init_kernel(BeamState bs, int K, int 
 //   a new running beam takes its candidate's state; a hypothesis that enters the finished set keeps the parent's state if it
 //     stopped on EOS (EOS moves nothing) and the candidate's if it stopped by length (the last token walks, as in greedy).
 //     The K old beam states and the K old hypothesis states are in LDS before any state is written - the argument of s_hist.
+// SOFT, the soft form (implies AUT; `aut` is a BeamSoftAutomata; every other form compiles to what it was).  transformers'
+//   generate(num_beams = K, sequence_bias = ...): the bias is a logits processor BEHIND the log_softmax, so it enters the
+//   ranked score, the running score and the token score, and nothing renormalises - not the greedy soft rule, which adds the
+//   weight before its softmax.  Three places differ from the AUT form.
+//   The mask of beam k: an OPEN state (default_next >= 0) starts from all ones with the EOS bit cleared unless it accepts,
+//     instead of zero plus the OR of the edge bits; the set AND and the bans follow as before.  Openness comes from the state
+//     in LDS: the branch is block-uniform.
+//   The row pass: gmax and log S are those of the raw row.  Per float4 a thread binary-searches the state's ascending edge
+//     tokens for its first column (dec_token_kernel's SOFT slab path) and keeps the weights of the edges inside it; the
+//     score is (((v - gmax) - log S) + w) + running, w skipped where it is 0, so a hard row keeps every bit.  The mask comes
+//     after: a weight never revives a masked token.
+//   The winners: the lane's binary search gives the edge, hence its target AND its weight - the token score is re-formed as
+//     ((v - gmax) - log S) + w, the very value ranked, so running' = s + running holds exactly.  A miss in an open state
+//     follows default_next; under AUT_DEFAULT_FALLBACK the token is looked up once more in the default state's edges.  A
+//     candidate that stopped on EOS and is carried on at score - 1e9 is no special case: EOS is never an edge, so an open
+//     state sends it along its default edge and a closed one to DEAD, as before.
 // LDS, static, at K = 4: ids and hypotheses 2 x 5 KiB, their log-probabilities 2 x 5 KiB (token form only), their trails
 // 2 x 1.25 KiB (trail form only), the mask 768 B, under 1 KiB of lists - 24 KiB of the 64 KiB a block may declare (the
 // automaton form's K + K + 2 K states and the base: 68 B more).
-template <typename T, int K, bool TOK = false, bool TRAIL = false, bool AUT = false>
+template <typename T, int K, bool TOK = false, bool TRAIL = false, bool AUT = false, bool SOFT = false>
 __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restrict__ slabs, int nslab, long long slab_stride,
                                                           const float* __restrict__ vbias, int V, DecState st, BeamState bs, int np,
                                                           const float* __restrict__ word, const float* __restrict__ type0,
@@ -137,9 +163,10 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
                                                           const float* __restrict__ beta, float* __restrict__ x_f32,
                                                           T* __restrict__ x_t, float eps, T* __restrict__ cache,
                                                           long long cache_batch_stride, uint8_t* __restrict__ cache8, float inv_sx8,
-                                                          BeamAutomata aut = BeamAutomata{}) {
+                                                          std::conditional_t<SOFT, BeamSoftAutomata, BeamAutomata> aut = {}) {
     static_assert(K >= 2 && K <= BEAM_MAX, "2 .. 4 beams");
     static_assert(!AUT || TOK, "the automaton form is a token form: its masks and the dead-candidate rule");
+    static_assert(!SOFT || AUT, "weights and default edges belong to an automaton");
     constexpr int D = 768, MW = 192, NC = 6, C2 = 2 * K;
     __shared__ int s_hist[K][BEAM_HIST];
     __shared__ int s_hyp[K][BEAM_HIST];
@@ -228,7 +255,31 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
         for (int j = 0; j < NC; ++j) mx = fmaxf(fmaxf(mx, fmaxf(a[j].x, a[j].y)), fmaxf(a[j].z, a[j].w));
         mx = wave_max(mx);
         if (lane == 0) s_red[wave] = mx;
-        if constexpr (AUT) {
+        int se0 = 0, se1 = 0;                         // SOFT: the edge range of beam k's state (empty: no automaton, or DEAD)
+        if constexpr (SOFT) {
+            if (s_abase >= 0) {                       // block-uniform: an open state allows every token, EOS iff it accepts
+                const int sk = s_ast[k];
+                const bool open = sk >= 0 && aut.default_next[sk] >= 0;
+                if (sk >= 0) { se0 = aut.edge_begin[sk]; se1 = aut.edge_begin[sk + 1]; }
+                if (tid < MW) s_mask[tid] = open ? 0xffffffffu : 0u;
+                __syncthreads();
+                if (open) {
+                    if (tid == 0 && !aut.accepting[sk] && (unsigned)st.eos_id < (unsigned)V)
+                        s_mask[st.eos_id >> 5] &= ~(1u << (st.eos_id & 31));
+                } else if (sk >= 0) {
+                    for (int i = se0 + tid; i < se1; i += 256) {
+                        const int x = aut.edge_token[i];
+                        if ((unsigned)x < (unsigned)V) atomicOr(&s_mask[x >> 5], 1u << (x & 31));
+                    }
+                    if (tid == 0 && aut.accepting[sk] && (unsigned)st.eos_id < (unsigned)V)
+                        atomicOr(&s_mask[st.eos_id >> 5], 1u << (st.eos_id & 31));
+                }
+                __syncthreads();
+                if (tid < MW) s_mask[tid] &= setw;
+            } else {
+                if (tid < MW) s_mask[tid] = setw;
+            }
+        } else if constexpr (AUT) {
             if (s_abase >= 0) {                       // block-uniform: A(state of beam k), then the crop's set
                 if (tid < MW) s_mask[tid] = 0u;
                 __syncthreads();
@@ -282,6 +333,30 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
             const int c = tid * 4 + j * 1024;
             const unsigned nib = (TOK || n > 0) ? (s_mask[c >> 5] >> (c & 31)) & 15u : 15u;
             const float v[4] = {a[j].x, a[j].y, a[j].z, a[j].w};
+            if constexpr (SOFT) {
+                // the weights of the state's edges inside this float4 (constant indices only: no register is indexed)
+                float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;
+                int lo = se0, hi = se1;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (aut.edge_token[mid] < c) lo = mid + 1; else hi = mid;
+                }
+                for (; lo < se1; ++lo) {
+                    const int d = aut.edge_token[lo] - c;
+                    if (d >= 4) break;
+                    const float wgt = aut.edge_weight[lo];
+                    if (d == 0) w0 = wgt; else if (d == 1) w1 = wgt; else if (d == 2) w2 = wgt; else w3 = wgt;
+                }
+                const float w[4] = {w0, w1, w2, w3};
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float lp = (v[q] - gmax) - logS;
+                    const float s = w[q] != 0.f ? lp + w[q] : lp;
+                    const float sc = ((nib >> q) & 1) ? s + bsc : -INFINITY;
+                    topn_insert(top, sc, k * V + c + q);
+                }
+                continue;
+            }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float sc = ((nib >> q) & 1) ? ((v[q] - gmax) - logS) + bsc : -INFINITY;
@@ -417,7 +492,27 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
                             const int mid = (lo + hi) >> 1;
                             if (aut.edge_token[mid] < c) lo = mid + 1; else hi = mid;
                         }
-                        if (lo < aut.edge_begin[sp + 1] && aut.edge_token[lo] == c) ns = aut.edge_next[lo];
+                        if (lo < aut.edge_begin[sp + 1] && aut.edge_token[lo] == c) {
+                            ns = aut.edge_next[lo];
+                            if constexpr (SOFT) {       // the edge's weight: the token score is the value the row pass ranked
+                                const float wgt = aut.edge_weight[lo];
+                                if (s_clive[tid] && wgt != 0.f) s_clp[tid] = lp + wgt;
+                            }
+                        } else if constexpr (SOFT) {    // a miss: along the default edge of an open state, DEAD in a closed one
+                            const int dn = aut.default_next[sp];
+                            if (dn >= 0) {
+                                ns = dn & AUT_DEFAULT_STATE;
+                                if (dn & AUT_DEFAULT_FALLBACK) {    // the token is walked from the default state: its edge, if it has one
+                                    const int f1 = aut.edge_begin[ns + 1];
+                                    int flo = aut.edge_begin[ns], fhi = f1;
+                                    while (flo < fhi) {
+                                        const int mid = (flo + fhi) >> 1;
+                                        if (aut.edge_token[mid] < c) flo = mid + 1; else fhi = mid;
+                                    }
+                                    if (flo < f1 && aut.edge_token[flo] == c) ns = aut.edge_next[flo];
+                                }
+                            }
+                        }
                     }
                 }
                 s_cst[tid] = ns;

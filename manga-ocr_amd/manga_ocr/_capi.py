@@ -259,6 +259,13 @@ SYMBOLS = {
     "mocr_recognize_device_beam_automaton": (C.c_int, [_P, _P, C.c_int32, C.POINTER(MocrBeamConfig), _P, _P, _P, _P, _P, _P, _P, _P]),
     "mocr_op_beam_select_automaton": (C.c_int, [_P, C.POINTER(MocrTokenArgs), C.POINTER(MocrBeamConfig), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                                 _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mocr_recognize_images_beam_soft": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.POINTER(MocrBeamConfig), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mocr_recognize_regions_beam_soft": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.POINTER(MocrRegion), C.c_int32,
+                                                   C.POINTER(MocrBeamConfig), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mocr_recognize_gray_host_beam_soft": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(MocrBeamConfig), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mocr_recognize_device_beam_soft": (C.c_int, [_P, _P, C.c_int32, C.POINTER(MocrBeamConfig), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mocr_op_beam_select_soft": (C.c_int, [_P, C.POINTER(MocrTokenArgs), C.POINTER(MocrBeamConfig), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mocr_beam_state_bytes": (C.c_int64, [_P]),
     "mocr_beam_token_state_bytes": (C.c_int64, [_P]),
     "mocr_beam_position_state_bytes": (C.c_int64, [_P]),

@@ -363,7 +363,7 @@ class Engine:
         return sets, ngram
 
     def _recognize(self, kind: str, n: int, lead, tail=(), *, beam, d_out=None, skip_empty: bool = False, beam_scores=False, beam_sets=None,
-                   beam_positions=False, beam_automata=None, beam_states=False, **req):
+                   beam_positions=False, beam_automata=None, beam_states=False, beam_soft=False, **req):
         """The one request path under recognize_images / _regions / _gray / _device.  ``kind``: the source kind as the C symbols
         spell it; ``n``: its number of sources; ``lead()``: (the call's leading C arguments, sources counted last; whatever they
         point into, kept until the call returns) - built only once the call is going to be made; ``tail``: what follows the
@@ -385,7 +385,9 @@ class Engine:
         ``beam_automata`` (one automaton handle for every crop, or one per crop, None / 0 = none) and ``beam_states`` (a host kind's
         flag; recognize_device: its ``d_out_beam_state`` buffer) belong to a beam call as well: with either in use the symbol is
         mocr_recognize_{kind}_beam_automaton - the _beam_positions call plus (automata, out_state), null where not asked - and
-        a host kind returns state int32 [n,K] as the LAST element, behind pos."""
+        a host kind returns state int32 [n,K] as the LAST element, behind pos.  ``beam_soft=True`` (a beam call, too): the symbol
+        is mocr_recognize_{kind}_beam_soft, the same argument list with soft handles allowed among ``beam_automata``
+        (include/mocr.h, "beam search under soft token automata"); without the flag every call is the one it was."""
         host = d_out is None
         automata, states = req.pop("automata", None), req.pop("states" if host else "d_out_state", None)
         if beam is not None and (automata is not None or (states is not None and states is not False)):
@@ -397,9 +399,11 @@ class Engine:
         wants_aut = beam_automata is not None or (beam_states is not None and beam_states is not False)
         if wants_aut and beam is None:
             raise ValueError("beam_automata / beam_states belong to a beam call: pass beam=")
+        if beam_soft and beam is None:
+            raise ValueError("beam_soft belongs to a beam call: pass beam=")
         if beam is not None:
             cfg, *out = self._beam_blocks(beam, n if host else 0, **req)
-            if wants_aut:
+            if wants_aut or beam_soft:
                 sets = self._sets(beam_sets, n) if beam_sets is not None else None
                 handles = self._automata(beam_automata, n) if beam_automata is not None else None
                 if host:
@@ -410,7 +414,7 @@ class Engine:
                     logp, pos, state = beam_scores, (beam_positions if wants_pos else None), (beam_states if beam_states is not False else None)
                 if n > 0 or not skip_empty:
                     args, keep = lead()
-                    self._check(getattr(self.lib, f"mocr_recognize_{kind}_beam_automaton")(
+                    self._check(getattr(self.lib, f"mocr_recognize_{kind}_beam_{'soft' if beam_soft else 'automaton'}")(
                         self._h, *args, *tail, C.byref(cfg), *map(_ptr, out if host else d_out), _ptr(logp), _ptr(sets), _ptr(pos),
                         _ptr(handles), _ptr(state)))
                 return (tuple(out) + tuple(x for x in (logp, pos, state) if x is not None)) if host else None
@@ -468,7 +472,7 @@ class Engine:
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False,
                          token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
                          beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False,
-                         beam_automata=None, beam_states: bool = False):
+                         beam_automata=None, beam_states: bool = False, beam_soft: bool = False):
         """Crops of any sizes (list of uint8 [h,w] / [h,w,3] arrays; `bgr`: 3-channel crops are in OpenCV order;
         `rotate`: per crop 0 / 1 (90 degrees clockwise) / 2 (counter-clockwise), applied on the device): luminance
         conversion and the Pillow-exact BILINEAR resize to 224x224 run on the device.
@@ -509,18 +513,21 @@ class Engine:
         crop walk it, each with its own state, so the hypotheses are the K best paths the automaton allows; ``beam_states`` adds
         a LAST element state int32 [n,K], the state behind every hypothesis' last token other than EOS (-1: no automaton, or an
         empty slot).  They combine with ``beam_scores`` / ``beam_sets`` / ``beam_positions``; ``automata`` / ``states`` stay
-        refused with ``beam``."""
+        refused with ``beam``.
+        ``beam_soft=True`` (only with ``beam``; include/mocr.h, "beam search under soft token automata"): ``beam_automata`` may
+        hold SOFT automata - their edge weights are added to the log-probabilities behind the log_softmax and enter the
+        hypotheses' scores (transformers' ``generate(num_beams=K, sequence_bias=...)``).  Without it a soft handle is refused."""
         def lead():
             descs, keep = self._image_descs(images, bgr, rotate)
             return (descs, len(keep)), keep
         return self._recognize("images", len(images), lead, beam=beam, beam_scores=beam_scores, beam_sets=beam_sets, beam_positions=beam_positions, skip_empty=True, scores=scores, alternatives=alternatives, token_sets=token_sets,
                                no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources, automata=automata, states=states,
-                               beam_automata=beam_automata, beam_states=beam_states)
+                               beam_automata=beam_automata, beam_states=beam_states, beam_soft=beam_soft)
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False,
                           token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
                           beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False,
-                         beam_automata=None, beam_states: bool = False):
+                         beam_automata=None, beam_states: bool = False, beam_soft: bool = False):
         """pages: list of uint8 [H,W,3] (or [H,W]) arrays; regions: iterable of (page_index, x, y, w, h) bounding
         rectangles.  Each page is uploaded once; the 8 %-padded, page-clipped crop of every region
         (``src/ui/main_window.py:9530-9540``) is cut on the device.  Returns (ids [n,max_len], lengths [n]);
@@ -547,7 +554,7 @@ class Engine:
             return (descs, len(keep), arr, len(regs)), keep
         return self._recognize("regions", len(regs), lead, beam=beam, beam_scores=beam_scores, beam_sets=beam_sets, beam_positions=beam_positions, skip_empty=True, scores=scores, alternatives=alternatives, token_sets=token_sets,
                                no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources, automata=automata, states=states,
-                               beam_automata=beam_automata, beam_states=beam_states)
+                               beam_automata=beam_automata, beam_states=beam_states, beam_soft=beam_soft)
 
     def graph_count(self) -> int:
         return int(self.lib.mocr_graph_count(self._h))
@@ -597,7 +604,7 @@ class Engine:
     def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None, d_out_alt_ids=None, d_out_alt_logp=None, *,
                          token_sets=None, no_repeat_ngram=None, d_out_pos=None, prefixes=None, sources=None, beam=None,
                          d_out_score=None, d_out_beam_logp=None, beam_sets=None, d_out_beam_pos=None, automata=None,
-                         d_out_state=None, beam_automata=None, d_out_beam_state=None) -> None:
+                         d_out_state=None, beam_automata=None, d_out_beam_state=None, beam_soft: bool = False) -> None:
         """Asynchronous; all are device buffers (torch CUDA tensors or raw addresses).  ``d_out_logp`` (float32
         [n,max_len]): also the token log-probabilities.  ``d_out_alt_ids`` (int32) with ``d_out_alt_logp`` (float32), both
         [n,max_len,4]: also the token alternatives.  ``token_sets``: a set handle for every crop, or one per crop (host values).
@@ -610,11 +617,13 @@ class Engine:
         [n,K,max_len]: also the hypotheses' token scores), ``beam_sets`` (host values) and ``d_out_beam_pos`` (float32 [n,K,max_len,5]: also
         the hypotheses' token positions), as for recognize_images.  ``automata`` (host values): a token automaton for every row, or
         one per row; ``d_out_state`` (int32 [rows]): also the rows' final states.  ``beam_automata`` (host values, only with ``beam``): a
-        token automaton for every crop, or one per crop; ``d_out_beam_state`` (int32 [n,K]): also the hypotheses' states."""
+        token automaton for every crop, or one per crop; ``d_out_beam_state`` (int32 [n,K]): also the hypotheses' states;
+        ``beam_soft=True``: the automata may be soft (see recognize_images)."""
         self._recognize("device", n, lambda: ((_ptr(d_gray), n), None), beam=beam, beam_scores=d_out_beam_logp, beam_sets=beam_sets, beam_positions=d_out_beam_pos, d_out=(d_out_ids, d_out_len, d_out_score), d_out_logp=d_out_logp,
                         d_out_alt_ids=d_out_alt_ids, d_out_alt_logp=d_out_alt_logp, token_sets=token_sets, no_repeat_ngram=no_repeat_ngram,
                         d_out_pos=d_out_pos, prefixes=prefixes, sources=sources, automata=automata, d_out_state=d_out_state,
-                        beam_automata=beam_automata, beam_states=d_out_beam_state if d_out_beam_state is not None else False)
+                        beam_automata=beam_automata, beam_states=d_out_beam_state if d_out_beam_state is not None else False,
+                        beam_soft=beam_soft)
 
     def set_generate_max_length(self, max_len: int) -> None:
         self._check(self.lib.mocr_set_generate_max_length(self._h, int(max_len)))
@@ -622,7 +631,7 @@ class Engine:
     def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False, alternatives: bool = False,
                        token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
                        beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False,
-                         beam_automata=None, beam_states: bool = False):
+                         beam_automata=None, beam_states: bool = False, beam_soft: bool = False):
         """Luminance planes uint8 [n,224,224] (host), generate(max_length) ``max_len``; the keywords as for recognize_images
         (``sources``: one plane index per output row; ``beam``: (ids [n,K,max_len], lengths [n,K], scores [n,K]), with ``beam_scores`` also
         logp [n,K,max_len]; ``beam_sets``: one set per plane; ``beam_positions``: also pos [n,K,max_len,5], last)."""
@@ -631,7 +640,7 @@ class Engine:
                                beam_sets=beam_sets, beam_positions=beam_positions, scores=scores,
                                alternatives=alternatives, token_sets=token_sets, no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes,
                                sources=sources, automata=automata, states=states,
-                               beam_automata=beam_automata, beam_states=beam_states)
+                               beam_automata=beam_automata, beam_states=beam_states, beam_soft=beam_soft)
 
     # ------------------------------------------------------------------ test hooks
     def encode(self, d_gray, n: int) -> np.ndarray:
@@ -837,6 +846,21 @@ class Engine:
             _ptr(d_hyp_len), _ptr(d_hyp_score), _ptr(d_heuristic_open), _ptr(d_beam_logp), _ptr(d_hyp_logp), _ptr(d_tok_mask),
             _ptr(d_set_of_row), _ptr(d_beam_trail), _ptr(d_hyp_trail), _ptr(d_edge_begin), _ptr(d_edge_token), _ptr(d_edge_next),
             _ptr(d_accepting), _ptr(d_aut_base_of_row), _ptr(d_aut_state), _ptr(d_hyp_state)))
+
+    def op_beam_select_soft(self, beam: BeamConfig, d_beam_score, d_parent, d_hyp_ids, d_hyp_len, d_hyp_score, d_heuristic_open,
+                            d_beam_logp=None, d_hyp_logp=None, d_tok_mask=None, d_set_of_row=None, d_beam_trail=None,
+                            d_hyp_trail=None, d_edge_begin=None, d_edge_token=None, d_edge_next=None, d_accepting=None,
+                            d_aut_base_of_row=None, d_aut_state=None, d_hyp_state=None, d_edge_weight=None, d_default_next=None,
+                            **kw) -> None:
+        """The selection in its SOFT form (include/mocr.h mocr_op_beam_select_soft): op_beam_select_automaton plus the edges'
+        weights float32 [edges] and the states' default edges int32 [states] (global numbers, -1: closed), both or neither;
+        keywords: the fields of mocr_token_args."""
+        cfg = beam.as_struct()
+        self._check(self.lib.mocr_op_beam_select_soft(
+            self._h, self._args(_capi.MocrTokenArgs, kw), C.byref(cfg), _ptr(d_beam_score), _ptr(d_parent), _ptr(d_hyp_ids),
+            _ptr(d_hyp_len), _ptr(d_hyp_score), _ptr(d_heuristic_open), _ptr(d_beam_logp), _ptr(d_hyp_logp), _ptr(d_tok_mask),
+            _ptr(d_set_of_row), _ptr(d_beam_trail), _ptr(d_hyp_trail), _ptr(d_edge_begin), _ptr(d_edge_token), _ptr(d_edge_next),
+            _ptr(d_accepting), _ptr(d_aut_base_of_row), _ptr(d_aut_state), _ptr(d_hyp_state), _ptr(d_edge_weight), _ptr(d_default_next)))
 
     def op_beam_permute(self, d_cache, layers: int, layer_stride: int, row_stride: int, segs: int, seg_stride: int, pos_bytes: int,
                         K: int, d_parent, d_rowmap, d_finished, d_step, n_slots: int, max_pos: int) -> None:

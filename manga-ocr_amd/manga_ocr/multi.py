@@ -459,8 +459,12 @@ class MultiGpuEngine:
                         streak[r] = 0
                         continue
                     stats["redealt"] += 1
-                    streak[r] += 1
                     _lo, _hi, att, _av, deaths = ent
+                    # only a chunk's FIRST failure counts against the child: a chunk that has failed before, and every piece of
+                    # it, carries a bad crop - wherever the pieces land, they say nothing about the child that meets them
+                    # (else one cursed crop drops whichever child happens to be dealt its half four times over)
+                    if att == 0:
+                        streak[r] += 1
                     if att == 0 and len(out) > 1:              # once more, on another child
                         queue.appendleft((lo, hi, 1, r, deaths))
                     elif hi - lo > 1:                          # still failing: halve it until the bad crop stands alone

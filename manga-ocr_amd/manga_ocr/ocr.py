@@ -97,7 +97,8 @@ class Lexicon(NamedTuple):
     entries: dict
     texts: tuple
     # a soft automaton (:meth:`MangaOcr.sequence_bias`, :meth:`MangaOcr.glossary`, :meth:`MangaOcr.automaton` with weights or
-    # default edges): it biases, it does not confine - ``accepted`` / ``entry`` stay None and ``match`` refuses it
+    # default edges): it biases, it does not confine - ``accepted`` / ``entry`` stay None and ``match`` refuses it (``search``
+    # takes it: beam search with the biases inside the hypotheses' scores)
     soft: bool = False
     spellings: tuple = ()       # glossary: the token ids of every entry, for :meth:`find`
 
@@ -384,6 +385,7 @@ class _Request(NamedTuple):
     automaton: int = 0                  # token automaton handle (``lexicon=``), 0: none; such a caller gets its final state, last
     beam_automaton: int = 0             # a beam request (``match``): the automaton its beams walk, 0: none; such a caller gets its
                                         # hypotheses' states [K], last
+    beam_soft: bool = False             # ... and that automaton may be soft (``search``): the batch makes the *_beam_soft call
 
 
 class _Batcher:
@@ -406,7 +408,8 @@ class _Batcher:
     hypotheses' token positions (``beam_positions``): only a beam batch with such a request passes ``beam_positions=True``, and
     only a caller that asked gets pos [K, max_len, 5] as its last element.  And for a beam request's token automaton
     (``beam_automaton``, the ``match`` methods): only a beam batch with such a request passes ``beam_automata=`` (one handle per
-    crop, 0 for the others) and ``beam_states=True``, and only such a caller gets state [K], behind everything else."""
+    crop, 0 for the others) and ``beam_states=True``, and only such a caller gets state [K], behind everything else.  A
+    ``search`` request marks its automaton ``beam_soft``: only a beam batch with such a request passes ``beam_soft=True``."""
 
     def __init__(self, engine: Engine, max_batch: int, timeout_ms: float):
         self.engine, self.max_batch, self.timeout = engine, max_batch, timeout_ms / 1000.0
@@ -419,14 +422,14 @@ class _Batcher:
     def submit(self, gray: np.ndarray, scored: bool = False, alternatives: bool = False, token_set: int = 0,
                no_repeat_ngram: int = 0, positions: bool = False, prefix=None, beam: Optional[BeamConfig] = None,
                beam_scores: bool = False, beam_set: int = 0, beam_positions: bool = False, automaton: int = 0,
-               beam_automaton: int = 0) -> Future:
+               beam_automaton: int = 0, beam_soft: bool = False) -> Future:
         f: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
             self._q.append(_Request(gray, f, bool(scored or alternatives), bool(alternatives), bool(positions), int(token_set), int(no_repeat_ngram),
                                     tuple(prefix) if prefix else None, beam, bool(beam_scores), int(beam_set), bool(beam_positions), int(automaton),
-                                    int(beam_automaton)))
+                                    int(beam_automaton), bool(beam_soft)))
             self._cv.notify()
         return f
 
@@ -461,6 +464,8 @@ class _Batcher:
                     if any(r.beam_automaton for r in batch):
                         bkw["beam_automata"] = [r.beam_automaton for r in batch]
                         bkw["beam_states"] = True
+                    if any(r.beam_soft for r in batch):
+                        bkw["beam_soft"] = True
                     ids, lens, sc, *rest = self.engine.recognize_images([r.gray for r in batch], beam=head, **bkw)
                     logp = rest.pop(0) if bkw.get("beam_scores") else None
                     pos = rest.pop(0) if bkw.get("beam_positions") else None
@@ -949,7 +954,9 @@ class MangaOcr:
         on from there (include/mocr.h, "forced prefixes").  ``lexicon``: a :class:`Lexicon` of :meth:`lexicon` / :meth:`automaton`
         for all crops, or one (or None) per crop - the row is decoded under that token automaton (include/mocr.h, "token
         automata"); the scored kinds then fill ``Recognition.state`` / ``accepted`` / ``entry``.  Every greedy ``recognize*``
-        method takes all four."""
+        method takes all four.  A call with ``lexicon=`` decodes GREEDILY even when this MangaOcr was built with ``num_beams=``:
+        :meth:`match` searches a lexicon with beams, :meth:`search` a glossary or ``sequence_bias`` (the biases then count inside
+        the hypotheses' scores)."""
         return self._run(lambda: _Images(list(crops), bgr, rotate), _TEXT, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
 
     def recognize(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> str:
@@ -1152,12 +1159,14 @@ class MangaOcr:
             raise ValueError("this MangaOcr decodes with beam search (num_beams=): allowed= / no_repeat_ngram= / prefix= do not combine with it")
         return True
 
-    def _beam(self, src, beam: BeamConfig, token_scores: bool = False, allowed=None, positions: bool = False, lexicons=None):
+    def _beam(self, src, beam: BeamConfig, token_scores: bool = False, allowed=None, positions: bool = False, lexicons=None,
+              soft: bool = False):
         """(ids [n, K, max_len], lengths [n, K], scores [n, K]) of a source: one crop through the batcher, any number of crops
         or regions max_batch // K of them per engine call (a beam request fits one batch: n * K <= max_batch).  With
         ``token_scores`` also logp [n, K, max_len]; ``allowed``: the crops' token sets; with ``positions`` also, last, pos
         [n, K, max_len, 5].  ``lexicons`` (the ``match`` methods): one Lexicon or None per crop - the beams walk the crops'
-        automata, and the hypotheses' states [n, K] come behind everything else.  The engine is passed only what was asked."""
+        automata, and the hypotheses' states [n, K] come behind everything else; ``soft`` (the ``search`` methods): those automata
+        may be soft, the call is the engine's ``beam_soft=True`` one.  The engine is passed only what was asked."""
         self._require("BEAM")
         if positions:
             self._require("BEAM_POSITIONS")
@@ -1171,6 +1180,8 @@ class MangaOcr:
                 kw["beam_set"] = hs[0]
             if lexicons is not None and lexicons[0] is not None:
                 kw["beam_automaton"] = lexicons[0].handle
+                if soft:
+                    kw["beam_soft"] = True
             out = tuple(a[None] for a in self._batcher.submit(src.pixels, beam=beam, **kw).result())
             if lexicons is not None and lexicons[0] is None:        # (no automaton: the batcher made the call it always made)
                 out += (np.full(out[1].shape, -1, dtype=np.int32),)
@@ -1180,7 +1191,8 @@ class MangaOcr:
         step = max(1, int(self.max_batch) // beam.num_beams)
         aut = None if lexicons is None else [0 if x is None else x.handle for x in lexicons]
         kw = lambda a: dict(**flags, **(dict(beam_sets=hs[a:a + step]) if hs is not None else {}),
-                            **(dict(beam_automata=aut[a:a + step], beam_states=True) if aut is not None else {}))
+                            **(dict(beam_automata=aut[a:a + step], beam_states=True) if aut is not None else {}),
+                            **(dict(beam_soft=True) if soft and aut is not None else {}))
         parts = [src.call(self, a, a + step, beam=beam, **kw(a)) for a in range(0, src.n, step)] or [src.call(self, beam=beam, **kw(0))]
         return tuple(np.concatenate([p[i] for p in parts]) for i in range(3 + bool(token_scores) + bool(positions) + (aut is not None)))
 
@@ -1263,10 +1275,11 @@ class MangaOcr:
 
     # ------------------------------------------------------------------ beam search under a lexicon
     def _run_match(self, source, lexicon, k, length_penalty, early_stopping, no_repeat_ngram, token_scores, allowed, positions,
-                   raw) -> List[List[Recognition]]:
+                   raw, soft: bool = False) -> List[List[Recognition]]:
         """the ``match*`` methods: the refusals (several devices), the configuration, the inputs, the lexicons; ONE beam search per
         crop whose K beams walk the crop's automaton; per crop the hypotheses marked with ``state`` / ``accepted`` / ``entry``,
-        and unless ``raw`` only the distinct accepted ones that are no padding beam's duplicate"""
+        and unless ``raw`` only the distinct accepted ones that are no padding beam's duplicate.  ``soft`` (the ``search*``
+        methods, always ``raw``): the lexicons may be soft, and a soft one leaves ``accepted`` / ``entry`` None"""
         self._require("BEAM")
         self._require("LEXICON")
         if lexicon is None:
@@ -1276,9 +1289,10 @@ class MangaOcr:
         if positions and isinstance(src, _Regions):
             src = src.with_rects()
         lex = _lexicons(lexicon, src.n) or [None] * src.n
-        if any(x is not None and x.soft for x in lex):
-            raise ValueError("match: beam search takes no soft automaton (sequence_bias / glossary / weights): use recognize*(lexicon=)")
-        ids, lens, sc, *rest = self._beam(src, beam, bool(token_scores), allowed, bool(positions), lex)
+        if not soft and any(x is not None and x.soft for x in lex):
+            raise ValueError("match: it ranks what a lexicon ALLOWS and takes no soft automaton (sequence_bias / glossary / weights): "
+                             "search() / search_batch() / search_bgr() / search_regions() run beam search under one")
+        ids, lens, sc, *rest = self._beam(src, beam, bool(token_scores), allowed, bool(positions), lex, soft)
         logp = rest.pop(0) if token_scores else None
         pos = rest.pop(0) if positions else None
         state = rest.pop(0)
@@ -1294,6 +1308,9 @@ class MangaOcr:
             marked = []
             for j, h in zip(live, hyps):
                 st = int(state[i, j])
+                if x is not None and x.soft:        # a soft automaton confines nothing: there is nothing to accept
+                    marked.append(replace(h, state=st, accepted=None, entry=None))
+                    continue
                 ok = x is not None and len(h.ids) > 1 and int(h.ids[-1]) == eos and st in x.accepting
                 marked.append(replace(h, state=st, accepted=bool(ok), entry=x.entries.get(st) if ok else None))
             if not raw:
@@ -1343,6 +1360,45 @@ class MangaOcr:
         """:meth:`match_batch` on regions of BGR pages, as ``recognize_regions`` takes them: [] for a sliver."""
         return self._run_match(lambda: _Regions(list(pages_bgr), list(regions)), lexicon, k, length_penalty, early_stopping,
                                no_repeat_ngram, token_scores, allowed, positions, raw)
+
+    # ------------------------------------------------------------------ beam search under a glossary
+    def search(self, img_or_path, bias, k: int = 4, *, length_penalty: float = 1.0, early_stopping=False, no_repeat_ngram: int = 0,
+               token_scores: bool = False, allowed=None, positions: bool = False) -> List[Recognition]:
+        """Beam search for one crop with a glossary's preferences INSIDE the hypotheses' scores (include/mocr.h, "beam search
+        under soft token automata"): transformers' ``generate(num_beams=k, sequence_bias=...)``.  ``bias``: a Lexicon of
+        :meth:`glossary` / :meth:`sequence_bias` / :meth:`automaton` with ``weights=`` or ``default=`` (a hard Lexicon is
+        allowed, and then confines as in :meth:`match`).  An edge's weight is added to its token's log-probability behind the
+        log_softmax - nothing renormalises, unlike the greedy ``lexicon=`` - so a cast list re-ranks whole hypotheses instead of
+        one token at a time.  Returns the finished hypotheses as the engine delivered them, best first, each with
+        ``sequence_score`` (the biases included) and ``state``; ``accepted`` / ``entry`` are None under a soft Lexicon and
+        :meth:`match`'s under a hard one.  ``Lexicon.find(hypothesis.ids)`` lists the glossary entries a hypothesis holds.
+        ``k`` 2 .. 4; ``length_penalty`` / ``early_stopping`` / ``no_repeat_ngram`` / ``token_scores`` (the biased values, whose
+        sum over ``(len - 1) ** length_penalty`` is the score) / ``allowed`` / ``positions``: as for :meth:`recognize_beam`.
+        A MangaOcr built with ``num_beams=`` still decodes a plain ``recognize(..., lexicon=)`` greedily: this is the call that
+        searches with beams under a glossary.  Goes through the batcher; only requests of one beam configuration share a batch."""
+        return self._run_match(self._one(img_or_path), bias, k, length_penalty, early_stopping, no_repeat_ngram, token_scores, allowed,
+                               positions, True, True)[0]
+
+    def search_batch(self, images: Sequence, bias, k: int = 4, *, length_penalty: float = 1.0, early_stopping=False,
+                     no_repeat_ngram: int = 0, token_scores: bool = False, allowed=None, positions: bool = False) -> List[List[Recognition]]:
+        """:meth:`search` for many crops: one list per crop (``bias``: one Lexicon for all, or one Lexicon or None per crop - a crop
+        without one is searched freely)."""
+        return self._run_match(self._pil(images), bias, k, length_penalty, early_stopping, no_repeat_ngram, token_scores, allowed, positions,
+                               True, True)
+
+    def search_bgr(self, crops_bgr: Sequence[np.ndarray], bias, orientations: Optional[Sequence[str]] = None, k: int = 4, *,
+                   length_penalty: float = 1.0, early_stopping=False, no_repeat_ngram: int = 0, token_scores: bool = False, allowed=None,
+                   positions: bool = False) -> List[List[Recognition]]:
+        """:meth:`search_batch` on BGR crops with their orientation settings, as ``recognize_bgr`` takes them."""
+        return self._run_match(lambda: self._bgr("search_bgr", crops_bgr, orientations), bias, k, length_penalty, early_stopping,
+                               no_repeat_ngram, token_scores, allowed, positions, True, True)
+
+    def search_regions(self, pages_bgr: Sequence[np.ndarray], regions, bias, k: int = 4, *, length_penalty: float = 1.0,
+                       early_stopping=False, no_repeat_ngram: int = 0, token_scores: bool = False, allowed=None,
+                       positions: bool = False) -> List[List[Recognition]]:
+        """:meth:`search_batch` on regions of BGR pages, as ``recognize_regions`` takes them: [] for a sliver."""
+        return self._run_match(lambda: _Regions(list(pages_bgr), list(regions)), bias, k, length_penalty, early_stopping,
+                               no_repeat_ngram, token_scores, allowed, positions, True, True)
 
     def recognize_page(self, page_bgr: np.ndarray, regions):
         """``_collect_manga_detections`` for one page: ``regions`` = the detector's (text, polygon) pairs."""

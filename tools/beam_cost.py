@@ -18,10 +18,17 @@
         automaton").  The lines of (i), (v), (viii) and (ix) are also appended to --automaton-out (by default
         profiles/beam_automaton_cost.jsonl): on the parent commit's build, which has no (viii) / (ix), (i) and (v) are the
         yardsticks - they launch what they launched and must lie within that build's own min .. max,
+  (x)   the beam batch of (i) with every crop under a glossary of 8,000 random names of 2 to 12 tokens over 200 tokens in
+        MangaOcr.glossary's compact (fallback) form, bonus 2, and (xi) with every crop in ONE state of 6,143 weighted edges -
+        the universal automaton with a weight on every edge, the worst case of the row pass (include/mocr.h "beam search under
+        soft token automata").  The lines of (i), (v), (viii), (x) and (xi) are also appended to --soft-out (by default
+        profiles/beam_soft_cost.jsonl): on the parent commit's build, which has no (x) / (xi), (i), (v) and (viii) are the
+        yardsticks,
 and, with --profile, the two new kernels' times from the engine's per-kernel profile at 400 rows.
 
     python tools/beam_cost.py [--tree DIR] [--label NAME] [--crops 64] [--beams 4] [--max-len 32] [--reps 7] [--profile]
                               [--positions-out profiles/beam_positions_cost.jsonl] [--automaton-out profiles/beam_automaton_cost.jsonl]
+                              [--soft-out profiles/beam_soft_cost.jsonl]
 
 --tree: the checkout whose package and library are measured (default: this one); a built checkout of the parent commit runs
 (ii) and (iii) alone - they are the yardsticks and must agree between the two builds within their own run-to-run spread.
@@ -47,6 +54,8 @@ def main():
                     help="append the plain beam line and the positions lines to this file ('' = nowhere)")
     ap.add_argument("--automaton-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "beam_automaton_cost.jsonl"),
                     help="append the plain beam line, the 40-token-set line and the automaton lines to this file ('' = nowhere)")
+    ap.add_argument("--soft-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "beam_soft_cost.jsonl"),
+                    help="append the plain beam line, the 40-token-set line, the trie line and the two soft lines to this file ('' = nowhere)")
     args = ap.parse_args()
     tree = os.path.abspath(args.tree)
     for p in (tree, os.path.join(tree, "manga-ocr_amd")):
@@ -91,6 +100,22 @@ def main():
             uni = eng.automaton(*pack_automaton({0: {t: 0 for t in range(DEFAULT_SPEC.vocab) if t != DEFAULT_SPEC.eos_id}}, [0]))
             forms.append(("beam_automaton_trie8000", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg, beam_automata=trie, beam_states=True)))
             forms.append(("beam_automaton_universal", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg, beam_automata=uni, beam_states=True)))
+        if hasattr(eng, "op_beam_select_soft"):         # (the parent commit has no beam search under soft automata)
+            from manga_ocr.text import bias_automaton, pack_automaton
+            rs = np.random.RandomState(8001)
+            seqs = {}
+            for _ in range(8000):       # MangaOcr.glossary's sequences: every prefix of two or more tokens of a name, bonus 2
+                name = tuple(int(t) + (1 if int(t) >= DEFAULT_SPEC.eos_id else 0) for t in rs.randint(5, 205, size=rs.randint(2, 13)))
+                for n in range(2, len(name) + 1):
+                    seqs[name[:n]] = 2.0
+            trans, weights = bias_automaton(seqs, compact=True)
+            gloss = eng.automaton(*pack_automaton(trans, set(trans), weights=weights, default=0, fallback=True))
+            every = {t: 0 for t in range(DEFAULT_SPEC.vocab) if t != DEFAULT_SPEC.eos_id}
+            heavy = eng.automaton(*pack_automaton({0: every}, [0], weights={0: {t: ((t * 37) % 17 - 8) / 8.0 or 0.125 for t in every}}))
+            forms.append(("beam_soft_glossary8000", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg, beam_automata=gloss, beam_states=True,
+                                                                                beam_soft=True)))
+            forms.append(("beam_soft_weighted6143", lambda: eng.recognize_gray(gray, args.max_len, beam=cfg, beam_automata=heavy, beam_states=True,
+                                                                                beam_soft=True)))
     for form, call in forms:
         for _ in range(2):
             call()
@@ -110,6 +135,10 @@ def main():
             os.makedirs(os.path.dirname(os.path.abspath(args.automaton_out)), exist_ok=True)
             with open(args.automaton_out, "a", encoding="utf-8") as f:
                 f.write(line + "\n")
+        if args.soft_out and form in ("beam", "beam_token_scores_set40", "beam_automaton_trie8000", "beam_soft_glossary8000", "beam_soft_weighted6143"):
+            os.makedirs(os.path.dirname(os.path.abspath(args.soft_out)), exist_ok=True)
+            with open(args.soft_out, "a", encoding="utf-8") as f:
+                f.write(line + "\n")
     eng.close()
     if args.profile and beam is not None:
         n = 400 // K
@@ -117,13 +146,18 @@ def main():
         g = np.random.RandomState(7).randint(0, 256, size=(n, 224, 224), dtype=np.uint8)
         kws = [{}] + ([dict(beam_scores=True)] if hasattr(eng, "beam_token_state_bytes") else [])
         kws += [dict(beam_positions=True)] if hasattr(eng, "beam_position_state_bytes") else []
+        if hasattr(eng, "op_beam_select_soft"):         # the soft selection, every crop in the state of 6,143 weighted edges
+            from manga_ocr.text import pack_automaton
+            every = {t: 0 for t in range(DEFAULT_SPEC.vocab) if t != DEFAULT_SPEC.eos_id}
+            heavy = eng.automaton(*pack_automaton({0: every}, [0], weights={0: {t: ((t * 37) % 17 - 8) / 8.0 or 0.125 for t in every}}))
+            kws += [dict(beam_automata=heavy, beam_states=True, beam_soft=True)]
         for kw in kws:
             eng.recognize_gray(g, args.max_len, beam=cfg, **kw)
             eng.profile_enable(True)
             eng.profile_reset()
             eng.recognize_gray(g, args.max_len, beam=cfg, **kw)
             for s in eng.profile_get():
-                if s["name"] in ("beam_select", "beam_select_tok", "beam_permute", "beam_init", "dec_attn_self", "latent_self", "gemm_dec_vocab",
+                if s["name"] in ("beam_select", "beam_select_tok", "beam_select_am", "beam_select_sw", "beam_permute", "beam_init", "dec_attn_self", "latent_self", "gemm_dec_vocab",
                                  "gemm_pos_k", "gemm_pos_q", "attn_positions"):
                     print(json.dumps(dict(what="beam_kernels", build=args.label, rows=n * K, max_len=args.max_len, kernel=s["name"],
                                           launches=s["launches"], total_ms=round(s["total_ms"], 3),
