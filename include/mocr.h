@@ -499,6 +499,47 @@ int mocr_recognize_gray_host_automaton(mocr_engine* e, const uint8_t* gray, int3
                                        const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld, const int32_t* automata,
                                        int32_t* out_state);
 
+/* ---- repetition penalty (transformers' generate(repetition_penalty=p) under greedy search) --------------------------------
+ * The *_penalty entry points: the *_automaton twins plus `penalty`, a HOST float32 array [n_rows] with one p per row (null:
+ * every row 1 - then the call IS the *_automaton call).  Each p is finite and > 0 (anything else: MOCR_ERR_ARG before any
+ * work); p < 1 rewards repeats and is allowed, as in transformers; p = 1 is off.
+ *   The rule is RepetitionPenaltyLogitsProcessor's, per row.  At the step that chooses ids[t + 1], `seen` is the set of ids at
+ *     positions 0 .. t of the row: the start token, forced prefix tokens and chosen tokens.  For every token c in `seen`, with v
+ *     the fp32 logit: v' = v < 0 ? v * p : v / p - an IEEE fp32 multiply or divide, never a reciprocal; v == 0 divides.
+ *   Order with the other processors is transformers': sequence_bias (a soft automaton's edge weight) first, then the penalty,
+ *     then the bans - v is (acc + edge weight) + bias, and the token sets, n-gram bans and automaton sets turn a column into
+ *     -inf afterwards.
+ *   Everything the step derives from the logits sees v': the arg-max (equal values: the lowest id), the token scores - the
+ *     log_softmax of the penalised, masked row -, the four alternatives, and the value a forced prefix token scores.  Prefix
+ *     steps are causal: step t sees the tokens before it.  mocr_decode_logits stays raw.
+ *   Bit identity: v * 1 and v / 1 are exact, so a row with p = 1 beside penalised rows returns the ids, scores and
+ *     alternatives it returns in a batch without the array; a batch in which every p is 1 launches exactly what it launched.
+ *   How: by ROW like ids, seen_mask uint32 [rows][192] and penalty_of_row float [rows] (772 B a row and lane, allocated by the
+ *     first batch with a p != 1; the same batch allocates the automaton arena and its soft part if no automaton has yet).  The
+ *     fused LM head's PEN form (profile name gemm_dec_vocab_rp) and the token kernel's (dec_token*_rp) are SOFT forms too: rows
+ *     without an automaton are in MOCR_STATE_NONE and add nothing.
+ *   Out of scope: beam search - a beam request cannot carry a penalty (under beams transformers penalises log-probabilities). */
+int mocr_recognize_images_penalty(mocr_engine* e, const mocr_image* images, int32_t n_images, int32_t n_rows, const int32_t* source,
+                                  int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
+                                  const int32_t* sets, const int32_t* ngram, float* out_pos, const int32_t* prefix,
+                                  const int32_t* prefix_len, int32_t prefix_ld, const int32_t* automata, int32_t* out_state,
+                                  const float* penalty);
+int mocr_recognize_regions_penalty(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                   int32_t n_regions, int32_t n_rows, const int32_t* source, int32_t* out_ids, int32_t* out_len,
+                                   float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets, const int32_t* ngram,
+                                   float* out_pos, const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld,
+                                   const int32_t* automata, int32_t* out_state, const float* penalty);
+int mocr_recognize_device_penalty(mocr_engine* e, const void* d_gray, int32_t n_planes, int32_t n_rows, const int32_t* source,
+                                  void* d_out_ids, void* d_out_len, void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp,
+                                  const int32_t* sets, const int32_t* ngram, void* d_out_pos, const int32_t* prefix,
+                                  const int32_t* prefix_len, int32_t prefix_ld, const int32_t* automata, void* d_out_state,
+                                  const float* penalty);
+int mocr_recognize_gray_host_penalty(mocr_engine* e, const uint8_t* gray, int32_t n_planes, int32_t n_rows, const int32_t* source,
+                                     int32_t max_len_override, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                     float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos,
+                                     const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld, const int32_t* automata,
+                                     int32_t* out_state, const float* penalty);
+
 /* Preprocessing only (test hook): out_gray [n, image_size, image_size] uint8 (host) = the plane the encoder sees
  * in each of its three equal input channels before the 1/255 and (x - 0.5)/0.5 scaling. */
 int mocr_preprocess(mocr_engine* e, const mocr_image* images, int32_t n, uint8_t* out_gray);
@@ -813,6 +854,23 @@ int mocr_op_dec_token_soft(mocr_engine* e, const mocr_token_args* a, const float
                            const int32_t* d_edge_begin, const int32_t* d_edge_token, const int32_t* d_edge_next,
                            const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state,
                            const float* d_edge_weight, const int32_t* d_default_next);
+/* The token step with a repetition penalty: mocr_op_dec_token_soft plus d_seen_mask uint32 [rows][192] and d_penalty_of_row
+ * float32 [rows], both by ROW and both or neither; they come with the four per-row mask arrays (d_row_mask ...).  Slab path:
+ * the thread's logits whose bit is set are penalised after the edge weights and before the masking.  Both paths: the token
+ * stored for a row that was unfinished before the step has its bit set in d_seen_mask.  Both NULL is mocr_op_dec_token_soft;
+ * the eight automaton arrays may all be NULL beside them (a penalty without any automaton), and an automaton beside them
+ * brings d_edge_weight and d_default_next. */
+int mocr_op_dec_token_penalty(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                              const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
+                              const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
+                              const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row,
+                              const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld, const float* d_tgt_val,
+                              const int32_t* d_edge_begin, const int32_t* d_edge_token, const int32_t* d_edge_next,
+                              const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state,
+                              const float* d_edge_weight, const int32_t* d_default_next, uint32_t* d_seen_mask,
+                              const float* d_penalty_of_row);
+/* The start of a batch with a repetition penalty: d_seen_mask [rows][vocab / 32] = the start token's bit alone. */
+int mocr_op_penalty_init(mocr_engine* e, uint32_t* d_seen_mask, int32_t rows);
 /* The start of a batch with soft token automata: mocr_op_automaton_init, where a start state with d_default_next >= 0 is open.
  * d_default_next NULL is mocr_op_automaton_init. */
 int mocr_op_automaton_init_soft(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
@@ -892,6 +950,16 @@ int mocr_op_gemm_argmax_soft(mocr_engine* e, const void* dA, const void* dW, con
                              int32_t K, int32_t tile, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
                              const int32_t* d_rowmap, const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld,
                              const int32_t* d_step, float* d_tgt_val, const mocr_soft_tables* soft);
+/* The LM head with a repetition penalty: mocr_op_gemm_argmax_soft plus d_seen_mask uint32 [rows][N / 32] and d_penalty_of_row
+ * float32 [rows], both by ROW (read through d_rowmap) and both or neither; needs d_tok_mask.  A column whose bit is set takes
+ * v < 0 ? v * p : v / p of v = (acc + edge weight) + bias before the mask applies, in the arg-max, the exp sums, the four best
+ * and d_tgt_val.  Both NULL is mocr_op_gemm_argmax_soft; soft = NULL with the two set is a penalty without any automaton. */
+int mocr_op_gemm_argmax_penalty(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                                int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N,
+                                int32_t K, int32_t tile, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
+                                const int32_t* d_rowmap, const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld,
+                                const int32_t* d_step, float* d_tgt_val, const mocr_soft_tables* soft, const uint32_t* d_seen_mask,
+                                const float* d_penalty_of_row);
 /* bf16 engines: the small-batch projection (rows <= 32; kernels_smallm.h SmallMParams), one of the (pro, epi) pairs the
  * small-batch decode step launches: (0,0) (1,0) (0,1) (1,2) (1,3). */
 typedef struct mocr_smallm_args {

@@ -141,6 +141,10 @@ __device__ __forceinline__ void glds16_nt(const void* gsrc_lane, void* lds_wave_
 #define LAT_GLDS glds16_nt
 #endif
 
+// transformers' RepetitionPenaltyLogitsProcessor on one fp32 logit of a seen token: an IEEE multiply or an IEEE divide (never
+// a reciprocal), so p = 1 returns v bit for bit; v == 0 divides.
+__device__ __forceinline__ float pen_logit(float v, float p) { return v < 0.f ? v * p : __fdiv_rn(v, p); }
+
 // A sorted list of the four best (value, column) pairs seen so far: value descending, the lower column first among equal
 // values - the order of the greedy pick.  Unfilled entries are (-inf, 0x7fffffff); a NaN wins no comparison and never enters.
 struct Top4 {

@@ -141,6 +141,9 @@ struct LaneCtx {
     int* aut_base_of_row = nullptr;                 // [Bp] the global number of every row's start state (-1: no automaton), by row
     int* aut_state = nullptr;                       // [Bp] the global state every row is in (AUT_STATE_NONE / AUT_STATE_DEAD), by row
     int* aut_state_out = nullptr;                   // [Bp] ... in the automaton's own numbering: what the jobs' out_state receives
+    // repetition penalty: allocated by the first batch with a row of p != 1 (ensure_penalty_buffers)
+    unsigned* seen_mask = nullptr;                  // [Bp][V / 32] the tokens every row holds (start, forced, chosen), by row
+    float* penalty_of_row = nullptr;                // [Bp] repetition_penalty of every row (1: off), by row
     // token positions: allocated by the first batch that asks (ensure_pos_buffers)
     void* pos_hist = nullptr;                      // [Bp][max_len][768] T (+ one GEMM tile of rows): the last layer's LayerNorm-1 output of every
                                                     // (row, input position), by row like ids - what the cross-attention query projection read.
@@ -202,6 +205,7 @@ struct Job {
     std::vector<int32_t> ngram;     // no-repeat n-grams (the *_norepeat entry points): one size per crop; empty = all 0
     std::vector<int32_t> automata;  // token automata (the *_automaton entry points): one handle per row; empty = all MOCR_AUTOMATON_NONE
     int32_t* out_state = nullptr;   // nullable: [n] the rows' final automaton states; host or device like out_ids
+    std::vector<float> penalty;     // repetition penalty (the *_penalty entry points): one p per row; empty = all 1
     float* out_pos = nullptr;      // nullable (the *_positions entry points): [n][max_len][MOCR_POSITION_FIELDS]; host or device like out_ids
     std::vector<int32_t> prefix_len;    // forced prefixes (the *_prefix entry points): one length per crop; empty = all 0
     std::vector<int32_t> prefix;        // ... and the tokens, [n][prefix_ld] (a copy: the caller's arrays need not outlive the call)
@@ -231,6 +235,9 @@ struct DecMode {
     bool soft = false;              // ... and one of those automata is SOFT (edge weights / open states; implies `automaton`): the LM head is the
                                     // SOFT form of the masked epilogue, the token kernel the SOFT one, the batch starts with
                                     // automaton_init_soft_kernel
+    bool penalty = false;           // a row has a repetition penalty p != 1 (implies `soft`, so that the build has one more family and not two:
+                                    // rows without an automaton read state NONE and add nothing): the LM head and the token kernel are the
+                                    // PEN forms, the batch also starts with penalty_init_kernel
     bool positions = false;        // a job asked for token positions: the steps record pos_hist, finish_batch runs the deferred pass
                                     // (a beam batch too: its selection then also keeps the beam-index trails the pass gathers by)
     bool prefix = false;            // a row has a forced prefix: the steps run scored and masked (level >= 1, mask; unconstrained rows read
@@ -245,17 +252,18 @@ struct DecMode {
                                     // `soft` (one of those automata is soft) in its SOFT form, on the arena's weights and default edges
     // a graph captured in one mode is never replayed in another: the mode's share of the decode-graph key (6 bits; a beam
     // batch: bit 6, its token form: bit 7, an automaton batch: bit 8, a beam batch's automaton form: bit 9, a soft automaton
-    // batch: bit 10, and a beam batch's configuration - kernel arguments of the captured launches - in the bits above, beam_key)
+    // batch: bit 10, a penalty batch: bit 11, and a beam batch's configuration - kernel arguments of the captured launches - in
+    // the bits above, beam_key)
     int key_bits() const {
         return level + (mask ? 4 : 0) + (ngram ? 8 : 0) + (positions ? 16 : 0) + (prefix ? 32 : 0) + (beam ? 64 : 0) + (beam_tokens ? 128 : 0) +
-               (automaton ? 256 : 0) + (beam_automaton ? 512 : 0) + (soft ? 1024 : 0);
+               (automaton ? 256 : 0) + (beam_automaton ? 512 : 0) + (soft ? 1024 : 0) + (penalty ? 2048 : 0);
     }
-    static constexpr int KEY_SPAN = 2048;
+    static constexpr int KEY_SPAN = 4096;
     int epilogue() const { return mask ? (level == 2 ? EPI_TOPK_M : level == 1 ? EPI_ARGMAX_LSE_M : EPI_ARGMAX_M)
                                        : (level == 2 ? EPI_TOPK : level == 1 ? EPI_ARGMAX_LSE : EPI_ARGMAX); }
     // profile names of the fused LM head and of the token kernel
     const char* head_name() const {
-        return soft ? "gemm_dec_vocab_sw" : mask ? "gemm_dec_vocab_m" : level == 2 ? "gemm_dec_vocab_topk" : level == 1 ? "gemm_dec_vocab_lse" : "gemm_dec_vocab";
+        return penalty ? "gemm_dec_vocab_rp" : soft ? "gemm_dec_vocab_sw" : mask ? "gemm_dec_vocab_m" : level == 2 ? "gemm_dec_vocab_topk" : level == 1 ? "gemm_dec_vocab_lse" : "gemm_dec_vocab";
     }
     const char* token_name() const {
         static const char* const names[3][3] = {{"dec_token", "dec_token_m", "dec_token_ng"},
@@ -263,7 +271,8 @@ struct DecMode {
                                                 {"dec_token_topk", "dec_token_topk_m", "dec_token_topk_ng"}};
         static const char* const automaton_names[3] = {"dec_token_am", "dec_token_lse_am", "dec_token_topk_am"};
         static const char* const soft_names[3] = {"dec_token_sw", "dec_token_lse_sw", "dec_token_topk_sw"};
-        return soft ? soft_names[level] : automaton ? automaton_names[level] : names[level][ngram ? 2 : mask ? 1 : 0];
+        static const char* const penalty_names[3] = {"dec_token_rp", "dec_token_lse_rp", "dec_token_topk_rp"};
+        return penalty ? penalty_names[level] : soft ? soft_names[level] : automaton ? automaton_names[level] : names[level][ngram ? 2 : mask ? 1 : 0];
     }
 };
 
@@ -288,7 +297,9 @@ static DecMode mode_of(const std::vector<Job>& jobs) {
         m.automaton = m.automaton || !j.automata.empty();      // (slice_rows: an array of MOCR_AUTOMATON_NONE alone comes as empty)
         m.positions = m.positions || j.out_pos;
         m.prefix = m.prefix || !j.prefix_len.empty();
+        m.penalty = m.penalty || !j.penalty.empty();            // (slice_job: rows of p = 1 alone come as empty)
     }
+    if (m.penalty) m.soft = m.automaton = true;     // the PEN forms are SOFT forms: rows without an automaton are in state NONE
     m.ngram = m.ngram || m.automaton;           // an automaton's sets reach the step through the same per-row masks
     if (m.prefix) m.level = std::max(m.level, 1);      // a forced token is one more per-row fact of the masked, scored step
     m.mask = m.mask || m.ngram || m.prefix;     // the bans are applied through the rows' masks, which start as the rows' sets
@@ -308,6 +319,7 @@ struct Lane {
     std::vector<int> h_sets, h_ngram;   // the uploads of set_of_row / ngram_of_row stage from here
     std::vector<int> h_plen, h_prefix;  // ... and those of prefix_len / prefix
     std::vector<int> h_aut;             // ... and that of aut_base_of_row
+    std::vector<float> h_penalty;       // ... and that of penalty_of_row
     int t = 0, steps = 0, chunk = 0;
     bool finishing = false;         // a flag of this batch has reported a finished row: rows are leaving, chunks get shorter
     bool flag_pending[2] = {false, false};
@@ -349,6 +361,7 @@ struct mocr_engine : LaneCtx {
     bool beam_batch = false;        // the batch being scheduled is a beam batch (set with `regime`): no one-launch-per-projection path
     bool automaton_batch = false;   // the batch being advanced brings token automata (set with `regime`): the token kernel gets the tables
     bool soft_batch = false;        // ... and one of them is soft: the token kernel and the LM head get the weights and the default edges too
+    bool penalty_batch = false;     // ... and a row has a repetition penalty: they get the rows' seen words and penalties too
     bool use_smallm(int n) const { return n <= smallm_rows && !use_latent(n) && !beam_batch; }
     std::vector<mocr_beam_config> beam_cfgs;    // the beam configurations seen: a decode graph bakes one in, its key names it by index
     std::map<std::string, std::vector<float>> host_w;
@@ -380,7 +393,7 @@ struct mocr_engine : LaneCtx {
     std::vector<int> aut_first{0}, aut_states{0};
     int aut_n_states = 0, aut_n_edges = 0;
     // decode-step HIP graphs, keyed by (lane, rows, (max_len, context bucket, DecMode::key_bits), steps per graph)
-    std::map<std::tuple<int, int, int, int, int>, hipGraphExec_t> graphs;      // + the regime
+    std::map<std::tuple<int, int, long long, int, int>, hipGraphExec_t> graphs;      // + the regime
     void bind(int i) { static_cast<LaneCtx&>(*this) = lanes[i].ctx; }
     void unbind(int i) { lanes[i].ctx = static_cast<LaneCtx&>(*this); }
     // device preprocessing (preprocess.h): resample tables per input size, grow-only scratch
@@ -561,6 +574,16 @@ template <typename T> struct SoftTileFamily {
     template <size_t I> static constexpr Kernel kernel() { constexpr Args a = forms[I]; return gemm_kernel<T, a.bm, a.bm, a.epi, a.ring, a.tgt, true>; }
     static constexpr int lds(const Args& a) { return a.ring * (a.bm + a.bm) * 128; }
 };
+// ... and their PEN forms (repetition penalty), which are SOFT too, on GemmParamsPen: one more family, not two
+template <typename T> struct PenTileFamily {
+    using Args = TileArgs;
+    using Kernel = void (*)(GemmParamsPen);
+    static constexpr std::array<Args, 20> forms = soft_tile_forms();
+    template <size_t I> static constexpr Kernel kernel() { constexpr Args a = forms[I]; return gemm_kernel<T, a.bm, a.bm, a.epi, a.ring, a.tgt, true, true>; }
+    static constexpr int lds(const Args& a) { return a.ring * (a.bm + a.bm) * 128; }
+};
+// Repetition penalty (the PEN forms): the rows' seen words and penalties (kernels_gemm.h GemmParamsPen)
+struct TokPen { const unsigned* seen_mask = nullptr; const float* penalty_of_row = nullptr; };
 // Soft token automata (the SOFT forms): the rows' states and the arena's edge tables (kernels_gemm.h GemmParamsSoft)
 struct TokSoft { const int* state = nullptr; const int* edge_begin = nullptr; const int* edge_token = nullptr; const float* edge_weight = nullptr; };
 
@@ -597,12 +620,21 @@ static TileLaunch tile_launch(const mocr_engine* e, int M, int N, int bm, int sp
 }
 
 template <typename T>
-void launch_gemm_tile(mocr_engine* e, const GemmParams& p0, int epi, int bm, int split, int ybatch, const TokSoft* soft = nullptr) {
+void launch_gemm_tile(mocr_engine* e, const GemmParams& p0, int epi, int bm, int split, int ybatch, const TokSoft* soft = nullptr,
+                      const TokPen* pen = nullptr) {
     GemmParams p = p0;
     const TileLaunch t = tile_launch(e, p.M, p.N, bm, split, ybatch, p.k_per_split / (128 / (int)sizeof(T)));
     p.ntn = t.ntn; p.ntm = t.ntm;
     dim3 grid(p.ntm * p.ntn, ybatch, split);
-    if (soft) {
+    if (pen) {          // (soft may be null here: a penalty without any automaton)
+        const auto f = find_form<PenTileFamily<T>>({epi, bm, t.ring, p.tgt_val != nullptr});
+        if (!f.kernel) throw ArgError{"a repetition penalty goes into the masked LM-head epilogues", MOCR_ERR_ARG};
+        GemmParamsPen pp{};
+        static_cast<GemmParams&>(pp) = p;
+        if (soft) { pp.aut_state = soft->state; pp.edge_begin = soft->edge_begin; pp.edge_token = soft->edge_token; pp.edge_weight = soft->edge_weight; }
+        pp.seen_mask = pen->seen_mask; pp.penalty_of_row = pen->penalty_of_row;
+        hipLaunchKernelGGL(f.kernel, grid, dim3(256), f.lds, e->stream, pp);
+    } else if (soft) {
         const auto f = find_form<SoftTileFamily<T>>({epi, bm, t.ring, p.tgt_val != nullptr});
         if (!f.kernel) throw ArgError{"edge weights go into the masked LM-head epilogues", MOCR_ERR_ARG};
         GemmParamsSoft ps{};
@@ -808,7 +840,7 @@ struct TokMask { const unsigned* table = nullptr; const int* set_of_row = nullpt
 // EPI_TOPK*), the exp sums (the _LSE and TOPK forms), the four best (TOPK) - and the mask the EPI_*_M forms apply
 // Forced prefixes (EPI_ARGMAX_LSE_M / EPI_TOPK_M): the rows' prefixes, the slots' steps and where the target column's value goes
 struct TokTarget { const int* prefix = nullptr; const int* prefix_len = nullptr; int prefix_ld = 0; const int* step = nullptr; float* tgt_val = nullptr; };
-struct LmHead { int* cand_idx = nullptr; float* cand_sum = nullptr; float* top_val = nullptr; int* top_idx = nullptr; TokMask mask; TokTarget target; TokSoft soft; };
+struct LmHead { int* cand_idx = nullptr; float* cand_sum = nullptr; float* top_val = nullptr; int* top_idx = nullptr; TokMask mask; TokTarget target; TokSoft soft; TokPen pen; };
 
 // One GEMM: A [M,K] (lda), W [N,K] (ldw = K), out (ldo).  tile: a tile code (TILE_CODES).  gemm_call states the operands and the
 // shape; a call site then names every extra it sets.  split > 1 only with EPI_SLAB.
@@ -889,6 +921,9 @@ void gemm(mocr_engine* e, const GemmCall& c) {
     const TokSoft* const soft = lm && lm->soft.state ? &lm->soft : nullptr;
     if (soft && (!tm.table || !soft->edge_begin || !soft->edge_token || !soft->edge_weight || !tile_is(tile, GemmKind::Tile)))
         throw ArgError{std::string("edge weights come with a masked LM-head epilogue on a 64 / 128 tile and all four arrays: ") + c.name, MOCR_ERR_ARG};
+    const TokPen* const pen = lm && lm->pen.seen_mask ? &lm->pen : nullptr;
+    if (pen && (!tm.table || !pen->penalty_of_row || !tile_is(tile, GemmKind::Tile)))
+        throw ArgError{std::string("a repetition penalty comes with a masked LM-head epilogue on a 64 / 128 tile and both arrays: ") + c.name, MOCR_ERR_ARG};
     p.M = M; p.N = N; p.lda = c.lda; p.ldw = K; p.ldo = c.ldo;
     int ybatch = 1;
     if (const HeadBatch* hb = c.hb) {
@@ -916,7 +951,7 @@ void gemm(mocr_engine* e, const GemmCall& c) {
     ProfScope ps(e, c.name, 2.0 * M * N * K * ybatch, bytes * ybatch);
     if (!tc) throw ArgError{"gemm tile must be 64, 128 or 4096", MOCR_ERR_ARG};
     switch (tc->kind) {
-        case GemmKind::Tile: launch_gemm_tile<T>(e, p, epi, tc->arg, split, ybatch, soft); break;
+        case GemmKind::Tile: launch_gemm_tile<T>(e, p, epi, tc->arg, split, ybatch, soft, pen); break;
         case GemmKind::Persistent: {
             static const int strip_env = env_int("MOCR_GEMM_STRIP", -1);     // -1: strips where they walk fewer rounds (r03, M = 50,432: O-proj 133 -> 113 us, FC2 303 -> 275)
             // the bf16-epilogue GEMMs: 1 = the one-barrier-per-two-K-tiles loop with the 64-deep LDS image (K64), 0 = one barrier per
@@ -1372,8 +1407,9 @@ struct DecTokenArgs {
     const float* top_val; const int* top_idx;             // alternatives steps (st.alt_ids set) on the candidate path: the tiles' four best
     float* x_f32; void* x_t;
     void* cache; uint8_t* cache8; float inv8; long long cstride;   // layer-0 latent cache row (T or e4m3), indexed by row
-    DecSoftAutomata aut;                                  // token automata (the six set: the AUTOMATON form; the state then has the per-row masks;
-                                                          // edge_weight and default_next set too: the SOFT form)
+    DecPenAutomata aut;                                   // token automata (the six set: the AUTOMATON form; the state then has the per-row masks;
+                                                          // edge_weight and default_next set too: the SOFT form; pen set: the PEN form,
+                                                          // in which the eight may be null)
 };
 
 // The operator hooks come with a bare DecState, so the kernel's form is read off the state: scores / alternatives /
@@ -1383,7 +1419,7 @@ void launch_dec_token(mocr_engine* e, const DecState& st, const DecTokenArgs& a,
     auto& w = e->w;
     DecMode m;
     m.level = st.alt_ids ? 2 : st.scores ? 1 : 0; m.mask = st.tok_mask != nullptr; m.ngram = st.row_mask != nullptr;
-    m.automaton = a.aut.state != nullptr; m.soft = a.aut.edge_weight != nullptr;
+    m.automaton = a.aut.state != nullptr; m.soft = a.aut.edge_weight != nullptr; m.penalty = a.aut.pen.seen_mask != nullptr;
     const bool cand = a.ncand > 0;
     ProfScope ps(e, FIRST ? "dec_token_first" : m.token_name(), 0, FIRST ? 0.0 : (double)n * e->V * 4 * a.nslab);
     auto launch = [&](auto kernel) {
@@ -1395,6 +1431,11 @@ void launch_dec_token(mocr_engine* e, const DecState& st, const DecTokenArgs& a,
     };
     // <T, 768, FIRST, SCORES, TOPK, MASK, NGRAM>: the start token's kernel, and level x (plain, MASK, NGRAM) for the steps
     if constexpr (FIRST) launch(dec_token_kernel<T, 768, true>);      // (the start step has nothing to score or to mask)
+    else if (m.penalty) switch (m.level) {        // the PEN form of every level
+        case 0: launch(dec_token_kernel<T, 768, false, false, false, true, true, true, true, true>); break;
+        case 1: launch(dec_token_kernel<T, 768, false, true, false, true, true, true, true, true>); break;
+        default: launch(dec_token_kernel<T, 768, false, true, true, true, true, true, true, true>); break;
+    }
     else if (m.soft) switch (m.level) {           // the SOFT form of every level
         case 0: launch(dec_token_kernel<T, 768, false, false, false, true, true, true, true>); break;
         case 1: launch(dec_token_kernel<T, 768, false, true, false, true, true, true, true>); break;
@@ -1434,6 +1475,7 @@ void dec_token(mocr_engine* e, const DecState& st, int nslab, int n, int ncand =
     if (!FIRST && e->automaton_batch) {
         static_cast<DecAutomata&>(a.aut) = DecAutomata{e->aut_edge_begin, e->aut_edge_token, e->aut_edge_next, e->aut_accepting, e->aut_base_of_row, e->aut_state};
         if (e->soft_batch) { a.aut.edge_weight = e->aut_edge_weight; a.aut.default_next = e->aut_default_next; }
+        if (e->penalty_batch) a.aut.pen = DecPenalty{e->seen_mask, e->penalty_of_row};
     }
     launch_dec_token<T, FIRST>(e, st, a, n);
 }
@@ -2051,6 +2093,7 @@ void decode_step(mocr_engine* e, const DecState& st, const DecMode& m, int n, in
         if (m.mask) lm.mask = TokMask{st.tok_mask, st.set_of_row, st.rowmap};
         if (m.prefix) lm.target = TokTarget{st.prefix, st.prefix_len, st.prefix_ld, st.step, e->tgt_val};
         if (m.soft) lm.soft = TokSoft{e->aut_state, e->aut_edge_begin, e->aut_edge_token, e->aut_edge_weight};
+        if (m.penalty) lm.pen = TokPen{e->seen_mask, e->penalty_of_row};
         GemmCall head = gemm_call(m.head_name(), e->z_t, D, w.wv, w.bv, e->cand_val, e->V, n, e->V, D, m.epilogue(), vt);
         head.lm = &lm;
         gemm<T>(e, head);
@@ -2083,7 +2126,7 @@ void quantize_enc(mocr_engine* e, int n) {
 // Raise the dynamic-LDS limit of every form of every kernel family (done once, at creation: outside any capture, from the
 // calling thread - decode steps are launched inside stream capture and from several lane threads).
 template <typename T> void init_kernel_attrs() {
-    raise_lds<TileFamily<T>, SoftTileFamily<T>, PersFamily, QqtFamily, SmallMFamily, LatentFamily, LatentTFamily, Latent8Family, LatentT8Family>();
+    raise_lds<TileFamily<T>, SoftTileFamily<T>, PenTileFamily<T>, PersFamily, QqtFamily, SmallMFamily, LatentFamily, LatentTFamily, Latent8Family, LatentT8Family>();
     for_each_enc_attn<T>([](auto kernel, int lds) { set_max_lds(kernel, lds); });
 #ifdef MOCR_EXPERIMENTS
     raise_lds<Gemm256Family, WideFamily, Wide2Family>();
@@ -2099,7 +2142,7 @@ hipGraphExec_t decode_graph(mocr_engine* e, const DecState& st, const DecMode& m
     const int bucket = need <= 3 ? 3 : need <= 5 ? 5 : need <= 8 ? 8 : 10;
     const int t_hi = std::min(bucket * 32, st.max_len) - 1;      // largest context this bucket covers
     // ... and by the mode of the steps: another LM-head epilogue, token kernel, set of pointers or launch each
-    int beam_key = 0;                // a beam batch: which configuration the captured launches carry (1-based, above the mode bits)
+    long long beam_key = 0;          // a beam batch: which configuration the captured launches carry (1-based, above the mode bits)
     if (m.beam) {
         auto& cfgs = e->beam_cfgs;
         size_t i = 0;
@@ -2108,9 +2151,9 @@ hipGraphExec_t decode_graph(mocr_engine* e, const DecState& st, const DecMode& m
             if (i >= 100) throw ArgError{"more than 100 distinct beam configurations on one engine", MOCR_ERR_UNSUPPORTED};
             cfgs.push_back(m.beam_cfg);
         }
-        beam_key = ((int)i + 1) << 24;
+        beam_key = ((long long)i + 1) << 32;
     }
-    const auto key = std::make_tuple(e->lane_id, n, (st.max_len * 16 + bucket) * DecMode::KEY_SPAN + m.key_bits() + beam_key, steps, e->rrows(n));
+    const auto key = std::make_tuple(e->lane_id, n, (long long)(st.max_len * 16 + bucket) * DecMode::KEY_SPAN + m.key_bits() + beam_key, steps, e->rrows(n));
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) return it->second;
     hipGraph_t g = nullptr;
@@ -2333,6 +2376,22 @@ static void launch_automaton_init(mocr_engine* e, unsigned* row_mask, const unsi
     else
     hipLaunchKernelGGL(automaton_init_kernel, dim3(rows), dim3(192), 0, e->stream, row_mask, base_mask, base_set_of_row, ngram_of_row, rows,
                        e->V / 32, e->cfg.start_id, e->cfg.eos_id, edge_begin, edge_token, accepting, aut_base_of_row, aut_state);
+    HIPCHECK(hipGetLastError());
+}
+
+// ---- repetition penalty ----------------------------------------------------------
+// The rows' seen words and penalties, for the bound lane: allocated by the first batch that has a row with p != 1, like the
+// n-gram masks (772 B a row).
+static void ensure_penalty_buffers(mocr_engine* e) {
+    if (e->seen_mask) return;
+    const size_t Bp = (size_t)e->Bp;
+    e->seen_mask = e->dalloc<unsigned>(Bp * (e->V / 32));
+    e->penalty_of_row = e->dalloc<float>(Bp);
+}
+
+static void launch_penalty_init(mocr_engine* e, unsigned* seen_mask, int rows) {
+    ProfScope ps(e, "penalty_init", 0, (double)rows * (e->V / 32) * 4);
+    hipLaunchKernelGGL(penalty_init_kernel, dim3(rows), dim3(192), 0, e->stream, seen_mask, rows, e->V / 32, e->cfg.start_id);
     HIPCHECK(hipGetLastError());
 }
 
@@ -2571,6 +2630,13 @@ void start_batch(mocr_engine* e, Lane& L) {
     // token automata: the rows' start states (the padding rows and the rows without an automaton: -1), their first masks
     if (m.automaton) {
         if (e->V != 6144) throw ArgError{"token automata need the 6144-token vocabulary", MOCR_ERR_UNSUPPORTED};
+        if (m.penalty) {
+            // (the PEN forms are SOFT forms, and a captured decode graph holds the arena's addresses: the arena and its soft part
+            // exist from the first penalty batch on, whether or not a row of it brings an automaton - a row under a hard automaton
+            // reads weight 0 / default -1 there)
+            ensure_automaton_arena(e);
+            ensure_soft_arena(e);
+        }
         ensure_automaton_buffers(e);
         L.h_aut.assign((size_t)L.np, -1);
         int r0 = 0;
@@ -2582,6 +2648,19 @@ void start_batch(mocr_engine* e, Lane& L) {
         HIPCHECK(hipMemcpyAsync(e->aut_base_of_row, L.h_aut.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
         launch_automaton_init(e, e->row_mask, e->tok_table, e->set_of_row, e->ngram_of_row, L.np, e->aut_edge_begin, e->aut_edge_token,
                               e->aut_accepting, e->aut_base_of_row, e->aut_state, m.soft ? e->aut_default_next : nullptr);
+    }
+    // repetition penalty: the rows' penalties (the padding rows and the rows of jobs without one: 1) and their first seen
+    // words, the start token alone
+    if (m.penalty) {
+        ensure_penalty_buffers(e);
+        L.h_penalty.assign((size_t)L.np, 1.f);
+        int r0 = 0;
+        for (const Job& j : L.jobs) {
+            std::copy(j.penalty.begin(), j.penalty.end(), L.h_penalty.begin() + r0);
+            r0 += j.n;
+        }
+        HIPCHECK(hipMemcpyAsync(e->penalty_of_row, L.h_penalty.data(), (size_t)L.np * sizeof(float), hipMemcpyHostToDevice, e->stream));
+        launch_penalty_init(e, e->seen_mask, L.np);
     }
     // token positions: position 0, the pad tail and the rows of the jobs that did not ask read 0
     if (m.positions) {
@@ -2824,9 +2903,9 @@ bool pump_once(mocr_engine* e) {
         if (L.active) {
             e->bind((int)i);
             e->regime = L.np0;
-            e->beam_batch = L.mode.beam; e->automaton_batch = L.mode.automaton; e->soft_batch = L.mode.soft;
+            e->beam_batch = L.mode.beam; e->automaton_batch = L.mode.automaton; e->soft_batch = L.mode.soft; e->penalty_batch = L.mode.penalty;
             advance<T>(e, L);
-            e->regime = 0; e->beam_batch = false; e->automaton_batch = false; e->soft_batch = false;
+            e->regime = 0; e->beam_batch = false; e->automaton_batch = false; e->soft_batch = false; e->penalty_batch = false;
             e->unbind((int)i);
             any = true;
         }
@@ -2840,7 +2919,7 @@ void drive(mocr_engine* e) {
         if (e->cfg.dtype == MOCR_BF16) { while (pump_once<bf16_t>(e)) {} }
         else { while (pump_once<float>(e)) {} }
     } catch (...) {
-        e->regime = 0; e->beam_batch = false; e->automaton_batch = false; e->soft_batch = false;
+        e->regime = 0; e->beam_batch = false; e->automaton_batch = false; e->soft_batch = false; e->penalty_batch = false;
         e->pending.clear();
         for (auto& L : e->lanes) { L.active = false; L.jobs.clear(); (void)hipStreamSynchronize(L.ctx.stream); }
         throw;
@@ -3493,7 +3572,17 @@ struct Request {
     const int32_t* automata = nullptr;
     int32_t* out_state = nullptr;
     bool beam_soft = false;     // a beam request from the *_beam_soft entry points: its automata may be soft
+    // repetition penalty (the *_penalty entry points): host [rows], finite and > 0 (null: every row 1)
+    const float* penalty = nullptr;
 };
+
+// repetition penalty: one p per row, finite and > 0 (p < 1 rewards repeats and is allowed); beam search takes none
+static void require_penalty(const Request& r, int n) {
+    if (!r.penalty) return;
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(r.penalty[i]) || !(r.penalty[i] > 0.f)) throw ArgError{"repetition_penalty must be finite and > 0", MOCR_ERR_ARG};
+    if (r.beam) throw ArgError{"beam search takes no repetition penalty", MOCR_ERR_ARG};
+}
 
 // token automata: one handle per row, MOCR_AUTOMATON_NONE or an automaton this engine has created (a beam request comes
 // from the *_beam_automaton entry points alone, with its crops' handles expanded to their K rows)
@@ -3550,6 +3639,7 @@ static void validate_request(mocr_engine* e, const Request& r, int n, Ready read
     require_ngram(e, r.ngram, n);
     require_prefix(e, r, n, gen_len);
     require_automata(e, r, n);
+    require_penalty(r, n);
 }
 
 // rows [base, base + n) of a per-crop array whose default is `dflt`, for the job that decodes them (empty: all default)
@@ -3574,6 +3664,9 @@ static void slice_job(Job& j, const Request& r, size_t base, int n, int max_len)
     j.ngram = slice_rows(r.ngram, base, n, 0);
     j.automata = slice_rows(r.automata, base, n, MOCR_AUTOMATON_NONE);
     j.out_state = r.out_state ? r.out_state + base : nullptr;
+    j.penalty.clear();
+    if (r.penalty && std::any_of(r.penalty + base, r.penalty + base + n, [](float p) { return p != 1.f; }))
+        j.penalty.assign(r.penalty + base, r.penalty + base + n);
     j.prefix_len = slice_rows(r.prefix_len, base, n, 0);
     j.prefix.clear(); j.prefix_ld = 0;
     if (!j.prefix_len.empty()) {
@@ -3612,6 +3705,12 @@ static Request request_of(void* out_logp = nullptr, void* out_alt_ids = nullptr,
 // ... and a request with the two arguments the *_automaton twins add
 static Request with_automata(Request r, const int32_t* automata, void* out_state) {
     r.automata = automata; r.out_state = static_cast<int32_t*>(out_state);
+    return r;
+}
+
+// ... and with the one the *_penalty twins add
+static Request with_penalty(Request r, const float* penalty) {
+    r.penalty = penalty;
     return r;
 }
 
@@ -3659,6 +3758,16 @@ int mocr_recognize_device_automaton(mocr_engine* e, const void* d_gray, int32_t 
     return recognize_device(e, d_gray, n_rows, d_out_ids, d_out_len,
                             with_automata(request_of(d_out_logp, d_out_alt_ids, d_out_alt_logp, sets, ngram, d_out_pos, prefix, prefix_len,
                                                      prefix_ld, source, n_planes), automata, d_out_state));
+}
+
+int mocr_recognize_device_penalty(mocr_engine* e, const void* d_gray, int32_t n_planes, int32_t n_rows, const int32_t* source,
+                                  void* d_out_ids, void* d_out_len, void* d_out_logp, void* d_out_alt_ids, void* d_out_alt_logp,
+                                  const int32_t* sets, const int32_t* ngram, void* d_out_pos, const int32_t* prefix,
+                                  const int32_t* prefix_len, int32_t prefix_ld, const int32_t* automata, void* d_out_state,
+                                  const float* penalty) {
+    return recognize_device(e, d_gray, n_rows, d_out_ids, d_out_len,
+                            with_penalty(with_automata(request_of(d_out_logp, d_out_alt_ids, d_out_alt_logp, sets, ngram, d_out_pos, prefix,
+                                                                  prefix_len, prefix_ld, source, n_planes), automata, d_out_state), penalty));
 }
 
 int mocr_recognize_device_norepeat(mocr_engine* e, const void* d_gray, int32_t n, void* d_out_ids, void* d_out_len,
@@ -3759,6 +3868,16 @@ int mocr_recognize_gray_host_automaton(mocr_engine* e, const uint8_t* gray, int3
     return recognize_gray_host(e, gray, n_rows, max_len_override, out_ids, out_len,
                                with_automata(request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len,
                                                         prefix_ld, source, n_planes), automata, out_state));
+}
+
+int mocr_recognize_gray_host_penalty(mocr_engine* e, const uint8_t* gray, int32_t n_planes, int32_t n_rows, const int32_t* source,
+                                     int32_t max_len_override, int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids,
+                                     float* out_alt_logp, const int32_t* sets, const int32_t* ngram, float* out_pos,
+                                     const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld, const int32_t* automata,
+                                     int32_t* out_state, const float* penalty) {
+    return recognize_gray_host(e, gray, n_rows, max_len_override, out_ids, out_len,
+                               with_penalty(with_automata(request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len,
+                                                                     prefix_ld, source, n_planes), automata, out_state), penalty));
 }
 
 int mocr_recognize_gray_host_norepeat(mocr_engine* e, const uint8_t* gray, int32_t n, int32_t max_len_override, int32_t* out_ids,
@@ -4084,6 +4203,16 @@ int mocr_recognize_images_automaton(mocr_engine* e, const mocr_image* images, in
                                                      source, n_images), automata, out_state));
 }
 
+int mocr_recognize_images_penalty(mocr_engine* e, const mocr_image* images, int32_t n_images, int32_t n_rows, const int32_t* source,
+                                  int32_t* out_ids, int32_t* out_len, float* out_logp, int32_t* out_alt_ids, float* out_alt_logp,
+                                  const int32_t* sets, const int32_t* ngram, float* out_pos, const int32_t* prefix,
+                                  const int32_t* prefix_len, int32_t prefix_ld, const int32_t* automata, int32_t* out_state,
+                                  const float* penalty) {
+    return recognize_images(e, images, n_rows, out_ids, out_len,
+                            with_penalty(with_automata(request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len,
+                                                                  prefix_ld, source, n_images), automata, out_state), penalty));
+}
+
 int mocr_recognize_images_norepeat(mocr_engine* e, const mocr_image* images, int32_t n, int32_t* out_ids, int32_t* out_len,
                                    float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets,
                                    const int32_t* ngram) {
@@ -4153,6 +4282,7 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
         std::vector<int32_t> view_ngram;                // ... and no-repeat n-gram sizes
         std::vector<int32_t> view_plen, view_prefix;    // ... and forced prefixes (a sliver's prefix is ignored)
         std::vector<int32_t> view_automata;             // ... and automata
+        std::vector<float> view_penalty;                // ... and repetition penalties
         for (int i = 0; i < n_rows; ++i) {
             const int v = view_of[req.source ? req.source[i] : i];
             if (v < 0) continue;
@@ -4161,6 +4291,7 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
             if (req.sets) view_sets.push_back(req.sets[i]);
             if (req.ngram) view_ngram.push_back(req.ngram[i]);
             if (req.automata) view_automata.push_back(req.automata[i]);
+            if (req.penalty) view_penalty.push_back(req.penalty[i]);
             if (req.prefix) {
                 view_plen.push_back(req.prefix_len[i]);
                 view_prefix.insert(view_prefix.end(), req.prefix + (size_t)i * req.prefix_ld, req.prefix + (size_t)(i + 1) * req.prefix_ld);
@@ -4192,6 +4323,7 @@ static int recognize_regions(mocr_engine* e, const mocr_image* pages, int32_t n_
                                        req.source ? view_src.data() : nullptr, req.source ? (int32_t)views.size() : -1);
             inner.beam = req.beam; inner.out_score = reinterpret_cast<float*>(rows_of(6));      // (a sliver drops all K rows of its crop)
             inner.automata = req.automata ? view_automata.data() : nullptr; inner.out_state = reinterpret_cast<int32_t*>(rows_of(7));
+            inner.penalty = req.penalty ? view_penalty.data() : nullptr;
             prepare_and_decode(e, srcs, views.data(), (int)nv, reinterpret_cast<int32_t*>(rows_of(0)), reinterpret_cast<int32_t*>(rows_of(1)), inner);
         }
         for (int i = 0; i < n_rows; ++i)
@@ -4226,6 +4358,16 @@ int mocr_recognize_regions_shared(mocr_engine* e, const mocr_image* pages, int32
     return recognize_regions(e, pages, n_pages, regions, n_regions, n_rows, out_ids, out_len,
                              request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len, prefix_ld, source,
                                         n_regions));
+}
+
+int mocr_recognize_regions_penalty(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
+                                   int32_t n_regions, int32_t n_rows, const int32_t* source, int32_t* out_ids, int32_t* out_len,
+                                   float* out_logp, int32_t* out_alt_ids, float* out_alt_logp, const int32_t* sets, const int32_t* ngram,
+                                   float* out_pos, const int32_t* prefix, const int32_t* prefix_len, int32_t prefix_ld,
+                                   const int32_t* automata, int32_t* out_state, const float* penalty) {
+    return recognize_regions(e, pages, n_pages, regions, n_regions, n_rows, out_ids, out_len,
+                             with_penalty(with_automata(request_of(out_logp, out_alt_ids, out_alt_logp, sets, ngram, out_pos, prefix, prefix_len,
+                                                                   prefix_ld, source, n_regions), automata, out_state), penalty));
 }
 
 int mocr_recognize_regions_automaton(mocr_engine* e, const mocr_image* pages, int32_t n_pages, const mocr_region* regions,
@@ -5004,7 +5146,8 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d
                         const float* d_tgt_val = nullptr, const int32_t* d_edge_begin = nullptr, const int32_t* d_edge_token = nullptr,
                         const int32_t* d_edge_next = nullptr, const uint8_t* d_accepting = nullptr,
                         const int32_t* d_aut_base_of_row = nullptr, int32_t* d_aut_state = nullptr,
-                        const float* d_edge_weight = nullptr, const int32_t* d_default_next = nullptr) {
+                        const float* d_edge_weight = nullptr, const int32_t* d_default_next = nullptr,
+                        uint32_t* d_seen_mask = nullptr, const float* d_penalty_of_row = nullptr) {
     return guarded(e, [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
@@ -5026,7 +5169,11 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d
             ((d_aut_state == nullptr) != (d_edge_begin == nullptr)) || ((d_aut_state == nullptr) != (d_edge_token == nullptr)) ||
             ((d_aut_state == nullptr) != (d_edge_next == nullptr)) || ((d_aut_state == nullptr) != (d_accepting == nullptr)) ||
             ((d_aut_state == nullptr) != (d_aut_base_of_row == nullptr)) || (d_aut_state && !d_row_mask) ||
-            ((d_edge_weight == nullptr) != (d_default_next == nullptr)) || (d_edge_weight && !d_aut_state))
+            ((d_edge_weight == nullptr) != (d_default_next == nullptr)) || (d_edge_weight && !d_aut_state) ||
+            // (the PEN form is a SOFT one: a penalty comes with the per-row masks, on the 6144-token vocabulary, and an
+            // automaton beside it is given with its weights and default edges)
+            ((d_seen_mask == nullptr) != (d_penalty_of_row == nullptr)) ||
+            (d_seen_mask && (!d_row_mask || e->V != 6144 || first || (d_aut_state && !d_edge_weight))))
             throw ArgError{"mocr_op_dec_token: bad argument", MOCR_ERR_ARG};
         DecState st{};
         st.n_real = a->n_real;
@@ -5043,6 +5190,7 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d
         DecTokenArgs t{};
         static_cast<DecAutomata&>(t.aut) = DecAutomata{d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state};
         t.aut.edge_weight = d_edge_weight; t.aut.default_next = d_default_next;
+        t.aut.pen = DecPenalty{d_seen_mask, d_penalty_of_row};
         t.slabs = a->slabs; t.nslab = first ? 0 : a->nslab; t.slab_stride = (long long)a->n * e->V;
         t.vbias = a->vbias ? a->vbias : e->w.bv;
         t.cand_val = a->cand_val; t.cand_idx = a->cand_idx; t.ncand = first ? 0 : std::max(a->ncand, 0);
@@ -5101,6 +5249,33 @@ int mocr_op_dec_token_soft(mocr_engine* e, const mocr_token_args* a, const float
     return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, d_row_mask,
                         d_base_mask, d_base_set_of_row, d_ngram_of_row, d_prefix, d_prefix_len, prefix_ld, d_tgt_val, d_edge_begin,
                         d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state, d_edge_weight, d_default_next);
+}
+
+int mocr_op_dec_token_penalty(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
+                              const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
+                              const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
+                              const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row,
+                              const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld, const float* d_tgt_val,
+                              const int32_t* d_edge_begin, const int32_t* d_edge_token, const int32_t* d_edge_next,
+                              const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state,
+                              const float* d_edge_weight, const int32_t* d_default_next, uint32_t* d_seen_mask,
+                              const float* d_penalty_of_row) {
+    return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, d_row_mask,
+                        d_base_mask, d_base_set_of_row, d_ngram_of_row, d_prefix, d_prefix_len, prefix_ld, d_tgt_val, d_edge_begin,
+                        d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state, d_edge_weight, d_default_next,
+                        d_seen_mask, d_penalty_of_row);
+}
+
+int mocr_op_penalty_init(mocr_engine* e, uint32_t* d_seen_mask, int32_t rows) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        if (!e->committed || !d_seen_mask || rows < 1 || e->V % 32) throw ArgError{"mocr_op_penalty_init: bad argument", MOCR_ERR_ARG};
+        launch_penalty_init(e, d_seen_mask, rows);
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
 }
 
 static int op_automaton_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
@@ -5185,6 +5360,9 @@ static int op_lm_head(mocr_engine* e, const void* dA, const void* dW, const floa
         if ((ts.state || ts.edge_begin || ts.edge_token || ts.edge_weight) &&
             (!ts.state || !ts.edge_begin || !ts.edge_token || !ts.edge_weight || !d_tok_mask))
             throw ArgError{"mocr_op_gemm_argmax_soft: the states and the three tables come together, with d_tok_mask", MOCR_ERR_ARG};
+        const TokPen& tp = lm.pen;
+        if ((tp.seen_mask || tp.penalty_of_row) && (!tp.seen_mask || !tp.penalty_of_row || !d_tok_mask))
+            throw ArgError{"mocr_op_gemm_argmax_penalty: d_seen_mask and d_penalty_of_row come together, with d_tok_mask", MOCR_ERR_ARG};
         // (the name and the epilogue by the richest output given, as the steps choose theirs by the batch's mode)
         DecMode m;
         m.level = d_top_val ? 2 : d_cand_sum ? 1 : 0; m.mask = d_tok_mask != nullptr;
@@ -5227,6 +5405,22 @@ int mocr_op_gemm_argmax_soft(mocr_engine* e, const void* dA, const void* dW, con
     return op_lm_head(e, dA, dW, d_bias, d_cand_val, M, N, K, tile,
                       LmHead{d_cand_idx, d_cand_sum, d_top_val, d_top_idx, TokMask{d_tok_mask, d_set_of_row, d_rowmap},
                              TokTarget{d_prefix, d_prefix_len, prefix_ld, d_step, d_tgt_val}, ts});
+}
+
+int mocr_op_gemm_argmax_penalty(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
+                                int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N,
+                                int32_t K, int32_t tile, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
+                                const int32_t* d_rowmap, const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld,
+                                const int32_t* d_step, float* d_tgt_val, const mocr_soft_tables* soft, const uint32_t* d_seen_mask,
+                                const float* d_penalty_of_row) {
+    TokSoft ts{};
+    if (soft) {
+        if (soft->struct_size != (int32_t)sizeof(mocr_soft_tables)) return MOCR_ERR_ARG;
+        ts = TokSoft{soft->d_aut_state, soft->d_edge_begin, soft->d_edge_token, soft->d_edge_weight};
+    }
+    return op_lm_head(e, dA, dW, d_bias, d_cand_val, M, N, K, tile,
+                      LmHead{d_cand_idx, d_cand_sum, d_top_val, d_top_idx, TokMask{d_tok_mask, d_set_of_row, d_rowmap},
+                             TokTarget{d_prefix, d_prefix_len, prefix_ld, d_step, d_tgt_val}, ts, TokPen{d_seen_mask, d_penalty_of_row}});
 }
 
 int mocr_op_gemm_topk(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,

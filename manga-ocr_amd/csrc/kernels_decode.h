@@ -184,6 +184,21 @@ struct DecSoftAutomata : DecAutomata {
     const int* default_next;
 };
 
+// Repetition penalty (mocr.h, "repetition penalty"): what dec_token_kernel's PEN form takes behind the automaton tables - by ROW
+// like ids, so a compaction moves nothing: seen_mask [B][V / 32], bit v = token v is in the row (the start token, forced prefix
+// tokens, chosen tokens; penalty_init_kernel sets the start bit, the PEN token kernel every stored token's), and
+// penalty_of_row [B], finite and > 0, 1 = off.
+struct DecPenalty {
+    unsigned* seen_mask;
+    const float* penalty_of_row;
+};
+
+// ... and the argument of the PEN form in the place of DecSoftAutomata: its eight pointers, which may all be null here (a
+// penalty without any automaton), with the DecPenalty trailing.  Only the PEN instantiations take this type.
+struct DecPenAutomata : DecSoftAutomata {
+    DecPenalty pen;
+};
+
 // The n-gram bans of a row that holds L tokens rid[0 .. L - 1], on its mask in LDS: the threads split the windows
 // i = 0 .. L - n, a window whose n - 1 key tokens equal the row's last n - 1 clears the bit of its follower.
 __device__ __forceinline__ void ngram_ban_windows(unsigned* s_mask, const int* rid, int L, int n, int V, int tid) {
@@ -251,8 +266,17 @@ __device__ __forceinline__ void ngram_ban_windows(unsigned* s_mask, const int* r
 //   the default state - to the target of that state's edge on it, if it has one (one more scan and barrier).  Mask rebuild: an open state starts from all ones, EOS by `accepting`,
 //   instead of zero plus the OR of the edge bits.  Rows under a hard automaton read weight 0 / default -1 and do what the
 //   AUTOMATON form does.
+// PEN = true (`aut` is a DecPenAutomata; implies SOFT): transformers' repetition_penalty under greedy search, per row.  Slab
+//   path: after the SOFT addition and before the MASK select a thread takes pen_logit(v, p) (common.h) of each of its 24
+//   logits whose bit is set in seen_mask[row] - one nibble of one word per float4 - so the argmax, the exp sum, the
+//   alternatives and the forced column's value see the penalised logits; logits_out has been stored before and stays raw.
+//   (Candidate path: the LM head's PEN form has already applied it.)  Both paths: once thread 0 has stored the token of a row
+//   that was unfinished before the step, chosen or forced, it sets the token's bit - a plain load, OR and vector store by the
+//   row's one writer; the next reader is the next step's LM head or token kernel, a later launch.  Every read of the row's
+//   seen words for THIS step precedes the argmax reduction's barrier, the write follows it: the n-gram mask's argument.  A row
+//   finished before the step writes nothing.  The automaton pointers may be null: then no row has a state or a start state.
 template <typename T, int D, bool FIRST, bool SCORES = false, bool TOPK = false, bool MASK = false, bool NGRAM = false,
-          bool AUTOMATON = false, bool SOFT = false>
+          bool AUTOMATON = false, bool SOFT = false, bool PEN = false>
 __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict__ slabs, int nslab, long long slab_stride,
                                                         const float* __restrict__ vbias, int V,
                                                         DecState st,
@@ -267,12 +291,13 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                                                         const float* __restrict__ cand_sum = nullptr,
                                                         const float* __restrict__ top_val = nullptr,
                                                         const int* __restrict__ top_idx = nullptr,
-                                                        std::conditional_t<SOFT, DecSoftAutomata, DecAutomata> aut = {}) {
+                                                        std::conditional_t<PEN, DecPenAutomata, std::conditional_t<SOFT, DecSoftAutomata, DecAutomata>> aut = {}) {
     static_assert(!TOPK || (SCORES && !FIRST), "alternatives come with scores, from the second token on");
     static_assert(!MASK || !FIRST, "the start token is not constrained");
     static_assert(!NGRAM || MASK, "the n-gram bans are applied through the row's mask");
     static_assert(!AUTOMATON || NGRAM, "an automaton's sets are applied through the row's mask");
     static_assert(!SOFT || AUTOMATON, "weights and default edges belong to an automaton");
+    static_assert(!PEN || SOFT, "the penalty form is the soft one too");
     constexpr int MW = 192;                             // mask words of a row (vocab 6144)
     __shared__ __attribute__((aligned(16))) unsigned s_mask[NGRAM ? MW : 4];
     __shared__ int s_ng, s_L;                           // NGRAM: the row's n (0: leave the mask alone) and its token count
@@ -325,9 +350,16 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
         }
         int se0 = 0, se1 = 0;                            // SOFT: the edge range of the row's state (empty: NONE or DEAD)
         if constexpr (SOFT) {
-            const int sst = aut.state[row];
-            if (sst >= 0) { se0 = aut.edge_begin[sst]; se1 = aut.edge_begin[sst + 1]; }
+            bool has = true;                             // PEN: the automaton pointers may be null
+            if constexpr (PEN) has = aut.state != nullptr;
+            if (has) {
+                const int sst = aut.state[row];
+                if (sst >= 0) { se0 = aut.edge_begin[sst]; se1 = aut.edge_begin[sst + 1]; }
+            }
         }
+        float pp = 1.f;                                  // PEN: the row's penalty and its seen words
+        const unsigned* seen = nullptr;
+        if constexpr (PEN) { pp = aut.pen.penalty_of_row[row]; seen = aut.pen.seen_mask + (size_t)row * (V >> 5); }
 #pragma unroll
         for (int j = 0; j < NC; ++j) {
             const int c = tid * 4 + j * 1024;
@@ -347,6 +379,13 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                         if (d == 0) a[j].x += wgt; else if (d == 1) a[j].y += wgt; else if (d == 2) a[j].z += wgt; else a[j].w += wgt;
                     }
                 }
+            }
+            if constexpr (PEN) {
+                const unsigned snib = (seen[c >> 5] >> (c & 31)) & 15u;
+                if (snib & 1) a[j].x = pen_logit(a[j].x, pp);
+                if (snib & 2) a[j].y = pen_logit(a[j].y, pp);
+                if (snib & 4) a[j].z = pen_logit(a[j].z, pp);
+                if (snib & 8) a[j].w = pen_logit(a[j].w, pp);
             }
             if constexpr (MASK) {
                 const unsigned nib = (st.tok_mask[(size_t)st.set_of_row[row] * (V >> 5) + (c >> 5)] >> (c & 31)) & 15u;
@@ -436,6 +475,12 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
             const bool force = ftok >= 0 && !fin;
             if (force) tok = ftok;
             if (t + 1 < st.ids_ld) st.ids[(size_t)row * st.ids_ld + t + 1] = tok;
+            if constexpr (PEN) {                         // the stored token is in the row from the next step on
+                if (!fin && t + 1 < st.ids_ld && (unsigned)tok < (unsigned)V) {
+                    unsigned* const sw = aut.pen.seen_mask + (size_t)row * (V >> 5) + (tok >> 5);
+                    *sw = *sw | (1u << (tok & 31));
+                }
+            }
             if constexpr (SCORES) {
                 const float S = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
                 const float score = -logf(S);
@@ -474,7 +519,9 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                 s_ng = live ? st.ngram_of_row[row] : 0;
                 s_L = t + 2;
                 if constexpr (AUTOMATON) {
-                    s_abase = fin ? -1 : aut.base_of_row[row];
+                    bool none = fin != 0;                // PEN: the automaton pointers may be null
+                    if constexpr (PEN) none = none || aut.base_of_row == nullptr;
+                    s_abase = none ? -1 : aut.base_of_row[row];
                     s_awalk = tok != st.eos_id;
                     s_alive = live;
                     s_anext = AUT_STATE_DEAD;
@@ -608,6 +655,15 @@ __global__ __launch_bounds__(192) void ngram_init_kernel(unsigned* __restrict__ 
         if (ban_start && w == (start_id >> 5)) m &= ~(1u << (start_id & 31));
         row_mask[(size_t)row * words + w] = m;
     }
+}
+
+// Start of a batch with a repetition penalty, one block of 192 threads per row: the sibling of ngram_init_kernel.  The row's
+// seen words are zeroed and the start token's bit is set - every word has one writer.
+__global__ __launch_bounds__(192) void penalty_init_kernel(unsigned* __restrict__ seen_mask, int rows, int words, int start_id) {
+    const int row = blockIdx.x;
+    if (row >= rows) return;
+    for (int w = threadIdx.x; w < words; w += blockDim.x)
+        seen_mask[(size_t)row * words + w] = ((unsigned)start_id < (unsigned)(words * 32) && w == (start_id >> 5)) ? 1u << (start_id & 31) : 0u;
 }
 
 // Start of a batch with token automata, one block of 192 threads per row (words <= 192): the sibling of ngram_init_kernel.

@@ -96,6 +96,13 @@ struct GemmParamsSoft : GemmParams {
     const float* edge_weight;   // [edges] what the edge adds to its token's logit
 };
 
+// Repetition penalty (EPI_*_M with gemm_kernel's PEN, which is SOFT too): GemmParamsSoft plus the rows' seen tokens and their
+// penalties, the argument of the PEN instantiations alone.  aut_state may be null here: a penalty without any automaton.
+struct GemmParamsPen : GemmParamsSoft {
+    const unsigned* seen_mask;      // [rows of the batch][N / 32] by ROW: bit n = token n is in the row (start, forced, chosen)
+    const float* penalty_of_row;    // [rows of the batch] by ROW: finite, > 0; 1 = off
+};
+
 // Linear tile id -> (tm, tn).  Tiles are ordered column-group by column-group: inside a group of
 // `group_n` N-tiles the order is M-major / N-minor, so the blocks resident on one XCD at a time cover
 // a few M-tiles x group_n N-tiles and the group's weight slice (group_n*BN rows of W) stays in that
@@ -196,10 +203,16 @@ __device__ __forceinline__ void gemm_epilogue(const float* sC, const GemmParams&
 // LDS, at the swizzled column.  A thread reads and writes its own group only, so there is no barrier; the max walk, the exp-sum
 // walk, the four best and the target column then see logit + weight with no further change.  Rows without an automaton, dead
 // rows and rows >= M add nothing.
+// PEN (implies SOFT; p is a GemmParamsPen): repetition penalty.  The thread loads the `seen` bits of its column group exactly
+// as it loads mbits - half a word or two words of seen_mask[row], by ROW - and the row's p.  Wherever a walk forms
+// v = (tile value + edge weight) + bias of a seen column it takes pen_logit(v, p) instead, before the mask's select: in the
+// first walk (plain and TOPK), in the exp-sum walk - the same expression, so v' - best is exactly 0 at the winner - and at the
+// target column.  Rows m >= M read nothing (no bit, p = 1).  The edge weights are skipped where aut_state is null.
 template <int BM, int BN, int NT, bool SWZ, bool LSE = false, bool TOPK = false, bool MASK = false, bool TGT = false, bool SOFT = false,
-          typename P = GemmParams>
+          typename P = GemmParams, bool PEN = false>
 __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const P& p, int m0, int n0, int tid) {
     static_assert(!SOFT || MASK, "the weighted LM head is a masked one");
+    static_assert(!PEN || SOFT, "the penalised LM head is the weighted one too");
     constexpr int TPRW = NT / BM, CPP = BN / TPRW;
     static_assert(TPRW == 2 || TPRW == 4, "two or four threads per row");
     const int row = tid / TPRW, part = tid % TPRW;
@@ -223,8 +236,26 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const P& p
             mbits = mrow[g0 >> 5] >> (g0 & 31);
         }
     }
-    if constexpr (SOFT) {
+    // PEN: bit (c - g0) of sbits = logical column c of the thread's group is in the row; pp = the row's penalty
+    unsigned long long sbits = 0ull;
+    float pp = 1.f;
+    if constexpr (PEN) {
         if (m < p.M) {
+            const int brow = p.rowmap ? p.rowmap[m] : m;
+            const unsigned* srow = p.seen_mask + (size_t)brow * (p.N >> 5);
+            if constexpr (CPP == 64) {
+                const uint2 w2 = *reinterpret_cast<const uint2*>(srow + (g0 >> 5));
+                sbits = ((unsigned long long)w2.y << 32) | w2.x;
+            } else {
+                sbits = srow[g0 >> 5] >> (g0 & 31);
+            }
+            pp = p.penalty_of_row[brow];
+        }
+    }
+    if constexpr (SOFT) {
+        bool weigh = m < p.M;
+        if constexpr (PEN) weigh = weigh && p.aut_state != nullptr;
+        if (weigh) {
             const int s = p.aut_state[p.rowmap ? p.rowmap[m] : m];
             if (s >= 0) {
                 float* const srow = const_cast<float*>(sC) + row * BN;
@@ -253,7 +284,15 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const P& p
             const float4 cv = *reinterpret_cast<const float4*>(&sC[row * BN + pc]);
             const int n = n0 + (pc ^ sw);
             const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-            if constexpr (MASK) {
+            if constexpr (PEN) {
+                const unsigned nib = (unsigned)(mbits >> (n - g0)) & 15u;
+                const unsigned snib = (unsigned)(sbits >> (n - g0)) & 15u;
+                const float vx = cv.x + bv.x, vy = cv.y + bv.y, vz = cv.z + bv.z, vw = cv.w + bv.w;
+                top4_insert(top, (nib & 1) ? ((snib & 1) ? pen_logit(vx, pp) : vx) : -INFINITY, (nib & 1) ? n : 0x7fffffff);
+                top4_insert(top, (nib & 2) ? ((snib & 2) ? pen_logit(vy, pp) : vy) : -INFINITY, (nib & 2) ? n + 1 : 0x7fffffff);
+                top4_insert(top, (nib & 4) ? ((snib & 4) ? pen_logit(vz, pp) : vz) : -INFINITY, (nib & 4) ? n + 2 : 0x7fffffff);
+                top4_insert(top, (nib & 8) ? ((snib & 8) ? pen_logit(vw, pp) : vw) : -INFINITY, (nib & 8) ? n + 3 : 0x7fffffff);
+            } else if constexpr (MASK) {
                 const unsigned nib = (unsigned)(mbits >> (n - g0)) & 15u;
                 top4_insert(top, (nib & 1) ? cv.x + bv.x : -INFINITY, (nib & 1) ? n : 0x7fffffff);
                 top4_insert(top, (nib & 2) ? cv.y + bv.y : -INFINITY, (nib & 2) ? n + 1 : 0x7fffffff);
@@ -276,7 +315,13 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const P& p
         const float4 cv = *reinterpret_cast<const float4*>(&sC[row * BN + pc]);
         const int n = n0 + (pc ^ sw);                                // logical (global) column of cv.x
         const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-        const float v[4] = {cv.x + bv.x, cv.y + bv.y, cv.z + bv.z, cv.w + bv.w};
+        float v[4] = {cv.x + bv.x, cv.y + bv.y, cv.z + bv.z, cv.w + bv.w};
+        if constexpr (PEN) {
+            const unsigned snib = (unsigned)(sbits >> (n - g0)) & 15u;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if ((snib >> e) & 1) v[e] = pen_logit(v[e], pp);
+        }
         if constexpr (MASK) {
             const unsigned nib = (unsigned)(mbits >> (n - g0)) & 15u;
 #pragma unroll
@@ -302,7 +347,15 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const P& p
             const int pc = part * CPP + ((rot + 4 * q) % CPP);
             const float4 cv = *reinterpret_cast<const float4*>(&sC[row * BN + pc]);
             const float4 bv = *reinterpret_cast<const float4*>(p.bias + n0 + (pc ^ sw));
-            if constexpr (MASK) {
+            if constexpr (PEN) {
+                const unsigned nib = (unsigned)(mbits >> (n0 + (pc ^ sw) - g0)) & 15u;
+                const unsigned snib = (unsigned)(sbits >> (n0 + (pc ^ sw) - g0)) & 15u;
+                const float vx = cv.x + bv.x, vy = cv.y + bv.y, vz = cv.z + bv.z, vw = cv.w + bv.w;
+                esum += (((nib & 1) ? __expf(((snib & 1) ? pen_logit(vx, pp) : vx) - best) : 0.f) +
+                         ((nib & 2) ? __expf(((snib & 2) ? pen_logit(vy, pp) : vy) - best) : 0.f)) +
+                        (((nib & 4) ? __expf(((snib & 4) ? pen_logit(vz, pp) : vz) - best) : 0.f) +
+                         ((nib & 8) ? __expf(((snib & 8) ? pen_logit(vw, pp) : vw) - best) : 0.f));
+            } else if constexpr (MASK) {
                 const unsigned nib = (unsigned)(mbits >> (n0 + (pc ^ sw) - g0)) & 15u;
                 esum += (((nib & 1) ? __expf((cv.x + bv.x) - best) : 0.f) + ((nib & 2) ? __expf((cv.y + bv.y) - best) : 0.f)) +
                         (((nib & 4) ? __expf((cv.z + bv.z) - best) : 0.f) + ((nib & 8) ? __expf((cv.w + bv.w) - best) : 0.f));
@@ -321,7 +374,10 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const P& p
             if ((unsigned)t < (unsigned)p.prefix_len[brow]) {
                 const int tgt = p.prefix[(size_t)brow * p.prefix_ld + t];
                 if (tgt >= g0 && tgt < g0 + CPP) {          // (logical column tgt - n0 sits at physical column (tgt - n0) ^ sw)
-                    const float v = sC[row * BN + ((tgt - n0) ^ sw)] + p.bias[tgt];
+                    float v = sC[row * BN + ((tgt - n0) ^ sw)] + p.bias[tgt];
+                    if constexpr (PEN) {
+                        if ((sbits >> (tgt - g0)) & 1ull) v = pen_logit(v, pp);
+                    }
                     p.tgt_val[m] = ((mbits >> (tgt - g0)) & 1ull) ? v : -INFINITY;
                 }
             }
@@ -363,10 +419,12 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
 // tile: 4 x 16 KiB) so a DMA has three K-tiles of time to land.
 // TGT (EPI_ARGMAX_LSE_M / EPI_TOPK_M only): the epilogue also stores the forced prefixes' target column (GemmParams::tgt_val).
 // SOFT (the three EPI_*_M forms only): the epilogue first adds the rows' automaton edge weights; the argument is a GemmParamsSoft.
-template <typename T, int BM, int BN, int EPI, int NST = 2, bool TGT = false, bool SOFT = false>
-__global__ __launch_bounds__(256) void gemm_kernel(std::conditional_t<SOFT, GemmParamsSoft, GemmParams> p) {
+// PEN (with SOFT): ... and applies the rows' repetition penalties to their seen columns; the argument is a GemmParamsPen.
+template <typename T, int BM, int BN, int EPI, int NST = 2, bool TGT = false, bool SOFT = false, bool PEN = false>
+__global__ __launch_bounds__(256) void gemm_kernel(std::conditional_t<PEN, GemmParamsPen, std::conditional_t<SOFT, GemmParamsSoft, GemmParams>> p) {
     static_assert(!SOFT || EPI == EPI_ARGMAX_M || EPI == EPI_ARGMAX_LSE_M || EPI == EPI_TOPK_M, "edge weights go into the masked LM head");
-    using P = std::conditional_t<SOFT, GemmParamsSoft, GemmParams>;
+    static_assert(!PEN || SOFT, "the penalised LM head is the weighted one too");
+    using P = std::conditional_t<PEN, GemmParamsPen, std::conditional_t<SOFT, GemmParamsSoft, GemmParams>>;
     constexpr int TM = BM / 64, TN = BN / 64;          // 32x32 MFMA tiles per wave
     constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE = A_BYTES + B_BYTES;
     constexpr int LPT = (BM / 8 + BN / 8) / 4;         // DMA instructions per wave per K-tile
@@ -556,11 +614,11 @@ __global__ __launch_bounds__(256) void gemm_kernel(std::conditional_t<SOFT, Gemm
     } else if constexpr (EPI == EPI_TOPK) {
         gemm_epilogue_argmax<BM, BN, 256, SWZ, true, true>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_ARGMAX_M) {
-        gemm_epilogue_argmax<BM, BN, 256, SWZ, false, false, true, false, SOFT, P>(sC, p, m0, n0, tid);
+        gemm_epilogue_argmax<BM, BN, 256, SWZ, false, false, true, false, SOFT, P, PEN>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_ARGMAX_LSE_M) {
-        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, false, true, TGT, SOFT, P>(sC, p, m0, n0, tid);
+        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, false, true, TGT, SOFT, P, PEN>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_TOPK_M) {
-        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, true, true, TGT, SOFT, P>(sC, p, m0, n0, tid);
+        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, true, true, TGT, SOFT, P, PEN>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_BIAS) {
         GemmParams q = p;
         q.out = reinterpret_cast<T*>(p.out) + (size_t)blockIdx.y * p.o_yoff;

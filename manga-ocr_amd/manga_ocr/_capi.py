@@ -184,6 +184,18 @@ SYMBOLS = {
     "mocr_op_automaton_init_soft": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "mocr_op_gemm_argmax_soft": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                            C.c_int32, _P, _P, C.POINTER(MocrSoftTables)]),
+    "mocr_recognize_images_penalty": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                C.c_int32, _P, _P, _P]),
+    "mocr_recognize_regions_penalty": (C.c_int, [_P, C.POINTER(MocrImage), C.c_int32, C.POINTER(MocrRegion), C.c_int32, C.c_int32, _P, _P, _P,
+                                                 _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    "mocr_recognize_device_penalty": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    "mocr_recognize_gray_host_penalty": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                   C.c_int32, _P, _P, _P]),
+    "mocr_op_dec_token_penalty": (C.c_int, [_P, C.POINTER(MocrTokenArgs), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P,
+                                            _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mocr_op_penalty_init": (C.c_int, [_P, _P, C.c_int32]),
+    "mocr_op_gemm_argmax_penalty": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
+                                              C.c_int32, _P, _P, C.POINTER(MocrSoftTables), _P, _P]),
     "mocr_op_enc_expand": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),
     "mocr_graph_count": (C.c_int, [_P]),
     "mocr_compaction_count": (C.c_int64, [_P]),

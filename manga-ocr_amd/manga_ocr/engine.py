@@ -282,6 +282,26 @@ class Engine:
             raise ValueError(f"no_repeat_ngram: sizes must be in 0 .. max_len ({self.spec.max_len}), 0 = off")
         return np.ascontiguousarray(a, dtype=np.int32)
 
+    # ------------------------------------------------------------------ repetition penalty
+    @staticmethod
+    def _penalty(penalty, n: int) -> np.ndarray:
+        """``penalty=``: one p for every row, or one per row -> float32 [n], each finite and > 0 (1 = off)"""
+        if isinstance(penalty, (bool, np.bool_, str, bytes)):
+            raise TypeError(f"penalty: a float or a sequence of floats, instead got {penalty!r}")
+        if isinstance(penalty, (int, float, np.integer, np.floating)):
+            a = np.full(n, float(penalty), dtype=np.float64)
+        else:
+            vals = list(penalty)
+            if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) for v in vals):
+                raise TypeError("penalty: the values must be floats")
+            a = np.asarray(vals, dtype=np.float64).ravel()
+            if a.size != n:
+                raise ValueError(f"penalty: {n} rows but {a.size} values")
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size and not (np.isfinite(a).all() and (a > 0).all()):
+            raise ValueError("penalty: a repetition penalty is finite and > 0 (1 = off)")
+        return a
+
     # ------------------------------------------------------------------ forced prefixes
     @staticmethod
     def _prefixes(prefixes, n: int):
@@ -363,7 +383,7 @@ class Engine:
         return sets, ngram
 
     def _recognize(self, kind: str, n: int, lead, tail=(), *, beam, d_out=None, skip_empty: bool = False, beam_scores=False, beam_sets=None,
-                   beam_positions=False, beam_automata=None, beam_states=False, beam_soft=False, **req):
+                   beam_positions=False, beam_automata=None, beam_states=False, beam_soft=False, penalty=None, **req):
         """The one request path under recognize_images / _regions / _gray / _device.  ``kind``: the source kind as the C symbols
         spell it; ``n``: its number of sources; ``lead()``: (the call's leading C arguments, sources counted last; whatever they
         point into, kept until the call returns) - built only once the call is going to be made; ``tail``: what follows the
@@ -387,8 +407,13 @@ class Engine:
         mocr_recognize_{kind}_beam_automaton - the _beam_positions call plus (automata, out_state), null where not asked - and
         a host kind returns state int32 [n,K] as the LAST element, behind pos.  ``beam_soft=True`` (a beam call, too): the symbol
         is mocr_recognize_{kind}_beam_soft, the same argument list with soft handles allowed among ``beam_automata``
-        (include/mocr.h, "beam search under soft token automata"); without the flag every call is the one it was."""
+        (include/mocr.h, "beam search under soft token automata"); without the flag every call is the one it was.
+        ``penalty`` (one repetition penalty for every row, or one per row; include/mocr.h, "repetition penalty"): the symbol is
+        mocr_recognize_{kind}_penalty, the _automaton call plus the penalties; a beam call refuses it; None is every call as it
+        was."""
         host = d_out is None
+        if beam is not None and penalty is not None:
+            raise ValueError("beam search does not combine with penalty")
         automata, states = req.pop("automata", None), req.pop("states" if host else "d_out_state", None)
         if beam is not None and (automata is not None or (states is not None and states is not False)):
             raise ValueError("beam search does not combine with automata / states")
@@ -463,6 +488,11 @@ class Engine:
                 variant, shared, forced = "automaton", shared or (rows, _ptr(None)), (_ptr(pre), _ptr(plen), ld)
                 handles = self._automata(automata, rows) if automata is not None else None      # (kept until the call returns)
                 forced += (_ptr(handles), _ptr(state))
+            if penalty is not None:         # the automaton call (automata / out_state null where not given) plus one
+                pen = self._penalty(penalty, rows)          # (kept until the call returns)
+                if variant != "automaton":
+                    variant, shared, forced = "automaton", shared or (rows, _ptr(None)), (_ptr(pre), _ptr(plen), ld, _ptr(None), _ptr(None))
+                variant, forced = "penalty", forced + (_ptr(pen),)
             self._check(getattr(self.lib, f"mocr_recognize_{kind}_{variant}")(self._h, *args, *shared, *tail, *map(_ptr, blocks[:5]), _ptr(sets), _ptr(ngram),
                                                                             _ptr(blocks[5]), *forced))
         if not host:
@@ -472,7 +502,7 @@ class Engine:
     def recognize_images(self, images, bgr: bool = False, rotate=None, *, scores: bool = False, alternatives: bool = False,
                          token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
                          beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False,
-                         beam_automata=None, beam_states: bool = False, beam_soft: bool = False):
+                         beam_automata=None, beam_states: bool = False, beam_soft: bool = False, penalty=None):
         """Crops of any sizes (list of uint8 [h,w] / [h,w,3] arrays; `bgr`: 3-channel crops are in OpenCV order;
         `rotate`: per crop 0 / 1 (90 degrees clockwise) / 2 (counter-clockwise), applied on the device): luminance
         conversion and the Pillow-exact BILINEAR resize to 224x224 run on the device.
@@ -516,18 +546,20 @@ class Engine:
         refused with ``beam``.
         ``beam_soft=True`` (only with ``beam``; include/mocr.h, "beam search under soft token automata"): ``beam_automata`` may
         hold SOFT automata - their edge weights are added to the log-probabilities behind the log_softmax and enter the
-        hypotheses' scores (transformers' ``generate(num_beams=K, sequence_bias=...)``).  Without it a soft handle is refused."""
+        hypotheses' scores (transformers' ``generate(num_beams=K, sequence_bias=...)``).  Without it a soft handle is refused.
+        ``penalty``: transformers' ``repetition_penalty`` under greedy decoding, one float for every ROW or one per row, finite
+        and > 0, 1 = off (include/mocr.h, "repetition penalty"); combines with everything but ``beam``."""
         def lead():
             descs, keep = self._image_descs(images, bgr, rotate)
             return (descs, len(keep)), keep
         return self._recognize("images", len(images), lead, beam=beam, beam_scores=beam_scores, beam_sets=beam_sets, beam_positions=beam_positions, skip_empty=True, scores=scores, alternatives=alternatives, token_sets=token_sets,
                                no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources, automata=automata, states=states,
-                               beam_automata=beam_automata, beam_states=beam_states, beam_soft=beam_soft)
+                               beam_automata=beam_automata, beam_states=beam_states, beam_soft=beam_soft, penalty=penalty)
 
     def recognize_regions(self, pages, regions, bgr: bool = True, *, scores: bool = False, alternatives: bool = False,
                           token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
                           beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False,
-                         beam_automata=None, beam_states: bool = False, beam_soft: bool = False):
+                         beam_automata=None, beam_states: bool = False, beam_soft: bool = False, penalty=None):
         """pages: list of uint8 [H,W,3] (or [H,W]) arrays; regions: iterable of (page_index, x, y, w, h) bounding
         rectangles.  Each page is uploaded once; the 8 %-padded, page-clipped crop of every region
         (``src/ui/main_window.py:9530-9540``) is cut on the device.  Returns (ids [n,max_len], lengths [n]);
@@ -554,7 +586,7 @@ class Engine:
             return (descs, len(keep), arr, len(regs)), keep
         return self._recognize("regions", len(regs), lead, beam=beam, beam_scores=beam_scores, beam_sets=beam_sets, beam_positions=beam_positions, skip_empty=True, scores=scores, alternatives=alternatives, token_sets=token_sets,
                                no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes, sources=sources, automata=automata, states=states,
-                               beam_automata=beam_automata, beam_states=beam_states, beam_soft=beam_soft)
+                               beam_automata=beam_automata, beam_states=beam_states, beam_soft=beam_soft, penalty=penalty)
 
     def graph_count(self) -> int:
         return int(self.lib.mocr_graph_count(self._h))
@@ -604,7 +636,7 @@ class Engine:
     def recognize_device(self, d_gray, n: int, d_out_ids, d_out_len, d_out_logp=None, d_out_alt_ids=None, d_out_alt_logp=None, *,
                          token_sets=None, no_repeat_ngram=None, d_out_pos=None, prefixes=None, sources=None, beam=None,
                          d_out_score=None, d_out_beam_logp=None, beam_sets=None, d_out_beam_pos=None, automata=None,
-                         d_out_state=None, beam_automata=None, d_out_beam_state=None, beam_soft: bool = False) -> None:
+                         d_out_state=None, beam_automata=None, d_out_beam_state=None, beam_soft: bool = False, penalty=None) -> None:
         """Asynchronous; all are device buffers (torch CUDA tensors or raw addresses).  ``d_out_logp`` (float32
         [n,max_len]): also the token log-probabilities.  ``d_out_alt_ids`` (int32) with ``d_out_alt_logp`` (float32), both
         [n,max_len,4]: also the token alternatives.  ``token_sets``: a set handle for every crop, or one per crop (host values).
@@ -623,7 +655,7 @@ class Engine:
                         d_out_alt_ids=d_out_alt_ids, d_out_alt_logp=d_out_alt_logp, token_sets=token_sets, no_repeat_ngram=no_repeat_ngram,
                         d_out_pos=d_out_pos, prefixes=prefixes, sources=sources, automata=automata, d_out_state=d_out_state,
                         beam_automata=beam_automata, beam_states=d_out_beam_state if d_out_beam_state is not None else False,
-                        beam_soft=beam_soft)
+                        beam_soft=beam_soft, penalty=penalty)
 
     def set_generate_max_length(self, max_len: int) -> None:
         self._check(self.lib.mocr_set_generate_max_length(self._h, int(max_len)))
@@ -631,7 +663,7 @@ class Engine:
     def recognize_gray(self, gray: np.ndarray, max_len: Optional[int] = None, *, scores: bool = False, alternatives: bool = False,
                        token_sets=None, no_repeat_ngram=None, positions: bool = False, prefixes=None, sources=None, beam=None,
                        beam_scores: bool = False, beam_sets=None, beam_positions: bool = False, automata=None, states: bool = False,
-                         beam_automata=None, beam_states: bool = False, beam_soft: bool = False):
+                         beam_automata=None, beam_states: bool = False, beam_soft: bool = False, penalty=None):
         """Luminance planes uint8 [n,224,224] (host), generate(max_length) ``max_len``; the keywords as for recognize_images
         (``sources``: one plane index per output row; ``beam``: (ids [n,K,max_len], lengths [n,K], scores [n,K]), with ``beam_scores`` also
         logp [n,K,max_len]; ``beam_sets``: one set per plane; ``beam_positions``: also pos [n,K,max_len,5], last)."""
@@ -640,7 +672,7 @@ class Engine:
                                beam_sets=beam_sets, beam_positions=beam_positions, scores=scores,
                                alternatives=alternatives, token_sets=token_sets, no_repeat_ngram=no_repeat_ngram, positions=positions, prefixes=prefixes,
                                sources=sources, automata=automata, states=states,
-                               beam_automata=beam_automata, beam_states=beam_states, beam_soft=beam_soft)
+                               beam_automata=beam_automata, beam_states=beam_states, beam_soft=beam_soft, penalty=penalty)
 
     # ------------------------------------------------------------------ test hooks
     def encode(self, d_gray, n: int) -> np.ndarray:
@@ -937,6 +969,39 @@ class Engine:
                                                       _ptr(d_cand_sum), _ptr(d_top_val), _ptr(d_top_idx), M, N, K, tile,
                                                       _ptr(d_tok_mask), _ptr(d_set_of_row), _ptr(d_rowmap), _ptr(d_prefix),
                                                       _ptr(d_prefix_len), int(prefix_ld), _ptr(d_step), _ptr(d_tgt_val), soft))
+
+    def op_dec_token_penalty(self, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row,
+                             d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, d_prefix, d_prefix_len, prefix_ld, d_tgt_val,
+                             d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state, d_edge_weight,
+                             d_default_next, d_seen_mask, d_penalty_of_row, **kw) -> None:
+        """The token step with a repetition penalty: op_dec_token_soft plus the rows' seen words and penalties (include/mocr.h
+        mocr_op_dec_token_penalty); both None is that call, and the automaton arrays may all be None beside them."""
+        self._check(self.lib.mocr_op_dec_token_penalty(
+            self._h, self._args(_capi.MocrTokenArgs, kw), _ptr(d_cand_sum), _ptr(d_scores), _ptr(d_top_val), _ptr(d_top_idx),
+            _ptr(d_alt_ids), _ptr(d_alt_logp), _ptr(d_tok_mask), _ptr(d_set_of_row), _ptr(d_row_mask), _ptr(d_base_mask),
+            _ptr(d_base_set_of_row), _ptr(d_ngram_of_row), _ptr(d_prefix), _ptr(d_prefix_len), int(prefix_ld), _ptr(d_tgt_val),
+            _ptr(d_edge_begin), _ptr(d_edge_token), _ptr(d_edge_next), _ptr(d_accepting), _ptr(d_aut_base_of_row), _ptr(d_aut_state),
+            _ptr(d_edge_weight), _ptr(d_default_next), _ptr(d_seen_mask), _ptr(d_penalty_of_row)))
+
+    def op_penalty_init(self, d_seen_mask, rows: int) -> None:
+        """Start of a batch with a repetition penalty: every row's seen words = the start token's bit alone."""
+        self._check(self.lib.mocr_op_penalty_init(self._h, _ptr(d_seen_mask), int(rows)))
+
+    def op_gemm_argmax_penalty(self, dA, dW, d_bias, d_cand_val, d_cand_idx, d_cand_sum, d_top_val, d_top_idx, M, N, K, tile,
+                               d_tok_mask, d_set_of_row, d_rowmap, d_prefix, d_prefix_len, prefix_ld, d_step, d_tgt_val,
+                               d_aut_state=None, d_edge_begin=None, d_edge_token=None, d_edge_weight=None, d_seen_mask=None,
+                               d_penalty_of_row=None) -> None:
+        """The masked LM head with a repetition penalty (include/mocr.h mocr_op_gemm_argmax_penalty): op_gemm_argmax_soft plus
+        the rows' seen words and penalties; the four soft arguments all None is a penalty without any automaton."""
+        soft = None
+        if not (d_aut_state is None and d_edge_begin is None and d_edge_token is None and d_edge_weight is None):
+            soft = self._args(_capi.MocrSoftTables, dict(d_aut_state=d_aut_state, d_edge_begin=d_edge_begin, d_edge_token=d_edge_token,
+                                                          d_edge_weight=d_edge_weight))
+        self._check(self.lib.mocr_op_gemm_argmax_penalty(self._h, _ptr(dA), _ptr(dW), _ptr(d_bias), _ptr(d_cand_val), _ptr(d_cand_idx),
+                                                         _ptr(d_cand_sum), _ptr(d_top_val), _ptr(d_top_idx), M, N, K, tile,
+                                                         _ptr(d_tok_mask), _ptr(d_set_of_row), _ptr(d_rowmap), _ptr(d_prefix),
+                                                         _ptr(d_prefix_len), int(prefix_ld), _ptr(d_step), _ptr(d_tgt_val), soft,
+                                                         _ptr(d_seen_mask), _ptr(d_penalty_of_row)))
 
     def op_ngram_init(self, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows: int) -> None:
         """Start of a batch with no-repeat n-grams: every row's mask = its base set (n = 1: minus the start token)."""

@@ -263,6 +263,8 @@ class MultiGpuEngine:
                       "engine): construct MangaOcr on one device to use token_set / allowed=")
     NO_NGRAM = ("no-repeat n-grams are not implemented for several devices (manga_ocr/multi.py: the workers make the plain greedy "
                 "call): construct MangaOcr on one device to use no_repeat_ngram_size / no_repeat_ngram=")
+    NO_PENALTY = ("a repetition penalty is not implemented for several devices (manga_ocr/multi.py: the workers make the plain greedy "
+                  "call): construct MangaOcr on one device to use repetition_penalty=")
     NO_POSITIONS = ("token positions are not implemented for several devices (manga_ocr/multi.py ships ids and lengths only): "
                     "construct MangaOcr on one device to use the *_positions calls")
     NO_PREFIX = ("forced prefixes are not implemented for several devices (manga_ocr/multi.py: the workers make the plain greedy "

@@ -150,6 +150,44 @@ def resolve_no_repeat_ngram(value, ignored: dict, max_len: int):
     return int(value), ignored
 
 
+def resolve_repetition_penalty(value, ignored: dict):
+    """``MangaOcr(repetition_penalty=...)`` -> (the penalty every call uses by default; what is then still ignored of the
+    checkpoint's generation config).  1.0 = off, as always; a float, finite and > 0; ``"checkpoint"`` = the checkpoint's
+    ``repetition_penalty`` (1.0 when its config has none), which is then honoured and leaves the ignored settings."""
+    ignored = dict(ignored)
+    if isinstance(value, str):
+        if value != "checkpoint":
+            raise ValueError(f"repetition_penalty: a float or 'checkpoint', instead got {value!r}")
+        value = ignored.pop("repetition_penalty", 1.0)
+    return _penalty_value(value, "repetition_penalty"), ignored
+
+
+def _penalty_value(value, name: str) -> float:
+    """one repetition penalty: a real number, finite and > 0"""
+    import math
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{name}: a float (finite, > 0; 1 = off), instead got {value!r}")
+    if not math.isfinite(float(value)) or not float(value) > 0:
+        raise ValueError(f"{name} must be finite and > 0 (1 = off; below 1 rewards repeats); got {value!r}")
+    return float(value)
+
+
+def _penalties(repetition_penalty, default: float, n: int) -> Optional[List[float]]:
+    """``repetition_penalty=`` of a call (None: the constructor's ``default``), one float for all crops or one per crop ->
+    one per crop, or None when every crop is at 1 (the call the method always made)"""
+    if repetition_penalty is None:
+        repetition_penalty = default
+    if isinstance(repetition_penalty, (str, bytes)):
+        raise TypeError(f"repetition_penalty: a float or a sequence of floats, instead got {repetition_penalty!r}")
+    if isinstance(repetition_penalty, (bool, np.bool_, int, float, np.integer, np.floating)):
+        ps = [_penalty_value(repetition_penalty, "repetition_penalty")] * n
+    else:
+        ps = [_penalty_value(p, "repetition_penalty") for p in repetition_penalty]
+        if len(ps) != n:
+            raise ValueError(f"repetition_penalty: {n} crops but {len(ps)} values")
+    return ps if any(p != 1.0 for p in ps) else None
+
+
 def resolve_num_beams(value, ignored: dict, ngram_default=None):
     """``MangaOcr(num_beams=...)`` -> (the :class:`BeamConfig` every plain call decodes with, or None for today's greedy
     behaviour; what is left of the checkpoint's ignored generation settings).  ``None``: nothing changes.  ``"checkpoint"``:
@@ -386,6 +424,7 @@ class _Request(NamedTuple):
     beam_automaton: int = 0             # a beam request (``match``): the automaton its beams walk, 0: none; such a caller gets its
                                         # hypotheses' states [K], last
     beam_soft: bool = False             # ... and that automaton may be soft (``search``): the batch makes the *_beam_soft call
+    penalty: float = 1.0                # repetition penalty, 1: off
 
 
 class _Batcher:
@@ -409,7 +448,9 @@ class _Batcher:
     only a caller that asked gets pos [K, max_len, 5] as its last element.  And for a beam request's token automaton
     (``beam_automaton``, the ``match`` methods): only a beam batch with such a request passes ``beam_automata=`` (one handle per
     crop, 0 for the others) and ``beam_states=True``, and only such a caller gets state [K], behind everything else.  A
-    ``search`` request marks its automaton ``beam_soft``: only a beam batch with such a request passes ``beam_soft=True``."""
+    ``search`` request marks its automaton ``beam_soft``: only a beam batch with such a request passes ``beam_soft=True``.  A
+    greedy request may carry a repetition penalty (``repetition_penalty=``): only a batch with a request of p != 1 passes
+    ``penalty=``, one value per crop, 1 for the others."""
 
     def __init__(self, engine: Engine, max_batch: int, timeout_ms: float):
         self.engine, self.max_batch, self.timeout = engine, max_batch, timeout_ms / 1000.0
@@ -422,14 +463,14 @@ class _Batcher:
     def submit(self, gray: np.ndarray, scored: bool = False, alternatives: bool = False, token_set: int = 0,
                no_repeat_ngram: int = 0, positions: bool = False, prefix=None, beam: Optional[BeamConfig] = None,
                beam_scores: bool = False, beam_set: int = 0, beam_positions: bool = False, automaton: int = 0,
-               beam_automaton: int = 0, beam_soft: bool = False) -> Future:
+               beam_automaton: int = 0, beam_soft: bool = False, penalty: float = 1.0) -> Future:
         f: Future = Future()
         with self._cv:
             if self._stop:
                 raise RuntimeError("MangaOcr is closed")
             self._q.append(_Request(gray, f, bool(scored or alternatives), bool(alternatives), bool(positions), int(token_set), int(no_repeat_ngram),
                                     tuple(prefix) if prefix else None, beam, bool(beam_scores), int(beam_set), bool(beam_positions), int(automaton),
-                                    int(beam_automaton), bool(beam_soft)))
+                                    int(beam_automaton), bool(beam_soft), float(penalty)))
             self._cv.notify()
         return f
 
@@ -488,6 +529,8 @@ class _Batcher:
                 if any(r.automaton for r in batch):         # (the same again for a token automaton, ``lexicon=``)
                     kw["automata"] = [r.automaton for r in batch]
                     kw["states"] = True
+                if any(r.penalty != 1.0 for r in batch):    # (and for a repetition penalty)
+                    kw["penalty"] = [r.penalty for r in batch]
                 res = self.engine.recognize_images([r.gray for r in batch], **kw)
                 state = res[-1] if kw.get("states") else None
                 got = dict(zip(result_layout(kw.get("scores", False), kw.get("alternatives", False), kw.get("positions", False)), res))
@@ -580,7 +623,8 @@ class _Single(NamedTuple):
     @staticmethod
     def batcher_kw(kw: dict) -> dict:
         """one row's engine keywords (``MangaOcr._decode_kw``) as ``_Batcher.submit`` names them"""
-        names = (("token_sets", "token_set"), ("no_repeat_ngram", "no_repeat_ngram"), ("prefixes", "prefix"), ("automata", "automaton"))
+        names = (("token_sets", "token_set"), ("no_repeat_ngram", "no_repeat_ngram"), ("prefixes", "prefix"), ("automata", "automaton"),
+                 ("penalty", "penalty"))
         return {single: kw[many][0] for many, single in names if many in kw}
 
     def call(self, ocr, scores: bool = False, alternatives: bool = False, positions: bool = False, states: bool = False, **kw):
@@ -594,7 +638,7 @@ class MangaOcr:
     def __init__(self, pretrained_model_name_or_path: str = DEFAULT_MODEL, force_cpu: bool = False, *,
                  dtype: Optional[str] = None, device: Optional[int] = None, devices: Optional[Sequence[int]] = None,
                  max_batch: Optional[int] = None, lanes: Optional[int] = None, batch_timeout_ms: Optional[float] = None,
-                 synthetic_seed: Optional[int] = None, no_repeat_ngram_size=None, num_beams=None):
+                 synthetic_seed: Optional[int] = None, no_repeat_ngram_size=None, num_beams=None, repetition_penalty=1.0):
         """``MangaOcr()`` as the application calls it (``src/ui/main_window.py:3394``) builds the engine on this
         process's GPU with two lanes and an internal batch sized from the free HBM.  ``devices=[0, 1, ...]`` (or
         ``MANGA_OCR_DEVICES=0,1,...``) instead starts one child process per GPU and shards every batch call over
@@ -616,7 +660,12 @@ class MangaOcr:
         (``recognize_scored``, ``recognize_alternatives``, ``recognize_nbest`` and their batch forms, ``score_text``) keep decoding
         greedily: they return one greedy row per crop, with its alternatives or prefix; use ``recognize_beam`` for all
         hypotheses with their sequence scores - and, with ``token_scores=True`` / ``allowed=`` / ``positions=True``, their token
-        log-probabilities, a search under a token set and their token positions."""
+        log-probabilities, a search under a token set and their token positions.
+        ``repetition_penalty``: transformers' setting of that name under this engine's greedy decoding (include/mocr.h,
+        "repetition penalty") for every greedy call that does not say otherwise (``repetition_penalty=``): 1.0 = off, as always;
+        a float, finite and > 0 (below 1 rewards repeats); or ``"checkpoint"`` = the value in the checkpoint's generation
+        config, which then leaves ``ignored_generation_config``.  It does not combine with ``num_beams`` (under beams
+        transformers penalises log-probabilities, which this engine does not do yet): ``ValueError``."""
         if force_cpu:
             raise RuntimeError("this MangaOcr is the MI355X engine: there is no CPU path (force_cpu=True is not supported)")
         dtype = dtype or os.environ.get("MANGA_OCR_DTYPE", "bf16")
@@ -662,6 +711,9 @@ class MangaOcr:
         # do the *_positions methods decode with those beams too (the best hypothesis with its positions)?  Every MangaOcr this
         # constructor builds with beams says yes; an instance that holds ``beam`` alone keeps the greedy positions rows it had
         self.beam_positions = self.beam is not None
+        self.repetition_penalty, self.ignored_generation_config = resolve_repetition_penalty(repetition_penalty, self.ignored_generation_config)
+        if self.beam is not None and self.repetition_penalty != 1.0:
+            raise ValueError("repetition_penalty does not combine with num_beams: beam search takes no repetition penalty")
         if num_beams is not None and self.ignored_generation_config:
             import warnings
             warnings.warn("checkpoint config asks for generation settings this engine still ignores: " + repr(self.ignored_generation_config) +
@@ -673,6 +725,9 @@ class MangaOcr:
         if self.beam is not None and devices is not None and len(devices) > 1:
             from .multi import MultiGpuEngine
             raise NotImplementedError(MultiGpuEngine.NO_BEAM)
+        if self.repetition_penalty != 1.0 and devices is not None and len(devices) > 1:
+            from .multi import MultiGpuEngine
+            raise NotImplementedError(MultiGpuEngine.NO_PENALTY)
         if devices is not None and len(devices) > 1:
             from .multi import MultiGpuEngine
             max_batch = int(max_batch or 2048)
@@ -703,7 +758,7 @@ class MangaOcr:
         return self.recognize(img_or_path)
 
     def _require(self, what: str) -> None:
-        """refuse ``what`` (SCORES, CONSTRAINTS, NGRAM, PREFIX, POSITIONS, ALTERNATIVES, BEAM, BEAM_POSITIONS) on an engine that says it cannot:
+        """refuse ``what`` (SCORES, CONSTRAINTS, NGRAM, PREFIX, POSITIONS, ALTERNATIVES, BEAM, BEAM_POSITIONS, PENALTY) on an engine that says it cannot:
         MultiGpuEngine, whose workers make the plain greedy call and ship ids and lengths only, has a NO_* message for each"""
         no = getattr(self.engine, "NO_" + what, None)
         if no:
@@ -827,9 +882,11 @@ class MangaOcr:
         return dict(token_sets=hs)
 
     # ------------------------------------------------------------------ the request path: a source x a result kind
-    def _decode_kw(self, allowed, no_repeat_ngram, n: int, prefix=None) -> dict:
-        """the engine keywords of ``allowed=``, ``no_repeat_ngram=`` and ``prefix=`` ({} when none is in use: the call the method
-        always made); a call's ``no_repeat_ngram`` overrides the constructor's ``no_repeat_ngram_size`` (0 = off for this call)"""
+    def _decode_kw(self, allowed, no_repeat_ngram, n: int, prefix=None, repetition_penalty=1.0) -> dict:
+        """the engine keywords of ``allowed=``, ``no_repeat_ngram=``, ``prefix=`` and ``repetition_penalty=`` ({} when none is in
+        use: the call the method always made); a call's ``no_repeat_ngram`` overrides the constructor's ``no_repeat_ngram_size``
+        (0 = off for this call); ``repetition_penalty`` is the call's own (``_run`` resolves the constructor's default; the
+        n-best and text-scoring methods, which take no penalty, leave it at 1)"""
         kw = self._allowed(allowed, n)
         gs = _ngram_sizes(no_repeat_ngram, getattr(self, "no_repeat_ngram_size", None), n)
         if gs is not None and any(gs):
@@ -839,13 +896,18 @@ class MangaOcr:
         if rows is not None:
             self._require("PREFIX")
             kw["prefixes"] = rows
+        ps = _penalties(repetition_penalty, 1.0, n)
+        if ps is not None:
+            self._require("PENALTY")
+            kw["penalty"] = ps
         return kw
 
     def _single(self, allowed, no_repeat_ngram, prefix=None) -> dict:
         """the batcher keywords of one crop's ``allowed=`` / ``no_repeat_ngram=`` / ``prefix=``"""
         return _Single.batcher_kw(self._decode_kw(allowed, no_repeat_ngram, 1, prefix))
 
-    def _run(self, source, kind: _Kind, allowed=None, no_repeat_ngram=None, prefix=None, sources=None, lexicon=None) -> list:
+    def _run(self, source, kind: _Kind, allowed=None, no_repeat_ngram=None, prefix=None, sources=None, lexicon=None,
+             repetition_penalty=None) -> list:
         """Every greedy recognise method: one row of ``kind`` per crop or region of the source - or per entry of ``sources``
         (shared encodings).  In this order: the kind's refusal (several devices), before the image is opened or any argument
         is looked at; for plain text and positions, whether the constructor's beams decode it instead (``_beam_default``: text
@@ -855,8 +917,10 @@ class MangaOcr:
         crop) makes the call greedy and adds ``automata=`` / ``states=True``; the rows then carry ``state``, ``accepted``, ``entry``."""
         if kind.refusal:
             self._require(kind.refusal)
+        if repetition_penalty is not None and getattr(self, "beam", None) is not None:
+            raise ValueError("this MangaOcr decodes with beam search (num_beams=): beam search takes no repetition_penalty=")
         beams = (kind is _TEXT or (kind is _POS and getattr(self, "beam_positions", False))) and lexicon is None and \
-            self._beam_default(allowed, no_repeat_ngram, prefix)
+            self._beam_default(allowed, no_repeat_ngram, prefix, repetition_penalty)
         if beams and kind is _POS:
             self._require("BEAM_POSITIONS")
         src = source()
@@ -867,7 +931,9 @@ class MangaOcr:
         if beams:
             ids, lens, _ = self._beam(src, self.beam)
             return [ids[i, 0, :lens[i, 0]].copy() for i in range(len(lens))]
-        kw = self._decode_kw(allowed, no_repeat_ngram, src.n if sources is None else len(sources), prefix)
+        if repetition_penalty is None:
+            repetition_penalty = getattr(self, "repetition_penalty", 1.0)
+        kw = self._decode_kw(allowed, no_repeat_ngram, src.n if sources is None else len(sources), prefix, repetition_penalty)
         if sources is not None:
             kw["sources"] = sources
         lex = _lexicons(lexicon, src.n if sources is None else len(sources))
@@ -944,7 +1010,7 @@ class MangaOcr:
 
     # ------------------------------------------------------------------ batch surface (callers that hold many crops)
     def recognize_ids(self, crops: Sequence[np.ndarray], bgr: bool = False, rotate: Optional[Sequence[int]] = None, *,
-                      allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[np.ndarray]:
+                      allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> List[np.ndarray]:
         """uint8 crops of any sizes ([h,w] luminance or [h,w,3] RGB; BGR with ``bgr=True``; ``rotate``: per crop 0 / 1 (90
         degrees clockwise) / 2 (counter-clockwise), done by the device) -> token ids (without padding).  ``allowed``: a
         token set of :meth:`token_set` for all crops, or one per crop.  ``no_repeat_ngram``: the no-repeat n-gram size of this
@@ -954,104 +1020,106 @@ class MangaOcr:
         on from there (include/mocr.h, "forced prefixes").  ``lexicon``: a :class:`Lexicon` of :meth:`lexicon` / :meth:`automaton`
         for all crops, or one (or None) per crop - the row is decoded under that token automaton (include/mocr.h, "token
         automata"); the scored kinds then fill ``Recognition.state`` / ``accepted`` / ``entry``.  Every greedy ``recognize*``
-        method takes all four.  A call with ``lexicon=`` decodes GREEDILY even when this MangaOcr was built with ``num_beams=``:
+        method takes all four, and ``repetition_penalty``: transformers' setting of that name under greedy decoding, a float for
+        all crops or one per crop, finite and > 0, 1 = off (None: the constructor's ``repetition_penalty``; include/mocr.h,
+        "repetition penalty") - a reader built with ``num_beams=`` refuses it.  A call with ``lexicon=`` decodes GREEDILY even when this MangaOcr was built with ``num_beams=``:
         :meth:`match` searches a lexicon with beams, :meth:`search` a glossary or ``sequence_bias`` (the biases then count inside
         the hypotheses' scores)."""
-        return self._run(lambda: _Images(list(crops), bgr, rotate), _TEXT, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
+        return self._run(lambda: _Images(list(crops), bgr, rotate), _TEXT, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty)
 
-    def recognize(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> str:
+    def recognize(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> str:
         """``__call__`` (which keeps the reference's signature) with ``allowed=``: one crop decoded under a token set, and
         ``no_repeat_ngram=``: this call's no-repeat n-gram size (None: the constructor's ``no_repeat_ngram_size``)."""
-        return self._texts(self._run(self._one(img_or_path), _TEXT, allowed, no_repeat_ngram, prefix, lexicon=lexicon))[0]
+        return self._texts(self._run(self._one(img_or_path), _TEXT, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty))[0]
 
-    def recognize_batch(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[str]:
+    def recognize_batch(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> List[str]:
         """All crops of a page (or chapter) at once - what ``_collect_manga_detections``
         (``src/ui/main_window.py:9462-9476``) does one region at a time."""
-        return self._texts(self.recognize_ids([to_pixels(im) for im in images], allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix, lexicon=lexicon))
+        return self._texts(self.recognize_ids([to_pixels(im) for im in images], allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix, lexicon=lexicon, repetition_penalty=repetition_penalty))
 
-    def recognize_batch_arrays(self, crops: Sequence[np.ndarray], *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[str]:
+    def recognize_batch_arrays(self, crops: Sequence[np.ndarray], *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> List[str]:
         """uint8 arrays ([h,w] luminance or [h,w,3] RGB, any sizes) -> strings: what a caller that already holds numpy
         crops (the crop-job queue) uses instead of wrapping each one in a PIL image."""
-        return self._texts(self.recognize_ids(crops, allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix, lexicon=lexicon))
+        return self._texts(self.recognize_ids(crops, allowed=allowed, no_repeat_ngram=no_repeat_ngram, prefix=prefix, lexicon=lexicon, repetition_penalty=repetition_penalty))
 
-    def recognize_bgr(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[str]:
+    def recognize_bgr(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> List[str]:
         """BGR crops exactly as the crop tools and the worker hold them (``cropped_cv_img``, ``src/core/workers.py:300``):
         the BGR -> RGB swap of ``src/ui/main_window.py:9800`` is folded into the device's luminance conversion, and with
         ``orientations`` (the jobs' "Auto-Detect" / "Vertical" / "Horizontal" settings) the orientation-only rotation of
         ``src/core/workers.py:320-326`` / ``src/ui/main_window.py:9787-9795`` into the device's resize addressing."""
         src = self._bgr("recognize_bgr", crops_bgr, orientations)
-        return self._texts(self._run(lambda: src, _TEXT, allowed, no_repeat_ngram, prefix, lexicon=lexicon))
+        return self._texts(self._run(lambda: src, _TEXT, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty))
 
-    def recognize_regions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[str]:
+    def recognize_regions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> List[str]:
         """``regions``: (page_index, x, y, w, h) bounding rectangles on BGR pages; every page is uploaded once and
         the padded crops (``src/ui/main_window.py:9530-9540``) are cut on the device.  One string per region
         ('' for a region reduced to a sliver, like the reference)."""
-        return self._texts(self._run(lambda: _Regions(list(pages_bgr), list(regions)), _TEXT, allowed, no_repeat_ngram, prefix, lexicon=lexicon))
+        return self._texts(self._run(lambda: _Regions(list(pages_bgr), list(regions)), _TEXT, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty))
 
     # ------------------------------------------------------------------ scored surface: the same recognitions + confidence
-    def recognize_scored(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> Recognition:
+    def recognize_scored(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> Recognition:
         """``__call__`` with the recogniser's confidence: same text, plus the token log-probabilities computed on the
         device (include/mocr.h, "token scores").  Goes through the same batcher as ``__call__``; scored and unscored
         callers may share a batch."""
-        return self._run(self._one(img_or_path), _SCORED, allowed, no_repeat_ngram, prefix, lexicon=lexicon)[0]
+        return self._run(self._one(img_or_path), _SCORED, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty)[0]
 
-    def recognize_batch_scored(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
+    def recognize_batch_scored(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> List[Recognition]:
         """``recognize_batch`` with confidences."""
-        return self._run(self._pil(images), _SCORED, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
+        return self._run(self._pil(images), _SCORED, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty)
 
     def recognize_bgr_scored(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
-                             allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
+                             allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> List[Recognition]:
         """``recognize_bgr`` with confidences."""
-        return self._run(lambda: self._bgr("recognize_bgr_scored", crops_bgr, orientations), _SCORED, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
+        return self._run(lambda: self._bgr("recognize_bgr_scored", crops_bgr, orientations), _SCORED, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty)
 
-    def recognize_regions_scored(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
+    def recognize_regions_scored(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> List[Recognition]:
         """``recognize_regions`` with confidences; a region reduced to a sliver gives text '' and confidence 0.0."""
-        return self._run(lambda: _Regions(list(pages_bgr), list(regions)), _SCORED, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
+        return self._run(lambda: _Regions(list(pages_bgr), list(regions)), _SCORED, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty)
 
     # ------------------------------------------------------------------ alternatives surface: + the runners-up of every position
-    def recognize_alternatives(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> Recognition:
+    def recognize_alternatives(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> Recognition:
         """``recognize_scored`` plus, for every generated position, the four most probable tokens and their log-probabilities
         (``Recognition.alt_ids`` / ``alt_logprobs`` / ``candidates``; include/mocr.h, "token alternatives").  Same text; goes
         through the same batcher as ``__call__``, and callers of all three kinds may share a batch."""
-        return self._run(self._one(img_or_path), _ALTS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)[0]
+        return self._run(self._one(img_or_path), _ALTS, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty)[0]
 
-    def recognize_batch_alternatives(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
+    def recognize_batch_alternatives(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> List[Recognition]:
         """``recognize_batch`` with confidences and alternatives."""
-        return self._run(self._pil(images), _ALTS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
+        return self._run(self._pil(images), _ALTS, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty)
 
     def recognize_bgr_alternatives(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
-                                   allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
+                                   allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> List[Recognition]:
         """``recognize_bgr`` with confidences and alternatives."""
-        return self._run(lambda: self._bgr("recognize_bgr_alternatives", crops_bgr, orientations), _ALTS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
+        return self._run(lambda: self._bgr("recognize_bgr_alternatives", crops_bgr, orientations), _ALTS, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty)
 
-    def recognize_regions_alternatives(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
+    def recognize_regions_alternatives(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> List[Recognition]:
         """``recognize_regions`` with confidences and alternatives; a region reduced to a sliver gives text '', confidence
         0.0 and empty alternatives."""
-        return self._run(lambda: _Regions(list(pages_bgr), list(regions)), _ALTS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
+        return self._run(lambda: _Regions(list(pages_bgr), list(regions)), _ALTS, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty)
 
     # ------------------------------------------------------------------ positions surface: + where each token was read
-    def recognize_positions(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> Recognition:
+    def recognize_positions(self, img_or_path, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> Recognition:
         """``recognize_scored`` plus ``Recognition.positions``: per token where in the crop the decoder looked when it emitted
         it (include/mocr.h, "token positions"); ``Recognition.boxes(width, height)`` gives pixel rectangles.  Same text and
         scores; goes through the same batcher as ``__call__``, and callers of all kinds may share a batch."""
-        return self._run(self._one(img_or_path), _POS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)[0]
+        return self._run(self._one(img_or_path), _POS, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty)[0]
 
-    def recognize_batch_positions(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
+    def recognize_batch_positions(self, images: Sequence, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> List[Recognition]:
         """``recognize_batch_scored`` with positions."""
-        return self._run(self._pil(images), _POS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
+        return self._run(self._pil(images), _POS, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty)
 
     def recognize_bgr_positions(self, crops_bgr: Sequence[np.ndarray], orientations: Optional[Sequence[str]] = None, *,
-                                allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
+                                allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> List[Recognition]:
         """``recognize_bgr_scored`` with positions.  The positions are those of the crop the encoder saw, i.e. after the
         orientation's rotation: pass the crop's rotation code (``queue_worker.rotation_code``) to ``Recognition.boxes`` to get
         rectangles on the crop as it was handed in."""
-        return self._run(lambda: self._bgr("recognize_bgr_positions", crops_bgr, orientations), _POS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
+        return self._run(lambda: self._bgr("recognize_bgr_positions", crops_bgr, orientations), _POS, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty)
 
-    def recognize_regions_positions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None) -> List[Recognition]:
+    def recognize_regions_positions(self, pages_bgr: Sequence[np.ndarray], regions, *, allowed=None, no_repeat_ngram=None, prefix=None, lexicon=None, repetition_penalty=None) -> List[Recognition]:
         """``recognize_regions_scored`` with positions: every Recognition carries ``rect``, the region's padded, clipped
         rectangle on its page (``regions.padded_rect``), so ``Recognition.page_boxes()`` gives the tokens' rectangles in page
         pixels.  A region reduced to a sliver gives text '', no positions rows and ``rect`` None."""
-        return self._run(lambda: _Regions(list(pages_bgr), list(regions)).with_rects(), _POS, allowed, no_repeat_ngram, prefix, lexicon=lexicon)
+        return self._run(lambda: _Regions(list(pages_bgr), list(regions)).with_rects(), _POS, allowed, no_repeat_ngram, prefix, lexicon=lexicon, repetition_penalty=repetition_penalty)
 
     # ------------------------------------------------------------------ forced prefixes: score a given text
     def _text_prefix(self, text) -> List[int]:
@@ -1151,12 +1219,14 @@ class MangaOcr:
         return self.recognize_batch_nbest([self._open(img_or_path)], k, allowed=allowed, no_repeat_ngram=no_repeat_ngram)[0]
 
     # ------------------------------------------------------------------ beam search
-    def _beam_default(self, allowed, no_repeat_ngram, prefix) -> bool:
+    def _beam_default(self, allowed, no_repeat_ngram, prefix, repetition_penalty=None) -> bool:
         """does a plain call decode with the constructor's beams?  (They do not combine with the per-call keywords.)"""
         if getattr(self, "beam", None) is None:
             return False
         if allowed is not None or no_repeat_ngram is not None or prefix is not None:
             raise ValueError("this MangaOcr decodes with beam search (num_beams=): allowed= / no_repeat_ngram= / prefix= do not combine with it")
+        if repetition_penalty is not None:
+            raise ValueError("this MangaOcr decodes with beam search (num_beams=): beam search takes no repetition_penalty=")
         return True
 
     def _beam(self, src, beam: BeamConfig, token_scores: bool = False, allowed=None, positions: bool = False, lexicons=None,
