@@ -261,18 +261,9 @@ struct DecMode {
     static constexpr int KEY_SPAN = 4096;
     int epilogue() const { return mask ? (level == 2 ? EPI_TOPK_M : level == 1 ? EPI_ARGMAX_LSE_M : EPI_ARGMAX_M)
                                        : (level == 2 ? EPI_TOPK : level == 1 ? EPI_ARGMAX_LSE : EPI_ARGMAX); }
-    // profile names of the fused LM head and of the token kernel
+    // profile name of the fused LM head (the token kernel's is its form's: TokenFamily)
     const char* head_name() const {
         return penalty ? "gemm_dec_vocab_rp" : soft ? "gemm_dec_vocab_sw" : mask ? "gemm_dec_vocab_m" : level == 2 ? "gemm_dec_vocab_topk" : level == 1 ? "gemm_dec_vocab_lse" : "gemm_dec_vocab";
-    }
-    const char* token_name() const {
-        static const char* const names[3][3] = {{"dec_token", "dec_token_m", "dec_token_ng"},
-                                                {"dec_token_lse", "dec_token_lse_m", "dec_token_lse_ng"},
-                                                {"dec_token_topk", "dec_token_topk_m", "dec_token_topk_ng"}};
-        static const char* const automaton_names[3] = {"dec_token_am", "dec_token_lse_am", "dec_token_topk_am"};
-        static const char* const soft_names[3] = {"dec_token_sw", "dec_token_lse_sw", "dec_token_topk_sw"};
-        static const char* const penalty_names[3] = {"dec_token_rp", "dec_token_lse_rp", "dec_token_topk_rp"};
-        return penalty ? penalty_names[level] : soft ? soft_names[level] : automaton ? automaton_names[level] : names[level][ngram ? 2 : mask ? 1 : 0];
     }
 };
 
@@ -515,13 +506,31 @@ template <typename Kernel> struct Form {
     int lds = 0;
 };
 
+// Forms whose trailing argument differs in TYPE (GemmParams / GemmParamsSoft / GemmParamsPen, DecAutomata / DecSoftAutomata /
+// DecPenAutomata, BeamAutomata / BeamSoftAutomata) have no one kernel-pointer type.  Such a family's kernel<I>() is still the
+// instantiation itself (raise_lds needs its address), and its `Kernel` is a thunk, Sliced<Launch>: the family's `Launch` holds one
+// launch's arguments with the RICHEST trailing struct, and Launch::operator()(kernel) passes them in one line - the call slices
+// that struct, by value, to the base the form takes, so every form's argument block is what it is without the richer ones.
+template <typename Launch> using Sliced = void (*)(const Launch&);
+template <typename Launch, auto K> void sliced_launch(const Launch& l) { l(K); }
+template <typename Fam, size_t I> constexpr typename Fam::Kernel form_kernel() {
+    constexpr auto k = Fam::template kernel<I>();
+    if constexpr (std::is_convertible_v<decltype(k), typename Fam::Kernel>) return k;
+    else return sliced_launch<typename Fam::Launch, k>;
+}
+
 template <typename Fam, size_t... I> Form<typename Fam::Kernel> find_form(const typename Fam::Args& key, std::index_sequence<I...>) {
     Form<typename Fam::Kernel> r;
-    (void)((Fam::forms[I] == key && (r = {Fam::template kernel<I>(), Fam::lds(Fam::forms[I])}, true)) || ...);
+    (void)((Fam::forms[I] == key && (r = {form_kernel<Fam, I>(), Fam::lds(Fam::forms[I])}, true)) || ...);
     return r;
 }
 template <typename Fam> Form<typename Fam::Kernel> find_form(const typename Fam::Args& key) {
     return find_form<Fam>(key, std::make_index_sequence<std::size(Fam::forms)>{});
+}
+// the row a key names (a family whose rows carry their profile name: operator== leaves the name out); null as find_form's kernel
+template <typename Fam> const typename Fam::Args* find_row(const typename Fam::Args& key) {
+    const auto it = std::find(std::begin(Fam::forms), std::end(Fam::forms), key);
+    return it == std::end(Fam::forms) ? nullptr : &*it;
 }
 
 template <typename Fam, size_t... I> void raise_lds(std::index_sequence<I...>) {
@@ -531,55 +540,37 @@ template <typename... Fam> void raise_lds() { (raise_lds<Fam>(std::make_index_se
 
 // ---------------------------------------------------------------------------------------- GEMM
 // gemm_kernel (kernels_gemm.h): epilogue x 64 / 128 tiles x two / four ring slots; the two scored masked epilogues also with a
-// forced prefix's target column (GemmParams::tgt_val is a template parameter of theirs).
-struct TileArgs { int epi, bm, ring; bool tgt; };
-constexpr bool operator==(const TileArgs& a, const TileArgs& b) { return a.epi == b.epi && a.bm == b.bm && a.ring == b.ring && a.tgt == b.tgt; }
-constexpr std::array<TileArgs, 56> tile_forms() {
-    std::array<TileArgs, 56> a{};
+// forced prefix's target column (GemmParams::tgt_val is a template parameter of theirs); the three masked epilogues also in
+// their SOFT form (soft token automata: the rows' edge weights go into the tile), on GemmParamsSoft, and in their PEN form
+// (repetition penalty), which is SOFT too, on GemmParamsPen - Sliced, so that the plain forms' argument stays GemmParams.
+struct TileArgs { int epi, bm, ring; bool tgt, soft, pen; };
+constexpr bool operator==(const TileArgs& a, const TileArgs& b) {
+    return a.epi == b.epi && a.bm == b.bm && a.ring == b.ring && a.tgt == b.tgt && a.soft == b.soft && a.pen == b.pen;
+}
+constexpr std::array<TileArgs, 96> tile_forms() {
+    std::array<TileArgs, 96> a{};
     int n = 0;
     for (int epi : {EPI_SLAB, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_PATCH, EPI_BIAS_F32, EPI_ARGMAX, EPI_ARGMAX_LSE, EPI_TOPK,
                     EPI_ARGMAX_M, EPI_ARGMAX_LSE_M, EPI_TOPK_M})
         for (int bm : {64, 128})
             for (int ring : {2, 4})
                 for (bool tgt : {false, true})
-                    if (!tgt || epi == EPI_ARGMAX_LSE_M || epi == EPI_TOPK_M) a[n++] = TileArgs{epi, bm, ring, tgt};
+                    for (int rich : {0, 1, 2})      // plain, SOFT, PEN
+                        if ((!tgt || epi == EPI_ARGMAX_LSE_M || epi == EPI_TOPK_M) &&
+                            (!rich || epi == EPI_ARGMAX_M || epi == EPI_ARGMAX_LSE_M || epi == EPI_TOPK_M))
+                            a[n++] = TileArgs{epi, bm, ring, tgt, rich >= 1, rich == 2};
     return a;
 }
 template <typename T> struct TileFamily {
     using Args = TileArgs;
-    using Kernel = void (*)(GemmParams);
-    static constexpr std::array<Args, 56> forms = tile_forms();
-    static_assert(forms[55].bm == 128 && forms[55].tgt, "tile_forms fills its table");
-    template <size_t I> static constexpr Kernel kernel() { constexpr Args a = forms[I]; return gemm_kernel<T, a.bm, a.bm, a.epi, a.ring, a.tgt>; }
-    static constexpr int lds(const Args& a) { return a.ring * (a.bm + a.bm) * 128; }
-};
-
-// ... and the SOFT forms of the three masked epilogues (soft token automata: the rows' edge weights go into the tile), on
-// GemmParamsSoft; a family of its own, so that TileFamily's table and its kernels' argument type stay what they were
-constexpr std::array<TileArgs, 20> soft_tile_forms() {
-    std::array<TileArgs, 20> a{};
-    int n = 0;
-    for (int epi : {EPI_ARGMAX_M, EPI_ARGMAX_LSE_M, EPI_TOPK_M})
-        for (int bm : {64, 128})
-            for (int ring : {2, 4})
-                for (bool tgt : {false, true})
-                    if (!tgt || epi != EPI_ARGMAX_M) a[n++] = TileArgs{epi, bm, ring, tgt};
-    return a;
-}
-template <typename T> struct SoftTileFamily {
-    using Args = TileArgs;
-    using Kernel = void (*)(GemmParamsSoft);
-    static constexpr std::array<Args, 20> forms = soft_tile_forms();
-    static_assert(forms[19].bm == 128 && forms[19].tgt, "soft_tile_forms fills its table");
-    template <size_t I> static constexpr Kernel kernel() { constexpr Args a = forms[I]; return gemm_kernel<T, a.bm, a.bm, a.epi, a.ring, a.tgt, true>; }
-    static constexpr int lds(const Args& a) { return a.ring * (a.bm + a.bm) * 128; }
-};
-// ... and their PEN forms (repetition penalty), which are SOFT too, on GemmParamsPen: one more family, not two
-template <typename T> struct PenTileFamily {
-    using Args = TileArgs;
-    using Kernel = void (*)(GemmParamsPen);
-    static constexpr std::array<Args, 20> forms = soft_tile_forms();
-    template <size_t I> static constexpr Kernel kernel() { constexpr Args a = forms[I]; return gemm_kernel<T, a.bm, a.bm, a.epi, a.ring, a.tgt, true, true>; }
+    struct Launch {
+        dim3 grid; int lds; hipStream_t stream; GemmParamsPen p;
+        template <typename K> void operator()(K kernel) const { hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, p); }
+    };
+    using Kernel = Sliced<Launch>;
+    static constexpr std::array<Args, 96> forms = tile_forms();
+    static_assert(forms[95].bm == 128 && forms[95].tgt && forms[95].pen, "tile_forms fills its table");
+    template <size_t I> static constexpr auto kernel() { constexpr Args a = forms[I]; return gemm_kernel<T, a.bm, a.bm, a.epi, a.ring, a.tgt, a.soft, a.pen>; }
     static constexpr int lds(const Args& a) { return a.ring * (a.bm + a.bm) * 128; }
 };
 // Repetition penalty (the PEN forms): the rows' seen words and penalties (kernels_gemm.h GemmParamsPen)
@@ -622,30 +613,19 @@ static TileLaunch tile_launch(const mocr_engine* e, int M, int N, int bm, int sp
 template <typename T>
 void launch_gemm_tile(mocr_engine* e, const GemmParams& p0, int epi, int bm, int split, int ybatch, const TokSoft* soft = nullptr,
                       const TokPen* pen = nullptr) {
-    GemmParams p = p0;
+    GemmParamsPen p{};      // the richest argument: a form takes the base it is declared with (TileFamily::Launch)
+    static_cast<GemmParams&>(p) = p0;
     const TileLaunch t = tile_launch(e, p.M, p.N, bm, split, ybatch, p.k_per_split / (128 / (int)sizeof(T)));
     p.ntn = t.ntn; p.ntm = t.ntm;
-    dim3 grid(p.ntm * p.ntn, ybatch, split);
-    if (pen) {          // (soft may be null here: a penalty without any automaton)
-        const auto f = find_form<PenTileFamily<T>>({epi, bm, t.ring, p.tgt_val != nullptr});
-        if (!f.kernel) throw ArgError{"a repetition penalty goes into the masked LM-head epilogues", MOCR_ERR_ARG};
-        GemmParamsPen pp{};
-        static_cast<GemmParams&>(pp) = p;
-        if (soft) { pp.aut_state = soft->state; pp.edge_begin = soft->edge_begin; pp.edge_token = soft->edge_token; pp.edge_weight = soft->edge_weight; }
-        pp.seen_mask = pen->seen_mask; pp.penalty_of_row = pen->penalty_of_row;
-        hipLaunchKernelGGL(f.kernel, grid, dim3(256), f.lds, e->stream, pp);
-    } else if (soft) {
-        const auto f = find_form<SoftTileFamily<T>>({epi, bm, t.ring, p.tgt_val != nullptr});
-        if (!f.kernel) throw ArgError{"edge weights go into the masked LM-head epilogues", MOCR_ERR_ARG};
-        GemmParamsSoft ps{};
-        static_cast<GemmParams&>(ps) = p;
-        ps.aut_state = soft->state; ps.edge_begin = soft->edge_begin; ps.edge_token = soft->edge_token; ps.edge_weight = soft->edge_weight;
-        hipLaunchKernelGGL(f.kernel, grid, dim3(256), f.lds, e->stream, ps);
-    } else {
-    const auto f = find_form<TileFamily<T>>({epi, bm, t.ring, p.tgt_val != nullptr});
-    if (!f.kernel) throw ArgError{"unknown GEMM epilogue", MOCR_ERR_ARG};
-    hipLaunchKernelGGL(f.kernel, grid, dim3(256), f.lds, e->stream, p);
-    }
+    if (soft) { p.aut_state = soft->state; p.edge_begin = soft->edge_begin; p.edge_token = soft->edge_token; p.edge_weight = soft->edge_weight; }
+    if (pen) { p.seen_mask = pen->seen_mask; p.penalty_of_row = pen->penalty_of_row; }
+    // (a penalty's form is a SOFT one whether or not `soft` is given: a penalty without any automaton)
+    const TileArgs key{epi, bm, t.ring, p.tgt_val != nullptr, soft || pen, pen != nullptr};
+    const auto f = find_form<TileFamily<T>>(key);
+    if (!f.kernel)
+        throw ArgError{key.pen ? "a repetition penalty goes into the masked LM-head epilogues"
+                               : key.soft ? "edge weights go into the masked LM-head epilogues" : "unknown GEMM epilogue", MOCR_ERR_ARG};
+    f.kernel({dim3(p.ntm * p.ntn, ybatch, split), f.lds, e->stream, p});
     HIPCHECK(hipGetLastError());
     g_last_tile = {bm, t.ring, (int)std::min<long long>(t.blocks, INT32_MAX), split};
 }
@@ -1412,66 +1392,88 @@ struct DecTokenArgs {
                                                           // in which the eight may be null)
 };
 
-// The operator hooks come with a bare DecState, so the kernel's form is read off the state: scores / alternatives /
-// token sets / per-row masks set (make_state sets them from the batch's DecMode).
+// dec_token_kernel (kernels_decode.h; T, 768, FIRST, SCORES, TOPK, MASK, NGRAM, AUTOMATON, SOFT, PEN): the start token's kernel (it
+// has nothing to score or to mask), then level (ids, SCORES, SCORES + TOPK) x kind - plain, MASK, NGRAM, AUTOMATON, SOFT, PEN, each
+// kind the one before plus its flag.  A row carries its profile name.
+struct TokenArgs { bool first, scores, topk, mask, ngram, automaton, soft, pen; const char* name; };
+constexpr bool operator==(const TokenArgs& a, const TokenArgs& b) {
+    return a.first == b.first && a.scores == b.scores && a.topk == b.topk && a.mask == b.mask && a.ngram == b.ngram &&
+           a.automaton == b.automaton && a.soft == b.soft && a.pen == b.pen;
+}
+// (the table's rows and the run-time key are both made here, so a key is always a row)
+constexpr TokenArgs token_form(bool first, int level, int kind, const char* name = nullptr) {
+    if (first) return TokenArgs{true, false, false, false, false, false, false, false, name};
+    return TokenArgs{false, level >= 1, level >= 2, kind >= 1, kind >= 2, kind >= 3, kind >= 4, kind >= 5, name};
+}
+constexpr std::array<TokenArgs, 19> token_forms() {
+    constexpr const char* names[3][6] = {
+        {"dec_token", "dec_token_m", "dec_token_ng", "dec_token_am", "dec_token_sw", "dec_token_rp"},
+        {"dec_token_lse", "dec_token_lse_m", "dec_token_lse_ng", "dec_token_lse_am", "dec_token_lse_sw", "dec_token_lse_rp"},
+        {"dec_token_topk", "dec_token_topk_m", "dec_token_topk_ng", "dec_token_topk_am", "dec_token_topk_sw", "dec_token_topk_rp"}};
+    std::array<TokenArgs, 19> a{};
+    int n = 0;
+    a[n++] = token_form(true, 0, 0, "dec_token_first");
+    for (int level = 0; level < 3; ++level)
+        for (int kind = 0; kind < 6; ++kind) a[n++] = token_form(false, level, kind, names[level][kind]);
+    return a;
+}
+// The operator hooks come with a bare DecState, so the form is read off the pointers: scores / alternatives, and the richest of
+// token sets / per-row masks / automaton tables / weights / seen words that is set (make_state and dec_token set them from the
+// batch's DecMode).
+static TokenArgs token_key(bool first, const DecState& st, const DecTokenArgs& a) {
+    return token_form(first, st.alt_ids ? 2 : st.scores ? 1 : 0,
+                      a.aut.pen.seen_mask ? 5 : a.aut.edge_weight ? 4 : a.aut.state ? 3 : st.row_mask ? 2 : st.tok_mask ? 1 : 0);
+}
+template <typename T> struct TokenFamily {
+    using Args = TokenArgs;
+    struct Launch {
+        mocr_engine* e; const DecState& st; const DecTokenArgs& a; int n;
+        template <typename K> void operator()(K kernel) const {
+            auto& w = e->w;
+            const bool cand = a.ncand > 0, scored = cand && (st.scores || st.alt_ids), alts = cand && st.alt_ids;
+            hipLaunchKernelGGL(kernel, dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab, a.slab_stride, a.vbias, e->V, st, w.word, w.type0,
+                               w.posd, w.embg, w.embb, a.x_f32, reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps, reinterpret_cast<T*>(a.cache),
+                               a.cstride, cand ? a.cand_val : nullptr, cand ? a.cand_idx : nullptr, a.ncand, a.cache8, a.inv8,
+                               scored ? a.cand_sum : nullptr, alts ? a.top_val : nullptr, alts ? a.top_idx : nullptr, a.aut);
+        }
+    };
+    using Kernel = Sliced<Launch>;
+    static constexpr std::array<Args, 19> forms = token_forms();
+    static_assert(forms[18].topk && forms[18].pen, "token_forms fills its table");
+    template <size_t I> static constexpr auto kernel() {
+        constexpr Args f = forms[I];
+        return dec_token_kernel<T, 768, f.first, f.scores, f.topk, f.mask, f.ngram, f.automaton, f.soft, f.pen>;
+    }
+    static constexpr int lds(const Args&) { return 0; }
+};
+
 template <typename T, bool FIRST>
 void launch_dec_token(mocr_engine* e, const DecState& st, const DecTokenArgs& a, int n) {
-    auto& w = e->w;
-    DecMode m;
-    m.level = st.alt_ids ? 2 : st.scores ? 1 : 0; m.mask = st.tok_mask != nullptr; m.ngram = st.row_mask != nullptr;
-    m.automaton = a.aut.state != nullptr; m.soft = a.aut.edge_weight != nullptr; m.penalty = a.aut.pen.seen_mask != nullptr;
-    const bool cand = a.ncand > 0;
-    ProfScope ps(e, FIRST ? "dec_token_first" : m.token_name(), 0, FIRST ? 0.0 : (double)n * e->V * 4 * a.nslab);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(n), dim3(256), 0, e->stream, a.slabs, a.nslab, a.slab_stride, a.vbias, e->V, st, w.word, w.type0,
-                           w.posd, w.embg, w.embb, a.x_f32, reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps, reinterpret_cast<T*>(a.cache),
-                           a.cstride, cand ? a.cand_val : nullptr, cand ? a.cand_idx : nullptr, a.ncand, a.cache8, a.inv8,
-                           cand && m.level >= 1 ? a.cand_sum : nullptr, cand && m.level >= 2 ? a.top_val : nullptr,
-                           cand && m.level >= 2 ? a.top_idx : nullptr, a.aut);
-    };
-    // <T, 768, FIRST, SCORES, TOPK, MASK, NGRAM>: the start token's kernel, and level x (plain, MASK, NGRAM) for the steps
-    if constexpr (FIRST) launch(dec_token_kernel<T, 768, true>);      // (the start step has nothing to score or to mask)
-    else if (m.penalty) switch (m.level) {        // the PEN form of every level
-        case 0: launch(dec_token_kernel<T, 768, false, false, false, true, true, true, true, true>); break;
-        case 1: launch(dec_token_kernel<T, 768, false, true, false, true, true, true, true, true>); break;
-        default: launch(dec_token_kernel<T, 768, false, true, true, true, true, true, true, true>); break;
-    }
-    else if (m.soft) switch (m.level) {           // the SOFT form of every level
-        case 0: launch(dec_token_kernel<T, 768, false, false, false, true, true, true, true>); break;
-        case 1: launch(dec_token_kernel<T, 768, false, true, false, true, true, true, true>); break;
-        default: launch(dec_token_kernel<T, 768, false, true, true, true, true, true, true>); break;
-    }
-    else if (m.automaton) switch (m.level) {      // ... and the AUTOMATON form of every level
-        case 0: launch(dec_token_kernel<T, 768, false, false, false, true, true, true>); break;
-        case 1: launch(dec_token_kernel<T, 768, false, true, false, true, true, true>); break;
-        default: launch(dec_token_kernel<T, 768, false, true, true, true, true, true>); break;
-    }
-    else switch (m.level * 3 + (m.ngram ? 2 : m.mask ? 1 : 0)) {
-        case 0: launch(dec_token_kernel<T, 768, false>); break;
-        case 1: launch(dec_token_kernel<T, 768, false, false, false, true>); break;
-        case 2: launch(dec_token_kernel<T, 768, false, false, false, true, true>); break;
-        case 3: launch(dec_token_kernel<T, 768, false, true>); break;
-        case 4: launch(dec_token_kernel<T, 768, false, true, false, true>); break;
-        case 5: launch(dec_token_kernel<T, 768, false, true, false, true, true>); break;
-        case 6: launch(dec_token_kernel<T, 768, false, true, true>); break;
-        case 7: launch(dec_token_kernel<T, 768, false, true, true, true>); break;
-        default: launch(dec_token_kernel<T, 768, false, true, true, true, true>); break;
-    }
+    const TokenArgs key = token_key(FIRST, st, a);
+    ProfScope ps(e, find_row<TokenFamily<T>>(key)->name, 0, FIRST ? 0.0 : (double)n * e->V * 4 * a.nslab);
+    find_form<TokenFamily<T>>(key).kernel({e, st, a, n});
     HIPCHECK(hipGetLastError());
 }
 
-template <typename T, bool FIRST>
-void dec_token(mocr_engine* e, const DecState& st, int nslab, int n, int ncand = 0) {
+// The step's token-kernel (or selection) arguments on the engine's buffers: the LM head's slabs, the embedding of the chosen
+// token and its layer-0 latent cache row
+static DecTokenArgs dec_token_args(mocr_engine* e, int nslab, int n) {
     const bool lat = e->use_latent(e->rrows(n));
     DecTokenArgs a{};
     a.slabs = e->slabs; a.nslab = nslab; a.slab_stride = (long long)e->Bp * e->V; a.vbias = e->w.bv;
-    a.cand_val = e->cand_val; a.cand_idx = e->cand_idx; a.ncand = ncand; a.cand_sum = e->cand_sum;
-    a.top_val = e->top_val; a.top_idx = e->top_idx;
     a.x_f32 = e->x_f32; a.x_t = e->x_t;
     a.cache = (lat && !e->fp8attn) ? e->xcache : nullptr;
     a.cache8 = (lat && e->fp8attn) ? e->x8cache : nullptr;
     a.inv8 = (lat && e->fp8attn) ? 1.0f / e->w.sx_self[0] : 0.f;
     a.cstride = (long long)e->cfg.max_len * e->D;
+    return a;
+}
+
+template <typename T, bool FIRST>
+void dec_token(mocr_engine* e, const DecState& st, int nslab, int n, int ncand = 0) {
+    DecTokenArgs a = dec_token_args(e, nslab, n);
+    a.cand_val = e->cand_val; a.cand_idx = e->cand_idx; a.ncand = ncand; a.cand_sum = e->cand_sum;
+    a.top_val = e->top_val; a.top_idx = e->top_idx;
     if (!FIRST && e->automaton_batch) {
         static_cast<DecAutomata&>(a.aut) = DecAutomata{e->aut_edge_begin, e->aut_edge_token, e->aut_edge_next, e->aut_accepting, e->aut_base_of_row, e->aut_state};
         if (e->soft_batch) { a.aut.edge_weight = e->aut_edge_weight; a.aut.default_next = e->aut_default_next; }
@@ -1501,24 +1503,46 @@ static BeamSoftAutomata make_beam_automata(mocr_engine* e, bool soft) {
     return a;
 }
 
+// beam_select_kernel (kernels_beam.h; T, K, TOK, TRAIL, AUT, SOFT): K = 2 .. 4 x kind - plain, TOK, AUT (a token form), SOFT, each
+// kind the one before plus its flag - without and with the two trails.  A row carries its profile name.
+struct BeamArgs { int K; bool tok, trail, aut, soft; const char* name; };
+constexpr bool operator==(const BeamArgs& a, const BeamArgs& b) {
+    return a.K == b.K && a.tok == b.tok && a.trail == b.trail && a.aut == b.aut && a.soft == b.soft;
+}
+constexpr std::array<BeamArgs, 24> beam_forms() {
+    constexpr const char* names[4][2] = {{"beam_select", "beam_select"}, {"beam_select_tok", "beam_select_tok"},
+                                         {"beam_select_am", "beam_select_am_tr"}, {"beam_select_sw", "beam_select_sw_tr"}};
+    std::array<BeamArgs, 24> a{};
+    int n = 0;
+    for (int K = 2; K <= 4; ++K)
+        for (int kind = 0; kind < 4; ++kind)
+            for (int trail = 0; trail < 2; ++trail) a[n++] = BeamArgs{K, kind >= 1, trail != 0, kind >= 2, kind >= 3, names[kind][trail]};
+    return a;
+}
+template <typename T> struct BeamSelectFamily {
+    using Args = BeamArgs;
+    struct Launch {
+        mocr_engine* e; const DecState& st; const BeamState& bs; const DecTokenArgs& a; int n, K; const BeamSoftAutomata& aut;
+        template <typename Kn> void operator()(Kn kernel) const {
+            auto& w = e->w;
+            hipLaunchKernelGGL(kernel, dim3((n + K - 1) / K), dim3(256), 0, e->stream, a.slabs, a.nslab, a.slab_stride, a.vbias, e->V, st, bs, n,
+                               w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32, reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps,
+                               reinterpret_cast<T*>(a.cache), a.cstride, a.cache8, a.inv8, aut);
+        }
+    };
+    using Kernel = Sliced<Launch>;
+    static constexpr std::array<Args, 24> forms = beam_forms();
+    static_assert(forms[23].K == 4 && forms[23].soft && forms[23].trail, "beam_forms fills its table");
+    template <size_t I> static constexpr auto kernel() { constexpr Args f = forms[I]; return beam_select_kernel<T, f.K, f.tok, f.trail, f.aut, f.soft>; }
+    static constexpr int lds(const Args&) { return 0; }
+};
+
 // n decode slots = groups of K (a trailing partial group is padding); the LM head's slabs, by slot, are in `a`
 template <typename T>
 void launch_beam_select(mocr_engine* e, const DecState& st, const BeamState& bs, const DecTokenArgs& a, int n, int K,
                         const BeamSoftAutomata& aut = BeamSoftAutomata{}) {
-    auto& w = e->w;
     if (e->D != 768 || e->V != 6144 || st.ids_ld > BEAM_HIST || st.max_len > st.ids_ld || a.nslab < 1)
         throw ArgError{"beam search needs hidden 768, vocab 6144 and max_len <= 320", MOCR_ERR_UNSUPPORTED};
-    ProfScope ps(e, aut.edge_weight ? (bs.beam_trail ? "beam_select_sw_tr" : "beam_select_sw")
-                    : aut.state     ? (bs.beam_trail ? "beam_select_am_tr" : "beam_select_am")
-                    : (bs.beam_logp || bs.tok_mask) ? "beam_select_tok" : "beam_select",
-                 0, (double)n * e->V * 4 * a.nslab);
-    // (`tail`: the trailing argument in the type the form takes - every form but the SOFT one gets the seven pointers alone)
-    auto launch_with = [&](auto kernel, const auto& tail) {
-        hipLaunchKernelGGL(kernel, dim3((n + K - 1) / K), dim3(256), 0, e->stream, a.slabs, a.nslab, a.slab_stride, a.vbias, e->V, st, bs, n,
-                           w.word, w.type0, w.posd, w.embg, w.embb, a.x_f32, reinterpret_cast<T*>(a.x_t), e->cfg.ln_eps,
-                           reinterpret_cast<T*>(a.cache), a.cstride, a.cache8, a.inv8, tail);
-    };
-    auto launch = [&](auto kernel) { launch_with(kernel, static_cast<const BeamAutomata&>(aut)); };
     // the token form when the state carries any of its four arrays (make_beam_state sets them from the batch's DecMode)
     const bool tok = bs.beam_logp || bs.hyp_logp || bs.tok_mask || bs.set_of_row;
     if ((bs.beam_logp == nullptr) != (bs.hyp_logp == nullptr) || (bs.tok_mask == nullptr) != (bs.set_of_row == nullptr))
@@ -1533,46 +1557,13 @@ void launch_beam_select(mocr_engine* e, const DecState& st, const BeamState& bs,
             throw ArgError{"beam_select: the automaton tables, the rows' bases and the two state arrays come together", MOCR_ERR_ARG};
         if ((aut.edge_weight == nullptr) != (aut.default_next == nullptr))
             throw ArgError{"beam_select: edge_weight and default_next come as a pair", MOCR_ERR_ARG};
-        if (aut.edge_weight) {      // the SOFT form: weights inside the beams' scores, open states
-            switch (K * 2 + (trail ? 1 : 0)) {
-                case 4: launch_with(beam_select_kernel<T, 2, true, false, true, true>, aut); break;
-                case 6: launch_with(beam_select_kernel<T, 3, true, false, true, true>, aut); break;
-                case 8: launch_with(beam_select_kernel<T, 4, true, false, true, true>, aut); break;
-                case 5: launch_with(beam_select_kernel<T, 2, true, true, true, true>, aut); break;
-                case 7: launch_with(beam_select_kernel<T, 3, true, true, true, true>, aut); break;
-                case 9: launch_with(beam_select_kernel<T, 4, true, true, true, true>, aut); break;
-                default: throw ArgError{"num_beams must be 2 .. 4", MOCR_ERR_ARG};
-            }
-            HIPCHECK(hipGetLastError());
-            return;
-        }
-        switch (K * 2 + (trail ? 1 : 0)) {
-            case 4: launch(beam_select_kernel<T, 2, true, false, true>); break;
-            case 6: launch(beam_select_kernel<T, 3, true, false, true>); break;
-            case 8: launch(beam_select_kernel<T, 4, true, false, true>); break;
-            case 5: launch(beam_select_kernel<T, 2, true, true, true>); break;
-            case 7: launch(beam_select_kernel<T, 3, true, true, true>); break;
-            case 9: launch(beam_select_kernel<T, 4, true, true, true>); break;
-            default: throw ArgError{"num_beams must be 2 .. 4", MOCR_ERR_ARG};
-        }
-        HIPCHECK(hipGetLastError());
-        return;
     }
-    switch (K * 4 + (trail ? 2 : 0) + (tok ? 1 : 0)) {
-        case 8: launch(beam_select_kernel<T, 2>); break;
-        case 12: launch(beam_select_kernel<T, 3>); break;
-        case 16: launch(beam_select_kernel<T, 4>); break;
-        case 9: launch(beam_select_kernel<T, 2, true>); break;
-        case 13: launch(beam_select_kernel<T, 3, true>); break;
-        case 17: launch(beam_select_kernel<T, 4, true>); break;
-        case 10: launch(beam_select_kernel<T, 2, false, true>); break;
-        case 14: launch(beam_select_kernel<T, 3, false, true>); break;
-        case 18: launch(beam_select_kernel<T, 4, false, true>); break;
-        case 11: launch(beam_select_kernel<T, 2, true, true>); break;
-        case 15: launch(beam_select_kernel<T, 3, true, true>); break;
-        case 19: launch(beam_select_kernel<T, 4, true, true>); break;
-        default: throw ArgError{"num_beams must be 2 .. 4", MOCR_ERR_ARG};
-    }
+    // ... and its SOFT form with the weights: inside the beams' scores, open states
+    const BeamArgs key{K, tok || aut.state, trail, aut.state != nullptr, aut.state && aut.edge_weight, nullptr};
+    const BeamArgs* const row = find_row<BeamSelectFamily<T>>(key);
+    if (!row) throw ArgError{"num_beams must be 2 .. 4", MOCR_ERR_ARG};
+    ProfScope ps(e, row->name, 0, (double)n * e->V * 4 * a.nslab);
+    find_form<BeamSelectFamily<T>>(key).kernel({e, st, bs, a, n, K, aut});
     HIPCHECK(hipGetLastError());
 }
 
@@ -1601,13 +1592,7 @@ template <typename T>
 void beam_finish_step(mocr_engine* e, const DecState& st, const DecMode& m, int nslab, int n, int t) {
     const int K = m.beam_cfg.num_beams;
     const bool lat = e->use_latent(e->rrows(n));
-    DecTokenArgs a{};
-    a.slabs = e->slabs; a.nslab = nslab; a.slab_stride = (long long)e->Bp * e->V; a.vbias = e->w.bv;
-    a.x_f32 = e->x_f32; a.x_t = e->x_t;
-    a.cache = (lat && !e->fp8attn) ? e->xcache : nullptr;
-    a.cache8 = (lat && e->fp8attn) ? e->x8cache : nullptr;
-    a.inv8 = (lat && e->fp8attn) ? 1.0f / e->w.sx_self[0] : 0.f;
-    a.cstride = (long long)e->cfg.max_len * e->D;
+    const DecTokenArgs a = dec_token_args(e, nslab, n);
     launch_beam_select<T>(e, st, make_beam_state(e, m.beam_cfg, m.beam_tokens, m.positions), a, n, K,
                           m.beam_automaton ? make_beam_automata(e, m.soft) : BeamSoftAutomata{});
     // `t` bounds the step index of this launch from above only when it is exact (eager steps).  A captured graph passes
@@ -2126,7 +2111,7 @@ void quantize_enc(mocr_engine* e, int n) {
 // Raise the dynamic-LDS limit of every form of every kernel family (done once, at creation: outside any capture, from the
 // calling thread - decode steps are launched inside stream capture and from several lane threads).
 template <typename T> void init_kernel_attrs() {
-    raise_lds<TileFamily<T>, SoftTileFamily<T>, PenTileFamily<T>, PersFamily, QqtFamily, SmallMFamily, LatentFamily, LatentTFamily, Latent8Family, LatentT8Family>();
+    raise_lds<TileFamily<T>, PersFamily, QqtFamily, SmallMFamily, LatentFamily, LatentTFamily, Latent8Family, LatentT8Family>();
     for_each_enc_attn<T>([](auto kernel, int lds) { set_max_lds(kernel, lds); });
 #ifdef MOCR_EXPERIMENTS
     raise_lds<Gemm256Family, WideFamily, Wide2Family>();
@@ -2473,6 +2458,19 @@ static void upload_per_row(mocr_engine* e, const Lane& L, std::vector<int>& stag
     HIPCHECK(hipMemcpyAsync(d_dst, stage.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
 }
 
+// Token automata: the global start state of every row's automaton (a beam batch: by row c K + k, like the sets), uploaded to
+// aut_base_of_row; the padding rows and the rows without an automaton: -1.
+static void upload_start_states(mocr_engine* e, Lane& L) {
+    L.h_aut.assign((size_t)L.np, -1);
+    int r0 = 0;
+    for (const Job& j : L.jobs) {
+        for (size_t i = 0; i < j.automata.size(); ++i)
+            if (j.automata[i] != MOCR_AUTOMATON_NONE) L.h_aut[r0 + i] = e->aut_first[j.automata[i]];
+        r0 += j.n;
+    }
+    HIPCHECK(hipMemcpyAsync(e->aut_base_of_row, L.h_aut.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
+}
+
 // The decode rows' source of a batch with shared encodings, for the bound lane: allocated by the first batch in which a job
 // shares, like the alternatives buffers.
 static void ensure_share_buffer(mocr_engine* e) {
@@ -2638,14 +2636,7 @@ void start_batch(mocr_engine* e, Lane& L) {
             ensure_soft_arena(e);
         }
         ensure_automaton_buffers(e);
-        L.h_aut.assign((size_t)L.np, -1);
-        int r0 = 0;
-        for (const Job& j : L.jobs) {
-            for (size_t i = 0; i < j.automata.size(); ++i)
-                if (j.automata[i] != MOCR_AUTOMATON_NONE) L.h_aut[r0 + i] = e->aut_first[j.automata[i]];
-            r0 += j.n;
-        }
-        HIPCHECK(hipMemcpyAsync(e->aut_base_of_row, L.h_aut.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        upload_start_states(e, L);
         launch_automaton_init(e, e->row_mask, e->tok_table, e->set_of_row, e->ngram_of_row, L.np, e->aut_edge_begin, e->aut_edge_token,
                               e->aut_accepting, e->aut_base_of_row, e->aut_state, m.soft ? e->aut_default_next : nullptr);
     }
@@ -2683,14 +2674,7 @@ void start_batch(mocr_engine* e, Lane& L) {
         if (m.positions) ensure_beam_position_buffers(e);
         if (m.beam_automaton) {     // the crops' start states by row (c K + k, like the sets), padding rows without one
             ensure_beam_automaton_buffers(e);
-            L.h_aut.assign((size_t)L.np, -1);
-            int r0 = 0;
-            for (const Job& j : L.jobs) {
-                for (size_t i = 0; i < j.automata.size(); ++i)
-                    if (j.automata[i] != MOCR_AUTOMATON_NONE) L.h_aut[r0 + i] = e->aut_first[j.automata[i]];
-                r0 += j.n;
-            }
-            HIPCHECK(hipMemcpyAsync(e->aut_base_of_row, L.h_aut.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
+            upload_start_states(e, L);
             ProfScope pa(e, "beam_automaton_init", 0, (double)L.np * 12);
             hipLaunchKernelGGL(beam_automaton_init_kernel, dim3((L.np + 255) / 256), dim3(256), 0, e->stream, (const int*)e->aut_base_of_row,
                                e->aut_state, e->hyp_state, L.np);
@@ -2704,6 +2688,22 @@ void start_batch(mocr_engine* e, Lane& L) {
     L.t = 0; L.steps = L.max_len - 1; L.chunk = 0;
     L.finishing = false;
     L.flag_pending[0] = L.flag_pending[1] = false;
+}
+
+// The last two outputs of a job, greedy or beam, from row0 of the batch: its token positions and its rows' (hypotheses') final
+// states.  A batch in which nobody brings an automaton keeps no states: every row MOCR_STATE_NONE = -1, a host fill or a device
+// memset.
+static void copy_out_pos_state(mocr_engine* e, const Lane& L, const Job& j, int row0) {
+    const hipMemcpyKind kind = j.out_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (j.out_pos) {
+        const size_t ld = (size_t)e->cfg.max_len * MOCR_POSITION_FIELDS;
+        HIPCHECK(hipMemcpyAsync(j.out_pos, e->pos_out + row0 * ld, j.n * ld * sizeof(float), kind, e->stream));
+    }
+    if (j.out_state) {
+        if (L.mode.automaton || L.mode.beam_automaton) HIPCHECK(hipMemcpyAsync(j.out_state, e->aut_state_out + row0, (size_t)j.n * sizeof(int), kind, e->stream));
+        else if (j.out_host) std::fill(j.out_state, j.out_state + j.n, (int32_t)MOCR_STATE_NONE);
+        else HIPCHECK(hipMemsetAsync(j.out_state, 0xFF, (size_t)j.n * sizeof(int), e->stream));
+    }
 }
 
 void finish_batch(mocr_engine* e, Lane& L) {
@@ -2729,15 +2729,7 @@ void finish_batch(mocr_engine* e, Lane& L) {
             HIPCHECK(hipMemcpyAsync(j.out_score, e->hyp_score + row0, (size_t)j.n * sizeof(float), kind, e->stream));
             if (j.out_logp)         // (a batch with such a job ran the token form)
                 HIPCHECK(hipMemcpyAsync(j.out_logp, e->hyp_logp + (size_t)row0 * e->cfg.max_len, (size_t)j.n * e->cfg.max_len * sizeof(float), kind, e->stream));
-            if (j.out_pos) {        // (a batch with such a job kept the trails and ran the deferred pass over its hypotheses)
-                const size_t ld = (size_t)e->cfg.max_len * MOCR_POSITION_FIELDS;
-                HIPCHECK(hipMemcpyAsync(j.out_pos, e->pos_out + row0 * ld, j.n * ld * sizeof(float), kind, e->stream));
-            }
-            if (j.out_state) {      // (a batch in which nobody brings an automaton keeps no states)
-                if (L.mode.beam_automaton) HIPCHECK(hipMemcpyAsync(j.out_state, e->aut_state_out + row0, (size_t)j.n * sizeof(int), kind, e->stream));
-                else if (j.out_host) std::fill(j.out_state, j.out_state + j.n, (int32_t)MOCR_STATE_NONE);
-                else HIPCHECK(hipMemsetAsync(j.out_state, 0xFF, (size_t)j.n * sizeof(int), e->stream));
-            }
+            copy_out_pos_state(e, L, j, row0);      // (positions: such a batch kept the trails and ran the deferred pass over its hypotheses)
             row0 += j.n;
             continue;
         }
@@ -2750,15 +2742,7 @@ void finish_batch(mocr_engine* e, Lane& L) {
             HIPCHECK(hipMemcpyAsync(j.out_alt_ids, e->alt_ids + row0 * ld, j.n * ld * sizeof(int), kind, e->stream));
             HIPCHECK(hipMemcpyAsync(j.out_alt_logp, e->alt_logp + row0 * ld, j.n * ld * sizeof(float), kind, e->stream));
         }
-        if (j.out_pos) {
-            const size_t ld = (size_t)e->cfg.max_len * MOCR_POSITION_FIELDS;
-            HIPCHECK(hipMemcpyAsync(j.out_pos, e->pos_out + row0 * ld, j.n * ld * sizeof(float), kind, e->stream));
-        }
-        if (j.out_state) {      // (a batch in which nobody brings an automaton keeps no states: every row MOCR_STATE_NONE = -1)
-            if (L.mode.automaton) HIPCHECK(hipMemcpyAsync(j.out_state, e->aut_state_out + row0, (size_t)j.n * sizeof(int), kind, e->stream));
-            else if (j.out_host) std::fill(j.out_state, j.out_state + j.n, (int32_t)MOCR_STATE_NONE);
-            else HIPCHECK(hipMemsetAsync(j.out_state, 0xFF, (size_t)j.n * sizeof(int), e->stream));
-        }
+        copy_out_pos_state(e, L, j, row0);
         row0 += j.n;
     }
     L.jobs.clear();
@@ -5136,19 +5120,30 @@ int mocr_op_ngram_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_b
     });
 }
 
-// The token kernel on the caller's buffers: the five mocr_op_dec_token* symbols are this with some of the pointers null.
-static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum = nullptr, float* d_scores = nullptr,
-                        const float* d_top_val = nullptr, const int32_t* d_top_idx = nullptr, int32_t* d_alt_ids = nullptr,
-                        float* d_alt_logp = nullptr, const uint32_t* d_tok_mask = nullptr, const int32_t* d_set_of_row = nullptr,
-                        uint32_t* d_row_mask = nullptr, const uint32_t* d_base_mask = nullptr,
-                        const int32_t* d_base_set_of_row = nullptr, const int32_t* d_ngram_of_row = nullptr,
-                        const int32_t* d_prefix = nullptr, const int32_t* d_prefix_len = nullptr, int32_t prefix_ld = 0,
-                        const float* d_tgt_val = nullptr, const int32_t* d_edge_begin = nullptr, const int32_t* d_edge_token = nullptr,
-                        const int32_t* d_edge_next = nullptr, const uint8_t* d_accepting = nullptr,
-                        const int32_t* d_aut_base_of_row = nullptr, int32_t* d_aut_state = nullptr,
-                        const float* d_edge_weight = nullptr, const int32_t* d_default_next = nullptr,
-                        uint32_t* d_seen_mask = nullptr, const float* d_penalty_of_row = nullptr) {
+// What the mocr_op_dec_token* symbols bring beside mocr_token_args, by feature, in the manner of LmHead (a group left out: null)
+struct TokenOp {
+    struct Scored { const float* cand_sum; float* scores; } scored{};
+    struct Alts { const float* top_val; const int32_t* top_idx; int32_t* alt_ids; float* alt_logp; } alts{};
+    struct Sets { const uint32_t* tok_mask; const int32_t* set_of_row; } sets{};
+    struct Ngram { uint32_t* row_mask; const uint32_t* base_mask; const int32_t* base_set_of_row; const int32_t* ngram_of_row; } ngram{};
+    struct Prefix { const int32_t* prefix; const int32_t* prefix_len; int32_t prefix_ld; const float* tgt_val; } prefix{};
+    DecPenAutomata aut{};           // the automaton tables and the rows' states {{{six}, edge_weight, default_next}, {seen_mask, penalty_of_row}}
+};
+
+// The token kernel on the caller's buffers: the mocr_op_dec_token* symbols are this with some of the groups left out.
+static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const TokenOp& o = {}) {
     return guarded(e, [&] {
+        const auto [d_cand_sum, d_scores] = o.scored;
+        const auto [d_top_val, d_top_idx, d_alt_ids, d_alt_logp] = o.alts;
+        const auto [d_tok_mask, d_set_of_row] = o.sets;
+        const auto [d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row] = o.ngram;
+        const auto [d_prefix, d_prefix_len, prefix_ld, d_tgt_val] = o.prefix;
+        const auto d_edge_begin = o.aut.edge_begin, d_edge_token = o.aut.edge_token, d_edge_next = o.aut.edge_next,
+                   d_aut_base_of_row = o.aut.base_of_row, d_default_next = o.aut.default_next;
+        const auto d_accepting = o.aut.accepting;
+        const auto d_aut_state = o.aut.state;
+        const auto d_edge_weight = o.aut.edge_weight, d_penalty_of_row = o.aut.pen.penalty_of_row;
+        const auto d_seen_mask = o.aut.pen.seen_mask;
         std::lock_guard<std::mutex> lk(e->mu);
         HIPCHECK(hipSetDevice(e->cfg.device));
         drive(e);
@@ -5188,9 +5183,7 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const float* d
         st.row_mask = d_row_mask; st.base_mask = d_base_mask; st.base_set_of_row = d_base_set_of_row; st.ngram_of_row = d_ngram_of_row;
         st.prefix = d_prefix; st.prefix_len = d_prefix_len; st.prefix_ld = prefix_ld; st.tgt_val = d_tgt_val;
         DecTokenArgs t{};
-        static_cast<DecAutomata&>(t.aut) = DecAutomata{d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state};
-        t.aut.edge_weight = d_edge_weight; t.aut.default_next = d_default_next;
-        t.aut.pen = DecPenalty{d_seen_mask, d_penalty_of_row};
+        t.aut = o.aut;
         t.slabs = a->slabs; t.nslab = first ? 0 : a->nslab; t.slab_stride = (long long)a->n * e->V;
         t.vbias = a->vbias ? a->vbias : e->w.bv;
         t.cand_val = a->cand_val; t.cand_idx = a->cand_idx; t.ncand = first ? 0 : std::max(a->ncand, 0);
@@ -5213,8 +5206,8 @@ int mocr_op_dec_token_ngram(mocr_engine* e, const mocr_token_args* a, const floa
                             const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
                             const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
                             const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row) {
-    return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, d_row_mask,
-                        d_base_mask, d_base_set_of_row, d_ngram_of_row);
+    return op_dec_token(e, a, TokenOp{{d_cand_sum, d_scores}, {d_top_val, d_top_idx, d_alt_ids, d_alt_logp}, {d_tok_mask, d_set_of_row},
+                                      {d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row}});
 }
 
 int mocr_op_dec_token_prefix(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
@@ -5222,8 +5215,8 @@ int mocr_op_dec_token_prefix(mocr_engine* e, const mocr_token_args* a, const flo
                              const uint32_t* d_tok_mask, const int32_t* d_set_of_row, uint32_t* d_row_mask,
                              const uint32_t* d_base_mask, const int32_t* d_base_set_of_row, const int32_t* d_ngram_of_row,
                              const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld, const float* d_tgt_val) {
-    return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, d_row_mask,
-                        d_base_mask, d_base_set_of_row, d_ngram_of_row, d_prefix, d_prefix_len, prefix_ld, d_tgt_val);
+    return op_dec_token(e, a, TokenOp{{d_cand_sum, d_scores}, {d_top_val, d_top_idx, d_alt_ids, d_alt_logp}, {d_tok_mask, d_set_of_row},
+                                      {d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row}, {d_prefix, d_prefix_len, prefix_ld, d_tgt_val}});
 }
 
 int mocr_op_dec_token_automaton(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
@@ -5233,9 +5226,9 @@ int mocr_op_dec_token_automaton(mocr_engine* e, const mocr_token_args* a, const 
                                 const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld, const float* d_tgt_val,
                                 const int32_t* d_edge_begin, const int32_t* d_edge_token, const int32_t* d_edge_next,
                                 const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state) {
-    return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, d_row_mask,
-                        d_base_mask, d_base_set_of_row, d_ngram_of_row, d_prefix, d_prefix_len, prefix_ld, d_tgt_val, d_edge_begin,
-                        d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state);
+    return op_dec_token(e, a, TokenOp{{d_cand_sum, d_scores}, {d_top_val, d_top_idx, d_alt_ids, d_alt_logp}, {d_tok_mask, d_set_of_row},
+                                      {d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row}, {d_prefix, d_prefix_len, prefix_ld, d_tgt_val},
+                                      {{{d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state}}}});
 }
 
 int mocr_op_dec_token_soft(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
@@ -5246,9 +5239,10 @@ int mocr_op_dec_token_soft(mocr_engine* e, const mocr_token_args* a, const float
                            const int32_t* d_edge_begin, const int32_t* d_edge_token, const int32_t* d_edge_next,
                            const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state,
                            const float* d_edge_weight, const int32_t* d_default_next) {
-    return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, d_row_mask,
-                        d_base_mask, d_base_set_of_row, d_ngram_of_row, d_prefix, d_prefix_len, prefix_ld, d_tgt_val, d_edge_begin,
-                        d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state, d_edge_weight, d_default_next);
+    return op_dec_token(e, a, TokenOp{{d_cand_sum, d_scores}, {d_top_val, d_top_idx, d_alt_ids, d_alt_logp}, {d_tok_mask, d_set_of_row},
+                                      {d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row}, {d_prefix, d_prefix_len, prefix_ld, d_tgt_val},
+                                      {{{d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state}, d_edge_weight,
+                                        d_default_next}}});
 }
 
 int mocr_op_dec_token_penalty(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
@@ -5260,10 +5254,10 @@ int mocr_op_dec_token_penalty(mocr_engine* e, const mocr_token_args* a, const fl
                               const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state,
                               const float* d_edge_weight, const int32_t* d_default_next, uint32_t* d_seen_mask,
                               const float* d_penalty_of_row) {
-    return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row, d_row_mask,
-                        d_base_mask, d_base_set_of_row, d_ngram_of_row, d_prefix, d_prefix_len, prefix_ld, d_tgt_val, d_edge_begin,
-                        d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state, d_edge_weight, d_default_next,
-                        d_seen_mask, d_penalty_of_row);
+    return op_dec_token(e, a, TokenOp{{d_cand_sum, d_scores}, {d_top_val, d_top_idx, d_alt_ids, d_alt_logp}, {d_tok_mask, d_set_of_row},
+                                      {d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row}, {d_prefix, d_prefix_len, prefix_ld, d_tgt_val},
+                                      {{{d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state}, d_edge_weight,
+                                        d_default_next}, {d_seen_mask, d_penalty_of_row}}});
 }
 
 int mocr_op_penalty_init(mocr_engine* e, uint32_t* d_seen_mask, int32_t rows) {
@@ -5319,16 +5313,16 @@ static int op_automaton_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_
 int mocr_op_dec_token_masked(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
                              const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp,
                              const uint32_t* d_tok_mask, const int32_t* d_set_of_row) {
-    return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp, d_tok_mask, d_set_of_row);
+    return op_dec_token(e, a, TokenOp{{d_cand_sum, d_scores}, {d_top_val, d_top_idx, d_alt_ids, d_alt_logp}, {d_tok_mask, d_set_of_row}});
 }
 
 int mocr_op_dec_token_topk(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
                            const float* d_top_val, const int32_t* d_top_idx, int32_t* d_alt_ids, float* d_alt_logp) {
-    return op_dec_token(e, a, d_cand_sum, d_scores, d_top_val, d_top_idx, d_alt_ids, d_alt_logp);
+    return op_dec_token(e, a, TokenOp{{d_cand_sum, d_scores}, {d_top_val, d_top_idx, d_alt_ids, d_alt_logp}});
 }
 
 int mocr_op_dec_token_scored(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores) {
-    return op_dec_token(e, a, d_cand_sum, d_scores);
+    return op_dec_token(e, a, TokenOp{{d_cand_sum, d_scores}});
 }
 
 int mocr_op_dec_token(mocr_engine* e, const mocr_token_args* a) { return op_dec_token(e, a); }
@@ -5392,16 +5386,20 @@ int mocr_op_gemm_argmax_target(mocr_engine* e, const void* dA, const void* dW, c
                              TokTarget{d_prefix, d_prefix_len, prefix_ld, d_step, d_tgt_val}});
 }
 
+// a caller's mocr_soft_tables (null: none) as the LM head takes them; false: not the struct this library knows
+static bool soft_tables(const mocr_soft_tables* soft, TokSoft& ts) {
+    if (soft && soft->struct_size != (int32_t)sizeof(mocr_soft_tables)) return false;
+    if (soft) ts = TokSoft{soft->d_aut_state, soft->d_edge_begin, soft->d_edge_token, soft->d_edge_weight};
+    return true;
+}
+
 int mocr_op_gemm_argmax_soft(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, float* d_cand_val,
                              int32_t* d_cand_idx, float* d_cand_sum, float* d_top_val, int32_t* d_top_idx, int32_t M, int32_t N,
                              int32_t K, int32_t tile, const uint32_t* d_tok_mask, const int32_t* d_set_of_row,
                              const int32_t* d_rowmap, const int32_t* d_prefix, const int32_t* d_prefix_len, int32_t prefix_ld,
                              const int32_t* d_step, float* d_tgt_val, const mocr_soft_tables* soft) {
     TokSoft ts{};
-    if (soft) {
-        if (soft->struct_size != (int32_t)sizeof(mocr_soft_tables)) return MOCR_ERR_ARG;
-        ts = TokSoft{soft->d_aut_state, soft->d_edge_begin, soft->d_edge_token, soft->d_edge_weight};
-    }
+    if (!soft_tables(soft, ts)) return MOCR_ERR_ARG;
     return op_lm_head(e, dA, dW, d_bias, d_cand_val, M, N, K, tile,
                       LmHead{d_cand_idx, d_cand_sum, d_top_val, d_top_idx, TokMask{d_tok_mask, d_set_of_row, d_rowmap},
                              TokTarget{d_prefix, d_prefix_len, prefix_ld, d_step, d_tgt_val}, ts});
@@ -5414,10 +5412,7 @@ int mocr_op_gemm_argmax_penalty(mocr_engine* e, const void* dA, const void* dW, 
                                 const int32_t* d_step, float* d_tgt_val, const mocr_soft_tables* soft, const uint32_t* d_seen_mask,
                                 const float* d_penalty_of_row) {
     TokSoft ts{};
-    if (soft) {
-        if (soft->struct_size != (int32_t)sizeof(mocr_soft_tables)) return MOCR_ERR_ARG;
-        ts = TokSoft{soft->d_aut_state, soft->d_edge_begin, soft->d_edge_token, soft->d_edge_weight};
-    }
+    if (!soft_tables(soft, ts)) return MOCR_ERR_ARG;
     return op_lm_head(e, dA, dW, d_bias, d_cand_val, M, N, K, tile,
                       LmHead{d_cand_idx, d_cand_sum, d_top_val, d_top_idx, TokMask{d_tok_mask, d_set_of_row, d_rowmap},
                              TokTarget{d_prefix, d_prefix_len, prefix_ld, d_step, d_tgt_val}, ts, TokPen{d_seen_mask, d_penalty_of_row}});
