@@ -145,23 +145,25 @@ __device__ __forceinline__ void glds16_nt(const void* gsrc_lane, void* lds_wave_
 // a reciprocal), so p = 1 returns v bit for bit; v == 0 divides.
 __device__ __forceinline__ float pen_logit(float v, float p) { return v < 0.f ? v * p : __fdiv_rn(v, p); }
 
-// A sorted list of the four best (value, column) pairs seen so far: value descending, the lower column first among equal
-// values - the order of the greedy pick.  Unfilled entries are (-inf, 0x7fffffff); a NaN wins no comparison and never enters.
-struct Top4 {
-    float v[4];
-    int i[4];
+// A sorted list of the N best (value, index) pairs seen so far: value descending, the lower index first among equal values -
+// the order of the greedy pick.  Unfilled entries are (-inf, 0x7fffffff); a NaN wins no comparison and never enters.  The LM
+// head and the token kernel keep the four best columns (Top4), beam search the 2 K best of K x V accumulated scores.
+template <int N> struct TopN {
+    float v[N];
+    int i[N];
 };
+using Top4 = TopN<4>;
 
-__device__ __forceinline__ void top4_clear(Top4& l) {
+template <int N> __device__ __forceinline__ void topn_clear(TopN<N>& l) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { l.v[k] = -INFINITY; l.i[k] = 0x7fffffff; }
+    for (int k = 0; k < N; ++k) { l.v[k] = -INFINITY; l.i[k] = 0x7fffffff; }
 }
 
 // Branch-free insertion: the candidate sinks down the list, taking the place of the first entry it precedes; the entry it
 // displaces precedes everything below it and pushes the rest down one place.
-__device__ __forceinline__ void top4_insert(Top4& l, float v, int i) {
+template <int N> __device__ __forceinline__ void topn_insert(TopN<N>& l, float v, int i) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < N; ++k) {
         const bool c = (v > l.v[k]) | ((v == l.v[k]) & (i < l.i[k]));        // (bitwise: selects, no control flow)
         const float tv = c ? l.v[k] : v;
         const int ti = c ? l.i[k] : i;
@@ -169,6 +171,16 @@ __device__ __forceinline__ void top4_insert(Top4& l, float v, int i) {
         l.i[k] = c ? i : l.i[k];
         v = tv; i = ti;
     }
+}
+
+// l = the N best of l and of the list the lane `xor_mask` away holds (both lanes end with the same list): the other lane's
+// entries are inserted one by one.  The two lists never share an index, so no entry is taken twice.
+template <int N> __device__ __forceinline__ void topn_merge_xor(TopN<N>& l, int xor_mask) {
+    TopN<N> o;
+#pragma unroll
+    for (int k = 0; k < N; ++k) { o.v[k] = __shfl_xor(l.v[k], xor_mask, 64); o.i[k] = __shfl_xor(l.i[k], xor_mask, 64); }
+#pragma unroll
+    for (int k = 0; k < N; ++k) topn_insert(l, o.v[k], o.i[k]);
 }
 
 // l = the four best of l and of the list the lane `xor_mask` away holds (both lanes end with the same list).  Two sorted
@@ -194,39 +206,4 @@ __device__ __forceinline__ void top4_merge_xor(Top4& l, int xor_mask) {
     }
     top4_order(l, 0, 2); top4_order(l, 1, 3);
     top4_order(l, 0, 1); top4_order(l, 2, 3);
-}
-
-// Top4's order for lists of any length (beam search keeps the 2 K best of K x V accumulated scores, kernels_beam.h): value
-// descending, the lower index first among equal values; unfilled entries are (-inf, 0x7fffffff), a NaN never enters.
-template <int N> struct TopN {
-    float v[N];
-    int i[N];
-};
-
-template <int N> __device__ __forceinline__ void topn_clear(TopN<N>& l) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) { l.v[k] = -INFINITY; l.i[k] = 0x7fffffff; }
-}
-
-// the same branch-free insertion as top4_insert
-template <int N> __device__ __forceinline__ void topn_insert(TopN<N>& l, float v, int i) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const bool c = (v > l.v[k]) | ((v == l.v[k]) & (i < l.i[k]));
-        const float tv = c ? l.v[k] : v;
-        const int ti = c ? l.i[k] : i;
-        l.v[k] = c ? v : l.v[k];
-        l.i[k] = c ? i : l.i[k];
-        v = tv; i = ti;
-    }
-}
-
-// l = the N best of l and of the list the lane `xor_mask` away holds (both lanes end with the same list): the other lane's
-// entries are inserted one by one.  The two lists never share an index, so no entry is taken twice.
-template <int N> __device__ __forceinline__ void topn_merge_xor(TopN<N>& l, int xor_mask) {
-    TopN<N> o;
-#pragma unroll
-    for (int k = 0; k < N; ++k) { o.v[k] = __shfl_xor(l.v[k], xor_mask, 64); o.i[k] = __shfl_xor(l.i[k], xor_mask, 64); }
-#pragma unroll
-    for (int k = 0; k < N; ++k) topn_insert(l, o.v[k], o.i[k]);
 }

@@ -234,7 +234,7 @@ struct DecMode {
                                     // AUTOMATON one, which also walks the rows' states, and the batch starts with automaton_init_kernel
     bool soft = false;              // ... and one of those automata is SOFT (edge weights / open states; implies `automaton`): the LM head is the
                                     // SOFT form of the masked epilogue, the token kernel the SOFT one, the batch starts with
-                                    // automaton_init_soft_kernel
+                                    // automaton_init_kernel<true>
     bool penalty = false;           // a row has a repetition penalty p != 1 (implies `soft`, so that the build has one more family and not two:
                                     // rows without an automaton read state NONE and add nothing): the LM head and the token kernel are the
                                     // PEN forms, the batch also starts with penalty_init_kernel
@@ -2354,13 +2354,10 @@ static void launch_automaton_init(mocr_engine* e, unsigned* row_mask, const unsi
                                   const uint8_t* accepting, const int* aut_base_of_row, int* aut_state,
                                   const int* default_next = nullptr) {
     ProfScope ps(e, default_next ? "automaton_init_sw" : "automaton_init", 0, (double)rows * (e->V / 32) * 8);
-    if (default_next)       // soft token automata: the start state may be open
-        hipLaunchKernelGGL(automaton_init_soft_kernel, dim3(rows), dim3(192), 0, e->stream, row_mask, base_mask, base_set_of_row, ngram_of_row,
-                           rows, e->V / 32, e->cfg.start_id, e->cfg.eos_id, edge_begin, edge_token, accepting, aut_base_of_row, aut_state,
-                           default_next);
-    else
-    hipLaunchKernelGGL(automaton_init_kernel, dim3(rows), dim3(192), 0, e->stream, row_mask, base_mask, base_set_of_row, ngram_of_row, rows,
-                       e->V / 32, e->cfg.start_id, e->cfg.eos_id, edge_begin, edge_token, accepting, aut_base_of_row, aut_state);
+    // (soft token automata: the start state may be open; the hard form never reads default_next)
+    hipLaunchKernelGGL(default_next ? automaton_init_kernel<true> : automaton_init_kernel<false>, dim3(rows), dim3(192), 0, e->stream, row_mask,
+                       base_mask, base_set_of_row, ngram_of_row, rows, e->V / 32, e->cfg.start_id, e->cfg.eos_id, edge_begin, edge_token,
+                       accepting, aut_base_of_row, aut_state, default_next);
     HIPCHECK(hipGetLastError());
 }
 

@@ -240,60 +240,22 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
     for (int k = 0; k < K; ++k) {
         const int b = slot0 + k;
         float4 a[NC];
-#pragma unroll
-        for (int j = 0; j < NC; ++j) a[j] = *reinterpret_cast<const float4*>(vbias + tid * 4 + j * 1024);
-        for (int s = 0; s < nslab; ++s) {
-            const float* sp = slabs + (size_t)s * slab_stride + (size_t)b * V + tid * 4;
-#pragma unroll
-            for (int j = 0; j < NC; ++j) {
-                const float4 x = *reinterpret_cast<const float4*>(sp + j * 1024);
-                a[j].x += x.x; a[j].y += x.y; a[j].z += x.z; a[j].w += x.w;
-            }
-        }
+        sum_slab_row(a, vbias, slabs, nslab, slab_stride, b, V, tid);
         float mx = -INFINITY;
 #pragma unroll
         for (int j = 0; j < NC; ++j) mx = fmaxf(fmaxf(mx, fmaxf(a[j].x, a[j].y)), fmaxf(a[j].z, a[j].w));
         mx = wave_max(mx);
         if (lane == 0) s_red[wave] = mx;
         int se0 = 0, se1 = 0;                         // SOFT: the edge range of beam k's state (empty: no automaton, or DEAD)
-        if constexpr (SOFT) {
-            if (s_abase >= 0) {                       // block-uniform: an open state allows every token, EOS iff it accepts
-                const int sk = s_ast[k];
-                const bool open = sk >= 0 && aut.default_next[sk] >= 0;
-                if (sk >= 0) { se0 = aut.edge_begin[sk]; se1 = aut.edge_begin[sk + 1]; }
-                if (tid < MW) s_mask[tid] = open ? 0xffffffffu : 0u;
-                __syncthreads();
-                if (open) {
-                    if (tid == 0 && !aut.accepting[sk] && (unsigned)st.eos_id < (unsigned)V)
-                        s_mask[st.eos_id >> 5] &= ~(1u << (st.eos_id & 31));
-                } else if (sk >= 0) {
-                    for (int i = se0 + tid; i < se1; i += 256) {
-                        const int x = aut.edge_token[i];
-                        if ((unsigned)x < (unsigned)V) atomicOr(&s_mask[x >> 5], 1u << (x & 31));
-                    }
-                    if (tid == 0 && aut.accepting[sk] && (unsigned)st.eos_id < (unsigned)V)
-                        atomicOr(&s_mask[st.eos_id >> 5], 1u << (st.eos_id & 31));
-                }
-                __syncthreads();
-                if (tid < MW) s_mask[tid] &= setw;
-            } else {
-                if (tid < MW) s_mask[tid] = setw;
-            }
-        } else if constexpr (AUT) {
+        if constexpr (AUT) {
             if (s_abase >= 0) {                       // block-uniform: A(state of beam k), then the crop's set
-                if (tid < MW) s_mask[tid] = 0u;
-                __syncthreads();
                 const int sk = s_ast[k];
-                if (sk >= 0) {
-                    const int e1 = aut.edge_begin[sk + 1];
-                    for (int i = aut.edge_begin[sk] + tid; i < e1; i += 256) {
-                        const int x = aut.edge_token[i];
-                        if ((unsigned)x < (unsigned)V) atomicOr(&s_mask[x >> 5], 1u << (x & 31));
-                    }
-                    if (tid == 0 && aut.accepting[sk] && (unsigned)st.eos_id < (unsigned)V)
-                        atomicOr(&s_mask[st.eos_id >> 5], 1u << (st.eos_id & 31));
+                bool open = false;
+                if constexpr (SOFT) {
+                    open = sk >= 0 && aut.default_next[sk] >= 0;
+                    if (sk >= 0) { se0 = aut.edge_begin[sk]; se1 = aut.edge_begin[sk + 1]; }
                 }
-                __syncthreads();
+                state_mask_to_lds(s_mask, sk, open, aut.edge_begin, aut.edge_token, aut.accepting, st.eos_id, V, MW, tid, 256);
                 if (tid < MW) s_mask[tid] &= setw;
             } else {
                 if (tid < MW) s_mask[tid] = setw;
@@ -312,16 +274,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
             es += (__expf(a[j].x - gmax) + __expf(a[j].y - gmax)) + (__expf(a[j].z - gmax) + __expf(a[j].w - gmax));
         es = wave_sum(es);
         if (lane == 0) s_red[wave] = es;
-        if (n > 0) {                                  // the bans of this beam's own history: windows i = 0 .. L - n
-            const int* rid = s_hist[k];
-            const int* key = rid + (L - n + 1);       // its last n - 1 tokens
-            for (int i = tid; i <= L - n; i += 256) {
-                bool same = true;
-                for (int q = 0; q < n - 1 && same; ++q) same = rid[i + q] == key[q];
-                const int ban = rid[i + n - 1];
-                if (same && (unsigned)ban < (unsigned)V) atomicAnd(&s_mask[ban >> 5], ~(1u << (ban & 31)));
-            }
-        }
+        if (n > 0) ngram_ban_windows(s_mask, s_hist[k], L, n, V, tid);     // the bans of this beam's own history
         __syncthreads();
         const float logS = logf((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
         const float bsc = bs.beam_score[s_row[k]];
@@ -336,12 +289,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
             if constexpr (SOFT) {
                 // the weights of the state's edges inside this float4 (constant indices only: no register is indexed)
                 float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;
-                int lo = se0, hi = se1;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (aut.edge_token[mid] < c) lo = mid + 1; else hi = mid;
-                }
-                for (; lo < se1; ++lo) {
+                for (int lo = edge_lower_bound(aut.edge_token, se0, se1, c); lo < se1; ++lo) {
                     const int d = aut.edge_token[lo] - c;
                     if (d >= 4) break;
                     const float wgt = aut.edge_weight[lo];
@@ -487,11 +435,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
                     ns = AUT_STATE_DEAD;
                     const int sp = s_ast[s_cpar[tid]], c = s_ctok[tid];
                     if (sp >= 0) {
-                        int lo = aut.edge_begin[sp], hi = aut.edge_begin[sp + 1];
-                        while (lo < hi) {
-                            const int mid = (lo + hi) >> 1;
-                            if (aut.edge_token[mid] < c) lo = mid + 1; else hi = mid;
-                        }
+                        const int lo = edge_lower_bound(aut.edge_token, aut.edge_begin[sp], aut.edge_begin[sp + 1], c);
                         if (lo < aut.edge_begin[sp + 1] && aut.edge_token[lo] == c) {
                             ns = aut.edge_next[lo];
                             if constexpr (SOFT) {       // the edge's weight: the token score is the value the row pass ranked
@@ -504,11 +448,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
                                 ns = dn & AUT_DEFAULT_STATE;
                                 if (dn & AUT_DEFAULT_FALLBACK) {    // the token is walked from the default state: its edge, if it has one
                                     const int f1 = aut.edge_begin[ns + 1];
-                                    int flo = aut.edge_begin[ns], fhi = f1;
-                                    while (flo < fhi) {
-                                        const int mid = (flo + fhi) >> 1;
-                                        if (aut.edge_token[mid] < c) flo = mid + 1; else fhi = mid;
-                                    }
+                                    const int flo = edge_lower_bound(aut.edge_token, aut.edge_begin[ns], f1, c);
                                     if (flo < f1 && aut.edge_token[flo] == c) ns = aut.edge_next[flo];
                                 }
                             }
@@ -634,42 +574,11 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
             if (tid == 0 && L < st.ids_ld) dst[L] = (uint8_t)p;
         }
     }
-    // embedding + LayerNorm of every new beam's next input (the tail of dec_token_kernel)
-    constexpr int PER = D / 256;
-    const int ps = t + 1;
+    // every new beam's next input (the tail of dec_token_kernel); s_red is the next beam's behind one more barrier
     for (int k = 0; k < K; ++k) {
-        const int tok = s_ntok[k], b = slot0 + k, row = s_row[k];
-        float v[PER];
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int d = tid + i * 256;
-            float e = word[(size_t)tok * D + d] + type0[d];
-            e = e + pos[(size_t)ps * D + d];
-            v[i] = e; s += e;
-        }
-        s = wave_sum(s);
-        if (lane == 0) s_red[wave] = s;
+        embed_ln_store<T, D>(s_ntok[k], t + 1, slot0 + k, s_row[k], word, type0, pos, gamma, beta, x_f32, x_t, eps, cache, cache_batch_stride,
+                             cache8, inv_sx8, s_red, tid);
         __syncthreads();
-        const float mean = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) * (1.0f / D);
-        __syncthreads();
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) { const float d = v[i] - mean; q += d * d; }
-        q = wave_sum(q);
-        if (lane == 0) s_red[wave] = q;
-        __syncthreads();
-        const float rstd = 1.0f / sqrtf((s_red[0] + s_red[1] + s_red[2] + s_red[3]) * (1.0f / D) + eps);
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int d = tid + i * 256;
-            const float o = (v[i] - mean) * rstd * gamma[d] + beta[d];
-            x_f32[(size_t)b * D + d] = o;
-            elem<T>::st(x_t + (size_t)b * D + d, o);
-            if (cache) elem<T>::st(cache + (size_t)row * cache_batch_stride + (size_t)ps * D + d, o);
-            if (cache8) cache8[(size_t)row * cache_batch_stride + (size_t)ps * D + d] = (uint8_t)(pack4_fp8(o * inv_sx8, 0.f, 0.f, 0.f) & 0xff);
-        }
     }
 }
 

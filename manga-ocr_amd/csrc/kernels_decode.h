@@ -5,6 +5,7 @@
 // atomics), adds the bias and fuses the element-wise work that follows.
 #pragma once
 #include "common.h"
+#include "token_rules.h"
 #include <type_traits>
 
 // out = LayerNorm( [gelu]( sum_s slab_s + bias ) [+ resid] ) ; writes fp32 (next residual) and T
@@ -199,18 +200,6 @@ struct DecPenAutomata : DecSoftAutomata {
     DecPenalty pen;
 };
 
-// The n-gram bans of a row that holds L tokens rid[0 .. L - 1], on its mask in LDS: the threads split the windows
-// i = 0 .. L - n, a window whose n - 1 key tokens equal the row's last n - 1 clears the bit of its follower.
-__device__ __forceinline__ void ngram_ban_windows(unsigned* s_mask, const int* rid, int L, int n, int V, int tid) {
-    const int* key = rid + (L - n + 1);         // the row's last n - 1 tokens
-    for (int i = tid; i <= L - n; i += 256) {
-        bool same = true;
-        for (int k = 0; k < n - 1 && same; ++k) same = rid[i + k] == key[k];
-        const int ban = rid[i + n - 1];
-        if (same && (unsigned)ban < (unsigned)V) atomicAnd(&s_mask[ban >> 5], ~(1u << (ban & 31)));
-    }
-}
-
 // End of a decode step, one block per sequence:
 //   logits = sum_s slab_s + bias  -> fp32 argmax (lowest index wins ties, like torch.argmax)
 //   finished rows emit pad_id (utils.py:2929); EOS or reaching max_len finishes a row (:2936)
@@ -338,16 +327,6 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                 if (cv > best || (cv == best && ci < bi)) { best = cv; bi = ci; }
             }
         } else {
-#pragma unroll
-        for (int j = 0; j < NC; ++j) a[j] = *reinterpret_cast<const float4*>(vbias + tid * 4 + j * 1024);
-        for (int s = 0; s < nslab; ++s) {
-            const float* sp = slabs + (size_t)s * slab_stride + (size_t)b * V + tid * 4;
-#pragma unroll
-            for (int j = 0; j < NC; ++j) {
-                const float4 x = *reinterpret_cast<const float4*>(sp + j * 1024);
-                a[j].x += x.x; a[j].y += x.y; a[j].z += x.z; a[j].w += x.w;
-            }
-        }
         int se0 = 0, se1 = 0;                            // SOFT: the edge range of the row's state (empty: NONE or DEAD)
         if constexpr (SOFT) {
             bool has = true;                             // PEN: the automaton pointers may be null
@@ -357,6 +336,7 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                 if (sst >= 0) { se0 = aut.edge_begin[sst]; se1 = aut.edge_begin[sst + 1]; }
             }
         }
+        sum_slab_row(a, vbias, slabs, nslab, slab_stride, b, V, tid);
         float pp = 1.f;                                  // PEN: the row's penalty and its seen words
         const unsigned* seen = nullptr;
         if constexpr (PEN) { pp = aut.pen.penalty_of_row[row]; seen = aut.pen.seen_mask + (size_t)row * (V >> 5); }
@@ -366,19 +346,7 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
             if (st.logits_out)
                 *reinterpret_cast<float4*>(st.logits_out + ((size_t)b * st.forced_T + t) * V + c) = a[j];
             if constexpr (SOFT) {
-                int lo = se0, hi = se1;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (aut.edge_token[mid] < c) lo = mid + 1; else hi = mid;
-                }
-                for (; lo < se1; ++lo) {
-                    const int d = aut.edge_token[lo] - c;
-                    if (d >= 4) break;
-                    const float wgt = aut.edge_weight[lo];
-                    if (wgt != 0.f) {
-                        if (d == 0) a[j].x += wgt; else if (d == 1) a[j].y += wgt; else if (d == 2) a[j].z += wgt; else a[j].w += wgt;
-                    }
-                }
+                add_edge_weights4(a[j], aut.edge_token, aut.edge_weight, se0, se1, c);
             }
             if constexpr (PEN) {
                 const unsigned snib = (seen[c >> 5] >> (c & 31)) & 15u;
@@ -430,13 +398,13 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
         if constexpr (TOPK) {
             __shared__ float s_tv[4][4];
             __shared__ int s_ti[4][4];
-            top4_clear(top);
+            topn_clear(top);
             if (cand_val) {
                 for (int c = tid; c < ncand; c += 256) {
                     const float4 tv = *reinterpret_cast<const float4*>(top_val + ((size_t)b * ncand + c) * 4);
                     const int4 ti = *reinterpret_cast<const int4*>(top_idx + ((size_t)b * ncand + c) * 4);
-                    top4_insert(top, tv.x, ti.x); top4_insert(top, tv.y, ti.y);
-                    top4_insert(top, tv.z, ti.z); top4_insert(top, tv.w, ti.w);
+                    topn_insert(top, tv.x, ti.x); topn_insert(top, tv.y, ti.y);
+                    topn_insert(top, tv.z, ti.z); topn_insert(top, tv.w, ti.w);
                 }
             } else {
 #pragma unroll
@@ -444,11 +412,11 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
                     const int c = tid * 4 + j * 1024;
                     if constexpr (MASK) {
                         const unsigned nib = abits >> (4 * j);
-                        top4_insert(top, a[j].x, (nib & 1) ? c : 0x7fffffff); top4_insert(top, a[j].y, (nib & 2) ? c + 1 : 0x7fffffff);
-                        top4_insert(top, a[j].z, (nib & 4) ? c + 2 : 0x7fffffff); top4_insert(top, a[j].w, (nib & 8) ? c + 3 : 0x7fffffff);
+                        topn_insert(top, a[j].x, (nib & 1) ? c : 0x7fffffff); topn_insert(top, a[j].y, (nib & 2) ? c + 1 : 0x7fffffff);
+                        topn_insert(top, a[j].z, (nib & 4) ? c + 2 : 0x7fffffff); topn_insert(top, a[j].w, (nib & 8) ? c + 3 : 0x7fffffff);
                     } else {
-                    top4_insert(top, a[j].x, c); top4_insert(top, a[j].y, c + 1);
-                    top4_insert(top, a[j].z, c + 2); top4_insert(top, a[j].w, c + 3);
+                    topn_insert(top, a[j].x, c); topn_insert(top, a[j].y, c + 1);
+                    topn_insert(top, a[j].z, c + 2); topn_insert(top, a[j].w, c + 3);
                     }
                 }
             }
@@ -462,7 +430,7 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
             if (tid == 0) {
                 for (int w = 1; w < 4; ++w)
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) top4_insert(top, s_tv[w][k], s_ti[w][k]);
+                    for (int k = 0; k < 4; ++k) topn_insert(top, s_tv[w][k], s_ti[w][k]);
             }
         }
         if (tid == 0) {
@@ -566,21 +534,7 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
             if (live) {
                 bool open = false;                      // SOFT: the new state allows every token, EOS iff it accepts
                 if constexpr (SOFT) open = state >= 0 && aut.default_next[state] >= 0;
-                if (tid < MW) s_mask[tid] = open ? ~0u : 0u;
-                __syncthreads();
-                if (open) {
-                    if (tid == 0 && !aut.accepting[state] && (unsigned)st.eos_id < (unsigned)V)
-                        s_mask[st.eos_id >> 5] &= ~(1u << (st.eos_id & 31));
-                } else if (state >= 0) {
-                    const int e1 = aut.edge_begin[state + 1];
-                    for (int i = aut.edge_begin[state] + tid; i < e1; i += 256) {
-                        const int a = aut.edge_token[i];
-                        if ((unsigned)a < (unsigned)V) atomicOr(&s_mask[a >> 5], 1u << (a & 31));
-                    }
-                    if (tid == 0 && aut.accepting[state] && (unsigned)st.eos_id < (unsigned)V)
-                        atomicOr(&s_mask[st.eos_id >> 5], 1u << (st.eos_id & 31));
-                }
-                __syncthreads();
+                state_mask_to_lds(s_mask, state, open, aut.edge_begin, aut.edge_token, aut.accepting, st.eos_id, V, MW, tid, 256);
                 if (tid < MW) s_mask[tid] &= st.base_mask[(size_t)st.base_set_of_row[row] * MW + tid];
                 __syncthreads();
                 if (n > 0) ngram_ban_windows(s_mask, st.ids + (size_t)row * st.ids_ld, L, n, V, tid);
@@ -608,38 +562,8 @@ __global__ __launch_bounds__(256) void dec_token_kernel(const float* __restrict_
         }
     }
     const int tok = s_tok, ps = s_pos;
-    // embedding + LayerNorm of the next input, block-wide over D = 768 (3 per thread)
-    constexpr int PER = D / 256;
-    float v[PER];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const int d = tid + i * 256;
-        float e = word[(size_t)tok * D + d] + type0[d];
-        e = e + pos[(size_t)ps * D + d];
-        v[i] = e; s += e;
-    }
-    s = wave_sum(s);
-    if (lane == 0) s_red[wave] = s;
-    __syncthreads();
-    const float mean = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) * (1.0f / D);
-    __syncthreads();
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) { const float d = v[i] - mean; q += d * d; }
-    q = wave_sum(q);
-    if (lane == 0) s_red[wave] = q;
-    __syncthreads();
-    const float rstd = 1.0f / sqrtf((s_red[0] + s_red[1] + s_red[2] + s_red[3]) * (1.0f / D) + eps);
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const int d = tid + i * 256;
-        const float o = (v[i] - mean) * rstd * gamma[d] + beta[d];
-        x_f32[(size_t)b * D + d] = o;
-        elem<T>::st(x_t + (size_t)b * D + d, o);
-        if (cache) elem<T>::st(cache + (size_t)row * cache_batch_stride + (size_t)ps * D + d, o);   // layer-0 key/value source
-        if (cache8) cache8[(size_t)row * cache_batch_stride + (size_t)ps * D + d] = (uint8_t)(pack4_fp8(o * inv_sx8, 0.f, 0.f, 0.f) & 0xff);
-    }
+    // the next input: embedding + LayerNorm, to x and the layer-0 key/value source
+    embed_ln_store<T, D>(tok, ps, b, row, word, type0, pos, gamma, beta, x_f32, x_t, eps, cache, cache_batch_stride, cache8, inv_sx8, s_red, tid);
 }
 
 // Start of a batch with no-repeat n-grams, one block of 192 threads per row: row_mask[row] = the row's base set.  The first
@@ -650,11 +574,8 @@ __global__ __launch_bounds__(192) void ngram_init_kernel(unsigned* __restrict__ 
     const int row = blockIdx.x;
     if (row >= rows) return;
     const bool ban_start = ngram_of_row[row] == 1 && (unsigned)start_id < (unsigned)(words * 32);
-    for (int w = threadIdx.x; w < words; w += blockDim.x) {
-        unsigned m = base_mask[(size_t)base_set_of_row[row] * words + w];
-        if (ban_start && w == (start_id >> 5)) m &= ~(1u << (start_id & 31));
-        row_mask[(size_t)row * words + w] = m;
-    }
+    for (int w = threadIdx.x; w < words; w += blockDim.x)
+        row_mask[(size_t)row * words + w] = base_row_word(base_mask, base_set_of_row[row], words, w, ban_start, start_id);
 }
 
 // Start of a batch with a repetition penalty, one block of 192 threads per row: the sibling of ngram_init_kernel.  The row's
@@ -669,13 +590,16 @@ __global__ __launch_bounds__(192) void penalty_init_kernel(unsigned* __restrict_
 // Start of a batch with token automata, one block of 192 threads per row (words <= 192): the sibling of ngram_init_kernel.
 // A row that brings an automaton (aut_base_of_row[row] >= 0) starts in its start state with the mask A(start) AND its base
 // set, minus the start token when n = 1, and {EOS} if nothing is left (the dead-end rule); a row without one gets what
-// ngram_init_kernel gives it and the state AUT_STATE_NONE.
+// ngram_init_kernel gives it and the state AUT_STATE_NONE.  SOFT (soft token automata; default_next is read by this form
+// alone): the start state may be OPEN (default_next[base] >= 0) - then A(start) is every token, EOS iff the state accepts.
+template <bool SOFT>
 __global__ __launch_bounds__(192) void automaton_init_kernel(unsigned* __restrict__ row_mask, const unsigned* __restrict__ base_mask,
                                                              const int* __restrict__ base_set_of_row, const int* __restrict__ ngram_of_row,
                                                              int rows, int words, int start_id, int eos_id,
                                                              const int* __restrict__ edge_begin, const int* __restrict__ edge_token,
                                                              const uint8_t* __restrict__ accepting,
-                                                             const int* __restrict__ aut_base_of_row, int* __restrict__ aut_state) {
+                                                             const int* __restrict__ aut_base_of_row, int* __restrict__ aut_state,
+                                                             const int* __restrict__ default_next) {
     __shared__ unsigned s_mask[192];
     const int row = blockIdx.x, tid = threadIdx.x;
     if (row >= rows) return;
@@ -684,75 +608,15 @@ __global__ __launch_bounds__(192) void automaton_init_kernel(unsigned* __restric
     const bool ban_start = ngram_of_row[row] == 1 && (unsigned)start_id < (unsigned)V;
     if (tid == 0) aut_state[row] = base >= 0 ? base : AUT_STATE_NONE;
     if (base < 0) {
-        for (int w = tid; w < words; w += blockDim.x) {
-            unsigned m = base_mask[(size_t)base_set_of_row[row] * words + w];
-            if (ban_start && w == (start_id >> 5)) m &= ~(1u << (start_id & 31));
-            row_mask[(size_t)row * words + w] = m;
-        }
+        for (int w = tid; w < words; w += blockDim.x)
+            row_mask[(size_t)row * words + w] = base_row_word(base_mask, base_set_of_row[row], words, w, ban_start, start_id);
         return;
     }
-    if (tid < words) s_mask[tid] = 0u;
-    __syncthreads();
-    const int e1 = edge_begin[base + 1];
-    for (int i = edge_begin[base] + tid; i < e1; i += blockDim.x) {
-        const int a = edge_token[i];
-        if ((unsigned)a < (unsigned)V) atomicOr(&s_mask[a >> 5], 1u << (a & 31));
-    }
-    if (tid == 0 && accepting[base] && (unsigned)eos_id < (unsigned)V) atomicOr(&s_mask[eos_id >> 5], 1u << (eos_id & 31));
-    __syncthreads();
+    bool open = false;                                  // block-uniform
+    if constexpr (SOFT) open = default_next[base] >= 0;
+    state_mask_to_lds(s_mask, base, open, edge_begin, edge_token, accepting, eos_id, V, words, tid, blockDim.x);
     unsigned m = 0u;
-    if (tid < words) {
-        m = s_mask[tid] & base_mask[(size_t)base_set_of_row[row] * words + tid];
-        if (ban_start && tid == (start_id >> 5)) m &= ~(1u << (start_id & 31));
-    }
-    const int any = __syncthreads_or(m != 0u);
-    if (!any && (unsigned)eos_id < (unsigned)V && tid == (eos_id >> 5)) m = 1u << (eos_id & 31);
-    if (tid < words) row_mask[(size_t)row * words + tid] = m;
-}
-
-// ... and its soft sibling: the start state may be OPEN (default_next[base] >= 0) - then A(start) is every token, EOS iff
-// the state accepts; a closed start state, and a row without an automaton, get what automaton_init_kernel gives them.
-__global__ __launch_bounds__(192) void automaton_init_soft_kernel(unsigned* __restrict__ row_mask, const unsigned* __restrict__ base_mask,
-                                                                  const int* __restrict__ base_set_of_row,
-                                                                  const int* __restrict__ ngram_of_row, int rows, int words, int start_id,
-                                                                  int eos_id, const int* __restrict__ edge_begin,
-                                                                  const int* __restrict__ edge_token, const uint8_t* __restrict__ accepting,
-                                                                  const int* __restrict__ aut_base_of_row, int* __restrict__ aut_state,
-                                                                  const int* __restrict__ default_next) {
-    __shared__ unsigned s_mask[192];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    if (row >= rows) return;
-    const int V = words * 32;
-    const int base = aut_base_of_row[row];              // block-uniform
-    const bool ban_start = ngram_of_row[row] == 1 && (unsigned)start_id < (unsigned)V;
-    if (tid == 0) aut_state[row] = base >= 0 ? base : AUT_STATE_NONE;
-    if (base < 0) {
-        for (int w = tid; w < words; w += blockDim.x) {
-            unsigned m = base_mask[(size_t)base_set_of_row[row] * words + w];
-            if (ban_start && w == (start_id >> 5)) m &= ~(1u << (start_id & 31));
-            row_mask[(size_t)row * words + w] = m;
-        }
-        return;
-    }
-    const bool open = default_next[base] >= 0;          // block-uniform
-    if (tid < words) s_mask[tid] = open ? ~0u : 0u;
-    __syncthreads();
-    if (open) {
-        if (tid == 0 && !accepting[base] && (unsigned)eos_id < (unsigned)V) s_mask[eos_id >> 5] &= ~(1u << (eos_id & 31));
-    } else {
-        const int e1 = edge_begin[base + 1];
-        for (int i = edge_begin[base] + tid; i < e1; i += blockDim.x) {
-            const int a = edge_token[i];
-            if ((unsigned)a < (unsigned)V) atomicOr(&s_mask[a >> 5], 1u << (a & 31));
-        }
-        if (tid == 0 && accepting[base] && (unsigned)eos_id < (unsigned)V) atomicOr(&s_mask[eos_id >> 5], 1u << (eos_id & 31));
-    }
-    __syncthreads();
-    unsigned m = 0u;
-    if (tid < words) {
-        m = s_mask[tid] & base_mask[(size_t)base_set_of_row[row] * words + tid];
-        if (ban_start && tid == (start_id >> 5)) m &= ~(1u << (start_id & 31));
-    }
+    if (tid < words) m = s_mask[tid] & base_row_word(base_mask, base_set_of_row[row], words, tid, ban_start, start_id);
     const int any = __syncthreads_or(m != 0u);
     if (!any && (unsigned)eos_id < (unsigned)V && tid == (eos_id >> 5)) m = 1u << (eos_id & 31);
     if (tid < words) row_mask[(size_t)row * words + tid] = m;

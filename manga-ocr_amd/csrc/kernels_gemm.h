@@ -21,6 +21,7 @@
 //     contiguous run of tiles, so tiles sharing an A row-panel share an L2.
 #pragma once
 #include "common.h"
+#include "token_rules.h"
 #include <type_traits>
 
 #ifndef MOCR_GEMM_MFMA16
@@ -208,9 +209,42 @@ __device__ __forceinline__ void gemm_epilogue(const float* sC, const GemmParams&
 // v = (tile value + edge weight) + bias of a seen column it takes pen_logit(v, p) instead, before the mask's select: in the
 // first walk (plain and TOPK), in the exp-sum walk - the same expression, so v' - best is exactly 0 at the winner - and at the
 // target column.  Rows m >= M read nothing (no bit, p = 1).  The edge weights are skipped where aut_state is null.
-template <int BM, int BN, int NT, bool SWZ, bool LSE = false, bool TOPK = false, bool MASK = false, bool TGT = false, bool SOFT = false,
-          typename P = GemmParams, bool PEN = false>
+// What an LM-head epilogue does is a function of EPI alone; TGT, SOFT and PEN come with gemm_kernel's own flags and P, the
+// parameter struct they need, is deduced.
+constexpr bool epi_is_lm_head(int epi) {
+    return epi == EPI_ARGMAX || epi == EPI_ARGMAX_LSE || epi == EPI_TOPK || epi == EPI_ARGMAX_M || epi == EPI_ARGMAX_LSE_M || epi == EPI_TOPK_M;
+}
+constexpr bool epi_mask(int epi) { return epi == EPI_ARGMAX_M || epi == EPI_ARGMAX_LSE_M || epi == EPI_TOPK_M; }
+constexpr bool epi_topk(int epi) { return epi == EPI_TOPK || epi == EPI_TOPK_M; }
+constexpr bool epi_lse(int epi) { return epi_topk(epi) || epi == EPI_ARGMAX_LSE || epi == EPI_ARGMAX_LSE_M; }
+
+// A thread's group of a row of a bit table (a set's mask, a row's seen words): bit (c - g0) = column c of [g0, g0 + CPP) -
+// half a word (CPP = 16, g0 a multiple of 16) or two whole words (CPP = 64, g0 a multiple of 64), loaded once.
+template <int CPP>
+__device__ __forceinline__ unsigned long long group_bits(const unsigned* wrow, int g0) {
+    static_assert(CPP == 16 || CPP == 64, "the group is half a mask word or two words");
+    if constexpr (CPP == 64) {
+        const uint2 w2 = *reinterpret_cast<const uint2*>(wrow + (g0 >> 5));
+        return ((unsigned long long)w2.y << 32) | w2.x;
+    } else {
+        return wrow[g0 >> 5] >> (g0 & 31);
+    }
+}
+
+// The effective logit of a column that exists: v = (tile value + edge weight) + bias, penalised where the row has seen the
+// column's token.  Every walk forms it with this one expression, so v - best is exactly 0 at the winner.  A column outside
+// the row's set does not exist; what that means is the walk's own: (-inf, index sentinel) in the four-best walk, no
+// comparison in the max walk, a term of 0 in the exp sum, -inf at the target column.
+template <bool PEN>
+__device__ __forceinline__ float lm_logit(float acc, float bias, bool seen, float pp) {
+    const float v = acc + bias;
+    if constexpr (PEN) return seen ? pen_logit(v, pp) : v;
+    return v;
+}
+
+template <int BM, int BN, int NT, bool SWZ, int EPI, bool TGT, bool SOFT, bool PEN, typename P>
 __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const P& p, int m0, int n0, int tid) {
+    constexpr bool LSE = epi_lse(EPI), TOPK = epi_topk(EPI), MASK = epi_mask(EPI);
     static_assert(!SOFT || MASK, "the weighted LM head is a masked one");
     static_assert(!PEN || SOFT, "the penalised LM head is the weighted one too");
     constexpr int TPRW = NT / BM, CPP = BN / TPRW;
@@ -225,16 +259,9 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const P& p
     unsigned long long mbits = ~0ull;
     const int g0 = n0 + (CPP < 64 ? ((part * CPP) ^ sw) : part * CPP);
     if constexpr (MASK) {
-        static_assert(CPP == 16 || CPP == 64, "the group is half a mask word or two words");
         int set = 0;
         if (m < p.M) set = p.set_of_row[p.rowmap ? p.rowmap[m] : m];
-        const unsigned* mrow = p.tok_mask + (size_t)set * (p.N >> 5);
-        if constexpr (CPP == 64) {
-            const uint2 w2 = *reinterpret_cast<const uint2*>(mrow + (g0 >> 5));
-            mbits = ((unsigned long long)w2.y << 32) | w2.x;
-        } else {
-            mbits = mrow[g0 >> 5] >> (g0 & 31);
-        }
+        mbits = group_bits<CPP>(p.tok_mask + (size_t)set * (p.N >> 5), g0);
     }
     // PEN: bit (c - g0) of sbits = logical column c of the thread's group is in the row; pp = the row's penalty
     unsigned long long sbits = 0ull;
@@ -242,13 +269,7 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const P& p
     if constexpr (PEN) {
         if (m < p.M) {
             const int brow = p.rowmap ? p.rowmap[m] : m;
-            const unsigned* srow = p.seen_mask + (size_t)brow * (p.N >> 5);
-            if constexpr (CPP == 64) {
-                const uint2 w2 = *reinterpret_cast<const uint2*>(srow + (g0 >> 5));
-                sbits = ((unsigned long long)w2.y << 32) | w2.x;
-            } else {
-                sbits = srow[g0 >> 5] >> (g0 & 31);
-            }
+            sbits = group_bits<CPP>(p.seen_mask + (size_t)brow * (p.N >> 5), g0);
             pp = p.penalty_of_row[brow];
         }
     }
@@ -260,12 +281,7 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const P& p
             if (s >= 0) {
                 float* const srow = const_cast<float*>(sC) + row * BN;
                 const int e1 = p.edge_begin[s + 1];
-                int lo = p.edge_begin[s], hi = e1;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (p.edge_token[mid] < g0) lo = mid + 1; else hi = mid;
-                }
-                for (; lo < e1; ++lo) {
+                for (int lo = edge_lower_bound(p.edge_token, p.edge_begin[s], e1, g0); lo < e1; ++lo) {
                     const int tok = p.edge_token[lo];
                     if (tok >= g0 + CPP) break;
                     const float wgt = p.edge_weight[lo];
@@ -274,71 +290,47 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const P& p
             }
         }
     }
+    // the four bits of a float4 that starts at logical column n: one nibble of the group's bits (constants where the form has none)
+    auto allowed4 = [&](int n) { return MASK ? (unsigned)(mbits >> (n - g0)) & 15u : 15u; };
+    auto seen4 = [&](int n) { return PEN ? (unsigned)(sbits >> (n - g0)) & 15u : 0u; };
     Top4 top;
     if constexpr (TOPK) {
-        static_assert(LSE, "EPI_TOPK keeps the exp sums too");
-        top4_clear(top);
+        topn_clear(top);
 #pragma unroll 2        // (a short body keeps the registers of the 128 x 128 variants below EPI_ARGMAX_LSE's: DESIGN.md 4.5)
         for (int q = 0; q < CPP / 4; ++q) {
             const int pc = part * CPP + ((rot + 4 * q) % CPP);
             const float4 cv = *reinterpret_cast<const float4*>(&sC[row * BN + pc]);
             const int n = n0 + (pc ^ sw);
             const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-            if constexpr (PEN) {
-                const unsigned nib = (unsigned)(mbits >> (n - g0)) & 15u;
-                const unsigned snib = (unsigned)(sbits >> (n - g0)) & 15u;
-                const float vx = cv.x + bv.x, vy = cv.y + bv.y, vz = cv.z + bv.z, vw = cv.w + bv.w;
-                top4_insert(top, (nib & 1) ? ((snib & 1) ? pen_logit(vx, pp) : vx) : -INFINITY, (nib & 1) ? n : 0x7fffffff);
-                top4_insert(top, (nib & 2) ? ((snib & 2) ? pen_logit(vy, pp) : vy) : -INFINITY, (nib & 2) ? n + 1 : 0x7fffffff);
-                top4_insert(top, (nib & 4) ? ((snib & 4) ? pen_logit(vz, pp) : vz) : -INFINITY, (nib & 4) ? n + 2 : 0x7fffffff);
-                top4_insert(top, (nib & 8) ? ((snib & 8) ? pen_logit(vw, pp) : vw) : -INFINITY, (nib & 8) ? n + 3 : 0x7fffffff);
-            } else if constexpr (MASK) {
-                const unsigned nib = (unsigned)(mbits >> (n - g0)) & 15u;
-                top4_insert(top, (nib & 1) ? cv.x + bv.x : -INFINITY, (nib & 1) ? n : 0x7fffffff);
-                top4_insert(top, (nib & 2) ? cv.y + bv.y : -INFINITY, (nib & 2) ? n + 1 : 0x7fffffff);
-                top4_insert(top, (nib & 4) ? cv.z + bv.z : -INFINITY, (nib & 4) ? n + 2 : 0x7fffffff);
-                top4_insert(top, (nib & 8) ? cv.w + bv.w : -INFINITY, (nib & 8) ? n + 3 : 0x7fffffff);
-            } else {
-            top4_insert(top, cv.x + bv.x, n);
-            top4_insert(top, cv.y + bv.y, n + 1);
-            top4_insert(top, cv.z + bv.z, n + 2);
-            top4_insert(top, cv.w + bv.w, n + 3);
-            }
+            const unsigned nib = allowed4(n), snib = seen4(n);
+            topn_insert(top, (nib & 1) ? lm_logit<PEN>(cv.x, bv.x, snib & 1, pp) : -INFINITY, (nib & 1) ? n : 0x7fffffff);
+            topn_insert(top, (nib & 2) ? lm_logit<PEN>(cv.y, bv.y, snib & 2, pp) : -INFINITY, (nib & 2) ? n + 1 : 0x7fffffff);
+            topn_insert(top, (nib & 4) ? lm_logit<PEN>(cv.z, bv.z, snib & 4, pp) : -INFINITY, (nib & 4) ? n + 2 : 0x7fffffff);
+            topn_insert(top, (nib & 8) ? lm_logit<PEN>(cv.w, bv.w, snib & 8, pp) : -INFINITY, (nib & 8) ? n + 3 : 0x7fffffff);
         }
 #pragma unroll
         for (int o = TPRW / 2; o > 0; o >>= 1) top4_merge_xor(top, o);
         best = top.v[0]; bi = top.i[0];
     } else {
 #pragma unroll
-    for (int q = 0; q < CPP / 4; ++q) {
-        const int pc = part * CPP + ((rot + 4 * q) % CPP);          // physical column of this float4
-        const float4 cv = *reinterpret_cast<const float4*>(&sC[row * BN + pc]);
-        const int n = n0 + (pc ^ sw);                                // logical (global) column of cv.x
-        const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-        float v[4] = {cv.x + bv.x, cv.y + bv.y, cv.z + bv.z, cv.w + bv.w};
-        if constexpr (PEN) {
-            const unsigned snib = (unsigned)(sbits >> (n - g0)) & 15u;
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if ((snib >> e) & 1) v[e] = pen_logit(v[e], pp);
-        }
-        if constexpr (MASK) {
-            const unsigned nib = (unsigned)(mbits >> (n - g0)) & 15u;
+        for (int q = 0; q < CPP / 4; ++q) {
+            const int pc = part * CPP + ((rot + 4 * q) % CPP);          // physical column of this float4
+            const float4 cv = *reinterpret_cast<const float4*>(&sC[row * BN + pc]);
+            const int n = n0 + (pc ^ sw);                                // logical (global) column of cv.x
+            const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
+            const unsigned nib = allowed4(n), snib = seen4(n);
+            const float v[4] = {lm_logit<PEN>(cv.x, bv.x, snib & 1, pp), lm_logit<PEN>(cv.y, bv.y, snib & 2, pp),
+                                lm_logit<PEN>(cv.z, bv.z, snib & 4, pp), lm_logit<PEN>(cv.w, bv.w, snib & 8, pp)};
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (((nib >> e) & 1) && (v[e] > best || (v[e] == best && n + e < bi))) { best = v[e]; bi = n + e; }
-        } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (v[e] > best || (v[e] == best && n + e < bi)) { best = v[e]; bi = n + e; }
         }
-    }
 #pragma unroll
-    for (int o = TPRW / 2; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
+        for (int o = TPRW / 2; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(best, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+        }
     }
     float esum = 0.f;
     if constexpr (LSE) {
@@ -346,23 +338,13 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const P& p
         for (int q = 0; q < CPP / 4; ++q) {
             const int pc = part * CPP + ((rot + 4 * q) % CPP);
             const float4 cv = *reinterpret_cast<const float4*>(&sC[row * BN + pc]);
-            const float4 bv = *reinterpret_cast<const float4*>(p.bias + n0 + (pc ^ sw));
-            if constexpr (PEN) {
-                const unsigned nib = (unsigned)(mbits >> (n0 + (pc ^ sw) - g0)) & 15u;
-                const unsigned snib = (unsigned)(sbits >> (n0 + (pc ^ sw) - g0)) & 15u;
-                const float vx = cv.x + bv.x, vy = cv.y + bv.y, vz = cv.z + bv.z, vw = cv.w + bv.w;
-                esum += (((nib & 1) ? __expf(((snib & 1) ? pen_logit(vx, pp) : vx) - best) : 0.f) +
-                         ((nib & 2) ? __expf(((snib & 2) ? pen_logit(vy, pp) : vy) - best) : 0.f)) +
-                        (((nib & 4) ? __expf(((snib & 4) ? pen_logit(vz, pp) : vz) - best) : 0.f) +
-                         ((nib & 8) ? __expf(((snib & 8) ? pen_logit(vw, pp) : vw) - best) : 0.f));
-            } else if constexpr (MASK) {
-                const unsigned nib = (unsigned)(mbits >> (n0 + (pc ^ sw) - g0)) & 15u;
-                esum += (((nib & 1) ? __expf((cv.x + bv.x) - best) : 0.f) + ((nib & 2) ? __expf((cv.y + bv.y) - best) : 0.f)) +
-                        (((nib & 4) ? __expf((cv.z + bv.z) - best) : 0.f) + ((nib & 8) ? __expf((cv.w + bv.w) - best) : 0.f));
-            } else {
-            esum += (__expf((cv.x + bv.x) - best) + __expf((cv.y + bv.y) - best)) +
-                    (__expf((cv.z + bv.z) - best) + __expf((cv.w + bv.w) - best));
-            }
+            const int n = n0 + (pc ^ sw);
+            const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
+            const unsigned nib = allowed4(n), snib = seen4(n);
+            esum += (((nib & 1) ? __expf(lm_logit<PEN>(cv.x, bv.x, snib & 1, pp) - best) : 0.f) +
+                     ((nib & 2) ? __expf(lm_logit<PEN>(cv.y, bv.y, snib & 2, pp) - best) : 0.f)) +
+                    (((nib & 4) ? __expf(lm_logit<PEN>(cv.z, bv.z, snib & 4, pp) - best) : 0.f) +
+                     ((nib & 8) ? __expf(lm_logit<PEN>(cv.w, bv.w, snib & 8, pp) - best) : 0.f));
         }
 #pragma unroll
         for (int o = TPRW / 2; o > 0; o >>= 1) esum += __shfl_xor(esum, o, 64);
@@ -374,10 +356,7 @@ __device__ __forceinline__ void gemm_epilogue_argmax(const float* sC, const P& p
             if ((unsigned)t < (unsigned)p.prefix_len[brow]) {
                 const int tgt = p.prefix[(size_t)brow * p.prefix_ld + t];
                 if (tgt >= g0 && tgt < g0 + CPP) {          // (logical column tgt - n0 sits at physical column (tgt - n0) ^ sw)
-                    float v = sC[row * BN + ((tgt - n0) ^ sw)] + p.bias[tgt];
-                    if constexpr (PEN) {
-                        if ((sbits >> (tgt - g0)) & 1ull) v = pen_logit(v, pp);
-                    }
+                    const float v = lm_logit<PEN>(sC[row * BN + ((tgt - n0) ^ sw)], p.bias[tgt], (sbits >> (tgt - g0)) & 1ull, pp);
                     p.tgt_val[m] = ((mbits >> (tgt - g0)) & 1ull) ? v : -INFINITY;
                 }
             }
@@ -424,7 +403,6 @@ template <typename T, int BM, int BN, int EPI, int NST = 2, bool TGT = false, bo
 __global__ __launch_bounds__(256) void gemm_kernel(std::conditional_t<PEN, GemmParamsPen, std::conditional_t<SOFT, GemmParamsSoft, GemmParams>> p) {
     static_assert(!SOFT || EPI == EPI_ARGMAX_M || EPI == EPI_ARGMAX_LSE_M || EPI == EPI_TOPK_M, "edge weights go into the masked LM head");
     static_assert(!PEN || SOFT, "the penalised LM head is the weighted one too");
-    using P = std::conditional_t<PEN, GemmParamsPen, std::conditional_t<SOFT, GemmParamsSoft, GemmParams>>;
     constexpr int TM = BM / 64, TN = BN / 64;          // 32x32 MFMA tiles per wave
     constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE = A_BYTES + B_BYTES;
     constexpr int LPT = (BM / 8 + BN / 8) / 4;         // DMA instructions per wave per K-tile
@@ -607,18 +585,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(std::conditional_t<PEN, GemmP
     }
     __syncthreads();
 
-    if constexpr (EPI == EPI_ARGMAX) {
-        gemm_epilogue_argmax<BM, BN, 256, SWZ>(sC, p, m0, n0, tid);
-    } else if constexpr (EPI == EPI_ARGMAX_LSE) {
-        gemm_epilogue_argmax<BM, BN, 256, SWZ, true>(sC, p, m0, n0, tid);
-    } else if constexpr (EPI == EPI_TOPK) {
-        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, true>(sC, p, m0, n0, tid);
-    } else if constexpr (EPI == EPI_ARGMAX_M) {
-        gemm_epilogue_argmax<BM, BN, 256, SWZ, false, false, true, false, SOFT, P, PEN>(sC, p, m0, n0, tid);
-    } else if constexpr (EPI == EPI_ARGMAX_LSE_M) {
-        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, false, true, TGT, SOFT, P, PEN>(sC, p, m0, n0, tid);
-    } else if constexpr (EPI == EPI_TOPK_M) {
-        gemm_epilogue_argmax<BM, BN, 256, SWZ, true, true, true, TGT, SOFT, P, PEN>(sC, p, m0, n0, tid);
+    if constexpr (epi_is_lm_head(EPI)) {
+        gemm_epilogue_argmax<BM, BN, 256, SWZ, EPI, TGT, SOFT, PEN>(sC, p, m0, n0, tid);
     } else if constexpr (EPI == EPI_BIAS) {
         GemmParams q = p;
         q.out = reinterpret_cast<T*>(p.out) + (size_t)blockIdx.y * p.o_yoff;

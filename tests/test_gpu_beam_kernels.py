@@ -157,6 +157,129 @@ def _state_of(sc, K):
     return st
 
 
+def _launch_and_check(eng, w, rs, K, nslab, dtype, cfg, bcfg, scs, n):
+    """One launch over the crop groups `scs` on n slots (beside two crops nobody decodes) against beam_util in float64
+    -> (the worst score error, the worst embedding error, the closest two candidates of the reference)."""
+    G = n // K
+    worst_score, worst_emb, min_gap = 0.0, 0.0, np.inf
+    crops_n = G + 2                             # two crops nobody decodes: their rows must stay as they are
+    R = crops_n * K
+    crop_of = rs.permutation(crops_n)[:G]
+    rowmap = np.full(n, R - 1, np.int32)        # (the padding slots of a partial group name a row of the last crop)
+    ids = np.full((R + 1, LD), SENT, np.int32)
+    step = np.zeros(n, np.int32)
+    finished = np.zeros(R, np.int32)
+    lens = np.full(R, ML, np.int32)
+    bscore = np.full(R, -5.5, np.float32)
+    parent = np.full(R, SENT, np.int32)
+    hyp_ids = np.full((R + 1, LD), PAD, np.int32)
+    hyp_len = np.zeros(R, np.int32)
+    hyp_score = np.full(R, -bu.NEG, np.float32)
+    hopen = np.full(crops_n, 1, np.int32)
+    logits = rs.randint(-512, -256, (n, V)).astype(np.float64) / 64.0
+    for g, sc in enumerate(scs):
+        c = int(crop_of[g])
+        for k in range(K):
+            r, s = c * K + k, g * K + k
+            rowmap[s] = r
+            step[s] = sc["t"]
+            ids[r, :sc["t"] + 1] = sc["hist"][k]
+            bscore[r] = sc["run"][k]
+            finished[r] = 1 if sc["finished"] else 0
+            logits[s] = sc["logits"][k]
+        for j, (s_, seq) in enumerate(sc["hyp"]):
+            hyp_ids[c * K + j, :len(seq)] = seq
+            hyp_len[c * K + j] = len(seq)
+            hyp_score[c * K + j] = s_
+        hopen[c] = 1 if sc["open"] else 0
+    step[G * K:] = 7                            # the padding slots' steps advance like everybody's
+    bias = rs.randint(-128, 128, V).astype(np.float64) / 64.0
+    parts = rs.randint(-128, 128, (nslab, n, V)).astype(np.float64) / 64.0
+    parts[-1] = logits - bias - parts[:-1].sum(0)
+    n_unf0 = 1000
+    d = dict(ids=_i32(ids), step=_i32(step), fin=_i32(finished), len=_i32(lens), unf=_i32([n_unf0, SENT]), map=_i32(rowmap),
+             bscore=_f32(bscore), parent=_i32(parent), hyp_ids=_i32(hyp_ids), hyp_len=_i32(hyp_len), hyp_score=_f32(hyp_score),
+             hopen=_i32(hopen))
+    x32 = torch.full((n + GUARD, D), float("nan"), device="cuda")
+    xt = torch.full((n + GUARD, D), float("nan"), device="cuda", dtype=torch.bfloat16 if dtype == "bf16" else torch.float32)
+    cache = torch.full((R, MAX_LEN, D), float("nan"), device="cuda", dtype=xt.dtype)
+    torch.cuda.synchronize()
+    eng.op_beam_select(bcfg, d["bscore"], d["parent"], d["hyp_ids"], d["hyp_len"], d["hyp_score"], d["hopen"],
+                       first=0, n=n, slabs=_f32(parts), nslab=nslab, vbias=_f32(bias), ids=d["ids"], step=d["step"], finished=d["fin"],
+                       len=d["len"], n_unfinished=d["unf"], rowmap=d["map"], ids_ld=LD, max_len=ML, n_real=G * K, x_f32=x32, x_t=xt,
+                       cache=cache)
+    got = {k: v.cpu().numpy() for k, v in d.items()}
+    # ---- the reference, group by group
+    want_ids, want_fin, want_len = ids.copy(), finished.copy(), lens.copy()
+    want_parent, want_hyp_ids, want_hyp_len = parent.copy(), hyp_ids.copy(), hyp_len.copy()
+    want_hyp_score = hyp_score.astype(np.float64)
+    want_bscore = bscore.astype(np.float64)
+    want_open = hopen.copy()
+    n_unf = n_unf0
+    emb = {}                                    # slot -> (row, token, position)
+    for g, sc in enumerate(scs):
+        c = int(crop_of[g])
+        if sc["finished"]:
+            continue
+        st = _state_of(sc, K)
+        cv, cpar, ctok, stop = bu.step(bu.accumulate(sc["logits"], st, cfg), st, cfg, ML, EOS)
+        assert sc["check"](dict(cv=cv, cpar=cpar, ctok=ctok, stop=stop)), f"situation {sc} is not what it says"
+        assert st.min_gap >= 1e-3, f"a constructed case has candidates {st.min_gap} apart"
+        min_gap = min(min_gap, st.min_gap)
+        L = sc["t"] + 1
+        for j in range(K):
+            r = c * K + j
+            want_hyp_len[r] = len(st.hyp_seq[j])
+            want_hyp_score[r] = st.hyp_score[j]
+            want_hyp_ids[r] = PAD
+            want_hyp_ids[r, :len(st.hyp_seq[j])] = st.hyp_seq[j]
+        want_open[c] = 1 if st.open else 0
+        for k in range(K):
+            r = c * K + k
+            if st.done:
+                want_fin[r], want_len[r], want_parent[r] = 1, sc["t"] + 2, k
+                want_bscore[r] = np.nan        # (written, but nobody reads a crop's running scores once it ended)
+            else:
+                want_parent[r] = st.parents[k]
+                want_bscore[r] = st.run[k]
+                want_ids[r, :L + 1] = st.seqs[k]
+                emb[g * K + k] = (r, st.seqs[k][-1], L)
+        n_unf -= K if st.done else 0
+    np.testing.assert_array_equal(got["ids"], want_ids, err_msg="ids: the new beams' histories (a crop that ended keeps its rows)")
+    np.testing.assert_array_equal(got["parent"], want_parent, err_msg="parent")
+    np.testing.assert_array_equal(got["fin"], want_fin, err_msg="finished")
+    np.testing.assert_array_equal(got["len"], want_len, err_msg="len")
+    np.testing.assert_array_equal(got["unf"], [n_unf, SENT], err_msg="n_unfinished drops by K per crop that ended")
+    np.testing.assert_array_equal(got["step"], step + 1, err_msg="step advances in every slot, padding and ended crops included")
+    np.testing.assert_array_equal(got["map"], rowmap)
+    np.testing.assert_array_equal(got["hopen"], want_open, err_msg="heuristic_open")
+    np.testing.assert_array_equal(got["hyp_len"], want_hyp_len, err_msg="finished set: lengths")
+    np.testing.assert_array_equal(got["hyp_ids"], want_hyp_ids, err_msg="finished set: ids")
+    live = ~np.isnan(want_bscore)
+    for name, g_, w_ in (("hyp_score", got["hyp_score"], want_hyp_score), ("beam_score", got["bscore"][live], want_bscore[live])):
+        err = float(np.abs(g_.astype(np.float64) - w_).max())
+        worst_score = max(worst_score, err)
+        assert err <= 1e-5, f"{name}: {err} from float64"
+    # ---- the next inputs: x by slot, the layer-0 cache by row at position t + 1; nothing else
+    g32, gt, gc = x32.cpu().numpy().astype(np.float64), xt.float().cpu().numpy().astype(np.float64), cache.float().cpu().numpy()
+    written = np.zeros((R, MAX_LEN), bool)
+    for s in range(n + GUARD):
+        if s not in emb:
+            assert np.isnan(g32[s]).all() and np.isnan(gt[s]).all(), f"x of slot {s} written (ended crop, padding or guard)"
+            continue
+        r, tok, p = emb[s]
+        ref = _emb_ref(w, tok, p)
+        err = float((np.abs(g32[s] - ref) / np.abs(ref).max()).max())
+        worst_emb = max(worst_emb, err)
+        assert err <= 1e-5, f"embedding of slot {s}: {err} of the row scale"
+        stored = bf16_round(g32[s].astype(np.float32)).astype(np.float64) if dtype == "bf16" else g32[s].astype(np.float32).astype(np.float64)
+        np.testing.assert_array_equal(gt[s], stored, err_msg="x_t != storage rounding of x_f32")
+        np.testing.assert_array_equal(gc[r, p].astype(np.float64), gt[s], err_msg="cache row != x_t")
+        written[r, p] = True
+    assert np.isnan(gc[~written]).all(), "cache written outside the new beams' rows at position t + 1"
+    return worst_score, worst_emb, min_gap
+
+
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("nslab", [1, 3])
 @pytest.mark.parametrize("K", [2, 3, 4])
@@ -174,124 +297,39 @@ def test_beam_select_against_float64(K, nslab, dtype):
     for first in range(0, len(SITUATIONS), G):
         scs = [SITUATIONS[(first + g) % len(SITUATIONS)](rs, K) for g in range(G)]
         seen.update((first + g) % len(SITUATIONS) for g in range(G))
-        crops_n = G + 2                             # two crops nobody decodes: their rows must stay as they are
-        R = crops_n * K
-        crop_of = rs.permutation(crops_n)[:G]
-        rowmap = np.full(n, R - 1, np.int32)        # (the padding slots of a partial group name a row of the last crop)
-        ids = np.full((R + 1, LD), SENT, np.int32)
-        step = np.zeros(n, np.int32)
-        finished = np.zeros(R, np.int32)
-        lens = np.full(R, ML, np.int32)
-        bscore = np.full(R, -5.5, np.float32)
-        parent = np.full(R, SENT, np.int32)
-        hyp_ids = np.full((R + 1, LD), PAD, np.int32)
-        hyp_len = np.zeros(R, np.int32)
-        hyp_score = np.full(R, -bu.NEG, np.float32)
-        hopen = np.full(crops_n, 1, np.int32)
-        logits = rs.randint(-512, -256, (n, V)).astype(np.float64) / 64.0
-        for g, sc in enumerate(scs):
-            c = int(crop_of[g])
-            for k in range(K):
-                r, s = c * K + k, g * K + k
-                rowmap[s] = r
-                step[s] = sc["t"]
-                ids[r, :sc["t"] + 1] = sc["hist"][k]
-                bscore[r] = sc["run"][k]
-                finished[r] = 1 if sc["finished"] else 0
-                logits[s] = sc["logits"][k]
-            for j, (s_, seq) in enumerate(sc["hyp"]):
-                hyp_ids[c * K + j, :len(seq)] = seq
-                hyp_len[c * K + j] = len(seq)
-                hyp_score[c * K + j] = s_
-            hopen[c] = 1 if sc["open"] else 0
-        step[G * K:] = 7                            # the padding slots' steps advance like everybody's
-        bias = rs.randint(-128, 128, V).astype(np.float64) / 64.0
-        parts = rs.randint(-128, 128, (nslab, n, V)).astype(np.float64) / 64.0
-        parts[-1] = logits - bias - parts[:-1].sum(0)
-        n_unf0 = 1000
-        d = dict(ids=_i32(ids), step=_i32(step), fin=_i32(finished), len=_i32(lens), unf=_i32([n_unf0, SENT]), map=_i32(rowmap),
-                 bscore=_f32(bscore), parent=_i32(parent), hyp_ids=_i32(hyp_ids), hyp_len=_i32(hyp_len), hyp_score=_f32(hyp_score),
-                 hopen=_i32(hopen))
-        x32 = torch.full((n + GUARD, D), float("nan"), device="cuda")
-        xt = torch.full((n + GUARD, D), float("nan"), device="cuda", dtype=torch.bfloat16 if dtype == "bf16" else torch.float32)
-        cache = torch.full((R, MAX_LEN, D), float("nan"), device="cuda", dtype=xt.dtype)
-        torch.cuda.synchronize()
-        eng.op_beam_select(bcfg, d["bscore"], d["parent"], d["hyp_ids"], d["hyp_len"], d["hyp_score"], d["hopen"],
-                           first=0, n=n, slabs=_f32(parts), nslab=nslab, vbias=_f32(bias), ids=d["ids"], step=d["step"], finished=d["fin"],
-                           len=d["len"], n_unfinished=d["unf"], rowmap=d["map"], ids_ld=LD, max_len=ML, n_real=G * K, x_f32=x32, x_t=xt,
-                           cache=cache)
-        got = {k: v.cpu().numpy() for k, v in d.items()}
-        # ---- the reference, group by group
-        want_ids, want_fin, want_len = ids.copy(), finished.copy(), lens.copy()
-        want_parent, want_hyp_ids, want_hyp_len = parent.copy(), hyp_ids.copy(), hyp_len.copy()
-        want_hyp_score = hyp_score.astype(np.float64)
-        want_bscore = bscore.astype(np.float64)
-        want_open = hopen.copy()
-        n_unf = n_unf0
-        emb = {}                                    # slot -> (row, token, position)
-        for g, sc in enumerate(scs):
-            c = int(crop_of[g])
-            if sc["finished"]:
-                continue
-            st = _state_of(sc, K)
-            cv, cpar, ctok, stop = bu.step(bu.accumulate(sc["logits"], st, cfg), st, cfg, ML, EOS)
-            assert sc["check"](dict(cv=cv, cpar=cpar, ctok=ctok, stop=stop)), f"situation {sc} is not what it says"
-            assert st.min_gap >= 1e-3, f"a constructed case has candidates {st.min_gap} apart"
-            min_gap = min(min_gap, st.min_gap)
-            L = sc["t"] + 1
-            for j in range(K):
-                r = c * K + j
-                want_hyp_len[r] = len(st.hyp_seq[j])
-                want_hyp_score[r] = st.hyp_score[j]
-                want_hyp_ids[r] = PAD
-                want_hyp_ids[r, :len(st.hyp_seq[j])] = st.hyp_seq[j]
-            want_open[c] = 1 if st.open else 0
-            for k in range(K):
-                r = c * K + k
-                if st.done:
-                    want_fin[r], want_len[r], want_parent[r] = 1, sc["t"] + 2, k
-                    want_bscore[r] = np.nan        # (written, but nobody reads a crop's running scores once it ended)
-                else:
-                    want_parent[r] = st.parents[k]
-                    want_bscore[r] = st.run[k]
-                    want_ids[r, :L + 1] = st.seqs[k]
-                    emb[g * K + k] = (r, st.seqs[k][-1], L)
-            n_unf -= K if st.done else 0
-        np.testing.assert_array_equal(got["ids"], want_ids, err_msg="ids: the new beams' histories (a crop that ended keeps its rows)")
-        np.testing.assert_array_equal(got["parent"], want_parent, err_msg="parent")
-        np.testing.assert_array_equal(got["fin"], want_fin, err_msg="finished")
-        np.testing.assert_array_equal(got["len"], want_len, err_msg="len")
-        np.testing.assert_array_equal(got["unf"], [n_unf, SENT], err_msg="n_unfinished drops by K per crop that ended")
-        np.testing.assert_array_equal(got["step"], step + 1, err_msg="step advances in every slot, padding and ended crops included")
-        np.testing.assert_array_equal(got["map"], rowmap)
-        np.testing.assert_array_equal(got["hopen"], want_open, err_msg="heuristic_open")
-        np.testing.assert_array_equal(got["hyp_len"], want_hyp_len, err_msg="finished set: lengths")
-        np.testing.assert_array_equal(got["hyp_ids"], want_hyp_ids, err_msg="finished set: ids")
-        live = ~np.isnan(want_bscore)
-        for name, g_, w_ in (("hyp_score", got["hyp_score"], want_hyp_score), ("beam_score", got["bscore"][live], want_bscore[live])):
-            err = float(np.abs(g_.astype(np.float64) - w_).max())
-            worst_score = max(worst_score, err)
-            assert err <= 1e-5, f"{name}: {err} from float64"
-        # ---- the next inputs: x by slot, the layer-0 cache by row at position t + 1; nothing else
-        g32, gt, gc = x32.cpu().numpy().astype(np.float64), xt.float().cpu().numpy().astype(np.float64), cache.float().cpu().numpy()
-        written = np.zeros((R, MAX_LEN), bool)
-        for s in range(n + GUARD):
-            if s not in emb:
-                assert np.isnan(g32[s]).all() and np.isnan(gt[s]).all(), f"x of slot {s} written (ended crop, padding or guard)"
-                continue
-            r, tok, p = emb[s]
-            ref = _emb_ref(w, tok, p)
-            err = float((np.abs(g32[s] - ref) / np.abs(ref).max()).max())
-            worst_emb = max(worst_emb, err)
-            assert err <= 1e-5, f"embedding of slot {s}: {err} of the row scale"
-            stored = bf16_round(g32[s].astype(np.float32)).astype(np.float64) if dtype == "bf16" else g32[s].astype(np.float32).astype(np.float64)
-            np.testing.assert_array_equal(gt[s], stored, err_msg="x_t != storage rounding of x_f32")
-            np.testing.assert_array_equal(gc[r, p].astype(np.float64), gt[s], err_msg="cache row != x_t")
-            written[r, p] = True
-        assert np.isnan(gc[~written]).all(), "cache written outside the new beams' rows at position t + 1"
+        ws, we, mg = _launch_and_check(eng, w, rs, K, nslab, dtype, cfg, bcfg, scs, n)
+        worst_score, worst_emb, min_gap = max(worst_score, ws), max(worst_emb, we), min(min_gap, mg)
     assert seen == set(range(len(SITUATIONS)))
     report(f"beam_select {dtype} K={K} nslab={nslab}: 8 situations exact; scores {worst_score:.2e} from float64, embedding {worst_emb:.2e} "
            f"of the row scale; closest candidates {min_gap:.2e}")
+
+
+def _sc_windows(rs, K, n):
+    """no_repeat_ngram_size n on histories of five tokens: token 60 - the best of both beams - is banned for beam 1 only.
+    n = 1: every token of a row is banned, and beam 1 alone holds 60.  n = 3: beam 1 ends in (50, 51), which it holds
+    followed by 60; beam 0 ends in (50, 51) too, but holds it nowhere else - it holds 51 followed by 60, the ban of n = 2."""
+    sc = _base(rs, K, 4)
+    sc["hist"][0] = {1: [START, 50, 61, 52, 53], 3: [START, 51, 60, 50, 51]}[n]
+    sc["hist"][1] = {1: [START, 50, 60, 52, 53], 3: [50, 51, 60, 50, 51]}[n]
+    for k in range(K):
+        sc["logits"][k, 60] = 5.0
+        _plant(sc, k, 600 + 10 * k, [3.0 - 0.5 * j - 0.125 * k for j in range(3)])
+    sc["check"] = lambda c: (0, 60) in list(zip(c["cpar"], c["ctok"])) and (1, 60) not in list(zip(c["cpar"], c["ctok"]))
+    return sc
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("n", [1, 3])
+def test_beam_ngram_windows_exact(n, dtype):
+    """The selection's n-gram scan at the window lengths the launches above (n = 2) do not run: an empty key and a key of two
+    tokens.  K = 2, one live group beside the two untouched crops, one slab; everything test_beam_select_against_float64 asserts."""
+    from manga_ocr.engine import BeamConfig
+    K = 2
+    rs = np.random.RandomState(77 + 10 * n + (dtype == "bf16"))
+    ws, we, mg = _launch_and_check(engine(dtype), weights(0), rs, K, 1, dtype, bu.Config(K, 1.0, True, n), BeamConfig(K, 1.0, True, n),
+                                   [_sc_windows(rs, K, n)], K)
+    report(f"beam_select {dtype} K={K} no_repeat_ngram_size={n}: exact; scores {ws:.2e} from float64, embedding {we:.2e} of the row scale; "
+           f"closest candidates {mg:.2e}")
 
 
 # ------------------------------------------------------------------------------------------------ the cache reorder
