@@ -348,12 +348,10 @@ struct mocr_engine : LaneCtx {
     int regime = 0;
     int rrows(int n) const { return regime > 0 ? regime : n; }
     bool use_latent(int n) const { return latent && n > classic_rows; }
-    int smallm_rows = 0;            // bf16: batches of up to this many rows take the one-launch-per-projection path (kernels_smallm.h)
-    bool beam_batch = false;        // the batch being scheduled is a beam batch (set with `regime`): no one-launch-per-projection path
-    bool automaton_batch = false;   // the batch being advanced brings token automata (set with `regime`): the token kernel gets the tables
-    bool soft_batch = false;        // ... and one of them is soft: the token kernel and the LM head get the weights and the default edges too
-    bool penalty_batch = false;     // ... and a row has a repetition penalty: they get the rows' seen words and penalties too
-    bool use_smallm(int n) const { return n <= smallm_rows && !use_latent(n) && !beam_batch; }
+    // bf16: greedy batches of up to this many rows take the one-launch-per-projection path (kernels_smallm.h); a beam batch
+    // never does - whoever asks about one says !DecMode::beam first
+    int smallm_rows = 0;
+    bool use_smallm(int n) const { return n <= smallm_rows && !use_latent(n); }
     std::vector<mocr_beam_config> beam_cfgs;    // the beam configurations seen: a decode graph bakes one in, its key names it by index
     std::map<std::string, std::vector<float>> host_w;
     std::map<std::string, std::vector<int64_t>> host_shape;
@@ -1469,15 +1467,16 @@ static DecTokenArgs dec_token_args(mocr_engine* e, int nslab, int n) {
     return a;
 }
 
+// The token kernel of a batch in mode `m` (the start token's, FIRST, is the same for every mode)
 template <typename T, bool FIRST>
-void dec_token(mocr_engine* e, const DecState& st, int nslab, int n, int ncand = 0) {
+void dec_token(mocr_engine* e, const DecState& st, const DecMode& m, int nslab, int n, int ncand = 0) {
     DecTokenArgs a = dec_token_args(e, nslab, n);
     a.cand_val = e->cand_val; a.cand_idx = e->cand_idx; a.ncand = ncand; a.cand_sum = e->cand_sum;
     a.top_val = e->top_val; a.top_idx = e->top_idx;
-    if (!FIRST && e->automaton_batch) {
+    if (!FIRST && m.automaton) {
         static_cast<DecAutomata&>(a.aut) = DecAutomata{e->aut_edge_begin, e->aut_edge_token, e->aut_edge_next, e->aut_accepting, e->aut_base_of_row, e->aut_state};
-        if (e->soft_batch) { a.aut.edge_weight = e->aut_edge_weight; a.aut.default_next = e->aut_default_next; }
-        if (e->penalty_batch) a.aut.pen = DecPenalty{e->seen_mask, e->penalty_of_row};
+        if (m.soft) { a.aut.edge_weight = e->aut_edge_weight; a.aut.default_next = e->aut_default_next; }
+        if (m.penalty) a.aut.pen = DecPenalty{e->seen_mask, e->penalty_of_row};
     }
     launch_dec_token<T, FIRST>(e, st, a, n);
 }
@@ -2008,7 +2007,7 @@ void decode_step_smallm(mocr_engine* e, const DecState& st, const DecMode& m, in
     v.rows = n; v.K = D; v.a_f32 = e->a_f32; v.ln_g = w.lntg; v.ln_b = w.lntb;
     v.w = W(w.wv); v.N = e->V; v.out = e->slabs; v.ldo = e->V;
     smallm_gemm(e, "sm_vocab", SM_PRO_LN, SM_EPI_RAW, v);
-    dec_token<T, false>(e, st, 1, n);
+    dec_token<T, false>(e, st, m, 1, n);
 }
 
 // One greedy step for n rows; `t` is only used for the profiler's byte estimate.
@@ -2082,10 +2081,10 @@ void decode_step(mocr_engine* e, const DecState& st, const DecMode& m, int n, in
         GemmCall head = gemm_call(m.head_name(), e->z_t, D, w.wv, w.bv, e->cand_val, e->V, n, e->V, D, m.epilogue(), vt);
         head.lm = &lm;
         gemm<T>(e, head);
-        dec_token<T, false>(e, st, 1, n, e->V / vt);
+        dec_token<T, false>(e, st, m, 1, n, e->V / vt);
     } else {
         ns = dec_gemm<T>(e, "gemm_dec_vocab", e->z_t, D, w.wv, e->V, D, n);
-        dec_token<T, false>(e, st, ns, n);
+        dec_token<T, false>(e, st, m, ns, n);
     }
 }
 
@@ -2162,7 +2161,7 @@ hipGraphExec_t decode_graph(mocr_engine* e, const DecState& st, const DecMode& m
 template <typename T>
 void run_decode_forced(mocr_engine* e, int n, const int* forced, int forced_T, float* logits_out) {
     DecState st = make_state(e, e->cfg.max_len, forced, forced_T, logits_out, n);
-    dec_token<T, true>(e, st, 0, n);
+    dec_token<T, true>(e, st, DecMode{}, 0, n);
     for (int t = 0; t < forced_T; ++t) decode_step<T>(e, st, DecMode{}, n, t);
 }
 
@@ -2221,7 +2220,8 @@ struct DecPlan {
     bool attn_nt;                     // classic attention: non-temporal K/V loads
     int chunk, graph_rows;            // steps per graph replay; the rows this count is rounded up to (<= max_batch)
 };
-// a test hook's regime: set for the hook's launches (or its plan), as the scheduler sets it around a batch's steps
+// The only writer of mocr_engine::regime: set around a batch's scheduling step (pump_once) or a test hook's launches (or its
+// plan), and put back on every way out - an exception too
 struct RegimeScope {
     mocr_engine* e; int old;
     RegimeScope(mocr_engine* e_, int r) : e(e_), old(e_->regime) { e->regime = r; }
@@ -2444,28 +2444,39 @@ void run_positions(mocr_engine* e, Lane& L) {
     }
 }
 
-// A per-crop int array of the batch's jobs (an empty one: `fill`), merged in row order over the np slots and uploaded.
-static void upload_per_row(mocr_engine* e, const Lane& L, std::vector<int>& stage, std::vector<int32_t> Job::*field, int fill, int* d_dst) {
-    stage.assign((size_t)L.np, fill);
-    int r0 = 0;
+// THE merge of a per-row array of the batch's jobs: `ld` elements a row over the np slots, in row order, staged in `stage` (the
+// lane's: it outlives the async copy) and uploaded to d_dst.  put(job, dst) writes the job's rows at dst, its first row; what
+// it leaves alone - the padding rows, a job without the array - reads `fill`.
+template <typename V, typename Put>
+static void upload_rows(mocr_engine* e, const Lane& L, std::vector<V>& stage, V fill, V* d_dst, Put put, size_t ld = 1) {
+    stage.assign((size_t)L.np * ld, fill);
+    size_t r0 = 0;
     for (const Job& j : L.jobs) {
-        std::copy((j.*field).begin(), (j.*field).end(), stage.begin() + r0);
+        put(j, stage.data() + r0 * ld);
         r0 += j.n;
     }
-    HIPCHECK(hipMemcpyAsync(d_dst, stage.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(hipMemcpyAsync(d_dst, stage.data(), stage.size() * sizeof(V), hipMemcpyHostToDevice, e->stream));
+}
+// put: a job's array as it comes, one element a row (empty: the job has none)
+template <typename V> static auto whole(std::vector<V> Job::*field) {
+    return [field](const Job& j, V* dst) { std::copy((j.*field).begin(), (j.*field).end(), dst); };
 }
 
-// Token automata: the global start state of every row's automaton (a beam batch: by row c K + k, like the sets), uploaded to
-// aut_base_of_row; the padding rows and the rows without an automaton: -1.
+// Token constraints: the merged rows' sets (a beam batch: by row c K + k - a beam job carries its crops' handles expanded);
+// the padding rows and the rows of unconstrained jobs: set 0, so the table exists whoever made no set
+static void upload_sets(mocr_engine* e, Lane& L) {
+    ensure_tok_table(e);
+    ensure_set_buffer(e);
+    upload_rows(e, L, L.h_sets, (int)MOCR_TOKEN_SET_ALL, e->set_of_row, whole(&Job::sets));
+}
+
+// Token automata: the global start state of every row's automaton (a beam batch: by row c K + k, like the sets); the padding
+// rows and the rows without an automaton: -1
 static void upload_start_states(mocr_engine* e, Lane& L) {
-    L.h_aut.assign((size_t)L.np, -1);
-    int r0 = 0;
-    for (const Job& j : L.jobs) {
+    upload_rows(e, L, L.h_aut, -1, e->aut_base_of_row, [e](const Job& j, int* dst) {
         for (size_t i = 0; i < j.automata.size(); ++i)
-            if (j.automata[i] != MOCR_AUTOMATON_NONE) L.h_aut[r0 + i] = e->aut_first[j.automata[i]];
-        r0 += j.n;
-    }
-    HIPCHECK(hipMemcpyAsync(e->aut_base_of_row, L.h_aut.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
+            if (j.automata[i] != MOCR_AUTOMATON_NONE) dst[i] = e->aut_first[j.automata[i]];
+    });
 }
 
 // The decode rows' source of a batch with shared encodings, for the bound lane: allocated by the first batch in which a job
@@ -2474,24 +2485,47 @@ static void ensure_share_buffer(mocr_engine* e) {
     if (!e->src_of_row) e->src_of_row = e->dalloc<int>((size_t)e->Bp);
 }
 
-// out[r] = in[d_src_of_row[r]] for r < rows, rows of S x D elements of the engine's dtype; `in` holds n_src of them and is
-// not `out` (kernels_share.h).
+// The three lazily allocated groups of beam buffers, each as the list of its arrays - arr(pointer, elements) for every one, on
+// the bound lane's pointers: ensure_beam_*_buffers allocates from the list (Dalloc), mocr_beam_*_state_bytes adds it up (a
+// lane's bytes are the same for every lane), so the report cannot drift from the allocation.
+struct Dalloc {
+    mocr_engine* e;
+    template <typename X> void operator()(X*& p, size_t count) const { p = e->dalloc<X>(count); }
+};
+// what the lanes that hold a group (`has`: the array its ensure function looks at) spend on it
+template <typename Has, typename Group> static int64_t beam_group_bytes(mocr_engine* e, Has has, Group group) {
+    if (!e) return -1;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int64_t lanes = 0, bytes = 0;
+    for (const Lane& L : e->lanes) lanes += has(L.ctx) ? 1 : 0;
+    group(e, [&bytes](auto* p, size_t count) { bytes += (int64_t)(count * sizeof(*p)); });
+    return lanes * bytes;
+}
+// five [Bp] arrays and hyp_ids [Bp][max_len]
+static const auto beam_state_arrays = [](mocr_engine* e, auto&& arr) {
+    const size_t Bp = (size_t)e->Bp;
+    arr(e->beam_score, Bp); arr(e->hyp_score, Bp);
+    arr(e->beam_parent, Bp); arr(e->hyp_len, Bp); arr(e->heuristic_open, Bp);
+    arr(e->hyp_ids, Bp * e->cfg.max_len);
+};
+// beam_logp and hyp_logp [Bp][max_len]
+static const auto beam_token_arrays = [](mocr_engine* e, auto&& arr) {
+    arr(e->beam_logp, (size_t)e->Bp * e->cfg.max_len); arr(e->hyp_logp, (size_t)e->Bp * e->cfg.max_len);
+};
+// beam_trail and hyp_trail [Bp][max_len], a byte each
+static const auto beam_position_arrays = [](mocr_engine* e, auto&& arr) {
+    arr(e->beam_trail, (size_t)e->Bp * e->cfg.max_len); arr(e->hyp_trail, (size_t)e->Bp * e->cfg.max_len);
+};
+
 // The beam state of the bound lane: allocated by the first beam batch, like the alternatives buffers.
 static void ensure_beam_buffers(mocr_engine* e) {
-    if (e->hyp_ids) return;
-    const size_t Bp = (size_t)e->Bp;
-    e->beam_score = e->dalloc<float>(Bp); e->hyp_score = e->dalloc<float>(Bp);
-    e->beam_parent = e->dalloc<int>(Bp); e->hyp_len = e->dalloc<int>(Bp); e->heuristic_open = e->dalloc<int>(Bp);
-    e->hyp_ids = e->dalloc<int>(Bp * e->cfg.max_len);
+    if (!e->hyp_ids) beam_state_arrays(e, Dalloc{e});
 }
 
 // The token form's two histories, for the bound lane: allocated by the first beam batch that asks for token scores or
 // brings a token set, so engines that run plain beam batches keep the footprint mocr_beam_state_bytes reports.
 static void ensure_beam_token_buffers(mocr_engine* e) {
-    if (e->hyp_logp) return;
-    const size_t Bp = (size_t)e->Bp;
-    e->beam_logp = e->dalloc<float>(Bp * e->cfg.max_len);
-    e->hyp_logp = e->dalloc<float>(Bp * e->cfg.max_len);
+    if (!e->hyp_logp) beam_token_arrays(e, Dalloc{e});
 }
 
 // The automaton form's hypothesis states, for the bound lane (the beams' states and the crops' start states are the greedy
@@ -2504,12 +2538,11 @@ static void ensure_beam_automaton_buffers(mocr_engine* e) {
 
 // The trail form's two histories, for the bound lane: allocated by the first beam batch that asks for token positions.
 static void ensure_beam_position_buffers(mocr_engine* e) {
-    if (e->hyp_trail) return;
-    const size_t Bp = (size_t)e->Bp;
-    e->beam_trail = e->dalloc<uint8_t>(Bp * e->cfg.max_len);
-    e->hyp_trail = e->dalloc<uint8_t>(Bp * e->cfg.max_len);
+    if (!e->hyp_trail) beam_position_arrays(e, Dalloc{e});
 }
 
+// out[r] = in[d_src_of_row[r]] for r < rows, rows of S x D elements of the engine's dtype; `in` holds n_src of them and is
+// not `out` (kernels_share.h).
 static void launch_enc_expand(mocr_engine* e, const void* in, void* out, const int* d_src_of_row, int n_src, int rows) {
     const size_t row_bytes = (size_t)e->S * e->D * e->esz;
     if (row_bytes % 16 || in == out) throw ArgError{"enc_expand: rows of whole 16-byte pieces, out of place", MOCR_ERR_UNSUPPORTED};
@@ -2520,13 +2553,11 @@ static void launch_enc_expand(mocr_engine* e, const void* in, void* out, const i
     HIPCHECK(hipGetLastError());
 }
 
-template <typename T>
-void start_batch(mocr_engine* e, Lane& L) {
+// start_batch, part 1: the jobs' planes staged in d_in, one per distinct source of every job - the encoder runs on n_enc <= n crops
+static void stage_planes(mocr_engine* e, const Lane& L) {
     const int IMG = e->cfg.image_size;
     const size_t plane = (size_t)IMG * IMG;
-    // one plane per distinct source of every job: the encoder runs on n_enc <= n crops
     int plane0 = 0;
-    bool shares = false;
     for (const Job& j : L.jobs) {
         uint8_t* gdst = e->d_in + (size_t)plane0 * plane;
         const size_t rowb = (size_t)IMG * j.channels;
@@ -2557,9 +2588,14 @@ void start_batch(mocr_engine* e, Lane& L) {
             HIPCHECK(hipGetLastError());
         }
         plane0 += j.n_src;
-        shares = shares || !j.src_of_row.empty();
     }
+}
+
+// start_batch, part 2: the staged planes encoded into ENC, one encoding per decode row, and what the attention path reads of them
+template <typename T>
+static void encode_batch(mocr_engine* e, Lane& L) {
     e->n_encoded += L.n_enc;
+    const bool shares = std::any_of(L.jobs.begin(), L.jobs.end(), [](const Job& j) { return !j.src_of_row.empty(); });
     if (!shares) run_encoder<T>(e, e->d_in, L.n);
     else {
         // Shared encodings: the final LayerNorm leaves the n_enc encodings in CTX - dead since the last layer's O-projection -
@@ -2567,59 +2603,48 @@ void start_batch(mocr_engine* e, Lane& L) {
         if (L.n_enc > L.n || (size_t)L.n_enc * e->S * e->D * sizeof(T) > e->ctx_cap)
             throw ArgError{"shared encodings: the staging buffer is too small for this batch", MOCR_ERR_STATE};
         ensure_share_buffer(e);
-        L.h_src.assign((size_t)L.np, 0);
-        int r0 = 0, p0 = 0;
-        for (const Job& j : L.jobs) {
-            for (int i = 0; i < j.n; ++i) L.h_src[r0 + i] = p0 + (j.src_of_row.empty() ? i : j.src_of_row[i]);
-            r0 += j.n; p0 += j.n_src;
-        }
-        HIPCHECK(hipMemcpyAsync(e->src_of_row, L.h_src.data(), (size_t)L.np * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        // (a row's source counts from the job's first plane of the batch, p0; a job that shares nothing: row i reads its plane i)
+        upload_rows(e, L, L.h_src, 0, e->src_of_row, [p0 = 0](const Job& j, int* dst) mutable {
+            for (int i = 0; i < j.n; ++i) dst[i] = p0 + (j.src_of_row.empty() ? i : j.src_of_row[i]);
+            p0 += j.n_src;
+        });
         run_encoder<T>(e, e->d_in, L.n_enc, e->CTX);
         launch_enc_expand(e, e->CTX, e->ENC, e->src_of_row, L.n_enc, L.n);
     }
     if (!e->use_latent(L.np0)) run_cross_kv<T>(e, L.n);
     else if (e->fp8attn) quantize_enc(e, L.n);
+}
+
+// start_batch, part 3: the decode state of the batch's mode - one block per feature, in stream order the uploads, memsets and
+// init kernels of the features, the start token's kernel, the beam state
+template <typename T>
+static void prepare_decode(mocr_engine* e, Lane& L) {
+    const DecMode& m = L.mode;
     // rows read pad_id (= 0) beyond what the loop writes
     HIPCHECK(hipMemsetAsync(e->ids, 0, (size_t)L.np * e->cfg.max_len * sizeof(int), e->stream));
-    // The batch runs in the richest mode any of its jobs asked for.  Scores: the start token and the pad tail score 0;
-    // alternatives: positions the steps do not write read -1 / 0
-    L.mode = mode_of(L.jobs);
-    if (L.mode.automaton || L.mode.beam_automaton)      // soft token automata: the batch takes the mode if any row's automaton is soft
-        for (const Job& j : L.jobs)
-            for (int32_t h : j.automata) L.mode.soft = L.mode.soft || e->aut_soft[h] != 0;
-    const DecMode& m = L.mode;
+    // Scores: the start token and the pad tail score 0; alternatives: positions the steps do not write read -1 / 0
     if (m.level >= 1) HIPCHECK(hipMemsetAsync(e->scores, 0, (size_t)L.np * e->cfg.max_len * sizeof(float), e->stream));
     if (m.level >= 2) {
         ensure_alt_buffers(e);
         HIPCHECK(hipMemsetAsync(e->alt_ids, 0xFF, (size_t)L.np * e->cfg.max_len * MOCR_ALTERNATIVES * sizeof(int), e->stream));
         HIPCHECK(hipMemsetAsync(e->alt_logp, 0, (size_t)L.np * e->cfg.max_len * MOCR_ALTERNATIVES * sizeof(float), e->stream));
     }
-    // token constraints: the merged rows' sets go up before the first decode graph (the padding rows and the rows of
-    // unconstrained jobs: set 0)
-    if (m.mask) {
-        if (m.prefix) ensure_tok_table(e);      // (a prefixed batch runs masked even when nobody made a set: every row reads set 0)
-        ensure_set_buffer(e);
-        upload_per_row(e, L, L.h_sets, &Job::sets, MOCR_TOKEN_SET_ALL, e->set_of_row);
-    }
+    // token constraints: the merged rows' sets go up before the first decode graph (a prefixed batch runs masked even when
+    // nobody made a set: every row reads set 0)
+    if (m.mask) upload_sets(e, L);
     // forced prefixes: the merged rows' lengths and tokens (the padding rows and the rows of jobs without a prefix: length 0)
     if (m.prefix) {
         ensure_prefix_buffers(e);
-        upload_per_row(e, L, L.h_plen, &Job::prefix_len, 0, e->prefix_len);
-        const size_t ML = (size_t)e->cfg.max_len;
-        L.h_prefix.assign((size_t)L.np * ML, 0);
-        int r0 = 0;
-        for (const Job& j : L.jobs) {
-            for (size_t i = 0; i < j.prefix_len.size(); ++i)
-                std::copy_n(j.prefix.begin() + i * j.prefix_ld, j.prefix_len[i], L.h_prefix.begin() + (r0 + i) * ML);
-            r0 += j.n;
-        }
-        HIPCHECK(hipMemcpyAsync(e->prefix, L.h_prefix.data(), L.h_prefix.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        upload_rows(e, L, L.h_plen, 0, e->prefix_len, whole(&Job::prefix_len));
+        const size_t ML = (size_t)e->cfg.max_len;       // a job's [n][prefix_ld] rows, packed, become [np][max_len] ones
+        upload_rows(e, L, L.h_prefix, 0, e->prefix, [ML](const Job& j, int* dst) {
+            for (size_t i = 0; i < j.prefix_len.size(); ++i) std::copy_n(j.prefix.begin() + i * j.prefix_ld, j.prefix_len[i], dst + i * ML);
+        }, ML);
     }
-    // no-repeat n-grams: the per-row masks start as the rows' sets
+    // no-repeat n-grams: the per-row masks start as the rows' sets (m.ngram implies m.mask: the table and the sets are up)
     if (m.ngram) {
-        ensure_tok_table(e);
         ensure_ngram_buffers(e);
-        upload_per_row(e, L, L.h_ngram, &Job::ngram, 0, e->ngram_of_row);
+        upload_rows(e, L, L.h_ngram, 0, e->ngram_of_row, whole(&Job::ngram));
         if (!m.automaton) launch_ngram_init(e, e->row_mask, e->tok_table, e->set_of_row, e->ngram_of_row, L.np);
     }
     // token automata: the rows' start states (the padding rows and the rows without an automaton: -1), their first masks
@@ -2641,13 +2666,7 @@ void start_batch(mocr_engine* e, Lane& L) {
     // words, the start token alone
     if (m.penalty) {
         ensure_penalty_buffers(e);
-        L.h_penalty.assign((size_t)L.np, 1.f);
-        int r0 = 0;
-        for (const Job& j : L.jobs) {
-            std::copy(j.penalty.begin(), j.penalty.end(), L.h_penalty.begin() + r0);
-            r0 += j.n;
-        }
-        HIPCHECK(hipMemcpyAsync(e->penalty_of_row, L.h_penalty.data(), (size_t)L.np * sizeof(float), hipMemcpyHostToDevice, e->stream));
+        upload_rows(e, L, L.h_penalty, 1.f, e->penalty_of_row, whole(&Job::penalty));
         launch_penalty_init(e, e->seen_mask, L.np);
     }
     // token positions: position 0, the pad tail and the rows of the jobs that did not ask read 0
@@ -2658,15 +2677,13 @@ void start_batch(mocr_engine* e, Lane& L) {
     // The decode steps run on np >= n rows (graph_rows): the padding rows are born finished, emit pad_id and read
     // whatever the workspace holds for them (finite values; no kernel mixes rows).
     DecState st = make_state(e, L.max_len, nullptr, 0, nullptr, L.n);
-    dec_token<T, true>(e, st, 0, L.np);
+    dec_token<T, true>(e, st, m, 0, L.np);
     // beam search: the start token's kernel is the greedy one; the beam state starts as [0, -1e9, ...] and an empty finished set
     if (m.beam) {
         ensure_beam_buffers(e);
-        if (m.beam_tokens) {        // the crops' handles by row (c K + k: a beam job carries them expanded), padding rows under set 0
-            ensure_tok_table(e);
-            ensure_set_buffer(e);
+        if (m.beam_tokens) {
             ensure_beam_token_buffers(e);
-            upload_per_row(e, L, L.h_sets, &Job::sets, MOCR_TOKEN_SET_ALL, e->set_of_row);
+            upload_sets(e, L);
         }
         if (m.positions) ensure_beam_position_buffers(e);
         if (m.beam_automaton) {     // the crops' start states by row (c K + k, like the sets), padding rows without one
@@ -2682,6 +2699,18 @@ void start_batch(mocr_engine* e, Lane& L) {
                            m.beam_cfg.num_beams, L.np, e->cfg.max_len, e->cfg.pad_id);
         HIPCHECK(hipGetLastError());
     }
+}
+
+// The batch runs in the richest mode any of its jobs asked for (mode_of; soft token automata: if any row's automaton is soft)
+template <typename T>
+void start_batch(mocr_engine* e, Lane& L) {
+    L.mode = mode_of(L.jobs);
+    if (L.mode.automaton || L.mode.beam_automaton)
+        for (const Job& j : L.jobs)
+            for (int32_t h : j.automata) L.mode.soft = L.mode.soft || e->aut_soft[h] != 0;
+    stage_planes(e, L);
+    encode_batch<T>(e, L);
+    prepare_decode<T>(e, L);
     L.t = 0; L.steps = L.max_len - 1; L.chunk = 0;
     L.finishing = false;
     L.flag_pending[0] = L.flag_pending[1] = false;
@@ -2707,39 +2736,32 @@ void finish_batch(mocr_engine* e, Lane& L) {
     if (L.mode.positions) {      // token positions: the deferred pass over the rows the steps recorded, before the outputs leave
         if (e->cfg.dtype == MOCR_BF16) run_positions<bf16_t>(e, L); else run_positions<float>(e, L);
     }
-    if (L.mode.automaton) {      // token automata: the rows' states in their automata's own numbering
-        hipLaunchKernelGGL(automaton_state_out_kernel, dim3((L.n + 255) / 256), dim3(256), 0, e->stream, (const int*)e->aut_state,
-                           (const int*)e->aut_base_of_row, e->aut_state_out, L.n);
+    const bool beam = L.mode.beam;
+    // token automata: the rows' states in their automata's own numbering - a beam batch: the hypotheses' (an empty slot and a crop
+    // without an automaton: MOCR_STATE_NONE)
+    if (L.mode.automaton || L.mode.beam_automaton) {
+        hipLaunchKernelGGL(automaton_state_out_kernel, dim3((L.n + 255) / 256), dim3(256), 0, e->stream,
+                           (const int*)(L.mode.beam_automaton ? e->hyp_state : e->aut_state), (const int*)e->aut_base_of_row, e->aut_state_out, L.n);
         HIPCHECK(hipGetLastError());
     }
-    if (L.mode.beam_automaton) { // ... and the hypotheses' states (an empty slot and a crop without an automaton: MOCR_STATE_NONE)
-        hipLaunchKernelGGL(automaton_state_out_kernel, dim3((L.n + 255) / 256), dim3(256), 0, e->stream, (const int*)e->hyp_state,
-                           (const int*)e->aut_base_of_row, e->aut_state_out, L.n);
-        HIPCHECK(hipGetLastError());
-    }
-    int row0 = 0;
+    // where a job's rows are read from: the rows themselves, or - beam search - the crops' finished sets, [crops][K] = the job's rows
+    // (logp: a beam batch with a job that asks ran the token form; positions: it kept the trails and ran the deferred pass over them)
+    struct OutView { const int *ids, *len; const float* logp; };
+    const OutView from = beam ? OutView{e->hyp_ids, e->hyp_len, e->hyp_logp} : OutView{e->ids, e->len, e->scores};
+    const size_t ML = (size_t)e->cfg.max_len;
+    size_t row0 = 0;
     for (const Job& j : L.jobs) {
         const hipMemcpyKind kind = j.out_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-        if (j.beam.num_beams > 0) {      // beam search: the crops' finished sets, [crops][K] = the job's rows
-            HIPCHECK(hipMemcpyAsync(j.out_ids, e->hyp_ids + (size_t)row0 * e->cfg.max_len, (size_t)j.n * e->cfg.max_len * sizeof(int), kind, e->stream));
-            HIPCHECK(hipMemcpyAsync(j.out_len, e->hyp_len + row0, (size_t)j.n * sizeof(int), kind, e->stream));
-            HIPCHECK(hipMemcpyAsync(j.out_score, e->hyp_score + row0, (size_t)j.n * sizeof(float), kind, e->stream));
-            if (j.out_logp)         // (a batch with such a job ran the token form)
-                HIPCHECK(hipMemcpyAsync(j.out_logp, e->hyp_logp + (size_t)row0 * e->cfg.max_len, (size_t)j.n * e->cfg.max_len * sizeof(float), kind, e->stream));
-            copy_out_pos_state(e, L, j, row0);      // (positions: such a batch kept the trails and ran the deferred pass over its hypotheses)
-            row0 += j.n;
-            continue;
-        }
-        HIPCHECK(hipMemcpyAsync(j.out_ids, e->ids + (size_t)row0 * e->cfg.max_len, (size_t)j.n * e->cfg.max_len * sizeof(int), kind, e->stream));
-        HIPCHECK(hipMemcpyAsync(j.out_len, e->len + row0, (size_t)j.n * sizeof(int), kind, e->stream));
-        if (j.out_logp)
-            HIPCHECK(hipMemcpyAsync(j.out_logp, e->scores + (size_t)row0 * e->cfg.max_len, (size_t)j.n * e->cfg.max_len * sizeof(float), kind, e->stream));
-        if (j.out_alt_ids) {
-            const size_t ld = (size_t)e->cfg.max_len * MOCR_ALTERNATIVES;
+        HIPCHECK(hipMemcpyAsync(j.out_ids, from.ids + row0 * ML, j.n * ML * sizeof(int), kind, e->stream));
+        HIPCHECK(hipMemcpyAsync(j.out_len, from.len + row0, (size_t)j.n * sizeof(int), kind, e->stream));
+        if (beam) HIPCHECK(hipMemcpyAsync(j.out_score, e->hyp_score + row0, (size_t)j.n * sizeof(float), kind, e->stream));
+        if (j.out_logp) HIPCHECK(hipMemcpyAsync(j.out_logp, from.logp + row0 * ML, j.n * ML * sizeof(float), kind, e->stream));
+        if (!beam && j.out_alt_ids) {
+            const size_t ld = ML * MOCR_ALTERNATIVES;
             HIPCHECK(hipMemcpyAsync(j.out_alt_ids, e->alt_ids + row0 * ld, j.n * ld * sizeof(int), kind, e->stream));
             HIPCHECK(hipMemcpyAsync(j.out_alt_logp, e->alt_logp + row0 * ld, j.n * ld * sizeof(float), kind, e->stream));
         }
-        copy_out_pos_state(e, L, j, row0);
+        copy_out_pos_state(e, L, j, (int)row0);
         row0 += j.n;
     }
     L.jobs.clear();
@@ -2757,7 +2779,7 @@ template <typename T>
 void compact_rows(mocr_engine* e, Lane& L, int unfinished) {
     if (e->cfg.flags & MOCR_FLAG_NO_COMPACTION) return;
     // (batches of the one-launch-per-projection path - <= 32 rows - stay as they are: their steps are launch-bound)
-    if (e->use_smallm(L.np0)) return;
+    if (!L.mode.beam && e->use_smallm(L.np0)) return;
     const int want = graph_rows(std::max(unfinished, 1), e->cfg.max_batch);
     if (want >= L.np || (long long)want * 8 > (long long)L.np * 7) return;
     ProfScope ps(e, "compact_rows", 0, (double)want * e->D * (4 + sizeof(T)) * 4);
@@ -2875,18 +2897,12 @@ bool pump_once(mocr_engine* e) {
             L.np = L.np0 = graph_rows(L.n, e->cfg.max_batch);
             L.active = true;
             e->bind((int)i);
-            e->regime = L.np0;
-            e->beam_batch = L.jobs.front().beam.num_beams > 0;
-            start_batch<T>(e, L);
-            e->regime = 0; e->beam_batch = false;
+            { RegimeScope rs(e, L.np0); start_batch<T>(e, L); }
             e->unbind((int)i);
         }
         if (L.active) {
             e->bind((int)i);
-            e->regime = L.np0;
-            e->beam_batch = L.mode.beam; e->automaton_batch = L.mode.automaton; e->soft_batch = L.mode.soft; e->penalty_batch = L.mode.penalty;
-            advance<T>(e, L);
-            e->regime = 0; e->beam_batch = false; e->automaton_batch = false; e->soft_batch = false; e->penalty_batch = false;
+            { RegimeScope rs(e, L.np0); advance<T>(e, L); }
             e->unbind((int)i);
             any = true;
         }
@@ -2899,8 +2915,7 @@ void drive(mocr_engine* e) {
     try {
         if (e->cfg.dtype == MOCR_BF16) { while (pump_once<bf16_t>(e)) {} }
         else { while (pump_once<float>(e)) {} }
-    } catch (...) {
-        e->regime = 0; e->beam_batch = false; e->automaton_batch = false; e->soft_batch = false; e->penalty_batch = false;
+    } catch (...) {      // (the batch's mode lives in its lane and its regime in a RegimeScope: nothing of either to restore here)
         e->pending.clear();
         for (auto& L : e->lanes) { L.active = false; L.jobs.clear(); (void)hipStreamSynchronize(L.ctx.stream); }
         throw;
@@ -3270,6 +3285,20 @@ template <typename F> int guarded(mocr_engine* e, F&& f) {
         set_error(e, x.what());
         return MOCR_ERR_STATE;
     }
+}
+
+// The frame of an operator hook: under the engine's lock and on its device, with every submitted job run to completion, f runs
+// on lane 0's buffers and stream, and the stream is waited for.  (A hook that checks arguments BEFORE the jobs are driven keeps
+// its own frame: with jobs pending the order shows.)
+template <typename F> int op_hook(mocr_engine* e, F&& f) {
+    return guarded(e, [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        drive(e);
+        e->bind(0);
+        f();
+        HIPCHECK(hipStreamSynchronize(e->stream));
+    });
 }
 
 void require_ready(mocr_engine* e, int n, bool bounded = true) {
@@ -4690,71 +4719,46 @@ int mocr_decode_logits(mocr_engine* e, const void* d_gray, int32_t n, const int3
 
 int mocr_op_gemm(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, void* d_out, const float* d_resid,
                  int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t tile, int32_t split_k) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (epilogue == EPI_PATCH || epilogue == EPI_ARGMAX || epilogue == EPI_ARGMAX_LSE || epilogue == EPI_TOPK)
             throw ArgError{"EPI_PATCH / EPI_ARGMAX are not exposed through mocr_op_gemm (EPI_ARGMAX: mocr_op_gemm_argmax)", MOCR_ERR_ARG};
         GemmCall c = gemm_call("op_gemm", dA, K, dW, d_bias, d_out, N, M, N, K, epilogue, tile);
         c.resid = d_resid; c.split = split_k; c.slab_stride = (long long)M * N;
         if (e->cfg.dtype == MOCR_BF16) gemm<bf16_t>(e, c); else gemm<float>(e, c);
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 int mocr_op_gemm_ln(mocr_engine* e, const void* dA, const void* dW, const float* d_bias, void* d_out, const float* d_resid,
                     int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t tile, float* d_part, const float* d_csum, void* d_xb) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (e->cfg.dtype != MOCR_BF16) throw ArgError{"mocr_op_gemm_ln: bf16 engines only", MOCR_ERR_UNSUPPORTED};
         LnFold f{d_part, d_csum, d_xb};
         GemmCall c = gemm_call("op_gemm_ln", dA, K, dW, d_bias, d_out, N, M, N, K, epilogue, tile);
         c.resid = d_resid; c.lnf = &f;
         gemm<bf16_t>(e, c);
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 int mocr_op_ln_prep(mocr_engine* e, const float* d_x, void* d_xb, float* d_part, int32_t M) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (e->D != 768) throw ArgError{"mocr_op_ln_prep: hidden size 768 only", MOCR_ERR_UNSUPPORTED};
         hipLaunchKernelGGL((ln_prep_kernel<768>), dim3((M + 3) / 4), dim3(256), 0, e->stream, d_x, reinterpret_cast<bf16_t*>(d_xb), d_part, M);
         HIPCHECK(hipGetLastError());
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 int mocr_op_layernorm(mocr_engine* e, const float* d_x, const float* d_gamma, const float* d_beta, void* d_out, int32_t M) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         dispatch(e, [&](auto tag) { layernorm<decltype(tag)>(e, d_x, d_gamma, d_beta, d_out, M); });
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 int mocr_op_enc_attention(mocr_engine* e, const void* d_qkv, void* d_ctx, int32_t n, int32_t impl) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         dispatch(e, [&](auto tag) {
             using T_ = decltype(tag);
             enc_attention<T_>(e, d_qkv, d_ctx, n, impl, enc_attn_ysplit<T_>(e, n, impl));
         });
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
@@ -4775,11 +4779,7 @@ int mocr_op_embed(mocr_engine* e, const void* d_gray, int32_t n, int32_t tile, v
 
 int mocr_op_layernorm_slab(mocr_engine* e, float* d_x, const float* d_slabs, int32_t nslab, int64_t slab_stride, const float* d_bias,
                            const float* d_gamma, const float* d_beta, void* d_out, int32_t M) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (e->D != 768) throw ArgError{"mocr_op_layernorm_slab: hidden size 768 only", MOCR_ERR_UNSUPPORTED};
         if (!d_x || !d_slabs || !d_bias || !d_gamma || !d_beta || !d_out || nslab < 1 || M < 1 || slab_stride < (int64_t)M * e->D ||
             (slab_stride & 3))
@@ -4787,7 +4787,6 @@ int mocr_op_layernorm_slab(mocr_engine* e, float* d_x, const float* d_slabs, int
         dispatch(e, [&](auto tag) {
             layernorm_slab<decltype(tag)>(e, d_x, d_slabs, nslab, (long long)slab_stride, d_bias, d_gamma, d_beta, d_out, M);
         });
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
@@ -4834,11 +4833,7 @@ int mocr_decode_plan(mocr_engine* e, int32_t rows, int32_t regime_rows, int32_t 
 }
 
 int mocr_op_gemm_args(mocr_engine* e, const mocr_gemm_args* a) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (!a || a->struct_size != (int32_t)sizeof(mocr_gemm_args)) throw ArgError{"mocr_op_gemm_args: bad struct_size", MOCR_ERR_ARG};
         const int epi = a->epilogue;
         if (epi == EPI_PATCH || epi == EPI_ARGMAX || epi == EPI_ARGMAX_LSE || epi == EPI_TOPK)
@@ -4859,7 +4854,6 @@ int mocr_op_gemm_args(mocr_engine* e, const mocr_gemm_args* a) {
         GemmCall c = gemm_call("op_gemm", a->A, lda, a->W, a->bias, a->out, ldo, a->M, a->N, a->K, epi, a->tile);
         c.resid = a->resid; c.split = a->split_k; c.slab_stride = slab_stride; c.group_n = a->group_n;
         if (e->cfg.dtype == MOCR_BF16) gemm<bf16_t>(e, c); else gemm<float>(e, c);
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
@@ -4872,11 +4866,7 @@ int mocr_last_tile_launch(mocr_engine* e, int32_t out[4]) {
 }
 
 int mocr_op_gemm_pers(mocr_engine* e, const mocr_gemm_pers_args* a) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (!a || a->struct_size != (int32_t)sizeof(mocr_gemm_pers_args)) throw ArgError{"mocr_op_gemm_pers: bad struct_size", MOCR_ERR_ARG};
         if (e->cfg.dtype != MOCR_BF16) throw ArgError{"mocr_op_gemm_pers: bf16 engines only", MOCR_ERR_UNSUPPORTED};
         const int epi = a->epilogue;
@@ -4892,7 +4882,6 @@ int mocr_op_gemm_pers(mocr_engine* e, const mocr_gemm_pers_args* a) {
         c.resid = a->resid; c.group_n = a->group_n;
         if (a->ln_part) c.lnf = &f;
         gemm<bf16_t>(e, c);
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
@@ -4938,27 +4927,18 @@ int mocr_op_latent_attention(mocr_engine* e, const void* d_qt, const void* d_x, 
 }
 
 int mocr_op_quant_fp8(mocr_engine* e, const void* d_x, void* d_x8, int64_t n_elems, float inv_sx) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (!d_x || !d_x8 || n_elems < 16 || n_elems % 16) throw ArgError{"bad argument (n_elems must be a positive multiple of 16)", MOCR_ERR_ARG};
         const long long n16 = n_elems / 16;
         hipLaunchKernelGGL(quant_rows_fp8_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, e->stream,
                            reinterpret_cast<const bf16_t*>(d_x), reinterpret_cast<uint8_t*>(d_x8), n16, inv_sx);
         HIPCHECK(hipGetLastError());
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 int mocr_op_latent_attention_fp8(mocr_engine* e, const void* d_qt, const void* d_x8, void* d_out, int32_t n, int32_t len,
                                  int64_t x_batch_stride_bytes, float sx) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (e->cfg.dtype != MOCR_BF16 || !d_qt || !d_x8 || !d_out || n < 1 || len < 1 || !(sx > 0.f)) throw ArgError{"bad argument", MOCR_ERR_ARG};
         Latent8Params p{};
         p.qt = reinterpret_cast<const bf16_t*>(d_qt); p.x8 = reinterpret_cast<const uint8_t*>(d_x8);
@@ -4966,34 +4946,24 @@ int mocr_op_latent_attention_fp8(mocr_engine* e, const void* d_qt, const void* d
         p.rows = n; p.sx = sx;
         ProfScope ps(e, "op_latent8", 0, (double)n * len * 768);
         launch_latent8(e, false, p);
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 int mocr_op_qqt(mocr_engine* e, const void* d_x, const void* d_wq, const float* d_bq, const void* d_wkT, void* d_qt, int32_t n) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (e->cfg.dtype != MOCR_BF16 || !d_x || !d_wq || !d_bq || !d_wkT || !d_qt || n < 1) throw ArgError{"bad argument", MOCR_ERR_ARG};
         QqtParams q{};
         q.x = reinterpret_cast<const bf16_t*>(d_x); q.wq = reinterpret_cast<const bf16_t*>(d_wq); q.bq = d_bq;
         q.wkT = reinterpret_cast<const bf16_t*>(d_wkT); q.qt = reinterpret_cast<bf16_t*>(d_qt);
         ProfScope ps(e, "op_qqt", 4.0 * n * 768 * 768, 0);
         launch_qqt(e, q, n, n);
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 int mocr_op_dec_attn(mocr_engine* e, int32_t self, const float* d_slabs, int32_t nslab, const float* d_bias, void* d_k, void* d_v,
                      int32_t layer, const int32_t* d_step, const int32_t* d_rowmap, void* d_ctx, int32_t n, int32_t approx_len,
                      int32_t nt) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (!e->committed || !d_slabs || !d_bias || !d_k || !d_ctx || n < 1 || nslab < 1 || nt < -1 || nt > 1 || e->D != 768 ||
             (self && (!d_v || !d_step || approx_len < 1 || approx_len > e->cfg.max_len)) ||
             (!self && (layer < 0 || layer >= e->cfg.dec_layers)))
@@ -5010,18 +4980,13 @@ int mocr_op_dec_attn(mocr_engine* e, int32_t self, const float* d_slabs, int32_t
                 launch_dec_attn<T_, false>(e, p, n, e->S);
             }
         });
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 int mocr_op_dec_add_ln(mocr_engine* e, const float* d_slabs, int32_t nslab, const float* d_bias, const float* d_resid,
                        const float* d_gamma, const float* d_beta, int32_t gelu, float* d_out_f32, void* d_out_t, int32_t rows,
                        void* d_cache, int32_t cache_fp8, float inv_sx, const int32_t* d_step, const int32_t* d_rowmap) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (!e->committed || !d_slabs || !d_bias || !d_gamma || !d_beta || !d_out_t || rows < 1 || nslab < 1 || e->D != 768 ||
             (d_cache && !d_step))
             throw ArgError{"mocr_op_dec_add_ln: bad argument", MOCR_ERR_ARG};
@@ -5034,21 +4999,15 @@ int mocr_op_dec_add_ln(mocr_engine* e, const float* d_slabs, int32_t nslab, cons
         if (d_cache && cache_fp8) { a.cache8 = reinterpret_cast<uint8_t*>(d_cache); a.inv8 = inv_sx; }
         else a.cache = d_cache;
         dispatch(e, [&](auto tag) { launch_dec_add_ln<decltype(tag)>(e, a); });
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 int mocr_op_dec_bias_gelu(mocr_engine* e, const float* d_slabs, int32_t nslab, const float* d_bias, void* d_out, int32_t rows,
                           int32_t N) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (!d_slabs || !d_bias || !d_out || rows < 1 || nslab < 1 || N < 4 || N % 4)
             throw ArgError{"mocr_op_dec_bias_gelu: bad argument", MOCR_ERR_ARG};
         dispatch(e, [&](auto tag) { launch_dec_bias_gelu<decltype(tag)>(e, d_slabs, nslab, (long long)rows * N, d_bias, d_out, rows, N); });
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
@@ -5059,11 +5018,7 @@ int mocr_op_attn_positions(mocr_engine* e, const void* d_q, const void* d_k, con
 
 int mocr_op_attn_positions_gathered(mocr_engine* e, const void* d_q, const void* d_k, const int32_t* d_len, int32_t rows, int32_t T,
                                     float* d_out_pos, float* d_out_map, const uint8_t* d_trail, int32_t trail_ld, int32_t K) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (!e->committed || !d_q || !d_k || !d_len || !d_out_pos || rows < 1 || T < 1)
             throw ArgError{"mocr_op_attn_positions: bad argument", MOCR_ERR_ARG};
         // positions at and behind d_len read 0: the kernel writes the computed ones only
@@ -5077,18 +5032,13 @@ int mocr_op_attn_positions_gathered(mocr_engine* e, const void* d_q, const void*
         p.out_map = d_out_map;
         if (d_trail) { p.trail = d_trail; p.trail_ld = trail_ld; p.K = K; }      // (launch_attn_positions checks the three)
         if (e->cfg.dtype == MOCR_BF16) launch_attn_positions<bf16_t>(e, p, rows); else launch_attn_positions<float>(e, p, rows);
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 // The expansion of shared encodings as start_batch runs it, on the caller's buffer: its first n_src rows are staged in the
 // lane's CTX, then row r of it becomes staged row d_src_of_row[r].
 int mocr_op_enc_expand(mocr_engine* e, void* d_enc, const int32_t* d_src_of_row, int32_t n_src, int32_t n_rows) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         const size_t row_bytes = (size_t)e->S * e->D * e->esz;
         if (!d_enc || !d_src_of_row || n_src < 1 || n_rows < 1 || n_src > e->cfg.max_batch || n_rows > e->cfg.max_batch ||
             (size_t)n_src * row_bytes > e->ctx_cap)
@@ -5099,21 +5049,15 @@ int mocr_op_enc_expand(mocr_engine* e, void* d_enc, const int32_t* d_src_of_row,
             if (v < 0 || v >= n_src) throw ArgError{"mocr_op_enc_expand: source index outside [0, n_src)", MOCR_ERR_ARG};
         HIPCHECK(hipMemcpyAsync(e->CTX, d_enc, (size_t)n_src * row_bytes, hipMemcpyDeviceToDevice, e->stream));
         launch_enc_expand(e, e->CTX, d_enc, d_src_of_row, n_src, n_rows);
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 int mocr_op_ngram_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
                        const int32_t* d_ngram_of_row, int32_t rows) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (!e->committed || !d_row_mask || !d_base_mask || !d_base_set_of_row || !d_ngram_of_row || rows < 1 || e->V % 32)
             throw ArgError{"mocr_op_ngram_init: bad argument", MOCR_ERR_ARG};
         launch_ngram_init(e, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows);
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
@@ -5129,7 +5073,7 @@ struct TokenOp {
 
 // The token kernel on the caller's buffers: the mocr_op_dec_token* symbols are this with some of the groups left out.
 static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const TokenOp& o = {}) {
-    return guarded(e, [&] {
+    return op_hook(e, [&] {
         const auto [d_cand_sum, d_scores] = o.scored;
         const auto [d_top_val, d_top_idx, d_alt_ids, d_alt_logp] = o.alts;
         const auto [d_tok_mask, d_set_of_row] = o.sets;
@@ -5141,10 +5085,6 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const TokenOp&
         const auto d_aut_state = o.aut.state;
         const auto d_edge_weight = o.aut.edge_weight, d_penalty_of_row = o.aut.pen.penalty_of_row;
         const auto d_seen_mask = o.aut.pen.seen_mask;
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
         if (!a || a->struct_size != (int32_t)sizeof(mocr_token_args)) throw ArgError{"mocr_op_dec_token: bad struct_size", MOCR_ERR_ARG};
         const bool first = a->first != 0;
         if (!e->committed || a->n < 1 || !a->ids || !a->step || !a->finished || !a->len || !a->n_unfinished || !a->rowmap ||
@@ -5195,7 +5135,6 @@ static int op_dec_token(mocr_engine* e, const mocr_token_args* a, const TokenOp&
             if (first) launch_dec_token<T_, true>(e, st, t, a->n);
             else launch_dec_token<T_, false>(e, st, t, a->n);
         });
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
@@ -5258,21 +5197,24 @@ int mocr_op_dec_token_penalty(mocr_engine* e, const mocr_token_args* a, const fl
 }
 
 int mocr_op_penalty_init(mocr_engine* e, uint32_t* d_seen_mask, int32_t rows) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (!e->committed || !d_seen_mask || rows < 1 || e->V % 32) throw ArgError{"mocr_op_penalty_init: bad argument", MOCR_ERR_ARG};
         launch_penalty_init(e, d_seen_mask, rows);
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 static int op_automaton_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
                              const int32_t* d_ngram_of_row, int32_t rows, const int32_t* d_edge_begin, const int32_t* d_edge_token,
                              const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state,
-                             const int32_t* d_default_next);
+                             const int32_t* d_default_next) {
+    return op_hook(e, [&] {
+        if (!e->committed || !d_row_mask || !d_base_mask || !d_base_set_of_row || !d_ngram_of_row || rows < 1 || e->V != 6144 ||
+            !d_edge_begin || !d_edge_token || !d_accepting || !d_aut_base_of_row || !d_aut_state)
+            throw ArgError{"mocr_op_automaton_init: bad argument", MOCR_ERR_ARG};
+        launch_automaton_init(e, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows, d_edge_begin, d_edge_token, d_accepting,
+                              d_aut_base_of_row, d_aut_state, d_default_next);
+    });
+}
 
 int mocr_op_automaton_init_soft(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
                                 const int32_t* d_ngram_of_row, int32_t rows, const int32_t* d_edge_begin, const int32_t* d_edge_token,
@@ -5287,24 +5229,6 @@ int mocr_op_automaton_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t*
                            const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state) {
     return op_automaton_init(e, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows, d_edge_begin, d_edge_token, d_accepting,
                              d_aut_base_of_row, d_aut_state, nullptr);
-}
-
-static int op_automaton_init(mocr_engine* e, uint32_t* d_row_mask, const uint32_t* d_base_mask, const int32_t* d_base_set_of_row,
-                             const int32_t* d_ngram_of_row, int32_t rows, const int32_t* d_edge_begin, const int32_t* d_edge_token,
-                             const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state,
-                             const int32_t* d_default_next) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
-        if (!e->committed || !d_row_mask || !d_base_mask || !d_base_set_of_row || !d_ngram_of_row || rows < 1 || e->V != 6144 ||
-            !d_edge_begin || !d_edge_token || !d_accepting || !d_aut_base_of_row || !d_aut_state)
-            throw ArgError{"mocr_op_automaton_init: bad argument", MOCR_ERR_ARG};
-        launch_automaton_init(e, d_row_mask, d_base_mask, d_base_set_of_row, d_ngram_of_row, rows, d_edge_begin, d_edge_token, d_accepting,
-                              d_aut_base_of_row, d_aut_state, d_default_next);
-        HIPCHECK(hipStreamSynchronize(e->stream));
-    });
 }
 
 int mocr_op_dec_token_masked(mocr_engine* e, const mocr_token_args* a, const float* d_cand_sum, float* d_scores,
@@ -5332,11 +5256,7 @@ static int op_lm_head(mocr_engine* e, const void* dA, const void* dW, const floa
     int32_t* const d_top_idx = lm.top_idx;
     const uint32_t* const d_tok_mask = lm.mask.table;
     const int32_t* const d_set_of_row = lm.mask.set_of_row;
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (!e->committed || !dA || !dW || !d_bias || !d_cand_val || !d_cand_idx || M < 1 || K < 1 || (tile != 64 && tile != 128))
             throw ArgError{"mocr_op_gemm_argmax: bad argument", MOCR_ERR_ARG};
         if ((d_top_val == nullptr) != (d_top_idx == nullptr) || (d_top_val && !d_cand_sum))
@@ -5361,7 +5281,6 @@ static int op_lm_head(mocr_engine* e, const void* dA, const void* dW, const floa
         GemmCall c = gemm_call(name, dA, K, dW, d_bias, d_cand_val, N, M, N, K, m.epilogue(), tile);
         c.lm = &lm;
         dispatch(e, [&](auto tag) { gemm<decltype(tag)>(e, c); });
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
@@ -5432,11 +5351,7 @@ int mocr_op_gemm_argmax(mocr_engine* e, const void* dA, const void* dW, const fl
 }
 
 int mocr_op_smallm_gemm(mocr_engine* e, const mocr_smallm_args* a) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (!a || a->struct_size != (int32_t)sizeof(mocr_smallm_args)) throw ArgError{"mocr_op_smallm_gemm: bad struct_size", MOCR_ERR_ARG};
         if (!e->committed || e->cfg.dtype != MOCR_BF16 || !a->w || !a->out || a->rows < 1 || a->N < 1 || a->ldo < a->N ||
             (a->pro == SM_PRO_PLAIN && !a->a_bf16) || (a->pro == SM_PRO_LN && (!a->a_f32 || !a->ln_g || !a->ln_b)) ||
@@ -5451,16 +5366,11 @@ int mocr_op_smallm_gemm(mocr_engine* e, const mocr_smallm_args* a) {
         if (!smallm_pair_exists(a->pro, a->epi))
             throw ArgError{"mocr_op_smallm_gemm: (pro, epi) is not a pair the small-batch decode step launches", MOCR_ERR_UNSUPPORTED};
         smallm_gemm(e, "op_smallm", a->pro, a->epi, p);
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 int mocr_op_latent_block(mocr_engine* e, const mocr_latent_args* a) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (!a || a->struct_size != (int32_t)sizeof(mocr_latent_args)) throw ArgError{"mocr_op_latent_block: bad struct_size", MOCR_ERR_ARG};
         if (!e->committed || e->cfg.dtype != MOCR_BF16 || e->D != 768 || e->H != 12 || a->n < 1 || a->regime_rows < 0 ||
             !a->x_in || !a->wq || !a->bq || !a->wkT || !a->wv || !a->bv || !a->keys || !a->q || !a->qt || !a->et || !a->ctx ||
@@ -5475,7 +5385,6 @@ int mocr_op_latent_block(mocr_engine* e, const mocr_latent_args* a) {
         // the choices are made by the batch's regime, as in the decode step (which sets it around a batch's steps)
         RegimeScope rs(e, a->regime_rows);
         launch_latent_block(e, b);
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
@@ -5552,11 +5461,7 @@ int mocr_op_beam_select_soft(mocr_engine* e, const mocr_token_args* a, const moc
                              uint8_t* d_hyp_trail, const int32_t* d_edge_begin, const int32_t* d_edge_token, const int32_t* d_edge_next,
                              const uint8_t* d_accepting, const int32_t* d_aut_base_of_row, int32_t* d_aut_state, int32_t* d_hyp_state,
                              const float* d_edge_weight, const int32_t* d_default_next) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (!a || a->struct_size != (int32_t)sizeof(mocr_token_args)) throw ArgError{"mocr_op_beam_select: bad struct_size", MOCR_ERR_ARG};
         if (!e->committed || !beam || beam->num_beams < 2 || beam->num_beams > MOCR_MAX_BEAMS || beam->early_stopping < 0 ||
             beam->early_stopping > 2 || beam->no_repeat_ngram_size < 0 || a->first || a->forced || a->ncand > 0 || a->n < 1 || !a->slabs ||
@@ -5593,53 +5498,32 @@ int mocr_op_beam_select_soft(mocr_engine* e, const mocr_token_args* a, const moc
         static_cast<BeamAutomata&>(aut) = BeamAutomata{d_edge_begin, d_edge_token, d_edge_next, d_accepting, d_aut_base_of_row, d_aut_state, d_hyp_state};
         aut.edge_weight = d_edge_weight; aut.default_next = d_default_next;
         dispatch(e, [&](auto tag) { launch_beam_select<decltype(tag)>(e, st, bs, t, a->n, beam->num_beams, aut); });
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 int mocr_op_beam_permute(mocr_engine* e, void* d_cache, int32_t layers, int64_t layer_stride, int64_t row_stride, int32_t segs,
                          int64_t seg_stride, int32_t pos_bytes, int32_t K, const int32_t* d_parent, const int32_t* d_rowmap,
                          const int32_t* d_finished, const int32_t* d_step, int32_t n_slots, int32_t max_pos) {
-    return guarded(e, [&] {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        drive(e);
-        e->bind(0);
+    return op_hook(e, [&] {
         if (!d_cache || !d_parent || !d_rowmap || !d_finished || !d_step || n_slots < 1 || K < 2 || K > MOCR_MAX_BEAMS || layer_stride < 0 ||
             row_stride < 16 || seg_stride < 0 || layer_stride % 16 || row_stride % 16 || seg_stride % 16 ||
             (reinterpret_cast<uintptr_t>(d_cache) & 15))
             throw ArgError{"mocr_op_beam_permute: bad argument", MOCR_ERR_ARG};
         BeamPermuteView v{reinterpret_cast<char*>(d_cache), layer_stride, row_stride, seg_stride, segs, pos_bytes};
         launch_beam_permute(e, v, layers, K, d_parent, d_rowmap, d_finished, d_step, n_slots, max_pos);
-        HIPCHECK(hipStreamSynchronize(e->stream));
     });
 }
 
 int64_t mocr_beam_state_bytes(mocr_engine* e) {
-    if (!e) return -1;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int64_t bytes = 0;
-    for (const Lane& L : e->lanes)
-        if (L.ctx.hyp_ids) bytes += (int64_t)e->Bp * (5 + e->cfg.max_len) * 4;      // five [Bp] arrays and hyp_ids [Bp][max_len]
-    return bytes;
+    return beam_group_bytes(e, [](const LaneCtx& c) { return c.hyp_ids != nullptr; }, beam_state_arrays);
 }
 
 int64_t mocr_beam_token_state_bytes(mocr_engine* e) {
-    if (!e) return -1;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int64_t bytes = 0;
-    for (const Lane& L : e->lanes)
-        if (L.ctx.hyp_logp) bytes += (int64_t)e->Bp * e->cfg.max_len * 2 * 4;      // beam_logp and hyp_logp [Bp][max_len]
-    return bytes;
+    return beam_group_bytes(e, [](const LaneCtx& c) { return c.hyp_logp != nullptr; }, beam_token_arrays);
 }
 
 int64_t mocr_beam_position_state_bytes(mocr_engine* e) {
-    if (!e) return -1;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int64_t bytes = 0;
-    for (const Lane& L : e->lanes)
-        if (L.ctx.hyp_trail) bytes += (int64_t)e->Bp * e->cfg.max_len * 2;      // beam_trail and hyp_trail [Bp][max_len], a byte each
-    return bytes;
+    return beam_group_bytes(e, [](const LaneCtx& c) { return c.hyp_trail != nullptr; }, beam_position_arrays);
 }
 
 int mocr_lane_rowmap(mocr_engine* e, int32_t lane, int32_t* out_rowmap, int32_t n) {
